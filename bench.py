@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark harness: DQMC sweeps/sec for the BASELINE.json headline workload.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 Starts by itself for any N: the parent never touches a GPU, it spawns `--workers` worker processes per GPU
 (`--device i`, default ONE), each holding `--batch` independent Markov chains spread over `--sub-batches` kernel contexts
@@ -24,6 +24,10 @@ The ONE JSON line carries, besides the contract's keys:
                              against its BINDING roof (HBM or fp64 MFMA, whichever fraction is larger)
   roofline_other_kernels, roofline_whole_step
   cpu_baseline, cpu_baseline_all_cores   the real reference binary (oracle/_ref) on this host, N = 1 only
+
+--dump-outputs DIR writes, after the timed steps, what the timed path computed in its last step as DIR/<name>.npy (see
+dump_outputs): the state of a fixed sample of the chains of the first worker.  The inputs are seeded, so two builds run with
+the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -260,12 +264,59 @@ class _FakeBatch:
     def __init__(self, B, device=0):
         self.B, self.device, self.timed = B, device, False
 
+    def chain(self, b):
+        """a tiny stand-in for the state of chain b (--dump-outputs)"""
+        import types
+        import numpy as np
+        info = types.SimpleNamespace(n_g=8, lastAccRatioLocal_phi=0.5, r=-1.0)
+        return types.SimpleNamespace(info=info, phi=np.full((3, 4, 2), float(b)), g=np.eye(8) * (1.0 + 1.0j * b))
+
     def sweepThermalization(self):
         time.sleep(0.01)
         # rehearsal of a worker that dies mid-run (tests/test_bench_cpu.py): DQMC_BENCH_FAKE_DIE = "<device>:<exit code>"
         die = os.environ.get("DQMC_BENCH_FAKE_DIE")
         if die and self.timed and int(die.split(":")[0]) == self.device:
             os._exit(int(die.split(":")[1]))
+
+
+DUMP_MAX_BYTES = 64 << 20     # --dump-outputs: all files together
+DUMP_CHAINS = 8               # chains sampled for the per-chain arrays
+DUMP_SEED = 20240917          # fixed: the same chains and Green's-function rows in every run
+
+
+def dump_outputs(batch, directory, nchains):
+    """What a caller of the timed path receives after its last step, as float64 .npy files in `directory`:
+      acceptance, r       (B,)                 last local acceptance ratio and control parameter r of every chain
+      chains              (k,)                 the sampled chains: a fixed seeded sample of k <= DUMP_CHAINS
+      phi                 (k, m+1, N, OPDIM)   their bosonic fields
+      green_re, green_im  (k, rows, n_g)       their equal-time Green's functions: every row while the files stay under
+      green_rows          (rows,)              DUMP_MAX_BYTES in all, otherwise a fixed seeded sample of rows (listed here)
+    k is the largest count up to DUMP_CHAINS whose fields and one Green's-function row each fit the limit.  Returns {name: shape}."""
+    import numpy as np
+    B = nchains
+    out = {"acceptance": np.array([batch.chain(b).info.lastAccRatioLocal_phi for b in range(B)], dtype=np.float64),
+           "r": np.array([batch.chain(b).info.r for b in range(B)], dtype=np.float64)}
+    n = int(batch.chain(0).info.n_g)
+    phi_bytes = np.asarray(batch.chain(0).phi).size * 8
+    headers = 7 * 4096                                              # generous bound of the seven .npy headers
+    fixed = sum(v.nbytes for v in out.values()) + 8 * n + headers   # + green_rows at its largest
+    k = min(B, DUMP_CHAINS, (DUMP_MAX_BYTES - fixed) // (8 + phi_bytes + 16 * n))
+    if k < 1:
+        raise ValueError("--dump-outputs: one chain's field does not fit %d bytes" % DUMP_MAX_BYTES)
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.sort(rng.choice(B, size=k, replace=False))
+    out["chains"] = idx.astype(np.float64)
+    out["phi"] = np.stack([np.asarray(batch.chain(int(b)).phi, dtype=np.float64) for b in idx])
+    rows = min(n, (DUMP_MAX_BYTES - fixed - out["chains"].nbytes - out["phi"].nbytes) // (16 * n * k))
+    sel = np.arange(n) if rows == n else np.sort(rng.choice(n, size=rows, replace=False))
+    g = np.stack([np.asarray(batch.chain(int(b)).g)[sel, :] for b in idx])
+    out.update(green_re=np.ascontiguousarray(g.real, dtype=np.float64), green_im=np.ascontiguousarray(g.imag, dtype=np.float64),
+               green_rows=sel.astype(np.float64))
+    assert sum(v.nbytes for v in out.values()) + headers <= DUMP_MAX_BYTES
+    os.makedirs(directory, exist_ok=True)
+    for name, v in out.items():
+        np.save(os.path.join(directory, name + ".npy"), v)
+    return {name: list(v.shape) for name, v in out.items()}
 
 
 def worker(a, readline=None, emit=None):
@@ -325,7 +376,10 @@ def worker(a, readline=None, emit=None):
     #            `value` is measured in (the contexts overlap, so a family's time includes waiting for the other contexts' kernels)
     while True:
         cmd = readline().strip()
-        if cmd == "SOLO":
+        if cmd.startswith("DUMP "):
+            # the state the timed steps left: before any of the profiled steps below
+            emit("DUMPED " + json.dumps(dump_outputs(batch, cmd[len("DUMP "):], B)))
+        elif cmd == "SOLO":
             if FAKE:
                 emit("SOLO " + json.dumps({"dt_profiled": dt, "prof": None}))
                 break
@@ -577,12 +631,16 @@ def main():
     ap.add_argument("--exchange", action="store_true",
                     help="the chains of a worker are the replicas of one parallel-tempering ensemble (r ladder -1.4 ... -0.6): a replica-exchange "
                          "step after every sweep, inside the timed region (BASELINE configs 4 / 5: --batch 8)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (a fixed sample of the chains of the first worker) as DIR/<name>.npy")
     ap.add_argument("--inprocess", action="store_true",
                     help="ONE context in this process instead of worker processes (for rocprofv3)")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--device", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--simindex", type=int, default=0, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     select_config(a.config)
     if a.batch <= 0:
         a.batch = CONFIGS[a.config]["batch"]
@@ -688,6 +746,9 @@ def main():
     lead = rank == 0
     inproc_solo = None
     prof4 = None
+    if lead and a.dump_outputs:
+        send(procs[0][1], "DUMP " + os.path.abspath(a.dump_outputs))
+        read_tag(procs[0][1], "DUMPED")
     if lead and not a.inprocess and R == 1 and n_gpus == 1:
         # the timed regime once more with per-family event timing in every context (only when ONE worker drives the whole GPU)
         send(procs[0][1], "PROF4")

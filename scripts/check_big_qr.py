@@ -1,7 +1,7 @@
 """QR ("UDT") decomposition at sizes beyond the register-resident panel: n_g = 784, 1296, 2304 (O(3) L = 24, BASELINE
 config 5) and 4096.  M = Q diag(d) T with Q unitary; reconstruction and unitarity against numpy."""
 import sys, time
-sys.path.insert(0, '/root/repo')
+import os; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from detqmc_amd import KernelContext
 

@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -101,3 +103,105 @@ def test_bench_config_selects_the_other_baseline_workloads():
         r = _line(out)
         assert label in r["metric"] and r["config"]["replicas_per_gpu"] == chains and "workload" in r["config"]
         assert r["dtype"] == "f64" and r["vs_baseline"] is None
+
+
+def test_bench_dump_outputs_writes_the_last_step_as_npy(tmp_path):
+    """`--dump-outputs DIR`: after the timed steps the first worker writes the state of a fixed sample of its chains as float .npy
+    files (here the stand-in worker's tiny chains); the result line keeps `ms_per_step` and the requested number of steps."""
+    import numpy as np
+    d = tmp_path / "out"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "4", "--no-cpu-baseline",
+                          "--dump-outputs", str(d)], capture_output=True, text=True, timeout=120, env=_env())
+    assert out.returncode == 0, out.stderr
+    r = _line(out)
+    assert r["steps"] == 3 and r["ms_per_step"] > 0
+    names = sorted(os.listdir(d))
+    assert names == sorted(n + ".npy" for n in ("acceptance", "r", "chains", "phi", "green_re", "green_im", "green_rows"))
+    arrs = {n[:-4]: np.load(d / n) for n in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in arrs.values())
+    assert list(arrs["chains"]) == [0, 1, 2, 3] and arrs["phi"].shape == (4, 3, 4, 2) and arrs["green_re"].shape == (4, 8, 8)
+    assert np.array_equal(arrs["phi"][:, 0, 0, 0], arrs["chains"]) and np.array_equal(arrs["green_im"][:, 0, 0], arrs["chains"])
+
+
+def test_dump_outputs_stays_under_the_size_limit_with_a_fixed_sample(tmp_path, monkeypatch):
+    """a Green's function too large for the limit is sampled by rows; the sample (chains and rows) is the same in every run"""
+    import types
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    n, B = 64, 20
+
+    class Chain:
+        def __init__(self, b):
+            self.info = types.SimpleNamespace(n_g=n, lastAccRatioLocal_phi=0.1 * b, r=-1.0 - b)
+            self.phi = np.full((5, 16, 2), float(b))
+            self.g = np.arange(n * n).reshape(n, n) + 1j * b
+
+    batch = types.SimpleNamespace(chain=Chain)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 200_000)
+    shapes = bench.dump_outputs(batch, str(tmp_path / "a"), B)
+    bench.dump_outputs(batch, str(tmp_path / "b"), B)
+    k = bench.DUMP_CHAINS
+    rows = shapes["green_rows"][0]
+    assert shapes["phi"] == [k, 5, 16, 2] and shapes["acceptance"] == [B] and 0 < rows < n and shapes["green_re"] == [k, rows, n]
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= bench.DUMP_MAX_BYTES
+    for f in os.listdir(tmp_path / "a"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+    ch, sel = np.load(tmp_path / "a" / "chains.npy"), np.load(tmp_path / "a" / "green_rows.npy")
+    assert len(set(ch)) == k and np.all(np.diff(sel) > 0)
+    g_re = np.load(tmp_path / "a" / "green_re.npy")
+    assert np.array_equal(g_re[0], np.arange(n * n).reshape(n, n)[sel.astype(int), :])
+    assert np.array_equal(np.load(tmp_path / "a" / "green_im.npy")[:, 0, 0], ch)
+
+
+def test_bench_worker_runs_exactly_steps_timed_sweeps(tmp_path, monkeypatch):
+    """`--steps K` is the number of sweeps the worker runs between GO and RESULT (counted on the stand-in batch), and a DUMP
+    after RESULT runs no sweep of its own"""
+    import argparse
+    sys.path.insert(0, ROOT)
+    import bench
+    counts = {"warmup": 0, "timed": 0}
+
+    class Counting(bench._FakeBatch):
+        def sweepThermalization(self):
+            counts["timed" if self.timed else "warmup"] += 1
+
+    monkeypatch.setattr(bench, "FAKE", True)
+    monkeypatch.setattr(bench, "_FakeBatch", Counting)
+    a = argparse.Namespace(batch=2, device=0, exchange=False, warmup=2, steps=5, sub_batches=1, simindex=0)
+    emitted = []
+    script = iter(["GO", "DUMP " + str(tmp_path), "QUIT"])
+    bench.worker(a, readline=lambda: next(script) + "\n", emit=emitted.append)
+    assert counts == {"warmup": 2, "timed": 5}
+    assert emitted[0] == "READY" and emitted[1].startswith("RESULT ") and emitted[2].startswith("DUMPED ")
+    assert os.path.exists(tmp_path / "phi.npy")
+
+
+def test_dump_outputs_samples_fewer_chains_when_their_fields_are_large(tmp_path, monkeypatch):
+    """the limit holds whatever the size of one chain's field: fewer chains are sampled (the same ones in every run)"""
+    import types
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    n, B = 64, 20
+
+    class Chain:
+        def __init__(self, b):
+            self.info = types.SimpleNamespace(n_g=n, lastAccRatioLocal_phi=0.1 * b, r=-1.0 - b)
+            self.phi = np.full((50, 64, 3), float(b))
+            self.g = np.eye(n) + 1j * b
+
+    batch = types.SimpleNamespace(chain=Chain)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 200_000)
+    shapes = bench.dump_outputs(batch, str(tmp_path / "a"), B)
+    bench.dump_outputs(batch, str(tmp_path / "b"), B)
+    k = shapes["chains"][0]
+    assert 1 <= k < bench.DUMP_CHAINS and shapes["phi"] == [k, 50, 64, 3] and shapes["green_re"][:2] == [k, shapes["green_rows"][0]]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= bench.DUMP_MAX_BYTES
+    for f in os.listdir(tmp_path / "a"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 50_000)           # not even one chain's field fits: an error, no files
+    with pytest.raises(ValueError):
+        bench.dump_outputs(batch, str(tmp_path / "c"), B)
+    assert not os.path.exists(tmp_path / "c")
