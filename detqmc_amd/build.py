@@ -3,7 +3,7 @@
     python -m detqmc_amd.build            # or detqmc_amd.build.build()
 
 hipcc cross-compiles without a GPU; the resulting detqmc_amd/lib/libdetqmc_amd.so is git-ignored but
-travels to the GPU box with the source snapshot.
+travels to the GPU box with the source snapshot; so does the test-only detqmc_amd/lib/libdqmc_primitives_test.so.
 """
 import os
 import subprocess
@@ -13,6 +13,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libdetqmc_amd.so")
+# test-only entry points into the internal launchers (tests/primitives.py), linked against LIB
+PRIM_SRC = os.path.join(CSRC, "testing", "primitives_shim.hip")
+PRIM_LIB = os.path.join(LIBDIR, "libdqmc_primitives_test.so")
 
 SOURCES = [
     "kernels_bmult.hip",
@@ -63,6 +66,11 @@ def build(force=False, verbose=True):
             raise RuntimeError("compile failed: " + " ".join(cmd))
     if procs or not os.path.exists(LIB):
         cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+    if force or _newer(PRIM_SRC, PRIM_LIB) or hdr_time > os.path.getmtime(PRIM_LIB) or os.path.getmtime(LIB) > os.path.getmtime(PRIM_LIB):
+        cmd = [hipcc] + flags + ["-shared", "-x", "hip", PRIM_SRC, "-L" + LIBDIR, "-ldetqmc_amd", "-Wl,-rpath,$ORIGIN", "-o", PRIM_LIB]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)

@@ -6,6 +6,7 @@
 #include "../../include/dqmc_hip.h"
 
 #include <stdlib.h>
+#include <float.h>
 // Developer A/B switches of individual kernels (tile shapes, 3M vs 4M products, ...).  None changes a result.  They exist only in
 // builds with -DDQMC_DEV_KNOBS (DQMC_BUILD_DEFINES=-DDQMC_DEV_KNOBS python -m detqmc_amd.build --force); the shipped library reads
 // ONE environment variable, DQMC_SYNC_CHECK (debug mode, dqmc_context.hip) -- everything else that selects an execution variant is
@@ -49,6 +50,20 @@ __device__ __forceinline__ cplx nt_load(const cplx* p) {
 }
 __device__ __forceinline__ void nt_store(cplx* p, const cplx& v) {
     __builtin_nontemporal_store(v.x, &p->x); __builtin_nontemporal_store(v.y, &p->y);
+}
+// 1 / v = conj(v) / |v|^2.  When |v|^2 is not a normal number (|v| outside ~ [1.5e-154, 1.3e154]: it would be 0, subnormal or inf) v is
+// first scaled by a power of two, s = v 2^-e with max(|re s|, |im s|) in [1, 2), and 1 / v = (conj(s) / |s|^2) 2^-e.  The scaled form
+// rounds exactly like the direct one would without the range limit, and inputs with a normal |v|^2 take the direct form unchanged.
+// v = 0, inf or NaN: the direct form (inf / NaN result).  Used by the triangular solve (k_trsm_block) and the LU pivots (k_lu_panel).
+__device__ __forceinline__ cplx cplx_recip(cplx v) {
+    const double dn = v.x * v.x + v.y * v.y;
+    const double mx = fmax(fabs(v.x), fabs(v.y));
+    if (!(dn >= DBL_MIN && dn <= DBL_MAX) && mx > 0.0 && mx <= DBL_MAX) {
+        const int e = ilogb(mx);
+        const double sx = ldexp(v.x, -e), sy = ldexp(v.y, -e), sn = sx * sx + sy * sy;
+        return make_double2(ldexp(sx / sn, -e), ldexp(-sy / sn, -e));
+    }
+    return make_double2(v.x / dn, -v.y / dn);
 }
 // XCD-aware launch shape for the wide MFMA kernels: consecutive workgroup ids go round-robin over the 8 XCDs (each with
 // its own L2), so with a 1-D grid and   xcd = id % 8,  chain = 8 * (id / 8 / tiles) + xcd,  tile = (id / 8) % tiles
@@ -150,7 +165,7 @@ struct GemmArgs {
     int Kmul;
     const double* kscale;       // optional scale of the contraction index
     int kscale_invert;          // use 1/kscale
-    const double* rowscale;     // optional epilogue: acc *= rowscale[i] * colscale[j]
+    const double* rowscale;     // optional epilogue: acc *= rowscale[i] * colscale[j] (either may be null: factor 1)
     const double* colscale;
     int accumulate;             // C += instead of C =
     int negate;                 // the product enters with a minus sign (C -= A B with accumulate)
@@ -165,6 +180,10 @@ struct GemmArgs {
                                 // name (template argument), so that profiles keep it apart from the model's n_g^3 products
 };
 void launch_gemm(const Launch& lc, const GemmArgs& a);
+// the kernel shape launch_gemm picks for these arguments and nb chains: tile 32 or 64, ksplit slices of K (1: no split-K; only with
+// 32 x 32 tiles), xcd 1: the XCD-grouped 1-D grid (nb a multiple of 8), 0: grid.z = chain
+struct GemmPlan { int tile, ksplit, xcd; };
+GemmPlan gemm_plan(const GemmArgs& a, int nb);
 // G += X GrT^T, K = min(Kmax, *Kdev * Kmul): the delayed-update flush as a register-only read-modify-write stream.  X and GrT are
 // n x K8 (K8 = K rounded up to a multiple of 8, columns K .. K8 - 1 zero), both with leading dimension ld
 void launch_flush(const Launch& lc, const cplx* X, const cplx* GrT, int ld, cplx* G, int ldc, int n, int Kmax,
@@ -240,7 +259,10 @@ int run_qr_apply_q(const Launch& lc, int n, cplx* C, const QrWork& w, int trans)
 int run_qr_bgs(const Launch& lc, int n, cplx* A, cplx* Q, const QrWork& w);
 void qr_reset_workspace(const Launch& lc, int n, const QrWork& w);      // zero w.V / w.T before Householder panels follow a block Gram-Schmidt run
 int run_trsm_right_upper(const Launch& lc, int n, const cplx* R, cplx* C, const QrWork& w, int trans = 0, int unit = 0);   // C <- C R^-1 (trans: R = (stored lower triangle)^H; unit: unit diagonal)
+// (the diagonal reciprocals are scale-safe, cplx_recip: a diagonal entry outside ~ [1e-154, 1e154] is no special case)
 #define LU_SWAP_INTS 128
+// pivot search and multipliers are scale-safe: LU of 2^k A has the pivots and L of A and U scaled by 2^k, also where |a|^2 leaves
+// the normal range; NaN entries are never chosen as pivots
 int run_lu(const Launch& lc, int n, cplx* A, int* perm, int* swaps, cplx* tneg);    // tneg: scratch of n * 32 complex per chain                                 // P A = L U in place (n <= 512, else -1), kernels_lu.hip
 void launch_gather_scale_cols(const Launch& lc, const cplx* X, const double* cs, const int* perm, int n, cplx* Y);   // Y[:, j] = X[:, perm[j]] cs[perm[j]]
 void launch_udt_init(const Launch& lc, const cplx* M, int ldm, const double* cs, const double* rs, const int* perm,

@@ -225,7 +225,7 @@ __global__ __launch_bounds__(256, 2) void k_zgemm(GemmArgs g, size_t cs, int nb)
                     if (gi < g.M && gj < g.N) g.part[((size_t)blockIdx.y * g.N + gj) * g.M + gi] = make_double2(re, im);
                     continue;
                 }
-                if (g.rowscale) { double sc = g.rowscale[gic] * g.colscale[min(gj, Nm1)]; re *= sc; im *= sc; }
+                if (g.rowscale) { double sc = g.rowscale[gic]; if (g.colscale) sc *= g.colscale[min(gj, Nm1)]; re *= sc; im *= sc; }
                 else if (g.colscale) { double sc = g.colscale[min(gj, Nm1)]; re *= sc; im *= sc; }
                 if (g.negate) { re = -re; im = -im; }
                 if (g.accumulate) { re += cold[r].x; im += cold[r].y; }
@@ -611,37 +611,44 @@ static void launch_gemm_ops(const Launch& lc, const GemmArgs& a, dim3 grid) {
         else        hipLaunchKernelGGL((k_zgemm<TM, TN, M3, TAG, true, true>), grid, dim3(256), 0, lc.st, a, lc.cs, lc.nb);
     }
 }
+// Which kernel shape a product takes (launch_gemm): 64 x 64 tiles only when they still give >= 256 workgroups (fill the chip),
+// otherwise 32 x 32 tiles, split into slices of K when few tiles meet a long contraction (below).  The XCD-grouped 1-D grid when the
+// number of chains is a multiple of 8, grid.z = chain otherwise.
+GemmPlan gemm_plan(const GemmArgs& a, int nb) {
+    GemmPlan p;
+    p.xcd = nb % 8 == 0;
+    p.ksplit = 1;
+    const long tiles64 = (long)((a.M + 63) / 64) * ((a.N + 63) / 64) * nb;
+    if (tiles64 >= 256 && a.N > 32 && a.M > 32) { p.tile = 64; return p; }
+    p.tile = 32;
+    // split-K: few tiles, long contraction, a scratch buffer offered and no epilogue scaling -> slices of >= 64 k until ~ 512
+    // workgroups are in flight (a workgroup's k loop is a chain of dependent trips to memory, 16 k per trip: a slice of 288 k took
+    // 30 us whatever the tile count; round 3 split into at most 8 slices of >= 256 k and only below 128 tiles)
+    const long wg = (long)((a.M + 31) / 32) * ((a.N + 31) / 32) * nb;
+    if (a.part && a.K >= 512 && !a.Kdev && !a.kscale && !a.rowscale && !a.colscale && !a.b_lower && wg < 256) {
+        const long cap = (long)((a.part_count ? a.part_count : (size_t)a.M * a.N * 8) / ((size_t)a.M * a.N));
+        const int ks = (int)std::min<long>(std::min<long>(std::min<long>(32, cap), a.K / 64), (512 + wg - 1) / wg);
+        if (ks >= 2) p.ksplit = ks;
+    }
+    return p;
+}
+
 template<int TAG>
 static void launch_gemm_tagged(const Launch& lc, const GemmArgs& a) {
-    // fill the chip: 64x64 tiles only when they still give >= 256 workgroups
-    long tiles64 = (long)((a.M + 63) / 64) * ((a.N + 63) / 64) * lc.nb;
-    if (tiles64 >= 256 && a.N > 32 && a.M > 32) {
-        const int t = ((a.M + 63) / 64) * ((a.N + 63) / 64);
-        const dim3 grid = (lc.nb % 8 == 0) ? dim3(t * lc.nb, 1, 1) : dim3(t, 1, lc.nb);
+    const GemmPlan p = gemm_plan(a, lc.nb);
+    const int t = ((a.M + p.tile - 1) / p.tile) * ((a.N + p.tile - 1) / p.tile);
+    dim3 grid = p.xcd ? dim3(t * lc.nb, 1, 1) : dim3(t, 1, lc.nb);
+    if (p.tile == 64) {
         if (use_4m() && TAG == 0) launch_gemm_ops<2, 2, false, 0>(lc, a, grid);
         else                      launch_gemm_ops<2, 2, true, TAG>(lc, a, grid);
+    } else if (p.ksplit > 1) {
+        GemmArgs g2 = a;
+        g2.ksplit = p.ksplit; g2.accumulate = 0; g2.negate = 0;
+        grid.y = p.ksplit;
+        launch_gemm_ops<1, 1, true, TAG>(lc, g2, grid);
+        hipLaunchKernelGGL(k_gemm_reduce, dim3(std::min(256, (a.M * a.N + 255) / 256), 1, lc.nb), dim3(256), 0, lc.st, a.part, p.ksplit, a.M, a.N,
+                           a.C, a.ldc, a.accumulate, a.negate, lc.cs);
     } else {
-        const int t = ((a.M + 31) / 32) * ((a.N + 31) / 32);
-        dim3 grid = (lc.nb % 8 == 0) ? dim3(t * lc.nb, 1, 1) : dim3(t, 1, lc.nb);
-        // split-K: few tiles, long contraction, a scratch buffer offered and no epilogue scaling -> slices of >= 64 k until ~ 512
-        // workgroups are in flight (a workgroup's k loop is a chain of dependent trips to memory, 16 k per trip: a slice of 288 k took
-        // 30 us whatever the tile count; round 3 split into at most 8 slices of >= 256 k and only below 128 tiles)
-        int ks = 1;
-        const long wg = (long)t * lc.nb;
-        if (a.part && a.K >= 512 && !a.Kdev && !a.kscale && !a.rowscale && !a.colscale && !a.b_lower && wg < 256) {
-            const long cap = (long)((a.part_count ? a.part_count : (size_t)a.M * a.N * 8) / ((size_t)a.M * a.N));
-            ks = (int)std::min<long>(std::min<long>(std::min<long>(32, cap), a.K / 64), (512 + wg - 1) / wg);
-            if (ks < 2) ks = 1;
-        }
-        if (ks > 1) {
-            GemmArgs g2 = a;
-            g2.ksplit = ks; g2.accumulate = 0; g2.negate = 0;
-            grid.y = ks;
-            launch_gemm_ops<1, 1, true, TAG>(lc, g2, grid);
-            hipLaunchKernelGGL(k_gemm_reduce, dim3(std::min(256, (a.M * a.N + 255) / 256), 1, lc.nb), dim3(256), 0, lc.st, a.part, ks, a.M, a.N,
-                               a.C, a.ldc, a.accumulate, a.negate, lc.cs);
-            return;
-        }
         if (use_4m() && TAG == 0) launch_gemm_ops<1, 1, false, 0>(lc, a, grid);
         else                      launch_gemm_ops<1, 1, true, TAG>(lc, a, grid);
     }

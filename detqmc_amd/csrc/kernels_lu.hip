@@ -50,10 +50,34 @@ struct LuPanelState {
     int myrow;                   // an interchange renames rows instead of moving registers: the thread that holds the pivot row
                                  // becomes row C, the thread that was row C takes the pivot's old place
     double* redv;                // [NW] per-wave maximum key
+    double* redv2;               // [NW] per-wave maximum entry (scale-safe search only)
+    double* redv3;               // [NW] per-wave maximum scaled key (scale-safe search only)
+    int* sBad;                   // [NB] column C has a candidate whose |a|^2 is not a normal number
     cplx* sPiv;                  // [NB] the pivot row (columns of the panel)
     int* sPrev;                  // the pivot row's place before the interchange
     int* sP;                     // [NB] pivot row of every column (relative to the panel's first row)
     int tid, lane, wave, rows, ncols;
+
+    // key of a candidate with squared modulus m: the bits of m with the low 9 replaced by 511 - thread
+    __device__ __forceinline__ double pivot_key(double m) const {
+        const unsigned long long bits = ((unsigned long long)__double_as_longlong(m) & ~0x1FFull) | (unsigned long long)(511 - tid);
+        return __longlong_as_double((long long)bits);
+    }
+    // maximum of a non-negative value over the workgroup (DPP inside the wave, buf[NW] in LDS across waves; one barrier)
+    __device__ __forceinline__ double reduce_max(double v, double* buf) const {
+        v = lu_dpp_max<0x111, 0xf>(v);      // row_shr:1
+        v = lu_dpp_max<0x112, 0xf>(v);      // row_shr:2
+        v = lu_dpp_max<0x114, 0xf>(v);      // row_shr:4
+        v = lu_dpp_max<0x118, 0xf>(v);      // row_shr:8 -> lane 15 of every row of 16
+        v = lu_dpp_max<0x142, 0xa>(v);      // row_bcast:15
+        v = lu_dpp_max<0x143, 0xc>(v);      // row_bcast:31 -> lane 63
+        if (lane == 63) buf[wave] = v;
+        __syncthreads();
+        double r = buf[0];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) r = fmax(r, buf[w]);
+        return r;
+    }
 
     template<int C>
     __device__ __forceinline__ void column() {
@@ -61,23 +85,29 @@ struct LuPanelState {
         // ---- pivot search: largest |a|^2 in column C among the rows at or below the diagonal.  ONE max-reduction of a 64-bit key:
         //      the bit pattern of a non-negative double orders like its value, so the low 9 mantissa bits carry 511 - thread (a pivot
         //      within 2^-43 of the largest candidate is as good as the largest).  DPP steps inside the wave, LDS across waves. ----
+        const bool cand = myrow >= C && myrow < rows;
         double key = 0.0;
         {
             const double m = a[C].x * a[C].x + a[C].y * a[C].y;
-            const unsigned long long bits = ((unsigned long long)__double_as_longlong(m) & ~0x1FFull) | (unsigned long long)(511 - tid);
-            if (myrow >= C && myrow < rows && m == m) key = __longlong_as_double((long long)bits);
+            if (cand && m == m) key = pivot_key(m);
+            // |a|^2 outside the normal range (|a| beyond ~ 1.3e154: inf, whose key is a NaN pattern that fmax drops; below ~ 1.5e-154:
+            // 0 or subnormal, ordered by the thread number) -- flag the column for the scaled search below
+            const double mx = fmax(fabs(a[C].x), fabs(a[C].y));
+            if (cand && mx > 0.0 && mx <= DBL_MAX && !(m >= DBL_MIN && m <= DBL_MAX)) sBad[C] = 1;
         }
-        key = lu_dpp_max<0x111, 0xf>(key);      // row_shr:1
-        key = lu_dpp_max<0x112, 0xf>(key);      // row_shr:2
-        key = lu_dpp_max<0x114, 0xf>(key);      // row_shr:4
-        key = lu_dpp_max<0x118, 0xf>(key);      // row_shr:8 -> lane 15 of every row of 16
-        key = lu_dpp_max<0x142, 0xa>(key);      // row_bcast:15
-        key = lu_dpp_max<0x143, 0xc>(key);      // row_bcast:31 -> lane 63
-        if (lane == 63) redv[wave] = key;
-        __syncthreads();
-        double best = redv[0];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) best = fmax(best, redv[w]);
+        double best = reduce_max(key, redv);
+        if (sBad[C]) {
+            // scale-safe search (uniform branch, never taken when every candidate's |a|^2 is normal): the same keys of a[C] 2^-e with
+            // 2^e from the largest candidate component -- e = 0 while that lies in [2^-500, 2^500], so the pivot is today's whenever
+            // the column's largest entry is in range, and the pivots of 2^k A are those of A
+            double amax = cand ? fmax(fabs(a[C].x), fabs(a[C].y)) : 0.0;
+            if (!(amax <= DBL_MAX)) amax = 0.0;
+            amax = reduce_max(amax, redv2);
+            const int e = (amax >= 0x1p-500 && amax <= 0x1p500) || amax == 0.0 ? 0 : ilogb(amax);
+            const double sx = ldexp(a[C].x, -e), sy = ldexp(a[C].y, -e), ms = sx * sx + sy * sy;
+            key = (cand && ms == ms) ? pivot_key(ms) : 0.0;
+            best = reduce_max(key, redv3);
+        }
         // the thread that holds the pivot row; a column without a usable entry (all NaN): the thread that is row C already
         const bool none = best == 0.0 && (__double_as_longlong(best) == 0);
         const int pt = 511 - (int)((unsigned long long)__double_as_longlong(best) & 0x1FFull);
@@ -99,7 +129,9 @@ struct LuPanelState {
 #define LU_FENCE() __builtin_amdgcn_sched_barrier(0)
         const cplx piv = sPiv[C];
         const double dn = piv.x * piv.x + piv.y * piv.y;
-        const cplx inv = dn > 0.0 ? make_double2(piv.x / dn, -piv.y / dn) : make_double2(0.0, 0.0);
+        // zero pivot (or a NaN column): zero multipliers; |piv|^2 outside the normal range: the scaled reciprocal (cplx_recip)
+        const bool nz = dn > 0.0 || (dn == 0.0 && (piv.x != 0.0 || piv.y != 0.0));
+        const cplx inv = nz ? cplx_recip(piv) : make_double2(0.0, 0.0);
         if (myrow > C && myrow < rows) {
             const cplx x = a[C];
             const cplx l = make_double2(x.x * inv.x - x.y * inv.y, x.x * inv.y + x.y * inv.x);
@@ -121,13 +153,14 @@ struct LuPanelState {
 template<int NT>
 __global__ __launch_bounds__(NT) void k_lu_panel(cplx* __restrict__ A, int lda, int n, int j0, int* __restrict__ perm,
                                                   int* __restrict__ swaps, size_t cs) {
-    __shared__ double redv[NT / 64];
+    __shared__ double redv[NT / 64], redv2[NT / 64], redv3[NT / 64];
+    __shared__ int sBad[LU_NB];
     __shared__ cplx sPiv[LU_NB];
     __shared__ int sP[LU_NB], sPrev;
     __shared__ int rowof[2 * LU_NB], content[2 * LU_NB];          // thread 0's bookkeeping of the interchanges (epilogue)
     CHAIN(A); CHAIN(perm); CHAIN(swaps);
     LuPanelState<NT> s;
-    s.redv = redv; s.sPiv = sPiv; s.sPrev = &sPrev; s.sP = sP;
+    s.redv = redv; s.redv2 = redv2; s.redv3 = redv3; s.sBad = sBad; s.sPiv = sPiv; s.sPrev = &sPrev; s.sP = sP;
     s.myrow = threadIdx.x;
     s.tid = threadIdx.x; s.lane = threadIdx.x & 63; s.wave = threadIdx.x >> 6;
     s.rows = n - j0;
@@ -139,7 +172,7 @@ __global__ __launch_bounds__(NT) void k_lu_panel(cplx* __restrict__ A, int lda, 
         const cplx t = A[(size_t)(j0 + min(c, s.ncols - 1)) * lda + (j0 + min(s.tid, s.rows - 1))];
         s.a[c] = (s.tid < s.rows && c < s.ncols) ? t : make_double2(0.0, 0.0);
     }
-    if (threadIdx.x < LU_NB) sP[threadIdx.x] = threadIdx.x;
+    if (threadIdx.x < LU_NB) { sP[threadIdx.x] = threadIdx.x; sBad[threadIdx.x] = 0; }
     __syncthreads();
     LuPanelStep<0>::run(s);
     if (s.myrow < s.rows) {

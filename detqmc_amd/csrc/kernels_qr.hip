@@ -786,8 +786,7 @@ __global__ __launch_bounds__(256) void k_trsm_block(cplx* __restrict__ C, int ld
             else v = R[(size_t)(j0 + c) * ldr + (j0 + r)];
         }
         if (r == c && r < nb) {                 // the diagonal is stored as its reciprocal: one complex multiply per column and row instead of two divisions
-            const double dn = v.x * v.x + v.y * v.y;
-            v = make_double2(v.x / dn, -v.y / dn);
+            v = cplx_recip(v);
         }
         sR[r][c] = v;
     }
