@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark harness: DQMC sweeps/sec for the BASELINE.json headline workload.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 Starts by itself for any N: the parent never touches a GPU, it spawns `--workers` worker processes per GPU
 (`--device i`, default ONE), each holding `--batch` independent Markov chains spread over `--sub-batches` kernel contexts
@@ -14,9 +14,14 @@ no fermion measurements.  Every chain is an independent M
 (simindex), like the replicas the reference runs one per MPI process (`mpirun -n 8`); there is no data-path collective,
 so scaling is weak.
 
-The ONE JSON line carries, besides the contract's keys:
+A plain run does only what the headline needs: set up, warm up, time the steps, dump (if asked) and print the ONE JSON line,
+which carries, besides the contract's keys:
   per_gpu                    sweeps/s of every GPU
   one_process_sweeps_per_s   what ONE detsdw_create_batch handle in ONE process delivers (a DetQMCPT port owning one process per GPU)
+  acceptance                 last local acceptance ratio of the first chains of the first worker
+
+--full adds the measurements that take runs of their own, after the timed region and the dump (rank 0, first GPU):
+  device_ms_by_family_timed_regime   the timed regime once more with per-family HIP-event timing in every context
   one_context_sweeps_per_s   ONE kernel context (one stream) alone on the GPU
   single_chain_sweeps_per_s  one context x one chain (latency of a single Markov chain)
   roofline                   the kernel family with the largest device time, measured with HIP events on the kernel's own
@@ -24,6 +29,7 @@ The ONE JSON line carries, besides the contract's keys:
                              against its BINDING roof (HBM or fp64 MFMA, whichever fraction is larger)
   roofline_other_kernels, roofline_whole_step
   cpu_baseline, cpu_baseline_all_cores   the real reference binary (oracle/_ref) on this host, N = 1 only
+                                         (--no-cpu-baseline leaves it out)
 
 --dump-outputs DIR writes, after the timed steps, what the timed path computed in its last step as DIR/<name>.npy (see
 dump_outputs): the state of a fixed sample of the chains of the first worker.  The inputs are seeded, so two builds run with
@@ -618,7 +624,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=6)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the per-kernel profiles, the one-context and single-chain rates, the rooflines and the CPU "
+                         "baseline (each a run of its own)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--config", default=DEFAULT_CONFIG, choices=sorted(CONFIGS),
                     help="BASELINE.json workload: o2_L16_b10 (config 3, the one the metric is quoted on; default), o2_L8_b5 (2), "
                          "o2_L16_b20 (4), o3_L24_b20 (5, without the flux the reference rejects)")
@@ -740,30 +749,31 @@ def main():
         per_gpu[g] = max(per_gpu.get(g, 0.0), r["dt"])
     per_gpu = [R * B * a.steps / per_gpu[g] for g in sorted(per_gpu)]
 
-    # post-phases (rank 0, first GPU), after every timed worker has left the GPU:
+    # post-phases (rank 0, first GPU), only with --full, after every timed worker has left the GPU:
     #   ONE kernel context (B / S chains, one stream) alone: its rate, then the same steps with per-kernel HIP-event timing;
     #   ONE context with ONE chain: the latency of a single Markov chain
     lead = rank == 0
+    full = lead and a.full
     inproc_solo = None
     prof4 = None
     if lead and a.dump_outputs:
         send(procs[0][1], "DUMP " + os.path.abspath(a.dump_outputs))
         read_tag(procs[0][1], "DUMPED")
-    if lead and not a.inprocess and R == 1 and n_gpus == 1:
+    if full and not a.inprocess and R == 1 and n_gpus == 1:
         # the timed regime once more with per-family event timing in every context (only when ONE worker drives the whole GPU)
         send(procs[0][1], "PROF4")
         prof4 = json.loads(read_tag(procs[0][1], "PROF4"))
     for i, (_, p) in enumerate(procs):
-        send(p, "SOLO" if (a.inprocess and lead and i == 0) else "QUIT")
-    if a.inprocess and lead:
+        send(p, "SOLO" if (a.inprocess and full and i == 0) else "QUIT")
+    if a.inprocess and full:
         inproc_solo = json.loads(read_tag(procs[0][1], "SOLO"))
         send(procs[0][1], "QUIT")
     for _, p in procs:
         p.wait()
-    cpu = CpuBaseline() if (lead and n_gpus == 1 and not a.no_cpu_baseline) else None     # 1-core run overlaps the post-phases
+    cpu = CpuBaseline() if (full and n_gpus == 1 and not a.no_cpu_baseline) else None     # 1-core run overlaps the post-phases
     single = one_ctx = solo = None
     Bc = B // S                                                                          # chains of one kernel context
-    if lead and not a.inprocess:
+    if full and not a.inprocess:
         pw = spawn(my_gpus[0], 7777, Bc, a.steps, a.warmup, sub=1)
         read_tag(pw, "READY")
         send(pw, "GO")
@@ -784,7 +794,7 @@ def main():
         send(sp, "QUIT")
         sp.wait()
         single = nst / sr["dt"]
-    elif lead:
+    elif full:
         solo, one_ctx = inproc_solo, B * a.steps / results[0]["dt"]
         Bc = B
     if dist is not None:
@@ -823,12 +833,13 @@ def main():
             "per_gpu": per_gpu,
             # what ONE detsdw_create_batch handle (one process) delivers: the headline itself when processes_per_gpu is 1
             "one_process_sweeps_per_s": per_gpu[0] / R,
-            # ONE kernel context (dqmc_create_batch: one stream, one launch sequence) of chains_per_context chains alone on the GPU
-            "one_context_sweeps_per_s": one_ctx,
-            "single_chain_sweeps_per_s": single,
-            "single_chain_delaySteps": (int(os.environ["DQMC_DELAY_STEPS"]) if os.environ.get("DQMC_DELAY_STEPS") else min(WORKLOAD["delaySteps"], 16)),
             "acceptance": r0["acceptance"],
         }
+        if full:
+            # ONE kernel context (dqmc_create_batch: one stream, one launch sequence) of chains_per_context chains alone on the GPU
+            res["one_context_sweeps_per_s"] = one_ctx
+            res["single_chain_sweeps_per_s"] = single
+            res["single_chain_delaySteps"] = (int(os.environ["DQMC_DELAY_STEPS"]) if os.environ.get("DQMC_DELAY_STEPS") else min(WORKLOAD["delaySteps"], 16))
         if solo and solo.get("prof"):
             prof, roofs, whole = rooflines(solo["prof"], n, r0["m"], Bc, load_traffic(Bc, WORKLOAD["delaySteps"]))
             res["roofline"] = roofs[0]

@@ -1,5 +1,5 @@
-"""Average launch durations: bench.py's live HIP-event averages (JSON line) next to the rocprofv3 --kernel-trace --stats summary of
-the same command.   python scripts/compare_events_vs_rocprof.py bench.json kernel_stats.csv
+"""Average launch durations: the live HIP-event averages of `bench.py --full` (JSON line) next to the rocprofv3 --kernel-trace --stats
+summary of the same command.   python scripts/compare_events_vs_rocprof.py bench.json kernel_stats.csv
 The csv covers every launch of the process (set-up, warm-up, timed steps, profiled steps), the JSON line the profiled steps only:
 with enough warm-up for the acceptance to settle the two agree to a few per cent."""
 import csv, json, sys

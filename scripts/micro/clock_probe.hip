@@ -4,7 +4,7 @@
 // bench.py prices MFMA-bound kernels against 78.6 TFLOP/s = 256 CUs x 128 flop/clk x 2.4 GHz; if the chip holds less than 2.4 GHz under
 // the fp64-MFMA + HBM load of the sweep, the roofline fractions understate how close the kernels are to what the silicon delivers.
 //   hipcc --offload-arch=gfx950 -O3 scripts/micro/clock_probe.hip -o scripts/micro/bin/clock_probe
-//   scripts/micro/bin/clock_probe 20 &  python bench.py --inprocess --batch 128 --sub-batches 1 --steps 10 --warmup 5 --no-cpu-baseline
+//   scripts/micro/bin/clock_probe 20 &  python bench.py --inprocess --batch 128 --sub-batches 1 --steps 10 --warmup 5 --full --no-cpu-baseline
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>

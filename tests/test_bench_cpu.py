@@ -27,7 +27,7 @@ def _line(out):
 
 def test_bench_starts_by_itself_for_two_gpus():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--workers", "2",
-                          "--batch", "4", "--no-cpu-baseline"], capture_output=True, text=True, timeout=120, env=_env())
+                          "--batch", "4", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=120, env=_env())
     assert out.returncode == 0, out.stderr
     r = _line(out)
     assert r["n_gpus"] == 2 and r["steps"] == 3 and r["warmup"] == 1 and r["scaling"] == "weak"
@@ -48,6 +48,28 @@ def test_bench_single_gpu_line_has_the_contract_keys():
               "data", "config", "per_gpu"):
         assert k in r, k
     assert r["n_gpus"] == 1 and "workload" in r["config"] and "model" not in r["config"]
+
+
+def test_plain_bench_run_reports_the_headline_only():
+    """A plain run sets up, warms up, times the steps and prints the line; what takes runs of its own (the timed regime profiled,
+    one context alone, a single chain, rooflines, the CPU baseline) comes only with --full."""
+    extra = ("one_context_sweeps_per_s", "single_chain_sweeps_per_s", "single_chain_delaySteps", "roofline", "roofline_other_kernels",
+             "roofline_whole_step", "device_ms_by_family", "device_ms_by_family_timed_regime", "cpu_baseline", "cpu_baseline_all_cores")
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "2"]
+    for variant in ([], ["--inprocess"]):
+        out = subprocess.run(base + variant, capture_output=True, text=True, timeout=120, env=_env())
+        assert out.returncode == 0, out.stderr
+        r = _line(out)
+        assert [k for k in extra if k in r] == [], variant
+        assert r["steps"] == 2 and r["warmup"] == 1 and r["ms_per_step"] > 0 and r["value"] > 0 and r["unit"] == "sweeps/s"
+        assert r["higher_is_better"] is True and r["dtype"] == "f64" and r["metric"].startswith("DQMC sweeps/sec")
+    for variant in ([], ["--inprocess"]):
+        out = subprocess.run(base + variant + ["--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=120, env=_env())
+        assert out.returncode == 0, out.stderr
+        r = _line(out)
+        assert r["one_context_sweeps_per_s"] > 0 and "cpu_baseline" not in r, variant
+        if not variant:
+            assert r["single_chain_sweeps_per_s"] > 0 and r["single_chain_delaySteps"] == 16
 
 
 def test_bench_under_torch_distributed_run_gloo():
