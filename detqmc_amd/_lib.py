@@ -42,7 +42,7 @@ class dqmc_params(C.Structure):
                 ("lambda_", C.c_double),
                 ("txhor", C.c_double), ("txver", C.c_double), ("tyhor", C.c_double), ("tyver", C.c_double),
                 ("mux", C.c_double), ("muy", C.c_double), ("accRatio", C.c_double), ("cdwU", C.c_double),
-                ("rng_window_per_site", C.c_int32), ("reserved_model", C.c_int32),
+                ("rng_window_per_site", C.c_int32), ("timedisplaced", C.c_int32),
                 ("tuning", dqmc_tuning)]
 
 
@@ -84,7 +84,7 @@ class detsdw_params(C.Structure):
                 ("wolffClusterUpdate", C.c_int32), ("wolffClusterShiftUpdate", C.c_int32),
                 ("repeatWolffPerSweep", C.c_int32), ("fermionMeasurements", C.c_int32),
                 ("spinProposalMethod", C.c_int32), ("adaptScaleVariance", C.c_int32), ("repeatUpdateInSlice", C.c_int32),
-                ("reserved_model", C.c_int32),
+                ("timeDisplacedMeasurements", C.c_int32),
                 ("tuning", dqmc_tuning)]
 
 
@@ -189,6 +189,11 @@ SYMBOLS = [
     ("dqmc_measure_slice", C.c_int, [_P]),
     ("dqmc_measure_accum_size", C.c_size_t, [_P]),
     ("dqmc_measure_read_host", C.c_int, [_P, _DP]),
+    ("dqmc_set_timedisplaced", C.c_int, [_P, C.c_int]),
+    ("dqmc_get_green_timedisplaced_host", C.c_int, [_P, _P, _P, C.POINTER(C.c_int)]),
+    ("dqmc_measure_timedisplaced", C.c_int, [_P, C.c_int]),
+    ("dqmc_measure_td_accum_size", C.c_size_t, [_P]),
+    ("dqmc_measure_td_read_host", C.c_int, [_P, _DP]),
     ("dqmc_profile_enable", C.c_int, [_P, C.c_int]),
     ("dqmc_profile_read", C.c_int, [_P, C.POINTER(dqmc_profile)]),
     ("detsdw_create", C.c_int, [C.POINTER(detsdw_params), C.POINTER(_P)]),
@@ -205,6 +210,7 @@ SYMBOLS = [
     ("detsdw_get_info", C.c_int, [_P, C.POINTER(detsdw_info)]),
     ("detsdw_get_observables", C.c_int, [_P, C.POINTER(detsdw_observables)]),
     ("detsdw_get_observable_vector", C.c_int, [_P, C.c_int, _DP]),
+    ("detsdw_get_tau_grid", C.c_int, [_P, _DP]),
     ("detsdw_get_phi", C.c_int, [_P, _DP]),
     ("detsdw_set_phi", C.c_int, [_P, _DP]),
     ("detsdw_get_cdwl", C.c_int, [_P, _P]),

@@ -71,6 +71,13 @@ struct dqmc_ctx {
     cplx *propKh[2] = {nullptr, nullptr};                    // CB_NONE only: e^{-+dtau K / 2} (propK_half, propK_half_inv)
     double* macc = nullptr;                                   // fermionic measurement accumulators (kernels_measure.hip)
     size_t macc_n = 0;
+    // time-displaced Green's functions (dqmc_params::timedisplaced reserves them; dqmc_set_timedisplaced switches them on)
+    bool td_reserved = false, td_on = false;
+    int td_slice = -1;                                        // tau slice of the last pair GT0 / G0T (all chains), -1: none yet
+    cplx *GT0 = nullptr, *G0T = nullptr, *td_W = nullptr;     // G(tau,0), G(0,tau), scratch of the extra solves
+    double* td_sv = nullptr;                                  // SVD mode: log-det output of the LU / QR route (c->sv keeps the Jacobi values)
+    double* tdacc = nullptr;                                  // accumulator block of dqmc_measure_timedisplaced (kernels_measure.hip)
+    size_t tdacc_n = 0;
     SvdWork sw{};
     double hub_e_m2a = 1.0, hub_e_p2a = 1.0;  // Hubbard: exp(-+2 alpha) of weightRatioSingleFlip (dethubbard.cpp:866-867)
     int stab = 0;                       // DQMC_STAB_SVD / DQMC_STAB_QR
@@ -468,6 +475,22 @@ static void build_hubbard_propK(const dqmc_params& p, const std::vector<int>& ne
 // ---------------------------------------------------------------------------------------------
 // lifetime
 // ---------------------------------------------------------------------------------------------
+// workspace of the QR-mode factorisations and of the scale-split inverse inside greenFromUdV (green_qr)
+static int alloc_qr_work(dqmc_ctx* c) {
+    const int ng = c->n_g, np = (ng + 15) / 16;
+    const size_t n2 = (size_t)ng * ng;
+    int rc;
+#define A_(x) if ((rc = (x))) return rc;
+    A_(dalloc(c, &c->qw.V, n2)); A_(dalloc(c, &c->qw.T, (size_t)np * 2 * 256));
+    A_(dalloc(c, &c->qw.W, (size_t)16 * ng)); A_(dalloc(c, &c->qw.W2, (size_t)16 * ng)); A_(dalloc(c, &c->qw.Rneg, (size_t)32 * ng));
+    if (ng > 1024) { c->qw.part_count = (size_t)ng * 64 * 8; A_(dalloc(c, &c->qw.part, c->qw.part_count)); }   // split-K scratch of the block Gram-Schmidt QR
+    A_(dalloc(c, &c->qr_perm, (size_t)ng)); A_(dalloc(c, &c->lu_swaps, (size_t)LU_SWAP_INTS)); A_(dalloc(c, &c->lu_tneg, (size_t)ng * 32)); A_(dalloc(c, &c->qr_perm_inv, (size_t)ng)); A_(dalloc(c, &c->qr_dinv, (size_t)ng));
+    A_(dalloc(c, &c->rmax_inv, (size_t)ng)); A_(dalloc(c, &c->rmin, (size_t)ng));
+    A_(dalloc(c, &c->lmax_inv, (size_t)ng)); A_(dalloc(c, &c->lmin, (size_t)ng));
+#undef A_
+    return 0;
+}
+
 static int alloc_slot(dqmc_ctx* c, UdVSlot& sl) {
     size_t n2 = (size_t)c->n_g * c->n_g;
     int rc;
@@ -641,15 +664,7 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
     // n_g > 1024: block Gram-Schmidt + Cholesky-QR2 on the GEMM kernel instead of 144 tall Householder panels (kernels_qr.hip)
     c->qr_bgs = p->tuning.qr_variant == 2 || (p->tuning.qr_variant == 0 && ng > 1024);
     c->green_lu = ng <= 512 && p->tuning.green_variant != 1;
-    if (c->stab == DQMC_STAB_QR) {
-        const int np = (ng + 15) / 16;
-        A_(dalloc(c, &c->qw.V, n2)); A_(dalloc(c, &c->qw.T, (size_t)np * 2 * 256));
-        A_(dalloc(c, &c->qw.W, (size_t)16 * ng)); A_(dalloc(c, &c->qw.W2, (size_t)16 * ng)); A_(dalloc(c, &c->qw.Rneg, (size_t)32 * ng));
-        if (ng > 1024) { c->qw.part_count = (size_t)ng * 64 * 8; A_(dalloc(c, &c->qw.part, c->qw.part_count)); }   // split-K scratch of the block Gram-Schmidt QR
-        A_(dalloc(c, &c->qr_perm, (size_t)ng)); A_(dalloc(c, &c->lu_swaps, (size_t)LU_SWAP_INTS)); A_(dalloc(c, &c->lu_tneg, (size_t)ng * 32)); A_(dalloc(c, &c->qr_perm_inv, (size_t)ng)); A_(dalloc(c, &c->qr_dinv, (size_t)ng));
-        A_(dalloc(c, &c->rmax_inv, (size_t)ng)); A_(dalloc(c, &c->rmin, (size_t)ng));
-        A_(dalloc(c, &c->lmax_inv, (size_t)ng)); A_(dalloc(c, &c->lmin, (size_t)ng));
-    }
+    if (c->stab == DQMC_STAB_QR) A_(alloc_qr_work(c));
     A_(alloc_slot(c, c->eye));
     const int WD = MSF * c->D;
     const int WD8 = (WD + 7) & ~7;          // X and GrT are zero padded to a multiple of 8 columns for the flush kernel
@@ -680,6 +695,14 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
     A_(salloc(c, &c->shift_buf, (size_t)c->nb * 3));
     c->macc_n = measure_accum_doubles(N, p->L);
     A_(dalloc(c, &c->macc, c->macc_n));
+    if (p->timedisplaced) {                 // behind every other buffer: the layout of a context without them is unchanged
+        if (p->model != DQMC_MODEL_SDW) return fail(DQMC_EINVAL, "timedisplaced: SDW model only");
+        c->td_reserved = true;
+        A_(dalloc(c, &c->GT0, n2)); A_(dalloc(c, &c->G0T, n2)); A_(dalloc(c, &c->td_W, n2));
+        if (c->stab != DQMC_STAB_QR) { A_(alloc_qr_work(c)); A_(dalloc(c, &c->td_sv, (size_t)ng)); }
+        c->tdacc_n = measure_td_doubles(p->L, c->n);
+        A_(dalloc(c, &c->tdacc, c->tdacc_n));
+    }
     A_(arena_commit(c));                    // from here on the per-chain pointers are real (chain 0) addresses, zero filled
 #undef A_
     c->qw.err = &c->us->chol_fail;
@@ -823,7 +846,7 @@ extern "C" int dqmc_get_fields_all_host(dqmc_ctx* c, double* phi_all) {
 // 2307-2324, 2406-2420)
 static void gemm_dev(dqmc_ctx* c, int opA, int opB, const cplx* A, const cplx* B, cplx* C,
                      const double* kscale = nullptr, int kinv = 0, const double* rowscale = nullptr,
-                     const double* colscale = nullptr, int accumulate = 0, int sharedA = 0, int sharedB = 0);
+                     const double* colscale = nullptr, int accumulate = 0, int sharedA = 0, int sharedB = 0, int negate = 0);
 
 static void bmult_dev(dqmc_ctx* c, int side, int inverse, int k2, int k1, cplx* A) {
     const int count = k2 - k1;
@@ -862,13 +885,13 @@ static void bmult_dev(dqmc_ctx* c, int side, int inverse, int k2, int k1, cplx* 
 
 static void gemm_dev(dqmc_ctx* c, int opA, int opB, const cplx* A, const cplx* B, cplx* C,
                      const double* kscale, int kinv, const double* rowscale,
-                     const double* colscale, int accumulate, int sharedA, int sharedB) {
+                     const double* colscale, int accumulate, int sharedA, int sharedB, int negate) {
     GemmArgs g;
     memset(&g, 0, sizeof(g));
     g.A = A; g.lda = c->n_g; g.opA = opA; g.B = B; g.ldb = c->n_g; g.opB = opB; g.C = C; g.ldc = c->n_g;
     g.M = g.N = g.K = c->n_g; g.Kmul = 1;
     g.kscale = kscale; g.kscale_invert = kinv; g.rowscale = rowscale; g.colscale = colscale; g.accumulate = accumulate;
-    g.sharedA = sharedA; g.sharedB = sharedB;
+    g.sharedA = sharedA; g.sharedB = sharedB; g.negate = negate;
     c->gemm_flops += 8.0 * (double)g.M * g.N * g.K * c->nb;
     ProfScope ps(c, FAM_GEMM, 1);
     launch_gemm(c->lc, g);
@@ -972,11 +995,56 @@ static int udt_dev(dqmc_ctx* c, const cplx* M, const double* colscale, const dou
     return DQMC_OK;
 }
 
+// Time-displaced pair from the factorisation of Z that green_qr has just made (dqmc_hip.h):
+//   G(tau,0) = [V_l Dlmax^-1] Z^-1 [Drmin V_r^H],   G(0,tau) = -[U_l Dlmin] Z^-1 [Drmax^-1 U_r^H].
+// The outer brackets of G(tau) are T3 = [V_l Dlmax^-1] (first half of Z^-1) and T1 (the other half with [Drmax^-1 U_r^H]), so each
+// new matrix is one more triangular solve (LU route) or Q application (QR route) and one GEMM.
+//   LU route, P Z = L U:  G(tau,0) = T3 [(V_r Drmin P^T) L^-H]^H,   G(0,tau) = -[(U_l Dlmin) U^-1] T1^H
+//   QR route, Z P = Q R:  G(tau,0) = T3 [Q^H Drmin V_r^H],          G(0,tau) = -[(U_l Dlmin P) R^-1] T1
+static void td_from_lu(dqmc_ctx* c, const UdVSlot& L, const UdVSlot& R) {
+    const int n = c->n_g;
+    {
+        ProfScope ps(c, FAM_JACOBI, 0);
+        launch_gather_scale_cols(c->lc, R.Vt, c->rmin, c->qr_perm, n, c->T4);         // T4 = (V_r Drmin) P^T
+        int launches = run_trsm_right_upper(c->lc, n, c->T2, c->T4, c->qw, 1, 1);      // T4 <- T4 L^-H
+        launch_permute_scale_cols(c->lc, L.U, c->lmin, nullptr, n, c->td_W);           // td_W = U_l Dlmin
+        launches += run_trsm_right_upper(c->lc, n, c->T2, c->td_W, c->qw);             // td_W <- td_W U^-1
+        c->fam_launches[FAM_JACOBI] += launches + 2;
+    }
+    gemm_dev(c, 0, 1, c->T3, c->T4, c->GT0);
+    gemm_dev(c, 0, 1, c->td_W, c->T1, c->G0T, nullptr, 0, nullptr, nullptr, 0, 0, 0, /*negate=*/1);
+}
+// bgs: Q is explicit in T4 (block Gram-Schmidt), else it is in reflector form in the QR workspace; R in sw.A
+static void td_from_qr(dqmc_ctx* c, const UdVSlot& L, const UdVSlot& R, bool bgs) {
+    const int n = c->n_g;
+    {
+        ProfScope ps(c, FAM_JACOBI, 0);
+        int launches = 0;
+        if (bgs) launch_udt_init(c->lc, R.Vt, n, c->rmin, nullptr, nullptr, 1, c->td_W, n);     // td_W = Drmin V_r^H
+        else {
+            launch_udt_init(c->lc, R.Vt, n, c->rmin, nullptr, nullptr, 1, c->T2, n);            // T2 = Drmin V_r^H
+            SvdProfHooks hk;
+            c->qw.apply_hooks = qr_hooks(c, hk);
+            launches += run_qr_apply_q(c->lc, n, c->T2, c->qw, 1);                               // T2 = Q^H Drmin V_r^H
+        }
+        c->fam_launches[FAM_JACOBI] += launches + 1;
+    }
+    if (bgs) gemm_dev(c, 1, 0, c->T4, c->td_W, c->T2);                                           // T2 = Q^H Drmin V_r^H
+    gemm_dev(c, 0, 0, c->T3, c->T2, c->GT0);
+    {
+        ProfScope ps(c, FAM_JACOBI, 0);
+        launch_permute_scale_cols(c->lc, L.U, c->lmin, c->qr_perm, n, c->td_W);                // td_W = U_l Dlmin P
+        c->fam_launches[FAM_JACOBI] += 1 + run_trsm_right_upper(c->lc, n, c->sw.A, c->td_W, c->qw);   // td_W <- td_W R^-1
+    }
+    gemm_dev(c, 0, 0, c->td_W, c->T1, c->G0T, nullptr, 0, nullptr, nullptr, 0, 0, 0, /*negate=*/1);
+}
+
 // G from an L-type and an R-type factorisation (nullptr = identity), with the scales split into their
 // parts > 1 and <= 1 so that the matrix that is actually inverted,
 //   Z = Drmax^-1 (U_r^H V_l) Dlmax^-1 + Drmin (V_r^H U_l) Dlmin,
 // has entries O(1):  G = (V_l Dlmax^-1) Z^-1 (U_r Drmax^-1)^H,  Z P = Q R  =>  Z^-1 = P R^-1 Q^H.
-static int green_qr(dqmc_ctx* c, const UdVSlot* Lp, const UdVSlot* Rp) {
+// Gout = nullptr: G itself is not formed (SVD mode builds only the time-displaced pair here); td: also G(tau,0), G(0,tau).
+static int green_qr(dqmc_ctx* c, const UdVSlot* Lp, const UdVSlot* Rp, cplx* Gout, double* svout, bool td = false) {
     const int n = c->n_g;
     const UdVSlot& L = Lp ? *Lp : c->eye;
     const UdVSlot& R = Rp ? *Rp : c->eye;
@@ -996,15 +1064,17 @@ static int green_qr(dqmc_ctx* c, const UdVSlot* Lp, const UdVSlot* Rp) {
             int launches = run_lu(c->lc, n, c->T2, c->qr_perm, c->lu_swaps, c->lu_tneg);                  // T2 = L \ U, qr_perm = row permutation
             launch_permute_scale_cols(c->lc, L.Vt, c->lmax_inv, nullptr, n, c->T3);
             launches += run_trsm_right_upper(c->lc, n, c->T2, c->T3, c->qw);                  // T3 = (V_l Dlmax^-1) U^-1
-            launch_logdet_vector(c->lc, c->T2, c->rmax_inv, c->lmax_inv, n, c->sv);           // |det Z| = prod |U_kk|
+            launch_logdet_vector(c->lc, c->T2, c->rmax_inv, c->lmax_inv, n, svout);           // |det Z| = prod |U_kk|
             launch_gather_scale_cols(c->lc, R.U, c->rmax_inv, c->qr_perm, n, c->T1);          // T1 = (U_r Drmax^-1) P^T
             launches += run_trsm_right_upper(c->lc, n, c->T2, c->T1, c->qw, 1, 1);            // T1 <- T1 (L^H)^-1
             c->fam_launches[FAM_JACOBI] += launches + 3;
             c->lu_calls += 1;
         }
-        gemm_dev(c, 0, 1, c->T3, c->T1, c->G);                                                // G = T3 T1^H
+        if (Gout) gemm_dev(c, 0, 1, c->T3, c->T1, Gout);                                      // G = T3 T1^H
+        if (td) td_from_lu(c, *Lp, *Rp);
         return DQMC_OK;
     }
+    bool fell_back = false;
     {
         ProfScope ps(c, FAM_JACOBI, 0);
         launch_scaled_norms_rank(c->lc, c->T2, n, nullptr, nullptr, 0, n, c->sw.norms, c->qr_perm, c->sw.rnorms);
@@ -1023,6 +1093,7 @@ static int green_qr(dqmc_ctx* c, const UdVSlot* Lp, const UdVSlot* Rp) {
             if (failed) {
                 c->cholqr_fallbacks += 1;
                 bgs = false;
+                fell_back = true;
                 qr_reset_workspace(c->lc, n, c->qw);
                 launch_udt_init(c->lc, c->T2, n, nullptr, nullptr, c->qr_perm, 0, c->sw.A, n);
                 launches += 3;
@@ -1031,7 +1102,7 @@ static int green_qr(dqmc_ctx* c, const UdVSlot* Lp, const UdVSlot* Rp) {
         if (!bgs) launches += run_qr(c->lc, n, c->sw.A, nullptr, c->qw);   // sw.A = R factor, Q stays in reflector form
         launch_permute_scale_cols(c->lc, L.Vt, c->lmax_inv, c->qr_perm, n, c->T3);
         launches += run_trsm_right_upper(c->lc, n, c->sw.A, c->T3, c->qw);   // T3 = (V_l Dlmax^-1 P) R^-1
-        launch_logdet_vector(c->lc, c->sw.A, c->rmax_inv, c->lmax_inv, n, c->sv);
+        launch_logdet_vector(c->lc, c->sw.A, c->rmax_inv, c->lmax_inv, n, svout);
         if (bgs) {
             launch_udt_init(c->lc, R.U, n, c->rmax_inv, nullptr, nullptr, 1, c->sw.V, n);   // sw.V = Drmax^-1 U_r^H
             c->fam_launches[FAM_JACOBI] += launches + 6;
@@ -1044,7 +1115,8 @@ static int green_qr(dqmc_ctx* c, const UdVSlot* Lp, const UdVSlot* Rp) {
             c->qr_calls += 1;
         }
     }
-    gemm_dev(c, 0, 0, c->T3, c->T1, c->G);                                 // G = T3 T1
+    if (Gout) gemm_dev(c, 0, 0, c->T3, c->T1, Gout);                       // G = T3 T1
+    if (td) td_from_qr(c, *Lp, *Rp, c->qr_bgs && !fell_back);
     return DQMC_OK;
 }
 
@@ -1084,8 +1156,9 @@ static int decompose_chained(dqmc_ctx* c, const cplx* M, const double* colscale,
 }
 
 // greenFromUdV (detmodel.h:769-818)
+// While the time-displaced functions are on, this is where they come from (every call is at an interior boundary).
 static int green_from_udv(dqmc_ctx* c, const UdVSlot& L, const UdVSlot& R) {
-    if (c->stab == DQMC_STAB_QR) return green_qr(c, &L, &R);
+    if (c->stab == DQMC_STAB_QR) return green_qr(c, &L, &R, c->G, c->sv, c->td_on);
     gemm_dev(c, 1, 0, R.U, L.Vt, c->T2);                                  // UtVt_rl = U_r^H V_t_l
     gemm_dev(c, 1, 0, R.Vt, L.U, c->T2, nullptr, 0, R.d, L.d, 1);         // += diag(d_r) (V_t_r^H U_l) diag(d_l)
     UdVSlot t = c->tmpudv; t.d = c->sv;
@@ -1094,11 +1167,13 @@ static int green_from_udv(dqmc_ctx* c, const UdVSlot& L, const UdVSlot& R) {
     gemm_dev(c, 0, 0, L.Vt, t.Vt, c->T3);                                 // Vt_product
     gemm_dev(c, 0, 0, R.U, t.U, c->T4);                                   // U_product
     gemm_dev(c, 0, 1, c->T3, c->T4, c->G, c->sv, 1);                      // G = Vt_product diag(1/sv) U_product^H
+    // SVD mode: G stays on the path above; the pair comes from the scale-split Z, built and factorised after G
+    if (c->td_on) return green_qr(c, &L, &R, nullptr, c->td_sv, true);
     return DQMC_OK;
 }
 // greenFromEye_and_UdV (detmodel.h:823-860); kind tells whether the factorisation is R-type or L-type
 static int green_from_eye(dqmc_ctx* c, const UdVSlot& R, int kind) {
-    if (c->stab == DQMC_STAB_QR) return (kind == KIND_R) ? green_qr(c, nullptr, &R) : green_qr(c, &R, nullptr);
+    if (c->stab == DQMC_STAB_QR) return (kind == KIND_R) ? green_qr(c, nullptr, &R, c->G, c->sv) : green_qr(c, &R, nullptr, c->G, c->sv);
     gemm_dev(c, 1, 0, R.U, R.Vt, c->T2);
     { ProfScope ps(c, FAM_OTHER, 1); launch_add_diag(c->lc, c->T2, R.d, c->n_g); }
     UdVSlot t = c->tmpudv; t.d = c->sv;
@@ -1169,8 +1244,10 @@ extern "C" int dqmc_advance(dqmc_ctx* c, int dir, int l) {
             bmult_dev(c, DQMC_RIGHT, 0, k_l, k_lm1, c->T1);
             if ((rc = decompose(c, c->T1, nullptr, nullptr, KIND_L, L))) return rc;
         }
-        if (l - 1 > 0) rc = green_from_udv(c, L, c->storage[l - 1]);
-        else rc = green_from_eye(c, L, KIND_L);
+        if (l - 1 > 0) {
+            rc = green_from_udv(c, L, c->storage[l - 1]);
+            if (!rc && c->td_on) c->td_slice = s * (l - 1);
+        } else rc = green_from_eye(c, L, KIND_L);
         if (rc) return rc;
         std::swap(c->storage[l - 1], c->spare);          // storage[l-1] = UdV_L
         c->currentTimeslice = s * (l - 1);
@@ -1184,8 +1261,10 @@ extern "C" int dqmc_advance(dqmc_ctx* c, int dir, int l) {
         launch_copy(c->lc, st.U, c->T1, (size_t)ng * ng);
         bmult_dev(c, DQMC_LEFT, 0, k_lp1, k_l, c->T1);
         if ((rc = decompose_chained(c, c->T1, st.d, nullptr, KIND_R, T, st.Vt))) return rc;
-        if (k_lp1 != m) rc = green_from_udv(c, c->storage[l + 1], T);
-        else rc = green_from_eye(c, T, KIND_R);
+        if (k_lp1 != m) {
+            rc = green_from_udv(c, c->storage[l + 1], T);
+            if (!rc && c->td_on) c->td_slice = k_lp1;
+        } else rc = green_from_eye(c, T, KIND_R);
         if (rc) return rc;
         std::swap(c->storage[l + 1], c->spare);
         c->currentTimeslice = k_lp1;
@@ -1495,10 +1574,10 @@ extern "C" int dqmc_restore(dqmc_ctx* c) {
 // ---------------------------------------------------------------------------------------------
 // fermionic measurements: shiftGreenSymmetric + per-slice accumulation on the device
 // ---------------------------------------------------------------------------------------------
-// T1 <- e^{-dtau K/2} G e^{+dtau K/2} (detsdwopdim.cpp:4507-4612)
-static void shift_green_dev(dqmc_ctx* c) {
+// T1 <- e^{-dtau K/2} G e^{+dtau K/2} (detsdwopdim.cpp:4507-4612); src: G (default) or another matrix of the same shape
+static void shift_green_dev(dqmc_ctx* c, const cplx* src = nullptr) {
     const size_t n2 = (size_t)c->n_g * c->n_g;
-    launch_copy(c->lc, c->G, c->T1, n2);
+    launch_copy(c->lc, src ? src : c->G, c->T1, n2);
     if (!c->hm.dense) {
         ProfScope ps(c, FAM_BMULT, 2);
         launch_bmult(c->lc, nullptr, c->hm, DQMC_RIGHT, 1, 0, 1, 1, c->T1, c->n_g, /*shift=*/1);   // right: +sinh half steps
@@ -1522,6 +1601,8 @@ extern "C" int dqmc_measure_reset(dqmc_ctx* c) {
     if (!c) return fail(DQMC_EINVAL, "null ctx");
     (void)hipSetDevice(c->p.device);
     for (int b = 0; b < c->nb; ++b) HIPCHK(hipMemsetAsync(chainp(c, c->macc, b), 0, c->macc_n * sizeof(double), c->st));
+    if (c->td_reserved)
+        for (int b = 0; b < c->nb; ++b) HIPCHK(hipMemsetAsync(chainp(c, c->tdacc, b), 0, c->tdacc_n * sizeof(double), c->st));
     return DQMC_OK;
 }
 extern "C" int dqmc_measure_slice(dqmc_ctx* c) {
@@ -1542,6 +1623,48 @@ extern "C" int dqmc_measure_read_host(dqmc_ctx* c, double* out) {
     (void)hipSetDevice(c->p.device);
     HIPCHK(hipStreamSynchronize(c->st));
     HIPCHK(copy_sync(c, out, selp(c, c->macc), c->macc_n * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+
+
+// ---------------------------------------------------------------------------------------------
+// time-displaced Green's functions (dqmc_hip.h; computed inside green_from_udv while td_on)
+// ---------------------------------------------------------------------------------------------
+extern "C" int dqmc_set_timedisplaced(dqmc_ctx* c, int on) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (on && !c->td_reserved) return fail(DQMC_EINVAL, "time-displaced Green's functions need a context created with dqmc_params::timedisplaced != 0");
+    c->td_on = on != 0;
+    return DQMC_OK;
+}
+extern "C" int dqmc_get_green_timedisplaced_host(dqmc_ctx* c, dqmc_cplx* g_t0, dqmc_cplx* g_0t, int* slice) {
+    if (!c || !g_t0 || !g_0t || !slice) return fail(DQMC_EINVAL, "null argument");
+    if (!c->td_reserved || c->td_slice < 0) return fail(DQMC_EINVAL, "no time-displaced Green's function has been computed");
+    (void)hipSetDevice(c->p.device);
+    HIPCHK(hipStreamSynchronize(c->st));
+    HIPCHK(hipGetLastError());
+    const size_t bytes = (size_t)c->n_g * c->n_g * sizeof(cplx);
+    HIPCHK(copy_sync(c, g_t0, selp(c, c->GT0), bytes, hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(c, g_0t, selp(c, c->G0T), bytes, hipMemcpyDeviceToHost));
+    *slice = c->td_slice;
+    return DQMC_OK;
+}
+extern "C" int dqmc_measure_timedisplaced(dqmc_ctx* c, int j) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (!c->td_reserved) return fail(DQMC_EINVAL, "context created without dqmc_params::timedisplaced");
+    if (j < 1 || j > c->n - 1) return fail(DQMC_EINVAL, "boundary index j must be in 1..n-1");
+    if (c->td_slice != c->s * j) return fail(DQMC_EINVAL, "the last time-displaced pair does not belong to boundary j");
+    (void)hipSetDevice(c->p.device);
+    shift_green_dev(c, c->GT0);              // T1 = e^{-dtau K/2} G(tau_j, 0) e^{+dtau K/2}
+    { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td(c->lc, c->hm, c->T1, c->tdacc, j); }
+    return finish(c, "dqmc_measure_timedisplaced");
+}
+extern "C" size_t dqmc_measure_td_accum_size(dqmc_ctx* c) { return c ? c->tdacc_n : 0; }
+extern "C" int dqmc_measure_td_read_host(dqmc_ctx* c, double* out) {
+    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
+    if (!c->td_reserved) return fail(DQMC_EINVAL, "context created without dqmc_params::timedisplaced");
+    (void)hipSetDevice(c->p.device);
+    HIPCHK(hipStreamSynchronize(c->st));
+    HIPCHK(copy_sync(c, out, selp(c, c->tdacc), c->tdacc_n * sizeof(double), hipMemcpyDeviceToHost));
     return DQMC_OK;
 }
 

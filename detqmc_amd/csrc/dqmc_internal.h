@@ -249,6 +249,9 @@ void launch_phi_shift(const Launch& lc, const DevModel& hm, const double* shifts
 // SX[(2L-1)^2] (re, im), SY[(2L-1)^2] (re, im)
 void launch_measure_accum(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc);
 size_t measure_accum_doubles(int N, int L);
+// time-displaced block: count[n-1], then per boundary j = 1 .. n-1 the S_X / S_Y bins of the shifted G(tau_j, 0) (dqmc_hip.h)
+void launch_measure_td(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc, int j);
+size_t measure_td_doubles(int L, int n);
 
 // ---- QR / UDT building blocks (kernels_qr.hip) ------------------------------------------------
 struct SvdProfHooks;

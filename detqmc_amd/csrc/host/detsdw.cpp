@@ -29,7 +29,7 @@ static bool same_model(const detsdw_params& a, const detsdw_params& b, bool seed
                       a.wolffClusterUpdate == b.wolffClusterUpdate && a.wolffClusterShiftUpdate == b.wolffClusterShiftUpdate &&
                       a.repeatWolffPerSweep == b.repeatWolffPerSweep && a.fermionMeasurements == b.fermionMeasurements &&
                       a.spinProposalMethod == b.spinProposalMethod && a.adaptScaleVariance == b.adaptScaleVariance &&
-                      a.repeatUpdateInSlice == b.repeatUpdateInSlice;
+                      a.repeatUpdateInSlice == b.repeatUpdateInSlice && a.timeDisplacedMeasurements == b.timeDisplacedMeasurements;
     const bool reals = a.beta == b.beta && a.dtau == b.dtau && a.c == b.c && a.u == b.u && a.lambda == b.lambda &&
                        a.txhor == b.txhor && a.txver == b.txver && a.tyhor == b.tyhor && a.tyver == b.tyver &&
                        a.mu == b.mu && a.mux == b.mux && a.muy == b.muy && a.accRatio == b.accRatio && a.cdwU == b.cdwU;
@@ -102,6 +102,8 @@ void DetSDW::normalise(detsdw_params& p, int& bcv) {
     if (p.repeatWolffPerSweep < 1) throw ParameterWrong("Parameter repeatWolffPerSweep has incorrect value");
     if (p.L % 2 != 0) throw ParameterWrong("Checker board decomposition only supported for even linear lattice sizes");
     if (p.stabilisation != 0 && p.stabilisation != 1) throw ParameterWrong("Parameter stabilisation has incorrect value");
+    if (p.timeDisplacedMeasurements && !p.fermionMeasurements)
+        throw ParameterWrong("timeDisplacedMeasurements needs fermionMeasurements");
     // createReplica (detsdwopdim.cpp:75-79)
     if (!p.has_mux_muy) { p.mux = p.mu; p.muy = p.mu; }
 }
@@ -144,6 +146,7 @@ DetSDW::DetSDW(const detsdw_params* in, int nchains, int sub_batches) {
     kp.stabilisation = p.stabilisation;
     kp.cb_none = p.cb_none ? 1 : 0;          // reference option checkerboard=false (DetSDW<CB_NONE, OPDIM>)
     kp.rng_window_per_site = uniformsPerSite();
+    kp.timedisplaced = p.timeDisplacedMeasurements ? 1 : 0;
     // result-neutral execution choices.  The pipelined update pays only while few contexts share the GPU (with more of them the
     // contexts overlap each other instead): automatic here means at most two sub-batches.
     kp.tuning = p.tuning;
@@ -233,6 +236,11 @@ void DetSDW::updateInSlice(Group& g, int k, bool thermalization) {
     if (measuring_) check(dqmc_measure_slice(g.ctx), "measure");     // updateInSliceAndMaybeMeasure (detmodel.h:1279-1285)
 }
 
+// the advance just made ended on the interior boundary tau_j = j s: it also computed G(tau_j, 0)
+void DetSDW::measureTimeDisplaced(Group& g, int j) {
+    if (measuringTD_) check(dqmc_measure_timedisplaced(g.ctx, j), "measureTimeDisplaced");
+}
+
 // detmodel.h:1333-1399
 void DetSDW::sweepDown(Group& g, bool thermalization) {
     dqmc_ctx* ctx_ = g.ctx;
@@ -242,6 +250,7 @@ void DetSDW::sweepDown(Group& g, bool thermalization) {
     }
     for (int l = n_ - 1; l >= 1; --l) {
         check(dqmc_advance(ctx_, DQMC_DOWN, l + 1), "advanceDownGreen");
+        measureTimeDisplaced(g, l);
         for (int k = l * s_; k >= (l - 1) * s_ + 1; --k) {
             updateInSlice(g, k, thermalization);
             check(dqmc_wrap(ctx_, DQMC_DOWN, k), "wrapDownGreen");
@@ -260,6 +269,7 @@ void DetSDW::sweepUp(Group& g, bool thermalization) {
             updateInSlice(g, k, thermalization);
         }
         check(dqmc_advance(ctx_, DQMC_UP, l), "advanceUpGreen");
+        measureTimeDisplaced(g, l + 1);
     }
     for (int k = (n_ - 1) * s_ + 1; k <= m_; ++k) {
         check(dqmc_wrap(ctx_, DQMC_UP, k - 1), "wrapUpGreen");
@@ -289,8 +299,16 @@ void DetSDW::sweep(bool takeMeasurements) {
     const bool fermionic = takeMeasurements && ch_[0].pars.fermionMeasurements;
     if (fermionic) for (auto& g : groups_) check(dqmc_measure_reset(g.ctx), "initMeasurements");
     measuring_ = fermionic;
-    try { forEachGroup([this](Group& g) { sweep_skeleton(g, false); }); } catch (...) { measuring_ = false; throw; }
-    measuring_ = false;
+    // the time-displaced pair is computed only during measurement sweeps: thermalisation sweeps pay nothing for it
+    measuringTD_ = fermionic && ch_[0].pars.timeDisplacedMeasurements;
+    if (measuringTD_) for (auto& g : groups_) check(dqmc_set_timedisplaced(g.ctx, 1), "dqmc_set_timedisplaced");
+    auto off = [this]() {
+        measuring_ = false;
+        if (measuringTD_) for (auto& g : groups_) (void)dqmc_set_timedisplaced(g.ctx, 0);
+        measuringTD_ = false;
+    };
+    try { forEachGroup([this](Group& g) { sweep_skeleton(g, false); }); } catch (...) { off(); throw; }
+    off();
     lastSweepDir_ = (lastSweepDir_ == Up) ? Down : Up;
     ++performedSweeps_;
     for (int b = 0; b < (int)ch_.size(); ++b) {
@@ -359,15 +377,58 @@ void DetSDW::finishFermionic(int b) {
         }
     o.pairPlusMax = pp / 9.0;
     o.pairMinusMax = pm / 9.0;
+    // G(k, tau_j) from the time-displaced bins: the same Fourier sum, one row per interior boundary
+    if (c.pars.timeDisplacedMeasurements) {
+        std::vector<double> td(dqmc_measure_td_accum_size(ctx_));
+        check(dqmc_measure_td_read_host(ctx_, td.data()), "dqmc_measure_td_read_host");
+        const int nj = n_ - 1;
+        c.greenKTauX.assign((size_t)nj * N, 0.0); c.greenKTauY.assign((size_t)nj * N, 0.0);
+        // separable: A(kx, dy) = sum_dx e^{i kx dx} S(dx, dy) first, then Re sum_dy e^{i ky dy} A(kx, dy) -- (n-1) rows per sweep
+        std::vector<double> A((size_t)L * W * 2);
+        for (int j = 1; j <= nj; ++j) {
+            const double cnt = td[j - 1];
+            if (cnt < 1.0) throw GeneralError(DQMC_EINVAL, "measurement sweep did not visit every stabilisation boundary");
+            for (int band = 0; band < 2; ++band) {
+                const double* T = &td[nj + (size_t)(j - 1) * 4 * nbins + (size_t)band * 2 * nbins];
+                for (int kx = 0; kx < L; ++kx) {
+                    const double* tx = &ex[(size_t)kx * W * 2];
+                    for (int iy = 0; iy < W; ++iy) {
+                        double re = 0.0, im = 0.0;
+                        for (int ix = 0; ix < W; ++ix) {
+                            const double sr = T[2 * (iy * W + ix)], si = T[2 * (iy * W + ix) + 1];
+                            re += tx[2 * ix] * sr - tx[2 * ix + 1] * si;
+                            im += tx[2 * ix] * si + tx[2 * ix + 1] * sr;
+                        }
+                        A[((size_t)kx * W + iy) * 2] = re; A[((size_t)kx * W + iy) * 2 + 1] = im;
+                    }
+                }
+                std::vector<double>& out = band == 0 ? c.greenKTauX : c.greenKTauY;
+                for (int ksite = 0; ksite < N; ++ksite) {
+                    const double* ty = &ey[(size_t)(ksite / L) * W * 2];
+                    const double* a = &A[(size_t)(ksite % L) * W * 2];
+                    double v = 0.0;
+                    for (int iy = 0; iy < W; ++iy) v += ty[2 * iy] * a[2 * iy] - ty[2 * iy + 1] * a[2 * iy + 1];
+                    out[(size_t)(j - 1) * N + ksite] = v / (2.0 * N * cnt);
+                }
+            }
+        }
+    }
     o.fermionic_valid = 1;
+}
+
+void DetSDW::getTauGrid(double* out) const {
+    for (int j = 1; j <= n_ - 1; ++j) out[j - 1] = j * s_ * ch_[0].pars.dtau;
 }
 
 void DetSDW::getObservableVector(int which, double* out, int b) const {
     const Chain& c = ch_[b];
     if (!c.obs.fermionic_valid) throw GeneralError(DQMC_EINVAL, "no fermionic measurement has been taken");
     const std::vector<double>* v = which == DETSDW_OBS_KOCCX ? &c.kOccX : which == DETSDW_OBS_KOCCY ? &c.kOccY
-                                 : which == DETSDW_OBS_PAIRPLUS ? &c.pairPlus : which == DETSDW_OBS_PAIRMINUS ? &c.pairMinus : nullptr;
+                                 : which == DETSDW_OBS_PAIRPLUS ? &c.pairPlus : which == DETSDW_OBS_PAIRMINUS ? &c.pairMinus
+                                 : which == DETSDW_OBS_GREENKTAU_X ? &c.greenKTauX : which == DETSDW_OBS_GREENKTAU_Y ? &c.greenKTauY : nullptr;
     if (!v) throw ParameterWrong("unknown observable vector");
+    if ((which == DETSDW_OBS_GREENKTAU_X || which == DETSDW_OBS_GREENKTAU_Y) && !c.pars.timeDisplacedMeasurements)
+        throw ParameterWrong("greenKTauX / greenKTauY need timeDisplacedMeasurements");
     std::memcpy(out, v->data(), v->size() * sizeof(double));
 }
 
@@ -863,6 +924,10 @@ extern "C" int detsdw_get_observables(detsdw_replica* r, detsdw_observables* out
 }
 extern "C" int detsdw_get_observable_vector(detsdw_replica* r, int which, double* out) {
     RGUARD(r->impl->getObservableVector(which, out, r->sel))
+}
+extern "C" int detsdw_get_tau_grid(detsdw_replica* r, double* out) {
+    if (!out) { g_host_err = "null argument"; return DQMC_EINVAL; }
+    RGUARD(r->impl->getTauGrid(out))
 }
 extern "C" int detsdw_get_phi(detsdw_replica* r, double* phi) { RGUARD(r->impl->getPhi(phi, r->sel)) }
 extern "C" int detsdw_set_phi(detsdw_replica* r, const double* phi) { RGUARD(r->impl->setPhi(phi, r->sel)) }

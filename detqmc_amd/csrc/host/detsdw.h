@@ -55,6 +55,7 @@ public:
     void getInfo(detsdw_info& out, int b = 0);
     void getObservables(detsdw_observables& out, int b = 0) const { out = ch_[b].obs; }
     void getObservableVector(int which, double* out, int b = 0) const;
+    void getTauGrid(double* out) const;
     void getPhi(double* phi, int b = 0);
     void setPhi(const double* phi, int b = 0);
     void getCdwl(int32_t* cdwl, int b = 0);
@@ -84,6 +85,7 @@ private:
         double angleDelta = 0.0, scaleDelta = 0.1;          // AdjustmentData::InitialAngleDelta / InitialScaleDelta (detsdwopdim.h:490-491)
         detsdw_observables obs{};
         std::vector<double> kOccX, kOccY, pairPlus, pairMinus;
+        std::vector<double> greenKTauX, greenKTauY;         // (n-1) x N, row j-1 = tau_j (timeDisplacedMeasurements)
         Chain(const detsdw_params& p) : pars(p), rng(p.rngSeed, (uint32_t)p.simindex + 1u) {}   // detqmc.h:181
     };
     std::vector<Chain> ch_;
@@ -109,6 +111,8 @@ private:
     void measureBosonic(Chain& c, bool descending);
     void finishFermionic(int b);
     bool measuring_ = false;          // measure(k) after the updates of slice k (updateInSliceAndMaybeMeasure)
+    bool measuringTD_ = false;        // ... and G(tau_j, 0) after every interior advance (timeDisplacedMeasurements)
+    void measureTimeDisplaced(Group& g, int j);
     void sweepDown(Group& g, bool thermalization);
     void sweepUp(Group& g, bool thermalization);
     void updateInSlice(Group& g, int k, bool thermalization);

@@ -54,6 +54,7 @@ class SDWParams:
     wolffClusterShiftUpdate: bool = False
     repeatWolffPerSweep: int = 1
     fermionMeasurements: bool = False    # sweep(True) also takes the G-dependent observables (reference default: on)
+    timeDisplacedMeasurements: bool = False   # ... and G(k, tau_j) at the interior stabilisation boundaries (needs fermionMeasurements)
     globalUpdateInterval: int = 100
     phi2bosons: bool = False
     cdwU: float = 0.0
@@ -96,12 +97,14 @@ class KernelContext:
     def __init__(self, opdim, L, m, s, dtau, delaySteps=16, bc="pbc", weakZflux=False, r=-1.0, c=3.0, u=1.0,
                  lambda_=1.0, txhor=-1.0, txver=-0.5, tyhor=0.5, tyver=1.0, mux=-0.5, muy=-0.5,
                  accRatio=0.5, phi2bosons=False, device=0, stabilisation="svd", checkerboard=True, nchains=1, cdwU=0.0,
-                 pipeline=0, qrVariant=0, greenVariant=0, maxJacobiSweeps=0, proposalBudget=0, rngWindowPerSite=0, decideThreads=0):
+                 pipeline=0, qrVariant=0, greenVariant=0, maxJacobiSweeps=0, proposalBudget=0, rngWindowPerSite=0, decideThreads=0,
+                 timeDisplaced=False):
         self.lib = load()
         p = _lib.dqmc_params(opdim=opdim, L=L, m=m, s=s, delaySteps=delaySteps, bc=BC[bc],
                              weakZflux=int(weakZflux), phi2bosons=int(phi2bosons), device=device,
                              stabilisation=STABILISATION[stabilisation], cb_none=int(not checkerboard), dtau=dtau, r=r, c=c, u=u, lambda_=lambda_, txhor=txhor, txver=txver,
                              tyhor=tyhor, tyver=tyver, mux=mux, muy=muy, accRatio=accRatio, cdwU=cdwU, rng_window_per_site=int(rngWindowPerSite),
+                             timedisplaced=int(timeDisplaced),
                              tuning=_tuning(pipeline, qrVariant, greenVariant, maxJacobiSweeps, proposalBudget, decideThreads))
         h = C.c_void_p()
         check(self.lib.dqmc_create_batch(C.byref(p), nchains, C.byref(h)))
@@ -128,6 +131,27 @@ class KernelContext:
         g = np.zeros((self.ng, self.ng), dtype=np.complex128, order="F")
         check(self.lib.dqmc_shift_green_symmetric_host(self.h, g.ctypes.data))
         return g
+
+    def set_timedisplaced(self, on=True):
+        """while on, every advance that ends on an interior boundary also computes G(tau,0) and G(0,tau) (needs timeDisplaced=True
+        at construction)"""
+        check(self.lib.dqmc_set_timedisplaced(self.h, int(on)))
+
+    def green_timedisplaced(self):
+        """(slice, G(tau,0), G(0,tau)) of the last interior advance, selected chain"""
+        gt0 = np.zeros((self.ng, self.ng), dtype=np.complex128, order="F")
+        g0t = np.zeros_like(gt0)
+        sl = C.c_int(-1)
+        check(self.lib.dqmc_get_green_timedisplaced_host(self.h, gt0.ctypes.data, g0t.ctypes.data, C.byref(sl)))
+        return sl.value, gt0, g0t
+
+    def measure_timedisplaced(self, j):
+        check(self.lib.dqmc_measure_timedisplaced(self.h, j))
+
+    def measure_td_read(self):
+        out = np.zeros(self.lib.dqmc_measure_td_accum_size(self.h))
+        check(self.lib.dqmc_measure_td_read_host(self.h, out.ctypes.data_as(_lib._DP)))
+        return out
 
     def select_chain(self, b):
         """host-buffer calls (fields, G, sv, UdV, uniforms, update state, ...) refer to chain b from now on"""
@@ -345,7 +369,7 @@ def _host_params(pars: SDWParams):
         wolffClusterUpdate=int(pars.wolffClusterUpdate), wolffClusterShiftUpdate=int(pars.wolffClusterShiftUpdate),
         repeatWolffPerSweep=int(pars.repeatWolffPerSweep), fermionMeasurements=int(pars.fermionMeasurements),
         spinProposalMethod=SPIN_PROPOSAL[pars.spinProposalMethod], adaptScaleVariance=int(pars.adaptScaleVariance),
-        repeatUpdateInSlice=int(pars.repeatUpdateInSlice),
+        repeatUpdateInSlice=int(pars.repeatUpdateInSlice), timeDisplacedMeasurements=int(pars.timeDisplacedMeasurements),
         tuning=_tuning(pars.pipeline, pars.qrVariant, pars.greenVariant, pars.maxJacobiSweeps, pars.proposalBudget, pars.decideThreads))
 
 
@@ -414,11 +438,19 @@ class DetSDW:
         return o
 
     def observable_vector(self, name):
-        """'kOccX', 'kOccY', 'pairPlus', 'pairMinus' of the last sweep(True) with fermionMeasurements"""
+        """'kOccX', 'kOccY', 'pairPlus', 'pairMinus' of the last sweep(True) with fermionMeasurements (length N); 'greenKTauX',
+        'greenKTauY' with timeDisplacedMeasurements: shape (n-1, N), row j-1 = tau_j of tau_grid()"""
         self._sel()
-        out = np.zeros(self.info.N)
-        which = {"kOccX": 0, "kOccY": 1, "pairPlus": 2, "pairMinus": 3}[name]
+        info = self.info
+        which = {"kOccX": 0, "kOccY": 1, "pairPlus": 2, "pairMinus": 3, "greenKTauX": 4, "greenKTauY": 5}[name]
+        out = np.zeros((info.n - 1, info.N) if which >= 4 else info.N)
         check(self.lib.detsdw_get_observable_vector(self.h, which, out.ctypes.data_as(_lib._DP)), host=True)
+        return out
+
+    def tau_grid(self):
+        """tau_j = j s dtau, j = 1 .. n-1: the rows of greenKTauX / greenKTauY"""
+        out = np.zeros(self.info.n - 1)
+        check(self.lib.detsdw_get_tau_grid(self.h, out.ctypes.data_as(_lib._DP)), host=True)
         return out
 
     @property

@@ -60,7 +60,8 @@ typedef struct detsdw_params {
                                          (src/detsdwparams.h:40-42, src/detsdwopdim.cpp:2447-2470) */
     int32_t adaptScaleVariance;       /* adapt scaleDelta during thermalization (src/detsdwparams.h:43) */
     int32_t repeatUpdateInSlice;      /* passes of local updates per time slice and sweep, 0 is read as 1 (src/detsdwparams.h:90) */
-    int32_t reserved_model;
+    int32_t timeDisplacedMeasurements; /* 1 (needs fermionMeasurements): a measurement sweep also takes G(k, tau_j) at the interior
+                                         stabilisation boundaries tau_j = j s dtau, j = 1 .. n-1 (DETSDW_OBS_GREENKTAU_X / _Y) */
     dqmc_tuning tuning;               /* result-neutral execution choices handed to every kernel context (dqmc_hip.h); all zero =
                                          automatic.  With pipeline = 0 the host layer switches the pipelined update on only for
                                          handles of at most two kernel contexts (more contexts overlap each other instead) */
@@ -107,7 +108,8 @@ typedef struct detsdw_observables {
     double pairPlusMax, pairMinusMax;   /* :986-1002 */
     double occDiffSq;                   /* :866-897, :1013 */
 } detsdw_observables;
-enum { DETSDW_OBS_KOCCX = 0, DETSDW_OBS_KOCCY = 1, DETSDW_OBS_PAIRPLUS = 2, DETSDW_OBS_PAIRMINUS = 3 };
+enum { DETSDW_OBS_KOCCX = 0, DETSDW_OBS_KOCCY = 1, DETSDW_OBS_PAIRPLUS = 2, DETSDW_OBS_PAIRMINUS = 3,
+       DETSDW_OBS_GREENKTAU_X = 4, DETSDW_OBS_GREENKTAU_Y = 5 };
 
 /* createReplica (src/detsdwopdim.cpp:49-84) + DetSDW ctor (:158-361): checks parameters, seeds the
  * RNG with (rngSeed, simindex + 1) (src/detqmc.h:181), draws the random field, builds UdV storage and
@@ -137,8 +139,12 @@ int detsdw_sweep_thermalization(detsdw_replica* r);
 
 int detsdw_get_info(detsdw_replica* r, detsdw_info* out);
 int detsdw_get_observables(detsdw_replica* r, detsdw_observables* out);
-/* N-vectors of the last measurement sweep: kOccX, kOccY (site index = k-vector, :616-659, :937-941), pairPlus, pairMinus */
+/* N-vectors of the last measurement sweep: kOccX, kOccY (site index = k-vector, :616-659, :937-941), pairPlus, pairMinus.
+ * With timeDisplacedMeasurements: greenKTauX / greenKTauY, (n-1) x N (row j-1 = tau_j, column = k-vector as for kOcc):
+ *   G_band(k, tau_j) = Re (1/2N) sum_spin sum_{a,b} e^{i k (r_a - r_b)} [e^{-dtau K/2} G(tau_j, 0) e^{+dtau K/2}]_{(a,band,spin),(b,band,spin)} */
 int detsdw_get_observable_vector(detsdw_replica* r, int which, double* out);
+/* tau_j = j s dtau of the rows of greenKTauX / Y, j = 1 .. n-1: out[n-1] */
+int detsdw_get_tau_grid(detsdw_replica* r, double* out);
 /* phi in the reference layout (N, OPDIM, m+1) column-major */
 int detsdw_get_phi(detsdw_replica* r, double* phi);
 int detsdw_set_phi(detsdw_replica* r, const double* phi);      /* also rebuilds UdV storage and G */

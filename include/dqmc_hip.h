@@ -100,7 +100,9 @@ typedef struct dqmc_params {
                                       with repeatUpdateInSlice = 1 can consume at most (opdim + 1, + 2 with cdwU).  Callers that use
                                       dqmc_update_slice_ex with more passes or the rotate / scale proposals (whose Gaussian draws consume
                                       a variable number) size it: repeat x (opdim + 1) resp. repeat x 8 (+ 2 with cdwU) */
-    int32_t reserved_model;
+    int32_t timedisplaced; /* != 0: reserve the per-chain buffers of the time-displaced Green's functions and their accumulator
+                              block (SDW model only); dqmc_set_timedisplaced switches the computation on and off.  0: nothing is
+                              reserved, nothing changes */
     dqmc_tuning tuning;   /* all zero = automatic */
 } dqmc_params;
 
@@ -263,6 +265,29 @@ int dqmc_measure_reset(dqmc_ctx* ctx);
 int dqmc_measure_slice(dqmc_ctx* ctx);
 size_t dqmc_measure_accum_size(dqmc_ctx* ctx);
 int dqmc_measure_read_host(dqmc_ctx* ctx, double* out);
+/* ---- time-displaced Green's functions ----------------------------------------------------------
+ * At an interior stabilisation boundary tau_j = j s (j = 1 .. n-1) the advance holds B(tau,0) = U_r D_r V_r^H and
+ * B(beta,tau) = U_l D_l V_l^H at once.  With the scales split into their parts > 1 and <= 1 and
+ *   Z = Drmax^-1 (U_r^H V_l) Dlmax^-1 + Drmin (V_r^H U_l) Dlmin
+ * (the matrix the QR mode inverts for G anyway):
+ *   G(tau)   =  [V_l Dlmax^-1] Z^-1 [Drmax^-1 U_r^H]
+ *   G(tau,0) =  [B(tau,0)^-1 + B(beta,tau)]^-1 =  [V_l Dlmax^-1] Z^-1 [Drmin V_r^H]
+ *   G(0,tau) = -[B(tau,0) + B(beta,tau)^-1]^-1 = -[U_l Dlmin] Z^-1 [Drmax^-1 U_r^H]
+ * Needs a context created with dqmc_params::timedisplaced != 0 (DQMC_EINVAL otherwise).  While switched on, every
+ * dqmc_advance that ends on an interior boundary also fills G(tau,0) and G(0,tau) of all chains: QR mode reuses the
+ * factorisation of Z (two more triangular solves or Q applications and two GEMMs); SVD mode leaves G on its own path and
+ * builds and factorises the split Z after it.  Switched off, nothing is computed. */
+int dqmc_set_timedisplaced(dqmc_ctx* ctx, int on);
+/* the last pair computed, selected chain; *slice = the tau slice s j it belongs to.  DQMC_EINVAL if none was computed yet */
+int dqmc_get_green_timedisplaced_host(dqmc_ctx* ctx, dqmc_cplx* g_t0, dqmc_cplx* g_0t, int* slice);
+/* bins the last pair's e^{-dtau K/2} G(tau_j,0) e^{+dtau K/2} (all chains; the pair must belong to boundary j) into a block of its
+ * own.  Layout (doubles, dqmc_measure_td_accum_size of them): count[n-1] (samples per boundary), then for j = 1 .. n-1 the bins
+ * S_X[(2L-1)^2] and S_Y[(2L-1)^2] as (re, im), defined like those of dqmc_measure_slice (spin summed, bin index
+ * (dy + L-1) (2L-1) + (dx + L-1)), at offset (n-1) + (j-1) 4 (2L-1)^2.  dqmc_measure_reset clears it as well. */
+int dqmc_measure_timedisplaced(dqmc_ctx* ctx, int j);
+size_t dqmc_measure_td_accum_size(dqmc_ctx* ctx);       /* 0 without the reservation */
+int dqmc_measure_td_read_host(dqmc_ctx* ctx, double* out);
+
 /* set_exchange_parameter_value (detsdwopdim.cpp:5195-5197): r only enters the bosonic action */
 int dqmc_set_exchange_parameter(dqmc_ctx* ctx, double r);
 
