@@ -145,6 +145,19 @@ class KernelContext:
         check(self.lib.dqmc_get_green_timedisplaced_host(self.h, gt0.ctypes.data, g0t.ctypes.data, C.byref(sl)))
         return sl.value, gt0, g0t
 
+    def measure_reset(self):
+        check(self.lib.dqmc_measure_reset(self.h))
+
+    def measure_slice(self):
+        """shiftGreenSymmetric of the current G and one sample added to every equal-time accumulator, all chains"""
+        check(self.lib.dqmc_measure_slice(self.h))
+
+    def measure_read(self):
+        """the selected chain's accumulators: [greenK0, greenLocal, occDiffSq, count, pairPlus[N], pairMinus[N], S_X, S_Y]"""
+        out = np.zeros(self.lib.dqmc_measure_accum_size(self.h))
+        check(self.lib.dqmc_measure_read_host(self.h, out.ctypes.data_as(_lib._DP)))
+        return out
+
     def measure_timedisplaced(self, j):
         check(self.lib.dqmc_measure_timedisplaced(self.h, j))
 
