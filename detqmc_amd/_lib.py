@@ -194,6 +194,9 @@ SYMBOLS = [
     ("dqmc_measure_timedisplaced", C.c_int, [_P, C.c_int]),
     ("dqmc_measure_td_accum_size", C.c_size_t, [_P]),
     ("dqmc_measure_td_read_host", C.c_int, [_P, _DP]),
+    ("dqmc_measure_timedisplaced_pair", C.c_int, [_P, C.c_int]),
+    ("dqmc_measure_td_pair_accum_size", C.c_size_t, [_P]),
+    ("dqmc_measure_td_pair_read_host", C.c_int, [_P, _DP]),
     ("dqmc_profile_enable", C.c_int, [_P, C.c_int]),
     ("dqmc_profile_read", C.c_int, [_P, C.POINTER(dqmc_profile)]),
     ("detsdw_create", C.c_int, [C.POINTER(detsdw_params), C.POINTER(_P)]),

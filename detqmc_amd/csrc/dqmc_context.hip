@@ -78,6 +78,8 @@ struct dqmc_ctx {
     double* td_sv = nullptr;                                  // SVD mode: log-det output of the LU / QR route (c->sv keeps the Jacobi values)
     double* tdacc = nullptr;                                  // accumulator block of dqmc_measure_timedisplaced (kernels_measure.hip)
     size_t tdacc_n = 0;
+    double* tdpacc = nullptr;                                 // accumulator block of dqmc_measure_timedisplaced_pair (timedisplaced == 2)
+    size_t tdpacc_n = 0;
     SvdWork sw{};
     double hub_e_m2a = 1.0, hub_e_p2a = 1.0;  // Hubbard: exp(-+2 alpha) of weightRatioSingleFlip (dethubbard.cpp:866-867)
     int stab = 0;                       // DQMC_STAB_SVD / DQMC_STAB_QR
@@ -695,6 +697,7 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
     A_(salloc(c, &c->shift_buf, (size_t)c->nb * 3));
     c->macc_n = measure_accum_doubles(N, p->L);
     A_(dalloc(c, &c->macc, c->macc_n));
+    if (p->timedisplaced < 0 || p->timedisplaced > 2) return fail(DQMC_EINVAL, "timedisplaced must be 0, 1 or 2");
     if (p->timedisplaced) {                 // behind every other buffer: the layout of a context without them is unchanged
         if (p->model != DQMC_MODEL_SDW) return fail(DQMC_EINVAL, "timedisplaced: SDW model only");
         c->td_reserved = true;
@@ -702,6 +705,10 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
         if (c->stab != DQMC_STAB_QR) { A_(alloc_qr_work(c)); A_(dalloc(c, &c->td_sv, (size_t)ng)); }
         c->tdacc_n = measure_td_doubles(p->L, c->n);
         A_(dalloc(c, &c->tdacc, c->tdacc_n));
+        if (p->timedisplaced == 2) {        // behind the block above: a context with timedisplaced == 1 is laid out as before
+            c->tdpacc_n = measure_td_pair_doubles(N, c->n);
+            A_(dalloc(c, &c->tdpacc, c->tdpacc_n));
+        }
     }
     A_(arena_commit(c));                    // from here on the per-chain pointers are real (chain 0) addresses, zero filled
 #undef A_
@@ -1603,6 +1610,8 @@ extern "C" int dqmc_measure_reset(dqmc_ctx* c) {
     for (int b = 0; b < c->nb; ++b) HIPCHK(hipMemsetAsync(chainp(c, c->macc, b), 0, c->macc_n * sizeof(double), c->st));
     if (c->td_reserved)
         for (int b = 0; b < c->nb; ++b) HIPCHK(hipMemsetAsync(chainp(c, c->tdacc, b), 0, c->tdacc_n * sizeof(double), c->st));
+    if (c->tdpacc_n)
+        for (int b = 0; b < c->nb; ++b) HIPCHK(hipMemsetAsync(chainp(c, c->tdpacc, b), 0, c->tdpacc_n * sizeof(double), c->st));
     return DQMC_OK;
 }
 extern "C" int dqmc_measure_slice(dqmc_ctx* c) {
@@ -1665,6 +1674,27 @@ extern "C" int dqmc_measure_td_read_host(dqmc_ctx* c, double* out) {
     (void)hipSetDevice(c->p.device);
     HIPCHK(hipStreamSynchronize(c->st));
     HIPCHK(copy_sync(c, out, selp(c, c->tdacc), c->tdacc_n * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+// pairing correlators of the same shifted G(tau_j, 0).  T1 is scratch of many other calls, so the shift is redone here and not
+// carried over from a dqmc_measure_timedisplaced(j) that may have come before
+extern "C" int dqmc_measure_timedisplaced_pair(dqmc_ctx* c, int j) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (!c->tdpacc_n) return fail(DQMC_EINVAL, "context created without dqmc_params::timedisplaced == 2");
+    if (j < 1 || j > c->n - 1) return fail(DQMC_EINVAL, "boundary index j must be in 1..n-1");
+    if (c->td_slice != c->s * j) return fail(DQMC_EINVAL, "the last time-displaced pair does not belong to boundary j");
+    (void)hipSetDevice(c->p.device);
+    shift_green_dev(c, c->GT0);              // T1 = e^{-dtau K/2} G(tau_j, 0) e^{+dtau K/2}
+    { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td_pair(c->lc, c->hm, c->T1, c->tdpacc, j); }
+    return finish(c, "dqmc_measure_timedisplaced_pair");
+}
+extern "C" size_t dqmc_measure_td_pair_accum_size(dqmc_ctx* c) { return c ? c->tdpacc_n : 0; }
+extern "C" int dqmc_measure_td_pair_read_host(dqmc_ctx* c, double* out) {
+    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
+    if (!c->tdpacc_n) return fail(DQMC_EINVAL, "context created without dqmc_params::timedisplaced == 2");
+    (void)hipSetDevice(c->p.device);
+    HIPCHK(hipStreamSynchronize(c->st));
+    HIPCHK(copy_sync(c, out, selp(c, c->tdpacc), c->tdpacc_n * sizeof(double), hipMemcpyDeviceToHost));
     return DQMC_OK;
 }
 

@@ -252,6 +252,9 @@ size_t measure_accum_doubles(int N, int L);
 // time-displaced block: count[n-1], then per boundary j = 1 .. n-1 the S_X / S_Y bins of the shifted G(tau_j, 0) (dqmc_hip.h)
 void launch_measure_td(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc, int j);
 size_t measure_td_doubles(int L, int n);
+// time-displaced pairing block: count[n-1], then per boundary j = 1 .. n-1 the sums over B of Re T+(B (+) d, B) [N] and Re T-(B (+) d, B) [N]
+void launch_measure_td_pair(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc, int j);
+size_t measure_td_pair_doubles(int N, int n);
 
 // ---- QR / UDT building blocks (kernels_qr.hip) ------------------------------------------------
 struct SvdProfHooks;

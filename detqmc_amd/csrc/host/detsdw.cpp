@@ -102,6 +102,8 @@ void DetSDW::normalise(detsdw_params& p, int& bcv) {
     if (p.repeatWolffPerSweep < 1) throw ParameterWrong("Parameter repeatWolffPerSweep has incorrect value");
     if (p.L % 2 != 0) throw ParameterWrong("Checker board decomposition only supported for even linear lattice sizes");
     if (p.stabilisation != 0 && p.stabilisation != 1) throw ParameterWrong("Parameter stabilisation has incorrect value");
+    if (p.timeDisplacedMeasurements < 0 || p.timeDisplacedMeasurements > 2)
+        throw ParameterWrong("Parameter timeDisplacedMeasurements has incorrect value");
     if (p.timeDisplacedMeasurements && !p.fermionMeasurements)
         throw ParameterWrong("timeDisplacedMeasurements needs fermionMeasurements");
     // createReplica (detsdwopdim.cpp:75-79)
@@ -146,7 +148,7 @@ DetSDW::DetSDW(const detsdw_params* in, int nchains, int sub_batches) {
     kp.stabilisation = p.stabilisation;
     kp.cb_none = p.cb_none ? 1 : 0;          // reference option checkerboard=false (DetSDW<CB_NONE, OPDIM>)
     kp.rng_window_per_site = uniformsPerSite();
-    kp.timedisplaced = p.timeDisplacedMeasurements ? 1 : 0;
+    kp.timedisplaced = p.timeDisplacedMeasurements;      // 1: G(tau_j, 0) and its bins, 2: and the pairing block
     // result-neutral execution choices.  The pipelined update pays only while few contexts share the GPU (with more of them the
     // contexts overlap each other instead): automatic here means at most two sub-batches.
     kp.tuning = p.tuning;
@@ -238,7 +240,9 @@ void DetSDW::updateInSlice(Group& g, int k, bool thermalization) {
 
 // the advance just made ended on the interior boundary tau_j = j s: it also computed G(tau_j, 0)
 void DetSDW::measureTimeDisplaced(Group& g, int j) {
-    if (measuringTD_) check(dqmc_measure_timedisplaced(g.ctx, j), "measureTimeDisplaced");
+    if (!measuringTD_) return;
+    check(dqmc_measure_timedisplaced(g.ctx, j), "measureTimeDisplaced");
+    if (ch_[0].pars.timeDisplacedMeasurements == 2) check(dqmc_measure_timedisplaced_pair(g.ctx, j), "measureTimeDisplacedPair");
 }
 
 // detmodel.h:1333-1399
@@ -413,6 +417,26 @@ void DetSDW::finishFermionic(int b) {
             }
         }
     }
+    // time-displaced pairing correlators: translation average (1 / N) and sample count; the q = 0 sums are the plain row sums
+    if (c.pars.timeDisplacedMeasurements == 2) {
+        std::vector<double> tp(dqmc_measure_td_pair_accum_size(ctx_));
+        check(dqmc_measure_td_pair_read_host(ctx_, tp.data()), "dqmc_measure_td_pair_read_host");
+        const int nj = n_ - 1;
+        c.pairPlusTau.assign((size_t)nj * N, 0.0); c.pairMinusTau.assign((size_t)nj * N, 0.0);
+        c.pairPlusTauQ0.assign(nj, 0.0); c.pairMinusTauQ0.assign(nj, 0.0);
+        for (int j = 1; j <= nj; ++j) {
+            const double cnt = tp[j - 1];
+            if (cnt < 1.0) throw GeneralError(DQMC_EINVAL, "measurement sweep did not visit every stabilisation boundary");
+            const double* T = &tp[nj + (size_t)(j - 1) * 2 * N];
+            double qp = 0.0, qm = 0.0;
+            for (int d = 0; d < N; ++d) {
+                const double vp = T[d] / (double(N) * cnt), vm = T[N + d] / (double(N) * cnt);
+                c.pairPlusTau[(size_t)(j - 1) * N + d] = vp; c.pairMinusTau[(size_t)(j - 1) * N + d] = vm;
+                qp += vp; qm += vm;
+            }
+            c.pairPlusTauQ0[j - 1] = qp; c.pairMinusTauQ0[j - 1] = qm;
+        }
+    }
     o.fermionic_valid = 1;
 }
 
@@ -425,10 +449,15 @@ void DetSDW::getObservableVector(int which, double* out, int b) const {
     if (!c.obs.fermionic_valid) throw GeneralError(DQMC_EINVAL, "no fermionic measurement has been taken");
     const std::vector<double>* v = which == DETSDW_OBS_KOCCX ? &c.kOccX : which == DETSDW_OBS_KOCCY ? &c.kOccY
                                  : which == DETSDW_OBS_PAIRPLUS ? &c.pairPlus : which == DETSDW_OBS_PAIRMINUS ? &c.pairMinus
-                                 : which == DETSDW_OBS_GREENKTAU_X ? &c.greenKTauX : which == DETSDW_OBS_GREENKTAU_Y ? &c.greenKTauY : nullptr;
+                                 : which == DETSDW_OBS_GREENKTAU_X ? &c.greenKTauX : which == DETSDW_OBS_GREENKTAU_Y ? &c.greenKTauY
+                                 : which == DETSDW_OBS_PAIRPLUSTAU ? &c.pairPlusTau : which == DETSDW_OBS_PAIRMINUSTAU ? &c.pairMinusTau
+                                 : which == DETSDW_OBS_PAIRPLUSTAU_Q0 ? &c.pairPlusTauQ0 : which == DETSDW_OBS_PAIRMINUSTAU_Q0 ? &c.pairMinusTauQ0
+                                 : nullptr;
     if (!v) throw ParameterWrong("unknown observable vector");
     if ((which == DETSDW_OBS_GREENKTAU_X || which == DETSDW_OBS_GREENKTAU_Y) && !c.pars.timeDisplacedMeasurements)
         throw ParameterWrong("greenKTauX / greenKTauY need timeDisplacedMeasurements");
+    if (which >= DETSDW_OBS_PAIRPLUSTAU && which <= DETSDW_OBS_PAIRMINUSTAU_Q0 && c.pars.timeDisplacedMeasurements != 2)
+        throw ParameterWrong("pairPlusTau / pairMinusTau need timeDisplacedMeasurements = 2");
     std::memcpy(out, v->data(), v->size() * sizeof(double));
 }
 

@@ -197,3 +197,80 @@ void launch_measure_td(const Launch& lc, const DevModel& hm, const cplx* gs, dou
     else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_td<2>), grid, dim3(256), 0, lc.st, hm, gs, acc, j, lc.cs);
     else hipLaunchKernelGGL((k_measure_td<3>), grid, dim3(256), 0, lc.st, hm, gs, acc, j, lc.cs);
 }
+
+// Time-displaced pairing block (dqmc_measure_timedisplaced_pair): with gs = e^{-dtau K/2} G(tau_j, 0) e^{+dtau K/2} and the P(b1, b2) of
+// role 2 above (:695-715) evaluated on gs for EVERY site pair (A, B),
+//   T+(A, B) = -4 [P(X,X) + P(X,Y) + P(Y,X) + P(Y,Y)],   T-(A, B) = -4 [P(X,X) - P(X,Y) - P(Y,X) + P(Y,Y)],
+// the block of boundary j receives  sum_B Re T+-(B (+) d, B)  for the N periodic site differences d = (dx, dy), bin dy L + dx (the 1 / N of
+// the translation average is left to the reader of the block).  A pair (A, B) needs the 4 x 4 band-spin elements gs(A bs1; B bs2), each
+// exactly once, so one launch streams gs once.  For OPDIM < 3 only the (XUP, YDOWN) sector e_rc = gs(A + N r; B + N c) is stored, the
+// (XDOWN, YUP) sector is its conjugate and the mixed sectors vanish (GreenAccess), which leaves
+//   P(X,X) = -|e_00|^2,  P(X,Y) = |e_01|^2,  P(Y,X) = |e_10|^2,  P(Y,Y) = -|e_11|^2:  four loads per pair instead of sixteen.
+// Shape: a workgroup owns 32 consecutive bins; thread (part, bin) walks the sites B = part, part + 8, ... in this order, so the 32 lanes
+// of a half wave read consecutive rows A of one column (runs of L elements between the periodic wraps).  The eight partial sums of a bin
+// meet in LDS and ONE thread adds them in the order part = 0 .. 7: one writer per accumulator, fixed order, reproducible bit for bit.
+size_t measure_td_pair_doubles(int N, int n) { return (size_t)(n - 1) * (1 + 2 * (size_t)N); }
+
+#define TDP_BINS 32
+#define TDP_PARTS 8
+template<int OPDIM>
+__global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_td_pair(DevModel dm, const cplx* __restrict__ gs, double* __restrict__ acc, int j, size_t cs) {
+    CHAIN(gs); CHAIN(acc);
+    __shared__ double red[2][TDP_PARTS][TDP_BINS];
+    const int N = dm.N, L = dm.L, tid = threadIdx.x;
+    const size_t ng = (size_t)dm.ng;
+    const int lb = tid % TDP_BINS, part = tid / TDP_BINS;
+    const int d = blockIdx.x * TDP_BINS + lb;
+    const bool valid = d < N;
+    const int dx = valid ? d % L : 0, dy = valid ? d / L : 0;
+    double tp = 0.0, tm = 0.0;
+    if (valid) {
+        int bx = part % L, by = part / L;                   // site B = part + 8 i, kept as (bx, by)
+        const int stepx = TDP_PARTS % L, stepy = TDP_PARTS / L;
+        for (int B = part; B < N; B += TDP_PARTS) {
+            int ax = bx + dx, ay = by + dy;
+            if (ax >= L) ax -= L;
+            if (ay >= L) ay -= L;
+            const cplx* p = gs + (size_t)B * ng + (size_t)(ay * L + ax);
+            auto abs2 = [](cplx v) { return v.x * v.x + v.y * v.y; };
+            if (OPDIM == 3) {
+                // e[bs1][bs2], BandSpin XUP = 0, YDOWN = 1, XDOWN = 2, YUP = 3
+                cplx e[4][4];
+#pragma unroll
+                for (int c2 = 0; c2 < 4; ++c2)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) e[r][c2] = p[(size_t)c2 * N * ng + (size_t)r * N];
+                auto re_mul = [](cplx a, cplx b) { return a.x * b.x - a.y * b.y; };
+                // Re P(b1, b2) with (dn1, up1) = band-spin rows of band b1, (up2, dn2) = band-spin columns of band b2
+                auto P = [&](int dn1, int up1, int up2, int dn2) { return re_mul(e[dn1][up2], e[up1][dn2]) - re_mul(e[dn1][dn2], e[up1][up2]); };
+                const double pxx = P(2, 0, 0, 2), pxy = P(2, 0, 3, 1), pyx = P(1, 3, 0, 2), pyy = P(1, 3, 3, 1);
+                tp += -4.0 * (((pxx + pxy) + pyx) + pyy);
+                tm += -4.0 * (((pxx - pxy) - pyx) + pyy);
+            } else {
+                const cplx e00 = p[0], e10 = p[N], e01 = p[(size_t)N * ng], e11 = p[(size_t)N * ng + N];
+                const double pxx = -abs2(e00), pxy = abs2(e01), pyx = abs2(e10), pyy = -abs2(e11);
+                tp += -4.0 * (((pxx + pxy) + pyx) + pyy);
+                tm += -4.0 * (((pxx - pxy) - pyx) + pyy);
+            }
+            bx += stepx; by += stepy;
+            if (bx >= L) { bx -= L; ++by; }
+        }
+    }
+    red[0][part][lb] = tp;
+    red[1][part][lb] = tm;
+    __syncthreads();
+    if (part < 2 && valid) {                                // part 0 writes C+ of its bin, part 1 writes C-
+        double s = red[part][0][lb];
+#pragma unroll
+        for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
+        acc[(dm.n - 1) + (size_t)(j - 1) * 2 * N + (size_t)part * N + d] += s;
+    }
+    if (blockIdx.x == 0 && tid == 0) acc[j - 1] += 1.0;
+}
+
+void launch_measure_td_pair(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc, int j) {
+    const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
+    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_td_pair<1>), grid, block, 0, lc.st, hm, gs, acc, j, lc.cs);
+    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_td_pair<2>), grid, block, 0, lc.st, hm, gs, acc, j, lc.cs);
+    else hipLaunchKernelGGL((k_measure_td_pair<3>), grid, block, 0, lc.st, hm, gs, acc, j, lc.cs);
+}

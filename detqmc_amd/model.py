@@ -55,6 +55,7 @@ class SDWParams:
     repeatWolffPerSweep: int = 1
     fermionMeasurements: bool = False    # sweep(True) also takes the G-dependent observables (reference default: on)
     timeDisplacedMeasurements: bool = False   # ... and G(k, tau_j) at the interior stabilisation boundaries (needs fermionMeasurements)
+    timeDisplacedPairing: bool = False        # ... and the pairing correlators P+-(r, tau_j) (needs timeDisplacedMeasurements)
     globalUpdateInterval: int = 100
     phi2bosons: bool = False
     cdwU: float = 0.0
@@ -164,6 +165,16 @@ class KernelContext:
     def measure_td_read(self):
         out = np.zeros(self.lib.dqmc_measure_td_accum_size(self.h))
         check(self.lib.dqmc_measure_td_read_host(self.h, out.ctypes.data_as(_lib._DP)))
+        return out
+
+    def measure_timedisplaced_pair(self, j):
+        """pairing correlators of the last pair's shifted G(tau_j, 0) into their block (needs timeDisplaced=2 at construction)"""
+        check(self.lib.dqmc_measure_timedisplaced_pair(self.h, j))
+
+    def measure_td_pair_read(self):
+        """count[n-1], then per boundary the N sums of Re T+ and the N sums of Re T- over the periodic site differences"""
+        out = np.zeros(self.lib.dqmc_measure_td_pair_accum_size(self.h))
+        check(self.lib.dqmc_measure_td_pair_read_host(self.h, out.ctypes.data_as(_lib._DP)))
         return out
 
     def select_chain(self, b):
@@ -368,6 +379,8 @@ class _CtxView(KernelContext):
 
 
 def _host_params(pars: SDWParams):
+    if pars.timeDisplacedPairing and not pars.timeDisplacedMeasurements:
+        raise ValueError("timeDisplacedPairing needs timeDisplacedMeasurements")
     return _lib.detsdw_params(
         opdim=pars.opdim, L=pars.L, m=pars.m, s=pars.s, delaySteps=pars.delaySteps,
         globalShift=int(pars.globalShift), globalUpdateInterval=pars.globalUpdateInterval,
@@ -382,7 +395,7 @@ def _host_params(pars: SDWParams):
         wolffClusterUpdate=int(pars.wolffClusterUpdate), wolffClusterShiftUpdate=int(pars.wolffClusterShiftUpdate),
         repeatWolffPerSweep=int(pars.repeatWolffPerSweep), fermionMeasurements=int(pars.fermionMeasurements),
         spinProposalMethod=SPIN_PROPOSAL[pars.spinProposalMethod], adaptScaleVariance=int(pars.adaptScaleVariance),
-        repeatUpdateInSlice=int(pars.repeatUpdateInSlice), timeDisplacedMeasurements=int(pars.timeDisplacedMeasurements),
+        repeatUpdateInSlice=int(pars.repeatUpdateInSlice), timeDisplacedMeasurements=(2 if pars.timeDisplacedPairing else int(bool(pars.timeDisplacedMeasurements))),
         tuning=_tuning(pars.pipeline, pars.qrVariant, pars.greenVariant, pars.maxJacobiSweeps, pars.proposalBudget, pars.decideThreads))
 
 
@@ -452,11 +465,14 @@ class DetSDW:
 
     def observable_vector(self, name):
         """'kOccX', 'kOccY', 'pairPlus', 'pairMinus' of the last sweep(True) with fermionMeasurements (length N); 'greenKTauX',
-        'greenKTauY' with timeDisplacedMeasurements: shape (n-1, N), row j-1 = tau_j of tau_grid()"""
+        'greenKTauY' with timeDisplacedMeasurements: shape (n-1, N), row j-1 = tau_j of tau_grid(); 'pairPlusTau', 'pairMinusTau'
+        with timeDisplacedPairing: shape (n-1, N), column = periodic site difference dy L + dx; 'pairPlusTauQ0', 'pairMinusTauQ0':
+        their sums over the site difference, length n-1"""
         self._sel()
         info = self.info
-        which = {"kOccX": 0, "kOccY": 1, "pairPlus": 2, "pairMinus": 3, "greenKTauX": 4, "greenKTauY": 5}[name]
-        out = np.zeros((info.n - 1, info.N) if which >= 4 else info.N)
+        which = {"kOccX": 0, "kOccY": 1, "pairPlus": 2, "pairMinus": 3, "greenKTauX": 4, "greenKTauY": 5,
+                 "pairPlusTau": 6, "pairMinusTau": 7, "pairPlusTauQ0": 8, "pairMinusTauQ0": 9}[name]
+        out = np.zeros(info.N if which < 4 else (info.n - 1, info.N) if which < 8 else info.n - 1)
         check(self.lib.detsdw_get_observable_vector(self.h, which, out.ctypes.data_as(_lib._DP)), host=True)
         return out
 

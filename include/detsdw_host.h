@@ -61,7 +61,8 @@ typedef struct detsdw_params {
     int32_t adaptScaleVariance;       /* adapt scaleDelta during thermalization (src/detsdwparams.h:43) */
     int32_t repeatUpdateInSlice;      /* passes of local updates per time slice and sweep, 0 is read as 1 (src/detsdwparams.h:90) */
     int32_t timeDisplacedMeasurements; /* 1 (needs fermionMeasurements): a measurement sweep also takes G(k, tau_j) at the interior
-                                         stabilisation boundaries tau_j = j s dtau, j = 1 .. n-1 (DETSDW_OBS_GREENKTAU_X / _Y) */
+                                         stabilisation boundaries tau_j = j s dtau, j = 1 .. n-1 (DETSDW_OBS_GREENKTAU_X / _Y); 2: and the
+                                         time-displaced pairing correlators (DETSDW_OBS_PAIRPLUSTAU .. _PAIRMINUSTAU_Q0) */
     dqmc_tuning tuning;               /* result-neutral execution choices handed to every kernel context (dqmc_hip.h); all zero =
                                          automatic.  With pipeline = 0 the host layer switches the pipelined update on only for
                                          handles of at most two kernel contexts (more contexts overlap each other instead) */
@@ -109,7 +110,8 @@ typedef struct detsdw_observables {
     double occDiffSq;                   /* :866-897, :1013 */
 } detsdw_observables;
 enum { DETSDW_OBS_KOCCX = 0, DETSDW_OBS_KOCCY = 1, DETSDW_OBS_PAIRPLUS = 2, DETSDW_OBS_PAIRMINUS = 3,
-       DETSDW_OBS_GREENKTAU_X = 4, DETSDW_OBS_GREENKTAU_Y = 5 };
+       DETSDW_OBS_GREENKTAU_X = 4, DETSDW_OBS_GREENKTAU_Y = 5,
+       DETSDW_OBS_PAIRPLUSTAU = 6, DETSDW_OBS_PAIRMINUSTAU = 7, DETSDW_OBS_PAIRPLUSTAU_Q0 = 8, DETSDW_OBS_PAIRMINUSTAU_Q0 = 9 };
 
 /* createReplica (src/detsdwopdim.cpp:49-84) + DetSDW ctor (:158-361): checks parameters, seeds the
  * RNG with (rngSeed, simindex + 1) (src/detqmc.h:181), draws the random field, builds UdV storage and
@@ -141,7 +143,10 @@ int detsdw_get_info(detsdw_replica* r, detsdw_info* out);
 int detsdw_get_observables(detsdw_replica* r, detsdw_observables* out);
 /* N-vectors of the last measurement sweep: kOccX, kOccY (site index = k-vector, :616-659, :937-941), pairPlus, pairMinus.
  * With timeDisplacedMeasurements: greenKTauX / greenKTauY, (n-1) x N (row j-1 = tau_j, column = k-vector as for kOcc):
- *   G_band(k, tau_j) = Re (1/2N) sum_spin sum_{a,b} e^{i k (r_a - r_b)} [e^{-dtau K/2} G(tau_j, 0) e^{+dtau K/2}]_{(a,band,spin),(b,band,spin)} */
+ *   G_band(k, tau_j) = Re (1/2N) sum_spin sum_{a,b} e^{i k (r_a - r_b)} [e^{-dtau K/2} G(tau_j, 0) e^{+dtau K/2}]_{(a,band,spin),(b,band,spin)}
+ * With timeDisplacedMeasurements == 2: pairPlusTau / pairMinusTau, (n-1) x N (row j-1 = tau_j, column = periodic site difference
+ * d = (dx, dy), index dy L + dx):  C+-(d, tau_j) = (1/N) sum_B Re T+-(B (+) d, B), T+- the pairPlus / pairMinus expressions (:695-715)
+ * on the same shifted G(tau_j, 0) (dqmc_measure_timedisplaced_pair); pairPlusTauQ0 / pairMinusTauQ0, n-1: their sums over d */
 int detsdw_get_observable_vector(detsdw_replica* r, int which, double* out);
 /* tau_j = j s dtau of the rows of greenKTauX / Y, j = 1 .. n-1: out[n-1] */
 int detsdw_get_tau_grid(detsdw_replica* r, double* out);

@@ -100,9 +100,10 @@ typedef struct dqmc_params {
                                       with repeatUpdateInSlice = 1 can consume at most (opdim + 1, + 2 with cdwU).  Callers that use
                                       dqmc_update_slice_ex with more passes or the rotate / scale proposals (whose Gaussian draws consume
                                       a variable number) size it: repeat x (opdim + 1) resp. repeat x 8 (+ 2 with cdwU) */
-    int32_t timedisplaced; /* != 0: reserve the per-chain buffers of the time-displaced Green's functions and their accumulator
-                              block (SDW model only); dqmc_set_timedisplaced switches the computation on and off.  0: nothing is
-                              reserved, nothing changes */
+    int32_t timedisplaced; /* 1: reserve the per-chain buffers of the time-displaced Green's functions and their accumulator
+                              block (SDW model only); dqmc_set_timedisplaced switches the computation on and off.  2: also the
+                              accumulator block of dqmc_measure_timedisplaced_pair.  0: nothing is reserved, nothing changes.
+                              Any other value: DQMC_EINVAL */
     dqmc_tuning tuning;   /* all zero = automatic */
 } dqmc_params;
 
@@ -287,6 +288,18 @@ int dqmc_get_green_timedisplaced_host(dqmc_ctx* ctx, dqmc_cplx* g_t0, dqmc_cplx*
 int dqmc_measure_timedisplaced(dqmc_ctx* ctx, int j);
 size_t dqmc_measure_td_accum_size(dqmc_ctx* ctx);       /* 0 without the reservation */
 int dqmc_measure_td_read_host(dqmc_ctx* ctx, double* out);
+/* Time-displaced pairing correlators from the same shifted matrix gs = e^{-dtau K/2} G(tau_j,0) e^{+dtau K/2} (all chains; same
+ * preconditions as dqmc_measure_timedisplaced, and a context created with dqmc_params::timedisplaced == 2).  With the band-spin
+ * access rule of the equal-time measurement (detsdwopdim.cpp:594-612) and, for a site pair (A, B),
+ *   P(b1,b2) = gs(A b1 dn; B b2 up) gs(A b1 up; B b2 dn) - gs(A b1 dn; B b2 dn) gs(A b1 up; B b2 up)        (:695-715)
+ *   T+ = -4 [P(X,X) + P(X,Y) + P(Y,X) + P(Y,Y)],   T- = -4 [P(X,X) - P(X,Y) - P(Y,X) + P(Y,Y)]
+ * the block of boundary j receives  sum_B Re T+-(B (+) d, B)  for every periodic site difference d = (dx, dy), bin dy L + dx (dividing
+ * by N and by the count gives the translation average).  Layout (doubles, dqmc_measure_td_pair_accum_size of them): count[n-1], then for
+ * j = 1 .. n-1 the T+ sums [N] followed by the T- sums [N], at offset (n-1) + (j-1) 2N.  A block of its own: the layout of the block of
+ * dqmc_measure_timedisplaced does not depend on it.  dqmc_measure_reset clears it as well. */
+int dqmc_measure_timedisplaced_pair(dqmc_ctx* ctx, int j);
+size_t dqmc_measure_td_pair_accum_size(dqmc_ctx* ctx);  /* 0 without the reservation */
+int dqmc_measure_td_pair_read_host(dqmc_ctx* ctx, double* out);
 
 /* set_exchange_parameter_value (detsdwopdim.cpp:5195-5197): r only enters the bosonic action */
 int dqmc_set_exchange_parameter(dqmc_ctx* ctx, double r);
