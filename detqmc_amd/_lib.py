@@ -24,7 +24,7 @@ class dqmc_cplx(C.Structure):
 
 class dqmc_tuning(C.Structure):
     _fields_ = [("pipeline", C.c_int32), ("qr_variant", C.c_int32), ("green_variant", C.c_int32),
-                ("max_jacobi_sweeps", C.c_int32), ("proposal_budget", C.c_int32), ("decide_threads", C.c_int32), ("reserved", C.c_int32 * 2)]
+                ("max_jacobi_sweeps", C.c_int32), ("proposal_budget", C.c_int32), ("decide_threads", C.c_int32), ("reserved", C.c_int32)]
 
 
 class dqmc_schedule_info(C.Structure):
@@ -43,7 +43,7 @@ class dqmc_params(C.Structure):
                 ("txhor", C.c_double), ("txver", C.c_double), ("tyhor", C.c_double), ("tyver", C.c_double),
                 ("mux", C.c_double), ("muy", C.c_double), ("accRatio", C.c_double), ("cdwU", C.c_double),
                 ("rng_window_per_site", C.c_int32), ("timedisplaced", C.c_int32),
-                ("tuning", dqmc_tuning)]
+                ("tuning", dqmc_tuning), ("td_particle_hole", C.c_int32)]
 
 
 class dqmc_update_state(C.Structure):
@@ -85,7 +85,7 @@ class detsdw_params(C.Structure):
                 ("repeatWolffPerSweep", C.c_int32), ("fermionMeasurements", C.c_int32),
                 ("spinProposalMethod", C.c_int32), ("adaptScaleVariance", C.c_int32), ("repeatUpdateInSlice", C.c_int32),
                 ("timeDisplacedMeasurements", C.c_int32),
-                ("tuning", dqmc_tuning)]
+                ("tuning", dqmc_tuning), ("timeDisplacedParticleHole", C.c_int32)]
 
 
 class detsdw_info(C.Structure):
@@ -197,6 +197,10 @@ SYMBOLS = [
     ("dqmc_measure_timedisplaced_pair", C.c_int, [_P, C.c_int]),
     ("dqmc_measure_td_pair_accum_size", C.c_size_t, [_P]),
     ("dqmc_measure_td_pair_read_host", C.c_int, [_P, _DP]),
+    ("dqmc_measure_timedisplaced_ph", C.c_int, [_P, C.c_int]),
+    ("dqmc_measure_td_ph_accum_size", C.c_size_t, [_P]),
+    ("dqmc_measure_td_ph_read_host", C.c_int, [_P, _DP]),
+    ("dqmc_get_green0_timedisplaced_host", C.c_int, [_P, _P, C.POINTER(C.c_int)]),
     ("dqmc_profile_enable", C.c_int, [_P, C.c_int]),
     ("dqmc_profile_read", C.c_int, [_P, C.POINTER(dqmc_profile)]),
     ("detsdw_create", C.c_int, [C.POINTER(detsdw_params), C.POINTER(_P)]),

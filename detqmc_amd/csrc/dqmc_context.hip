@@ -80,6 +80,10 @@ struct dqmc_ctx {
     size_t tdacc_n = 0;
     double* tdpacc = nullptr;                                 // accumulator block of dqmc_measure_timedisplaced_pair (timedisplaced == 2)
     size_t tdpacc_n = 0;
+    // dqmc_params::td_particle_hole: G(0) of the boundary's own field configuration, (shifted G(0,tau))^H, one-body values, accumulators
+    cplx *G00 = nullptr, *ph_H = nullptr, *ph_ob = nullptr;
+    double* tdphacc = nullptr;
+    size_t tdphacc_n = 0;
     SvdWork sw{};
     double hub_e_m2a = 1.0, hub_e_p2a = 1.0;  // Hubbard: exp(-+2 alpha) of weightRatioSingleFlip (dethubbard.cpp:866-867)
     int stab = 0;                       // DQMC_STAB_SVD / DQMC_STAB_QR
@@ -710,6 +714,14 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
             A_(dalloc(c, &c->tdpacc, c->tdpacc_n));
         }
     }
+    if (p->td_particle_hole != 0 && p->td_particle_hole != 1) return fail(DQMC_EINVAL, "td_particle_hole must be 0 or 1");
+    if (p->td_particle_hole) {              // behind the blocks above: contexts without the flag are laid out as before
+        if (!p->timedisplaced) return fail(DQMC_EINVAL, "td_particle_hole needs timedisplaced >= 1");
+        A_(dalloc(c, &c->G00, n2)); A_(dalloc(c, &c->ph_H, n2));
+        A_(dalloc(c, &c->ph_ob, measure_td_ph_onebody_cplx(N)));
+        c->tdphacc_n = measure_td_ph_doubles(N, c->n);
+        A_(dalloc(c, &c->tdphacc, c->tdphacc_n));
+    }
     A_(arena_commit(c));                    // from here on the per-chain pointers are real (chain 0) addresses, zero filled
 #undef A_
     c->qw.err = &c->us->chol_fail;
@@ -1008,6 +1020,15 @@ static int udt_dev(dqmc_ctx* c, const cplx* M, const double* colscale, const dou
 // new matrix is one more triangular solve (LU route) or Q application (QR route) and one GEMM.
 //   LU route, P Z = L U:  G(tau,0) = T3 [(V_r Drmin P^T) L^-H]^H,   G(0,tau) = -[(U_l Dlmin) U^-1] T1^H
 //   QR route, Z P = Q R:  G(tau,0) = T3 [Q^H Drmin V_r^H],          G(0,tau) = -[(U_l Dlmin P) R^-1] T1
+// td_particle_hole: the equal-time G(0) of the SAME field configuration,
+//   1 - G(0) = B(beta,tau) G(tau) B(tau,0) = [U_l Dlmin] Z^-1 [Drmin V_r^H]
+// (the fourth combination of the outer brackets; no unitarity of V is assumed): the left factor of G(0,tau), td_W, times the right
+// factor of G(tau,0) -- one GEMM with the negate epilogue, then + 1 on the diagonal (eye.d holds ones).
+static void green0_from_factors(dqmc_ctx* c, int opB, const cplx* right) {
+    gemm_dev(c, 0, opB, c->td_W, right, c->G00, nullptr, 0, nullptr, nullptr, 0, 0, 0, /*negate=*/1);
+    ProfScope ps(c, FAM_OTHER, 1);
+    launch_add_diag(c->lc, c->G00, c->eye.d, c->n_g);
+}
 static void td_from_lu(dqmc_ctx* c, const UdVSlot& L, const UdVSlot& R) {
     const int n = c->n_g;
     {
@@ -1020,6 +1041,7 @@ static void td_from_lu(dqmc_ctx* c, const UdVSlot& L, const UdVSlot& R) {
     }
     gemm_dev(c, 0, 1, c->T3, c->T4, c->GT0);
     gemm_dev(c, 0, 1, c->td_W, c->T1, c->G0T, nullptr, 0, nullptr, nullptr, 0, 0, 0, /*negate=*/1);
+    if (c->G00) green0_from_factors(c, 1, c->T4);                                      // G(0) = 1 - td_W T4^H
 }
 // bgs: Q is explicit in T4 (block Gram-Schmidt), else it is in reflector form in the QR workspace; R in sw.A
 static void td_from_qr(dqmc_ctx* c, const UdVSlot& L, const UdVSlot& R, bool bgs) {
@@ -1044,6 +1066,8 @@ static void td_from_qr(dqmc_ctx* c, const UdVSlot& L, const UdVSlot& R, bool bgs
         c->fam_launches[FAM_JACOBI] += 1 + run_trsm_right_upper(c->lc, n, c->sw.A, c->td_W, c->qw);   // td_W <- td_W R^-1
     }
     gemm_dev(c, 0, 0, c->td_W, c->T1, c->G0T, nullptr, 0, nullptr, nullptr, 0, 0, 0, /*negate=*/1);
+    // T2 still holds Q^H Drmin V_r^H: nothing above writes it after G(tau,0), and td_W (scratch of the bgs branch first) has its final value
+    if (c->G00) green0_from_factors(c, 0, c->T2);                                                // G(0) = 1 - td_W T2
 }
 
 // G from an L-type and an R-type factorisation (nullptr = identity), with the scales split into their
@@ -1612,6 +1636,8 @@ extern "C" int dqmc_measure_reset(dqmc_ctx* c) {
         for (int b = 0; b < c->nb; ++b) HIPCHK(hipMemsetAsync(chainp(c, c->tdacc, b), 0, c->tdacc_n * sizeof(double), c->st));
     if (c->tdpacc_n)
         for (int b = 0; b < c->nb; ++b) HIPCHK(hipMemsetAsync(chainp(c, c->tdpacc, b), 0, c->tdpacc_n * sizeof(double), c->st));
+    if (c->tdphacc_n)
+        for (int b = 0; b < c->nb; ++b) HIPCHK(hipMemsetAsync(chainp(c, c->tdphacc, b), 0, c->tdphacc_n * sizeof(double), c->st));
     return DQMC_OK;
 }
 extern "C" int dqmc_measure_slice(dqmc_ctx* c) {
@@ -1695,6 +1721,46 @@ extern "C" int dqmc_measure_td_pair_read_host(dqmc_ctx* c, double* out) {
     (void)hipSetDevice(c->p.device);
     HIPCHK(hipStreamSynchronize(c->st));
     HIPCHK(copy_sync(c, out, selp(c, c->tdpacc), c->tdpacc_n * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+// particle-hole correlators of the boundary the context stands on.  One-body values first (shifted G(tau_j), shifted G(0): only their
+// site-diagonal 4 x 4 blocks are needed, so neither shifted matrix is kept); then the shifted G(0,tau) leaves the shift scratch through
+// the conjugate tile transpose -- the copy it needs anyway -- and the shifted G(tau,0) stays in T1
+extern "C" int dqmc_measure_timedisplaced_ph(dqmc_ctx* c, int j) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (!c->tdphacc_n) return fail(DQMC_EINVAL, "context created without dqmc_params::td_particle_hole");
+    if (j < 1 || j > c->n - 1) return fail(DQMC_EINVAL, "boundary index j must be in 1..n-1");
+    if (c->td_slice != c->s * j) return fail(DQMC_EINVAL, "the last time-displaced pair does not belong to boundary j");
+    if (c->currentTimeslice != c->s * j) return fail(DQMC_EINVAL, "the context has left boundary j: G is no longer G(tau_j)");
+    (void)hipSetDevice(c->p.device);
+    shift_green_dev(c);
+    { ProfScope ps(c, FAM_OTHER, 1); launch_td_ph_onebody(c->lc, c->hm, c->T1, c->ph_ob, 0); }
+    shift_green_dev(c, c->G00);
+    { ProfScope ps(c, FAM_OTHER, 1); launch_td_ph_onebody(c->lc, c->hm, c->T1, c->ph_ob, 1); }
+    shift_green_dev(c, c->G0T);
+    { ProfScope ps(c, FAM_OTHER, 1); launch_conj_transpose(c->lc, c->T1, c->ph_H, c->n_g); }
+    shift_green_dev(c, c->GT0);
+    { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td_ph(c->lc, c->hm, c->T1, c->ph_H, c->ph_ob, c->tdphacc, j); }
+    return finish(c, "dqmc_measure_timedisplaced_ph");
+}
+extern "C" size_t dqmc_measure_td_ph_accum_size(dqmc_ctx* c) { return c ? c->tdphacc_n : 0; }
+extern "C" int dqmc_measure_td_ph_read_host(dqmc_ctx* c, double* out) {
+    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
+    if (!c->tdphacc_n) return fail(DQMC_EINVAL, "context created without dqmc_params::td_particle_hole");
+    (void)hipSetDevice(c->p.device);
+    HIPCHK(hipStreamSynchronize(c->st));
+    HIPCHK(copy_sync(c, out, selp(c, c->tdphacc), c->tdphacc_n * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+extern "C" int dqmc_get_green0_timedisplaced_host(dqmc_ctx* c, dqmc_cplx* g00, int* slice) {
+    if (!c || !g00 || !slice) return fail(DQMC_EINVAL, "null argument");
+    if (!c->G00) return fail(DQMC_EINVAL, "context created without dqmc_params::td_particle_hole");
+    if (c->td_slice < 0) return fail(DQMC_EINVAL, "no time-displaced Green's function has been computed");
+    (void)hipSetDevice(c->p.device);
+    HIPCHK(hipStreamSynchronize(c->st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(copy_sync(c, g00, selp(c, c->G00), (size_t)c->n_g * c->n_g * sizeof(cplx), hipMemcpyDeviceToHost));
+    *slice = c->td_slice;
     return DQMC_OK;
 }
 

@@ -255,6 +255,13 @@ size_t measure_td_doubles(int L, int n);
 // time-displaced pairing block: count[n-1], then per boundary j = 1 .. n-1 the sums over B of Re T+(B (+) d, B) [N] and Re T-(B (+) d, B) [N]
 void launch_measure_td_pair(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc, int j);
 size_t measure_td_pair_doubles(int N, int n);
+// time-displaced particle-hole block: count[n-1], then per boundary j = 1 .. n-1 the sums over B of Re W(B (+) d, B) for charge [N], spinZ [N], sdw [N].
+// gs = shifted G(tau_j, 0), hs = (shifted G(0, tau_j))^H, ob = the one-body values [2][5][N] that launch_td_ph_onebody wrote from the
+// shifted equal-time matrices (t = 0: G(tau_j), t = 1: G(0))
+void launch_td_ph_onebody(const Launch& lc, const DevModel& hm, const cplx* gs, cplx* ob, int t);
+void launch_measure_td_ph(const Launch& lc, const DevModel& hm, const cplx* gs, const cplx* hs, const cplx* ob, double* acc, int j);
+size_t measure_td_ph_doubles(int N, int n);
+size_t measure_td_ph_onebody_cplx(int N);
 
 // ---- QR / UDT building blocks (kernels_qr.hip) ------------------------------------------------
 struct SvdProfHooks;

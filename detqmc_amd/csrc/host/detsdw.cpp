@@ -29,7 +29,8 @@ static bool same_model(const detsdw_params& a, const detsdw_params& b, bool seed
                       a.wolffClusterUpdate == b.wolffClusterUpdate && a.wolffClusterShiftUpdate == b.wolffClusterShiftUpdate &&
                       a.repeatWolffPerSweep == b.repeatWolffPerSweep && a.fermionMeasurements == b.fermionMeasurements &&
                       a.spinProposalMethod == b.spinProposalMethod && a.adaptScaleVariance == b.adaptScaleVariance &&
-                      a.repeatUpdateInSlice == b.repeatUpdateInSlice && a.timeDisplacedMeasurements == b.timeDisplacedMeasurements;
+                      a.repeatUpdateInSlice == b.repeatUpdateInSlice && a.timeDisplacedMeasurements == b.timeDisplacedMeasurements &&
+                      a.timeDisplacedParticleHole == b.timeDisplacedParticleHole;
     const bool reals = a.beta == b.beta && a.dtau == b.dtau && a.c == b.c && a.u == b.u && a.lambda == b.lambda &&
                        a.txhor == b.txhor && a.txver == b.txver && a.tyhor == b.tyhor && a.tyver == b.tyver &&
                        a.mu == b.mu && a.mux == b.mux && a.muy == b.muy && a.accRatio == b.accRatio && a.cdwU == b.cdwU;
@@ -106,6 +107,10 @@ void DetSDW::normalise(detsdw_params& p, int& bcv) {
         throw ParameterWrong("Parameter timeDisplacedMeasurements has incorrect value");
     if (p.timeDisplacedMeasurements && !p.fermionMeasurements)
         throw ParameterWrong("timeDisplacedMeasurements needs fermionMeasurements");
+    if (p.timeDisplacedParticleHole != 0 && p.timeDisplacedParticleHole != 1)
+        throw ParameterWrong("Parameter timeDisplacedParticleHole has incorrect value");
+    if (p.timeDisplacedParticleHole && !p.timeDisplacedMeasurements)
+        throw ParameterWrong("timeDisplacedParticleHole needs timeDisplacedMeasurements");
     // createReplica (detsdwopdim.cpp:75-79)
     if (!p.has_mux_muy) { p.mux = p.mu; p.muy = p.mu; }
 }
@@ -149,6 +154,7 @@ DetSDW::DetSDW(const detsdw_params* in, int nchains, int sub_batches) {
     kp.cb_none = p.cb_none ? 1 : 0;          // reference option checkerboard=false (DetSDW<CB_NONE, OPDIM>)
     kp.rng_window_per_site = uniformsPerSite();
     kp.timedisplaced = p.timeDisplacedMeasurements;      // 1: G(tau_j, 0) and its bins, 2: and the pairing block
+    kp.td_particle_hole = p.timeDisplacedParticleHole;
     // result-neutral execution choices.  The pipelined update pays only while few contexts share the GPU (with more of them the
     // contexts overlap each other instead): automatic here means at most two sub-batches.
     kp.tuning = p.tuning;
@@ -243,6 +249,7 @@ void DetSDW::measureTimeDisplaced(Group& g, int j) {
     if (!measuringTD_) return;
     check(dqmc_measure_timedisplaced(g.ctx, j), "measureTimeDisplaced");
     if (ch_[0].pars.timeDisplacedMeasurements == 2) check(dqmc_measure_timedisplaced_pair(g.ctx, j), "measureTimeDisplacedPair");
+    if (ch_[0].pars.timeDisplacedParticleHole) check(dqmc_measure_timedisplaced_ph(g.ctx, j), "measureTimeDisplacedParticleHole");
 }
 
 // detmodel.h:1333-1399
@@ -437,6 +444,27 @@ void DetSDW::finishFermionic(int b) {
             c.pairPlusTauQ0[j - 1] = qp; c.pairMinusTauQ0[j - 1] = qm;
         }
     }
+    // time-displaced particle-hole correlators (charge, spinZ, sdw): the same normalisation
+    if (c.pars.timeDisplacedParticleHole) {
+        std::vector<double> tp(dqmc_measure_td_ph_accum_size(ctx_));
+        check(dqmc_measure_td_ph_read_host(ctx_, tp.data()), "dqmc_measure_td_ph_read_host");
+        const int nj = n_ - 1;
+        for (int ch = 0; ch < 3; ++ch) { c.phTau[ch].assign((size_t)nj * N, 0.0); c.phTauQ0[ch].assign(nj, 0.0); }
+        for (int j = 1; j <= nj; ++j) {
+            const double cnt = tp[j - 1];
+            if (cnt < 1.0) throw GeneralError(DQMC_EINVAL, "measurement sweep did not visit every stabilisation boundary");
+            for (int ch = 0; ch < 3; ++ch) {
+                const double* T = &tp[nj + ((size_t)(j - 1) * 3 + ch) * N];
+                double q = 0.0;
+                for (int d = 0; d < N; ++d) {
+                    const double v = T[d] / (double(N) * cnt);
+                    c.phTau[ch][(size_t)(j - 1) * N + d] = v;
+                    q += v;
+                }
+                c.phTauQ0[ch][j - 1] = q;
+            }
+        }
+    }
     o.fermionic_valid = 1;
 }
 
@@ -452,12 +480,16 @@ void DetSDW::getObservableVector(int which, double* out, int b) const {
                                  : which == DETSDW_OBS_GREENKTAU_X ? &c.greenKTauX : which == DETSDW_OBS_GREENKTAU_Y ? &c.greenKTauY
                                  : which == DETSDW_OBS_PAIRPLUSTAU ? &c.pairPlusTau : which == DETSDW_OBS_PAIRMINUSTAU ? &c.pairMinusTau
                                  : which == DETSDW_OBS_PAIRPLUSTAU_Q0 ? &c.pairPlusTauQ0 : which == DETSDW_OBS_PAIRMINUSTAU_Q0 ? &c.pairMinusTauQ0
+                                 : which >= DETSDW_OBS_CHARGETAU && which <= DETSDW_OBS_SDWTAU ? &c.phTau[which - DETSDW_OBS_CHARGETAU]
+                                 : which >= DETSDW_OBS_CHARGETAU_Q0 && which <= DETSDW_OBS_SDWTAU_Q0 ? &c.phTauQ0[which - DETSDW_OBS_CHARGETAU_Q0]
                                  : nullptr;
     if (!v) throw ParameterWrong("unknown observable vector");
     if ((which == DETSDW_OBS_GREENKTAU_X || which == DETSDW_OBS_GREENKTAU_Y) && !c.pars.timeDisplacedMeasurements)
         throw ParameterWrong("greenKTauX / greenKTauY need timeDisplacedMeasurements");
     if (which >= DETSDW_OBS_PAIRPLUSTAU && which <= DETSDW_OBS_PAIRMINUSTAU_Q0 && c.pars.timeDisplacedMeasurements != 2)
         throw ParameterWrong("pairPlusTau / pairMinusTau need timeDisplacedMeasurements = 2");
+    if (which >= DETSDW_OBS_CHARGETAU && which <= DETSDW_OBS_SDWTAU_Q0 && !c.pars.timeDisplacedParticleHole)
+        throw ParameterWrong("chargeTau / spinZTau / sdwTau need timeDisplacedParticleHole");
     std::memcpy(out, v->data(), v->size() * sizeof(double));
 }
 

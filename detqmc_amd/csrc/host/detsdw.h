@@ -88,6 +88,7 @@ private:
         std::vector<double> greenKTauX, greenKTauY;         // (n-1) x N, row j-1 = tau_j (timeDisplacedMeasurements)
         std::vector<double> pairPlusTau, pairMinusTau;      // (n-1) x N, column = periodic site difference (timeDisplacedMeasurements == 2)
         std::vector<double> pairPlusTauQ0, pairMinusTauQ0;  // n-1: their row sums
+        std::vector<double> phTau[3], phTauQ0[3];           // charge, spinZ, sdw: (n-1) x N and the row sums (timeDisplacedParticleHole)
         Chain(const detsdw_params& p) : pars(p), rng(p.rngSeed, (uint32_t)p.simindex + 1u) {}   // detqmc.h:181
     };
     std::vector<Chain> ch_;

@@ -274,3 +274,151 @@ void launch_measure_td_pair(const Launch& lc, const DevModel& hm, const cplx* gs
     else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_td_pair<2>), grid, block, 0, lc.st, hm, gs, acc, j, lc.cs);
     else hipLaunchKernelGGL((k_measure_td_pair<3>), grid, block, 0, lc.st, hm, gs, acc, j, lc.cs);
 }
+
+// Time-displaced particle-hole block (dqmc_measure_timedisplaced_ph; definitions in dqmc_hip.h and DESIGN.md 6e).  For a site bilinear
+// O^M_i = sum_ab c^+_ia M_ab c_ib and the four shifted matrices of one boundary,
+//   W^M(A, B) = o^M_tau(A) o^M_0(B) - sum_abcd M_ab M_cd g0t(B d; A a) gt0(A b; B c),     o^M_t(A) = tr M - sum_ab M_ab g_t(A b; A a).
+// Every M used here has ONE non-zero entry per row, M(a, pi(a)) = m_a, so the connected part is
+//   sum_{a, c} m_a m_c  gt0(A pi(a); B c)  g0t(B pi(c); A a)                                                     (16 products per M)
+// and all coefficient products m_a m_c are real (M_y: m = i y with y = (-1, +1, +1, -1)).  The second factor is read from
+// hs = (shifted G(0, tau))^H, written by the tile transpose that takes the shifted matrix out of the shift scratch anyway:
+//   g0t(B d; A a) = conj hs(A a; B d),
+// the SAME address pattern as gt0(A b; B c) -- lanes run over consecutive rows A of one column for both streams, and each matrix is read
+// exactly once per launch.  Only Re W is binned, Re (x conj y) = x.re y.re + x.im y.im.
+// OPDIM < 3: both matrices are diag(stored sector, its conjugate); all M of the channels in use (charge, spinZ, M_x, M_y) are block
+// diagonal in that structure, so the second sector contributes the complex conjugate of the first: with e_rc = gt0(A + N r; B + N c),
+// h_rc = hs(A + N r; B + N c), d_rc = Re e_rc conj h_rc and q_ac = Re e_(1-a)c conj h_a(1-c),
+//   charge = 2 sum d_rc,   spinZ = (d_00 + d_11 - d_01 - d_10) / 2,   M_x = 2 (q_00 + q_01 + q_10 + q_11),   M_y = 2 (-q_00 + q_01 + q_10 - q_11):
+// eight loads per pair, nothing multiplied by a structural zero.
+// Shape, reduction and reproducibility: those of k_measure_td_pair above (32 bins x 8 parts, one writer per accumulator, fixed order).
+size_t measure_td_ph_doubles(int N, int n) { return (size_t)(n - 1) * (1 + 3 * (size_t)N); }
+
+#define TDPH_CH 5       // one-body values per site and time: charge, spinZ, M_x, M_y, M_z
+
+// ob[t][channel][site] for one of the two equal-time matrices (t = 0: G(tau_j), t = 1: G(0)); gs is its shifted form
+template<int OPDIM>
+__global__ __launch_bounds__(256) void k_td_ph_onebody(DevModel dm, const cplx* __restrict__ gs, cplx* __restrict__ ob, int t, size_t cs) {
+    CHAIN(gs); CHAIN(ob);
+    const int N = dm.N, A = blockIdx.x * 256 + threadIdx.x;
+    if (A >= N) return;
+    const GreenAccess<OPDIM> g1{gs, dm.ng, N};
+    auto g = [&](int r, int c2) { return g1(A, r, A, c2); };       // g(b, a) = g_t(A b; A a); constant indices: the zero sectors fold away
+    cplx* o = ob + (size_t)t * TDPH_CH * N + A;
+    const cplx tr = m_add(m_add(g(0, 0), g(1, 1)), m_add(g(2, 2), g(3, 3)));
+    o[0] = make_double2(4.0 - tr.x, -tr.y);
+    o[(size_t)N] = m_scale(-0.5, m_sub(m_add(g(0, 0), g(3, 3)), m_add(g(1, 1), g(2, 2))));
+    o[(size_t)2 * N] = m_scale(-1.0, m_add(m_add(g(1, 0), g(0, 1)), m_add(g(3, 2), g(2, 3))));
+    if (OPDIM >= 2) {       // tr M_y g = i (g01 - g10 + g32 - g23)
+        const cplx v = m_add(m_sub(g(0, 1), g(1, 0)), m_sub(g(3, 2), g(2, 3)));
+        o[(size_t)3 * N] = make_double2(v.y, -v.x);                // -i v
+    }
+    if (OPDIM == 3) o[(size_t)4 * N] = m_scale(-1.0, m_sub(m_add(g(3, 0), g(0, 3)), m_add(g(2, 1), g(1, 2))));
+}
+
+template<int OPDIM>
+__global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_td_ph(DevModel dm, const cplx* __restrict__ gs, const cplx* __restrict__ hs,
+                                                                        const cplx* __restrict__ ob, double* __restrict__ acc, int j, size_t cs) {
+    CHAIN(gs); CHAIN(hs); CHAIN(ob); CHAIN(acc);
+    __shared__ double red[3][TDP_PARTS][TDP_BINS];
+    const int N = dm.N, L = dm.L, tid = threadIdx.x;
+    const size_t ng = (size_t)dm.ng;
+    const int lb = tid % TDP_BINS, part = tid / TDP_BINS;
+    const int d = blockIdx.x * TDP_BINS + lb;
+    const bool valid = d < N;
+    const int dx = valid ? d % L : 0, dy = valid ? d / L : 0;
+    const cplx* ot = ob;                                    // o_tau(A)
+    const cplx* o0 = ob + (size_t)TDPH_CH * N;              // o_0(B)
+    auto rd = [](cplx a, cplx b) { return a.x * b.x + a.y * b.y; };       // Re a conj b
+    auto re_mul = [](cplx a, cplx b) { return a.x * b.x - a.y * b.y; };   // Re a b
+    double wc = 0.0, wz = 0.0, ws = 0.0;
+    if (valid) {
+        int bx = part % L, by = part / L;                   // site B = part + 8 i, kept as (bx, by)
+        const int stepx = TDP_PARTS % L, stepy = TDP_PARTS / L;
+        for (int B = part; B < N; B += TDP_PARTS) {
+            int ax = bx + dx, ay = by + dy;
+            if (ax >= L) ax -= L;
+            if (ay >= L) ay -= L;
+            const int A = ay * L + ax;
+            const size_t off = (size_t)B * ng + (size_t)A;
+            const cplx* pe = gs + off;
+            const cplx* ph = hs + off;
+            // disconnected parts
+            const double dc = re_mul(ot[A], o0[B]), dz = re_mul(ot[N + A], o0[N + B]);
+            double ds = re_mul(ot[2 * N + A], o0[2 * N + B]);
+            if (OPDIM >= 2) ds += re_mul(ot[3 * N + A], o0[3 * N + B]);
+            if (OPDIM == 3) ds += re_mul(ot[4 * N + A], o0[4 * N + B]);
+            double cc, cz, cs2;
+            if (OPDIM == 3) {
+                cplx e[4][4];
+#pragma unroll
+                for (int c2 = 0; c2 < 4; ++c2)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) e[r][c2] = pe[(size_t)c2 * N * ng + (size_t)r * N];
+                constexpr int pxy[4] = {1, 0, 3, 2}, pz[4] = {3, 2, 1, 0};
+                constexpr double sz[4] = {1.0, -1.0, -1.0, 1.0};      // spinZ diagonal (x 2), the y of M_y and the m of M_z alike
+                cc = 0.0; cz = 0.0;
+                double cx = 0.0, cy = 0.0, cq = 0.0;
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    cplx h[4];                                        // h[dl] = hs(A a; B dl)
+#pragma unroll
+                    for (int dl = 0; dl < 4; ++dl) h[dl] = ph[(size_t)dl * N * ng + (size_t)a * N];
+#pragma unroll
+                    for (int c2 = 0; c2 < 4; ++c2) {
+                        const double v = rd(e[a][c2], h[c2]);
+                        cc += v;
+                        cz += sz[a] * sz[c2] * v;
+                        const double q = rd(e[pxy[a]][c2], h[pxy[c2]]);
+                        cx += q;
+                        cy += sz[a] * sz[c2] * q;                    // m_a m_c = -y_a y_c with y = -sz
+                        cq += sz[a] * sz[c2] * rd(e[pz[a]][c2], h[pz[c2]]);
+                    }
+                }
+                cz *= 0.25;
+                cs2 = (cx - cy) + cq;
+            } else {
+                const size_t cN = (size_t)N * ng;
+                const cplx e00 = pe[0], e10 = pe[N], e01 = pe[cN], e11 = pe[cN + N];
+                const cplx h00 = ph[0], h10 = ph[N], h01 = ph[cN], h11 = ph[cN + N];
+                const double d00 = rd(e00, h00), d11 = rd(e11, h11), d01 = rd(e01, h01), d10 = rd(e10, h10);
+                cc = 2.0 * ((d00 + d11) + (d01 + d10));
+                cz = 0.5 * ((d00 + d11) - (d01 + d10));
+                const double q01 = rd(e11, h00), q10 = rd(e00, h11);
+                if (OPDIM == 1) cs2 = 2.0 * ((rd(e10, h01) + rd(e01, h10)) + (q01 + q10));
+                else cs2 = 4.0 * (q01 + q10);                        // M_x + M_y: the q_00 and q_11 terms cancel
+            }
+            wc += dc - cc;
+            wz += dz - cz;
+            ws += (ds - cs2) * (1.0 / OPDIM);
+            bx += stepx; by += stepy;
+            if (bx >= L) { bx -= L; ++by; }
+        }
+    }
+    red[0][part][lb] = wc;
+    red[1][part][lb] = wz;
+    red[2][part][lb] = ws;
+    __syncthreads();
+    if (part < 3 && valid) {                                // part 0 writes charge of its bin, part 1 spinZ, part 2 sdw
+        double s = red[part][0][lb];
+#pragma unroll
+        for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
+        acc[(dm.n - 1) + (size_t)(j - 1) * 3 * N + (size_t)part * N + d] += s;
+    }
+    if (blockIdx.x == 0 && tid == 0) acc[j - 1] += 1.0;
+}
+
+size_t measure_td_ph_onebody_cplx(int N) { return (size_t)2 * TDPH_CH * N; }
+
+void launch_td_ph_onebody(const Launch& lc, const DevModel& hm, const cplx* gs, cplx* ob, int t) {
+    const dim3 grid((hm.N + 255) / 256, 1, lc.nb);
+    if (hm.opdim == 1) hipLaunchKernelGGL((k_td_ph_onebody<1>), grid, dim3(256), 0, lc.st, hm, gs, ob, t, lc.cs);
+    else if (hm.opdim == 2) hipLaunchKernelGGL((k_td_ph_onebody<2>), grid, dim3(256), 0, lc.st, hm, gs, ob, t, lc.cs);
+    else hipLaunchKernelGGL((k_td_ph_onebody<3>), grid, dim3(256), 0, lc.st, hm, gs, ob, t, lc.cs);
+}
+
+void launch_measure_td_ph(const Launch& lc, const DevModel& hm, const cplx* gs, const cplx* hs, const cplx* ob, double* acc, int j) {
+    const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
+    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_td_ph<1>), grid, block, 0, lc.st, hm, gs, hs, ob, acc, j, lc.cs);
+    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_td_ph<2>), grid, block, 0, lc.st, hm, gs, hs, ob, acc, j, lc.cs);
+    else hipLaunchKernelGGL((k_measure_td_ph<3>), grid, block, 0, lc.st, hm, gs, hs, ob, acc, j, lc.cs);
+}

@@ -66,6 +66,9 @@ typedef struct detsdw_params {
     dqmc_tuning tuning;               /* result-neutral execution choices handed to every kernel context (dqmc_hip.h); all zero =
                                          automatic.  With pipeline = 0 the host layer switches the pipelined update on only for
                                          handles of at most two kernel contexts (more contexts overlap each other instead) */
+    int32_t timeDisplacedParticleHole; /* 1 (needs timeDisplacedMeasurements >= 1): a measurement sweep also takes the time-displaced
+                                         charge, spin-z and SDW order-parameter correlators (DETSDW_OBS_CHARGETAU .. _SDWTAU_Q0).  The
+                                         field took the second reserved slot of dqmc_tuning: the bytes of the struct are where they were */
 } detsdw_params;
 
 typedef struct detsdw_info {
@@ -97,7 +100,8 @@ typedef struct detsdw_control_data {
 
 /* bosonic observables of a measurement sweep: initMeasurements / measure / finishMeasurements with
  * turnoffFermionMeasurements (src/detsdwopdim.cpp:441-456, :509-545, :903-921); valid after detsdw_sweep(r, 1).
- * The fermionic observables (pairing, k-space occupation, ...) are not built yet. */
+ * With fermionMeasurements the G-dependent observables follow (:545-899): the scalars below fermionic_valid and the vectors of
+ * detsdw_get_observable_vector. */
 typedef struct detsdw_observables {
     double meanPhi[3];
     double normMeanPhi;
@@ -111,7 +115,9 @@ typedef struct detsdw_observables {
 } detsdw_observables;
 enum { DETSDW_OBS_KOCCX = 0, DETSDW_OBS_KOCCY = 1, DETSDW_OBS_PAIRPLUS = 2, DETSDW_OBS_PAIRMINUS = 3,
        DETSDW_OBS_GREENKTAU_X = 4, DETSDW_OBS_GREENKTAU_Y = 5,
-       DETSDW_OBS_PAIRPLUSTAU = 6, DETSDW_OBS_PAIRMINUSTAU = 7, DETSDW_OBS_PAIRPLUSTAU_Q0 = 8, DETSDW_OBS_PAIRMINUSTAU_Q0 = 9 };
+       DETSDW_OBS_PAIRPLUSTAU = 6, DETSDW_OBS_PAIRMINUSTAU = 7, DETSDW_OBS_PAIRPLUSTAU_Q0 = 8, DETSDW_OBS_PAIRMINUSTAU_Q0 = 9,
+       DETSDW_OBS_CHARGETAU = 10, DETSDW_OBS_SPINZTAU = 11, DETSDW_OBS_SDWTAU = 12,
+       DETSDW_OBS_CHARGETAU_Q0 = 13, DETSDW_OBS_SPINZTAU_Q0 = 14, DETSDW_OBS_SDWTAU_Q0 = 15 };
 
 /* createReplica (src/detsdwopdim.cpp:49-84) + DetSDW ctor (:158-361): checks parameters, seeds the
  * RNG with (rngSeed, simindex + 1) (src/detqmc.h:181), draws the random field, builds UdV storage and
@@ -146,7 +152,10 @@ int detsdw_get_observables(detsdw_replica* r, detsdw_observables* out);
  *   G_band(k, tau_j) = Re (1/2N) sum_spin sum_{a,b} e^{i k (r_a - r_b)} [e^{-dtau K/2} G(tau_j, 0) e^{+dtau K/2}]_{(a,band,spin),(b,band,spin)}
  * With timeDisplacedMeasurements == 2: pairPlusTau / pairMinusTau, (n-1) x N (row j-1 = tau_j, column = periodic site difference
  * d = (dx, dy), index dy L + dx):  C+-(d, tau_j) = (1/N) sum_B Re T+-(B (+) d, B), T+- the pairPlus / pairMinus expressions (:695-715)
- * on the same shifted G(tau_j, 0) (dqmc_measure_timedisplaced_pair); pairPlusTauQ0 / pairMinusTauQ0, n-1: their sums over d */
+ * on the same shifted G(tau_j, 0) (dqmc_measure_timedisplaced_pair); pairPlusTauQ0 / pairMinusTauQ0, n-1: their sums over d
+ * With timeDisplacedParticleHole: chargeTau / spinZTau / sdwTau, (n-1) x N, same rows and columns:
+ *   C(d, tau_j) = (1/N) sum_B Re W(B (+) d, B),  W the Wick contraction of <O_A(tau_j) O_B(0)> for the site bilinears of
+ * dqmc_measure_timedisplaced_ph (dqmc_hip.h); chargeTauQ0 / spinZTauQ0 / sdwTauQ0, n-1: their sums over d */
 int detsdw_get_observable_vector(detsdw_replica* r, int which, double* out);
 /* tau_j = j s dtau of the rows of greenKTauX / Y, j = 1 .. n-1: out[n-1] */
 int detsdw_get_tau_grid(detsdw_replica* r, double* out);

@@ -68,7 +68,7 @@ typedef struct dqmc_tuning {
                                   limit, > 0 that many (at least delaySteps) */
     int32_t decide_threads;    /* threads per workgroup of the decision kernel: 0 automatic (512 for O(1) / O(2) contexts of at most 32
                                   chains, else 256), 256, 512 (O(3): always 256).  Launch shape only: the chain does not depend on it */
-    int32_t reserved[2];
+    int32_t reserved;
 } dqmc_tuning;
 
 /* ModelParamsDetSDW fields the kernels depend on (src/detsdwparams.h:24-120) */
@@ -105,6 +105,11 @@ typedef struct dqmc_params {
                               accumulator block of dqmc_measure_timedisplaced_pair.  0: nothing is reserved, nothing changes.
                               Any other value: DQMC_EINVAL */
     dqmc_tuning tuning;   /* all zero = automatic */
+    int32_t td_particle_hole; /* 1 (needs timedisplaced >= 1, SDW model; DQMC_EINVAL otherwise): also reserve, behind every other buffer,
+                                 the equal-time G(0) of the boundary's own field configuration, one matrix for a shifted copy, the
+                                 per-site one-body values and the accumulator block of dqmc_measure_timedisplaced_ph.  0: nothing is
+                                 reserved, nothing changes.  (The field took the second reserved slot of dqmc_tuning: the bytes of the
+                                 struct are where they were.) */
 } dqmc_params;
 
 /* AdjustmentData + slice bookkeeping that lives on the device between calls
@@ -300,6 +305,28 @@ int dqmc_measure_td_read_host(dqmc_ctx* ctx, double* out);
 int dqmc_measure_timedisplaced_pair(dqmc_ctx* ctx, int j);
 size_t dqmc_measure_td_pair_accum_size(dqmc_ctx* ctx);  /* 0 without the reservation */
 int dqmc_measure_td_pair_read_host(dqmc_ctx* ctx, double* out);
+/* Time-displaced particle-hole correlators (charge, spin-z, SDW order parameter); context created with td_particle_hole = 1.
+ * While the time-displaced functions are switched on, an advance that ends on an interior boundary then also forms the equal-time
+ *   G(0) = 1 - B(beta,tau) G(tau) B(tau,0) = 1 - [U_l Dlmin] Z^-1 [Drmin V_r^H]
+ * of the SAME (half-updated) field configuration, one GEMM from the left factor of G(0,tau) and the right factor of G(tau,0).
+ * With g~ = e^{-dtau K/2} g e^{+dtau K/2} for all four matrices, G(tau,0)_ab = <c_a(tau) c_b^+(0)>, G(0,tau)_ab = -<c_b^+(tau) c_a(0)>,
+ * the band-spin order XUP, YDOWN, XDOWN, YUP and a site bilinear O^M_i = sum_ab c^+_ia M_ab c_ib (M a Hermitian 4 x 4 matrix):
+ *   o^M_t(A) = tr M - sum_ab M_ab g~(t)(A b; A a)                                                            (t = tau, 0)
+ *   W^M(A,B) = o^M_tau(A) o^M_0(B) - sum_abcd M_ab M_cd g~(0,tau)(B d; A a) g~(tau,0)(A b; B c)
+ * Channels: charge M = 1; spinZ M = diag(+1,-1,-1,+1) / 2; sdw = (1/OPDIM) sum_{a < OPDIM} W^{M_a} with the inter-band spin bilinears
+ *   M_x: (0,1) = (1,0) = (2,3) = (3,2) = 1;   M_y: (0,1) = -i, (1,0) = +i, (2,3) = +i, (3,2) = -i;   M_z: (0,3) = (3,0) = 1, (1,2) = (2,1) = -1.
+ * dqmc_measure_timedisplaced_ph(j) (all chains) adds sum_B Re W(B (+) d, B) for every periodic site difference d = (dx, dy), bin
+ * dy L + dx, to the block of boundary j.  Preconditions: the last pair belongs to boundary j AND the context still stands on that
+ * boundary (G is the G(tau_j) the advance produced: call it before the next wrap or update); DQMC_EINVAL otherwise.
+ * Layout (doubles, dqmc_measure_td_ph_accum_size of them): count[n-1], then for j = 1 .. n-1 the charge sums [N], the spinZ sums [N]
+ * and the sdw sums [N], at offset (n-1) + (j-1) 3N; dividing by N and by the count gives the translation average.
+ * dqmc_measure_reset clears the block as well. */
+int dqmc_measure_timedisplaced_ph(dqmc_ctx* ctx, int j);
+size_t dqmc_measure_td_ph_accum_size(dqmc_ctx* ctx);    /* 0 without the reservation */
+int dqmc_measure_td_ph_read_host(dqmc_ctx* ctx, double* out);
+/* G(0) of the last pair's field configuration, selected chain; *slice as for dqmc_get_green_timedisplaced_host.  DQMC_EINVAL without
+ * td_particle_hole or if no pair was computed yet */
+int dqmc_get_green0_timedisplaced_host(dqmc_ctx* ctx, dqmc_cplx* g00, int* slice);
 
 /* set_exchange_parameter_value (detsdwopdim.cpp:5195-5197): r only enters the bosonic action */
 int dqmc_set_exchange_parameter(dqmc_ctx* ctx, double r);
