@@ -122,6 +122,7 @@ struct dqmc_ctx {
     uint64_t fam_launches[FAM_COUNT] = {0};
     double gemm_flops = 0.0;
     SubProf subprof{};                  // hooks handed to the launchers through Launch::sub while profiling is on
+    SvdProfHooks qr_apply_hooks{};      // and through QrWork::apply_hooks (timing of the k_qr_apply launches)
     std::vector<std::pair<int, int>> sub_open;      // (sub-family, begin event)
     double sub_ms[SUBFAM_COUNT] = {0}, sub_flops[SUBFAM_COUNT] = {0}, sub_bytes[SUBFAM_COUNT] = {0};
     uint64_t sub_launches[SUBFAM_COUNT] = {0};
@@ -190,6 +191,15 @@ static hipError_t copy_sync(dqmc_ctx* c, void* dst, const void* src, size_t byte
 
 static void prof_collect(dqmc_ctx* c);
 enum { PROF_EVENT_CAP = 8192 };     // events alive at most: beyond that the finished pairs are collected and reused
+// A fresh (begin, end) pair of timing events: records the begin event on st and returns its index; the end event is index + 1
+static int prof_event_pair(dqmc_ctx* c, hipStream_t st) {
+    if (c->ev_used + 2 > c->ev_pool.size())
+        for (int i = 0; i < 2; ++i) { hipEvent_t e; (void)hipEventCreate(&e); c->ev_pool.push_back(e); }
+    const int idx = (int)c->ev_used;
+    (void)hipEventRecord(c->ev_pool[idx], st);
+    c->ev_used += 2;
+    return idx;
+}
 
 struct ProfScope {
     dqmc_ctx* c; int fam; uint64_t launches; int idx = -1;     // idx: this scope's begin event (scopes may nest)
@@ -199,13 +209,8 @@ struct ProfScope {
         if (!c->prof) return;
         if (c->ev_used + 2 > PROF_EVENT_CAP && c->prof_depth == 0) prof_collect(c);   // not while an outer scope is open
         ++c->prof_depth;
-        if (c->ev_used + 2 > c->ev_pool.size()) {
-            for (int i = 0; i < 2; ++i) { hipEvent_t e; (void)hipEventCreate(&e); c->ev_pool.push_back(e); }
-        }
-        idx = (int)c->ev_used;
-        (void)hipEventRecord(c->ev_pool[idx], st);
+        idx = prof_event_pair(c, st);
         c->ev_open.push_back({fam, idx});
-        c->ev_used += 2;
     }
     ~ProfScope() {
         if (sync_check_on() && c->fault.empty()) {
@@ -861,12 +866,23 @@ extern "C" int dqmc_get_fields_all_host(dqmc_ctx* c, double* phi_all) {
 // ---------------------------------------------------------------------------------------------
 // device-side building blocks
 // ---------------------------------------------------------------------------------------------
+// C = op(A) op(B) with n_g x n_g operands; callers set the options (negate, accumulate, scales, sharedA / sharedB, ...) by name
+static GemmArgs gemm_square(dqmc_ctx* c, const cplx* A, int opA, const cplx* B, int opB, cplx* C) {
+    GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.A = A; g.lda = c->n_g; g.opA = opA; g.B = B; g.ldb = c->n_g; g.opB = opB; g.C = C; g.ldc = c->n_g;
+    g.M = g.N = g.K = c->n_g; g.Kmul = 1;
+    return g;
+}
+// every n_g^3 product of the model goes through here: flop accounting (a lower triangular op(B) takes half the multiply-adds) and timing
+static void run_gemm(dqmc_ctx* c, const GemmArgs& g) {
+    c->gemm_flops += (g.b_lower ? 4.0 : 8.0) * (double)g.M * g.N * g.K * c->nb;
+    ProfScope ps(c, FAM_GEMM, 1);
+    launch_gemm(c->lc, g);
+}
+
 // chain order of checkerboard{Left,Right}MultiplyBmat[Inv] (detsdwopdim.cpp:2076-2090, 2172-2186,
 // 2307-2324, 2406-2420)
-static void gemm_dev(dqmc_ctx* c, int opA, int opB, const cplx* A, const cplx* B, cplx* C,
-                     const double* kscale = nullptr, int kinv = 0, const double* rowscale = nullptr,
-                     const double* colscale = nullptr, int accumulate = 0, int sharedA = 0, int sharedB = 0, int negate = 0);
-
 static void bmult_dev(dqmc_ctx* c, int side, int inverse, int k2, int k1, cplx* A) {
     const int count = k2 - k1;
     if (count <= 0) return;
@@ -888,8 +904,9 @@ static void bmult_dev(dqmc_ctx* c, int side, int inverse, int k2, int k1, cplx* 
     for (int i = 0; i < count; ++i) {
         const int k = kfirst + i * kstep;
         auto hop = [&]() {
-            if (side == DQMC_LEFT) gemm_dev(c, 0, 0, PK, A, c->Tdense, nullptr, 0, nullptr, nullptr, 0, /*sharedA=*/1, 0);
-            else                   gemm_dev(c, 0, 0, A, PK, c->Tdense, nullptr, 0, nullptr, nullptr, 0, 0, /*sharedB=*/1);
+            GemmArgs g = (side == DQMC_LEFT) ? gemm_square(c, PK, 0, A, 0, c->Tdense) : gemm_square(c, A, 0, PK, 0, c->Tdense);
+            g.sharedA = (side == DQMC_LEFT); g.sharedB = !g.sharedA;
+            run_gemm(c, g);
             launch_copy(c->lc, c->Tdense, A, n2);
         };
         if (hop_first) hop();
@@ -902,28 +919,10 @@ static void bmult_dev(dqmc_ctx* c, int side, int inverse, int k2, int k1, cplx* 
     }
 }
 
-static void gemm_dev(dqmc_ctx* c, int opA, int opB, const cplx* A, const cplx* B, cplx* C,
-                     const double* kscale, int kinv, const double* rowscale,
-                     const double* colscale, int accumulate, int sharedA, int sharedB, int negate) {
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A = A; g.lda = c->n_g; g.opA = opA; g.B = B; g.ldb = c->n_g; g.opB = opB; g.C = C; g.ldc = c->n_g;
-    g.M = g.N = g.K = c->n_g; g.Kmul = 1;
-    g.kscale = kscale; g.kscale_invert = kinv; g.rowscale = rowscale; g.colscale = colscale; g.accumulate = accumulate;
-    g.sharedA = sharedA; g.sharedB = sharedB; g.negate = negate;
-    c->gemm_flops += 8.0 * (double)g.M * g.N * g.K * c->nb;
-    ProfScope ps(c, FAM_GEMM, 1);
-    launch_gemm(c->lc, g);
-}
-
 // udvDecompose (udv.h:68-102) of diag(rowscale) M diag(colscale)
 static void svd_prof_begin(void* u) {
     dqmc_ctx* c = (dqmc_ctx*)u;
-    if (c->ev_used + 2 > c->ev_pool.size())
-        for (int i = 0; i < 2; ++i) { hipEvent_t e; (void)hipEventCreate(&e); c->ev_pool.push_back(e); }
-    (void)hipEventRecord(c->ev_pool[c->ev_used], c->st);
-    c->ev_open.push_back({FAM_ROUNDS, (int)c->ev_used});
-    c->ev_used += 2;
+    c->ev_open.push_back({FAM_ROUNDS, prof_event_pair(c, c->st)});
 }
 static void svd_prof_end(void* u, int launches) {
     dqmc_ctx* c = (dqmc_ctx*)u;
@@ -936,11 +935,6 @@ static void qr_apply_prof_end(void* u, int launches) {
     dqmc_ctx* c = (dqmc_ctx*)u;
     (void)hipEventRecord(c->ev_pool[c->ev_open.back().second + 1], c->st);
     c->fam_launches[FAM_ROUNDS] += launches;
-}
-static const SvdProfHooks* qr_hooks(dqmc_ctx* c, SvdProfHooks& h) {
-    if (!c->prof) return nullptr;
-    h = SvdProfHooks{svd_prof_begin, qr_apply_prof_end, c};
-    return &h;
 }
 static int udv_dev(dqmc_ctx* c, const cplx* M, const double* colscale, const double* rowscale, UdVSlot out) {
     SvdProfHooks hooks{svd_prof_begin, svd_prof_end, c};
@@ -978,176 +972,169 @@ static int chol_failed(dqmc_ctx* c, int* failed) {
     return DQMC_OK;
 }
 
+// Pivoted QR of M' = diag(rs) M diag(cs) (of its adjoint if transpose), M' P = Q R: the columns are ranked by their norms (qr_perm = P)
+// and R is left in sw.A.  qr_bgs (n > 1024): block Gram-Schmidt + Cholesky-QR2 on the GEMM kernel instead of 144 tall Householder panels
+// (kernels_qr.hip); it holds on the graded B-chains of udt_dev and on the scale-split sum Z of green_qr (entries O(1)) alike.  A panel
+// too ill conditioned for Cholesky-QR (pivot test in k_chol64) is not an error: the factorisation is redone right here with the
+// unconditionally stable Householder panels, for all chains of the context (one stream synchronisation per factorisation, which at
+// these sizes takes tens of milliseconds).
+// Qdst: where an explicit Q goes.  form_q: the Householder panels form Q there as well; without it they leave Q in reflector form in
+// the QR workspace (run_qr_apply_q), so a caller that can live with either learns from q_explicit which one it got.
+struct QrOutcome { int launches; bool q_explicit; };
+static int qr_factorise(dqmc_ctx* c, const cplx* M, const double* cs, const double* rs, int transpose, cplx* Qdst, bool form_q, QrOutcome* out) {
+    const int n = c->n_g;
+    launch_scaled_norms_rank(c->lc, M, n, cs, rs, transpose, n, c->sw.norms, c->qr_perm, c->sw.rnorms);
+    launch_udt_init(c->lc, M, n, cs, rs, c->qr_perm, transpose, c->sw.A, n);
+    int launches = 3;                                   // norms, ranks, init
+    bool bgs = c->qr_bgs;
+    if (bgs) {
+        launches += run_qr_bgs(c->lc, n, c->sw.A, Qdst, c->qw);
+        int failed = 0;
+        { int rc = chol_failed(c, &failed); if (rc) return rc; }
+        if (failed) {
+            c->cholqr_fallbacks += 1;
+            bgs = false;
+            qr_reset_workspace(c->lc, n, c->qw);
+            launch_udt_init(c->lc, M, n, cs, rs, c->qr_perm, transpose, c->sw.A, n);
+            launches += 3;                              // two fills, init
+        }
+    }
+    if (!bgs) launches += run_qr(c->lc, n, c->sw.A, form_q ? Qdst : nullptr, c->qw);
+    c->qr_calls += 1;
+    *out = QrOutcome{launches, bgs || form_q};
+    return DQMC_OK;
+}
+
 // lazy != 0: the non-unitary factor T^H = (D^-1 R P^T)^H is not formed; R stays in sw.A, 1/d and the inverse permutation
 // go to qr_dinv / qr_perm_inv for the triangular chaining product of decompose_chained
 static int udt_dev(dqmc_ctx* c, const cplx* M, const double* colscale, const double* rowscale, int kind, UdVSlot out, int lazy = 0) {
     const int n = c->n_g;
     const int transpose = (kind == KIND_L);
     ProfScope ps(c, FAM_JACOBI, 0);
-    launch_scaled_norms_rank(c->lc, M, n, colscale, rowscale, transpose, n, c->sw.norms, c->qr_perm, c->sw.rnorms);
-    launch_udt_init(c->lc, M, n, colscale, rowscale, c->qr_perm, transpose, c->sw.A, n);
     cplx* Q = transpose ? out.Vt : out.U;
     cplx* Tt = transpose ? out.U : out.Vt;
-    SvdProfHooks hk;
-    c->qw.apply_hooks = qr_hooks(c, hk);
-    // n > 1024: block Gram-Schmidt + Cholesky-QR2 on the GEMM kernel instead of 144 tall Householder panels (kernels_qr.hip).  A panel
-    // too ill conditioned for Cholesky-QR (pivot test in k_chol64) is not an error: the factorisation is redone right here with the
-    // unconditionally stable Householder panels, for all chains of the context (one stream synchronisation per factorisation,
-    // which at these sizes takes tens of milliseconds).
-    int launches;
-    if (c->qr_bgs) {
-        launches = run_qr_bgs(c->lc, n, c->sw.A, Q, c->qw);
-        int failed = 0;
-        { int rc = chol_failed(c, &failed); if (rc) return rc; }
-        if (failed) {
-            c->cholqr_fallbacks += 1;
-            qr_reset_workspace(c->lc, n, c->qw);
-            launch_udt_init(c->lc, M, n, colscale, rowscale, c->qr_perm, transpose, c->sw.A, n);
-            launches += 3 + run_qr(c->lc, n, c->sw.A, Q, c->qw);
-        }
-    } else launches = run_qr(c->lc, n, c->sw.A, Q, c->qw);
+    QrOutcome qr;
+    { int rc = qr_factorise(c, M, colscale, rowscale, transpose, Q, true, &qr); if (rc) return rc; }
     launch_udt_diag(c->lc, c->sw.A, n, out.d);
     if (lazy) launch_udt_lazy(c->lc, out.d, c->qr_perm, n, c->qr_dinv, c->qr_perm_inv);
     else launch_udt_tmat(c->lc, c->sw.A, out.d, c->qr_perm, n, Tt);
-    c->fam_launches[FAM_JACOBI] += launches + 5;
-    c->qr_calls += 1;
+    c->fam_launches[FAM_JACOBI] += qr.launches + 2;     // + diag, lazy / tmat
     return DQMC_OK;
 }
 
-// Time-displaced pair from the factorisation of Z that green_qr has just made (dqmc_hip.h):
-//   G(tau,0) = [V_l Dlmax^-1] Z^-1 [Drmin V_r^H],   G(0,tau) = -[U_l Dlmin] Z^-1 [Drmax^-1 U_r^H].
-// The outer brackets of G(tau) are T3 = [V_l Dlmax^-1] (first half of Z^-1) and T1 (the other half with [Drmax^-1 U_r^H]), so each
-// new matrix is one more triangular solve (LU route) or Q application (QR route) and one GEMM.
-//   LU route, P Z = L U:  G(tau,0) = T3 [(V_r Drmin P^T) L^-H]^H,   G(0,tau) = -[(U_l Dlmin) U^-1] T1^H
-//   QR route, Z P = Q R:  G(tau,0) = T3 [Q^H Drmin V_r^H],          G(0,tau) = -[(U_l Dlmin P) R^-1] T1
-// td_particle_hole: the equal-time G(0) of the SAME field configuration,
-//   1 - G(0) = B(beta,tau) G(tau) B(tau,0) = [U_l Dlmin] Z^-1 [Drmin V_r^H]
-// (the fourth combination of the outer brackets; no unitarity of V is assumed): the left factor of G(0,tau), td_W, times the right
-// factor of G(tau,0) -- one GEMM with the negate epilogue, then + 1 on the diagonal (eye.d holds ones).
-static void green0_from_factors(dqmc_ctx* c, int opB, const cplx* right) {
-    gemm_dev(c, 0, opB, c->td_W, right, c->G00, nullptr, 0, nullptr, nullptr, 0, 0, 0, /*negate=*/1);
-    ProfScope ps(c, FAM_OTHER, 1);
-    launch_add_diag(c->lc, c->G00, c->eye.d, c->n_g);
-}
-static void td_from_lu(dqmc_ctx* c, const UdVSlot& L, const UdVSlot& R) {
+// ---------------------------------------------------------------------------------------------
+// G, the time-displaced pair and G(0) of one boundary from one factorisation of the scale-split matrix
+//   Z = Drmax^-1 (U_r^H V_l) Dlmax^-1 + Drmin (V_r^H U_l) Dlmin
+// (the scales of the L-type and the R-type factorisation split into their parts > 1 and <= 1, so that Z has entries O(1)).  Each of
+// the four matrices is a left bracket {V_l Dlmax^-1, U_l Dlmin} and a right bracket {Drmax^-1 U_r^H, Drmin V_r^H} around Z^-1
+// (dqmc_hip.h; no unitarity of the graded factors is assumed):
+//   G        =  [V_l Dlmax^-1] Z^-1 [Drmax^-1 U_r^H] =  A_max B_max
+//   G(tau,0) =  [V_l Dlmax^-1] Z^-1 [Drmin V_r^H]    =  A_max B_min
+//   G(0,tau) = -[U_l Dlmin]    Z^-1 [Drmax^-1 U_r^H] = -A_min B_max
+//   1 - G(0) =  [U_l Dlmin]    Z^-1 [Drmin V_r^H]    =  A_min B_min        (G(0) of the boundary's own field configuration)
+// where every half takes one factor of Z^-1 along: A = left_half(left bracket), B = right_half(right bracket).  So each matrix beyond
+// G costs one more triangular solve or Q application and one GEMM.  Per route of the factorisation (ZFactors):
+//   LU          P Z = L U, L \ U in T2 (n_g <= 512)   A = X U^-1      B = L^-1 P Y, kept as its adjoint (Y^H P^T) L^-H (two right-hand
+//                                                                     triangular solves; the products take it with opB = 1)
+//   reflectors  Z P = Q R, R in sw.A                  A = X P R^-1    B = Q^H Y, Q applied from the QR workspace and never formed
+//   explicit Q  Z P = Q R, R in sw.A, Q in T4         A = X P R^-1    B = Q^H Y by GEMM, Y staged in a scratch matrix first
+// (dqmc_tuning::green_variant = 1 keeps a QR route where LU would do; Q is explicit when block Gram-Schmidt made it.)
+// Buffers:  A_max -> T3 and B_max -> T1: scratch of the chain step before, dead once that was decomposed.
+//           B_min -> T4 on the LU route: T2 still holds L \ U, and no Q lives in T4.
+//           B_min -> T2 on the QR routes: the factorisation worked on a copy of Z in sw.A (also when it fell back and copied it
+//                    again), so T2 is free from there on, and T4 may hold Q.
+//           A_min -> td_W, the only buffer of its own the pair has.  The explicit-Q route stages Y in sw.V for B_max (Jacobi
+//                    workspace: idle in QR mode, done with in SVD mode) and in td_W for B_min -- so B_min comes before A_min.
+// The helpers return the launches they made in the decomposition family; their GEMMs count themselves (run_gemm).
+// ---------------------------------------------------------------------------------------------
+enum ZRoute { Z_LU, Z_QR_REFLECTORS, Z_QR_EXPLICIT };
+struct ZFactors {
+    ZRoute route;
+    const cplx* tri;        // the triangular factor(s): T2 = L \ U, or sw.A = R
+    const cplx* Q;          // T4 on the explicit-Q route, else nullptr
+    int adjoint;            // the right halves are stored as their adjoints: opB of every product A B
+};
+// factorises Z (in T2) and writes the log-det vector: |det Z| = prod |U_kk| = prod |R_kk|
+static int factorise_z(dqmc_ctx* c, double* svout, ZFactors* z, int* launches) {
     const int n = c->n_g;
-    {
-        ProfScope ps(c, FAM_JACOBI, 0);
-        launch_gather_scale_cols(c->lc, R.Vt, c->rmin, c->qr_perm, n, c->T4);         // T4 = (V_r Drmin) P^T
-        int launches = run_trsm_right_upper(c->lc, n, c->T2, c->T4, c->qw, 1, 1);      // T4 <- T4 L^-H
-        launch_permute_scale_cols(c->lc, L.U, c->lmin, nullptr, n, c->td_W);           // td_W = U_l Dlmin
-        launches += run_trsm_right_upper(c->lc, n, c->T2, c->td_W, c->qw);             // td_W <- td_W U^-1
-        c->fam_launches[FAM_JACOBI] += launches + 2;
+    ProfScope ps(c, FAM_JACOBI, 0);
+    if (c->green_lu) {
+        *launches = run_lu(c->lc, n, c->T2, c->qr_perm, c->lu_swaps, c->lu_tneg);      // T2 = L \ U, qr_perm = row permutation
+        c->lu_calls += 1;
+        *z = ZFactors{Z_LU, c->T2, nullptr, 1};
+    } else {
+        QrOutcome qr;
+        { int rc = qr_factorise(c, c->T2, nullptr, nullptr, 0, c->T4, false, &qr); if (rc) return rc; }
+        *launches = qr.launches;
+        *z = ZFactors{qr.q_explicit ? Z_QR_EXPLICIT : Z_QR_REFLECTORS, c->sw.A, qr.q_explicit ? c->T4 : nullptr, 0};
     }
-    gemm_dev(c, 0, 1, c->T3, c->T4, c->GT0);
-    gemm_dev(c, 0, 1, c->td_W, c->T1, c->G0T, nullptr, 0, nullptr, nullptr, 0, 0, 0, /*negate=*/1);
-    if (c->G00) green0_from_factors(c, 1, c->T4);                                      // G(0) = 1 - td_W T4^H
+    launch_logdet_vector(c->lc, z->tri, c->rmax_inv, c->lmax_inv, n, svout);
+    *launches += 1;
+    return DQMC_OK;
 }
-// bgs: Q is explicit in T4 (block Gram-Schmidt), else it is in reflector form in the QR workspace; R in sw.A
-static void td_from_qr(dqmc_ctx* c, const UdVSlot& L, const UdVSlot& R, bool bgs) {
+// dst = (X diag(scale)) U^-1 (LU)  or  (X diag(scale)) P R^-1 (QR routes)
+static int left_half(dqmc_ctx* c, const ZFactors& z, const cplx* X, const double* scale, cplx* dst) {
+    ProfScope ps(c, FAM_JACOBI, 0);
+    launch_permute_scale_cols(c->lc, X, scale, z.route == Z_LU ? nullptr : c->qr_perm, c->n_g, dst);
+    return 1 + run_trsm_right_upper(c->lc, c->n_g, z.tri, dst, c->qw);
+}
+// dst = [L^-1 P (diag(scale) Yh^H)]^H (LU)  or  Q^H (diag(scale) Yh^H) (QR routes); stage: scratch of the explicit-Q route
+static int right_half(dqmc_ctx* c, const ZFactors& z, const cplx* Yh, const double* scale, cplx* dst, cplx* stage) {
     const int n = c->n_g;
+    int launches = 1;
     {
         ProfScope ps(c, FAM_JACOBI, 0);
-        int launches = 0;
-        if (bgs) launch_udt_init(c->lc, R.Vt, n, c->rmin, nullptr, nullptr, 1, c->td_W, n);     // td_W = Drmin V_r^H
-        else {
-            launch_udt_init(c->lc, R.Vt, n, c->rmin, nullptr, nullptr, 1, c->T2, n);            // T2 = Drmin V_r^H
-            SvdProfHooks hk;
-            c->qw.apply_hooks = qr_hooks(c, hk);
-            launches += run_qr_apply_q(c->lc, n, c->T2, c->qw, 1);                               // T2 = Q^H Drmin V_r^H
-        }
-        c->fam_launches[FAM_JACOBI] += launches + 1;
+        if (z.route == Z_LU) {
+            launch_gather_scale_cols(c->lc, Yh, scale, c->qr_perm, n, dst);                  // dst = (Yh diag(scale)) P^T
+            launches += run_trsm_right_upper(c->lc, n, z.tri, dst, c->qw, 1, 1);             // dst <- dst L^-H
+        } else if (z.route == Z_QR_REFLECTORS) {
+            launch_udt_init(c->lc, Yh, n, scale, nullptr, nullptr, 1, dst, n);               // dst = diag(scale) Yh^H
+            launches += run_qr_apply_q(c->lc, n, dst, c->qw, 1);                             // dst <- Q^H dst
+        } else launch_udt_init(c->lc, Yh, n, scale, nullptr, nullptr, 1, stage, n);          // stage = diag(scale) Yh^H
     }
-    if (bgs) gemm_dev(c, 1, 0, c->T4, c->td_W, c->T2);                                           // T2 = Q^H Drmin V_r^H
-    gemm_dev(c, 0, 0, c->T3, c->T2, c->GT0);
-    {
-        ProfScope ps(c, FAM_JACOBI, 0);
-        launch_permute_scale_cols(c->lc, L.U, c->lmin, c->qr_perm, n, c->td_W);                // td_W = U_l Dlmin P
-        c->fam_launches[FAM_JACOBI] += 1 + run_trsm_right_upper(c->lc, n, c->sw.A, c->td_W, c->qw);   // td_W <- td_W R^-1
-    }
-    gemm_dev(c, 0, 0, c->td_W, c->T1, c->G0T, nullptr, 0, nullptr, nullptr, 0, 0, 0, /*negate=*/1);
-    // T2 still holds Q^H Drmin V_r^H: nothing above writes it after G(tau,0), and td_W (scratch of the bgs branch first) has its final value
-    if (c->G00) green0_from_factors(c, 0, c->T2);                                                // G(0) = 1 - td_W T2
+    if (z.route == Z_QR_EXPLICIT) run_gemm(c, gemm_square(c, z.Q, 1, stage, 0, dst));        // dst = Q^H stage
+    return launches;
 }
 
-// G from an L-type and an R-type factorisation (nullptr = identity), with the scales split into their
-// parts > 1 and <= 1 so that the matrix that is actually inverted,
-//   Z = Drmax^-1 (U_r^H V_l) Dlmax^-1 + Drmin (V_r^H U_l) Dlmin,
-// has entries O(1):  G = (V_l Dlmax^-1) Z^-1 (U_r Drmax^-1)^H,  Z P = Q R  =>  Z^-1 = P R^-1 Q^H.
-// Gout = nullptr: G itself is not formed (SVD mode builds only the time-displaced pair here); td: also G(tau,0), G(0,tau).
+// Lp / Rp: the L-type / R-type factorisation (nullptr = identity).  Gout = nullptr: G itself is not formed (SVD mode builds only the
+// time-displaced pair here); td: also G(tau,0), G(0,tau) and, with dqmc_params::td_particle_hole, G(0).
 static int green_qr(dqmc_ctx* c, const UdVSlot* Lp, const UdVSlot* Rp, cplx* Gout, double* svout, bool td = false) {
-    const int n = c->n_g;
     const UdVSlot& L = Lp ? *Lp : c->eye;
     const UdVSlot& R = Rp ? *Rp : c->eye;
     {
         ProfScope ps(c, FAM_OTHER, 2);
-        launch_split_scales(c->lc, R.d, n, c->rmax_inv, c->rmin);
-        launch_split_scales(c->lc, L.d, n, c->lmax_inv, c->lmin);
+        launch_split_scales(c->lc, R.d, c->n_g, c->rmax_inv, c->rmin);
+        launch_split_scales(c->lc, L.d, c->n_g, c->lmax_inv, c->lmin);
     }
-    gemm_dev(c, 1, 0, R.U, L.Vt, c->T2, nullptr, 0, c->rmax_inv, c->lmax_inv, 0);
-    gemm_dev(c, 1, 0, R.Vt, L.U, c->T2, nullptr, 0, c->rmin, c->lmin, 1);
-    // Z^-1 from an LU factorisation with partial pivoting (kernels_lu.hip; n_g <= 512): P Z = L U, so
-    //   G = [(V_l Dlmax^-1) U^-1] [L^-1 P Drmax^-1 U_r^H] = T3 T1^H  with  T1 = (U_r Drmax^-1 P^T) L^-H,
-    // both brackets as right-hand triangular solves.  dqmc_tuning::green_variant = 1 keeps the QR route below (A/B, larger n_g).
-    if (c->green_lu) {
-        {
-            ProfScope ps(c, FAM_JACOBI, 0);
-            int launches = run_lu(c->lc, n, c->T2, c->qr_perm, c->lu_swaps, c->lu_tneg);                  // T2 = L \ U, qr_perm = row permutation
-            launch_permute_scale_cols(c->lc, L.Vt, c->lmax_inv, nullptr, n, c->T3);
-            launches += run_trsm_right_upper(c->lc, n, c->T2, c->T3, c->qw);                  // T3 = (V_l Dlmax^-1) U^-1
-            launch_logdet_vector(c->lc, c->T2, c->rmax_inv, c->lmax_inv, n, svout);           // |det Z| = prod |U_kk|
-            launch_gather_scale_cols(c->lc, R.U, c->rmax_inv, c->qr_perm, n, c->T1);          // T1 = (U_r Drmax^-1) P^T
-            launches += run_trsm_right_upper(c->lc, n, c->T2, c->T1, c->qw, 1, 1);            // T1 <- T1 (L^H)^-1
-            c->fam_launches[FAM_JACOBI] += launches + 3;
-            c->lu_calls += 1;
-        }
-        if (Gout) gemm_dev(c, 0, 1, c->T3, c->T1, Gout);                                      // G = T3 T1^H
-        if (td) td_from_lu(c, *Lp, *Rp);
-        return DQMC_OK;
-    }
-    bool fell_back = false;
-    {
-        ProfScope ps(c, FAM_JACOBI, 0);
-        launch_scaled_norms_rank(c->lc, c->T2, n, nullptr, nullptr, 0, n, c->sw.norms, c->qr_perm, c->sw.rnorms);
-        launch_udt_init(c->lc, c->T2, n, nullptr, nullptr, c->qr_perm, 0, c->sw.A, n);
-        SvdProfHooks hk;
-        c->qw.apply_hooks = qr_hooks(c, hk);
-        // the matrix inverted here is not a graded B-chain but the scale-split sum Z (entries O(1)); the block Gram-Schmidt QR holds
-        // on it as well (tests: every QR-mode fixture with qr_variant = 2, green_variant = 1; the reference's G at n_g = 2304); a panel
-        // that fails the pivot test sends the factorisation to the Householder panels.
-        bool bgs = c->qr_bgs;
-        int launches = 0;
-        if (bgs) {
-            launches = run_qr_bgs(c->lc, n, c->sw.A, c->T4, c->qw);        // explicit Q in T4
-            int failed = 0;
-            { int rc = chol_failed(c, &failed); if (rc) return rc; }
-            if (failed) {
-                c->cholqr_fallbacks += 1;
-                bgs = false;
-                fell_back = true;
-                qr_reset_workspace(c->lc, n, c->qw);
-                launch_udt_init(c->lc, c->T2, n, nullptr, nullptr, c->qr_perm, 0, c->sw.A, n);
-                launches += 3;
-            }
-        }
-        if (!bgs) launches += run_qr(c->lc, n, c->sw.A, nullptr, c->qw);   // sw.A = R factor, Q stays in reflector form
-        launch_permute_scale_cols(c->lc, L.Vt, c->lmax_inv, c->qr_perm, n, c->T3);
-        launches += run_trsm_right_upper(c->lc, n, c->sw.A, c->T3, c->qw);   // T3 = (V_l Dlmax^-1 P) R^-1
-        launch_logdet_vector(c->lc, c->sw.A, c->rmax_inv, c->lmax_inv, n, svout);
-        if (bgs) {
-            launch_udt_init(c->lc, R.U, n, c->rmax_inv, nullptr, nullptr, 1, c->sw.V, n);   // sw.V = Drmax^-1 U_r^H
-            c->fam_launches[FAM_JACOBI] += launches + 6;
-            c->qr_calls += 1;
-            gemm_dev(c, 1, 0, c->T4, c->sw.V, c->T1);                     // T1 = Q^H Drmax^-1 U_r^H
-        } else {
-            launch_udt_init(c->lc, R.U, n, c->rmax_inv, nullptr, nullptr, 1, c->T1, n);   // T1 = Drmax^-1 U_r^H
-            launches += run_qr_apply_q(c->lc, n, c->T1, c->qw, 1);            // T1 = Q^H Drmax^-1 U_r^H: Q is never formed
-            c->fam_launches[FAM_JACOBI] += launches + 6;
-            c->qr_calls += 1;
+    GemmArgs g = gemm_square(c, R.U, 1, L.Vt, 0, c->T2);
+    g.rowscale = c->rmax_inv; g.colscale = c->lmax_inv;
+    run_gemm(c, g);
+    g = gemm_square(c, R.Vt, 1, L.U, 0, c->T2);
+    g.rowscale = c->rmin; g.colscale = c->lmin; g.accumulate = 1;
+    run_gemm(c, g);
+    ZFactors z;
+    int launches = 0;
+    { int rc = factorise_z(c, svout, &z, &launches); if (rc) return rc; }
+    launches += left_half(c, z, L.Vt, c->lmax_inv, c->T3);                                   // A_max
+    launches += right_half(c, z, R.U, c->rmax_inv, c->T1, c->sw.V);                          // B_max
+    if (Gout) run_gemm(c, gemm_square(c, c->T3, 0, c->T1, z.adjoint, Gout));
+    if (td) {
+        cplx* Bmin = z.route == Z_LU ? c->T4 : c->T2;
+        launches += right_half(c, z, R.Vt, c->rmin, Bmin, c->td_W);
+        launches += left_half(c, z, L.U, c->lmin, c->td_W);                                  // A_min
+        run_gemm(c, gemm_square(c, c->T3, 0, Bmin, z.adjoint, c->GT0));
+        g = gemm_square(c, c->td_W, 0, c->T1, z.adjoint, c->G0T);
+        g.negate = 1;
+        run_gemm(c, g);
+        if (c->G00) {                                                                        // G(0) = 1 - A_min B_min (eye.d holds ones)
+            g = gemm_square(c, c->td_W, 0, Bmin, z.adjoint, c->G00);
+            g.negate = 1;
+            run_gemm(c, g);
+            ProfScope ps(c, FAM_OTHER, 1);
+            launch_add_diag(c->lc, c->G00, c->eye.d, c->n_g);
         }
     }
-    if (Gout) gemm_dev(c, 0, 0, c->T3, c->T1, Gout);                       // G = T3 T1
-    if (td) td_from_qr(c, *Lp, *Rp, c->qr_bgs && !fell_back);
+    c->fam_launches[FAM_JACOBI] += launches;
     return DQMC_OK;
 }
 
@@ -1168,36 +1155,39 @@ static int decompose_chained(dqmc_ctx* c, const cplx* M, const double* colscale,
     if (c->stab == DQMC_STAB_QR) {
         int rc = udt_dev(c, M, colscale, rowscale, kind, out, 1);
         if (rc) return rc;
-        GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        g.A = Aold; g.lda = c->n_g; g.opA = 0; g.a_kgather = c->qr_perm_inv;
-        g.B = c->sw.A; g.ldb = c->n_g; g.opB = 1; g.b_lower = 1;
-        g.C = dest; g.ldc = c->n_g; g.M = g.N = g.K = c->n_g; g.Kmul = 1; g.colscale = c->qr_dinv;
-        c->gemm_flops += 4.0 * (double)g.M * g.N * g.K * c->nb;
-        ProfScope ps(c, FAM_GEMM, 1);
-        launch_gemm(c->lc, g);
+        GemmArgs g = gemm_square(c, Aold, 0, c->sw.A, 1, dest);               // dest = Aold[:, P^-1] R^H D^-1
+        g.a_kgather = c->qr_perm_inv; g.b_lower = 1; g.colscale = c->qr_dinv;
+        run_gemm(c, g);
         return DQMC_OK;
     }
     UdVSlot t = out;
     if (kind == KIND_R) t.Vt = c->tmpudv.Vt; else t.U = c->tmpudv.U;
     int rc = decompose(c, M, colscale, rowscale, kind, t);
     if (rc) return rc;
-    gemm_dev(c, 0, 0, Aold, (kind == KIND_R) ? c->tmpudv.Vt : c->tmpudv.U, dest);
+    run_gemm(c, gemm_square(c, Aold, 0, (kind == KIND_R) ? c->tmpudv.Vt : c->tmpudv.U, 0, dest));
     return DQMC_OK;
 }
 
+// SVD mode: G = (Vl t.Vt) diag(1 / sv) (Ur t.U)^H from the SVD t of the matrix inside the inverse (t.d = sv)
+static void green_from_svd(dqmc_ctx* c, const cplx* Vl, const cplx* Ur, const UdVSlot& t) {
+    run_gemm(c, gemm_square(c, Vl, 0, t.Vt, 0, c->T3));                   // Vt_product
+    run_gemm(c, gemm_square(c, Ur, 0, t.U, 0, c->T4));                    // U_product
+    GemmArgs g = gemm_square(c, c->T3, 0, c->T4, 1, c->G);
+    g.kscale = c->sv; g.kscale_invert = 1;
+    run_gemm(c, g);
+}
 // greenFromUdV (detmodel.h:769-818)
 // While the time-displaced functions are on, this is where they come from (every call is at an interior boundary).
 static int green_from_udv(dqmc_ctx* c, const UdVSlot& L, const UdVSlot& R) {
     if (c->stab == DQMC_STAB_QR) return green_qr(c, &L, &R, c->G, c->sv, c->td_on);
-    gemm_dev(c, 1, 0, R.U, L.Vt, c->T2);                                  // UtVt_rl = U_r^H V_t_l
-    gemm_dev(c, 1, 0, R.Vt, L.U, c->T2, nullptr, 0, R.d, L.d, 1);         // += diag(d_r) (V_t_r^H U_l) diag(d_l)
+    run_gemm(c, gemm_square(c, R.U, 1, L.Vt, 0, c->T2));                  // UtVt_rl = U_r^H V_t_l
+    GemmArgs g = gemm_square(c, R.Vt, 1, L.U, 0, c->T2);                  // += diag(d_r) (V_t_r^H U_l) diag(d_l)
+    g.rowscale = R.d; g.colscale = L.d; g.accumulate = 1;
+    run_gemm(c, g);
     UdVSlot t = c->tmpudv; t.d = c->sv;
     int rc = udv_dev(c, c->T2, nullptr, nullptr, t);
     if (rc) return rc;
-    gemm_dev(c, 0, 0, L.Vt, t.Vt, c->T3);                                 // Vt_product
-    gemm_dev(c, 0, 0, R.U, t.U, c->T4);                                   // U_product
-    gemm_dev(c, 0, 1, c->T3, c->T4, c->G, c->sv, 1);                      // G = Vt_product diag(1/sv) U_product^H
+    green_from_svd(c, L.Vt, R.U, t);
     // SVD mode: G stays on the path above; the pair comes from the scale-split Z, built and factorised after G
     if (c->td_on) return green_qr(c, &L, &R, nullptr, c->td_sv, true);
     return DQMC_OK;
@@ -1205,14 +1195,12 @@ static int green_from_udv(dqmc_ctx* c, const UdVSlot& L, const UdVSlot& R) {
 // greenFromEye_and_UdV (detmodel.h:823-860); kind tells whether the factorisation is R-type or L-type
 static int green_from_eye(dqmc_ctx* c, const UdVSlot& R, int kind) {
     if (c->stab == DQMC_STAB_QR) return (kind == KIND_R) ? green_qr(c, nullptr, &R, c->G, c->sv) : green_qr(c, &R, nullptr, c->G, c->sv);
-    gemm_dev(c, 1, 0, R.U, R.Vt, c->T2);
+    run_gemm(c, gemm_square(c, R.U, 1, R.Vt, 0, c->T2));
     { ProfScope ps(c, FAM_OTHER, 1); launch_add_diag(c->lc, c->T2, R.d, c->n_g); }
     UdVSlot t = c->tmpudv; t.d = c->sv;
     int rc = udv_dev(c, c->T2, nullptr, nullptr, t);
     if (rc) return rc;
-    gemm_dev(c, 0, 0, R.Vt, t.Vt, c->T3);
-    gemm_dev(c, 0, 0, R.U, t.U, c->T4);
-    gemm_dev(c, 0, 1, c->T3, c->T4, c->G, c->sv, 1);
+    green_from_svd(c, R.Vt, R.U, t);
     return DQMC_OK;
 }
 
@@ -1512,7 +1500,7 @@ extern "C" int dqmc_gemm_host(dqmc_ctx* c, int opA, int opB, const dqmc_cplx* A,
         HIPCHK(hipMemcpyAsync(chainp(c, c->T1, b), A, n2 * sizeof(cplx), hipMemcpyHostToDevice, c->st));
         HIPCHK(hipMemcpyAsync(chainp(c, c->T2, b), B, n2 * sizeof(cplx), hipMemcpyHostToDevice, c->st));
     }
-    gemm_dev(c, opA, opB, c->T1, c->T2, c->T3);
+    run_gemm(c, gemm_square(c, c->T1, opA, c->T2, opB, c->T3));
     HIPCHK(hipMemcpyAsync(C, selp(c, c->T3), n2 * sizeof(cplx), hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
     return finish(c, "dqmc_gemm_host");
@@ -1614,8 +1602,12 @@ static void shift_green_dev(dqmc_ctx* c, const cplx* src = nullptr) {
         launch_bmult(c->lc, nullptr, c->hm, DQMC_RIGHT, 1, 0, 1, 1, c->T1, c->n_g, /*shift=*/1);   // right: +sinh half steps
         launch_bmult(c->lc, nullptr, c->hm, DQMC_LEFT, 0, 0, 1, 1, c->T1, c->n_g, /*shift=*/1);    // left:  -sinh half steps
     } else {
-        gemm_dev(c, 0, 0, c->T1, c->propKh[1], c->Tdense, nullptr, 0, nullptr, nullptr, 0, 0, /*sharedB=*/1);
-        gemm_dev(c, 0, 0, c->propKh[0], c->Tdense, c->T1, nullptr, 0, nullptr, nullptr, 0, /*sharedA=*/1, 0);
+        GemmArgs g = gemm_square(c, c->T1, 0, c->propKh[1], 0, c->Tdense);
+        g.sharedB = 1;
+        run_gemm(c, g);
+        g = gemm_square(c, c->propKh[0], 0, c->Tdense, 0, c->T1);
+        g.sharedA = 1;
+        run_gemm(c, g);
     }
 }
 extern "C" int dqmc_shift_green_symmetric_host(dqmc_ctx* c, dqmc_cplx* out) {
@@ -1826,11 +1818,7 @@ extern "C" int dqmc_set_exchange_parameter(dqmc_ctx* c, double r) {
 // ---------------------------------------------------------------------------------------------
 static void sub_prof_begin(void* u, int sub) {
     dqmc_ctx* c = (dqmc_ctx*)u;
-    if (c->ev_used + 2 > c->ev_pool.size())
-        for (int i = 0; i < 2; ++i) { hipEvent_t e; (void)hipEventCreate(&e); c->ev_pool.push_back(e); }
-    (void)hipEventRecord(c->ev_pool[c->ev_used], c->st);
-    c->sub_open.push_back({sub, (int)c->ev_used});
-    c->ev_used += 2;
+    c->sub_open.push_back({sub, prof_event_pair(c, c->st)});
 }
 static void sub_prof_end(void* u, int sub, double flops, double bytes) {
     dqmc_ctx* c = (dqmc_ctx*)u;
@@ -1861,6 +1849,8 @@ extern "C" int dqmc_profile_enable(dqmc_ctx* c, int on) {
     c->prof = on != 0;
     c->subprof = SubProf{sub_prof_begin, sub_prof_end, c};
     c->lc.sub = c->prof ? &c->subprof : nullptr;
+    c->qr_apply_hooks = SvdProfHooks{svd_prof_begin, qr_apply_prof_end, c};
+    c->qw.apply_hooks = c->prof ? &c->qr_apply_hooks : nullptr;
     for (int i = 0; i < FAM_COUNT; ++i) { c->fam_ms[i] = 0; c->fam_launches[i] = 0; }
     for (int i = 0; i < SUBFAM_COUNT; ++i) { c->sub_ms[i] = 0; c->sub_flops[i] = 0; c->sub_bytes[i] = 0; c->sub_launches[i] = 0; }
     c->svd_calls = 0; c->svd_sweeps_total = 0; c->svd_sweeps_max = 0; c->qr_calls = 0; c->lu_calls = 0; c->gemm_flops = 0.0;
