@@ -201,6 +201,9 @@ SYMBOLS = [
     ("dqmc_measure_td_ph_accum_size", C.c_size_t, [_P]),
     ("dqmc_measure_td_ph_read_host", C.c_int, [_P, _DP]),
     ("dqmc_get_green0_timedisplaced_host", C.c_int, [_P, _P, C.POINTER(C.c_int)]),
+    ("dqmc_measure_timedisplaced_current", C.c_int, [_P, C.c_int]),
+    ("dqmc_measure_td_current_accum_size", C.c_size_t, [_P]),
+    ("dqmc_measure_td_current_read_host", C.c_int, [_P, _DP]),
     ("dqmc_profile_enable", C.c_int, [_P, C.c_int]),
     ("dqmc_profile_read", C.c_int, [_P, C.POINTER(dqmc_profile)]),
     ("detsdw_create", C.c_int, [C.POINTER(detsdw_params), C.POINTER(_P)]),

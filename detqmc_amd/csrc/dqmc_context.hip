@@ -84,6 +84,10 @@ struct dqmc_ctx {
     cplx *G00 = nullptr, *ph_H = nullptr, *ph_ob = nullptr;
     double* tdphacc = nullptr;
     size_t tdphacc_n = 0;
+    // td_particle_hole == 2: bond amplitudes (shared by the chains), one-body values and accumulators of the current-current correlators
+    cplx *cur_bt = nullptr, *cur_ob = nullptr;
+    double* tdcacc = nullptr;
+    size_t tdcacc_n = 0;
     SvdWork sw{};
     double hub_e_m2a = 1.0, hub_e_p2a = 1.0;  // Hubbard: exp(-+2 alpha) of weightRatioSingleFlip (dethubbard.cpp:866-867)
     int stab = 0;                       // DQMC_STAB_SVD / DQMC_STAB_QR
@@ -399,37 +403,61 @@ static void herm_exp_dense(int n, std::vector<hc>& A, double pref_minus, double 
     }
 }
 
-static void build_dense_propK(const dqmc_params& p, const std::vector<int>& neigh, int MSF,
-                              std::vector<hc>& out_minus, std::vector<hc>& out_plus, double tfac = 1.0) {
-    const int L = p.L, N = L * L, ng = MSF * N;
+// Hopping matrix of one band's stored sector (setupPropK, detsdwopdim.cpp:1210-1285), row major K[row * N + col]: -mu on the diagonal,
+// -t on the bonds with the APBC signs and the Peierls phases of zmag[XUP] / zmag[YDOWN]
+static void build_hopping_K(const dqmc_params& p, const std::vector<int>& neigh, int band, std::vector<hc>& K) {
+    const int L = p.L, N = L * L;
     const double hopHor[2] = {p.txhor, p.tyhor}, hopVer[2] = {p.txver, p.tyver}, mu[2] = {p.mux, p.muy};
     const bool apbc_x = (p.bc == DQMC_BC_APBC_X || p.bc == DQMC_BC_APBC_XY);
     const bool apbc_y = (p.bc == DQMC_BC_APBC_Y || p.bc == DQMC_BC_APBC_XY);
     const double zmag = p.weakZflux ? 1.0 / N : 0.0, pi = M_PI;
+    K.assign((size_t)N * N, hc(0.0));
+    for (int i = 0; i < N; ++i) K[(size_t)i * N + i] = -mu[band];
+    for (int site = 0; site < N; ++site) {
+        const int sx = site % L, sy = site / L;
+        for (int dir = 0; dir < 4; ++dir) {           // XPLUS, XMINUS, YPLUS, YMINUS
+            double hop = dir < 2 ? hopHor[band] : hopVer[band];
+            if (apbc_x && ((sx == 0 && dir == 1) || (sx == L - 1 && dir == 0))) hop *= -1;
+            if (apbc_y && ((sy == 0 && dir == 3) || (sy == L - 1 && dir == 2))) hop *= -1;
+            hc phase = 1.0;
+            if (dir == 0) phase = std::exp(hc(0.0, -2.0 * pi * zmag * sy));
+            if (dir == 1) phase = std::exp(hc(0.0, +2.0 * pi * zmag * sy));
+            if (dir == 2 && sy == L - 1) phase = std::exp(hc(0.0, +2.0 * pi * zmag * L * sx));
+            if (dir == 3 && sy == 0) phase = std::exp(hc(0.0, -2.0 * pi * zmag * L * sx));
+            K[(size_t)site * N + neigh[dir * N + site]] -= hop * phase;
+        }
+    }
+}
+
+static void build_dense_propK(const dqmc_params& p, const std::vector<int>& neigh, int MSF,
+                              std::vector<hc>& out_minus, std::vector<hc>& out_plus, double tfac = 1.0) {
+    const int L = p.L, N = L * L, ng = MSF * N;
     out_minus.assign((size_t)ng * ng, hc(0.0)); out_plus.assign((size_t)ng * ng, hc(0.0));
     for (int band = 0; band < 2; ++band) {
-        std::vector<hc> K((size_t)N * N, hc(0.0));
-        for (int i = 0; i < N; ++i) K[(size_t)i * N + i] = -mu[band];
-        for (int site = 0; site < N; ++site) {
-            const int sx = site % L, sy = site / L;
-            for (int dir = 0; dir < 4; ++dir) {           // XPLUS, XMINUS, YPLUS, YMINUS
-                double hop = dir < 2 ? hopHor[band] : hopVer[band];
-                if (apbc_x && ((sx == 0 && dir == 1) || (sx == L - 1 && dir == 0))) hop *= -1;
-                if (apbc_y && ((sy == 0 && dir == 3) || (sy == L - 1 && dir == 2))) hop *= -1;
-                hc phase = 1.0;
-                if (dir == 0) phase = std::exp(hc(0.0, -2.0 * pi * zmag * sy));
-                if (dir == 1) phase = std::exp(hc(0.0, +2.0 * pi * zmag * sy));
-                if (dir == 2 && sy == L - 1) phase = std::exp(hc(0.0, +2.0 * pi * zmag * L * sx));
-                if (dir == 3 && sy == 0) phase = std::exp(hc(0.0, -2.0 * pi * zmag * L * sx));
-                K[(size_t)site * N + neigh[dir * N + site]] -= hop * phase;
-            }
-        }
+        std::vector<hc> K;
+        build_hopping_K(p, neigh, band, K);
         std::vector<hc> Em, Ep;
         herm_exp_dense(N, K, -p.dtau * tfac, +p.dtau * tfac, Em, Ep);
         for (int b = band; b < MSF; b += 2)
             for (int i = 0; i < N; ++i) for (int j = 0; j < N; ++j) {
                 out_minus[(size_t)(b * N + j) * ng + (b * N + i)] = Em[(size_t)i * N + j];
                 out_plus[(size_t)(b * N + j) * ng + (b * N + i)] = Ep[(size_t)i * N + j];
+            }
+    }
+}
+
+// Bond amplitudes of dqmc_measure_timedisplaced_current, bt[(mu * MSF + flavour) * N + site] = T_flavour(site) = K^flavour[site (+) mu, site]:
+// read off the hopping matrices above.  Stored flavours XUP, YDOWN (, XDOWN, YUP for O(3), which has no flux: the same two bands again).
+static void build_bond_table(const dqmc_params& p, const std::vector<int>& neigh, int MSF, std::vector<hc>& bt) {
+    const int N = p.L * p.L;
+    bt.assign((size_t)2 * MSF * N, hc(0.0));
+    for (int band = 0; band < 2; ++band) {
+        std::vector<hc> K;
+        build_hopping_K(p, neigh, band, K);
+        for (int mu = 0; mu < 2; ++mu)
+            for (int site = 0; site < N; ++site) {
+                const hc T = K[(size_t)neigh[(mu == 0 ? 0 : 2) * N + site] * N + site];
+                for (int b = band; b < MSF; b += 2) bt[(size_t)(mu * MSF + b) * N + site] = T;
             }
     }
 }
@@ -719,13 +747,22 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
             A_(dalloc(c, &c->tdpacc, c->tdpacc_n));
         }
     }
-    if (p->td_particle_hole != 0 && p->td_particle_hole != 1) return fail(DQMC_EINVAL, "td_particle_hole must be 0 or 1");
+    if (p->td_particle_hole < 0 || p->td_particle_hole > 2) return fail(DQMC_EINVAL, "td_particle_hole must be 0, 1 or 2");
     if (p->td_particle_hole) {              // behind the blocks above: contexts without the flag are laid out as before
         if (!p->timedisplaced) return fail(DQMC_EINVAL, "td_particle_hole needs timedisplaced >= 1");
         A_(dalloc(c, &c->G00, n2)); A_(dalloc(c, &c->ph_H, n2));
         A_(dalloc(c, &c->ph_ob, measure_td_ph_onebody_cplx(N)));
         c->tdphacc_n = measure_td_ph_doubles(N, c->n);
         A_(dalloc(c, &c->tdphacc, c->tdphacc_n));
+    }
+    if (p->td_particle_hole == 2) {         // behind the blocks above again: value 1 keeps its layout
+        std::vector<hc> bt;
+        build_bond_table(*p, neigh, MSF, bt);
+        A_(salloc(c, &c->cur_bt, bt.size()));
+        HIPCHK(copy_sync(c, c->cur_bt, bt.data(), bt.size() * sizeof(hc), hipMemcpyHostToDevice));
+        A_(dalloc(c, &c->cur_ob, measure_td_current_onebody_cplx(N)));
+        c->tdcacc_n = measure_td_current_doubles(N, c->n);
+        A_(dalloc(c, &c->tdcacc, c->tdcacc_n));
     }
     A_(arena_commit(c));                    // from here on the per-chain pointers are real (chain 0) addresses, zero filled
 #undef A_
@@ -1630,6 +1667,8 @@ extern "C" int dqmc_measure_reset(dqmc_ctx* c) {
         for (int b = 0; b < c->nb; ++b) HIPCHK(hipMemsetAsync(chainp(c, c->tdpacc, b), 0, c->tdpacc_n * sizeof(double), c->st));
     if (c->tdphacc_n)
         for (int b = 0; b < c->nb; ++b) HIPCHK(hipMemsetAsync(chainp(c, c->tdphacc, b), 0, c->tdphacc_n * sizeof(double), c->st));
+    if (c->tdcacc_n)
+        for (int b = 0; b < c->nb; ++b) HIPCHK(hipMemsetAsync(chainp(c, c->tdcacc, b), 0, c->tdcacc_n * sizeof(double), c->st));
     return DQMC_OK;
 }
 extern "C" int dqmc_measure_slice(dqmc_ctx* c) {
@@ -1742,6 +1781,34 @@ extern "C" int dqmc_measure_td_ph_read_host(dqmc_ctx* c, double* out) {
     (void)hipSetDevice(c->p.device);
     HIPCHK(hipStreamSynchronize(c->st));
     HIPCHK(copy_sync(c, out, selp(c, c->tdphacc), c->tdphacc_n * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+// current-current correlators of the boundary the context stands on: the same four shifted matrices, prepared here again so that the call
+// stands on its own next to dqmc_measure_timedisplaced_ph (either order); ph_H and T1 are scratch of both
+extern "C" int dqmc_measure_timedisplaced_current(dqmc_ctx* c, int j) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (!c->tdcacc_n) return fail(DQMC_EINVAL, "context created without dqmc_params::td_particle_hole = 2");
+    if (j < 1 || j > c->n - 1) return fail(DQMC_EINVAL, "boundary index j must be in 1..n-1");
+    if (c->td_slice != c->s * j) return fail(DQMC_EINVAL, "the last time-displaced pair does not belong to boundary j");
+    if (c->currentTimeslice != c->s * j) return fail(DQMC_EINVAL, "the context has left boundary j: G is no longer G(tau_j)");
+    (void)hipSetDevice(c->p.device);
+    shift_green_dev(c);
+    { ProfScope ps(c, FAM_OTHER, 1); launch_td_current_onebody(c->lc, c->hm, c->T1, c->cur_bt, c->cur_ob, 0); }
+    shift_green_dev(c, c->G00);
+    { ProfScope ps(c, FAM_OTHER, 1); launch_td_current_onebody(c->lc, c->hm, c->T1, c->cur_bt, c->cur_ob, 1); }
+    shift_green_dev(c, c->G0T);
+    { ProfScope ps(c, FAM_OTHER, 1); launch_conj_transpose(c->lc, c->T1, c->ph_H, c->n_g); }
+    shift_green_dev(c, c->GT0);
+    { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td_current(c->lc, c->hm, c->T1, c->ph_H, c->cur_bt, c->cur_ob, c->tdcacc, j); }
+    return finish(c, "dqmc_measure_timedisplaced_current");
+}
+extern "C" size_t dqmc_measure_td_current_accum_size(dqmc_ctx* c) { return c ? c->tdcacc_n : 0; }
+extern "C" int dqmc_measure_td_current_read_host(dqmc_ctx* c, double* out) {
+    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
+    if (!c->tdcacc_n) return fail(DQMC_EINVAL, "context created without dqmc_params::td_particle_hole = 2");
+    (void)hipSetDevice(c->p.device);
+    HIPCHK(hipStreamSynchronize(c->st));
+    HIPCHK(copy_sync(c, out, selp(c, c->tdcacc), c->tdcacc_n * sizeof(double), hipMemcpyDeviceToHost));
     return DQMC_OK;
 }
 extern "C" int dqmc_get_green0_timedisplaced_host(dqmc_ctx* c, dqmc_cplx* g00, int* slice) {

@@ -262,6 +262,14 @@ void launch_td_ph_onebody(const Launch& lc, const DevModel& hm, const cplx* gs, 
 void launch_measure_td_ph(const Launch& lc, const DevModel& hm, const cplx* gs, const cplx* hs, const cplx* ob, double* acc, int j);
 size_t measure_td_ph_doubles(int N, int n);
 size_t measure_td_ph_onebody_cplx(int N);
+// time-displaced current-current block: count[n-1], then per boundary j = 1 .. n-1 the sums over B of Re W[j_mu(B (+) d), j_mu(B)] for mu = x [N]
+// and mu = y [N], then sum_A Re o_tau[k_x(A)] and sum_A Re o_tau[k_y(A)].  bt = bond amplitudes [2][MSF][N] (shared by all chains),
+// ob = the one-body values [2][4][N] (j_x, j_y, k_x, k_y) that launch_td_current_onebody wrote; gs, hs as for launch_measure_td_ph
+void launch_td_current_onebody(const Launch& lc, const DevModel& hm, const cplx* gs, const cplx* bt, cplx* ob, int t);
+void launch_measure_td_current(const Launch& lc, const DevModel& hm, const cplx* gs, const cplx* hs, const cplx* bt, const cplx* ob, double* acc, int j);
+size_t measure_td_current_doubles(int N, int n);
+size_t measure_td_current_onebody_cplx(int N);
+size_t measure_td_current_bond_cplx(int N, int opdim);
 
 // ---- QR / UDT building blocks (kernels_qr.hip) ------------------------------------------------
 struct SvdProfHooks;

@@ -107,7 +107,7 @@ void DetSDW::normalise(detsdw_params& p, int& bcv) {
         throw ParameterWrong("Parameter timeDisplacedMeasurements has incorrect value");
     if (p.timeDisplacedMeasurements && !p.fermionMeasurements)
         throw ParameterWrong("timeDisplacedMeasurements needs fermionMeasurements");
-    if (p.timeDisplacedParticleHole != 0 && p.timeDisplacedParticleHole != 1)
+    if (p.timeDisplacedParticleHole < 0 || p.timeDisplacedParticleHole > 2)
         throw ParameterWrong("Parameter timeDisplacedParticleHole has incorrect value");
     if (p.timeDisplacedParticleHole && !p.timeDisplacedMeasurements)
         throw ParameterWrong("timeDisplacedParticleHole needs timeDisplacedMeasurements");
@@ -250,6 +250,7 @@ void DetSDW::measureTimeDisplaced(Group& g, int j) {
     check(dqmc_measure_timedisplaced(g.ctx, j), "measureTimeDisplaced");
     if (ch_[0].pars.timeDisplacedMeasurements == 2) check(dqmc_measure_timedisplaced_pair(g.ctx, j), "measureTimeDisplacedPair");
     if (ch_[0].pars.timeDisplacedParticleHole) check(dqmc_measure_timedisplaced_ph(g.ctx, j), "measureTimeDisplacedParticleHole");
+    if (ch_[0].pars.timeDisplacedParticleHole == 2) check(dqmc_measure_timedisplaced_current(g.ctx, j), "measureTimeDisplacedCurrent");
 }
 
 // detmodel.h:1333-1399
@@ -465,6 +466,30 @@ void DetSDW::finishFermionic(int b) {
             }
         }
     }
+    // time-displaced current-current correlators and the bond kinetic energy: the same normalisation
+    if (c.pars.timeDisplacedParticleHole == 2) {
+        std::vector<double> tc(dqmc_measure_td_current_accum_size(ctx_));
+        check(dqmc_measure_td_current_read_host(ctx_, tc.data()), "dqmc_measure_td_current_read_host");
+        const int nj = n_ - 1;
+        for (int mu = 0; mu < 2; ++mu) {
+            c.currentTau[mu].assign((size_t)nj * N, 0.0); c.currentTauQ0[mu].assign(nj, 0.0); c.bondKinetic[mu].assign(nj, 0.0);
+        }
+        for (int j = 1; j <= nj; ++j) {
+            const double cnt = tc[j - 1];
+            if (cnt < 1.0) throw GeneralError(DQMC_EINVAL, "measurement sweep did not visit every stabilisation boundary");
+            const double* blk = &tc[nj + (size_t)(j - 1) * (2 * (size_t)N + 2)];
+            for (int mu = 0; mu < 2; ++mu) {
+                double q = 0.0;
+                for (int d = 0; d < N; ++d) {
+                    const double v = blk[(size_t)mu * N + d] / (double(N) * cnt);
+                    c.currentTau[mu][(size_t)(j - 1) * N + d] = v;
+                    q += v;
+                }
+                c.currentTauQ0[mu][j - 1] = q;
+                c.bondKinetic[mu][j - 1] = blk[2 * (size_t)N + mu] / (double(N) * cnt);
+            }
+        }
+    }
     o.fermionic_valid = 1;
 }
 
@@ -482,6 +507,9 @@ void DetSDW::getObservableVector(int which, double* out, int b) const {
                                  : which == DETSDW_OBS_PAIRPLUSTAU_Q0 ? &c.pairPlusTauQ0 : which == DETSDW_OBS_PAIRMINUSTAU_Q0 ? &c.pairMinusTauQ0
                                  : which >= DETSDW_OBS_CHARGETAU && which <= DETSDW_OBS_SDWTAU ? &c.phTau[which - DETSDW_OBS_CHARGETAU]
                                  : which >= DETSDW_OBS_CHARGETAU_Q0 && which <= DETSDW_OBS_SDWTAU_Q0 ? &c.phTauQ0[which - DETSDW_OBS_CHARGETAU_Q0]
+                                 : which == DETSDW_OBS_CURRENTXTAU || which == DETSDW_OBS_CURRENTYTAU ? &c.currentTau[which - DETSDW_OBS_CURRENTXTAU]
+                                 : which == DETSDW_OBS_CURRENTXTAU_Q0 || which == DETSDW_OBS_CURRENTYTAU_Q0 ? &c.currentTauQ0[which - DETSDW_OBS_CURRENTXTAU_Q0]
+                                 : which == DETSDW_OBS_BONDKINETICX || which == DETSDW_OBS_BONDKINETICY ? &c.bondKinetic[which - DETSDW_OBS_BONDKINETICX]
                                  : nullptr;
     if (!v) throw ParameterWrong("unknown observable vector");
     if ((which == DETSDW_OBS_GREENKTAU_X || which == DETSDW_OBS_GREENKTAU_Y) && !c.pars.timeDisplacedMeasurements)
@@ -490,6 +518,8 @@ void DetSDW::getObservableVector(int which, double* out, int b) const {
         throw ParameterWrong("pairPlusTau / pairMinusTau need timeDisplacedMeasurements = 2");
     if (which >= DETSDW_OBS_CHARGETAU && which <= DETSDW_OBS_SDWTAU_Q0 && !c.pars.timeDisplacedParticleHole)
         throw ParameterWrong("chargeTau / spinZTau / sdwTau need timeDisplacedParticleHole");
+    if (which >= DETSDW_OBS_CURRENTXTAU && which <= DETSDW_OBS_BONDKINETICY && c.pars.timeDisplacedParticleHole != 2)
+        throw ParameterWrong("currentXTau / currentYTau / bondKineticX / bondKineticY need timeDisplacedParticleHole = 2");
     std::memcpy(out, v->data(), v->size() * sizeof(double));
 }
 

@@ -89,6 +89,7 @@ private:
         std::vector<double> pairPlusTau, pairMinusTau;      // (n-1) x N, column = periodic site difference (timeDisplacedMeasurements == 2)
         std::vector<double> pairPlusTauQ0, pairMinusTauQ0;  // n-1: their row sums
         std::vector<double> phTau[3], phTauQ0[3];           // charge, spinZ, sdw: (n-1) x N and the row sums (timeDisplacedParticleHole)
+        std::vector<double> currentTau[2], currentTauQ0[2], bondKinetic[2];   // x, y: (n-1) x N, row sums, n-1 (timeDisplacedParticleHole == 2)
         Chain(const detsdw_params& p) : pars(p), rng(p.rngSeed, (uint32_t)p.simindex + 1u) {}   // detqmc.h:181
     };
     std::vector<Chain> ch_;

@@ -422,3 +422,166 @@ void launch_measure_td_ph(const Launch& lc, const DevModel& hm, const cplx* gs, 
     else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_td_ph<2>), grid, block, 0, lc.st, hm, gs, hs, ob, acc, j, lc.cs);
     else hipLaunchKernelGGL((k_measure_td_ph<3>), grid, block, 0, lc.st, hm, gs, hs, ob, acc, j, lc.cs);
 }
+
+// Time-displaced current-current block (dqmc_measure_timedisplaced_current; definitions in dqmc_hip.h and DESIGN.md 6e).  A bond operator
+// at site i in direction mu (i' = i (+) mu) has two one-body entries per flavour, M[i' a, i a] = m_a(i), M[i a, i' a] = conj m_a(i), with
+// m = i T (current j_mu) or m = T (bond kinetic energy k_mu) and T_a(i) = K^a[i', i] from the bond table bt[mu][flavour][site].  With
+// A^1 = A', A^0 = A, m_1 = m, m_0 = conj m the general Wick form reduces to
+//   o_t(A)     = - sum_a [ m_a(A) g_t(A a; A' a) + conj m_a(A) g_t(A' a; A a) ]
+//   conn(A, B) = sum_{a b} sum_{u v} m_u^a(A) m_v^b(B) g0t(B^(1-v) b; A^u a) gt0(A^(1-u) a; B^v b),      g0t(B b; A a) = conj hs(A a; B b).
+// For the current, with c = T_a(A) T_b(B), d = T_a(A) conj T_b(B) and P_uv = conj hs(A^u a; B^(1-v) b) gt0(A^(1-u) a; B^v b):
+//   Re conn = sum_{a b} [ -Re c P_11 + Re d P_10 + Re conj(d) P_01 - Re conj(c) P_00 ].
+// Both directions of one (A, B, a, b) read gt0 and hs at the rows {A, Ax, Ay} x columns {B, Bx, By} without (Ax, By), (Ay, Bx): seven
+// elements of each matrix.  OPDIM < 3: M is flavour diagonal and the conjugate sector carries -conj(M) for j, +conj(M) for k, while both
+// matrices are diag(stored sector, its conjugate): the second sector contributes the complex conjugate of the first, so
+//   Re conn = 2 Re conn_stored,   o[j] = -2 i Re sum_stored (x - y),   o[k] = -2 Re sum_stored (x + y),   x = T g(A; A'), y = conj T g(A'; A),
+// and nothing is multiplied by a structural zero.  O(3) runs over the full 4 x 4 flavour pairs.
+// Shape, walk order over B, reduction and reproducibility: those of k_measure_td_ph (32 bins x 8 parts, partial sums meet in LDS, one writer
+// per accumulator, fixed order, no atomics).  Reuse instead of an LDS tile: the lanes of a half wave hold consecutive A of one column B, so
+// Ax is the neighbouring 16 bytes of the same cache lines and Ay the row L further down the same column, which the lane of bin d + L reads
+// in the same step; column Bx is the column of part + 1 of the same step and By the column this workgroup walks one (L / 8 steps) later:
+// every re-read is served by the CU's L1 or the XCD's L2, and each matrix leaves HBM once per launch.
+// Workgroup 0 also sums Re o_tau[k_mu] over the sites (fixed tree), the diamagnetic term.
+size_t measure_td_current_doubles(int N, int n) { return (size_t)(n - 1) * (1 + 2 * (size_t)N + 2); }
+
+#define TDC_OB 4        // one-body values per site and time: j_x, j_y, k_x, k_y
+size_t measure_td_current_onebody_cplx(int N) { return (size_t)2 * TDC_OB * N; }
+size_t measure_td_current_bond_cplx(int N, int opdim) { return (size_t)2 * (opdim == 3 ? 4 : 2) * N; }
+
+__device__ __forceinline__ cplx m_conj(cplx a) { return make_double2(a.x, -a.y); }
+
+// ob[t][j_x, j_y, k_x, k_y][site] for one of the two equal-time matrices (t = 0: G(tau_j), t = 1: G(0)); gs is its shifted form
+template<int OPDIM>
+__global__ __launch_bounds__(256) void k_td_current_onebody(DevModel dm, const cplx* __restrict__ gs, const cplx* __restrict__ bt,
+                                                            cplx* __restrict__ ob, int t, size_t cs) {
+    CHAIN(gs); CHAIN(ob);
+    constexpr int MSF = OPDIM == 3 ? 4 : 2;
+    const int N = dm.N, L = dm.L, A = blockIdx.x * 256 + threadIdx.x;
+    if (A >= N) return;
+    const size_t ng = (size_t)dm.ng;
+    const int ax = A % L, ay = A / L;
+    cplx* o = ob + (size_t)t * TDC_OB * N + A;
+#pragma unroll
+    for (int mu = 0; mu < 2; ++mu) {
+        const int An = mu == 0 ? ay * L + (ax + 1 == L ? 0 : ax + 1) : (ay + 1 == L ? 0 : ay + 1) * L + ax;
+        cplx sm = make_double2(0.0, 0.0), sp = make_double2(0.0, 0.0);
+#pragma unroll
+        for (int a = 0; a < MSF; ++a) {
+            const cplx T = bt[(size_t)(mu * MSF + a) * N + A];
+            const cplx x = m_mul(T, gs[(size_t)(An + N * a) * ng + A + N * a]);               // T g(A a; A' a)
+            const cplx y = m_mul(m_conj(T), gs[(size_t)(A + N * a) * ng + An + N * a]);       // conj T g(A' a; A a)
+            sm = m_add(sm, m_sub(x, y));
+            sp = m_add(sp, m_add(x, y));
+        }
+        if (OPDIM == 3) {
+            o[(size_t)mu * N] = make_double2(sm.y, -sm.x);                                    // -i sum (x - y)
+            o[(size_t)(2 + mu) * N] = make_double2(-sp.x, -sp.y);
+        } else {
+            o[(size_t)mu * N] = make_double2(0.0, -2.0 * sm.x);
+            o[(size_t)(2 + mu) * N] = make_double2(-2.0 * sp.x, 0.0);
+        }
+    }
+}
+
+template<int OPDIM>
+__global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_td_current(DevModel dm, const cplx* __restrict__ gs, const cplx* __restrict__ hs,
+                                                                             const cplx* __restrict__ bt, const cplx* __restrict__ ob,
+                                                                             double* __restrict__ acc, int j, size_t cs) {
+    CHAIN(gs); CHAIN(hs); CHAIN(ob); CHAIN(acc);
+    constexpr int MSF = OPDIM == 3 ? 4 : 2;
+    __shared__ double red[2][TDP_PARTS][TDP_BINS];
+    __shared__ double redk[TDP_BINS * TDP_PARTS];
+    const int N = dm.N, L = dm.L, tid = threadIdx.x;
+    const size_t ng = (size_t)dm.ng;
+    const int lb = tid % TDP_BINS, part = tid / TDP_BINS;
+    const int d = blockIdx.x * TDP_BINS + lb;
+    const bool valid = d < N;
+    const int dx = valid ? d % L : 0, dy = valid ? d / L : 0;
+    const cplx* ot = ob;                                    // o_tau(A)
+    const cplx* o0 = ob + (size_t)TDC_OB * N;               // o_0(B)
+    auto re_mul = [](cplx a, cplx b) { return a.x * b.x - a.y * b.y; };   // Re a b
+    auto hce = [](cplx h, cplx e) { return make_double2(h.x * e.x + h.y * e.y, h.x * e.y - h.y * e.x); };      // conj(h) e
+    double wx = 0.0, wy = 0.0;
+    if (valid) {
+        int bx = part % L, by = part / L;                   // site B = part + 8 i, kept as (bx, by)
+        const int stepx = TDP_PARTS % L, stepy = TDP_PARTS / L;
+        for (int B = part; B < N; B += TDP_PARTS) {
+            int ax = bx + dx, ay = by + dy;
+            if (ax >= L) ax -= L;
+            if (ay >= L) ay -= L;
+            const int A = ay * L + ax;
+            // element offsets of the x and y neighbours: rows of A, columns of B
+            const ptrdiff_t rx = ax + 1 == L ? 1 - L : 1, ry = ay + 1 == L ? (ptrdiff_t)L - N : L;
+            const ptrdiff_t cx = (ptrdiff_t)(bx + 1 == L ? 1 - L : 1) * (ptrdiff_t)ng, cy = (ptrdiff_t)(by + 1 == L ? L - N : L) * (ptrdiff_t)ng;
+            double sx = re_mul(ot[A], o0[B]), sy = re_mul(ot[N + A], o0[N + B]);      // disconnected parts
+            double kx = 0.0, ky = 0.0;                                                // connected parts
+#pragma unroll
+            for (int a = 0; a < MSF; ++a) {
+                const cplx tax = bt[(size_t)a * N + A], tay = bt[(size_t)(MSF + a) * N + A];
+#pragma unroll
+                for (int b = 0; b < MSF; ++b) {
+                    const cplx tbx = bt[(size_t)b * N + B], tby = bt[(size_t)(MSF + b) * N + B];
+                    const size_t off = (size_t)(B + N * b) * ng + (size_t)(A + N * a);
+                    const cplx* pe = gs + off;
+                    const cplx* ph = hs + off;
+                    const cplx e00 = pe[0], h00 = ph[0];
+                    {   // mu = x: rows {A, Ax}, columns {B, Bx}
+                        const cplx e10 = pe[rx], e01 = pe[cx], e11 = pe[rx + cx];
+                        const cplx h10 = ph[rx], h01 = ph[cx], h11 = ph[rx + cx];
+                        const cplx c = m_mul(tax, tbx), dd = m_mul(tax, m_conj(tbx));
+                        // P_uv = conj hs(A^u; B^(1-v)) gt0(A^(1-u); B^v)
+                        const cplx p11 = hce(h10, e01), p10 = hce(h11, e00), p01 = hce(h00, e11), p00 = hce(h01, e10);
+                        kx += (re_mul(dd, p10) + re_mul(m_conj(dd), p01)) - (re_mul(c, p11) + re_mul(m_conj(c), p00));
+                    }
+                    {   // mu = y: rows {A, Ay}, columns {B, By}
+                        const cplx e10 = pe[ry], e01 = pe[cy], e11 = pe[ry + cy];
+                        const cplx h10 = ph[ry], h01 = ph[cy], h11 = ph[ry + cy];
+                        const cplx c = m_mul(tay, tby), dd = m_mul(tay, m_conj(tby));
+                        const cplx p11 = hce(h10, e01), p10 = hce(h11, e00), p01 = hce(h00, e11), p00 = hce(h01, e10);
+                        ky += (re_mul(dd, p10) + re_mul(m_conj(dd), p01)) - (re_mul(c, p11) + re_mul(m_conj(c), p00));
+                    }
+                }
+            }
+            if (OPDIM < 3) { kx *= 2.0; ky *= 2.0; }
+            wx += sx - kx;
+            wy += sy - ky;
+            bx += stepx; by += stepy;
+            if (bx >= L) { bx -= L; ++by; }
+        }
+    }
+    red[0][part][lb] = wx;
+    red[1][part][lb] = wy;
+    __syncthreads();
+    double* blk = acc + (dm.n - 1) + (size_t)(j - 1) * (2 * (size_t)N + 2);
+    if (part < 2 && valid) {                                // part 0 writes Lambda_xx of its bin, part 1 Lambda_yy
+        double s = red[part][0][lb];
+#pragma unroll
+        for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
+        blk[(size_t)part * N + d] += s;
+    }
+    if (blockIdx.x == 0) {                                  // sum_A Re o_tau[k_mu(A)]
+        double vx = 0.0, vy = 0.0;
+        for (int A = tid; A < N; A += TDP_BINS * TDP_PARTS) { vx += ot[2 * N + A].x; vy += ot[3 * N + A].x; }
+        vx = block_sum(vx, redk);
+        vy = block_sum(vy, redk);
+        if (tid == 0) {
+            blk[2 * (size_t)N] += vx;
+            blk[2 * (size_t)N + 1] += vy;
+            acc[j - 1] += 1.0;
+        }
+    }
+}
+
+void launch_td_current_onebody(const Launch& lc, const DevModel& hm, const cplx* gs, const cplx* bt, cplx* ob, int t) {
+    const dim3 grid((hm.N + 255) / 256, 1, lc.nb);
+    if (hm.opdim == 1) hipLaunchKernelGGL((k_td_current_onebody<1>), grid, dim3(256), 0, lc.st, hm, gs, bt, ob, t, lc.cs);
+    else if (hm.opdim == 2) hipLaunchKernelGGL((k_td_current_onebody<2>), grid, dim3(256), 0, lc.st, hm, gs, bt, ob, t, lc.cs);
+    else hipLaunchKernelGGL((k_td_current_onebody<3>), grid, dim3(256), 0, lc.st, hm, gs, bt, ob, t, lc.cs);
+}
+
+void launch_measure_td_current(const Launch& lc, const DevModel& hm, const cplx* gs, const cplx* hs, const cplx* bt, const cplx* ob, double* acc, int j) {
+    const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
+    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_td_current<1>), grid, block, 0, lc.st, hm, gs, hs, bt, ob, acc, j, lc.cs);
+    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_td_current<2>), grid, block, 0, lc.st, hm, gs, hs, bt, ob, acc, j, lc.cs);
+    else hipLaunchKernelGGL((k_measure_td_current<3>), grid, block, 0, lc.st, hm, gs, hs, bt, ob, acc, j, lc.cs);
+}

@@ -57,6 +57,7 @@ class SDWParams:
     timeDisplacedMeasurements: bool = False   # ... and G(k, tau_j) at the interior stabilisation boundaries (needs fermionMeasurements)
     timeDisplacedPairing: bool = False        # ... and the pairing correlators P+-(r, tau_j) (needs timeDisplacedMeasurements)
     timeDisplacedParticleHole: bool = False   # ... and the charge / spin-z / SDW correlators C(r, tau_j) (needs timeDisplacedMeasurements)
+    timeDisplacedCurrent: bool = False        # ... and the current-current correlators Lambda_xx/yy(r, tau_j) (needs timeDisplacedParticleHole)
     globalUpdateInterval: int = 100
     phi2bosons: bool = False
     cdwU: float = 0.0
@@ -100,13 +101,13 @@ class KernelContext:
                  lambda_=1.0, txhor=-1.0, txver=-0.5, tyhor=0.5, tyver=1.0, mux=-0.5, muy=-0.5,
                  accRatio=0.5, phi2bosons=False, device=0, stabilisation="svd", checkerboard=True, nchains=1, cdwU=0.0,
                  pipeline=0, qrVariant=0, greenVariant=0, maxJacobiSweeps=0, proposalBudget=0, rngWindowPerSite=0, decideThreads=0,
-                 timeDisplaced=False, tdParticleHole=False):
+                 timeDisplaced=False, tdParticleHole=False, tdCurrent=False):
         self.lib = load()
         p = _lib.dqmc_params(opdim=opdim, L=L, m=m, s=s, delaySteps=delaySteps, bc=BC[bc],
                              weakZflux=int(weakZflux), phi2bosons=int(phi2bosons), device=device,
                              stabilisation=STABILISATION[stabilisation], cb_none=int(not checkerboard), dtau=dtau, r=r, c=c, u=u, lambda_=lambda_, txhor=txhor, txver=txver,
                              tyhor=tyhor, tyver=tyver, mux=mux, muy=muy, accRatio=accRatio, cdwU=cdwU, rng_window_per_site=int(rngWindowPerSite),
-                             timedisplaced=int(timeDisplaced), td_particle_hole=int(tdParticleHole),
+                             timedisplaced=int(timeDisplaced), td_particle_hole=(2 if tdCurrent else int(tdParticleHole)),
                              tuning=_tuning(pipeline, qrVariant, greenVariant, maxJacobiSweeps, proposalBudget, decideThreads))
         h = C.c_void_p()
         check(self.lib.dqmc_create_batch(C.byref(p), nchains, C.byref(h)))
@@ -194,6 +195,18 @@ class KernelContext:
         """count[n-1], then per boundary the N sums of Re W over the periodic site differences for charge, spinZ and sdw"""
         out = np.zeros(self.lib.dqmc_measure_td_ph_accum_size(self.h))
         check(self.lib.dqmc_measure_td_ph_read_host(self.h, out.ctypes.data_as(_lib._DP)))
+        return out
+
+    def measure_timedisplaced_current(self, j):
+        """current-current correlators and bond kinetic energy of boundary j into their block (needs tdCurrent=True at construction; call
+        it right after the advance that ended on boundary j)"""
+        check(self.lib.dqmc_measure_timedisplaced_current(self.h, j))
+
+    def measure_td_current_read(self):
+        """count[n-1], then per boundary the N sums of Re W[j_x, j_x], the N sums of Re W[j_y, j_y] over the periodic site differences and
+        the two sums of Re o_tau[k_x], Re o_tau[k_y] over the sites"""
+        out = np.zeros(self.lib.dqmc_measure_td_current_accum_size(self.h))
+        check(self.lib.dqmc_measure_td_current_read_host(self.h, out.ctypes.data_as(_lib._DP)))
         return out
 
     def select_chain(self, b):
@@ -402,6 +415,8 @@ def _host_params(pars: SDWParams):
         raise ValueError("timeDisplacedPairing needs timeDisplacedMeasurements")
     if pars.timeDisplacedParticleHole and not pars.timeDisplacedMeasurements:
         raise ValueError("timeDisplacedParticleHole needs timeDisplacedMeasurements")
+    if pars.timeDisplacedCurrent and not pars.timeDisplacedParticleHole:
+        raise ValueError("timeDisplacedCurrent needs timeDisplacedParticleHole")
     return _lib.detsdw_params(
         opdim=pars.opdim, L=pars.L, m=pars.m, s=pars.s, delaySteps=pars.delaySteps,
         globalShift=int(pars.globalShift), globalUpdateInterval=pars.globalUpdateInterval,
@@ -417,7 +432,7 @@ def _host_params(pars: SDWParams):
         repeatWolffPerSweep=int(pars.repeatWolffPerSweep), fermionMeasurements=int(pars.fermionMeasurements),
         spinProposalMethod=SPIN_PROPOSAL[pars.spinProposalMethod], adaptScaleVariance=int(pars.adaptScaleVariance),
         repeatUpdateInSlice=int(pars.repeatUpdateInSlice), timeDisplacedMeasurements=(2 if pars.timeDisplacedPairing else int(bool(pars.timeDisplacedMeasurements))),
-        timeDisplacedParticleHole=int(bool(pars.timeDisplacedParticleHole)),
+        timeDisplacedParticleHole=(2 if pars.timeDisplacedCurrent else int(bool(pars.timeDisplacedParticleHole))),
         tuning=_tuning(pars.pipeline, pars.qrVariant, pars.greenVariant, pars.maxJacobiSweeps, pars.proposalBudget, pars.decideThreads))
 
 
@@ -490,13 +505,16 @@ class DetSDW:
         'greenKTauY' with timeDisplacedMeasurements: shape (n-1, N), row j-1 = tau_j of tau_grid(); 'pairPlusTau', 'pairMinusTau'
         with timeDisplacedPairing: shape (n-1, N), column = periodic site difference dy L + dx; 'pairPlusTauQ0', 'pairMinusTauQ0':
         their sums over the site difference, length n-1; 'chargeTau', 'spinZTau', 'sdwTau' with timeDisplacedParticleHole: shape
-        (n-1, N), same rows and columns; 'chargeTauQ0', 'spinZTauQ0', 'sdwTauQ0': their sums over the site difference"""
+        (n-1, N), same rows and columns; 'chargeTauQ0', 'spinZTauQ0', 'sdwTauQ0': their sums over the site difference; 'currentXTau',
+        'currentYTau' with timeDisplacedCurrent: shape (n-1, N), same rows and columns; 'currentXTauQ0', 'currentYTauQ0': their sums over
+        the site difference; 'bondKineticX', 'bondKineticY': the bond kinetic energy per site at tau_j, length n-1"""
         self._sel()
         info = self.info
         which = {"kOccX": 0, "kOccY": 1, "pairPlus": 2, "pairMinus": 3, "greenKTauX": 4, "greenKTauY": 5,
                  "pairPlusTau": 6, "pairMinusTau": 7, "pairPlusTauQ0": 8, "pairMinusTauQ0": 9,
-                 "chargeTau": 10, "spinZTau": 11, "sdwTau": 12, "chargeTauQ0": 13, "spinZTauQ0": 14, "sdwTauQ0": 15}[name]
-        out = np.zeros(info.N if which < 4 else (info.n - 1, info.N) if which < 8 or 10 <= which < 13 else info.n - 1)
+                 "chargeTau": 10, "spinZTau": 11, "sdwTau": 12, "chargeTauQ0": 13, "spinZTauQ0": 14, "sdwTauQ0": 15,
+                 "currentXTau": 16, "currentYTau": 17, "currentXTauQ0": 18, "currentYTauQ0": 19, "bondKineticX": 20, "bondKineticY": 21}[name]
+        out = np.zeros(info.N if which < 4 else (info.n - 1, info.N) if which < 8 or 10 <= which < 13 or 16 <= which < 18 else info.n - 1)
         check(self.lib.detsdw_get_observable_vector(self.h, which, out.ctypes.data_as(_lib._DP)), host=True)
         return out
 

@@ -68,7 +68,9 @@ typedef struct detsdw_params {
                                          handles of at most two kernel contexts (more contexts overlap each other instead) */
     int32_t timeDisplacedParticleHole; /* 1 (needs timeDisplacedMeasurements >= 1): a measurement sweep also takes the time-displaced
                                          charge, spin-z and SDW order-parameter correlators (DETSDW_OBS_CHARGETAU .. _SDWTAU_Q0).  The
-                                         field took the second reserved slot of dqmc_tuning: the bytes of the struct are where they were */
+                                         field took the second reserved slot of dqmc_tuning: the bytes of the struct are where they were.
+                                         2: also the current-current correlators and the bond kinetic energy (DETSDW_OBS_CURRENTXTAU ..
+                                         _BONDKINETICY).  Any other value: ParameterWrong */
 } detsdw_params;
 
 typedef struct detsdw_info {
@@ -117,7 +119,9 @@ enum { DETSDW_OBS_KOCCX = 0, DETSDW_OBS_KOCCY = 1, DETSDW_OBS_PAIRPLUS = 2, DETS
        DETSDW_OBS_GREENKTAU_X = 4, DETSDW_OBS_GREENKTAU_Y = 5,
        DETSDW_OBS_PAIRPLUSTAU = 6, DETSDW_OBS_PAIRMINUSTAU = 7, DETSDW_OBS_PAIRPLUSTAU_Q0 = 8, DETSDW_OBS_PAIRMINUSTAU_Q0 = 9,
        DETSDW_OBS_CHARGETAU = 10, DETSDW_OBS_SPINZTAU = 11, DETSDW_OBS_SDWTAU = 12,
-       DETSDW_OBS_CHARGETAU_Q0 = 13, DETSDW_OBS_SPINZTAU_Q0 = 14, DETSDW_OBS_SDWTAU_Q0 = 15 };
+       DETSDW_OBS_CHARGETAU_Q0 = 13, DETSDW_OBS_SPINZTAU_Q0 = 14, DETSDW_OBS_SDWTAU_Q0 = 15,
+       DETSDW_OBS_CURRENTXTAU = 16, DETSDW_OBS_CURRENTYTAU = 17, DETSDW_OBS_CURRENTXTAU_Q0 = 18, DETSDW_OBS_CURRENTYTAU_Q0 = 19,
+       DETSDW_OBS_BONDKINETICX = 20, DETSDW_OBS_BONDKINETICY = 21 };
 
 /* createReplica (src/detsdwopdim.cpp:49-84) + DetSDW ctor (:158-361): checks parameters, seeds the
  * RNG with (rngSeed, simindex + 1) (src/detqmc.h:181), draws the random field, builds UdV storage and
@@ -155,7 +159,11 @@ int detsdw_get_observables(detsdw_replica* r, detsdw_observables* out);
  * on the same shifted G(tau_j, 0) (dqmc_measure_timedisplaced_pair); pairPlusTauQ0 / pairMinusTauQ0, n-1: their sums over d
  * With timeDisplacedParticleHole: chargeTau / spinZTau / sdwTau, (n-1) x N, same rows and columns:
  *   C(d, tau_j) = (1/N) sum_B Re W(B (+) d, B),  W the Wick contraction of <O_A(tau_j) O_B(0)> for the site bilinears of
- * dqmc_measure_timedisplaced_ph (dqmc_hip.h); chargeTauQ0 / spinZTauQ0 / sdwTauQ0, n-1: their sums over d */
+ * dqmc_measure_timedisplaced_ph (dqmc_hip.h); chargeTauQ0 / spinZTauQ0 / sdwTauQ0, n-1: their sums over d
+ * With timeDisplacedParticleHole == 2: currentXTau / currentYTau, (n-1) x N, same rows and columns:
+ *   Lambda_mumu(d, tau_j) = (1/N) sum_B Re W[j_mu(B (+) d), j_mu(B)],  j_mu the bond current of dqmc_measure_timedisplaced_current;
+ * currentXTauQ0 / currentYTauQ0, n-1: their sums over d; bondKineticX / bondKineticY, n-1: (1/N) sum_A Re <k_mu(A)> at tau_j, the
+ * diamagnetic term.  The tau quadrature and the q -> 0 limits stay with the caller */
 int detsdw_get_observable_vector(detsdw_replica* r, int which, double* out);
 /* tau_j = j s dtau of the rows of greenKTauX / Y, j = 1 .. n-1: out[n-1] */
 int detsdw_get_tau_grid(detsdw_replica* r, double* out);

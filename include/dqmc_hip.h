@@ -108,8 +108,10 @@ typedef struct dqmc_params {
     int32_t td_particle_hole; /* 1 (needs timedisplaced >= 1, SDW model; DQMC_EINVAL otherwise): also reserve, behind every other buffer,
                                  the equal-time G(0) of the boundary's own field configuration, one matrix for a shifted copy, the
                                  per-site one-body values and the accumulator block of dqmc_measure_timedisplaced_ph.  0: nothing is
-                                 reserved, nothing changes.  (The field took the second reserved slot of dqmc_tuning: the bytes of the
-                                 struct are where they were.) */
+                                 reserved, nothing changes.  2: everything value 1 reserves with the same layout, launches and results,
+                                 and behind it the bond-amplitude table, the per-site one-body values and the accumulator block of
+                                 dqmc_measure_timedisplaced_current.  Any other value: DQMC_EINVAL.  (The field took the second
+                                 reserved slot of dqmc_tuning: the bytes of the struct are where they were.) */
 } dqmc_params;
 
 /* AdjustmentData + slice bookkeeping that lives on the device between calls
@@ -324,6 +326,29 @@ int dqmc_measure_td_pair_read_host(dqmc_ctx* ctx, double* out);
 int dqmc_measure_timedisplaced_ph(dqmc_ctx* ctx, int j);
 size_t dqmc_measure_td_ph_accum_size(dqmc_ctx* ctx);    /* 0 without the reservation */
 int dqmc_measure_td_ph_read_host(dqmc_ctx* ctx, double* out);
+/* Time-displaced current-current correlators Lambda_xx, Lambda_yy and the bond kinetic energy; context created with td_particle_hole = 2.
+ * Full index space: flavour N + site, flavour order XUP, YDOWN, XDOWN, YUP; engine matrices expanded by the access rule of the equal-time
+ * measurement (OPDIM < 3: stored sector, its conjugate, zeros).  K^a is the hopping matrix of flavour a, the one the dense propagator
+ * e^{-dtau K} is built from: band X for XUP / XDOWN, band Y for YDOWN / YUP, t*hor on x bonds, t*ver on y bonds, APBC sign on bonds that
+ * cross the boundary, with flux the Peierls phase of the stored sector, complex conjugated for the flavours of the conjugate sector.
+ * For a direction mu in {x, y}, a site i and i' = i (+) mu let T_a(i) = K^a[i', i], the coefficient of c^+_{i' a} c_{i a}:
+ *   current              j_mu(i) = sum_a i [ T_a(i) c^+_{i' a} c_{i a} - conj T_a(i) c^+_{i a} c_{i' a} ]
+ *   bond kinetic energy  k_mu(i) = sum_a   [ T_a(i) c^+_{i' a} c_{i a} + h.c. ]
+ * and for a one-body operator O = sum_pq c^+_p M_pq c_q on the four shifted matrices g~ of a boundary (conventions as above)
+ *   o_t[M]      = tr M - sum_pq M_pq g~_t(q, p)
+ *   W[M_A, M_B] = o_tau[M_A] o_0[M_B] - sum_pqrs (M_A)_pq (M_B)_rs g~(0,tau)(s, p) g~(tau,0)(q, r).
+ * dqmc_measure_timedisplaced_current(j) (all chains) adds to the block of boundary j, for every periodic site difference d = (dx, dy),
+ * bin dy L + dx,  sum_B Re W[j_mu(B (+) d), j_mu(B)]  for mu = x and mu = y, and the two sums  sum_A Re o_tau[k_mu(A)]  (the diamagnetic
+ * term, from g~(tau_j)).  Preconditions and DQMC_EINVAL behaviour of dqmc_measure_timedisplaced_ph; the call prepares its own shifted
+ * matrices, leaves G and the other measurement blocks alone and works in either order with the other calls of the boundary.
+ * Layout (doubles, dqmc_measure_td_current_accum_size of them): count[n-1], then for j = 1 .. n-1 the Lambda_xx sums [N], the Lambda_yy
+ * sums [N], sum_A Re o_tau[k_x] and sum_A Re o_tau[k_y], at offset (n-1) + (j-1) (2N + 2); dividing by N and by the count gives the
+ * translation averages.  The tau quadrature and the q -> 0 limits of the superfluid density
+ *   rho_s = 1/4 [ Lambda_xx(q_x -> 0, q_y = 0, i omega = 0) - Lambda_xx(q_x = 0, q_y -> 0, i omega = 0) ]
+ * stay with the reader of the block.  dqmc_measure_reset clears the block as well. */
+int dqmc_measure_timedisplaced_current(dqmc_ctx* ctx, int j);
+size_t dqmc_measure_td_current_accum_size(dqmc_ctx* ctx);   /* 0 without the reservation */
+int dqmc_measure_td_current_read_host(dqmc_ctx* ctx, double* out);
 /* G(0) of the last pair's field configuration, selected chain; *slice as for dqmc_get_green_timedisplaced_host.  DQMC_EINVAL without
  * td_particle_hole or if no pair was computed yet */
 int dqmc_get_green0_timedisplaced_host(dqmc_ctx* ctx, dqmc_cplx* g00, int* slice);
