@@ -18,6 +18,11 @@ class DqmcError(RuntimeError):
         self.code = code
 
 
+DQMC_TD_EVERY_SLICE = 0x100     # flag bit of dqmc_params.timedisplaced
+DETSDW_TD_EVERY_SLICE = 0x100   # flag bit of detsdw_params.timeDisplacedMeasurements
+DETSDW_OBS_FINE = 0x100         # flag bit of the observable index: the every-slice twin
+
+
 class dqmc_cplx(C.Structure):
     _fields_ = [("re", C.c_double), ("im", C.c_double)]
 
@@ -204,6 +209,12 @@ SYMBOLS = [
     ("dqmc_measure_timedisplaced_current", C.c_int, [_P, C.c_int]),
     ("dqmc_measure_td_current_accum_size", C.c_size_t, [_P]),
     ("dqmc_measure_td_current_read_host", C.c_int, [_P, _DP]),
+    ("dqmc_measure_timedisplaced_segment", C.c_int, [_P, C.c_int]),
+    ("dqmc_measure_timedisplaced_ends", C.c_int, [_P]),
+    ("dqmc_measure_td_fine_accum_size", C.c_size_t, [_P, C.c_int]),
+    ("dqmc_measure_td_fine_read_host", C.c_int, [_P, C.c_int, _DP]),
+    ("dqmc_get_green_td_fine_host", C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_int)]),
+    ("dqmc_td_fine_propagate", C.c_int, [_P, C.c_int, C.c_int]),     # tests only: exported, not declared in include/dqmc_hip.h
     ("dqmc_profile_enable", C.c_int, [_P, C.c_int]),
     ("dqmc_profile_read", C.c_int, [_P, C.POINTER(dqmc_profile)]),
     ("detsdw_create", C.c_int, [C.POINTER(detsdw_params), C.POINTER(_P)]),
@@ -221,6 +232,7 @@ SYMBOLS = [
     ("detsdw_get_observables", C.c_int, [_P, C.POINTER(detsdw_observables)]),
     ("detsdw_get_observable_vector", C.c_int, [_P, C.c_int, _DP]),
     ("detsdw_get_tau_grid", C.c_int, [_P, _DP]),
+    ("detsdw_get_tau_grid_fine", C.c_int, [_P, _DP]),
     ("detsdw_get_phi", C.c_int, [_P, _DP]),
     ("detsdw_set_phi", C.c_int, [_P, _DP]),
     ("detsdw_get_cdwl", C.c_int, [_P, _P]),

@@ -88,6 +88,13 @@ struct dqmc_ctx {
     cplx *cur_bt = nullptr, *cur_ob = nullptr;
     double* tdcacc = nullptr;
     size_t tdcacc_n = 0;
+    // DQMC_TD_EVERY_SLICE: work copies of G(tau_k,0), G(0,tau_k), G(tau_k) that the segment / ends entries propagate (the sweep's own G,
+    // GT0, G0T, G00 are only read), the slice they stand on, and one fine accumulator block (m + 1 rows) per enabled channel
+    bool td_fine = false;
+    int fine_slice = -1;
+    cplx *fGT0 = nullptr, *fG0T = nullptr, *fGTT = nullptr;
+    double* facc[4] = {nullptr, nullptr, nullptr, nullptr};   // 0 G(k, tau) bins, 1 pairing, 2 particle-hole, 3 current
+    size_t facc_n[4] = {0, 0, 0, 0};
     SvdWork sw{};
     double hub_e_m2a = 1.0, hub_e_p2a = 1.0;  // Hubbard: exp(-+2 alpha) of weightRatioSingleFlip (dethubbard.cpp:866-867)
     int stab = 0;                       // DQMC_STAB_SVD / DQMC_STAB_QR
@@ -734,22 +741,24 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
     A_(salloc(c, &c->shift_buf, (size_t)c->nb * 3));
     c->macc_n = measure_accum_doubles(N, p->L);
     A_(dalloc(c, &c->macc, c->macc_n));
-    if (p->timedisplaced < 0 || p->timedisplaced > 2) return fail(DQMC_EINVAL, "timedisplaced must be 0, 1 or 2");
-    if (p->timedisplaced) {                 // behind every other buffer: the layout of a context without them is unchanged
+    const int td_level = p->timedisplaced & ~DQMC_TD_EVERY_SLICE;
+    if (p->timedisplaced < 0 || td_level > 2) return fail(DQMC_EINVAL, "timedisplaced must be 0, 1 or 2 (| DQMC_TD_EVERY_SLICE)");
+    if ((p->timedisplaced & DQMC_TD_EVERY_SLICE) && !td_level) return fail(DQMC_EINVAL, "DQMC_TD_EVERY_SLICE needs timedisplaced >= 1");
+    if (td_level) {                 // behind every other buffer: the layout of a context without them is unchanged
         if (p->model != DQMC_MODEL_SDW) return fail(DQMC_EINVAL, "timedisplaced: SDW model only");
         c->td_reserved = true;
         A_(dalloc(c, &c->GT0, n2)); A_(dalloc(c, &c->G0T, n2)); A_(dalloc(c, &c->td_W, n2));
         if (c->stab != DQMC_STAB_QR) { A_(alloc_qr_work(c)); A_(dalloc(c, &c->td_sv, (size_t)ng)); }
         c->tdacc_n = measure_td_doubles(p->L, c->n);
         A_(dalloc(c, &c->tdacc, c->tdacc_n));
-        if (p->timedisplaced == 2) {        // behind the block above: a context with timedisplaced == 1 is laid out as before
+        if (td_level == 2) {        // behind the block above: a context with timedisplaced == 1 is laid out as before
             c->tdpacc_n = measure_td_pair_doubles(N, c->n);
             A_(dalloc(c, &c->tdpacc, c->tdpacc_n));
         }
     }
     if (p->td_particle_hole < 0 || p->td_particle_hole > 2) return fail(DQMC_EINVAL, "td_particle_hole must be 0, 1 or 2");
     if (p->td_particle_hole) {              // behind the blocks above: contexts without the flag are laid out as before
-        if (!p->timedisplaced) return fail(DQMC_EINVAL, "td_particle_hole needs timedisplaced >= 1");
+        if (!td_level) return fail(DQMC_EINVAL, "td_particle_hole needs timedisplaced >= 1");
         A_(dalloc(c, &c->G00, n2)); A_(dalloc(c, &c->ph_H, n2));
         A_(dalloc(c, &c->ph_ob, measure_td_ph_onebody_cplx(N)));
         c->tdphacc_n = measure_td_ph_doubles(N, c->n);
@@ -763,6 +772,16 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
         A_(dalloc(c, &c->cur_ob, measure_td_current_onebody_cplx(N)));
         c->tdcacc_n = measure_td_current_doubles(N, c->n);
         A_(dalloc(c, &c->tdcacc, c->tdcacc_n));
+    }
+    if (p->timedisplaced & DQMC_TD_EVERY_SLICE) {   // behind every block above: contexts without the flag are laid out as before
+        c->td_fine = true;
+        A_(dalloc(c, &c->fGT0, n2)); A_(dalloc(c, &c->fG0T, n2)); A_(dalloc(c, &c->fGTT, n2));
+        const bool on[4] = {true, td_level == 2, p->td_particle_hole >= 1, p->td_particle_hole == 2};
+        for (int ch = 0; ch < 4; ++ch)
+            if (on[ch]) {
+                c->facc_n[ch] = (size_t)(p->m + 1) * (1 + measure_td_row_doubles(ch, N, p->L));
+                A_(dalloc(c, &c->facc[ch], c->facc_n[ch]));
+            }
     }
     A_(arena_commit(c));                    // from here on the per-chain pointers are real (chain 0) addresses, zero filled
 #undef A_
@@ -1669,6 +1688,9 @@ extern "C" int dqmc_measure_reset(dqmc_ctx* c) {
         for (int b = 0; b < c->nb; ++b) HIPCHK(hipMemsetAsync(chainp(c, c->tdphacc, b), 0, c->tdphacc_n * sizeof(double), c->st));
     if (c->tdcacc_n)
         for (int b = 0; b < c->nb; ++b) HIPCHK(hipMemsetAsync(chainp(c, c->tdcacc, b), 0, c->tdcacc_n * sizeof(double), c->st));
+    for (int ch = 0; ch < 4; ++ch)
+        if (c->facc_n[ch])
+            for (int b = 0; b < c->nb; ++b) HIPCHK(hipMemsetAsync(chainp(c, c->facc[ch], b), 0, c->facc_n[ch] * sizeof(double), c->st));
     return DQMC_OK;
 }
 extern "C" int dqmc_measure_slice(dqmc_ctx* c) {
@@ -1721,7 +1743,7 @@ extern "C" int dqmc_measure_timedisplaced(dqmc_ctx* c, int j) {
     if (c->td_slice != c->s * j) return fail(DQMC_EINVAL, "the last time-displaced pair does not belong to boundary j");
     (void)hipSetDevice(c->p.device);
     shift_green_dev(c, c->GT0);              // T1 = e^{-dtau K/2} G(tau_j, 0) e^{+dtau K/2}
-    { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td(c->lc, c->hm, c->T1, c->tdacc, j); }
+    { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td(c->lc, c->hm, c->T1, c->tdacc, j - 1, c->n - 1); }
     return finish(c, "dqmc_measure_timedisplaced");
 }
 extern "C" size_t dqmc_measure_td_accum_size(dqmc_ctx* c) { return c ? c->tdacc_n : 0; }
@@ -1742,7 +1764,7 @@ extern "C" int dqmc_measure_timedisplaced_pair(dqmc_ctx* c, int j) {
     if (c->td_slice != c->s * j) return fail(DQMC_EINVAL, "the last time-displaced pair does not belong to boundary j");
     (void)hipSetDevice(c->p.device);
     shift_green_dev(c, c->GT0);              // T1 = e^{-dtau K/2} G(tau_j, 0) e^{+dtau K/2}
-    { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td_pair(c->lc, c->hm, c->T1, c->tdpacc, j); }
+    { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td_pair(c->lc, c->hm, c->T1, c->tdpacc, j - 1, c->n - 1); }
     return finish(c, "dqmc_measure_timedisplaced_pair");
 }
 extern "C" size_t dqmc_measure_td_pair_accum_size(dqmc_ctx* c) { return c ? c->tdpacc_n : 0; }
@@ -1771,7 +1793,7 @@ extern "C" int dqmc_measure_timedisplaced_ph(dqmc_ctx* c, int j) {
     shift_green_dev(c, c->G0T);
     { ProfScope ps(c, FAM_OTHER, 1); launch_conj_transpose(c->lc, c->T1, c->ph_H, c->n_g); }
     shift_green_dev(c, c->GT0);
-    { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td_ph(c->lc, c->hm, c->T1, c->ph_H, c->ph_ob, c->tdphacc, j); }
+    { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td_ph(c->lc, c->hm, c->T1, c->ph_H, c->ph_ob, c->tdphacc, j - 1, c->n - 1); }
     return finish(c, "dqmc_measure_timedisplaced_ph");
 }
 extern "C" size_t dqmc_measure_td_ph_accum_size(dqmc_ctx* c) { return c ? c->tdphacc_n : 0; }
@@ -1799,7 +1821,7 @@ extern "C" int dqmc_measure_timedisplaced_current(dqmc_ctx* c, int j) {
     shift_green_dev(c, c->G0T);
     { ProfScope ps(c, FAM_OTHER, 1); launch_conj_transpose(c->lc, c->T1, c->ph_H, c->n_g); }
     shift_green_dev(c, c->GT0);
-    { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td_current(c->lc, c->hm, c->T1, c->ph_H, c->cur_bt, c->cur_ob, c->tdcacc, j); }
+    { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td_current(c->lc, c->hm, c->T1, c->ph_H, c->cur_bt, c->cur_ob, c->tdcacc, j - 1, c->n - 1); }
     return finish(c, "dqmc_measure_timedisplaced_current");
 }
 extern "C" size_t dqmc_measure_td_current_accum_size(dqmc_ctx* c) { return c ? c->tdcacc_n : 0; }
@@ -1820,6 +1842,142 @@ extern "C" int dqmc_get_green0_timedisplaced_host(dqmc_ctx* c, dqmc_cplx* g00, i
     HIPCHK(hipGetLastError());
     HIPCHK(copy_sync(c, g00, selp(c, c->G00), (size_t)c->n_g * c->n_g * sizeof(cplx), hipMemcpyDeviceToHost));
     *slice = c->td_slice;
+    return DQMC_OK;
+}
+
+// ---- every time slice (DQMC_TD_EVERY_SLICE) ----------------------------------------------------------------------------------
+// One-body values of an equal-time matrix for the particle-hole and current kernels: one shift, both tables (t = 0: tau side, 1: 0 side)
+static void td_fine_onebody(dqmc_ctx* c, const cplx* g, int t) {
+    if (!c->facc_n[2]) return;
+    shift_green_dev(c, g);
+    { ProfScope ps(c, FAM_OTHER, 1); launch_td_ph_onebody(c->lc, c->hm, c->T1, c->ph_ob, t); }
+    if (c->facc_n[3]) { ProfScope ps(c, FAM_OTHER, 1); launch_td_current_onebody(c->lc, c->hm, c->T1, c->cur_bt, c->cur_ob, t); }
+}
+// Row k of every enabled fine block from (gt0, g0t, gtt) = (G(tau_k,0), G(0,tau_k), G(tau_k)).  The shifted matrices are prepared ONCE
+// and handed to all channel kernels: shifted gtt -> tau-side one-body values (gtt == nullptr: already there), (shifted g0t)^H -> ph_H,
+// shifted gt0 -> T1.  The 0-side one-body values are the caller's business (once per segment).  Same kernels, operands and order as the
+// four coarse entries, which prepare the same matrices once EACH.
+static void td_fine_row(dqmc_ctx* c, int k, const cplx* gt0, const cplx* g0t, const cplx* gtt) {
+    const int rows = c->m + 1;
+    if (gtt) td_fine_onebody(c, gtt, 0);
+    if (c->facc_n[2]) {
+        shift_green_dev(c, g0t);
+        { ProfScope ps(c, FAM_OTHER, 1); launch_conj_transpose(c->lc, c->T1, c->ph_H, c->n_g); }
+    }
+    shift_green_dev(c, gt0);
+    { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td(c->lc, c->hm, c->T1, c->facc[0], k, rows); }
+    if (c->facc_n[1]) { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td_pair(c->lc, c->hm, c->T1, c->facc[1], k, rows); }
+    if (c->facc_n[2]) { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td_ph(c->lc, c->hm, c->T1, c->ph_H, c->ph_ob, c->facc[2], k, rows); }
+    if (c->facc_n[3]) {
+        ProfScope ps(c, FAM_OTHER, 1);
+        launch_measure_td_current(c->lc, c->hm, c->T1, c->ph_H, c->cur_bt, c->cur_ob, c->facc[3], k, rows);
+    }
+}
+// the work copies from slice k to k + 1 (dir > 0) or to k - 1 (dir < 0), fields as they are on the device now:
+//   up:   G(t,0) <- B_{k+1} G(t,0),   G(0,t) <- G(0,t) B_{k+1}^-1,   G(t) <- B_{k+1} G(t) B_{k+1}^-1
+//   down: G(t,0) <- B_k^-1 G(t,0),    G(0,t) <- G(0,t) B_k,          G(t) <- B_k^-1 G(t) B_k
+static void td_fine_step(dqmc_ctx* c, int k, int dir) {
+    if (dir > 0) {
+        bmult_dev(c, DQMC_LEFT, 0, k + 1, k, c->fGT0);
+        bmult_dev(c, DQMC_RIGHT, 1, k + 1, k, c->fG0T);
+        bmult_dev(c, DQMC_RIGHT, 1, k + 1, k, c->fGTT);
+        bmult_dev(c, DQMC_LEFT, 0, k + 1, k, c->fGTT);
+    } else {
+        bmult_dev(c, DQMC_LEFT, 1, k, k - 1, c->fGT0);
+        bmult_dev(c, DQMC_RIGHT, 0, k, k - 1, c->fG0T);
+        bmult_dev(c, DQMC_RIGHT, 0, k, k - 1, c->fGTT);
+        bmult_dev(c, DQMC_LEFT, 1, k, k - 1, c->fGTT);
+    }
+    c->fine_slice = k + (dir > 0 ? 1 : -1);
+}
+static void td_fine_load_boundary(dqmc_ctx* c) {
+    const size_t n2 = (size_t)c->n_g * c->n_g;
+    ProfScope ps(c, FAM_OTHER, 3);
+    launch_copy(c->lc, c->GT0, c->fGT0, n2);
+    launch_copy(c->lc, c->G0T, c->fG0T, n2);
+    launch_copy(c->lc, c->G, c->fGTT, n2);
+    c->fine_slice = c->td_slice;
+}
+extern "C" int dqmc_measure_timedisplaced_segment(dqmc_ctx* c, int j) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (!c->td_fine) return fail(DQMC_EINVAL, "context created without DQMC_TD_EVERY_SLICE");
+    if (j < 1 || j > c->n - 1) return fail(DQMC_EINVAL, "boundary index j must be in 1..n-1");
+    if (c->td_slice != c->s * j) return fail(DQMC_EINVAL, "the last time-displaced pair does not belong to boundary j");
+    if (c->currentTimeslice != c->s * j) return fail(DQMC_EINVAL, "the context has left boundary j: G is no longer G(tau_j)");
+    (void)hipSetDevice(c->p.device);
+    const int s = c->s, k0 = s * j, k1 = (s * (j + 1) < c->m ? s * (j + 1) : c->m) - 1;
+    td_fine_onebody(c, c->G00, 1);            // G(0) does not move with tau: once per segment
+    td_fine_load_boundary(c);
+    for (int k = k0; k <= k1; ++k) {
+        td_fine_row(c, k, c->fGT0, c->fG0T, c->fGTT);
+        if (k < k1) td_fine_step(c, k, +1);
+    }
+    if (j == 1 && s > 1) {                    // the slices below the first boundary have no boundary of their own
+        td_fine_load_boundary(c);
+        for (int k = s; k >= 2; --k) {
+            td_fine_step(c, k, -1);
+            td_fine_row(c, k - 1, c->fGT0, c->fG0T, c->fGTT);
+        }
+    }
+    return finish(c, "dqmc_measure_timedisplaced_segment");
+}
+// For the tests only, exported but not part of include/dqmc_hip.h: the work copies at slice k of boundary j's segment, by the steps
+// dqmc_measure_timedisplaced_segment takes (its preconditions; DQMC_EINVAL for a k outside the segment); nothing is measured
+extern "C" int dqmc_td_fine_propagate(dqmc_ctx* c, int j, int k) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (!c->td_fine) return fail(DQMC_EINVAL, "context created without DQMC_TD_EVERY_SLICE");
+    if (j < 1 || j > c->n - 1) return fail(DQMC_EINVAL, "boundary index j must be in 1..n-1");
+    if (c->td_slice != c->s * j) return fail(DQMC_EINVAL, "the last time-displaced pair does not belong to boundary j");
+    if (c->currentTimeslice != c->s * j) return fail(DQMC_EINVAL, "the context has left boundary j: G is no longer G(tau_j)");
+    const int s = c->s, k0 = s * j, k1 = (s * (j + 1) < c->m ? s * (j + 1) : c->m) - 1;
+    if (k > k1 || k < (j == 1 ? 1 : k0)) return fail(DQMC_EINVAL, "slice k does not belong to the segment of boundary j");
+    (void)hipSetDevice(c->p.device);
+    td_fine_load_boundary(c);
+    for (int q = k0; q < k; ++q) td_fine_step(c, q, +1);
+    for (int q = k0; q > k; --q) td_fine_step(c, q, -1);
+    return finish(c, "dqmc_td_fine_propagate");
+}
+extern "C" int dqmc_measure_timedisplaced_ends(dqmc_ctx* c) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (!c->td_fine) return fail(DQMC_EINVAL, "context created without DQMC_TD_EVERY_SLICE");
+    if (c->currentTimeslice != 0 && c->currentTimeslice != c->m)
+        return fail(DQMC_EINVAL, "the context does not stand at tau = 0 (beta): G is not G(0)");
+    (void)hipSetDevice(c->p.device);
+    // row m from the work copies (they are what dqmc_get_green_td_fine_host reports afterwards), row 0 from T2 / T3: scratch of the
+    // Green's function routines, idle here (the shifts use T1 and, with the dense B, Tdense only)
+    { ProfScope ps(c, FAM_OTHER, 1); launch_td_ends(c->lc, c->G, c->T2, c->T3, c->fGT0, c->fG0T, c->fGTT, c->n_g); }
+    c->fine_slice = c->m;
+    td_fine_onebody(c, c->G, 0);              // G(tau) = G(0) = G for both rows and both sides: ONE shift of G
+    if (c->facc_n[2]) {
+        { ProfScope ps(c, FAM_OTHER, 1); launch_td_ph_onebody(c->lc, c->hm, c->T1, c->ph_ob, 1); }
+        if (c->facc_n[3]) { ProfScope ps(c, FAM_OTHER, 1); launch_td_current_onebody(c->lc, c->hm, c->T1, c->cur_bt, c->cur_ob, 1); }
+    }
+    td_fine_row(c, 0, c->T2, c->T3, nullptr);
+    td_fine_row(c, c->m, c->fGT0, c->fG0T, nullptr);
+    return finish(c, "dqmc_measure_timedisplaced_ends");
+}
+extern "C" size_t dqmc_measure_td_fine_accum_size(dqmc_ctx* c, int channel) {
+    return c && channel >= 0 && channel < 4 ? c->facc_n[channel] : 0;
+}
+extern "C" int dqmc_measure_td_fine_read_host(dqmc_ctx* c, int channel, double* out) {
+    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
+    if (channel < 0 || channel >= 4 || !c->facc_n[channel]) return fail(DQMC_EINVAL, "no every-slice block for this channel");
+    (void)hipSetDevice(c->p.device);
+    HIPCHK(hipStreamSynchronize(c->st));
+    HIPCHK(copy_sync(c, out, selp(c, c->facc[channel]), c->facc_n[channel] * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+extern "C" int dqmc_get_green_td_fine_host(dqmc_ctx* c, dqmc_cplx* g_t0, dqmc_cplx* g_0t, dqmc_cplx* g_tt, int* slice) {
+    if (!c || !g_t0 || !g_0t || !g_tt || !slice) return fail(DQMC_EINVAL, "null argument");
+    if (!c->td_fine || c->fine_slice < 0) return fail(DQMC_EINVAL, "no every-slice Green's function has been propagated");
+    (void)hipSetDevice(c->p.device);
+    HIPCHK(hipStreamSynchronize(c->st));
+    HIPCHK(hipGetLastError());
+    const size_t bytes = (size_t)c->n_g * c->n_g * sizeof(cplx);
+    HIPCHK(copy_sync(c, g_t0, selp(c, c->fGT0), bytes, hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(c, g_0t, selp(c, c->fG0T), bytes, hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(c, g_tt, selp(c, c->fGTT), bytes, hipMemcpyDeviceToHost));
+    *slice = c->fine_slice;
     return DQMC_OK;
 }
 

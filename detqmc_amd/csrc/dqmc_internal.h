@@ -250,23 +250,28 @@ void launch_phi_shift(const Launch& lc, const DevModel& hm, const double* shifts
 void launch_measure_accum(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc);
 size_t measure_accum_doubles(int N, int L);
 // time-displaced block: count[n-1], then per boundary j = 1 .. n-1 the S_X / S_Y bins of the shifted G(tau_j, 0) (dqmc_hip.h)
-void launch_measure_td(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc, int j);
+// (row, rows): the block holds count[rows], then row `row` at offset rows + row * stride -- (j - 1, n - 1) for the coarse blocks,
+// (k, m + 1) for the every-slice blocks; the same for the three launchers below
+void launch_measure_td(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc, int row, int rows);
+size_t measure_td_row_doubles(int channel, int N, int L);   // stride of a row: channel 0 bins, 1 pairing, 2 particle-hole, 3 current
+// every-slice end rows: (G, G - 1) -> (a_t0, a_0t), (1 - G, -G) -> (b_t0, b_0t), G -> gtt; one elementwise pass, all chains
+void launch_td_ends(const Launch& lc, const cplx* G, cplx* a_t0, cplx* a_0t, cplx* b_t0, cplx* b_0t, cplx* gtt, int ng);
 size_t measure_td_doubles(int L, int n);
 // time-displaced pairing block: count[n-1], then per boundary j = 1 .. n-1 the sums over B of Re T+(B (+) d, B) [N] and Re T-(B (+) d, B) [N]
-void launch_measure_td_pair(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc, int j);
+void launch_measure_td_pair(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc, int row, int rows);
 size_t measure_td_pair_doubles(int N, int n);
 // time-displaced particle-hole block: count[n-1], then per boundary j = 1 .. n-1 the sums over B of Re W(B (+) d, B) for charge [N], spinZ [N], sdw [N].
 // gs = shifted G(tau_j, 0), hs = (shifted G(0, tau_j))^H, ob = the one-body values [2][5][N] that launch_td_ph_onebody wrote from the
 // shifted equal-time matrices (t = 0: G(tau_j), t = 1: G(0))
 void launch_td_ph_onebody(const Launch& lc, const DevModel& hm, const cplx* gs, cplx* ob, int t);
-void launch_measure_td_ph(const Launch& lc, const DevModel& hm, const cplx* gs, const cplx* hs, const cplx* ob, double* acc, int j);
+void launch_measure_td_ph(const Launch& lc, const DevModel& hm, const cplx* gs, const cplx* hs, const cplx* ob, double* acc, int row, int rows);
 size_t measure_td_ph_doubles(int N, int n);
 size_t measure_td_ph_onebody_cplx(int N);
 // time-displaced current-current block: count[n-1], then per boundary j = 1 .. n-1 the sums over B of Re W[j_mu(B (+) d), j_mu(B)] for mu = x [N]
 // and mu = y [N], then sum_A Re o_tau[k_x(A)] and sum_A Re o_tau[k_y(A)].  bt = bond amplitudes [2][MSF][N] (shared by all chains),
 // ob = the one-body values [2][4][N] (j_x, j_y, k_x, k_y) that launch_td_current_onebody wrote; gs, hs as for launch_measure_td_ph
 void launch_td_current_onebody(const Launch& lc, const DevModel& hm, const cplx* gs, const cplx* bt, cplx* ob, int t);
-void launch_measure_td_current(const Launch& lc, const DevModel& hm, const cplx* gs, const cplx* hs, const cplx* bt, const cplx* ob, double* acc, int j);
+void launch_measure_td_current(const Launch& lc, const DevModel& hm, const cplx* gs, const cplx* hs, const cplx* bt, const cplx* ob, double* acc, int row, int rows);
 size_t measure_td_current_doubles(int N, int n);
 size_t measure_td_current_onebody_cplx(int N);
 size_t measure_td_current_bond_cplx(int N, int opdim);

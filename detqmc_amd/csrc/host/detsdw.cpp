@@ -19,6 +19,10 @@ void DetSDW::check(int rc, const char* what) {
     if (rc != DQMC_OK) throw GeneralError(rc, std::string(what) + ": " + dqmc_last_error());
 }
 
+// timeDisplacedMeasurements carries the level (0 / 1 / 2) in its low bits and DETSDW_TD_EVERY_SLICE as a flag bit
+static int td_level(const detsdw_params& p) { return p.timeDisplacedMeasurements & ~DETSDW_TD_EVERY_SLICE; }
+static bool td_every_slice(const detsdw_params& p) { return (p.timeDisplacedMeasurements & DETSDW_TD_EVERY_SLICE) != 0; }
+
 // field-wise comparison of two normalised parameter sets (struct padding is not the caller's business); everything but
 // the exchange parameter r, the device and -- unless seeds_too -- the RNG stream identity
 static bool same_model(const detsdw_params& a, const detsdw_params& b, bool seeds_too) {
@@ -29,8 +33,8 @@ static bool same_model(const detsdw_params& a, const detsdw_params& b, bool seed
                       a.wolffClusterUpdate == b.wolffClusterUpdate && a.wolffClusterShiftUpdate == b.wolffClusterShiftUpdate &&
                       a.repeatWolffPerSweep == b.repeatWolffPerSweep && a.fermionMeasurements == b.fermionMeasurements &&
                       a.spinProposalMethod == b.spinProposalMethod && a.adaptScaleVariance == b.adaptScaleVariance &&
-                      a.repeatUpdateInSlice == b.repeatUpdateInSlice && a.timeDisplacedMeasurements == b.timeDisplacedMeasurements &&
-                      a.timeDisplacedParticleHole == b.timeDisplacedParticleHole;
+                      a.repeatUpdateInSlice == b.repeatUpdateInSlice && td_level(a) == td_level(b) &&
+                      td_every_slice(a) == td_every_slice(b) && a.timeDisplacedParticleHole == b.timeDisplacedParticleHole;
     const bool reals = a.beta == b.beta && a.dtau == b.dtau && a.c == b.c && a.u == b.u && a.lambda == b.lambda &&
                        a.txhor == b.txhor && a.txver == b.txver && a.tyhor == b.tyhor && a.tyver == b.tyver &&
                        a.mu == b.mu && a.mux == b.mux && a.muy == b.muy && a.accRatio == b.accRatio && a.cdwU == b.cdwU;
@@ -103,8 +107,10 @@ void DetSDW::normalise(detsdw_params& p, int& bcv) {
     if (p.repeatWolffPerSweep < 1) throw ParameterWrong("Parameter repeatWolffPerSweep has incorrect value");
     if (p.L % 2 != 0) throw ParameterWrong("Checker board decomposition only supported for even linear lattice sizes");
     if (p.stabilisation != 0 && p.stabilisation != 1) throw ParameterWrong("Parameter stabilisation has incorrect value");
-    if (p.timeDisplacedMeasurements < 0 || p.timeDisplacedMeasurements > 2)
+    if (p.timeDisplacedMeasurements < 0 || td_level(p) > 2)
         throw ParameterWrong("Parameter timeDisplacedMeasurements has incorrect value");
+    if (td_every_slice(p) && !td_level(p))
+        throw ParameterWrong("timeDisplacedEverySlice needs timeDisplacedMeasurements");
     if (p.timeDisplacedMeasurements && !p.fermionMeasurements)
         throw ParameterWrong("timeDisplacedMeasurements needs fermionMeasurements");
     if (p.timeDisplacedParticleHole < 0 || p.timeDisplacedParticleHole > 2)
@@ -153,7 +159,7 @@ DetSDW::DetSDW(const detsdw_params* in, int nchains, int sub_batches) {
     kp.stabilisation = p.stabilisation;
     kp.cb_none = p.cb_none ? 1 : 0;          // reference option checkerboard=false (DetSDW<CB_NONE, OPDIM>)
     kp.rng_window_per_site = uniformsPerSite();
-    kp.timedisplaced = p.timeDisplacedMeasurements;      // 1: G(tau_j, 0) and its bins, 2: and the pairing block
+    kp.timedisplaced = td_level(p) | (td_every_slice(p) ? DQMC_TD_EVERY_SLICE : 0);   // 1: G(tau_j, 0) and its bins, 2: and the pairing block
     kp.td_particle_hole = p.timeDisplacedParticleHole;
     // result-neutral execution choices.  The pipelined update pays only while few contexts share the GPU (with more of them the
     // contexts overlap each other instead): automatic here means at most two sub-batches.
@@ -248,9 +254,15 @@ void DetSDW::updateInSlice(Group& g, int k, bool thermalization) {
 void DetSDW::measureTimeDisplaced(Group& g, int j) {
     if (!measuringTD_) return;
     check(dqmc_measure_timedisplaced(g.ctx, j), "measureTimeDisplaced");
-    if (ch_[0].pars.timeDisplacedMeasurements == 2) check(dqmc_measure_timedisplaced_pair(g.ctx, j), "measureTimeDisplacedPair");
+    if (td_level(ch_[0].pars) == 2) check(dqmc_measure_timedisplaced_pair(g.ctx, j), "measureTimeDisplacedPair");
     if (ch_[0].pars.timeDisplacedParticleHole) check(dqmc_measure_timedisplaced_ph(g.ctx, j), "measureTimeDisplacedParticleHole");
     if (ch_[0].pars.timeDisplacedParticleHole == 2) check(dqmc_measure_timedisplaced_current(g.ctx, j), "measureTimeDisplacedCurrent");
+    // every slice of the boundary's segment, in the boundary's own field configuration
+    if (td_every_slice(ch_[0].pars)) check(dqmc_measure_timedisplaced_segment(g.ctx, j), "measureTimeDisplacedSegment");
+}
+// the closing advance of a sweep left G = G(0): rows 0 and m of the every-slice blocks
+void DetSDW::measureTimeDisplacedEnds(Group& g) {
+    if (measuringTD_ && td_every_slice(ch_[0].pars)) check(dqmc_measure_timedisplaced_ends(g.ctx), "measureTimeDisplacedEnds");
 }
 
 // detmodel.h:1333-1399
@@ -269,6 +281,7 @@ void DetSDW::sweepDown(Group& g, bool thermalization) {
         }
     }
     check(dqmc_advance(ctx_, DQMC_DOWN, 1), "advanceDownGreen");
+    measureTimeDisplacedEnds(g);
 }
 
 // detmodel.h:1266-1325
@@ -288,6 +301,7 @@ void DetSDW::sweepUp(Group& g, bool thermalization) {
         updateInSlice(g, k, thermalization);
     }
     check(dqmc_advance(ctx_, DQMC_UP, n_ - 1), "advanceUpGreen");
+    measureTimeDisplacedEnds(g);
 }
 
 // detmodel.h:1408-1478 and detsdwopdim.cpp:4423-4502
@@ -389,132 +403,164 @@ void DetSDW::finishFermionic(int b) {
         }
     o.pairPlusMax = pp / 9.0;
     o.pairMinusMax = pm / 9.0;
-    // G(k, tau_j) from the time-displaced bins: the same Fourier sum, one row per interior boundary
-    if (c.pars.timeDisplacedMeasurements) {
-        std::vector<double> td(dqmc_measure_td_accum_size(ctx_));
-        check(dqmc_measure_td_read_host(ctx_, td.data()), "dqmc_measure_td_read_host");
-        const int nj = n_ - 1;
-        c.greenKTauX.assign((size_t)nj * N, 0.0); c.greenKTauY.assign((size_t)nj * N, 0.0);
-        // separable: A(kx, dy) = sum_dx e^{i kx dx} S(dx, dy) first, then Re sum_dy e^{i ky dy} A(kx, dy) -- (n-1) rows per sweep
-        std::vector<double> A((size_t)L * W * 2);
-        for (int j = 1; j <= nj; ++j) {
-            const double cnt = td[j - 1];
-            if (cnt < 1.0) throw GeneralError(DQMC_EINVAL, "measurement sweep did not visit every stabilisation boundary");
-            for (int band = 0; band < 2; ++band) {
-                const double* T = &td[nj + (size_t)(j - 1) * 4 * nbins + (size_t)band * 2 * nbins];
-                for (int kx = 0; kx < L; ++kx) {
-                    const double* tx = &ex[(size_t)kx * W * 2];
-                    for (int iy = 0; iy < W; ++iy) {
-                        double re = 0.0, im = 0.0;
-                        for (int ix = 0; ix < W; ++ix) {
-                            const double sr = T[2 * (iy * W + ix)], si = T[2 * (iy * W + ix) + 1];
-                            re += tx[2 * ix] * sr - tx[2 * ix + 1] * si;
-                            im += tx[2 * ix] * si + tx[2 * ix + 1] * sr;
+    // Time-displaced observables from one family of blocks: the coarse one (rows = interior boundaries j = 1 .. n-1) or, with
+    // timeDisplacedEverySlice, also the fine one (rows = slices k = 0 .. m).  Same arithmetic for both.
+    auto fill = [&](bool fine, TdObs& t) {
+        const int rows = fine ? m + 1 : n_ - 1;
+        const char* missing = fine ? "measurement sweep did not visit every time slice (time-displaced)"
+                                   : "measurement sweep did not visit every stabilisation boundary";
+        auto read = [&](int channel, std::vector<double>& buf) {
+            if (fine) {
+                buf.resize(dqmc_measure_td_fine_accum_size(ctx_, channel));
+                check(dqmc_measure_td_fine_read_host(ctx_, channel, buf.data()), "dqmc_measure_td_fine_read_host");
+            } else if (channel == 0) {
+                buf.resize(dqmc_measure_td_accum_size(ctx_));
+                check(dqmc_measure_td_read_host(ctx_, buf.data()), "dqmc_measure_td_read_host");
+            } else if (channel == 1) {
+                buf.resize(dqmc_measure_td_pair_accum_size(ctx_));
+                check(dqmc_measure_td_pair_read_host(ctx_, buf.data()), "dqmc_measure_td_pair_read_host");
+            } else if (channel == 2) {
+                buf.resize(dqmc_measure_td_ph_accum_size(ctx_));
+                check(dqmc_measure_td_ph_read_host(ctx_, buf.data()), "dqmc_measure_td_ph_read_host");
+            } else {
+                buf.resize(dqmc_measure_td_current_accum_size(ctx_));
+                check(dqmc_measure_td_current_read_host(ctx_, buf.data()), "dqmc_measure_td_current_read_host");
+            }
+        };
+        // G(k, tau) from the time-displaced bins: the same Fourier sum as kOcc, one row per tau
+        {
+            std::vector<double> td;
+            read(0, td);
+            t.greenKTauX.assign((size_t)rows * N, 0.0); t.greenKTauY.assign((size_t)rows * N, 0.0);
+            // separable: A(kx, dy) = sum_dx e^{i kx dx} S(dx, dy) first, then Re sum_dy e^{i ky dy} A(kx, dy)
+            std::vector<double> A((size_t)L * W * 2);
+            for (int r = 0; r < rows; ++r) {
+                const double cnt = td[r];
+                if (cnt < 1.0) throw GeneralError(DQMC_EINVAL, missing);
+                for (int band = 0; band < 2; ++band) {
+                    const double* T = &td[rows + (size_t)r * 4 * nbins + (size_t)band * 2 * nbins];
+                    for (int kx = 0; kx < L; ++kx) {
+                        const double* tx = &ex[(size_t)kx * W * 2];
+                        for (int iy = 0; iy < W; ++iy) {
+                            double re = 0.0, im = 0.0;
+                            for (int ix = 0; ix < W; ++ix) {
+                                const double sr = T[2 * (iy * W + ix)], si = T[2 * (iy * W + ix) + 1];
+                                re += tx[2 * ix] * sr - tx[2 * ix + 1] * si;
+                                im += tx[2 * ix] * si + tx[2 * ix + 1] * sr;
+                            }
+                            A[((size_t)kx * W + iy) * 2] = re; A[((size_t)kx * W + iy) * 2 + 1] = im;
                         }
-                        A[((size_t)kx * W + iy) * 2] = re; A[((size_t)kx * W + iy) * 2 + 1] = im;
+                    }
+                    std::vector<double>& out = band == 0 ? t.greenKTauX : t.greenKTauY;
+                    for (int ksite = 0; ksite < N; ++ksite) {
+                        const double* ty = &ey[(size_t)(ksite / L) * W * 2];
+                        const double* a = &A[(size_t)(ksite % L) * W * 2];
+                        double v = 0.0;
+                        for (int iy = 0; iy < W; ++iy) v += ty[2 * iy] * a[2 * iy] - ty[2 * iy + 1] * a[2 * iy + 1];
+                        out[(size_t)r * N + ksite] = v / (2.0 * N * cnt);
                     }
                 }
-                std::vector<double>& out = band == 0 ? c.greenKTauX : c.greenKTauY;
-                for (int ksite = 0; ksite < N; ++ksite) {
-                    const double* ty = &ey[(size_t)(ksite / L) * W * 2];
-                    const double* a = &A[(size_t)(ksite % L) * W * 2];
-                    double v = 0.0;
-                    for (int iy = 0; iy < W; ++iy) v += ty[2 * iy] * a[2 * iy] - ty[2 * iy + 1] * a[2 * iy + 1];
-                    out[(size_t)(j - 1) * N + ksite] = v / (2.0 * N * cnt);
-                }
             }
         }
-    }
-    // time-displaced pairing correlators: translation average (1 / N) and sample count; the q = 0 sums are the plain row sums
-    if (c.pars.timeDisplacedMeasurements == 2) {
-        std::vector<double> tp(dqmc_measure_td_pair_accum_size(ctx_));
-        check(dqmc_measure_td_pair_read_host(ctx_, tp.data()), "dqmc_measure_td_pair_read_host");
-        const int nj = n_ - 1;
-        c.pairPlusTau.assign((size_t)nj * N, 0.0); c.pairMinusTau.assign((size_t)nj * N, 0.0);
-        c.pairPlusTauQ0.assign(nj, 0.0); c.pairMinusTauQ0.assign(nj, 0.0);
-        for (int j = 1; j <= nj; ++j) {
-            const double cnt = tp[j - 1];
-            if (cnt < 1.0) throw GeneralError(DQMC_EINVAL, "measurement sweep did not visit every stabilisation boundary");
-            const double* T = &tp[nj + (size_t)(j - 1) * 2 * N];
-            double qp = 0.0, qm = 0.0;
-            for (int d = 0; d < N; ++d) {
-                const double vp = T[d] / (double(N) * cnt), vm = T[N + d] / (double(N) * cnt);
-                c.pairPlusTau[(size_t)(j - 1) * N + d] = vp; c.pairMinusTau[(size_t)(j - 1) * N + d] = vm;
-                qp += vp; qm += vm;
-            }
-            c.pairPlusTauQ0[j - 1] = qp; c.pairMinusTauQ0[j - 1] = qm;
-        }
-    }
-    // time-displaced particle-hole correlators (charge, spinZ, sdw): the same normalisation
-    if (c.pars.timeDisplacedParticleHole) {
-        std::vector<double> tp(dqmc_measure_td_ph_accum_size(ctx_));
-        check(dqmc_measure_td_ph_read_host(ctx_, tp.data()), "dqmc_measure_td_ph_read_host");
-        const int nj = n_ - 1;
-        for (int ch = 0; ch < 3; ++ch) { c.phTau[ch].assign((size_t)nj * N, 0.0); c.phTauQ0[ch].assign(nj, 0.0); }
-        for (int j = 1; j <= nj; ++j) {
-            const double cnt = tp[j - 1];
-            if (cnt < 1.0) throw GeneralError(DQMC_EINVAL, "measurement sweep did not visit every stabilisation boundary");
-            for (int ch = 0; ch < 3; ++ch) {
-                const double* T = &tp[nj + ((size_t)(j - 1) * 3 + ch) * N];
-                double q = 0.0;
+        // pairing correlators: translation average (1 / N) and sample count; the q = 0 sums are the plain row sums
+        if (td_level(c.pars) == 2) {
+            std::vector<double> tp;
+            read(1, tp);
+            t.pairPlusTau.assign((size_t)rows * N, 0.0); t.pairMinusTau.assign((size_t)rows * N, 0.0);
+            t.pairPlusTauQ0.assign(rows, 0.0); t.pairMinusTauQ0.assign(rows, 0.0);
+            for (int r = 0; r < rows; ++r) {
+                const double cnt = tp[r];
+                if (cnt < 1.0) throw GeneralError(DQMC_EINVAL, missing);
+                const double* T = &tp[rows + (size_t)r * 2 * N];
+                double qp = 0.0, qm = 0.0;
                 for (int d = 0; d < N; ++d) {
-                    const double v = T[d] / (double(N) * cnt);
-                    c.phTau[ch][(size_t)(j - 1) * N + d] = v;
-                    q += v;
+                    const double vp = T[d] / (double(N) * cnt), vm = T[N + d] / (double(N) * cnt);
+                    t.pairPlusTau[(size_t)r * N + d] = vp; t.pairMinusTau[(size_t)r * N + d] = vm;
+                    qp += vp; qm += vm;
                 }
-                c.phTauQ0[ch][j - 1] = q;
+                t.pairPlusTauQ0[r] = qp; t.pairMinusTauQ0[r] = qm;
             }
         }
-    }
-    // time-displaced current-current correlators and the bond kinetic energy: the same normalisation
-    if (c.pars.timeDisplacedParticleHole == 2) {
-        std::vector<double> tc(dqmc_measure_td_current_accum_size(ctx_));
-        check(dqmc_measure_td_current_read_host(ctx_, tc.data()), "dqmc_measure_td_current_read_host");
-        const int nj = n_ - 1;
-        for (int mu = 0; mu < 2; ++mu) {
-            c.currentTau[mu].assign((size_t)nj * N, 0.0); c.currentTauQ0[mu].assign(nj, 0.0); c.bondKinetic[mu].assign(nj, 0.0);
+        // particle-hole correlators (charge, spinZ, sdw): the same normalisation
+        if (c.pars.timeDisplacedParticleHole) {
+            std::vector<double> tp;
+            read(2, tp);
+            for (int ch = 0; ch < 3; ++ch) { t.phTau[ch].assign((size_t)rows * N, 0.0); t.phTauQ0[ch].assign(rows, 0.0); }
+            for (int r = 0; r < rows; ++r) {
+                const double cnt = tp[r];
+                if (cnt < 1.0) throw GeneralError(DQMC_EINVAL, missing);
+                for (int ch = 0; ch < 3; ++ch) {
+                    const double* T = &tp[rows + ((size_t)r * 3 + ch) * N];
+                    double q = 0.0;
+                    for (int d = 0; d < N; ++d) {
+                        const double v = T[d] / (double(N) * cnt);
+                        t.phTau[ch][(size_t)r * N + d] = v;
+                        q += v;
+                    }
+                    t.phTauQ0[ch][r] = q;
+                }
+            }
         }
-        for (int j = 1; j <= nj; ++j) {
-            const double cnt = tc[j - 1];
-            if (cnt < 1.0) throw GeneralError(DQMC_EINVAL, "measurement sweep did not visit every stabilisation boundary");
-            const double* blk = &tc[nj + (size_t)(j - 1) * (2 * (size_t)N + 2)];
+        // current-current correlators and the bond kinetic energy: the same normalisation
+        if (c.pars.timeDisplacedParticleHole == 2) {
+            std::vector<double> tc;
+            read(3, tc);
             for (int mu = 0; mu < 2; ++mu) {
-                double q = 0.0;
-                for (int d = 0; d < N; ++d) {
-                    const double v = blk[(size_t)mu * N + d] / (double(N) * cnt);
-                    c.currentTau[mu][(size_t)(j - 1) * N + d] = v;
-                    q += v;
+                t.currentTau[mu].assign((size_t)rows * N, 0.0); t.currentTauQ0[mu].assign(rows, 0.0); t.bondKinetic[mu].assign(rows, 0.0);
+            }
+            for (int r = 0; r < rows; ++r) {
+                const double cnt = tc[r];
+                if (cnt < 1.0) throw GeneralError(DQMC_EINVAL, missing);
+                const double* blk = &tc[rows + (size_t)r * (2 * (size_t)N + 2)];
+                for (int mu = 0; mu < 2; ++mu) {
+                    double q = 0.0;
+                    for (int d = 0; d < N; ++d) {
+                        const double v = blk[(size_t)mu * N + d] / (double(N) * cnt);
+                        t.currentTau[mu][(size_t)r * N + d] = v;
+                        q += v;
+                    }
+                    t.currentTauQ0[mu][r] = q;
+                    t.bondKinetic[mu][r] = blk[2 * (size_t)N + mu] / (double(N) * cnt);
                 }
-                c.currentTauQ0[mu][j - 1] = q;
-                c.bondKinetic[mu][j - 1] = blk[2 * (size_t)N + mu] / (double(N) * cnt);
             }
         }
-    }
+    };
+    if (td_level(c.pars)) fill(false, c.td);
+    if (td_every_slice(c.pars)) fill(true, c.tdFine);
     o.fermionic_valid = 1;
 }
 
 void DetSDW::getTauGrid(double* out) const {
     for (int j = 1; j <= n_ - 1; ++j) out[j - 1] = j * s_ * ch_[0].pars.dtau;
 }
+void DetSDW::getTauGridFine(double* out) const {
+    if (!td_every_slice(ch_[0].pars)) throw ParameterWrong("the fine tau grid needs timeDisplacedEverySlice");
+    for (int k = 0; k <= m_; ++k) out[k] = k * ch_[0].pars.dtau;
+}
 
-void DetSDW::getObservableVector(int which, double* out, int b) const {
+void DetSDW::getObservableVector(int which_in, double* out, int b) const {
     const Chain& c = ch_[b];
     if (!c.obs.fermionic_valid) throw GeneralError(DQMC_EINVAL, "no fermionic measurement has been taken");
+    const bool fine = (which_in & DETSDW_OBS_FINE) != 0;
+    const int which = which_in & ~DETSDW_OBS_FINE;
+    if (fine && (which < DETSDW_OBS_GREENKTAU_X || which > DETSDW_OBS_BONDKINETICY)) throw ParameterWrong("unknown observable vector");
+    if (fine && !td_every_slice(c.pars)) throw ParameterWrong("the ...Fine observables need timeDisplacedEverySlice");
+    const TdObs& t = fine ? c.tdFine : c.td;
     const std::vector<double>* v = which == DETSDW_OBS_KOCCX ? &c.kOccX : which == DETSDW_OBS_KOCCY ? &c.kOccY
                                  : which == DETSDW_OBS_PAIRPLUS ? &c.pairPlus : which == DETSDW_OBS_PAIRMINUS ? &c.pairMinus
-                                 : which == DETSDW_OBS_GREENKTAU_X ? &c.greenKTauX : which == DETSDW_OBS_GREENKTAU_Y ? &c.greenKTauY
-                                 : which == DETSDW_OBS_PAIRPLUSTAU ? &c.pairPlusTau : which == DETSDW_OBS_PAIRMINUSTAU ? &c.pairMinusTau
-                                 : which == DETSDW_OBS_PAIRPLUSTAU_Q0 ? &c.pairPlusTauQ0 : which == DETSDW_OBS_PAIRMINUSTAU_Q0 ? &c.pairMinusTauQ0
-                                 : which >= DETSDW_OBS_CHARGETAU && which <= DETSDW_OBS_SDWTAU ? &c.phTau[which - DETSDW_OBS_CHARGETAU]
-                                 : which >= DETSDW_OBS_CHARGETAU_Q0 && which <= DETSDW_OBS_SDWTAU_Q0 ? &c.phTauQ0[which - DETSDW_OBS_CHARGETAU_Q0]
-                                 : which == DETSDW_OBS_CURRENTXTAU || which == DETSDW_OBS_CURRENTYTAU ? &c.currentTau[which - DETSDW_OBS_CURRENTXTAU]
-                                 : which == DETSDW_OBS_CURRENTXTAU_Q0 || which == DETSDW_OBS_CURRENTYTAU_Q0 ? &c.currentTauQ0[which - DETSDW_OBS_CURRENTXTAU_Q0]
-                                 : which == DETSDW_OBS_BONDKINETICX || which == DETSDW_OBS_BONDKINETICY ? &c.bondKinetic[which - DETSDW_OBS_BONDKINETICX]
+                                 : which == DETSDW_OBS_GREENKTAU_X ? &t.greenKTauX : which == DETSDW_OBS_GREENKTAU_Y ? &t.greenKTauY
+                                 : which == DETSDW_OBS_PAIRPLUSTAU ? &t.pairPlusTau : which == DETSDW_OBS_PAIRMINUSTAU ? &t.pairMinusTau
+                                 : which == DETSDW_OBS_PAIRPLUSTAU_Q0 ? &t.pairPlusTauQ0 : which == DETSDW_OBS_PAIRMINUSTAU_Q0 ? &t.pairMinusTauQ0
+                                 : which >= DETSDW_OBS_CHARGETAU && which <= DETSDW_OBS_SDWTAU ? &t.phTau[which - DETSDW_OBS_CHARGETAU]
+                                 : which >= DETSDW_OBS_CHARGETAU_Q0 && which <= DETSDW_OBS_SDWTAU_Q0 ? &t.phTauQ0[which - DETSDW_OBS_CHARGETAU_Q0]
+                                 : which == DETSDW_OBS_CURRENTXTAU || which == DETSDW_OBS_CURRENTYTAU ? &t.currentTau[which - DETSDW_OBS_CURRENTXTAU]
+                                 : which == DETSDW_OBS_CURRENTXTAU_Q0 || which == DETSDW_OBS_CURRENTYTAU_Q0 ? &t.currentTauQ0[which - DETSDW_OBS_CURRENTXTAU_Q0]
+                                 : which == DETSDW_OBS_BONDKINETICX || which == DETSDW_OBS_BONDKINETICY ? &t.bondKinetic[which - DETSDW_OBS_BONDKINETICX]
                                  : nullptr;
     if (!v) throw ParameterWrong("unknown observable vector");
-    if ((which == DETSDW_OBS_GREENKTAU_X || which == DETSDW_OBS_GREENKTAU_Y) && !c.pars.timeDisplacedMeasurements)
+    if ((which == DETSDW_OBS_GREENKTAU_X || which == DETSDW_OBS_GREENKTAU_Y) && !td_level(c.pars))
         throw ParameterWrong("greenKTauX / greenKTauY need timeDisplacedMeasurements");
-    if (which >= DETSDW_OBS_PAIRPLUSTAU && which <= DETSDW_OBS_PAIRMINUSTAU_Q0 && c.pars.timeDisplacedMeasurements != 2)
+    if (which >= DETSDW_OBS_PAIRPLUSTAU && which <= DETSDW_OBS_PAIRMINUSTAU_Q0 && td_level(c.pars) != 2)
         throw ParameterWrong("pairPlusTau / pairMinusTau need timeDisplacedMeasurements = 2");
     if (which >= DETSDW_OBS_CHARGETAU && which <= DETSDW_OBS_SDWTAU_Q0 && !c.pars.timeDisplacedParticleHole)
         throw ParameterWrong("chargeTau / spinZTau / sdwTau need timeDisplacedParticleHole");
@@ -1019,6 +1065,10 @@ extern "C" int detsdw_get_observable_vector(detsdw_replica* r, int which, double
 extern "C" int detsdw_get_tau_grid(detsdw_replica* r, double* out) {
     if (!out) { g_host_err = "null argument"; return DQMC_EINVAL; }
     RGUARD(r->impl->getTauGrid(out))
+}
+extern "C" int detsdw_get_tau_grid_fine(detsdw_replica* r, double* out) {
+    if (!out) { g_host_err = "null argument"; return DQMC_EINVAL; }
+    RGUARD(r->impl->getTauGridFine(out))
 }
 extern "C" int detsdw_get_phi(detsdw_replica* r, double* phi) { RGUARD(r->impl->getPhi(phi, r->sel)) }
 extern "C" int detsdw_set_phi(detsdw_replica* r, const double* phi) { RGUARD(r->impl->setPhi(phi, r->sel)) }

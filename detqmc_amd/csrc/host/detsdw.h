@@ -56,6 +56,7 @@ public:
     void getObservables(detsdw_observables& out, int b = 0) const { out = ch_[b].obs; }
     void getObservableVector(int which, double* out, int b = 0) const;
     void getTauGrid(double* out) const;
+    void getTauGridFine(double* out) const;        // k dtau, k = 0 .. m (timeDisplacedEverySlice)
     void getPhi(double* phi, int b = 0);
     void setPhi(const double* phi, int b = 0);
     void getCdwl(int32_t* cdwl, int b = 0);
@@ -72,6 +73,13 @@ public:
 
 private:
     enum SweepDirection { Up = +1, Down = -1 };
+    struct TdObs {                                 // time-displaced observables, one row per tau of the family's grid
+        std::vector<double> greenKTauX, greenKTauY;         // rows x N (timeDisplacedMeasurements)
+        std::vector<double> pairPlusTau, pairMinusTau;      // rows x N, column = periodic site difference (timeDisplacedMeasurements == 2)
+        std::vector<double> pairPlusTauQ0, pairMinusTauQ0;  // rows: their row sums
+        std::vector<double> phTau[3], phTauQ0[3];           // charge, spinZ, sdw: rows x N and the row sums (timeDisplacedParticleHole)
+        std::vector<double> currentTau[2], currentTauQ0[2], bondKinetic[2];   // x, y: rows x N, row sums, rows (timeDisplacedParticleHole == 2)
+    };
     struct Chain {
         detsdw_params pars;
         RngStream rng;
@@ -85,11 +93,7 @@ private:
         double angleDelta = 0.0, scaleDelta = 0.1;          // AdjustmentData::InitialAngleDelta / InitialScaleDelta (detsdwopdim.h:490-491)
         detsdw_observables obs{};
         std::vector<double> kOccX, kOccY, pairPlus, pairMinus;
-        std::vector<double> greenKTauX, greenKTauY;         // (n-1) x N, row j-1 = tau_j (timeDisplacedMeasurements)
-        std::vector<double> pairPlusTau, pairMinusTau;      // (n-1) x N, column = periodic site difference (timeDisplacedMeasurements == 2)
-        std::vector<double> pairPlusTauQ0, pairMinusTauQ0;  // n-1: their row sums
-        std::vector<double> phTau[3], phTauQ0[3];           // charge, spinZ, sdw: (n-1) x N and the row sums (timeDisplacedParticleHole)
-        std::vector<double> currentTau[2], currentTauQ0[2], bondKinetic[2];   // x, y: (n-1) x N, row sums, n-1 (timeDisplacedParticleHole == 2)
+        TdObs td, tdFine;                      // rows = interior boundaries j = 1 .. n-1 / time slices k = 0 .. m (timeDisplacedEverySlice)
         Chain(const detsdw_params& p) : pars(p), rng(p.rngSeed, (uint32_t)p.simindex + 1u) {}   // detqmc.h:181
     };
     std::vector<Chain> ch_;
@@ -117,6 +121,7 @@ private:
     bool measuring_ = false;          // measure(k) after the updates of slice k (updateInSliceAndMaybeMeasure)
     bool measuringTD_ = false;        // ... and G(tau_j, 0) after every interior advance (timeDisplacedMeasurements)
     void measureTimeDisplaced(Group& g, int j);
+    void measureTimeDisplacedEnds(Group& g);
     void sweepDown(Group& g, bool thermalization);
     void sweepUp(Group& g, bool thermalization);
     void updateInSlice(Group& g, int k, bool thermalization);

@@ -176,26 +176,33 @@ void launch_measure_accum(const Launch& lc, const DevModel& hm, const cplx* gs, 
 
 // Time-displaced block (dqmc_measure_timedisplaced): the S_X / S_Y bins of gs = e^{-dtau K/2} G(tau_j, 0) e^{+dtau K/2} into the block of
 // boundary j, and one sample counted.  Same bins, lanes and summation order as the equal-time kOcc bins above.
+// Addressing of every time-displaced block below: count[rows], then row `row` at offset rows + row * stride.  The coarse blocks are
+// written with (row, rows) = (j - 1, n - 1), the every-slice blocks (dqmc_measure_timedisplaced_segment / _ends) with (k, m + 1).
 size_t measure_td_doubles(int L, int n) {
     const size_t nbins = (size_t)(2 * L - 1) * (2 * L - 1);
     return (size_t)(n - 1) * (1 + 4 * nbins);
 }
+// stride of one row of a time-displaced block: channel 0 G(k, tau) bins, 1 pairing, 2 particle-hole, 3 current
+size_t measure_td_row_doubles(int channel, int N, int L) {
+    const size_t nbins = (size_t)(2 * L - 1) * (2 * L - 1);
+    return channel == 0 ? 4 * nbins : channel == 1 ? 2 * (size_t)N : channel == 2 ? 3 * (size_t)N : 2 * (size_t)N + 2;
+}
 
 template<int OPDIM>
-__global__ __launch_bounds__(256) void k_measure_td(DevModel dm, const cplx* __restrict__ gs, double* __restrict__ acc, int j, size_t cs) {
+__global__ __launch_bounds__(256) void k_measure_td(DevModel dm, const cplx* __restrict__ gs, double* __restrict__ acc, int row, int rows, size_t cs) {
     CHAIN(gs); CHAIN(acc);
     const int N = dm.N, L = dm.L, nbins = (2 * L - 1) * (2 * L - 1);
     const GreenAccess<OPDIM> g1{gs, dm.ng, N};
-    accum_bins(g1, N, L, blockIdx.x * 256 + threadIdx.x, acc + (dm.n - 1) + (size_t)(j - 1) * 4 * nbins);
-    if (blockIdx.x == 0 && threadIdx.x == 0) acc[j - 1] += 1.0;
+    accum_bins(g1, N, L, blockIdx.x * 256 + threadIdx.x, acc + rows + (size_t)row * 4 * nbins);
+    if (blockIdx.x == 0 && threadIdx.x == 0) acc[row] += 1.0;
 }
 
-void launch_measure_td(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc, int j) {
+void launch_measure_td(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc, int row, int rows) {
     const int nbins = (2 * hm.L - 1) * (2 * hm.L - 1);
     const dim3 grid((2 * nbins * 8 + 255) / 256, 1, lc.nb);
-    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_td<1>), grid, dim3(256), 0, lc.st, hm, gs, acc, j, lc.cs);
-    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_td<2>), grid, dim3(256), 0, lc.st, hm, gs, acc, j, lc.cs);
-    else hipLaunchKernelGGL((k_measure_td<3>), grid, dim3(256), 0, lc.st, hm, gs, acc, j, lc.cs);
+    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_td<1>), grid, dim3(256), 0, lc.st, hm, gs, acc, row, rows, lc.cs);
+    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_td<2>), grid, dim3(256), 0, lc.st, hm, gs, acc, row, rows, lc.cs);
+    else hipLaunchKernelGGL((k_measure_td<3>), grid, dim3(256), 0, lc.st, hm, gs, acc, row, rows, lc.cs);
 }
 
 // Time-displaced pairing block (dqmc_measure_timedisplaced_pair): with gs = e^{-dtau K/2} G(tau_j, 0) e^{+dtau K/2} and the P(b1, b2) of
@@ -214,7 +221,7 @@ size_t measure_td_pair_doubles(int N, int n) { return (size_t)(n - 1) * (1 + 2 *
 #define TDP_BINS 32
 #define TDP_PARTS 8
 template<int OPDIM>
-__global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_td_pair(DevModel dm, const cplx* __restrict__ gs, double* __restrict__ acc, int j, size_t cs) {
+__global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_td_pair(DevModel dm, const cplx* __restrict__ gs, double* __restrict__ acc, int row, int rows, size_t cs) {
     CHAIN(gs); CHAIN(acc);
     __shared__ double red[2][TDP_PARTS][TDP_BINS];
     const int N = dm.N, L = dm.L, tid = threadIdx.x;
@@ -263,16 +270,16 @@ __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_td_pair(DevMod
         double s = red[part][0][lb];
 #pragma unroll
         for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
-        acc[(dm.n - 1) + (size_t)(j - 1) * 2 * N + (size_t)part * N + d] += s;
+        acc[rows + (size_t)row * 2 * N + (size_t)part * N + d] += s;
     }
-    if (blockIdx.x == 0 && tid == 0) acc[j - 1] += 1.0;
+    if (blockIdx.x == 0 && tid == 0) acc[row] += 1.0;
 }
 
-void launch_measure_td_pair(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc, int j) {
+void launch_measure_td_pair(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc, int row, int rows) {
     const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
-    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_td_pair<1>), grid, block, 0, lc.st, hm, gs, acc, j, lc.cs);
-    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_td_pair<2>), grid, block, 0, lc.st, hm, gs, acc, j, lc.cs);
-    else hipLaunchKernelGGL((k_measure_td_pair<3>), grid, block, 0, lc.st, hm, gs, acc, j, lc.cs);
+    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_td_pair<1>), grid, block, 0, lc.st, hm, gs, acc, row, rows, lc.cs);
+    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_td_pair<2>), grid, block, 0, lc.st, hm, gs, acc, row, rows, lc.cs);
+    else hipLaunchKernelGGL((k_measure_td_pair<3>), grid, block, 0, lc.st, hm, gs, acc, row, rows, lc.cs);
 }
 
 // Time-displaced particle-hole block (dqmc_measure_timedisplaced_ph; definitions in dqmc_hip.h and DESIGN.md 6e).  For a site bilinear
@@ -317,7 +324,7 @@ __global__ __launch_bounds__(256) void k_td_ph_onebody(DevModel dm, const cplx* 
 
 template<int OPDIM>
 __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_td_ph(DevModel dm, const cplx* __restrict__ gs, const cplx* __restrict__ hs,
-                                                                        const cplx* __restrict__ ob, double* __restrict__ acc, int j, size_t cs) {
+                                                                        const cplx* __restrict__ ob, double* __restrict__ acc, int row, int rows, size_t cs) {
     CHAIN(gs); CHAIN(hs); CHAIN(ob); CHAIN(acc);
     __shared__ double red[3][TDP_PARTS][TDP_BINS];
     const int N = dm.N, L = dm.L, tid = threadIdx.x;
@@ -402,9 +409,9 @@ __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_td_ph(DevModel
         double s = red[part][0][lb];
 #pragma unroll
         for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
-        acc[(dm.n - 1) + (size_t)(j - 1) * 3 * N + (size_t)part * N + d] += s;
+        acc[rows + (size_t)row * 3 * N + (size_t)part * N + d] += s;
     }
-    if (blockIdx.x == 0 && tid == 0) acc[j - 1] += 1.0;
+    if (blockIdx.x == 0 && tid == 0) acc[row] += 1.0;
 }
 
 size_t measure_td_ph_onebody_cplx(int N) { return (size_t)2 * TDPH_CH * N; }
@@ -416,11 +423,11 @@ void launch_td_ph_onebody(const Launch& lc, const DevModel& hm, const cplx* gs, 
     else hipLaunchKernelGGL((k_td_ph_onebody<3>), grid, dim3(256), 0, lc.st, hm, gs, ob, t, lc.cs);
 }
 
-void launch_measure_td_ph(const Launch& lc, const DevModel& hm, const cplx* gs, const cplx* hs, const cplx* ob, double* acc, int j) {
+void launch_measure_td_ph(const Launch& lc, const DevModel& hm, const cplx* gs, const cplx* hs, const cplx* ob, double* acc, int row, int rows) {
     const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
-    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_td_ph<1>), grid, block, 0, lc.st, hm, gs, hs, ob, acc, j, lc.cs);
-    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_td_ph<2>), grid, block, 0, lc.st, hm, gs, hs, ob, acc, j, lc.cs);
-    else hipLaunchKernelGGL((k_measure_td_ph<3>), grid, block, 0, lc.st, hm, gs, hs, ob, acc, j, lc.cs);
+    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_td_ph<1>), grid, block, 0, lc.st, hm, gs, hs, ob, acc, row, rows, lc.cs);
+    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_td_ph<2>), grid, block, 0, lc.st, hm, gs, hs, ob, acc, row, rows, lc.cs);
+    else hipLaunchKernelGGL((k_measure_td_ph<3>), grid, block, 0, lc.st, hm, gs, hs, ob, acc, row, rows, lc.cs);
 }
 
 // Time-displaced current-current block (dqmc_measure_timedisplaced_current; definitions in dqmc_hip.h and DESIGN.md 6e).  A bond operator
@@ -486,7 +493,7 @@ __global__ __launch_bounds__(256) void k_td_current_onebody(DevModel dm, const c
 template<int OPDIM>
 __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_td_current(DevModel dm, const cplx* __restrict__ gs, const cplx* __restrict__ hs,
                                                                              const cplx* __restrict__ bt, const cplx* __restrict__ ob,
-                                                                             double* __restrict__ acc, int j, size_t cs) {
+                                                                             double* __restrict__ acc, int row, int rows, size_t cs) {
     CHAIN(gs); CHAIN(hs); CHAIN(ob); CHAIN(acc);
     constexpr int MSF = OPDIM == 3 ? 4 : 2;
     __shared__ double red[2][TDP_PARTS][TDP_BINS];
@@ -552,7 +559,7 @@ __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_td_current(Dev
     red[0][part][lb] = wx;
     red[1][part][lb] = wy;
     __syncthreads();
-    double* blk = acc + (dm.n - 1) + (size_t)(j - 1) * (2 * (size_t)N + 2);
+    double* blk = acc + rows + (size_t)row * (2 * (size_t)N + 2);
     if (part < 2 && valid) {                                // part 0 writes Lambda_xx of its bin, part 1 Lambda_yy
         double s = red[part][0][lb];
 #pragma unroll
@@ -567,7 +574,7 @@ __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_td_current(Dev
         if (tid == 0) {
             blk[2 * (size_t)N] += vx;
             blk[2 * (size_t)N + 1] += vy;
-            acc[j - 1] += 1.0;
+            acc[row] += 1.0;
         }
     }
 }
@@ -579,9 +586,36 @@ void launch_td_current_onebody(const Launch& lc, const DevModel& hm, const cplx*
     else hipLaunchKernelGGL((k_td_current_onebody<3>), grid, dim3(256), 0, lc.st, hm, gs, bt, ob, t, lc.cs);
 }
 
-void launch_measure_td_current(const Launch& lc, const DevModel& hm, const cplx* gs, const cplx* hs, const cplx* bt, const cplx* ob, double* acc, int j) {
+void launch_measure_td_current(const Launch& lc, const DevModel& hm, const cplx* gs, const cplx* hs, const cplx* bt, const cplx* ob, double* acc, int row, int rows) {
     const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
-    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_td_current<1>), grid, block, 0, lc.st, hm, gs, hs, bt, ob, acc, j, lc.cs);
-    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_td_current<2>), grid, block, 0, lc.st, hm, gs, hs, bt, ob, acc, j, lc.cs);
-    else hipLaunchKernelGGL((k_measure_td_current<3>), grid, block, 0, lc.st, hm, gs, hs, bt, ob, acc, j, lc.cs);
+    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_td_current<1>), grid, block, 0, lc.st, hm, gs, hs, bt, ob, acc, row, rows, lc.cs);
+    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_td_current<2>), grid, block, 0, lc.st, hm, gs, hs, bt, ob, acc, row, rows, lc.cs);
+    else hipLaunchKernelGGL((k_measure_td_current<3>), grid, block, 0, lc.st, hm, gs, hs, bt, ob, acc, row, rows, lc.cs);
+}
+
+// End rows of the every-slice blocks (dqmc_measure_timedisplaced_ends): from the equal-time G = G(0), one elementwise pass writes
+//   tau = 0+:    G(0+,0) = G,          G(0,0+) = G - 1          -> a_t0, a_0t
+//   tau = beta-: G(beta-,0) = 1 - G,   G(0,beta-) = -G          -> b_t0, b_0t
+// and a copy of G (the equal-time function of both rows) -> gtt.  Threads past the end read element 0 and store nothing.
+__global__ __launch_bounds__(256) void k_td_ends(const cplx* __restrict__ G, cplx* __restrict__ a_t0, cplx* __restrict__ a_0t,
+                                                 cplx* __restrict__ b_t0, cplx* __restrict__ b_0t, cplx* __restrict__ gtt, int ng, size_t cs) {
+    CHAIN(G); CHAIN(a_t0); CHAIN(a_0t); CHAIN(b_t0); CHAIN(b_0t); CHAIN(gtt);
+    const size_t total = (size_t)ng * ng, gid = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const bool valid = gid < total;
+    const size_t idx = valid ? gid : 0;
+    const cplx g = G[idx];
+    const double one = (idx % (size_t)ng == idx / (size_t)ng) ? 1.0 : 0.0;
+    if (valid) {
+        a_t0[idx] = g;
+        a_0t[idx] = make_double2(g.x - one, g.y);
+        b_t0[idx] = make_double2(one - g.x, -g.y);
+        b_0t[idx] = make_double2(-g.x, -g.y);
+        gtt[idx] = g;
+    }
+}
+
+void launch_td_ends(const Launch& lc, const cplx* G, cplx* a_t0, cplx* a_0t, cplx* b_t0, cplx* b_0t, cplx* gtt, int ng) {
+    const size_t total = (size_t)ng * ng;
+    const dim3 grid((unsigned)((total + 255) / 256), 1, lc.nb);
+    hipLaunchKernelGGL(k_td_ends, grid, dim3(256), 0, lc.st, G, a_t0, a_0t, b_t0, b_0t, gtt, ng, lc.cs);
 }

@@ -58,6 +58,7 @@ class SDWParams:
     timeDisplacedPairing: bool = False        # ... and the pairing correlators P+-(r, tau_j) (needs timeDisplacedMeasurements)
     timeDisplacedParticleHole: bool = False   # ... and the charge / spin-z / SDW correlators C(r, tau_j) (needs timeDisplacedMeasurements)
     timeDisplacedCurrent: bool = False        # ... and the current-current correlators Lambda_xx/yy(r, tau_j) (needs timeDisplacedParticleHole)
+    timeDisplacedEverySlice: bool = False     # ... every enabled channel also on every slice tau_k = k dtau, k = 0 .. m: the '...Fine' observables (needs timeDisplacedMeasurements)
     globalUpdateInterval: int = 100
     phi2bosons: bool = False
     cdwU: float = 0.0
@@ -101,13 +102,13 @@ class KernelContext:
                  lambda_=1.0, txhor=-1.0, txver=-0.5, tyhor=0.5, tyver=1.0, mux=-0.5, muy=-0.5,
                  accRatio=0.5, phi2bosons=False, device=0, stabilisation="svd", checkerboard=True, nchains=1, cdwU=0.0,
                  pipeline=0, qrVariant=0, greenVariant=0, maxJacobiSweeps=0, proposalBudget=0, rngWindowPerSite=0, decideThreads=0,
-                 timeDisplaced=False, tdParticleHole=False, tdCurrent=False):
+                 timeDisplaced=False, tdParticleHole=False, tdCurrent=False, tdEverySlice=False):
         self.lib = load()
         p = _lib.dqmc_params(opdim=opdim, L=L, m=m, s=s, delaySteps=delaySteps, bc=BC[bc],
                              weakZflux=int(weakZflux), phi2bosons=int(phi2bosons), device=device,
                              stabilisation=STABILISATION[stabilisation], cb_none=int(not checkerboard), dtau=dtau, r=r, c=c, u=u, lambda_=lambda_, txhor=txhor, txver=txver,
                              tyhor=tyhor, tyver=tyver, mux=mux, muy=muy, accRatio=accRatio, cdwU=cdwU, rng_window_per_site=int(rngWindowPerSite),
-                             timedisplaced=int(timeDisplaced), td_particle_hole=(2 if tdCurrent else int(tdParticleHole)),
+                             timedisplaced=int(timeDisplaced) | (_lib.DQMC_TD_EVERY_SLICE if tdEverySlice else 0), td_particle_hole=(2 if tdCurrent else int(tdParticleHole)),
                              tuning=_tuning(pipeline, qrVariant, greenVariant, maxJacobiSweeps, proposalBudget, decideThreads))
         h = C.c_void_p()
         check(self.lib.dqmc_create_batch(C.byref(p), nchains, C.byref(h)))
@@ -208,6 +209,33 @@ class KernelContext:
         out = np.zeros(self.lib.dqmc_measure_td_current_accum_size(self.h))
         check(self.lib.dqmc_measure_td_current_read_host(self.h, out.ctypes.data_as(_lib._DP)))
         return out
+
+    def measure_timedisplaced_segment(self, j):
+        """every slice of boundary j's segment into the fine blocks, by propagation from the boundary's matrices (needs tdEverySlice=True at
+        construction; call it right after the advance that ended on boundary j)"""
+        check(self.lib.dqmc_measure_timedisplaced_segment(self.h, j))
+
+    def measure_timedisplaced_ends(self):
+        """rows 0 and m of the fine blocks from G = G(0) (the context must stand at time slice 0 or m)"""
+        check(self.lib.dqmc_measure_timedisplaced_ends(self.h))
+
+    def measure_td_fine_read(self, channel):
+        """fine block of channel 0 (G(k, tau) bins), 1 (pairing), 2 (particle-hole), 3 (current): count[m+1], then rows k = 0 .. m"""
+        out = np.zeros(self.lib.dqmc_measure_td_fine_accum_size(self.h, channel))
+        check(self.lib.dqmc_measure_td_fine_read_host(self.h, channel, out.ctypes.data_as(_lib._DP)))
+        return out
+
+    def td_fine_propagate(self, j, k):
+        """for tests: the work copies at slice k of boundary j's segment, by the steps of measure_timedisplaced_segment; measures nothing"""
+        check(self.lib.dqmc_td_fine_propagate(self.h, j, k))
+
+    def green_td_fine(self):
+        """(slice k, G(tau_k,0), G(0,tau_k), G(tau_k)): the last propagated triple of the selected chain"""
+        gt0 = np.zeros((self.ng, self.ng), dtype=np.complex128, order="F")
+        g0t, gtt = np.zeros_like(gt0), np.zeros_like(gt0)
+        sl = C.c_int(-1)
+        check(self.lib.dqmc_get_green_td_fine_host(self.h, gt0.ctypes.data, g0t.ctypes.data, gtt.ctypes.data, C.byref(sl)))
+        return sl.value, gt0, g0t, gtt
 
     def select_chain(self, b):
         """host-buffer calls (fields, G, sv, UdV, uniforms, update state, ...) refer to chain b from now on"""
@@ -431,7 +459,8 @@ def _host_params(pars: SDWParams):
         wolffClusterUpdate=int(pars.wolffClusterUpdate), wolffClusterShiftUpdate=int(pars.wolffClusterShiftUpdate),
         repeatWolffPerSweep=int(pars.repeatWolffPerSweep), fermionMeasurements=int(pars.fermionMeasurements),
         spinProposalMethod=SPIN_PROPOSAL[pars.spinProposalMethod], adaptScaleVariance=int(pars.adaptScaleVariance),
-        repeatUpdateInSlice=int(pars.repeatUpdateInSlice), timeDisplacedMeasurements=(2 if pars.timeDisplacedPairing else int(bool(pars.timeDisplacedMeasurements))),
+        repeatUpdateInSlice=int(pars.repeatUpdateInSlice), timeDisplacedMeasurements=(2 if pars.timeDisplacedPairing else int(bool(pars.timeDisplacedMeasurements)))
+        | (_lib.DETSDW_TD_EVERY_SLICE if pars.timeDisplacedEverySlice else 0),     # without timeDisplacedMeasurements: ParameterWrong from the library
         timeDisplacedParticleHole=(2 if pars.timeDisplacedCurrent else int(bool(pars.timeDisplacedParticleHole))),
         tuning=_tuning(pars.pipeline, pars.qrVariant, pars.greenVariant, pars.maxJacobiSweeps, pars.proposalBudget, pars.decideThreads))
 
@@ -507,19 +536,32 @@ class DetSDW:
         their sums over the site difference, length n-1; 'chargeTau', 'spinZTau', 'sdwTau' with timeDisplacedParticleHole: shape
         (n-1, N), same rows and columns; 'chargeTauQ0', 'spinZTauQ0', 'sdwTauQ0': their sums over the site difference; 'currentXTau',
         'currentYTau' with timeDisplacedCurrent: shape (n-1, N), same rows and columns; 'currentXTauQ0', 'currentYTauQ0': their sums over
-        the site difference; 'bondKineticX', 'bondKineticY': the bond kinetic energy per site at tau_j, length n-1"""
+        the site difference; 'bondKineticX', 'bondKineticY': the bond kinetic energy per site at tau_j, length n-1.  With
+        timeDisplacedEverySlice every name from 'greenKTauX' on has a twin name + 'Fine' (e.g. 'chargeTauFine', 'pairPlusTauQ0Fine',
+        'bondKineticXFine') with m+1 rows instead of n-1: row k = tau_k of tau_grid(fine=True), k = 0 .. m"""
         self._sel()
         info = self.info
+        fine = name.endswith("Fine")
+        if fine:
+            name = name[:-4]
         which = {"kOccX": 0, "kOccY": 1, "pairPlus": 2, "pairMinus": 3, "greenKTauX": 4, "greenKTauY": 5,
                  "pairPlusTau": 6, "pairMinusTau": 7, "pairPlusTauQ0": 8, "pairMinusTauQ0": 9,
                  "chargeTau": 10, "spinZTau": 11, "sdwTau": 12, "chargeTauQ0": 13, "spinZTauQ0": 14, "sdwTauQ0": 15,
                  "currentXTau": 16, "currentYTau": 17, "currentXTauQ0": 18, "currentYTauQ0": 19, "bondKineticX": 20, "bondKineticY": 21}[name]
-        out = np.zeros(info.N if which < 4 else (info.n - 1, info.N) if which < 8 or 10 <= which < 13 or 16 <= which < 18 else info.n - 1)
-        check(self.lib.detsdw_get_observable_vector(self.h, which, out.ctypes.data_as(_lib._DP)), host=True)
+        if fine and which < 4:
+            raise KeyError(name + "Fine")
+        rows = info.m + 1 if fine else info.n - 1
+        out = np.zeros(info.N if which < 4 else (rows, info.N) if which < 8 or 10 <= which < 13 or 16 <= which < 18 else rows)
+        check(self.lib.detsdw_get_observable_vector(self.h, which | (_lib.DETSDW_OBS_FINE if fine else 0), out.ctypes.data_as(_lib._DP)), host=True)
         return out
 
-    def tau_grid(self):
-        """tau_j = j s dtau, j = 1 .. n-1: the rows of greenKTauX / greenKTauY"""
+    def tau_grid(self, fine=False):
+        """tau_j = j s dtau, j = 1 .. n-1: the rows of greenKTauX / greenKTauY; fine=True (timeDisplacedEverySlice): tau_k = k dtau,
+        k = 0 .. m, the rows of the '...Fine' observables"""
+        if fine:
+            out = np.zeros(self.info.m + 1)
+            check(self.lib.detsdw_get_tau_grid_fine(self.h, out.ctypes.data_as(_lib._DP)), host=True)
+            return out
         out = np.zeros(self.info.n - 1)
         check(self.lib.detsdw_get_tau_grid(self.h, out.ctypes.data_as(_lib._DP)), host=True)
         return out

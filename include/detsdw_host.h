@@ -62,7 +62,11 @@ typedef struct detsdw_params {
     int32_t repeatUpdateInSlice;      /* passes of local updates per time slice and sweep, 0 is read as 1 (src/detsdwparams.h:90) */
     int32_t timeDisplacedMeasurements; /* 1 (needs fermionMeasurements): a measurement sweep also takes G(k, tau_j) at the interior
                                          stabilisation boundaries tau_j = j s dtau, j = 1 .. n-1 (DETSDW_OBS_GREENKTAU_X / _Y); 2: and the
-                                         time-displaced pairing correlators (DETSDW_OBS_PAIRPLUSTAU .. _PAIRMINUSTAU_Q0) */
+                                         time-displaced pairing correlators (DETSDW_OBS_PAIRPLUSTAU .. _PAIRMINUSTAU_Q0).
+                                         | DETSDW_TD_EVERY_SLICE (timeDisplacedEverySlice; needs a level >= 1, ParameterWrong otherwise):
+                                         every enabled time-displaced channel is also measured on every time slice tau_k = k dtau,
+                                         k = 0 .. m (DETSDW_OBS_FINE).  The struct has no free slot and its bytes stay where they are,
+                                         so the option travels as a flag bit, as in dqmc_params::timedisplaced */
     dqmc_tuning tuning;               /* result-neutral execution choices handed to every kernel context (dqmc_hip.h); all zero =
                                          automatic.  With pipeline = 0 the host layer switches the pipelined update on only for
                                          handles of at most two kernel contexts (more contexts overlap each other instead) */
@@ -122,6 +126,11 @@ enum { DETSDW_OBS_KOCCX = 0, DETSDW_OBS_KOCCY = 1, DETSDW_OBS_PAIRPLUS = 2, DETS
        DETSDW_OBS_CHARGETAU_Q0 = 13, DETSDW_OBS_SPINZTAU_Q0 = 14, DETSDW_OBS_SDWTAU_Q0 = 15,
        DETSDW_OBS_CURRENTXTAU = 16, DETSDW_OBS_CURRENTYTAU = 17, DETSDW_OBS_CURRENTXTAU_Q0 = 18, DETSDW_OBS_CURRENTYTAU_Q0 = 19,
        DETSDW_OBS_BONDKINETICX = 20, DETSDW_OBS_BONDKINETICY = 21 };
+/* timeDisplacedEverySlice: flag bit of detsdw_params::timeDisplacedMeasurements */
+enum { DETSDW_TD_EVERY_SLICE = 0x100 };
+/* which | DETSDW_OBS_FINE for which = DETSDW_OBS_GREENKTAU_X .. _BONDKINETICY: the every-slice twin ("...Fine") of the observable, rows
+ * k = 0 .. m instead of j = 1 .. n-1, columns unchanged; needs timeDisplacedEverySlice next to the option its coarse twin needs */
+enum { DETSDW_OBS_FINE = 0x100 };    /* a bit of the observable index: unrelated to DETSDW_TD_EVERY_SLICE, a bit of a parameter */
 
 /* createReplica (src/detsdwopdim.cpp:49-84) + DetSDW ctor (:158-361): checks parameters, seeds the
  * RNG with (rngSeed, simindex + 1) (src/detqmc.h:181), draws the random field, builds UdV storage and
@@ -167,6 +176,11 @@ int detsdw_get_observables(detsdw_replica* r, detsdw_observables* out);
 int detsdw_get_observable_vector(detsdw_replica* r, int which, double* out);
 /* tau_j = j s dtau of the rows of greenKTauX / Y, j = 1 .. n-1: out[n-1] */
 int detsdw_get_tau_grid(detsdw_replica* r, double* out);
+/* With timeDisplacedEverySlice: tau_k = k dtau of the rows of the ...Fine observables, k = 0 .. m: out[m+1].  Interior rows k = 1 .. m-1
+ * are measured in the half-updated field configuration of the stabilisation boundary whose segment they lie in (k < 2 s: boundary 1,
+ * else boundary floor(k / s)), by at most s - 1 unstabilised propagation steps from that boundary's G(tau_j,0), G(0,tau_j), G(tau_j);
+ * rows 0 and m in the field at the end of the sweep, from G(0) alone.  Row j s equals row j - 1 of the coarse observable bit for bit */
+int detsdw_get_tau_grid_fine(detsdw_replica* r, double* out);
 /* phi in the reference layout (N, OPDIM, m+1) column-major */
 int detsdw_get_phi(detsdw_replica* r, double* phi);
 int detsdw_set_phi(detsdw_replica* r, const double* phi);      /* also rebuilds UdV storage and G */

@@ -50,6 +50,9 @@ enum { DQMC_LEFT = 0, DQMC_RIGHT = 1 };
 enum { DQMC_UP = +1, DQMC_DOWN = -1 };
 enum { DQMC_STAB_SVD = 0, DQMC_STAB_QR = 1 };
 enum { DQMC_MODEL_SDW = 0, DQMC_MODEL_HUBBARD = 1 };
+/* flag bit of dqmc_params::timedisplaced (the low bits keep their values 0 / 1 / 2): also reserve what the every-slice entries
+ * dqmc_measure_timedisplaced_segment / _ends need */
+enum { DQMC_TD_EVERY_SLICE = 0x100 };
 
 /* Execution choices that change NO result (the parity tests hold for every value); 0 = automatic everywhere.  They are
  * create-time parameters of a context: nothing about a context's launch schedule depends on the environment or on other
@@ -103,7 +106,10 @@ typedef struct dqmc_params {
     int32_t timedisplaced; /* 1: reserve the per-chain buffers of the time-displaced Green's functions and their accumulator
                               block (SDW model only); dqmc_set_timedisplaced switches the computation on and off.  2: also the
                               accumulator block of dqmc_measure_timedisplaced_pair.  0: nothing is reserved, nothing changes.
-                              Any other value: DQMC_EINVAL */
+                              1 | DQMC_TD_EVERY_SLICE, 2 | DQMC_TD_EVERY_SLICE: everything the low value reserves with the same layout,
+                              launches and results, and behind every other buffer (those of td_particle_hole included) three work
+                              matrices and one every-slice accumulator block per enabled channel (the struct has no free slot: the
+                              option travels as a flag bit).  Any other value, any other bit: DQMC_EINVAL */
     dqmc_tuning tuning;   /* all zero = automatic */
     int32_t td_particle_hole; /* 1 (needs timedisplaced >= 1, SDW model; DQMC_EINVAL otherwise): also reserve, behind every other buffer,
                                  the equal-time G(0) of the boundary's own field configuration, one matrix for a shifted copy, the
@@ -352,6 +358,34 @@ int dqmc_measure_td_current_read_host(dqmc_ctx* ctx, double* out);
 /* G(0) of the last pair's field configuration, selected chain; *slice as for dqmc_get_green_timedisplaced_host.  DQMC_EINVAL without
  * td_particle_hole or if no pair was computed yet */
 int dqmc_get_green0_timedisplaced_host(dqmc_ctx* ctx, dqmc_cplx* g00, int* slice);
+/* Every time slice, tau_k = k dtau, k = 0 .. m (context created with timedisplaced | DQMC_TD_EVERY_SLICE; DQMC_EINVAL otherwise).
+ * Inside ONE field configuration the functions of neighbouring slices follow from each other without a new factorisation:
+ *   G(tau_{k+1},0) = B_{k+1} G(tau_k,0),   G(0,tau_{k+1}) = G(0,tau_k) B_{k+1}^-1,   G(tau_{k+1}) = B_{k+1} G(tau_k) B_{k+1}^-1,   G(0) unchanged
+ *   G(tau_{k-1},0) = B_k^-1 G(tau_k,0),    G(0,tau_{k-1}) = G(0,tau_k) B_k,         G(tau_{k-1}) = B_k^-1 G(tau_k) B_k
+ * and the end rows from the equal-time G(0) alone:
+ *   G(0+,0) = G(0),  G(0,0+) = G(0) - 1,  G(beta-,0) = 1 - G(0),  G(0,beta-) = -G(0).
+ * dqmc_measure_timedisplaced_segment(j) (all chains; preconditions of dqmc_measure_timedisplaced_ph: the last pair belongs to boundary j
+ * and the context still stands on it) measures, with the fields as they are on the device at that moment, the slices
+ * k = j s .. min((j+1) s, m) - 1 by upward propagation from the boundary's matrices and, for j = 1, also k = s-1 .. 1 by downward
+ * propagation: at most s - 1 unstabilised steps, the distance of the equal-time wrap.  Calling it once at every boundary j = 1 .. n-1
+ * hits every k in 1 .. m-1 exactly once, also when s does not divide m.  Propagation works on copies: G, the boundary pair and G(0)
+ * come out bit-identical.  Per slice the four shifted matrices e^{-dtau K/2} g e^{+dtau K/2} are prepared once and handed to every
+ * enabled channel kernel (the kernels, operands and summation order of dqmc_measure_timedisplaced, _pair, _ph and _current: row j s
+ * equals row j of the coarse block bit for bit); the one-body values of G(0) are formed once per segment.
+ * dqmc_measure_timedisplaced_ends() (all chains) measures rows 0 and m.  Precondition: the context stands at tau = 0 == beta
+ * (current time slice 0 or m: the state after the closing advance of either sweep direction), so that G = G(0); DQMC_EINVAL
+ * otherwise.  Both rows use G(tau) = G(0) = G.
+ * Blocks: channel 0 = bins of dqmc_measure_timedisplaced, 1 = _pair, 2 = _ph, 3 = _current; a channel has a block if its coarse
+ * block is reserved.  Layout (doubles, dqmc_measure_td_fine_accum_size of them, 0 without the block): count[m+1], then row k = 0 .. m
+ * at offset (m+1) + k stride, stride and contents of a row as in the coarse block: 4 (2L-1)^2, 2N, 3N, 2N + 2.
+ * dqmc_measure_reset clears them as well. */
+int dqmc_measure_timedisplaced_segment(dqmc_ctx* ctx, int j);
+int dqmc_measure_timedisplaced_ends(dqmc_ctx* ctx);
+size_t dqmc_measure_td_fine_accum_size(dqmc_ctx* ctx, int channel);
+int dqmc_measure_td_fine_read_host(dqmc_ctx* ctx, int channel, double* out);
+/* for tests: the last propagated triple G(tau_k,0), G(0,tau_k), G(tau_k) of the selected chain and its slice k (after
+ * dqmc_measure_timedisplaced_ends: the triple of row m) */
+int dqmc_get_green_td_fine_host(dqmc_ctx* ctx, dqmc_cplx* g_t0, dqmc_cplx* g_0t, dqmc_cplx* g_tt, int* slice);
 
 /* set_exchange_parameter_value (detsdwopdim.cpp:5195-5197): r only enters the bosonic action */
 int dqmc_set_exchange_parameter(dqmc_ctx* ctx, double r);
