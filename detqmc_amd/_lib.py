@@ -20,6 +20,7 @@ class DqmcError(RuntimeError):
 
 DQMC_TD_EVERY_SLICE = 0x100     # flag bit of dqmc_params.timedisplaced
 DETSDW_TD_EVERY_SLICE = 0x100   # flag bit of detsdw_params.timeDisplacedMeasurements
+DETSDW_TD_FINE_ON_DEVICE = 0x200  # flag bit of detsdw_params.timeDisplacedMeasurements: the fine blocks stay on the device
 DETSDW_OBS_FINE = 0x100         # flag bit of the observable index: the every-slice twin
 
 
@@ -213,6 +214,8 @@ SYMBOLS = [
     ("dqmc_measure_timedisplaced_ends", C.c_int, [_P]),
     ("dqmc_measure_td_fine_accum_size", C.c_size_t, [_P, C.c_int]),
     ("dqmc_measure_td_fine_read_host", C.c_int, [_P, C.c_int, _DP]),
+    ("dqmc_measure_td_matsubara_size", C.c_size_t, [_P, C.c_int, C.c_int]),
+    ("dqmc_measure_td_matsubara_host", C.c_int, [_P, C.c_int, C.c_int, _DP]),
     ("dqmc_get_green_td_fine_host", C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_int)]),
     ("dqmc_td_fine_propagate", C.c_int, [_P, C.c_int, C.c_int]),     # tests only: exported, not declared in include/dqmc_hip.h
     ("dqmc_profile_enable", C.c_int, [_P, C.c_int]),
@@ -231,6 +234,8 @@ SYMBOLS = [
     ("detsdw_get_info", C.c_int, [_P, C.POINTER(detsdw_info)]),
     ("detsdw_get_observables", C.c_int, [_P, C.POINTER(detsdw_observables)]),
     ("detsdw_get_observable_vector", C.c_int, [_P, C.c_int, _DP]),
+    ("detsdw_get_matsubara", C.c_int, [_P, C.c_int, C.c_int, _DP]),
+    ("detsdw_get_matsubara_all", C.c_int, [_P, C.c_int, C.c_int, _DP]),
     ("detsdw_get_tau_grid", C.c_int, [_P, _DP]),
     ("detsdw_get_tau_grid_fine", C.c_int, [_P, _DP]),
     ("detsdw_get_phi", C.c_int, [_P, _DP]),

@@ -95,6 +95,8 @@ struct dqmc_ctx {
     cplx *fGT0 = nullptr, *fG0T = nullptr, *fGTT = nullptr;
     double* facc[4] = {nullptr, nullptr, nullptr, nullptr};   // 0 G(k, tau) bins, 1 pairing, 2 particle-hole, 3 current
     size_t facc_n[4] = {0, 0, 0, 0};
+    double* mats_out = nullptr;                               // dqmc_measure_td_matsubara_host: results + one flag per chain, outside the arena,
+    size_t mats_cap = 0;                                      // allocated on first use and grown on demand (doubles)
     SvdWork sw{};
     double hub_e_m2a = 1.0, hub_e_p2a = 1.0;  // Hubbard: exp(-+2 alpha) of weightRatioSingleFlip (dethubbard.cpp:866-867)
     int stab = 0;                       // DQMC_STAB_SVD / DQMC_STAB_QR
@@ -822,6 +824,7 @@ extern "C" void dqmc_destroy(dqmc_ctx* c) {
     (void)hipSetDevice(c->p.device);
     if (c->st) (void)hipStreamSynchronize(c->st);
     for (void* q : c->allocs) (void)hipFree(q);
+    if (c->mats_out) (void)hipFree(c->mats_out);
     if (c->jacobi_graph) (void)hipGraphExecDestroy(c->jacobi_graph);
     if (c->sw.hflag) (void)hipHostFree(c->sw.hflag);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
@@ -1965,6 +1968,34 @@ extern "C" int dqmc_measure_td_fine_read_host(dqmc_ctx* c, int channel, double* 
     (void)hipSetDevice(c->p.device);
     HIPCHK(hipStreamSynchronize(c->st));
     HIPCHK(copy_sync(c, out, selp(c, c->facc[channel]), c->facc_n[channel] * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+extern "C" size_t dqmc_measure_td_matsubara_size(dqmc_ctx* c, int channel, int nfreq) {
+    if (!c || channel < 0 || channel >= 4 || !c->facc_n[channel] || nfreq < 1 || nfreq > c->m) return 0;
+    return (size_t)c->nb * (channel == 2 ? 3 : 2) * nfreq * c->N * 2;
+}
+extern "C" int dqmc_measure_td_matsubara_host(dqmc_ctx* c, int channel, int nfreq, double* out) {
+    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
+    if (!c->td_fine) return fail(DQMC_EINVAL, "context created without DQMC_TD_EVERY_SLICE");
+    if (channel < 0 || channel >= 4 || !c->facc_n[channel]) return fail(DQMC_EINVAL, "no every-slice block for this channel");
+    if (nfreq < 1 || nfreq > c->m) return fail(DQMC_EINVAL, "nfreq must be in 1..m");
+    (void)hipSetDevice(c->p.device);
+    const size_t n_out = dqmc_measure_td_matsubara_size(c, channel, nfreq), need = n_out + (size_t)c->nb;
+    if (need > c->mats_cap) {
+        HIPCHK(hipStreamSynchronize(c->st));
+        if (c->mats_out) { (void)hipFree(c->mats_out); c->mats_out = nullptr; c->mats_cap = 0; }
+        HIPCHK(hipMalloc((void**)&c->mats_out, need * sizeof(double)));
+        c->mats_cap = need;
+    }
+    const int apbx = c->p.bc == DQMC_BC_APBC_X || c->p.bc == DQMC_BC_APBC_XY, apby = c->p.bc == DQMC_BC_APBC_Y || c->p.bc == DQMC_BC_APBC_XY;
+    bool launched;
+    { ProfScope ps(c, FAM_OTHER, 1); launched = launch_td_matsubara(c->lc, c->hm, c->facc[channel], channel, nfreq, apbx, apby, c->mats_out, c->mats_out + n_out); }
+    if (!launched) return fail(DQMC_EINVAL, "dqmc_measure_td_matsubara_host: the lattice is too large for the kernel's LDS");
+    { const int rc = finish(c, "dqmc_measure_td_matsubara_host"); if (rc != DQMC_OK) return rc; }
+    std::vector<double> bad((size_t)c->nb);
+    HIPCHK(copy_sync(c, bad.data(), c->mats_out + n_out, bad.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (double b : bad) if (b != 0.0) return fail(DQMC_EINVAL, "an every-slice row has no sample: the measurement sweep did not visit every time slice");
+    HIPCHK(copy_sync(c, out, c->mats_out, n_out * sizeof(double), hipMemcpyDeviceToHost));
     return DQMC_OK;
 }
 extern "C" int dqmc_get_green_td_fine_host(dqmc_ctx* c, dqmc_cplx* g_t0, dqmc_cplx* g_0t, dqmc_cplx* g_tt, int* slice) {

@@ -257,6 +257,11 @@ size_t measure_td_row_doubles(int channel, int N, int L);   // stride of a row: 
 // every-slice end rows: (G, G - 1) -> (a_t0, a_0t), (1 - G, -G) -> (b_t0, b_0t), G -> gtt; one elementwise pass, all chains
 void launch_td_ends(const Launch& lc, const cplx* G, cplx* a_t0, cplx* a_0t, cplx* b_t0, cplx* b_0t, cplx* gtt, int ng);
 size_t measure_td_doubles(int L, int n);
+// Matsubara transforms of the every-slice block `acc` of `channel` (count[m+1], then the rows): out[chain][component][nfreq][N] (re, im),
+// bad[chain] = 1 if a row of the chain was never measured; out and bad are plain device arrays (no chain stride).  false: the lattice
+// is too large for the kernel's LDS, nothing was launched
+bool launch_td_matsubara(const Launch& lc, const DevModel& hm, const double* acc, int channel, int nfreq, int apbx, int apby,
+                         double* out, double* bad);
 // time-displaced pairing block: count[n-1], then per boundary j = 1 .. n-1 the sums over B of Re T+(B (+) d, B) [N] and Re T-(B (+) d, B) [N]
 void launch_measure_td_pair(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc, int row, int rows);
 size_t measure_td_pair_doubles(int N, int n);

@@ -19,9 +19,10 @@ void DetSDW::check(int rc, const char* what) {
     if (rc != DQMC_OK) throw GeneralError(rc, std::string(what) + ": " + dqmc_last_error());
 }
 
-// timeDisplacedMeasurements carries the level (0 / 1 / 2) in its low bits and DETSDW_TD_EVERY_SLICE as a flag bit
-static int td_level(const detsdw_params& p) { return p.timeDisplacedMeasurements & ~DETSDW_TD_EVERY_SLICE; }
+// timeDisplacedMeasurements carries the level (0 / 1 / 2) in its low bits and DETSDW_TD_EVERY_SLICE, DETSDW_TD_FINE_ON_DEVICE as flag bits
+static int td_level(const detsdw_params& p) { return p.timeDisplacedMeasurements & ~(DETSDW_TD_EVERY_SLICE | DETSDW_TD_FINE_ON_DEVICE); }
 static bool td_every_slice(const detsdw_params& p) { return (p.timeDisplacedMeasurements & DETSDW_TD_EVERY_SLICE) != 0; }
+static bool td_fine_on_device(const detsdw_params& p) { return (p.timeDisplacedMeasurements & DETSDW_TD_FINE_ON_DEVICE) != 0; }
 
 // field-wise comparison of two normalised parameter sets (struct padding is not the caller's business); everything but
 // the exchange parameter r, the device and -- unless seeds_too -- the RNG stream identity
@@ -34,7 +35,8 @@ static bool same_model(const detsdw_params& a, const detsdw_params& b, bool seed
                       a.repeatWolffPerSweep == b.repeatWolffPerSweep && a.fermionMeasurements == b.fermionMeasurements &&
                       a.spinProposalMethod == b.spinProposalMethod && a.adaptScaleVariance == b.adaptScaleVariance &&
                       a.repeatUpdateInSlice == b.repeatUpdateInSlice && td_level(a) == td_level(b) &&
-                      td_every_slice(a) == td_every_slice(b) && a.timeDisplacedParticleHole == b.timeDisplacedParticleHole;
+                      td_every_slice(a) == td_every_slice(b) && td_fine_on_device(a) == td_fine_on_device(b) &&
+                      a.timeDisplacedParticleHole == b.timeDisplacedParticleHole;
     const bool reals = a.beta == b.beta && a.dtau == b.dtau && a.c == b.c && a.u == b.u && a.lambda == b.lambda &&
                        a.txhor == b.txhor && a.txver == b.txver && a.tyhor == b.tyhor && a.tyver == b.tyver &&
                        a.mu == b.mu && a.mux == b.mux && a.muy == b.muy && a.accRatio == b.accRatio && a.cdwU == b.cdwU;
@@ -111,6 +113,8 @@ void DetSDW::normalise(detsdw_params& p, int& bcv) {
         throw ParameterWrong("Parameter timeDisplacedMeasurements has incorrect value");
     if (td_every_slice(p) && !td_level(p))
         throw ParameterWrong("timeDisplacedEverySlice needs timeDisplacedMeasurements");
+    if (td_fine_on_device(p) && !td_every_slice(p))
+        throw ParameterWrong("timeDisplacedFineOnDevice needs timeDisplacedEverySlice");
     if (p.timeDisplacedMeasurements && !p.fermionMeasurements)
         throw ParameterWrong("timeDisplacedMeasurements needs fermionMeasurements");
     if (p.timeDisplacedParticleHole < 0 || p.timeDisplacedParticleHole > 2)
@@ -323,6 +327,7 @@ void DetSDW::sweep_skeleton(Group& g, bool thermalization) {
 // the sweep, so they are accumulated afterwards from the final field, in the slice order of the sweep just done.
 void DetSDW::sweep(bool takeMeasurements) {
     const bool fermionic = takeMeasurements && ch_[0].pars.fermionMeasurements;
+    invalidateMatsubara();
     if (fermionic) for (auto& g : groups_) check(dqmc_measure_reset(g.ctx), "initMeasurements");
     measuring_ = fermionic;
     // the time-displaced pair is computed only during measurement sweeps: thermalisation sweeps pay nothing for it
@@ -334,6 +339,7 @@ void DetSDW::sweep(bool takeMeasurements) {
         measuringTD_ = false;
     };
     try { forEachGroup([this](Group& g) { sweep_skeleton(g, false); }); } catch (...) { off(); throw; }
+    tdBlocksValid_ = measuringTD_;
     off();
     lastSweepDir_ = (lastSweepDir_ == Up) ? Down : Up;
     ++performedSweeps_;
@@ -526,7 +532,8 @@ void DetSDW::finishFermionic(int b) {
         }
     };
     if (td_level(c.pars)) fill(false, c.td);
-    if (td_every_slice(c.pars)) fill(true, c.tdFine);
+    // timeDisplacedFineOnDevice: the fine blocks stay on the device, their reader is getMatsubara
+    if (td_every_slice(c.pars) && !td_fine_on_device(c.pars)) fill(true, c.tdFine);
     o.fermionic_valid = 1;
 }
 
@@ -545,6 +552,8 @@ void DetSDW::getObservableVector(int which_in, double* out, int b) const {
     const int which = which_in & ~DETSDW_OBS_FINE;
     if (fine && (which < DETSDW_OBS_GREENKTAU_X || which > DETSDW_OBS_BONDKINETICY)) throw ParameterWrong("unknown observable vector");
     if (fine && !td_every_slice(c.pars)) throw ParameterWrong("the ...Fine observables need timeDisplacedEverySlice");
+    if (fine && td_fine_on_device(c.pars))
+        throw ParameterWrong("the ...Fine observables are not formed with timeDisplacedFineOnDevice: read the Matsubara transforms");
     const TdObs& t = fine ? c.tdFine : c.td;
     const std::vector<double>* v = which == DETSDW_OBS_KOCCX ? &c.kOccX : which == DETSDW_OBS_KOCCY ? &c.kOccY
                                  : which == DETSDW_OBS_PAIRPLUS ? &c.pairPlus : which == DETSDW_OBS_PAIRMINUS ? &c.pairMinus
@@ -567,6 +576,54 @@ void DetSDW::getObservableVector(int which_in, double* out, int b) const {
     if (which >= DETSDW_OBS_CURRENTXTAU && which <= DETSDW_OBS_BONDKINETICY && c.pars.timeDisplacedParticleHole != 2)
         throw ParameterWrong("currentXTau / currentYTau / bondKineticX / bondKineticY need timeDisplacedParticleHole = 2");
     std::memcpy(out, v->data(), v->size() * sizeof(double));
+}
+
+// Matsubara transforms of the every-slice blocks.  which -> (channel, component) of dqmc_measure_td_matsubara_host; one device call per
+// kernel context transforms every chain and every component of the channel, and its result is kept until the next sweep, so the nine
+// observables of all chains cost four calls per context.
+void DetSDW::invalidateMatsubara() {
+    tdBlocksValid_ = false;
+    for (auto& g : groups_) for (int ch = 0; ch < 4; ++ch) g.matsNfreq[ch] = 0;
+}
+const double* DetSDW::matsubara(Group& g, int which, int nfreq, int& ncomp, int& comp) {
+    const detsdw_params& p = ch_[0].pars;
+    int channel;
+    if (which == DETSDW_OBS_GREENKTAU_X || which == DETSDW_OBS_GREENKTAU_Y) { channel = 0; comp = which - DETSDW_OBS_GREENKTAU_X; }
+    else if (which == DETSDW_OBS_PAIRPLUSTAU || which == DETSDW_OBS_PAIRMINUSTAU) { channel = 1; comp = which - DETSDW_OBS_PAIRPLUSTAU; }
+    else if (which >= DETSDW_OBS_CHARGETAU && which <= DETSDW_OBS_SDWTAU) { channel = 2; comp = which - DETSDW_OBS_CHARGETAU; }
+    else if (which == DETSDW_OBS_CURRENTXTAU || which == DETSDW_OBS_CURRENTYTAU) { channel = 3; comp = which - DETSDW_OBS_CURRENTXTAU; }
+    else throw ParameterWrong("no Matsubara transform of this observable");
+    ncomp = channel == 2 ? 3 : 2;
+    if (!td_every_slice(p)) throw ParameterWrong("the Matsubara transforms need timeDisplacedEverySlice");
+    if (channel == 1 && td_level(p) != 2) throw ParameterWrong("pairPlusTau / pairMinusTau need timeDisplacedMeasurements = 2");
+    if (channel == 2 && !p.timeDisplacedParticleHole) throw ParameterWrong("chargeTau / spinZTau / sdwTau need timeDisplacedParticleHole");
+    if (channel == 3 && p.timeDisplacedParticleHole != 2) throw ParameterWrong("currentXTau / currentYTau need timeDisplacedParticleHole = 2");
+    if (nfreq < 1 || nfreq > m_) throw ParameterWrong("nfreq must be in 1 .. m");
+    if (!tdBlocksValid_) throw GeneralError(DQMC_EINVAL, "the Matsubara transforms are valid after a measurement sweep and until the next sweep");
+    if (g.matsNfreq[channel] != nfreq) {
+        g.mats[channel].resize(dqmc_measure_td_matsubara_size(g.ctx, channel, nfreq));
+        g.matsNfreq[channel] = 0;
+        check(dqmc_measure_td_matsubara_host(g.ctx, channel, nfreq, g.mats[channel].data()), "dqmc_measure_td_matsubara_host");
+        g.matsNfreq[channel] = nfreq;
+    }
+    return g.mats[channel].data();
+}
+void DetSDW::getMatsubara(int which, int nfreq, double* out, int b) {
+    if (b < 0 || b >= (int)ch_.size()) throw ParameterWrong("chain index out of range");
+    Group& g = grp(b);
+    int ncomp, comp;
+    const double* v = matsubara(g, which, nfreq, ncomp, comp);
+    const size_t one = (size_t)nfreq * N_ * 2;
+    std::memcpy(out, v + ((size_t)(b - g.first) * ncomp + comp) * one, one * sizeof(double));
+}
+void DetSDW::getMatsubaraAll(int which, int nfreq, double* out) {
+    const size_t one = (size_t)nfreq * N_ * 2;
+    for (auto& g : groups_) {
+        int ncomp, comp;
+        const double* v = matsubara(g, which, nfreq, ncomp, comp);
+        for (int b = 0; b < g.count; ++b)
+            std::memcpy(out + (size_t)(g.first + b) * one, v + ((size_t)b * ncomp + comp) * one, one * sizeof(double));
+    }
 }
 
 // initMeasurements / measure / finishMeasurements, bosonic part (detsdwopdim.cpp:441-456, :509-545, :903-921)
@@ -610,6 +667,7 @@ void DetSDW::measureBosonic(Chain& c, bool descending) {
     o.valid = 1;
 }
 void DetSDW::sweepThermalization() {
+    invalidateMatsubara();
     forEachGroup([this](Group& g) { sweep_skeleton(g, true); });
     lastSweepDir_ = (lastSweepDir_ == Up) ? Down : Up;
     ++performedSweeps_;
@@ -895,6 +953,7 @@ void DetSDW::getCdwl(int32_t* out, int b) {
 }
 void DetSDW::setCdwl(const int32_t* in, int b) {
     if (ch_[b].pars.cdwU == 0.0) throw ParameterWrong("setCdwl: the replica was created with cdwU == 0");
+    invalidateMatsubara();
     dqmc_ctx* ctx_ = select(b);
     std::memcpy(ch_[b].cdwl.data(), in, ch_[b].cdwl.size() * sizeof(int32_t));
     check(dqmc_set_cdwl_host(ctx_, ch_[b].cdwl.data()), "dqmc_set_cdwl_host");
@@ -903,6 +962,7 @@ void DetSDW::setCdwl(const int32_t* in, int b) {
 }
 // also rebuilds UdV storage and G -- of every chain of the batch (one batched setup)
 void DetSDW::setPhi(const double* in, int b) {
+    invalidateMatsubara();
     dqmc_ctx* ctx_ = select(b);
     std::memcpy(ch_[b].phi.data(), in, ch_[b].phi.size() * sizeof(double));
     check(dqmc_set_fields_host(ctx_, ch_[b].phi.data()), "dqmc_set_fields_host");
@@ -1000,6 +1060,7 @@ void DetSDW::loadState(const std::string& path) {
         set_control_data(cd, b);
     }
     performedSweeps_ = hdr[2];
+    invalidateMatsubara();
     forEachGroup([this](Group& g) { setupUdVStorage_and_calculateGreen(g); });   // like the reference's resume: G(beta) from scratch, next sweep goes down
     lastSweepDir_ = Up;
 }
@@ -1061,6 +1122,14 @@ extern "C" int detsdw_get_observables(detsdw_replica* r, detsdw_observables* out
 }
 extern "C" int detsdw_get_observable_vector(detsdw_replica* r, int which, double* out) {
     RGUARD(r->impl->getObservableVector(which, out, r->sel))
+}
+extern "C" int detsdw_get_matsubara(detsdw_replica* r, int which, int nfreq, double* out) {
+    if (!out) { g_host_err = "null argument"; return DQMC_EINVAL; }
+    RGUARD(r->impl->getMatsubara(which, nfreq, out, r->sel))
+}
+extern "C" int detsdw_get_matsubara_all(detsdw_replica* r, int which, int nfreq, double* out) {
+    if (!out) { g_host_err = "null argument"; return DQMC_EINVAL; }
+    RGUARD(r->impl->getMatsubaraAll(which, nfreq, out))
 }
 extern "C" int detsdw_get_tau_grid(detsdw_replica* r, double* out) {
     if (!out) { g_host_err = "null argument"; return DQMC_EINVAL; }

@@ -57,6 +57,10 @@ public:
     void getObservableVector(int which, double* out, int b = 0) const;
     void getTauGrid(double* out) const;
     void getTauGridFine(double* out) const;        // k dtau, k = 0 .. m (timeDisplacedEverySlice)
+    // chi(q, i omega_n) / G(k, i omega_n) of the every-slice observable `which`, n = 0 .. nfreq-1: out[nfreq][N] (re, im) of chain b, or
+    // out[nchains][nfreq][N] of every chain in handle order; valid after a measurement sweep and until the next sweep
+    void getMatsubara(int which, int nfreq, double* out, int b = 0);
+    void getMatsubaraAll(int which, int nfreq, double* out);
     void getPhi(double* phi, int b = 0);
     void setPhi(const double* phi, int b = 0);
     void getCdwl(int32_t* cdwl, int b = 0);
@@ -102,6 +106,8 @@ private:
         int first = 0, count = 0;
         std::vector<double> window;                // uniforms of the coming sweep, all chains of the group
         std::vector<double> fields;                // host staging of all chains' fields (global moves)
+        std::vector<double> mats[4];               // Matsubara transforms of the group's chains per channel, [chain][component][nfreq][N] (re, im)
+        int matsNfreq[4] = {0, 0, 0, 0};           // ... and the nfreq they hold (0: none); cleared by every sweep
     };
     std::vector<Group> groups_;
     int N_, MSF_, ng_, m_, s_, n_, opdim_;
@@ -120,6 +126,9 @@ private:
     void finishFermionic(int b);
     bool measuring_ = false;          // measure(k) after the updates of slice k (updateInSliceAndMaybeMeasure)
     bool measuringTD_ = false;        // ... and G(tau_j, 0) after every interior advance (timeDisplacedMeasurements)
+    bool tdBlocksValid_ = false;      // the device's time-displaced blocks are those of the last sweep, a measurement sweep
+    void invalidateMatsubara();
+    const double* matsubara(Group& g, int which, int nfreq, int& ncomp, int& comp);
     void measureTimeDisplaced(Group& g, int j);
     void measureTimeDisplacedEnds(Group& g);
     void sweepDown(Group& g, bool thermalization);

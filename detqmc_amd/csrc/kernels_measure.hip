@@ -619,3 +619,152 @@ void launch_td_ends(const Launch& lc, const cplx* G, cplx* a_t0, cplx* a_0t, cpl
     const dim3 grid((unsigned)((total + 255) / 256), 1, lc.nb);
     hipLaunchKernelGGL(k_td_ends, grid, dim3(256), 0, lc.st, G, a_t0, a_0t, b_t0, b_0t, gtt, ng, lc.cs);
 }
+
+// Matsubara transforms of one every-slice block (dqmc_measure_td_matsubara_host; definitions in dqmc_hip.h and DESIGN.md 6e).  With the
+// rows row_k[e] of one component (a correlator over the N periodic site differences, or the (2L-1)^2 complex bins of one band), their
+// sample counts and the trapezoid weights w_0 = w_m = 1/2,
+//   A_n[e] = sum_k w_k cos(phi_nk) row_k[e] / count_k,   B_n[e] = sum_k w_k sin(phi_nk) row_k[e] / count_k,   phi_nk = omega_n tau_k,
+// followed by the spatial Fourier sum of A_n and B_n.  phi_nk is a rational multiple of pi: 2 pi (n k mod m) / m for the bosonic
+// frequencies, pi ((2n+1) k mod 2m) / m for the fermionic ones; the index is reduced in integers and goes through sincospi, so the
+// twiddles of a large n k are as exact as those of a small one.  The same holds for the spatial phases (index mod 2L).
+// Shape: one workgroup per (frequency tile, component, chain).  A tile of nf <= TDM_FT frequencies keeps its weighted twiddles
+// tw[f][k] in LDS; thread e walks the rows k = 0 .. m of column e (lanes read consecutive doubles of a row) with the 2 nf sums in
+// registers, so a tile reads its component once, and leaves A and B in LDS.  There the separable transform runs per frequency: first
+// over y (lanes along x, stride 1), then over x (table rows padded to an odd length, so that lanes on consecutive k_x hit different
+// banks).  Correlators: chi = F(A) + i F(B) = F(A + i B) with e^{-i q d}, one complex transform.  Channel 0: A and B are complex and
+// G = Re F(A) + i Re F(B) with the phases e^{+i k (d - (L-1))}, k = -pi + (kk + 1/2 on antiperiodic directions) 2 pi / L, of the host's
+// greenKTau sum: two transforms, each writes its half of the output element.  One writer per output element, fixed summation order
+// (k, then y, then x ascending), no atomics.  bad[chain] = 1 if a row of the chain has a count < 1 (written by workgroup (0, 0) alone).
+#define TDM_FT 8
+struct TdmShape { int channel, ncomp, nfreq, ftile, m, L, N, W, WP, rlen, stride, apbx, apby; double scale; };
+
+size_t measure_td_matsubara_lds_doubles(int ftile, int m, int L, int W, int rlen) {
+    const int WP = W | 1;
+    return (size_t)ftile * (m + 1) * 2 + 2 * (size_t)(2 * L * WP) + (size_t)2 * L * W + (size_t)ftile * 2 * rlen;
+}
+
+// T[ky][ix] = sum_iy ty[ky][iy] U[iy][ix], then emit(ky L + kx, sum_ix tx[kx][ix] T[ky][ix]); U = (ur, ui)[(iy W + ix) str]
+template<class Emit>
+__device__ __forceinline__ void tdm_dft2(const TdmShape& a, const double* tx, const double* ty, double* T, const double* ur, const double* ui,
+                                         int str, Emit emit) {
+    const int L = a.L, W = a.W, WP = a.WP;
+    for (int i = threadIdx.x; i < L * W; i += 256) {
+        const int ky = i / W, ix = i - ky * W;
+        const double* t = ty + (size_t)2 * ky * WP;
+        double re = 0.0, im = 0.0;
+        for (int iy = 0; iy < W; ++iy) {
+            const double c = t[2 * iy], s = t[2 * iy + 1], xr = ur[(size_t)(iy * W + ix) * str], xi = ui[(size_t)(iy * W + ix) * str];
+            re += c * xr - s * xi;
+            im += c * xi + s * xr;
+        }
+        T[2 * i] = re; T[2 * i + 1] = im;
+    }
+    __syncthreads();
+    for (int q = threadIdx.x; q < a.N; q += 256) {
+        const int ky = q / L, kx = q - ky * L;
+        const double* t = tx + (size_t)2 * kx * WP;
+        const double* v = T + (size_t)2 * ky * W;
+        double re = 0.0, im = 0.0;
+        for (int ix = 0; ix < W; ++ix) {
+            const double c = t[2 * ix], s = t[2 * ix + 1];
+            re += c * v[2 * ix] - s * v[2 * ix + 1];
+            im += c * v[2 * ix + 1] + s * v[2 * ix];
+        }
+        emit(q, re, im);
+    }
+    __syncthreads();                                        // T is free again
+}
+
+__global__ __launch_bounds__(256) void k_td_matsubara(const double* __restrict__ acc, double* __restrict__ out, double* __restrict__ bad,
+                                                      TdmShape a, size_t cs) {
+    CHAIN(acc);
+    extern __shared__ double tdm_sm[];
+    const int tid = threadIdx.x, comp = blockIdx.y, rows = a.m + 1, m = a.m, L = a.L, W = a.W, WP = a.WP, R = a.rlen;
+    const int f0 = blockIdx.x * a.ftile, nf = a.nfreq - f0 < a.ftile ? a.nfreq - f0 : a.ftile;
+    const bool fermionic = a.channel == 0;
+    double* tw = tdm_sm;                                    // [ftile][rows] (w_k cos / count_k, w_k sin / count_k)
+    double* tx = tw + (size_t)a.ftile * rows * 2;           // [L][WP] (cos, sin)
+    double* ty = tx + (size_t)2 * L * WP;
+    double* T = ty + (size_t)2 * L * WP;                    // [L][W] complex, between the two passes
+    double* Z = T + (size_t)2 * L * W;                      // [ftile][A, B][R]
+    int anybad = 0;
+    for (int k = tid; k < rows; k += 256) anybad |= !(acc[k] >= 1.0);
+    for (int i = tid; i < nf * rows; i += 256) {
+        const int f = i / rows, k = i - f * rows, n = f0 + f;
+        const long long red = fermionic ? ((long long)(2 * n + 1) * k) % (2 * m) : (2 * (((long long)n * k) % m));
+        double s, c;
+        sincospi((double)red / (double)m, &s, &c);
+        const double w = ((k == 0 || k == m) ? 0.5 : 1.0) / acc[k];
+        tw[2 * i] = w * c; tw[2 * i + 1] = w * s;
+    }
+    for (int i = tid; i < L * W; i += 256) {
+        const int kk = i / W, d = i - kk * W;
+        int numx, numy;                                     // phase = pi num / L
+        if (fermionic) { numx = (d - (L - 1)) * (2 * kk + a.apbx - L); numy = (d - (L - 1)) * (2 * kk + a.apby - L); }
+        else numx = numy = -2 * kk * d;
+        numx %= 2 * L; if (numx < 0) numx += 2 * L;
+        numy %= 2 * L; if (numy < 0) numy += 2 * L;
+        double s, c;
+        sincospi((double)numx / (double)L, &s, &c);
+        tx[2 * (kk * WP + d)] = c; tx[2 * (kk * WP + d) + 1] = s;
+        sincospi((double)numy / (double)L, &s, &c);
+        ty[2 * (kk * WP + d)] = c; ty[2 * (kk * WP + d) + 1] = s;
+    }
+    anybad = __syncthreads_or(anybad);
+    if (blockIdx.x == 0 && comp == 0 && tid == 0) bad[blockIdx.z] = anybad ? 1.0 : 0.0;
+    // time step: column e of the component, rows in ascending order
+    const double* rowsp = acc + rows + (size_t)comp * R;
+    for (int e0 = 0; e0 < R; e0 += 256) {
+        const int e = e0 + tid;
+        const bool valid = e < R;
+        const double* p = rowsp + (valid ? e : 0);
+        double A[TDM_FT], B[TDM_FT];
+#pragma unroll
+        for (int f = 0; f < TDM_FT; ++f) { A[f] = 0.0; B[f] = 0.0; }
+#pragma unroll 4
+        for (int k = 0; k < rows; ++k) {
+            const double v = p[(size_t)k * a.stride];
+#pragma unroll
+            for (int f = 0; f < TDM_FT; ++f)
+                if (f < nf) { A[f] += tw[2 * (f * rows + k)] * v; B[f] += tw[2 * (f * rows + k) + 1] * v; }
+        }
+        if (valid) {
+#pragma unroll
+            for (int f = 0; f < TDM_FT; ++f)
+                if (f < nf) { Z[(size_t)(2 * f) * R + e] = A[f]; Z[(size_t)(2 * f + 1) * R + e] = B[f]; }
+        }
+    }
+    __syncthreads();
+    double* o = out + (((size_t)blockIdx.z * a.ncomp + comp) * a.nfreq + f0) * (size_t)a.N * 2;
+    for (int f = 0; f < nf; ++f, o += (size_t)a.N * 2) {
+        const double* zA = Z + (size_t)(2 * f) * R;
+        const double* zB = zA + R;
+        const double sc = a.scale;
+        if (fermionic) {
+            tdm_dft2(a, tx, ty, T, zA, zA + 1, 2, [&](int q, double re, double) { o[2 * q] = sc * re; });
+            tdm_dft2(a, tx, ty, T, zB, zB + 1, 2, [&](int q, double re, double) { o[2 * q + 1] = sc * re; });
+        } else {
+            tdm_dft2(a, tx, ty, T, zA, zB, 1, [&](int q, double re, double im) { o[2 * q] = sc * re; o[2 * q + 1] = sc * im; });
+        }
+    }
+}
+
+// out: [chain][component][nfreq][N] (re, im), bad: [chain]; both plain device arrays outside the arena.  Returns false if not even one
+// frequency of the lattice fits the LDS of a workgroup (nothing is launched then).
+bool launch_td_matsubara(const Launch& lc, const DevModel& hm, const double* acc, int channel, int nfreq, int apbx, int apby,
+                         double* out, double* bad) {
+    const int L = hm.L, N = hm.N, m = hm.m, W = channel == 0 ? 2 * L - 1 : L;
+    const int rlen = channel == 0 ? 2 * W * W : N, ncomp = channel == 2 ? 3 : 2;
+    const size_t budget = 152 * 1024;
+    int ftile = nfreq < TDM_FT ? nfreq : TDM_FT;
+    while (ftile >= 1 && measure_td_matsubara_lds_doubles(ftile, m, L, W, rlen) * sizeof(double) > budget) --ftile;
+    if (ftile < 1) return false;
+    const size_t lds = measure_td_matsubara_lds_doubles(ftile, m, L, W, rlen) * sizeof(double);
+    if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)k_td_matsubara, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        (void)hipGetLastError();                            // the launch below then reports the problem
+    TdmShape a{channel, ncomp, nfreq, ftile, m, L, N, W, W | 1, rlen, (int)measure_td_row_doubles(channel, N, L), apbx, apby,
+               hm.dtau / (channel == 0 ? 2.0 * N : (double)N)};
+    const dim3 grid((nfreq + ftile - 1) / ftile, ncomp, lc.nb);
+    hipLaunchKernelGGL(k_td_matsubara, grid, dim3(256), lds, lc.st, acc, out, bad, a, lc.cs);
+    return true;
+}

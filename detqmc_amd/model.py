@@ -59,6 +59,7 @@ class SDWParams:
     timeDisplacedParticleHole: bool = False   # ... and the charge / spin-z / SDW correlators C(r, tau_j) (needs timeDisplacedMeasurements)
     timeDisplacedCurrent: bool = False        # ... and the current-current correlators Lambda_xx/yy(r, tau_j) (needs timeDisplacedParticleHole)
     timeDisplacedEverySlice: bool = False     # ... every enabled channel also on every slice tau_k = k dtau, k = 0 .. m: the '...Fine' observables (needs timeDisplacedMeasurements)
+    timeDisplacedFineOnDevice: bool = False   # ... whose blocks then stay on the device: no '...Fine' observables, matsubara() reads them (needs timeDisplacedEverySlice)
     globalUpdateInterval: int = 100
     phi2bosons: bool = False
     cdwU: float = 0.0
@@ -77,6 +78,20 @@ class SDWParams:
     maxJacobiSweeps: int = 0     # SVD mode: sweep budget of the Jacobi SVD (0 = 80)
     proposalBudget: int = 0      # proposals per delayed-update block (-1: no limit)
     decideThreads: int = 0       # threads per workgroup of the decision kernel (0: automatic, 256, 512); launch shape only
+
+
+# observables with a Matsubara transform (DetSDW.matsubara): name -> index of detsdw_get_observable_vector
+MATSUBARA = {"greenKTauX": 4, "greenKTauY": 5, "pairPlusTau": 6, "pairMinusTau": 7, "chargeTau": 10, "spinZTau": 11, "sdwTau": 12,
+             "currentXTau": 16, "currentYTau": 17}
+
+
+def superfluid_stiffness(chi_xx, chi_yy, L):
+    """rho_s = 1/8 Re [Lxx(qx=1, qy=0; 0) - Lxx(qx=0, qy=1; 0) + Lyy(qx=0, qy=1; 0) - Lyy(qx=1, qy=0; 0)] from
+    chi_xx = matsubara('currentXTau', nfreq), chi_yy = matsubara('currentYTau', nfreq) (last two axes: frequency, q = qy L + qx):
+    rho_s = 1/4 [Lambda_xx(q_x -> 0, q_y = 0) - Lambda_xx(q_x = 0, q_y -> 0)] at i omega = 0 and the smallest non-zero q, averaged over
+    the two directions.  Leading axes (chains) are kept."""
+    xx, yy = np.asarray(chi_xx)[..., 0, :], np.asarray(chi_yy)[..., 0, :]
+    return 0.125 * np.real(xx[..., 1] - xx[..., L] + yy[..., L] - yy[..., 1])
 
 
 SPIN_PROPOSAL = {"box": 0, "rotate_then_scale": 1, "rotate_and_scale": 2}
@@ -224,6 +239,12 @@ class KernelContext:
         out = np.zeros(self.lib.dqmc_measure_td_fine_accum_size(self.h, channel))
         check(self.lib.dqmc_measure_td_fine_read_host(self.h, channel, out.ctypes.data_as(_lib._DP)))
         return out
+
+    def measure_td_matsubara(self, channel, nfreq):
+        """Matsubara transforms of the fine block of `channel`, every chain and component: complex (nchains, components, nfreq, N)"""
+        out = np.zeros(self.lib.dqmc_measure_td_matsubara_size(self.h, channel, nfreq))
+        check(self.lib.dqmc_measure_td_matsubara_host(self.h, channel, nfreq, out.ctypes.data_as(_lib._DP)))
+        return out.view(np.complex128).reshape(self.nchains_total(), 3 if channel == 2 else 2, nfreq, self.N)
 
     def td_fine_propagate(self, j, k):
         """for tests: the work copies at slice k of boundary j's segment, by the steps of measure_timedisplaced_segment; measures nothing"""
@@ -460,7 +481,8 @@ def _host_params(pars: SDWParams):
         repeatWolffPerSweep=int(pars.repeatWolffPerSweep), fermionMeasurements=int(pars.fermionMeasurements),
         spinProposalMethod=SPIN_PROPOSAL[pars.spinProposalMethod], adaptScaleVariance=int(pars.adaptScaleVariance),
         repeatUpdateInSlice=int(pars.repeatUpdateInSlice), timeDisplacedMeasurements=(2 if pars.timeDisplacedPairing else int(bool(pars.timeDisplacedMeasurements)))
-        | (_lib.DETSDW_TD_EVERY_SLICE if pars.timeDisplacedEverySlice else 0),     # without timeDisplacedMeasurements: ParameterWrong from the library
+        | (_lib.DETSDW_TD_EVERY_SLICE if pars.timeDisplacedEverySlice else 0)      # without timeDisplacedMeasurements: ParameterWrong from the library
+        | (_lib.DETSDW_TD_FINE_ON_DEVICE if pars.timeDisplacedFineOnDevice else 0),  # without timeDisplacedEverySlice: the same
         timeDisplacedParticleHole=(2 if pars.timeDisplacedCurrent else int(bool(pars.timeDisplacedParticleHole))),
         tuning=_tuning(pars.pipeline, pars.qrVariant, pars.greenVariant, pars.maxJacobiSweeps, pars.proposalBudget, pars.decideThreads))
 
@@ -554,6 +576,21 @@ class DetSDW:
         out = np.zeros(info.N if which < 4 else (rows, info.N) if which < 8 or 10 <= which < 13 or 16 <= which < 18 else rows)
         check(self.lib.detsdw_get_observable_vector(self.h, which | (_lib.DETSDW_OBS_FINE if fine else 0), out.ctypes.data_as(_lib._DP)), host=True)
         return out
+
+    def matsubara(self, name, nfreq):
+        """chi(q, i omega_n) of 'pairPlusTau', 'pairMinusTau', 'chargeTau', 'spinZTau', 'sdwTau', 'currentXTau', 'currentYTau' (column
+        qy L + qx, q = 2 pi (qx, qy) / L) or G(k, i omega_n) of 'greenKTauX', 'greenKTauY' (column = k-vector as for kOcc), n = 0 ..
+        nfreq-1: complex (nfreq, N), formed on the device from the every-slice blocks of the last sweep(True) by the trapezoid rule
+        (needs timeDisplacedEverySlice; valid until the next sweep).  Frequencies: matsubara_frequencies()"""
+        self._sel()
+        out = np.zeros((int(nfreq), self.info.N), dtype=np.complex128)
+        check(self.lib.detsdw_get_matsubara(self.h, MATSUBARA[name], int(nfreq), out.ctypes.data_as(_lib._DP)), host=True)
+        return out
+
+    def matsubara_frequencies(self, nfreq, fermionic=False):
+        """omega_n, n = 0 .. nfreq-1: 2 pi n / beta, or (2n+1) pi / beta for the fermionic 'greenKTauX' / 'greenKTauY'"""
+        n = np.arange(int(nfreq))
+        return ((2 * n + 1) if fermionic else 2 * n) * np.pi / self.info.beta
 
     def tau_grid(self, fine=False):
         """tau_j = j s dtau, j = 1 .. n-1: the rows of greenKTauX / greenKTauY; fine=True (timeDisplacedEverySlice): tau_k = k dtau,
@@ -696,6 +733,12 @@ class DetSDWBatch:
 
     def load_state(self, path):
         check(self.lib.detsdw_load_state(self.h, str(path).encode()), host=True)
+
+    def matsubara_all(self, name, nfreq):
+        """DetSDW.matsubara of every chain: complex (nchains, nfreq, N), one device call per sub-batch"""
+        out = np.zeros((len(self.chains), int(nfreq), self.chains[0].info.N), dtype=np.complex128)
+        check(self.lib.detsdw_get_matsubara_all(self.h, MATSUBARA[name], int(nfreq), out.ctypes.data_as(_lib._DP)), host=True)
+        return out
 
     def exchange_actions_device(self, device_ptr):
         """get_exchange_action_contribution of EVERY chain written to device memory (len(self) doubles at device_ptr, e.g.

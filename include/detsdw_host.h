@@ -66,7 +66,10 @@ typedef struct detsdw_params {
                                          | DETSDW_TD_EVERY_SLICE (timeDisplacedEverySlice; needs a level >= 1, ParameterWrong otherwise):
                                          every enabled time-displaced channel is also measured on every time slice tau_k = k dtau,
                                          k = 0 .. m (DETSDW_OBS_FINE).  The struct has no free slot and its bytes stay where they are,
-                                         so the option travels as a flag bit, as in dqmc_params::timedisplaced */
+                                         so the option travels as a flag bit, as in dqmc_params::timedisplaced.
+                                         | DETSDW_TD_FINE_ON_DEVICE (timeDisplacedFineOnDevice; needs DETSDW_TD_EVERY_SLICE, ParameterWrong
+                                         otherwise): the every-slice blocks are not copied to the host after a measurement sweep; the
+                                         ...Fine observables raise ParameterWrong and detsdw_get_matsubara* are their readers */
     dqmc_tuning tuning;               /* result-neutral execution choices handed to every kernel context (dqmc_hip.h); all zero =
                                          automatic.  With pipeline = 0 the host layer switches the pipelined update on only for
                                          handles of at most two kernel contexts (more contexts overlap each other instead) */
@@ -128,6 +131,8 @@ enum { DETSDW_OBS_KOCCX = 0, DETSDW_OBS_KOCCY = 1, DETSDW_OBS_PAIRPLUS = 2, DETS
        DETSDW_OBS_BONDKINETICX = 20, DETSDW_OBS_BONDKINETICY = 21 };
 /* timeDisplacedEverySlice: flag bit of detsdw_params::timeDisplacedMeasurements */
 enum { DETSDW_TD_EVERY_SLICE = 0x100 };
+/* timeDisplacedFineOnDevice: flag bit of detsdw_params::timeDisplacedMeasurements; never reaches dqmc_params::timedisplaced */
+enum { DETSDW_TD_FINE_ON_DEVICE = 0x200 };
 /* which | DETSDW_OBS_FINE for which = DETSDW_OBS_GREENKTAU_X .. _BONDKINETICY: the every-slice twin ("...Fine") of the observable, rows
  * k = 0 .. m instead of j = 1 .. n-1, columns unchanged; needs timeDisplacedEverySlice next to the option its coarse twin needs */
 enum { DETSDW_OBS_FINE = 0x100 };    /* a bit of the observable index: unrelated to DETSDW_TD_EVERY_SLICE, a bit of a parameter */
@@ -172,8 +177,22 @@ int detsdw_get_observables(detsdw_replica* r, detsdw_observables* out);
  * With timeDisplacedParticleHole == 2: currentXTau / currentYTau, (n-1) x N, same rows and columns:
  *   Lambda_mumu(d, tau_j) = (1/N) sum_B Re W[j_mu(B (+) d), j_mu(B)],  j_mu the bond current of dqmc_measure_timedisplaced_current;
  * currentXTauQ0 / currentYTauQ0, n-1: their sums over d; bondKineticX / bondKineticY, n-1: (1/N) sum_A Re <k_mu(A)> at tau_j, the
- * diamagnetic term.  The tau quadrature and the q -> 0 limits stay with the caller */
+ * diamagnetic term.  The tau quadrature and the Fourier sum over d of the every-slice twins: detsdw_get_matsubara below */
 int detsdw_get_observable_vector(detsdw_replica* r, int which, double* out);
+/* With timeDisplacedEverySlice: the Matsubara transforms of the every-slice observable `which`, formed on the device from the blocks
+ * of the last measurement sweep (dqmc_measure_td_matsubara_host, dqmc_hip.h), n = 0 .. nfreq-1, 1 <= nfreq <= m, trapezoid weights
+ * w_0 = w_m = 1/2 over tau_k = k dtau.  which = DETSDW_OBS_PAIRPLUSTAU, _PAIRMINUSTAU, _CHARGETAU, _SPINZTAU, _SDWTAU, _CURRENTXTAU,
+ * _CURRENTYTAU (no DETSDW_OBS_FINE bit), omega_n = 2 pi n / beta:
+ *   chi(q, i omega_n) = dtau sum_k w_k e^{i omega_n tau_k} sum_d e^{-i q d} C(d, tau_k),   q = (2 pi / L)(qx, qy), column qy L + qx;
+ * which = DETSDW_OBS_GREENKTAU_X / _Y, omega_n = (2n+1) pi / beta:
+ *   G_band(k, i omega_n) = dtau sum_k w_k e^{i omega_n tau_k} G_band(k, tau_k),   column = k-vector as for kOcc.
+ * detsdw_get_matsubara: the selected chain, out[nfreq][N] complex as (re, im); detsdw_get_matsubara_all: every chain in handle order,
+ * out[nchains][nfreq][N], ONE device call per kernel context.  Valid after detsdw_sweep(r, 1) and until the next sweep of either
+ * kind (DQMC_EINVAL otherwise); ParameterWrong if the option `which` needs, or timeDisplacedEverySlice, is off.  The superfluid density
+ * follows from Lambda_xx, Lambda_yy at i omega = 0 and the smallest non-zero q:
+ *   rho_s = 1/8 Re [ Lxx(qx=1, qy=0) - Lxx(qx=0, qy=1) + Lyy(qx=0, qy=1) - Lyy(qx=1, qy=0) ] */
+int detsdw_get_matsubara(detsdw_replica* r, int which, int nfreq, double* out);
+int detsdw_get_matsubara_all(detsdw_replica* r, int which, int nfreq, double* out);
 /* tau_j = j s dtau of the rows of greenKTauX / Y, j = 1 .. n-1: out[n-1] */
 int detsdw_get_tau_grid(detsdw_replica* r, double* out);
 /* With timeDisplacedEverySlice: tau_k = k dtau of the rows of the ...Fine observables, k = 0 .. m: out[m+1].  Interior rows k = 1 .. m-1

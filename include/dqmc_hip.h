@@ -349,9 +349,10 @@ int dqmc_measure_td_ph_read_host(dqmc_ctx* ctx, double* out);
  * matrices, leaves G and the other measurement blocks alone and works in either order with the other calls of the boundary.
  * Layout (doubles, dqmc_measure_td_current_accum_size of them): count[n-1], then for j = 1 .. n-1 the Lambda_xx sums [N], the Lambda_yy
  * sums [N], sum_A Re o_tau[k_x] and sum_A Re o_tau[k_y], at offset (n-1) + (j-1) (2N + 2); dividing by N and by the count gives the
- * translation averages.  The tau quadrature and the q -> 0 limits of the superfluid density
+ * translation averages.  The superfluid density
  *   rho_s = 1/4 [ Lambda_xx(q_x -> 0, q_y = 0, i omega = 0) - Lambda_xx(q_x = 0, q_y -> 0, i omega = 0) ]
- * stay with the reader of the block.  dqmc_measure_reset clears the block as well. */
+ * needs the tau quadrature and the smallest non-zero q: with DQMC_TD_EVERY_SLICE, dqmc_measure_td_matsubara_host (below) forms
+ * Lambda_mumu(q, i omega_n) on the device; a reader of the coarse block does it itself.  dqmc_measure_reset clears the block as well. */
 int dqmc_measure_timedisplaced_current(dqmc_ctx* ctx, int j);
 size_t dqmc_measure_td_current_accum_size(dqmc_ctx* ctx);   /* 0 without the reservation */
 int dqmc_measure_td_current_read_host(dqmc_ctx* ctx, double* out);
@@ -383,6 +384,23 @@ int dqmc_measure_timedisplaced_segment(dqmc_ctx* ctx, int j);
 int dqmc_measure_timedisplaced_ends(dqmc_ctx* ctx);
 size_t dqmc_measure_td_fine_accum_size(dqmc_ctx* ctx, int channel);
 int dqmc_measure_td_fine_read_host(dqmc_ctx* ctx, int channel, double* out);
+/* Matsubara transforms of one every-slice block, all chains and all components of the block in ONE launch (kernels_measure.hip).
+ * With C_X(d, tau_k) = row k of component X divided by N and by the row's sample count, the trapezoid weights w_0 = w_m = 1/2 (1 otherwise)
+ * over the closed grid tau_k = k dtau, k = 0 .. m, and n = 0 .. nfreq-1 (1 <= nfreq <= m):
+ *   channels 1, 2, 3 (bosonic, omega_n = 2 pi n / beta):
+ *     chi_X(q, i omega_n) = dtau sum_k w_k e^{i omega_n tau_k} sum_d e^{-i q d} C_X(d, tau_k),  q = (2 pi / L)(qx, qy), column qy L + qx
+ *   channel 0 (fermionic, omega_n = (2n+1) pi / beta), band X, Y:
+ *     G_band(k, i omega_n) = dtau sum_k w_k e^{i omega_n tau_k} G_band(k, tau_k),  G_band(k, tau) = Re (Fourier sum over the bins) / 2N,
+ *     column = the k-vector index of kOcc / greenKTau (k = -pi + (kk + 1/2 along antiperiodic directions) 2 pi / L); rows 0 and m as
+ *     dqmc_measure_timedisplaced_ends wrote them.
+ * out: [chain][component][nfreq][N] complex as (re, im), dqmc_measure_td_matsubara_size(ctx, channel, nfreq) doubles (0 for arguments
+ * the call below rejects); component order = the block's order: X, Y / T+, T- / charge, spinZ, sdw / Lambda_xx, Lambda_yy (the two bond
+ * kinetic sums of channel 3 are not transformed).  DQMC_EINVAL without the every-slice reservation, without that channel's block, for
+ * nfreq outside 1 .. m, or if a row of any chain has a sample count < 1 (nothing is written to out then).  Reads the block only: G, the
+ * pair, G(0) and every accumulator stay bit-identical; one writer per output element and a fixed summation order, so two calls give
+ * identical bits.  The device result buffer lies outside the arena, is allocated on first use and freed with the context. */
+size_t dqmc_measure_td_matsubara_size(dqmc_ctx* ctx, int channel, int nfreq);
+int dqmc_measure_td_matsubara_host(dqmc_ctx* ctx, int channel, int nfreq, double* out);
 /* for tests: the last propagated triple G(tau_k,0), G(0,tau_k), G(tau_k) of the selected chain and its slice k (after
  * dqmc_measure_timedisplaced_ends: the triple of row m) */
 int dqmc_get_green_td_fine_host(dqmc_ctx* ctx, dqmc_cplx* g_t0, dqmc_cplx* g_0t, dqmc_cplx* g_tt, int* slice);
