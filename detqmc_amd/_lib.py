@@ -22,6 +22,7 @@ DQMC_TD_EVERY_SLICE = 0x100     # flag bit of dqmc_params.timedisplaced
 DETSDW_TD_EVERY_SLICE = 0x100   # flag bit of detsdw_params.timeDisplacedMeasurements
 DETSDW_TD_FINE_ON_DEVICE = 0x200  # flag bit of detsdw_params.timeDisplacedMeasurements: the fine blocks stay on the device
 DETSDW_OBS_FINE = 0x100         # flag bit of the observable index: the every-slice twin
+DETSDW_FM_EQ_CORRELATORS = 0x100  # flag bit of detsdw_params.fermionMeasurements: equal-time charge / spin / SDW / pairing correlators
 
 
 class dqmc_cplx(C.Structure):
@@ -195,6 +196,9 @@ SYMBOLS = [
     ("dqmc_measure_slice", C.c_int, [_P]),
     ("dqmc_measure_accum_size", C.c_size_t, [_P]),
     ("dqmc_measure_read_host", C.c_int, [_P, _DP]),
+    ("dqmc_set_equal_time_correlators", C.c_int, [_P, C.c_int]),
+    ("dqmc_measure_eq_accum_size", C.c_size_t, [_P]),
+    ("dqmc_measure_eq_read_host", C.c_int, [_P, _DP]),
     ("dqmc_set_timedisplaced", C.c_int, [_P, C.c_int]),
     ("dqmc_get_green_timedisplaced_host", C.c_int, [_P, _P, _P, C.POINTER(C.c_int)]),
     ("dqmc_measure_timedisplaced", C.c_int, [_P, C.c_int]),

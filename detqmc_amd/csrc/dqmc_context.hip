@@ -97,6 +97,11 @@ struct dqmc_ctx {
     size_t facc_n[4] = {0, 0, 0, 0};
     double* mats_out = nullptr;                               // dqmc_measure_td_matsubara_host: results + one flag per chain, outside the arena,
     size_t mats_cap = 0;                                      // allocated on first use and grown on demand (doubles)
+    // dqmc_set_equal_time_correlators: block [chain][1 + 5 N] and one-body scratch [chain][5 N], outside the arena, allocated by the first enable
+    bool eq_on = false;
+    double* eqacc = nullptr;
+    cplx* eq_ob = nullptr;
+    size_t eqacc_n = 0;                                       // doubles per chain, 0 before the first enable
     SvdWork sw{};
     double hub_e_m2a = 1.0, hub_e_p2a = 1.0;  // Hubbard: exp(-+2 alpha) of weightRatioSingleFlip (dethubbard.cpp:866-867)
     int stab = 0;                       // DQMC_STAB_SVD / DQMC_STAB_QR
@@ -1694,6 +1699,7 @@ extern "C" int dqmc_measure_reset(dqmc_ctx* c) {
     for (int ch = 0; ch < 4; ++ch)
         if (c->facc_n[ch])
             for (int b = 0; b < c->nb; ++b) HIPCHK(hipMemsetAsync(chainp(c, c->facc[ch], b), 0, c->facc_n[ch] * sizeof(double), c->st));
+    if (c->eqacc_n) HIPCHK(hipMemsetAsync(c->eqacc, 0, c->eqacc_n * (size_t)c->nb * sizeof(double), c->st));
     return DQMC_OK;
 }
 extern "C" int dqmc_measure_slice(dqmc_ctx* c) {
@@ -1706,6 +1712,7 @@ extern "C" int dqmc_measure_slice(dqmc_ctx* c) {
     }
     shift_green_dev(c);
     { ProfScope ps(c, FAM_OTHER, 1); launch_measure_accum(c->lc, c->hm, c->T1, c->macc); }
+    if (c->eq_on) { ProfScope ps(c, FAM_OTHER, 2); launch_measure_eq_corr(c->lc, c->hm, c->T1, c->eq_ob, c->eqacc); }   // same T1, no second shift
     return finish(c, "dqmc_measure_slice");
 }
 extern "C" size_t dqmc_measure_accum_size(dqmc_ctx* c) { return c ? c->macc_n : 0; }
@@ -1714,6 +1721,31 @@ extern "C" int dqmc_measure_read_host(dqmc_ctx* c, double* out) {
     (void)hipSetDevice(c->p.device);
     HIPCHK(hipStreamSynchronize(c->st));
     HIPCHK(copy_sync(c, out, selp(c, c->macc), c->macc_n * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+// equal-time charge / spin / SDW / pairing correlators (dqmc_hip.h): a switch of dqmc_measure_slice with a block of its own
+extern "C" int dqmc_set_equal_time_correlators(dqmc_ctx* c, int on) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (c->hm.hubbard) return fail(DQMC_EINVAL, "the equal-time correlators belong to the SDW model");
+    if (on && !c->eqacc_n) {
+        (void)hipSetDevice(c->p.device);
+        const size_t n = measure_eq_doubles(c->N);
+        if (const int rc = salloc(c, &c->eqacc, n * (size_t)c->nb)) return rc;
+        if (const int rc = salloc(c, &c->eq_ob, measure_eq_onebody_cplx(c->N) * (size_t)c->nb)) return rc;
+        HIPCHK(hipMemsetAsync(c->eqacc, 0, n * (size_t)c->nb * sizeof(double), c->st));
+        HIPCHK(hipMemsetAsync(c->eq_ob, 0, measure_eq_onebody_cplx(c->N) * (size_t)c->nb * sizeof(cplx), c->st));
+        c->eqacc_n = n;
+    }
+    c->eq_on = on != 0;
+    return DQMC_OK;
+}
+extern "C" size_t dqmc_measure_eq_accum_size(dqmc_ctx* c) { return c ? c->eqacc_n : 0; }
+extern "C" int dqmc_measure_eq_read_host(dqmc_ctx* c, double* out) {
+    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
+    if (!c->eqacc_n) return fail(DQMC_EINVAL, "the equal-time correlators have never been enabled (dqmc_set_equal_time_correlators)");
+    (void)hipSetDevice(c->p.device);
+    HIPCHK(hipStreamSynchronize(c->st));
+    HIPCHK(copy_sync(c, out, c->eqacc + (size_t)c->sel * c->eqacc_n, c->eqacc_n * sizeof(double), hipMemcpyDeviceToHost));
     return DQMC_OK;
 }
 

@@ -272,6 +272,12 @@ void launch_td_ph_onebody(const Launch& lc, const DevModel& hm, const cplx* gs, 
 void launch_measure_td_ph(const Launch& lc, const DevModel& hm, const cplx* gs, const cplx* hs, const cplx* ob, double* acc, int row, int rows);
 size_t measure_td_ph_doubles(int N, int n);
 size_t measure_td_ph_onebody_cplx(int N);
+// equal-time two-particle block (dqmc_set_equal_time_correlators): count, then the sums over B of Re W(B (+) d, B) for charge [N], spinZ [N],
+// sdw [N] and of Re T+-(B (+) d, B) for pairPlus [N], pairMinus [N], all from the one shifted matrix gs.  acc and the one-body scratch ob
+// are plain device arrays outside the arena: chain b at acc + b * measure_eq_doubles(N) and ob + b * measure_eq_onebody_cplx(N)
+void launch_measure_eq_corr(const Launch& lc, const DevModel& hm, const cplx* gs, cplx* ob, double* acc);
+size_t measure_eq_doubles(int N);
+size_t measure_eq_onebody_cplx(int N);
 // time-displaced current-current block: count[n-1], then per boundary j = 1 .. n-1 the sums over B of Re W[j_mu(B (+) d), j_mu(B)] for mu = x [N]
 // and mu = y [N], then sum_A Re o_tau[k_x(A)] and sum_A Re o_tau[k_y(A)].  bt = bond amplitudes [2][MSF][N] (shared by all chains),
 // ob = the one-body values [2][4][N] (j_x, j_y, k_x, k_y) that launch_td_current_onebody wrote; gs, hs as for launch_measure_td_ph

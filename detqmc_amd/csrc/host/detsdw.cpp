@@ -23,6 +23,8 @@ void DetSDW::check(int rc, const char* what) {
 static int td_level(const detsdw_params& p) { return p.timeDisplacedMeasurements & ~(DETSDW_TD_EVERY_SLICE | DETSDW_TD_FINE_ON_DEVICE); }
 static bool td_every_slice(const detsdw_params& p) { return (p.timeDisplacedMeasurements & DETSDW_TD_EVERY_SLICE) != 0; }
 static bool td_fine_on_device(const detsdw_params& p) { return (p.timeDisplacedMeasurements & DETSDW_TD_FINE_ON_DEVICE) != 0; }
+// fermionMeasurements carries the switch in bit 0 and DETSDW_FM_EQ_CORRELATORS as a flag bit
+static bool eq_correlators(const detsdw_params& p) { return (p.fermionMeasurements & DETSDW_FM_EQ_CORRELATORS) != 0; }
 
 // field-wise comparison of two normalised parameter sets (struct padding is not the caller's business); everything but
 // the exchange parameter r, the device and -- unless seeds_too -- the RNG stream identity
@@ -115,6 +117,10 @@ void DetSDW::normalise(detsdw_params& p, int& bcv) {
         throw ParameterWrong("timeDisplacedEverySlice needs timeDisplacedMeasurements");
     if (td_fine_on_device(p) && !td_every_slice(p))
         throw ParameterWrong("timeDisplacedFineOnDevice needs timeDisplacedEverySlice");
+    if (p.fermionMeasurements & ~(1 | DETSDW_FM_EQ_CORRELATORS))
+        throw ParameterWrong("Parameter fermionMeasurements has incorrect value");
+    if (eq_correlators(p) && !(p.fermionMeasurements & 1))
+        throw ParameterWrong("equalTimeCorrelators needs fermionMeasurements");
     if (p.timeDisplacedMeasurements && !p.fermionMeasurements)
         throw ParameterWrong("timeDisplacedMeasurements needs fermionMeasurements");
     if (p.timeDisplacedParticleHole < 0 || p.timeDisplacedParticleHole > 2)
@@ -333,7 +339,11 @@ void DetSDW::sweep(bool takeMeasurements) {
     // the time-displaced pair is computed only during measurement sweeps: thermalisation sweeps pay nothing for it
     measuringTD_ = fermionic && ch_[0].pars.timeDisplacedMeasurements;
     if (measuringTD_) for (auto& g : groups_) check(dqmc_set_timedisplaced(g.ctx, 1), "dqmc_set_timedisplaced");
-    auto off = [this]() {
+    // the equal-time correlators ride on the measure(k) calls of measurement sweeps only: thermalisation sweeps launch nothing new
+    const bool eq = fermionic && eq_correlators(ch_[0].pars);
+    if (eq) for (auto& g : groups_) check(dqmc_set_equal_time_correlators(g.ctx, 1), "dqmc_set_equal_time_correlators");
+    auto off = [this, eq]() {
+        if (eq) for (auto& g : groups_) (void)dqmc_set_equal_time_correlators(g.ctx, 0);
         measuring_ = false;
         if (measuringTD_) for (auto& g : groups_) (void)dqmc_set_timedisplaced(g.ctx, 0);
         measuringTD_ = false;
@@ -409,6 +419,34 @@ void DetSDW::finishFermionic(int b) {
         }
     o.pairPlusMax = pp / 9.0;
     o.pairMinusMax = pm / 9.0;
+    // equal-time correlators: C(d) = sum / (count N), and S(q) = sum_d cos(q d) C(d), the real part of the Fourier sum
+    if (eq_correlators(c.pars)) {
+        std::vector<double> eq(dqmc_measure_eq_accum_size(ctx_));
+        check(dqmc_measure_eq_read_host(ctx_, eq.data()), "dqmc_measure_eq_read_host");
+        if ((int)eq[0] != m) throw GeneralError(DQMC_EINVAL, "measurement sweep did not visit every time slice (equal-time correlators)");
+        // separable: cos(qx dx + qy dy) = cos cos - sin sin, phases 2 pi (q d mod L) / L from two tables -- O(N L) per channel
+        std::vector<double> ct(L), st(L), Ac((size_t)N), As((size_t)N);
+        for (int j = 0; j < L; ++j) { ct[j] = std::cos(2.0 * pi * double(j) / double(L)); st[j] = std::sin(2.0 * pi * double(j) / double(L)); }
+        for (int ch = 0; ch < 5; ++ch) {
+            c.eqCorr[ch].assign(N, 0.0); c.eqSq[ch].assign(N, 0.0);
+            for (int d = 0; d < N; ++d) c.eqCorr[ch][d] = eq[1 + (size_t)ch * N + d] / (double(N) * eq[0]);
+            for (int dy = 0; dy < L; ++dy)
+                for (int qx = 0; qx < L; ++qx) {
+                    double sc = 0.0, ss = 0.0;
+                    for (int dx = 0; dx < L; ++dx) {
+                        const double v = c.eqCorr[ch][dy * L + dx];
+                        sc += ct[(qx * dx) % L] * v; ss += st[(qx * dx) % L] * v;
+                    }
+                    Ac[(size_t)dy * L + qx] = sc; As[(size_t)dy * L + qx] = ss;
+                }
+            for (int qy = 0; qy < L; ++qy)
+                for (int qx = 0; qx < L; ++qx) {
+                    double sq = 0.0;
+                    for (int dy = 0; dy < L; ++dy) sq += ct[(qy * dy) % L] * Ac[(size_t)dy * L + qx] - st[(qy * dy) % L] * As[(size_t)dy * L + qx];
+                    c.eqSq[ch][(size_t)qy * L + qx] = sq;
+                }
+        }
+    }
     // Time-displaced observables from one family of blocks: the coarse one (rows = interior boundaries j = 1 .. n-1) or, with
     // timeDisplacedEverySlice, also the fine one (rows = slices k = 0 .. m).  Same arithmetic for both.
     auto fill = [&](bool fine, TdObs& t) {
@@ -555,6 +593,13 @@ void DetSDW::getObservableVector(int which_in, double* out, int b) const {
     if (fine && td_fine_on_device(c.pars))
         throw ParameterWrong("the ...Fine observables are not formed with timeDisplacedFineOnDevice: read the Matsubara transforms");
     const TdObs& t = fine ? c.tdFine : c.td;
+    if (!fine && which >= DETSDW_OBS_CHARGECORR && which <= DETSDW_OBS_PAIRMINUSSQ) {
+        if (!eq_correlators(c.pars))
+            throw ParameterWrong("the equal-time correlators and structure factors need equalTimeCorrelators (DETSDW_FM_EQ_CORRELATORS)");
+        const std::vector<double>& e = which < DETSDW_OBS_CHARGESQ ? c.eqCorr[which - DETSDW_OBS_CHARGECORR] : c.eqSq[which - DETSDW_OBS_CHARGESQ];
+        std::memcpy(out, e.data(), e.size() * sizeof(double));
+        return;
+    }
     const std::vector<double>* v = which == DETSDW_OBS_KOCCX ? &c.kOccX : which == DETSDW_OBS_KOCCY ? &c.kOccY
                                  : which == DETSDW_OBS_PAIRPLUS ? &c.pairPlus : which == DETSDW_OBS_PAIRMINUS ? &c.pairMinus
                                  : which == DETSDW_OBS_GREENKTAU_X ? &t.greenKTauX : which == DETSDW_OBS_GREENKTAU_Y ? &t.greenKTauY

@@ -97,6 +97,7 @@ private:
         double angleDelta = 0.0, scaleDelta = 0.1;          // AdjustmentData::InitialAngleDelta / InitialScaleDelta (detsdwopdim.h:490-491)
         detsdw_observables obs{};
         std::vector<double> kOccX, kOccY, pairPlus, pairMinus;
+        std::vector<double> eqCorr[5], eqSq[5];    // charge, spinZ, sdw, pairPlus, pairMinus: C(d) and S(q), N each (DETSDW_FM_EQ_CORRELATORS)
         TdObs td, tdFine;                      // rows = interior boundaries j = 1 .. n-1 / time slices k = 0 .. m (timeDisplacedEverySlice)
         Chain(const detsdw_params& p) : pars(p), rng(p.rngSeed, (uint32_t)p.simindex + 1u) {}   // detqmc.h:181
     };

@@ -430,6 +430,167 @@ void launch_measure_td_ph(const Launch& lc, const DevModel& hm, const cplx* gs, 
     else hipLaunchKernelGGL((k_measure_td_ph<3>), grid, block, 0, lc.st, hm, gs, hs, ob, acc, row, rows, lc.cs);
 }
 
+// Equal-time two-particle block (dqmc_set_equal_time_correlators; definitions in dqmc_hip.h and DESIGN.md 6e).  The Wick forms of
+// k_measure_td_ph and k_measure_td_pair with ONE matrix gs = e^{-dtau K/2} G(tau_k) e^{+dtau K/2} in both roles: G(tau, 0) -> gs and
+// G(0, tau) -> gs - 1, so
+//   W^M(A, B) = o^M(A) o^M(B) - sum_abcd M_ab M_cd gs(B d; A a) gs(A b; B c) + delta_AB sum_bc (M^2)_cb gs(A b; A c).
+// gs - 1 is never formed: M^2 = 1 for charge and every SDW component and 1/4 for spinZ, so the delta term is tr_4 gs(B; B) = 4 - o^charge(B)
+// (times 1/4 for spinZ), added to the d = 0 bin from the one-body value already in hand.  The pairing sums T+-(A, B) contain gs(A .; B .)
+// only and have no delta term.
+// The transposed factor gs(B d; A a) is read directly: t_ac = gs[(A + N a) ng + B + N c] takes the place of conj hs(A a; B c) in
+// k_measure_td_ph, Re e conj h -> Re e t.  With the 32 bins x 8 parts shape one step of a workgroup reads (row B, column B (+) d + N a) for
+// eight consecutive rows B and 32 consecutive bins d: a band of about 39 columns x 8 rows, one aligned 128-byte line per column, whose
+// eight elements are used in that step by the lanes (part p, bin d0 - p) -- fewer only at the band's edges and at the wraps of x.  The
+// forward factor keeps the pattern of the time-displaced kernels (lanes over consecutive rows A of one column).  No transposed copy, no
+// n_g^2 buffer.
+// One-body values: k_eq_onebody writes ob[5][N] (the t = 0 half of k_td_ph_onebody's layout) from the same matrix, 5 N complex numbers.
+// OPDIM < 3: the stored sector and its conjugate as in k_measure_td_ph and k_measure_td_pair -- eight loads per pair serve all five sums;
+// O(3): the sixteen e and sixteen t of the full 4 x 4 blocks.  Shape, walk order, reduction and reproducibility: those of k_measure_td_ph.
+// Block of one chain (doubles): count, charge[N], spinZ[N], sdw[N], pairPlus[N], pairMinus[N]; it lives outside the chain arena, chain b
+// at acc + b (1 + 5 N).
+size_t measure_eq_doubles(int N) { return 1 + 5 * (size_t)N; }
+size_t measure_eq_onebody_cplx(int N) { return (size_t)TDPH_CH * N; }
+
+template<int OPDIM>
+__global__ __launch_bounds__(256) void k_eq_onebody(DevModel dm, const cplx* __restrict__ gs, cplx* __restrict__ ob, size_t cs) {
+    CHAIN(gs);
+    const int N = dm.N, A = blockIdx.x * 256 + threadIdx.x;
+    if (A >= N) return;
+    const GreenAccess<OPDIM> g1{gs, dm.ng, N};
+    auto g = [&](int r, int c2) { return g1(A, r, A, c2); };       // g(b, a) = gs(A b; A a)
+    cplx* o = ob + (size_t)blockIdx.z * TDPH_CH * N + A;
+    const cplx tr = m_add(m_add(g(0, 0), g(1, 1)), m_add(g(2, 2), g(3, 3)));
+    o[0] = make_double2(4.0 - tr.x, -tr.y);
+    o[(size_t)N] = m_scale(-0.5, m_sub(m_add(g(0, 0), g(3, 3)), m_add(g(1, 1), g(2, 2))));
+    o[(size_t)2 * N] = m_scale(-1.0, m_add(m_add(g(1, 0), g(0, 1)), m_add(g(3, 2), g(2, 3))));
+    if (OPDIM >= 2) {       // tr M_y g = i (g01 - g10 + g32 - g23)
+        const cplx v = m_add(m_sub(g(0, 1), g(1, 0)), m_sub(g(3, 2), g(2, 3)));
+        o[(size_t)3 * N] = make_double2(v.y, -v.x);                // -i v
+    }
+    if (OPDIM == 3) o[(size_t)4 * N] = m_scale(-1.0, m_sub(m_add(g(3, 0), g(0, 3)), m_add(g(2, 1), g(1, 2))));
+}
+
+#define EQ_CH 5         // binned sums: charge, spinZ, sdw, pairPlus, pairMinus
+template<int OPDIM>
+__global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_eq_corr(DevModel dm, const cplx* __restrict__ gs, const cplx* __restrict__ ob,
+                                                                          double* __restrict__ acc, size_t cs) {
+    CHAIN(gs);
+    ob += (size_t)blockIdx.z * TDPH_CH * dm.N;
+    acc += (size_t)blockIdx.z * (1 + (size_t)EQ_CH * dm.N);
+    __shared__ double red[EQ_CH][TDP_PARTS][TDP_BINS];
+    const int N = dm.N, L = dm.L, tid = threadIdx.x;
+    const size_t ng = (size_t)dm.ng;
+    const int lb = tid % TDP_BINS, part = tid / TDP_BINS;
+    const int d = blockIdx.x * TDP_BINS + lb;
+    const bool valid = d < N;
+    const int dx = valid ? d % L : 0, dy = valid ? d / L : 0;
+    auto re_mul = [](cplx a, cplx b) { return a.x * b.x - a.y * b.y; };   // Re a b
+    auto abs2 = [](cplx v) { return v.x * v.x + v.y * v.y; };
+    double wc = 0.0, wz = 0.0, ws = 0.0, tp = 0.0, tm = 0.0;
+    if (valid) {
+        int bx = part % L, by = part / L;                   // site B = part + 8 i, kept as (bx, by)
+        const int stepx = TDP_PARTS % L, stepy = TDP_PARTS / L;
+        for (int B = part; B < N; B += TDP_PARTS) {
+            int ax = bx + dx, ay = by + dy;
+            if (ax >= L) ax -= L;
+            if (ay >= L) ay -= L;
+            const int A = ay * L + ax;
+            const cplx* pe = gs + (size_t)B * ng + (size_t)A;     // e_rc = gs(A + N r; B + N c) = pe[c N ng + r N]
+            const cplx* pt = gs + (size_t)A * ng + (size_t)B;     // t_rc = gs(B + N c; A + N r) = pt[r N ng + c N]
+            // disconnected parts
+            const cplx ocB = ob[B];
+            double dc = re_mul(ob[A], ocB), dz = re_mul(ob[N + A], ob[N + B]);
+            double ds = re_mul(ob[2 * N + A], ob[2 * N + B]);
+            if (OPDIM >= 2) ds += re_mul(ob[3 * N + A], ob[3 * N + B]);
+            if (OPDIM == 3) ds += re_mul(ob[4 * N + A], ob[4 * N + B]);
+            ds *= 1.0 / OPDIM;
+            if (d == 0) {                                   // the delta term: tr_4 gs(B; B) for M^2 = 1
+                const double tr = 4.0 - ocB.x;
+                dc += tr; dz += 0.25 * tr; ds += tr;
+            }
+            double cc, cz, cs2, pxx, pxy, pyx, pyy;
+            if (OPDIM == 3) {
+                cplx e[4][4];
+#pragma unroll
+                for (int c2 = 0; c2 < 4; ++c2)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) e[r][c2] = pe[(size_t)c2 * N * ng + (size_t)r * N];
+                // Re P(b1, b2) with (dn1, up1) = band-spin rows of band b1, (up2, dn2) = band-spin columns of band b2
+                auto P = [&](int dn1, int up1, int up2, int dn2) { return re_mul(e[dn1][up2], e[up1][dn2]) - re_mul(e[dn1][dn2], e[up1][up2]); };
+                pxx = P(2, 0, 0, 2); pxy = P(2, 0, 3, 1); pyx = P(1, 3, 0, 2); pyy = P(1, 3, 3, 1);
+                constexpr int pxyp[4] = {1, 0, 3, 2}, pz[4] = {3, 2, 1, 0};
+                constexpr double sz[4] = {1.0, -1.0, -1.0, 1.0};      // spinZ diagonal (x 2), the y of M_y and the m of M_z alike
+                cc = 0.0; cz = 0.0;
+                double cx = 0.0, cy = 0.0, cq = 0.0;
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    cplx t[4];                                        // t[dl] = gs(B dl; A a)
+#pragma unroll
+                    for (int dl = 0; dl < 4; ++dl) t[dl] = pt[(size_t)a * N * ng + (size_t)dl * N];
+#pragma unroll
+                    for (int c2 = 0; c2 < 4; ++c2) {
+                        const double v = re_mul(e[a][c2], t[c2]);
+                        cc += v;
+                        cz += sz[a] * sz[c2] * v;
+                        const double q = re_mul(e[pxyp[a]][c2], t[pxyp[c2]]);
+                        cx += q;
+                        cy += sz[a] * sz[c2] * q;                    // m_a m_c = -y_a y_c with y = -sz
+                        cq += sz[a] * sz[c2] * re_mul(e[pz[a]][c2], t[pz[c2]]);
+                    }
+                }
+                cz *= 0.25;
+                cs2 = (cx - cy) + cq;
+            } else {
+                const size_t cN = (size_t)N * ng;
+                const cplx e00 = pe[0], e10 = pe[N], e01 = pe[cN], e11 = pe[cN + N];
+                const cplx t00 = pt[0], t10 = pt[cN], t01 = pt[N], t11 = pt[cN + N];
+                const double d00 = re_mul(e00, t00), d11 = re_mul(e11, t11), d01 = re_mul(e01, t01), d10 = re_mul(e10, t10);
+                cc = 2.0 * ((d00 + d11) + (d01 + d10));
+                cz = 0.5 * ((d00 + d11) - (d01 + d10));
+                const double q01 = re_mul(e11, t00), q10 = re_mul(e00, t11);
+                if (OPDIM == 1) cs2 = 2.0 * ((re_mul(e10, t01) + re_mul(e01, t10)) + (q01 + q10));
+                else cs2 = 4.0 * (q01 + q10);                        // M_x + M_y: the q_00 and q_11 terms cancel
+                pxx = -abs2(e00); pxy = abs2(e01); pyx = abs2(e10); pyy = -abs2(e11);
+            }
+            wc += dc - cc;
+            wz += dz - cz;
+            ws += ds - cs2 * (1.0 / OPDIM);
+            tp += -4.0 * (((pxx + pxy) + pyx) + pyy);
+            tm += -4.0 * (((pxx - pxy) - pyx) + pyy);
+            bx += stepx; by += stepy;
+            if (bx >= L) { bx -= L; ++by; }
+        }
+    }
+    red[0][part][lb] = wc;
+    red[1][part][lb] = wz;
+    red[2][part][lb] = ws;
+    red[3][part][lb] = tp;
+    red[4][part][lb] = tm;
+    __syncthreads();
+    if (part < EQ_CH && valid) {                            // part c writes channel c of its bin
+        double s = red[part][0][lb];
+#pragma unroll
+        for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
+        acc[1 + (size_t)part * N + d] += s;
+    }
+    if (blockIdx.x == 0 && tid == 0) acc[0] += 1.0;
+}
+
+void launch_measure_eq_corr(const Launch& lc, const DevModel& hm, const cplx* gs, cplx* ob, double* acc) {
+    const dim3 g1((hm.N + 255) / 256, 1, lc.nb);
+    const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
+    if (hm.opdim == 1) {
+        hipLaunchKernelGGL((k_eq_onebody<1>), g1, dim3(256), 0, lc.st, hm, gs, ob, lc.cs);
+        hipLaunchKernelGGL((k_measure_eq_corr<1>), grid, block, 0, lc.st, hm, gs, ob, acc, lc.cs);
+    } else if (hm.opdim == 2) {
+        hipLaunchKernelGGL((k_eq_onebody<2>), g1, dim3(256), 0, lc.st, hm, gs, ob, lc.cs);
+        hipLaunchKernelGGL((k_measure_eq_corr<2>), grid, block, 0, lc.st, hm, gs, ob, acc, lc.cs);
+    } else {
+        hipLaunchKernelGGL((k_eq_onebody<3>), g1, dim3(256), 0, lc.st, hm, gs, ob, lc.cs);
+        hipLaunchKernelGGL((k_measure_eq_corr<3>), grid, block, 0, lc.st, hm, gs, ob, acc, lc.cs);
+    }
+}
+
 // Time-displaced current-current block (dqmc_measure_timedisplaced_current; definitions in dqmc_hip.h and DESIGN.md 6e).  A bond operator
 // at site i in direction mu (i' = i (+) mu) has two one-body entries per flavour, M[i' a, i a] = m_a(i), M[i a, i' a] = conj m_a(i), with
 // m = i T (current j_mu) or m = T (bond kinetic energy k_mu) and T_a(i) = K^a[i', i] from the bond table bt[mu][flavour][site].  With

@@ -54,6 +54,7 @@ class SDWParams:
     wolffClusterShiftUpdate: bool = False
     repeatWolffPerSweep: int = 1
     fermionMeasurements: bool = False    # sweep(True) also takes the G-dependent observables (reference default: on)
+    equalTimeCorrelators: bool = False   # ... and the equal-time charge / spinZ / SDW / pairing correlators C(d) and S(q), all m slices (needs fermionMeasurements)
     timeDisplacedMeasurements: bool = False   # ... and G(k, tau_j) at the interior stabilisation boundaries (needs fermionMeasurements)
     timeDisplacedPairing: bool = False        # ... and the pairing correlators P+-(r, tau_j) (needs timeDisplacedMeasurements)
     timeDisplacedParticleHole: bool = False   # ... and the charge / spin-z / SDW correlators C(r, tau_j) (needs timeDisplacedMeasurements)
@@ -83,6 +84,23 @@ class SDWParams:
 # observables with a Matsubara transform (DetSDW.matsubara): name -> index of detsdw_get_observable_vector
 MATSUBARA = {"greenKTauX": 4, "greenKTauY": 5, "pairPlusTau": 6, "pairMinusTau": 7, "chargeTau": 10, "spinZTau": 11, "sdwTau": 12,
              "currentXTau": 16, "currentYTau": 17}
+
+
+# equal-time correlators and structure factors (SDWParams.equalTimeCorrelators): name -> index of detsdw_get_observable_vector
+EQ_CORRELATORS = {"chargeCorr": 22, "spinZCorr": 23, "sdwCorr": 24, "pairPlusCorr": 25, "pairMinusCorr": 26,
+                  "chargeSq": 27, "spinZSq": 28, "sdwSq": 29, "pairPlusSq": 30, "pairMinusSq": 31}
+
+
+def structure_factor(c, L):
+    """S(q) = sum_d cos(q . d) C(d) of an equal-time correlator C over the periodic site differences (last axis, index dy L + dx):
+    last axis of the result = qy L + qx, q = 2 pi (qx, qy) / L.  The sum the '...Sq' observables are formed with, for averages of
+    '...Corr' a user keeps; leading axes are kept."""
+    c = np.asarray(c, dtype=np.float64)
+    L = int(L)
+    x = np.arange(L * L) % L
+    y = np.arange(L * L) // L
+    ph = 2.0 * np.pi / L * (np.outer(x, x) + np.outer(y, y))      # [q, d]
+    return c @ np.cos(ph).T
 
 
 def superfluid_stiffness(chi_xx, chi_yy, L):
@@ -175,6 +193,18 @@ class KernelContext:
         """the selected chain's accumulators: [greenK0, greenLocal, occDiffSq, count, pairPlus[N], pairMinus[N], S_X, S_Y]"""
         out = np.zeros(self.lib.dqmc_measure_accum_size(self.h))
         check(self.lib.dqmc_measure_read_host(self.h, out.ctypes.data_as(_lib._DP)))
+        return out
+
+    def set_equal_time_correlators(self, on=True):
+        """while on, every measure_slice also bins the equal-time charge / spinZ / sdw / pairPlus / pairMinus sums of the same shifted
+        matrix into a block of their own (SDW model only; the first enable allocates the block)"""
+        check(self.lib.dqmc_set_equal_time_correlators(self.h, int(on)))
+
+    def measure_eq_read(self):
+        """the selected chain's equal-time block: [count, charge[N], spinZ[N], sdw[N], pairPlus[N], pairMinus[N]], raw sums over B of
+        Re W(B (+) d, B), index dy L + dx; C(d) = sum / (count N)"""
+        out = np.zeros(self.lib.dqmc_measure_eq_accum_size(self.h))
+        check(self.lib.dqmc_measure_eq_read_host(self.h, out.ctypes.data_as(_lib._DP)))
         return out
 
     def measure_timedisplaced(self, j):
@@ -464,6 +494,8 @@ def _host_params(pars: SDWParams):
         raise ValueError("timeDisplacedPairing needs timeDisplacedMeasurements")
     if pars.timeDisplacedParticleHole and not pars.timeDisplacedMeasurements:
         raise ValueError("timeDisplacedParticleHole needs timeDisplacedMeasurements")
+    if pars.equalTimeCorrelators and not pars.fermionMeasurements:
+        raise ValueError("equalTimeCorrelators needs fermionMeasurements")
     if pars.timeDisplacedCurrent and not pars.timeDisplacedParticleHole:
         raise ValueError("timeDisplacedCurrent needs timeDisplacedParticleHole")
     return _lib.detsdw_params(
@@ -478,7 +510,7 @@ def _host_params(pars: SDWParams):
         mu=pars.mu, mux=pars.mux or 0.0, muy=pars.muy or 0.0, accRatio=pars.accRatio, cdwU=pars.cdwU,
         stabilisation=STABILISATION[pars.stabilisation], cb_none=int(not pars.checkerboard),
         wolffClusterUpdate=int(pars.wolffClusterUpdate), wolffClusterShiftUpdate=int(pars.wolffClusterShiftUpdate),
-        repeatWolffPerSweep=int(pars.repeatWolffPerSweep), fermionMeasurements=int(pars.fermionMeasurements),
+        repeatWolffPerSweep=int(pars.repeatWolffPerSweep), fermionMeasurements=int(bool(pars.fermionMeasurements)) | (_lib.DETSDW_FM_EQ_CORRELATORS if pars.equalTimeCorrelators else 0),
         spinProposalMethod=SPIN_PROPOSAL[pars.spinProposalMethod], adaptScaleVariance=int(pars.adaptScaleVariance),
         repeatUpdateInSlice=int(pars.repeatUpdateInSlice), timeDisplacedMeasurements=(2 if pars.timeDisplacedPairing else int(bool(pars.timeDisplacedMeasurements)))
         | (_lib.DETSDW_TD_EVERY_SLICE if pars.timeDisplacedEverySlice else 0)      # without timeDisplacedMeasurements: ParameterWrong from the library
@@ -560,9 +592,16 @@ class DetSDW:
         'currentYTau' with timeDisplacedCurrent: shape (n-1, N), same rows and columns; 'currentXTauQ0', 'currentYTauQ0': their sums over
         the site difference; 'bondKineticX', 'bondKineticY': the bond kinetic energy per site at tau_j, length n-1.  With
         timeDisplacedEverySlice every name from 'greenKTauX' on has a twin name + 'Fine' (e.g. 'chargeTauFine', 'pairPlusTauQ0Fine',
-        'bondKineticXFine') with m+1 rows instead of n-1: row k = tau_k of tau_grid(fine=True), k = 0 .. m"""
+        'bondKineticXFine') with m+1 rows instead of n-1: row k = tau_k of tau_grid(fine=True), k = 0 .. m.  With equalTimeCorrelators:
+        'chargeCorr', 'spinZCorr', 'sdwCorr', 'pairPlusCorr', 'pairMinusCorr' (length N, column = periodic site difference dy L + dx,
+        averaged over the m slices of the sweep and over translations) and their structure factors 'chargeSq', 'spinZSq', 'sdwSq',
+        'pairPlusSq', 'pairMinusSq' (length N, column qy L + qx, q = 2 pi (qx, qy) / L; structure_factor of the former)"""
         self._sel()
         info = self.info
+        if name in EQ_CORRELATORS:
+            out = np.zeros(info.N)
+            check(self.lib.detsdw_get_observable_vector(self.h, EQ_CORRELATORS[name], out.ctypes.data_as(_lib._DP)), host=True)
+            return out
         fine = name.endswith("Fine")
         if fine:
             name = name[:-4]

@@ -55,7 +55,11 @@ typedef struct detsdw_params {
     int32_t wolffClusterShiftUpdate;  /* combined cluster + global shift (:3647-3751); excludes the two individual moves */
     int32_t repeatWolffPerSweep;      /* cluster flips per attempt, 0 is read as 1 */
     int32_t fermionMeasurements;      /* 1: sweep(takeMeasurements) also takes the G-dependent observables (the reference's
-                                         default, i.e. turnoffFermionMeasurements = false); 0: bosonic observables only */
+                                         default, i.e. turnoffFermionMeasurements = false); 0: bosonic observables only.
+                                         | DETSDW_FM_EQ_CORRELATORS (equalTimeCorrelators; needs bit 0, ParameterWrong otherwise): a
+                                         measurement sweep also bins the equal-time charge, spin-z, SDW and pairing correlators on
+                                         every one of its m slices (DETSDW_OBS_CHARGECORR .. _PAIRMINUSSQ).  The struct has no free
+                                         slot, so the option travels as a flag bit.  Any other bit: ParameterWrong */
     int32_t spinProposalMethod;       /* 0 box (default), 1 rotate_then_scale, 2 rotate_and_scale -- the latter two for opdim == 3 only
                                          (src/detsdwparams.h:40-42, src/detsdwopdim.cpp:2447-2470) */
     int32_t adaptScaleVariance;       /* adapt scaleDelta during thermalization (src/detsdwparams.h:43) */
@@ -128,7 +132,11 @@ enum { DETSDW_OBS_KOCCX = 0, DETSDW_OBS_KOCCY = 1, DETSDW_OBS_PAIRPLUS = 2, DETS
        DETSDW_OBS_CHARGETAU = 10, DETSDW_OBS_SPINZTAU = 11, DETSDW_OBS_SDWTAU = 12,
        DETSDW_OBS_CHARGETAU_Q0 = 13, DETSDW_OBS_SPINZTAU_Q0 = 14, DETSDW_OBS_SDWTAU_Q0 = 15,
        DETSDW_OBS_CURRENTXTAU = 16, DETSDW_OBS_CURRENTYTAU = 17, DETSDW_OBS_CURRENTXTAU_Q0 = 18, DETSDW_OBS_CURRENTYTAU_Q0 = 19,
-       DETSDW_OBS_BONDKINETICX = 20, DETSDW_OBS_BONDKINETICY = 21 };
+       DETSDW_OBS_BONDKINETICX = 20, DETSDW_OBS_BONDKINETICY = 21,
+       DETSDW_OBS_CHARGECORR = 22, DETSDW_OBS_SPINZCORR = 23, DETSDW_OBS_SDWCORR = 24, DETSDW_OBS_PAIRPLUSCORR = 25, DETSDW_OBS_PAIRMINUSCORR = 26,
+       DETSDW_OBS_CHARGESQ = 27, DETSDW_OBS_SPINZSQ = 28, DETSDW_OBS_SDWSQ = 29, DETSDW_OBS_PAIRPLUSSQ = 30, DETSDW_OBS_PAIRMINUSSQ = 31 };
+/* equalTimeCorrelators: flag bit of detsdw_params::fermionMeasurements */
+enum { DETSDW_FM_EQ_CORRELATORS = 0x100 };
 /* timeDisplacedEverySlice: flag bit of detsdw_params::timeDisplacedMeasurements */
 enum { DETSDW_TD_EVERY_SLICE = 0x100 };
 /* timeDisplacedFineOnDevice: flag bit of detsdw_params::timeDisplacedMeasurements; never reaches dqmc_params::timedisplaced */
@@ -177,7 +185,13 @@ int detsdw_get_observables(detsdw_replica* r, detsdw_observables* out);
  * With timeDisplacedParticleHole == 2: currentXTau / currentYTau, (n-1) x N, same rows and columns:
  *   Lambda_mumu(d, tau_j) = (1/N) sum_B Re W[j_mu(B (+) d), j_mu(B)],  j_mu the bond current of dqmc_measure_timedisplaced_current;
  * currentXTauQ0 / currentYTauQ0, n-1: their sums over d; bondKineticX / bondKineticY, n-1: (1/N) sum_A Re <k_mu(A)> at tau_j, the
- * diamagnetic term.  The tau quadrature and the Fourier sum over d of the every-slice twins: detsdw_get_matsubara below */
+ * diamagnetic term.  The tau quadrature and the Fourier sum over d of the every-slice twins: detsdw_get_matsubara below
+ * With DETSDW_FM_EQ_CORRELATORS (ParameterWrong without it; no DETSDW_OBS_FINE twins): chargeCorr / spinZCorr / sdwCorr / pairPlusCorr /
+ * pairMinusCorr, N, column = periodic site difference dy L + dx:
+ *   C_X(d) = (1 / (m N)) sum_{slices k = 1 .. m} sum_B Re W_X(B (+) d, B)   on g~ = e^{-dtau K/2} G(tau_k) e^{+dtau K/2} after the updates
+ * of slice k (dqmc_set_equal_time_correlators, dqmc_hip.h: the Wick forms of the time-displaced channels with G(tau,0) -> g~,
+ * G(0,tau) -> g~ - 1, and T+- on g~); chargeSq / spinZSq / sdwSq / pairPlusSq / pairMinusSq, N, column qy L + qx, q = 2 pi (qx, qy) / L:
+ *   S_X(q) = sum_d cos(q d) C_X(d).   Values of ONE sweep: averages and error bars over sweeps stay with the caller */
 int detsdw_get_observable_vector(detsdw_replica* r, int which, double* out);
 /* With timeDisplacedEverySlice: the Matsubara transforms of the every-slice observable `which`, formed on the device from the blocks
  * of the last measurement sweep (dqmc_measure_td_matsubara_host, dqmc_hip.h), n = 0 .. nfreq-1, 1 <= nfreq <= m, trapezoid weights

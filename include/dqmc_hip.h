@@ -279,6 +279,20 @@ int dqmc_measure_reset(dqmc_ctx* ctx);
 int dqmc_measure_slice(dqmc_ctx* ctx);
 size_t dqmc_measure_accum_size(dqmc_ctx* ctx);
 int dqmc_measure_read_host(dqmc_ctx* ctx, double* out);
+/* ---- equal-time charge, spin, SDW and pairing correlators (SDW model only) ----------
+ * A switch of dqmc_measure_slice, not a create-time parameter.  While on, every dqmc_measure_slice also bins, from the same shifted
+ * matrix g~ = e^{-dtau K/2} G(tau_k) e^{+dtau K/2} (no second shift), for every periodic site difference d = (dx, dy), bin dy L + dx,
+ *   sum_B Re W_X(B (+) d, B),  X = charge, spinZ, sdw:  the W^M(A, B) of dqmc_measure_timedisplaced_ph with G(tau,0) -> g~ and
+ *                              G(0,tau) -> g~ - 1 (both one-body factors from g~; the delta term enters the d = 0 bin analytically),
+ *   sum_B Re T+-(B (+) d, B):  the T+- of dqmc_measure_timedisplaced_pair evaluated on g~,
+ * and counts one sample.  All chains in one launch; one writer per accumulator, fixed summation order, bit-reproducible.
+ * Block of one chain (doubles, dqmc_measure_eq_accum_size of them): count, charge[N], spinZ[N], sdw[N], pairPlus[N], pairMinus[N] --
+ * raw sums, C_X(d) = sum / (count N).  The first enable allocates the block for all chains outside the per-chain arena (no existing
+ * buffer moves); it is freed with the context and cleared by dqmc_measure_reset.  While off, dqmc_measure_slice launches what it always
+ * did; the block of dqmc_measure_read_host is the same either way.  The Hubbard model returns DQMC_EINVAL. */
+int dqmc_set_equal_time_correlators(dqmc_ctx* ctx, int on);
+size_t dqmc_measure_eq_accum_size(dqmc_ctx* ctx);       /* 0 before the first enable, else 1 + 5 N */
+int dqmc_measure_eq_read_host(dqmc_ctx* ctx, double* out);   /* selected chain; DQMC_EINVAL before the first enable */
 /* ---- time-displaced Green's functions ----------------------------------------------------------
  * At an interior stabilisation boundary tau_j = j s (j = 1 .. n-1) the advance holds B(tau,0) = U_r D_r V_r^H and
  * B(beta,tau) = U_l D_l V_l^H at once.  With the scales split into their parts > 1 and <= 1 and
