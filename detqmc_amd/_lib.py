@@ -22,6 +22,7 @@ DQMC_TD_EVERY_SLICE = 0x100     # flag bit of dqmc_params.timedisplaced
 DETSDW_TD_EVERY_SLICE = 0x100   # flag bit of detsdw_params.timeDisplacedMeasurements
 DETSDW_TD_FINE_ON_DEVICE = 0x200  # flag bit of detsdw_params.timeDisplacedMeasurements: the fine blocks stay on the device
 DETSDW_OBS_FINE = 0x100         # flag bit of the observable index: the every-slice twin
+DETSDW_SERIES_NO_HOST_COPY = 1    # flag of detsdw_series_begin: no equal-time block copy per measurement sweep while the series is open
 DETSDW_FM_EQ_CORRELATORS = 0x100  # flag bit of detsdw_params.fermionMeasurements: equal-time charge / spin / SDW / pairing correlators
 
 
@@ -220,6 +221,14 @@ SYMBOLS = [
     ("dqmc_measure_td_fine_read_host", C.c_int, [_P, C.c_int, _DP]),
     ("dqmc_measure_td_matsubara_size", C.c_size_t, [_P, C.c_int, C.c_int]),
     ("dqmc_measure_td_matsubara_host", C.c_int, [_P, C.c_int, C.c_int, _DP]),
+    ("dqmc_series_begin", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("dqmc_series_layout", C.c_int, [_P, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    ("dqmc_series_add_sweep", C.c_int, [_P]),
+    ("dqmc_series_info", C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    ("dqmc_series_read_bins_host", C.c_int, [_P, C.c_int, C.c_int, _DP]),
+    ("dqmc_series_stats_host", C.c_int, [_P, _DP, _DP]),
+    ("dqmc_series_derived_host", C.c_int, [_P, _DP, _DP]),
+    ("dqmc_series_end", C.c_int, [_P]),
     ("dqmc_get_green_td_fine_host", C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_int)]),
     ("dqmc_td_fine_propagate", C.c_int, [_P, C.c_int, C.c_int]),     # tests only: exported, not declared in include/dqmc_hip.h
     ("dqmc_profile_enable", C.c_int, [_P, C.c_int]),
@@ -240,6 +249,13 @@ SYMBOLS = [
     ("detsdw_get_observable_vector", C.c_int, [_P, C.c_int, _DP]),
     ("detsdw_get_matsubara", C.c_int, [_P, C.c_int, C.c_int, _DP]),
     ("detsdw_get_matsubara_all", C.c_int, [_P, C.c_int, C.c_int, _DP]),
+    ("detsdw_series_begin", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("detsdw_series_info", C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    ("detsdw_series_stats", C.c_int, [_P, C.c_int, _DP, _DP]),
+    ("detsdw_series_stats_all", C.c_int, [_P, C.c_int, _DP, _DP]),
+    ("detsdw_series_derived_all", C.c_int, [_P, C.c_int, _DP, _DP]),
+    ("detsdw_series_read_bins", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _DP]),
+    ("detsdw_series_end", C.c_int, [_P]),
     ("detsdw_get_tau_grid", C.c_int, [_P, _DP]),
     ("detsdw_get_tau_grid_fine", C.c_int, [_P, _DP]),
     ("detsdw_get_phi", C.c_int, [_P, _DP]),

@@ -102,6 +102,15 @@ struct dqmc_ctx {
     double* eqacc = nullptr;
     cplx* eq_ob = nullptr;
     size_t eqacc_n = 0;                                       // doubles per chain, 0 before the first enable
+    // dqmc_series_*: the measurement series.  Device buffers outside the arena, allocated by dqmc_series_begin and freed by dqmc_series_end
+    // or with the context: sample [nb][S], open bin [nb][S], closed bins [max_bins][nb][S], the per-part flags [5][nb], the cos / sin table
+    // and the result buffer of the statistics calls (mean, err [nb][S] each, then value, err [nb][6] each).  The counters live on the host.
+    struct Series {
+        bool open = false;
+        int bin_size = 0, max_bins = 0, nfreq = 0, parts = 0, closed = 0, in_open = 0;
+        size_t S = 0, off[5] = {0, 0, 0, 0, 0}, len[5] = {0, 0, 0, 0, 0};
+        double *sample = nullptr, *openbin = nullptr, *bins = nullptr, *bad = nullptr, *trig = nullptr, *stat = nullptr;
+    } ser;
     SvdWork sw{};
     double hub_e_m2a = 1.0, hub_e_p2a = 1.0;  // Hubbard: exp(-+2 alpha) of weightRatioSingleFlip (dethubbard.cpp:866-867)
     int stab = 0;                       // DQMC_STAB_SVD / DQMC_STAB_QR
@@ -824,12 +833,19 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
     return DQMC_OK;
 }
 
+static void series_free(dqmc_ctx* c) {
+    dqmc_ctx::Series& s = c->ser;
+    for (double* q : {s.sample, s.openbin, s.bins, s.bad, s.trig, s.stat}) if (q) (void)hipFree(q);
+    s = dqmc_ctx::Series{};
+}
+
 extern "C" void dqmc_destroy(dqmc_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->p.device);
     if (c->st) (void)hipStreamSynchronize(c->st);
     for (void* q : c->allocs) (void)hipFree(q);
     if (c->mats_out) (void)hipFree(c->mats_out);
+    series_free(c);
     if (c->jacobi_graph) (void)hipGraphExecDestroy(c->jacobi_graph);
     if (c->sw.hflag) (void)hipHostFree(c->sw.hflag);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
@@ -2030,6 +2046,160 @@ extern "C" int dqmc_measure_td_matsubara_host(dqmc_ctx* c, int channel, int nfre
     HIPCHK(copy_sync(c, out, c->mats_out, n_out * sizeof(double), hipMemcpyDeviceToHost));
     return DQMC_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// measurement series (dqmc_hip.h; kernels in kernels_measure.hip)
+// ---------------------------------------------------------------------------------------------
+static bool ser_apbx(const dqmc_ctx* c) { return c->p.bc == DQMC_BC_APBC_X || c->p.bc == DQMC_BC_APBC_XY; }
+static bool ser_apby(const dqmc_ctx* c) { return c->p.bc == DQMC_BC_APBC_Y || c->p.bc == DQMC_BC_APBC_XY; }
+extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nfreq, int parts) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (c->hm.hubbard) return fail(DQMC_EINVAL, "the measurement series belongs to the SDW model");
+    if (c->ser.open) return fail(DQMC_EINVAL, "a measurement series is already open (dqmc_series_end)");
+    if (parts <= 0 || (parts & ~0x1f)) return fail(DQMC_EINVAL, "dqmc_series_begin: parts must be a non-empty mask of bits 0 .. 4");
+    if (bin_size < 1) return fail(DQMC_EINVAL, "dqmc_series_begin: bin_size must be at least 1");
+    if (max_bins < 2) return fail(DQMC_EINVAL, "dqmc_series_begin: max_bins must be at least 2");
+    if ((parts & 1) && !c->eqacc_n) return fail(DQMC_EINVAL, "dqmc_series_begin: the equal-time block has never been enabled (dqmc_set_equal_time_correlators)");
+    if ((parts & 1) && series_eq_sample_lds_bytes(c->hm.L) > 152 * 1024)
+        return fail(DQMC_EINVAL, "dqmc_series_begin: the lattice is too large for the equal-time sample kernel's LDS");
+    dqmc_ctx::Series s;
+    const size_t N = (size_t)c->N;
+    if (parts & 1) { s.off[0] = 0; s.len[0] = 10 * N; s.S = 10 * N; }
+    for (int ch = 0; ch < 4; ++ch) {
+        if (!(parts & (2 << ch))) continue;
+        if (!c->td_fine || !c->facc_n[ch]) return fail(DQMC_EINVAL, "dqmc_series_begin: no every-slice block for a channel of the mask");
+        if (nfreq < 1 || nfreq > c->m) return fail(DQMC_EINVAL, "dqmc_series_begin: nfreq must be in 1..m");
+        if (!td_matsubara_fits(c->hm, ch, nfreq)) return fail(DQMC_EINVAL, "dqmc_series_begin: the lattice is too large for the Matsubara kernel's LDS");
+        s.off[1 + ch] = s.S; s.len[1 + ch] = (size_t)(ch == 2 ? 3 : 2) * nfreq * N * 2; s.S += s.len[1 + ch];
+    }
+    s.bin_size = bin_size; s.max_bins = max_bins; s.nfreq = (parts & 0x1e) ? nfreq : 0; s.parts = parts;
+    (void)hipSetDevice(c->p.device);
+    const size_t n = (size_t)c->nb * s.S, L = (size_t)c->hm.L;
+    c->ser = s;                                             // from here on series_free releases what was allocated
+    dqmc_ctx::Series& r = c->ser;
+    hipError_t e = hipMalloc((void**)&r.sample, n * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&r.openbin, n * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&r.bins, (size_t)max_bins * n * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&r.bad, (size_t)5 * c->nb * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&r.trig, 2 * L * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&r.stat, (2 * n + (size_t)12 * c->nb) * sizeof(double));
+    if (e == hipSuccess) e = hipMemsetAsync(r.sample, 0, n * sizeof(double), c->st);
+    if (e == hipSuccess) e = hipMemsetAsync(r.openbin, 0, n * sizeof(double), c->st);
+    if (e == hipSuccess) e = hipMemsetAsync(r.bins, 0, (size_t)max_bins * n * sizeof(double), c->st);
+    if (e == hipSuccess) e = hipMemsetAsync(r.bad, 0, (size_t)5 * c->nb * sizeof(double), c->st);
+    if (e == hipSuccess) {
+        // cos / sin(2 pi j / L) as finishFermionic of the host layer forms them: the device's structure factors use the same values
+        std::vector<double> trig(2 * L);
+        for (size_t j = 0; j < L; ++j) { trig[j] = std::cos(2.0 * M_PI * double(j) / double(L)); trig[L + j] = std::sin(2.0 * M_PI * double(j) / double(L)); }
+        e = copy_sync(c, r.trig, trig.data(), trig.size() * sizeof(double), hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) { series_free(c); return fail(DQMC_EHIP, std::string("dqmc_series_begin: ") + hipGetErrorString(e)); }
+    r.open = true;
+    return DQMC_OK;
+}
+extern "C" int dqmc_series_end(dqmc_ctx* c) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (!c->ser.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    (void)hipSetDevice(c->p.device);
+    HIPCHK(hipStreamSynchronize(c->st));
+    series_free(c);
+    return DQMC_OK;
+}
+extern "C" int dqmc_series_layout(dqmc_ctx* c, int part, size_t* offset, size_t* length) {
+    if (!c || !offset || !length) return fail(DQMC_EINVAL, "null argument");
+    if (!c->ser.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (part < 0 || part > 4 || !(c->ser.parts & (1 << part))) return fail(DQMC_EINVAL, "dqmc_series_layout: the part is not in the series");
+    *offset = c->ser.off[part]; *length = c->ser.len[part];
+    return DQMC_OK;
+}
+extern "C" int dqmc_series_info(dqmc_ctx* c, int* bins_closed, int* sweeps_in_open_bin, size_t* sample_len) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (!c->ser.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (bins_closed) *bins_closed = c->ser.closed;
+    if (sweeps_in_open_bin) *sweeps_in_open_bin = c->ser.in_open;
+    if (sample_len) *sample_len = c->ser.S;
+    return DQMC_OK;
+}
+extern "C" int dqmc_series_add_sweep(dqmc_ctx* c) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    dqmc_ctx::Series& s = c->ser;
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (s.closed >= s.max_bins) return fail(DQMC_EINVAL, "dqmc_series_add_sweep: the series is full (max_bins bins are closed)");
+    (void)hipSetDevice(c->p.device);
+    // the sample of all chains from the blocks as they stand; the flags of the parts behind each other, [part][chain]
+    int nparts = 0;
+    {
+        ProfScope ps(c, FAM_OTHER, 0);
+        if (s.parts & 1) {
+            if (!launch_series_eq_sample(c->lc, c->hm, c->eqacc, c->eqacc_n, s.trig, s.sample, s.S, s.off[0], s.bad))
+                return fail(DQMC_EINVAL, "dqmc_series_add_sweep: the lattice is too large for the equal-time sample kernel's LDS");
+            ++nparts;
+        }
+        for (int ch = 0; ch < 4; ++ch)
+            if (s.parts & (2 << ch)) {
+                if (!launch_td_matsubara(c->lc, c->hm, c->facc[ch], ch, s.nfreq, ser_apbx(c), ser_apby(c), s.sample + s.off[1 + ch],
+                                         s.bad + (size_t)nparts * c->nb, s.S))
+                    return fail(DQMC_EINVAL, "dqmc_series_add_sweep: the lattice is too large for the Matsubara kernel's LDS");
+                ++nparts;
+            }
+        c->fam_launches[FAM_OTHER] += (uint64_t)nparts;
+    }
+    { const int rc = finish(c, "dqmc_series_add_sweep"); if (rc != DQMC_OK) return rc; }
+    std::vector<double> bad((size_t)nparts * c->nb);
+    HIPCHK(copy_sync(c, bad.data(), s.bad, bad.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (double b : bad)
+        if (b != 0.0) return fail(DQMC_EINVAL, "dqmc_series_add_sweep: a block of the series has no sample (equal-time count or an every-slice row count < 1)");
+    const size_t n = (size_t)c->nb * s.S;
+    const int close = s.in_open + 1 == s.bin_size;
+    { ProfScope ps(c, FAM_OTHER, 1); launch_series_accum(c->lc, s.sample, s.openbin, s.bins + (size_t)s.closed * n, n, close, s.bin_size); }
+    { const int rc = finish(c, "dqmc_series_add_sweep"); if (rc != DQMC_OK) return rc; }
+    if (close) { ++s.closed; s.in_open = 0; } else ++s.in_open;
+    return DQMC_OK;
+}
+extern "C" int dqmc_series_read_bins_host(dqmc_ctx* c, int first, int count, double* out) {
+    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
+    const dqmc_ctx::Series& s = c->ser;
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (first < 0 || count < 1 || first > s.closed || count > s.closed - first) return fail(DQMC_EINVAL, "dqmc_series_read_bins_host: bins outside the closed range");
+    (void)hipSetDevice(c->p.device);
+    const size_t n = (size_t)c->nb * s.S;
+    HIPCHK(hipMemcpy2DAsync(out, s.S * sizeof(double), s.bins + (size_t)first * n + (size_t)c->sel * s.S, n * sizeof(double),
+                            s.S * sizeof(double), (size_t)count, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    return DQMC_OK;
+}
+extern "C" int dqmc_series_stats_host(dqmc_ctx* c, double* mean, double* err) {
+    if (!c || !mean || !err) return fail(DQMC_EINVAL, "null argument");
+    const dqmc_ctx::Series& s = c->ser;
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (s.closed < 2) return fail(DQMC_EINVAL, "dqmc_series_stats_host: the jackknife needs at least two closed bins");
+    (void)hipSetDevice(c->p.device);
+    const size_t n = (size_t)c->nb * s.S;
+    { ProfScope ps(c, FAM_OTHER, 1); launch_series_stats(c->lc, s.bins, n, s.closed, s.stat, s.stat + n); }
+    { const int rc = finish(c, "dqmc_series_stats_host"); if (rc != DQMC_OK) return rc; }
+    HIPCHK(copy_sync(c, mean, s.stat, n * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(c, err, s.stat + n, n * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+extern "C" int dqmc_series_derived_host(dqmc_ctx* c, double* value, double* err) {
+    if (!c || !value || !err) return fail(DQMC_EINVAL, "null argument");
+    const dqmc_ctx::Series& s = c->ser;
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (s.closed < 2) return fail(DQMC_EINVAL, "dqmc_series_derived_host: the jackknife needs at least two closed bins");
+    (void)hipSetDevice(c->p.device);
+    const size_t n = (size_t)c->nb * s.S, nd = (size_t)6 * c->nb;
+    double* dv = s.stat + 2 * n;
+    {
+        ProfScope ps(c, FAM_OTHER, 1);
+        launch_series_derived(c->lc, c->hm, s.bins, s.S, s.closed, s.nfreq, (s.parts & 1) ? (long long)s.off[0] : -1,
+                              (s.parts & 16) ? (long long)s.off[4] : -1, dv, dv + nd);
+    }
+    { const int rc = finish(c, "dqmc_series_derived_host"); if (rc != DQMC_OK) return rc; }
+    HIPCHK(copy_sync(c, value, dv, nd * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(c, err, dv + nd, nd * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+
 extern "C" int dqmc_get_green_td_fine_host(dqmc_ctx* c, dqmc_cplx* g_t0, dqmc_cplx* g_0t, dqmc_cplx* g_tt, int* slice) {
     if (!c || !g_t0 || !g_0t || !g_tt || !slice) return fail(DQMC_EINVAL, "null argument");
     if (!c->td_fine || c->fine_slice < 0) return fail(DQMC_EINVAL, "no every-slice Green's function has been propagated");

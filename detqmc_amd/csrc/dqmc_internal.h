@@ -259,9 +259,18 @@ void launch_td_ends(const Launch& lc, const cplx* G, cplx* a_t0, cplx* a_0t, cpl
 size_t measure_td_doubles(int L, int n);
 // Matsubara transforms of the every-slice block `acc` of `channel` (count[m+1], then the rows): out[chain][component][nfreq][N] (re, im),
 // bad[chain] = 1 if a row of the chain was never measured; out and bad are plain device arrays (no chain stride).  false: the lattice
-// is too large for the kernel's LDS, nothing was launched
+// is too large for the kernel's LDS, nothing was launched.  out_chain_stride (doubles) != 0: chain b's results at out + b * stride
 bool launch_td_matsubara(const Launch& lc, const DevModel& hm, const double* acc, int channel, int nfreq, int apbx, int apby,
-                         double* out, double* bad);
+                         double* out, double* bad, size_t out_chain_stride = 0);
+bool td_matsubara_fits(const DevModel& hm, int channel, int nfreq);     // what launch_td_matsubara would return, nothing launched
+// measurement series (dqmc_series_*): sample / open / closed / bad are plain device arrays, chain b of an [nb][S] array at b * S
+bool launch_series_eq_sample(const Launch& lc, const DevModel& hm, const double* eqacc, size_t eq_n, const double* trig, double* sample,
+                             size_t S, size_t off, double* bad);
+size_t series_eq_sample_lds_bytes(int L);
+void launch_series_accum(const Launch& lc, const double* sample, double* open, double* closed, size_t n, int close, int bin_size);
+void launch_series_stats(const Launch& lc, const double* bins, size_t n, int B, double* mean, double* err);
+void launch_series_derived(const Launch& lc, const DevModel& hm, const double* bins, size_t S, int B, int nfreq, long long off_eq,
+                           long long off_cur, double* value, double* err);
 // time-displaced pairing block: count[n-1], then per boundary j = 1 .. n-1 the sums over B of Re T+(B (+) d, B) [N] and Re T-(B (+) d, B) [N]
 void launch_measure_td_pair(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc, int row, int rows);
 size_t measure_td_pair_doubles(int N, int n);

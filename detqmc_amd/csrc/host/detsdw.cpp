@@ -333,6 +333,12 @@ void DetSDW::sweep_skeleton(Group& g, bool thermalization) {
 // the sweep, so they are accumulated afterwards from the final field, in the slice order of the sweep just done.
 void DetSDW::sweep(bool takeMeasurements) {
     const bool fermionic = takeMeasurements && ch_[0].pars.fermionMeasurements;
+    const bool feedSeries = fermionic && series_.open;
+    if (feedSeries) {                  // nothing is dropped silently, and nothing has changed yet
+        int closed = 0;
+        check(dqmc_series_info(groups_[0].ctx, &closed, nullptr, nullptr), "dqmc_series_info");
+        if (closed >= series_.maxBins) throw GeneralError(DQMC_EINVAL, "the measurement series is full (maxBins bins are closed): read it out and end it");
+    }
     invalidateMatsubara();
     if (fermionic) for (auto& g : groups_) check(dqmc_measure_reset(g.ctx), "initMeasurements");
     measuring_ = fermionic;
@@ -348,7 +354,12 @@ void DetSDW::sweep(bool takeMeasurements) {
         if (measuringTD_) for (auto& g : groups_) (void)dqmc_set_timedisplaced(g.ctx, 0);
         measuringTD_ = false;
     };
-    try { forEachGroup([this](Group& g) { sweep_skeleton(g, false); }); } catch (...) { off(); throw; }
+    try {
+        forEachGroup([this, feedSeries](Group& g) {
+            sweep_skeleton(g, false);
+            if (feedSeries) { g.seriesStatsBins = 0; check(dqmc_series_add_sweep(g.ctx), "dqmc_series_add_sweep"); }
+        });
+    } catch (...) { off(); throw; }
     tdBlocksValid_ = measuringTD_;
     off();
     lastSweepDir_ = (lastSweepDir_ == Up) ? Down : Up;
@@ -420,7 +431,7 @@ void DetSDW::finishFermionic(int b) {
     o.pairPlusMax = pp / 9.0;
     o.pairMinusMax = pm / 9.0;
     // equal-time correlators: C(d) = sum / (count N), and S(q) = sum_d cos(q d) C(d), the real part of the Fourier sum
-    if (eq_correlators(c.pars)) {
+    if (eq_correlators(c.pars) && !seriesNoHostCopy()) {
         std::vector<double> eq(dqmc_measure_eq_accum_size(ctx_));
         check(dqmc_measure_eq_read_host(ctx_, eq.data()), "dqmc_measure_eq_read_host");
         if ((int)eq[0] != m) throw GeneralError(DQMC_EINVAL, "measurement sweep did not visit every time slice (equal-time correlators)");
@@ -596,6 +607,8 @@ void DetSDW::getObservableVector(int which_in, double* out, int b) const {
     if (!fine && which >= DETSDW_OBS_CHARGECORR && which <= DETSDW_OBS_PAIRMINUSSQ) {
         if (!eq_correlators(c.pars))
             throw ParameterWrong("the equal-time correlators and structure factors need equalTimeCorrelators (DETSDW_FM_EQ_CORRELATORS)");
+        if (seriesNoHostCopy())
+            throw ParameterWrong("the equal-time correlators are not copied to the host while a series with DETSDW_SERIES_NO_HOST_COPY is open: read the series");
         const std::vector<double>& e = which < DETSDW_OBS_CHARGESQ ? c.eqCorr[which - DETSDW_OBS_CHARGECORR] : c.eqSq[which - DETSDW_OBS_CHARGESQ];
         std::memcpy(out, e.data(), e.size() * sizeof(double));
         return;
@@ -669,6 +682,123 @@ void DetSDW::getMatsubaraAll(int which, int nfreq, double* out) {
         for (int b = 0; b < g.count; ++b)
             std::memcpy(out + (size_t)(g.first + b) * one, v + ((size_t)b * ncomp + comp) * one, one * sizeof(double));
     }
+}
+
+// Measurement series (include/detsdw_host.h): one dqmc_series per kernel context with the parts the handle's options provide.
+void DetSDW::seriesBegin(int binSize, int maxBins, int nfreq, int flags) {
+    const detsdw_params& p = ch_[0].pars;
+    if (series_.open) throw GeneralError(DQMC_EINVAL, "a measurement series is already open");
+    if (flags & ~DETSDW_SERIES_NO_HOST_COPY) throw ParameterWrong("unknown flag of detsdw_series_begin");
+    int parts = 0;
+    if (eq_correlators(p)) parts |= DQMC_SERIES_EQ;
+    if (td_every_slice(p)) {
+        parts |= DQMC_SERIES_MATS_G;
+        if (td_level(p) == 2) parts |= DQMC_SERIES_MATS_PAIR;
+        if (p.timeDisplacedParticleHole) parts |= DQMC_SERIES_MATS_PH;
+        if (p.timeDisplacedParticleHole == 2) parts |= DQMC_SERIES_MATS_CURRENT;
+    }
+    if (!parts) throw ParameterWrong("a measurement series needs equalTimeCorrelators or timeDisplacedEverySlice");
+    size_t opened = 0;
+    try {
+        for (auto& g : groups_) {
+            if (parts & DQMC_SERIES_EQ) {          // the first enable allocates the block; measurement sweeps switch it on themselves
+                check(dqmc_set_equal_time_correlators(g.ctx, 1), "dqmc_set_equal_time_correlators");
+                check(dqmc_set_equal_time_correlators(g.ctx, 0), "dqmc_set_equal_time_correlators");
+            }
+            check(dqmc_series_begin(g.ctx, binSize, maxBins, nfreq, parts), "dqmc_series_begin");
+            g.seriesStatsBins = 0;
+            ++opened;
+        }
+    } catch (...) {
+        for (size_t i = 0; i < opened; ++i) (void)dqmc_series_end(groups_[i].ctx);
+        throw;
+    }
+    series_.open = true; series_.binSize = binSize; series_.maxBins = maxBins; series_.nfreq = (parts & ~DQMC_SERIES_EQ) ? nfreq : 0;
+    series_.parts = parts; series_.flags = flags;
+}
+void DetSDW::seriesEnd() {
+    if (!series_.open) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
+    series_.open = false;
+    for (auto& g : groups_) { g.seriesStatsBins = 0; g.seriesMean.clear(); g.seriesErr.clear(); check(dqmc_series_end(g.ctx), "dqmc_series_end"); }
+}
+void DetSDW::seriesInfo(int* binsClosed, int* sweepsInOpenBin, size_t* sampleLen) {
+    if (!series_.open) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
+    check(dqmc_series_info(groups_[0].ctx, binsClosed, sweepsInOpenBin, sampleLen), "dqmc_series_info");
+}
+void DetSDW::seriesSlice(int which, int& part, size_t& offset, size_t& length) {
+    if (!series_.open) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
+    size_t sub;
+    if (which >= DETSDW_OBS_CHARGECORR && which <= DETSDW_OBS_PAIRMINUSSQ) {
+        if (!(series_.parts & DQMC_SERIES_EQ)) throw ParameterWrong("the equal-time part of the series needs equalTimeCorrelators");
+        part = 0; length = (size_t)N_; sub = (size_t)(which - DETSDW_OBS_CHARGECORR) * N_;
+    } else {
+        int channel, comp;
+        if (which == DETSDW_OBS_GREENKTAU_X || which == DETSDW_OBS_GREENKTAU_Y) { channel = 0; comp = which - DETSDW_OBS_GREENKTAU_X; }
+        else if (which == DETSDW_OBS_PAIRPLUSTAU || which == DETSDW_OBS_PAIRMINUSTAU) { channel = 1; comp = which - DETSDW_OBS_PAIRPLUSTAU; }
+        else if (which >= DETSDW_OBS_CHARGETAU && which <= DETSDW_OBS_SDWTAU) { channel = 2; comp = which - DETSDW_OBS_CHARGETAU; }
+        else if (which == DETSDW_OBS_CURRENTXTAU || which == DETSDW_OBS_CURRENTYTAU) { channel = 3; comp = which - DETSDW_OBS_CURRENTXTAU; }
+        else throw ParameterWrong("the measurement series does not hold this observable");
+        if (!(series_.parts & (2 << channel))) throw ParameterWrong("the series has no Matsubara part for this observable: the option it needs, or timeDisplacedEverySlice, is off");
+        part = 1 + channel; length = (size_t)series_.nfreq * N_ * 2; sub = (size_t)comp * length;
+    }
+    size_t off = 0, len = 0;
+    check(dqmc_series_layout(groups_[0].ctx, part, &off, &len), "dqmc_series_layout");
+    offset = off + sub;
+}
+void DetSDW::seriesStatsOf(Group& g) {
+    int closed = 0; size_t S = 0;
+    check(dqmc_series_info(g.ctx, &closed, nullptr, &S), "dqmc_series_info");
+    if (g.seriesStatsBins == closed && closed >= 2) return;
+    g.seriesStatsBins = 0;
+    g.seriesMean.resize((size_t)g.count * S); g.seriesErr.resize((size_t)g.count * S);
+    check(dqmc_series_stats_host(g.ctx, g.seriesMean.data(), g.seriesErr.data()), "dqmc_series_stats_host");
+    g.seriesStatsBins = closed;
+}
+void DetSDW::seriesStats(int which, double* mean, double* err, int b) {
+    if (b < 0 || b >= (int)ch_.size()) throw ParameterWrong("chain index out of range");
+    int part; size_t off, len;
+    seriesSlice(which, part, off, len);
+    Group& g = grp(b);
+    seriesStatsOf(g);
+    const size_t S = g.seriesMean.size() / (size_t)g.count, at = (size_t)(b - g.first) * S + off;
+    std::memcpy(mean, &g.seriesMean[at], len * sizeof(double));
+    std::memcpy(err, &g.seriesErr[at], len * sizeof(double));
+}
+void DetSDW::seriesStatsAll(int which, double* mean, double* err) {
+    int part; size_t off, len;
+    seriesSlice(which, part, off, len);
+    for (auto& g : groups_) {
+        seriesStatsOf(g);
+        const size_t S = g.seriesMean.size() / (size_t)g.count;
+        for (int b = 0; b < g.count; ++b) {
+            std::memcpy(mean + (size_t)(g.first + b) * len, &g.seriesMean[(size_t)b * S + off], len * sizeof(double));
+            std::memcpy(err + (size_t)(g.first + b) * len, &g.seriesErr[(size_t)b * S + off], len * sizeof(double));
+        }
+    }
+}
+void DetSDW::seriesDerivedAll(int what, double* value, double* err) {
+    if (!series_.open) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
+    if (what < DETSDW_SERIES_R_CHARGE || what > DETSDW_SERIES_RHO_S) throw ParameterWrong("unknown derived quantity of the measurement series");
+    if (what <= DETSDW_SERIES_R_PAIRMINUS && !(series_.parts & DQMC_SERIES_EQ)) throw ParameterWrong("the correlation ratios need equalTimeCorrelators");
+    if (what == DETSDW_SERIES_RHO_S && !(series_.parts & DQMC_SERIES_MATS_CURRENT))
+        throw ParameterWrong("rho_s needs timeDisplacedParticleHole = 2 and timeDisplacedEverySlice");
+    std::vector<double> v, e;
+    for (auto& g : groups_) {
+        v.resize((size_t)g.count * 6); e.resize((size_t)g.count * 6);
+        check(dqmc_series_derived_host(g.ctx, v.data(), e.data()), "dqmc_series_derived_host");
+        for (int b = 0; b < g.count; ++b) { value[g.first + b] = v[(size_t)b * 6 + what]; err[g.first + b] = e[(size_t)b * 6 + what]; }
+    }
+}
+void DetSDW::seriesReadBins(int which, int first, int count, double* out, int b) {
+    int part; size_t off, len;
+    seriesSlice(which, part, off, len);
+    dqmc_ctx* ctx_ = select(b);
+    size_t S = 0;
+    check(dqmc_series_info(ctx_, nullptr, nullptr, &S), "dqmc_series_info");
+    if (count < 1) throw ParameterWrong("detsdw_series_read_bins: count must be at least 1");
+    std::vector<double> buf((size_t)count * S);
+    check(dqmc_series_read_bins_host(ctx_, first, count, buf.data()), "dqmc_series_read_bins_host");
+    for (int i = 0; i < count; ++i) std::memcpy(out + (size_t)i * len, &buf[(size_t)i * S + off], len * sizeof(double));
 }
 
 // initMeasurements / measure / finishMeasurements, bosonic part (detsdwopdim.cpp:441-456, :509-545, :903-921)
@@ -1176,6 +1306,29 @@ extern "C" int detsdw_get_matsubara_all(detsdw_replica* r, int which, int nfreq,
     if (!out) { g_host_err = "null argument"; return DQMC_EINVAL; }
     RGUARD(r->impl->getMatsubaraAll(which, nfreq, out))
 }
+extern "C" int detsdw_series_begin(detsdw_replica* r, int binSize, int maxBins, int nfreq, int flags) {
+    RGUARD(r->impl->seriesBegin(binSize, maxBins, nfreq, flags))
+}
+extern "C" int detsdw_series_info(detsdw_replica* r, int* binsClosed, int* sweepsInOpenBin, size_t* sampleLen) {
+    RGUARD(r->impl->seriesInfo(binsClosed, sweepsInOpenBin, sampleLen))
+}
+extern "C" int detsdw_series_stats(detsdw_replica* r, int which, double* mean, double* err) {
+    if (!mean || !err) { g_host_err = "null argument"; return DQMC_EINVAL; }
+    RGUARD(r->impl->seriesStats(which, mean, err, r->sel))
+}
+extern "C" int detsdw_series_stats_all(detsdw_replica* r, int which, double* mean, double* err) {
+    if (!mean || !err) { g_host_err = "null argument"; return DQMC_EINVAL; }
+    RGUARD(r->impl->seriesStatsAll(which, mean, err))
+}
+extern "C" int detsdw_series_derived_all(detsdw_replica* r, int what, double* value, double* err) {
+    if (!value || !err) { g_host_err = "null argument"; return DQMC_EINVAL; }
+    RGUARD(r->impl->seriesDerivedAll(what, value, err))
+}
+extern "C" int detsdw_series_read_bins(detsdw_replica* r, int which, int first, int count, double* out) {
+    if (!out) { g_host_err = "null argument"; return DQMC_EINVAL; }
+    RGUARD(r->impl->seriesReadBins(which, first, count, out, r->sel))
+}
+extern "C" int detsdw_series_end(detsdw_replica* r) { RGUARD(r->impl->seriesEnd()) }
 extern "C" int detsdw_get_tau_grid(detsdw_replica* r, double* out) {
     if (!out) { g_host_err = "null argument"; return DQMC_EINVAL; }
     RGUARD(r->impl->getTauGrid(out))

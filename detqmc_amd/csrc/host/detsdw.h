@@ -61,6 +61,14 @@ public:
     // out[nchains][nfreq][N] of every chain in handle order; valid after a measurement sweep and until the next sweep
     void getMatsubara(int which, int nfreq, double* out, int b = 0);
     void getMatsubaraAll(int which, int nfreq, double* out);
+    // measurement series (include/detsdw_host.h): one dqmc_series per kernel context, fed by every sweep(true) while it is open
+    void seriesBegin(int binSize, int maxBins, int nfreq, int flags);
+    void seriesEnd();
+    void seriesInfo(int* binsClosed, int* sweepsInOpenBin, size_t* sampleLen);
+    void seriesStats(int which, double* mean, double* err, int b = 0);
+    void seriesStatsAll(int which, double* mean, double* err);
+    void seriesDerivedAll(int what, double* value, double* err);
+    void seriesReadBins(int which, int first, int count, double* out, int b = 0);
     void getPhi(double* phi, int b = 0);
     void setPhi(const double* phi, int b = 0);
     void getCdwl(int32_t* cdwl, int b = 0);
@@ -109,6 +117,8 @@ private:
         std::vector<double> fields;                // host staging of all chains' fields (global moves)
         std::vector<double> mats[4];               // Matsubara transforms of the group's chains per channel, [chain][component][nfreq][N] (re, im)
         int matsNfreq[4] = {0, 0, 0, 0};           // ... and the nfreq they hold (0: none); cleared by every sweep
+        std::vector<double> seriesMean, seriesErr; // dqmc_series_stats_host of the group's chains, [chain][S] each ...
+        int seriesStatsBins = 0;                   // ... and the number of closed bins they were formed from (0: none)
     };
     std::vector<Group> groups_;
     int N_, MSF_, ng_, m_, s_, n_, opdim_;
@@ -128,6 +138,10 @@ private:
     bool measuring_ = false;          // measure(k) after the updates of slice k (updateInSliceAndMaybeMeasure)
     bool measuringTD_ = false;        // ... and G(tau_j, 0) after every interior advance (timeDisplacedMeasurements)
     bool tdBlocksValid_ = false;      // the device's time-displaced blocks are those of the last sweep, a measurement sweep
+    struct { bool open = false; int binSize = 0, maxBins = 0, nfreq = 0, parts = 0, flags = 0; } series_;
+    bool seriesNoHostCopy() const { return series_.open && (series_.flags & DETSDW_SERIES_NO_HOST_COPY); }
+    void seriesSlice(int which, int& part, size_t& offset, size_t& length);   // where `which` sits inside its part
+    void seriesStatsOf(Group& g);                                             // fills the group's cache
     void invalidateMatsubara();
     const double* matsubara(Group& g, int which, int nfreq, int& ncomp, int& comp);
     void measureTimeDisplaced(Group& g, int j);

@@ -797,7 +797,7 @@ void launch_td_ends(const Launch& lc, const cplx* G, cplx* a_t0, cplx* a_0t, cpl
 // greenKTau sum: two transforms, each writes its half of the output element.  One writer per output element, fixed summation order
 // (k, then y, then x ascending), no atomics.  bad[chain] = 1 if a row of the chain has a count < 1 (written by workgroup (0, 0) alone).
 #define TDM_FT 8
-struct TdmShape { int channel, ncomp, nfreq, ftile, m, L, N, W, WP, rlen, stride, apbx, apby; double scale; };
+struct TdmShape { int channel, ncomp, nfreq, ftile, m, L, N, W, WP, rlen, stride, apbx, apby; double scale; size_t ocs; };   // ocs: chain stride of out (doubles)
 
 size_t measure_td_matsubara_lds_doubles(int ftile, int m, int L, int W, int rlen) {
     const int WP = W | 1;
@@ -896,7 +896,7 @@ __global__ __launch_bounds__(256) void k_td_matsubara(const double* __restrict__
         }
     }
     __syncthreads();
-    double* o = out + (((size_t)blockIdx.z * a.ncomp + comp) * a.nfreq + f0) * (size_t)a.N * 2;
+    double* o = out + (size_t)blockIdx.z * a.ocs + ((size_t)comp * a.nfreq + f0) * (size_t)a.N * 2;
     for (int f = 0; f < nf; ++f, o += (size_t)a.N * 2) {
         const double* zA = Z + (size_t)(2 * f) * R;
         const double* zB = zA + R;
@@ -911,21 +911,184 @@ __global__ __launch_bounds__(256) void k_td_matsubara(const double* __restrict__
 }
 
 // out: [chain][component][nfreq][N] (re, im), bad: [chain]; both plain device arrays outside the arena.  Returns false if not even one
-// frequency of the lattice fits the LDS of a workgroup (nothing is launched then).
-bool launch_td_matsubara(const Launch& lc, const DevModel& hm, const double* acc, int channel, int nfreq, int apbx, int apby,
-                         double* out, double* bad) {
+// frequency of the lattice fits the LDS of a workgroup (nothing is launched then).  out_chain_stride (doubles): distance between the
+// results of consecutive chains, 0 = packed (components * nfreq * N * 2); the measurement series hands in its sample buffer this way.
+static int tdm_ftile(const DevModel& hm, int channel, int nfreq) {
     const int L = hm.L, N = hm.N, m = hm.m, W = channel == 0 ? 2 * L - 1 : L;
-    const int rlen = channel == 0 ? 2 * W * W : N, ncomp = channel == 2 ? 3 : 2;
+    const int rlen = channel == 0 ? 2 * W * W : N;
     const size_t budget = 152 * 1024;
     int ftile = nfreq < TDM_FT ? nfreq : TDM_FT;
     while (ftile >= 1 && measure_td_matsubara_lds_doubles(ftile, m, L, W, rlen) * sizeof(double) > budget) --ftile;
+    return ftile;
+}
+bool td_matsubara_fits(const DevModel& hm, int channel, int nfreq) { return tdm_ftile(hm, channel, nfreq) >= 1; }
+bool launch_td_matsubara(const Launch& lc, const DevModel& hm, const double* acc, int channel, int nfreq, int apbx, int apby,
+                         double* out, double* bad, size_t out_chain_stride) {
+    const int L = hm.L, N = hm.N, m = hm.m, W = channel == 0 ? 2 * L - 1 : L;
+    const int rlen = channel == 0 ? 2 * W * W : N, ncomp = channel == 2 ? 3 : 2;
+    const int ftile = tdm_ftile(hm, channel, nfreq);
     if (ftile < 1) return false;
     const size_t lds = measure_td_matsubara_lds_doubles(ftile, m, L, W, rlen) * sizeof(double);
     if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)k_td_matsubara, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         (void)hipGetLastError();                            // the launch below then reports the problem
     TdmShape a{channel, ncomp, nfreq, ftile, m, L, N, W, W | 1, rlen, (int)measure_td_row_doubles(channel, N, L), apbx, apby,
-               hm.dtau / (channel == 0 ? 2.0 * N : (double)N)};
+               hm.dtau / (channel == 0 ? 2.0 * N : (double)N), out_chain_stride ? out_chain_stride : (size_t)ncomp * nfreq * N * 2};
     const dim3 grid((nfreq + ftile - 1) / ftile, ncomp, lc.nb);
     hipLaunchKernelGGL(k_td_matsubara, grid, dim3(256), lds, lc.st, acc, out, bad, a, lc.cs);
     return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Measurement series (dqmc_series_*, dqmc_hip.h): one sample per measurement sweep, accumulated into bins on the device.
+// All buffers are plain device arrays outside the arena, chain b of a [nb][S] array at b * S.  Every kernel has one writer per output
+// element, a fixed summation order and no atomics; no element of one chain depends on another chain or on the number of chains.
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Equal-time part of the sample: C_X(d) = sum / (N count) into out[X][d], S_X(q) = sum_d cos(q d) C_X(d) into out[5 + X][q], column
+// qy L + qx.  One workgroup per (channel X, chain): C_X in LDS, then the separable cosine sum in the order of the host's finishFermionic --
+// over dx into (Ac, As)[dy][qx], then over dy -- with the phase index reduced mod L in integers and cos / sin(2 pi j / L) from the table
+// `trig` = (cos[L], sin[L]) the host computed.  bad[chain] = 1 if the block's count is < 1 (written by the workgroup of channel 0).
+size_t series_eq_sample_lds_bytes(int L) { return ((size_t)3 * L * L + 2 * (size_t)L) * sizeof(double); }
+__global__ __launch_bounds__(256) void k_series_eq_sample(const double* __restrict__ eqacc, size_t eq_n, const double* __restrict__ trig,
+                                                          double* __restrict__ sample, size_t S, size_t off, double* __restrict__ bad, int L) {
+    extern __shared__ double ses_sm[];
+    const int tid = threadIdx.x, ch = blockIdx.x, N = L * L;
+    const double* blk = eqacc + (size_t)blockIdx.z * eq_n;
+    double* out = sample + (size_t)blockIdx.z * S + off;
+    double* C = ses_sm;                                     // [N]
+    double* Ac = C + N;                                     // [dy][qx]
+    double* As = Ac + N;
+    double* ct = As + N;                                    // [L]
+    double* st = ct + L;
+    const double cnt = blk[0];
+    if (ch == 0 && tid == 0) bad[blockIdx.z] = cnt >= 1.0 ? 0.0 : 1.0;
+    for (int j = tid; j < L; j += 256) { ct[j] = trig[j]; st[j] = trig[L + j]; }
+    const double den = (double)N * cnt;
+    for (int d = tid; d < N; d += 256) {
+        const double v = blk[1 + (size_t)ch * N + d] / den;
+        C[d] = v;
+        out[(size_t)ch * N + d] = v;
+    }
+    __syncthreads();
+    for (int i = tid; i < N; i += 256) {
+        const int dy = i / L, qx = i - dy * L;
+        double sc = 0.0, ss = 0.0;
+        for (int dx = 0; dx < L; ++dx) {
+            const double v = C[dy * L + dx];
+            const int j = (qx * dx) % L;
+            sc += ct[j] * v; ss += st[j] * v;
+        }
+        Ac[i] = sc; As[i] = ss;
+    }
+    __syncthreads();
+    for (int q = tid; q < N; q += 256) {
+        const int qy = q / L, qx = q - qy * L;
+        double sq = 0.0;
+        for (int dy = 0; dy < L; ++dy) {
+            const int j = (qy * dy) % L;
+            sq += ct[j] * Ac[dy * L + qx] - st[j] * As[dy * L + qx];
+        }
+        out[(size_t)(5 + ch) * N + q] = sq;
+    }
+}
+// false: the lattice is too large for the kernel's LDS, nothing was launched
+bool launch_series_eq_sample(const Launch& lc, const DevModel& hm, const double* eqacc, size_t eq_n, const double* trig, double* sample,
+                             size_t S, size_t off, double* bad) {
+    const size_t lds = series_eq_sample_lds_bytes(hm.L);
+    if (lds > 152 * 1024) return false;
+    if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)k_series_eq_sample, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        (void)hipGetLastError();
+    hipLaunchKernelGGL(k_series_eq_sample, dim3(5, 1, lc.nb), dim3(256), lds, lc.st, eqacc, eq_n, trig, sample, S, off, bad, hm.L);
+    return true;
+}
+
+// open += sample over the n = nb S elements; close != 0: closed = open / bin_size and the open bin is cleared
+__global__ __launch_bounds__(256) void k_series_accum(const double* __restrict__ sample, double* __restrict__ open, double* __restrict__ closed,
+                                                      size_t n, int close, double bin_size) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double o = open[i] + sample[i];
+    if (close) { closed[i] = o / bin_size; open[i] = 0.0; }
+    else open[i] = o;
+}
+void launch_series_accum(const Launch& lc, const double* sample, double* open, double* closed, size_t n, int close, int bin_size) {
+    hipLaunchKernelGGL(k_series_accum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, lc.st, sample, open, closed, n, close, (double)bin_size);
+}
+
+// Jackknife over the B closed bins, bins[b][n]: mean = (sum_b x_b) / B, x_(b) = (B mean - x_b) / (B - 1),
+// err = sqrt((B - 1) / B sum_b (x_(b) - mean)^2).  One thread per element, bins in index order.
+__global__ __launch_bounds__(256) void k_series_stats(const double* __restrict__ bins, size_t n, int B, double* __restrict__ mean,
+                                                      double* __restrict__ err) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double sum = 0.0;
+    for (int b = 0; b < B; ++b) sum += bins[(size_t)b * n + i];
+    const double mu = sum / (double)B, tot = (double)B * mu;
+    double acc = 0.0;
+    for (int b = 0; b < B; ++b) {
+        const double d = (tot - bins[(size_t)b * n + i]) / (double)(B - 1) - mu;
+        acc += d * d;
+    }
+    mean[i] = mu;
+    err[i] = sqrt((double)(B - 1) / (double)B * acc);
+}
+void launch_series_stats(const Launch& lc, const double* bins, size_t n, int B, double* mean, double* err) {
+    hipLaunchKernelGGL(k_series_stats, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, lc.st, bins, n, B, mean, err);
+}
+
+// Jackknifed derived quantities, out[chain][6]: entries 0 .. 4 the correlation ratios R_X = 1 - (S_X(Q + dx) + S_X(Q + dy)) / (2 S_X(Q)),
+// Q = (L/2, L/2) for charge, spinZ, sdw and (0, 0) for pairPlus, pairMinus; entry 5 rho_s = 1/8 [Lxx(1,0) - Lxx(0,1) + Lyy(0,1) - Lyy(1,0)]
+// at frequency 0 (real parts).  value = f(mean); err about the mean of theta_(b) = f(x_(b)).  off_eq / off_cur: offset of the equal-time
+// part / of the channel-3 Matsubara part inside a sample, -1 if the part is not in the series (NaN then).  One thread per (chain, entry).
+struct SeriesDerivedShape { long long off_eq, off_cur; int L, N, nfreq, nb, B; size_t S; };
+__device__ __forceinline__ double series_derived_f(int e, const double* x) {
+    if (e < 5) return 1.0 - 0.5 * (x[1] + x[2]) / x[0];
+    return 0.125 * (x[0] - x[1] + x[2] - x[3]);
+}
+__global__ __launch_bounds__(64) void k_series_derived(const double* __restrict__ bins, SeriesDerivedShape a, double* __restrict__ value,
+                                                       double* __restrict__ err) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= a.nb * 6) return;
+    const int chain = t / 6, e = t - chain * 6, L = a.L, N = a.N;
+    const long long off = e < 5 ? a.off_eq : a.off_cur;
+    if (off < 0) { value[t] = nan(""); err[t] = nan(""); return; }
+    size_t idx[4];
+    int cnt;
+    if (e < 5) {
+        const int Q = e < 3 ? L / 2 : 0, qx1 = (Q + 1) % L, qy1 = (Q + 1) % L;
+        const size_t base = (size_t)off + (size_t)(5 + e) * N;
+        idx[0] = base + (size_t)Q * L + Q; idx[1] = base + (size_t)Q * L + qx1; idx[2] = base + (size_t)qy1 * L + Q; idx[3] = idx[0];
+        cnt = 3;
+    } else {
+        const size_t xx = (size_t)off, yy = (size_t)off + (size_t)a.nfreq * N * 2;     // component 0 / 1, frequency 0, real parts
+        idx[0] = xx + 2 * (size_t)(1 % N); idx[1] = xx + 2 * (size_t)(L % N); idx[2] = yy + 2 * (size_t)(L % N); idx[3] = yy + 2 * (size_t)(1 % N);
+        cnt = 4;
+    }
+    const size_t n = (size_t)a.nb * a.S;
+    const double* p = bins + (size_t)chain * a.S;
+    const int B = a.B;
+    double mu[4] = {0.0, 0.0, 0.0, 0.0}, tot[4], x[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int j = 0; j < cnt; ++j) {
+        double sum = 0.0;
+        for (int b = 0; b < B; ++b) sum += p[(size_t)b * n + idx[j]];
+        mu[j] = sum / (double)B; tot[j] = (double)B * mu[j];
+    }
+    double tsum = 0.0;
+    for (int b = 0; b < B; ++b) {
+        for (int j = 0; j < cnt; ++j) x[j] = (tot[j] - p[(size_t)b * n + idx[j]]) / (double)(B - 1);
+        tsum += series_derived_f(e, x);
+    }
+    const double tbar = tsum / (double)B;
+    double acc = 0.0;
+    for (int b = 0; b < B; ++b) {
+        for (int j = 0; j < cnt; ++j) x[j] = (tot[j] - p[(size_t)b * n + idx[j]]) / (double)(B - 1);
+        const double d = series_derived_f(e, x) - tbar;
+        acc += d * d;
+    }
+    value[t] = series_derived_f(e, mu);
+    err[t] = sqrt((double)(B - 1) / (double)B * acc);
+}
+void launch_series_derived(const Launch& lc, const DevModel& hm, const double* bins, size_t S, int B, int nfreq, long long off_eq,
+                           long long off_cur, double* value, double* err) {
+    SeriesDerivedShape a{off_eq, off_cur, hm.L, hm.N, nfreq, lc.nb, B, S};
+    hipLaunchKernelGGL(k_series_derived, dim3((unsigned)((lc.nb * 6 + 63) / 64)), dim3(64), 0, lc.st, bins, a, value, err);
 }

@@ -112,6 +112,29 @@ def superfluid_stiffness(chi_xx, chi_yy, L):
     return 0.125 * np.real(xx[..., 1] - xx[..., L] + yy[..., L] - yy[..., 1])
 
 
+# derived quantities of a measurement series (DetSDWBatch.series_derived_all): name -> index of detsdw_series_derived_all
+SERIES_DERIVED = {"R_charge": 0, "R_spinZ": 1, "R_sdw": 2, "R_pairPlus": 3, "R_pairMinus": 4, "rhoS": 5}
+# parts of a kernel-level series (KernelContext.series_begin): bit 0 the equal-time block, bits 1 .. 4 the Matsubara transform of channel 0 .. 3
+SERIES_EQ, SERIES_MATS_G, SERIES_MATS_PAIR, SERIES_MATS_PH, SERIES_MATS_CURRENT = 1, 2, 4, 8, 16
+
+
+def jackknife(bins, f=None):
+    """Jackknife over the leading axis of `bins` (B >= 2 bin means x_b), the formulas of dqmc_series_stats_host / _derived_host:
+    mean = (1/B) sum_b x_b, x_(b) = (B mean - x_b) / (B - 1).  f=None: returns (mean, err) with
+    err = sqrt((B - 1)/B sum_b (x_(b) - mean)^2), element by element.  With a function f of one bin-shaped array: returns
+    (f(mean), err) with err = sqrt((B - 1)/B sum_b (theta_(b) - mean_b theta_(b))^2), theta_(b) = f(x_(b))."""
+    x = np.asarray(bins, dtype=np.float64)
+    B = x.shape[0]
+    if B < 2:
+        raise ValueError("the jackknife needs at least two bins")
+    mean = x.sum(axis=0) / B
+    loo = (B * mean - x) / (B - 1)
+    if f is None:
+        return mean, np.sqrt((B - 1) / B * ((loo - mean) ** 2).sum(axis=0))
+    theta = np.array([f(v) for v in loo])
+    return f(mean), np.sqrt((B - 1) / B * ((theta - theta.sum(axis=0) / B) ** 2).sum(axis=0))
+
+
 SPIN_PROPOSAL = {"box": 0, "rotate_then_scale": 1, "rotate_and_scale": 2}
 PROPOSE = {"box": 0, "rotate": 1, "scale": 2, "rotate_and_scale": 3}
 ADAPT = {"box": 0, "rotate": 1, "scale": 2}
@@ -275,6 +298,52 @@ class KernelContext:
         out = np.zeros(self.lib.dqmc_measure_td_matsubara_size(self.h, channel, nfreq))
         check(self.lib.dqmc_measure_td_matsubara_host(self.h, channel, nfreq, out.ctypes.data_as(_lib._DP)))
         return out.view(np.complex128).reshape(self.nchains_total(), 3 if channel == 2 else 2, nfreq, self.N)
+
+    def series_begin(self, bin_size, max_bins, nfreq=0, parts=SERIES_EQ):
+        """open the measurement series of this context: bins of bin_size samples, at most max_bins of them; parts = SERIES_EQ |
+        SERIES_MATS_G | ... (the equal-time block must have been enabled, the Matsubara parts need their every-slice block)"""
+        check(self.lib.dqmc_series_begin(self.h, int(bin_size), int(max_bins), int(nfreq), int(parts)))
+
+    def series_add_sweep(self):
+        """one sample of every chain from the blocks as they stand, added to the open bin"""
+        check(self.lib.dqmc_series_add_sweep(self.h))
+
+    def series_info(self):
+        """(bins closed, samples in the open bin, doubles per sample S)"""
+        a, b, s = C.c_int(0), C.c_int(0), C.c_size_t(0)
+        check(self.lib.dqmc_series_info(self.h, C.byref(a), C.byref(b), C.byref(s)))
+        return a.value, b.value, s.value
+
+    def series_layout(self, part):
+        """(offset, length) of part 0 (equal-time: C_X(d) [5][N], S_X(q) [5][N]) or 1 + channel (Matsubara, [component][nfreq][N] (re, im))"""
+        off, ln = C.c_size_t(0), C.c_size_t(0)
+        check(self.lib.dqmc_series_layout(self.h, int(part), C.byref(off), C.byref(ln)))
+        return off.value, ln.value
+
+    def series_bins(self, first=0, count=None):
+        """closed bins first .. first + count - 1 (default: all from first) of the selected chain: (count, S)"""
+        closed, _, S = self.series_info()
+        count = closed - first if count is None else int(count)
+        out = np.zeros((max(count, 0), S))
+        check(self.lib.dqmc_series_read_bins_host(self.h, int(first), count, out.ctypes.data_as(_lib._DP)))
+        return out
+
+    def series_stats(self):
+        """(mean, err) of every element over the closed bins, jackknife, all chains: (nchains, S) each"""
+        S = self.series_info()[2]
+        mean, err = np.zeros((self.nchains_total(), S)), np.zeros((self.nchains_total(), S))
+        check(self.lib.dqmc_series_stats_host(self.h, mean.ctypes.data_as(_lib._DP), err.ctypes.data_as(_lib._DP)))
+        return mean, err
+
+    def series_derived(self):
+        """(value, err), (nchains, 6) each: the correlation ratios R_charge, R_spinZ, R_sdw, R_pairPlus, R_pairMinus and rho_s; NaN where
+        the part is not in the series"""
+        v, e = np.zeros((self.nchains_total(), 6)), np.zeros((self.nchains_total(), 6))
+        check(self.lib.dqmc_series_derived_host(self.h, v.ctypes.data_as(_lib._DP), e.ctypes.data_as(_lib._DP)))
+        return v, e
+
+    def series_end(self):
+        check(self.lib.dqmc_series_end(self.h))
 
     def td_fine_propagate(self, j, k):
         """for tests: the work copies at slice k of boundary j's segment, by the steps of measure_timedisplaced_segment; measures nothing"""
@@ -626,6 +695,34 @@ class DetSDW:
         check(self.lib.detsdw_get_matsubara(self.h, MATSUBARA[name], int(nfreq), out.ctypes.data_as(_lib._DP)), host=True)
         return out
 
+    def _series_shape(self, name):
+        """(index of detsdw_series_stats, shape of one chain's values, complex?) of a series observable"""
+        if self._batch is None:
+            raise RuntimeError("a measurement series is opened on a batch: DetSDWBatch([pars]).series_begin()")
+        info = self.info
+        if name in EQ_CORRELATORS:
+            return EQ_CORRELATORS[name], (info.N,), False
+        return MATSUBARA[name], (self._batch._series_nfreq, info.N), True
+
+    def series_stats(self, name):
+        """(mean, err) of this chain over the closed bins of the open series (DetSDWBatch.series_begin): name = an equal-time
+        '...Corr' / '...Sq' observable, length N, or a name of matsubara(), complex (nfreq, N) with err = err(Re) + i err(Im)"""
+        self._sel()
+        which, shape, cplx = self._series_shape(name)
+        mean, err = (np.zeros(shape, dtype=np.complex128 if cplx else np.float64) for _ in range(2))
+        check(self.lib.detsdw_series_stats(self.h, which, mean.ctypes.data_as(_lib._DP), err.ctypes.data_as(_lib._DP)), host=True)
+        return mean, err
+
+    def series_bins(self, name, first=0, count=None):
+        """the closed bin means first .. first + count - 1 (default: all from first) of this chain: (count,) + the shape of series_stats"""
+        self._sel()
+        which, shape, cplx = self._series_shape(name)
+        if count is None:
+            count = self._batch.series_info()[0] - first
+        out = np.zeros((max(int(count), 0),) + shape, dtype=np.complex128 if cplx else np.float64)
+        check(self.lib.detsdw_series_read_bins(self.h, which, int(first), int(count), out.ctypes.data_as(_lib._DP)), host=True)
+        return out
+
     def matsubara_frequencies(self, nfreq, fermionic=False):
         """omega_n, n = 0 .. nfreq-1: 2 pi n / beta, or (2n+1) pi / beta for the fermionic 'greenKTauX' / 'greenKTauY'"""
         n = np.arange(int(nfreq))
@@ -753,6 +850,7 @@ class DetSDWBatch:
         check(self.lib.detsdw_create_batch_ex(arr, len(self.pars_list), int(sub_batches), C.byref(h)), host=True)
         self.h = h
         self.sub_batches = self.lib.detsdw_num_sub_batches(h)
+        self._series_nfreq = 0
         self.chains = [DetSDW(_batch=self, _chain=b) for b in range(len(self.pars_list))]
 
     def __len__(self):
@@ -778,6 +876,38 @@ class DetSDWBatch:
         out = np.zeros((len(self.chains), int(nfreq), self.chains[0].info.N), dtype=np.complex128)
         check(self.lib.detsdw_get_matsubara_all(self.h, MATSUBARA[name], int(nfreq), out.ctypes.data_as(_lib._DP)), host=True)
         return out
+
+    def series_begin(self, binSize, maxBins, nfreq=0, host_copy=True):
+        """open a measurement series on the device: from now on every sweep(True) adds one sample per chain -- the equal-time C(d),
+        S(q) with equalTimeCorrelators, the Matsubara transforms at nfreq frequencies of every enabled channel with
+        timeDisplacedEverySlice -- to bins of binSize sweeps, at most maxBins of them.  host_copy=False: measurement sweeps no longer
+        copy the equal-time block to the host ('...Corr' / '...Sq' of observable_vector raise while the series is open)"""
+        flags = 0 if host_copy else _lib.DETSDW_SERIES_NO_HOST_COPY
+        check(self.lib.detsdw_series_begin(self.h, int(binSize), int(maxBins), int(nfreq), flags), host=True)
+        self._series_nfreq = int(nfreq)
+
+    def series_info(self):
+        """(bins closed, sweeps in the open bin, doubles per sample)"""
+        a, b, s = C.c_int(0), C.c_int(0), C.c_size_t(0)
+        check(self.lib.detsdw_series_info(self.h, C.byref(a), C.byref(b), C.byref(s)), host=True)
+        return a.value, b.value, s.value
+
+    def series_stats_all(self, name):
+        """DetSDW.series_stats of every chain: (mean, err), (nchains,) + the per-chain shape each; one device call per sub-batch"""
+        which, shape, cplx = self.chains[0]._series_shape(name)
+        mean, err = (np.zeros((len(self.chains),) + shape, dtype=np.complex128 if cplx else np.float64) for _ in range(2))
+        check(self.lib.detsdw_series_stats_all(self.h, which, mean.ctypes.data_as(_lib._DP), err.ctypes.data_as(_lib._DP)), host=True)
+        return mean, err
+
+    def series_derived_all(self, name):
+        """(value, err) per chain of a jackknifed derived quantity: the correlation ratios 'R_charge', 'R_spinZ', 'R_sdw',
+        'R_pairPlus', 'R_pairMinus' (equalTimeCorrelators) or 'rhoS' (timeDisplacedCurrent with timeDisplacedEverySlice)"""
+        v, e = np.zeros(len(self.chains)), np.zeros(len(self.chains))
+        check(self.lib.detsdw_series_derived_all(self.h, SERIES_DERIVED[name], v.ctypes.data_as(_lib._DP), e.ctypes.data_as(_lib._DP)), host=True)
+        return v, e
+
+    def series_end(self):
+        check(self.lib.detsdw_series_end(self.h), host=True)
 
     def exchange_actions_device(self, device_ptr):
         """get_exchange_action_contribution of EVERY chain written to device memory (len(self) doubles at device_ptr, e.g.

@@ -191,7 +191,7 @@ int detsdw_get_observables(detsdw_replica* r, detsdw_observables* out);
  *   C_X(d) = (1 / (m N)) sum_{slices k = 1 .. m} sum_B Re W_X(B (+) d, B)   on g~ = e^{-dtau K/2} G(tau_k) e^{+dtau K/2} after the updates
  * of slice k (dqmc_set_equal_time_correlators, dqmc_hip.h: the Wick forms of the time-displaced channels with G(tau,0) -> g~,
  * G(0,tau) -> g~ - 1, and T+- on g~); chargeSq / spinZSq / sdwSq / pairPlusSq / pairMinusSq, N, column qy L + qx, q = 2 pi (qx, qy) / L:
- *   S_X(q) = sum_d cos(q d) C_X(d).   Values of ONE sweep: averages and error bars over sweeps stay with the caller */
+ *   S_X(q) = sum_d cos(q d) C_X(d).   Values of ONE sweep; averages and error bars over sweeps: the measurement series below */
 int detsdw_get_observable_vector(detsdw_replica* r, int which, double* out);
 /* With timeDisplacedEverySlice: the Matsubara transforms of the every-slice observable `which`, formed on the device from the blocks
  * of the last measurement sweep (dqmc_measure_td_matsubara_host, dqmc_hip.h), n = 0 .. nfreq-1, 1 <= nfreq <= m, trapezoid weights
@@ -207,6 +207,37 @@ int detsdw_get_observable_vector(detsdw_replica* r, int which, double* out);
  *   rho_s = 1/8 Re [ Lxx(qx=1, qy=0) - Lxx(qx=0, qy=1) + Lyy(qx=0, qy=1) - Lyy(qx=1, qy=0) ] */
 int detsdw_get_matsubara(detsdw_replica* r, int which, int nfreq, double* out);
 int detsdw_get_matsubara_all(detsdw_replica* r, int which, int nfreq, double* out);
+/* Measurement series: bins over measurement sweeps and jackknife errors, kept on the device (dqmc_series_*, dqmc_hip.h).
+ * detsdw_series_begin opens one series per kernel context.  Its parts follow from the handle's options: the equal-time part with
+ * equalTimeCorrelators, one Matsubara part (nfreq frequencies, 1 <= nfreq <= m) per enabled every-slice channel; nfreq is ignored
+ * without timeDisplacedEverySlice; ParameterWrong if neither option is on.  While the series is open every detsdw_sweep(r, 1) ends
+ * with dqmc_series_add_sweep on every context (after binSize of them a bin closes); thermalisation sweeps and detsdw_sweep(r, 0) add
+ * nothing.  A measurement sweep on a full series (maxBins bins closed) fails with DQMC_EINVAL before it changes anything: read the
+ * series out and end it.
+ * flags: DETSDW_SERIES_NO_HOST_COPY -- while the series is open a measurement sweep does not copy the equal-time block to the host
+ * and forms no cosine sums there; DETSDW_OBS_CHARGECORR .. _PAIRMINUSSQ of detsdw_get_observable_vector then raise ParameterWrong
+ * (as the ...Fine observables do with timeDisplacedFineOnDevice).
+ * Readers (DQMC_EINVAL with fewer than two closed bins; definitions of mean, err and the derived quantities in dqmc_hip.h):
+ *   detsdw_series_stats: the selected chain; which = DETSDW_OBS_CHARGECORR .. _PAIRMINUSSQ: mean[N], err[N]; which = one of the
+ *     observables of detsdw_get_matsubara: mean[nfreq][N] complex as (re, im), err likewise with the errors of the real and the
+ *     imaginary part separately.  detsdw_series_stats_all: every chain in handle order, [nchains] x the same; one device call per
+ *     kernel context serves every `which` until the next bin closes.
+ *   detsdw_series_derived_all: what = DETSDW_SERIES_R_CHARGE .. _R_PAIRMINUS (correlation ratios) or DETSDW_SERIES_RHO_S, value[nchains]
+ *     and err[nchains]; ParameterWrong if the option the quantity needs is off.
+ *   detsdw_series_read_bins: closed bins first .. first + count - 1 of `which`, selected chain: out[count] x (N, or [nfreq][N] complex).
+ * detsdw_save_state does not store the series, and detsdw_load_state leaves an open series alone (bins closed before the load stay,
+ * the open bin keeps what it holds).  A series belongs to a chain SLOT of the handle, not to an exchange parameter: after a replica
+ * exchange that swaps parameters between slots the bins of a slot mix parameters unless the caller routes them. */
+enum { DETSDW_SERIES_NO_HOST_COPY = 1 };
+enum { DETSDW_SERIES_R_CHARGE = 0, DETSDW_SERIES_R_SPINZ = 1, DETSDW_SERIES_R_SDW = 2, DETSDW_SERIES_R_PAIRPLUS = 3,
+       DETSDW_SERIES_R_PAIRMINUS = 4, DETSDW_SERIES_RHO_S = 5 };
+int detsdw_series_begin(detsdw_replica* r, int binSize, int maxBins, int nfreq, int flags);
+int detsdw_series_info(detsdw_replica* r, int* binsClosed, int* sweepsInOpenBin, size_t* sampleLen);
+int detsdw_series_stats(detsdw_replica* r, int which, double* mean, double* err);
+int detsdw_series_stats_all(detsdw_replica* r, int which, double* mean, double* err);
+int detsdw_series_derived_all(detsdw_replica* r, int what, double* value, double* err);
+int detsdw_series_read_bins(detsdw_replica* r, int which, int first, int count, double* out);
+int detsdw_series_end(detsdw_replica* r);
 /* tau_j = j s dtau of the rows of greenKTauX / Y, j = 1 .. n-1: out[n-1] */
 int detsdw_get_tau_grid(detsdw_replica* r, double* out);
 /* With timeDisplacedEverySlice: tau_k = k dtau of the rows of the ...Fine observables, k = 0 .. m: out[m+1].  Interior rows k = 1 .. m-1

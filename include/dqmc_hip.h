@@ -415,6 +415,45 @@ int dqmc_measure_td_fine_read_host(dqmc_ctx* ctx, int channel, double* out);
  * identical bits.  The device result buffer lies outside the arena, is allocated on first use and freed with the context. */
 size_t dqmc_measure_td_matsubara_size(dqmc_ctx* ctx, int channel, int nfreq);
 int dqmc_measure_td_matsubara_host(dqmc_ctx* ctx, int channel, int nfreq, double* out);
+/* ---- measurement series: bins over sweeps and jackknife errors on the device (SDW model only) ----------
+ * One sample per measurement sweep, formed from the blocks above as they stand and accumulated into bins of bin_size sweeps; nothing is
+ * copied per sweep.  All run-time calls: dqmc_params stays byte for byte.
+ * parts (bit mask): bit 0 = the equal-time block (needs dqmc_measure_eq_accum_size != 0); bits 1 .. 4 = the Matsubara transform of
+ * every-slice channel 0 .. 3 (each needs that channel's fine block and 1 <= nfreq <= m; nfreq is ignored without such a bit).
+ * The sample of one chain has S doubles, the parts in mask order:
+ *   bit 0:  C_X(d) [5][N] then S_X(q) [5][N], X = charge, spinZ, sdw, pairPlus, pairMinus:  C_X(d) = sum / (double(N) count) (one
+ *           division), S_X(q) = sum_d cos(q d) C_X(d), column qy L + qx, the phase index reduced mod L in integers and the cos / sin of
+ *           2 pi j / L taken from a table computed on the host
+ *   bit 1 + channel:  what dqmc_measure_td_matsubara_host returns for (channel, nfreq), [component][nfreq][N] complex as (re, im) -- the
+ *           same kernel, launched with the sample buffer as its target
+ * dqmc_series_begin allocates, outside the arena, the sample [nb][S], the open bin [nb][S], the closed bins [max_bins][nb][S], the
+ * per-part flags and the result buffer of the statistics calls.  DQMC_EINVAL: empty or unknown mask, a missing block, bin_size < 1,
+ * max_bins < 2, a series already open, a Hubbard context, a lattice too large for the LDS of the Matsubara or sample kernel.
+ * dqmc_series_layout: where part (= bit number 0 .. 4) sits inside S.
+ * dqmc_series_add_sweep (all chains): forms the sample and adds it to the open bin, open += sample, in call order; the bin_size-th call
+ * writes closed[k] = open / bin_size and clears the open bin.  DQMC_EINVAL with no bin changed: the equal-time count of any chain or a
+ * fine row count of any chain and channel of the mask is < 1; max_bins bins are already closed (nothing is dropped silently, and there
+ * is no re-binning).  Reads the blocks only: G and every accumulator stay bit-identical.  dqmc_measure_reset does not touch the series.
+ * The call synchronises (it reads the flags back, nb doubles per part).
+ * dqmc_series_read_bins_host: closed bins first .. first + count - 1 of the selected chain, out[count][S] -- what a user persists.
+ * dqmc_series_stats_host (all chains, mean and err [nb][S]): over the B closed bins x_b (DQMC_EINVAL for B < 2),
+ *   mean = (1/B) sum_b x_b,   x_(b) = (B mean - x_b) / (B - 1),   err = sqrt((B - 1)/B sum_b (x_(b) - mean)^2).
+ * dqmc_series_derived_host (all chains, value and err [nb][6]; entries whose part is not in the mask are NaN):
+ *   0 .. 4:  R_X = 1 - 1/2 [S_X(Q + dx) + S_X(Q + dy)] / S_X(Q),  dx = (1,0), dy = (0,1) in units of 2 pi / L,  Q = (L/2, L/2) for
+ *            charge, spinZ, sdw and (0,0) for pairPlus, pairMinus
+ *   5:       rho_s = 1/8 Re [Lxx(1,0) - Lxx(0,1) + Lyy(0,1) - Lyy(1,0)] at frequency n = 0 of channel 3
+ *   value = f(mean);  err = the jackknife over theta_(b) = f(x_(b)), about the mean of the theta_(b).
+ * One writer per output element, fixed summation order (bins in index order), no atomics: bins and statistics do not depend on how
+ * chains are batched, and two statistics calls give identical bits.  dqmc_series_end frees the buffers; dqmc_destroy does it too. */
+enum { DQMC_SERIES_EQ = 1, DQMC_SERIES_MATS_G = 2, DQMC_SERIES_MATS_PAIR = 4, DQMC_SERIES_MATS_PH = 8, DQMC_SERIES_MATS_CURRENT = 16 };
+int dqmc_series_begin(dqmc_ctx* ctx, int bin_size, int max_bins, int nfreq, int parts);
+int dqmc_series_layout(dqmc_ctx* ctx, int part, size_t* offset, size_t* length);
+int dqmc_series_add_sweep(dqmc_ctx* ctx);
+int dqmc_series_info(dqmc_ctx* ctx, int* bins_closed, int* sweeps_in_open_bin, size_t* sample_len);
+int dqmc_series_read_bins_host(dqmc_ctx* ctx, int first, int count, double* out);
+int dqmc_series_stats_host(dqmc_ctx* ctx, double* mean, double* err);
+int dqmc_series_derived_host(dqmc_ctx* ctx, double* value, double* err);
+int dqmc_series_end(dqmc_ctx* ctx);
 /* for tests: the last propagated triple G(tau_k,0), G(0,tau_k), G(tau_k) of the selected chain and its slice k (after
  * dqmc_measure_timedisplaced_ends: the triple of row m) */
 int dqmc_get_green_td_fine_host(dqmc_ctx* ctx, dqmc_cplx* g_t0, dqmc_cplx* g_0t, dqmc_cplx* g_tt, int* slice);
