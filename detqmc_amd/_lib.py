@@ -224,6 +224,9 @@ SYMBOLS = [
     ("dqmc_series_begin", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("dqmc_series_layout", C.c_int, [_P, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     ("dqmc_series_add_sweep", C.c_int, [_P]),
+    ("dqmc_series_form_sample", C.c_int, [_P]),
+    ("dqmc_series_sample_device", C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    ("dqmc_series_accumulate", C.c_int, [_P, C.POINTER(C.c_void_p)]),
     ("dqmc_series_info", C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     ("dqmc_series_read_bins_host", C.c_int, [_P, C.c_int, C.c_int, _DP]),
     ("dqmc_series_stats_host", C.c_int, [_P, _DP, _DP]),
@@ -250,6 +253,8 @@ SYMBOLS = [
     ("detsdw_get_matsubara", C.c_int, [_P, C.c_int, C.c_int, _DP]),
     ("detsdw_get_matsubara_all", C.c_int, [_P, C.c_int, C.c_int, _DP]),
     ("detsdw_series_begin", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("detsdw_series_route", C.c_int, [_P, C.POINTER(C.c_int)]),
+    ("detsdw_series_get_route", C.c_int, [_P, C.POINTER(C.c_int)]),
     ("detsdw_series_info", C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     ("detsdw_series_stats", C.c_int, [_P, C.c_int, _DP, _DP]),
     ("detsdw_series_stats_all", C.c_int, [_P, C.c_int, _DP, _DP]),

@@ -105,11 +105,15 @@ struct dqmc_ctx {
     // dqmc_series_*: the measurement series.  Device buffers outside the arena, allocated by dqmc_series_begin and freed by dqmc_series_end
     // or with the context: sample [nb][S], open bin [nb][S], closed bins [max_bins][nb][S], the per-part flags [5][nb], the cos / sin table
     // and the result buffer of the statistics calls (mean, err [nb][S] each, then value, err [nb][6] each).  The counters live on the host.
+    // srctab [nb]: the source rows of dqmc_series_accumulate, filled from srchost before every launch; formed: the sample buffer holds
+    // the sample of a successful dqmc_series_form_sample that no dqmc_series_accumulate has consumed yet.
     struct Series {
-        bool open = false;
+        bool open = false, formed = false;
         int bin_size = 0, max_bins = 0, nfreq = 0, parts = 0, closed = 0, in_open = 0;
         size_t S = 0, off[5] = {0, 0, 0, 0, 0}, len[5] = {0, 0, 0, 0, 0};
         double *sample = nullptr, *openbin = nullptr, *bins = nullptr, *bad = nullptr, *trig = nullptr, *stat = nullptr;
+        const double** srctab = nullptr;
+        std::vector<const double*> srchost;
     } ser;
     SvdWork sw{};
     double hub_e_m2a = 1.0, hub_e_p2a = 1.0;  // Hubbard: exp(-+2 alpha) of weightRatioSingleFlip (dethubbard.cpp:866-867)
@@ -836,6 +840,7 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
 static void series_free(dqmc_ctx* c) {
     dqmc_ctx::Series& s = c->ser;
     for (double* q : {s.sample, s.openbin, s.bins, s.bad, s.trig, s.stat}) if (q) (void)hipFree(q);
+    if (s.srctab) (void)hipFree((void*)s.srctab);
     s = dqmc_ctx::Series{};
 }
 
@@ -2083,6 +2088,7 @@ extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nf
     if (e == hipSuccess) e = hipMalloc((void**)&r.bad, (size_t)5 * c->nb * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&r.trig, 2 * L * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&r.stat, (2 * n + (size_t)12 * c->nb) * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&r.srctab, (size_t)c->nb * sizeof(const double*));
     if (e == hipSuccess) e = hipMemsetAsync(r.sample, 0, n * sizeof(double), c->st);
     if (e == hipSuccess) e = hipMemsetAsync(r.openbin, 0, n * sizeof(double), c->st);
     if (e == hipSuccess) e = hipMemsetAsync(r.bins, 0, (size_t)max_bins * n * sizeof(double), c->st);
@@ -2120,41 +2126,101 @@ extern "C" int dqmc_series_info(dqmc_ctx* c, int* bins_closed, int* sweeps_in_op
     if (sample_len) *sample_len = c->ser.S;
     return DQMC_OK;
 }
-extern "C" int dqmc_series_add_sweep(dqmc_ctx* c) {
-    if (!c) return fail(DQMC_EINVAL, "null ctx");
+// The first half of dqmc_series_add_sweep: the sample of all chains from the blocks as they stand, and the flags read back.  `entry`
+// names the public call in the messages.
+static int series_form_sample(dqmc_ctx* c, const char* entry) {
     dqmc_ctx::Series& s = c->ser;
+    const std::string who(entry);
     if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
-    if (s.closed >= s.max_bins) return fail(DQMC_EINVAL, "dqmc_series_add_sweep: the series is full (max_bins bins are closed)");
+    if (s.closed >= s.max_bins) return fail(DQMC_EINVAL, who + ": the series is full (max_bins bins are closed)");
     (void)hipSetDevice(c->p.device);
-    // the sample of all chains from the blocks as they stand; the flags of the parts behind each other, [part][chain]
+    s.formed = false;                                       // the sample buffer is rewritten from here on
+    // the flags of the parts behind each other, [part][chain]
     int nparts = 0;
     {
         ProfScope ps(c, FAM_OTHER, 0);
         if (s.parts & 1) {
             if (!launch_series_eq_sample(c->lc, c->hm, c->eqacc, c->eqacc_n, s.trig, s.sample, s.S, s.off[0], s.bad))
-                return fail(DQMC_EINVAL, "dqmc_series_add_sweep: the lattice is too large for the equal-time sample kernel's LDS");
+                return fail(DQMC_EINVAL, who + ": the lattice is too large for the equal-time sample kernel's LDS");
             ++nparts;
         }
         for (int ch = 0; ch < 4; ++ch)
             if (s.parts & (2 << ch)) {
                 if (!launch_td_matsubara(c->lc, c->hm, c->facc[ch], ch, s.nfreq, ser_apbx(c), ser_apby(c), s.sample + s.off[1 + ch],
                                          s.bad + (size_t)nparts * c->nb, s.S))
-                    return fail(DQMC_EINVAL, "dqmc_series_add_sweep: the lattice is too large for the Matsubara kernel's LDS");
+                    return fail(DQMC_EINVAL, who + ": the lattice is too large for the Matsubara kernel's LDS");
                 ++nparts;
             }
         c->fam_launches[FAM_OTHER] += (uint64_t)nparts;
     }
-    { const int rc = finish(c, "dqmc_series_add_sweep"); if (rc != DQMC_OK) return rc; }
+    { const int rc = finish(c, entry); if (rc != DQMC_OK) return rc; }
     std::vector<double> bad((size_t)nparts * c->nb);
     HIPCHK(copy_sync(c, bad.data(), s.bad, bad.size() * sizeof(double), hipMemcpyDeviceToHost));
     for (double b : bad)
-        if (b != 0.0) return fail(DQMC_EINVAL, "dqmc_series_add_sweep: a block of the series has no sample (equal-time count or an every-slice row count < 1)");
+        if (b != 0.0) return fail(DQMC_EINVAL, who + ": a block of the series has no sample (equal-time count or an every-slice row count < 1)");
+    s.formed = true;
+    return DQMC_OK;
+}
+// true if [p, p + bytes) is device memory of `device`; a host address, an address the runtime does not know and a range that leaves its
+// allocation are all false, and no error stays pending
+static bool series_device_range(const void* p, size_t bytes, int device) {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (attr.type != hipMemoryTypeDevice || attr.device != device) return false;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    const uintptr_t lo = (uintptr_t)base, at = (uintptr_t)p;
+    return at >= lo && bytes <= size && at - lo <= size - bytes;
+}
+// The second half: open[s] += src[s][0 .. S) for every slot s of this context, src == nullptr: the context's own rows in order
+static int series_accumulate(dqmc_ctx* c, const double* const* src, const char* entry) {
+    dqmc_ctx::Series& s = c->ser;
+    const std::string who(entry);
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (!s.formed) return fail(DQMC_EINVAL, who + ": the context's sample is not formed (dqmc_series_form_sample)");
+    if (s.closed >= s.max_bins) return fail(DQMC_EINVAL, who + ": the series is full (max_bins bins are closed)");
+    (void)hipSetDevice(c->p.device);
     const size_t n = (size_t)c->nb * s.S;
     const int close = s.in_open + 1 == s.bin_size;
-    { ProfScope ps(c, FAM_OTHER, 1); launch_series_accum(c->lc, s.sample, s.openbin, s.bins + (size_t)s.closed * n, n, close, s.bin_size); }
-    { const int rc = finish(c, "dqmc_series_add_sweep"); if (rc != DQMC_OK) return rc; }
+    if (!src) {
+        ProfScope ps(c, FAM_OTHER, 1);
+        launch_series_accum(c->lc, s.sample, s.openbin, s.bins + (size_t)s.closed * n, n, close, s.bin_size);
+    } else {
+        for (int b = 0; b < c->nb; ++b) {
+            if (!src[b]) return fail(DQMC_EINVAL, who + ": a source row is null");
+            if (((uintptr_t)src[b] & (sizeof(double) - 1)) || !series_device_range(src[b], s.S * sizeof(double), c->p.device))
+                return fail(DQMC_EINVAL, who + ": a source row is not S doubles of device memory on the context's device");
+        }
+        s.srchost.assign(src, src + c->nb);                 // stays alive until the stream has taken the copy
+        HIPCHK(hipMemcpyAsync((void*)s.srctab, s.srchost.data(), (size_t)c->nb * sizeof(const double*), hipMemcpyHostToDevice, c->st));
+        ProfScope ps(c, FAM_OTHER, 1);
+        launch_series_accum_routed(c->lc, s.srctab, s.openbin, s.bins + (size_t)s.closed * n, s.S, close, s.bin_size);
+    }
+    s.formed = false;
+    { const int rc = finish(c, entry); if (rc != DQMC_OK) return rc; }
+    HIPCHK(hipStreamSynchronize(c->st));                    // the rows may belong to another context: they are free again on return
     if (close) { ++s.closed; s.in_open = 0; } else ++s.in_open;
     return DQMC_OK;
+}
+extern "C" int dqmc_series_form_sample(dqmc_ctx* c) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    return series_form_sample(c, "dqmc_series_form_sample");
+}
+extern "C" int dqmc_series_sample_device(dqmc_ctx* c, const double** rows, size_t* S) {
+    if (!c || !rows || !S) return fail(DQMC_EINVAL, "null argument");
+    if (!c->ser.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    *rows = c->ser.sample; *S = c->ser.S;
+    return DQMC_OK;
+}
+extern "C" int dqmc_series_accumulate(dqmc_ctx* c, const double* const* src) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    return series_accumulate(c, src, "dqmc_series_accumulate");
+}
+extern "C" int dqmc_series_add_sweep(dqmc_ctx* c) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    const int rc = series_form_sample(c, "dqmc_series_add_sweep");
+    return rc != DQMC_OK ? rc : series_accumulate(c, nullptr, "dqmc_series_add_sweep");
 }
 extern "C" int dqmc_series_read_bins_host(dqmc_ctx* c, int first, int count, double* out) {
     if (!c || !out) return fail(DQMC_EINVAL, "null argument");

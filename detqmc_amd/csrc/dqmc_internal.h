@@ -268,6 +268,7 @@ bool launch_series_eq_sample(const Launch& lc, const DevModel& hm, const double*
                              size_t S, size_t off, double* bad);
 size_t series_eq_sample_lds_bytes(int L);
 void launch_series_accum(const Launch& lc, const double* sample, double* open, double* closed, size_t n, int close, int bin_size);
+void launch_series_accum_routed(const Launch& lc, const double* const* src, double* open, double* closed, size_t S, int close, int bin_size);
 void launch_series_stats(const Launch& lc, const double* bins, size_t n, int B, double* mean, double* err);
 void launch_series_derived(const Launch& lc, const DevModel& hm, const double* bins, size_t S, int B, int nfreq, long long off_eq,
                            long long off_cur, double* value, double* err);

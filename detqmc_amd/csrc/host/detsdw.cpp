@@ -10,7 +10,9 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <algorithm>
 #include <exception>
+#include <numeric>
 #include <thread>
 
 namespace detqmc {
@@ -357,8 +359,24 @@ void DetSDW::sweep(bool takeMeasurements) {
     try {
         forEachGroup([this, feedSeries](Group& g) {
             sweep_skeleton(g, false);
-            if (feedSeries) { g.seriesStatsBins = 0; check(dqmc_series_add_sweep(g.ctx), "dqmc_series_add_sweep"); }
+            if (feedSeries) check(dqmc_series_form_sample(g.ctx), "dqmc_series_form_sample");
         });
+        // every group has formed its sample (a failure above: no group accumulates, every series as it was): slot s takes the sample of
+        // the chain the route sends there, from whichever group holds that chain
+        if (feedSeries) {
+            std::vector<const double*> src(ch_.size());
+            for (int c = 0; c < (int)ch_.size(); ++c) {
+                Group& gc = grp(c);
+                const double* rows = nullptr;
+                size_t S = 0;
+                check(dqmc_series_sample_device(gc.ctx, &rows, &S), "dqmc_series_sample_device");
+                src[(size_t)seriesRoute_[c]] = rows + (size_t)(c - gc.first) * S;
+            }
+            forEachGroup([&src](Group& g) {
+                g.seriesStatsBins = 0;
+                check(dqmc_series_accumulate(g.ctx, src.data() + g.first), "dqmc_series_accumulate");
+            });
+        }
     } catch (...) { off(); throw; }
     tdBlocksValid_ = measuringTD_;
     off();
@@ -715,11 +733,30 @@ void DetSDW::seriesBegin(int binSize, int maxBins, int nfreq, int flags) {
     }
     series_.open = true; series_.binSize = binSize; series_.maxBins = maxBins; series_.nfreq = (parts & ~DQMC_SERIES_EQ) ? nfreq : 0;
     series_.parts = parts; series_.flags = flags;
+    seriesRoute_.resize(ch_.size());
+    std::iota(seriesRoute_.begin(), seriesRoute_.end(), 0);
 }
 void DetSDW::seriesEnd() {
     if (!series_.open) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
     series_.open = false;
+    std::iota(seriesRoute_.begin(), seriesRoute_.end(), 0);
     for (auto& g : groups_) { g.seriesStatsBins = 0; g.seriesMean.clear(); g.seriesErr.clear(); check(dqmc_series_end(g.ctx), "dqmc_series_end"); }
+}
+void DetSDW::seriesRoute(const int* slotOfChain) {
+    if (!series_.open) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
+    if (!slotOfChain) throw ParameterWrong("detsdw_series_route: null route");
+    const int n = (int)ch_.size();
+    std::vector<char> seen((size_t)n, 0);
+    for (int c = 0; c < n; ++c) {
+        const int s = slotOfChain[c];
+        if (s < 0 || s >= n || seen[(size_t)s]) throw ParameterWrong("detsdw_series_route: the route must be a permutation of 0 .. nchains-1");
+        seen[(size_t)s] = 1;
+    }
+    seriesRoute_.assign(slotOfChain, slotOfChain + n);
+}
+void DetSDW::seriesGetRoute(int* out) const {
+    if (!series_.open) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
+    std::copy(seriesRoute_.begin(), seriesRoute_.end(), out);
 }
 void DetSDW::seriesInfo(int* binsClosed, int* sweepsInOpenBin, size_t* sampleLen) {
     if (!series_.open) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
@@ -1308,6 +1345,11 @@ extern "C" int detsdw_get_matsubara_all(detsdw_replica* r, int which, int nfreq,
 }
 extern "C" int detsdw_series_begin(detsdw_replica* r, int binSize, int maxBins, int nfreq, int flags) {
     RGUARD(r->impl->seriesBegin(binSize, maxBins, nfreq, flags))
+}
+extern "C" int detsdw_series_route(detsdw_replica* r, const int* slotOfChain) { RGUARD(r->impl->seriesRoute(slotOfChain)) }
+extern "C" int detsdw_series_get_route(detsdw_replica* r, int* out) {
+    if (!out) { g_host_err = "null argument"; return DQMC_EINVAL; }
+    RGUARD(r->impl->seriesGetRoute(out))
 }
 extern "C" int detsdw_series_info(detsdw_replica* r, int* binsClosed, int* sweepsInOpenBin, size_t* sampleLen) {
     RGUARD(r->impl->seriesInfo(binsClosed, sweepsInOpenBin, sampleLen))

@@ -64,6 +64,8 @@ public:
     // measurement series (include/detsdw_host.h): one dqmc_series per kernel context, fed by every sweep(true) while it is open
     void seriesBegin(int binSize, int maxBins, int nfreq, int flags);
     void seriesEnd();
+    void seriesRoute(const int* slotOfChain);      // permutation over all chains of the handle: the sample of chain c goes to slot slotOfChain[c]
+    void seriesGetRoute(int* out) const;
     void seriesInfo(int* binsClosed, int* sweepsInOpenBin, size_t* sampleLen);
     void seriesStats(int which, double* mean, double* err, int b = 0);
     void seriesStatsAll(int which, double* mean, double* err);
@@ -139,6 +141,7 @@ private:
     bool measuringTD_ = false;        // ... and G(tau_j, 0) after every interior advance (timeDisplacedMeasurements)
     bool tdBlocksValid_ = false;      // the device's time-displaced blocks are those of the last sweep, a measurement sweep
     struct { bool open = false; int binSize = 0, maxBins = 0, nfreq = 0, parts = 0, flags = 0; } series_;
+    std::vector<int> seriesRoute_;    // slotOfChain, the identity unless detsdw_series_route has set another
     bool seriesNoHostCopy() const { return series_.open && (series_.flags & DETSDW_SERIES_NO_HOST_COPY); }
     void seriesSlice(int which, int& part, size_t& offset, size_t& length);   // where `which` sits inside its part
     void seriesStatsOf(Group& g);                                             // fills the group's cache

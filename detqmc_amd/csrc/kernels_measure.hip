@@ -1013,6 +1013,22 @@ __global__ __launch_bounds__(256) void k_series_accum(const double* __restrict__
 void launch_series_accum(const Launch& lc, const double* sample, double* open, double* closed, size_t n, int close, int bin_size) {
     hipLaunchKernelGGL(k_series_accum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, lc.st, sample, open, closed, n, close, (double)bin_size);
 }
+// The same with the sample of slot s read through a pointer table: open[s] += src[s][0 .. S).  Grid (ceil(S / 256), nb), one thread per
+// element of a slot row; the rows src points to may lie in the sample buffer of another context of the same device.  The two operations
+// of k_series_accum in the same order, so the identity table gives its bits.
+__global__ __launch_bounds__(256) void k_series_accum_routed(const double* const* __restrict__ src, double* __restrict__ open,
+                                                             double* __restrict__ closed, size_t S, int close, double bin_size) {
+    const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= S) return;
+    const size_t i = (size_t)blockIdx.y * S + j;
+    const double o = open[i] + src[blockIdx.y][j];
+    if (close) { closed[i] = o / bin_size; open[i] = 0.0; }
+    else open[i] = o;
+}
+void launch_series_accum_routed(const Launch& lc, const double* const* src, double* open, double* closed, size_t S, int close, int bin_size) {
+    hipLaunchKernelGGL(k_series_accum_routed, dim3((unsigned)((S + 255) / 256), (unsigned)lc.nb), dim3(256), 0, lc.st, src, open, closed, S,
+                       close, (double)bin_size);
+}
 
 // Jackknife over the B closed bins, bins[b][n]: mean = (sum_b x_b) / B, x_(b) = (B mean - x_b) / (B - 1),
 // err = sqrt((B - 1) / B sum_b (x_(b) - mean)^2).  One thread per element, bins in index order.

@@ -308,6 +308,27 @@ class KernelContext:
         """one sample of every chain from the blocks as they stand, added to the open bin"""
         check(self.lib.dqmc_series_add_sweep(self.h))
 
+    def series_form_sample(self):
+        """the first half of series_add_sweep: the sample of every chain into the sample buffer; moves no counter, touches no bin"""
+        check(self.lib.dqmc_series_form_sample(self.h))
+
+    def series_sample_device(self):
+        """(device address of the sample buffer [nchains][S], S): chain b at address + 8 b S; valid while the series is open"""
+        rows, s = C.c_void_p(0), C.c_size_t(0)
+        check(self.lib.dqmc_series_sample_device(self.h, C.byref(rows), C.byref(s)))
+        return rows.value, s.value
+
+    def series_accumulate(self, ptrs=None):
+        """the second half: slot s adds the S doubles at device address ptrs[s] (one per chain of this context; rows of any context of the
+        same device whose sample is formed) to its open bin; None: the context's own rows in order"""
+        if ptrs is None:
+            check(self.lib.dqmc_series_accumulate(self.h, None))
+            return
+        ptrs = [int(p) if p else None for p in ptrs]
+        if len(ptrs) != self.nchains_total():
+            raise ValueError("series_accumulate needs one pointer per chain of the context")
+        check(self.lib.dqmc_series_accumulate(self.h, (C.c_void_p * len(ptrs))(*ptrs)))
+
     def series_info(self):
         """(bins closed, samples in the open bin, doubles per sample S)"""
         a, b, s = C.c_int(0), C.c_int(0), C.c_size_t(0)
@@ -851,6 +872,7 @@ class DetSDWBatch:
         self.h = h
         self.sub_batches = self.lib.detsdw_num_sub_batches(h)
         self._series_nfreq = 0
+        self._series_open = False
         self.chains = [DetSDW(_batch=self, _chain=b) for b in range(len(self.pars_list))]
 
     def __len__(self):
@@ -885,6 +907,24 @@ class DetSDWBatch:
         flags = 0 if host_copy else _lib.DETSDW_SERIES_NO_HOST_COPY
         check(self.lib.detsdw_series_begin(self.h, int(binSize), int(maxBins), int(nfreq), flags), host=True)
         self._series_nfreq = int(nfreq)
+        self._series_open = True
+
+    def series_is_open(self):
+        return self._series_open
+
+    def series_route(self, slots=None):
+        """slots = a permutation of range(len(self)): from now on the sample of chain c goes to series slot slots[c] (a slot is what the
+        series readers index; under replica exchange keep slots = the chains' control parameter indices and row s is parameter s).
+        May change between any two sweeps; series_end resets it to the identity.  No argument: returns the current route"""
+        n = len(self.chains)
+        if slots is None:
+            out = (C.c_int * n)()
+            check(self.lib.detsdw_series_get_route(self.h, out), host=True)
+            return list(out)
+        slots = [int(s) for s in slots]
+        if len(slots) != n:
+            raise ValueError("series_route needs one slot per chain of the batch")
+        check(self.lib.detsdw_series_route(self.h, (C.c_int * n)(*slots)), host=True)
 
     def series_info(self):
         """(bins closed, sweeps in the open bin, doubles per sample)"""
@@ -908,6 +948,7 @@ class DetSDWBatch:
 
     def series_end(self):
         check(self.lib.detsdw_series_end(self.h), host=True)
+        self._series_open = False
 
     def exchange_actions_device(self, device_ptr):
         """get_exchange_action_contribution of EVERY chain written to device memory (len(self) doubles at device_ptr, e.g.

@@ -99,10 +99,13 @@ class ReplicaAdapter:
         return self.rep.rand01()
 
 
-def replica_exchange_step(replica, state: ExchangeState, dist, device="cpu"):
+def replica_exchange_step(replica, state: ExchangeState, dist, device="cpu", route_series=False):
     """One replicaExchangeStep (src/detqmcpt.h:963-1118).  Collective: call on every rank.  `replica` is one
     replica or the list of this rank's replicas (state.n_local of them); dist = None runs a single process
-    (all replicas local, e.g. one GPU holding the whole ensemble).  Returns the new parameter index (list for a list)."""
+    (all replicas local, e.g. one GPU holding the whole ensemble).  Returns the new parameter index (list for a list).
+    route_series=True: when the local replicas are the chains of ONE DetSDWBatch with a measurement series open, the series is routed
+    by the new parameter indices (batch.series_route), so slot s of the series keeps collecting control parameter s.  Only for an
+    ensemble on one rank: ValueError if it spans ranks."""
     import torch
     single = not isinstance(replica, (list, tuple))
     reps = [replica] if single else list(replica)
@@ -110,6 +113,8 @@ def replica_exchange_step(replica, state: ExchangeState, dist, device="cpu"):
     if nl != state.n_local:
         raise ValueError("expected %d local replicas, got %d" % (state.n_local, nl))
     rank, world = (dist.get_rank(), dist.get_world_size()) if dist is not None else (0, 1)
+    if route_series and world > 1:
+        raise ValueError("route_series: the measurement series is routed within one DetSDWBatch only, not across %d ranks" % world)
     nproc = world * nl
     blobs_local = [r.get_control_data() for r in reps]
     nblob = len(blobs_local[0])
@@ -119,8 +124,9 @@ def replica_exchange_step(replica, state: ExchangeState, dist, device="cpu"):
     # the GPU straight into the send tensor of the all_gather (detsdw_exchange_actions_device) -- no device -> host -> device hop;
     # the control blobs (host-side statistics + the step-size state) travel in a second all_gather.
     batch = getattr(getattr(reps[0], "rep", None), "_batch", None)
-    on_device = (str(device) != "cpu" and batch is not None and len(batch) == nl
+    one_batch = (batch is not None and len(batch) == nl
                  and all(getattr(getattr(r, "rep", None), "_batch", None) is batch and r.rep._chain == b for b, r in enumerate(reps)))
+    on_device = str(device) != "cpu" and one_batch
     state.exchange_payload = "device" if on_device else "host"       # which path the last step took (drivers report it)
     if on_device:
         send_act = torch.empty(nl, dtype=torch.float64, device=device)
@@ -189,6 +195,8 @@ def replica_exchange_step(replica, state: ExchangeState, dist, device="cpu"):
         rep.set_exchange_parameter_value(state.controlParameterValues[new_index])
         rep.set_control_data(mine[8:])
         new_indices.append(new_index)
+    if route_series and one_batch and batch.series_is_open():
+        batch.series_route(new_indices)
     state.local_parameter_indices = new_indices
     state.local_current_parameter_index = new_indices[0]
     return new_indices[0] if single else new_indices

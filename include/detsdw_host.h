@@ -211,7 +211,7 @@ int detsdw_get_matsubara_all(detsdw_replica* r, int which, int nfreq, double* ou
  * detsdw_series_begin opens one series per kernel context.  Its parts follow from the handle's options: the equal-time part with
  * equalTimeCorrelators, one Matsubara part (nfreq frequencies, 1 <= nfreq <= m) per enabled every-slice channel; nfreq is ignored
  * without timeDisplacedEverySlice; ParameterWrong if neither option is on.  While the series is open every detsdw_sweep(r, 1) ends
- * with dqmc_series_add_sweep on every context (after binSize of them a bin closes); thermalisation sweeps and detsdw_sweep(r, 0) add
+ * with one sample of every chain added to the series (after binSize of them a bin closes); thermalisation sweeps and detsdw_sweep(r, 0) add
  * nothing.  A measurement sweep on a full series (maxBins bins closed) fails with DQMC_EINVAL before it changes anything: read the
  * series out and end it.
  * flags: DETSDW_SERIES_NO_HOST_COPY -- while the series is open a measurement sweep does not copy the equal-time block to the host
@@ -226,12 +226,27 @@ int detsdw_get_matsubara_all(detsdw_replica* r, int which, int nfreq, double* ou
  *     and err[nchains]; ParameterWrong if the option the quantity needs is off.
  *   detsdw_series_read_bins: closed bins first .. first + count - 1 of `which`, selected chain: out[count] x (N, or [nfreq][N] complex).
  * detsdw_save_state does not store the series, and detsdw_load_state leaves an open series alone (bins closed before the load stay,
- * the open bin keeps what it holds).  A series belongs to a chain SLOT of the handle, not to an exchange parameter: after a replica
- * exchange that swaps parameters between slots the bins of a slot mix parameters unless the caller routes them. */
+ * the open bin keeps what it holds; neither stores the route).
+ * Slots and the route: a SLOT is a row of the series buffers (open bin, closed bins, statistics), indexed like a chain; the index of
+ * every reader above -- the selected chain, or the position in an ..._all result -- means the slot.  A measurement sweep adds the sample
+ * of chain c to slot slotOfChain[c]; the route is the identity after detsdw_series_begin, which is a series per chain.  Under replica
+ * exchange within the handle a chain's control parameter changes: keep the route equal to the chains' parameter indices
+ * (detsdw_series_route after every exchange step) and row s is control parameter s, whichever chain measured it.
+ *   detsdw_series_route: slotOfChain[nchains] over ALL chains of the handle, whatever chain is selected; ParameterWrong unless it is a
+ *     permutation of 0 .. nchains-1, DQMC_EINVAL when no series is open.  It may be called between any two sweeps, in mid-bin too: the
+ *     open bin of a slot then goes on with the samples of another chain.  detsdw_series_end resets it to the identity.
+ *   detsdw_series_get_route: the stored route, out[nchains].
+ * A measurement sweep runs in two phases: every kernel context sweeps and forms its sample (dqmc_series_form_sample); when all have
+ * finished, every context accumulates its slots from the rows of whichever contexts hold the routed chains (dqmc_series_accumulate;
+ * this is how the ordering rule of dqmc_hip.h is kept).  If a context fails in the first phase no context accumulates and every series
+ * is as it was; the sweep itself has happened.  With the identity the bins are bit for bit those of a series without a route, for any
+ * number of sub-batches.  The route changes no trajectory and no observable of a sweep.  Routing across handles (GPUs) is not provided. */
 enum { DETSDW_SERIES_NO_HOST_COPY = 1 };
 enum { DETSDW_SERIES_R_CHARGE = 0, DETSDW_SERIES_R_SPINZ = 1, DETSDW_SERIES_R_SDW = 2, DETSDW_SERIES_R_PAIRPLUS = 3,
        DETSDW_SERIES_R_PAIRMINUS = 4, DETSDW_SERIES_RHO_S = 5 };
 int detsdw_series_begin(detsdw_replica* r, int binSize, int maxBins, int nfreq, int flags);
+int detsdw_series_route(detsdw_replica* r, const int* slotOfChain);
+int detsdw_series_get_route(detsdw_replica* r, int* out);
 int detsdw_series_info(detsdw_replica* r, int* binsClosed, int* sweepsInOpenBin, size_t* sampleLen);
 int detsdw_series_stats(detsdw_replica* r, int which, double* mean, double* err);
 int detsdw_series_stats_all(detsdw_replica* r, int which, double* mean, double* err);

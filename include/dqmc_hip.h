@@ -434,7 +434,25 @@ int dqmc_measure_td_matsubara_host(dqmc_ctx* ctx, int channel, int nfreq, double
  * writes closed[k] = open / bin_size and clears the open bin.  DQMC_EINVAL with no bin changed: the equal-time count of any chain or a
  * fine row count of any chain and channel of the mask is < 1; max_bins bins are already closed (nothing is dropped silently, and there
  * is no re-binning).  Reads the blocks only: G and every accumulator stay bit-identical.  dqmc_measure_reset does not touch the series.
- * The call synchronises (it reads the flags back, nb doubles per part).
+ * The call synchronises (it reads the flags back, nb doubles per part).  It is dqmc_series_form_sample followed by
+ * dqmc_series_accumulate(ctx, NULL):
+ * A SLOT is a row of the series buffers (open bin, closed bins, statistics), indexed like a chain.  The two halves let a caller add the
+ * sample of any chain of the device to any slot -- under replica exchange, the sample of the chain that holds control parameter s to slot s.
+ * dqmc_series_form_sample (all chains): the sample of every chain from the blocks as they stand into the sample buffer, and the flags read
+ * back.  The DQMC_EINVALs of dqmc_series_add_sweep: no series open, max_bins bins closed, a lattice too large for the LDS, a block without
+ * a sample.  On success the context's sample is marked as formed; no counter moves and no bin is touched.  A second call forms the
+ * sample again.
+ * dqmc_series_sample_device: the device address of the sample buffer [nb][S] (chain b at *rows + b S) and S; valid from
+ * dqmc_series_begin to dqmc_series_end.
+ * dqmc_series_accumulate: src = host array of nb device pointers; slot s of this context does open[s] += src[s][0 .. S), and on the
+ * bin_size-th call closed[k][s] = open[s] / bin_size with open[s] cleared -- the operations of dqmc_series_add_sweep, the same bits.
+ * src == NULL: the context's own rows in order.  DQMC_EINVAL, with every bin and counter as it was and nothing launched: the context's
+ * sample is not formed; an entry is null; an entry is not S doubles of device memory on the context's device (hipPointerGetAttributes
+ * and the allocation's range: a wrong pointer is an error code, never a launch).  Clears the formed mark, moves the counters as
+ * dqmc_series_add_sweep does and returns after the stream has finished, so every sample buffer it read may be rewritten afterwards.
+ * Ordering rule: a context may read another context's sample rows only between that context's successful dqmc_series_form_sample and
+ * its next dqmc_series_form_sample.  Both calls synchronise their own stream before they return; keeping to the rule across contexts
+ * (and host threads) is the caller's job.  The readers below are indexed by slot.
  * dqmc_series_read_bins_host: closed bins first .. first + count - 1 of the selected chain, out[count][S] -- what a user persists.
  * dqmc_series_stats_host (all chains, mean and err [nb][S]): over the B closed bins x_b (DQMC_EINVAL for B < 2),
  *   mean = (1/B) sum_b x_b,   x_(b) = (B mean - x_b) / (B - 1),   err = sqrt((B - 1)/B sum_b (x_(b) - mean)^2).
@@ -449,6 +467,9 @@ enum { DQMC_SERIES_EQ = 1, DQMC_SERIES_MATS_G = 2, DQMC_SERIES_MATS_PAIR = 4, DQ
 int dqmc_series_begin(dqmc_ctx* ctx, int bin_size, int max_bins, int nfreq, int parts);
 int dqmc_series_layout(dqmc_ctx* ctx, int part, size_t* offset, size_t* length);
 int dqmc_series_add_sweep(dqmc_ctx* ctx);
+int dqmc_series_form_sample(dqmc_ctx* ctx);
+int dqmc_series_sample_device(dqmc_ctx* ctx, const double** rows, size_t* S);
+int dqmc_series_accumulate(dqmc_ctx* ctx, const double* const* src);
 int dqmc_series_info(dqmc_ctx* ctx, int* bins_closed, int* sweeps_in_open_bin, size_t* sample_len);
 int dqmc_series_read_bins_host(dqmc_ctx* ctx, int first, int count, double* out);
 int dqmc_series_stats_host(dqmc_ctx* ctx, double* mean, double* err);
