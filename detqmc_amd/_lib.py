@@ -22,6 +22,7 @@ DQMC_TD_EVERY_SLICE = 0x100     # flag bit of dqmc_params.timedisplaced
 DETSDW_TD_EVERY_SLICE = 0x100   # flag bit of detsdw_params.timeDisplacedMeasurements
 DETSDW_TD_FINE_ON_DEVICE = 0x200  # flag bit of detsdw_params.timeDisplacedMeasurements: the fine blocks stay on the device
 DETSDW_OBS_FINE = 0x100         # flag bit of the observable index: the every-slice twin
+DQMC_SERIES_AUTO_REBIN, DQMC_SERIES_TRACK_VARIANCE = 1, 2   # flags of dqmc_series_configure / detsdw_series_configure
 DETSDW_SERIES_NO_HOST_COPY = 1    # flag of detsdw_series_begin: no equal-time block copy per measurement sweep while the series is open
 DETSDW_FM_EQ_CORRELATORS = 0x100  # flag bit of detsdw_params.fermionMeasurements: equal-time charge / spin / SDW / pairing correlators
 
@@ -66,6 +67,12 @@ class dqmc_update_state(C.Structure):
                 ("rot_runningAverage", C.c_double), ("rot_values", C.c_double * 100),
                 ("scl_runningAverage", C.c_double), ("scl_values", C.c_double * 100),
                 ("rot_samplesAdded", C.c_int32), ("rot_head", C.c_int32), ("scl_samplesAdded", C.c_int32), ("scl_head", C.c_int32)]
+
+
+class dqmc_series_state(C.Structure):
+    _fields_ = [("bin_size", C.c_int), ("max_bins", C.c_int), ("nfreq", C.c_int), ("parts", C.c_int), ("flags", C.c_int),
+                ("bins_closed", C.c_int), ("sweeps_in_open_bin", C.c_int), ("nb", C.c_int),
+                ("samples", C.c_longlong), ("rebins", C.c_longlong), ("sample_len", C.c_size_t)]
 
 
 class dqmc_profile(C.Structure):
@@ -232,6 +239,12 @@ SYMBOLS = [
     ("dqmc_series_stats_host", C.c_int, [_P, _DP, _DP]),
     ("dqmc_series_derived_host", C.c_int, [_P, _DP, _DP]),
     ("dqmc_series_end", C.c_int, [_P]),
+    ("dqmc_series_configure", C.c_int, [_P, C.c_int]),
+    ("dqmc_series_get_state", C.c_int, [_P, C.POINTER(dqmc_series_state)]),
+    ("dqmc_series_rebin", C.c_int, [_P]),
+    ("dqmc_series_binning_host", C.c_int, [_P, C.c_int, _DP, _DP]),
+    ("dqmc_series_export_host", C.c_int, [_P, _DP, C.c_size_t]),
+    ("dqmc_series_import_host", C.c_int, [_P, C.POINTER(dqmc_series_state), _DP, C.c_size_t]),
     ("dqmc_get_green_td_fine_host", C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_int)]),
     ("dqmc_td_fine_propagate", C.c_int, [_P, C.c_int, C.c_int]),     # tests only: exported, not declared in include/dqmc_hip.h
     ("dqmc_profile_enable", C.c_int, [_P, C.c_int]),
@@ -261,6 +274,13 @@ SYMBOLS = [
     ("detsdw_series_derived_all", C.c_int, [_P, C.c_int, _DP, _DP]),
     ("detsdw_series_read_bins", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _DP]),
     ("detsdw_series_end", C.c_int, [_P]),
+    ("detsdw_series_configure", C.c_int, [_P, C.c_int]),
+    ("detsdw_series_rebin", C.c_int, [_P]),
+    ("detsdw_series_get_state", C.c_int, [_P, C.POINTER(dqmc_series_state)]),
+    ("detsdw_series_binning", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
+    ("detsdw_series_binning_all", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
+    ("detsdw_series_save", C.c_int, [_P, C.c_char_p]),
+    ("detsdw_series_load", C.c_int, [_P, C.c_char_p]),
     ("detsdw_get_tau_grid", C.c_int, [_P, _DP]),
     ("detsdw_get_tau_grid_fine", C.c_int, [_P, _DP]),
     ("detsdw_get_phi", C.c_int, [_P, _DP]),

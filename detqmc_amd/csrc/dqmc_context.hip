@@ -110,8 +110,13 @@ struct dqmc_ctx {
     struct Series {
         bool open = false, formed = false;
         int bin_size = 0, max_bins = 0, nfreq = 0, parts = 0, closed = 0, in_open = 0;
+        int flags = 0;                                        // DQMC_SERIES_AUTO_REBIN | DQMC_SERIES_TRACK_VARIANCE (dqmc_series_configure)
+        long long samples = 0, rebins = 0;                    // accumulates since begin / merges of neighbouring bins so far
         size_t S = 0, off[5] = {0, 0, 0, 0, 0}, len[5] = {0, 0, 0, 0, 0};
         double *sample = nullptr, *openbin = nullptr, *bins = nullptr, *bad = nullptr, *trig = nullptr, *stat = nullptr;
+        double *var = nullptr;                                // running mean w [nb][S], then m2 [nb][S]: allocated with TRACK_VARIANCE
+        double *binning = nullptr;                            // result of dqmc_series_binning_host, err then tau [levels][nb][S] each,
+        size_t binning_cap = 0;                               // allocated on first use and grown on demand (doubles)
         const double** srctab = nullptr;
         std::vector<const double*> srchost;
     } ser;
@@ -839,7 +844,7 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
 
 static void series_free(dqmc_ctx* c) {
     dqmc_ctx::Series& s = c->ser;
-    for (double* q : {s.sample, s.openbin, s.bins, s.bad, s.trig, s.stat}) if (q) (void)hipFree(q);
+    for (double* q : {s.sample, s.openbin, s.bins, s.bad, s.trig, s.stat, s.var, s.binning}) if (q) (void)hipFree(q);
     if (s.srctab) (void)hipFree((void*)s.srctab);
     s = dqmc_ctx::Series{};
 }
@@ -2173,6 +2178,18 @@ static bool series_device_range(const void* p, size_t bytes, int device) {
     const uintptr_t lo = (uintptr_t)base, at = (uintptr_t)p;
     return at >= lo && bytes <= size && at - lo <= size - bytes;
 }
+// closed[k] = (closed[2k] + closed[2k+1]) * 0.5 for all slots; the caller has checked an even number of closed bins and the bin size
+constexpr int SERIES_MAX_BIN_SIZE = 1 << 29;                // the largest bin_size that can still double: the result stays within 2^30
+static int series_rebin(dqmc_ctx* c, const char* entry) {
+    dqmc_ctx::Series& s = c->ser;
+    if (s.closed > 0) {
+        { ProfScope ps(c, FAM_OTHER, 1); launch_series_rebin(c->lc, s.bins, (size_t)c->nb * s.S, s.closed / 2); }
+        { const int rc = finish(c, entry); if (rc != DQMC_OK) return rc; }
+        HIPCHK(hipStreamSynchronize(c->st));
+    }
+    s.closed /= 2; s.bin_size *= 2; ++s.rebins;
+    return DQMC_OK;
+}
 // The second half: open[s] += src[s][0 .. S) for every slot s of this context, src == nullptr: the context's own rows in order
 static int series_accumulate(dqmc_ctx* c, const double* const* src, const char* entry) {
     dqmc_ctx::Series& s = c->ser;
@@ -2197,10 +2214,18 @@ static int series_accumulate(dqmc_ctx* c, const double* const* src, const char* 
         ProfScope ps(c, FAM_OTHER, 1);
         launch_series_accum_routed(c->lc, s.srctab, s.openbin, s.bins + (size_t)s.closed * n, s.S, close, s.bin_size);
     }
+    if (s.flags & DQMC_SERIES_TRACK_VARIANCE) {             // the same rows once more, into the running mean and m2 of the slot
+        ProfScope ps(c, FAM_OTHER, 1);
+        launch_series_welford(c->lc, s.sample, src ? s.srctab : nullptr, s.var, s.var + n, s.S, s.samples + 1);
+    }
     s.formed = false;
     { const int rc = finish(c, entry); if (rc != DQMC_OK) return rc; }
     HIPCHK(hipStreamSynchronize(c->st));                    // the rows may belong to another context: they are free again on return
+    ++s.samples;
     if (close) { ++s.closed; s.in_open = 0; } else ++s.in_open;
+    // auto re-binning: the close that fills the series merges neighbouring bins before the call returns, so the series is never
+    // observed full; if bin_size cannot double any more the series becomes full as it does without the flag
+    if (close && (s.flags & DQMC_SERIES_AUTO_REBIN) && s.closed == s.max_bins && s.bin_size <= SERIES_MAX_BIN_SIZE) return series_rebin(c, entry);
     return DQMC_OK;
 }
 extern "C" int dqmc_series_form_sample(dqmc_ctx* c) {
@@ -2263,6 +2288,127 @@ extern "C" int dqmc_series_derived_host(dqmc_ctx* c, double* value, double* err)
     { const int rc = finish(c, "dqmc_series_derived_host"); if (rc != DQMC_OK) return rc; }
     HIPCHK(copy_sync(c, value, dv, nd * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHK(copy_sync(c, err, dv + nd, nd * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+
+// ---- long runs: options, re-binning, binning analysis, export / import (dqmc_hip.h) ----
+static bool series_flags_valid(int flags, int max_bins) {
+    if (flags & ~(DQMC_SERIES_AUTO_REBIN | DQMC_SERIES_TRACK_VARIANCE)) return false;
+    return !(flags & DQMC_SERIES_AUTO_REBIN) || (max_bins >= 4 && max_bins % 2 == 0);
+}
+// w and m2 [nb][S], zeroed; kept until the series ends once they exist
+static hipError_t series_alloc_variance(dqmc_ctx* c) {
+    dqmc_ctx::Series& s = c->ser;
+    const size_t bytes = 2 * (size_t)c->nb * s.S * sizeof(double);
+    if (!s.var) {
+        const hipError_t e = hipMalloc((void**)&s.var, bytes);
+        if (e != hipSuccess) { s.var = nullptr; return e; }
+    }
+    return hipMemsetAsync(s.var, 0, bytes, c->st);
+}
+extern "C" int dqmc_series_configure(dqmc_ctx* c, int flags) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    dqmc_ctx::Series& s = c->ser;
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (s.samples || s.closed || s.in_open) return fail(DQMC_EINVAL, "dqmc_series_configure: the series is not empty any more");
+    if (!series_flags_valid(flags, s.max_bins))
+        return fail(DQMC_EINVAL, "dqmc_series_configure: unknown flag, or DQMC_SERIES_AUTO_REBIN with max_bins odd or below 4");
+    (void)hipSetDevice(c->p.device);
+    if (flags & DQMC_SERIES_TRACK_VARIANCE) {
+        HIPCHK(series_alloc_variance(c));
+        HIPCHK(hipStreamSynchronize(c->st));
+    }
+    s.flags = flags;
+    return DQMC_OK;
+}
+static void series_fill_state(const dqmc_ctx* c, dqmc_series_state* st) {
+    const dqmc_ctx::Series& s = c->ser;
+    std::memset(st, 0, sizeof(*st));
+    st->bin_size = s.bin_size; st->max_bins = s.max_bins; st->nfreq = s.nfreq; st->parts = s.parts; st->flags = s.flags;
+    st->bins_closed = s.closed; st->sweeps_in_open_bin = s.in_open; st->nb = c->nb;
+    st->samples = s.samples; st->rebins = s.rebins; st->sample_len = s.S;
+}
+extern "C" int dqmc_series_get_state(dqmc_ctx* c, dqmc_series_state* st) {
+    if (!c || !st) return fail(DQMC_EINVAL, "null argument");
+    if (!c->ser.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    series_fill_state(c, st);
+    return DQMC_OK;
+}
+extern "C" int dqmc_series_rebin(dqmc_ctx* c) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    dqmc_ctx::Series& s = c->ser;
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (s.closed % 2) return fail(DQMC_EINVAL, "dqmc_series_rebin: the number of closed bins is odd");
+    if (s.bin_size > SERIES_MAX_BIN_SIZE) return fail(DQMC_EINVAL, "dqmc_series_rebin: bin_size cannot double any more");
+    (void)hipSetDevice(c->p.device);
+    return series_rebin(c, "dqmc_series_rebin");
+}
+extern "C" int dqmc_series_binning_host(dqmc_ctx* c, int levels, double* err, double* tau) {
+    if (!c || !err) return fail(DQMC_EINVAL, "null argument");
+    dqmc_ctx::Series& s = c->ser;
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (levels < 1 || levels > 12) return fail(DQMC_EINVAL, "dqmc_series_binning_host: levels must be in 1..12");
+    if ((s.closed >> (levels - 1)) < 2) return fail(DQMC_EINVAL, "dqmc_series_binning_host: the top level needs at least two merged bins");
+    if (tau && !(s.flags & DQMC_SERIES_TRACK_VARIANCE)) return fail(DQMC_EINVAL, "dqmc_series_binning_host: tau needs DQMC_SERIES_TRACK_VARIANCE");
+    if (tau && s.samples < 2) return fail(DQMC_EINVAL, "dqmc_series_binning_host: tau needs at least two samples");
+    (void)hipSetDevice(c->p.device);
+    const size_t n = (size_t)c->nb * s.S, need = 2 * (size_t)levels * n;
+    if (need > s.binning_cap) {
+        HIPCHK(hipStreamSynchronize(c->st));
+        if (s.binning) { (void)hipFree(s.binning); s.binning = nullptr; s.binning_cap = 0; }
+        HIPCHK(hipMalloc((void**)&s.binning, need * sizeof(double)));
+        s.binning_cap = need;
+    }
+    double* derr = s.binning;
+    double* dtau = tau ? s.binning + (size_t)levels * n : nullptr;
+    {
+        ProfScope ps(c, FAM_OTHER, 1);
+        launch_series_binning(c->lc, s.bins, tau ? s.var + n : nullptr, n, s.closed, levels, s.bin_size, s.samples, derr, dtau);
+    }
+    { const int rc = finish(c, "dqmc_series_binning_host"); if (rc != DQMC_OK) return rc; }
+    HIPCHK(copy_sync(c, err, derr, (size_t)levels * n * sizeof(double), hipMemcpyDeviceToHost));
+    if (tau) HIPCHK(copy_sync(c, tau, dtau, (size_t)levels * n * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+static size_t series_export_len(size_t n, int closed, int flags) {
+    return ((size_t)closed + 1 + ((flags & DQMC_SERIES_TRACK_VARIANCE) ? 2 : 0)) * n;
+}
+extern "C" int dqmc_series_export_host(dqmc_ctx* c, double* out, size_t len) {
+    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
+    const dqmc_ctx::Series& s = c->ser;
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    const size_t n = (size_t)c->nb * s.S;
+    if (len != series_export_len(n, s.closed, s.flags)) return fail(DQMC_EINVAL, "dqmc_series_export_host: len is not the size of the series");
+    (void)hipSetDevice(c->p.device);
+    HIPCHK(hipStreamSynchronize(c->st));
+    const size_t nc = (size_t)s.closed * n;
+    if (nc) HIPCHK(copy_sync(c, out, s.bins, nc * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(c, out + nc, s.openbin, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (s.flags & DQMC_SERIES_TRACK_VARIANCE) HIPCHK(copy_sync(c, out + nc + n, s.var, 2 * n * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+extern "C" int dqmc_series_import_host(dqmc_ctx* c, const dqmc_series_state* st, const double* in, size_t len) {
+    if (!c || !st || !in) return fail(DQMC_EINVAL, "null argument");
+    dqmc_ctx::Series& s = c->ser;
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (st->nb != c->nb || st->sample_len != s.S || st->parts != s.parts || st->nfreq != s.nfreq)
+        return fail(DQMC_EINVAL, "dqmc_series_import_host: chains, sample length, parts or nfreq differ from the open series");
+    if (st->bins_closed < 0 || st->bins_closed >= s.max_bins) return fail(DQMC_EINVAL, "dqmc_series_import_host: bins_closed must be below max_bins of the open series");
+    if (st->bin_size < 1 || st->sweeps_in_open_bin < 0 || st->sweeps_in_open_bin >= st->bin_size)
+        return fail(DQMC_EINVAL, "dqmc_series_import_host: sweeps_in_open_bin must be below bin_size");
+    if (!series_flags_valid(st->flags, s.max_bins)) return fail(DQMC_EINVAL, "dqmc_series_import_host: the flags are not valid for max_bins of the open series");
+    if (st->samples < 0 || st->rebins < 0) return fail(DQMC_EINVAL, "dqmc_series_import_host: negative counter");
+    const size_t n = (size_t)c->nb * s.S;
+    if (len != series_export_len(n, st->bins_closed, st->flags)) return fail(DQMC_EINVAL, "dqmc_series_import_host: len is not the size of the series");
+    (void)hipSetDevice(c->p.device);
+    HIPCHK(hipStreamSynchronize(c->st));
+    if ((st->flags & DQMC_SERIES_TRACK_VARIANCE) && !s.var) HIPCHK(series_alloc_variance(c));   // nothing of the series has changed yet
+    const size_t nc = (size_t)st->bins_closed * n;
+    if (nc) HIPCHK(copy_sync(c, s.bins, in, nc * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(copy_sync(c, s.openbin, in + nc, n * sizeof(double), hipMemcpyHostToDevice));
+    if (st->flags & DQMC_SERIES_TRACK_VARIANCE) HIPCHK(copy_sync(c, s.var, in + nc + n, 2 * n * sizeof(double), hipMemcpyHostToDevice));
+    s.bin_size = st->bin_size; s.flags = st->flags; s.closed = st->bins_closed; s.in_open = st->sweeps_in_open_bin;
+    s.samples = st->samples; s.rebins = st->rebins; s.formed = false;
     return DQMC_OK;
 }
 

@@ -272,6 +272,13 @@ void launch_series_accum_routed(const Launch& lc, const double* const* src, doub
 void launch_series_stats(const Launch& lc, const double* bins, size_t n, int B, double* mean, double* err);
 void launch_series_derived(const Launch& lc, const DevModel& hm, const double* bins, size_t S, int B, int nfreq, long long off_eq,
                            long long off_cur, double* value, double* err);
+// long runs: in-place merge of neighbouring closed bins (half = pairs to merge), Welford's update of (w, m2) [nb][S] with the sample rows
+// (src == nullptr: the rows of `sample` in order; cnt = samples including this one), and the binning analysis err / tau [levels][n]
+// (tau == nullptr: errors only; m2 is read only with tau)
+void launch_series_rebin(const Launch& lc, double* bins, size_t n, int half);
+void launch_series_welford(const Launch& lc, const double* sample, const double* const* src, double* w, double* m2, size_t S, long long cnt);
+void launch_series_binning(const Launch& lc, const double* bins, const double* m2, size_t n, int B, int levels, int bin_size,
+                           long long samples, double* err, double* tau);
 // time-displaced pairing block: count[n-1], then per boundary j = 1 .. n-1 the sums over B of Re T+(B (+) d, B) [N] and Re T-(B (+) d, B) [N]
 void launch_measure_td_pair(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc, int row, int rows);
 size_t measure_td_pair_doubles(int N, int n);

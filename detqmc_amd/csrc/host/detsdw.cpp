@@ -724,7 +724,7 @@ void DetSDW::seriesBegin(int binSize, int maxBins, int nfreq, int flags) {
                 check(dqmc_set_equal_time_correlators(g.ctx, 0), "dqmc_set_equal_time_correlators");
             }
             check(dqmc_series_begin(g.ctx, binSize, maxBins, nfreq, parts), "dqmc_series_begin");
-            g.seriesStatsBins = 0;
+            seriesDropCaches(g);
             ++opened;
         }
     } catch (...) {
@@ -740,7 +740,11 @@ void DetSDW::seriesEnd() {
     if (!series_.open) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
     series_.open = false;
     std::iota(seriesRoute_.begin(), seriesRoute_.end(), 0);
-    for (auto& g : groups_) { g.seriesStatsBins = 0; g.seriesMean.clear(); g.seriesErr.clear(); check(dqmc_series_end(g.ctx), "dqmc_series_end"); }
+    for (auto& g : groups_) {
+        g.seriesStatsBins = 0; g.seriesMean.clear(); g.seriesErr.clear();
+        g.seriesBinLevels = 0; g.seriesBinErr.clear(); g.seriesBinTau.clear();
+        check(dqmc_series_end(g.ctx), "dqmc_series_end");
+    }
 }
 void DetSDW::seriesRoute(const int* slotOfChain) {
     if (!series_.open) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
@@ -836,6 +840,65 @@ void DetSDW::seriesReadBins(int which, int first, int count, double* out, int b)
     std::vector<double> buf((size_t)count * S);
     check(dqmc_series_read_bins_host(ctx_, first, count, buf.data()), "dqmc_series_read_bins_host");
     for (int i = 0; i < count; ++i) std::memcpy(out + (size_t)i * len, &buf[(size_t)i * S + off], len * sizeof(double));
+}
+
+// ---- the series over a long run (include/detsdw_host.h) ----
+// All kernel contexts accumulate in the same sweeps, so their options and counters agree and they re-bin in the same sweep: what group 0
+// accepts every group accepts.
+void DetSDW::seriesConfigure(int flags) {
+    if (!series_.open) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
+    for (auto& g : groups_) check(dqmc_series_configure(g.ctx, flags), "dqmc_series_configure");
+}
+void DetSDW::seriesGetState(dqmc_series_state& out) {
+    if (!series_.open) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
+    check(dqmc_series_get_state(groups_[0].ctx, &out), "dqmc_series_get_state");
+    out.nb = (int)ch_.size();
+}
+void DetSDW::seriesRebin() {
+    if (!series_.open) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
+    for (auto& g : groups_) {
+        check(dqmc_series_rebin(g.ctx), "dqmc_series_rebin");
+        seriesDropCaches(g);                       // the number of closed bins repeats after a re-bin: the cached statistics are stale
+    }
+}
+void DetSDW::seriesBinningOf(Group& g, int levels, bool withTau) {
+    if (levels < 1 || levels > 12) throw ParameterWrong("detsdw_series_binning: levels must be in 1..12");
+    dqmc_series_state st;
+    check(dqmc_series_get_state(g.ctx, &st), "dqmc_series_get_state");
+    if (g.seriesBinLevels == levels && g.seriesBinHasTau == withTau && g.seriesBinSamples == st.samples && g.seriesBinRebins == st.rebins) return;
+    g.seriesBinLevels = 0;
+    const size_t len = (size_t)levels * g.count * st.sample_len;
+    g.seriesBinErr.resize(len);
+    if (withTau) g.seriesBinTau.resize(len);
+    check(dqmc_series_binning_host(g.ctx, levels, g.seriesBinErr.data(), withTau ? g.seriesBinTau.data() : nullptr), "dqmc_series_binning_host");
+    g.seriesBinLevels = levels; g.seriesBinHasTau = withTau; g.seriesBinSamples = st.samples; g.seriesBinRebins = st.rebins;
+}
+void DetSDW::seriesBinning(int which, int levels, double* err, double* tau, int b) {
+    if (b < 0 || b >= (int)ch_.size()) throw ParameterWrong("chain index out of range");
+    int part; size_t off, len;
+    seriesSlice(which, part, off, len);
+    Group& g = grp(b);
+    seriesBinningOf(g, levels, tau != nullptr);
+    const size_t S = g.seriesBinErr.size() / ((size_t)levels * g.count);
+    for (int l = 0; l < levels; ++l) {
+        const size_t at = ((size_t)l * g.count + (size_t)(b - g.first)) * S + off;
+        std::memcpy(err + (size_t)l * len, &g.seriesBinErr[at], len * sizeof(double));
+        if (tau) std::memcpy(tau + (size_t)l * len, &g.seriesBinTau[at], len * sizeof(double));
+    }
+}
+void DetSDW::seriesBinningAll(int which, int levels, double* err, double* tau) {
+    int part; size_t off, len;
+    seriesSlice(which, part, off, len);
+    for (auto& g : groups_) {
+        seriesBinningOf(g, levels, tau != nullptr);
+        const size_t S = g.seriesBinErr.size() / ((size_t)levels * g.count);
+        for (int b = 0; b < g.count; ++b)
+            for (int l = 0; l < levels; ++l) {
+                const size_t at = ((size_t)l * g.count + (size_t)b) * S + off, to = ((size_t)(g.first + b) * levels + (size_t)l) * len;
+                std::memcpy(err + to, &g.seriesBinErr[at], len * sizeof(double));
+                if (tau) std::memcpy(tau + to, &g.seriesBinTau[at], len * sizeof(double));
+            }
+    }
 }
 
 // initMeasurements / measure / finishMeasurements, bosonic part (detsdwopdim.cpp:441-456, :509-545, :903-921)
@@ -1277,6 +1340,88 @@ void DetSDW::loadState(const std::string& path) {
     lastSweepDir_ = Up;
 }
 
+// ---- the series file: magic, version, dqmc_series_state (nb = all chains), the route [nchains] int32, then per SLOT in handle order
+// the closed bins [bins_closed][S], the open bin [S] and, if the variance is tracked, w [S] and m2 [S].  Nothing in it depends on how
+// the chains are spread over kernel contexts.
+namespace {
+const char kSeriesMagic[8] = {'D', 'Q', 'M', 'C', 'S', 'E', 'R', '1'};
+const int32_t kSeriesVersion = 1;
+// rows per slot of the file / blocks [nb][S] of an export after the closed bins
+size_t seriesExtra(int flags) { return (flags & DQMC_SERIES_TRACK_VARIANCE) ? 3 : 1; }
+}  // namespace
+
+void DetSDW::seriesSave(const std::string& path) {
+    dqmc_series_state st;
+    seriesGetState(st);
+    FileCloser fc{std::fopen(path.c_str(), "wb")};
+    if (!fc.f) throw GeneralError(DQMC_EINVAL, "Could not open file " + path + " for writing");
+    wr(fc.f, kSeriesMagic, 8); wr(fc.f, &kSeriesVersion, sizeof(kSeriesVersion)); wr(fc.f, &st, sizeof(st));
+    const std::vector<int32_t> route(seriesRoute_.begin(), seriesRoute_.end());
+    wr(fc.f, route.data(), route.size() * sizeof(int32_t));
+    const size_t S = st.sample_len, B = (size_t)st.bins_closed, extra = seriesExtra(st.flags);
+    std::vector<double> buf, row((B + extra) * S);
+    for (auto& g : groups_) {
+        const size_t n = (size_t)g.count * S;
+        buf.resize((B + extra) * n);
+        check(dqmc_series_export_host(g.ctx, buf.data(), buf.size()), "dqmc_series_export_host");
+        for (int b = 0; b < g.count; ++b) {                  // the export is [block][chain][S]: gather the slot's rows
+            for (size_t k = 0; k < B + extra; ++k) std::memcpy(&row[k * S], &buf[k * n + (size_t)b * S], S * sizeof(double));
+            wr(fc.f, row.data(), row.size() * sizeof(double));
+        }
+    }
+}
+
+void DetSDW::seriesLoad(const std::string& path) {
+    if (!series_.open) throw GeneralError(DQMC_EINVAL, "no measurement series is open: detsdw_series_begin with the options of the run first");
+    FileCloser fc{std::fopen(path.c_str(), "rb")};
+    if (!fc.f) throw GeneralError(DQMC_EINVAL, "Could not open file " + path + " for reading");
+    char magic[8]; int32_t version = 0; dqmc_series_state st;
+    rd(fc.f, magic, 8); rd(fc.f, &version, sizeof(version)); rd(fc.f, &st, sizeof(st));
+    if (std::memcmp(magic, kSeriesMagic, 8) != 0 || version != kSeriesVersion) throw GeneralError(DQMC_EINVAL, "series file: not a detqmc_amd series file of this version");
+    const int nch = (int)ch_.size();
+    if (st.nb != nch) throw ParameterWrong("series file: written for a different number of chains");
+    // the whole file is read and checked against every kernel context before any context imports
+    for (auto& g : groups_) {
+        dqmc_series_state own;
+        check(dqmc_series_get_state(g.ctx, &own), "dqmc_series_get_state");
+        if (st.sample_len != own.sample_len || st.parts != own.parts || st.nfreq != own.nfreq)
+            throw ParameterWrong("series file: parts, nfreq or the sample length differ from the open series");
+        if (st.bins_closed < 0 || st.bins_closed >= own.max_bins) throw ParameterWrong("series file: more closed bins than maxBins of the open series holds");
+        if (st.bin_size < 1 || st.sweeps_in_open_bin < 0 || st.sweeps_in_open_bin >= st.bin_size || st.samples < 0 || st.rebins < 0)
+            throw ParameterWrong("series file: bad counters");
+        if ((st.flags & ~(DQMC_SERIES_AUTO_REBIN | DQMC_SERIES_TRACK_VARIANCE)) ||
+            ((st.flags & DQMC_SERIES_AUTO_REBIN) && (own.max_bins < 4 || own.max_bins % 2)))
+            throw ParameterWrong("series file: its options are not valid for maxBins of the open series");
+    }
+    std::vector<int32_t> route((size_t)nch);
+    rd(fc.f, route.data(), route.size() * sizeof(int32_t));
+    std::vector<char> seen((size_t)nch, 0);
+    for (int32_t s : route) {
+        if (s < 0 || s >= nch || seen[(size_t)s]) throw ParameterWrong("series file: the route is no permutation");
+        seen[(size_t)s] = 1;
+    }
+    const size_t S = st.sample_len, B = (size_t)st.bins_closed, extra = seriesExtra(st.flags);
+    std::vector<double> slots((size_t)nch * (B + extra) * S);
+    rd(fc.f, slots.data(), slots.size() * sizeof(double));
+    char more;
+    if (std::fread(&more, 1, 1, fc.f) != 0) throw GeneralError(DQMC_EINVAL, "series file: longer than its header says");
+    std::vector<double> buf;
+    for (auto& g : groups_) {
+        const size_t n = (size_t)g.count * S;
+        buf.resize((B + extra) * n);
+        for (int b = 0; b < g.count; ++b) {
+            const double* row = &slots[(size_t)(g.first + b) * (B + extra) * S];
+            for (size_t k = 0; k < B + extra; ++k) std::memcpy(&buf[k * n + (size_t)b * S], row + k * S, S * sizeof(double));
+        }
+        dqmc_series_state own = st;
+        own.nb = g.count;
+        check(dqmc_series_import_host(g.ctx, &own, buf.data(), buf.size()), "dqmc_series_import_host");
+        seriesDropCaches(g);
+    }
+    series_.binSize = st.bin_size;
+    seriesRoute_.assign(route.begin(), route.end());
+}
+
 void DetSDW::getGreen(dqmc_cplx* g, int b) { check(dqmc_get_green_host(select(b), g), "dqmc_get_green_host"); }
 void DetSDW::getGreenInvSv(double* sv, int b) { check(dqmc_get_sv_host(select(b), sv), "dqmc_get_sv_host"); }
 
@@ -1371,6 +1516,28 @@ extern "C" int detsdw_series_read_bins(detsdw_replica* r, int which, int first, 
     RGUARD(r->impl->seriesReadBins(which, first, count, out, r->sel))
 }
 extern "C" int detsdw_series_end(detsdw_replica* r) { RGUARD(r->impl->seriesEnd()) }
+extern "C" int detsdw_series_configure(detsdw_replica* r, int flags) { RGUARD(r->impl->seriesConfigure(flags)) }
+extern "C" int detsdw_series_rebin(detsdw_replica* r) { RGUARD(r->impl->seriesRebin()) }
+extern "C" int detsdw_series_get_state(detsdw_replica* r, dqmc_series_state* out) {
+    if (!out) { g_host_err = "null argument"; return DQMC_EINVAL; }
+    RGUARD(r->impl->seriesGetState(*out))
+}
+extern "C" int detsdw_series_binning(detsdw_replica* r, int which, int levels, double* err, double* tau) {
+    if (!err) { g_host_err = "null argument"; return DQMC_EINVAL; }
+    RGUARD(r->impl->seriesBinning(which, levels, err, tau, r->sel))
+}
+extern "C" int detsdw_series_binning_all(detsdw_replica* r, int which, int levels, double* err, double* tau) {
+    if (!err) { g_host_err = "null argument"; return DQMC_EINVAL; }
+    RGUARD(r->impl->seriesBinningAll(which, levels, err, tau))
+}
+extern "C" int detsdw_series_save(detsdw_replica* r, const char* path) {
+    if (!path) { g_host_err = "null path"; return DQMC_EINVAL; }
+    RGUARD(r->impl->seriesSave(path))
+}
+extern "C" int detsdw_series_load(detsdw_replica* r, const char* path) {
+    if (!path) { g_host_err = "null path"; return DQMC_EINVAL; }
+    RGUARD(r->impl->seriesLoad(path))
+}
 extern "C" int detsdw_get_tau_grid(detsdw_replica* r, double* out) {
     if (!out) { g_host_err = "null argument"; return DQMC_EINVAL; }
     RGUARD(r->impl->getTauGrid(out))

@@ -71,6 +71,14 @@ public:
     void seriesStatsAll(int which, double* mean, double* err);
     void seriesDerivedAll(int what, double* value, double* err);
     void seriesReadBins(int which, int first, int count, double* out, int b = 0);
+    // long runs: options, re-binning, binning analysis (err, tau [levels] x the slice of seriesStats; tau may be null), series file
+    void seriesConfigure(int flags);
+    void seriesRebin();
+    void seriesGetState(dqmc_series_state& out);   // the state every kernel context shares, nb = all chains of the handle
+    void seriesBinning(int which, int levels, double* err, double* tau, int b = 0);
+    void seriesBinningAll(int which, int levels, double* err, double* tau);
+    void seriesSave(const std::string& path);
+    void seriesLoad(const std::string& path);
     void getPhi(double* phi, int b = 0);
     void setPhi(const double* phi, int b = 0);
     void getCdwl(int32_t* cdwl, int b = 0);
@@ -121,6 +129,10 @@ private:
         int matsNfreq[4] = {0, 0, 0, 0};           // ... and the nfreq they hold (0: none); cleared by every sweep
         std::vector<double> seriesMean, seriesErr; // dqmc_series_stats_host of the group's chains, [chain][S] each ...
         int seriesStatsBins = 0;                   // ... and the number of closed bins they were formed from (0: none)
+        std::vector<double> seriesBinErr, seriesBinTau;   // dqmc_series_binning_host of the group's chains, [level][chain][S] each ...
+        int seriesBinLevels = 0;                          // ... the levels they hold (0: none), whether tau was formed, and the samples
+        bool seriesBinHasTau = false;                     // and rebins of the series they were formed from
+        long long seriesBinSamples = 0, seriesBinRebins = 0;
     };
     std::vector<Group> groups_;
     int N_, MSF_, ng_, m_, s_, n_, opdim_;
@@ -145,6 +157,8 @@ private:
     bool seriesNoHostCopy() const { return series_.open && (series_.flags & DETSDW_SERIES_NO_HOST_COPY); }
     void seriesSlice(int which, int& part, size_t& offset, size_t& length);   // where `which` sits inside its part
     void seriesStatsOf(Group& g);                                             // fills the group's cache
+    void seriesBinningOf(Group& g, int levels, bool withTau);                 // the same for the binning analysis
+    static void seriesDropCaches(Group& g) { g.seriesStatsBins = 0; g.seriesBinLevels = 0; }   // after a re-bin or a load: the keys repeat
     void invalidateMatsubara();
     const double* matsubara(Group& g, int which, int nfreq, int& ncomp, int& comp);
     void measureTimeDisplaced(Group& g, int j);

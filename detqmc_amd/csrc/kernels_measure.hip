@@ -1108,3 +1108,102 @@ void launch_series_derived(const Launch& lc, const DevModel& hm, const double* b
     SeriesDerivedShape a{off_eq, off_cur, hm.L, hm.N, nfreq, lc.nb, B, S};
     hipLaunchKernelGGL(k_series_derived, dim3((unsigned)((lc.nb * 6 + 63) / 64)), dim3(64), 0, lc.st, bins, a, value, err);
 }
+
+// ---- long runs: re-binning, running variance, binning analysis (dqmc_series_rebin / _configure / _binning_host) ----------------
+// closed[k] = (closed[2k] + closed[2k+1]) * 0.5 for k < half, in place over the n = nb S elements.  One thread per element walks k
+// upwards: it reads bins 2k and 2k + 1 >= k of its own element after it wrote bins < k, and no other thread touches the element.
+__global__ __launch_bounds__(256) void k_series_rebin(double* __restrict__ bins, size_t n, int half) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    for (int k = 0; k < half; ++k) {
+        const double a = bins[(size_t)(2 * k) * n + i], b = bins[(size_t)(2 * k + 1) * n + i];
+        bins[(size_t)k * n + i] = (a + b) * 0.5;
+    }
+}
+void launch_series_rebin(const Launch& lc, double* bins, size_t n, int half) {
+    hipLaunchKernelGGL(k_series_rebin, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, lc.st, bins, n, half);
+}
+
+// Welford's update of the running mean w and the sum of squared deviations m2 with the sample of every slot, cnt = the number of samples
+// including this one: d = x - w; w += d / cnt; m2 += d (x - w).  Grid (ceil(S / 256), nb); src == nullptr: slot s takes row s of
+// `sample`, otherwise the row src[s] (the table of k_series_accum_routed).  One writer per element.
+__global__ __launch_bounds__(256) void k_series_welford(const double* __restrict__ sample, const double* const* __restrict__ src,
+                                                        double* __restrict__ w, double* __restrict__ m2, size_t S, double cnt) {
+    const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= S) return;
+    const size_t i = (size_t)blockIdx.y * S + j;
+    const double x = src ? src[blockIdx.y][j] : sample[i];
+    const double d = x - w[i];
+    const double wn = w[i] + d / cnt;
+    w[i] = wn;
+    m2[i] += d * (x - wn);
+}
+void launch_series_welford(const Launch& lc, const double* sample, const double* const* src, double* w, double* m2, size_t S, long long cnt) {
+    hipLaunchKernelGGL(k_series_welford, dim3((unsigned)((S + 255) / 256), (unsigned)lc.nb), dim3(256), 0, lc.st, sample, src, w, m2, S,
+                       (double)cnt);
+}
+
+// Binning analysis: level l holds B_l = B >> l merged bins y^l_k, y^0_k = closed bin k, y^l_k = (y^(l-1)_2k + y^(l-1)_(2k+1)) * 0.5 --
+// what l calls of k_series_rebin would leave; closed bins beyond 2^l B_l never complete a merged bin of level l and do not enter it.
+// err[l] = the jackknife error of k_series_stats over y^l_0 .. y^l_(B_l - 1); tau[l] = 1/2 err[l]^2 (B_l 2^l bin_size) / sigma^2 with
+// sigma^2 = m2 / (samples - 1), NaN unless sigma^2 > 0 (tau == nullptr: not formed).  One thread per element streams the bins twice,
+// once for the level means and once for the squared deviations: bin k is added to level 0, and whenever a level completes a pair the
+// merged value moves one level up.  The half-finished pair of every level (carry) and the sums live in registers: the level loops run
+// to the compile-time SERIES_MAX_LEVELS and are fully unrolled, so no array is indexed at run time.  Sums in index order, no atomics.
+constexpr int SERIES_MAX_LEVELS = 12;
+struct SeriesBinningShape { size_t n; int B, levels; double bin_size, samples; };
+__global__ __launch_bounds__(256) void k_series_binning(const double* __restrict__ bins, const double* __restrict__ m2, SeriesBinningShape a,
+                                                        double* __restrict__ err, double* __restrict__ tau) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n) return;
+    const size_t n = a.n;
+    const int B = a.B, levels = a.levels;
+    double carry[SERIES_MAX_LEVELS], sum[SERIES_MAX_LEVELS], mu[SERIES_MAX_LEVELS], tot[SERIES_MAX_LEVELS], inv[SERIES_MAX_LEVELS];
+#pragma unroll
+    for (int l = 0; l < SERIES_MAX_LEVELS; ++l) { carry[l] = 0.0; sum[l] = 0.0; }
+    for (int k = 0; k < B; ++k) {
+        double y = bins[(size_t)k * n + i];
+        bool live = true;
+#pragma unroll
+        for (int l = 0; l < SERIES_MAX_LEVELS; ++l) {
+            if (live && l < levels) {
+                sum[l] += y;
+                if ((k >> l) & 1) y = (carry[l] + y) * 0.5;      // the pair of level l is complete: its mean is the next value of level l + 1
+                else { carry[l] = y; live = false; }
+            }
+        }
+    }
+#pragma unroll
+    for (int l = 0; l < SERIES_MAX_LEVELS; ++l) {
+        const double Bl = (double)(B >> l);
+        mu[l] = sum[l] / Bl; tot[l] = Bl * mu[l]; inv[l] = Bl - 1.0; sum[l] = 0.0; carry[l] = 0.0;
+    }
+    for (int k = 0; k < B; ++k) {
+        double y = bins[(size_t)k * n + i];
+        bool live = true;
+#pragma unroll
+        for (int l = 0; l < SERIES_MAX_LEVELS; ++l) {
+            if (live && l < levels) {
+                const double d = (tot[l] - y) / inv[l] - mu[l];
+                sum[l] += d * d;
+                if ((k >> l) & 1) y = (carry[l] + y) * 0.5;
+                else { carry[l] = y; live = false; }
+            }
+        }
+    }
+    const double var = tau ? m2[i] / (a.samples - 1.0) : 0.0;
+#pragma unroll
+    for (int l = 0; l < SERIES_MAX_LEVELS; ++l) {
+        if (l < levels) {
+            const double Bl = (double)(B >> l);
+            const double e = sqrt((Bl - 1.0) / Bl * sum[l]);
+            err[(size_t)l * n + i] = e;
+            if (tau) tau[(size_t)l * n + i] = var > 0.0 ? 0.5 * e * e * (Bl * (double)(1 << l) * a.bin_size) / var : nan("");
+        }
+    }
+}
+void launch_series_binning(const Launch& lc, const double* bins, const double* m2, size_t n, int B, int levels, int bin_size,
+                           long long samples, double* err, double* tau) {
+    SeriesBinningShape a{n, B, levels, (double)bin_size, (double)samples};
+    hipLaunchKernelGGL(k_series_binning, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, lc.st, bins, m2, a, err, tau);
+}

@@ -135,6 +135,31 @@ def jackknife(bins, f=None):
     return f(mean), np.sqrt((B - 1) / B * ((theta - theta.sum(axis=0) / B) ** 2).sum(axis=0))
 
 
+def binning_analysis(bins, bin_size, variance=None):
+    """Binning analysis over the leading axis of `bins` (B closed bin means of bin_size sweeps each), the formulas of
+    dqmc_series_binning_host: level l holds B_l = B >> l merged bins, y^0 = bins, y^l_k = (y^(l-1)_2k + y^(l-1)_(2k+1)) * 0.5 (bins beyond
+    2^l B_l are not used), for every level with B_l >= 2.  Returns err [levels] + bins.shape[1:], the jackknife error of every level,
+    or with variance = sigma^2 of the single samples (m2 / (samples - 1)) the pair (err, tau) with the integrated autocorrelation time
+    tau_l = 1/2 err_l^2 (B_l 2^l bin_size) / sigma^2 in sweeps, NaN where sigma^2 is not > 0."""
+    y = np.asarray(bins, dtype=np.float64)
+    if y.shape[0] < 2:
+        raise ValueError("the binning analysis needs at least two bins")
+    errs, taus = [], []
+    if variance is not None:
+        var = np.asarray(variance, dtype=np.float64)
+        safe = np.where(var > 0, var, 1.0)
+    level = 0
+    while y.shape[0] >= 2:
+        errs.append(jackknife(y)[1])
+        if variance is not None:
+            t = 0.5 * errs[-1] * errs[-1] * (float(y.shape[0]) * float(1 << level) * float(bin_size)) / safe
+            taus.append(np.where(var > 0, t, np.nan))
+        half = y.shape[0] // 2
+        y = (y[0:2 * half:2] + y[1:2 * half:2]) * 0.5
+        level += 1
+    return np.array(errs) if variance is None else (np.array(errs), np.array(taus))
+
+
 SPIN_PROPOSAL = {"box": 0, "rotate_then_scale": 1, "rotate_and_scale": 2}
 PROPOSE = {"box": 0, "rotate": 1, "scale": 2, "rotate_and_scale": 3}
 ADAPT = {"box": 0, "rotate": 1, "scale": 2}
@@ -365,6 +390,52 @@ class KernelContext:
 
     def series_end(self):
         check(self.lib.dqmc_series_end(self.h))
+
+    def series_configure(self, auto_rebin=False, track_variance=False):
+        """options of the open, still empty series: auto_rebin merges neighbouring bins whenever max_bins (even, >= 4) bins are closed;
+        track_variance keeps the running mean and m2 of the single samples per slot (for tau of series_binning)"""
+        flags = (_lib.DQMC_SERIES_AUTO_REBIN if auto_rebin else 0) | (_lib.DQMC_SERIES_TRACK_VARIANCE if track_variance else 0)
+        check(self.lib.dqmc_series_configure(self.h, flags))
+
+    def series_state(self):
+        """the dqmc_series_state of the open series: bin_size, max_bins, nfreq, parts, flags, bins_closed, sweeps_in_open_bin, nb, samples,
+        rebins, sample_len"""
+        st = _lib.dqmc_series_state()
+        check(self.lib.dqmc_series_get_state(self.h, C.byref(st)))
+        return st
+
+    def series_rebin(self):
+        """merge neighbouring closed bins in place: half as many bins of twice the size"""
+        check(self.lib.dqmc_series_rebin(self.h))
+
+    def series_binning(self, levels, tau=True):
+        """binning analysis of every slot: (err, tau), (levels, nchains, S) each -- the jackknife error over the bins merged l times and the
+        integrated autocorrelation time in sweeps it implies (needs track_variance); tau=False: err alone"""
+        S = self.series_info()[2]
+        shape = (max(int(levels), 0), self.nchains_total(), S)
+        err = np.zeros(shape)
+        if not tau:
+            check(self.lib.dqmc_series_binning_host(self.h, int(levels), err.ctypes.data_as(_lib._DP), None))
+            return err
+        t = np.zeros(shape)
+        check(self.lib.dqmc_series_binning_host(self.h, int(levels), err.ctypes.data_as(_lib._DP), t.ctypes.data_as(_lib._DP)))
+        return err, t
+
+    def _series_export_len(self, st):
+        return (st.bins_closed + 1 + (2 if st.flags & _lib.DQMC_SERIES_TRACK_VARIANCE else 0)) * st.nb * st.sample_len
+
+    def series_export(self):
+        """(state, data): data = the closed bins [bins_closed][nchains][S], the open bin [nchains][S] and, with track_variance, w and m2
+        [nchains][S] each, flat"""
+        st = self.series_state()
+        out = np.zeros(self._series_export_len(st))
+        check(self.lib.dqmc_series_export_host(self.h, out.ctypes.data_as(_lib._DP), out.size))
+        return st, out
+
+    def series_import(self, state, data):
+        """restore what series_export returned into the open series (series_begin with the same parts, nfreq and chains first)"""
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        check(self.lib.dqmc_series_import_host(self.h, C.byref(state), data.ctypes.data_as(_lib._DP), data.size))
 
     def td_fine_propagate(self, j, k):
         """for tests: the work copies at slice k of boundary j's segment, by the steps of measure_timedisplaced_segment; measures nothing"""
@@ -744,6 +815,15 @@ class DetSDW:
         check(self.lib.detsdw_series_read_bins(self.h, which, int(first), int(count), out.ctypes.data_as(_lib._DP)), host=True)
         return out
 
+    def series_binning(self, name, levels):
+        """(err, tau) of this chain's slot, (levels,) + the shape of series_stats each: the binning analysis of the open series (needs
+        track_variance); for complex observables the real and the imaginary part are analysed separately"""
+        self._sel()
+        which, shape, cplx = self._series_shape(name)
+        err, tau = (np.zeros((max(int(levels), 0),) + shape, dtype=np.complex128 if cplx else np.float64) for _ in range(2))
+        check(self.lib.detsdw_series_binning(self.h, which, int(levels), err.ctypes.data_as(_lib._DP), tau.ctypes.data_as(_lib._DP)), host=True)
+        return err, tau
+
     def matsubara_frequencies(self, nfreq, fermionic=False):
         """omega_n, n = 0 .. nfreq-1: 2 pi n / beta, or (2n+1) pi / beta for the fermionic 'greenKTauX' / 'greenKTauY'"""
         n = np.arange(int(nfreq))
@@ -899,15 +979,50 @@ class DetSDWBatch:
         check(self.lib.detsdw_get_matsubara_all(self.h, MATSUBARA[name], int(nfreq), out.ctypes.data_as(_lib._DP)), host=True)
         return out
 
-    def series_begin(self, binSize, maxBins, nfreq=0, host_copy=True):
+    def series_begin(self, binSize, maxBins, nfreq=0, host_copy=True, auto_rebin=False, track_variance=False):
         """open a measurement series on the device: from now on every sweep(True) adds one sample per chain -- the equal-time C(d),
         S(q) with equalTimeCorrelators, the Matsubara transforms at nfreq frequencies of every enabled channel with
         timeDisplacedEverySlice -- to bins of binSize sweeps, at most maxBins of them.  host_copy=False: measurement sweeps no longer
-        copy the equal-time block to the host ('...Corr' / '...Sq' of observable_vector raise while the series is open)"""
+        copy the equal-time block to the host ('...Corr' / '...Sq' of observable_vector raise while the series is open).
+        auto_rebin: whenever maxBins (even, >= 4) bins are closed, neighbouring bins are merged -- the run never outlives the series;
+        track_variance: keep the variance of the single samples, which series_binning_all needs for tau"""
         flags = 0 if host_copy else _lib.DETSDW_SERIES_NO_HOST_COPY
         check(self.lib.detsdw_series_begin(self.h, int(binSize), int(maxBins), int(nfreq), flags), host=True)
         self._series_nfreq = int(nfreq)
         self._series_open = True
+        if auto_rebin or track_variance:
+            opts = (_lib.DQMC_SERIES_AUTO_REBIN if auto_rebin else 0) | (_lib.DQMC_SERIES_TRACK_VARIANCE if track_variance else 0)
+            try:
+                check(self.lib.detsdw_series_configure(self.h, opts), host=True)
+            except _lib.DqmcError:
+                self.lib.detsdw_series_end(self.h)         # refused options: no half-configured series stays open
+                self._series_open = False
+                raise
+
+    def series_state(self):
+        """the dqmc_series_state all kernel contexts share (nb = the chains of the batch)"""
+        st = _lib.dqmc_series_state()
+        check(self.lib.detsdw_series_get_state(self.h, C.byref(st)), host=True)
+        return st
+
+    def series_rebin(self):
+        """merge neighbouring closed bins of every slot: half as many bins of twice the size"""
+        check(self.lib.detsdw_series_rebin(self.h), host=True)
+
+    def series_binning_all(self, name, levels):
+        """DetSDW.series_binning of every slot: (err, tau), (nchains, levels) + the per-chain shape each; one device call per sub-batch"""
+        which, shape, cplx = self.chains[0]._series_shape(name)
+        err, tau = (np.zeros((len(self.chains), max(int(levels), 0)) + shape, dtype=np.complex128 if cplx else np.float64) for _ in range(2))
+        check(self.lib.detsdw_series_binning_all(self.h, which, int(levels), err.ctypes.data_as(_lib._DP), tau.ctypes.data_as(_lib._DP)), host=True)
+        return err, tau
+
+    def series_save(self, path):
+        """the whole series -- bins, open bin, counters, variance, route -- to a file of its own, next to save_state"""
+        check(self.lib.detsdw_series_save(self.h, str(path).encode()), host=True)
+
+    def series_load(self, path):
+        """restore a series_save file into the open series (series_begin with the options of the run first); restores the route too"""
+        check(self.lib.detsdw_series_load(self.h, str(path).encode()), host=True)
 
     def series_is_open(self):
         return self._series_open

@@ -213,7 +213,7 @@ int detsdw_get_matsubara_all(detsdw_replica* r, int which, int nfreq, double* ou
  * without timeDisplacedEverySlice; ParameterWrong if neither option is on.  While the series is open every detsdw_sweep(r, 1) ends
  * with one sample of every chain added to the series (after binSize of them a bin closes); thermalisation sweeps and detsdw_sweep(r, 0) add
  * nothing.  A measurement sweep on a full series (maxBins bins closed) fails with DQMC_EINVAL before it changes anything: read the
- * series out and end it.
+ * series out and end it, or let it re-bin itself (detsdw_series_configure below).
  * flags: DETSDW_SERIES_NO_HOST_COPY -- while the series is open a measurement sweep does not copy the equal-time block to the host
  * and forms no cosine sums there; DETSDW_OBS_CHARGECORR .. _PAIRMINUSSQ of detsdw_get_observable_vector then raise ParameterWrong
  * (as the ...Fine observables do with timeDisplacedFineOnDevice).
@@ -226,7 +226,7 @@ int detsdw_get_matsubara_all(detsdw_replica* r, int which, int nfreq, double* ou
  *     and err[nchains]; ParameterWrong if the option the quantity needs is off.
  *   detsdw_series_read_bins: closed bins first .. first + count - 1 of `which`, selected chain: out[count] x (N, or [nfreq][N] complex).
  * detsdw_save_state does not store the series, and detsdw_load_state leaves an open series alone (bins closed before the load stay,
- * the open bin keeps what it holds; neither stores the route).
+ * the open bin keeps what it holds; neither stores the route): the series has a file of its own, detsdw_series_save / _load below.
  * Slots and the route: a SLOT is a row of the series buffers (open bin, closed bins, statistics), indexed like a chain; the index of
  * every reader above -- the selected chain, or the position in an ..._all result -- means the slot.  A measurement sweep adds the sample
  * of chain c to slot slotOfChain[c]; the route is the identity after detsdw_series_begin, which is a series per chain.  Under replica
@@ -253,6 +253,30 @@ int detsdw_series_stats_all(detsdw_replica* r, int which, double* mean, double* 
 int detsdw_series_derived_all(detsdw_replica* r, int what, double* value, double* err);
 int detsdw_series_read_bins(detsdw_replica* r, int which, int first, int count, double* out);
 int detsdw_series_end(detsdw_replica* r);
+/* The series over a long run (kernel calls and formulas: dqmc_hip.h).  All of it is new surface: without these calls nothing changes.
+ *   detsdw_series_configure: flags = DQMC_SERIES_AUTO_REBIN | DQMC_SERIES_TRACK_VARIANCE, applied to every kernel context, only while
+ *     the series is empty.  With AUTO_REBIN (maxBins even and >= 4) the sweep that closes bin maxBins merges neighbouring bins before it
+ *     returns -- half as many bins of twice the size -- so a measurement sweep is never refused for a full series.  All contexts
+ *     accumulate in the same sweeps, so they re-bin in the same sweep.
+ *   detsdw_series_rebin: the same merge on request (DQMC_EINVAL for an odd number of closed bins).
+ *   detsdw_series_get_state: the state all contexts share; nb = the chains of the handle.
+ *   detsdw_series_binning / _binning_all: the binning analysis of the selected slot, err[levels] x the slice of detsdw_series_stats and
+ *     tau likewise (tau may be NULL; it needs TRACK_VARIANCE), or of every slot in handle order, [nchains][levels] x the slice.  One
+ *     device call per kernel context serves every `which` until the next sample or re-bin.
+ *   detsdw_series_save / _load: the series file -- magic "DQMCSER1", int32 version, dqmc_series_state (nb = all chains), the route
+ *     int32[nchains], then per SLOT in handle order the closed bins [bins_closed][S], the open bin [S] and, with TRACK_VARIANCE, w [S] and
+ *     m2 [S].  It does not depend on sub_batches.  detsdw_series_load needs a series already open (detsdw_series_begin with the options of
+ *     the run: NO_HOST_COPY is taken from that call, bin size, options, counters, bins and the route from the file).  The whole file is
+ *     checked against every kernel context before any context imports; a mismatch (chains, parts, nfreq, more bins than maxBins holds,
+ *     options not valid for maxBins, a truncated file) is ParameterWrong or DQMC_EINVAL and leaves the series and the route as they were.
+ *     detsdw_save_state / detsdw_load_state and their file do not change: a checkpoint of a run with a series is the two files. */
+int detsdw_series_configure(detsdw_replica* r, int flags);
+int detsdw_series_rebin(detsdw_replica* r);
+int detsdw_series_get_state(detsdw_replica* r, dqmc_series_state* out);
+int detsdw_series_binning(detsdw_replica* r, int which, int levels, double* err, double* tau);
+int detsdw_series_binning_all(detsdw_replica* r, int which, int levels, double* err, double* tau);
+int detsdw_series_save(detsdw_replica* r, const char* path);
+int detsdw_series_load(detsdw_replica* r, const char* path);
 /* tau_j = j s dtau of the rows of greenKTauX / Y, j = 1 .. n-1: out[n-1] */
 int detsdw_get_tau_grid(detsdw_replica* r, double* out);
 /* With timeDisplacedEverySlice: tau_k = k dtau of the rows of the ...Fine observables, k = 0 .. m: out[m+1].  Interior rows k = 1 .. m-1

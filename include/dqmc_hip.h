@@ -433,7 +433,7 @@ int dqmc_measure_td_matsubara_host(dqmc_ctx* ctx, int channel, int nfreq, double
  * dqmc_series_add_sweep (all chains): forms the sample and adds it to the open bin, open += sample, in call order; the bin_size-th call
  * writes closed[k] = open / bin_size and clears the open bin.  DQMC_EINVAL with no bin changed: the equal-time count of any chain or a
  * fine row count of any chain and channel of the mask is < 1; max_bins bins are already closed (nothing is dropped silently, and there
- * is no re-binning).  Reads the blocks only: G and every accumulator stay bit-identical.  dqmc_measure_reset does not touch the series.
+ * is no re-binning unless DQMC_SERIES_AUTO_REBIN is set, below).  Reads the blocks only: G and every accumulator stay bit-identical.  dqmc_measure_reset does not touch the series.
  * The call synchronises (it reads the flags back, nb doubles per part).  It is dqmc_series_form_sample followed by
  * dqmc_series_accumulate(ctx, NULL):
  * A SLOT is a row of the series buffers (open bin, closed bins, statistics), indexed like a chain.  The two halves let a caller add the
@@ -475,6 +475,41 @@ int dqmc_series_read_bins_host(dqmc_ctx* ctx, int first, int count, double* out)
 int dqmc_series_stats_host(dqmc_ctx* ctx, double* mean, double* err);
 int dqmc_series_derived_host(dqmc_ctx* ctx, double* value, double* err);
 int dqmc_series_end(dqmc_ctx* ctx);
+/* ---- the series over a long run: re-binning, binning analysis with tau_int, export / import ------------
+ * All of it is new surface: with none of these calls used, every call above keeps its bits, its error codes and its launches.
+ * dqmc_series_configure: the options of the open series, allowed only while it is empty (no accumulate since dqmc_series_begin).
+ *   DQMC_SERIES_AUTO_REBIN needs max_bins even and >= 4.  DQMC_EINVAL with nothing changed otherwise, and for unknown bits.  The options
+ *   are no bits of `parts`: dqmc_series_begin refuses parts = 32.
+ * dqmc_series_rebin: merges neighbouring closed bins in place, all slots: closed[k] = (closed[2k] + closed[2k+1]) * 0.5 for k < B/2 (two
+ *   IEEE operations); bins_closed halves, bin_size doubles, rebins increments.  The open bin and sweeps_in_open_bin stay: the open bin
+ *   now closes after the new bin_size samples.  DQMC_EINVAL with nothing changed: an odd number of closed bins; a bin_size that would
+ *   rise above 2^30.  Zero closed bins: only bin_size doubles.
+ * AUTO_REBIN: the dqmc_series_accumulate / dqmc_series_add_sweep whose close makes bins_closed == max_bins re-bins before it returns, so
+ *   the series is never observed full (dqmc_series_form_sample is unchanged).  If bin_size cannot double, the series becomes full.
+ * TRACK_VARIANCE: two more buffers [nb][S] per slot, a running mean w and m2, routed like the open bin.  Every accumulate raises
+ *   `samples` to n and does d = x - w; w += d / n; m2 += d (x - w) (Welford) in a kernel of its own.  `samples` counts without the flag too.
+ * dqmc_series_binning_host (all chains; err and tau [levels][nb][S]; tau may be NULL): levels in 1 .. 12.  Level l has B_l = bins_closed >> l
+ *   merged bins y^l_k, y^0_k = closed bin k, y^l_k = (y^(l-1)_2k + y^(l-1)_(2k+1)) * 0.5 -- what l calls of dqmc_series_rebin would leave;
+ *   closed bins beyond 2^l B_l are not used.  err_l = the err of dqmc_series_stats_host over y^l_0 .. y^l_(B_l - 1) in index order;
+ *   tau_l = 1/2 err_l^2 (B_l 2^l bin_size) / sigma^2, sigma^2 = m2 / (samples - 1) over all samples of the slot, in sweeps; NaN where
+ *   sigma^2 is not > 0.  DQMC_EINVAL: levels out of range, B_(levels-1) < 2, tau without TRACK_VARIANCE or with samples < 2.  The bins are
+ *   only read (twice, whatever `levels` is); one writer per element, index order, no atomics: two calls give identical bits, and a
+ *   chain's results do not depend on how chains are batched.
+ * dqmc_series_export_host / _import_host: the closed bins [bins_closed][nb][S], the open bin [nb][S], then w and m2 [nb][S] each if the
+ *   variance is tracked; len must be exactly that many doubles.  Import goes into an open series (dqmc_series_begin): nb, sample_len,
+ *   parts and nfreq of the struct must match it, bins_closed < its max_bins, 0 <= sweeps_in_open_bin < bin_size, the flags valid for its
+ *   max_bins (max_bins of the struct is not read).  It sets bin_size, flags, the counters, samples and rebins from the struct and clears
+ *   the formed mark.  Every DQMC_EINVAL leaves the series as it was.  With dqmc_series_begin this is the restore path of a checkpoint. */
+#define DQMC_SERIES_AUTO_REBIN     1
+#define DQMC_SERIES_TRACK_VARIANCE 2
+typedef struct { int bin_size, max_bins, nfreq, parts, flags, bins_closed, sweeps_in_open_bin, nb;
+                 long long samples, rebins; size_t sample_len; } dqmc_series_state;
+int dqmc_series_configure(dqmc_ctx* ctx, int flags);
+int dqmc_series_get_state(dqmc_ctx* ctx, dqmc_series_state* state);
+int dqmc_series_rebin(dqmc_ctx* ctx);
+int dqmc_series_binning_host(dqmc_ctx* ctx, int levels, double* err, double* tau);
+int dqmc_series_export_host(dqmc_ctx* ctx, double* out, size_t len);
+int dqmc_series_import_host(dqmc_ctx* ctx, const dqmc_series_state* state, const double* in, size_t len);
 /* for tests: the last propagated triple G(tau_k,0), G(0,tau_k), G(tau_k) of the selected chain and its slice k (after
  * dqmc_measure_timedisplaced_ends: the triple of row m) */
 int dqmc_get_green_td_fine_host(dqmc_ctx* ctx, dqmc_cplx* g_t0, dqmc_cplx* g_0t, dqmc_cplx* g_tt, int* slice);
