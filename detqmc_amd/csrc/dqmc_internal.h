@@ -180,6 +180,9 @@ struct GemmArgs {
                                 // name (template argument), so that profiles keep it apart from the model's n_g^3 products
 };
 void launch_gemm(const Launch& lc, const GemmArgs& a);
+// the same with the kernel path named: -1 what launch_gemm does, 0 the generic kernel, 1 the whole-tile kernel where the arguments
+// allow it (kernels_gemm.hip, gemm_full_path).  Returns the path that ran (0 / 1).  Both paths give bit-identical C.
+int launch_gemm_path(const Launch& lc, const GemmArgs& a, int path);
 // the kernel shape launch_gemm picks for these arguments and nb chains: tile 32 or 64, ksplit slices of K (1: no split-K; only with
 // 32 x 32 tiles), xcd 1: the XCD-grouped 1-D grid (nb a multiple of 8), 0: grid.z = chain
 struct GemmPlan { int tile, ksplit, xcd; };

@@ -29,7 +29,13 @@ typedef double v4d __attribute__((ext_vector_type(4)));
 // OPA / OPB (op = conjugate transpose) are template parameters: as run-time flags the two addressing variants of each operand were
 // two branches in the tile loop, and the compiler -- reusing the registers of one variant as addresses of the other -- waited for
 // ALL outstanding loads (s_waitcnt vmcnt(0)) between them, in front of the MFMA block of every tile.
-template<int TM, int TN, bool M3, int TAG, bool OPA, bool OPB>
+//
+// FULL (round 5): the instantiation for products made of whole tiles -- M and N multiples of the block tile, K a multiple of 16, no
+// device-side K, no k-scale, no split-K (launch_gemm_path decides).  1: plain operands, 2: with the column gather of A (OPA false only).
+// b_lower is a run-time flag in both.  Same MFMAs on the same operands in the same order as FULL = 0: bit-identical C.  What differs is
+// how the operand tiles travel: no clamps, bounds masks, selects or stand-in loads, addresses = uniform base + per-thread 32-bit offset,
+// and a prefetch distance of TWO k-steps through two register sets (see the FULL branch below).
+template<int TM, int TN, bool M3, int TAG, bool OPA, bool OPB, int FULL>
 __global__ __launch_bounds__(256, 2) void k_zgemm(GemmArgs g, size_t cs, int nb) {   // 2 workgroups per CU: <= 256 registers
     constexpr int BM = 32 * TM, BN = 32 * TN, BK = 16;
     constexpr int NA = BM * BK / 256, NB_ = BN * BK / 256;      // elements of the A / B tile staged per thread
@@ -40,16 +46,17 @@ __global__ __launch_bounds__(256, 2) void k_zgemm(GemmArgs g, size_t cs, int nb)
     xcd_chain_tile(tm * tnn, nb, chain, tile);
     if (!g.sharedA) g.A = chain_ptr_i(g.A, cs, chain);
     if (!g.sharedB) g.B = chain_ptr_i(g.B, cs, chain);
-    g.C = chain_ptr_i(g.C, cs, chain); g.Kdev = chain_ptr_i(g.Kdev, cs, chain); g.kscale = chain_ptr_i(g.kscale, cs, chain);
+    g.C = chain_ptr_i(g.C, cs, chain);
+    if constexpr (!FULL) { g.Kdev = chain_ptr_i(g.Kdev, cs, chain); g.kscale = chain_ptr_i(g.kscale, cs, chain); }
     g.rowscale = chain_ptr_i(g.rowscale, cs, chain); g.colscale = chain_ptr_i(g.colscale, cs, chain);
     g.a_kgather = chain_ptr_i(g.a_kgather, cs, chain);
 
     int K = g.K;
-    if (g.Kdev) { int kd = (*g.Kdev) * g.Kmul; K = kd < K ? kd : K; }
-    if (K <= 0 && g.accumulate) return;
+    if (!FULL && g.Kdev) { int kd = (*g.Kdev) * g.Kmul; K = kd < K ? kd : K; }
+    if (!FULL && K <= 0 && g.accumulate) return;
     // split-K: this workgroup contracts k in [kslice0, K) only (K shortened to the end of its slice); raw sums go to g.part
     int kslice0 = 0;
-    if (g.ksplit > 1) {
+    if (!FULL && g.ksplit > 1) {
         const int kc = ((K + g.ksplit - 1) / g.ksplit + 15) & ~15;
         kslice0 = blockIdx.y * kc;
         K = min(K, kslice0 + kc);
@@ -68,6 +75,136 @@ __global__ __launch_bounds__(256, 2) void k_zgemm(GemmArgs g, size_t cs, int nb)
 #pragma unroll
         for (int b = 0; b < TN; ++b) { acc_re[a][b] = (v4d)(0.0); acc_im[a][b] = (v4d)(0.0); if (M3) acc_p2[a][b] = (v4d)(0.0); }
 
+    // the MFMAs of one k-step on the tile staged in LDS buffer buf
+    auto mfma_tile = [&](int buf) {
+#pragma unroll
+        for (int kk = 0; kk < BK; kk += 4) {
+            cplx af[TM], bf[TN];
+#pragma unroll
+            for (int a = 0; a < TM; ++a) af[a] = sA[buf][kk + l4][wm * 16 * TM + a * 16 + l15];
+#pragma unroll
+            for (int b = 0; b < TN; ++b) bf[b] = sB[buf][kk + l4][wn * 16 * TN + b * 16 + l15];
+            double asum[TM], bsum[TN];
+            if (M3) {
+#pragma unroll
+                for (int a = 0; a < TM; ++a) asum[a] = af[a].x + af[a].y;
+#pragma unroll
+                for (int b = 0; b < TN; ++b) bsum[b] = bf[b].x + bf[b].y;
+            }
+#pragma unroll
+            for (int a = 0; a < TM; ++a)
+#pragma unroll
+                for (int b = 0; b < TN; ++b) {
+                    // roles swapped: first operand indexes the OUTPUT "row" (= column j of C)
+                    if (M3) {
+                        acc_re[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[b].x, af[a].x, acc_re[a][b], 0, 0, 0);
+                        acc_p2[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[b].y, af[a].y, acc_p2[a][b], 0, 0, 0);
+                        acc_im[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(bsum[b], asum[a], acc_im[a][b], 0, 0, 0);
+                    } else {
+                        acc_re[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[b].x, af[a].x, acc_re[a][b], 0, 0, 0);
+                        acc_re[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(-bf[b].y, af[a].y, acc_re[a][b], 0, 0, 0);
+                        acc_im[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[b].y, af[a].x, acc_im[a][b], 0, 0, 0);
+                        acc_im[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[b].x, af[a].y, acc_im[a][b], 0, 0, 0);
+                    }
+                }
+        }
+    };
+    const int Mm1 = g.M - 1, Nm1 = g.N - 1;
+
+    if constexpr (FULL != 0) {
+    // ---- whole tiles: every address is valid and every element is used.  An operand element of k-step s lives at
+    //   (uniform base of the tile) + s * (uniform step stride) + e * (uniform element stride) + (per-thread offset, 32 bits, set up once)
+    // -- the scalar unit keeps the uniform part, one 64-bit vector add per element and step is left.  (The gathered A keeps its index ->
+    // element chain: the indices of step s + 1 are requested right behind the elements of step s, a whole k-step before they are used.)
+    // Prefetch distance TWO: two register sets, written out twice so that no register copy closes the cycle (as in k_flush).  The
+    // loads of step t + 2 go out at the top of step t; the LDS stores of step t + 1 at the bottom of step t consume a set requested a
+    // whole step earlier (s_waitcnt vmcnt counts in order: it lets the younger set stay in flight).  A step past the end requests
+    // the last step again (a uniform clamp of the step number instead of a branch around the loads, which would put vmcnt(0) behind it).
+    constexpr bool GATHER = FULL == 2;
+    constexpr double csgnA = OPA ? -1.0 : 1.0, csgnB = OPB ? -1.0 : 1.0;       // op = conjugate transpose
+    const int kbeg = g.b_lower ? (j0 / BK) * BK : 0;      // triangular op(B): rows above the tile's first column are zero
+    const int last = (K - kbeg) / BK - 1;                 // >= 0: K >= N with b_lower (launch_gemm_path)
+    const cplx *baseA, *baseB;
+    unsigned offA, offB;
+    size_t esA, ssA, esB, ssB;
+    if (!OPA) { baseA = g.A + (size_t)kbeg * g.lda + i0; offA = (unsigned)(tid / BM) * g.lda + tid % BM; esA = (size_t)(256 / BM) * g.lda; ssA = (size_t)BK * g.lda; }
+    else      { baseA = g.A + (size_t)i0 * g.lda + kbeg; offA = (unsigned)(tid / BK) * g.lda + tid % BK; esA = (size_t)(256 / BK) * g.lda; ssA = BK; }
+    if (!OPB) { baseB = g.B + (size_t)j0 * g.ldb + kbeg; offB = (unsigned)(tid / BK) * g.ldb + tid % BK; esB = (size_t)(256 / BK) * g.ldb; ssB = BK; }
+    else      { baseB = g.B + (size_t)kbeg * g.ldb + j0; offB = (unsigned)(tid / BN) * g.ldb + tid % BN; esB = (size_t)(256 / BN) * g.ldb; ssB = (size_t)BK * g.ldb; }
+    int cnext[GATHER ? NA : 1];
+    auto gidx = [&](int s) {
+        if constexpr (GATHER) {
+            const int* kg = g.a_kgather + kbeg + min(s, last) * BK + tid / BM;
+#pragma unroll
+            for (int e = 0; e < NA; ++e) cnext[e] = kg[e * (256 / BM)];
+        }
+    };
+    // gathered A: call with s = 0, 1, 2, ... strictly in order, after gidx(0) -- cnext holds the indices of step s on entry and those of
+    // step s + 1 on return
+    auto gload = [&](int s, cplx (&ra)[NA], cplx (&rb)[NB_]) {
+        const int sc = min(s, last);
+        if constexpr (GATHER) {
+            const cplx* a = g.A + i0 + tid % BM;
+#pragma unroll
+            for (int e = 0; e < NA; ++e) ra[e] = a[(size_t)cnext[e] * g.lda];
+            gidx(s + 1);
+        } else {
+            const cplx* a = baseA + (size_t)sc * ssA;
+#pragma unroll
+            for (int e = 0; e < NA; ++e) ra[e] = (a + e * esA)[offA];
+        }
+        const cplx* b = baseB + (size_t)sc * ssB;
+#pragma unroll
+        for (int e = 0; e < NB_; ++e) rb[e] = (b + e * esB)[offB];
+    };
+    auto sstore = [&](int buf, const cplx (&ra)[NA], const cplx (&rb)[NB_]) {
+#pragma unroll
+        for (int e = 0; e < NA; ++e) {
+            const int idx = tid + e * 256;
+            int i, k;
+            if (!OPA) { i = idx % BM; k = idx / BM; } else { k = idx % BK; i = idx / BK; }
+            sA[buf][k][i] = make_double2(ra[e].x, csgnA * ra[e].y);
+        }
+#pragma unroll
+        for (int e = 0; e < NB_; ++e) {
+            const int idx = tid + e * 256;
+            int j, k;
+            if (!OPB) { k = idx % BK; j = idx / BK; } else { j = idx % BN; k = idx / BN; }
+            sB[buf][k][j] = make_double2(rb[e].x, csgnB * rb[e].y);
+        }
+    };
+    cplx raA[NA], rbA[NB_], raB[NA], rbB[NB_];
+    gidx(0);
+    gload(0, raA, rbA);
+    gload(1, raB, rbB);
+    sstore(0, raA, rbA);
+    __syncthreads();
+    // Steps t and t + 1 per trip while a step t + 2 exists; the loop body has no exit between a batch of loads and the MFMA block
+    // behind it (a loop exit there lets the compiler sink the loads below the MFMAs, onto the path that uses them).  The last one
+    // or two steps follow the loop and request nothing.
+    int t = 0;
+    for (; t + 2 <= last; t += 2) {
+        gload(t + 2, raA, rbA);
+        __builtin_amdgcn_sched_barrier(0);      // the loads stay in front of the MFMA block, their first use behind the next one
+        mfma_tile(0);
+        __builtin_amdgcn_sched_barrier(0);
+        sstore(1, raB, rbB);
+        __syncthreads();       // one barrier per k-step: nobody refills a buffer that a slower wave still reads
+        gload(t + 3, raB, rbB);
+        __builtin_amdgcn_sched_barrier(0);
+        mfma_tile(1);
+        __builtin_amdgcn_sched_barrier(0);
+        sstore(0, raA, rbA);
+        __syncthreads();
+    }
+    mfma_tile(0);
+    if (t < last) {
+        __builtin_amdgcn_sched_barrier(0);
+        sstore(1, raB, rbB);
+        __syncthreads();
+        mfma_tile(1);
+    }
+    } else {
     cplx ra[NA], rb[NB_];
     double rsc[NA];
     bool oka[NA], okb[NB_];
@@ -76,7 +213,6 @@ __global__ __launch_bounds__(256, 2) void k_zgemm(GemmArgs g, size_t cs, int nb)
     // sstore(), i.e. AFTER the MFMAs of the tile before.  (Round 2 applied the select right after the load: the compiler put
     // s_waitcnt vmcnt(..) + v_cndmask in front of the MFMA block, so every tile waited for its successor's loads before it
     // started computing -- the double buffering overlapped nothing.)
-    const int Mm1 = g.M - 1, Nm1 = g.N - 1;
     // column gather of A (a_kgather): the indices of a tile are requested ONE TILE AHEAD, so the dependent index -> element
     // chain never sits in front of an MFMA block
     // Optional operands (gather list, k-scale) are loaded UNCONDITIONALLY, from a stand-in address inside A when absent: a
@@ -165,40 +301,11 @@ __global__ __launch_bounds__(256, 2) void k_zgemm(GemmArgs g, size_t cs, int nb)
         const bool more = k0 + BK < K;
         if (more) gload(k0 + BK);
         __builtin_amdgcn_sched_barrier(0);      // the loads stay in front of the MFMA block, their first use behind it
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += 4) {
-            cplx af[TM], bf[TN];
-#pragma unroll
-            for (int a = 0; a < TM; ++a) af[a] = sA[buf][kk + l4][wm * 16 * TM + a * 16 + l15];
-#pragma unroll
-            for (int b = 0; b < TN; ++b) bf[b] = sB[buf][kk + l4][wn * 16 * TN + b * 16 + l15];
-            double asum[TM], bsum[TN];
-            if (M3) {
-#pragma unroll
-                for (int a = 0; a < TM; ++a) asum[a] = af[a].x + af[a].y;
-#pragma unroll
-                for (int b = 0; b < TN; ++b) bsum[b] = bf[b].x + bf[b].y;
-            }
-#pragma unroll
-            for (int a = 0; a < TM; ++a)
-#pragma unroll
-                for (int b = 0; b < TN; ++b) {
-                    // roles swapped: first operand indexes the OUTPUT "row" (= column j of C)
-                    if (M3) {
-                        acc_re[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[b].x, af[a].x, acc_re[a][b], 0, 0, 0);
-                        acc_p2[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[b].y, af[a].y, acc_p2[a][b], 0, 0, 0);
-                        acc_im[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(bsum[b], asum[a], acc_im[a][b], 0, 0, 0);
-                    } else {
-                        acc_re[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[b].x, af[a].x, acc_re[a][b], 0, 0, 0);
-                        acc_re[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(-bf[b].y, af[a].y, acc_re[a][b], 0, 0, 0);
-                        acc_im[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[b].y, af[a].x, acc_im[a][b], 0, 0, 0);
-                        acc_im[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[b].x, af[a].y, acc_im[a][b], 0, 0, 0);
-                    }
-                }
-        }
+        mfma_tile(buf);
         __builtin_amdgcn_sched_barrier(0);
         if (more) sstore(buf ^ 1);
         __syncthreads();       // one barrier per tile: nobody refills a buffer that a slower wave still reads
+    }
     }
 
     // ---- epilogue: accumulator element r of lane: out-row (=j) = l4 + 4 r, out-col (=i) = l15 ----
@@ -207,13 +314,13 @@ __global__ __launch_bounds__(256, 2) void k_zgemm(GemmArgs g, size_t cs, int nb)
 #pragma unroll
         for (int b = 0; b < TN; ++b) {
             const int gi = i0 + wm * 16 * TM + a * 16 + l15;
-            const int gic = min(gi, Mm1);
+            const int gic = FULL ? gi : min(gi, Mm1);
             cplx cold[4];
             if (g.accumulate) {                                    // the four loads together, bounds by select (see gload)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int gj = j0 + wn * 16 * TN + b * 16 + l4 + 4 * r;
-                    cold[r] = g.C[(size_t)min(gj, Nm1) * g.ldc + gic];
+                    cold[r] = g.C[(size_t)(FULL ? gj : min(gj, Nm1)) * g.ldc + gic];
                 }
             }
 #pragma unroll
@@ -221,15 +328,16 @@ __global__ __launch_bounds__(256, 2) void k_zgemm(GemmArgs g, size_t cs, int nb)
                 const int gj = j0 + wn * 16 * TN + b * 16 + l4 + 4 * r;
                 double re = acc_re[a][b][r], im = acc_im[a][b][r];
                 if (M3) { const double p1 = re, p2 = acc_p2[a][b][r]; re = p1 - p2; im = (im - p1) - p2; }
-                if (g.ksplit > 1) {
+                if (!FULL && g.ksplit > 1) {
                     if (gi < g.M && gj < g.N) g.part[((size_t)blockIdx.y * g.N + gj) * g.M + gi] = make_double2(re, im);
                     continue;
                 }
-                if (g.rowscale) { double sc = g.rowscale[gic]; if (g.colscale) sc *= g.colscale[min(gj, Nm1)]; re *= sc; im *= sc; }
-                else if (g.colscale) { double sc = g.colscale[min(gj, Nm1)]; re *= sc; im *= sc; }
+                const int gjc = FULL ? gj : min(gj, Nm1);
+                if (g.rowscale) { double sc = g.rowscale[gic]; if (g.colscale) sc *= g.colscale[gjc]; re *= sc; im *= sc; }
+                else if (g.colscale) { double sc = g.colscale[gjc]; re *= sc; im *= sc; }
                 if (g.negate) { re = -re; im = -im; }
                 if (g.accumulate) { re += cold[r].x; im += cold[r].y; }
-                if (gi < g.M && gj < g.N) g.C[(size_t)gj * g.ldc + gi] = make_double2(re, im);
+                if (FULL || (gi < g.M && gj < g.N)) g.C[(size_t)gj * g.ldc + gi] = make_double2(re, im);
             }
         }
 }
@@ -601,14 +709,14 @@ __global__ void k_gemm_reduce(const cplx* __restrict__ part, int ksplit, int M, 
     }
 }
 
-template<int TM, int TN, bool M3, int TAG>
+template<int TM, int TN, bool M3, int TAG, int FULL>
 static void launch_gemm_ops(const Launch& lc, const GemmArgs& a, dim3 grid) {
     if (!a.opA) {
-        if (!a.opB) hipLaunchKernelGGL((k_zgemm<TM, TN, M3, TAG, false, false>), grid, dim3(256), 0, lc.st, a, lc.cs, lc.nb);
-        else        hipLaunchKernelGGL((k_zgemm<TM, TN, M3, TAG, false, true>), grid, dim3(256), 0, lc.st, a, lc.cs, lc.nb);
-    } else {
-        if (!a.opB) hipLaunchKernelGGL((k_zgemm<TM, TN, M3, TAG, true, false>), grid, dim3(256), 0, lc.st, a, lc.cs, lc.nb);
-        else        hipLaunchKernelGGL((k_zgemm<TM, TN, M3, TAG, true, true>), grid, dim3(256), 0, lc.st, a, lc.cs, lc.nb);
+        if (!a.opB) hipLaunchKernelGGL((k_zgemm<TM, TN, M3, TAG, false, false, FULL>), grid, dim3(256), 0, lc.st, a, lc.cs, lc.nb);
+        else        hipLaunchKernelGGL((k_zgemm<TM, TN, M3, TAG, false, true, FULL>), grid, dim3(256), 0, lc.st, a, lc.cs, lc.nb);
+    } else if constexpr (FULL != 2) {                      // the gathered A is never transposed
+        if (!a.opB) hipLaunchKernelGGL((k_zgemm<TM, TN, M3, TAG, true, false, FULL>), grid, dim3(256), 0, lc.st, a, lc.cs, lc.nb);
+        else        hipLaunchKernelGGL((k_zgemm<TM, TN, M3, TAG, true, true, FULL>), grid, dim3(256), 0, lc.st, a, lc.cs, lc.nb);
     }
 }
 // Which kernel shape a product takes (launch_gemm): 64 x 64 tiles only when they still give >= 256 workgroups (fill the chip),
@@ -623,7 +731,8 @@ GemmPlan gemm_plan(const GemmArgs& a, int nb) {
     p.tile = 32;
     // split-K: few tiles, long contraction, a scratch buffer offered and no epilogue scaling -> slices of >= 64 k until ~ 512
     // workgroups are in flight (a workgroup's k loop is a chain of dependent trips to memory, 16 k per trip: a slice of 288 k took
-    // 30 us whatever the tile count; round 3 split into at most 8 slices of >= 256 k and only below 128 tiles)
+    // 30 us whatever the tile count; round 3 split into at most 8 slices of >= 256 k and only below 128 tiles).  The slices stay
+    // on the generic kernel with its prefetch distance of one k-step; the whole-tile kernel (gemm_full_path) requests two steps ahead
     const long wg = (long)((a.M + 31) / 32) * ((a.N + 31) / 32) * nb;
     if (a.part && a.K >= 512 && !a.Kdev && !a.kscale && !a.rowscale && !a.colscale && !a.b_lower && wg < 256) {
         const long cap = (long)((a.part_count ? a.part_count : (size_t)a.M * a.N * 8) / ((size_t)a.M * a.N));
@@ -633,31 +742,65 @@ GemmPlan gemm_plan(const GemmArgs& a, int nb) {
     return p;
 }
 
+// The whole-tile instantiation (k_zgemm, FULL) for a product with plan p: 0 no, 1 yes, 2 yes with the column gather of A.  Needs M and
+// N in whole block tiles, K in whole k-steps of 16, K fixed on the host, no k-scale and no split-K; a lower-triangular op(B) must reach
+// down to the last column tile (K >= N: every tile has at least one k-step); offsets inside a tile fit 32 bits.  The gathered variant
+// exists for the untagged products only (the chained factor of a stabilisation step is the one caller).  The developer switch
+// DQMC_GEMM_4M=1 (builds with -DDQMC_DEV_KNOBS) turns the whole-tile path off for EVERY product, the tagged ones included although they
+// stay on 3M: an A/B run then compares generic kernels only -- and tests/test_gpu_gemm_fullpath.py, which asserts that the whole-tile
+// path ran, fails under it.
+static int gemm_full_path(const GemmArgs& a, const GemmPlan& p) {
+    if (p.ksplit > 1 || use_4m() || a.M <= 0 || a.N <= 0 || a.M % p.tile || a.N % p.tile || a.K < 16 || a.K % 16 || a.Kdev || a.kscale) return 0;
+    if (a.b_lower && a.K < a.N) return 0;
+    if (a.lda < 1 || a.ldb < 1 || a.lda > (1 << 22) || a.ldb > (1 << 22)) return 0;
+    const bool gather = a.a_kgather && !a.opA;
+    if (gather && a.tag) return 0;
+    return gather ? 2 : 1;
+}
+
 template<int TAG>
-static void launch_gemm_tagged(const Launch& lc, const GemmArgs& a) {
+static int launch_gemm_tagged(const Launch& lc, const GemmArgs& a, int path) {
     const GemmPlan p = gemm_plan(a, lc.nb);
     const int t = ((a.M + p.tile - 1) / p.tile) * ((a.N + p.tile - 1) / p.tile);
     dim3 grid = p.xcd ? dim3(t * lc.nb, 1, 1) : dim3(t, 1, lc.nb);
+    int full = path == 0 ? 0 : gemm_full_path(a, p);
+    if (full == 2 && TAG != 0) full = 0;          // no gathered whole-tile kernel with a tag: the generic kernel below
+    if (full == 1) {
+        if (p.tile == 64) launch_gemm_ops<2, 2, true, TAG, 1>(lc, a, grid);
+        else              launch_gemm_ops<1, 1, true, TAG, 1>(lc, a, grid);
+        return 1;
+    }
+    if constexpr (TAG == 0) {
+        if (full == 2) {
+            if (p.tile == 64) launch_gemm_ops<2, 2, true, 0, 2>(lc, a, grid);
+            else              launch_gemm_ops<1, 1, true, 0, 2>(lc, a, grid);
+            return 1;
+        }
+    }
     if (p.tile == 64) {
-        if (use_4m() && TAG == 0) launch_gemm_ops<2, 2, false, 0>(lc, a, grid);
-        else                      launch_gemm_ops<2, 2, true, TAG>(lc, a, grid);
+        if (use_4m() && TAG == 0) launch_gemm_ops<2, 2, false, 0, 0>(lc, a, grid);
+        else                      launch_gemm_ops<2, 2, true, TAG, 0>(lc, a, grid);
     } else if (p.ksplit > 1) {
         GemmArgs g2 = a;
         g2.ksplit = p.ksplit; g2.accumulate = 0; g2.negate = 0;
         grid.y = p.ksplit;
-        launch_gemm_ops<1, 1, true, TAG>(lc, g2, grid);
+        launch_gemm_ops<1, 1, true, TAG, 0>(lc, g2, grid);
         hipLaunchKernelGGL(k_gemm_reduce, dim3(std::min(256, (a.M * a.N + 255) / 256), 1, lc.nb), dim3(256), 0, lc.st, a.part, p.ksplit, a.M, a.N,
                            a.C, a.ldc, a.accumulate, a.negate, lc.cs);
     } else {
-        if (use_4m() && TAG == 0) launch_gemm_ops<1, 1, false, 0>(lc, a, grid);
-        else                      launch_gemm_ops<1, 1, true, TAG>(lc, a, grid);
+        if (use_4m() && TAG == 0) launch_gemm_ops<1, 1, false, 0, 0>(lc, a, grid);
+        else                      launch_gemm_ops<1, 1, true, TAG, 0>(lc, a, grid);
     }
+    return 0;
 }
-void launch_gemm(const Launch& lc, const GemmArgs& a) {
+int launch_gemm_path(const Launch& lc, const GemmArgs& a, int path) {
+    int ran;
     if (a.tag) {
         if (lc.sub) lc.sub->begin(lc.sub->user, SUBFAM_FACT_GEMM);
-        launch_gemm_tagged<1>(lc, a);
+        ran = launch_gemm_tagged<1>(lc, a, path);
         if (lc.sub) lc.sub->end(lc.sub->user, SUBFAM_FACT_GEMM, 8.0 * a.M * a.N * a.K * lc.nb,
                                 16.0 * ((double)a.M * a.K + (double)a.K * a.N + (a.accumulate ? 2.0 : 1.0) * a.M * a.N) * lc.nb);
-    } else launch_gemm_tagged<0>(lc, a);
+    } else ran = launch_gemm_tagged<0>(lc, a, path);
+    return ran;
 }
+void launch_gemm(const Launch& lc, const GemmArgs& a) { (void)launch_gemm_path(lc, a, -1); }

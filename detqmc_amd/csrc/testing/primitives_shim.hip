@@ -90,6 +90,15 @@ int dqmc_prim_gemm(void* arena, size_t bytes, int nb, size_t cs, const PrimGemm*
     });
 }
 
+// dqmc_prim_gemm with the kernel path forced: path 0 the generic kernel, 1 the whole-tile kernel where the arguments allow it, -1 as
+// launch_gemm decides.  *ran: the path that ran (0 generic, 1 whole-tile)
+int dqmc_prim_gemm_path(void* arena, size_t bytes, int nb, size_t cs, const PrimGemm* p, int path, int* ran, char* msg, int msglen) {
+    return with_arena(arena, bytes, nb, cs, msg, msglen, [&](void* d, const Launch& lc) {
+        *ran = launch_gemm_path(lc, gemm_args(d, *p), path);
+        return 0;
+    });
+}
+
 // G += X GrT^T, K = min(Kmax, *Kdev * Kmul) (Kdev < 0: Kmax)
 int dqmc_prim_flush(void* arena, size_t bytes, int nb, size_t cs, long long X, long long GrT, int ld, long long G, int ldc, int n,
                     int Kmax, long long Kdev, int Kmul, int tag, char* msg, int msglen) {
