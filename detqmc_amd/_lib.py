@@ -33,7 +33,7 @@ class dqmc_cplx(C.Structure):
 
 class dqmc_tuning(C.Structure):
     _fields_ = [("pipeline", C.c_int32), ("qr_variant", C.c_int32), ("green_variant", C.c_int32),
-                ("max_jacobi_sweeps", C.c_int32), ("proposal_budget", C.c_int32), ("decide_threads", C.c_int32), ("reserved", C.c_int32)]
+                ("max_jacobi_sweeps", C.c_int32), ("proposal_budget", C.c_int32), ("decide_threads", C.c_int32), ("bmult_path", C.c_int32)]
 
 
 class dqmc_schedule_info(C.Structure):
@@ -177,6 +177,7 @@ SYMBOLS = [
     ("dqmc_udv_setup", C.c_int, [_P]),
     ("dqmc_advance", C.c_int, [_P, C.c_int, C.c_int]),
     ("dqmc_wrap", C.c_int, [_P, C.c_int, C.c_int]),
+    ("dqmc_wrap_skip", C.c_int, [_P, C.c_int, C.c_int]),
     ("dqmc_reset_storage0", C.c_int, [_P]),
     ("dqmc_push_uniforms_host", C.c_int, [_P, _DP, C.c_size_t]),
     ("dqmc_push_uniforms_all_host", C.c_int, [_P, _DP, C.c_size_t]),

@@ -148,6 +148,7 @@ struct dqmc_ctx {
     double* scalar_out = nullptr;
     double* shift_buf = nullptr;        // [nchains][opdim] displacements of a global shift move (shared buffer)
     int currentTimeslice = 0;
+    bool g_stale = false;          // dqmc_wrap_skip moved currentTimeslice without computing G: nothing may read G until it is rebuilt
     // profiling
     bool prof = false;
     int prof_depth = 0;                 // open ProfScopes (they nest)
@@ -590,6 +591,7 @@ extern "C" int dqmc_create_batch(const dqmc_params* p, int nchains, dqmc_ctx** o
     if (p->bc < 0 || p->bc > 3) return fail(DQMC_EINVAL, "bc");
     if (p->tuning.decide_threads != 0 && p->tuning.decide_threads != 256 && p->tuning.decide_threads != 512)
         return fail(DQMC_EINVAL, "tuning.decide_threads must be 0, 256 or 512");
+    if (p->tuning.bmult_path < 0 || p->tuning.bmult_path > 2) return fail(DQMC_EINVAL, "tuning.bmult_path must be 0, 1 or 2");
     if (p->stabilisation != DQMC_STAB_SVD && p->stabilisation != DQMC_STAB_QR) return fail(DQMC_EINVAL, "stabilisation");
     if (!(p->dtau > 0)) return fail(DQMC_EINVAL, "dtau");
     if (p->model != DQMC_MODEL_SDW && p->model != DQMC_MODEL_HUBBARD) return fail(DQMC_EINVAL, "model");
@@ -638,6 +640,7 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
     if (p->tuning.proposal_budget != 0) hm.pbudget = p->tuning.proposal_budget < 0 ? 0 : p->tuning.proposal_budget;
     if (hm.pbudget > 0 && hm.pbudget < p->delaySteps) hm.pbudget = p->delaySteps;
     hm.decide_nt = p->tuning.decide_threads;
+    hm.bmult_path = p->tuning.bmult_path;
 #ifdef DQMC_DECIDE_TIMING
     hm.dbg = (getenv("DQMC_DECIDE_TIMING") && atoi(getenv("DQMC_DECIDE_TIMING"))) ? 8 : 0;   // phase timers of k_update_decide; never changes a result
 #endif
@@ -1323,6 +1326,7 @@ extern "C" int dqmc_udv_setup(dqmc_ctx* c) {
     }
     if ((rc = green_from_eye(c, c->storage[n], KIND_R))) return rc;
     c->currentTimeslice = m;
+    c->g_stale = false;
     return finish(c, "dqmc_udv_setup");
 }
 
@@ -1360,6 +1364,7 @@ extern "C" int dqmc_advance(dqmc_ctx* c, int dir, int l) {
         if (rc) return rc;
         std::swap(c->storage[l - 1], c->spare);          // storage[l-1] = UdV_L
         c->currentTimeslice = s * (l - 1);
+        c->g_stale = false;
         return finish(c, "dqmc_advance");
     } else if (dir == DQMC_UP) {
         if (l < 0 || l > n - 1) return fail(DQMC_EINVAL, "advanceUp: l out of range");
@@ -1377,15 +1382,20 @@ extern "C" int dqmc_advance(dqmc_ctx* c, int dir, int l) {
         if (rc) return rc;
         std::swap(c->storage[l + 1], c->spare);
         c->currentTimeslice = k_lp1;
+        c->g_stale = false;
         return finish(c, "dqmc_advance");
     }
     return fail(DQMC_EINVAL, "dir must be DQMC_UP or DQMC_DOWN");
 }
 
+// every entry that reads G refuses while dqmc_wrap_skip has left it stale
+#define G_FRESH(c, who) do { if ((c)->g_stale) return fail(DQMC_EINVAL, who ": G is stale after dqmc_wrap_skip (dqmc_advance, dqmc_udv_setup or dqmc_set_green_host rebuild it)"); } while (0)
+
 // wrapUpGreen / wrapDownGreen (detmodel.h:1236-1259, 1066-1095)
 extern "C" int dqmc_wrap(dqmc_ctx* c, int dir, int k) {
     if (!c) return fail(DQMC_EINVAL, "null ctx");
     (void)hipSetDevice(c->p.device);
+    G_FRESH(c, "wrap");
     if (c->currentTimeslice != k) return fail(DQMC_EINVAL, "wrap: currentTimeslice != k");
     if (dir == DQMC_UP) {
         if (k < 0 || k >= c->m) return fail(DQMC_EINVAL, "wrapUp: k out of range");
@@ -1399,6 +1409,22 @@ extern "C" int dqmc_wrap(dqmc_ctx* c, int dir, int k) {
         c->currentTimeslice = k - 1;
     } else return fail(DQMC_EINVAL, "dir must be DQMC_UP or DQMC_DOWN");
     return finish(c, "dqmc_wrap");
+}
+// the checks and the bookkeeping of dqmc_wrap for a wrap whose G the following dqmc_advance overwrites: nothing is launched
+extern "C" int dqmc_wrap_skip(dqmc_ctx* c, int dir, int k) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    (void)hipSetDevice(c->p.device);
+    G_FRESH(c, "wrap");
+    if (c->currentTimeslice != k) return fail(DQMC_EINVAL, "wrap: currentTimeslice != k");
+    if (dir == DQMC_UP) {
+        if (k < 0 || k >= c->m) return fail(DQMC_EINVAL, "wrapUp: k out of range");
+        c->currentTimeslice = k + 1;
+    } else if (dir == DQMC_DOWN) {
+        if (k < 1 || k > c->m) return fail(DQMC_EINVAL, "wrapDown: k out of range");
+        c->currentTimeslice = k - 1;
+    } else return fail(DQMC_EINVAL, "dir must be DQMC_UP or DQMC_DOWN");
+    c->g_stale = true;
+    return DQMC_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1451,6 +1477,7 @@ extern "C" int dqmc_update_slice_ex(dqmc_ctx* c, int k, int thermalization, int 
     (void)hipSetDevice(c->p.device);
     if (k < 1 || k > c->m) return fail(DQMC_EINVAL, "updateInSlice: k out of range");
     if (c->currentTimeslice != k) return fail(DQMC_EINVAL, "updateInSlice: currentTimeslice != k");
+    G_FRESH(c, "updateInSlice");
     if (proposal < DQMC_PROPOSE_BOX || proposal > DQMC_PROPOSE_ROTATE_AND_SCALE) return fail(DQMC_EINVAL, "updateInSlice: unknown proposal kind");
     if (proposal != DQMC_PROPOSE_BOX && (c->p.opdim != 3 || c->hm.hubbard))
         return fail(DQMC_EINVAL, "rotate / scale proposals are only supported for the O(3) model");      // detsdwopdim.cpp:3938, 4012, 4085
@@ -1598,6 +1625,7 @@ extern "C" int dqmc_gemm_host(dqmc_ctx* c, int opA, int opB, const dqmc_cplx* A,
 
 extern "C" int dqmc_get_green_host(dqmc_ctx* c, dqmc_cplx* out) {
     if (!c || !out) return fail(DQMC_EINVAL, "null argument");
+    G_FRESH(c, "dqmc_get_green_host");
     (void)hipSetDevice(c->p.device);
     HIPCHK(hipStreamSynchronize(c->st));
     HIPCHK(copy_sync(c, out, selp(c, c->G), (size_t)c->n_g * c->n_g * sizeof(cplx), hipMemcpyDeviceToHost));
@@ -1609,6 +1637,7 @@ extern "C" int dqmc_set_green_host(dqmc_ctx* c, const dqmc_cplx* in, int current
     HIPCHK(hipStreamSynchronize(c->st));
     HIPCHK(copy_sync(c, selp(c, c->G), in, (size_t)c->n_g * c->n_g * sizeof(cplx), hipMemcpyHostToDevice));
     c->currentTimeslice = currentTimeslice;
+    c->g_stale = false;
     return DQMC_OK;
 }
 extern "C" int dqmc_get_sv_host(dqmc_ctx* c, double* out) {
@@ -1651,6 +1680,7 @@ static void swap_state(dqmc_ctx* c) {
 }
 extern "C" int dqmc_backup(dqmc_ctx* c) {
     if (!c) return fail(DQMC_EINVAL, "null ctx");
+    G_FRESH(c, "dqmc_backup");
     (void)hipSetDevice(c->p.device);
     const size_t nphi = (size_t)(c->m + 1) * c->p.opdim * c->N, ncs = (size_t)(c->m + 1) * c->N;
     launch_copy_bytes(c->lc, c->phi, c->phi_bak, nphi * sizeof(double));
@@ -1677,6 +1707,7 @@ extern "C" int dqmc_restore(dqmc_ctx* c) {
     }
 #undef CP_
     c->currentTimeslice = c->m;
+    c->g_stale = false;                  // backups are only ever taken of a fresh G
     return finish(c, "dqmc_restore");
 }
 
@@ -1703,6 +1734,7 @@ static void shift_green_dev(dqmc_ctx* c, const cplx* src = nullptr) {
 extern "C" int dqmc_shift_green_symmetric_host(dqmc_ctx* c, dqmc_cplx* out) {
     if (!c || !out) return fail(DQMC_EINVAL, "null argument");
     if (c->hm.hubbard) return fail(DQMC_EINVAL, "shiftGreenSymmetric belongs to the SDW model");
+    G_FRESH(c, "dqmc_shift_green_symmetric_host");
     (void)hipSetDevice(c->p.device);
     shift_green_dev(c);
     HIPCHK(hipStreamSynchronize(c->st));
@@ -1730,6 +1762,7 @@ extern "C" int dqmc_measure_reset(dqmc_ctx* c) {
 }
 extern "C" int dqmc_measure_slice(dqmc_ctx* c) {
     if (!c) return fail(DQMC_EINVAL, "null ctx");
+    G_FRESH(c, "dqmc_measure_slice");
     (void)hipSetDevice(c->p.device);
     if (c->hm.hubbard) {            // DetHubbard::measure (dethubbard.cpp:521-545): accumulator layout in kernels_hubbard.hip
         ProfScope ps(c, FAM_OTHER, 1);
@@ -1846,6 +1879,7 @@ extern "C" int dqmc_measure_timedisplaced_ph(dqmc_ctx* c, int j) {
     if (j < 1 || j > c->n - 1) return fail(DQMC_EINVAL, "boundary index j must be in 1..n-1");
     if (c->td_slice != c->s * j) return fail(DQMC_EINVAL, "the last time-displaced pair does not belong to boundary j");
     if (c->currentTimeslice != c->s * j) return fail(DQMC_EINVAL, "the context has left boundary j: G is no longer G(tau_j)");
+    G_FRESH(c, "time-displaced measurement");
     (void)hipSetDevice(c->p.device);
     shift_green_dev(c);
     { ProfScope ps(c, FAM_OTHER, 1); launch_td_ph_onebody(c->lc, c->hm, c->T1, c->ph_ob, 0); }
@@ -1874,6 +1908,7 @@ extern "C" int dqmc_measure_timedisplaced_current(dqmc_ctx* c, int j) {
     if (j < 1 || j > c->n - 1) return fail(DQMC_EINVAL, "boundary index j must be in 1..n-1");
     if (c->td_slice != c->s * j) return fail(DQMC_EINVAL, "the last time-displaced pair does not belong to boundary j");
     if (c->currentTimeslice != c->s * j) return fail(DQMC_EINVAL, "the context has left boundary j: G is no longer G(tau_j)");
+    G_FRESH(c, "time-displaced measurement");
     (void)hipSetDevice(c->p.device);
     shift_green_dev(c);
     { ProfScope ps(c, FAM_OTHER, 1); launch_td_current_onebody(c->lc, c->hm, c->T1, c->cur_bt, c->cur_ob, 0); }
@@ -1965,6 +2000,7 @@ extern "C" int dqmc_measure_timedisplaced_segment(dqmc_ctx* c, int j) {
     if (j < 1 || j > c->n - 1) return fail(DQMC_EINVAL, "boundary index j must be in 1..n-1");
     if (c->td_slice != c->s * j) return fail(DQMC_EINVAL, "the last time-displaced pair does not belong to boundary j");
     if (c->currentTimeslice != c->s * j) return fail(DQMC_EINVAL, "the context has left boundary j: G is no longer G(tau_j)");
+    G_FRESH(c, "time-displaced measurement");
     (void)hipSetDevice(c->p.device);
     const int s = c->s, k0 = s * j, k1 = (s * (j + 1) < c->m ? s * (j + 1) : c->m) - 1;
     td_fine_onebody(c, c->G00, 1);            // G(0) does not move with tau: once per segment
@@ -1990,6 +2026,7 @@ extern "C" int dqmc_td_fine_propagate(dqmc_ctx* c, int j, int k) {
     if (j < 1 || j > c->n - 1) return fail(DQMC_EINVAL, "boundary index j must be in 1..n-1");
     if (c->td_slice != c->s * j) return fail(DQMC_EINVAL, "the last time-displaced pair does not belong to boundary j");
     if (c->currentTimeslice != c->s * j) return fail(DQMC_EINVAL, "the context has left boundary j: G is no longer G(tau_j)");
+    G_FRESH(c, "time-displaced measurement");
     const int s = c->s, k0 = s * j, k1 = (s * (j + 1) < c->m ? s * (j + 1) : c->m) - 1;
     if (k > k1 || k < (j == 1 ? 1 : k0)) return fail(DQMC_EINVAL, "slice k does not belong to the segment of boundary j");
     (void)hipSetDevice(c->p.device);
@@ -2003,6 +2040,7 @@ extern "C" int dqmc_measure_timedisplaced_ends(dqmc_ctx* c) {
     if (!c->td_fine) return fail(DQMC_EINVAL, "context created without DQMC_TD_EVERY_SLICE");
     if (c->currentTimeslice != 0 && c->currentTimeslice != c->m)
         return fail(DQMC_EINVAL, "the context does not stand at tau = 0 (beta): G is not G(0)");
+    G_FRESH(c, "dqmc_measure_timedisplaced_ends");
     (void)hipSetDevice(c->p.device);
     // row m from the work copies (they are what dqmc_get_green_td_fine_host reports afterwards), row 0 from T2 / T3: scratch of the
     // Green's function routines, idle here (the shifts use T1 and, with the dense B, Tdense only)

@@ -88,6 +88,7 @@ struct DevModel {
     int opdim, MSF, L, N, ng, m, s, n, D, P;   // P = plaquettes per subgroup = N/4
     int phi2bosons;
     int decide_nt;     // threads per workgroup of k_update_decide: 0 automatic, 256, 512 (dqmc_tuning::decide_threads)
+    int bmult_path;    // checkerboard B-multiply kernel: 0 automatic, 1 k_bmult_chain, 2 k_bmult_direct where it applies (dqmc_tuning::bmult_path)
     int pbudget;       // proposals per delayed-update block (0: no limit); a launch-balancing knob, the chain does not depend on it
     int dbg;           // bit 3: phase timers of k_update_decide; only ever set in builds with -DDQMC_DECIDE_TIMING (always 0 otherwise)
     int dense;         // CB_NONE: the hopping part is a dense GEMM done by the host loop, the chain kernel

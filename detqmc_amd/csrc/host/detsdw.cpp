@@ -280,16 +280,17 @@ void DetSDW::measureTimeDisplacedEnds(Group& g) {
 // detmodel.h:1333-1399
 void DetSDW::sweepDown(Group& g, bool thermalization) {
     dqmc_ctx* ctx_ = g.ctx;
+    // the last wrap of every segment is dead: the advance that follows rebuilds G from the UdV factors (dqmc_wrap_skip)
     for (int k = m_; k >= (n_ - 1) * s_ + 1; --k) {
         updateInSlice(g, k, thermalization);
-        check(dqmc_wrap(ctx_, DQMC_DOWN, k), "wrapDownGreen");
+        check(k > (n_ - 1) * s_ + 1 ? dqmc_wrap(ctx_, DQMC_DOWN, k) : dqmc_wrap_skip(ctx_, DQMC_DOWN, k), "wrapDownGreen");
     }
     for (int l = n_ - 1; l >= 1; --l) {
         check(dqmc_advance(ctx_, DQMC_DOWN, l + 1), "advanceDownGreen");
         measureTimeDisplaced(g, l);
         for (int k = l * s_; k >= (l - 1) * s_ + 1; --k) {
             updateInSlice(g, k, thermalization);
-            check(dqmc_wrap(ctx_, DQMC_DOWN, k), "wrapDownGreen");
+            check(k > (l - 1) * s_ + 1 ? dqmc_wrap(ctx_, DQMC_DOWN, k) : dqmc_wrap_skip(ctx_, DQMC_DOWN, k), "wrapDownGreen");
         }
     }
     check(dqmc_advance(ctx_, DQMC_DOWN, 1), "advanceDownGreen");

@@ -360,9 +360,224 @@ __global__ __launch_bounds__(512, MSF == 2 ? 4 : 2) void k_bmult_chain(DevModel 
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Direct path (checkerboard launches outside shift mode): the first plaquette pass of a launch takes its operands straight
+// from global memory and the last one stores straight to it, and between two slices of a chain the trailing sub-1 half step
+// of slice k and the leading one of the next slice are ONE pass.  Every pass works on items (plaquette p, vector v) that hold
+// all MSF bands of the four sites, as the fused pass of k_bmult_chain does.  LDS round trips per element: 2 for a single
+// slice (4 in k_bmult_chain), 2 s for s slices (3 s + 1).  Per element the floating-point operations and their order are
+// those of k_bmult_chain: the two kernels give the same bits.
+// ---------------------------------------------------------------------------------------------
+// e^{-+dtau V_k} (with the chemical-potential factor) on the four sites of an item: the vmix of k_bmult_chain
+template<int MSF, bool RIGHT, bool INV, bool CDW>
+__device__ __forceinline__ void direct_site_mix(const DevModel& dm, int k, const int (&site)[4], cplx (&x)[MSF][4]) {
+    constexpr bool PASSES_FIRST = (RIGHT == INV);
+    const double vsign = INV ? +1.0 : -1.0;
+    const int N = dm.N;
+    const double* ph = dm.phi + (size_t)k * dm.opdim * N;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int i = site[q];
+        const double c = dm.coshT[(size_t)k * N + i];
+        double xs = dm.sinhT[(size_t)k * N + i], c0, c1;
+        if constexpr (CDW) cdw_site_terms(dm, (size_t)k * N + i, vsign, c, c0, c1, xs); else { c0 = c; c1 = c; }
+        const double p0 = ph[i];
+        const double p1 = dm.opdim > 1 ? ph[N + i] : 0.0;
+        const double p2 = dm.opdim > 2 ? ph[2 * N + i] : 0.0;
+        cplx V[MSF][MSF];
+        build_V<MSF>(V, vsign, c0, c1, xs, p0, p1, p2);
+        cplx in[MSF], out[MSF];
+#pragma unroll
+        for (int b = 0; b < MSF; ++b) in[b] = x[b][q];
+        if (PASSES_FIRST) {
+#pragma unroll
+            for (int b = 0; b < MSF; ++b) in[b] = cscale(in[b], INV ? dm.ovinv[b & 1] : dm.ov[b & 1]);
+        }
+#pragma unroll
+        for (int o = 0; o < MSF; ++o) {
+            cplx acc = make_double2(0.0, 0.0);
+#pragma unroll
+            for (int b = 0; b < MSF; ++b) {
+                const cplx vv = RIGHT ? V[b][o] : V[o][b];
+                acc = cfma(vv, in[b], acc);
+            }
+            if (!PASSES_FIRST) acc = cscale(acc, INV ? dm.ovinv[o & 1] : dm.ov[o & 1]);
+            out[o] = acc;
+        }
+#pragma unroll
+        for (int b = 0; b < MSF; ++b) x[b][q] = out[b];
+    }
+}
+// the 4 x 4 plaquette exponential of sub-lattice `sub` on every band of an item
+// (REALT: the real four-entry tables, DevModel::pm_real -- a template parameter here: as a run-time branch next to the complex
+// path the kernel does not fit its register budget without scratch.  Complex tables exist for opdim == 2 only, so MSF == 2.)
+template<int MSF, bool RIGHT, bool INV, bool REALT>
+__device__ __forceinline__ void direct_plaq_step(const DevModel& dm, int sub, int p, cplx (&x)[MSF][4]) {
+    const int signIdx = INV ? 1 : 0;
+    const int P = dm.P;
+#pragma unroll
+    for (int b = 0; b < MSF; ++b) {
+        const int tbl = ((b & 1) * 2 + signIdx) * 2 + sub;
+        cplx y[4];
+        if constexpr (REALT) {
+            double co[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) co[q] = dm.pabcd[(tbl * 4 + q) * P + p];
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                cplx acc = make_double2(0.0, 0.0);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const double m = co[a ^ q];
+                    acc.x = fma(m, x[b][q].x, acc.x);
+                    acc.y = fma(m, x[b][q].y, acc.y);
+                }
+                y[a] = acc;
+            }
+        } else if (!dm.pm_real) {
+            // (always taken in this instantiation.  The run-time test keeps every band's 16 matrix entries in a basic block of their
+            // own: as straight-line code the compiler requests those of all bands and of both half steps of a slice boundary at
+            // once and spills hundreds of bytes per lane)
+            const cplx* mat = dm.pmats + (size_t)tbl * 16 * P + p;
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                cplx acc = make_double2(0.0, 0.0);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const cplx mm = RIGHT ? mat[(size_t)(q * 4 + a) * P] : mat[(size_t)(a * 4 + q) * P];
+                    acc = cfma(mm, x[b][q], acc);
+                }
+                y[a] = acc;
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) x[b][q] = y[q];
+            continue;
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) x[b][q] = y[q];
+    }
+}
+
+// register budget: that of k_bmult_chain with the real tables; the complex-table instantiations get that of two waves per SIMD
+template<int MSF, bool RIGHT, bool INV, bool CDW, bool REALT>
+__global__ __launch_bounds__(512, (MSF == 2 && REALT) ? 4 : 2) void k_bmult_direct(DevModel dm, cplx* __restrict__ A, int lda, int nvec,
+                                                       int kfirst, int kstep, int kcount, size_t cs) {
+    extern __shared__ cplx sm[];
+    dm = chain_model(dm, cs); CHAIN(A);
+    const int N = dm.N, ng = dm.ng, P = dm.P;
+    const int v0 = blockIdx.x * nvec;
+    const int nv = min(nvec, ng - v0);
+    if (nv <= 0) return;
+    const int tid = threadIdx.x, nth = blockDim.x;
+    // the tile of k_bmult_chain: LDS address and global element e of vector v
+    const int rstride = nvec + 1;
+    auto addr = [&](int v, int e) -> int { return RIGHT ? (e * rstride + v) : (v * ng + e); };
+    // byte offsets in 32 bits (the launcher sends larger matrices to k_bmult_chain): one uniform base and a 32-bit lane offset per
+    // access instead of a 64-bit address per element in flight
+    auto gptr = [&](int v, int e) -> cplx* {
+        const unsigned el = RIGHT ? (unsigned)e * (unsigned)lda + (unsigned)(v0 + v) : (unsigned)(v0 + v) * (unsigned)lda + (unsigned)e;
+        return (cplx*)((char*)A + (size_t)(el * 16u));
+    };
+    constexpr bool PASSES_FIRST = (RIGHT == INV);   // left B, right B^-1: hopping part acts first
+    // items (p, v).  RIGHT: v fastest over the lanes -- the lanes of a tile row are one 128-byte piece of a column, the global
+    // access shape of the staging loops of k_bmult_chain.  LEFT: p fastest -- with the x-fastest plaquette order the corners
+    // (0, 1) and (2, 3) of a wave's plaquettes are x-neighbours and cover whole lines between them.
+    const int items = nv * P;
+    auto item = [&](int idx, int sub, int& p, int& v, int (&site)[4]) {
+        if (RIGHT) { v = idx % nv; p = idx / nv; } else { p = idx % P; v = idx / P; }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) site[q] = dm.psites[(sub * 4 + q) * P + p];
+    };
+
+    // ---- first pass: global -> sub-1 half step (after e^{-+dtau V} of the first slice where that acts first) -> LDS ----
+    // in place is safe: the tile belongs to this workgroup alone and every global load precedes the first barrier, every
+    // global store follows it
+    for (int idx = tid; idx < items; idx += nth) {
+        int p, v, site[4];
+        item(idx, 1, p, v, site);
+        cplx x[MSF][4];
+#pragma unroll
+        for (int b = 0; b < MSF; ++b)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) x[b][q] = nt_load(gptr(v, b * N + site[q]));      // all requested before the first use
+        if (!PASSES_FIRST) direct_site_mix<MSF, RIGHT, INV, CDW>(dm, kfirst, site, x);
+        direct_plaq_step<MSF, RIGHT, INV, REALT>(dm, 1, p, x);
+#pragma unroll
+        for (int b = 0; b < MSF; ++b)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) sm[addr(v, b * N + site[q])] = x[b][q];
+    }
+    __syncthreads();
+
+    for (int kc = 0; kc < kcount; ++kc) {
+        const int k = kfirst + kc * kstep;
+        const bool last = kc == kcount - 1;
+        // ---- sub 0, full step: LDS -> LDS ----
+        for (int idx = tid; idx < items; idx += nth) {
+            int p, v, site[4];
+            item(idx, 0, p, v, site);
+            cplx x[MSF][4];
+#pragma unroll
+            for (int b = 0; b < MSF; ++b)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) x[b][q] = sm[addr(v, b * N + site[q])];
+            direct_plaq_step<MSF, RIGHT, INV, REALT>(dm, 0, p, x);
+#pragma unroll
+            for (int b = 0; b < MSF; ++b)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) sm[addr(v, b * N + site[q])] = x[b][q];
+        }
+        __syncthreads();
+        // ---- sub 1: the trailing half step of slice k, then either the store to global memory or, in registers, the site mix
+        // between the slices and the leading half step of the next slice ----
+        for (int idx = tid; idx < items; idx += nth) {
+            int p, v, site[4];
+            item(idx, 1, p, v, site);
+            cplx x[MSF][4];
+#pragma unroll
+            for (int b = 0; b < MSF; ++b)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) x[b][q] = sm[addr(v, b * N + site[q])];
+            direct_plaq_step<MSF, RIGHT, INV, REALT>(dm, 1, p, x);
+            if (PASSES_FIRST) direct_site_mix<MSF, RIGHT, INV, CDW>(dm, k, site, x);
+            if (last) {
+#pragma unroll
+                for (int b = 0; b < MSF; ++b)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) nt_store(gptr(v, b * N + site[q]), x[b][q]);
+            } else {
+                if (!PASSES_FIRST) direct_site_mix<MSF, RIGHT, INV, CDW>(dm, k + kstep, site, x);
+                direct_plaq_step<MSF, RIGHT, INV, REALT>(dm, 1, p, x);
+#pragma unroll
+                for (int b = 0; b < MSF; ++b)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) sm[addr(v, b * N + site[q])] = x[b][q];
+            }
+        }
+        if (!last) __syncthreads();
+    }
+}
+
+// Which launches take k_bmult_direct: checkerboard, not in shift mode, and DevModel::bmult_path (dqmc_tuning::bmult_path) 2, or 0
+// ("automatic") for the launch kinds where the direct kernel measured faster
+static bool bmult_use_direct(const DevModel& hm, int side, int kcount, int shift, int lda) {
+    if (shift || hm.dense || kcount < 1) return false;
+    if (hm.MSF == 4 && !hm.pm_real) return false;      // no such model (a flux needs opdim == 2): not instantiated
+    if ((size_t)hm.ng * lda * sizeof(cplx) > 0xffffffffull) return false;      // the kernel's 32-bit byte offsets
+    static const int env_p = dev_knob("DQMC_BMULT_PATH") ? atoi(dev_knob("DQMC_BMULT_PATH")) : 0;      // developer knob
+    const int path = hm.bmult_path ? hm.bmult_path : env_p;
+    if (path == 1) return false;
+    if (path == 2) return true;
+    // automatic (measured at the headline shape, 128 chains of n_g = 512): RIGHT launches and LEFT chains of two or more
+    // slices are faster on the direct kernel; a single-slice LEFT launch is slower there (295 - 305 us against 219 us: its first
+    // pass reads 16-byte pieces 32 bytes apart, two instructions per line) and stays on k_bmult_chain
+    return side == DQMC_RIGHT || kcount >= 2;
+}
+
 void launch_bmult(const Launch& lc, const DevModel* /*dm*/, const DevModel& hm, int side, int inverse,
                   int kfirst, int kstep, int kcount, cplx* A, int lda, int shift) {
     const int ng = hm.ng;
+    const bool direct = bmult_use_direct(hm, side, kcount, shift, lda);
     // LEFT: <= 64 KiB of LDS; RIGHT: up to 144 KiB (one workgroup per CU then, two below 80 KiB) so that a row tile can be
     // 8 rows = one full 128-byte line of every column
     const size_t lds_cap = side == DQMC_LEFT ? 65536 : 144 * 1024;
@@ -388,18 +603,21 @@ void launch_bmult(const Launch& lc, const DevModel* /*dm*/, const DevModel& hm, 
     const size_t lds = (size_t)(side == DQMC_LEFT ? nvec : nvec + 1) * ng * sizeof(cplx);
     if (lds > 48 * 1024) {      // raise the dynamic-LDS limit of the instantiation once per device
         static std::mutex mu;
-        static size_t raised_tab[64][16] = {};
+        static size_t raised_tab[64][48] = {};
         int dev = 0;
         (void)hipGetDevice(&dev);
-        const int slot = (hm.cdw_on ? 8 : 0) + (hm.MSF == 4 ? 4 : 0) + (side == DQMC_LEFT ? 0 : 2) + (inverse ? 1 : 0);
+        const int slot = (direct ? (hm.pm_real ? 32 : 16) : 0) + (hm.cdw_on ? 8 : 0) + (hm.MSF == 4 ? 4 : 0) + (side == DQMC_LEFT ? 0 : 2) + (inverse ? 1 : 0);
         std::lock_guard<std::mutex> lk(mu);
         size_t& raised = raised_tab[dev & 63][slot];
         if (lds > raised) {
             const void* f = nullptr;
-#define BM_F(MSFV, R, I) (hm.cdw_on ? (const void*)k_bmult_chain<MSFV, R, I, true> : (const void*)k_bmult_chain<MSFV, R, I, false>)
+#define BM_D(MSFV, R, I, C) ((hm.pm_real || MSFV == 4) ? (const void*)k_bmult_direct<MSFV, R, I, C, true> : (const void*)k_bmult_direct<2, R, I, C, false>)
+#define BM_F(MSFV, R, I) (direct ? (hm.cdw_on ? BM_D(MSFV, R, I, true) : BM_D(MSFV, R, I, false)) \
+                                 : (hm.cdw_on ? (const void*)k_bmult_chain<MSFV, R, I, true> : (const void*)k_bmult_chain<MSFV, R, I, false>))
             if (hm.MSF == 2) f = side == DQMC_LEFT ? (inverse ? BM_F(2, false, true) : BM_F(2, false, false)) : (inverse ? BM_F(2, true, true) : BM_F(2, true, false));
             else             f = side == DQMC_LEFT ? (inverse ? BM_F(4, false, true) : BM_F(4, false, false)) : (inverse ? BM_F(4, true, true) : BM_F(4, true, false));
 #undef BM_F
+#undef BM_D
             if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) raised = lds;
             else (void)hipGetLastError();      // the launch below then reports the problem
         }
@@ -408,8 +626,13 @@ void launch_bmult(const Launch& lc, const DevModel* /*dm*/, const DevModel& hm, 
     // number of resident waves (the only thing that hides the LDS / memory latency of this streaming kernel) the same
     static const int env_t = dev_knob("DQMC_BMULT_THREADS_R") ? atoi(dev_knob("DQMC_BMULT_THREADS_R")) : 0;
     const int nthreads = (side == DQMC_LEFT) ? 256 : (env_t ? env_t : (nvec >= 8 ? 512 : 256));
+    // the direct path keeps the tile shapes, LDS footprint and thread counts of the rule above
+#define LAUNCH_DT(MSFV, R, I, C, T) hipLaunchKernelGGL((k_bmult_direct<MSFV, R, I, C, T>), dim3(grid, 1, lc.nb), dim3(nthreads), lds, lc.st, hm, A, lda, \
+                                                      nvec, kfirst, kstep, kcount, lc.cs)
+#define LAUNCH_D(MSFV, R, I, C) do { if (hm.pm_real || MSFV == 4) LAUNCH_DT(MSFV, R, I, C, true); else LAUNCH_DT(2, R, I, C, false); } while (0)
 #define LAUNCH(MSFV, R, I)                                                                              \
-    do { if (hm.cdw_on) hipLaunchKernelGGL((k_bmult_chain<MSFV, R, I, true>), dim3(grid, 1, lc.nb), dim3(nthreads), lds, lc.st, hm, A, lda, nvec, \
+    do { if (direct) { if (hm.cdw_on) LAUNCH_D(MSFV, R, I, true); else LAUNCH_D(MSFV, R, I, false); }   \
+         else if (hm.cdw_on) hipLaunchKernelGGL((k_bmult_chain<MSFV, R, I, true>), dim3(grid, 1, lc.nb), dim3(nthreads), lds, lc.st, hm, A, lda, nvec, \
                                            kfirst, kstep, kcount, shift, lc.cs);                        \
          else hipLaunchKernelGGL((k_bmult_chain<MSFV, R, I, false>), dim3(grid, 1, lc.nb), dim3(nthreads), lds, lc.st, hm, A, lda, nvec, \
                                  kfirst, kstep, kcount, shift, lc.cs); } while (0)
@@ -421,6 +644,8 @@ void launch_bmult(const Launch& lc, const DevModel* /*dm*/, const DevModel& hm, 
         else                   { if (!inverse) LAUNCH(4, true, false);  else LAUNCH(4, true, true); }
     }
 #undef LAUNCH
+#undef LAUNCH_D
+#undef LAUNCH_DT
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -79,6 +79,7 @@ class SDWParams:
     maxJacobiSweeps: int = 0     # SVD mode: sweep budget of the Jacobi SVD (0 = 80)
     proposalBudget: int = 0      # proposals per delayed-update block (-1: no limit)
     decideThreads: int = 0       # threads per workgroup of the decision kernel (0: automatic, 256, 512); launch shape only
+    bmultPath: int = 0           # checkerboard B-multiply kernel (0: automatic, 1: staged, 2: direct wherever it applies); same bits
 
 
 # observables with a Matsubara transform (DetSDW.matsubara): name -> index of detsdw_get_observable_vector
@@ -165,10 +166,10 @@ PROPOSE = {"box": 0, "rotate": 1, "scale": 2, "rotate_and_scale": 3}
 ADAPT = {"box": 0, "rotate": 1, "scale": 2}
 
 
-def _tuning(pipeline=0, qrVariant=0, greenVariant=0, maxJacobiSweeps=0, proposalBudget=0, decideThreads=0):
+def _tuning(pipeline=0, qrVariant=0, greenVariant=0, maxJacobiSweeps=0, proposalBudget=0, decideThreads=0, bmultPath=0):
     return _lib.dqmc_tuning(pipeline=int(pipeline), qr_variant=int(qrVariant), green_variant=int(greenVariant),
                             max_jacobi_sweeps=int(maxJacobiSweeps), proposal_budget=int(proposalBudget),
-                            decide_threads=int(decideThreads))
+                            decide_threads=int(decideThreads), bmult_path=int(bmultPath))
 
 
 def _fmat(a):
@@ -182,7 +183,7 @@ class KernelContext:
     def __init__(self, opdim, L, m, s, dtau, delaySteps=16, bc="pbc", weakZflux=False, r=-1.0, c=3.0, u=1.0,
                  lambda_=1.0, txhor=-1.0, txver=-0.5, tyhor=0.5, tyver=1.0, mux=-0.5, muy=-0.5,
                  accRatio=0.5, phi2bosons=False, device=0, stabilisation="svd", checkerboard=True, nchains=1, cdwU=0.0,
-                 pipeline=0, qrVariant=0, greenVariant=0, maxJacobiSweeps=0, proposalBudget=0, rngWindowPerSite=0, decideThreads=0,
+                 pipeline=0, qrVariant=0, greenVariant=0, maxJacobiSweeps=0, proposalBudget=0, rngWindowPerSite=0, decideThreads=0, bmultPath=0,
                  timeDisplaced=False, tdParticleHole=False, tdCurrent=False, tdEverySlice=False):
         self.lib = load()
         p = _lib.dqmc_params(opdim=opdim, L=L, m=m, s=s, delaySteps=delaySteps, bc=BC[bc],
@@ -190,7 +191,7 @@ class KernelContext:
                              stabilisation=STABILISATION[stabilisation], cb_none=int(not checkerboard), dtau=dtau, r=r, c=c, u=u, lambda_=lambda_, txhor=txhor, txver=txver,
                              tyhor=tyhor, tyver=tyver, mux=mux, muy=muy, accRatio=accRatio, cdwU=cdwU, rng_window_per_site=int(rngWindowPerSite),
                              timedisplaced=int(timeDisplaced) | (_lib.DQMC_TD_EVERY_SLICE if tdEverySlice else 0), td_particle_hole=(2 if tdCurrent else int(tdParticleHole)),
-                             tuning=_tuning(pipeline, qrVariant, greenVariant, maxJacobiSweeps, proposalBudget, decideThreads))
+                             tuning=_tuning(pipeline, qrVariant, greenVariant, maxJacobiSweeps, proposalBudget, decideThreads, bmultPath))
         h = C.c_void_p()
         check(self.lib.dqmc_create_batch(C.byref(p), nchains, C.byref(h)))
         self.h = h
@@ -525,6 +526,10 @@ class KernelContext:
     def wrapUpGreen(self, k):
         check(self.lib.dqmc_wrap(self.h, UP, k))
 
+    def wrapSkip(self, direction, k):
+        """dqmc_wrap_skip: the bookkeeping of a wrap whose G the following advance overwrites; G is stale until then"""
+        check(self.lib.dqmc_wrap_skip(self.h, direction, k))
+
     def reset_storage0(self):
         check(self.lib.dqmc_reset_storage0(self.h))
 
@@ -677,7 +682,7 @@ def _host_params(pars: SDWParams):
         | (_lib.DETSDW_TD_EVERY_SLICE if pars.timeDisplacedEverySlice else 0)      # without timeDisplacedMeasurements: ParameterWrong from the library
         | (_lib.DETSDW_TD_FINE_ON_DEVICE if pars.timeDisplacedFineOnDevice else 0),  # without timeDisplacedEverySlice: the same
         timeDisplacedParticleHole=(2 if pars.timeDisplacedCurrent else int(bool(pars.timeDisplacedParticleHole))),
-        tuning=_tuning(pars.pipeline, pars.qrVariant, pars.greenVariant, pars.maxJacobiSweeps, pars.proposalBudget, pars.decideThreads))
+        tuning=_tuning(pars.pipeline, pars.qrVariant, pars.greenVariant, pars.maxJacobiSweeps, pars.proposalBudget, pars.decideThreads, pars.bmultPath))
 
 
 class DetSDW:

@@ -71,7 +71,10 @@ typedef struct dqmc_tuning {
                                   limit, > 0 that many (at least delaySteps) */
     int32_t decide_threads;    /* threads per workgroup of the decision kernel: 0 automatic (512 for O(1) / O(2) contexts of at most 32
                                   chains, else 256), 256, 512 (O(3): always 256).  Launch shape only: the chain does not depend on it */
-    int32_t reserved;
+    int32_t bmult_path;        /* checkerboard B-multiply kernel: 0 automatic (the direct kernel for the launch kinds where it measured
+                                  faster), 1: the staged kernel k_bmult_chain everywhere, 2: the direct kernel wherever it
+                                  applies (checkerboard launches outside shift mode).  Both give the same bits.  Other values:
+                                  DQMC_EINVAL.  (The field took the last reserved slot: the bytes of the struct are where they were.) */
 } dqmc_tuning;
 
 /* ModelParamsDetSDW fields the kernels depend on (src/detsdwparams.h:24-120) */
@@ -203,6 +206,11 @@ int dqmc_advance(dqmc_ctx* ctx, int dir, int l);
 /* wrapUpGreen(k): G <- B_{k+1} G B_{k+1}^-1 ; wrapDownGreen(k): G <- B_k^-1 G B_k
  * (detmodel.h:1236-1259, 1066-1095) */
 int dqmc_wrap(dqmc_ctx* ctx, int dir, int k);
+/* A wrap whose result nobody reads: the checks of dqmc_wrap, currentTimeslice moves as there, nothing is launched and G is
+ * marked stale.  For the last wrap of a segment of a down sweep, which the dqmc_advance that follows overwrites (it rebuilds G
+ * from the UdV factors).  While G is stale every entry that reads G (update, wrap, measure, get / shift Green, backup, ...)
+ * returns DQMC_EINVAL; dqmc_advance, dqmc_udv_setup and dqmc_set_green_host clear the mark. */
+int dqmc_wrap_skip(dqmc_ctx* ctx, int dir, int k);
 /* sweepUp resets storage[0] to the identity (detmodel.h:1293-1295) */
 int dqmc_reset_storage0(dqmc_ctx* ctx);
 
