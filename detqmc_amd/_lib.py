@@ -24,6 +24,7 @@ DETSDW_TD_FINE_ON_DEVICE = 0x200  # flag bit of detsdw_params.timeDisplacedMeasu
 DETSDW_OBS_FINE = 0x100         # flag bit of the observable index: the every-slice twin
 DQMC_SERIES_AUTO_REBIN, DQMC_SERIES_TRACK_VARIANCE = 1, 2   # flags of dqmc_series_configure / detsdw_series_configure
 DETSDW_SERIES_NO_HOST_COPY = 1    # flag of detsdw_series_begin: no equal-time block copy per measurement sweep while the series is open
+DETSDW_SERIES_PHI = 2             # flag of detsdw_series_begin: the order-parameter part (chi_phi(q, i omega_n) and its scalars)
 DETSDW_FM_EQ_CORRELATORS = 0x100  # flag bit of detsdw_params.fermionMeasurements: equal-time charge / spin / SDW / pairing correlators
 
 
@@ -239,6 +240,7 @@ SYMBOLS = [
     ("dqmc_series_read_bins_host", C.c_int, [_P, C.c_int, C.c_int, _DP]),
     ("dqmc_series_stats_host", C.c_int, [_P, _DP, _DP]),
     ("dqmc_series_derived_host", C.c_int, [_P, _DP, _DP]),
+    ("dqmc_series_phi_derived_host", C.c_int, [_P, _DP, _DP]),
     ("dqmc_series_end", C.c_int, [_P]),
     ("dqmc_series_configure", C.c_int, [_P, C.c_int]),
     ("dqmc_series_get_state", C.c_int, [_P, C.POINTER(dqmc_series_state)]),

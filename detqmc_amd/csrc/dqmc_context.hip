@@ -104,7 +104,8 @@ struct dqmc_ctx {
     size_t eqacc_n = 0;                                       // doubles per chain, 0 before the first enable
     // dqmc_series_*: the measurement series.  Device buffers outside the arena, allocated by dqmc_series_begin and freed by dqmc_series_end
     // or with the context: sample [nb][S], open bin [nb][S], closed bins [max_bins][nb][S], the per-part flags [5][nb], the cos / sin table
-    // and the result buffer of the statistics calls (mean, err [nb][S] each, then value, err [nb][6] each).  The counters live on the host.
+    // (2 pi j / L [2 L]; with the order-parameter part, index 6 of off / len, also 2 pi j / m [2 m] behind it) and the result buffer
+    // of the statistics calls (mean, err [nb][S] each, then value, err [nb][6] each).  The counters live on the host.
     // srctab [nb]: the source rows of dqmc_series_accumulate, filled from srchost before every launch; formed: the sample buffer holds
     // the sample of a successful dqmc_series_form_sample that no dqmc_series_accumulate has consumed yet.
     struct Series {
@@ -112,7 +113,7 @@ struct dqmc_ctx {
         int bin_size = 0, max_bins = 0, nfreq = 0, parts = 0, closed = 0, in_open = 0;
         int flags = 0;                                        // DQMC_SERIES_AUTO_REBIN | DQMC_SERIES_TRACK_VARIANCE (dqmc_series_configure)
         long long samples = 0, rebins = 0;                    // accumulates since begin / merges of neighbouring bins so far
-        size_t S = 0, off[5] = {0, 0, 0, 0, 0}, len[5] = {0, 0, 0, 0, 0};
+        size_t S = 0, off[7] = {0, 0, 0, 0, 0, 0, 0}, len[7] = {0, 0, 0, 0, 0, 0, 0};   // index = bit number; 5 is never used
         double *sample = nullptr, *openbin = nullptr, *bins = nullptr, *bad = nullptr, *trig = nullptr, *stat = nullptr;
         double *var = nullptr;                                // running mean w [nb][S], then m2 [nb][S]: allocated with TRACK_VARIANCE
         double *binning = nullptr;                            // result of dqmc_series_binning_host, err then tau [levels][nb][S] each,
@@ -2104,7 +2105,7 @@ extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nf
     if (!c) return fail(DQMC_EINVAL, "null ctx");
     if (c->hm.hubbard) return fail(DQMC_EINVAL, "the measurement series belongs to the SDW model");
     if (c->ser.open) return fail(DQMC_EINVAL, "a measurement series is already open (dqmc_series_end)");
-    if (parts <= 0 || (parts & ~0x1f)) return fail(DQMC_EINVAL, "dqmc_series_begin: parts must be a non-empty mask of bits 0 .. 4");
+    if (parts <= 0 || (parts & ~0x5f)) return fail(DQMC_EINVAL, "dqmc_series_begin: parts must be a non-empty mask of bits 0 .. 4 and 6");
     if (bin_size < 1) return fail(DQMC_EINVAL, "dqmc_series_begin: bin_size must be at least 1");
     if (max_bins < 2) return fail(DQMC_EINVAL, "dqmc_series_begin: max_bins must be at least 2");
     if ((parts & 1) && !c->eqacc_n) return fail(DQMC_EINVAL, "dqmc_series_begin: the equal-time block has never been enabled (dqmc_set_equal_time_correlators)");
@@ -2120,16 +2121,24 @@ extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nf
         if (!td_matsubara_fits(c->hm, ch, nfreq)) return fail(DQMC_EINVAL, "dqmc_series_begin: the lattice is too large for the Matsubara kernel's LDS");
         s.off[1 + ch] = s.S; s.len[1 + ch] = (size_t)(ch == 2 ? 3 : 2) * nfreq * N * 2; s.S += s.len[1 + ch];
     }
-    s.bin_size = bin_size; s.max_bins = max_bins; s.nfreq = (parts & 0x1e) ? nfreq : 0; s.parts = parts;
+    if (parts & DQMC_SERIES_PHI) {                          // the field always exists: no block to ask for
+        if (nfreq < 1 || nfreq > c->m) return fail(DQMC_EINVAL, "dqmc_series_begin: nfreq must be in 1..m");
+        if (series_phi_sample_fgroup(c->hm.L, c->m, nfreq) < 1)
+            return fail(DQMC_EINVAL, "dqmc_series_begin: the lattice is too large for the order-parameter sample kernel's LDS");
+        s.off[6] = s.S; s.len[6] = (size_t)nfreq * N + 5; s.S += s.len[6];
+    }
+    s.bin_size = bin_size; s.max_bins = max_bins; s.nfreq = (parts & (0x1e | DQMC_SERIES_PHI)) ? nfreq : 0; s.parts = parts;
     (void)hipSetDevice(c->p.device);
     const size_t n = (size_t)c->nb * s.S, L = (size_t)c->hm.L;
     c->ser = s;                                             // from here on series_free releases what was allocated
     dqmc_ctx::Series& r = c->ser;
-    hipError_t e = hipMalloc((void**)&r.sample, n * sizeof(double));
+    hipError_t e = (parts & DQMC_SERIES_PHI) ? series_phi_sample_prepare() : hipSuccess;   // an attribute failure is an error here, not at launch
+    if (e == hipSuccess) e = hipMalloc((void**)&r.sample, n * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&r.openbin, n * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&r.bins, (size_t)max_bins * n * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&r.bad, (size_t)5 * c->nb * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&r.trig, 2 * L * sizeof(double));
+    const size_t mt = (parts & DQMC_SERIES_PHI) ? (size_t)c->m : 0;     // the temporal table of the order-parameter part
+    if (e == hipSuccess) e = hipMalloc((void**)&r.trig, 2 * (L + mt) * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&r.stat, (2 * n + (size_t)12 * c->nb) * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&r.srctab, (size_t)c->nb * sizeof(const double*));
     if (e == hipSuccess) e = hipMemsetAsync(r.sample, 0, n * sizeof(double), c->st);
@@ -2138,8 +2147,9 @@ extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nf
     if (e == hipSuccess) e = hipMemsetAsync(r.bad, 0, (size_t)5 * c->nb * sizeof(double), c->st);
     if (e == hipSuccess) {
         // cos / sin(2 pi j / L) as finishFermionic of the host layer forms them: the device's structure factors use the same values
-        std::vector<double> trig(2 * L);
+        std::vector<double> trig(2 * (L + mt));
         for (size_t j = 0; j < L; ++j) { trig[j] = std::cos(2.0 * M_PI * double(j) / double(L)); trig[L + j] = std::sin(2.0 * M_PI * double(j) / double(L)); }
+        for (size_t j = 0; j < mt; ++j) { trig[2 * L + j] = std::cos(2.0 * M_PI * double(j) / double(mt)); trig[2 * L + mt + j] = std::sin(2.0 * M_PI * double(j) / double(mt)); }
         e = copy_sync(c, r.trig, trig.data(), trig.size() * sizeof(double), hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) { series_free(c); return fail(DQMC_EHIP, std::string("dqmc_series_begin: ") + hipGetErrorString(e)); }
@@ -2157,7 +2167,7 @@ extern "C" int dqmc_series_end(dqmc_ctx* c) {
 extern "C" int dqmc_series_layout(dqmc_ctx* c, int part, size_t* offset, size_t* length) {
     if (!c || !offset || !length) return fail(DQMC_EINVAL, "null argument");
     if (!c->ser.open) return fail(DQMC_EINVAL, "no measurement series is open");
-    if (part < 0 || part > 4 || !(c->ser.parts & (1 << part))) return fail(DQMC_EINVAL, "dqmc_series_layout: the part is not in the series");
+    if (part < 0 || part > 6 || !(c->ser.parts & (1 << part))) return fail(DQMC_EINVAL, "dqmc_series_layout: the part is not in the series");
     *offset = c->ser.off[part]; *length = c->ser.len[part];
     return DQMC_OK;
 }
@@ -2195,10 +2205,16 @@ static int series_form_sample(dqmc_ctx* c, const char* entry) {
                 ++nparts;
             }
         c->fam_launches[FAM_OTHER] += (uint64_t)nparts;
+        if (s.parts & DQMC_SERIES_PHI) {                    // after the other parts; no flag row: the field always exists
+            if (!launch_series_phi_sample(c->lc, c->hm, s.trig, s.trig + 2 * (size_t)c->hm.L, s.nfreq, s.sample, s.S, s.off[6]))
+                return fail(DQMC_EINVAL, who + ": the lattice is too large for the order-parameter sample kernel's LDS");
+            ++c->fam_launches[FAM_OTHER];
+        }
     }
     { const int rc = finish(c, entry); if (rc != DQMC_OK) return rc; }
     std::vector<double> bad((size_t)nparts * c->nb);
-    HIPCHK(copy_sync(c, bad.data(), s.bad, bad.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (nparts) HIPCHK(copy_sync(c, bad.data(), s.bad, bad.size() * sizeof(double), hipMemcpyDeviceToHost));
+    else HIPCHK(hipStreamSynchronize(c->st));               // the order-parameter part alone: no flags, the call still synchronises
     for (double b : bad)
         if (b != 0.0) return fail(DQMC_EINVAL, who + ": a block of the series has no sample (equal-time count or an every-slice row count < 1)");
     s.formed = true;
@@ -2324,6 +2340,21 @@ extern "C" int dqmc_series_derived_host(dqmc_ctx* c, double* value, double* err)
                               (s.parts & 16) ? (long long)s.off[4] : -1, dv, dv + nd);
     }
     { const int rc = finish(c, "dqmc_series_derived_host"); if (rc != DQMC_OK) return rc; }
+    HIPCHK(copy_sync(c, value, dv, nd * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(c, err, dv + nd, nd * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+extern "C" int dqmc_series_phi_derived_host(dqmc_ctx* c, double* value, double* err) {
+    if (!c || !value || !err) return fail(DQMC_EINVAL, "null argument");
+    const dqmc_ctx::Series& s = c->ser;
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (!(s.parts & DQMC_SERIES_PHI)) return fail(DQMC_EINVAL, "dqmc_series_phi_derived_host: the series has no order-parameter part");
+    if (s.closed < 2) return fail(DQMC_EINVAL, "dqmc_series_phi_derived_host: the jackknife needs at least two closed bins");
+    (void)hipSetDevice(c->p.device);
+    const size_t n = (size_t)c->nb * s.S, nd = (size_t)6 * c->nb;
+    double* dv = s.stat + 2 * n;                            // the result rows of dqmc_series_derived_host: the calls are synchronous
+    { ProfScope ps(c, FAM_OTHER, 1); launch_series_phi_derived(c->lc, c->hm, s.bins, s.S, s.closed, s.nfreq, s.off[6], dv, dv + nd); }
+    { const int rc = finish(c, "dqmc_series_phi_derived_host"); if (rc != DQMC_OK) return rc; }
     HIPCHK(copy_sync(c, value, dv, nd * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHK(copy_sync(c, err, dv + nd, nd * sizeof(double), hipMemcpyDeviceToHost));
     return DQMC_OK;

@@ -276,6 +276,14 @@ void launch_series_accum_routed(const Launch& lc, const double* const* src, doub
 void launch_series_stats(const Launch& lc, const double* bins, size_t n, int B, double* mean, double* err);
 void launch_series_derived(const Launch& lc, const DevModel& hm, const double* bins, size_t S, int B, int nfreq, long long off_eq,
                            long long off_cur, double* value, double* err);
+// the order-parameter part (DQMC_SERIES_PHI): chi [nfreq][N] and five scalars from the field; trig = (cos, sin)(2 pi j / L) [2 L], ttab =
+// (cos, sin)(2 pi j / m) [2 m].  series_phi_sample_fgroup: frequencies per workgroup, 0 if a single frequency does not fit the LDS
+bool launch_series_phi_sample(const Launch& lc, const DevModel& hm, const double* trig, const double* ttab, int nfreq, double* sample,
+                              size_t S, size_t off);
+int series_phi_sample_fgroup(int L, int m, int nfreq);
+hipError_t series_phi_sample_prepare();                     // the kernel's dynamic LDS limit, set by dqmc_series_begin on the series' device
+void launch_series_phi_derived(const Launch& lc, const DevModel& hm, const double* bins, size_t S, int B, int nfreq, size_t off,
+                               double* value, double* err);
 // long runs: in-place merge of neighbouring closed bins (half = pairs to merge), Welford's update of (w, m2) [nb][S] with the sample rows
 // (src == nullptr: the rows of `sample` in order; cnt = samples including this one), and the binning analysis err / tau [levels][n]
 // (tau == nullptr: errors only; m2 is read only with tau)

@@ -336,7 +336,8 @@ void DetSDW::sweep_skeleton(Group& g, bool thermalization) {
 // the sweep, so they are accumulated afterwards from the final field, in the slice order of the sweep just done.
 void DetSDW::sweep(bool takeMeasurements) {
     const bool fermionic = takeMeasurements && ch_[0].pars.fermionMeasurements;
-    const bool feedSeries = fermionic && series_.open;
+    // a series that holds the order-parameter part alone needs no Green's function measurement: it is fed without fermionMeasurements too
+    const bool feedSeries = takeMeasurements && series_.open && (fermionic || series_.parts == DQMC_SERIES_PHI);
     if (feedSeries) {                  // nothing is dropped silently, and nothing has changed yet
         int closed = 0;
         check(dqmc_series_info(groups_[0].ctx, &closed, nullptr, nullptr), "dqmc_series_info");
@@ -707,10 +708,13 @@ void DetSDW::getMatsubaraAll(int which, int nfreq, double* out) {
 void DetSDW::seriesBegin(int binSize, int maxBins, int nfreq, int flags) {
     const detsdw_params& p = ch_[0].pars;
     if (series_.open) throw GeneralError(DQMC_EINVAL, "a measurement series is already open");
-    if (flags & ~DETSDW_SERIES_NO_HOST_COPY) throw ParameterWrong("unknown flag of detsdw_series_begin");
-    int parts = 0;
-    if (eq_correlators(p)) parts |= DQMC_SERIES_EQ;
-    if (td_every_slice(p)) {
+    if (flags & ~(DETSDW_SERIES_NO_HOST_COPY | DETSDW_SERIES_PHI)) throw ParameterWrong("unknown flag of detsdw_series_begin");
+    const bool phi = (flags & DETSDW_SERIES_PHI) != 0;
+    // with DETSDW_SERIES_PHI a handle without fermionMeasurements opens the order-parameter part alone: its blocks are never filled
+    const bool blocks = !phi || (p.fermionMeasurements & 1);
+    int parts = phi ? DQMC_SERIES_PHI : 0;
+    if (blocks && eq_correlators(p)) parts |= DQMC_SERIES_EQ;
+    if (blocks && td_every_slice(p)) {
         parts |= DQMC_SERIES_MATS_G;
         if (td_level(p) == 2) parts |= DQMC_SERIES_MATS_PAIR;
         if (p.timeDisplacedParticleHole) parts |= DQMC_SERIES_MATS_PH;
@@ -732,7 +736,7 @@ void DetSDW::seriesBegin(int binSize, int maxBins, int nfreq, int flags) {
         for (size_t i = 0; i < opened; ++i) (void)dqmc_series_end(groups_[i].ctx);
         throw;
     }
-    series_.open = true; series_.binSize = binSize; series_.maxBins = maxBins; series_.nfreq = (parts & ~DQMC_SERIES_EQ) ? nfreq : 0;
+    series_.open = true; series_.binSize = binSize; series_.maxBins = maxBins; series_.nfreq = (parts & ~DQMC_SERIES_EQ) ? nfreq : 0;   // the phi part keeps nfreq too
     series_.parts = parts; series_.flags = flags;
     seriesRoute_.resize(ch_.size());
     std::iota(seriesRoute_.begin(), seriesRoute_.end(), 0);
@@ -773,6 +777,11 @@ void DetSDW::seriesSlice(int which, int& part, size_t& offset, size_t& length) {
     if (which >= DETSDW_OBS_CHARGECORR && which <= DETSDW_OBS_PAIRMINUSSQ) {
         if (!(series_.parts & DQMC_SERIES_EQ)) throw ParameterWrong("the equal-time part of the series needs equalTimeCorrelators");
         part = 0; length = (size_t)N_; sub = (size_t)(which - DETSDW_OBS_CHARGECORR) * N_;
+    } else if (which == DETSDW_OBS_PHICHI || which == DETSDW_OBS_PHISCALARS) {
+        if (!(series_.parts & DQMC_SERIES_PHI)) throw ParameterWrong("the series has no order-parameter part: detsdw_series_begin with DETSDW_SERIES_PHI");
+        part = 6;
+        if (which == DETSDW_OBS_PHICHI) { length = (size_t)series_.nfreq * N_; sub = 0; }
+        else { length = 5; sub = (size_t)series_.nfreq * N_; }
     } else {
         int channel, comp;
         if (which == DETSDW_OBS_GREENKTAU_X || which == DETSDW_OBS_GREENKTAU_Y) { channel = 0; comp = which - DETSDW_OBS_GREENKTAU_X; }
@@ -820,6 +829,17 @@ void DetSDW::seriesStatsAll(int which, double* mean, double* err) {
 }
 void DetSDW::seriesDerivedAll(int what, double* value, double* err) {
     if (!series_.open) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
+    if (what >= DETSDW_SERIES_BINDER_PHI && what <= DETSDW_SERIES_XI_PHI) {
+        if (!(series_.parts & DQMC_SERIES_PHI)) throw ParameterWrong("the order-parameter quantities need a series opened with DETSDW_SERIES_PHI");
+        std::vector<double> v, e;
+        const int at = what - DETSDW_SERIES_BINDER_PHI;
+        for (auto& g : groups_) {
+            v.resize((size_t)g.count * 6); e.resize((size_t)g.count * 6);
+            check(dqmc_series_phi_derived_host(g.ctx, v.data(), e.data()), "dqmc_series_phi_derived_host");
+            for (int b = 0; b < g.count; ++b) { value[g.first + b] = v[(size_t)b * 6 + at]; err[g.first + b] = e[(size_t)b * 6 + at]; }
+        }
+        return;
+    }
     if (what < DETSDW_SERIES_R_CHARGE || what > DETSDW_SERIES_RHO_S) throw ParameterWrong("unknown derived quantity of the measurement series");
     if (what <= DETSDW_SERIES_R_PAIRMINUS && !(series_.parts & DQMC_SERIES_EQ)) throw ParameterWrong("the correlation ratios need equalTimeCorrelators");
     if (what == DETSDW_SERIES_RHO_S && !(series_.parts & DQMC_SERIES_MATS_CURRENT))

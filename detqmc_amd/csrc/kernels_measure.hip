@@ -1109,6 +1109,219 @@ void launch_series_derived(const Launch& lc, const DevModel& hm, const double* b
     hipLaunchKernelGGL(k_series_derived, dim3((unsigned)((lc.nb * 6 + 63) / 64)), dim3(64), 0, lc.st, bins, a, value, err);
 }
 
+// ---- the order-parameter part of the sample (DQMC_SERIES_PHI): chi_phi(q, i omega_n) and five scalars straight from the field ----
+// out[chain] = chi [nfreq][N] then the scalars [5] (dqmc_hip.h).  A_d(n, q) = (1/K) sum_k sum_r phi_d(r, k) e^{+i 2 pi n k / m}
+// e^{-i q r}, chi = sum_d |A_d|^2, K = m N.  Grid (frequency groups, 1, chains), 256 threads; a group holds fg <= SPHI_FG consecutive
+// frequencies.  Per component d:
+//   stage 0  thread t owns sites t, t + 256, ... (coalesced loads) and walks k = 1 .. m upwards, four slices in flight, with the fg
+//            complex accumulators in registers: phi is read once per group.  The phase index j = n k mod m is stepped in integers
+//            (j += n, minus m on overflow), cos / sin(2 pi j / m) come from the host table `ttab` = (cos[m], sin[m]) kept in LDS.
+//            T[f][y][x] goes to LDS.
+//   stage 1  over x: U[f][y][qx] = sum_x T[f][y][x] (cos - i sin)(2 pi (qx x mod L) / L), table `trig` of the equal-time kernel
+//   stage 2  over y: A[f][qy][qx] = sum_y U[f][y][qx] (cos - i sin)(2 pi (qy y mod L) / L) / K; the thread that owns element (f, q)
+//            adds |A|^2 to chi[f][q] in LDS -- always the same thread, d in order: one writer, no atomics.
+// Group 0 (it holds n = 0) forms the scalars from a second pass over the field, which the first pass left in the L2: wave w takes
+// the rows (k, d) = w, w + 4, ..., its lanes the sites lane, lane + 64, ...; the site sum of a row is a butterfly over the wave (every
+// lane ends with the same bits), sum phi^2 stays per lane until the end; the four wave results are added in wave order by thread 0.
+// Nothing depends on another chain, on the number of chains or on the grouping of the frequencies.
+constexpr int SPHI_FG = 4;
+size_t series_phi_sample_lds_bytes(int L, int m, int fg) {
+    return ((size_t)5 * fg * L * L + 2 * (size_t)L + 2 * (size_t)m + 8) * sizeof(double);
+}
+// frequencies per workgroup: as many as SPHI_FG while the tile stays within 64 KiB, a single one up to the 152 KiB of the other sample
+// kernels; 0: even a single frequency does not fit
+int series_phi_sample_fgroup(int L, int m, int nfreq) {
+    for (int fg = nfreq < SPHI_FG ? nfreq : SPHI_FG; fg > 1; --fg)
+        if (series_phi_sample_lds_bytes(L, m, fg) <= 64 * 1024) return fg;
+    return series_phi_sample_lds_bytes(L, m, 1) <= 152 * 1024 ? 1 : 0;
+}
+struct SeriesPhiShape { int L, N, m, opdim, nfreq, fg; size_t S, off; };
+__device__ __forceinline__ double sphi_wave_sum(double v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__global__ __launch_bounds__(256) void k_series_phi_sample(const double* __restrict__ phi, const double* __restrict__ trig,
+                                                           const double* __restrict__ ttab, double* __restrict__ sample, SeriesPhiShape a,
+                                                           size_t cs) {
+    extern __shared__ __attribute__((aligned(16))) double sphi_sm[];
+    CHAIN(phi);
+    const int tid = threadIdx.x, L = a.L, N = a.N, m = a.m, OPD = a.opdim;
+    const int n0 = blockIdx.x * a.fg, fg = min(a.fg, a.nfreq - n0), fN = fg * N;
+    double* out = sample + (size_t)blockIdx.z * a.S + a.off;
+    double* Tr = sphi_sm;                                   // [fg][y][x]
+    double* Ti = Tr + (size_t)a.fg * N;
+    double* Ur = Ti + (size_t)a.fg * N;                     // [fg][y][qx]
+    double* Ui = Ur + (size_t)a.fg * N;
+    double* chi = Ui + (size_t)a.fg * N;                    // [fg][q]
+    double* ct = chi + (size_t)a.fg * N;                    // [L]
+    double* st = ct + L;
+    double* tc = st + L;                                    // [m]
+    double* ts = tc + m;
+    double* red = ts + m;                                   // [8]
+    for (int j = tid; j < L; j += 256) { ct[j] = trig[j]; st[j] = trig[L + j]; }
+    for (int j = tid; j < m; j += 256) { tc[j] = ttab[j]; ts[j] = ttab[m + j]; }
+    for (int e = tid; e < fN; e += 256) chi[e] = 0.0;
+    __syncthreads();
+    const double K = (double)m * (double)N;
+    const size_t kstride = (size_t)OPD * N;
+    for (int d = 0; d < OPD; ++d) {
+        for (int r = tid; r < N; r += 256) {
+            const double* p = phi + kstride + (size_t)d * N + r;      // slice 1
+            double are[SPHI_FG], aim[SPHI_FG];
+            int j[SPHI_FG];
+#pragma unroll
+            for (int f = 0; f < SPHI_FG; ++f) { are[f] = 0.0; aim[f] = 0.0; j[f] = f < fg ? n0 + f : 0; }   // n k mod m at k = 1 (n < m)
+            int k = 1;
+            for (; k + 3 <= m; k += 4) {
+                double v[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) v[u] = p[(size_t)u * kstride];
+                p += 4 * kstride;
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int f = 0; f < SPHI_FG; ++f)
+                        if (f < fg) {
+                            are[f] += v[u] * tc[j[f]]; aim[f] += v[u] * ts[j[f]];
+                            j[f] += n0 + f; if (j[f] >= m) j[f] -= m;
+                        }
+            }
+            for (; k <= m; ++k) {
+                const double v = *p;
+                p += kstride;
+#pragma unroll
+                for (int f = 0; f < SPHI_FG; ++f)
+                    if (f < fg) {
+                        are[f] += v * tc[j[f]]; aim[f] += v * ts[j[f]];
+                        j[f] += n0 + f; if (j[f] >= m) j[f] -= m;
+                    }
+            }
+#pragma unroll
+            for (int f = 0; f < SPHI_FG; ++f)
+                if (f < fg) { Tr[f * N + r] = are[f]; Ti[f * N + r] = aim[f]; }
+        }
+        __syncthreads();
+        for (int e = tid; e < fN; e += 256) {
+            const int f = e / N, i = e - f * N, y = i / L, qx = i - y * L;
+            const double* tr = Tr + f * N + y * L;
+            const double* ti = Ti + f * N + y * L;
+            double sr = 0.0, si = 0.0;
+            for (int x = 0; x < L; ++x) {
+                const int jj = (qx * x) % L;
+                const double c = ct[jj], s = st[jj];
+                sr += tr[x] * c + ti[x] * s; si += ti[x] * c - tr[x] * s;
+            }
+            Ur[e] = sr; Ui[e] = si;
+        }
+        __syncthreads();
+        for (int e = tid; e < fN; e += 256) {
+            const int f = e / N, q = e - f * N, qy = q / L, qx = q - qy * L;
+            const double* ur = Ur + f * N + qx;
+            const double* ui = Ui + f * N + qx;
+            double sr = 0.0, si = 0.0;
+            for (int y = 0; y < L; ++y) {
+                const int jj = (qy * y) % L;
+                const double c = ct[jj], s = st[jj];
+                sr += ur[y * L] * c + ui[y * L] * s; si += ui[y * L] * c - ur[y * L] * s;
+            }
+            sr /= K; si /= K;
+            chi[e] += sr * sr + si * si;
+        }
+        // the next component's stage 0 writes T, which stage 2 does not read; its stage 1 writes U behind the barrier after stage 0
+    }
+    for (int e = tid; e < fN; e += 256) out[(size_t)n0 * N + e] = chi[e];
+    if (blockIdx.x != 0) return;
+    // the scalars: rows (k, d) of the field, k = 1 .. m, lie behind each other from phi + OPD N
+    const int w = tid >> 6, lane = tid & 63, rows = m * OPD;
+    double eqs = 0.0, sq = 0.0;
+    for (int row = w; row < rows; row += 4) {
+        const double* p = phi + kstride + (size_t)row * N;
+        double s = 0.0;
+        for (int r = lane; r < N; r += 64) { const double v = p[r]; s += v; sq += v * v; }
+        s = sphi_wave_sum(s) / (double)N;
+        eqs += s * s;
+    }
+    sq = sphi_wave_sum(sq);
+    if (lane == 0) { red[w] = eqs; red[4 + w] = sq; }
+    __syncthreads();
+    if (tid == 0) {
+        const double c0 = chi[0];
+        double* sc = out + (size_t)a.nfreq * N;
+        sc[0] = sqrt(c0); sc[1] = c0; sc[2] = c0 * c0;
+        sc[3] = (((red[0] + red[1]) + red[2]) + red[3]) * ((double)N / (double)m);
+        sc[4] = (((red[4] + red[5]) + red[6]) + red[7]) / (2.0 * (double)N * (double)m);
+    }
+}
+// Once per series, on the series' device: lets the kernel use the whole 152 KiB, the ceiling of series_phi_sample_fgroup, so that no
+// launch depends on an attribute call of its own and contexts with different tiles do not lower each other's limit
+hipError_t series_phi_sample_prepare() {
+    return hipFuncSetAttribute((const void*)k_series_phi_sample, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
+}
+// false: the lattice is too large for the kernel's LDS, nothing was launched (dqmc_series_begin refuses such a series)
+bool launch_series_phi_sample(const Launch& lc, const DevModel& hm, const double* trig, const double* ttab, int nfreq, double* sample,
+                              size_t S, size_t off) {
+    const int fg = series_phi_sample_fgroup(hm.L, hm.m, nfreq);
+    if (fg < 1) return false;
+    const size_t lds = series_phi_sample_lds_bytes(hm.L, hm.m, fg);           // within the limit series_phi_sample_prepare has set
+    SeriesPhiShape a{hm.L, hm.N, hm.m, hm.opdim, nfreq, fg, S, off};
+    hipLaunchKernelGGL(k_series_phi_sample, dim3((unsigned)((nfreq + fg - 1) / fg), 1, lc.nb), dim3(256), lds, lc.st, hm.phi, trig, ttab,
+                       sample, a, lc.cs);
+    return true;
+}
+// The jackknife of k_series_derived over the order-parameter part, out[chain][6] (dqmc_hip.h): off = offset of the part inside a
+// sample, x = (|phibar|, |phibar|^2, |phibar|^4) for entries 0 .. 3 and (chi0, chix, chiy) at frequency 0 for entries 4, 5.
+struct SeriesPhiDerivedShape { size_t S, off; int L, N, nfreq, nb, B; double betaN, twosin; };
+__device__ __forceinline__ double series_phi_derived_f(int e, const double* x, double betaN, double twosin) {
+    switch (e) {
+    case 0: return 1.0 - x[2] / (3.0 * x[1] * x[1]);
+    case 1: return x[2] / (x[1] * x[1]);
+    case 2: return betaN * x[1];
+    case 3: return betaN * (x[1] - x[0] * x[0]);
+    case 4: return 1.0 - 0.5 * (x[1] + x[2]) / x[0];
+    default: {
+        const double arg = x[0] / (0.5 * (x[1] + x[2])) - 1.0;
+        return arg >= 0.0 ? sqrt(arg) / twosin : nan("");
+    }
+    }
+}
+__global__ __launch_bounds__(64) void k_series_phi_derived(const double* __restrict__ bins, SeriesPhiDerivedShape a, double* __restrict__ value,
+                                                           double* __restrict__ err) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= a.nb * 6) return;
+    const int chain = t / 6, e = t - chain * 6;
+    size_t idx[3];
+    if (e < 4) { const size_t sc = a.off + (size_t)a.nfreq * a.N; idx[0] = sc; idx[1] = sc + 1; idx[2] = sc + 2; }
+    else { idx[0] = a.off; idx[1] = a.off + (size_t)(1 % a.N); idx[2] = a.off + (size_t)(a.L % a.N); }
+    const size_t n = (size_t)a.nb * a.S;
+    const double* p = bins + (size_t)chain * a.S;
+    const int B = a.B;
+    double mu[3], tot[3], x[3];
+    for (int j = 0; j < 3; ++j) {
+        double sum = 0.0;
+        for (int b = 0; b < B; ++b) sum += p[(size_t)b * n + idx[j]];
+        mu[j] = sum / (double)B; tot[j] = (double)B * mu[j];
+    }
+    double tsum = 0.0;
+    for (int b = 0; b < B; ++b) {
+        for (int j = 0; j < 3; ++j) x[j] = (tot[j] - p[(size_t)b * n + idx[j]]) / (double)(B - 1);
+        tsum += series_phi_derived_f(e, x, a.betaN, a.twosin);
+    }
+    const double tbar = tsum / (double)B;
+    double acc = 0.0;
+    for (int b = 0; b < B; ++b) {
+        for (int j = 0; j < 3; ++j) x[j] = (tot[j] - p[(size_t)b * n + idx[j]]) / (double)(B - 1);
+        const double d = series_phi_derived_f(e, x, a.betaN, a.twosin) - tbar;
+        acc += d * d;
+    }
+    value[t] = series_phi_derived_f(e, mu, a.betaN, a.twosin);
+    err[t] = sqrt((double)(B - 1) / (double)B * acc);
+}
+void launch_series_phi_derived(const Launch& lc, const DevModel& hm, const double* bins, size_t S, int B, int nfreq, size_t off,
+                               double* value, double* err) {
+    SeriesPhiDerivedShape a{S, off, hm.L, hm.N, nfreq, lc.nb, B, (double)hm.m * hm.dtau * (double)hm.N, 2.0 * std::sin(M_PI / (double)hm.L)};
+    hipLaunchKernelGGL(k_series_phi_derived, dim3((unsigned)((lc.nb * 6 + 63) / 64)), dim3(64), 0, lc.st, bins, a, value, err);
+}
+
 // ---- long runs: re-binning, running variance, binning analysis (dqmc_series_rebin / _configure / _binning_host) ----------------
 // closed[k] = (closed[2k] + closed[2k+1]) * 0.5 for k < half, in place over the n = nb S elements.  One thread per element walks k
 // upwards: it reads bins 2k and 2k + 1 >= k of its own element after it wrote bins < k, and no other thread touches the element.

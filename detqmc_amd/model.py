@@ -114,9 +114,38 @@ def superfluid_stiffness(chi_xx, chi_yy, L):
 
 
 # derived quantities of a measurement series (DetSDWBatch.series_derived_all): name -> index of detsdw_series_derived_all
-SERIES_DERIVED = {"R_charge": 0, "R_spinZ": 1, "R_sdw": 2, "R_pairPlus": 3, "R_pairMinus": 4, "rhoS": 5}
-# parts of a kernel-level series (KernelContext.series_begin): bit 0 the equal-time block, bits 1 .. 4 the Matsubara transform of channel 0 .. 3
+SERIES_DERIVED = {"R_charge": 0, "R_spinZ": 1, "R_sdw": 2, "R_pairPlus": 3, "R_pairMinus": 4, "rhoS": 5,
+                  "binderPhi": 6, "binderRatioPhi": 7, "chiPhi": 8, "chiPhiConnected": 9, "R_phi": 10, "xiPhi": 11}
+# parts of a kernel-level series (KernelContext.series_begin): bit 0 the equal-time block, bits 1 .. 4 the Matsubara transform of channel 0 .. 3,
+# bit 6 (part index 6 of series_layout) the order-parameter part: chi_phi [nfreq][N] and five scalars from the field itself
 SERIES_EQ, SERIES_MATS_G, SERIES_MATS_PAIR, SERIES_MATS_PH, SERIES_MATS_CURRENT = 1, 2, 4, 8, 16
+SERIES_PHI = 64
+# the order-parameter part of a series opened with phi=True: name -> index of detsdw_series_stats (real, (nfreq, N) and (5,))
+SERIES_PHI_OBS = {"phiChi": 32, "phiScalars": 33}
+
+
+def phi_sample(phi, L, nfreq):
+    """The order-parameter part of a series sample in numpy, from a field phi (m+1, N, opdim) with slices 1 .. m (slice 0 is not read):
+    (chi, scalars) with chi (nfreq, N), column qy L + qx,
+        A_d(n, q) = (1/(m N)) sum_{k=1..m} sum_r phi_d(r, k) exp(i 2 pi n k / m - i 2 pi (qx x + qy y) / L),   chi(n, q) = sum_d |A_d(n, q)|^2
+    (the physical susceptibility is beta N <chi>), and scalars = (|phibar|, |phibar|^2, |phibar|^4, the equal-time susceptibility
+    (N/m) sum_k sum_d ((1/N) sum_r phi_d(r, k))^2, associatedEnergy = sum phi^2 / (2 N m)) with |phibar|^2 = chi(0, 0)."""
+    phi = np.asarray(phi, dtype=np.float64)
+    L, nfreq = int(L), int(nfreq)
+    m, N, opdim = phi.shape[0] - 1, phi.shape[1], phi.shape[2]
+    if N != L * L or not 1 <= nfreq <= m:
+        raise ValueError("phi_sample needs phi of shape (m+1, L L, opdim) and 1 <= nfreq <= m")
+    f = phi[1:]                                             # [k-1][r][d]
+    k = np.arange(1, m + 1)
+    et = np.exp(2j * np.pi * np.outer(np.arange(nfreq), k) / m)            # [n][k]
+    j = np.arange(L)
+    es = np.exp(-2j * np.pi * np.outer(j, j) / L)                          # [q][x]
+    t = np.einsum("nk,kyxd->nyxd", et, f.reshape(m, L, L, opdim))
+    a = np.einsum("qy,px,nyxd->nqpd", es, es, t) / (m * N)                 # [n][qy][qx][d]
+    chi = (np.abs(a) ** 2).sum(axis=3).reshape(nfreq, N)
+    m2 = chi[0, 0]
+    eqt = ((f.sum(axis=1) / N) ** 2).sum() * N / m
+    return chi, np.array([np.sqrt(m2), m2, m2 * m2, eqt, (f ** 2).sum() / (2.0 * N * m)])
 
 
 def jackknife(bins, f=None):
@@ -327,7 +356,8 @@ class KernelContext:
 
     def series_begin(self, bin_size, max_bins, nfreq=0, parts=SERIES_EQ):
         """open the measurement series of this context: bins of bin_size samples, at most max_bins of them; parts = SERIES_EQ |
-        SERIES_MATS_G | ... (the equal-time block must have been enabled, the Matsubara parts need their every-slice block)"""
+        SERIES_MATS_G | ... (the equal-time block must have been enabled, the Matsubara parts need their every-slice block) | SERIES_PHI
+        (the order-parameter part: needs no block, 1 <= nfreq <= m; it may be the only part)"""
         check(self.lib.dqmc_series_begin(self.h, int(bin_size), int(max_bins), int(nfreq), int(parts)))
 
     def series_add_sweep(self):
@@ -387,6 +417,13 @@ class KernelContext:
         the part is not in the series"""
         v, e = np.zeros((self.nchains_total(), 6)), np.zeros((self.nchains_total(), 6))
         check(self.lib.dqmc_series_derived_host(self.h, v.ctypes.data_as(_lib._DP), e.ctypes.data_as(_lib._DP)))
+        return v, e
+
+    def series_phi_derived(self):
+        """(value, err), (nchains, 6) each, of a series with SERIES_PHI: the jackknifed Binder cumulant and ratio of |phibar|, beta N
+        <|phibar|^2>, its connected part, the correlation ratio R_phi and the second-moment correlation length xi_phi"""
+        v, e = np.zeros((self.nchains_total(), 6)), np.zeros((self.nchains_total(), 6))
+        check(self.lib.dqmc_series_phi_derived_host(self.h, v.ctypes.data_as(_lib._DP), e.ctypes.data_as(_lib._DP)))
         return v, e
 
     def series_end(self):
@@ -799,6 +836,8 @@ class DetSDW:
         info = self.info
         if name in EQ_CORRELATORS:
             return EQ_CORRELATORS[name], (info.N,), False
+        if name in SERIES_PHI_OBS:
+            return SERIES_PHI_OBS[name], ((self._batch._series_nfreq, info.N) if name == "phiChi" else (5,)), False
         return MATSUBARA[name], (self._batch._series_nfreq, info.N), True
 
     def series_stats(self, name):
@@ -984,14 +1023,18 @@ class DetSDWBatch:
         check(self.lib.detsdw_get_matsubara_all(self.h, MATSUBARA[name], int(nfreq), out.ctypes.data_as(_lib._DP)), host=True)
         return out
 
-    def series_begin(self, binSize, maxBins, nfreq=0, host_copy=True, auto_rebin=False, track_variance=False):
+    def series_begin(self, binSize, maxBins, nfreq=0, host_copy=True, auto_rebin=False, track_variance=False, phi=False):
         """open a measurement series on the device: from now on every sweep(True) adds one sample per chain -- the equal-time C(d),
         S(q) with equalTimeCorrelators, the Matsubara transforms at nfreq frequencies of every enabled channel with
         timeDisplacedEverySlice -- to bins of binSize sweeps, at most maxBins of them.  host_copy=False: measurement sweeps no longer
         copy the equal-time block to the host ('...Corr' / '...Sq' of observable_vector raise while the series is open).
         auto_rebin: whenever maxBins (even, >= 4) bins are closed, neighbouring bins are merged -- the run never outlives the series;
-        track_variance: keep the variance of the single samples, which series_binning_all needs for tau"""
-        flags = 0 if host_copy else _lib.DETSDW_SERIES_NO_HOST_COPY
+        track_variance: keep the variance of the single samples, which series_binning_all needs for tau;
+        phi: add the order-parameter part, formed on the device from the field -- 'phiChi' (nfreq, N), chi_phi(q, i omega_n) with the
+        physical susceptibility beta N <chi>, and 'phiScalars' (|phibar|, |phibar|^2, |phibar|^4, equal-time susceptibility,
+        associatedEnergy), with 'binderPhi', 'binderRatioPhi', 'chiPhi', 'chiPhiConnected', 'R_phi', 'xiPhi' of series_derived_all.  Needs
+        1 <= nfreq <= m and no other option: a batch without fermionMeasurements may open such a series"""
+        flags = (0 if host_copy else _lib.DETSDW_SERIES_NO_HOST_COPY) | (_lib.DETSDW_SERIES_PHI if phi else 0)
         check(self.lib.detsdw_series_begin(self.h, int(binSize), int(maxBins), int(nfreq), flags), host=True)
         self._series_nfreq = int(nfreq)
         self._series_open = True

@@ -134,7 +134,9 @@ enum { DETSDW_OBS_KOCCX = 0, DETSDW_OBS_KOCCY = 1, DETSDW_OBS_PAIRPLUS = 2, DETS
        DETSDW_OBS_CURRENTXTAU = 16, DETSDW_OBS_CURRENTYTAU = 17, DETSDW_OBS_CURRENTXTAU_Q0 = 18, DETSDW_OBS_CURRENTYTAU_Q0 = 19,
        DETSDW_OBS_BONDKINETICX = 20, DETSDW_OBS_BONDKINETICY = 21,
        DETSDW_OBS_CHARGECORR = 22, DETSDW_OBS_SPINZCORR = 23, DETSDW_OBS_SDWCORR = 24, DETSDW_OBS_PAIRPLUSCORR = 25, DETSDW_OBS_PAIRMINUSCORR = 26,
-       DETSDW_OBS_CHARGESQ = 27, DETSDW_OBS_SPINZSQ = 28, DETSDW_OBS_SDWSQ = 29, DETSDW_OBS_PAIRPLUSSQ = 30, DETSDW_OBS_PAIRMINUSSQ = 31 };
+       DETSDW_OBS_CHARGESQ = 27, DETSDW_OBS_SPINZSQ = 28, DETSDW_OBS_SDWSQ = 29, DETSDW_OBS_PAIRPLUSSQ = 30, DETSDW_OBS_PAIRMINUSSQ = 31,
+       /* the order-parameter part of a measurement series only (detsdw_series_* below; detsdw_get_observable_vector refuses them) */
+       DETSDW_OBS_PHICHI = 32, DETSDW_OBS_PHISCALARS = 33 };
 /* equalTimeCorrelators: flag bit of detsdw_params::fermionMeasurements */
 enum { DETSDW_FM_EQ_CORRELATORS = 0x100 };
 /* timeDisplacedEverySlice: flag bit of detsdw_params::timeDisplacedMeasurements */
@@ -210,7 +212,8 @@ int detsdw_get_matsubara_all(detsdw_replica* r, int which, int nfreq, double* ou
 /* Measurement series: bins over measurement sweeps and jackknife errors, kept on the device (dqmc_series_*, dqmc_hip.h).
  * detsdw_series_begin opens one series per kernel context.  Its parts follow from the handle's options: the equal-time part with
  * equalTimeCorrelators, one Matsubara part (nfreq frequencies, 1 <= nfreq <= m) per enabled every-slice channel; nfreq is ignored
- * without timeDisplacedEverySlice; ParameterWrong if neither option is on.  While the series is open every detsdw_sweep(r, 1) ends
+ * without timeDisplacedEverySlice; ParameterWrong if neither option is on -- unless flags holds DETSDW_SERIES_PHI, the third way to
+ * open a series (the order-parameter part below, which needs no option).  While the series is open every detsdw_sweep(r, 1) ends
  * with one sample of every chain added to the series (after binSize of them a bin closes); thermalisation sweeps and detsdw_sweep(r, 0) add
  * nothing.  A measurement sweep on a full series (maxBins bins closed) fails with DQMC_EINVAL before it changes anything: read the
  * series out and end it, or let it re-bin itself (detsdw_series_configure below).
@@ -225,6 +228,17 @@ int detsdw_get_matsubara_all(detsdw_replica* r, int which, int nfreq, double* ou
  *   detsdw_series_derived_all: what = DETSDW_SERIES_R_CHARGE .. _R_PAIRMINUS (correlation ratios) or DETSDW_SERIES_RHO_S, value[nchains]
  *     and err[nchains]; ParameterWrong if the option the quantity needs is off.
  *   detsdw_series_read_bins: closed bins first .. first + count - 1 of `which`, selected chain: out[count] x (N, or [nfreq][N] complex).
+ * The order-parameter part, flags & DETSDW_SERIES_PHI (the part DQMC_SERIES_PHI of dqmc_hip.h, formed on the device from the field
+ * itself): chi_phi(q, i omega_n), n = 0 .. nfreq-1 (1 <= nfreq <= m), and the scalars |phibar|, |phibar|^2, |phibar|^4, the equal-time
+ * susceptibility and associatedEnergy -- what the reference gets offline from its configuration stream.  It is added to whatever parts
+ * the options provide, and a handle with no other part may open a series with it, also one with fermionMeasurements = 0 (then every
+ * detsdw_sweep(r, 1) feeds the series, and no Green's function measurement is needed).  Without the flag nothing changes.
+ *   which = DETSDW_OBS_PHICHI: [nfreq][N] real, column qy L + qx; DETSDW_OBS_PHISCALARS: [5], for detsdw_series_stats, _stats_all,
+ *     _read_bins, _binning, _binning_all (ParameterWrong without the part).  The physical susceptibility is beta N <chi>.
+ *   what = DETSDW_SERIES_BINDER_PHI (1 - <|phibar|^4> / (3 <|phibar|^2>^2)), _BINDER_RATIO_PHI (<|phibar|^4> / <|phibar|^2>^2), _CHI_PHI
+ *     (beta N <|phibar|^2>), _CHI_PHI_CONNECTED (beta N (<|phibar|^2> - <|phibar|>^2)), _R_PHI (1 - (chi(0; 1,0) + chi(0; 0,1)) / (2 chi(0; 0,0)))
+ *     and _XI_PHI (the second-moment correlation length, NaN where undefined) for detsdw_series_derived_all: dqmc_series_phi_derived_host;
+ *     ParameterWrong without the part.  A series file with the part loads only into a series opened with the flag.
  * detsdw_save_state does not store the series, and detsdw_load_state leaves an open series alone (bins closed before the load stay,
  * the open bin keeps what it holds; neither stores the route): the series has a file of its own, detsdw_series_save / _load below.
  * Slots and the route: a SLOT is a row of the series buffers (open bin, closed bins, statistics), indexed like a chain; the index of
@@ -241,9 +255,11 @@ int detsdw_get_matsubara_all(detsdw_replica* r, int which, int nfreq, double* ou
  * this is how the ordering rule of dqmc_hip.h is kept).  If a context fails in the first phase no context accumulates and every series
  * is as it was; the sweep itself has happened.  With the identity the bins are bit for bit those of a series without a route, for any
  * number of sub-batches.  The route changes no trajectory and no observable of a sweep.  Routing across handles (GPUs) is not provided. */
-enum { DETSDW_SERIES_NO_HOST_COPY = 1 };
+enum { DETSDW_SERIES_NO_HOST_COPY = 1, DETSDW_SERIES_PHI = 2 };
 enum { DETSDW_SERIES_R_CHARGE = 0, DETSDW_SERIES_R_SPINZ = 1, DETSDW_SERIES_R_SDW = 2, DETSDW_SERIES_R_PAIRPLUS = 3,
-       DETSDW_SERIES_R_PAIRMINUS = 4, DETSDW_SERIES_RHO_S = 5 };
+       DETSDW_SERIES_R_PAIRMINUS = 4, DETSDW_SERIES_RHO_S = 5,
+       DETSDW_SERIES_BINDER_PHI = 6, DETSDW_SERIES_BINDER_RATIO_PHI = 7, DETSDW_SERIES_CHI_PHI = 8, DETSDW_SERIES_CHI_PHI_CONNECTED = 9,
+       DETSDW_SERIES_R_PHI = 10, DETSDW_SERIES_XI_PHI = 11 };
 int detsdw_series_begin(detsdw_replica* r, int binSize, int maxBins, int nfreq, int flags);
 int detsdw_series_route(detsdw_replica* r, const int* slotOfChain);
 int detsdw_series_get_route(detsdw_replica* r, int* out);

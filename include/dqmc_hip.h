@@ -437,7 +437,7 @@ int dqmc_measure_td_matsubara_host(dqmc_ctx* ctx, int channel, int nfreq, double
  * dqmc_series_begin allocates, outside the arena, the sample [nb][S], the open bin [nb][S], the closed bins [max_bins][nb][S], the
  * per-part flags and the result buffer of the statistics calls.  DQMC_EINVAL: empty or unknown mask, a missing block, bin_size < 1,
  * max_bins < 2, a series already open, a Hubbard context, a lattice too large for the LDS of the Matsubara or sample kernel.
- * dqmc_series_layout: where part (= bit number 0 .. 4) sits inside S.
+ * dqmc_series_layout: where part (= bit number 0 .. 4, or 6: the order-parameter part below) sits inside S.
  * dqmc_series_add_sweep (all chains): forms the sample and adds it to the open bin, open += sample, in call order; the bin_size-th call
  * writes closed[k] = open / bin_size and clears the open bin.  DQMC_EINVAL with no bin changed: the equal-time count of any chain or a
  * fine row count of any chain and channel of the mask is < 1; max_bins bins are already closed (nothing is dropped silently, and there
@@ -470,8 +470,26 @@ int dqmc_measure_td_matsubara_host(dqmc_ctx* ctx, int channel, int nfreq, double
  *   5:       rho_s = 1/8 Re [Lxx(1,0) - Lxx(0,1) + Lyy(0,1) - Lyy(1,0)] at frequency n = 0 of channel 3
  *   value = f(mean);  err = the jackknife over theta_(b) = f(x_(b)), about the mean of the theta_(b).
  * One writer per output element, fixed summation order (bins in index order), no atomics: bins and statistics do not depend on how
- * chains are batched, and two statistics calls give identical bits.  dqmc_series_end frees the buffers; dqmc_destroy does it too. */
-enum { DQMC_SERIES_EQ = 1, DQMC_SERIES_MATS_G = 2, DQMC_SERIES_MATS_PAIR = 4, DQMC_SERIES_MATS_PH = 8, DQMC_SERIES_MATS_CURRENT = 16 };
+ * chains are batched, and two statistics calls give identical bits.  dqmc_series_end frees the buffers; dqmc_destroy does it too.
+ * The order-parameter part, DQMC_SERIES_PHI = 64: bit 6 and part index 6 of dqmc_series_layout (bit 5 stays refused: the accepted mask is
+ * 0x5f).  It needs no block -- the field phi(r, k), k = 1 .. m, always exists -- and no flag, so it may be the only part of a series; it
+ * needs 1 <= nfreq <= m, and nfreq is stored in the state even when no Matsubara part is present.  It sits after all other parts and
+ * holds nfreq N + 5 doubles:
+ *   chi [nfreq][N], real, column qy L + qx.  With K = m N, q = 2 pi (qx, qy) / L, omega_n = 2 pi n / beta, n = 0 .. nfreq-1:
+ *           A_d(n, q) = (1/K) sum_{k=1..m} sum_r phi_d(r, k) exp(i 2 pi n k / m - i 2 pi (qx x + qy y) / L),   chi(n, q) = sum_d |A_d(n, q)|^2
+ *           (temporal sign +1, spatial sign -1, both normalisations inside A).  The physical susceptibility is beta N <chi(n, q)>.
+ *           The temporal phases cos / sin(2 pi j / m), j = n k mod m reduced in integers, and the spatial ones come from host tables.
+ *   scalars [5]:  |phibar| = sqrt(chi(0, 0));  |phibar|^2 = chi(0, 0), the bits of that chi element;  |phibar|^4 = (|phibar|^2)^2;
+ *           the equal-time susceptibility (N/m) sum_k sum_d ((1/N) sum_r phi_d(r, k))^2;  associatedEnergy = sum phi^2 / (2 N m).
+ * DQMC_EINVAL at dqmc_series_begin: nfreq outside 1 .. m, a lattice whose single-frequency tile exceeds the sample kernel's LDS.
+ * dqmc_series_phi_derived_host (all chains, value and err [nb][6]; DQMC_EINVAL for B < 2 or a series without the part), the jackknife
+ * of dqmc_series_derived_host, with beta = m dtau, chi0 = chi(0, (0,0)), chix = chi(0, column 1), chiy = chi(0, column L):
+ *   0: Binder cumulant 1 - <|phibar|^4> / (3 <|phibar|^2>^2)      1: Binder ratio <|phibar|^4> / <|phibar|^2>^2
+ *   2: beta N <|phibar|^2>                                        3: beta N (<|phibar|^2> - <|phibar|>^2)
+ *   4: R_phi = 1 - 1/2 (chix + chiy) / chi0                       5: xi_phi = sqrt(chi0 / (1/2 (chix + chiy)) - 1) / (2 sin(pi / L)),
+ *                                                                    NaN where the argument of the root is negative */
+enum { DQMC_SERIES_EQ = 1, DQMC_SERIES_MATS_G = 2, DQMC_SERIES_MATS_PAIR = 4, DQMC_SERIES_MATS_PH = 8, DQMC_SERIES_MATS_CURRENT = 16,
+       DQMC_SERIES_PHI = 64 };
 int dqmc_series_begin(dqmc_ctx* ctx, int bin_size, int max_bins, int nfreq, int parts);
 int dqmc_series_layout(dqmc_ctx* ctx, int part, size_t* offset, size_t* length);
 int dqmc_series_add_sweep(dqmc_ctx* ctx);
@@ -482,6 +500,7 @@ int dqmc_series_info(dqmc_ctx* ctx, int* bins_closed, int* sweeps_in_open_bin, s
 int dqmc_series_read_bins_host(dqmc_ctx* ctx, int first, int count, double* out);
 int dqmc_series_stats_host(dqmc_ctx* ctx, double* mean, double* err);
 int dqmc_series_derived_host(dqmc_ctx* ctx, double* value, double* err);
+int dqmc_series_phi_derived_host(dqmc_ctx* ctx, double* value, double* err);
 int dqmc_series_end(dqmc_ctx* ctx);
 /* ---- the series over a long run: re-binning, binning analysis with tau_int, export / import ------------
  * All of it is new surface: with none of these calls used, every call above keeps its bits, its error codes and its launches.
