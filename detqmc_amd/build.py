@@ -27,6 +27,7 @@ SOURCES = [
     "kernels_measure.hip",
     "kernels_hubbard.hip",
     "dqmc_context.hip",
+    "dqmc_measure_api.hip",
     os.path.join("host", "dsfmt19937.cpp"),
     os.path.join("host", "detsdw.cpp"),
     os.path.join("host", "dethubbard.cpp"),
@@ -42,7 +43,7 @@ def build(force=False, verbose=True):
     os.makedirs(LIBDIR, exist_ok=True)
     objdir = os.path.join(LIBDIR, "obj")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, "dqmc_internal.h"), os.path.join(CSRC, "host", "detsdw.h"),
+    headers = [os.path.join(CSRC, "dqmc_internal.h"), os.path.join(CSRC, "dqmc_ctx.h"), os.path.join(CSRC, "host", "detsdw.h"),
                os.path.join(CSRC, "host", "dsfmt19937.h"),
                os.path.join(CSRC, "host", "dethubbard.h"),
                os.path.join(HERE, "..", "include", "dqmc_hip.h"), os.path.join(HERE, "..", "include", "detsdw_host.h"),

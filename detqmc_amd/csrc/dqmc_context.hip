@@ -1,6 +1,6 @@
 // C-ABI implementation (include/dqmc_hip.h): device context of one DQMC replica and the
 // stabilised-sweep building blocks of DetModelGC (reference src/detmodel.h) on top of the kernels.
-#include "dqmc_internal.h"
+#include "dqmc_ctx.h"
 #include <cmath>
 #include <complex>
 #include <cstddef>
@@ -12,187 +12,8 @@
 
 void build_tournament(int nblk, std::vector<int>& out);   // kernels_svd.hip
 
-static thread_local std::string g_err;
-static int fail(int code, const std::string& msg) { g_err = msg; return code; }
-#define HIPCHK(x)                                                                                       \
-    do {                                                                                                \
-        hipError_t e_ = (x);                                                                            \
-        if (e_ != hipSuccess)                                                                           \
-            return fail(DQMC_EHIP, std::string(#x) + ": " + hipGetErrorString(e_) + " (" + __FILE__ + ":" + \
-                                       std::to_string(__LINE__) + ")");                                  \
-    } while (0)
+thread_local std::string g_err;
 
-// DQMC_SYNC_CHECK=1 (debug mode): every entry point that only enqueues work waits for its stream before it returns and
-// every kernel family scope waits when it closes, so an asynchronous GPU fault is reported by the call -- and the kernel
-// family -- that caused it.  Without it the enqueue-only entry points see a fault whenever the runtime notices it, i.e.
-// possibly one or more calls later (the message says so).  Results are identical either way.
-static bool sync_check_on() {
-    static const bool on = getenv("DQMC_SYNC_CHECK") && atoi(getenv("DQMC_SYNC_CHECK")) != 0;
-    return on;
-}
-
-struct UdVSlot { cplx* U; double* d; cplx* Vt; };
-
-enum { FAM_BMULT = DQMC_FAM_BMULT, FAM_GEMM = DQMC_FAM_GEMM, FAM_JACOBI = DQMC_FAM_DECOMP, FAM_UPDATE = DQMC_FAM_DECIDE,
-       FAM_OTHER = DQMC_FAM_OTHER, FAM_GATHER = DQMC_FAM_GATHER, FAM_FLUSH = DQMC_FAM_FLUSH, FAM_ROUNDS = 7, FAM_COUNT = DQMC_FAM_COUNT };
-
-struct dqmc_ctx {
-    dqmc_params p;
-    DevModel hm;
-    hipStream_t st = nullptr;
-    // pipelined local updates (dqmc_update_slice): the flush of block b runs on st2 while the decisions of block b + 1 run on st
-    hipStream_t st2 = nullptr;
-    hipEvent_t ev_win = nullptr, ev_flush = nullptr;
-    cplx* Gwin = nullptr;          // (MSF pbudget)^2: the next block's proposal window of G (k_update_window)
-    int pipe_P = 0;                // pbudget when the pipelined schedule is in effect, else 0
-    bool pipelined = false;        // latched at dqmc_create (dqmc_tuning::pipeline, n_g, chains): nothing else decides the schedule
-    uint64_t blocks_pipelined = 0, blocks_sequential = 0, cholqr_fallbacks = 0;
-    bool qr_bgs = false, green_lu = false;       // latched at dqmc_create (dqmc_tuning::qr_variant / green_variant)
-    std::vector<int> err_host;     // scratch of chol_failed()
-    // batched chains: nb chains in lockstep; per-chain buffers of chain b = chain 0's + b * cs (one arena)
-    Launch lc{nullptr, 1, 0};
-    int nb = 1, sel = 0;                // sel: chain the host-buffer entry points talk to (dqmc_select_chain)
-    char* arena = nullptr;
-    size_t arena_off = 0;
-    std::vector<void**> fixups;
-    int n_g = 0, MSF = 0, N = 0, m = 0, s = 0, n = 0, D = 0;
-    std::vector<void*> allocs;
-    // fields + backups
-    double *phi = nullptr, *coshT = nullptr, *sinhT = nullptr;
-    double *cdwl = nullptr, *cdwC = nullptr, *cdwS = nullptr;      // cdwU != 0 only
-    double *phi_bak = nullptr, *cosh_bak = nullptr, *sinh_bak = nullptr;
-    // Green's function, singular values of G^-1
-    cplx *G = nullptr, *G_bak = nullptr;
-    double *sv = nullptr, *sv_bak = nullptr;
-    std::vector<UdVSlot> storage, storage_bak;
-    UdVSlot spare{}, tmpudv{};
-    cplx *T1 = nullptr, *T2 = nullptr, *T3 = nullptr, *T4 = nullptr;
-    cplx *propK[2] = {nullptr, nullptr}, *Tdense = nullptr;   // CB_NONE only: blockdiag e^{-+dtau K} (n_g x n_g), GEMM target
-    cplx *propKh[2] = {nullptr, nullptr};                    // CB_NONE only: e^{-+dtau K / 2} (propK_half, propK_half_inv)
-    double* macc = nullptr;                                   // fermionic measurement accumulators (kernels_measure.hip)
-    size_t macc_n = 0;
-    // time-displaced Green's functions (dqmc_params::timedisplaced reserves them; dqmc_set_timedisplaced switches them on)
-    bool td_reserved = false, td_on = false;
-    int td_slice = -1;                                        // tau slice of the last pair GT0 / G0T (all chains), -1: none yet
-    cplx *GT0 = nullptr, *G0T = nullptr, *td_W = nullptr;     // G(tau,0), G(0,tau), scratch of the extra solves
-    double* td_sv = nullptr;                                  // SVD mode: log-det output of the LU / QR route (c->sv keeps the Jacobi values)
-    double* tdacc = nullptr;                                  // accumulator block of dqmc_measure_timedisplaced (kernels_measure.hip)
-    size_t tdacc_n = 0;
-    double* tdpacc = nullptr;                                 // accumulator block of dqmc_measure_timedisplaced_pair (timedisplaced == 2)
-    size_t tdpacc_n = 0;
-    // dqmc_params::td_particle_hole: G(0) of the boundary's own field configuration, (shifted G(0,tau))^H, one-body values, accumulators
-    cplx *G00 = nullptr, *ph_H = nullptr, *ph_ob = nullptr;
-    double* tdphacc = nullptr;
-    size_t tdphacc_n = 0;
-    // td_particle_hole == 2: bond amplitudes (shared by the chains), one-body values and accumulators of the current-current correlators
-    cplx *cur_bt = nullptr, *cur_ob = nullptr;
-    double* tdcacc = nullptr;
-    size_t tdcacc_n = 0;
-    // DQMC_TD_EVERY_SLICE: work copies of G(tau_k,0), G(0,tau_k), G(tau_k) that the segment / ends entries propagate (the sweep's own G,
-    // GT0, G0T, G00 are only read), the slice they stand on, and one fine accumulator block (m + 1 rows) per enabled channel
-    bool td_fine = false;
-    int fine_slice = -1;
-    cplx *fGT0 = nullptr, *fG0T = nullptr, *fGTT = nullptr;
-    double* facc[4] = {nullptr, nullptr, nullptr, nullptr};   // 0 G(k, tau) bins, 1 pairing, 2 particle-hole, 3 current
-    size_t facc_n[4] = {0, 0, 0, 0};
-    double* mats_out = nullptr;                               // dqmc_measure_td_matsubara_host: results + one flag per chain, outside the arena,
-    size_t mats_cap = 0;                                      // allocated on first use and grown on demand (doubles)
-    // dqmc_set_equal_time_correlators: block [chain][1 + 5 N] and one-body scratch [chain][5 N], outside the arena, allocated by the first enable
-    bool eq_on = false;
-    double* eqacc = nullptr;
-    cplx* eq_ob = nullptr;
-    size_t eqacc_n = 0;                                       // doubles per chain, 0 before the first enable
-    // dqmc_series_*: the measurement series.  Device buffers outside the arena, allocated by dqmc_series_begin and freed by dqmc_series_end
-    // or with the context: sample [nb][S], open bin [nb][S], closed bins [max_bins][nb][S], the per-part flags [5][nb], the cos / sin table
-    // (2 pi j / L [2 L]; with the order-parameter part, index 6 of off / len, also 2 pi j / m [2 m] behind it) and the result buffer
-    // of the statistics calls (mean, err [nb][S] each, then value, err [nb][6] each).  The counters live on the host.
-    // srctab [nb]: the source rows of dqmc_series_accumulate, filled from srchost before every launch; formed: the sample buffer holds
-    // the sample of a successful dqmc_series_form_sample that no dqmc_series_accumulate has consumed yet.
-    struct Series {
-        bool open = false, formed = false;
-        int bin_size = 0, max_bins = 0, nfreq = 0, parts = 0, closed = 0, in_open = 0;
-        int flags = 0;                                        // DQMC_SERIES_AUTO_REBIN | DQMC_SERIES_TRACK_VARIANCE (dqmc_series_configure)
-        long long samples = 0, rebins = 0;                    // accumulates since begin / merges of neighbouring bins so far
-        size_t S = 0, off[7] = {0, 0, 0, 0, 0, 0, 0}, len[7] = {0, 0, 0, 0, 0, 0, 0};   // index = bit number; 5 is never used
-        double *sample = nullptr, *openbin = nullptr, *bins = nullptr, *bad = nullptr, *trig = nullptr, *stat = nullptr;
-        double *var = nullptr;                                // running mean w [nb][S], then m2 [nb][S]: allocated with TRACK_VARIANCE
-        double *binning = nullptr;                            // result of dqmc_series_binning_host, err then tau [levels][nb][S] each,
-        size_t binning_cap = 0;                               // allocated on first use and grown on demand (doubles)
-        const double** srctab = nullptr;
-        std::vector<const double*> srchost;
-    } ser;
-    SvdWork sw{};
-    double hub_e_m2a = 1.0, hub_e_p2a = 1.0;  // Hubbard: exp(-+2 alpha) of weightRatioSingleFlip (dethubbard.cpp:866-867)
-    int stab = 0;                       // DQMC_STAB_SVD / DQMC_STAB_QR
-    QrWork qw{};
-    int* qr_perm = nullptr;
-    int* lu_swaps = nullptr;
-    cplx* lu_tneg = nullptr;       // -U12^T of the current LU panel (n_g x 32), operand of the trailing update on k_flush
-    uint64_t lu_calls = 0;         // gather lists of the LU panels (kernels_lu.hip)
-    int* qr_perm_inv = nullptr;      // inverse of qr_perm and 1/d of the last lazy UDT (triangular chaining product)
-    double* qr_dinv = nullptr;
-    double *rmax_inv = nullptr, *rmin = nullptr, *lmax_inv = nullptr, *lmin = nullptr;
-    UdVSlot eye{};
-    uint64_t qr_calls = 0;
-    int max_jacobi_sweeps = 80;
-    int last_svd_sweeps = 0;
-    double last_svd_residual = 0.0;
-    hipGraphExec_t jacobi_graph = nullptr;
-    unsigned long long jacobi_host_seq = 0;
-    uint64_t svd_calls = 0, svd_sweeps_total = 0;
-    int svd_sweeps_max = 0;
-    // updates
-    cplx *X = nullptr, *Gr = nullptr, *W = nullptr;
-    double* uniforms = nullptr;
-    size_t uni_cap = 0;
-    DevUpdateState* us = nullptr;
-    double* scalar_out = nullptr;
-    double* shift_buf = nullptr;        // [nchains][opdim] displacements of a global shift move (shared buffer)
-    int currentTimeslice = 0;
-    bool g_stale = false;          // dqmc_wrap_skip moved currentTimeslice without computing G: nothing may read G until it is rebuilt
-    // profiling
-    bool prof = false;
-    int prof_depth = 0;                 // open ProfScopes (they nest)
-    std::vector<hipEvent_t> ev_pool;
-    std::vector<std::pair<int, int>> ev_open;   // (family, index of begin event); end = index+1
-    size_t ev_used = 0;
-    double fam_ms[FAM_COUNT] = {0};
-    uint64_t fam_launches[FAM_COUNT] = {0};
-    double gemm_flops = 0.0;
-    SubProf subprof{};                  // hooks handed to the launchers through Launch::sub while profiling is on
-    SvdProfHooks qr_apply_hooks{};      // and through QrWork::apply_hooks (timing of the k_qr_apply launches)
-    std::vector<std::pair<int, int>> sub_open;      // (sub-family, begin event)
-    double sub_ms[SUBFAM_COUNT] = {0}, sub_flops[SUBFAM_COUNT] = {0}, sub_bytes[SUBFAM_COUNT] = {0};
-    uint64_t sub_launches[SUBFAM_COUNT] = {0};
-    std::string fault;                  // DQMC_SYNC_CHECK: first kernel family whose work came back with an error
-};
-static const char* const kFamName[FAM_COUNT] = {"k_bmult_chain / site-local V", "k_zgemm (n_g^3 products)", "decomposition (QR / LU / Jacobi, triangular solves)",
-                                                "k_update_decide / k_hubbard_slice", "small kernels (copies, scales, set-up)", "k_update_gather", "k_flush", "rounds"};
-// end of an entry point that only enqueued work
-static int finish(dqmc_ctx* c, const char* entry) {
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && sync_check_on()) e = hipStreamSynchronize(c->st);
-    if (e == hipSuccess && sync_check_on() && c->pipelined) {      // the flushes of a pipelined update run on the second stream
-        e = hipStreamSynchronize(c->st2);
-        if (e != hipSuccess && c->fault.empty()) c->fault = std::string("k_flush (second stream) (") + hipGetErrorString(e) + ")";
-    }
-    if (e == hipSuccess && c->fault.empty()) return DQMC_OK;
-    std::string msg = std::string(entry) + ": " + (e != hipSuccess ? hipGetErrorString(e) : "GPU fault");
-    if (!c->fault.empty()) msg += " in " + c->fault;
-    msg += sync_check_on() ? " [DQMC_SYNC_CHECK: raised by work this call enqueued]"
-                           : " [asynchronous: may stem from an earlier call; rerun with DQMC_SYNC_CHECK=1 to name the call and kernel family]";
-    return fail(DQMC_EHIP, msg);
-}
-
-// shared (chain independent) device memory
-template<class T>
-static int salloc(dqmc_ctx* c, T** p, size_t count) {
-    void* q = nullptr;
-    HIPCHK(hipMalloc(&q, count * sizeof(T)));
-    c->allocs.push_back(q);
-    *p = (T*)q;
-    return 0;
-}
 // per-chain device memory: reserves a range of the arena layout; *p holds the offset (+256) until
 // arena_commit turns it into chain 0's address.  p must stay where it is until then.
 template<class T>
@@ -216,52 +37,6 @@ static int arena_commit(dqmc_ctx* c) {
     c->lc = Launch{c->st, c->nb, cs};
     return 0;
 }
-// the selected chain's copy of a per-chain buffer (host-buffer entry points)
-template<class T> static T* selp(dqmc_ctx* c, T* p) { return (T*)((char*)p + (size_t)c->sel * c->lc.cs); }
-template<class T> static T* chainp(dqmc_ctx* c, T* p, int b) { return (T*)((char*)p + (size_t)b * c->lc.cs); }
-// Blocking copy on the context's OWN (non-blocking) stream.  Nothing in this library touches the legacy null stream: a
-// null-stream copy would wait for -- and hold up -- every blocking stream of the process, i.e. serialise contexts that
-// different host threads drive concurrently (one context per sub-batch of replicas, host/detsdw.cpp).
-static hipError_t copy_sync(dqmc_ctx* c, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
-    hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, c->st);
-    return e != hipSuccess ? e : hipStreamSynchronize(c->st);
-}
-
-static void prof_collect(dqmc_ctx* c);
-enum { PROF_EVENT_CAP = 8192 };     // events alive at most: beyond that the finished pairs are collected and reused
-// A fresh (begin, end) pair of timing events: records the begin event on st and returns its index; the end event is index + 1
-static int prof_event_pair(dqmc_ctx* c, hipStream_t st) {
-    if (c->ev_used + 2 > c->ev_pool.size())
-        for (int i = 0; i < 2; ++i) { hipEvent_t e; (void)hipEventCreate(&e); c->ev_pool.push_back(e); }
-    const int idx = (int)c->ev_used;
-    (void)hipEventRecord(c->ev_pool[idx], st);
-    c->ev_used += 2;
-    return idx;
-}
-
-struct ProfScope {
-    dqmc_ctx* c; int fam; uint64_t launches; int idx = -1;     // idx: this scope's begin event (scopes may nest)
-    hipStream_t st;                                            // the stream the scope's kernels are launched on (c->st, or c->st2 for a pipelined flush)
-    ProfScope(dqmc_ctx* c_, int fam_, uint64_t launches_, hipStream_t st_ = nullptr) : c(c_), fam(fam_), launches(launches_), st(st_ ? st_ : c_->st) {
-        c->fam_launches[fam] += launches;
-        if (!c->prof) return;
-        if (c->ev_used + 2 > PROF_EVENT_CAP && c->prof_depth == 0) prof_collect(c);   // not while an outer scope is open
-        ++c->prof_depth;
-        idx = prof_event_pair(c, st);
-        c->ev_open.push_back({fam, idx});
-    }
-    ~ProfScope() {
-        if (sync_check_on() && c->fault.empty()) {
-            hipError_t e = hipGetLastError();
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) c->fault = std::string(kFamName[fam]) + (st == c->st ? "" : " (second stream)") + " (" + hipGetErrorString(e) + ")";
-        }
-        if (idx < 0) return;
-        (void)hipEventRecord(c->ev_pool[idx + 1], st);
-        --c->prof_depth;
-    }
-};
-
 extern "C" const char* dqmc_last_error(void) { return g_err.c_str(); }
 static int set_slot_identity(dqmc_ctx* c, UdVSlot& sl);
 
@@ -768,8 +543,8 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
     A_(dalloc(c, &c->us, 1));
     A_(dalloc(c, &c->scalar_out, 8));
     A_(salloc(c, &c->shift_buf, (size_t)c->nb * 3));
-    c->macc_n = measure_accum_doubles(N, p->L);
-    A_(dalloc(c, &c->macc, c->macc_n));
+    auto acc_alloc = [c](int id, size_t count) { c->acc[id].n = count; return dalloc(c, &c->acc[id].p, count); };
+    A_(acc_alloc(ACC_SLICE, measure_accum_doubles(N, p->L)));
     const int td_level = p->timedisplaced & ~DQMC_TD_EVERY_SLICE;
     if (p->timedisplaced < 0 || td_level > 2) return fail(DQMC_EINVAL, "timedisplaced must be 0, 1 or 2 (| DQMC_TD_EVERY_SLICE)");
     if ((p->timedisplaced & DQMC_TD_EVERY_SLICE) && !td_level) return fail(DQMC_EINVAL, "DQMC_TD_EVERY_SLICE needs timedisplaced >= 1");
@@ -778,20 +553,15 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
         c->td_reserved = true;
         A_(dalloc(c, &c->GT0, n2)); A_(dalloc(c, &c->G0T, n2)); A_(dalloc(c, &c->td_W, n2));
         if (c->stab != DQMC_STAB_QR) { A_(alloc_qr_work(c)); A_(dalloc(c, &c->td_sv, (size_t)ng)); }
-        c->tdacc_n = measure_td_doubles(p->L, c->n);
-        A_(dalloc(c, &c->tdacc, c->tdacc_n));
-        if (td_level == 2) {        // behind the block above: a context with timedisplaced == 1 is laid out as before
-            c->tdpacc_n = measure_td_pair_doubles(N, c->n);
-            A_(dalloc(c, &c->tdpacc, c->tdpacc_n));
-        }
+        A_(acc_alloc(ACC_TD, measure_td_doubles(p->L, c->n)));
+        if (td_level == 2) A_(acc_alloc(ACC_TD_PAIR, measure_td_pair_doubles(N, c->n)));   // behind the block above: timedisplaced == 1 keeps its layout
     }
     if (p->td_particle_hole < 0 || p->td_particle_hole > 2) return fail(DQMC_EINVAL, "td_particle_hole must be 0, 1 or 2");
     if (p->td_particle_hole) {              // behind the blocks above: contexts without the flag are laid out as before
         if (!td_level) return fail(DQMC_EINVAL, "td_particle_hole needs timedisplaced >= 1");
         A_(dalloc(c, &c->G00, n2)); A_(dalloc(c, &c->ph_H, n2));
         A_(dalloc(c, &c->ph_ob, measure_td_ph_onebody_cplx(N)));
-        c->tdphacc_n = measure_td_ph_doubles(N, c->n);
-        A_(dalloc(c, &c->tdphacc, c->tdphacc_n));
+        A_(acc_alloc(ACC_TD_PH, measure_td_ph_doubles(N, c->n)));
     }
     if (p->td_particle_hole == 2) {         // behind the blocks above again: value 1 keeps its layout
         std::vector<hc> bt;
@@ -799,21 +569,18 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
         A_(salloc(c, &c->cur_bt, bt.size()));
         HIPCHK(copy_sync(c, c->cur_bt, bt.data(), bt.size() * sizeof(hc), hipMemcpyHostToDevice));
         A_(dalloc(c, &c->cur_ob, measure_td_current_onebody_cplx(N)));
-        c->tdcacc_n = measure_td_current_doubles(N, c->n);
-        A_(dalloc(c, &c->tdcacc, c->tdcacc_n));
+        A_(acc_alloc(ACC_TD_CUR, measure_td_current_doubles(N, c->n)));
     }
     if (p->timedisplaced & DQMC_TD_EVERY_SLICE) {   // behind every block above: contexts without the flag are laid out as before
         c->td_fine = true;
         A_(dalloc(c, &c->fGT0, n2)); A_(dalloc(c, &c->fG0T, n2)); A_(dalloc(c, &c->fGTT, n2));
         const bool on[4] = {true, td_level == 2, p->td_particle_hole >= 1, p->td_particle_hole == 2};
         for (int ch = 0; ch < 4; ++ch)
-            if (on[ch]) {
-                c->facc_n[ch] = (size_t)(p->m + 1) * (1 + measure_td_row_doubles(ch, N, p->L));
-                A_(dalloc(c, &c->facc[ch], c->facc_n[ch]));
-            }
+            if (on[ch]) A_(acc_alloc(ACC_FINE0 + ch, (size_t)(p->m + 1) * (1 + measure_td_row_doubles(ch, N, p->L))));
     }
     A_(arena_commit(c));                    // from here on the per-chain pointers are real (chain 0) addresses, zero filled
 #undef A_
+    for (int id = 0; id < ACC_EQ; ++id) c->acc[id].stride = c->lc.cs;
     c->qw.err = &c->us->chol_fail;
     hm.phi = c->phi; hm.coshT = c->coshT; hm.sinhT = c->sinhT;
     if (p->cdwU != 0.0) {
@@ -846,7 +613,7 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
     return DQMC_OK;
 }
 
-static void series_free(dqmc_ctx* c) {
+void series_free(dqmc_ctx* c) {
     dqmc_ctx::Series& s = c->ser;
     for (double* q : {s.sample, s.openbin, s.bins, s.bad, s.trig, s.stat, s.var, s.binning}) if (q) (void)hipFree(q);
     if (s.srctab) (void)hipFree((void*)s.srctab);
@@ -961,7 +728,7 @@ extern "C" int dqmc_get_fields_all_host(dqmc_ctx* c, double* phi_all) {
 // device-side building blocks
 // ---------------------------------------------------------------------------------------------
 // C = op(A) op(B) with n_g x n_g operands; callers set the options (negate, accumulate, scales, sharedA / sharedB, ...) by name
-static GemmArgs gemm_square(dqmc_ctx* c, const cplx* A, int opA, const cplx* B, int opB, cplx* C) {
+GemmArgs gemm_square(dqmc_ctx* c, const cplx* A, int opA, const cplx* B, int opB, cplx* C) {
     GemmArgs g;
     memset(&g, 0, sizeof(g));
     g.A = A; g.lda = c->n_g; g.opA = opA; g.B = B; g.ldb = c->n_g; g.opB = opB; g.C = C; g.ldc = c->n_g;
@@ -969,7 +736,7 @@ static GemmArgs gemm_square(dqmc_ctx* c, const cplx* A, int opA, const cplx* B, 
     return g;
 }
 // every n_g^3 product of the model goes through here: flop accounting (a lower triangular op(B) takes half the multiply-adds) and timing
-static void run_gemm(dqmc_ctx* c, const GemmArgs& g) {
+void run_gemm(dqmc_ctx* c, const GemmArgs& g) {
     c->gemm_flops += (g.b_lower ? 4.0 : 8.0) * (double)g.M * g.N * g.K * c->nb;
     ProfScope ps(c, FAM_GEMM, 1);
     launch_gemm(c->lc, g);
@@ -977,7 +744,7 @@ static void run_gemm(dqmc_ctx* c, const GemmArgs& g) {
 
 // chain order of checkerboard{Left,Right}MultiplyBmat[Inv] (detsdwopdim.cpp:2076-2090, 2172-2186,
 // 2307-2324, 2406-2420)
-static void bmult_dev(dqmc_ctx* c, int side, int inverse, int k2, int k1, cplx* A) {
+void bmult_dev(dqmc_ctx* c, int side, int inverse, int k2, int k1, cplx* A) {
     const int count = k2 - k1;
     if (count <= 0) return;
     bool ascending = (side == DQMC_LEFT) ? !inverse : (bool)inverse;
@@ -1390,7 +1157,6 @@ extern "C" int dqmc_advance(dqmc_ctx* c, int dir, int l) {
 }
 
 // every entry that reads G refuses while dqmc_wrap_skip has left it stale
-#define G_FRESH(c, who) do { if ((c)->g_stale) return fail(DQMC_EINVAL, who ": G is stale after dqmc_wrap_skip (dqmc_advance, dqmc_udv_setup or dqmc_set_green_host rebuild it)"); } while (0)
 
 // wrapUpGreen / wrapDownGreen (detmodel.h:1236-1259, 1066-1095)
 extern "C" int dqmc_wrap(dqmc_ctx* c, int dir, int k) {
@@ -1712,789 +1478,6 @@ extern "C" int dqmc_restore(dqmc_ctx* c) {
     return finish(c, "dqmc_restore");
 }
 
-// ---------------------------------------------------------------------------------------------
-// fermionic measurements: shiftGreenSymmetric + per-slice accumulation on the device
-// ---------------------------------------------------------------------------------------------
-// T1 <- e^{-dtau K/2} G e^{+dtau K/2} (detsdwopdim.cpp:4507-4612); src: G (default) or another matrix of the same shape
-static void shift_green_dev(dqmc_ctx* c, const cplx* src = nullptr) {
-    const size_t n2 = (size_t)c->n_g * c->n_g;
-    launch_copy(c->lc, src ? src : c->G, c->T1, n2);
-    if (!c->hm.dense) {
-        ProfScope ps(c, FAM_BMULT, 2);
-        launch_bmult(c->lc, nullptr, c->hm, DQMC_RIGHT, 1, 0, 1, 1, c->T1, c->n_g, /*shift=*/1);   // right: +sinh half steps
-        launch_bmult(c->lc, nullptr, c->hm, DQMC_LEFT, 0, 0, 1, 1, c->T1, c->n_g, /*shift=*/1);    // left:  -sinh half steps
-    } else {
-        GemmArgs g = gemm_square(c, c->T1, 0, c->propKh[1], 0, c->Tdense);
-        g.sharedB = 1;
-        run_gemm(c, g);
-        g = gemm_square(c, c->propKh[0], 0, c->Tdense, 0, c->T1);
-        g.sharedA = 1;
-        run_gemm(c, g);
-    }
-}
-extern "C" int dqmc_shift_green_symmetric_host(dqmc_ctx* c, dqmc_cplx* out) {
-    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
-    if (c->hm.hubbard) return fail(DQMC_EINVAL, "shiftGreenSymmetric belongs to the SDW model");
-    G_FRESH(c, "dqmc_shift_green_symmetric_host");
-    (void)hipSetDevice(c->p.device);
-    shift_green_dev(c);
-    HIPCHK(hipStreamSynchronize(c->st));
-    HIPCHK(hipGetLastError());
-    HIPCHK(copy_sync(c, out, selp(c, c->T1), (size_t)c->n_g * c->n_g * sizeof(cplx), hipMemcpyDeviceToHost));
-    return DQMC_OK;
-}
-extern "C" int dqmc_measure_reset(dqmc_ctx* c) {
-    if (!c) return fail(DQMC_EINVAL, "null ctx");
-    (void)hipSetDevice(c->p.device);
-    for (int b = 0; b < c->nb; ++b) HIPCHK(hipMemsetAsync(chainp(c, c->macc, b), 0, c->macc_n * sizeof(double), c->st));
-    if (c->td_reserved)
-        for (int b = 0; b < c->nb; ++b) HIPCHK(hipMemsetAsync(chainp(c, c->tdacc, b), 0, c->tdacc_n * sizeof(double), c->st));
-    if (c->tdpacc_n)
-        for (int b = 0; b < c->nb; ++b) HIPCHK(hipMemsetAsync(chainp(c, c->tdpacc, b), 0, c->tdpacc_n * sizeof(double), c->st));
-    if (c->tdphacc_n)
-        for (int b = 0; b < c->nb; ++b) HIPCHK(hipMemsetAsync(chainp(c, c->tdphacc, b), 0, c->tdphacc_n * sizeof(double), c->st));
-    if (c->tdcacc_n)
-        for (int b = 0; b < c->nb; ++b) HIPCHK(hipMemsetAsync(chainp(c, c->tdcacc, b), 0, c->tdcacc_n * sizeof(double), c->st));
-    for (int ch = 0; ch < 4; ++ch)
-        if (c->facc_n[ch])
-            for (int b = 0; b < c->nb; ++b) HIPCHK(hipMemsetAsync(chainp(c, c->facc[ch], b), 0, c->facc_n[ch] * sizeof(double), c->st));
-    if (c->eqacc_n) HIPCHK(hipMemsetAsync(c->eqacc, 0, c->eqacc_n * (size_t)c->nb * sizeof(double), c->st));
-    return DQMC_OK;
-}
-extern "C" int dqmc_measure_slice(dqmc_ctx* c) {
-    if (!c) return fail(DQMC_EINVAL, "null ctx");
-    G_FRESH(c, "dqmc_measure_slice");
-    (void)hipSetDevice(c->p.device);
-    if (c->hm.hubbard) {            // DetHubbard::measure (dethubbard.cpp:521-545): accumulator layout in kernels_hubbard.hip
-        ProfScope ps(c, FAM_OTHER, 1);
-        launch_hubbard_measure(c->lc, c->hm, c->G, c->macc);
-        return finish(c, "dqmc_measure_slice");
-    }
-    shift_green_dev(c);
-    { ProfScope ps(c, FAM_OTHER, 1); launch_measure_accum(c->lc, c->hm, c->T1, c->macc); }
-    if (c->eq_on) { ProfScope ps(c, FAM_OTHER, 2); launch_measure_eq_corr(c->lc, c->hm, c->T1, c->eq_ob, c->eqacc); }   // same T1, no second shift
-    return finish(c, "dqmc_measure_slice");
-}
-extern "C" size_t dqmc_measure_accum_size(dqmc_ctx* c) { return c ? c->macc_n : 0; }
-extern "C" int dqmc_measure_read_host(dqmc_ctx* c, double* out) {
-    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
-    (void)hipSetDevice(c->p.device);
-    HIPCHK(hipStreamSynchronize(c->st));
-    HIPCHK(copy_sync(c, out, selp(c, c->macc), c->macc_n * sizeof(double), hipMemcpyDeviceToHost));
-    return DQMC_OK;
-}
-// equal-time charge / spin / SDW / pairing correlators (dqmc_hip.h): a switch of dqmc_measure_slice with a block of its own
-extern "C" int dqmc_set_equal_time_correlators(dqmc_ctx* c, int on) {
-    if (!c) return fail(DQMC_EINVAL, "null ctx");
-    if (c->hm.hubbard) return fail(DQMC_EINVAL, "the equal-time correlators belong to the SDW model");
-    if (on && !c->eqacc_n) {
-        (void)hipSetDevice(c->p.device);
-        const size_t n = measure_eq_doubles(c->N);
-        if (const int rc = salloc(c, &c->eqacc, n * (size_t)c->nb)) return rc;
-        if (const int rc = salloc(c, &c->eq_ob, measure_eq_onebody_cplx(c->N) * (size_t)c->nb)) return rc;
-        HIPCHK(hipMemsetAsync(c->eqacc, 0, n * (size_t)c->nb * sizeof(double), c->st));
-        HIPCHK(hipMemsetAsync(c->eq_ob, 0, measure_eq_onebody_cplx(c->N) * (size_t)c->nb * sizeof(cplx), c->st));
-        c->eqacc_n = n;
-    }
-    c->eq_on = on != 0;
-    return DQMC_OK;
-}
-extern "C" size_t dqmc_measure_eq_accum_size(dqmc_ctx* c) { return c ? c->eqacc_n : 0; }
-extern "C" int dqmc_measure_eq_read_host(dqmc_ctx* c, double* out) {
-    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
-    if (!c->eqacc_n) return fail(DQMC_EINVAL, "the equal-time correlators have never been enabled (dqmc_set_equal_time_correlators)");
-    (void)hipSetDevice(c->p.device);
-    HIPCHK(hipStreamSynchronize(c->st));
-    HIPCHK(copy_sync(c, out, c->eqacc + (size_t)c->sel * c->eqacc_n, c->eqacc_n * sizeof(double), hipMemcpyDeviceToHost));
-    return DQMC_OK;
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// time-displaced Green's functions (dqmc_hip.h; computed inside green_from_udv while td_on)
-// ---------------------------------------------------------------------------------------------
-extern "C" int dqmc_set_timedisplaced(dqmc_ctx* c, int on) {
-    if (!c) return fail(DQMC_EINVAL, "null ctx");
-    if (on && !c->td_reserved) return fail(DQMC_EINVAL, "time-displaced Green's functions need a context created with dqmc_params::timedisplaced != 0");
-    c->td_on = on != 0;
-    return DQMC_OK;
-}
-extern "C" int dqmc_get_green_timedisplaced_host(dqmc_ctx* c, dqmc_cplx* g_t0, dqmc_cplx* g_0t, int* slice) {
-    if (!c || !g_t0 || !g_0t || !slice) return fail(DQMC_EINVAL, "null argument");
-    if (!c->td_reserved || c->td_slice < 0) return fail(DQMC_EINVAL, "no time-displaced Green's function has been computed");
-    (void)hipSetDevice(c->p.device);
-    HIPCHK(hipStreamSynchronize(c->st));
-    HIPCHK(hipGetLastError());
-    const size_t bytes = (size_t)c->n_g * c->n_g * sizeof(cplx);
-    HIPCHK(copy_sync(c, g_t0, selp(c, c->GT0), bytes, hipMemcpyDeviceToHost));
-    HIPCHK(copy_sync(c, g_0t, selp(c, c->G0T), bytes, hipMemcpyDeviceToHost));
-    *slice = c->td_slice;
-    return DQMC_OK;
-}
-extern "C" int dqmc_measure_timedisplaced(dqmc_ctx* c, int j) {
-    if (!c) return fail(DQMC_EINVAL, "null ctx");
-    if (!c->td_reserved) return fail(DQMC_EINVAL, "context created without dqmc_params::timedisplaced");
-    if (j < 1 || j > c->n - 1) return fail(DQMC_EINVAL, "boundary index j must be in 1..n-1");
-    if (c->td_slice != c->s * j) return fail(DQMC_EINVAL, "the last time-displaced pair does not belong to boundary j");
-    (void)hipSetDevice(c->p.device);
-    shift_green_dev(c, c->GT0);              // T1 = e^{-dtau K/2} G(tau_j, 0) e^{+dtau K/2}
-    { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td(c->lc, c->hm, c->T1, c->tdacc, j - 1, c->n - 1); }
-    return finish(c, "dqmc_measure_timedisplaced");
-}
-extern "C" size_t dqmc_measure_td_accum_size(dqmc_ctx* c) { return c ? c->tdacc_n : 0; }
-extern "C" int dqmc_measure_td_read_host(dqmc_ctx* c, double* out) {
-    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
-    if (!c->td_reserved) return fail(DQMC_EINVAL, "context created without dqmc_params::timedisplaced");
-    (void)hipSetDevice(c->p.device);
-    HIPCHK(hipStreamSynchronize(c->st));
-    HIPCHK(copy_sync(c, out, selp(c, c->tdacc), c->tdacc_n * sizeof(double), hipMemcpyDeviceToHost));
-    return DQMC_OK;
-}
-// pairing correlators of the same shifted G(tau_j, 0).  T1 is scratch of many other calls, so the shift is redone here and not
-// carried over from a dqmc_measure_timedisplaced(j) that may have come before
-extern "C" int dqmc_measure_timedisplaced_pair(dqmc_ctx* c, int j) {
-    if (!c) return fail(DQMC_EINVAL, "null ctx");
-    if (!c->tdpacc_n) return fail(DQMC_EINVAL, "context created without dqmc_params::timedisplaced == 2");
-    if (j < 1 || j > c->n - 1) return fail(DQMC_EINVAL, "boundary index j must be in 1..n-1");
-    if (c->td_slice != c->s * j) return fail(DQMC_EINVAL, "the last time-displaced pair does not belong to boundary j");
-    (void)hipSetDevice(c->p.device);
-    shift_green_dev(c, c->GT0);              // T1 = e^{-dtau K/2} G(tau_j, 0) e^{+dtau K/2}
-    { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td_pair(c->lc, c->hm, c->T1, c->tdpacc, j - 1, c->n - 1); }
-    return finish(c, "dqmc_measure_timedisplaced_pair");
-}
-extern "C" size_t dqmc_measure_td_pair_accum_size(dqmc_ctx* c) { return c ? c->tdpacc_n : 0; }
-extern "C" int dqmc_measure_td_pair_read_host(dqmc_ctx* c, double* out) {
-    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
-    if (!c->tdpacc_n) return fail(DQMC_EINVAL, "context created without dqmc_params::timedisplaced == 2");
-    (void)hipSetDevice(c->p.device);
-    HIPCHK(hipStreamSynchronize(c->st));
-    HIPCHK(copy_sync(c, out, selp(c, c->tdpacc), c->tdpacc_n * sizeof(double), hipMemcpyDeviceToHost));
-    return DQMC_OK;
-}
-// particle-hole correlators of the boundary the context stands on.  One-body values first (shifted G(tau_j), shifted G(0): only their
-// site-diagonal 4 x 4 blocks are needed, so neither shifted matrix is kept); then the shifted G(0,tau) leaves the shift scratch through
-// the conjugate tile transpose -- the copy it needs anyway -- and the shifted G(tau,0) stays in T1
-extern "C" int dqmc_measure_timedisplaced_ph(dqmc_ctx* c, int j) {
-    if (!c) return fail(DQMC_EINVAL, "null ctx");
-    if (!c->tdphacc_n) return fail(DQMC_EINVAL, "context created without dqmc_params::td_particle_hole");
-    if (j < 1 || j > c->n - 1) return fail(DQMC_EINVAL, "boundary index j must be in 1..n-1");
-    if (c->td_slice != c->s * j) return fail(DQMC_EINVAL, "the last time-displaced pair does not belong to boundary j");
-    if (c->currentTimeslice != c->s * j) return fail(DQMC_EINVAL, "the context has left boundary j: G is no longer G(tau_j)");
-    G_FRESH(c, "time-displaced measurement");
-    (void)hipSetDevice(c->p.device);
-    shift_green_dev(c);
-    { ProfScope ps(c, FAM_OTHER, 1); launch_td_ph_onebody(c->lc, c->hm, c->T1, c->ph_ob, 0); }
-    shift_green_dev(c, c->G00);
-    { ProfScope ps(c, FAM_OTHER, 1); launch_td_ph_onebody(c->lc, c->hm, c->T1, c->ph_ob, 1); }
-    shift_green_dev(c, c->G0T);
-    { ProfScope ps(c, FAM_OTHER, 1); launch_conj_transpose(c->lc, c->T1, c->ph_H, c->n_g); }
-    shift_green_dev(c, c->GT0);
-    { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td_ph(c->lc, c->hm, c->T1, c->ph_H, c->ph_ob, c->tdphacc, j - 1, c->n - 1); }
-    return finish(c, "dqmc_measure_timedisplaced_ph");
-}
-extern "C" size_t dqmc_measure_td_ph_accum_size(dqmc_ctx* c) { return c ? c->tdphacc_n : 0; }
-extern "C" int dqmc_measure_td_ph_read_host(dqmc_ctx* c, double* out) {
-    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
-    if (!c->tdphacc_n) return fail(DQMC_EINVAL, "context created without dqmc_params::td_particle_hole");
-    (void)hipSetDevice(c->p.device);
-    HIPCHK(hipStreamSynchronize(c->st));
-    HIPCHK(copy_sync(c, out, selp(c, c->tdphacc), c->tdphacc_n * sizeof(double), hipMemcpyDeviceToHost));
-    return DQMC_OK;
-}
-// current-current correlators of the boundary the context stands on: the same four shifted matrices, prepared here again so that the call
-// stands on its own next to dqmc_measure_timedisplaced_ph (either order); ph_H and T1 are scratch of both
-extern "C" int dqmc_measure_timedisplaced_current(dqmc_ctx* c, int j) {
-    if (!c) return fail(DQMC_EINVAL, "null ctx");
-    if (!c->tdcacc_n) return fail(DQMC_EINVAL, "context created without dqmc_params::td_particle_hole = 2");
-    if (j < 1 || j > c->n - 1) return fail(DQMC_EINVAL, "boundary index j must be in 1..n-1");
-    if (c->td_slice != c->s * j) return fail(DQMC_EINVAL, "the last time-displaced pair does not belong to boundary j");
-    if (c->currentTimeslice != c->s * j) return fail(DQMC_EINVAL, "the context has left boundary j: G is no longer G(tau_j)");
-    G_FRESH(c, "time-displaced measurement");
-    (void)hipSetDevice(c->p.device);
-    shift_green_dev(c);
-    { ProfScope ps(c, FAM_OTHER, 1); launch_td_current_onebody(c->lc, c->hm, c->T1, c->cur_bt, c->cur_ob, 0); }
-    shift_green_dev(c, c->G00);
-    { ProfScope ps(c, FAM_OTHER, 1); launch_td_current_onebody(c->lc, c->hm, c->T1, c->cur_bt, c->cur_ob, 1); }
-    shift_green_dev(c, c->G0T);
-    { ProfScope ps(c, FAM_OTHER, 1); launch_conj_transpose(c->lc, c->T1, c->ph_H, c->n_g); }
-    shift_green_dev(c, c->GT0);
-    { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td_current(c->lc, c->hm, c->T1, c->ph_H, c->cur_bt, c->cur_ob, c->tdcacc, j - 1, c->n - 1); }
-    return finish(c, "dqmc_measure_timedisplaced_current");
-}
-extern "C" size_t dqmc_measure_td_current_accum_size(dqmc_ctx* c) { return c ? c->tdcacc_n : 0; }
-extern "C" int dqmc_measure_td_current_read_host(dqmc_ctx* c, double* out) {
-    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
-    if (!c->tdcacc_n) return fail(DQMC_EINVAL, "context created without dqmc_params::td_particle_hole = 2");
-    (void)hipSetDevice(c->p.device);
-    HIPCHK(hipStreamSynchronize(c->st));
-    HIPCHK(copy_sync(c, out, selp(c, c->tdcacc), c->tdcacc_n * sizeof(double), hipMemcpyDeviceToHost));
-    return DQMC_OK;
-}
-extern "C" int dqmc_get_green0_timedisplaced_host(dqmc_ctx* c, dqmc_cplx* g00, int* slice) {
-    if (!c || !g00 || !slice) return fail(DQMC_EINVAL, "null argument");
-    if (!c->G00) return fail(DQMC_EINVAL, "context created without dqmc_params::td_particle_hole");
-    if (c->td_slice < 0) return fail(DQMC_EINVAL, "no time-displaced Green's function has been computed");
-    (void)hipSetDevice(c->p.device);
-    HIPCHK(hipStreamSynchronize(c->st));
-    HIPCHK(hipGetLastError());
-    HIPCHK(copy_sync(c, g00, selp(c, c->G00), (size_t)c->n_g * c->n_g * sizeof(cplx), hipMemcpyDeviceToHost));
-    *slice = c->td_slice;
-    return DQMC_OK;
-}
-
-// ---- every time slice (DQMC_TD_EVERY_SLICE) ----------------------------------------------------------------------------------
-// One-body values of an equal-time matrix for the particle-hole and current kernels: one shift, both tables (t = 0: tau side, 1: 0 side)
-static void td_fine_onebody(dqmc_ctx* c, const cplx* g, int t) {
-    if (!c->facc_n[2]) return;
-    shift_green_dev(c, g);
-    { ProfScope ps(c, FAM_OTHER, 1); launch_td_ph_onebody(c->lc, c->hm, c->T1, c->ph_ob, t); }
-    if (c->facc_n[3]) { ProfScope ps(c, FAM_OTHER, 1); launch_td_current_onebody(c->lc, c->hm, c->T1, c->cur_bt, c->cur_ob, t); }
-}
-// Row k of every enabled fine block from (gt0, g0t, gtt) = (G(tau_k,0), G(0,tau_k), G(tau_k)).  The shifted matrices are prepared ONCE
-// and handed to all channel kernels: shifted gtt -> tau-side one-body values (gtt == nullptr: already there), (shifted g0t)^H -> ph_H,
-// shifted gt0 -> T1.  The 0-side one-body values are the caller's business (once per segment).  Same kernels, operands and order as the
-// four coarse entries, which prepare the same matrices once EACH.
-static void td_fine_row(dqmc_ctx* c, int k, const cplx* gt0, const cplx* g0t, const cplx* gtt) {
-    const int rows = c->m + 1;
-    if (gtt) td_fine_onebody(c, gtt, 0);
-    if (c->facc_n[2]) {
-        shift_green_dev(c, g0t);
-        { ProfScope ps(c, FAM_OTHER, 1); launch_conj_transpose(c->lc, c->T1, c->ph_H, c->n_g); }
-    }
-    shift_green_dev(c, gt0);
-    { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td(c->lc, c->hm, c->T1, c->facc[0], k, rows); }
-    if (c->facc_n[1]) { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td_pair(c->lc, c->hm, c->T1, c->facc[1], k, rows); }
-    if (c->facc_n[2]) { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td_ph(c->lc, c->hm, c->T1, c->ph_H, c->ph_ob, c->facc[2], k, rows); }
-    if (c->facc_n[3]) {
-        ProfScope ps(c, FAM_OTHER, 1);
-        launch_measure_td_current(c->lc, c->hm, c->T1, c->ph_H, c->cur_bt, c->cur_ob, c->facc[3], k, rows);
-    }
-}
-// the work copies from slice k to k + 1 (dir > 0) or to k - 1 (dir < 0), fields as they are on the device now:
-//   up:   G(t,0) <- B_{k+1} G(t,0),   G(0,t) <- G(0,t) B_{k+1}^-1,   G(t) <- B_{k+1} G(t) B_{k+1}^-1
-//   down: G(t,0) <- B_k^-1 G(t,0),    G(0,t) <- G(0,t) B_k,          G(t) <- B_k^-1 G(t) B_k
-static void td_fine_step(dqmc_ctx* c, int k, int dir) {
-    if (dir > 0) {
-        bmult_dev(c, DQMC_LEFT, 0, k + 1, k, c->fGT0);
-        bmult_dev(c, DQMC_RIGHT, 1, k + 1, k, c->fG0T);
-        bmult_dev(c, DQMC_RIGHT, 1, k + 1, k, c->fGTT);
-        bmult_dev(c, DQMC_LEFT, 0, k + 1, k, c->fGTT);
-    } else {
-        bmult_dev(c, DQMC_LEFT, 1, k, k - 1, c->fGT0);
-        bmult_dev(c, DQMC_RIGHT, 0, k, k - 1, c->fG0T);
-        bmult_dev(c, DQMC_RIGHT, 0, k, k - 1, c->fGTT);
-        bmult_dev(c, DQMC_LEFT, 1, k, k - 1, c->fGTT);
-    }
-    c->fine_slice = k + (dir > 0 ? 1 : -1);
-}
-static void td_fine_load_boundary(dqmc_ctx* c) {
-    const size_t n2 = (size_t)c->n_g * c->n_g;
-    ProfScope ps(c, FAM_OTHER, 3);
-    launch_copy(c->lc, c->GT0, c->fGT0, n2);
-    launch_copy(c->lc, c->G0T, c->fG0T, n2);
-    launch_copy(c->lc, c->G, c->fGTT, n2);
-    c->fine_slice = c->td_slice;
-}
-extern "C" int dqmc_measure_timedisplaced_segment(dqmc_ctx* c, int j) {
-    if (!c) return fail(DQMC_EINVAL, "null ctx");
-    if (!c->td_fine) return fail(DQMC_EINVAL, "context created without DQMC_TD_EVERY_SLICE");
-    if (j < 1 || j > c->n - 1) return fail(DQMC_EINVAL, "boundary index j must be in 1..n-1");
-    if (c->td_slice != c->s * j) return fail(DQMC_EINVAL, "the last time-displaced pair does not belong to boundary j");
-    if (c->currentTimeslice != c->s * j) return fail(DQMC_EINVAL, "the context has left boundary j: G is no longer G(tau_j)");
-    G_FRESH(c, "time-displaced measurement");
-    (void)hipSetDevice(c->p.device);
-    const int s = c->s, k0 = s * j, k1 = (s * (j + 1) < c->m ? s * (j + 1) : c->m) - 1;
-    td_fine_onebody(c, c->G00, 1);            // G(0) does not move with tau: once per segment
-    td_fine_load_boundary(c);
-    for (int k = k0; k <= k1; ++k) {
-        td_fine_row(c, k, c->fGT0, c->fG0T, c->fGTT);
-        if (k < k1) td_fine_step(c, k, +1);
-    }
-    if (j == 1 && s > 1) {                    // the slices below the first boundary have no boundary of their own
-        td_fine_load_boundary(c);
-        for (int k = s; k >= 2; --k) {
-            td_fine_step(c, k, -1);
-            td_fine_row(c, k - 1, c->fGT0, c->fG0T, c->fGTT);
-        }
-    }
-    return finish(c, "dqmc_measure_timedisplaced_segment");
-}
-// For the tests only, exported but not part of include/dqmc_hip.h: the work copies at slice k of boundary j's segment, by the steps
-// dqmc_measure_timedisplaced_segment takes (its preconditions; DQMC_EINVAL for a k outside the segment); nothing is measured
-extern "C" int dqmc_td_fine_propagate(dqmc_ctx* c, int j, int k) {
-    if (!c) return fail(DQMC_EINVAL, "null ctx");
-    if (!c->td_fine) return fail(DQMC_EINVAL, "context created without DQMC_TD_EVERY_SLICE");
-    if (j < 1 || j > c->n - 1) return fail(DQMC_EINVAL, "boundary index j must be in 1..n-1");
-    if (c->td_slice != c->s * j) return fail(DQMC_EINVAL, "the last time-displaced pair does not belong to boundary j");
-    if (c->currentTimeslice != c->s * j) return fail(DQMC_EINVAL, "the context has left boundary j: G is no longer G(tau_j)");
-    G_FRESH(c, "time-displaced measurement");
-    const int s = c->s, k0 = s * j, k1 = (s * (j + 1) < c->m ? s * (j + 1) : c->m) - 1;
-    if (k > k1 || k < (j == 1 ? 1 : k0)) return fail(DQMC_EINVAL, "slice k does not belong to the segment of boundary j");
-    (void)hipSetDevice(c->p.device);
-    td_fine_load_boundary(c);
-    for (int q = k0; q < k; ++q) td_fine_step(c, q, +1);
-    for (int q = k0; q > k; --q) td_fine_step(c, q, -1);
-    return finish(c, "dqmc_td_fine_propagate");
-}
-extern "C" int dqmc_measure_timedisplaced_ends(dqmc_ctx* c) {
-    if (!c) return fail(DQMC_EINVAL, "null ctx");
-    if (!c->td_fine) return fail(DQMC_EINVAL, "context created without DQMC_TD_EVERY_SLICE");
-    if (c->currentTimeslice != 0 && c->currentTimeslice != c->m)
-        return fail(DQMC_EINVAL, "the context does not stand at tau = 0 (beta): G is not G(0)");
-    G_FRESH(c, "dqmc_measure_timedisplaced_ends");
-    (void)hipSetDevice(c->p.device);
-    // row m from the work copies (they are what dqmc_get_green_td_fine_host reports afterwards), row 0 from T2 / T3: scratch of the
-    // Green's function routines, idle here (the shifts use T1 and, with the dense B, Tdense only)
-    { ProfScope ps(c, FAM_OTHER, 1); launch_td_ends(c->lc, c->G, c->T2, c->T3, c->fGT0, c->fG0T, c->fGTT, c->n_g); }
-    c->fine_slice = c->m;
-    td_fine_onebody(c, c->G, 0);              // G(tau) = G(0) = G for both rows and both sides: ONE shift of G
-    if (c->facc_n[2]) {
-        { ProfScope ps(c, FAM_OTHER, 1); launch_td_ph_onebody(c->lc, c->hm, c->T1, c->ph_ob, 1); }
-        if (c->facc_n[3]) { ProfScope ps(c, FAM_OTHER, 1); launch_td_current_onebody(c->lc, c->hm, c->T1, c->cur_bt, c->cur_ob, 1); }
-    }
-    td_fine_row(c, 0, c->T2, c->T3, nullptr);
-    td_fine_row(c, c->m, c->fGT0, c->fG0T, nullptr);
-    return finish(c, "dqmc_measure_timedisplaced_ends");
-}
-extern "C" size_t dqmc_measure_td_fine_accum_size(dqmc_ctx* c, int channel) {
-    return c && channel >= 0 && channel < 4 ? c->facc_n[channel] : 0;
-}
-extern "C" int dqmc_measure_td_fine_read_host(dqmc_ctx* c, int channel, double* out) {
-    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
-    if (channel < 0 || channel >= 4 || !c->facc_n[channel]) return fail(DQMC_EINVAL, "no every-slice block for this channel");
-    (void)hipSetDevice(c->p.device);
-    HIPCHK(hipStreamSynchronize(c->st));
-    HIPCHK(copy_sync(c, out, selp(c, c->facc[channel]), c->facc_n[channel] * sizeof(double), hipMemcpyDeviceToHost));
-    return DQMC_OK;
-}
-extern "C" size_t dqmc_measure_td_matsubara_size(dqmc_ctx* c, int channel, int nfreq) {
-    if (!c || channel < 0 || channel >= 4 || !c->facc_n[channel] || nfreq < 1 || nfreq > c->m) return 0;
-    return (size_t)c->nb * (channel == 2 ? 3 : 2) * nfreq * c->N * 2;
-}
-extern "C" int dqmc_measure_td_matsubara_host(dqmc_ctx* c, int channel, int nfreq, double* out) {
-    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
-    if (!c->td_fine) return fail(DQMC_EINVAL, "context created without DQMC_TD_EVERY_SLICE");
-    if (channel < 0 || channel >= 4 || !c->facc_n[channel]) return fail(DQMC_EINVAL, "no every-slice block for this channel");
-    if (nfreq < 1 || nfreq > c->m) return fail(DQMC_EINVAL, "nfreq must be in 1..m");
-    (void)hipSetDevice(c->p.device);
-    const size_t n_out = dqmc_measure_td_matsubara_size(c, channel, nfreq), need = n_out + (size_t)c->nb;
-    if (need > c->mats_cap) {
-        HIPCHK(hipStreamSynchronize(c->st));
-        if (c->mats_out) { (void)hipFree(c->mats_out); c->mats_out = nullptr; c->mats_cap = 0; }
-        HIPCHK(hipMalloc((void**)&c->mats_out, need * sizeof(double)));
-        c->mats_cap = need;
-    }
-    const int apbx = c->p.bc == DQMC_BC_APBC_X || c->p.bc == DQMC_BC_APBC_XY, apby = c->p.bc == DQMC_BC_APBC_Y || c->p.bc == DQMC_BC_APBC_XY;
-    bool launched;
-    { ProfScope ps(c, FAM_OTHER, 1); launched = launch_td_matsubara(c->lc, c->hm, c->facc[channel], channel, nfreq, apbx, apby, c->mats_out, c->mats_out + n_out); }
-    if (!launched) return fail(DQMC_EINVAL, "dqmc_measure_td_matsubara_host: the lattice is too large for the kernel's LDS");
-    { const int rc = finish(c, "dqmc_measure_td_matsubara_host"); if (rc != DQMC_OK) return rc; }
-    std::vector<double> bad((size_t)c->nb);
-    HIPCHK(copy_sync(c, bad.data(), c->mats_out + n_out, bad.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (double b : bad) if (b != 0.0) return fail(DQMC_EINVAL, "an every-slice row has no sample: the measurement sweep did not visit every time slice");
-    HIPCHK(copy_sync(c, out, c->mats_out, n_out * sizeof(double), hipMemcpyDeviceToHost));
-    return DQMC_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// measurement series (dqmc_hip.h; kernels in kernels_measure.hip)
-// ---------------------------------------------------------------------------------------------
-static bool ser_apbx(const dqmc_ctx* c) { return c->p.bc == DQMC_BC_APBC_X || c->p.bc == DQMC_BC_APBC_XY; }
-static bool ser_apby(const dqmc_ctx* c) { return c->p.bc == DQMC_BC_APBC_Y || c->p.bc == DQMC_BC_APBC_XY; }
-extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nfreq, int parts) {
-    if (!c) return fail(DQMC_EINVAL, "null ctx");
-    if (c->hm.hubbard) return fail(DQMC_EINVAL, "the measurement series belongs to the SDW model");
-    if (c->ser.open) return fail(DQMC_EINVAL, "a measurement series is already open (dqmc_series_end)");
-    if (parts <= 0 || (parts & ~0x5f)) return fail(DQMC_EINVAL, "dqmc_series_begin: parts must be a non-empty mask of bits 0 .. 4 and 6");
-    if (bin_size < 1) return fail(DQMC_EINVAL, "dqmc_series_begin: bin_size must be at least 1");
-    if (max_bins < 2) return fail(DQMC_EINVAL, "dqmc_series_begin: max_bins must be at least 2");
-    if ((parts & 1) && !c->eqacc_n) return fail(DQMC_EINVAL, "dqmc_series_begin: the equal-time block has never been enabled (dqmc_set_equal_time_correlators)");
-    if ((parts & 1) && series_eq_sample_lds_bytes(c->hm.L) > 152 * 1024)
-        return fail(DQMC_EINVAL, "dqmc_series_begin: the lattice is too large for the equal-time sample kernel's LDS");
-    dqmc_ctx::Series s;
-    const size_t N = (size_t)c->N;
-    if (parts & 1) { s.off[0] = 0; s.len[0] = 10 * N; s.S = 10 * N; }
-    for (int ch = 0; ch < 4; ++ch) {
-        if (!(parts & (2 << ch))) continue;
-        if (!c->td_fine || !c->facc_n[ch]) return fail(DQMC_EINVAL, "dqmc_series_begin: no every-slice block for a channel of the mask");
-        if (nfreq < 1 || nfreq > c->m) return fail(DQMC_EINVAL, "dqmc_series_begin: nfreq must be in 1..m");
-        if (!td_matsubara_fits(c->hm, ch, nfreq)) return fail(DQMC_EINVAL, "dqmc_series_begin: the lattice is too large for the Matsubara kernel's LDS");
-        s.off[1 + ch] = s.S; s.len[1 + ch] = (size_t)(ch == 2 ? 3 : 2) * nfreq * N * 2; s.S += s.len[1 + ch];
-    }
-    if (parts & DQMC_SERIES_PHI) {                          // the field always exists: no block to ask for
-        if (nfreq < 1 || nfreq > c->m) return fail(DQMC_EINVAL, "dqmc_series_begin: nfreq must be in 1..m");
-        if (series_phi_sample_fgroup(c->hm.L, c->m, nfreq) < 1)
-            return fail(DQMC_EINVAL, "dqmc_series_begin: the lattice is too large for the order-parameter sample kernel's LDS");
-        s.off[6] = s.S; s.len[6] = (size_t)nfreq * N + 5; s.S += s.len[6];
-    }
-    s.bin_size = bin_size; s.max_bins = max_bins; s.nfreq = (parts & (0x1e | DQMC_SERIES_PHI)) ? nfreq : 0; s.parts = parts;
-    (void)hipSetDevice(c->p.device);
-    const size_t n = (size_t)c->nb * s.S, L = (size_t)c->hm.L;
-    c->ser = s;                                             // from here on series_free releases what was allocated
-    dqmc_ctx::Series& r = c->ser;
-    hipError_t e = (parts & DQMC_SERIES_PHI) ? series_phi_sample_prepare() : hipSuccess;   // an attribute failure is an error here, not at launch
-    if (e == hipSuccess) e = hipMalloc((void**)&r.sample, n * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&r.openbin, n * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&r.bins, (size_t)max_bins * n * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&r.bad, (size_t)5 * c->nb * sizeof(double));
-    const size_t mt = (parts & DQMC_SERIES_PHI) ? (size_t)c->m : 0;     // the temporal table of the order-parameter part
-    if (e == hipSuccess) e = hipMalloc((void**)&r.trig, 2 * (L + mt) * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&r.stat, (2 * n + (size_t)12 * c->nb) * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&r.srctab, (size_t)c->nb * sizeof(const double*));
-    if (e == hipSuccess) e = hipMemsetAsync(r.sample, 0, n * sizeof(double), c->st);
-    if (e == hipSuccess) e = hipMemsetAsync(r.openbin, 0, n * sizeof(double), c->st);
-    if (e == hipSuccess) e = hipMemsetAsync(r.bins, 0, (size_t)max_bins * n * sizeof(double), c->st);
-    if (e == hipSuccess) e = hipMemsetAsync(r.bad, 0, (size_t)5 * c->nb * sizeof(double), c->st);
-    if (e == hipSuccess) {
-        // cos / sin(2 pi j / L) as finishFermionic of the host layer forms them: the device's structure factors use the same values
-        std::vector<double> trig(2 * (L + mt));
-        for (size_t j = 0; j < L; ++j) { trig[j] = std::cos(2.0 * M_PI * double(j) / double(L)); trig[L + j] = std::sin(2.0 * M_PI * double(j) / double(L)); }
-        for (size_t j = 0; j < mt; ++j) { trig[2 * L + j] = std::cos(2.0 * M_PI * double(j) / double(mt)); trig[2 * L + mt + j] = std::sin(2.0 * M_PI * double(j) / double(mt)); }
-        e = copy_sync(c, r.trig, trig.data(), trig.size() * sizeof(double), hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) { series_free(c); return fail(DQMC_EHIP, std::string("dqmc_series_begin: ") + hipGetErrorString(e)); }
-    r.open = true;
-    return DQMC_OK;
-}
-extern "C" int dqmc_series_end(dqmc_ctx* c) {
-    if (!c) return fail(DQMC_EINVAL, "null ctx");
-    if (!c->ser.open) return fail(DQMC_EINVAL, "no measurement series is open");
-    (void)hipSetDevice(c->p.device);
-    HIPCHK(hipStreamSynchronize(c->st));
-    series_free(c);
-    return DQMC_OK;
-}
-extern "C" int dqmc_series_layout(dqmc_ctx* c, int part, size_t* offset, size_t* length) {
-    if (!c || !offset || !length) return fail(DQMC_EINVAL, "null argument");
-    if (!c->ser.open) return fail(DQMC_EINVAL, "no measurement series is open");
-    if (part < 0 || part > 6 || !(c->ser.parts & (1 << part))) return fail(DQMC_EINVAL, "dqmc_series_layout: the part is not in the series");
-    *offset = c->ser.off[part]; *length = c->ser.len[part];
-    return DQMC_OK;
-}
-extern "C" int dqmc_series_info(dqmc_ctx* c, int* bins_closed, int* sweeps_in_open_bin, size_t* sample_len) {
-    if (!c) return fail(DQMC_EINVAL, "null ctx");
-    if (!c->ser.open) return fail(DQMC_EINVAL, "no measurement series is open");
-    if (bins_closed) *bins_closed = c->ser.closed;
-    if (sweeps_in_open_bin) *sweeps_in_open_bin = c->ser.in_open;
-    if (sample_len) *sample_len = c->ser.S;
-    return DQMC_OK;
-}
-// The first half of dqmc_series_add_sweep: the sample of all chains from the blocks as they stand, and the flags read back.  `entry`
-// names the public call in the messages.
-static int series_form_sample(dqmc_ctx* c, const char* entry) {
-    dqmc_ctx::Series& s = c->ser;
-    const std::string who(entry);
-    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
-    if (s.closed >= s.max_bins) return fail(DQMC_EINVAL, who + ": the series is full (max_bins bins are closed)");
-    (void)hipSetDevice(c->p.device);
-    s.formed = false;                                       // the sample buffer is rewritten from here on
-    // the flags of the parts behind each other, [part][chain]
-    int nparts = 0;
-    {
-        ProfScope ps(c, FAM_OTHER, 0);
-        if (s.parts & 1) {
-            if (!launch_series_eq_sample(c->lc, c->hm, c->eqacc, c->eqacc_n, s.trig, s.sample, s.S, s.off[0], s.bad))
-                return fail(DQMC_EINVAL, who + ": the lattice is too large for the equal-time sample kernel's LDS");
-            ++nparts;
-        }
-        for (int ch = 0; ch < 4; ++ch)
-            if (s.parts & (2 << ch)) {
-                if (!launch_td_matsubara(c->lc, c->hm, c->facc[ch], ch, s.nfreq, ser_apbx(c), ser_apby(c), s.sample + s.off[1 + ch],
-                                         s.bad + (size_t)nparts * c->nb, s.S))
-                    return fail(DQMC_EINVAL, who + ": the lattice is too large for the Matsubara kernel's LDS");
-                ++nparts;
-            }
-        c->fam_launches[FAM_OTHER] += (uint64_t)nparts;
-        if (s.parts & DQMC_SERIES_PHI) {                    // after the other parts; no flag row: the field always exists
-            if (!launch_series_phi_sample(c->lc, c->hm, s.trig, s.trig + 2 * (size_t)c->hm.L, s.nfreq, s.sample, s.S, s.off[6]))
-                return fail(DQMC_EINVAL, who + ": the lattice is too large for the order-parameter sample kernel's LDS");
-            ++c->fam_launches[FAM_OTHER];
-        }
-    }
-    { const int rc = finish(c, entry); if (rc != DQMC_OK) return rc; }
-    std::vector<double> bad((size_t)nparts * c->nb);
-    if (nparts) HIPCHK(copy_sync(c, bad.data(), s.bad, bad.size() * sizeof(double), hipMemcpyDeviceToHost));
-    else HIPCHK(hipStreamSynchronize(c->st));               // the order-parameter part alone: no flags, the call still synchronises
-    for (double b : bad)
-        if (b != 0.0) return fail(DQMC_EINVAL, who + ": a block of the series has no sample (equal-time count or an every-slice row count < 1)");
-    s.formed = true;
-    return DQMC_OK;
-}
-// true if [p, p + bytes) is device memory of `device`; a host address, an address the runtime does not know and a range that leaves its
-// allocation are all false, and no error stays pending
-static bool series_device_range(const void* p, size_t bytes, int device) {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    if (attr.type != hipMemoryTypeDevice || attr.device != device) return false;
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    const uintptr_t lo = (uintptr_t)base, at = (uintptr_t)p;
-    return at >= lo && bytes <= size && at - lo <= size - bytes;
-}
-// closed[k] = (closed[2k] + closed[2k+1]) * 0.5 for all slots; the caller has checked an even number of closed bins and the bin size
-constexpr int SERIES_MAX_BIN_SIZE = 1 << 29;                // the largest bin_size that can still double: the result stays within 2^30
-static int series_rebin(dqmc_ctx* c, const char* entry) {
-    dqmc_ctx::Series& s = c->ser;
-    if (s.closed > 0) {
-        { ProfScope ps(c, FAM_OTHER, 1); launch_series_rebin(c->lc, s.bins, (size_t)c->nb * s.S, s.closed / 2); }
-        { const int rc = finish(c, entry); if (rc != DQMC_OK) return rc; }
-        HIPCHK(hipStreamSynchronize(c->st));
-    }
-    s.closed /= 2; s.bin_size *= 2; ++s.rebins;
-    return DQMC_OK;
-}
-// The second half: open[s] += src[s][0 .. S) for every slot s of this context, src == nullptr: the context's own rows in order
-static int series_accumulate(dqmc_ctx* c, const double* const* src, const char* entry) {
-    dqmc_ctx::Series& s = c->ser;
-    const std::string who(entry);
-    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
-    if (!s.formed) return fail(DQMC_EINVAL, who + ": the context's sample is not formed (dqmc_series_form_sample)");
-    if (s.closed >= s.max_bins) return fail(DQMC_EINVAL, who + ": the series is full (max_bins bins are closed)");
-    (void)hipSetDevice(c->p.device);
-    const size_t n = (size_t)c->nb * s.S;
-    const int close = s.in_open + 1 == s.bin_size;
-    if (!src) {
-        ProfScope ps(c, FAM_OTHER, 1);
-        launch_series_accum(c->lc, s.sample, s.openbin, s.bins + (size_t)s.closed * n, n, close, s.bin_size);
-    } else {
-        for (int b = 0; b < c->nb; ++b) {
-            if (!src[b]) return fail(DQMC_EINVAL, who + ": a source row is null");
-            if (((uintptr_t)src[b] & (sizeof(double) - 1)) || !series_device_range(src[b], s.S * sizeof(double), c->p.device))
-                return fail(DQMC_EINVAL, who + ": a source row is not S doubles of device memory on the context's device");
-        }
-        s.srchost.assign(src, src + c->nb);                 // stays alive until the stream has taken the copy
-        HIPCHK(hipMemcpyAsync((void*)s.srctab, s.srchost.data(), (size_t)c->nb * sizeof(const double*), hipMemcpyHostToDevice, c->st));
-        ProfScope ps(c, FAM_OTHER, 1);
-        launch_series_accum_routed(c->lc, s.srctab, s.openbin, s.bins + (size_t)s.closed * n, s.S, close, s.bin_size);
-    }
-    if (s.flags & DQMC_SERIES_TRACK_VARIANCE) {             // the same rows once more, into the running mean and m2 of the slot
-        ProfScope ps(c, FAM_OTHER, 1);
-        launch_series_welford(c->lc, s.sample, src ? s.srctab : nullptr, s.var, s.var + n, s.S, s.samples + 1);
-    }
-    s.formed = false;
-    { const int rc = finish(c, entry); if (rc != DQMC_OK) return rc; }
-    HIPCHK(hipStreamSynchronize(c->st));                    // the rows may belong to another context: they are free again on return
-    ++s.samples;
-    if (close) { ++s.closed; s.in_open = 0; } else ++s.in_open;
-    // auto re-binning: the close that fills the series merges neighbouring bins before the call returns, so the series is never
-    // observed full; if bin_size cannot double any more the series becomes full as it does without the flag
-    if (close && (s.flags & DQMC_SERIES_AUTO_REBIN) && s.closed == s.max_bins && s.bin_size <= SERIES_MAX_BIN_SIZE) return series_rebin(c, entry);
-    return DQMC_OK;
-}
-extern "C" int dqmc_series_form_sample(dqmc_ctx* c) {
-    if (!c) return fail(DQMC_EINVAL, "null ctx");
-    return series_form_sample(c, "dqmc_series_form_sample");
-}
-extern "C" int dqmc_series_sample_device(dqmc_ctx* c, const double** rows, size_t* S) {
-    if (!c || !rows || !S) return fail(DQMC_EINVAL, "null argument");
-    if (!c->ser.open) return fail(DQMC_EINVAL, "no measurement series is open");
-    *rows = c->ser.sample; *S = c->ser.S;
-    return DQMC_OK;
-}
-extern "C" int dqmc_series_accumulate(dqmc_ctx* c, const double* const* src) {
-    if (!c) return fail(DQMC_EINVAL, "null ctx");
-    return series_accumulate(c, src, "dqmc_series_accumulate");
-}
-extern "C" int dqmc_series_add_sweep(dqmc_ctx* c) {
-    if (!c) return fail(DQMC_EINVAL, "null ctx");
-    const int rc = series_form_sample(c, "dqmc_series_add_sweep");
-    return rc != DQMC_OK ? rc : series_accumulate(c, nullptr, "dqmc_series_add_sweep");
-}
-extern "C" int dqmc_series_read_bins_host(dqmc_ctx* c, int first, int count, double* out) {
-    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
-    const dqmc_ctx::Series& s = c->ser;
-    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
-    if (first < 0 || count < 1 || first > s.closed || count > s.closed - first) return fail(DQMC_EINVAL, "dqmc_series_read_bins_host: bins outside the closed range");
-    (void)hipSetDevice(c->p.device);
-    const size_t n = (size_t)c->nb * s.S;
-    HIPCHK(hipMemcpy2DAsync(out, s.S * sizeof(double), s.bins + (size_t)first * n + (size_t)c->sel * s.S, n * sizeof(double),
-                            s.S * sizeof(double), (size_t)count, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-    return DQMC_OK;
-}
-extern "C" int dqmc_series_stats_host(dqmc_ctx* c, double* mean, double* err) {
-    if (!c || !mean || !err) return fail(DQMC_EINVAL, "null argument");
-    const dqmc_ctx::Series& s = c->ser;
-    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
-    if (s.closed < 2) return fail(DQMC_EINVAL, "dqmc_series_stats_host: the jackknife needs at least two closed bins");
-    (void)hipSetDevice(c->p.device);
-    const size_t n = (size_t)c->nb * s.S;
-    { ProfScope ps(c, FAM_OTHER, 1); launch_series_stats(c->lc, s.bins, n, s.closed, s.stat, s.stat + n); }
-    { const int rc = finish(c, "dqmc_series_stats_host"); if (rc != DQMC_OK) return rc; }
-    HIPCHK(copy_sync(c, mean, s.stat, n * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(copy_sync(c, err, s.stat + n, n * sizeof(double), hipMemcpyDeviceToHost));
-    return DQMC_OK;
-}
-extern "C" int dqmc_series_derived_host(dqmc_ctx* c, double* value, double* err) {
-    if (!c || !value || !err) return fail(DQMC_EINVAL, "null argument");
-    const dqmc_ctx::Series& s = c->ser;
-    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
-    if (s.closed < 2) return fail(DQMC_EINVAL, "dqmc_series_derived_host: the jackknife needs at least two closed bins");
-    (void)hipSetDevice(c->p.device);
-    const size_t n = (size_t)c->nb * s.S, nd = (size_t)6 * c->nb;
-    double* dv = s.stat + 2 * n;
-    {
-        ProfScope ps(c, FAM_OTHER, 1);
-        launch_series_derived(c->lc, c->hm, s.bins, s.S, s.closed, s.nfreq, (s.parts & 1) ? (long long)s.off[0] : -1,
-                              (s.parts & 16) ? (long long)s.off[4] : -1, dv, dv + nd);
-    }
-    { const int rc = finish(c, "dqmc_series_derived_host"); if (rc != DQMC_OK) return rc; }
-    HIPCHK(copy_sync(c, value, dv, nd * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(copy_sync(c, err, dv + nd, nd * sizeof(double), hipMemcpyDeviceToHost));
-    return DQMC_OK;
-}
-extern "C" int dqmc_series_phi_derived_host(dqmc_ctx* c, double* value, double* err) {
-    if (!c || !value || !err) return fail(DQMC_EINVAL, "null argument");
-    const dqmc_ctx::Series& s = c->ser;
-    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
-    if (!(s.parts & DQMC_SERIES_PHI)) return fail(DQMC_EINVAL, "dqmc_series_phi_derived_host: the series has no order-parameter part");
-    if (s.closed < 2) return fail(DQMC_EINVAL, "dqmc_series_phi_derived_host: the jackknife needs at least two closed bins");
-    (void)hipSetDevice(c->p.device);
-    const size_t n = (size_t)c->nb * s.S, nd = (size_t)6 * c->nb;
-    double* dv = s.stat + 2 * n;                            // the result rows of dqmc_series_derived_host: the calls are synchronous
-    { ProfScope ps(c, FAM_OTHER, 1); launch_series_phi_derived(c->lc, c->hm, s.bins, s.S, s.closed, s.nfreq, s.off[6], dv, dv + nd); }
-    { const int rc = finish(c, "dqmc_series_phi_derived_host"); if (rc != DQMC_OK) return rc; }
-    HIPCHK(copy_sync(c, value, dv, nd * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(copy_sync(c, err, dv + nd, nd * sizeof(double), hipMemcpyDeviceToHost));
-    return DQMC_OK;
-}
-
-// ---- long runs: options, re-binning, binning analysis, export / import (dqmc_hip.h) ----
-static bool series_flags_valid(int flags, int max_bins) {
-    if (flags & ~(DQMC_SERIES_AUTO_REBIN | DQMC_SERIES_TRACK_VARIANCE)) return false;
-    return !(flags & DQMC_SERIES_AUTO_REBIN) || (max_bins >= 4 && max_bins % 2 == 0);
-}
-// w and m2 [nb][S], zeroed; kept until the series ends once they exist
-static hipError_t series_alloc_variance(dqmc_ctx* c) {
-    dqmc_ctx::Series& s = c->ser;
-    const size_t bytes = 2 * (size_t)c->nb * s.S * sizeof(double);
-    if (!s.var) {
-        const hipError_t e = hipMalloc((void**)&s.var, bytes);
-        if (e != hipSuccess) { s.var = nullptr; return e; }
-    }
-    return hipMemsetAsync(s.var, 0, bytes, c->st);
-}
-extern "C" int dqmc_series_configure(dqmc_ctx* c, int flags) {
-    if (!c) return fail(DQMC_EINVAL, "null ctx");
-    dqmc_ctx::Series& s = c->ser;
-    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
-    if (s.samples || s.closed || s.in_open) return fail(DQMC_EINVAL, "dqmc_series_configure: the series is not empty any more");
-    if (!series_flags_valid(flags, s.max_bins))
-        return fail(DQMC_EINVAL, "dqmc_series_configure: unknown flag, or DQMC_SERIES_AUTO_REBIN with max_bins odd or below 4");
-    (void)hipSetDevice(c->p.device);
-    if (flags & DQMC_SERIES_TRACK_VARIANCE) {
-        HIPCHK(series_alloc_variance(c));
-        HIPCHK(hipStreamSynchronize(c->st));
-    }
-    s.flags = flags;
-    return DQMC_OK;
-}
-static void series_fill_state(const dqmc_ctx* c, dqmc_series_state* st) {
-    const dqmc_ctx::Series& s = c->ser;
-    std::memset(st, 0, sizeof(*st));
-    st->bin_size = s.bin_size; st->max_bins = s.max_bins; st->nfreq = s.nfreq; st->parts = s.parts; st->flags = s.flags;
-    st->bins_closed = s.closed; st->sweeps_in_open_bin = s.in_open; st->nb = c->nb;
-    st->samples = s.samples; st->rebins = s.rebins; st->sample_len = s.S;
-}
-extern "C" int dqmc_series_get_state(dqmc_ctx* c, dqmc_series_state* st) {
-    if (!c || !st) return fail(DQMC_EINVAL, "null argument");
-    if (!c->ser.open) return fail(DQMC_EINVAL, "no measurement series is open");
-    series_fill_state(c, st);
-    return DQMC_OK;
-}
-extern "C" int dqmc_series_rebin(dqmc_ctx* c) {
-    if (!c) return fail(DQMC_EINVAL, "null ctx");
-    dqmc_ctx::Series& s = c->ser;
-    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
-    if (s.closed % 2) return fail(DQMC_EINVAL, "dqmc_series_rebin: the number of closed bins is odd");
-    if (s.bin_size > SERIES_MAX_BIN_SIZE) return fail(DQMC_EINVAL, "dqmc_series_rebin: bin_size cannot double any more");
-    (void)hipSetDevice(c->p.device);
-    return series_rebin(c, "dqmc_series_rebin");
-}
-extern "C" int dqmc_series_binning_host(dqmc_ctx* c, int levels, double* err, double* tau) {
-    if (!c || !err) return fail(DQMC_EINVAL, "null argument");
-    dqmc_ctx::Series& s = c->ser;
-    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
-    if (levels < 1 || levels > 12) return fail(DQMC_EINVAL, "dqmc_series_binning_host: levels must be in 1..12");
-    if ((s.closed >> (levels - 1)) < 2) return fail(DQMC_EINVAL, "dqmc_series_binning_host: the top level needs at least two merged bins");
-    if (tau && !(s.flags & DQMC_SERIES_TRACK_VARIANCE)) return fail(DQMC_EINVAL, "dqmc_series_binning_host: tau needs DQMC_SERIES_TRACK_VARIANCE");
-    if (tau && s.samples < 2) return fail(DQMC_EINVAL, "dqmc_series_binning_host: tau needs at least two samples");
-    (void)hipSetDevice(c->p.device);
-    const size_t n = (size_t)c->nb * s.S, need = 2 * (size_t)levels * n;
-    if (need > s.binning_cap) {
-        HIPCHK(hipStreamSynchronize(c->st));
-        if (s.binning) { (void)hipFree(s.binning); s.binning = nullptr; s.binning_cap = 0; }
-        HIPCHK(hipMalloc((void**)&s.binning, need * sizeof(double)));
-        s.binning_cap = need;
-    }
-    double* derr = s.binning;
-    double* dtau = tau ? s.binning + (size_t)levels * n : nullptr;
-    {
-        ProfScope ps(c, FAM_OTHER, 1);
-        launch_series_binning(c->lc, s.bins, tau ? s.var + n : nullptr, n, s.closed, levels, s.bin_size, s.samples, derr, dtau);
-    }
-    { const int rc = finish(c, "dqmc_series_binning_host"); if (rc != DQMC_OK) return rc; }
-    HIPCHK(copy_sync(c, err, derr, (size_t)levels * n * sizeof(double), hipMemcpyDeviceToHost));
-    if (tau) HIPCHK(copy_sync(c, tau, dtau, (size_t)levels * n * sizeof(double), hipMemcpyDeviceToHost));
-    return DQMC_OK;
-}
-static size_t series_export_len(size_t n, int closed, int flags) {
-    return ((size_t)closed + 1 + ((flags & DQMC_SERIES_TRACK_VARIANCE) ? 2 : 0)) * n;
-}
-extern "C" int dqmc_series_export_host(dqmc_ctx* c, double* out, size_t len) {
-    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
-    const dqmc_ctx::Series& s = c->ser;
-    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
-    const size_t n = (size_t)c->nb * s.S;
-    if (len != series_export_len(n, s.closed, s.flags)) return fail(DQMC_EINVAL, "dqmc_series_export_host: len is not the size of the series");
-    (void)hipSetDevice(c->p.device);
-    HIPCHK(hipStreamSynchronize(c->st));
-    const size_t nc = (size_t)s.closed * n;
-    if (nc) HIPCHK(copy_sync(c, out, s.bins, nc * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(copy_sync(c, out + nc, s.openbin, n * sizeof(double), hipMemcpyDeviceToHost));
-    if (s.flags & DQMC_SERIES_TRACK_VARIANCE) HIPCHK(copy_sync(c, out + nc + n, s.var, 2 * n * sizeof(double), hipMemcpyDeviceToHost));
-    return DQMC_OK;
-}
-extern "C" int dqmc_series_import_host(dqmc_ctx* c, const dqmc_series_state* st, const double* in, size_t len) {
-    if (!c || !st || !in) return fail(DQMC_EINVAL, "null argument");
-    dqmc_ctx::Series& s = c->ser;
-    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
-    if (st->nb != c->nb || st->sample_len != s.S || st->parts != s.parts || st->nfreq != s.nfreq)
-        return fail(DQMC_EINVAL, "dqmc_series_import_host: chains, sample length, parts or nfreq differ from the open series");
-    if (st->bins_closed < 0 || st->bins_closed >= s.max_bins) return fail(DQMC_EINVAL, "dqmc_series_import_host: bins_closed must be below max_bins of the open series");
-    if (st->bin_size < 1 || st->sweeps_in_open_bin < 0 || st->sweeps_in_open_bin >= st->bin_size)
-        return fail(DQMC_EINVAL, "dqmc_series_import_host: sweeps_in_open_bin must be below bin_size");
-    if (!series_flags_valid(st->flags, s.max_bins)) return fail(DQMC_EINVAL, "dqmc_series_import_host: the flags are not valid for max_bins of the open series");
-    if (st->samples < 0 || st->rebins < 0) return fail(DQMC_EINVAL, "dqmc_series_import_host: negative counter");
-    const size_t n = (size_t)c->nb * s.S;
-    if (len != series_export_len(n, st->bins_closed, st->flags)) return fail(DQMC_EINVAL, "dqmc_series_import_host: len is not the size of the series");
-    (void)hipSetDevice(c->p.device);
-    HIPCHK(hipStreamSynchronize(c->st));
-    if ((st->flags & DQMC_SERIES_TRACK_VARIANCE) && !s.var) HIPCHK(series_alloc_variance(c));   // nothing of the series has changed yet
-    const size_t nc = (size_t)st->bins_closed * n;
-    if (nc) HIPCHK(copy_sync(c, s.bins, in, nc * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(copy_sync(c, s.openbin, in + nc, n * sizeof(double), hipMemcpyHostToDevice));
-    if (st->flags & DQMC_SERIES_TRACK_VARIANCE) HIPCHK(copy_sync(c, s.var, in + nc + n, 2 * n * sizeof(double), hipMemcpyHostToDevice));
-    s.bin_size = st->bin_size; s.flags = st->flags; s.closed = st->bins_closed; s.in_open = st->sweeps_in_open_bin;
-    s.samples = st->samples; s.rebins = st->rebins; s.formed = false;
-    return DQMC_OK;
-}
-
-extern "C" int dqmc_get_green_td_fine_host(dqmc_ctx* c, dqmc_cplx* g_t0, dqmc_cplx* g_0t, dqmc_cplx* g_tt, int* slice) {
-    if (!c || !g_t0 || !g_0t || !g_tt || !slice) return fail(DQMC_EINVAL, "null argument");
-    if (!c->td_fine || c->fine_slice < 0) return fail(DQMC_EINVAL, "no every-slice Green's function has been propagated");
-    (void)hipSetDevice(c->p.device);
-    HIPCHK(hipStreamSynchronize(c->st));
-    HIPCHK(hipGetLastError());
-    const size_t bytes = (size_t)c->n_g * c->n_g * sizeof(cplx);
-    HIPCHK(copy_sync(c, g_t0, selp(c, c->fGT0), bytes, hipMemcpyDeviceToHost));
-    HIPCHK(copy_sync(c, g_0t, selp(c, c->fG0T), bytes, hipMemcpyDeviceToHost));
-    HIPCHK(copy_sync(c, g_tt, selp(c, c->fGTT), bytes, hipMemcpyDeviceToHost));
-    *slice = c->fine_slice;
-    return DQMC_OK;
-}
-
 extern "C" int dqmc_exchange_action_host(dqmc_ctx* c, double* out) {
     if (!c || !out) return fail(DQMC_EINVAL, "null argument");
     (void)hipSetDevice(c->p.device);
@@ -2564,7 +1547,7 @@ static void sub_prof_end(void* u, int sub, double flops, double bytes) {
     (void)hipEventRecord(c->ev_pool[c->sub_open.back().second + 1], c->st);
     c->sub_launches[sub] += 1; c->sub_flops[sub] += flops; c->sub_bytes[sub] += bytes;
 }
-static void prof_collect(dqmc_ctx* c) {
+void prof_collect(dqmc_ctx* c) {
     (void)hipStreamSynchronize(c->st);
     if (c->st2) (void)hipStreamSynchronize(c->st2);
     for (auto& o : c->ev_open) {

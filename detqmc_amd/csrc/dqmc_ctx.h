@@ -1,0 +1,249 @@
+// Private to the two units of the C-ABI implementation (dqmc_context.hip: context, sweep building blocks; dqmc_measure_api.hip: measurement and
+// series entry points): the context itself and the helpers every entry point is written with.
+#pragma once
+#include "dqmc_internal.h"
+#include <cstdint>
+#include <cstdlib>
+#include <string>
+#include <utility>
+#include <vector>
+
+#define DQMC_PRIVATE __attribute__((visibility("hidden")))     // shared by the two units, not part of the library's interface
+
+extern DQMC_PRIVATE thread_local std::string g_err;     // the one definition: dqmc_context.hip
+static int fail(int code, const std::string& msg) { g_err = msg; return code; }
+#define HIPCHK(x)                                                                                       \
+    do {                                                                                                \
+        hipError_t e_ = (x);                                                                            \
+        if (e_ != hipSuccess)                                                                           \
+            return fail(DQMC_EHIP, std::string(#x) + ": " + hipGetErrorString(e_) + " (" + __FILE__ + ":" + \
+                                       std::to_string(__LINE__) + ")");                                  \
+    } while (0)
+
+// DQMC_SYNC_CHECK=1 (debug mode): every entry point that only enqueues work waits for its stream before it returns and
+// every kernel family scope waits when it closes, so an asynchronous GPU fault is reported by the call -- and the kernel
+// family -- that caused it.  Without it the enqueue-only entry points see a fault whenever the runtime notices it, i.e.
+// possibly one or more calls later (the message says so).  Results are identical either way.
+static bool sync_check_on() {
+    static const bool on = getenv("DQMC_SYNC_CHECK") && atoi(getenv("DQMC_SYNC_CHECK")) != 0;
+    return on;
+}
+
+struct UdVSlot { cplx* U; double* d; cplx* Vt; };
+
+enum { FAM_BMULT = DQMC_FAM_BMULT, FAM_GEMM = DQMC_FAM_GEMM, FAM_JACOBI = DQMC_FAM_DECOMP, FAM_UPDATE = DQMC_FAM_DECIDE,
+       FAM_OTHER = DQMC_FAM_OTHER, FAM_GATHER = DQMC_FAM_GATHER, FAM_FLUSH = DQMC_FAM_FLUSH, FAM_ROUNDS = 7, FAM_COUNT = DQMC_FAM_COUNT };
+
+// The measurement accumulator blocks of a context, one table (dqmc_ctx::acc): the per-slice observables, the four coarse time-displaced
+// channels, the four every-slice ones (channel ch at ACC_FINE0 + ch, as ACC_TD + ch for the coarse ones) and the equal-time correlators
+enum { ACC_SLICE, ACC_TD, ACC_TD_PAIR, ACC_TD_PH, ACC_TD_CUR, ACC_FINE0, ACC_EQ = ACC_FINE0 + 4, ACC_COUNT };
+// n: doubles per chain, 0 while the context has no such block; chain b starts at (char*)p + b * stride (the arena's chain stride; the
+// equal-time block lives outside the arena as [chain][n]); missing: what a read of an absent block reports
+struct AccBlock { double* p; size_t n, stride; const char* missing; };
+
+struct dqmc_ctx {
+    dqmc_params p;
+    DevModel hm;
+    hipStream_t st = nullptr;
+    // pipelined local updates (dqmc_update_slice): the flush of block b runs on st2 while the decisions of block b + 1 run on st
+    hipStream_t st2 = nullptr;
+    hipEvent_t ev_win = nullptr, ev_flush = nullptr;
+    cplx* Gwin = nullptr;          // (MSF pbudget)^2: the next block's proposal window of G (k_update_window)
+    int pipe_P = 0;                // pbudget when the pipelined schedule is in effect, else 0
+    bool pipelined = false;        // latched at dqmc_create (dqmc_tuning::pipeline, n_g, chains): nothing else decides the schedule
+    uint64_t blocks_pipelined = 0, blocks_sequential = 0, cholqr_fallbacks = 0;
+    bool qr_bgs = false, green_lu = false;       // latched at dqmc_create (dqmc_tuning::qr_variant / green_variant)
+    std::vector<int> err_host;     // scratch of chol_failed()
+    // batched chains: nb chains in lockstep; per-chain buffers of chain b = chain 0's + b * cs (one arena)
+    Launch lc{nullptr, 1, 0};
+    int nb = 1, sel = 0;                // sel: chain the host-buffer entry points talk to (dqmc_select_chain)
+    char* arena = nullptr;
+    size_t arena_off = 0;
+    std::vector<void**> fixups;
+    int n_g = 0, MSF = 0, N = 0, m = 0, s = 0, n = 0, D = 0;
+    std::vector<void*> allocs;
+    // fields + backups
+    double *phi = nullptr, *coshT = nullptr, *sinhT = nullptr;
+    double *cdwl = nullptr, *cdwC = nullptr, *cdwS = nullptr;      // cdwU != 0 only
+    double *phi_bak = nullptr, *cosh_bak = nullptr, *sinh_bak = nullptr;
+    // Green's function, singular values of G^-1
+    cplx *G = nullptr, *G_bak = nullptr;
+    double *sv = nullptr, *sv_bak = nullptr;
+    std::vector<UdVSlot> storage, storage_bak;
+    UdVSlot spare{}, tmpudv{};
+    cplx *T1 = nullptr, *T2 = nullptr, *T3 = nullptr, *T4 = nullptr;
+    cplx *propK[2] = {nullptr, nullptr}, *Tdense = nullptr;   // CB_NONE only: blockdiag e^{-+dtau K} (n_g x n_g), GEMM target
+    cplx *propKh[2] = {nullptr, nullptr};                    // CB_NONE only: e^{-+dtau K / 2} (propK_half, propK_half_inv)
+    AccBlock acc[ACC_COUNT] = {
+        {nullptr, 0, 0, "the context has no measurement accumulators"},                       // every context has them
+        {nullptr, 0, 0, "context created without dqmc_params::timedisplaced"},
+        {nullptr, 0, 0, "context created without dqmc_params::timedisplaced == 2"},
+        {nullptr, 0, 0, "context created without dqmc_params::td_particle_hole"},
+        {nullptr, 0, 0, "context created without dqmc_params::td_particle_hole = 2"},
+        {nullptr, 0, 0, "no every-slice block for this channel"}, {nullptr, 0, 0, "no every-slice block for this channel"},
+        {nullptr, 0, 0, "no every-slice block for this channel"}, {nullptr, 0, 0, "no every-slice block for this channel"},
+        {nullptr, 0, 0, "the equal-time correlators have never been enabled (dqmc_set_equal_time_correlators)"}};
+    // time-displaced Green's functions (dqmc_params::timedisplaced reserves them; dqmc_set_timedisplaced switches them on)
+    bool td_reserved = false, td_on = false;
+    int td_slice = -1;                                        // tau slice of the last pair GT0 / G0T (all chains), -1: none yet
+    cplx *GT0 = nullptr, *G0T = nullptr, *td_W = nullptr;     // G(tau,0), G(0,tau), scratch of the extra solves
+    double* td_sv = nullptr;                                  // SVD mode: log-det output of the LU / QR route (c->sv keeps the Jacobi values)
+    // dqmc_params::td_particle_hole: G(0) of the boundary's own field configuration, (shifted G(0,tau))^H, one-body values
+    cplx *G00 = nullptr, *ph_H = nullptr, *ph_ob = nullptr;
+    // td_particle_hole == 2: bond amplitudes (shared by the chains) and one-body values of the current-current correlators
+    cplx *cur_bt = nullptr, *cur_ob = nullptr;
+    // DQMC_TD_EVERY_SLICE: work copies of G(tau_k,0), G(0,tau_k), G(tau_k) that the segment / ends entries propagate (the sweep's own G,
+    // GT0, G0T, G00 are only read) and the slice they stand on; one fine accumulator block (m + 1 rows) per enabled channel: 0 G(k, tau)
+    // bins, 1 pairing, 2 particle-hole, 3 current
+    bool td_fine = false;
+    int fine_slice = -1;
+    cplx *fGT0 = nullptr, *fG0T = nullptr, *fGTT = nullptr;
+    double* mats_out = nullptr;                               // dqmc_measure_td_matsubara_host: results + one flag per chain, outside the arena,
+    size_t mats_cap = 0;                                      // allocated on first use and grown on demand (doubles)
+    // dqmc_set_equal_time_correlators: block [chain][1 + 5 N] and one-body scratch [chain][5 N], outside the arena, allocated by the first enable
+    bool eq_on = false;
+    cplx* eq_ob = nullptr;
+    // dqmc_series_*: the measurement series.  Device buffers outside the arena, allocated by dqmc_series_begin and freed by dqmc_series_end
+    // or with the context: sample [nb][S], open bin [nb][S], closed bins [max_bins][nb][S], the per-part flags [5][nb], the cos / sin table
+    // (2 pi j / L [2 L]; with the order-parameter part, index 6 of off / len, also 2 pi j / m [2 m] behind it) and the result buffer
+    // of the statistics calls (mean, err [nb][S] each, then value, err [nb][6] each).  The counters live on the host.
+    // srctab [nb]: the source rows of dqmc_series_accumulate, filled from srchost before every launch; formed: the sample buffer holds
+    // the sample of a successful dqmc_series_form_sample that no dqmc_series_accumulate has consumed yet.
+    struct Series {
+        bool open = false, formed = false;
+        int bin_size = 0, max_bins = 0, nfreq = 0, parts = 0, closed = 0, in_open = 0;
+        int flags = 0;                                        // DQMC_SERIES_AUTO_REBIN | DQMC_SERIES_TRACK_VARIANCE (dqmc_series_configure)
+        long long samples = 0, rebins = 0;                    // accumulates since begin / merges of neighbouring bins so far
+        size_t S = 0, off[7] = {0, 0, 0, 0, 0, 0, 0}, len[7] = {0, 0, 0, 0, 0, 0, 0};   // index = bit number; 5 is never used
+        double *sample = nullptr, *openbin = nullptr, *bins = nullptr, *bad = nullptr, *trig = nullptr, *stat = nullptr;
+        double *var = nullptr;                                // running mean w [nb][S], then m2 [nb][S]: allocated with TRACK_VARIANCE
+        double *binning = nullptr;                            // result of dqmc_series_binning_host, err then tau [levels][nb][S] each,
+        size_t binning_cap = 0;                               // allocated on first use and grown on demand (doubles)
+        const double** srctab = nullptr;
+        std::vector<const double*> srchost;
+    } ser;
+    SvdWork sw{};
+    double hub_e_m2a = 1.0, hub_e_p2a = 1.0;  // Hubbard: exp(-+2 alpha) of weightRatioSingleFlip (dethubbard.cpp:866-867)
+    int stab = 0;                       // DQMC_STAB_SVD / DQMC_STAB_QR
+    QrWork qw{};
+    int* qr_perm = nullptr;
+    int* lu_swaps = nullptr;
+    cplx* lu_tneg = nullptr;       // -U12^T of the current LU panel (n_g x 32), operand of the trailing update on k_flush
+    uint64_t lu_calls = 0;         // gather lists of the LU panels (kernels_lu.hip)
+    int* qr_perm_inv = nullptr;      // inverse of qr_perm and 1/d of the last lazy UDT (triangular chaining product)
+    double* qr_dinv = nullptr;
+    double *rmax_inv = nullptr, *rmin = nullptr, *lmax_inv = nullptr, *lmin = nullptr;
+    UdVSlot eye{};
+    uint64_t qr_calls = 0;
+    int max_jacobi_sweeps = 80;
+    int last_svd_sweeps = 0;
+    double last_svd_residual = 0.0;
+    hipGraphExec_t jacobi_graph = nullptr;
+    unsigned long long jacobi_host_seq = 0;
+    uint64_t svd_calls = 0, svd_sweeps_total = 0;
+    int svd_sweeps_max = 0;
+    // updates
+    cplx *X = nullptr, *Gr = nullptr, *W = nullptr;
+    double* uniforms = nullptr;
+    size_t uni_cap = 0;
+    DevUpdateState* us = nullptr;
+    double* scalar_out = nullptr;
+    double* shift_buf = nullptr;        // [nchains][opdim] displacements of a global shift move (shared buffer)
+    int currentTimeslice = 0;
+    bool g_stale = false;          // dqmc_wrap_skip moved currentTimeslice without computing G: nothing may read G until it is rebuilt
+    // profiling
+    bool prof = false;
+    int prof_depth = 0;                 // open ProfScopes (they nest)
+    std::vector<hipEvent_t> ev_pool;
+    std::vector<std::pair<int, int>> ev_open;   // (family, index of begin event); end = index+1
+    size_t ev_used = 0;
+    double fam_ms[FAM_COUNT] = {0};
+    uint64_t fam_launches[FAM_COUNT] = {0};
+    double gemm_flops = 0.0;
+    SubProf subprof{};                  // hooks handed to the launchers through Launch::sub while profiling is on
+    SvdProfHooks qr_apply_hooks{};      // and through QrWork::apply_hooks (timing of the k_qr_apply launches)
+    std::vector<std::pair<int, int>> sub_open;      // (sub-family, begin event)
+    double sub_ms[SUBFAM_COUNT] = {0}, sub_flops[SUBFAM_COUNT] = {0}, sub_bytes[SUBFAM_COUNT] = {0};
+    uint64_t sub_launches[SUBFAM_COUNT] = {0};
+    std::string fault;                  // DQMC_SYNC_CHECK: first kernel family whose work came back with an error
+};
+static const char* const kFamName[FAM_COUNT] = {"k_bmult_chain / site-local V", "k_zgemm (n_g^3 products)", "decomposition (QR / LU / Jacobi, triangular solves)",
+                                                "k_update_decide / k_hubbard_slice", "small kernels (copies, scales, set-up)", "k_update_gather", "k_flush", "rounds"};
+// end of an entry point that only enqueued work
+static int finish(dqmc_ctx* c, const char* entry) {
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && sync_check_on()) e = hipStreamSynchronize(c->st);
+    if (e == hipSuccess && sync_check_on() && c->pipelined) {      // the flushes of a pipelined update run on the second stream
+        e = hipStreamSynchronize(c->st2);
+        if (e != hipSuccess && c->fault.empty()) c->fault = std::string("k_flush (second stream) (") + hipGetErrorString(e) + ")";
+    }
+    if (e == hipSuccess && c->fault.empty()) return DQMC_OK;
+    std::string msg = std::string(entry) + ": " + (e != hipSuccess ? hipGetErrorString(e) : "GPU fault");
+    if (!c->fault.empty()) msg += " in " + c->fault;
+    msg += sync_check_on() ? " [DQMC_SYNC_CHECK: raised by work this call enqueued]"
+                           : " [asynchronous: may stem from an earlier call; rerun with DQMC_SYNC_CHECK=1 to name the call and kernel family]";
+    return fail(DQMC_EHIP, msg);
+}
+
+// shared (chain independent) device memory
+template<class T>
+static int salloc(dqmc_ctx* c, T** p, size_t count) {
+    void* q = nullptr;
+    HIPCHK(hipMalloc(&q, count * sizeof(T)));
+    c->allocs.push_back(q);
+    *p = (T*)q;
+    return 0;
+}
+// the selected chain's copy of a per-chain buffer (host-buffer entry points)
+template<class T> static T* selp(dqmc_ctx* c, T* p) { return (T*)((char*)p + (size_t)c->sel * c->lc.cs); }
+template<class T> static T* chainp(dqmc_ctx* c, T* p, int b) { return (T*)((char*)p + (size_t)b * c->lc.cs); }
+// Blocking copy on the context's OWN (non-blocking) stream.  Nothing in this library touches the legacy null stream: a
+// null-stream copy would wait for -- and hold up -- every blocking stream of the process, i.e. serialise contexts that
+// different host threads drive concurrently (one context per sub-batch of replicas, host/detsdw.cpp).
+static hipError_t copy_sync(dqmc_ctx* c, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, c->st);
+    return e != hipSuccess ? e : hipStreamSynchronize(c->st);
+}
+
+DQMC_PRIVATE void prof_collect(dqmc_ctx* c);                 // dqmc_context.hip
+enum { PROF_EVENT_CAP = 8192 };     // events alive at most: beyond that the finished pairs are collected and reused
+// A fresh (begin, end) pair of timing events: records the begin event on st and returns its index; the end event is index + 1
+static int prof_event_pair(dqmc_ctx* c, hipStream_t st) {
+    if (c->ev_used + 2 > c->ev_pool.size())
+        for (int i = 0; i < 2; ++i) { hipEvent_t e; (void)hipEventCreate(&e); c->ev_pool.push_back(e); }
+    const int idx = (int)c->ev_used;
+    (void)hipEventRecord(c->ev_pool[idx], st);
+    c->ev_used += 2;
+    return idx;
+}
+
+struct ProfScope {
+    dqmc_ctx* c; int fam; uint64_t launches; int idx = -1;     // idx: this scope's begin event (scopes may nest)
+    hipStream_t st;                                            // the stream the scope's kernels are launched on (c->st, or c->st2 for a pipelined flush)
+    ProfScope(dqmc_ctx* c_, int fam_, uint64_t launches_, hipStream_t st_ = nullptr) : c(c_), fam(fam_), launches(launches_), st(st_ ? st_ : c_->st) {
+        c->fam_launches[fam] += launches;
+        if (!c->prof) return;
+        if (c->ev_used + 2 > PROF_EVENT_CAP && c->prof_depth == 0) prof_collect(c);   // not while an outer scope is open
+        ++c->prof_depth;
+        idx = prof_event_pair(c, st);
+        c->ev_open.push_back({fam, idx});
+    }
+    ~ProfScope() {
+        if (sync_check_on() && c->fault.empty()) {
+            hipError_t e = hipGetLastError();
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) c->fault = std::string(kFamName[fam]) + (st == c->st ? "" : " (second stream)") + " (" + hipGetErrorString(e) + ")";
+        }
+        if (idx < 0) return;
+        (void)hipEventRecord(c->ev_pool[idx + 1], st);
+        --c->prof_depth;
+    }
+};
+
+#define G_FRESH(c, who) do { if ((c)->g_stale) return fail(DQMC_EINVAL, who ": G is stale after dqmc_wrap_skip (dqmc_advance, dqmc_udv_setup or dqmc_set_green_host rebuild it)"); } while (0)
+
+// building blocks of dqmc_context.hip that the measurement entry points use
+DQMC_PRIVATE GemmArgs gemm_square(dqmc_ctx* c, const cplx* A, int opA, const cplx* B, int opB, cplx* C);
+DQMC_PRIVATE void run_gemm(dqmc_ctx* c, const GemmArgs& g);
+DQMC_PRIVATE void bmult_dev(dqmc_ctx* c, int side, int inverse, int k2, int k1, cplx* A);
+DQMC_PRIVATE void series_free(dqmc_ctx* c);

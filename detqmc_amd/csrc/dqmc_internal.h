@@ -9,7 +9,7 @@
 #include <float.h>
 // Developer A/B switches of individual kernels (tile shapes, 3M vs 4M products, ...).  None changes a result.  They exist only in
 // builds with -DDQMC_DEV_KNOBS (DQMC_BUILD_DEFINES=-DDQMC_DEV_KNOBS python -m detqmc_amd.build --force); the shipped library reads
-// ONE environment variable, DQMC_SYNC_CHECK (debug mode, dqmc_context.hip) -- everything else that selects an execution variant is
+// ONE environment variable, DQMC_SYNC_CHECK (debug mode, dqmc_ctx.h) -- everything else that selects an execution variant is
 // a create-time parameter (dqmc_tuning, include/dqmc_hip.h).
 static inline const char* dev_knob(const char* name) {
 #ifdef DQMC_DEV_KNOBS

@@ -1,0 +1,715 @@
+// C-ABI implementation (include/dqmc_hip.h), second unit: the measurement entry points -- per-slice and equal-time accumulators, the
+// time-displaced channels at the boundaries and on every slice, their Matsubara transforms -- and the measurement series.
+#include "dqmc_ctx.h"
+#include <cmath>
+#include <cstddef>
+#include <cstring>
+
+// ---------------------------------------------------------------------------------------------
+// fermionic measurements: shiftGreenSymmetric + per-slice accumulation on the device
+// ---------------------------------------------------------------------------------------------
+// T1 <- e^{-dtau K/2} G e^{+dtau K/2} (detsdwopdim.cpp:4507-4612); src: G (default) or another matrix of the same shape
+static void shift_green_dev(dqmc_ctx* c, const cplx* src = nullptr) {
+    const size_t n2 = (size_t)c->n_g * c->n_g;
+    launch_copy(c->lc, src ? src : c->G, c->T1, n2);
+    if (!c->hm.dense) {
+        ProfScope ps(c, FAM_BMULT, 2);
+        launch_bmult(c->lc, nullptr, c->hm, DQMC_RIGHT, 1, 0, 1, 1, c->T1, c->n_g, /*shift=*/1);   // right: +sinh half steps
+        launch_bmult(c->lc, nullptr, c->hm, DQMC_LEFT, 0, 0, 1, 1, c->T1, c->n_g, /*shift=*/1);    // left:  -sinh half steps
+    } else {
+        GemmArgs g = gemm_square(c, c->T1, 0, c->propKh[1], 0, c->Tdense);
+        g.sharedB = 1;
+        run_gemm(c, g);
+        g = gemm_square(c, c->propKh[0], 0, c->Tdense, 0, c->T1);
+        g.sharedA = 1;
+        run_gemm(c, g);
+    }
+}
+extern "C" int dqmc_shift_green_symmetric_host(dqmc_ctx* c, dqmc_cplx* out) {
+    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
+    if (c->hm.hubbard) return fail(DQMC_EINVAL, "shiftGreenSymmetric belongs to the SDW model");
+    G_FRESH(c, "dqmc_shift_green_symmetric_host");
+    (void)hipSetDevice(c->p.device);
+    shift_green_dev(c);
+    HIPCHK(hipStreamSynchronize(c->st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(copy_sync(c, out, selp(c, c->T1), (size_t)c->n_g * c->n_g * sizeof(cplx), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+// zero fill of every block the context has: per chain inside the arena, the equal-time block ([chain][n], contiguous) in one call
+static int acc_reset_all(dqmc_ctx* c) {
+    for (int id = 0; id < ACC_EQ; ++id)
+        for (int b = 0; c->acc[id].n && b < c->nb; ++b)
+            HIPCHK(hipMemsetAsync(chainp(c, c->acc[id].p, b), 0, c->acc[id].n * sizeof(double), c->st));
+    const AccBlock& eq = c->acc[ACC_EQ];
+    if (eq.n) HIPCHK(hipMemsetAsync(eq.p, 0, eq.n * (size_t)c->nb * sizeof(double), c->st));
+    return DQMC_OK;
+}
+// the selected chain's copy of block id, after everything enqueued so far
+static int acc_read(dqmc_ctx* c, int id, double* out) {
+    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
+    const AccBlock& a = c->acc[id];
+    if (!a.n) return fail(DQMC_EINVAL, a.missing);
+    (void)hipSetDevice(c->p.device);
+    HIPCHK(hipStreamSynchronize(c->st));
+    HIPCHK(copy_sync(c, out, (const char*)a.p + (size_t)c->sel * a.stride, a.n * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+static size_t acc_size(dqmc_ctx* c, int id) { return c ? c->acc[id].n : 0; }
+extern "C" int dqmc_measure_reset(dqmc_ctx* c) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    (void)hipSetDevice(c->p.device);
+    return acc_reset_all(c);
+}
+extern "C" int dqmc_measure_slice(dqmc_ctx* c) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    G_FRESH(c, "dqmc_measure_slice");
+    (void)hipSetDevice(c->p.device);
+    if (c->hm.hubbard) {            // DetHubbard::measure (dethubbard.cpp:521-545): accumulator layout in kernels_hubbard.hip
+        ProfScope ps(c, FAM_OTHER, 1);
+        launch_hubbard_measure(c->lc, c->hm, c->G, c->acc[ACC_SLICE].p);
+        return finish(c, "dqmc_measure_slice");
+    }
+    shift_green_dev(c);
+    { ProfScope ps(c, FAM_OTHER, 1); launch_measure_accum(c->lc, c->hm, c->T1, c->acc[ACC_SLICE].p); }
+    if (c->eq_on) { ProfScope ps(c, FAM_OTHER, 2); launch_measure_eq_corr(c->lc, c->hm, c->T1, c->eq_ob, c->acc[ACC_EQ].p); }   // same T1, no second shift
+    return finish(c, "dqmc_measure_slice");
+}
+extern "C" size_t dqmc_measure_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_SLICE); }
+extern "C" int dqmc_measure_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_SLICE, out); }
+// equal-time charge / spin / SDW / pairing correlators (dqmc_hip.h): a switch of dqmc_measure_slice with a block of its own
+extern "C" int dqmc_set_equal_time_correlators(dqmc_ctx* c, int on) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (c->hm.hubbard) return fail(DQMC_EINVAL, "the equal-time correlators belong to the SDW model");
+    AccBlock& eq = c->acc[ACC_EQ];
+    if (on && !eq.n) {
+        (void)hipSetDevice(c->p.device);
+        const size_t n = measure_eq_doubles(c->N);
+        if (const int rc = salloc(c, &eq.p, n * (size_t)c->nb)) return rc;
+        if (const int rc = salloc(c, &c->eq_ob, measure_eq_onebody_cplx(c->N) * (size_t)c->nb)) return rc;
+        HIPCHK(hipMemsetAsync(eq.p, 0, n * (size_t)c->nb * sizeof(double), c->st));
+        HIPCHK(hipMemsetAsync(c->eq_ob, 0, measure_eq_onebody_cplx(c->N) * (size_t)c->nb * sizeof(cplx), c->st));
+        eq.n = n; eq.stride = n * sizeof(double);
+    }
+    c->eq_on = on != 0;
+    return DQMC_OK;
+}
+extern "C" size_t dqmc_measure_eq_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_EQ); }
+extern "C" int dqmc_measure_eq_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_EQ, out); }
+
+// ---------------------------------------------------------------------------------------------
+// time-displaced Green's functions (dqmc_hip.h; computed inside green_from_udv while td_on)
+// ---------------------------------------------------------------------------------------------
+extern "C" int dqmc_set_timedisplaced(dqmc_ctx* c, int on) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (on && !c->td_reserved) return fail(DQMC_EINVAL, "time-displaced Green's functions need a context created with dqmc_params::timedisplaced != 0");
+    c->td_on = on != 0;
+    return DQMC_OK;
+}
+extern "C" int dqmc_get_green_timedisplaced_host(dqmc_ctx* c, dqmc_cplx* g_t0, dqmc_cplx* g_0t, int* slice) {
+    if (!c || !g_t0 || !g_0t || !slice) return fail(DQMC_EINVAL, "null argument");
+    if (!c->td_reserved || c->td_slice < 0) return fail(DQMC_EINVAL, "no time-displaced Green's function has been computed");
+    (void)hipSetDevice(c->p.device);
+    HIPCHK(hipStreamSynchronize(c->st));
+    HIPCHK(hipGetLastError());
+    const size_t bytes = (size_t)c->n_g * c->n_g * sizeof(cplx);
+    HIPCHK(copy_sync(c, g_t0, selp(c, c->GT0), bytes, hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(c, g_0t, selp(c, c->G0T), bytes, hipMemcpyDeviceToHost));
+    *slice = c->td_slice;
+    return DQMC_OK;
+}
+// ---- the channel kernels: coarse boundaries and every time slice (DQMC_TD_EVERY_SLICE) ---------------------------------------------
+enum { CH_G = 1, CH_PAIR = 2, CH_PH = 4, CH_CUR = 8, CH_TWO_BODY = CH_PH | CH_CUR };     // bit ch of a channel mask
+// One-body values of an equal-time matrix for the masked particle-hole / current kernels (t = 0: tau side, 1: 0 side): one shift of g,
+// then each masked table.  g == nullptr: T1 still holds the shifted matrix of the call before.
+static void td_onebody(dqmc_ctx* c, unsigned mask, const cplx* g, int t) {
+    if (!(mask & CH_TWO_BODY)) return;
+    if (g) shift_green_dev(c, g);
+    if (mask & CH_PH) { ProfScope ps(c, FAM_OTHER, 1); launch_td_ph_onebody(c->lc, c->hm, c->T1, c->ph_ob, t); }
+    if (mask & CH_CUR) { ProfScope ps(c, FAM_OTHER, 1); launch_td_current_onebody(c->lc, c->hm, c->T1, c->cur_bt, c->cur_ob, t); }
+}
+// The one place that launches the channel kernels: row `row` of `rows` of the masked channels' blocks (channel ch: acc[first + ch]) from
+// (gt0, g0t, gtt, g00) = (G(tau,0), G(0,tau), G(tau), G(0)).  Every shifted matrix is prepared once and handed to all masked kernels:
+// shifted gtt / g00 -> one-body values of the tau / 0 side (nullptr: already there), (shifted g0t)^H -> ph_H, shifted gt0 -> T1.  Only the
+// particle-hole and current channels need the first three.  T1 is scratch of many other calls, so nothing is carried between calls.
+static void td_row(dqmc_ctx* c, unsigned mask, int first, int row, int rows, const cplx* gt0, const cplx* g0t, const cplx* gtt, const cplx* g00) {
+    if (gtt) td_onebody(c, mask, gtt, 0);
+    if (g00) td_onebody(c, mask, g00, 1);
+    if (mask & CH_TWO_BODY) {
+        shift_green_dev(c, g0t);
+        { ProfScope ps(c, FAM_OTHER, 1); launch_conj_transpose(c->lc, c->T1, c->ph_H, c->n_g); }
+    }
+    shift_green_dev(c, gt0);
+    if (mask & CH_G) { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td(c->lc, c->hm, c->T1, c->acc[first].p, row, rows); }
+    if (mask & CH_PAIR) { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td_pair(c->lc, c->hm, c->T1, c->acc[first + 1].p, row, rows); }
+    if (mask & CH_PH) { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td_ph(c->lc, c->hm, c->T1, c->ph_H, c->ph_ob, c->acc[first + 2].p, row, rows); }
+    if (mask & CH_CUR) {
+        ProfScope ps(c, FAM_OTHER, 1);
+        launch_measure_td_current(c->lc, c->hm, c->T1, c->ph_H, c->cur_bt, c->cur_ob, c->acc[first + 3].p, row, rows);
+    }
+}
+// what every entry that works at boundary j asks for; need_current_G: the entry also reads G, which must still be G(tau_j)
+static int td_boundary_ok(dqmc_ctx* c, int j, bool need_current_G) {
+    if (j < 1 || j > c->n - 1) return fail(DQMC_EINVAL, "boundary index j must be in 1..n-1");
+    if (c->td_slice != c->s * j) return fail(DQMC_EINVAL, "the last time-displaced pair does not belong to boundary j");
+    if (!need_current_G) return DQMC_OK;
+    if (c->currentTimeslice != c->s * j) return fail(DQMC_EINVAL, "the context has left boundary j: G is no longer G(tau_j)");
+    G_FRESH(c, "time-displaced measurement");
+    return DQMC_OK;
+}
+// Row j - 1 of n - 1 of one coarse block, channel ch: G(k, tau) bins, pairing (neither reads G), particle-hole, current (both of the
+// boundary the context stands on).  Each call prepares its shifted matrices itself, so the four stand on their own in any order.
+static int td_coarse(dqmc_ctx* c, int ch, int j, const char* entry) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (!c->acc[ACC_TD + ch].n) return fail(DQMC_EINVAL, c->acc[ACC_TD + ch].missing);
+    if (const int rc = td_boundary_ok(c, j, ((1u << ch) & CH_TWO_BODY) != 0)) return rc;
+    (void)hipSetDevice(c->p.device);
+    td_row(c, 1u << ch, ACC_TD, j - 1, c->n - 1, c->GT0, c->G0T, c->G, c->G00);
+    return finish(c, entry);
+}
+extern "C" int dqmc_measure_timedisplaced(dqmc_ctx* c, int j) { return td_coarse(c, 0, j, "dqmc_measure_timedisplaced"); }
+extern "C" int dqmc_measure_timedisplaced_pair(dqmc_ctx* c, int j) { return td_coarse(c, 1, j, "dqmc_measure_timedisplaced_pair"); }
+extern "C" int dqmc_measure_timedisplaced_ph(dqmc_ctx* c, int j) { return td_coarse(c, 2, j, "dqmc_measure_timedisplaced_ph"); }
+extern "C" int dqmc_measure_timedisplaced_current(dqmc_ctx* c, int j) { return td_coarse(c, 3, j, "dqmc_measure_timedisplaced_current"); }
+extern "C" size_t dqmc_measure_td_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_TD); }
+extern "C" int dqmc_measure_td_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_TD, out); }
+extern "C" size_t dqmc_measure_td_pair_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_TD_PAIR); }
+extern "C" int dqmc_measure_td_pair_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_TD_PAIR, out); }
+extern "C" size_t dqmc_measure_td_ph_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_TD_PH); }
+extern "C" int dqmc_measure_td_ph_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_TD_PH, out); }
+extern "C" size_t dqmc_measure_td_current_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_TD_CUR); }
+extern "C" int dqmc_measure_td_current_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_TD_CUR, out); }
+extern "C" int dqmc_get_green0_timedisplaced_host(dqmc_ctx* c, dqmc_cplx* g00, int* slice) {
+    if (!c || !g00 || !slice) return fail(DQMC_EINVAL, "null argument");
+    if (!c->G00) return fail(DQMC_EINVAL, "context created without dqmc_params::td_particle_hole");
+    if (c->td_slice < 0) return fail(DQMC_EINVAL, "no time-displaced Green's function has been computed");
+    (void)hipSetDevice(c->p.device);
+    HIPCHK(hipStreamSynchronize(c->st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(copy_sync(c, g00, selp(c, c->G00), (size_t)c->n_g * c->n_g * sizeof(cplx), hipMemcpyDeviceToHost));
+    *slice = c->td_slice;
+    return DQMC_OK;
+}
+
+// ---- every time slice (DQMC_TD_EVERY_SLICE) ----------------------------------------------------------------------------------
+static size_t td_fine_n(const dqmc_ctx* c, int channel) { return channel >= 0 && channel < 4 ? c->acc[ACC_FINE0 + channel].n : 0; }
+static unsigned td_fine_mask(const dqmc_ctx* c) {
+    unsigned mask = 0;
+    for (int ch = 0; ch < 4; ++ch) if (td_fine_n(c, ch)) mask |= 1u << ch;
+    return mask;
+}
+// the work copies from slice k to k + 1 (dir > 0) or to k - 1 (dir < 0), fields as they are on the device now:
+//   up:   G(t,0) <- B_{k+1} G(t,0),   G(0,t) <- G(0,t) B_{k+1}^-1,   G(t) <- B_{k+1} G(t) B_{k+1}^-1
+//   down: G(t,0) <- B_k^-1 G(t,0),    G(0,t) <- G(0,t) B_k,          G(t) <- B_k^-1 G(t) B_k
+static void td_fine_step(dqmc_ctx* c, int k, int dir) {
+    if (dir > 0) {
+        bmult_dev(c, DQMC_LEFT, 0, k + 1, k, c->fGT0);
+        bmult_dev(c, DQMC_RIGHT, 1, k + 1, k, c->fG0T);
+        bmult_dev(c, DQMC_RIGHT, 1, k + 1, k, c->fGTT);
+        bmult_dev(c, DQMC_LEFT, 0, k + 1, k, c->fGTT);
+    } else {
+        bmult_dev(c, DQMC_LEFT, 1, k, k - 1, c->fGT0);
+        bmult_dev(c, DQMC_RIGHT, 0, k, k - 1, c->fG0T);
+        bmult_dev(c, DQMC_RIGHT, 0, k, k - 1, c->fGTT);
+        bmult_dev(c, DQMC_LEFT, 1, k, k - 1, c->fGTT);
+    }
+    c->fine_slice = k + (dir > 0 ? 1 : -1);
+}
+static void td_fine_load_boundary(dqmc_ctx* c) {
+    const size_t n2 = (size_t)c->n_g * c->n_g;
+    ProfScope ps(c, FAM_OTHER, 3);
+    launch_copy(c->lc, c->GT0, c->fGT0, n2);
+    launch_copy(c->lc, c->G0T, c->fG0T, n2);
+    launch_copy(c->lc, c->G, c->fGTT, n2);
+    c->fine_slice = c->td_slice;
+}
+extern "C" int dqmc_measure_timedisplaced_segment(dqmc_ctx* c, int j) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (!c->td_fine) return fail(DQMC_EINVAL, "context created without DQMC_TD_EVERY_SLICE");
+    if (const int rc = td_boundary_ok(c, j, true)) return rc;
+    (void)hipSetDevice(c->p.device);
+    const int s = c->s, k0 = s * j, k1 = (s * (j + 1) < c->m ? s * (j + 1) : c->m) - 1;
+    const unsigned mask = td_fine_mask(c);
+    const int rows = c->m + 1;
+    td_onebody(c, mask, c->G00, 1);           // G(0) does not move with tau: once per segment
+    td_fine_load_boundary(c);
+    for (int k = k0; k <= k1; ++k) {
+        td_row(c, mask, ACC_FINE0, k, rows, c->fGT0, c->fG0T, c->fGTT, nullptr);
+        if (k < k1) td_fine_step(c, k, +1);
+    }
+    if (j == 1 && s > 1) {                    // the slices below the first boundary have no boundary of their own
+        td_fine_load_boundary(c);
+        for (int k = s; k >= 2; --k) {
+            td_fine_step(c, k, -1);
+            td_row(c, mask, ACC_FINE0, k - 1, rows, c->fGT0, c->fG0T, c->fGTT, nullptr);
+        }
+    }
+    return finish(c, "dqmc_measure_timedisplaced_segment");
+}
+// For the tests only, exported but not part of include/dqmc_hip.h: the work copies at slice k of boundary j's segment, by the steps
+// dqmc_measure_timedisplaced_segment takes (its preconditions; DQMC_EINVAL for a k outside the segment); nothing is measured
+extern "C" int dqmc_td_fine_propagate(dqmc_ctx* c, int j, int k) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (!c->td_fine) return fail(DQMC_EINVAL, "context created without DQMC_TD_EVERY_SLICE");
+    if (const int rc = td_boundary_ok(c, j, true)) return rc;
+    const int s = c->s, k0 = s * j, k1 = (s * (j + 1) < c->m ? s * (j + 1) : c->m) - 1;
+    if (k > k1 || k < (j == 1 ? 1 : k0)) return fail(DQMC_EINVAL, "slice k does not belong to the segment of boundary j");
+    (void)hipSetDevice(c->p.device);
+    td_fine_load_boundary(c);
+    for (int q = k0; q < k; ++q) td_fine_step(c, q, +1);
+    for (int q = k0; q > k; --q) td_fine_step(c, q, -1);
+    return finish(c, "dqmc_td_fine_propagate");
+}
+extern "C" int dqmc_measure_timedisplaced_ends(dqmc_ctx* c) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (!c->td_fine) return fail(DQMC_EINVAL, "context created without DQMC_TD_EVERY_SLICE");
+    if (c->currentTimeslice != 0 && c->currentTimeslice != c->m)
+        return fail(DQMC_EINVAL, "the context does not stand at tau = 0 (beta): G is not G(0)");
+    G_FRESH(c, "dqmc_measure_timedisplaced_ends");
+    (void)hipSetDevice(c->p.device);
+    // row m from the work copies (they are what dqmc_get_green_td_fine_host reports afterwards), row 0 from T2 / T3: scratch of the
+    // Green's function routines, idle here (the shifts use T1 and, with the dense B, Tdense only)
+    { ProfScope ps(c, FAM_OTHER, 1); launch_td_ends(c->lc, c->G, c->T2, c->T3, c->fGT0, c->fG0T, c->fGTT, c->n_g); }
+    c->fine_slice = c->m;
+    const unsigned mask = td_fine_mask(c);
+    td_onebody(c, mask, c->G, 0);             // G(tau) = G(0) = G for both rows and both sides: ONE shift of G
+    td_onebody(c, mask, nullptr, 1);
+    td_row(c, mask, ACC_FINE0, 0, c->m + 1, c->T2, c->T3, nullptr, nullptr);
+    td_row(c, mask, ACC_FINE0, c->m, c->m + 1, c->fGT0, c->fG0T, nullptr, nullptr);
+    return finish(c, "dqmc_measure_timedisplaced_ends");
+}
+extern "C" size_t dqmc_measure_td_fine_accum_size(dqmc_ctx* c, int channel) { return c ? td_fine_n(c, channel) : 0; }
+extern "C" int dqmc_measure_td_fine_read_host(dqmc_ctx* c, int channel, double* out) {
+    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
+    if (!td_fine_n(c, channel)) return fail(DQMC_EINVAL, c->acc[ACC_FINE0].missing);
+    return acc_read(c, ACC_FINE0 + channel, out);
+}
+static bool ser_apbx(const dqmc_ctx* c) { return c->p.bc == DQMC_BC_APBC_X || c->p.bc == DQMC_BC_APBC_XY; }
+static bool ser_apby(const dqmc_ctx* c) { return c->p.bc == DQMC_BC_APBC_Y || c->p.bc == DQMC_BC_APBC_XY; }
+extern "C" size_t dqmc_measure_td_matsubara_size(dqmc_ctx* c, int channel, int nfreq) {
+    if (!c || !td_fine_n(c, channel) || nfreq < 1 || nfreq > c->m) return 0;
+    return (size_t)c->nb * (channel == 2 ? 3 : 2) * nfreq * c->N * 2;
+}
+extern "C" int dqmc_measure_td_matsubara_host(dqmc_ctx* c, int channel, int nfreq, double* out) {
+    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
+    if (!c->td_fine) return fail(DQMC_EINVAL, "context created without DQMC_TD_EVERY_SLICE");
+    if (!td_fine_n(c, channel)) return fail(DQMC_EINVAL, c->acc[ACC_FINE0].missing);
+    if (nfreq < 1 || nfreq > c->m) return fail(DQMC_EINVAL, "nfreq must be in 1..m");
+    (void)hipSetDevice(c->p.device);
+    const size_t n_out = dqmc_measure_td_matsubara_size(c, channel, nfreq), need = n_out + (size_t)c->nb;
+    if (need > c->mats_cap) {
+        HIPCHK(hipStreamSynchronize(c->st));
+        if (c->mats_out) { (void)hipFree(c->mats_out); c->mats_out = nullptr; c->mats_cap = 0; }
+        HIPCHK(hipMalloc((void**)&c->mats_out, need * sizeof(double)));
+        c->mats_cap = need;
+    }
+    bool launched;
+    {
+        ProfScope ps(c, FAM_OTHER, 1);
+        launched = launch_td_matsubara(c->lc, c->hm, c->acc[ACC_FINE0 + channel].p, channel, nfreq, ser_apbx(c), ser_apby(c), c->mats_out, c->mats_out + n_out);
+    }
+    if (!launched) return fail(DQMC_EINVAL, "dqmc_measure_td_matsubara_host: the lattice is too large for the kernel's LDS");
+    { const int rc = finish(c, "dqmc_measure_td_matsubara_host"); if (rc != DQMC_OK) return rc; }
+    std::vector<double> bad((size_t)c->nb);
+    HIPCHK(copy_sync(c, bad.data(), c->mats_out + n_out, bad.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (double b : bad) if (b != 0.0) return fail(DQMC_EINVAL, "an every-slice row has no sample: the measurement sweep did not visit every time slice");
+    HIPCHK(copy_sync(c, out, c->mats_out, n_out * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// measurement series (dqmc_hip.h; kernels in kernels_measure.hip)
+// ---------------------------------------------------------------------------------------------
+extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nfreq, int parts) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (c->hm.hubbard) return fail(DQMC_EINVAL, "the measurement series belongs to the SDW model");
+    if (c->ser.open) return fail(DQMC_EINVAL, "a measurement series is already open (dqmc_series_end)");
+    if (parts <= 0 || (parts & ~0x5f)) return fail(DQMC_EINVAL, "dqmc_series_begin: parts must be a non-empty mask of bits 0 .. 4 and 6");
+    if (bin_size < 1) return fail(DQMC_EINVAL, "dqmc_series_begin: bin_size must be at least 1");
+    if (max_bins < 2) return fail(DQMC_EINVAL, "dqmc_series_begin: max_bins must be at least 2");
+    if ((parts & 1) && !c->acc[ACC_EQ].n) return fail(DQMC_EINVAL, "dqmc_series_begin: the equal-time block has never been enabled (dqmc_set_equal_time_correlators)");
+    if ((parts & 1) && series_eq_sample_lds_bytes(c->hm.L) > 152 * 1024)
+        return fail(DQMC_EINVAL, "dqmc_series_begin: the lattice is too large for the equal-time sample kernel's LDS");
+    dqmc_ctx::Series s;
+    const size_t N = (size_t)c->N;
+    if (parts & 1) { s.off[0] = 0; s.len[0] = 10 * N; s.S = 10 * N; }
+    for (int ch = 0; ch < 4; ++ch) {
+        if (!(parts & (2 << ch))) continue;
+        if (!c->td_fine || !td_fine_n(c, ch)) return fail(DQMC_EINVAL, "dqmc_series_begin: no every-slice block for a channel of the mask");
+        if (nfreq < 1 || nfreq > c->m) return fail(DQMC_EINVAL, "dqmc_series_begin: nfreq must be in 1..m");
+        if (!td_matsubara_fits(c->hm, ch, nfreq)) return fail(DQMC_EINVAL, "dqmc_series_begin: the lattice is too large for the Matsubara kernel's LDS");
+        s.off[1 + ch] = s.S; s.len[1 + ch] = (size_t)(ch == 2 ? 3 : 2) * nfreq * N * 2; s.S += s.len[1 + ch];
+    }
+    if (parts & DQMC_SERIES_PHI) {                          // the field always exists: no block to ask for
+        if (nfreq < 1 || nfreq > c->m) return fail(DQMC_EINVAL, "dqmc_series_begin: nfreq must be in 1..m");
+        if (series_phi_sample_fgroup(c->hm.L, c->m, nfreq) < 1)
+            return fail(DQMC_EINVAL, "dqmc_series_begin: the lattice is too large for the order-parameter sample kernel's LDS");
+        s.off[6] = s.S; s.len[6] = (size_t)nfreq * N + 5; s.S += s.len[6];
+    }
+    s.bin_size = bin_size; s.max_bins = max_bins; s.nfreq = (parts & (0x1e | DQMC_SERIES_PHI)) ? nfreq : 0; s.parts = parts;
+    (void)hipSetDevice(c->p.device);
+    const size_t n = (size_t)c->nb * s.S, L = (size_t)c->hm.L;
+    c->ser = s;                                             // from here on series_free releases what was allocated
+    dqmc_ctx::Series& r = c->ser;
+    hipError_t e = (parts & DQMC_SERIES_PHI) ? series_phi_sample_prepare() : hipSuccess;   // an attribute failure is an error here, not at launch
+    if (e == hipSuccess) e = hipMalloc((void**)&r.sample, n * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&r.openbin, n * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&r.bins, (size_t)max_bins * n * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&r.bad, (size_t)5 * c->nb * sizeof(double));
+    const size_t mt = (parts & DQMC_SERIES_PHI) ? (size_t)c->m : 0;     // the temporal table of the order-parameter part
+    if (e == hipSuccess) e = hipMalloc((void**)&r.trig, 2 * (L + mt) * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&r.stat, (2 * n + (size_t)12 * c->nb) * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&r.srctab, (size_t)c->nb * sizeof(const double*));
+    if (e == hipSuccess) e = hipMemsetAsync(r.sample, 0, n * sizeof(double), c->st);
+    if (e == hipSuccess) e = hipMemsetAsync(r.openbin, 0, n * sizeof(double), c->st);
+    if (e == hipSuccess) e = hipMemsetAsync(r.bins, 0, (size_t)max_bins * n * sizeof(double), c->st);
+    if (e == hipSuccess) e = hipMemsetAsync(r.bad, 0, (size_t)5 * c->nb * sizeof(double), c->st);
+    if (e == hipSuccess) {
+        // cos / sin(2 pi j / L) as finishFermionic of the host layer forms them: the device's structure factors use the same values
+        std::vector<double> trig(2 * (L + mt));
+        for (size_t j = 0; j < L; ++j) { trig[j] = std::cos(2.0 * M_PI * double(j) / double(L)); trig[L + j] = std::sin(2.0 * M_PI * double(j) / double(L)); }
+        for (size_t j = 0; j < mt; ++j) { trig[2 * L + j] = std::cos(2.0 * M_PI * double(j) / double(mt)); trig[2 * L + mt + j] = std::sin(2.0 * M_PI * double(j) / double(mt)); }
+        e = copy_sync(c, r.trig, trig.data(), trig.size() * sizeof(double), hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) { series_free(c); return fail(DQMC_EHIP, std::string("dqmc_series_begin: ") + hipGetErrorString(e)); }
+    r.open = true;
+    return DQMC_OK;
+}
+extern "C" int dqmc_series_end(dqmc_ctx* c) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (!c->ser.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    (void)hipSetDevice(c->p.device);
+    HIPCHK(hipStreamSynchronize(c->st));
+    series_free(c);
+    return DQMC_OK;
+}
+extern "C" int dqmc_series_layout(dqmc_ctx* c, int part, size_t* offset, size_t* length) {
+    if (!c || !offset || !length) return fail(DQMC_EINVAL, "null argument");
+    if (!c->ser.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (part < 0 || part > 6 || !(c->ser.parts & (1 << part))) return fail(DQMC_EINVAL, "dqmc_series_layout: the part is not in the series");
+    *offset = c->ser.off[part]; *length = c->ser.len[part];
+    return DQMC_OK;
+}
+extern "C" int dqmc_series_info(dqmc_ctx* c, int* bins_closed, int* sweeps_in_open_bin, size_t* sample_len) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (!c->ser.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (bins_closed) *bins_closed = c->ser.closed;
+    if (sweeps_in_open_bin) *sweeps_in_open_bin = c->ser.in_open;
+    if (sample_len) *sample_len = c->ser.S;
+    return DQMC_OK;
+}
+// The first half of dqmc_series_add_sweep: the sample of all chains from the blocks as they stand, and the flags read back.  `entry`
+// names the public call in the messages.
+static int series_form_sample(dqmc_ctx* c, const char* entry) {
+    dqmc_ctx::Series& s = c->ser;
+    const std::string who(entry);
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (s.closed >= s.max_bins) return fail(DQMC_EINVAL, who + ": the series is full (max_bins bins are closed)");
+    (void)hipSetDevice(c->p.device);
+    s.formed = false;                                       // the sample buffer is rewritten from here on
+    // the flags of the parts behind each other, [part][chain]
+    int nparts = 0;
+    {
+        ProfScope ps(c, FAM_OTHER, 0);
+        if (s.parts & 1) {
+            if (!launch_series_eq_sample(c->lc, c->hm, c->acc[ACC_EQ].p, c->acc[ACC_EQ].n, s.trig, s.sample, s.S, s.off[0], s.bad))
+                return fail(DQMC_EINVAL, who + ": the lattice is too large for the equal-time sample kernel's LDS");
+            ++nparts;
+        }
+        for (int ch = 0; ch < 4; ++ch)
+            if (s.parts & (2 << ch)) {
+                if (!launch_td_matsubara(c->lc, c->hm, c->acc[ACC_FINE0 + ch].p, ch, s.nfreq, ser_apbx(c), ser_apby(c), s.sample + s.off[1 + ch],
+                                         s.bad + (size_t)nparts * c->nb, s.S))
+                    return fail(DQMC_EINVAL, who + ": the lattice is too large for the Matsubara kernel's LDS");
+                ++nparts;
+            }
+        c->fam_launches[FAM_OTHER] += (uint64_t)nparts;
+        if (s.parts & DQMC_SERIES_PHI) {                    // after the other parts; no flag row: the field always exists
+            if (!launch_series_phi_sample(c->lc, c->hm, s.trig, s.trig + 2 * (size_t)c->hm.L, s.nfreq, s.sample, s.S, s.off[6]))
+                return fail(DQMC_EINVAL, who + ": the lattice is too large for the order-parameter sample kernel's LDS");
+            ++c->fam_launches[FAM_OTHER];
+        }
+    }
+    { const int rc = finish(c, entry); if (rc != DQMC_OK) return rc; }
+    std::vector<double> bad((size_t)nparts * c->nb);
+    if (nparts) HIPCHK(copy_sync(c, bad.data(), s.bad, bad.size() * sizeof(double), hipMemcpyDeviceToHost));
+    else HIPCHK(hipStreamSynchronize(c->st));               // the order-parameter part alone: no flags, the call still synchronises
+    for (double b : bad)
+        if (b != 0.0) return fail(DQMC_EINVAL, who + ": a block of the series has no sample (equal-time count or an every-slice row count < 1)");
+    s.formed = true;
+    return DQMC_OK;
+}
+// true if [p, p + bytes) is device memory of `device`; a host address, an address the runtime does not know and a range that leaves its
+// allocation are all false, and no error stays pending
+static bool series_device_range(const void* p, size_t bytes, int device) {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (attr.type != hipMemoryTypeDevice || attr.device != device) return false;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    const uintptr_t lo = (uintptr_t)base, at = (uintptr_t)p;
+    return at >= lo && bytes <= size && at - lo <= size - bytes;
+}
+// closed[k] = (closed[2k] + closed[2k+1]) * 0.5 for all slots; the caller has checked an even number of closed bins and the bin size
+constexpr int SERIES_MAX_BIN_SIZE = 1 << 29;                // the largest bin_size that can still double: the result stays within 2^30
+static int series_rebin(dqmc_ctx* c, const char* entry) {
+    dqmc_ctx::Series& s = c->ser;
+    if (s.closed > 0) {
+        { ProfScope ps(c, FAM_OTHER, 1); launch_series_rebin(c->lc, s.bins, (size_t)c->nb * s.S, s.closed / 2); }
+        { const int rc = finish(c, entry); if (rc != DQMC_OK) return rc; }
+        HIPCHK(hipStreamSynchronize(c->st));
+    }
+    s.closed /= 2; s.bin_size *= 2; ++s.rebins;
+    return DQMC_OK;
+}
+// The second half: open[s] += src[s][0 .. S) for every slot s of this context, src == nullptr: the context's own rows in order
+static int series_accumulate(dqmc_ctx* c, const double* const* src, const char* entry) {
+    dqmc_ctx::Series& s = c->ser;
+    const std::string who(entry);
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (!s.formed) return fail(DQMC_EINVAL, who + ": the context's sample is not formed (dqmc_series_form_sample)");
+    if (s.closed >= s.max_bins) return fail(DQMC_EINVAL, who + ": the series is full (max_bins bins are closed)");
+    (void)hipSetDevice(c->p.device);
+    const size_t n = (size_t)c->nb * s.S;
+    const int close = s.in_open + 1 == s.bin_size;
+    if (!src) {
+        ProfScope ps(c, FAM_OTHER, 1);
+        launch_series_accum(c->lc, s.sample, s.openbin, s.bins + (size_t)s.closed * n, n, close, s.bin_size);
+    } else {
+        for (int b = 0; b < c->nb; ++b) {
+            if (!src[b]) return fail(DQMC_EINVAL, who + ": a source row is null");
+            if (((uintptr_t)src[b] & (sizeof(double) - 1)) || !series_device_range(src[b], s.S * sizeof(double), c->p.device))
+                return fail(DQMC_EINVAL, who + ": a source row is not S doubles of device memory on the context's device");
+        }
+        s.srchost.assign(src, src + c->nb);                 // stays alive until the stream has taken the copy
+        HIPCHK(hipMemcpyAsync((void*)s.srctab, s.srchost.data(), (size_t)c->nb * sizeof(const double*), hipMemcpyHostToDevice, c->st));
+        ProfScope ps(c, FAM_OTHER, 1);
+        launch_series_accum_routed(c->lc, s.srctab, s.openbin, s.bins + (size_t)s.closed * n, s.S, close, s.bin_size);
+    }
+    if (s.flags & DQMC_SERIES_TRACK_VARIANCE) {             // the same rows once more, into the running mean and m2 of the slot
+        ProfScope ps(c, FAM_OTHER, 1);
+        launch_series_welford(c->lc, s.sample, src ? s.srctab : nullptr, s.var, s.var + n, s.S, s.samples + 1);
+    }
+    s.formed = false;
+    { const int rc = finish(c, entry); if (rc != DQMC_OK) return rc; }
+    HIPCHK(hipStreamSynchronize(c->st));                    // the rows may belong to another context: they are free again on return
+    ++s.samples;
+    if (close) { ++s.closed; s.in_open = 0; } else ++s.in_open;
+    // auto re-binning: the close that fills the series merges neighbouring bins before the call returns, so the series is never
+    // observed full; if bin_size cannot double any more the series becomes full as it does without the flag
+    if (close && (s.flags & DQMC_SERIES_AUTO_REBIN) && s.closed == s.max_bins && s.bin_size <= SERIES_MAX_BIN_SIZE) return series_rebin(c, entry);
+    return DQMC_OK;
+}
+extern "C" int dqmc_series_form_sample(dqmc_ctx* c) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    return series_form_sample(c, "dqmc_series_form_sample");
+}
+extern "C" int dqmc_series_sample_device(dqmc_ctx* c, const double** rows, size_t* S) {
+    if (!c || !rows || !S) return fail(DQMC_EINVAL, "null argument");
+    if (!c->ser.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    *rows = c->ser.sample; *S = c->ser.S;
+    return DQMC_OK;
+}
+extern "C" int dqmc_series_accumulate(dqmc_ctx* c, const double* const* src) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    return series_accumulate(c, src, "dqmc_series_accumulate");
+}
+extern "C" int dqmc_series_add_sweep(dqmc_ctx* c) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    const int rc = series_form_sample(c, "dqmc_series_add_sweep");
+    return rc != DQMC_OK ? rc : series_accumulate(c, nullptr, "dqmc_series_add_sweep");
+}
+extern "C" int dqmc_series_read_bins_host(dqmc_ctx* c, int first, int count, double* out) {
+    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
+    const dqmc_ctx::Series& s = c->ser;
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (first < 0 || count < 1 || first > s.closed || count > s.closed - first) return fail(DQMC_EINVAL, "dqmc_series_read_bins_host: bins outside the closed range");
+    (void)hipSetDevice(c->p.device);
+    const size_t n = (size_t)c->nb * s.S;
+    HIPCHK(hipMemcpy2DAsync(out, s.S * sizeof(double), s.bins + (size_t)first * n + (size_t)c->sel * s.S, n * sizeof(double),
+                            s.S * sizeof(double), (size_t)count, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    return DQMC_OK;
+}
+extern "C" int dqmc_series_stats_host(dqmc_ctx* c, double* mean, double* err) {
+    if (!c || !mean || !err) return fail(DQMC_EINVAL, "null argument");
+    const dqmc_ctx::Series& s = c->ser;
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (s.closed < 2) return fail(DQMC_EINVAL, "dqmc_series_stats_host: the jackknife needs at least two closed bins");
+    (void)hipSetDevice(c->p.device);
+    const size_t n = (size_t)c->nb * s.S;
+    { ProfScope ps(c, FAM_OTHER, 1); launch_series_stats(c->lc, s.bins, n, s.closed, s.stat, s.stat + n); }
+    { const int rc = finish(c, "dqmc_series_stats_host"); if (rc != DQMC_OK) return rc; }
+    HIPCHK(copy_sync(c, mean, s.stat, n * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(c, err, s.stat + n, n * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+extern "C" int dqmc_series_derived_host(dqmc_ctx* c, double* value, double* err) {
+    if (!c || !value || !err) return fail(DQMC_EINVAL, "null argument");
+    const dqmc_ctx::Series& s = c->ser;
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (s.closed < 2) return fail(DQMC_EINVAL, "dqmc_series_derived_host: the jackknife needs at least two closed bins");
+    (void)hipSetDevice(c->p.device);
+    const size_t n = (size_t)c->nb * s.S, nd = (size_t)6 * c->nb;
+    double* dv = s.stat + 2 * n;
+    {
+        ProfScope ps(c, FAM_OTHER, 1);
+        launch_series_derived(c->lc, c->hm, s.bins, s.S, s.closed, s.nfreq, (s.parts & 1) ? (long long)s.off[0] : -1,
+                              (s.parts & 16) ? (long long)s.off[4] : -1, dv, dv + nd);
+    }
+    { const int rc = finish(c, "dqmc_series_derived_host"); if (rc != DQMC_OK) return rc; }
+    HIPCHK(copy_sync(c, value, dv, nd * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(c, err, dv + nd, nd * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+extern "C" int dqmc_series_phi_derived_host(dqmc_ctx* c, double* value, double* err) {
+    if (!c || !value || !err) return fail(DQMC_EINVAL, "null argument");
+    const dqmc_ctx::Series& s = c->ser;
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (!(s.parts & DQMC_SERIES_PHI)) return fail(DQMC_EINVAL, "dqmc_series_phi_derived_host: the series has no order-parameter part");
+    if (s.closed < 2) return fail(DQMC_EINVAL, "dqmc_series_phi_derived_host: the jackknife needs at least two closed bins");
+    (void)hipSetDevice(c->p.device);
+    const size_t n = (size_t)c->nb * s.S, nd = (size_t)6 * c->nb;
+    double* dv = s.stat + 2 * n;                            // the result rows of dqmc_series_derived_host: the calls are synchronous
+    { ProfScope ps(c, FAM_OTHER, 1); launch_series_phi_derived(c->lc, c->hm, s.bins, s.S, s.closed, s.nfreq, s.off[6], dv, dv + nd); }
+    { const int rc = finish(c, "dqmc_series_phi_derived_host"); if (rc != DQMC_OK) return rc; }
+    HIPCHK(copy_sync(c, value, dv, nd * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(c, err, dv + nd, nd * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+
+// ---- long runs: options, re-binning, binning analysis, export / import (dqmc_hip.h) ----
+static bool series_flags_valid(int flags, int max_bins) {
+    if (flags & ~(DQMC_SERIES_AUTO_REBIN | DQMC_SERIES_TRACK_VARIANCE)) return false;
+    return !(flags & DQMC_SERIES_AUTO_REBIN) || (max_bins >= 4 && max_bins % 2 == 0);
+}
+// w and m2 [nb][S], zeroed; kept until the series ends once they exist
+static hipError_t series_alloc_variance(dqmc_ctx* c) {
+    dqmc_ctx::Series& s = c->ser;
+    const size_t bytes = 2 * (size_t)c->nb * s.S * sizeof(double);
+    if (!s.var) {
+        const hipError_t e = hipMalloc((void**)&s.var, bytes);
+        if (e != hipSuccess) { s.var = nullptr; return e; }
+    }
+    return hipMemsetAsync(s.var, 0, bytes, c->st);
+}
+extern "C" int dqmc_series_configure(dqmc_ctx* c, int flags) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    dqmc_ctx::Series& s = c->ser;
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (s.samples || s.closed || s.in_open) return fail(DQMC_EINVAL, "dqmc_series_configure: the series is not empty any more");
+    if (!series_flags_valid(flags, s.max_bins))
+        return fail(DQMC_EINVAL, "dqmc_series_configure: unknown flag, or DQMC_SERIES_AUTO_REBIN with max_bins odd or below 4");
+    (void)hipSetDevice(c->p.device);
+    if (flags & DQMC_SERIES_TRACK_VARIANCE) {
+        HIPCHK(series_alloc_variance(c));
+        HIPCHK(hipStreamSynchronize(c->st));
+    }
+    s.flags = flags;
+    return DQMC_OK;
+}
+static void series_fill_state(const dqmc_ctx* c, dqmc_series_state* st) {
+    const dqmc_ctx::Series& s = c->ser;
+    std::memset(st, 0, sizeof(*st));
+    st->bin_size = s.bin_size; st->max_bins = s.max_bins; st->nfreq = s.nfreq; st->parts = s.parts; st->flags = s.flags;
+    st->bins_closed = s.closed; st->sweeps_in_open_bin = s.in_open; st->nb = c->nb;
+    st->samples = s.samples; st->rebins = s.rebins; st->sample_len = s.S;
+}
+extern "C" int dqmc_series_get_state(dqmc_ctx* c, dqmc_series_state* st) {
+    if (!c || !st) return fail(DQMC_EINVAL, "null argument");
+    if (!c->ser.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    series_fill_state(c, st);
+    return DQMC_OK;
+}
+extern "C" int dqmc_series_rebin(dqmc_ctx* c) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    dqmc_ctx::Series& s = c->ser;
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (s.closed % 2) return fail(DQMC_EINVAL, "dqmc_series_rebin: the number of closed bins is odd");
+    if (s.bin_size > SERIES_MAX_BIN_SIZE) return fail(DQMC_EINVAL, "dqmc_series_rebin: bin_size cannot double any more");
+    (void)hipSetDevice(c->p.device);
+    return series_rebin(c, "dqmc_series_rebin");
+}
+extern "C" int dqmc_series_binning_host(dqmc_ctx* c, int levels, double* err, double* tau) {
+    if (!c || !err) return fail(DQMC_EINVAL, "null argument");
+    dqmc_ctx::Series& s = c->ser;
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (levels < 1 || levels > 12) return fail(DQMC_EINVAL, "dqmc_series_binning_host: levels must be in 1..12");
+    if ((s.closed >> (levels - 1)) < 2) return fail(DQMC_EINVAL, "dqmc_series_binning_host: the top level needs at least two merged bins");
+    if (tau && !(s.flags & DQMC_SERIES_TRACK_VARIANCE)) return fail(DQMC_EINVAL, "dqmc_series_binning_host: tau needs DQMC_SERIES_TRACK_VARIANCE");
+    if (tau && s.samples < 2) return fail(DQMC_EINVAL, "dqmc_series_binning_host: tau needs at least two samples");
+    (void)hipSetDevice(c->p.device);
+    const size_t n = (size_t)c->nb * s.S, need = 2 * (size_t)levels * n;
+    if (need > s.binning_cap) {
+        HIPCHK(hipStreamSynchronize(c->st));
+        if (s.binning) { (void)hipFree(s.binning); s.binning = nullptr; s.binning_cap = 0; }
+        HIPCHK(hipMalloc((void**)&s.binning, need * sizeof(double)));
+        s.binning_cap = need;
+    }
+    double* derr = s.binning;
+    double* dtau = tau ? s.binning + (size_t)levels * n : nullptr;
+    {
+        ProfScope ps(c, FAM_OTHER, 1);
+        launch_series_binning(c->lc, s.bins, tau ? s.var + n : nullptr, n, s.closed, levels, s.bin_size, s.samples, derr, dtau);
+    }
+    { const int rc = finish(c, "dqmc_series_binning_host"); if (rc != DQMC_OK) return rc; }
+    HIPCHK(copy_sync(c, err, derr, (size_t)levels * n * sizeof(double), hipMemcpyDeviceToHost));
+    if (tau) HIPCHK(copy_sync(c, tau, dtau, (size_t)levels * n * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+static size_t series_export_len(size_t n, int closed, int flags) {
+    return ((size_t)closed + 1 + ((flags & DQMC_SERIES_TRACK_VARIANCE) ? 2 : 0)) * n;
+}
+extern "C" int dqmc_series_export_host(dqmc_ctx* c, double* out, size_t len) {
+    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
+    const dqmc_ctx::Series& s = c->ser;
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    const size_t n = (size_t)c->nb * s.S;
+    if (len != series_export_len(n, s.closed, s.flags)) return fail(DQMC_EINVAL, "dqmc_series_export_host: len is not the size of the series");
+    (void)hipSetDevice(c->p.device);
+    HIPCHK(hipStreamSynchronize(c->st));
+    const size_t nc = (size_t)s.closed * n;
+    if (nc) HIPCHK(copy_sync(c, out, s.bins, nc * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(c, out + nc, s.openbin, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (s.flags & DQMC_SERIES_TRACK_VARIANCE) HIPCHK(copy_sync(c, out + nc + n, s.var, 2 * n * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+extern "C" int dqmc_series_import_host(dqmc_ctx* c, const dqmc_series_state* st, const double* in, size_t len) {
+    if (!c || !st || !in) return fail(DQMC_EINVAL, "null argument");
+    dqmc_ctx::Series& s = c->ser;
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (st->nb != c->nb || st->sample_len != s.S || st->parts != s.parts || st->nfreq != s.nfreq)
+        return fail(DQMC_EINVAL, "dqmc_series_import_host: chains, sample length, parts or nfreq differ from the open series");
+    if (st->bins_closed < 0 || st->bins_closed >= s.max_bins) return fail(DQMC_EINVAL, "dqmc_series_import_host: bins_closed must be below max_bins of the open series");
+    if (st->bin_size < 1 || st->sweeps_in_open_bin < 0 || st->sweeps_in_open_bin >= st->bin_size)
+        return fail(DQMC_EINVAL, "dqmc_series_import_host: sweeps_in_open_bin must be below bin_size");
+    if (!series_flags_valid(st->flags, s.max_bins)) return fail(DQMC_EINVAL, "dqmc_series_import_host: the flags are not valid for max_bins of the open series");
+    if (st->samples < 0 || st->rebins < 0) return fail(DQMC_EINVAL, "dqmc_series_import_host: negative counter");
+    const size_t n = (size_t)c->nb * s.S;
+    if (len != series_export_len(n, st->bins_closed, st->flags)) return fail(DQMC_EINVAL, "dqmc_series_import_host: len is not the size of the series");
+    (void)hipSetDevice(c->p.device);
+    HIPCHK(hipStreamSynchronize(c->st));
+    if ((st->flags & DQMC_SERIES_TRACK_VARIANCE) && !s.var) HIPCHK(series_alloc_variance(c));   // nothing of the series has changed yet
+    const size_t nc = (size_t)st->bins_closed * n;
+    if (nc) HIPCHK(copy_sync(c, s.bins, in, nc * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(copy_sync(c, s.openbin, in + nc, n * sizeof(double), hipMemcpyHostToDevice));
+    if (st->flags & DQMC_SERIES_TRACK_VARIANCE) HIPCHK(copy_sync(c, s.var, in + nc + n, 2 * n * sizeof(double), hipMemcpyHostToDevice));
+    s.bin_size = st->bin_size; s.flags = st->flags; s.closed = st->bins_closed; s.in_open = st->sweeps_in_open_bin;
+    s.samples = st->samples; s.rebins = st->rebins; s.formed = false;
+    return DQMC_OK;
+}
+
+extern "C" int dqmc_get_green_td_fine_host(dqmc_ctx* c, dqmc_cplx* g_t0, dqmc_cplx* g_0t, dqmc_cplx* g_tt, int* slice) {
+    if (!c || !g_t0 || !g_0t || !g_tt || !slice) return fail(DQMC_EINVAL, "null argument");
+    if (!c->td_fine || c->fine_slice < 0) return fail(DQMC_EINVAL, "no every-slice Green's function has been propagated");
+    (void)hipSetDevice(c->p.device);
+    HIPCHK(hipStreamSynchronize(c->st));
+    HIPCHK(hipGetLastError());
+    const size_t bytes = (size_t)c->n_g * c->n_g * sizeof(cplx);
+    HIPCHK(copy_sync(c, g_t0, selp(c, c->fGT0), bytes, hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(c, g_0t, selp(c, c->fG0T), bytes, hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(c, g_tt, selp(c, c->fGTT), bytes, hipMemcpyDeviceToHost));
+    *slice = c->fine_slice;
+    return DQMC_OK;
+}

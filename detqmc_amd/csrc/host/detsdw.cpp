@@ -484,23 +484,16 @@ void DetSDW::finishFermionic(int b) {
         const int rows = fine ? m + 1 : n_ - 1;
         const char* missing = fine ? "measurement sweep did not visit every time slice (time-displaced)"
                                    : "measurement sweep did not visit every stabilisation boundary";
+        // the coarse blocks' (size, read) entry points by channel; the fine blocks share one pair that takes the channel
+        struct Coarse { size_t (*size)(dqmc_ctx*); int (*read)(dqmc_ctx*, double*); const char* name; };
+        static const Coarse coarse[4] = {{dqmc_measure_td_accum_size, dqmc_measure_td_read_host, "dqmc_measure_td_read_host"},
+                                         {dqmc_measure_td_pair_accum_size, dqmc_measure_td_pair_read_host, "dqmc_measure_td_pair_read_host"},
+                                         {dqmc_measure_td_ph_accum_size, dqmc_measure_td_ph_read_host, "dqmc_measure_td_ph_read_host"},
+                                         {dqmc_measure_td_current_accum_size, dqmc_measure_td_current_read_host, "dqmc_measure_td_current_read_host"}};
         auto read = [&](int channel, std::vector<double>& buf) {
-            if (fine) {
-                buf.resize(dqmc_measure_td_fine_accum_size(ctx_, channel));
-                check(dqmc_measure_td_fine_read_host(ctx_, channel, buf.data()), "dqmc_measure_td_fine_read_host");
-            } else if (channel == 0) {
-                buf.resize(dqmc_measure_td_accum_size(ctx_));
-                check(dqmc_measure_td_read_host(ctx_, buf.data()), "dqmc_measure_td_read_host");
-            } else if (channel == 1) {
-                buf.resize(dqmc_measure_td_pair_accum_size(ctx_));
-                check(dqmc_measure_td_pair_read_host(ctx_, buf.data()), "dqmc_measure_td_pair_read_host");
-            } else if (channel == 2) {
-                buf.resize(dqmc_measure_td_ph_accum_size(ctx_));
-                check(dqmc_measure_td_ph_read_host(ctx_, buf.data()), "dqmc_measure_td_ph_read_host");
-            } else {
-                buf.resize(dqmc_measure_td_current_accum_size(ctx_));
-                check(dqmc_measure_td_current_read_host(ctx_, buf.data()), "dqmc_measure_td_current_read_host");
-            }
+            buf.resize(fine ? dqmc_measure_td_fine_accum_size(ctx_, channel) : coarse[channel].size(ctx_));
+            if (fine) check(dqmc_measure_td_fine_read_host(ctx_, channel, buf.data()), "dqmc_measure_td_fine_read_host");
+            else check(coarse[channel].read(ctx_, buf.data()), coarse[channel].name);
         };
         // G(k, tau) from the time-displaced bins: the same Fourier sum as kOcc, one row per tau
         {

@@ -260,6 +260,12 @@ class KernelContext:
         check(self.lib.dqmc_get_green_timedisplaced_host(self.h, gt0.ctypes.data, g0t.ctypes.data, C.byref(sl)))
         return sl.value, gt0, g0t
 
+    def _read_block(self, size_fn, read_fn, *which):
+        """one accumulator block of the selected chain through its (size, read) pair of entry points"""
+        out = np.zeros(size_fn(self.h, *which))
+        check(read_fn(self.h, *which, out.ctypes.data_as(_lib._DP)))
+        return out
+
     def measure_reset(self):
         check(self.lib.dqmc_measure_reset(self.h))
 
@@ -269,9 +275,7 @@ class KernelContext:
 
     def measure_read(self):
         """the selected chain's accumulators: [greenK0, greenLocal, occDiffSq, count, pairPlus[N], pairMinus[N], S_X, S_Y]"""
-        out = np.zeros(self.lib.dqmc_measure_accum_size(self.h))
-        check(self.lib.dqmc_measure_read_host(self.h, out.ctypes.data_as(_lib._DP)))
-        return out
+        return self._read_block(self.lib.dqmc_measure_accum_size, self.lib.dqmc_measure_read_host)
 
     def set_equal_time_correlators(self, on=True):
         """while on, every measure_slice also bins the equal-time charge / spinZ / sdw / pairPlus / pairMinus sums of the same shifted
@@ -281,17 +285,13 @@ class KernelContext:
     def measure_eq_read(self):
         """the selected chain's equal-time block: [count, charge[N], spinZ[N], sdw[N], pairPlus[N], pairMinus[N]], raw sums over B of
         Re W(B (+) d, B), index dy L + dx; C(d) = sum / (count N)"""
-        out = np.zeros(self.lib.dqmc_measure_eq_accum_size(self.h))
-        check(self.lib.dqmc_measure_eq_read_host(self.h, out.ctypes.data_as(_lib._DP)))
-        return out
+        return self._read_block(self.lib.dqmc_measure_eq_accum_size, self.lib.dqmc_measure_eq_read_host)
 
     def measure_timedisplaced(self, j):
         check(self.lib.dqmc_measure_timedisplaced(self.h, j))
 
     def measure_td_read(self):
-        out = np.zeros(self.lib.dqmc_measure_td_accum_size(self.h))
-        check(self.lib.dqmc_measure_td_read_host(self.h, out.ctypes.data_as(_lib._DP)))
-        return out
+        return self._read_block(self.lib.dqmc_measure_td_accum_size, self.lib.dqmc_measure_td_read_host)
 
     def measure_timedisplaced_pair(self, j):
         """pairing correlators of the last pair's shifted G(tau_j, 0) into their block (needs timeDisplaced=2 at construction)"""
@@ -299,9 +299,7 @@ class KernelContext:
 
     def measure_td_pair_read(self):
         """count[n-1], then per boundary the N sums of Re T+ and the N sums of Re T- over the periodic site differences"""
-        out = np.zeros(self.lib.dqmc_measure_td_pair_accum_size(self.h))
-        check(self.lib.dqmc_measure_td_pair_read_host(self.h, out.ctypes.data_as(_lib._DP)))
-        return out
+        return self._read_block(self.lib.dqmc_measure_td_pair_accum_size, self.lib.dqmc_measure_td_pair_read_host)
 
     def green0_timedisplaced(self):
         """(slice, G(0)) of the last interior advance's own field configuration, selected chain (needs tdParticleHole=True)"""
@@ -317,9 +315,7 @@ class KernelContext:
 
     def measure_td_ph_read(self):
         """count[n-1], then per boundary the N sums of Re W over the periodic site differences for charge, spinZ and sdw"""
-        out = np.zeros(self.lib.dqmc_measure_td_ph_accum_size(self.h))
-        check(self.lib.dqmc_measure_td_ph_read_host(self.h, out.ctypes.data_as(_lib._DP)))
-        return out
+        return self._read_block(self.lib.dqmc_measure_td_ph_accum_size, self.lib.dqmc_measure_td_ph_read_host)
 
     def measure_timedisplaced_current(self, j):
         """current-current correlators and bond kinetic energy of boundary j into their block (needs tdCurrent=True at construction; call
@@ -329,9 +325,7 @@ class KernelContext:
     def measure_td_current_read(self):
         """count[n-1], then per boundary the N sums of Re W[j_x, j_x], the N sums of Re W[j_y, j_y] over the periodic site differences and
         the two sums of Re o_tau[k_x], Re o_tau[k_y] over the sites"""
-        out = np.zeros(self.lib.dqmc_measure_td_current_accum_size(self.h))
-        check(self.lib.dqmc_measure_td_current_read_host(self.h, out.ctypes.data_as(_lib._DP)))
-        return out
+        return self._read_block(self.lib.dqmc_measure_td_current_accum_size, self.lib.dqmc_measure_td_current_read_host)
 
     def measure_timedisplaced_segment(self, j):
         """every slice of boundary j's segment into the fine blocks, by propagation from the boundary's matrices (needs tdEverySlice=True at
@@ -344,9 +338,7 @@ class KernelContext:
 
     def measure_td_fine_read(self, channel):
         """fine block of channel 0 (G(k, tau) bins), 1 (pairing), 2 (particle-hole), 3 (current): count[m+1], then rows k = 0 .. m"""
-        out = np.zeros(self.lib.dqmc_measure_td_fine_accum_size(self.h, channel))
-        check(self.lib.dqmc_measure_td_fine_read_host(self.h, channel, out.ctypes.data_as(_lib._DP)))
-        return out
+        return self._read_block(self.lib.dqmc_measure_td_fine_accum_size, self.lib.dqmc_measure_td_fine_read_host, channel)
 
     def measure_td_matsubara(self, channel, nfreq):
         """Matsubara transforms of the fine block of `channel`, every chain and component: complex (nchains, components, nfreq, N)"""
