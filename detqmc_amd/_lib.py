@@ -26,6 +26,10 @@ DQMC_SERIES_AUTO_REBIN, DQMC_SERIES_TRACK_VARIANCE = 1, 2   # flags of dqmc_seri
 DETSDW_SERIES_NO_HOST_COPY = 1    # flag of detsdw_series_begin: no equal-time block copy per measurement sweep while the series is open
 DETSDW_SERIES_PHI = 2             # flag of detsdw_series_begin: the order-parameter part (chi_phi(q, i omega_n) and its scalars)
 DETSDW_FM_EQ_CORRELATORS = 0x100  # flag bit of detsdw_params.fermionMeasurements: equal-time charge / spin / SDW / pairing correlators
+DQMC_TD_PH_BAND = 0x100           # flag bit of dqmc_params.td_particle_hole: the band-resolved charge channels bandDiff / bandMix
+DETSDW_TD_PH_BAND = 0x100         # flag bit of detsdw_params.timeDisplacedParticleHole: the same at the host level
+DETSDW_FM_EQ_BAND = 0x200         # flag bit of detsdw_params.fermionMeasurements: equal-time bandDiff / bandMix correlators
+DQMC_SERIES_MATS_BAND, DQMC_SERIES_EQ_BAND = 128, 256   # parts of dqmc_series_begin: Matsubara transform of channel 4, equal-time band block
 
 
 class dqmc_cplx(C.Structure):
@@ -209,6 +213,9 @@ SYMBOLS = [
     ("dqmc_set_equal_time_correlators", C.c_int, [_P, C.c_int]),
     ("dqmc_measure_eq_accum_size", C.c_size_t, [_P]),
     ("dqmc_measure_eq_read_host", C.c_int, [_P, _DP]),
+    ("dqmc_set_equal_time_band", C.c_int, [_P, C.c_int]),
+    ("dqmc_measure_eq_band_accum_size", C.c_size_t, [_P]),
+    ("dqmc_measure_eq_band_read_host", C.c_int, [_P, _DP]),
     ("dqmc_set_timedisplaced", C.c_int, [_P, C.c_int]),
     ("dqmc_get_green_timedisplaced_host", C.c_int, [_P, _P, _P, C.POINTER(C.c_int)]),
     ("dqmc_measure_timedisplaced", C.c_int, [_P, C.c_int]),
@@ -224,6 +231,9 @@ SYMBOLS = [
     ("dqmc_measure_timedisplaced_current", C.c_int, [_P, C.c_int]),
     ("dqmc_measure_td_current_accum_size", C.c_size_t, [_P]),
     ("dqmc_measure_td_current_read_host", C.c_int, [_P, _DP]),
+    ("dqmc_measure_timedisplaced_band", C.c_int, [_P, C.c_int]),
+    ("dqmc_measure_td_band_accum_size", C.c_size_t, [_P]),
+    ("dqmc_measure_td_band_read_host", C.c_int, [_P, _DP]),
     ("dqmc_measure_timedisplaced_segment", C.c_int, [_P, C.c_int]),
     ("dqmc_measure_timedisplaced_ends", C.c_int, [_P]),
     ("dqmc_measure_td_fine_accum_size", C.c_size_t, [_P, C.c_int]),
@@ -241,6 +251,7 @@ SYMBOLS = [
     ("dqmc_series_stats_host", C.c_int, [_P, _DP, _DP]),
     ("dqmc_series_derived_host", C.c_int, [_P, _DP, _DP]),
     ("dqmc_series_phi_derived_host", C.c_int, [_P, _DP, _DP]),
+    ("dqmc_series_band_derived_host", C.c_int, [_P, _DP, _DP]),
     ("dqmc_series_end", C.c_int, [_P]),
     ("dqmc_series_configure", C.c_int, [_P, C.c_int]),
     ("dqmc_series_get_state", C.c_int, [_P, C.POINTER(dqmc_series_state)]),
@@ -275,6 +286,7 @@ SYMBOLS = [
     ("detsdw_series_stats", C.c_int, [_P, C.c_int, _DP, _DP]),
     ("detsdw_series_stats_all", C.c_int, [_P, C.c_int, _DP, _DP]),
     ("detsdw_series_derived_all", C.c_int, [_P, C.c_int, _DP, _DP]),
+    ("detsdw_series_band_derived", C.c_int, [_P, C.c_int, _DP, _DP]),
     ("detsdw_series_read_bins", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _DP]),
     ("detsdw_series_end", C.c_int, [_P]),
     ("detsdw_series_configure", C.c_int, [_P, C.c_int]),

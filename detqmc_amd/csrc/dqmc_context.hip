@@ -556,14 +556,17 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
         A_(acc_alloc(ACC_TD, measure_td_doubles(p->L, c->n)));
         if (td_level == 2) A_(acc_alloc(ACC_TD_PAIR, measure_td_pair_doubles(N, c->n)));   // behind the block above: timedisplaced == 1 keeps its layout
     }
-    if (p->td_particle_hole < 0 || p->td_particle_hole > 2) return fail(DQMC_EINVAL, "td_particle_hole must be 0, 1 or 2");
-    if (p->td_particle_hole) {              // behind the blocks above: contexts without the flag are laid out as before
+    const int ph_level = p->td_particle_hole & ~DQMC_TD_PH_BAND;
+    const bool ph_band = p->td_particle_hole >= 0 && (p->td_particle_hole & DQMC_TD_PH_BAND);
+    if (p->td_particle_hole < 0 || ph_level > 2) return fail(DQMC_EINVAL, "td_particle_hole must be 0, 1 or 2 (| DQMC_TD_PH_BAND)");
+    if (ph_band && !ph_level) return fail(DQMC_EINVAL, "DQMC_TD_PH_BAND needs td_particle_hole >= 1");
+    if (ph_level) {              // behind the blocks above: contexts without the flag are laid out as before
         if (!td_level) return fail(DQMC_EINVAL, "td_particle_hole needs timedisplaced >= 1");
         A_(dalloc(c, &c->G00, n2)); A_(dalloc(c, &c->ph_H, n2));
         A_(dalloc(c, &c->ph_ob, measure_td_ph_onebody_cplx(N)));
         A_(acc_alloc(ACC_TD_PH, measure_td_ph_doubles(N, c->n)));
     }
-    if (p->td_particle_hole == 2) {         // behind the blocks above again: value 1 keeps its layout
+    if (ph_level == 2) {                    // behind the blocks above again: value 1 keeps its layout
         std::vector<hc> bt;
         build_bond_table(*p, neigh, MSF, bt);
         A_(salloc(c, &c->cur_bt, bt.size()));
@@ -574,9 +577,14 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
     if (p->timedisplaced & DQMC_TD_EVERY_SLICE) {   // behind every block above: contexts without the flag are laid out as before
         c->td_fine = true;
         A_(dalloc(c, &c->fGT0, n2)); A_(dalloc(c, &c->fG0T, n2)); A_(dalloc(c, &c->fGTT, n2));
-        const bool on[4] = {true, td_level == 2, p->td_particle_hole >= 1, p->td_particle_hole == 2};
+        const bool on[4] = {true, td_level == 2, ph_level >= 1, ph_level == 2};
         for (int ch = 0; ch < 4; ++ch)
             if (on[ch]) A_(acc_alloc(ACC_FINE0 + ch, (size_t)(p->m + 1) * (1 + measure_td_row_doubles(ch, N, p->L))));
+    }
+    if (ph_band) {                          // behind every buffer above: contexts without the flag are laid out as before
+        A_(dalloc(c, &c->band_ob, measure_td_band_onebody_cplx(N)));
+        A_(acc_alloc(ACC_TD_BAND, measure_td_band_doubles(N, c->n)));
+        if (c->td_fine) A_(acc_alloc(ACC_FINE0 + 4, (size_t)(p->m + 1) * (1 + measure_td_row_doubles(4, N, p->L))));
     }
     A_(arena_commit(c));                    // from here on the per-chain pointers are real (chain 0) addresses, zero filled
 #undef A_

@@ -35,8 +35,10 @@ enum { FAM_BMULT = DQMC_FAM_BMULT, FAM_GEMM = DQMC_FAM_GEMM, FAM_JACOBI = DQMC_F
        FAM_OTHER = DQMC_FAM_OTHER, FAM_GATHER = DQMC_FAM_GATHER, FAM_FLUSH = DQMC_FAM_FLUSH, FAM_ROUNDS = 7, FAM_COUNT = DQMC_FAM_COUNT };
 
 // The measurement accumulator blocks of a context, one table (dqmc_ctx::acc): the per-slice observables, the four coarse time-displaced
-// channels, the four every-slice ones (channel ch at ACC_FINE0 + ch, as ACC_TD + ch for the coarse ones) and the equal-time correlators
-enum { ACC_SLICE, ACC_TD, ACC_TD_PAIR, ACC_TD_PH, ACC_TD_CUR, ACC_FINE0, ACC_EQ = ACC_FINE0 + 4, ACC_COUNT };
+// channels, the four every-slice ones (channel ch at ACC_FINE0 + ch, as ACC_TD + ch for the coarse ones) and the equal-time correlators;
+// channel 4 of both families and ACC_EQ_BAND are the band-resolved charge blocks (DQMC_TD_PH_BAND, dqmc_set_equal_time_band)
+enum { TD_CHANNELS = 5 };
+enum { ACC_SLICE, ACC_TD, ACC_TD_PAIR, ACC_TD_PH, ACC_TD_CUR, ACC_TD_BAND, ACC_FINE0, ACC_EQ = ACC_FINE0 + TD_CHANNELS, ACC_EQ_BAND, ACC_COUNT };
 // n: doubles per chain, 0 while the context has no such block; chain b starts at (char*)p + b * stride (the arena's chain stride; the
 // equal-time block lives outside the arena as [chain][n]); missing: what a read of an absent block reports
 struct AccBlock { double* p; size_t n, stride; const char* missing; };
@@ -80,9 +82,12 @@ struct dqmc_ctx {
         {nullptr, 0, 0, "context created without dqmc_params::timedisplaced == 2"},
         {nullptr, 0, 0, "context created without dqmc_params::td_particle_hole"},
         {nullptr, 0, 0, "context created without dqmc_params::td_particle_hole = 2"},
+        {nullptr, 0, 0, "context created without DQMC_TD_PH_BAND"},
         {nullptr, 0, 0, "no every-slice block for this channel"}, {nullptr, 0, 0, "no every-slice block for this channel"},
         {nullptr, 0, 0, "no every-slice block for this channel"}, {nullptr, 0, 0, "no every-slice block for this channel"},
-        {nullptr, 0, 0, "the equal-time correlators have never been enabled (dqmc_set_equal_time_correlators)"}};
+        {nullptr, 0, 0, "no every-slice block for this channel"},
+        {nullptr, 0, 0, "the equal-time correlators have never been enabled (dqmc_set_equal_time_correlators)"},
+        {nullptr, 0, 0, "the equal-time band correlators have never been enabled (dqmc_set_equal_time_band)"}};
     // time-displaced Green's functions (dqmc_params::timedisplaced reserves them; dqmc_set_timedisplaced switches them on)
     bool td_reserved = false, td_on = false;
     int td_slice = -1;                                        // tau slice of the last pair GT0 / G0T (all chains), -1: none yet
@@ -92,6 +97,8 @@ struct dqmc_ctx {
     cplx *G00 = nullptr, *ph_H = nullptr, *ph_ob = nullptr;
     // td_particle_hole == 2: bond amplitudes (shared by the chains) and one-body values of the current-current correlators
     cplx *cur_bt = nullptr, *cur_ob = nullptr;
+    // DQMC_TD_PH_BAND: one-body values [2][2][N] of the band-resolved charge channels
+    cplx *band_ob = nullptr;
     // DQMC_TD_EVERY_SLICE: work copies of G(tau_k,0), G(0,tau_k), G(tau_k) that the segment / ends entries propagate (the sweep's own G,
     // GT0, G0T, G00 are only read) and the slice they stand on; one fine accumulator block (m + 1 rows) per enabled channel: 0 G(k, tau)
     // bins, 1 pairing, 2 particle-hole, 3 current
@@ -103,8 +110,11 @@ struct dqmc_ctx {
     // dqmc_set_equal_time_correlators: block [chain][1 + 5 N] and one-body scratch [chain][5 N], outside the arena, allocated by the first enable
     bool eq_on = false;
     cplx* eq_ob = nullptr;
+    // dqmc_set_equal_time_band: block [chain][1 + 2 N] and one-body scratch [chain][3 N], outside the arena, allocated by the first enable
+    bool eqb_on = false;
+    cplx* eqb_ob = nullptr;
     // dqmc_series_*: the measurement series.  Device buffers outside the arena, allocated by dqmc_series_begin and freed by dqmc_series_end
-    // or with the context: sample [nb][S], open bin [nb][S], closed bins [max_bins][nb][S], the per-part flags [5][nb], the cos / sin table
+    // or with the context: sample [nb][S], open bin [nb][S], closed bins [max_bins][nb][S], the per-part flags [7][nb], the cos / sin table
     // (2 pi j / L [2 L]; with the order-parameter part, index 6 of off / len, also 2 pi j / m [2 m] behind it) and the result buffer
     // of the statistics calls (mean, err [nb][S] each, then value, err [nb][6] each).  The counters live on the host.
     // srctab [nb]: the source rows of dqmc_series_accumulate, filled from srchost before every launch; formed: the sample buffer holds
@@ -114,7 +124,7 @@ struct dqmc_ctx {
         int bin_size = 0, max_bins = 0, nfreq = 0, parts = 0, closed = 0, in_open = 0;
         int flags = 0;                                        // DQMC_SERIES_AUTO_REBIN | DQMC_SERIES_TRACK_VARIANCE (dqmc_series_configure)
         long long samples = 0, rebins = 0;                    // accumulates since begin / merges of neighbouring bins so far
-        size_t S = 0, off[7] = {0, 0, 0, 0, 0, 0, 0}, len[7] = {0, 0, 0, 0, 0, 0, 0};   // index = bit number; 5 is never used
+        size_t S = 0, off[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, len[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // index = bit number; 5 is never used
         double *sample = nullptr, *openbin = nullptr, *bins = nullptr, *bad = nullptr, *trig = nullptr, *stat = nullptr;
         double *var = nullptr;                                // running mean w [nb][S], then m2 [nb][S]: allocated with TRACK_VARIANCE
         double *binning = nullptr;                            // result of dqmc_series_binning_host, err then tau [levels][nb][S] each,

@@ -257,7 +257,7 @@ size_t measure_accum_doubles(int N, int L);
 // (row, rows): the block holds count[rows], then row `row` at offset rows + row * stride -- (j - 1, n - 1) for the coarse blocks,
 // (k, m + 1) for the every-slice blocks; the same for the three launchers below
 void launch_measure_td(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc, int row, int rows);
-size_t measure_td_row_doubles(int channel, int N, int L);   // stride of a row: channel 0 bins, 1 pairing, 2 particle-hole, 3 current
+size_t measure_td_row_doubles(int channel, int N, int L);   // stride of a row: channel 0 bins, 1 pairing, 2 particle-hole, 3 current, 4 band
 // every-slice end rows: (G, G - 1) -> (a_t0, a_0t), (1 - G, -G) -> (b_t0, b_0t), G -> gtt; one elementwise pass, all chains
 void launch_td_ends(const Launch& lc, const cplx* G, cplx* a_t0, cplx* a_0t, cplx* b_t0, cplx* b_0t, cplx* gtt, int ng);
 size_t measure_td_doubles(int L, int n);
@@ -268,8 +268,9 @@ bool launch_td_matsubara(const Launch& lc, const DevModel& hm, const double* acc
                          double* out, double* bad, size_t out_chain_stride = 0);
 bool td_matsubara_fits(const DevModel& hm, int channel, int nfreq);     // what launch_td_matsubara would return, nothing launched
 // measurement series (dqmc_series_*): sample / open / closed / bad are plain device arrays, chain b of an [nb][S] array at b * S
-bool launch_series_eq_sample(const Launch& lc, const DevModel& hm, const double* eqacc, size_t eq_n, const double* trig, double* sample,
-                             size_t S, size_t off, double* bad);
+bool launch_series_eq_sample(const Launch& lc, const DevModel& hm, const double* eqacc, size_t eq_n, int nch, const double* trig, double* sample,
+                             size_t S, size_t off, double* bad);     // nch channels of the block count, X[nch][N] -> C_X [nch][N], S_X [nch][N]
+void launch_series_band_derived(const Launch& lc, const DevModel& hm, const double* bins, size_t S, int B, size_t off, double* value, double* err);
 size_t series_eq_sample_lds_bytes(int L);
 void launch_series_accum(const Launch& lc, const double* sample, double* open, double* closed, size_t n, int close, int bin_size);
 void launch_series_accum_routed(const Launch& lc, const double* const* src, double* open, double* closed, size_t S, int close, int bin_size);
@@ -315,6 +316,17 @@ void launch_measure_td_current(const Launch& lc, const DevModel& hm, const cplx*
 size_t measure_td_current_doubles(int N, int n);
 size_t measure_td_current_onebody_cplx(int N);
 size_t measure_td_current_bond_cplx(int N, int opdim);
+// band-resolved charge blocks (DQMC_TD_PH_BAND, dqmc_set_equal_time_band): the sums over B of Re W(B (+) d, B) for bandDiff [N] and bandMix [N].
+// Time-displaced: count[n-1], then the rows; gs, hs as for launch_measure_td_ph, ob = the one-body values [2][2][N] of launch_td_band_onebody.
+// Equal-time: count, bandDiff[N], bandMix[N] from the one shifted matrix gs; acc and the scratch ob [3][N] are plain device arrays outside
+// the arena, chain b at acc + b * measure_eq_band_doubles(N) and ob + b * measure_eq_band_onebody_cplx(N)
+void launch_td_band_onebody(const Launch& lc, const DevModel& hm, const cplx* gs, cplx* ob, int t);
+void launch_measure_td_band(const Launch& lc, const DevModel& hm, const cplx* gs, const cplx* hs, const cplx* ob, double* acc, int row, int rows);
+size_t measure_td_band_doubles(int N, int n);
+size_t measure_td_band_onebody_cplx(int N);
+void launch_measure_eq_band(const Launch& lc, const DevModel& hm, const cplx* gs, cplx* ob, double* acc);
+size_t measure_eq_band_doubles(int N);
+size_t measure_eq_band_onebody_cplx(int N);
 
 // ---- QR / UDT building blocks (kernels_qr.hip) ------------------------------------------------
 struct SvdProfHooks;

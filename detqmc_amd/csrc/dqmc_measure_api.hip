@@ -36,13 +36,15 @@ extern "C" int dqmc_shift_green_symmetric_host(dqmc_ctx* c, dqmc_cplx* out) {
     HIPCHK(copy_sync(c, out, selp(c, c->T1), (size_t)c->n_g * c->n_g * sizeof(cplx), hipMemcpyDeviceToHost));
     return DQMC_OK;
 }
-// zero fill of every block the context has: per chain inside the arena, the equal-time block ([chain][n], contiguous) in one call
+// zero fill of every block the context has: per chain inside the arena, the equal-time blocks ([chain][n], contiguous) in one call each
 static int acc_reset_all(dqmc_ctx* c) {
     for (int id = 0; id < ACC_EQ; ++id)
         for (int b = 0; c->acc[id].n && b < c->nb; ++b)
             HIPCHK(hipMemsetAsync(chainp(c, c->acc[id].p, b), 0, c->acc[id].n * sizeof(double), c->st));
-    const AccBlock& eq = c->acc[ACC_EQ];
-    if (eq.n) HIPCHK(hipMemsetAsync(eq.p, 0, eq.n * (size_t)c->nb * sizeof(double), c->st));
+    for (int id = ACC_EQ; id < ACC_COUNT; ++id) {
+        const AccBlock& eq = c->acc[id];
+        if (eq.n) HIPCHK(hipMemsetAsync(eq.p, 0, eq.n * (size_t)c->nb * sizeof(double), c->st));
+    }
     return DQMC_OK;
 }
 // the selected chain's copy of block id, after everything enqueued so far
@@ -73,6 +75,7 @@ extern "C" int dqmc_measure_slice(dqmc_ctx* c) {
     shift_green_dev(c);
     { ProfScope ps(c, FAM_OTHER, 1); launch_measure_accum(c->lc, c->hm, c->T1, c->acc[ACC_SLICE].p); }
     if (c->eq_on) { ProfScope ps(c, FAM_OTHER, 2); launch_measure_eq_corr(c->lc, c->hm, c->T1, c->eq_ob, c->acc[ACC_EQ].p); }   // same T1, no second shift
+    if (c->eqb_on) { ProfScope ps(c, FAM_OTHER, 2); launch_measure_eq_band(c->lc, c->hm, c->T1, c->eqb_ob, c->acc[ACC_EQ_BAND].p); }
     return finish(c, "dqmc_measure_slice");
 }
 extern "C" size_t dqmc_measure_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_SLICE); }
@@ -96,6 +99,25 @@ extern "C" int dqmc_set_equal_time_correlators(dqmc_ctx* c, int on) {
 }
 extern "C" size_t dqmc_measure_eq_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_EQ); }
 extern "C" int dqmc_measure_eq_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_EQ, out); }
+// equal-time bandDiff / bandMix correlators (dqmc_hip.h): a second, independent switch of dqmc_measure_slice with a block of its own
+extern "C" int dqmc_set_equal_time_band(dqmc_ctx* c, int on) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (c->hm.hubbard) return fail(DQMC_EINVAL, "the equal-time band correlators belong to the SDW model");
+    AccBlock& eq = c->acc[ACC_EQ_BAND];
+    if (on && !eq.n) {
+        (void)hipSetDevice(c->p.device);
+        const size_t n = measure_eq_band_doubles(c->N), nob = measure_eq_band_onebody_cplx(c->N);
+        if (const int rc = salloc(c, &eq.p, n * (size_t)c->nb)) return rc;
+        if (const int rc = salloc(c, &c->eqb_ob, nob * (size_t)c->nb)) return rc;
+        HIPCHK(hipMemsetAsync(eq.p, 0, n * (size_t)c->nb * sizeof(double), c->st));
+        HIPCHK(hipMemsetAsync(c->eqb_ob, 0, nob * (size_t)c->nb * sizeof(cplx), c->st));
+        eq.n = n; eq.stride = n * sizeof(double);
+    }
+    c->eqb_on = on != 0;
+    return DQMC_OK;
+}
+extern "C" size_t dqmc_measure_eq_band_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_EQ_BAND); }
+extern "C" int dqmc_measure_eq_band_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_EQ_BAND, out); }
 
 // ---------------------------------------------------------------------------------------------
 // time-displaced Green's functions (dqmc_hip.h; computed inside green_from_udv while td_on)
@@ -119,19 +141,20 @@ extern "C" int dqmc_get_green_timedisplaced_host(dqmc_ctx* c, dqmc_cplx* g_t0, d
     return DQMC_OK;
 }
 // ---- the channel kernels: coarse boundaries and every time slice (DQMC_TD_EVERY_SLICE) ---------------------------------------------
-enum { CH_G = 1, CH_PAIR = 2, CH_PH = 4, CH_CUR = 8, CH_TWO_BODY = CH_PH | CH_CUR };     // bit ch of a channel mask
-// One-body values of an equal-time matrix for the masked particle-hole / current kernels (t = 0: tau side, 1: 0 side): one shift of g,
+enum { CH_G = 1, CH_PAIR = 2, CH_PH = 4, CH_CUR = 8, CH_BAND = 16, CH_TWO_BODY = CH_PH | CH_CUR | CH_BAND };     // bit ch of a channel mask
+// One-body values of an equal-time matrix for the masked particle-hole / current / band kernels (t = 0: tau side, 1: 0 side): one shift of g,
 // then each masked table.  g == nullptr: T1 still holds the shifted matrix of the call before.
 static void td_onebody(dqmc_ctx* c, unsigned mask, const cplx* g, int t) {
     if (!(mask & CH_TWO_BODY)) return;
     if (g) shift_green_dev(c, g);
     if (mask & CH_PH) { ProfScope ps(c, FAM_OTHER, 1); launch_td_ph_onebody(c->lc, c->hm, c->T1, c->ph_ob, t); }
     if (mask & CH_CUR) { ProfScope ps(c, FAM_OTHER, 1); launch_td_current_onebody(c->lc, c->hm, c->T1, c->cur_bt, c->cur_ob, t); }
+    if (mask & CH_BAND) { ProfScope ps(c, FAM_OTHER, 1); launch_td_band_onebody(c->lc, c->hm, c->T1, c->band_ob, t); }
 }
 // The one place that launches the channel kernels: row `row` of `rows` of the masked channels' blocks (channel ch: acc[first + ch]) from
 // (gt0, g0t, gtt, g00) = (G(tau,0), G(0,tau), G(tau), G(0)).  Every shifted matrix is prepared once and handed to all masked kernels:
 // shifted gtt / g00 -> one-body values of the tau / 0 side (nullptr: already there), (shifted g0t)^H -> ph_H, shifted gt0 -> T1.  Only the
-// particle-hole and current channels need the first three.  T1 is scratch of many other calls, so nothing is carried between calls.
+// particle-hole, current and band channels need the first three.  T1 is scratch of many other calls, so nothing is carried between calls.
 static void td_row(dqmc_ctx* c, unsigned mask, int first, int row, int rows, const cplx* gt0, const cplx* g0t, const cplx* gtt, const cplx* g00) {
     if (gtt) td_onebody(c, mask, gtt, 0);
     if (g00) td_onebody(c, mask, g00, 1);
@@ -147,6 +170,7 @@ static void td_row(dqmc_ctx* c, unsigned mask, int first, int row, int rows, con
         ProfScope ps(c, FAM_OTHER, 1);
         launch_measure_td_current(c->lc, c->hm, c->T1, c->ph_H, c->cur_bt, c->cur_ob, c->acc[first + 3].p, row, rows);
     }
+    if (mask & CH_BAND) { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td_band(c->lc, c->hm, c->T1, c->ph_H, c->band_ob, c->acc[first + 4].p, row, rows); }
 }
 // what every entry that works at boundary j asks for; need_current_G: the entry also reads G, which must still be G(tau_j)
 static int td_boundary_ok(dqmc_ctx* c, int j, bool need_current_G) {
@@ -157,8 +181,8 @@ static int td_boundary_ok(dqmc_ctx* c, int j, bool need_current_G) {
     G_FRESH(c, "time-displaced measurement");
     return DQMC_OK;
 }
-// Row j - 1 of n - 1 of one coarse block, channel ch: G(k, tau) bins, pairing (neither reads G), particle-hole, current (both of the
-// boundary the context stands on).  Each call prepares its shifted matrices itself, so the four stand on their own in any order.
+// Row j - 1 of n - 1 of one coarse block, channel ch: G(k, tau) bins, pairing (neither reads G), particle-hole, current, band (all three
+// of the boundary the context stands on).  Each call prepares its shifted matrices itself, so the five stand on their own in any order.
 static int td_coarse(dqmc_ctx* c, int ch, int j, const char* entry) {
     if (!c) return fail(DQMC_EINVAL, "null ctx");
     if (!c->acc[ACC_TD + ch].n) return fail(DQMC_EINVAL, c->acc[ACC_TD + ch].missing);
@@ -171,6 +195,7 @@ extern "C" int dqmc_measure_timedisplaced(dqmc_ctx* c, int j) { return td_coarse
 extern "C" int dqmc_measure_timedisplaced_pair(dqmc_ctx* c, int j) { return td_coarse(c, 1, j, "dqmc_measure_timedisplaced_pair"); }
 extern "C" int dqmc_measure_timedisplaced_ph(dqmc_ctx* c, int j) { return td_coarse(c, 2, j, "dqmc_measure_timedisplaced_ph"); }
 extern "C" int dqmc_measure_timedisplaced_current(dqmc_ctx* c, int j) { return td_coarse(c, 3, j, "dqmc_measure_timedisplaced_current"); }
+extern "C" int dqmc_measure_timedisplaced_band(dqmc_ctx* c, int j) { return td_coarse(c, 4, j, "dqmc_measure_timedisplaced_band"); }
 extern "C" size_t dqmc_measure_td_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_TD); }
 extern "C" int dqmc_measure_td_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_TD, out); }
 extern "C" size_t dqmc_measure_td_pair_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_TD_PAIR); }
@@ -179,6 +204,8 @@ extern "C" size_t dqmc_measure_td_ph_accum_size(dqmc_ctx* c) { return acc_size(c
 extern "C" int dqmc_measure_td_ph_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_TD_PH, out); }
 extern "C" size_t dqmc_measure_td_current_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_TD_CUR); }
 extern "C" int dqmc_measure_td_current_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_TD_CUR, out); }
+extern "C" size_t dqmc_measure_td_band_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_TD_BAND); }
+extern "C" int dqmc_measure_td_band_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_TD_BAND, out); }
 extern "C" int dqmc_get_green0_timedisplaced_host(dqmc_ctx* c, dqmc_cplx* g00, int* slice) {
     if (!c || !g00 || !slice) return fail(DQMC_EINVAL, "null argument");
     if (!c->G00) return fail(DQMC_EINVAL, "context created without dqmc_params::td_particle_hole");
@@ -192,10 +219,10 @@ extern "C" int dqmc_get_green0_timedisplaced_host(dqmc_ctx* c, dqmc_cplx* g00, i
 }
 
 // ---- every time slice (DQMC_TD_EVERY_SLICE) ----------------------------------------------------------------------------------
-static size_t td_fine_n(const dqmc_ctx* c, int channel) { return channel >= 0 && channel < 4 ? c->acc[ACC_FINE0 + channel].n : 0; }
+static size_t td_fine_n(const dqmc_ctx* c, int channel) { return channel >= 0 && channel < TD_CHANNELS ? c->acc[ACC_FINE0 + channel].n : 0; }
 static unsigned td_fine_mask(const dqmc_ctx* c) {
     unsigned mask = 0;
-    for (int ch = 0; ch < 4; ++ch) if (td_fine_n(c, ch)) mask |= 1u << ch;
+    for (int ch = 0; ch < TD_CHANNELS; ++ch) if (td_fine_n(c, ch)) mask |= 1u << ch;
     return mask;
 }
 // the work copies from slice k to k + 1 (dir > 0) or to k - 1 (dir < 0), fields as they are on the device now:
@@ -324,11 +351,12 @@ extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nf
     if (!c) return fail(DQMC_EINVAL, "null ctx");
     if (c->hm.hubbard) return fail(DQMC_EINVAL, "the measurement series belongs to the SDW model");
     if (c->ser.open) return fail(DQMC_EINVAL, "a measurement series is already open (dqmc_series_end)");
-    if (parts <= 0 || (parts & ~0x5f)) return fail(DQMC_EINVAL, "dqmc_series_begin: parts must be a non-empty mask of bits 0 .. 4 and 6");
+    if (parts <= 0 || (parts & ~0x1df)) return fail(DQMC_EINVAL, "dqmc_series_begin: parts must be a non-empty mask of bits 0 .. 4 and 6 .. 8");
     if (bin_size < 1) return fail(DQMC_EINVAL, "dqmc_series_begin: bin_size must be at least 1");
     if (max_bins < 2) return fail(DQMC_EINVAL, "dqmc_series_begin: max_bins must be at least 2");
     if ((parts & 1) && !c->acc[ACC_EQ].n) return fail(DQMC_EINVAL, "dqmc_series_begin: the equal-time block has never been enabled (dqmc_set_equal_time_correlators)");
-    if ((parts & 1) && series_eq_sample_lds_bytes(c->hm.L) > 152 * 1024)
+    if ((parts & DQMC_SERIES_EQ_BAND) && !c->acc[ACC_EQ_BAND].n) return fail(DQMC_EINVAL, "dqmc_series_begin: the equal-time band block has never been enabled (dqmc_set_equal_time_band)");
+    if ((parts & (1 | DQMC_SERIES_EQ_BAND)) && series_eq_sample_lds_bytes(c->hm.L) > 152 * 1024)
         return fail(DQMC_EINVAL, "dqmc_series_begin: the lattice is too large for the equal-time sample kernel's LDS");
     dqmc_ctx::Series s;
     const size_t N = (size_t)c->N;
@@ -346,7 +374,14 @@ extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nf
             return fail(DQMC_EINVAL, "dqmc_series_begin: the lattice is too large for the order-parameter sample kernel's LDS");
         s.off[6] = s.S; s.len[6] = (size_t)nfreq * N + 5; s.S += s.len[6];
     }
-    s.bin_size = bin_size; s.max_bins = max_bins; s.nfreq = (parts & (0x1e | DQMC_SERIES_PHI)) ? nfreq : 0; s.parts = parts;
+    if (parts & DQMC_SERIES_MATS_BAND) {                    // the new parts lie behind every part that existed before them
+        if (!c->td_fine || !td_fine_n(c, 4)) return fail(DQMC_EINVAL, "dqmc_series_begin: no every-slice block for a channel of the mask");
+        if (nfreq < 1 || nfreq > c->m) return fail(DQMC_EINVAL, "dqmc_series_begin: nfreq must be in 1..m");
+        if (!td_matsubara_fits(c->hm, 4, nfreq)) return fail(DQMC_EINVAL, "dqmc_series_begin: the lattice is too large for the Matsubara kernel's LDS");
+        s.off[7] = s.S; s.len[7] = (size_t)2 * nfreq * N * 2; s.S += s.len[7];
+    }
+    if (parts & DQMC_SERIES_EQ_BAND) { s.off[8] = s.S; s.len[8] = 4 * N; s.S += s.len[8]; }
+    s.bin_size = bin_size; s.max_bins = max_bins; s.nfreq = (parts & (0x1e | DQMC_SERIES_PHI | DQMC_SERIES_MATS_BAND)) ? nfreq : 0; s.parts = parts;
     (void)hipSetDevice(c->p.device);
     const size_t n = (size_t)c->nb * s.S, L = (size_t)c->hm.L;
     c->ser = s;                                             // from here on series_free releases what was allocated
@@ -355,7 +390,7 @@ extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nf
     if (e == hipSuccess) e = hipMalloc((void**)&r.sample, n * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&r.openbin, n * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&r.bins, (size_t)max_bins * n * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&r.bad, (size_t)5 * c->nb * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&r.bad, (size_t)7 * c->nb * sizeof(double));
     const size_t mt = (parts & DQMC_SERIES_PHI) ? (size_t)c->m : 0;     // the temporal table of the order-parameter part
     if (e == hipSuccess) e = hipMalloc((void**)&r.trig, 2 * (L + mt) * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&r.stat, (2 * n + (size_t)12 * c->nb) * sizeof(double));
@@ -363,7 +398,7 @@ extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nf
     if (e == hipSuccess) e = hipMemsetAsync(r.sample, 0, n * sizeof(double), c->st);
     if (e == hipSuccess) e = hipMemsetAsync(r.openbin, 0, n * sizeof(double), c->st);
     if (e == hipSuccess) e = hipMemsetAsync(r.bins, 0, (size_t)max_bins * n * sizeof(double), c->st);
-    if (e == hipSuccess) e = hipMemsetAsync(r.bad, 0, (size_t)5 * c->nb * sizeof(double), c->st);
+    if (e == hipSuccess) e = hipMemsetAsync(r.bad, 0, (size_t)7 * c->nb * sizeof(double), c->st);
     if (e == hipSuccess) {
         // cos / sin(2 pi j / L) as finishFermionic of the host layer forms them: the device's structure factors use the same values
         std::vector<double> trig(2 * (L + mt));
@@ -386,7 +421,7 @@ extern "C" int dqmc_series_end(dqmc_ctx* c) {
 extern "C" int dqmc_series_layout(dqmc_ctx* c, int part, size_t* offset, size_t* length) {
     if (!c || !offset || !length) return fail(DQMC_EINVAL, "null argument");
     if (!c->ser.open) return fail(DQMC_EINVAL, "no measurement series is open");
-    if (part < 0 || part > 6 || !(c->ser.parts & (1 << part))) return fail(DQMC_EINVAL, "dqmc_series_layout: the part is not in the series");
+    if (part < 0 || part > 8 || !(c->ser.parts & (1 << part))) return fail(DQMC_EINVAL, "dqmc_series_layout: the part is not in the series");
     *offset = c->ser.off[part]; *length = c->ser.len[part];
     return DQMC_OK;
 }
@@ -412,7 +447,7 @@ static int series_form_sample(dqmc_ctx* c, const char* entry) {
     {
         ProfScope ps(c, FAM_OTHER, 0);
         if (s.parts & 1) {
-            if (!launch_series_eq_sample(c->lc, c->hm, c->acc[ACC_EQ].p, c->acc[ACC_EQ].n, s.trig, s.sample, s.S, s.off[0], s.bad))
+            if (!launch_series_eq_sample(c->lc, c->hm, c->acc[ACC_EQ].p, c->acc[ACC_EQ].n, 5, s.trig, s.sample, s.S, s.off[0], s.bad))
                 return fail(DQMC_EINVAL, who + ": the lattice is too large for the equal-time sample kernel's LDS");
             ++nparts;
         }
@@ -423,6 +458,18 @@ static int series_form_sample(dqmc_ctx* c, const char* entry) {
                     return fail(DQMC_EINVAL, who + ": the lattice is too large for the Matsubara kernel's LDS");
                 ++nparts;
             }
+        if (s.parts & DQMC_SERIES_MATS_BAND) {
+            if (!launch_td_matsubara(c->lc, c->hm, c->acc[ACC_FINE0 + 4].p, 4, s.nfreq, ser_apbx(c), ser_apby(c), s.sample + s.off[7],
+                                     s.bad + (size_t)nparts * c->nb, s.S))
+                return fail(DQMC_EINVAL, who + ": the lattice is too large for the Matsubara kernel's LDS");
+            ++nparts;
+        }
+        if (s.parts & DQMC_SERIES_EQ_BAND) {
+            if (!launch_series_eq_sample(c->lc, c->hm, c->acc[ACC_EQ_BAND].p, c->acc[ACC_EQ_BAND].n, 2, s.trig, s.sample, s.S, s.off[8],
+                                         s.bad + (size_t)nparts * c->nb))
+                return fail(DQMC_EINVAL, who + ": the lattice is too large for the equal-time sample kernel's LDS");
+            ++nparts;
+        }
         c->fam_launches[FAM_OTHER] += (uint64_t)nparts;
         if (s.parts & DQMC_SERIES_PHI) {                    // after the other parts; no flag row: the field always exists
             if (!launch_series_phi_sample(c->lc, c->hm, s.trig, s.trig + 2 * (size_t)c->hm.L, s.nfreq, s.sample, s.S, s.off[6]))
@@ -559,6 +606,21 @@ extern "C" int dqmc_series_derived_host(dqmc_ctx* c, double* value, double* err)
                               (s.parts & 16) ? (long long)s.off[4] : -1, dv, dv + nd);
     }
     { const int rc = finish(c, "dqmc_series_derived_host"); if (rc != DQMC_OK) return rc; }
+    HIPCHK(copy_sync(c, value, dv, nd * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(c, err, dv + nd, nd * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+extern "C" int dqmc_series_band_derived_host(dqmc_ctx* c, double* value, double* err) {
+    if (!c || !value || !err) return fail(DQMC_EINVAL, "null argument");
+    const dqmc_ctx::Series& s = c->ser;
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (!(s.parts & DQMC_SERIES_EQ_BAND)) return fail(DQMC_EINVAL, "dqmc_series_band_derived_host: the series has no equal-time band part");
+    if (s.closed < 2) return fail(DQMC_EINVAL, "dqmc_series_band_derived_host: the jackknife needs at least two closed bins");
+    (void)hipSetDevice(c->p.device);
+    const size_t n = (size_t)c->nb * s.S, nd = (size_t)3 * c->nb;
+    double* dv = s.stat + 2 * n;                            // the result rows of dqmc_series_derived_host: the calls are synchronous
+    { ProfScope ps(c, FAM_OTHER, 1); launch_series_band_derived(c->lc, c->hm, s.bins, s.S, s.closed, s.off[8], dv, dv + nd); }
+    { const int rc = finish(c, "dqmc_series_band_derived_host"); if (rc != DQMC_OK) return rc; }
     HIPCHK(copy_sync(c, value, dv, nd * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHK(copy_sync(c, err, dv + nd, nd * sizeof(double), hipMemcpyDeviceToHost));
     return DQMC_OK;

@@ -27,6 +27,10 @@ static bool td_every_slice(const detsdw_params& p) { return (p.timeDisplacedMeas
 static bool td_fine_on_device(const detsdw_params& p) { return (p.timeDisplacedMeasurements & DETSDW_TD_FINE_ON_DEVICE) != 0; }
 // fermionMeasurements carries the switch in bit 0 and DETSDW_FM_EQ_CORRELATORS as a flag bit
 static bool eq_correlators(const detsdw_params& p) { return (p.fermionMeasurements & DETSDW_FM_EQ_CORRELATORS) != 0; }
+// ... and DETSDW_FM_EQ_BAND; timeDisplacedParticleHole carries the level (0 / 1 / 2) in its low bits and DETSDW_TD_PH_BAND as a flag bit
+static bool eq_band(const detsdw_params& p) { return (p.fermionMeasurements & DETSDW_FM_EQ_BAND) != 0; }
+static int ph_level(const detsdw_params& p) { return p.timeDisplacedParticleHole & ~DETSDW_TD_PH_BAND; }
+static bool td_band(const detsdw_params& p) { return (p.timeDisplacedParticleHole & DETSDW_TD_PH_BAND) != 0; }
 
 // field-wise comparison of two normalised parameter sets (struct padding is not the caller's business); everything but
 // the exchange parameter r, the device and -- unless seeds_too -- the RNG stream identity
@@ -119,14 +123,18 @@ void DetSDW::normalise(detsdw_params& p, int& bcv) {
         throw ParameterWrong("timeDisplacedEverySlice needs timeDisplacedMeasurements");
     if (td_fine_on_device(p) && !td_every_slice(p))
         throw ParameterWrong("timeDisplacedFineOnDevice needs timeDisplacedEverySlice");
-    if (p.fermionMeasurements & ~(1 | DETSDW_FM_EQ_CORRELATORS))
+    if (p.fermionMeasurements & ~(1 | DETSDW_FM_EQ_CORRELATORS | DETSDW_FM_EQ_BAND))
         throw ParameterWrong("Parameter fermionMeasurements has incorrect value");
     if (eq_correlators(p) && !(p.fermionMeasurements & 1))
         throw ParameterWrong("equalTimeCorrelators needs fermionMeasurements");
+    if (eq_band(p) && !eq_correlators(p))
+        throw ParameterWrong("bandCorrelators (DETSDW_FM_EQ_BAND) needs equalTimeCorrelators");
     if (p.timeDisplacedMeasurements && !p.fermionMeasurements)
         throw ParameterWrong("timeDisplacedMeasurements needs fermionMeasurements");
-    if (p.timeDisplacedParticleHole < 0 || p.timeDisplacedParticleHole > 2)
+    if (p.timeDisplacedParticleHole < 0 || ph_level(p) > 2)
         throw ParameterWrong("Parameter timeDisplacedParticleHole has incorrect value");
+    if (td_band(p) && !ph_level(p))
+        throw ParameterWrong("bandCorrelators (DETSDW_TD_PH_BAND) needs timeDisplacedParticleHole");
     if (p.timeDisplacedParticleHole && !p.timeDisplacedMeasurements)
         throw ParameterWrong("timeDisplacedParticleHole needs timeDisplacedMeasurements");
     // createReplica (detsdwopdim.cpp:75-79)
@@ -172,7 +180,7 @@ DetSDW::DetSDW(const detsdw_params* in, int nchains, int sub_batches) {
     kp.cb_none = p.cb_none ? 1 : 0;          // reference option checkerboard=false (DetSDW<CB_NONE, OPDIM>)
     kp.rng_window_per_site = uniformsPerSite();
     kp.timedisplaced = td_level(p) | (td_every_slice(p) ? DQMC_TD_EVERY_SLICE : 0);   // 1: G(tau_j, 0) and its bins, 2: and the pairing block
-    kp.td_particle_hole = p.timeDisplacedParticleHole;
+    kp.td_particle_hole = ph_level(p) | (td_band(p) ? DQMC_TD_PH_BAND : 0);
     // result-neutral execution choices.  The pipelined update pays only while few contexts share the GPU (with more of them the
     // contexts overlap each other instead): automatic here means at most two sub-batches.
     kp.tuning = p.tuning;
@@ -267,8 +275,9 @@ void DetSDW::measureTimeDisplaced(Group& g, int j) {
     if (!measuringTD_) return;
     check(dqmc_measure_timedisplaced(g.ctx, j), "measureTimeDisplaced");
     if (td_level(ch_[0].pars) == 2) check(dqmc_measure_timedisplaced_pair(g.ctx, j), "measureTimeDisplacedPair");
-    if (ch_[0].pars.timeDisplacedParticleHole) check(dqmc_measure_timedisplaced_ph(g.ctx, j), "measureTimeDisplacedParticleHole");
-    if (ch_[0].pars.timeDisplacedParticleHole == 2) check(dqmc_measure_timedisplaced_current(g.ctx, j), "measureTimeDisplacedCurrent");
+    if (ph_level(ch_[0].pars)) check(dqmc_measure_timedisplaced_ph(g.ctx, j), "measureTimeDisplacedParticleHole");
+    if (ph_level(ch_[0].pars) == 2) check(dqmc_measure_timedisplaced_current(g.ctx, j), "measureTimeDisplacedCurrent");
+    if (td_band(ch_[0].pars)) check(dqmc_measure_timedisplaced_band(g.ctx, j), "measureTimeDisplacedBand");
     // every slice of the boundary's segment, in the boundary's own field configuration
     if (td_every_slice(ch_[0].pars)) check(dqmc_measure_timedisplaced_segment(g.ctx, j), "measureTimeDisplacedSegment");
 }
@@ -351,9 +360,12 @@ void DetSDW::sweep(bool takeMeasurements) {
     if (measuringTD_) for (auto& g : groups_) check(dqmc_set_timedisplaced(g.ctx, 1), "dqmc_set_timedisplaced");
     // the equal-time correlators ride on the measure(k) calls of measurement sweeps only: thermalisation sweeps launch nothing new
     const bool eq = fermionic && eq_correlators(ch_[0].pars);
+    const bool eqb = fermionic && eq_band(ch_[0].pars);
     if (eq) for (auto& g : groups_) check(dqmc_set_equal_time_correlators(g.ctx, 1), "dqmc_set_equal_time_correlators");
-    auto off = [this, eq]() {
+    if (eqb) for (auto& g : groups_) check(dqmc_set_equal_time_band(g.ctx, 1), "dqmc_set_equal_time_band");
+    auto off = [this, eq, eqb]() {
         if (eq) for (auto& g : groups_) (void)dqmc_set_equal_time_correlators(g.ctx, 0);
+        if (eqb) for (auto& g : groups_) (void)dqmc_set_equal_time_band(g.ctx, 0);
         measuring_ = false;
         if (measuringTD_) for (auto& g : groups_) (void)dqmc_set_timedisplaced(g.ctx, 0);
         measuringTD_ = false;
@@ -458,9 +470,17 @@ void DetSDW::finishFermionic(int b) {
         // separable: cos(qx dx + qy dy) = cos cos - sin sin, phases 2 pi (q d mod L) / L from two tables -- O(N L) per channel
         std::vector<double> ct(L), st(L), Ac((size_t)N), As((size_t)N);
         for (int j = 0; j < L; ++j) { ct[j] = std::cos(2.0 * pi * double(j) / double(L)); st[j] = std::sin(2.0 * pi * double(j) / double(L)); }
-        for (int ch = 0; ch < 5; ++ch) {
+        std::vector<double> eqb;
+        if (eq_band(c.pars)) {
+            eqb.resize(dqmc_measure_eq_band_accum_size(ctx_));
+            check(dqmc_measure_eq_band_read_host(ctx_, eqb.data()), "dqmc_measure_eq_band_read_host");
+            if ((int)eqb[0] != m) throw GeneralError(DQMC_EINVAL, "measurement sweep did not visit every time slice (equal-time band correlators)");
+        }
+        for (int ch = 0; ch < (eqb.empty() ? 5 : 7); ++ch) {     // 5, 6: bandDiff, bandMix from the block of their own
             c.eqCorr[ch].assign(N, 0.0); c.eqSq[ch].assign(N, 0.0);
-            for (int d = 0; d < N; ++d) c.eqCorr[ch][d] = eq[1 + (size_t)ch * N + d] / (double(N) * eq[0]);
+            const double* src = ch < 5 ? &eq[1 + (size_t)ch * N] : &eqb[1 + (size_t)(ch - 5) * N];
+            const double cnt = ch < 5 ? eq[0] : eqb[0];
+            for (int d = 0; d < N; ++d) c.eqCorr[ch][d] = src[d] / (double(N) * cnt);
             for (int dy = 0; dy < L; ++dy)
                 for (int qx = 0; qx < L; ++qx) {
                     double sc = 0.0, ss = 0.0;
@@ -486,10 +506,11 @@ void DetSDW::finishFermionic(int b) {
                                    : "measurement sweep did not visit every stabilisation boundary";
         // the coarse blocks' (size, read) entry points by channel; the fine blocks share one pair that takes the channel
         struct Coarse { size_t (*size)(dqmc_ctx*); int (*read)(dqmc_ctx*, double*); const char* name; };
-        static const Coarse coarse[4] = {{dqmc_measure_td_accum_size, dqmc_measure_td_read_host, "dqmc_measure_td_read_host"},
+        static const Coarse coarse[5] = {{dqmc_measure_td_accum_size, dqmc_measure_td_read_host, "dqmc_measure_td_read_host"},
                                          {dqmc_measure_td_pair_accum_size, dqmc_measure_td_pair_read_host, "dqmc_measure_td_pair_read_host"},
                                          {dqmc_measure_td_ph_accum_size, dqmc_measure_td_ph_read_host, "dqmc_measure_td_ph_read_host"},
-                                         {dqmc_measure_td_current_accum_size, dqmc_measure_td_current_read_host, "dqmc_measure_td_current_read_host"}};
+                                         {dqmc_measure_td_current_accum_size, dqmc_measure_td_current_read_host, "dqmc_measure_td_current_read_host"},
+                                         {dqmc_measure_td_band_accum_size, dqmc_measure_td_band_read_host, "dqmc_measure_td_band_read_host"}};
         auto read = [&](int channel, std::vector<double>& buf) {
             buf.resize(fine ? dqmc_measure_td_fine_accum_size(ctx_, channel) : coarse[channel].size(ctx_));
             if (fine) check(dqmc_measure_td_fine_read_host(ctx_, channel, buf.data()), "dqmc_measure_td_fine_read_host");
@@ -550,7 +571,7 @@ void DetSDW::finishFermionic(int b) {
             }
         }
         // particle-hole correlators (charge, spinZ, sdw): the same normalisation
-        if (c.pars.timeDisplacedParticleHole) {
+        if (ph_level(c.pars)) {
             std::vector<double> tp;
             read(2, tp);
             for (int ch = 0; ch < 3; ++ch) { t.phTau[ch].assign((size_t)rows * N, 0.0); t.phTauQ0[ch].assign(rows, 0.0); }
@@ -570,7 +591,7 @@ void DetSDW::finishFermionic(int b) {
             }
         }
         // current-current correlators and the bond kinetic energy: the same normalisation
-        if (c.pars.timeDisplacedParticleHole == 2) {
+        if (ph_level(c.pars) == 2) {
             std::vector<double> tc;
             read(3, tc);
             for (int mu = 0; mu < 2; ++mu) {
@@ -589,6 +610,26 @@ void DetSDW::finishFermionic(int b) {
                     }
                     t.currentTauQ0[mu][r] = q;
                     t.bondKinetic[mu][r] = blk[2 * (size_t)N + mu] / (double(N) * cnt);
+                }
+            }
+        }
+        // band-resolved charge correlators (bandDiff, bandMix): the normalisation of the particle-hole channels
+        if (td_band(c.pars)) {
+            std::vector<double> tb;
+            read(4, tb);
+            for (int ch = 0; ch < 2; ++ch) { t.bandTau[ch].assign((size_t)rows * N, 0.0); t.bandTauQ0[ch].assign(rows, 0.0); }
+            for (int r = 0; r < rows; ++r) {
+                const double cnt = tb[r];
+                if (cnt < 1.0) throw GeneralError(DQMC_EINVAL, missing);
+                for (int ch = 0; ch < 2; ++ch) {
+                    const double* T = &tb[rows + ((size_t)r * 2 + ch) * N];
+                    double q = 0.0;
+                    for (int d = 0; d < N; ++d) {
+                        const double v = T[d] / (double(N) * cnt);
+                        t.bandTau[ch][(size_t)r * N + d] = v;
+                        q += v;
+                    }
+                    t.bandTauQ0[ch][r] = q;
                 }
             }
         }
@@ -612,7 +653,8 @@ void DetSDW::getObservableVector(int which_in, double* out, int b) const {
     if (!c.obs.fermionic_valid) throw GeneralError(DQMC_EINVAL, "no fermionic measurement has been taken");
     const bool fine = (which_in & DETSDW_OBS_FINE) != 0;
     const int which = which_in & ~DETSDW_OBS_FINE;
-    if (fine && (which < DETSDW_OBS_GREENKTAU_X || which > DETSDW_OBS_BONDKINETICY)) throw ParameterWrong("unknown observable vector");
+    const bool bandTau = which >= DETSDW_OBS_BANDDIFFTAU && which <= DETSDW_OBS_BANDMIXTAU_Q0;
+    if (fine && (which < DETSDW_OBS_GREENKTAU_X || which > DETSDW_OBS_BONDKINETICY) && !bandTau) throw ParameterWrong("unknown observable vector");
     if (fine && !td_every_slice(c.pars)) throw ParameterWrong("the ...Fine observables need timeDisplacedEverySlice");
     if (fine && td_fine_on_device(c.pars))
         throw ParameterWrong("the ...Fine observables are not formed with timeDisplacedFineOnDevice: read the Matsubara transforms");
@@ -626,6 +668,14 @@ void DetSDW::getObservableVector(int which_in, double* out, int b) const {
         std::memcpy(out, e.data(), e.size() * sizeof(double));
         return;
     }
+    if (!fine && which >= DETSDW_OBS_BANDDIFFCORR && which <= DETSDW_OBS_BANDMIXSQ) {
+        if (!eq_band(c.pars)) throw ParameterWrong("bandDiffCorr / bandMixCorr / bandDiffSq / bandMixSq need bandCorrelators with equalTimeCorrelators (DETSDW_FM_EQ_BAND)");
+        if (seriesNoHostCopy())
+            throw ParameterWrong("the equal-time correlators are not copied to the host while a series with DETSDW_SERIES_NO_HOST_COPY is open: read the series");
+        const std::vector<double>& e = which < DETSDW_OBS_BANDDIFFSQ ? c.eqCorr[5 + which - DETSDW_OBS_BANDDIFFCORR] : c.eqSq[5 + which - DETSDW_OBS_BANDDIFFSQ];
+        std::memcpy(out, e.data(), e.size() * sizeof(double));
+        return;
+    }
     const std::vector<double>* v = which == DETSDW_OBS_KOCCX ? &c.kOccX : which == DETSDW_OBS_KOCCY ? &c.kOccY
                                  : which == DETSDW_OBS_PAIRPLUS ? &c.pairPlus : which == DETSDW_OBS_PAIRMINUS ? &c.pairMinus
                                  : which == DETSDW_OBS_GREENKTAU_X ? &t.greenKTauX : which == DETSDW_OBS_GREENKTAU_Y ? &t.greenKTauY
@@ -636,16 +686,20 @@ void DetSDW::getObservableVector(int which_in, double* out, int b) const {
                                  : which == DETSDW_OBS_CURRENTXTAU || which == DETSDW_OBS_CURRENTYTAU ? &t.currentTau[which - DETSDW_OBS_CURRENTXTAU]
                                  : which == DETSDW_OBS_CURRENTXTAU_Q0 || which == DETSDW_OBS_CURRENTYTAU_Q0 ? &t.currentTauQ0[which - DETSDW_OBS_CURRENTXTAU_Q0]
                                  : which == DETSDW_OBS_BONDKINETICX || which == DETSDW_OBS_BONDKINETICY ? &t.bondKinetic[which - DETSDW_OBS_BONDKINETICX]
+                                 : which == DETSDW_OBS_BANDDIFFTAU || which == DETSDW_OBS_BANDMIXTAU ? &t.bandTau[which - DETSDW_OBS_BANDDIFFTAU]
+                                 : which == DETSDW_OBS_BANDDIFFTAU_Q0 || which == DETSDW_OBS_BANDMIXTAU_Q0 ? &t.bandTauQ0[which - DETSDW_OBS_BANDDIFFTAU_Q0]
                                  : nullptr;
     if (!v) throw ParameterWrong("unknown observable vector");
     if ((which == DETSDW_OBS_GREENKTAU_X || which == DETSDW_OBS_GREENKTAU_Y) && !td_level(c.pars))
         throw ParameterWrong("greenKTauX / greenKTauY need timeDisplacedMeasurements");
     if (which >= DETSDW_OBS_PAIRPLUSTAU && which <= DETSDW_OBS_PAIRMINUSTAU_Q0 && td_level(c.pars) != 2)
         throw ParameterWrong("pairPlusTau / pairMinusTau need timeDisplacedMeasurements = 2");
-    if (which >= DETSDW_OBS_CHARGETAU && which <= DETSDW_OBS_SDWTAU_Q0 && !c.pars.timeDisplacedParticleHole)
+    if (which >= DETSDW_OBS_CHARGETAU && which <= DETSDW_OBS_SDWTAU_Q0 && !ph_level(c.pars))
         throw ParameterWrong("chargeTau / spinZTau / sdwTau need timeDisplacedParticleHole");
-    if (which >= DETSDW_OBS_CURRENTXTAU && which <= DETSDW_OBS_BONDKINETICY && c.pars.timeDisplacedParticleHole != 2)
+    if (which >= DETSDW_OBS_CURRENTXTAU && which <= DETSDW_OBS_BONDKINETICY && ph_level(c.pars) != 2)
         throw ParameterWrong("currentXTau / currentYTau / bondKineticX / bondKineticY need timeDisplacedParticleHole = 2");
+    if (bandTau && !td_band(c.pars))
+        throw ParameterWrong("bandDiffTau / bandMixTau need bandCorrelators with timeDisplacedParticleHole (DETSDW_TD_PH_BAND)");
     std::memcpy(out, v->data(), v->size() * sizeof(double));
 }
 
@@ -654,7 +708,7 @@ void DetSDW::getObservableVector(int which_in, double* out, int b) const {
 // observables of all chains cost four calls per context.
 void DetSDW::invalidateMatsubara() {
     tdBlocksValid_ = false;
-    for (auto& g : groups_) for (int ch = 0; ch < 4; ++ch) g.matsNfreq[ch] = 0;
+    for (auto& g : groups_) for (int ch = 0; ch < 5; ++ch) g.matsNfreq[ch] = 0;
 }
 const double* DetSDW::matsubara(Group& g, int which, int nfreq, int& ncomp, int& comp) {
     const detsdw_params& p = ch_[0].pars;
@@ -663,12 +717,14 @@ const double* DetSDW::matsubara(Group& g, int which, int nfreq, int& ncomp, int&
     else if (which == DETSDW_OBS_PAIRPLUSTAU || which == DETSDW_OBS_PAIRMINUSTAU) { channel = 1; comp = which - DETSDW_OBS_PAIRPLUSTAU; }
     else if (which >= DETSDW_OBS_CHARGETAU && which <= DETSDW_OBS_SDWTAU) { channel = 2; comp = which - DETSDW_OBS_CHARGETAU; }
     else if (which == DETSDW_OBS_CURRENTXTAU || which == DETSDW_OBS_CURRENTYTAU) { channel = 3; comp = which - DETSDW_OBS_CURRENTXTAU; }
+    else if (which == DETSDW_OBS_BANDDIFFTAU || which == DETSDW_OBS_BANDMIXTAU) { channel = 4; comp = which - DETSDW_OBS_BANDDIFFTAU; }
     else throw ParameterWrong("no Matsubara transform of this observable");
     ncomp = channel == 2 ? 3 : 2;
     if (!td_every_slice(p)) throw ParameterWrong("the Matsubara transforms need timeDisplacedEverySlice");
     if (channel == 1 && td_level(p) != 2) throw ParameterWrong("pairPlusTau / pairMinusTau need timeDisplacedMeasurements = 2");
-    if (channel == 2 && !p.timeDisplacedParticleHole) throw ParameterWrong("chargeTau / spinZTau / sdwTau need timeDisplacedParticleHole");
-    if (channel == 3 && p.timeDisplacedParticleHole != 2) throw ParameterWrong("currentXTau / currentYTau need timeDisplacedParticleHole = 2");
+    if (channel == 2 && !ph_level(p)) throw ParameterWrong("chargeTau / spinZTau / sdwTau need timeDisplacedParticleHole");
+    if (channel == 3 && ph_level(p) != 2) throw ParameterWrong("currentXTau / currentYTau need timeDisplacedParticleHole = 2");
+    if (channel == 4 && !td_band(p)) throw ParameterWrong("bandDiffTau / bandMixTau need bandCorrelators with timeDisplacedParticleHole (DETSDW_TD_PH_BAND)");
     if (nfreq < 1 || nfreq > m_) throw ParameterWrong("nfreq must be in 1 .. m");
     if (!tdBlocksValid_) throw GeneralError(DQMC_EINVAL, "the Matsubara transforms are valid after a measurement sweep and until the next sweep");
     if (g.matsNfreq[channel] != nfreq) {
@@ -707,11 +763,13 @@ void DetSDW::seriesBegin(int binSize, int maxBins, int nfreq, int flags) {
     const bool blocks = !phi || (p.fermionMeasurements & 1);
     int parts = phi ? DQMC_SERIES_PHI : 0;
     if (blocks && eq_correlators(p)) parts |= DQMC_SERIES_EQ;
+    if (blocks && eq_band(p)) parts |= DQMC_SERIES_EQ_BAND;
     if (blocks && td_every_slice(p)) {
         parts |= DQMC_SERIES_MATS_G;
         if (td_level(p) == 2) parts |= DQMC_SERIES_MATS_PAIR;
-        if (p.timeDisplacedParticleHole) parts |= DQMC_SERIES_MATS_PH;
-        if (p.timeDisplacedParticleHole == 2) parts |= DQMC_SERIES_MATS_CURRENT;
+        if (ph_level(p)) parts |= DQMC_SERIES_MATS_PH;
+        if (ph_level(p) == 2) parts |= DQMC_SERIES_MATS_CURRENT;
+        if (td_band(p)) parts |= DQMC_SERIES_MATS_BAND;
     }
     if (!parts) throw ParameterWrong("a measurement series needs equalTimeCorrelators or timeDisplacedEverySlice");
     size_t opened = 0;
@@ -721,6 +779,10 @@ void DetSDW::seriesBegin(int binSize, int maxBins, int nfreq, int flags) {
                 check(dqmc_set_equal_time_correlators(g.ctx, 1), "dqmc_set_equal_time_correlators");
                 check(dqmc_set_equal_time_correlators(g.ctx, 0), "dqmc_set_equal_time_correlators");
             }
+            if (parts & DQMC_SERIES_EQ_BAND) {
+                check(dqmc_set_equal_time_band(g.ctx, 1), "dqmc_set_equal_time_band");
+                check(dqmc_set_equal_time_band(g.ctx, 0), "dqmc_set_equal_time_band");
+            }
             check(dqmc_series_begin(g.ctx, binSize, maxBins, nfreq, parts), "dqmc_series_begin");
             seriesDropCaches(g);
             ++opened;
@@ -729,7 +791,7 @@ void DetSDW::seriesBegin(int binSize, int maxBins, int nfreq, int flags) {
         for (size_t i = 0; i < opened; ++i) (void)dqmc_series_end(groups_[i].ctx);
         throw;
     }
-    series_.open = true; series_.binSize = binSize; series_.maxBins = maxBins; series_.nfreq = (parts & ~DQMC_SERIES_EQ) ? nfreq : 0;   // the phi part keeps nfreq too
+    series_.open = true; series_.binSize = binSize; series_.maxBins = maxBins; series_.nfreq = (parts & ~(DQMC_SERIES_EQ | DQMC_SERIES_EQ_BAND)) ? nfreq : 0;   // the phi part keeps nfreq too
     series_.parts = parts; series_.flags = flags;
     seriesRoute_.resize(ch_.size());
     std::iota(seriesRoute_.begin(), seriesRoute_.end(), 0);
@@ -770,6 +832,9 @@ void DetSDW::seriesSlice(int which, int& part, size_t& offset, size_t& length) {
     if (which >= DETSDW_OBS_CHARGECORR && which <= DETSDW_OBS_PAIRMINUSSQ) {
         if (!(series_.parts & DQMC_SERIES_EQ)) throw ParameterWrong("the equal-time part of the series needs equalTimeCorrelators");
         part = 0; length = (size_t)N_; sub = (size_t)(which - DETSDW_OBS_CHARGECORR) * N_;
+    } else if (which >= DETSDW_OBS_BANDDIFFCORR && which <= DETSDW_OBS_BANDMIXSQ) {
+        if (!(series_.parts & DQMC_SERIES_EQ_BAND)) throw ParameterWrong("the equal-time band part of the series needs bandCorrelators with equalTimeCorrelators");
+        part = 8; length = (size_t)N_; sub = (size_t)(which - DETSDW_OBS_BANDDIFFCORR) * N_;
     } else if (which == DETSDW_OBS_PHICHI || which == DETSDW_OBS_PHISCALARS) {
         if (!(series_.parts & DQMC_SERIES_PHI)) throw ParameterWrong("the series has no order-parameter part: detsdw_series_begin with DETSDW_SERIES_PHI");
         part = 6;
@@ -781,9 +846,10 @@ void DetSDW::seriesSlice(int which, int& part, size_t& offset, size_t& length) {
         else if (which == DETSDW_OBS_PAIRPLUSTAU || which == DETSDW_OBS_PAIRMINUSTAU) { channel = 1; comp = which - DETSDW_OBS_PAIRPLUSTAU; }
         else if (which >= DETSDW_OBS_CHARGETAU && which <= DETSDW_OBS_SDWTAU) { channel = 2; comp = which - DETSDW_OBS_CHARGETAU; }
         else if (which == DETSDW_OBS_CURRENTXTAU || which == DETSDW_OBS_CURRENTYTAU) { channel = 3; comp = which - DETSDW_OBS_CURRENTXTAU; }
+        else if (which == DETSDW_OBS_BANDDIFFTAU || which == DETSDW_OBS_BANDMIXTAU) { channel = 4; comp = which - DETSDW_OBS_BANDDIFFTAU; }
         else throw ParameterWrong("the measurement series does not hold this observable");
-        if (!(series_.parts & (2 << channel))) throw ParameterWrong("the series has no Matsubara part for this observable: the option it needs, or timeDisplacedEverySlice, is off");
-        part = 1 + channel; length = (size_t)series_.nfreq * N_ * 2; sub = (size_t)comp * length;
+        if (!(series_.parts & (channel == 4 ? DQMC_SERIES_MATS_BAND : (2 << channel)))) throw ParameterWrong("the series has no Matsubara part for this observable: the option it needs, or timeDisplacedEverySlice, is off");
+        part = channel == 4 ? 7 : 1 + channel; length = (size_t)series_.nfreq * N_ * 2; sub = (size_t)comp * length;
     }
     size_t off = 0, len = 0;
     check(dqmc_series_layout(groups_[0].ctx, part, &off, &len), "dqmc_series_layout");
@@ -833,6 +899,7 @@ void DetSDW::seriesDerivedAll(int what, double* value, double* err) {
         }
         return;
     }
+    if (what >= DETSDW_SERIES_R_DCDW && what <= DETSDW_SERIES_R_BANDMIX) { seriesBandDerived(what - DETSDW_SERIES_R_DCDW, value, err); return; }
     if (what < DETSDW_SERIES_R_CHARGE || what > DETSDW_SERIES_RHO_S) throw ParameterWrong("unknown derived quantity of the measurement series");
     if (what <= DETSDW_SERIES_R_PAIRMINUS && !(series_.parts & DQMC_SERIES_EQ)) throw ParameterWrong("the correlation ratios need equalTimeCorrelators");
     if (what == DETSDW_SERIES_RHO_S && !(series_.parts & DQMC_SERIES_MATS_CURRENT))
@@ -842,6 +909,18 @@ void DetSDW::seriesDerivedAll(int what, double* value, double* err) {
         v.resize((size_t)g.count * 6); e.resize((size_t)g.count * 6);
         check(dqmc_series_derived_host(g.ctx, v.data(), e.data()), "dqmc_series_derived_host");
         for (int b = 0; b < g.count; ++b) { value[g.first + b] = v[(size_t)b * 6 + what]; err[g.first + b] = e[(size_t)b * 6 + what]; }
+    }
+}
+// entry `at` (0 R_dCDW, 1 R_nematic, 2 R_bandMix) of dqmc_series_band_derived_host for every chain in handle order
+void DetSDW::seriesBandDerived(int at, double* value, double* err) {
+    if (!series_.open) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
+    if (at < 0 || at > 2) throw ParameterWrong("unknown derived quantity of the measurement series");
+    if (!(series_.parts & DQMC_SERIES_EQ_BAND)) throw ParameterWrong("R_dCDW / R_nematic / R_bandMix need bandCorrelators with equalTimeCorrelators");
+    std::vector<double> v, e;
+    for (auto& g : groups_) {
+        v.resize((size_t)g.count * 3); e.resize((size_t)g.count * 3);
+        check(dqmc_series_band_derived_host(g.ctx, v.data(), e.data()), "dqmc_series_band_derived_host");
+        for (int b = 0; b < g.count; ++b) { value[g.first + b] = v[(size_t)b * 3 + at]; err[g.first + b] = e[(size_t)b * 3 + at]; }
     }
 }
 void DetSDW::seriesReadBins(int which, int first, int count, double* out, int b) {
@@ -1524,6 +1603,10 @@ extern "C" int detsdw_series_stats_all(detsdw_replica* r, int which, double* mea
 extern "C" int detsdw_series_derived_all(detsdw_replica* r, int what, double* value, double* err) {
     if (!value || !err) { g_host_err = "null argument"; return DQMC_EINVAL; }
     RGUARD(r->impl->seriesDerivedAll(what, value, err))
+}
+extern "C" int detsdw_series_band_derived(detsdw_replica* r, int what, double* value, double* err) {
+    if (!value || !err) { g_host_err = "null argument"; return DQMC_EINVAL; }
+    RGUARD(r->impl->seriesBandDerived(what, value, err))
 }
 extern "C" int detsdw_series_read_bins(detsdw_replica* r, int which, int first, int count, double* out) {
     if (!out) { g_host_err = "null argument"; return DQMC_EINVAL; }

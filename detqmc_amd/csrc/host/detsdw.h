@@ -70,6 +70,7 @@ public:
     void seriesStats(int which, double* mean, double* err, int b = 0);
     void seriesStatsAll(int which, double* mean, double* err);
     void seriesDerivedAll(int what, double* value, double* err);
+    void seriesBandDerived(int at, double* value, double* err);
     void seriesReadBins(int which, int first, int count, double* out, int b = 0);
     // long runs: options, re-binning, binning analysis (err, tau [levels] x the slice of seriesStats; tau may be null), series file
     void seriesConfigure(int flags);
@@ -101,6 +102,7 @@ private:
         std::vector<double> pairPlusTauQ0, pairMinusTauQ0;  // rows: their row sums
         std::vector<double> phTau[3], phTauQ0[3];           // charge, spinZ, sdw: rows x N and the row sums (timeDisplacedParticleHole)
         std::vector<double> currentTau[2], currentTauQ0[2], bondKinetic[2];   // x, y: rows x N, row sums, rows (timeDisplacedParticleHole == 2)
+        std::vector<double> bandTau[2], bandTauQ0[2];       // bandDiff, bandMix: rows x N and the row sums (DETSDW_TD_PH_BAND)
     };
     struct Chain {
         detsdw_params pars;
@@ -115,7 +117,7 @@ private:
         double angleDelta = 0.0, scaleDelta = 0.1;          // AdjustmentData::InitialAngleDelta / InitialScaleDelta (detsdwopdim.h:490-491)
         detsdw_observables obs{};
         std::vector<double> kOccX, kOccY, pairPlus, pairMinus;
-        std::vector<double> eqCorr[5], eqSq[5];    // charge, spinZ, sdw, pairPlus, pairMinus: C(d) and S(q), N each (DETSDW_FM_EQ_CORRELATORS)
+        std::vector<double> eqCorr[7], eqSq[7];    // charge, spinZ, sdw, pairPlus, pairMinus: C(d) and S(q), N each (DETSDW_FM_EQ_CORRELATORS); 5, 6: bandDiff, bandMix (DETSDW_FM_EQ_BAND)
         TdObs td, tdFine;                      // rows = interior boundaries j = 1 .. n-1 / time slices k = 0 .. m (timeDisplacedEverySlice)
         Chain(const detsdw_params& p) : pars(p), rng(p.rngSeed, (uint32_t)p.simindex + 1u) {}   // detqmc.h:181
     };
@@ -125,8 +127,8 @@ private:
         int first = 0, count = 0;
         std::vector<double> window;                // uniforms of the coming sweep, all chains of the group
         std::vector<double> fields;                // host staging of all chains' fields (global moves)
-        std::vector<double> mats[4];               // Matsubara transforms of the group's chains per channel, [chain][component][nfreq][N] (re, im)
-        int matsNfreq[4] = {0, 0, 0, 0};           // ... and the nfreq they hold (0: none); cleared by every sweep
+        std::vector<double> mats[5];               // Matsubara transforms of the group's chains per channel, [chain][component][nfreq][N] (re, im)
+        int matsNfreq[5] = {0, 0, 0, 0, 0};          // ... and the nfreq they hold (0: none); cleared by every sweep
         std::vector<double> seriesMean, seriesErr; // dqmc_series_stats_host of the group's chains, [chain][S] each ...
         int seriesStatsBins = 0;                   // ... and the number of closed bins they were formed from (0: none)
         std::vector<double> seriesBinErr, seriesBinTau;   // dqmc_series_binning_host of the group's chains, [level][chain][S] each ...

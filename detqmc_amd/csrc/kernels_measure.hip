@@ -182,10 +182,10 @@ size_t measure_td_doubles(int L, int n) {
     const size_t nbins = (size_t)(2 * L - 1) * (2 * L - 1);
     return (size_t)(n - 1) * (1 + 4 * nbins);
 }
-// stride of one row of a time-displaced block: channel 0 G(k, tau) bins, 1 pairing, 2 particle-hole, 3 current
+// stride of one row of a time-displaced block: channel 0 G(k, tau) bins, 1 pairing, 2 particle-hole, 3 current, 4 band-resolved charge
 size_t measure_td_row_doubles(int channel, int N, int L) {
     const size_t nbins = (size_t)(2 * L - 1) * (2 * L - 1);
-    return channel == 0 ? 4 * nbins : channel == 1 ? 2 * (size_t)N : channel == 2 ? 3 * (size_t)N : 2 * (size_t)N + 2;
+    return channel == 0 ? 4 * nbins : channel == 2 ? 3 * (size_t)N : channel == 3 ? 2 * (size_t)N + 2 : 2 * (size_t)N;
 }
 
 template<int OPDIM>
@@ -754,6 +754,269 @@ void launch_measure_td_current(const Launch& lc, const DevModel& hm, const cplx*
     else hipLaunchKernelGGL((k_measure_td_current<3>), grid, block, 0, lc.st, hm, gs, hs, bt, ob, acc, row, rows, lc.cs);
 }
 
+// Band-resolved charge channels (dqmc_measure_timedisplaced_band, dqmc_set_equal_time_band; definitions in dqmc_hip.h and DESIGN.md 6e):
+// the W^M(A, B) of k_measure_td_ph for the two spin-singlet bilinears
+//   bandDiff  M_BAND = diag(+1, -1, +1, -1)                       n_x - n_y:  pi = identity, m = (+1, -1, +1, -1)
+//   bandMix   M_MIX:  (0,3) = (3,0) = (1,2) = (2,1) = +1          sum_s psi^+_xs psi_ys + h.c.:  pi = (3, 2, 1, 0), m = 1
+// in the one-entry-per-row form of that kernel, connected part sum_{a, c} m_a m_c gt0(A pi(a); B c) g0t(B pi(c); A a), and with the same
+// prepared operands gs = shifted G(tau, 0), hs = (shifted G(0, tau))^H.  tr M = 0 for both.
+// OPDIM < 3, with e_rc, h_rc and d_rc = Re e_rc conj h_rc of k_measure_td_ph:
+//   bandDiff is sector diagonal with the sign pattern (+, -) inside BOTH sectors, so the conjugate sector doubles the stored one:
+//     connected = 2 (d_00 + d_11 - d_01 - d_10)  (four times that of spinZ),   o = -2 Re (g_00 - g_11)  (spinZ: -i Im of the same number);
+//   bandMix couples the stored sector to its conjugate: M_MIX g has no diagonal block, o = 0 exactly (written, not computed), and every
+//   connected term takes one element of each sector -- e(A pi(a); B c) from the sector opposite to a, h(A a; B pi(c)) from a's own:
+//     a in the stored sector:     conj e_(1-a)(1-c) conj h_a c,     a in the conjugate sector:  e_(1-a)(1-c) h_a c      (same real part)
+//     connected = 2 Re (e_10 h_01 + e_11 h_00 + e_00 h_11 + e_01 h_10).
+//   The eight loads of k_measure_td_ph serve both sums; nothing is multiplied by a structural zero.
+// O(3): the sixteen e and sixteen h of the full blocks.  Shape, walk order, reduction and reproducibility: those of k_measure_td_ph.
+#define TDB_CH 2        // one-body values per site and time: bandDiff, bandMix
+size_t measure_td_band_doubles(int N, int n) { return (size_t)(n - 1) * (1 + 2 * (size_t)N); }
+size_t measure_td_band_onebody_cplx(int N) { return (size_t)2 * TDB_CH * N; }
+
+// the two one-body values of site A from the shifted equal-time matrix gs
+template<int OPDIM>
+__device__ __forceinline__ void band_onebody(const cplx* __restrict__ gs, int ng, int N, int A, cplx& ob, cplx& om) {
+    const cplx* p = gs + (size_t)A * ng + A;                // g(r, c) = gs(A r; A c) = p[c N ng + r N]
+    const size_t cN = (size_t)N * ng;
+    if (OPDIM == 3) {
+        const cplx v = m_add(m_sub(p[0], p[cN + N]), m_sub(p[2 * cN + 2 * N], p[3 * cN + 3 * N]));
+        ob = make_double2(-v.x, -v.y);
+        const cplx w = m_add(m_add(p[3 * N], p[3 * cN]), m_add(p[cN + 2 * N], p[2 * cN + N]));      // g(3,0) + g(0,3) + g(2,1) + g(1,2)
+        om = make_double2(-w.x, -w.y);
+    } else {
+        ob = make_double2(-2.0 * (p[0].x - p[cN + N].x), 0.0);
+        om = make_double2(0.0, 0.0);
+    }
+}
+
+// ob[t][bandDiff, bandMix][site] for one of the two equal-time matrices (t = 0: G(tau), t = 1: G(0)); gs is its shifted form
+template<int OPDIM>
+__global__ __launch_bounds__(256) void k_td_band_onebody(DevModel dm, const cplx* __restrict__ gs, cplx* __restrict__ ob, int t, size_t cs) {
+    CHAIN(gs); CHAIN(ob);
+    const int N = dm.N, A = blockIdx.x * 256 + threadIdx.x;
+    if (A >= N) return;
+    cplx vb, vm;
+    band_onebody<OPDIM>(gs, dm.ng, N, A, vb, vm);
+    cplx* o = ob + (size_t)t * TDB_CH * N + A;
+    o[0] = vb;
+    o[(size_t)N] = vm;
+}
+
+template<int OPDIM>
+__global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_td_band(DevModel dm, const cplx* __restrict__ gs, const cplx* __restrict__ hs,
+                                                                          const cplx* __restrict__ ob, double* __restrict__ acc, int row, int rows, size_t cs) {
+    CHAIN(gs); CHAIN(hs); CHAIN(ob); CHAIN(acc);
+    __shared__ double red[TDB_CH][TDP_PARTS][TDP_BINS];
+    const int N = dm.N, L = dm.L, tid = threadIdx.x;
+    const size_t ng = (size_t)dm.ng;
+    const int lb = tid % TDP_BINS, part = tid / TDP_BINS;
+    const int d = blockIdx.x * TDP_BINS + lb;
+    const bool valid = d < N;
+    const int dx = valid ? d % L : 0, dy = valid ? d / L : 0;
+    const cplx* ot = ob;                                    // o_tau(A)
+    const cplx* o0 = ob + (size_t)TDB_CH * N;               // o_0(B)
+    auto rd = [](cplx a, cplx b) { return a.x * b.x + a.y * b.y; };       // Re a conj b
+    auto re_mul = [](cplx a, cplx b) { return a.x * b.x - a.y * b.y; };   // Re a b
+    double wb = 0.0, wm = 0.0;
+    if (valid) {
+        int bx = part % L, by = part / L;                   // site B = part + 8 i, kept as (bx, by)
+        const int stepx = TDP_PARTS % L, stepy = TDP_PARTS / L;
+        for (int B = part; B < N; B += TDP_PARTS) {
+            int ax = bx + dx, ay = by + dy;
+            if (ax >= L) ax -= L;
+            if (ay >= L) ay -= L;
+            const int A = ay * L + ax;
+            const size_t off = (size_t)B * ng + (size_t)A;
+            const cplx* pe = gs + off;
+            const cplx* ph = hs + off;
+            double db, dmx, cb, cm;
+            if (OPDIM == 3) {
+                db = re_mul(ot[A], o0[B]);
+                dmx = re_mul(ot[N + A], o0[N + B]);
+                cplx e[4][4];
+#pragma unroll
+                for (int c2 = 0; c2 < 4; ++c2)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) e[r][c2] = pe[(size_t)c2 * N * ng + (size_t)r * N];
+                constexpr int pz[4] = {3, 2, 1, 0};
+                constexpr double sb[4] = {1.0, -1.0, 1.0, -1.0};
+                cb = 0.0; cm = 0.0;
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    cplx h[4];                                        // h[dl] = hs(A a; B dl)
+#pragma unroll
+                    for (int dl = 0; dl < 4; ++dl) h[dl] = ph[(size_t)dl * N * ng + (size_t)a * N];
+#pragma unroll
+                    for (int c2 = 0; c2 < 4; ++c2) {
+                        cb += sb[a] * sb[c2] * rd(e[a][c2], h[c2]);
+                        cm += rd(e[pz[a]][c2], h[pz[c2]]);
+                    }
+                }
+            } else {
+                db = ot[A].x * o0[B].x;                              // both real; the bandMix values are exact zeros
+                dmx = 0.0;
+                const size_t cN = (size_t)N * ng;
+                const cplx e00 = pe[0], e10 = pe[N], e01 = pe[cN], e11 = pe[cN + N];
+                const cplx h00 = ph[0], h10 = ph[N], h01 = ph[cN], h11 = ph[cN + N];
+                const double d00 = rd(e00, h00), d11 = rd(e11, h11), d01 = rd(e01, h01), d10 = rd(e10, h10);
+                cb = 2.0 * ((d00 + d11) - (d01 + d10));
+                cm = 2.0 * ((re_mul(e10, h01) + re_mul(e01, h10)) + (re_mul(e11, h00) + re_mul(e00, h11)));
+            }
+            wb += db - cb;
+            wm += dmx - cm;
+            bx += stepx; by += stepy;
+            if (bx >= L) { bx -= L; ++by; }
+        }
+    }
+    red[0][part][lb] = wb;
+    red[1][part][lb] = wm;
+    __syncthreads();
+    if (part < TDB_CH && valid) {                           // part 0 writes bandDiff of its bin, part 1 bandMix
+        double s = red[part][0][lb];
+#pragma unroll
+        for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
+        acc[rows + (size_t)row * TDB_CH * N + (size_t)part * N + d] += s;
+    }
+    if (blockIdx.x == 0 && tid == 0) acc[row] += 1.0;
+}
+
+void launch_td_band_onebody(const Launch& lc, const DevModel& hm, const cplx* gs, cplx* ob, int t) {
+    const dim3 grid((hm.N + 255) / 256, 1, lc.nb);
+    if (hm.opdim == 1) hipLaunchKernelGGL((k_td_band_onebody<1>), grid, dim3(256), 0, lc.st, hm, gs, ob, t, lc.cs);
+    else if (hm.opdim == 2) hipLaunchKernelGGL((k_td_band_onebody<2>), grid, dim3(256), 0, lc.st, hm, gs, ob, t, lc.cs);
+    else hipLaunchKernelGGL((k_td_band_onebody<3>), grid, dim3(256), 0, lc.st, hm, gs, ob, t, lc.cs);
+}
+
+void launch_measure_td_band(const Launch& lc, const DevModel& hm, const cplx* gs, const cplx* hs, const cplx* ob, double* acc, int row, int rows) {
+    const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
+    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_td_band<1>), grid, block, 0, lc.st, hm, gs, hs, ob, acc, row, rows, lc.cs);
+    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_td_band<2>), grid, block, 0, lc.st, hm, gs, hs, ob, acc, row, rows, lc.cs);
+    else hipLaunchKernelGGL((k_measure_td_band<3>), grid, block, 0, lc.st, hm, gs, hs, ob, acc, row, rows, lc.cs);
+}
+
+// Equal-time form (dqmc_set_equal_time_band): one matrix gs in both roles as in k_measure_eq_corr, the transposed factor read in place,
+// t_ac = gs[(A + N a) ng + B + N c] for conj hs(A a; B c): Re e conj h -> Re e t, and in the bandMix sum of OPDIM < 3, where the two
+// factors come from opposite sectors, Re e h -> Re e conj t.  M^2 = 1 for both matrices: the delta term tr_4 gs(B; B) goes to the d = 0
+// bin from the third one-body value.  ob[chain][bandDiff, bandMix, tr_4 gs][N]; block of one chain: count, bandDiff[N], bandMix[N], both
+// plain device arrays outside the arena.
+#define EQB_OB 3
+size_t measure_eq_band_doubles(int N) { return 1 + (size_t)TDB_CH * N; }
+size_t measure_eq_band_onebody_cplx(int N) { return (size_t)EQB_OB * N; }
+
+template<int OPDIM>
+__global__ __launch_bounds__(256) void k_eq_band_onebody(DevModel dm, const cplx* __restrict__ gs, cplx* __restrict__ ob, size_t cs) {
+    CHAIN(gs);
+    const int N = dm.N, A = blockIdx.x * 256 + threadIdx.x;
+    if (A >= N) return;
+    cplx vb, vm;
+    band_onebody<OPDIM>(gs, dm.ng, N, A, vb, vm);
+    const cplx* p = gs + (size_t)A * dm.ng + A;
+    const size_t cN = (size_t)N * dm.ng;
+    cplx tr;
+    if (OPDIM == 3) tr = m_add(m_add(p[0], p[cN + N]), m_add(p[2 * cN + 2 * N], p[3 * cN + 3 * N]));
+    else tr = make_double2(2.0 * (p[0].x + p[cN + N].x), 0.0);
+    cplx* o = ob + (size_t)blockIdx.z * EQB_OB * N + A;
+    o[0] = vb;
+    o[(size_t)N] = vm;
+    o[(size_t)2 * N] = tr;
+}
+
+template<int OPDIM>
+__global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_eq_band(DevModel dm, const cplx* __restrict__ gs, const cplx* __restrict__ ob,
+                                                                          double* __restrict__ acc, size_t cs) {
+    CHAIN(gs);
+    ob += (size_t)blockIdx.z * EQB_OB * dm.N;
+    acc += (size_t)blockIdx.z * (1 + (size_t)TDB_CH * dm.N);
+    __shared__ double red[TDB_CH][TDP_PARTS][TDP_BINS];
+    const int N = dm.N, L = dm.L, tid = threadIdx.x;
+    const size_t ng = (size_t)dm.ng;
+    const int lb = tid % TDP_BINS, part = tid / TDP_BINS;
+    const int d = blockIdx.x * TDP_BINS + lb;
+    const bool valid = d < N;
+    const int dx = valid ? d % L : 0, dy = valid ? d / L : 0;
+    auto rd = [](cplx a, cplx b) { return a.x * b.x + a.y * b.y; };       // Re a conj b
+    auto re_mul = [](cplx a, cplx b) { return a.x * b.x - a.y * b.y; };   // Re a b
+    double wb = 0.0, wm = 0.0;
+    if (valid) {
+        int bx = part % L, by = part / L;                   // site B = part + 8 i, kept as (bx, by)
+        const int stepx = TDP_PARTS % L, stepy = TDP_PARTS / L;
+        for (int B = part; B < N; B += TDP_PARTS) {
+            int ax = bx + dx, ay = by + dy;
+            if (ax >= L) ax -= L;
+            if (ay >= L) ay -= L;
+            const int A = ay * L + ax;
+            const cplx* pe = gs + (size_t)B * ng + (size_t)A;     // e_rc = gs(A + N r; B + N c) = pe[c N ng + r N]
+            const cplx* pt = gs + (size_t)A * ng + (size_t)B;     // t_rc = gs(B + N c; A + N r) = pt[r N ng + c N]
+            double db, dmx, cb, cm;
+            if (OPDIM == 3) {
+                db = re_mul(ob[A], ob[B]);
+                dmx = re_mul(ob[N + A], ob[N + B]);
+                cplx e[4][4];
+#pragma unroll
+                for (int c2 = 0; c2 < 4; ++c2)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) e[r][c2] = pe[(size_t)c2 * N * ng + (size_t)r * N];
+                constexpr int pz[4] = {3, 2, 1, 0};
+                constexpr double sb[4] = {1.0, -1.0, 1.0, -1.0};
+                cb = 0.0; cm = 0.0;
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    cplx t[4];                                        // t[dl] = gs(B dl; A a)
+#pragma unroll
+                    for (int dl = 0; dl < 4; ++dl) t[dl] = pt[(size_t)a * N * ng + (size_t)dl * N];
+#pragma unroll
+                    for (int c2 = 0; c2 < 4; ++c2) {
+                        cb += sb[a] * sb[c2] * re_mul(e[a][c2], t[c2]);
+                        cm += re_mul(e[pz[a]][c2], t[pz[c2]]);
+                    }
+                }
+            } else {
+                db = ob[A].x * ob[B].x;                              // both real; the bandMix values are exact zeros
+                dmx = 0.0;
+                const size_t cN = (size_t)N * ng;
+                const cplx e00 = pe[0], e10 = pe[N], e01 = pe[cN], e11 = pe[cN + N];
+                const cplx t00 = pt[0], t10 = pt[cN], t01 = pt[N], t11 = pt[cN + N];
+                const double d00 = re_mul(e00, t00), d11 = re_mul(e11, t11), d01 = re_mul(e01, t01), d10 = re_mul(e10, t10);
+                cb = 2.0 * ((d00 + d11) - (d01 + d10));
+                cm = 2.0 * ((rd(e10, t01) + rd(e01, t10)) + (rd(e11, t00) + rd(e00, t11)));
+            }
+            if (d == 0) {                                   // the delta term: tr_4 gs(B; B) for M^2 = 1
+                const double tr = ob[2 * N + B].x;
+                db += tr; dmx += tr;
+            }
+            wb += db - cb;
+            wm += dmx - cm;
+            bx += stepx; by += stepy;
+            if (bx >= L) { bx -= L; ++by; }
+        }
+    }
+    red[0][part][lb] = wb;
+    red[1][part][lb] = wm;
+    __syncthreads();
+    if (part < TDB_CH && valid) {                           // part 0 writes bandDiff of its bin, part 1 bandMix
+        double s = red[part][0][lb];
+#pragma unroll
+        for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
+        acc[1 + (size_t)part * N + d] += s;
+    }
+    if (blockIdx.x == 0 && tid == 0) acc[0] += 1.0;
+}
+
+void launch_measure_eq_band(const Launch& lc, const DevModel& hm, const cplx* gs, cplx* ob, double* acc) {
+    const dim3 g1((hm.N + 255) / 256, 1, lc.nb);
+    const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
+    if (hm.opdim == 1) {
+        hipLaunchKernelGGL((k_eq_band_onebody<1>), g1, dim3(256), 0, lc.st, hm, gs, ob, lc.cs);
+        hipLaunchKernelGGL((k_measure_eq_band<1>), grid, block, 0, lc.st, hm, gs, ob, acc, lc.cs);
+    } else if (hm.opdim == 2) {
+        hipLaunchKernelGGL((k_eq_band_onebody<2>), g1, dim3(256), 0, lc.st, hm, gs, ob, lc.cs);
+        hipLaunchKernelGGL((k_measure_eq_band<2>), grid, block, 0, lc.st, hm, gs, ob, acc, lc.cs);
+    } else {
+        hipLaunchKernelGGL((k_eq_band_onebody<3>), g1, dim3(256), 0, lc.st, hm, gs, ob, lc.cs);
+        hipLaunchKernelGGL((k_measure_eq_band<3>), grid, block, 0, lc.st, hm, gs, ob, acc, lc.cs);
+    }
+}
+
 // End rows of the every-slice blocks (dqmc_measure_timedisplaced_ends): from the equal-time G = G(0), one elementwise pass writes
 //   tau = 0+:    G(0+,0) = G,          G(0,0+) = G - 1          -> a_t0, a_0t
 //   tau = beta-: G(beta-,0) = 1 - G,   G(0,beta-) = -G          -> b_t0, b_0t
@@ -943,12 +1206,13 @@ bool launch_td_matsubara(const Launch& lc, const DevModel& hm, const double* acc
 // All buffers are plain device arrays outside the arena, chain b of a [nb][S] array at b * S.  Every kernel has one writer per output
 // element, a fixed summation order and no atomics; no element of one chain depends on another chain or on the number of chains.
 // ---------------------------------------------------------------------------------------------------------------------------------
-// Equal-time part of the sample: C_X(d) = sum / (N count) into out[X][d], S_X(q) = sum_d cos(q d) C_X(d) into out[5 + X][q], column
+// Equal-time part of the sample, for a block count, X[nch][N] (nch = 5: the equal-time correlators, 2: the band-resolved charge block):
+// C_X(d) = sum / (N count) into out[X][d], S_X(q) = sum_d cos(q d) C_X(d) into out[nch + X][q], column
 // qy L + qx.  One workgroup per (channel X, chain): C_X in LDS, then the separable cosine sum in the order of the host's finishFermionic --
 // over dx into (Ac, As)[dy][qx], then over dy -- with the phase index reduced mod L in integers and cos / sin(2 pi j / L) from the table
 // `trig` = (cos[L], sin[L]) the host computed.  bad[chain] = 1 if the block's count is < 1 (written by the workgroup of channel 0).
 size_t series_eq_sample_lds_bytes(int L) { return ((size_t)3 * L * L + 2 * (size_t)L) * sizeof(double); }
-__global__ __launch_bounds__(256) void k_series_eq_sample(const double* __restrict__ eqacc, size_t eq_n, const double* __restrict__ trig,
+__global__ __launch_bounds__(256) void k_series_eq_sample(const double* __restrict__ eqacc, size_t eq_n, int nch, const double* __restrict__ trig,
                                                           double* __restrict__ sample, size_t S, size_t off, double* __restrict__ bad, int L) {
     extern __shared__ double ses_sm[];
     const int tid = threadIdx.x, ch = blockIdx.x, N = L * L;
@@ -987,17 +1251,17 @@ __global__ __launch_bounds__(256) void k_series_eq_sample(const double* __restri
             const int j = (qy * dy) % L;
             sq += ct[j] * Ac[dy * L + qx] - st[j] * As[dy * L + qx];
         }
-        out[(size_t)(5 + ch) * N + q] = sq;
+        out[(size_t)(nch + ch) * N + q] = sq;
     }
 }
 // false: the lattice is too large for the kernel's LDS, nothing was launched
-bool launch_series_eq_sample(const Launch& lc, const DevModel& hm, const double* eqacc, size_t eq_n, const double* trig, double* sample,
+bool launch_series_eq_sample(const Launch& lc, const DevModel& hm, const double* eqacc, size_t eq_n, int nch, const double* trig, double* sample,
                              size_t S, size_t off, double* bad) {
     const size_t lds = series_eq_sample_lds_bytes(hm.L);
     if (lds > 152 * 1024) return false;
     if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)k_series_eq_sample, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         (void)hipGetLastError();
-    hipLaunchKernelGGL(k_series_eq_sample, dim3(5, 1, lc.nb), dim3(256), lds, lc.st, eqacc, eq_n, trig, sample, S, off, bad, hm.L);
+    hipLaunchKernelGGL(k_series_eq_sample, dim3(nch, 1, lc.nb), dim3(256), lds, lc.st, eqacc, eq_n, nch, trig, sample, S, off, bad, hm.L);
     return true;
 }
 
@@ -1107,6 +1371,47 @@ void launch_series_derived(const Launch& lc, const DevModel& hm, const double* b
                            long long off_cur, double* value, double* err) {
     SeriesDerivedShape a{off_eq, off_cur, hm.L, hm.N, nfreq, lc.nb, B, S};
     hipLaunchKernelGGL(k_series_derived, dim3((unsigned)((lc.nb * 6 + 63) / 64)), dim3(64), 0, lc.st, bins, a, value, err);
+}
+
+// The jackknife of k_series_derived over the equal-time band part, out[chain][3] (dqmc_hip.h): R = 1 - (S(Q + dx) + S(Q + dy)) / (2 S(Q)) for
+// 0: bandDiff at Q = (L/2, L/2), 1: bandDiff at Q = (0, 0), 2: bandMix at Q = (L/2, L/2).  off = offset of the part inside a sample,
+// S_X(q) at off + (2 + X) N.  One thread per (chain, entry).
+struct SeriesBandDerivedShape { size_t S, off; int L, N, nb, B; };
+__global__ __launch_bounds__(64) void k_series_band_derived(const double* __restrict__ bins, SeriesBandDerivedShape a, double* __restrict__ value,
+                                                            double* __restrict__ err) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= a.nb * 3) return;
+    const int chain = t / 3, e = t - chain * 3, L = a.L, N = a.N;
+    const int Q = e == 1 ? 0 : L / 2, q1 = (Q + 1) % L;
+    const size_t base = a.off + (size_t)(2 + (e == 2 ? 1 : 0)) * N;
+    const size_t idx[3] = {base + (size_t)Q * L + Q, base + (size_t)Q * L + q1, base + (size_t)q1 * L + Q};
+    const size_t n = (size_t)a.nb * a.S;
+    const double* p = bins + (size_t)chain * a.S;
+    const int B = a.B;
+    double mu[3], tot[3], x[3];
+    for (int j = 0; j < 3; ++j) {
+        double sum = 0.0;
+        for (int b = 0; b < B; ++b) sum += p[(size_t)b * n + idx[j]];
+        mu[j] = sum / (double)B; tot[j] = (double)B * mu[j];
+    }
+    double tsum = 0.0;
+    for (int b = 0; b < B; ++b) {
+        for (int j = 0; j < 3; ++j) x[j] = (tot[j] - p[(size_t)b * n + idx[j]]) / (double)(B - 1);
+        tsum += series_derived_f(0, x);
+    }
+    const double tbar = tsum / (double)B;
+    double acc = 0.0;
+    for (int b = 0; b < B; ++b) {
+        for (int j = 0; j < 3; ++j) x[j] = (tot[j] - p[(size_t)b * n + idx[j]]) / (double)(B - 1);
+        const double d = series_derived_f(0, x) - tbar;
+        acc += d * d;
+    }
+    value[t] = series_derived_f(0, mu);
+    err[t] = sqrt((double)(B - 1) / (double)B * acc);
+}
+void launch_series_band_derived(const Launch& lc, const DevModel& hm, const double* bins, size_t S, int B, size_t off, double* value, double* err) {
+    SeriesBandDerivedShape a{S, off, hm.L, hm.N, lc.nb, B};
+    hipLaunchKernelGGL(k_series_band_derived, dim3((unsigned)((lc.nb * 3 + 63) / 64)), dim3(64), 0, lc.st, bins, a, value, err);
 }
 
 // ---- the order-parameter part of the sample (DQMC_SERIES_PHI): chi_phi(q, i omega_n) and five scalars straight from the field ----

@@ -60,6 +60,8 @@ class SDWParams:
     timeDisplacedParticleHole: bool = False   # ... and the charge / spin-z / SDW correlators C(r, tau_j) (needs timeDisplacedMeasurements)
     timeDisplacedCurrent: bool = False        # ... and the current-current correlators Lambda_xx/yy(r, tau_j) (needs timeDisplacedParticleHole)
     timeDisplacedEverySlice: bool = False     # ... every enabled channel also on every slice tau_k = k dtau, k = 0 .. m: the '...Fine' observables (needs timeDisplacedMeasurements)
+    bandCorrelators: bool = False             # ... and the band-resolved charge channels bandDiff (n_x - n_y: nematic / d-wave CDW) and bandMix, time-displaced with
+                                              #     timeDisplacedParticleHole, equal-time with equalTimeCorrelators (needs at least one of the two)
     timeDisplacedFineOnDevice: bool = False   # ... whose blocks then stay on the device: no '...Fine' observables, matsubara() reads them (needs timeDisplacedEverySlice)
     globalUpdateInterval: int = 100
     phi2bosons: bool = False
@@ -84,12 +86,14 @@ class SDWParams:
 
 # observables with a Matsubara transform (DetSDW.matsubara): name -> index of detsdw_get_observable_vector
 MATSUBARA = {"greenKTauX": 4, "greenKTauY": 5, "pairPlusTau": 6, "pairMinusTau": 7, "chargeTau": 10, "spinZTau": 11, "sdwTau": 12,
-             "currentXTau": 16, "currentYTau": 17}
+             "currentXTau": 16, "currentYTau": 17, "bandDiffTau": 34, "bandMixTau": 35}
 
 
 # equal-time correlators and structure factors (SDWParams.equalTimeCorrelators): name -> index of detsdw_get_observable_vector
 EQ_CORRELATORS = {"chargeCorr": 22, "spinZCorr": 23, "sdwCorr": 24, "pairPlusCorr": 25, "pairMinusCorr": 26,
                   "chargeSq": 27, "spinZSq": 28, "sdwSq": 29, "pairPlusSq": 30, "pairMinusSq": 31}
+# ... of the band-resolved charge channels (SDWParams.bandCorrelators with equalTimeCorrelators), read and binned in a series like the above
+BAND_EQ_CORRELATORS = {"bandDiffCorr": 38, "bandMixCorr": 39, "bandDiffSq": 40, "bandMixSq": 41}
 
 
 def structure_factor(c, L):
@@ -115,11 +119,14 @@ def superfluid_stiffness(chi_xx, chi_yy, L):
 
 # derived quantities of a measurement series (DetSDWBatch.series_derived_all): name -> index of detsdw_series_derived_all
 SERIES_DERIVED = {"R_charge": 0, "R_spinZ": 1, "R_sdw": 2, "R_pairPlus": 3, "R_pairMinus": 4, "rhoS": 5,
-                  "binderPhi": 6, "binderRatioPhi": 7, "chiPhi": 8, "chiPhiConnected": 9, "R_phi": 10, "xiPhi": 11}
+                  "binderPhi": 6, "binderRatioPhi": 7, "chiPhi": 8, "chiPhiConnected": 9, "R_phi": 10, "xiPhi": 11,
+                  "R_dCDW": 12, "R_nematic": 13, "R_bandMix": 14}
 # parts of a kernel-level series (KernelContext.series_begin): bit 0 the equal-time block, bits 1 .. 4 the Matsubara transform of channel 0 .. 3,
 # bit 6 (part index 6 of series_layout) the order-parameter part: chi_phi [nfreq][N] and five scalars from the field itself
 SERIES_EQ, SERIES_MATS_G, SERIES_MATS_PAIR, SERIES_MATS_PH, SERIES_MATS_CURRENT = 1, 2, 4, 8, 16
 SERIES_PHI = 64
+# bit 7: the Matsubara transform of channel 4 (bandDiff, bandMix), bit 8: the equal-time band block, C_X(d) [2][N] then S_X(q) [2][N]
+SERIES_MATS_BAND, SERIES_EQ_BAND = 128, 256
 # the order-parameter part of a series opened with phi=True: name -> index of detsdw_series_stats (real, (nfreq, N) and (5,))
 SERIES_PHI_OBS = {"phiChi": 32, "phiScalars": 33}
 
@@ -213,13 +220,13 @@ class KernelContext:
                  lambda_=1.0, txhor=-1.0, txver=-0.5, tyhor=0.5, tyver=1.0, mux=-0.5, muy=-0.5,
                  accRatio=0.5, phi2bosons=False, device=0, stabilisation="svd", checkerboard=True, nchains=1, cdwU=0.0,
                  pipeline=0, qrVariant=0, greenVariant=0, maxJacobiSweeps=0, proposalBudget=0, rngWindowPerSite=0, decideThreads=0, bmultPath=0,
-                 timeDisplaced=False, tdParticleHole=False, tdCurrent=False, tdEverySlice=False):
+                 timeDisplaced=False, tdParticleHole=False, tdCurrent=False, tdEverySlice=False, tdBand=False):
         self.lib = load()
         p = _lib.dqmc_params(opdim=opdim, L=L, m=m, s=s, delaySteps=delaySteps, bc=BC[bc],
                              weakZflux=int(weakZflux), phi2bosons=int(phi2bosons), device=device,
                              stabilisation=STABILISATION[stabilisation], cb_none=int(not checkerboard), dtau=dtau, r=r, c=c, u=u, lambda_=lambda_, txhor=txhor, txver=txver,
                              tyhor=tyhor, tyver=tyver, mux=mux, muy=muy, accRatio=accRatio, cdwU=cdwU, rng_window_per_site=int(rngWindowPerSite),
-                             timedisplaced=int(timeDisplaced) | (_lib.DQMC_TD_EVERY_SLICE if tdEverySlice else 0), td_particle_hole=(2 if tdCurrent else int(tdParticleHole)),
+                             timedisplaced=int(timeDisplaced) | (_lib.DQMC_TD_EVERY_SLICE if tdEverySlice else 0), td_particle_hole=(2 if tdCurrent else int(tdParticleHole)) | (_lib.DQMC_TD_PH_BAND if tdBand else 0),
                              tuning=_tuning(pipeline, qrVariant, greenVariant, maxJacobiSweeps, proposalBudget, decideThreads, bmultPath))
         h = C.c_void_p()
         check(self.lib.dqmc_create_batch(C.byref(p), nchains, C.byref(h)))
@@ -287,6 +294,15 @@ class KernelContext:
         Re W(B (+) d, B), index dy L + dx; C(d) = sum / (count N)"""
         return self._read_block(self.lib.dqmc_measure_eq_accum_size, self.lib.dqmc_measure_eq_read_host)
 
+    def set_equal_time_band(self, on=True):
+        """while on, every measure_slice also bins the equal-time bandDiff / bandMix sums of the same shifted matrix into a block of their
+        own (SDW model only; the first enable allocates the block; independent of set_equal_time_correlators)"""
+        check(self.lib.dqmc_set_equal_time_band(self.h, int(on)))
+
+    def measure_eq_band_read(self):
+        """the selected chain's equal-time band block: [count, bandDiff[N], bandMix[N]], raw sums, index dy L + dx"""
+        return self._read_block(self.lib.dqmc_measure_eq_band_accum_size, self.lib.dqmc_measure_eq_band_read_host)
+
     def measure_timedisplaced(self, j):
         check(self.lib.dqmc_measure_timedisplaced(self.h, j))
 
@@ -327,6 +343,15 @@ class KernelContext:
         the two sums of Re o_tau[k_x], Re o_tau[k_y] over the sites"""
         return self._read_block(self.lib.dqmc_measure_td_current_accum_size, self.lib.dqmc_measure_td_current_read_host)
 
+    def measure_timedisplaced_band(self, j):
+        """bandDiff / bandMix correlators of boundary j from the four shifted Green's functions into their block (needs tdBand=True at
+        construction; call it right after the advance that ended on boundary j)"""
+        check(self.lib.dqmc_measure_timedisplaced_band(self.h, j))
+
+    def measure_td_band_read(self):
+        """count[n-1], then per boundary the N sums of Re W over the periodic site differences for bandDiff and bandMix"""
+        return self._read_block(self.lib.dqmc_measure_td_band_accum_size, self.lib.dqmc_measure_td_band_read_host)
+
     def measure_timedisplaced_segment(self, j):
         """every slice of boundary j's segment into the fine blocks, by propagation from the boundary's matrices (needs tdEverySlice=True at
         construction; call it right after the advance that ended on boundary j)"""
@@ -337,7 +362,7 @@ class KernelContext:
         check(self.lib.dqmc_measure_timedisplaced_ends(self.h))
 
     def measure_td_fine_read(self, channel):
-        """fine block of channel 0 (G(k, tau) bins), 1 (pairing), 2 (particle-hole), 3 (current): count[m+1], then rows k = 0 .. m"""
+        """fine block of channel 0 (G(k, tau) bins), 1 (pairing), 2 (particle-hole), 3 (current), 4 (band): count[m+1], then rows k = 0 .. m"""
         return self._read_block(self.lib.dqmc_measure_td_fine_accum_size, self.lib.dqmc_measure_td_fine_read_host, channel)
 
     def measure_td_matsubara(self, channel, nfreq):
@@ -384,7 +409,8 @@ class KernelContext:
         return a.value, b.value, s.value
 
     def series_layout(self, part):
-        """(offset, length) of part 0 (equal-time: C_X(d) [5][N], S_X(q) [5][N]) or 1 + channel (Matsubara, [component][nfreq][N] (re, im))"""
+        """(offset, length) of part 0 (equal-time: C_X(d) [5][N], S_X(q) [5][N]), 1 + channel (Matsubara, [component][nfreq][N] (re, im)), 6
+        (order parameter), 7 (Matsubara of the band channel) or 8 (equal-time band: C_X(d) [2][N], S_X(q) [2][N])"""
         off, ln = C.c_size_t(0), C.c_size_t(0)
         check(self.lib.dqmc_series_layout(self.h, int(part), C.byref(off), C.byref(ln)))
         return off.value, ln.value
@@ -409,6 +435,13 @@ class KernelContext:
         the part is not in the series"""
         v, e = np.zeros((self.nchains_total(), 6)), np.zeros((self.nchains_total(), 6))
         check(self.lib.dqmc_series_derived_host(self.h, v.ctypes.data_as(_lib._DP), e.ctypes.data_as(_lib._DP)))
+        return v, e
+
+    def series_band_derived(self):
+        """(value, err), (nchains, 3) each, of a series with SERIES_EQ_BAND: the jackknifed correlation ratios R_dCDW (bandDiff at (pi, pi)),
+        R_nematic (bandDiff at q = 0) and R_bandMix (bandMix at (pi, pi))"""
+        v, e = np.zeros((self.nchains_total(), 3)), np.zeros((self.nchains_total(), 3))
+        check(self.lib.dqmc_series_band_derived_host(self.h, v.ctypes.data_as(_lib._DP), e.ctypes.data_as(_lib._DP)))
         return v, e
 
     def series_phi_derived(self):
@@ -693,6 +726,10 @@ def _host_params(pars: SDWParams):
         raise ValueError("equalTimeCorrelators needs fermionMeasurements")
     if pars.timeDisplacedCurrent and not pars.timeDisplacedParticleHole:
         raise ValueError("timeDisplacedCurrent needs timeDisplacedParticleHole")
+    if pars.bandCorrelators and not (pars.timeDisplacedParticleHole or pars.equalTimeCorrelators):
+        raise ValueError("bandCorrelators needs timeDisplacedParticleHole or equalTimeCorrelators")
+    band_td = bool(pars.bandCorrelators and pars.timeDisplacedParticleHole)
+    band_eq = bool(pars.bandCorrelators and pars.equalTimeCorrelators)
     return _lib.detsdw_params(
         opdim=pars.opdim, L=pars.L, m=pars.m, s=pars.s, delaySteps=pars.delaySteps,
         globalShift=int(pars.globalShift), globalUpdateInterval=pars.globalUpdateInterval,
@@ -705,12 +742,13 @@ def _host_params(pars: SDWParams):
         mu=pars.mu, mux=pars.mux or 0.0, muy=pars.muy or 0.0, accRatio=pars.accRatio, cdwU=pars.cdwU,
         stabilisation=STABILISATION[pars.stabilisation], cb_none=int(not pars.checkerboard),
         wolffClusterUpdate=int(pars.wolffClusterUpdate), wolffClusterShiftUpdate=int(pars.wolffClusterShiftUpdate),
-        repeatWolffPerSweep=int(pars.repeatWolffPerSweep), fermionMeasurements=int(bool(pars.fermionMeasurements)) | (_lib.DETSDW_FM_EQ_CORRELATORS if pars.equalTimeCorrelators else 0),
+        repeatWolffPerSweep=int(pars.repeatWolffPerSweep), fermionMeasurements=int(bool(pars.fermionMeasurements)) | (_lib.DETSDW_FM_EQ_CORRELATORS if pars.equalTimeCorrelators else 0)
+        | (_lib.DETSDW_FM_EQ_BAND if band_eq else 0),
         spinProposalMethod=SPIN_PROPOSAL[pars.spinProposalMethod], adaptScaleVariance=int(pars.adaptScaleVariance),
         repeatUpdateInSlice=int(pars.repeatUpdateInSlice), timeDisplacedMeasurements=(2 if pars.timeDisplacedPairing else int(bool(pars.timeDisplacedMeasurements)))
         | (_lib.DETSDW_TD_EVERY_SLICE if pars.timeDisplacedEverySlice else 0)      # without timeDisplacedMeasurements: ParameterWrong from the library
         | (_lib.DETSDW_TD_FINE_ON_DEVICE if pars.timeDisplacedFineOnDevice else 0),  # without timeDisplacedEverySlice: the same
-        timeDisplacedParticleHole=(2 if pars.timeDisplacedCurrent else int(bool(pars.timeDisplacedParticleHole))),
+        timeDisplacedParticleHole=(2 if pars.timeDisplacedCurrent else int(bool(pars.timeDisplacedParticleHole))) | (_lib.DETSDW_TD_PH_BAND if band_td else 0),
         tuning=_tuning(pars.pipeline, pars.qrVariant, pars.greenVariant, pars.maxJacobiSweeps, pars.proposalBudget, pars.decideThreads, pars.bmultPath))
 
 
@@ -790,12 +828,15 @@ class DetSDW:
         'bondKineticXFine') with m+1 rows instead of n-1: row k = tau_k of tau_grid(fine=True), k = 0 .. m.  With equalTimeCorrelators:
         'chargeCorr', 'spinZCorr', 'sdwCorr', 'pairPlusCorr', 'pairMinusCorr' (length N, column = periodic site difference dy L + dx,
         averaged over the m slices of the sweep and over translations) and their structure factors 'chargeSq', 'spinZSq', 'sdwSq',
-        'pairPlusSq', 'pairMinusSq' (length N, column qy L + qx, q = 2 pi (qx, qy) / L; structure_factor of the former)"""
+        'pairPlusSq', 'pairMinusSq' (length N, column qy L + qx, q = 2 pi (qx, qy) / L; structure_factor of the former).  With
+        bandCorrelators: 'bandDiffTau', 'bandMixTau', 'bandDiffTauQ0', 'bandMixTauQ0' (and their 'Fine' twins) next to 'chargeTau', and
+        'bandDiffCorr', 'bandMixCorr', 'bandDiffSq', 'bandMixSq' next to 'chargeCorr' / 'chargeSq'"""
         self._sel()
         info = self.info
-        if name in EQ_CORRELATORS:
+        if name in EQ_CORRELATORS or name in BAND_EQ_CORRELATORS:
             out = np.zeros(info.N)
-            check(self.lib.detsdw_get_observable_vector(self.h, EQ_CORRELATORS[name], out.ctypes.data_as(_lib._DP)), host=True)
+            which = EQ_CORRELATORS.get(name, BAND_EQ_CORRELATORS.get(name))
+            check(self.lib.detsdw_get_observable_vector(self.h, which, out.ctypes.data_as(_lib._DP)), host=True)
             return out
         fine = name.endswith("Fine")
         if fine:
@@ -803,11 +844,12 @@ class DetSDW:
         which = {"kOccX": 0, "kOccY": 1, "pairPlus": 2, "pairMinus": 3, "greenKTauX": 4, "greenKTauY": 5,
                  "pairPlusTau": 6, "pairMinusTau": 7, "pairPlusTauQ0": 8, "pairMinusTauQ0": 9,
                  "chargeTau": 10, "spinZTau": 11, "sdwTau": 12, "chargeTauQ0": 13, "spinZTauQ0": 14, "sdwTauQ0": 15,
-                 "currentXTau": 16, "currentYTau": 17, "currentXTauQ0": 18, "currentYTauQ0": 19, "bondKineticX": 20, "bondKineticY": 21}[name]
+                 "currentXTau": 16, "currentYTau": 17, "currentXTauQ0": 18, "currentYTauQ0": 19, "bondKineticX": 20, "bondKineticY": 21,
+                 "bandDiffTau": 34, "bandMixTau": 35, "bandDiffTauQ0": 36, "bandMixTauQ0": 37}[name]
         if fine and which < 4:
             raise KeyError(name + "Fine")
         rows = info.m + 1 if fine else info.n - 1
-        out = np.zeros(info.N if which < 4 else (rows, info.N) if which < 8 or 10 <= which < 13 or 16 <= which < 18 else rows)
+        out = np.zeros(info.N if which < 4 else (rows, info.N) if which < 8 or 10 <= which < 13 or 16 <= which < 18 or 34 <= which < 36 else rows)
         check(self.lib.detsdw_get_observable_vector(self.h, which | (_lib.DETSDW_OBS_FINE if fine else 0), out.ctypes.data_as(_lib._DP)), host=True)
         return out
 
@@ -828,6 +870,8 @@ class DetSDW:
         info = self.info
         if name in EQ_CORRELATORS:
             return EQ_CORRELATORS[name], (info.N,), False
+        if name in BAND_EQ_CORRELATORS:
+            return BAND_EQ_CORRELATORS[name], (info.N,), False
         if name in SERIES_PHI_OBS:
             return SERIES_PHI_OBS[name], ((self._batch._series_nfreq, info.N) if name == "phiChi" else (5,)), False
         return MATSUBARA[name], (self._batch._series_nfreq, info.N), True

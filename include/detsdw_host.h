@@ -59,7 +59,10 @@ typedef struct detsdw_params {
                                          | DETSDW_FM_EQ_CORRELATORS (equalTimeCorrelators; needs bit 0, ParameterWrong otherwise): a
                                          measurement sweep also bins the equal-time charge, spin-z, SDW and pairing correlators on
                                          every one of its m slices (DETSDW_OBS_CHARGECORR .. _PAIRMINUSSQ).  The struct has no free
-                                         slot, so the option travels as a flag bit.  Any other bit: ParameterWrong */
+                                         slot, so the option travels as a flag bit.
+                                         | DETSDW_FM_EQ_BAND (bandCorrelators; needs DETSDW_FM_EQ_CORRELATORS, ParameterWrong otherwise):
+                                         and the equal-time bandDiff / bandMix correlators (DETSDW_OBS_BANDDIFFCORR .. _BANDMIXSQ).
+                                         Any other bit: ParameterWrong */
     int32_t spinProposalMethod;       /* 0 box (default), 1 rotate_then_scale, 2 rotate_and_scale -- the latter two for opdim == 3 only
                                          (src/detsdwparams.h:40-42, src/detsdwopdim.cpp:2447-2470) */
     int32_t adaptScaleVariance;       /* adapt scaleDelta during thermalization (src/detsdwparams.h:43) */
@@ -81,7 +84,11 @@ typedef struct detsdw_params {
                                          charge, spin-z and SDW order-parameter correlators (DETSDW_OBS_CHARGETAU .. _SDWTAU_Q0).  The
                                          field took the second reserved slot of dqmc_tuning: the bytes of the struct are where they were.
                                          2: also the current-current correlators and the bond kinetic energy (DETSDW_OBS_CURRENTXTAU ..
-                                         _BONDKINETICY).  Any other value: ParameterWrong */
+                                         _BONDKINETICY).
+                                         | DETSDW_TD_PH_BAND (bandCorrelators; needs a value >= 1, ParameterWrong otherwise): and the
+                                         band-resolved charge correlators bandDiff (n_x - n_y: nematic at q = 0, d-wave CDW at (pi, pi))
+                                         and bandMix (dqmc_measure_timedisplaced_band; DETSDW_OBS_BANDDIFFTAU .. _BANDMIXTAU_Q0).
+                                         Any other value, any other bit: ParameterWrong */
 } detsdw_params;
 
 typedef struct detsdw_info {
@@ -136,14 +143,20 @@ enum { DETSDW_OBS_KOCCX = 0, DETSDW_OBS_KOCCY = 1, DETSDW_OBS_PAIRPLUS = 2, DETS
        DETSDW_OBS_CHARGECORR = 22, DETSDW_OBS_SPINZCORR = 23, DETSDW_OBS_SDWCORR = 24, DETSDW_OBS_PAIRPLUSCORR = 25, DETSDW_OBS_PAIRMINUSCORR = 26,
        DETSDW_OBS_CHARGESQ = 27, DETSDW_OBS_SPINZSQ = 28, DETSDW_OBS_SDWSQ = 29, DETSDW_OBS_PAIRPLUSSQ = 30, DETSDW_OBS_PAIRMINUSSQ = 31,
        /* the order-parameter part of a measurement series only (detsdw_series_* below; detsdw_get_observable_vector refuses them) */
-       DETSDW_OBS_PHICHI = 32, DETSDW_OBS_PHISCALARS = 33 };
+       DETSDW_OBS_PHICHI = 32, DETSDW_OBS_PHISCALARS = 33,
+       /* bandCorrelators: the time-displaced ones have DETSDW_OBS_FINE twins and Matsubara transforms like chargeTau, the equal-time
+          ones are read and enter a series like chargeCorr / chargeSq */
+       DETSDW_OBS_BANDDIFFTAU = 34, DETSDW_OBS_BANDMIXTAU = 35, DETSDW_OBS_BANDDIFFTAU_Q0 = 36, DETSDW_OBS_BANDMIXTAU_Q0 = 37,
+       DETSDW_OBS_BANDDIFFCORR = 38, DETSDW_OBS_BANDMIXCORR = 39, DETSDW_OBS_BANDDIFFSQ = 40, DETSDW_OBS_BANDMIXSQ = 41 };
 /* equalTimeCorrelators: flag bit of detsdw_params::fermionMeasurements */
 enum { DETSDW_FM_EQ_CORRELATORS = 0x100 };
+/* bandCorrelators: DETSDW_FM_EQ_BAND is a flag bit of detsdw_params::fermionMeasurements, DETSDW_TD_PH_BAND one of ::timeDisplacedParticleHole */
+enum { DETSDW_FM_EQ_BAND = 0x200, DETSDW_TD_PH_BAND = 0x100 };
 /* timeDisplacedEverySlice: flag bit of detsdw_params::timeDisplacedMeasurements */
 enum { DETSDW_TD_EVERY_SLICE = 0x100 };
 /* timeDisplacedFineOnDevice: flag bit of detsdw_params::timeDisplacedMeasurements; never reaches dqmc_params::timedisplaced */
 enum { DETSDW_TD_FINE_ON_DEVICE = 0x200 };
-/* which | DETSDW_OBS_FINE for which = DETSDW_OBS_GREENKTAU_X .. _BONDKINETICY: the every-slice twin ("...Fine") of the observable, rows
+/* which | DETSDW_OBS_FINE for which = DETSDW_OBS_GREENKTAU_X .. _BONDKINETICY and DETSDW_OBS_BANDDIFFTAU .. _BANDMIXTAU_Q0: the every-slice twin ("...Fine") of the observable, rows
  * k = 0 .. m instead of j = 1 .. n-1, columns unchanged; needs timeDisplacedEverySlice next to the option its coarse twin needs */
 enum { DETSDW_OBS_FINE = 0x100 };    /* a bit of the observable index: unrelated to DETSDW_TD_EVERY_SLICE, a bit of a parameter */
 
@@ -193,7 +206,10 @@ int detsdw_get_observables(detsdw_replica* r, detsdw_observables* out);
  *   C_X(d) = (1 / (m N)) sum_{slices k = 1 .. m} sum_B Re W_X(B (+) d, B)   on g~ = e^{-dtau K/2} G(tau_k) e^{+dtau K/2} after the updates
  * of slice k (dqmc_set_equal_time_correlators, dqmc_hip.h: the Wick forms of the time-displaced channels with G(tau,0) -> g~,
  * G(0,tau) -> g~ - 1, and T+- on g~); chargeSq / spinZSq / sdwSq / pairPlusSq / pairMinusSq, N, column qy L + qx, q = 2 pi (qx, qy) / L:
- *   S_X(q) = sum_d cos(q d) C_X(d).   Values of ONE sweep; averages and error bars over sweeps: the measurement series below */
+ *   S_X(q) = sum_d cos(q d) C_X(d).   Values of ONE sweep; averages and error bars over sweeps: the measurement series below
+ * With DETSDW_TD_PH_BAND: bandDiffTau / bandMixTau, (n-1) x N, and bandDiffTauQ0 / bandMixTauQ0, n-1, rows, columns and normalisation of
+ * chargeTau, for the bilinears M_BAND / M_MIX of dqmc_measure_timedisplaced_band.  With DETSDW_FM_EQ_BAND: bandDiffCorr / bandMixCorr and
+ * bandDiffSq / bandMixSq, N, defined like chargeCorr / chargeSq (dqmc_set_equal_time_band) */
 int detsdw_get_observable_vector(detsdw_replica* r, int which, double* out);
 /* With timeDisplacedEverySlice: the Matsubara transforms of the every-slice observable `which`, formed on the device from the blocks
  * of the last measurement sweep (dqmc_measure_td_matsubara_host, dqmc_hip.h), n = 0 .. nfreq-1, 1 <= nfreq <= m, trapezoid weights
@@ -211,7 +227,8 @@ int detsdw_get_matsubara(detsdw_replica* r, int which, int nfreq, double* out);
 int detsdw_get_matsubara_all(detsdw_replica* r, int which, int nfreq, double* out);
 /* Measurement series: bins over measurement sweeps and jackknife errors, kept on the device (dqmc_series_*, dqmc_hip.h).
  * detsdw_series_begin opens one series per kernel context.  Its parts follow from the handle's options: the equal-time part with
- * equalTimeCorrelators, one Matsubara part (nfreq frequencies, 1 <= nfreq <= m) per enabled every-slice channel; nfreq is ignored
+ * equalTimeCorrelators (and the equal-time band part with DETSDW_FM_EQ_BAND), one Matsubara part (nfreq frequencies, 1 <= nfreq <= m) per
+ * enabled every-slice channel (bandDiffTau / bandMixTau with DETSDW_TD_PH_BAND included); nfreq is ignored
  * without timeDisplacedEverySlice; ParameterWrong if neither option is on -- unless flags holds DETSDW_SERIES_PHI, the third way to
  * open a series (the order-parameter part below, which needs no option).  While the series is open every detsdw_sweep(r, 1) ends
  * with one sample of every chain added to the series (after binSize of them a bin closes); thermalisation sweeps and detsdw_sweep(r, 0) add
@@ -259,7 +276,9 @@ enum { DETSDW_SERIES_NO_HOST_COPY = 1, DETSDW_SERIES_PHI = 2 };
 enum { DETSDW_SERIES_R_CHARGE = 0, DETSDW_SERIES_R_SPINZ = 1, DETSDW_SERIES_R_SDW = 2, DETSDW_SERIES_R_PAIRPLUS = 3,
        DETSDW_SERIES_R_PAIRMINUS = 4, DETSDW_SERIES_RHO_S = 5,
        DETSDW_SERIES_BINDER_PHI = 6, DETSDW_SERIES_BINDER_RATIO_PHI = 7, DETSDW_SERIES_CHI_PHI = 8, DETSDW_SERIES_CHI_PHI_CONNECTED = 9,
-       DETSDW_SERIES_R_PHI = 10, DETSDW_SERIES_XI_PHI = 11 };
+       DETSDW_SERIES_R_PHI = 10, DETSDW_SERIES_XI_PHI = 11,
+       /* correlation ratios of the equal-time band part (dqmc_series_band_derived_host): bandDiff at (pi, pi), bandDiff at 0, bandMix at (pi, pi) */
+       DETSDW_SERIES_R_DCDW = 12, DETSDW_SERIES_R_NEMATIC = 13, DETSDW_SERIES_R_BANDMIX = 14 };
 int detsdw_series_begin(detsdw_replica* r, int binSize, int maxBins, int nfreq, int flags);
 int detsdw_series_route(detsdw_replica* r, const int* slotOfChain);
 int detsdw_series_get_route(detsdw_replica* r, int* out);
@@ -267,6 +286,9 @@ int detsdw_series_info(detsdw_replica* r, int* binsClosed, int* sweepsInOpenBin,
 int detsdw_series_stats(detsdw_replica* r, int which, double* mean, double* err);
 int detsdw_series_stats_all(detsdw_replica* r, int which, double* mean, double* err);
 int detsdw_series_derived_all(detsdw_replica* r, int what, double* value, double* err);
+/* what = 0 R_dCDW, 1 R_nematic, 2 R_bandMix (the same numbers as DETSDW_SERIES_R_DCDW .. _R_BANDMIX of detsdw_series_derived_all):
+ * value[nchains], err[nchains]; ParameterWrong without DETSDW_FM_EQ_BAND */
+int detsdw_series_band_derived(detsdw_replica* r, int what, double* value, double* err);
 int detsdw_series_read_bins(detsdw_replica* r, int which, int first, int count, double* out);
 int detsdw_series_end(detsdw_replica* r);
 /* The series over a long run (kernel calls and formulas: dqmc_hip.h).  All of it is new surface: without these calls nothing changes.

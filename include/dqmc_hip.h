@@ -53,6 +53,9 @@ enum { DQMC_MODEL_SDW = 0, DQMC_MODEL_HUBBARD = 1 };
 /* flag bit of dqmc_params::timedisplaced (the low bits keep their values 0 / 1 / 2): also reserve what the every-slice entries
  * dqmc_measure_timedisplaced_segment / _ends need */
 enum { DQMC_TD_EVERY_SLICE = 0x100 };
+/* flag bit of dqmc_params::td_particle_hole (the low bits keep their values 0 / 1 / 2): also reserve what the band-resolved charge
+ * channels bandDiff / bandMix need (dqmc_measure_timedisplaced_band below) */
+enum { DQMC_TD_PH_BAND = 0x100 };
 
 /* Execution choices that change NO result (the parity tests hold for every value); 0 = automatic everywhere.  They are
  * create-time parameters of a context: nothing about a context's launch schedule depends on the environment or on other
@@ -119,8 +122,12 @@ typedef struct dqmc_params {
                                  per-site one-body values and the accumulator block of dqmc_measure_timedisplaced_ph.  0: nothing is
                                  reserved, nothing changes.  2: everything value 1 reserves with the same layout, launches and results,
                                  and behind it the bond-amplitude table, the per-site one-body values and the accumulator block of
-                                 dqmc_measure_timedisplaced_current.  Any other value: DQMC_EINVAL.  (The field took the second
-                                 reserved slot of dqmc_tuning: the bytes of the struct are where they were.) */
+                                 dqmc_measure_timedisplaced_current.  1 | DQMC_TD_PH_BAND, 2 | DQMC_TD_PH_BAND: everything the low value
+                                 reserves with the same layout, launches and results, and behind every other buffer (the every-slice
+                                 ones included) the one-body values and the accumulator block of dqmc_measure_timedisplaced_band, with
+                                 DQMC_TD_EVERY_SLICE also an every-slice block for channel 4.  Any other value, any other bit, the flag
+                                 on 0: DQMC_EINVAL.  (The field took the second reserved slot of dqmc_tuning: the bytes of the struct
+                                 are where they were.) */
 } dqmc_params;
 
 /* AdjustmentData + slice bookkeeping that lives on the device between calls
@@ -301,6 +308,15 @@ int dqmc_measure_read_host(dqmc_ctx* ctx, double* out);
 int dqmc_set_equal_time_correlators(dqmc_ctx* ctx, int on);
 size_t dqmc_measure_eq_accum_size(dqmc_ctx* ctx);       /* 0 before the first enable, else 1 + 5 N */
 int dqmc_measure_eq_read_host(dqmc_ctx* ctx, double* out);   /* selected chain; DQMC_EINVAL before the first enable */
+/* The equal-time form of the band-resolved charge channels (bandDiff, bandMix: dqmc_measure_timedisplaced_band below): a second switch of
+ * dqmc_measure_slice, independent of the one above, with a block of its own outside the arena that the first enable allocates:
+ * count, bandDiff[N], bandMix[N] per chain (dqmc_measure_eq_band_accum_size = 1 + 2 N doubles), raw sums of Re W(B (+) d, B) with one
+ * matrix g~ in both roles.  Both matrices have M^2 = 1, so the delta term is tr_4 g~(B; B) = 4 - o^charge(B), added to the d = 0 bin as for
+ * the charge channel.  The transposed factor is read in place.  While off, and for every other block while on, nothing changes;
+ * dqmc_measure_reset clears the block.  The Hubbard model returns DQMC_EINVAL. */
+int dqmc_set_equal_time_band(dqmc_ctx* ctx, int on);
+size_t dqmc_measure_eq_band_accum_size(dqmc_ctx* ctx);  /* 0 before the first enable, else 1 + 2 N */
+int dqmc_measure_eq_band_read_host(dqmc_ctx* ctx, double* out);   /* selected chain; DQMC_EINVAL before the first enable */
 /* ---- time-displaced Green's functions ----------------------------------------------------------
  * At an interior stabilisation boundary tau_j = j s (j = 1 .. n-1) the advance holds B(tau,0) = U_r D_r V_r^H and
  * B(beta,tau) = U_l D_l V_l^H at once.  With the scales split into their parts > 1 and <= 1 and
@@ -378,6 +394,25 @@ int dqmc_measure_td_ph_read_host(dqmc_ctx* ctx, double* out);
 int dqmc_measure_timedisplaced_current(dqmc_ctx* ctx, int j);
 size_t dqmc_measure_td_current_accum_size(dqmc_ctx* ctx);   /* 0 without the reservation */
 int dqmc_measure_td_current_read_host(dqmc_ctx* ctx, double* out);
+/* Band-resolved charge correlators; context created with td_particle_hole = 1 | DQMC_TD_PH_BAND or 2 | DQMC_TD_PH_BAND.  The W^M(A,B) of
+ * dqmc_measure_timedisplaced_ph, on the same four shifted matrices, for the two spin-singlet bilinears the channels above leave out:
+ *   bandDiff  M_BAND = diag(+1, -1, +1, -1):  n_x - n_y.  q = 0: the B1g (nematic) susceptibility; q = (pi, pi): the d-wave charge-density
+ *             wave sum_s (psi^+_xs psi_xs - psi^+_ys psi_ys), the particle-hole partner of pairMinus
+ *   bandMix   M_MIX: (0,3) = (3,0) = (1,2) = (2,1) = +1:  sum_s (psi^+_xs psi_ys + h.c.), M_z of the sdw channel with the relative sign of
+ *             the two spin species flipped: the charge partner of the SDW order parameter
+ *   o^M_t(A) = tr M - sum_ab M_ab g~_t(A b; A a),   W^M(A,B) = o^M_tau(A) o^M_0(B) - sum_abcd M_ab M_cd g~(0,tau)(B d; A a) g~(tau,0)(A b; B c)
+ * OPDIM < 3 (stored sector (XUP, YDOWN), its conjugate (XDOWN, YUP)): M_BAND is sector diagonal with the same signs in both sectors, so
+ * its connected part is 4 x that of spinZ and o = -2 Re (g~_00 - g~_11) where spinZ has -i Im of the same number; M_MIX couples the two
+ * sectors, o = 0 exactly and every connected term is a product of one element of each sector (kernels_measure.hip).
+ * dqmc_measure_timedisplaced_band(j) (all chains) adds sum_B Re W(B (+) d, B) for every periodic site difference d = (dx, dy), bin
+ * dy L + dx, to the block of boundary j.  Preconditions and DQMC_EINVAL behaviour of dqmc_measure_timedisplaced_ph; the call prepares its
+ * own shifted matrices, leaves G and the other measurement blocks alone and works in either order with the other calls of the boundary.
+ * Layout (doubles, dqmc_measure_td_band_accum_size of them): count[n-1], then for j = 1 .. n-1 the bandDiff sums [N] and the bandMix
+ * sums [N], at offset (n-1) + (j-1) 2N; raw sums: dividing by N and by the count gives the translation average.  dqmc_measure_reset
+ * clears the block as well. */
+int dqmc_measure_timedisplaced_band(dqmc_ctx* ctx, int j);
+size_t dqmc_measure_td_band_accum_size(dqmc_ctx* ctx);  /* 0 without the reservation */
+int dqmc_measure_td_band_read_host(dqmc_ctx* ctx, double* out);
 /* G(0) of the last pair's field configuration, selected chain; *slice as for dqmc_get_green_timedisplaced_host.  DQMC_EINVAL without
  * td_particle_hole or if no pair was computed yet */
 int dqmc_get_green0_timedisplaced_host(dqmc_ctx* ctx, dqmc_cplx* g00, int* slice);
@@ -398,8 +433,8 @@ int dqmc_get_green0_timedisplaced_host(dqmc_ctx* ctx, dqmc_cplx* g00, int* slice
  * dqmc_measure_timedisplaced_ends() (all chains) measures rows 0 and m.  Precondition: the context stands at tau = 0 == beta
  * (current time slice 0 or m: the state after the closing advance of either sweep direction), so that G = G(0); DQMC_EINVAL
  * otherwise.  Both rows use G(tau) = G(0) = G.
- * Blocks: channel 0 = bins of dqmc_measure_timedisplaced, 1 = _pair, 2 = _ph, 3 = _current; a channel has a block if its coarse
- * block is reserved.  Layout (doubles, dqmc_measure_td_fine_accum_size of them, 0 without the block): count[m+1], then row k = 0 .. m
+ * Blocks: channel 0 = bins of dqmc_measure_timedisplaced, 1 = _pair, 2 = _ph, 3 = _current, 4 = _band (row stride 2N); a channel has a
+ * block if its coarse block is reserved.  Layout (doubles, dqmc_measure_td_fine_accum_size of them, 0 without the block): count[m+1], then row k = 0 .. m
  * at offset (m+1) + k stride, stride and contents of a row as in the coarse block: 4 (2L-1)^2, 2N, 3N, 2N + 2.
  * dqmc_measure_reset clears them as well. */
 int dqmc_measure_timedisplaced_segment(dqmc_ctx* ctx, int j);
@@ -409,7 +444,7 @@ int dqmc_measure_td_fine_read_host(dqmc_ctx* ctx, int channel, double* out);
 /* Matsubara transforms of one every-slice block, all chains and all components of the block in ONE launch (kernels_measure.hip).
  * With C_X(d, tau_k) = row k of component X divided by N and by the row's sample count, the trapezoid weights w_0 = w_m = 1/2 (1 otherwise)
  * over the closed grid tau_k = k dtau, k = 0 .. m, and n = 0 .. nfreq-1 (1 <= nfreq <= m):
- *   channels 1, 2, 3 (bosonic, omega_n = 2 pi n / beta):
+ *   channels 1, 2, 3, 4 (bosonic, omega_n = 2 pi n / beta):
  *     chi_X(q, i omega_n) = dtau sum_k w_k e^{i omega_n tau_k} sum_d e^{-i q d} C_X(d, tau_k),  q = (2 pi / L)(qx, qy), column qy L + qx
  *   channel 0 (fermionic, omega_n = (2n+1) pi / beta), band X, Y:
  *     G_band(k, i omega_n) = dtau sum_k w_k e^{i omega_n tau_k} G_band(k, tau_k),  G_band(k, tau) = Re (Fourier sum over the bins) / 2N,
@@ -417,7 +452,7 @@ int dqmc_measure_td_fine_read_host(dqmc_ctx* ctx, int channel, double* out);
  *     dqmc_measure_timedisplaced_ends wrote them.
  * out: [chain][component][nfreq][N] complex as (re, im), dqmc_measure_td_matsubara_size(ctx, channel, nfreq) doubles (0 for arguments
  * the call below rejects); component order = the block's order: X, Y / T+, T- / charge, spinZ, sdw / Lambda_xx, Lambda_yy (the two bond
- * kinetic sums of channel 3 are not transformed).  DQMC_EINVAL without the every-slice reservation, without that channel's block, for
+ * kinetic sums of channel 3 are not transformed) / bandDiff, bandMix.  DQMC_EINVAL without the every-slice reservation, without that channel's block, for
  * nfreq outside 1 .. m, or if a row of any chain has a sample count < 1 (nothing is written to out then).  Reads the block only: G, the
  * pair, G(0) and every accumulator stay bit-identical; one writer per output element and a fixed summation order, so two calls give
  * identical bits.  The device result buffer lies outside the arena, is allocated on first use and freed with the context. */
@@ -437,7 +472,7 @@ int dqmc_measure_td_matsubara_host(dqmc_ctx* ctx, int channel, int nfreq, double
  * dqmc_series_begin allocates, outside the arena, the sample [nb][S], the open bin [nb][S], the closed bins [max_bins][nb][S], the
  * per-part flags and the result buffer of the statistics calls.  DQMC_EINVAL: empty or unknown mask, a missing block, bin_size < 1,
  * max_bins < 2, a series already open, a Hubbard context, a lattice too large for the LDS of the Matsubara or sample kernel.
- * dqmc_series_layout: where part (= bit number 0 .. 4, or 6: the order-parameter part below) sits inside S.
+ * dqmc_series_layout: where part (= bit number 0 .. 4, 6: the order-parameter part, 7, 8: the band parts, all below) sits inside S.
  * dqmc_series_add_sweep (all chains): forms the sample and adds it to the open bin, open += sample, in call order; the bin_size-th call
  * writes closed[k] = open / bin_size and clears the open bin.  DQMC_EINVAL with no bin changed: the equal-time count of any chain or a
  * fine row count of any chain and channel of the mask is < 1; max_bins bins are already closed (nothing is dropped silently, and there
@@ -471,8 +506,8 @@ int dqmc_measure_td_matsubara_host(dqmc_ctx* ctx, int channel, int nfreq, double
  *   value = f(mean);  err = the jackknife over theta_(b) = f(x_(b)), about the mean of the theta_(b).
  * One writer per output element, fixed summation order (bins in index order), no atomics: bins and statistics do not depend on how
  * chains are batched, and two statistics calls give identical bits.  dqmc_series_end frees the buffers; dqmc_destroy does it too.
- * The order-parameter part, DQMC_SERIES_PHI = 64: bit 6 and part index 6 of dqmc_series_layout (bit 5 stays refused: the accepted mask is
- * 0x5f).  It needs no block -- the field phi(r, k), k = 1 .. m, always exists -- and no flag, so it may be the only part of a series; it
+ * The order-parameter part, DQMC_SERIES_PHI = 64: bit 6 and part index 6 of dqmc_series_layout (bit 5 stays refused: with the band parts below the accepted
+ * mask is 0x1df).  It needs no block -- the field phi(r, k), k = 1 .. m, always exists -- and no flag, so it may be the only part of a series; it
  * needs 1 <= nfreq <= m, and nfreq is stored in the state even when no Matsubara part is present.  It sits after all other parts and
  * holds nfreq N + 5 doubles:
  *   chi [nfreq][N], real, column qy L + qx.  With K = m N, q = 2 pi (qx, qy) / L, omega_n = 2 pi n / beta, n = 0 .. nfreq-1:
@@ -487,9 +522,16 @@ int dqmc_measure_td_matsubara_host(dqmc_ctx* ctx, int channel, int nfreq, double
  *   0: Binder cumulant 1 - <|phibar|^4> / (3 <|phibar|^2>^2)      1: Binder ratio <|phibar|^4> / <|phibar|^2>^2
  *   2: beta N <|phibar|^2>                                        3: beta N (<|phibar|^2> - <|phibar|>^2)
  *   4: R_phi = 1 - 1/2 (chix + chiy) / chi0                       5: xi_phi = sqrt(chi0 / (1/2 (chix + chiy)) - 1) / (2 sin(pi / L)),
- *                                                                    NaN where the argument of the root is negative */
+ *                                                                    NaN where the argument of the root is negative
+ * The band parts: DQMC_SERIES_MATS_BAND = 128 (bit 7: the Matsubara transform of every-slice channel 4, [2][nfreq][N] complex) and
+ * DQMC_SERIES_EQ_BAND = 256 (bit 8: the block of dqmc_set_equal_time_band as C_X(d) [2][N] then S_X(q) [2][N], X = bandDiff, bandMix, formed
+ * like bit 0 with the same cosine table and integer phase reduction).  The accepted mask is 0x1df.  Parts sit in mask order: the two lie
+ * behind the order-parameter part, and every mask without them keeps its S, its offsets and its bits.
+ * dqmc_series_band_derived_host (all chains, value and err [nb][3]; DQMC_EINVAL for B < 2 or a series without bit 8), the jackknife of
+ * dqmc_series_derived_host over R = 1 - 1/2 [S(Q + dx) + S(Q + dy)] / S(Q):
+ *   0: bandDiff at Q = (L/2, L/2), the d-wave CDW     1: bandDiff at Q = (0, 0), the nematic     2: bandMix at Q = (L/2, L/2) */
 enum { DQMC_SERIES_EQ = 1, DQMC_SERIES_MATS_G = 2, DQMC_SERIES_MATS_PAIR = 4, DQMC_SERIES_MATS_PH = 8, DQMC_SERIES_MATS_CURRENT = 16,
-       DQMC_SERIES_PHI = 64 };
+       DQMC_SERIES_PHI = 64, DQMC_SERIES_MATS_BAND = 128, DQMC_SERIES_EQ_BAND = 256 };
 int dqmc_series_begin(dqmc_ctx* ctx, int bin_size, int max_bins, int nfreq, int parts);
 int dqmc_series_layout(dqmc_ctx* ctx, int part, size_t* offset, size_t* length);
 int dqmc_series_add_sweep(dqmc_ctx* ctx);
@@ -501,6 +543,7 @@ int dqmc_series_read_bins_host(dqmc_ctx* ctx, int first, int count, double* out)
 int dqmc_series_stats_host(dqmc_ctx* ctx, double* mean, double* err);
 int dqmc_series_derived_host(dqmc_ctx* ctx, double* value, double* err);
 int dqmc_series_phi_derived_host(dqmc_ctx* ctx, double* value, double* err);
+int dqmc_series_band_derived_host(dqmc_ctx* ctx, double* value, double* err);
 int dqmc_series_end(dqmc_ctx* ctx);
 /* ---- the series over a long run: re-binning, binning analysis with tau_int, export / import ------------
  * All of it is new surface: with none of these calls used, every call above keeps its bits, its error codes and its launches.
