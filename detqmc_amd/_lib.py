@@ -30,6 +30,8 @@ DQMC_TD_PH_BAND = 0x100           # flag bit of dqmc_params.td_particle_hole: th
 DETSDW_TD_PH_BAND = 0x100         # flag bit of detsdw_params.timeDisplacedParticleHole: the same at the host level
 DETSDW_FM_EQ_BAND = 0x200         # flag bit of detsdw_params.fermionMeasurements: equal-time bandDiff / bandMix correlators
 DQMC_SERIES_MATS_BAND, DQMC_SERIES_EQ_BAND = 128, 256   # parts of dqmc_series_begin: Matsubara transform of channel 4, equal-time band block
+DQMC_SERIES_MATS_CUSTOM, DQMC_SERIES_EQ_CUSTOM = 512, 1024   # ... Matsubara transform of channel 5, equal-time block of the custom bilinears
+DQMC_CUSTOM_MAX = 4               # matrices of dqmc_set_custom_bilinears at most
 
 
 class dqmc_cplx(C.Structure):
@@ -234,6 +236,14 @@ SYMBOLS = [
     ("dqmc_measure_timedisplaced_band", C.c_int, [_P, C.c_int]),
     ("dqmc_measure_td_band_accum_size", C.c_size_t, [_P]),
     ("dqmc_measure_td_band_read_host", C.c_int, [_P, _DP]),
+    ("dqmc_set_custom_bilinears", C.c_int, [_P, C.c_int, _P]),
+    ("dqmc_get_custom_bilinears", C.c_int, [_P, C.POINTER(C.c_int), _P]),
+    ("dqmc_measure_timedisplaced_custom", C.c_int, [_P, C.c_int]),
+    ("dqmc_measure_td_custom_accum_size", C.c_size_t, [_P]),
+    ("dqmc_measure_td_custom_read_host", C.c_int, [_P, _DP]),
+    ("dqmc_set_equal_time_custom", C.c_int, [_P, C.c_int]),
+    ("dqmc_measure_eq_custom_accum_size", C.c_size_t, [_P]),
+    ("dqmc_measure_eq_custom_read_host", C.c_int, [_P, _DP]),
     ("dqmc_measure_timedisplaced_segment", C.c_int, [_P, C.c_int]),
     ("dqmc_measure_timedisplaced_ends", C.c_int, [_P]),
     ("dqmc_measure_td_fine_accum_size", C.c_size_t, [_P, C.c_int]),
@@ -252,6 +262,7 @@ SYMBOLS = [
     ("dqmc_series_derived_host", C.c_int, [_P, _DP, _DP]),
     ("dqmc_series_phi_derived_host", C.c_int, [_P, _DP, _DP]),
     ("dqmc_series_band_derived_host", C.c_int, [_P, _DP, _DP]),
+    ("dqmc_series_custom_derived_host", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
     ("dqmc_series_end", C.c_int, [_P]),
     ("dqmc_series_configure", C.c_int, [_P, C.c_int]),
     ("dqmc_series_get_state", C.c_int, [_P, C.POINTER(dqmc_series_state)]),
@@ -287,6 +298,8 @@ SYMBOLS = [
     ("detsdw_series_stats_all", C.c_int, [_P, C.c_int, _DP, _DP]),
     ("detsdw_series_derived_all", C.c_int, [_P, C.c_int, _DP, _DP]),
     ("detsdw_series_band_derived", C.c_int, [_P, C.c_int, _DP, _DP]),
+    ("detsdw_set_custom_bilinears", C.c_int, [_P, C.c_int, _P]),
+    ("detsdw_series_custom_derived", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _DP, _DP]),
     ("detsdw_series_read_bins", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _DP]),
     ("detsdw_series_end", C.c_int, [_P]),
     ("detsdw_series_configure", C.c_int, [_P, C.c_int]),

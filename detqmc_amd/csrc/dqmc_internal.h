@@ -257,20 +257,24 @@ size_t measure_accum_doubles(int N, int L);
 // (row, rows): the block holds count[rows], then row `row` at offset rows + row * stride -- (j - 1, n - 1) for the coarse blocks,
 // (k, m + 1) for the every-slice blocks; the same for the three launchers below
 void launch_measure_td(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc, int row, int rows);
-size_t measure_td_row_doubles(int channel, int N, int L);   // stride of a row: channel 0 bins, 1 pairing, 2 particle-hole, 3 current, 4 band
+size_t measure_td_row_doubles(int channel, int N, int L);   // stride of a row: channel 0 bins, 1 pairing, 2 particle-hole, 3 current, 4 band (5: measure_custom_row_doubles)
 // every-slice end rows: (G, G - 1) -> (a_t0, a_0t), (1 - G, -G) -> (b_t0, b_0t), G -> gtt; one elementwise pass, all chains
 void launch_td_ends(const Launch& lc, const cplx* G, cplx* a_t0, cplx* a_0t, cplx* b_t0, cplx* b_0t, cplx* gtt, int ng);
 size_t measure_td_doubles(int L, int n);
 // Matsubara transforms of the every-slice block `acc` of `channel` (count[m+1], then the rows): out[chain][component][nfreq][N] (re, im),
 // bad[chain] = 1 if a row of the chain was never measured; out and bad are plain device arrays (no chain stride).  false: the lattice
-// is too large for the kernel's LDS, nothing was launched.  out_chain_stride (doubles) != 0: chain b's results at out + b * stride
+// is too large for the kernel's LDS, nothing was launched.  out_chain_stride (doubles) != 0: chain b's results at out + b * stride.
+// Channel 5 (user-defined bilinears): custom_count components per row, and the block lives outside the arena, chain b at
+// (char*)acc + b * custom_chain_bytes
 bool launch_td_matsubara(const Launch& lc, const DevModel& hm, const double* acc, int channel, int nfreq, int apbx, int apby,
-                         double* out, double* bad, size_t out_chain_stride = 0);
+                         double* out, double* bad, size_t out_chain_stride = 0, int custom_count = 0, size_t custom_chain_bytes = 0);
 bool td_matsubara_fits(const DevModel& hm, int channel, int nfreq);     // what launch_td_matsubara would return, nothing launched
 // measurement series (dqmc_series_*): sample / open / closed / bad are plain device arrays, chain b of an [nb][S] array at b * S
 bool launch_series_eq_sample(const Launch& lc, const DevModel& hm, const double* eqacc, size_t eq_n, int nch, const double* trig, double* sample,
                              size_t S, size_t off, double* bad);     // nch channels of the block count, X[nch][N] -> C_X [nch][N], S_X [nch][N]
 void launch_series_band_derived(const Launch& lc, const DevModel& hm, const double* bins, size_t S, int B, size_t off, double* value, double* err);
+void launch_series_custom_derived(const Launch& lc, const DevModel& hm, const double* bins, size_t S, int B, size_t off, int count, int qx, int qy,
+                                  double* value, double* err);      // value, err [nb][count]: R of every user-defined bilinear at Q = (qx, qy)
 size_t series_eq_sample_lds_bytes(int L);
 void launch_series_accum(const Launch& lc, const double* sample, double* open, double* closed, size_t n, int close, int bin_size);
 void launch_series_accum_routed(const Launch& lc, const double* const* src, double* open, double* closed, size_t S, int close, int bin_size);
@@ -327,6 +331,19 @@ size_t measure_td_band_onebody_cplx(int N);
 void launch_measure_eq_band(const Launch& lc, const DevModel& hm, const cplx* gs, cplx* ob, double* acc);
 size_t measure_eq_band_doubles(int N);
 size_t measure_eq_band_onebody_cplx(int N);
+// user-defined bilinears (dqmc_set_custom_bilinears): count matrices M [count][4][4] (row-major, host memory: they travel as a kernel argument)
+// with their non-zero masks (bit 4 a + b: M_ab != 0), every channel in one launch; a row holds the channels' sums over B of Re W(B (+) d, B),
+// [count][N].  Time-displaced: count[rows], then the rows; gs, hs as for launch_measure_td_ph.  Equal-time: count, then one row; M2, mask2 =
+// the squares of the matrices (the delta term).  acc and the scratch ob are plain device arrays outside the arena: chain b at acc + b * acs
+// (equal-time: 1 + measure_custom_row_doubles) and ob + b * measure_*_custom_onebody_cplx
+void launch_td_custom_onebody(const Launch& lc, const DevModel& hm, int count, const cplx* M, const unsigned* mask, const cplx* gs, cplx* ob, int t);
+void launch_measure_td_custom(const Launch& lc, const DevModel& hm, int count, const cplx* M, const unsigned* mask, const cplx* gs, const cplx* hs,
+                              const cplx* ob, double* acc, size_t acs, int row, int rows);
+void launch_measure_eq_custom(const Launch& lc, const DevModel& hm, int count, const cplx* M, const unsigned* mask, const cplx* M2, const unsigned* mask2,
+                              const cplx* gs, cplx* ob, double* acc);
+size_t measure_custom_row_doubles(int count, int N);
+size_t measure_td_custom_onebody_cplx(int count, int N);
+size_t measure_eq_custom_onebody_cplx(int count, int N);
 
 // ---- QR / UDT building blocks (kernels_qr.hip) ------------------------------------------------
 struct SvdProfHooks;

@@ -36,14 +36,14 @@ extern "C" int dqmc_shift_green_symmetric_host(dqmc_ctx* c, dqmc_cplx* out) {
     HIPCHK(copy_sync(c, out, selp(c, c->T1), (size_t)c->n_g * c->n_g * sizeof(cplx), hipMemcpyDeviceToHost));
     return DQMC_OK;
 }
-// zero fill of every block the context has: per chain inside the arena, the equal-time blocks ([chain][n], contiguous) in one call each
+// zero fill of every block the context has, by the block's own stride: the blocks outside the arena are [chain][n], contiguous, and take
+// one call; a block inside the arena takes one call per chain
 static int acc_reset_all(dqmc_ctx* c) {
-    for (int id = 0; id < ACC_EQ; ++id)
-        for (int b = 0; c->acc[id].n && b < c->nb; ++b)
-            HIPCHK(hipMemsetAsync(chainp(c, c->acc[id].p, b), 0, c->acc[id].n * sizeof(double), c->st));
-    for (int id = ACC_EQ; id < ACC_COUNT; ++id) {
-        const AccBlock& eq = c->acc[id];
-        if (eq.n) HIPCHK(hipMemsetAsync(eq.p, 0, eq.n * (size_t)c->nb * sizeof(double), c->st));
+    for (int id = 0; id < ACC_COUNT; ++id) {
+        const AccBlock& a = c->acc[id];
+        if (!a.n) continue;
+        if (a.stride == a.n * sizeof(double)) { HIPCHK(hipMemsetAsync(a.p, 0, a.n * (size_t)c->nb * sizeof(double), c->st)); continue; }
+        for (int b = 0; b < c->nb; ++b) HIPCHK(hipMemsetAsync((char*)a.p + (size_t)b * a.stride, 0, a.n * sizeof(double), c->st));
     }
     return DQMC_OK;
 }
@@ -76,6 +76,10 @@ extern "C" int dqmc_measure_slice(dqmc_ctx* c) {
     { ProfScope ps(c, FAM_OTHER, 1); launch_measure_accum(c->lc, c->hm, c->T1, c->acc[ACC_SLICE].p); }
     if (c->eq_on) { ProfScope ps(c, FAM_OTHER, 2); launch_measure_eq_corr(c->lc, c->hm, c->T1, c->eq_ob, c->acc[ACC_EQ].p); }   // same T1, no second shift
     if (c->eqb_on) { ProfScope ps(c, FAM_OTHER, 2); launch_measure_eq_band(c->lc, c->hm, c->T1, c->eqb_ob, c->acc[ACC_EQ_BAND].p); }
+    if (c->eqc_on) {
+        ProfScope ps(c, FAM_OTHER, 2);
+        launch_measure_eq_custom(c->lc, c->hm, c->cst_count, c->cst_M, c->cst_mask, c->cst_M2, c->cst_mask2, c->T1, c->cst_eq_ob, c->acc[ACC_EQ_CUSTOM].p);
+    }
     return finish(c, "dqmc_measure_slice");
 }
 extern "C" size_t dqmc_measure_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_SLICE); }
@@ -118,6 +122,102 @@ extern "C" int dqmc_set_equal_time_band(dqmc_ctx* c, int on) {
 }
 extern "C" size_t dqmc_measure_eq_band_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_EQ_BAND); }
 extern "C" int dqmc_measure_eq_band_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_EQ_BAND, out); }
+// user-defined bilinears (dqmc_hip.h): the matrices stay on the host, the blocks and the one-body scratch live outside the arena
+void custom_free(dqmc_ctx* c) {
+    for (void* q : {(void*)c->acc[ACC_TD_CUSTOM].p, (void*)c->acc[ACC_FINE0 + 5].p, (void*)c->acc[ACC_EQ_CUSTOM].p, (void*)c->cst_td_ob, (void*)c->cst_eq_ob})
+        if (q) (void)hipFree(q);
+    c->acc[ACC_TD_CUSTOM].p = c->acc[ACC_FINE0 + 5].p = c->acc[ACC_EQ_CUSTOM].p = nullptr;
+    c->acc[ACC_TD_CUSTOM].n = c->acc[ACC_FINE0 + 5].n = c->acc[ACC_EQ_CUSTOM].n = 0;
+    c->cst_td_ob = c->cst_eq_ob = nullptr;
+    c->cst_count = 0;
+    c->eqc_on = false;
+}
+extern "C" int dqmc_set_custom_bilinears(dqmc_ctx* c, int count, const dqmc_cplx* M) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (c->hm.hubbard) return fail(DQMC_EINVAL, "the user-defined bilinears belong to the SDW model");
+    if (count < 0 || count > DQMC_CUSTOM_MAX) return fail(DQMC_EINVAL, "dqmc_set_custom_bilinears: count must be in 0 .. DQMC_CUSTOM_MAX");
+    if (count && !M) return fail(DQMC_EINVAL, "null argument");
+    if (c->ser.open && (c->ser.parts & (DQMC_SERIES_MATS_CUSTOM | DQMC_SERIES_EQ_CUSTOM)))
+        return fail(DQMC_EINVAL, "dqmc_set_custom_bilinears: a measurement series with a part of the user-defined bilinears is open");
+    for (int ch = 0; ch < count; ++ch) {
+        const dqmc_cplx* m = M + 16 * ch;
+        bool any = false;
+        for (int a = 0; a < 4; ++a)
+            for (int b = 0; b < 4; ++b) {
+                const dqmc_cplx v = m[4 * a + b], w = m[4 * b + a];
+                if (!std::isfinite(v.re) || !std::isfinite(v.im)) return fail(DQMC_EINVAL, "dqmc_set_custom_bilinears: an entry is not finite");
+                if (v.re != w.re || v.im != -w.im) return fail(DQMC_EINVAL, "dqmc_set_custom_bilinears: a matrix is not Hermitian");
+                any = any || v.re != 0.0 || v.im != 0.0;
+            }
+        if (!any) return fail(DQMC_EINVAL, "dqmc_set_custom_bilinears: a matrix is all zero");
+    }
+    (void)hipSetDevice(c->p.device);
+    // the new buffers first: a failed allocation leaves the context as it was
+    const size_t nb = (size_t)c->nb, row = measure_custom_row_doubles(count, c->N);
+    const size_t n_eq = count ? 1 + row : 0, n_td = count && c->G00 ? (size_t)(c->n - 1) * (1 + row) : 0;
+    const size_t n_fine = n_td && c->td_fine ? (size_t)(c->m + 1) * (1 + row) : 0;
+    const size_t ob_eq = count ? measure_eq_custom_onebody_cplx(count, c->N) : 0, ob_td = n_td ? measure_td_custom_onebody_cplx(count, c->N) : 0;
+    double *eq = nullptr, *td = nullptr, *fine = nullptr;
+    cplx *oe = nullptr, *ot = nullptr;
+    hipError_t e = hipSuccess;
+    if (n_eq) e = hipMalloc((void**)&eq, n_eq * nb * sizeof(double));
+    if (e == hipSuccess && ob_eq) e = hipMalloc((void**)&oe, ob_eq * nb * sizeof(cplx));
+    if (e == hipSuccess && n_td) e = hipMalloc((void**)&td, n_td * nb * sizeof(double));
+    if (e == hipSuccess && ob_td) e = hipMalloc((void**)&ot, ob_td * nb * sizeof(cplx));
+    if (e == hipSuccess && n_fine) e = hipMalloc((void**)&fine, n_fine * nb * sizeof(double));
+    if (e == hipSuccess && n_fine) e = hipMemsetAsync(fine, 0, n_fine * nb * sizeof(double), c->st);
+    if (e == hipSuccess && n_eq) e = hipMemsetAsync(eq, 0, n_eq * nb * sizeof(double), c->st);
+    if (e == hipSuccess && ob_eq) e = hipMemsetAsync(oe, 0, ob_eq * nb * sizeof(cplx), c->st);
+    if (e == hipSuccess && n_td) e = hipMemsetAsync(td, 0, n_td * nb * sizeof(double), c->st);
+    if (e == hipSuccess && ob_td) e = hipMemsetAsync(ot, 0, ob_td * nb * sizeof(cplx), c->st);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->st);  // also: nothing enqueued still uses the blocks released below
+    if (e != hipSuccess) {
+        for (void* q : {(void*)eq, (void*)oe, (void*)td, (void*)ot, (void*)fine}) if (q) (void)hipFree(q);
+        return fail(DQMC_EHIP, std::string("dqmc_set_custom_bilinears: ") + hipGetErrorString(e));
+    }
+    const bool eq_switch = c->eqc_on && count > 0;          // the switch outlives a replacement, not the removal
+    custom_free(c);
+    c->eqc_on = eq_switch;
+    c->acc[ACC_EQ_CUSTOM].p = eq; c->acc[ACC_EQ_CUSTOM].n = n_eq; c->acc[ACC_EQ_CUSTOM].stride = n_eq * sizeof(double);
+    c->acc[ACC_TD_CUSTOM].p = td; c->acc[ACC_TD_CUSTOM].n = n_td; c->acc[ACC_TD_CUSTOM].stride = n_td * sizeof(double);
+    c->acc[ACC_FINE0 + 5].p = fine; c->acc[ACC_FINE0 + 5].n = n_fine; c->acc[ACC_FINE0 + 5].stride = n_fine * sizeof(double);
+    c->cst_eq_ob = oe; c->cst_td_ob = ot;
+    c->cst_count = count;
+    for (int ch = 0; ch < count; ++ch) {
+        cplx* m = c->cst_M + 16 * ch;
+        cplx* m2 = c->cst_M2 + 16 * ch;
+        for (int k = 0; k < 16; ++k) m[k] = make_double2(M[16 * ch + k].re, M[16 * ch + k].im);
+        c->cst_mask[ch] = c->cst_mask2[ch] = 0;
+        for (int a = 0; a < 4; ++a)
+            for (int b = 0; b < 4; ++b) {
+                cplx v = make_double2(0.0, 0.0);
+                for (int k = 0; k < 4; ++k) {
+                    v.x += m[4 * a + k].x * m[4 * k + b].x - m[4 * a + k].y * m[4 * k + b].y;
+                    v.y += m[4 * a + k].x * m[4 * k + b].y + m[4 * a + k].y * m[4 * k + b].x;
+                }
+                m2[4 * a + b] = v;
+                if (m[4 * a + b].x != 0.0 || m[4 * a + b].y != 0.0) c->cst_mask[ch] |= 1u << (4 * a + b);
+                if (v.x != 0.0 || v.y != 0.0) c->cst_mask2[ch] |= 1u << (4 * a + b);
+            }
+    }
+    return DQMC_OK;
+}
+extern "C" int dqmc_get_custom_bilinears(dqmc_ctx* c, int* count, dqmc_cplx* M) {
+    if (!c || !count) return fail(DQMC_EINVAL, "null argument");
+    if (c->hm.hubbard) return fail(DQMC_EINVAL, "the user-defined bilinears belong to the SDW model");
+    *count = c->cst_count;
+    for (int k = 0; M && k < 16 * c->cst_count; ++k) { M[k].re = c->cst_M[k].x; M[k].im = c->cst_M[k].y; }
+    return DQMC_OK;
+}
+extern "C" int dqmc_set_equal_time_custom(dqmc_ctx* c, int on) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (c->hm.hubbard) return fail(DQMC_EINVAL, "the user-defined bilinears belong to the SDW model");
+    if (on && !c->cst_count) return fail(DQMC_EINVAL, c->acc[ACC_EQ_CUSTOM].missing);
+    c->eqc_on = on != 0;
+    return DQMC_OK;
+}
+extern "C" size_t dqmc_measure_eq_custom_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_EQ_CUSTOM); }
+extern "C" int dqmc_measure_eq_custom_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_EQ_CUSTOM, out); }
 
 // ---------------------------------------------------------------------------------------------
 // time-displaced Green's functions (dqmc_hip.h; computed inside green_from_udv while td_on)
@@ -141,7 +241,7 @@ extern "C" int dqmc_get_green_timedisplaced_host(dqmc_ctx* c, dqmc_cplx* g_t0, d
     return DQMC_OK;
 }
 // ---- the channel kernels: coarse boundaries and every time slice (DQMC_TD_EVERY_SLICE) ---------------------------------------------
-enum { CH_G = 1, CH_PAIR = 2, CH_PH = 4, CH_CUR = 8, CH_BAND = 16, CH_TWO_BODY = CH_PH | CH_CUR | CH_BAND };     // bit ch of a channel mask
+enum { CH_G = 1, CH_PAIR = 2, CH_PH = 4, CH_CUR = 8, CH_BAND = 16, CH_CUSTOM = 32, CH_TWO_BODY = CH_PH | CH_CUR | CH_BAND | CH_CUSTOM };     // bit ch of a channel mask
 // One-body values of an equal-time matrix for the masked particle-hole / current / band kernels (t = 0: tau side, 1: 0 side): one shift of g,
 // then each masked table.  g == nullptr: T1 still holds the shifted matrix of the call before.
 static void td_onebody(dqmc_ctx* c, unsigned mask, const cplx* g, int t) {
@@ -150,6 +250,7 @@ static void td_onebody(dqmc_ctx* c, unsigned mask, const cplx* g, int t) {
     if (mask & CH_PH) { ProfScope ps(c, FAM_OTHER, 1); launch_td_ph_onebody(c->lc, c->hm, c->T1, c->ph_ob, t); }
     if (mask & CH_CUR) { ProfScope ps(c, FAM_OTHER, 1); launch_td_current_onebody(c->lc, c->hm, c->T1, c->cur_bt, c->cur_ob, t); }
     if (mask & CH_BAND) { ProfScope ps(c, FAM_OTHER, 1); launch_td_band_onebody(c->lc, c->hm, c->T1, c->band_ob, t); }
+    if (mask & CH_CUSTOM) { ProfScope ps(c, FAM_OTHER, 1); launch_td_custom_onebody(c->lc, c->hm, c->cst_count, c->cst_M, c->cst_mask, c->T1, c->cst_td_ob, t); }
 }
 // The one place that launches the channel kernels: row `row` of `rows` of the masked channels' blocks (channel ch: acc[first + ch]) from
 // (gt0, g0t, gtt, g00) = (G(tau,0), G(0,tau), G(tau), G(0)).  Every shifted matrix is prepared once and handed to all masked kernels:
@@ -171,6 +272,11 @@ static void td_row(dqmc_ctx* c, unsigned mask, int first, int row, int rows, con
         launch_measure_td_current(c->lc, c->hm, c->T1, c->ph_H, c->cur_bt, c->cur_ob, c->acc[first + 3].p, row, rows);
     }
     if (mask & CH_BAND) { ProfScope ps(c, FAM_OTHER, 1); launch_measure_td_band(c->lc, c->hm, c->T1, c->ph_H, c->band_ob, c->acc[first + 4].p, row, rows); }
+    if (mask & CH_CUSTOM) {
+        ProfScope ps(c, FAM_OTHER, 1);
+        const AccBlock& a = c->acc[first + 5];
+        launch_measure_td_custom(c->lc, c->hm, c->cst_count, c->cst_M, c->cst_mask, c->T1, c->ph_H, c->cst_td_ob, a.p, a.stride / sizeof(double), row, rows);
+    }
 }
 // what every entry that works at boundary j asks for; need_current_G: the entry also reads G, which must still be G(tau_j)
 static int td_boundary_ok(dqmc_ctx* c, int j, bool need_current_G) {
@@ -196,6 +302,7 @@ extern "C" int dqmc_measure_timedisplaced_pair(dqmc_ctx* c, int j) { return td_c
 extern "C" int dqmc_measure_timedisplaced_ph(dqmc_ctx* c, int j) { return td_coarse(c, 2, j, "dqmc_measure_timedisplaced_ph"); }
 extern "C" int dqmc_measure_timedisplaced_current(dqmc_ctx* c, int j) { return td_coarse(c, 3, j, "dqmc_measure_timedisplaced_current"); }
 extern "C" int dqmc_measure_timedisplaced_band(dqmc_ctx* c, int j) { return td_coarse(c, 4, j, "dqmc_measure_timedisplaced_band"); }
+extern "C" int dqmc_measure_timedisplaced_custom(dqmc_ctx* c, int j) { return td_coarse(c, 5, j, "dqmc_measure_timedisplaced_custom"); }
 extern "C" size_t dqmc_measure_td_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_TD); }
 extern "C" int dqmc_measure_td_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_TD, out); }
 extern "C" size_t dqmc_measure_td_pair_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_TD_PAIR); }
@@ -206,6 +313,8 @@ extern "C" size_t dqmc_measure_td_current_accum_size(dqmc_ctx* c) { return acc_s
 extern "C" int dqmc_measure_td_current_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_TD_CUR, out); }
 extern "C" size_t dqmc_measure_td_band_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_TD_BAND); }
 extern "C" int dqmc_measure_td_band_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_TD_BAND, out); }
+extern "C" size_t dqmc_measure_td_custom_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_TD_CUSTOM); }
+extern "C" int dqmc_measure_td_custom_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_TD_CUSTOM, out); }
 extern "C" int dqmc_get_green0_timedisplaced_host(dqmc_ctx* c, dqmc_cplx* g00, int* slice) {
     if (!c || !g00 || !slice) return fail(DQMC_EINVAL, "null argument");
     if (!c->G00) return fail(DQMC_EINVAL, "context created without dqmc_params::td_particle_hole");
@@ -313,9 +422,15 @@ extern "C" int dqmc_measure_td_fine_read_host(dqmc_ctx* c, int channel, double* 
 }
 static bool ser_apbx(const dqmc_ctx* c) { return c->p.bc == DQMC_BC_APBC_X || c->p.bc == DQMC_BC_APBC_XY; }
 static bool ser_apby(const dqmc_ctx* c) { return c->p.bc == DQMC_BC_APBC_Y || c->p.bc == DQMC_BC_APBC_XY; }
+static int td_ncomp(const dqmc_ctx* c, int channel) { return channel == 5 ? c->cst_count : channel == 2 ? 3 : 2; }
+// the Matsubara launch of one every-slice block; channel 5 brings its component count and its own chain stride
+static bool mats_launch(dqmc_ctx* c, int ch, int nfreq, double* out, double* bad, size_t out_chain_stride) {
+    const AccBlock& a = c->acc[ACC_FINE0 + ch];
+    return launch_td_matsubara(c->lc, c->hm, a.p, ch, nfreq, ser_apbx(c), ser_apby(c), out, bad, out_chain_stride, c->cst_count, a.stride);
+}
 extern "C" size_t dqmc_measure_td_matsubara_size(dqmc_ctx* c, int channel, int nfreq) {
     if (!c || !td_fine_n(c, channel) || nfreq < 1 || nfreq > c->m) return 0;
-    return (size_t)c->nb * (channel == 2 ? 3 : 2) * nfreq * c->N * 2;
+    return (size_t)c->nb * td_ncomp(c, channel) * nfreq * c->N * 2;
 }
 extern "C" int dqmc_measure_td_matsubara_host(dqmc_ctx* c, int channel, int nfreq, double* out) {
     if (!c || !out) return fail(DQMC_EINVAL, "null argument");
@@ -333,7 +448,7 @@ extern "C" int dqmc_measure_td_matsubara_host(dqmc_ctx* c, int channel, int nfre
     bool launched;
     {
         ProfScope ps(c, FAM_OTHER, 1);
-        launched = launch_td_matsubara(c->lc, c->hm, c->acc[ACC_FINE0 + channel].p, channel, nfreq, ser_apbx(c), ser_apby(c), c->mats_out, c->mats_out + n_out);
+        launched = mats_launch(c, channel, nfreq, c->mats_out, c->mats_out + n_out, 0);
     }
     if (!launched) return fail(DQMC_EINVAL, "dqmc_measure_td_matsubara_host: the lattice is too large for the kernel's LDS");
     { const int rc = finish(c, "dqmc_measure_td_matsubara_host"); if (rc != DQMC_OK) return rc; }
@@ -351,12 +466,13 @@ extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nf
     if (!c) return fail(DQMC_EINVAL, "null ctx");
     if (c->hm.hubbard) return fail(DQMC_EINVAL, "the measurement series belongs to the SDW model");
     if (c->ser.open) return fail(DQMC_EINVAL, "a measurement series is already open (dqmc_series_end)");
-    if (parts <= 0 || (parts & ~0x1df)) return fail(DQMC_EINVAL, "dqmc_series_begin: parts must be a non-empty mask of bits 0 .. 4 and 6 .. 8");
+    if (parts <= 0 || (parts & ~0x7df)) return fail(DQMC_EINVAL, "dqmc_series_begin: parts must be a non-empty mask of bits 0 .. 4 and 6 .. 10");
     if (bin_size < 1) return fail(DQMC_EINVAL, "dqmc_series_begin: bin_size must be at least 1");
     if (max_bins < 2) return fail(DQMC_EINVAL, "dqmc_series_begin: max_bins must be at least 2");
     if ((parts & 1) && !c->acc[ACC_EQ].n) return fail(DQMC_EINVAL, "dqmc_series_begin: the equal-time block has never been enabled (dqmc_set_equal_time_correlators)");
     if ((parts & DQMC_SERIES_EQ_BAND) && !c->acc[ACC_EQ_BAND].n) return fail(DQMC_EINVAL, "dqmc_series_begin: the equal-time band block has never been enabled (dqmc_set_equal_time_band)");
-    if ((parts & (1 | DQMC_SERIES_EQ_BAND)) && series_eq_sample_lds_bytes(c->hm.L) > 152 * 1024)
+    if ((parts & DQMC_SERIES_EQ_CUSTOM) && !c->acc[ACC_EQ_CUSTOM].n) return fail(DQMC_EINVAL, "dqmc_series_begin: no user-defined bilinear is set (dqmc_set_custom_bilinears)");
+    if ((parts & (1 | DQMC_SERIES_EQ_BAND | DQMC_SERIES_EQ_CUSTOM)) && series_eq_sample_lds_bytes(c->hm.L) > 152 * 1024)
         return fail(DQMC_EINVAL, "dqmc_series_begin: the lattice is too large for the equal-time sample kernel's LDS");
     dqmc_ctx::Series s;
     const size_t N = (size_t)c->N;
@@ -381,7 +497,15 @@ extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nf
         s.off[7] = s.S; s.len[7] = (size_t)2 * nfreq * N * 2; s.S += s.len[7];
     }
     if (parts & DQMC_SERIES_EQ_BAND) { s.off[8] = s.S; s.len[8] = 4 * N; s.S += s.len[8]; }
-    s.bin_size = bin_size; s.max_bins = max_bins; s.nfreq = (parts & (0x1e | DQMC_SERIES_PHI | DQMC_SERIES_MATS_BAND)) ? nfreq : 0; s.parts = parts;
+    if (parts & DQMC_SERIES_MATS_CUSTOM) {                  // the parts of the user-defined bilinears: behind everything else again
+        if (!c->td_fine || !td_fine_n(c, 5)) return fail(DQMC_EINVAL, "dqmc_series_begin: no every-slice block for a channel of the mask");
+        if (nfreq < 1 || nfreq > c->m) return fail(DQMC_EINVAL, "dqmc_series_begin: nfreq must be in 1..m");
+        if (!td_matsubara_fits(c->hm, 5, nfreq)) return fail(DQMC_EINVAL, "dqmc_series_begin: the lattice is too large for the Matsubara kernel's LDS");
+        s.off[9] = s.S; s.len[9] = (size_t)c->cst_count * nfreq * N * 2; s.S += s.len[9];
+    }
+    if (parts & DQMC_SERIES_EQ_CUSTOM) { s.off[10] = s.S; s.len[10] = (size_t)2 * c->cst_count * N; s.S += s.len[10]; }
+    s.bin_size = bin_size; s.max_bins = max_bins; s.parts = parts;
+    s.nfreq = (parts & (0x1e | DQMC_SERIES_PHI | DQMC_SERIES_MATS_BAND | DQMC_SERIES_MATS_CUSTOM)) ? nfreq : 0;
     (void)hipSetDevice(c->p.device);
     const size_t n = (size_t)c->nb * s.S, L = (size_t)c->hm.L;
     c->ser = s;                                             // from here on series_free releases what was allocated
@@ -390,7 +514,7 @@ extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nf
     if (e == hipSuccess) e = hipMalloc((void**)&r.sample, n * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&r.openbin, n * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&r.bins, (size_t)max_bins * n * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&r.bad, (size_t)7 * c->nb * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&r.bad, (size_t)9 * c->nb * sizeof(double));
     const size_t mt = (parts & DQMC_SERIES_PHI) ? (size_t)c->m : 0;     // the temporal table of the order-parameter part
     if (e == hipSuccess) e = hipMalloc((void**)&r.trig, 2 * (L + mt) * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&r.stat, (2 * n + (size_t)12 * c->nb) * sizeof(double));
@@ -398,7 +522,7 @@ extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nf
     if (e == hipSuccess) e = hipMemsetAsync(r.sample, 0, n * sizeof(double), c->st);
     if (e == hipSuccess) e = hipMemsetAsync(r.openbin, 0, n * sizeof(double), c->st);
     if (e == hipSuccess) e = hipMemsetAsync(r.bins, 0, (size_t)max_bins * n * sizeof(double), c->st);
-    if (e == hipSuccess) e = hipMemsetAsync(r.bad, 0, (size_t)7 * c->nb * sizeof(double), c->st);
+    if (e == hipSuccess) e = hipMemsetAsync(r.bad, 0, (size_t)9 * c->nb * sizeof(double), c->st);
     if (e == hipSuccess) {
         // cos / sin(2 pi j / L) as finishFermionic of the host layer forms them: the device's structure factors use the same values
         std::vector<double> trig(2 * (L + mt));
@@ -421,7 +545,7 @@ extern "C" int dqmc_series_end(dqmc_ctx* c) {
 extern "C" int dqmc_series_layout(dqmc_ctx* c, int part, size_t* offset, size_t* length) {
     if (!c || !offset || !length) return fail(DQMC_EINVAL, "null argument");
     if (!c->ser.open) return fail(DQMC_EINVAL, "no measurement series is open");
-    if (part < 0 || part > 8 || !(c->ser.parts & (1 << part))) return fail(DQMC_EINVAL, "dqmc_series_layout: the part is not in the series");
+    if (part < 0 || part > 10 || !(c->ser.parts & (1 << part))) return fail(DQMC_EINVAL, "dqmc_series_layout: the part is not in the series");
     *offset = c->ser.off[part]; *length = c->ser.len[part];
     return DQMC_OK;
 }
@@ -466,6 +590,17 @@ static int series_form_sample(dqmc_ctx* c, const char* entry) {
         }
         if (s.parts & DQMC_SERIES_EQ_BAND) {
             if (!launch_series_eq_sample(c->lc, c->hm, c->acc[ACC_EQ_BAND].p, c->acc[ACC_EQ_BAND].n, 2, s.trig, s.sample, s.S, s.off[8],
+                                         s.bad + (size_t)nparts * c->nb))
+                return fail(DQMC_EINVAL, who + ": the lattice is too large for the equal-time sample kernel's LDS");
+            ++nparts;
+        }
+        if (s.parts & DQMC_SERIES_MATS_CUSTOM) {
+            if (!mats_launch(c, 5, s.nfreq, s.sample + s.off[9], s.bad + (size_t)nparts * c->nb, s.S))
+                return fail(DQMC_EINVAL, who + ": the lattice is too large for the Matsubara kernel's LDS");
+            ++nparts;
+        }
+        if (s.parts & DQMC_SERIES_EQ_CUSTOM) {
+            if (!launch_series_eq_sample(c->lc, c->hm, c->acc[ACC_EQ_CUSTOM].p, c->acc[ACC_EQ_CUSTOM].n, c->cst_count, s.trig, s.sample, s.S, s.off[10],
                                          s.bad + (size_t)nparts * c->nb))
                 return fail(DQMC_EINVAL, who + ": the lattice is too large for the equal-time sample kernel's LDS");
             ++nparts;
@@ -621,6 +756,22 @@ extern "C" int dqmc_series_band_derived_host(dqmc_ctx* c, double* value, double*
     double* dv = s.stat + 2 * n;                            // the result rows of dqmc_series_derived_host: the calls are synchronous
     { ProfScope ps(c, FAM_OTHER, 1); launch_series_band_derived(c->lc, c->hm, s.bins, s.S, s.closed, s.off[8], dv, dv + nd); }
     { const int rc = finish(c, "dqmc_series_band_derived_host"); if (rc != DQMC_OK) return rc; }
+    HIPCHK(copy_sync(c, value, dv, nd * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(c, err, dv + nd, nd * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+extern "C" int dqmc_series_custom_derived_host(dqmc_ctx* c, int qx, int qy, double* value, double* err) {
+    if (!c || !value || !err) return fail(DQMC_EINVAL, "null argument");
+    const dqmc_ctx::Series& s = c->ser;
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (!(s.parts & DQMC_SERIES_EQ_CUSTOM)) return fail(DQMC_EINVAL, "dqmc_series_custom_derived_host: the series has no equal-time part of the user-defined bilinears");
+    if (qx < 0 || qx >= c->hm.L || qy < 0 || qy >= c->hm.L) return fail(DQMC_EINVAL, "dqmc_series_custom_derived_host: qx and qy must be in 0 .. L-1");
+    if (s.closed < 2) return fail(DQMC_EINVAL, "dqmc_series_custom_derived_host: the jackknife needs at least two closed bins");
+    (void)hipSetDevice(c->p.device);
+    const size_t n = (size_t)c->nb * s.S, nd = (size_t)c->cst_count * c->nb;
+    double* dv = s.stat + 2 * n;                            // the result rows of dqmc_series_derived_host: the calls are synchronous
+    { ProfScope ps(c, FAM_OTHER, 1); launch_series_custom_derived(c->lc, c->hm, s.bins, s.S, s.closed, s.off[10], c->cst_count, qx, qy, dv, dv + nd); }
+    { const int rc = finish(c, "dqmc_series_custom_derived_host"); if (rc != DQMC_OK) return rc; }
     HIPCHK(copy_sync(c, value, dv, nd * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHK(copy_sync(c, err, dv + nd, nd * sizeof(double), hipMemcpyDeviceToHost));
     return DQMC_OK;

@@ -278,6 +278,7 @@ void DetSDW::measureTimeDisplaced(Group& g, int j) {
     if (ph_level(ch_[0].pars)) check(dqmc_measure_timedisplaced_ph(g.ctx, j), "measureTimeDisplacedParticleHole");
     if (ph_level(ch_[0].pars) == 2) check(dqmc_measure_timedisplaced_current(g.ctx, j), "measureTimeDisplacedCurrent");
     if (td_band(ch_[0].pars)) check(dqmc_measure_timedisplaced_band(g.ctx, j), "measureTimeDisplacedBand");
+    if (customTd()) check(dqmc_measure_timedisplaced_custom(g.ctx, j), "measureTimeDisplacedCustom");
     // every slice of the boundary's segment, in the boundary's own field configuration
     if (td_every_slice(ch_[0].pars)) check(dqmc_measure_timedisplaced_segment(g.ctx, j), "measureTimeDisplacedSegment");
 }
@@ -362,10 +363,13 @@ void DetSDW::sweep(bool takeMeasurements) {
     const bool eq = fermionic && eq_correlators(ch_[0].pars);
     const bool eqb = fermionic && eq_band(ch_[0].pars);
     if (eq) for (auto& g : groups_) check(dqmc_set_equal_time_correlators(g.ctx, 1), "dqmc_set_equal_time_correlators");
+    const bool eqc = fermionic && customEq();
     if (eqb) for (auto& g : groups_) check(dqmc_set_equal_time_band(g.ctx, 1), "dqmc_set_equal_time_band");
-    auto off = [this, eq, eqb]() {
+    if (eqc) for (auto& g : groups_) check(dqmc_set_equal_time_custom(g.ctx, 1), "dqmc_set_equal_time_custom");
+    auto off = [this, eq, eqb, eqc]() {
         if (eq) for (auto& g : groups_) (void)dqmc_set_equal_time_correlators(g.ctx, 0);
         if (eqb) for (auto& g : groups_) (void)dqmc_set_equal_time_band(g.ctx, 0);
+        if (eqc) for (auto& g : groups_) (void)dqmc_set_equal_time_custom(g.ctx, 0);
         measuring_ = false;
         if (measuringTD_) for (auto& g : groups_) (void)dqmc_set_timedisplaced(g.ctx, 0);
         measuringTD_ = false;
@@ -476,16 +480,15 @@ void DetSDW::finishFermionic(int b) {
             check(dqmc_measure_eq_band_read_host(ctx_, eqb.data()), "dqmc_measure_eq_band_read_host");
             if ((int)eqb[0] != m) throw GeneralError(DQMC_EINVAL, "measurement sweep did not visit every time slice (equal-time band correlators)");
         }
-        for (int ch = 0; ch < (eqb.empty() ? 5 : 7); ++ch) {     // 5, 6: bandDiff, bandMix from the block of their own
-            c.eqCorr[ch].assign(N, 0.0); c.eqSq[ch].assign(N, 0.0);
-            const double* src = ch < 5 ? &eq[1 + (size_t)ch * N] : &eqb[1 + (size_t)(ch - 5) * N];
-            const double cnt = ch < 5 ? eq[0] : eqb[0];
-            for (int d = 0; d < N; ++d) c.eqCorr[ch][d] = src[d] / (double(N) * cnt);
+        // one channel: the raw sums src [N] of a block with `cnt` samples -> C(d) and S(q)
+        auto form = [&](const double* src, double cnt, std::vector<double>& corr, std::vector<double>& sqv) {
+            corr.assign(N, 0.0); sqv.assign(N, 0.0);
+            for (int d = 0; d < N; ++d) corr[d] = src[d] / (double(N) * cnt);
             for (int dy = 0; dy < L; ++dy)
                 for (int qx = 0; qx < L; ++qx) {
                     double sc = 0.0, ss = 0.0;
                     for (int dx = 0; dx < L; ++dx) {
-                        const double v = c.eqCorr[ch][dy * L + dx];
+                        const double v = corr[dy * L + dx];
                         sc += ct[(qx * dx) % L] * v; ss += st[(qx * dx) % L] * v;
                     }
                     Ac[(size_t)dy * L + qx] = sc; As[(size_t)dy * L + qx] = ss;
@@ -494,8 +497,16 @@ void DetSDW::finishFermionic(int b) {
                 for (int qx = 0; qx < L; ++qx) {
                     double sq = 0.0;
                     for (int dy = 0; dy < L; ++dy) sq += ct[(qy * dy) % L] * Ac[(size_t)dy * L + qx] - st[(qy * dy) % L] * As[(size_t)dy * L + qx];
-                    c.eqSq[ch][(size_t)qy * L + qx] = sq;
+                    sqv[(size_t)qy * L + qx] = sq;
                 }
+        };
+        for (int ch = 0; ch < (eqb.empty() ? 5 : 7); ++ch)       // 5, 6: bandDiff, bandMix from the block of their own
+            form(ch < 5 ? &eq[1 + (size_t)ch * N] : &eqb[1 + (size_t)(ch - 5) * N], ch < 5 ? eq[0] : eqb[0], c.eqCorr[ch], c.eqSq[ch]);
+        if (customEq()) {                                        // the user-defined bilinears, from theirs
+            std::vector<double> eqc(dqmc_measure_eq_custom_accum_size(ctx_));
+            check(dqmc_measure_eq_custom_read_host(ctx_, eqc.data()), "dqmc_measure_eq_custom_read_host");
+            if ((int)eqc[0] != m) throw GeneralError(DQMC_EINVAL, "measurement sweep did not visit every time slice (equal-time custom bilinears)");
+            for (int ch = 0; ch < customCount(); ++ch) form(&eqc[1 + (size_t)ch * N], eqc[0], c.customCorr[ch], c.customSq[ch]);
         }
     }
     // Time-displaced observables from one family of blocks: the coarse one (rows = interior boundaries j = 1 .. n-1) or, with
@@ -506,11 +517,12 @@ void DetSDW::finishFermionic(int b) {
                                    : "measurement sweep did not visit every stabilisation boundary";
         // the coarse blocks' (size, read) entry points by channel; the fine blocks share one pair that takes the channel
         struct Coarse { size_t (*size)(dqmc_ctx*); int (*read)(dqmc_ctx*, double*); const char* name; };
-        static const Coarse coarse[5] = {{dqmc_measure_td_accum_size, dqmc_measure_td_read_host, "dqmc_measure_td_read_host"},
+        static const Coarse coarse[6] = {{dqmc_measure_td_accum_size, dqmc_measure_td_read_host, "dqmc_measure_td_read_host"},
                                          {dqmc_measure_td_pair_accum_size, dqmc_measure_td_pair_read_host, "dqmc_measure_td_pair_read_host"},
                                          {dqmc_measure_td_ph_accum_size, dqmc_measure_td_ph_read_host, "dqmc_measure_td_ph_read_host"},
                                          {dqmc_measure_td_current_accum_size, dqmc_measure_td_current_read_host, "dqmc_measure_td_current_read_host"},
-                                         {dqmc_measure_td_band_accum_size, dqmc_measure_td_band_read_host, "dqmc_measure_td_band_read_host"}};
+                                         {dqmc_measure_td_band_accum_size, dqmc_measure_td_band_read_host, "dqmc_measure_td_band_read_host"},
+                                         {dqmc_measure_td_custom_accum_size, dqmc_measure_td_custom_read_host, "dqmc_measure_td_custom_read_host"}};
         auto read = [&](int channel, std::vector<double>& buf) {
             buf.resize(fine ? dqmc_measure_td_fine_accum_size(ctx_, channel) : coarse[channel].size(ctx_));
             if (fine) check(dqmc_measure_td_fine_read_host(ctx_, channel, buf.data()), "dqmc_measure_td_fine_read_host");
@@ -633,6 +645,27 @@ void DetSDW::finishFermionic(int b) {
                 }
             }
         }
+        // user-defined bilinears: the same normalisation, `count` rows of N per tau
+        if (customTd()) {
+            const int nc = customCount();
+            std::vector<double> tb;
+            read(5, tb);
+            for (int ch = 0; ch < nc; ++ch) { t.customTau[ch].assign((size_t)rows * N, 0.0); t.customTauQ0[ch].assign(rows, 0.0); }
+            for (int r = 0; r < rows; ++r) {
+                const double cnt = tb[r];
+                if (cnt < 1.0) throw GeneralError(DQMC_EINVAL, missing);
+                for (int ch = 0; ch < nc; ++ch) {
+                    const double* T = &tb[rows + ((size_t)r * nc + ch) * N];
+                    double q = 0.0;
+                    for (int d = 0; d < N; ++d) {
+                        const double v = T[d] / (double(N) * cnt);
+                        t.customTau[ch][(size_t)r * N + d] = v;
+                        q += v;
+                    }
+                    t.customTauQ0[ch][r] = q;
+                }
+            }
+        }
     };
     if (td_level(c.pars)) fill(false, c.td);
     // timeDisplacedFineOnDevice: the fine blocks stay on the device, their reader is getMatsubara
@@ -654,7 +687,8 @@ void DetSDW::getObservableVector(int which_in, double* out, int b) const {
     const bool fine = (which_in & DETSDW_OBS_FINE) != 0;
     const int which = which_in & ~DETSDW_OBS_FINE;
     const bool bandTau = which >= DETSDW_OBS_BANDDIFFTAU && which <= DETSDW_OBS_BANDMIXTAU_Q0;
-    if (fine && (which < DETSDW_OBS_GREENKTAU_X || which > DETSDW_OBS_BONDKINETICY) && !bandTau) throw ParameterWrong("unknown observable vector");
+    const bool customTau = which >= DETSDW_OBS_CUSTOMTAU && which < DETSDW_OBS_CUSTOMCORR;
+    if (fine && (which < DETSDW_OBS_GREENKTAU_X || which > DETSDW_OBS_BONDKINETICY) && !bandTau && !customTau) throw ParameterWrong("unknown observable vector");
     if (fine && !td_every_slice(c.pars)) throw ParameterWrong("the ...Fine observables need timeDisplacedEverySlice");
     if (fine && td_fine_on_device(c.pars))
         throw ParameterWrong("the ...Fine observables are not formed with timeDisplacedFineOnDevice: read the Matsubara transforms");
@@ -673,6 +707,19 @@ void DetSDW::getObservableVector(int which_in, double* out, int b) const {
         if (seriesNoHostCopy())
             throw ParameterWrong("the equal-time correlators are not copied to the host while a series with DETSDW_SERIES_NO_HOST_COPY is open: read the series");
         const std::vector<double>& e = which < DETSDW_OBS_BANDDIFFSQ ? c.eqCorr[5 + which - DETSDW_OBS_BANDDIFFCORR] : c.eqSq[5 + which - DETSDW_OBS_BANDDIFFSQ];
+        std::memcpy(out, e.data(), e.size() * sizeof(double));
+        return;
+    }
+    if (which >= DETSDW_OBS_CUSTOMTAU && which < DETSDW_OBS_CUSTOMSQ + DQMC_CUSTOM_MAX) {
+        const int ch = (which - DETSDW_OBS_CUSTOMTAU) % DQMC_CUSTOM_MAX;
+        if (ch >= customCount()) throw ParameterWrong("no user-defined bilinear with this index is set (detsdw_set_custom_bilinears)");
+        if (customTau ? !customTd() : !customEq())
+            throw ParameterWrong(customTau ? "custom{c}Tau needs timeDisplacedParticleHole" : "custom{c}Corr / custom{c}Sq need equalTimeCorrelators");
+        if (!customTau && seriesNoHostCopy())
+            throw ParameterWrong("the equal-time correlators are not copied to the host while a series with DETSDW_SERIES_NO_HOST_COPY is open: read the series");
+        const std::vector<double>& e = which < DETSDW_OBS_CUSTOMTAU_Q0 ? t.customTau[ch] : which < DETSDW_OBS_CUSTOMCORR ? t.customTauQ0[ch]
+                                     : which < DETSDW_OBS_CUSTOMSQ ? c.customCorr[ch] : c.customSq[ch];
+        if (e.empty()) throw GeneralError(DQMC_EINVAL, "no measurement sweep has run since the user-defined bilinears were set");
         std::memcpy(out, e.data(), e.size() * sizeof(double));
         return;
     }
@@ -708,7 +755,7 @@ void DetSDW::getObservableVector(int which_in, double* out, int b) const {
 // observables of all chains cost four calls per context.
 void DetSDW::invalidateMatsubara() {
     tdBlocksValid_ = false;
-    for (auto& g : groups_) for (int ch = 0; ch < 5; ++ch) g.matsNfreq[ch] = 0;
+    for (auto& g : groups_) for (int ch = 0; ch < 6; ++ch) g.matsNfreq[ch] = 0;
 }
 const double* DetSDW::matsubara(Group& g, int which, int nfreq, int& ncomp, int& comp) {
     const detsdw_params& p = ch_[0].pars;
@@ -718,8 +765,11 @@ const double* DetSDW::matsubara(Group& g, int which, int nfreq, int& ncomp, int&
     else if (which >= DETSDW_OBS_CHARGETAU && which <= DETSDW_OBS_SDWTAU) { channel = 2; comp = which - DETSDW_OBS_CHARGETAU; }
     else if (which == DETSDW_OBS_CURRENTXTAU || which == DETSDW_OBS_CURRENTYTAU) { channel = 3; comp = which - DETSDW_OBS_CURRENTXTAU; }
     else if (which == DETSDW_OBS_BANDDIFFTAU || which == DETSDW_OBS_BANDMIXTAU) { channel = 4; comp = which - DETSDW_OBS_BANDDIFFTAU; }
+    else if (which >= DETSDW_OBS_CUSTOMTAU && which < DETSDW_OBS_CUSTOMTAU_Q0) { channel = 5; comp = which - DETSDW_OBS_CUSTOMTAU; }
     else throw ParameterWrong("no Matsubara transform of this observable");
-    ncomp = channel == 2 ? 3 : 2;
+    ncomp = channel == 5 ? customCount() : channel == 2 ? 3 : 2;
+    if (channel == 5 && (!customTd() || comp >= customCount()))
+        throw ParameterWrong("custom{c}Tau needs a matrix set by detsdw_set_custom_bilinears and timeDisplacedParticleHole");
     if (!td_every_slice(p)) throw ParameterWrong("the Matsubara transforms need timeDisplacedEverySlice");
     if (channel == 1 && td_level(p) != 2) throw ParameterWrong("pairPlusTau / pairMinusTau need timeDisplacedMeasurements = 2");
     if (channel == 2 && !ph_level(p)) throw ParameterWrong("chargeTau / spinZTau / sdwTau need timeDisplacedParticleHole");
@@ -770,7 +820,9 @@ void DetSDW::seriesBegin(int binSize, int maxBins, int nfreq, int flags) {
         if (ph_level(p)) parts |= DQMC_SERIES_MATS_PH;
         if (ph_level(p) == 2) parts |= DQMC_SERIES_MATS_CURRENT;
         if (td_band(p)) parts |= DQMC_SERIES_MATS_BAND;
+        if (customTd()) parts |= DQMC_SERIES_MATS_CUSTOM;
     }
+    if (blocks && customEq()) parts |= DQMC_SERIES_EQ_CUSTOM;
     if (!parts) throw ParameterWrong("a measurement series needs equalTimeCorrelators or timeDisplacedEverySlice");
     size_t opened = 0;
     try {
@@ -791,7 +843,7 @@ void DetSDW::seriesBegin(int binSize, int maxBins, int nfreq, int flags) {
         for (size_t i = 0; i < opened; ++i) (void)dqmc_series_end(groups_[i].ctx);
         throw;
     }
-    series_.open = true; series_.binSize = binSize; series_.maxBins = maxBins; series_.nfreq = (parts & ~(DQMC_SERIES_EQ | DQMC_SERIES_EQ_BAND)) ? nfreq : 0;   // the phi part keeps nfreq too
+    series_.open = true; series_.binSize = binSize; series_.maxBins = maxBins; series_.nfreq = (parts & ~(DQMC_SERIES_EQ | DQMC_SERIES_EQ_BAND | DQMC_SERIES_EQ_CUSTOM)) ? nfreq : 0;   // the phi part keeps nfreq too
     series_.parts = parts; series_.flags = flags;
     seriesRoute_.resize(ch_.size());
     std::iota(seriesRoute_.begin(), seriesRoute_.end(), 0);
@@ -835,6 +887,16 @@ void DetSDW::seriesSlice(int which, int& part, size_t& offset, size_t& length) {
     } else if (which >= DETSDW_OBS_BANDDIFFCORR && which <= DETSDW_OBS_BANDMIXSQ) {
         if (!(series_.parts & DQMC_SERIES_EQ_BAND)) throw ParameterWrong("the equal-time band part of the series needs bandCorrelators with equalTimeCorrelators");
         part = 8; length = (size_t)N_; sub = (size_t)(which - DETSDW_OBS_BANDDIFFCORR) * N_;
+    } else if (which >= DETSDW_OBS_CUSTOMCORR && which < DETSDW_OBS_CUSTOMSQ + DQMC_CUSTOM_MAX) {
+        const int ch = (which - DETSDW_OBS_CUSTOMCORR) % DQMC_CUSTOM_MAX;
+        if (!(series_.parts & DQMC_SERIES_EQ_CUSTOM) || ch >= customCount())
+            throw ParameterWrong("the series holds no equal-time part of this user-defined bilinear");
+        part = 10; length = (size_t)N_; sub = (size_t)((which >= DETSDW_OBS_CUSTOMSQ ? customCount() : 0) + ch) * N_;
+    } else if (which >= DETSDW_OBS_CUSTOMTAU && which < DETSDW_OBS_CUSTOMTAU_Q0) {
+        const int ch = which - DETSDW_OBS_CUSTOMTAU;
+        if (!(series_.parts & DQMC_SERIES_MATS_CUSTOM) || ch >= customCount())
+            throw ParameterWrong("the series holds no Matsubara part of this user-defined bilinear");
+        part = 9; length = (size_t)series_.nfreq * N_ * 2; sub = (size_t)ch * length;
     } else if (which == DETSDW_OBS_PHICHI || which == DETSDW_OBS_PHISCALARS) {
         if (!(series_.parts & DQMC_SERIES_PHI)) throw ParameterWrong("the series has no order-parameter part: detsdw_series_begin with DETSDW_SERIES_PHI");
         part = 6;
@@ -921,6 +983,48 @@ void DetSDW::seriesBandDerived(int at, double* value, double* err) {
         v.resize((size_t)g.count * 3); e.resize((size_t)g.count * 3);
         check(dqmc_series_band_derived_host(g.ctx, v.data(), e.data()), "dqmc_series_band_derived_host");
         for (int b = 0; b < g.count; ++b) { value[g.first + b] = v[(size_t)b * 3 + at]; err[g.first + b] = e[(size_t)b * 3 + at]; }
+    }
+}
+// R of user-defined bilinear c at Q = (qx, qy) for every chain in handle order
+void DetSDW::seriesCustomDerived(int c, int qx, int qy, double* value, double* err) {
+    if (!series_.open) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
+    if (!(series_.parts & DQMC_SERIES_EQ_CUSTOM)) throw ParameterWrong("R_custom needs matrices set by detsdw_set_custom_bilinears before the series began, and equalTimeCorrelators");
+    const int nc = customCount();
+    if (c < 0 || c >= nc) throw ParameterWrong("no user-defined bilinear with this index is set");
+    std::vector<double> v, e;
+    for (auto& g : groups_) {
+        v.resize((size_t)g.count * nc); e.resize((size_t)g.count * nc);
+        check(dqmc_series_custom_derived_host(g.ctx, qx, qy, v.data(), e.data()), "dqmc_series_custom_derived_host");
+        for (int b = 0; b < g.count; ++b) { value[g.first + b] = v[(size_t)b * nc + c]; err[g.first + b] = e[(size_t)b * nc + c]; }
+    }
+}
+bool DetSDW::customTd() const { return customCount() && ph_level(ch_[0].pars); }
+bool DetSDW::customEq() const { return customCount() && eq_correlators(ch_[0].pars); }
+void DetSDW::setCustomBilinears(int count, const dqmc_cplx* M) {
+    const detsdw_params& p = ch_[0].pars;
+    if (!eq_correlators(p) && !ph_level(p)) throw ParameterWrong("custom bilinears need equalTimeCorrelators or timeDisplacedParticleHole");
+    if (count < 0 || count > DQMC_CUSTOM_MAX || (count && !M)) throw ParameterWrong("detsdw_set_custom_bilinears: count must be in 0 .. 4, with the matrices");
+    // such a series has no part for matrices set after it began and suppresses the host copy: their equal-time block would land nowhere
+    if (seriesNoHostCopy()) throw ParameterWrong("custom bilinears cannot be set while a series with DETSDW_SERIES_NO_HOST_COPY is open");
+    // The kernel contexts validate alike, so a refusal of the matrices comes from the first one and nothing has changed.  An allocation
+    // can fail in a later one: the contexts that already took the new matrices get the old ones back (their blocks cleared), so that
+    // every context and customM_ agree again before the error is passed on.
+    for (size_t i = 0; i < groups_.size(); ++i) {
+        const int rc = dqmc_set_custom_bilinears(groups_[i].ctx, count, M);
+        if (rc == DQMC_OK) continue;
+        const std::string why = dqmc_last_error();
+        for (size_t k = 0; k < i; ++k)
+            if (dqmc_set_custom_bilinears(groups_[k].ctx, customCount(), customM_.data()) != DQMC_OK)
+                throw GeneralError(rc, "dqmc_set_custom_bilinears: " + why + "; restoring the earlier matrices failed as well: the handle's kernel contexts disagree, destroy it");
+        throw GeneralError(rc, "dqmc_set_custom_bilinears: " + why);
+    }
+    customM_.assign(M, M + (size_t)16 * count);
+    for (auto& g : groups_) g.matsNfreq[5] = 0;            // the other channels' transforms and blocks are untouched
+    for (auto& c : ch_) {
+        for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) {
+            c.customCorr[ch].clear(); c.customSq[ch].clear();
+            for (TdObs* t : {&c.td, &c.tdFine}) { t->customTau[ch].clear(); t->customTauQ0[ch].clear(); }
+        }
     }
 }
 void DetSDW::seriesReadBins(int which, int first, int count, double* out, int b) {
@@ -1462,6 +1566,11 @@ void DetSDW::seriesSave(const std::string& path) {
             wr(fc.f, row.data(), row.size() * sizeof(double));
         }
     }
+    if (st.parts & (DQMC_SERIES_MATS_CUSTOM | DQMC_SERIES_EQ_CUSTOM)) {     // behind everything else: files of other series keep their bytes
+        const int32_t nc = customCount();
+        wr(fc.f, &nc, sizeof(nc));
+        wr(fc.f, customM_.data(), customM_.size() * sizeof(dqmc_cplx));
+    }
 }
 
 void DetSDW::seriesLoad(const std::string& path) {
@@ -1496,6 +1605,15 @@ void DetSDW::seriesLoad(const std::string& path) {
     const size_t S = st.sample_len, B = (size_t)st.bins_closed, extra = seriesExtra(st.flags);
     std::vector<double> slots((size_t)nch * (B + extra) * S);
     rd(fc.f, slots.data(), slots.size() * sizeof(double));
+    if (st.parts & (DQMC_SERIES_MATS_CUSTOM | DQMC_SERIES_EQ_CUSTOM)) {
+        int32_t nc = -1;
+        rd(fc.f, &nc, sizeof(nc));
+        if (nc != customCount()) throw ParameterWrong("series file: written with a different number of user-defined bilinears");
+        std::vector<dqmc_cplx> M((size_t)16 * nc);
+        rd(fc.f, M.data(), M.size() * sizeof(dqmc_cplx));
+        if (std::memcmp(M.data(), customM_.data(), M.size() * sizeof(dqmc_cplx)) != 0)
+            throw ParameterWrong("series file: written with other user-defined bilinears than the ones that are set");
+    }
     char more;
     if (std::fread(&more, 1, 1, fc.f) != 0) throw GeneralError(DQMC_EINVAL, "series file: longer than its header says");
     std::vector<double> buf;
@@ -1603,6 +1721,13 @@ extern "C" int detsdw_series_stats_all(detsdw_replica* r, int which, double* mea
 extern "C" int detsdw_series_derived_all(detsdw_replica* r, int what, double* value, double* err) {
     if (!value || !err) { g_host_err = "null argument"; return DQMC_EINVAL; }
     RGUARD(r->impl->seriesDerivedAll(what, value, err))
+}
+extern "C" int detsdw_set_custom_bilinears(detsdw_replica* r, int count, const dqmc_cplx* M) {
+    RGUARD(r->impl->setCustomBilinears(count, M))
+}
+extern "C" int detsdw_series_custom_derived(detsdw_replica* r, int c, int qx, int qy, double* value, double* err) {
+    if (!value || !err) { g_host_err = "null argument"; return DQMC_EINVAL; }
+    RGUARD(r->impl->seriesCustomDerived(c, qx, qy, value, err))
 }
 extern "C" int detsdw_series_band_derived(detsdw_replica* r, int what, double* value, double* err) {
     if (!value || !err) { g_host_err = "null argument"; return DQMC_EINVAL; }

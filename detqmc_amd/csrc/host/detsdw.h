@@ -71,6 +71,9 @@ public:
     void seriesStatsAll(int which, double* mean, double* err);
     void seriesDerivedAll(int what, double* value, double* err);
     void seriesBandDerived(int at, double* value, double* err);
+    void seriesCustomDerived(int c, int qx, int qy, double* value, double* err);
+    // user-defined bilinears (include/detsdw_host.h): count Hermitian 4 x 4 matrices for every kernel context, between sweeps
+    void setCustomBilinears(int count, const dqmc_cplx* M);
     void seriesReadBins(int which, int first, int count, double* out, int b = 0);
     // long runs: options, re-binning, binning analysis (err, tau [levels] x the slice of seriesStats; tau may be null), series file
     void seriesConfigure(int flags);
@@ -103,6 +106,7 @@ private:
         std::vector<double> phTau[3], phTauQ0[3];           // charge, spinZ, sdw: rows x N and the row sums (timeDisplacedParticleHole)
         std::vector<double> currentTau[2], currentTauQ0[2], bondKinetic[2];   // x, y: rows x N, row sums, rows (timeDisplacedParticleHole == 2)
         std::vector<double> bandTau[2], bandTauQ0[2];       // bandDiff, bandMix: rows x N and the row sums (DETSDW_TD_PH_BAND)
+        std::vector<double> customTau[DQMC_CUSTOM_MAX], customTauQ0[DQMC_CUSTOM_MAX];   // the same per user-defined bilinear (setCustomBilinears)
     };
     struct Chain {
         detsdw_params pars;
@@ -118,6 +122,7 @@ private:
         detsdw_observables obs{};
         std::vector<double> kOccX, kOccY, pairPlus, pairMinus;
         std::vector<double> eqCorr[7], eqSq[7];    // charge, spinZ, sdw, pairPlus, pairMinus: C(d) and S(q), N each (DETSDW_FM_EQ_CORRELATORS); 5, 6: bandDiff, bandMix (DETSDW_FM_EQ_BAND)
+        std::vector<double> customCorr[DQMC_CUSTOM_MAX], customSq[DQMC_CUSTOM_MAX];   // C(d) and S(q) of the user-defined bilinears, N each
         TdObs td, tdFine;                      // rows = interior boundaries j = 1 .. n-1 / time slices k = 0 .. m (timeDisplacedEverySlice)
         Chain(const detsdw_params& p) : pars(p), rng(p.rngSeed, (uint32_t)p.simindex + 1u) {}   // detqmc.h:181
     };
@@ -127,8 +132,8 @@ private:
         int first = 0, count = 0;
         std::vector<double> window;                // uniforms of the coming sweep, all chains of the group
         std::vector<double> fields;                // host staging of all chains' fields (global moves)
-        std::vector<double> mats[5];               // Matsubara transforms of the group's chains per channel, [chain][component][nfreq][N] (re, im)
-        int matsNfreq[5] = {0, 0, 0, 0, 0};          // ... and the nfreq they hold (0: none); cleared by every sweep
+        std::vector<double> mats[6];               // Matsubara transforms of the group's chains per channel, [chain][component][nfreq][N] (re, im)
+        int matsNfreq[6] = {0, 0, 0, 0, 0, 0};          // ... and the nfreq they hold (0: none); cleared by every sweep
         std::vector<double> seriesMean, seriesErr; // dqmc_series_stats_host of the group's chains, [chain][S] each ...
         int seriesStatsBins = 0;                   // ... and the number of closed bins they were formed from (0: none)
         std::vector<double> seriesBinErr, seriesBinTau;   // dqmc_series_binning_host of the group's chains, [level][chain][S] each ...
@@ -140,6 +145,10 @@ private:
     int N_, MSF_, ng_, m_, s_, n_, opdim_;
     SweepDirection lastSweepDir_ = Up;
     int performedSweeps_ = 0;
+    std::vector<dqmc_cplx> customM_;               // the matrices of setCustomBilinears, [count][4][4] (every kernel context holds the same)
+    int customCount() const { return (int)customM_.size() / 16; }
+    bool customTd() const;                         // matrices are set and the handle measures the particle-hole family
+    bool customEq() const;                         // ... the equal-time correlators
 
     Group& grp(int b) { return groups_[(size_t)b / (size_t)groups_[0].count]; }
     static void check(int rc, const char* what);

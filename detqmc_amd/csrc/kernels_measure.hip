@@ -1017,6 +1017,278 @@ void launch_measure_eq_band(const Launch& lc, const DevModel& hm, const cplx* gs
     }
 }
 
+// User-defined bilinears (dqmc_set_custom_bilinears; definitions in dqmc_hip.h and DESIGN.md 6e): the W^M(A, B) of k_measure_td_ph for up to
+// DQMC_CUSTOM_MAX Hermitian 4 x 4 matrices that arrive as a kernel argument, all channels in ONE launch.  Per site pair the blocks
+//   E_bc = g~(tau,0)(A b; B c)      and      T_da = g~(0,tau)(B d; A a) = conj hs(A a; B d)
+// are loaded once (4 + 4 complex for OPDIM < 3, 16 + 16 for O(3)); the connected part of a channel is Re tr(M E M T), formed for a = 0 .. 3
+// from row a of M E and column a of M T.  OPDIM < 3: only the (XUP, YDOWN) sector is stored, the (XDOWN, YUP) sector is its complex
+// conjugate and the blocks between the sectors vanish (GreenAccess), which cst_E / cst_same resolve at compile time after unrolling -- a
+// matrix that couples the sectors is as legal as any other.  A 16-bit mask per channel (bit 4 a + b: M_ab != 0) skips the structural
+// zeros; it is uniform over the launch, so no wave diverges.  Grid shape, walk order over B, LDS reduction, one writer per accumulator and
+// fixed summation order: those of k_measure_td_band.  The blocks and the one-body scratch live outside the arena: chain b at
+// acc + b * acs and ob + b * obs.
+struct CustomMats { cplx m[DQMC_CUSTOM_MAX][4][4]; unsigned mask[DQMC_CUSTOM_MAX]; int count; };
+size_t measure_custom_row_doubles(int count, int N) { return (size_t)count * N; }
+size_t measure_td_custom_onebody_cplx(int count, int N) { return (size_t)2 * count * N; }
+size_t measure_eq_custom_onebody_cplx(int count, int N) { return (size_t)2 * count * N; }
+
+template<int OPDIM> __device__ __forceinline__ constexpr bool cst_same(int r, int c) { return OPDIM == 3 || ((r < 2) == (c < 2)); }
+// element (r, c), r and c in the same sector, of the full 4 x 4 block whose stored part is x
+template<int OPDIM, int R>
+__device__ __forceinline__ cplx cst_E(const cplx (&x)[R][R], int r, int c) {
+    if (OPDIM == 3 || r < 2) return x[r & (R - 1)][c & (R - 1)];
+    const cplx v = x[r - 2][c - 2];
+    return make_double2(v.x, -v.y);
+}
+__device__ __forceinline__ void cst_fma(cplx& acc, cplx a, cplx b) {
+    acc.x = fma(a.x, b.x, fma(-a.y, b.y, acc.x));
+    acc.y = fma(a.x, b.y, fma(a.y, b.x, acc.y));
+}
+// Re tr(M E M T); e[r][c] = E_rc, t[r][c] = T_rc of the stored part
+template<int OPDIM, int R>
+__device__ __forceinline__ double cst_connected(const cplx (&e)[R][R], const cplx (&t)[R][R], const cplx (&M)[4][4], unsigned mask) {
+    double s = 0.0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        cplx x[4], y[4];                                    // x[c] = (M E)_ac, y[c] = (M T)_ca
+#pragma unroll
+        for (int c2 = 0; c2 < 4; ++c2) x[c2] = y[c2] = make_double2(0.0, 0.0);
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+            if (mask & (1u << (4 * a + b))) {
+#pragma unroll
+                for (int c2 = 0; c2 < 4; ++c2)
+                    if (cst_same<OPDIM>(b, c2)) cst_fma(x[c2], M[a][b], cst_E<OPDIM, R>(e, b, c2));
+            }
+#pragma unroll
+        for (int c2 = 0; c2 < 4; ++c2)
+#pragma unroll
+            for (int dl = 0; dl < 4; ++dl)
+                if (cst_same<OPDIM>(dl, a) && (mask & (1u << (4 * c2 + dl)))) cst_fma(y[c2], M[c2][dl], cst_E<OPDIM, R>(t, dl, a));
+#pragma unroll
+        for (int c2 = 0; c2 < 4; ++c2) s += x[c2].x * y[c2].x - x[c2].y * y[c2].y;
+    }
+    return s;
+}
+// tr M - sum_ab M_ab g(A b; A a) of site A from the shifted equal-time matrix gs; with tr M = 0 handed in: -sum_ab M_ab g(A b; A a)
+template<int OPDIM>
+__device__ __forceinline__ cplx cst_onebody(const cplx* __restrict__ gs, int ng, int N, int A, const cplx (&M)[4][4], unsigned mask, bool with_trace) {
+    constexpr int R = OPDIM == 3 ? 4 : 2;
+    const cplx* p = gs + (size_t)A * ng + A;                // g(r, c) = gs(A r; A c) = p[c N ng + r N]
+    cplx g[R][R];
+#pragma unroll
+    for (int c2 = 0; c2 < R; ++c2)
+#pragma unroll
+        for (int r = 0; r < R; ++r) g[r][c2] = p[(size_t)c2 * N * ng + (size_t)r * N];
+    cplx v = make_double2(0.0, 0.0);
+    if (with_trace) v = m_add(m_add(M[0][0], M[1][1]), m_add(M[2][2], M[3][3]));
+    cplx s = make_double2(0.0, 0.0);
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+            if (cst_same<OPDIM>(b, a) && (mask & (1u << (4 * a + b)))) cst_fma(s, M[a][b], cst_E<OPDIM, R>(g, b, a));
+    return m_sub(v, s);
+}
+
+// ob[chain][t][channel][site] for one of the two equal-time matrices (t = 0: G(tau), t = 1: G(0)); gs is its shifted form
+template<int OPDIM>
+__global__ __launch_bounds__(256) void k_td_custom_onebody(DevModel dm, CustomMats cm, const cplx* __restrict__ gs, cplx* __restrict__ ob, int t,
+                                                           size_t obs, size_t cs) {
+    CHAIN(gs);
+    const int N = dm.N, A = blockIdx.x * 256 + threadIdx.x;
+    if (A >= N) return;
+    cplx* o = ob + (size_t)blockIdx.z * obs + (size_t)t * cm.count * N + A;
+#pragma unroll
+    for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
+        if (ch < cm.count) o[(size_t)ch * N] = cst_onebody<OPDIM>(gs, dm.ng, N, A, cm.m[ch], cm.mask[ch], true);
+}
+
+template<int OPDIM>
+__global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_td_custom(DevModel dm, CustomMats cm, const cplx* __restrict__ gs,
+                                                                            const cplx* __restrict__ hs, const cplx* __restrict__ ob,
+                                                                            double* __restrict__ acc, int row, int rows, size_t obs, size_t acs, size_t cs) {
+    CHAIN(gs); CHAIN(hs);
+    constexpr int R = OPDIM == 3 ? 4 : 2;
+    ob += (size_t)blockIdx.z * obs;
+    acc += (size_t)blockIdx.z * acs;
+    __shared__ double red[DQMC_CUSTOM_MAX][TDP_PARTS][TDP_BINS];
+    const int N = dm.N, L = dm.L, tid = threadIdx.x, count = cm.count;
+    const size_t ng = (size_t)dm.ng;
+    const int lb = tid % TDP_BINS, part = tid / TDP_BINS;
+    const int d = blockIdx.x * TDP_BINS + lb;
+    const bool valid = d < N;
+    const int dx = valid ? d % L : 0, dy = valid ? d / L : 0;
+    const cplx* ot = ob;                                    // o_tau(A)
+    const cplx* o0 = ob + (size_t)count * N;                // o_0(B)
+    double w[DQMC_CUSTOM_MAX] = {0.0, 0.0, 0.0, 0.0};
+    if (valid) {
+        int bx = part % L, by = part / L;                   // site B = part + 8 i, kept as (bx, by)
+        const int stepx = TDP_PARTS % L, stepy = TDP_PARTS / L;
+        for (int B = part; B < N; B += TDP_PARTS) {
+            int ax = bx + dx, ay = by + dy;
+            if (ax >= L) ax -= L;
+            if (ay >= L) ay -= L;
+            const int A = ay * L + ax;
+            const size_t off = (size_t)B * ng + (size_t)A;
+            const cplx* pe = gs + off;
+            const cplx* ph = hs + off;
+            cplx e[R][R], t[R][R];
+#pragma unroll
+            for (int c2 = 0; c2 < R; ++c2)
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    e[r][c2] = pe[(size_t)c2 * N * ng + (size_t)r * N];
+                    const cplx h = ph[(size_t)c2 * N * ng + (size_t)r * N];      // hs(A r; B c2) = conj T_(c2 r)
+                    t[c2][r] = make_double2(h.x, -h.y);
+                }
+#pragma unroll
+            for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
+                if (ch < count) {
+                    const cplx a = ot[(size_t)ch * N + A], b = o0[(size_t)ch * N + B];
+                    w[ch] += (a.x * b.x - a.y * b.y) - cst_connected<OPDIM, R>(e, t, cm.m[ch], cm.mask[ch]);
+                }
+            bx += stepx; by += stepy;
+            if (bx >= L) { bx -= L; ++by; }
+        }
+    }
+#pragma unroll
+    for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) red[ch][part][lb] = w[ch];
+    __syncthreads();
+    if (part < count && valid) {                            // part ch writes channel ch of its bin
+        double s = red[part][0][lb];
+#pragma unroll
+        for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
+        acc[rows + (size_t)row * count * N + (size_t)part * N + d] += s;
+    }
+    if (blockIdx.x == 0 && tid == 0) acc[row] += 1.0;
+}
+
+static CustomMats custom_mats(int count, const cplx* M, const unsigned* mask) {
+    CustomMats cm{};
+    cm.count = count;
+    for (int ch = 0; ch < count; ++ch) {
+        cm.mask[ch] = mask[ch];
+        for (int k = 0; k < 16; ++k) cm.m[ch][k / 4][k % 4] = M[16 * ch + k];
+    }
+    return cm;
+}
+
+void launch_td_custom_onebody(const Launch& lc, const DevModel& hm, int count, const cplx* M, const unsigned* mask, const cplx* gs, cplx* ob, int t) {
+    const CustomMats cm = custom_mats(count, M, mask);
+    const dim3 grid((hm.N + 255) / 256, 1, lc.nb);
+    const size_t obs = measure_td_custom_onebody_cplx(count, hm.N);
+    if (hm.opdim == 1) hipLaunchKernelGGL((k_td_custom_onebody<1>), grid, dim3(256), 0, lc.st, hm, cm, gs, ob, t, obs, lc.cs);
+    else if (hm.opdim == 2) hipLaunchKernelGGL((k_td_custom_onebody<2>), grid, dim3(256), 0, lc.st, hm, cm, gs, ob, t, obs, lc.cs);
+    else hipLaunchKernelGGL((k_td_custom_onebody<3>), grid, dim3(256), 0, lc.st, hm, cm, gs, ob, t, obs, lc.cs);
+}
+
+void launch_measure_td_custom(const Launch& lc, const DevModel& hm, int count, const cplx* M, const unsigned* mask, const cplx* gs, const cplx* hs,
+                              const cplx* ob, double* acc, size_t acs, int row, int rows) {
+    const CustomMats cm = custom_mats(count, M, mask);
+    const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
+    const size_t obs = measure_td_custom_onebody_cplx(count, hm.N);
+    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_td_custom<1>), grid, block, 0, lc.st, hm, cm, gs, hs, ob, acc, row, rows, obs, acs, lc.cs);
+    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_td_custom<2>), grid, block, 0, lc.st, hm, cm, gs, hs, ob, acc, row, rows, obs, acs, lc.cs);
+    else hipLaunchKernelGGL((k_measure_td_custom<3>), grid, block, 0, lc.st, hm, cm, gs, hs, ob, acc, row, rows, obs, acs, lc.cs);
+}
+
+// Equal-time form (dqmc_set_equal_time_custom): one matrix gs in both roles as in k_measure_eq_band, the transposed factor read in place,
+// T_da = gs(B d; A a) = gs[(A + N a) ng + B + N d].  M^2 = 1 is not assumed: the delta term sum_bc (M^2)_cb gs(B b; B c) goes to the d = 0
+// bin from a one-body value of its own, formed with M^2 (cm2, trace left out) by the routine that forms o^M.
+// ob[chain][o^M: count][delta: count][N]; block of one chain: count, then the channels [N] each.
+template<int OPDIM>
+__global__ __launch_bounds__(256) void k_eq_custom_onebody(DevModel dm, CustomMats cm, CustomMats cm2, const cplx* __restrict__ gs, cplx* __restrict__ ob,
+                                                           size_t obs, size_t cs) {
+    CHAIN(gs);
+    const int N = dm.N, A = blockIdx.x * 256 + threadIdx.x;
+    if (A >= N) return;
+    cplx* o = ob + (size_t)blockIdx.z * obs + A;
+#pragma unroll
+    for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
+        if (ch < cm.count) {
+            o[(size_t)ch * N] = cst_onebody<OPDIM>(gs, dm.ng, N, A, cm.m[ch], cm.mask[ch], true);
+            const cplx dl = cst_onebody<OPDIM>(gs, dm.ng, N, A, cm2.m[ch], cm2.mask[ch], false);     // -sum_bc (M^2)_cb gs(A b; A c)
+            o[(size_t)(cm.count + ch) * N] = make_double2(-dl.x, -dl.y);
+        }
+}
+
+template<int OPDIM>
+__global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_eq_custom(DevModel dm, CustomMats cm, const cplx* __restrict__ gs,
+                                                                            const cplx* __restrict__ ob, double* __restrict__ acc, size_t obs, size_t acs,
+                                                                            size_t cs) {
+    CHAIN(gs);
+    constexpr int R = OPDIM == 3 ? 4 : 2;
+    ob += (size_t)blockIdx.z * obs;
+    acc += (size_t)blockIdx.z * acs;
+    __shared__ double red[DQMC_CUSTOM_MAX][TDP_PARTS][TDP_BINS];
+    const int N = dm.N, L = dm.L, tid = threadIdx.x, count = cm.count;
+    const size_t ng = (size_t)dm.ng;
+    const int lb = tid % TDP_BINS, part = tid / TDP_BINS;
+    const int d = blockIdx.x * TDP_BINS + lb;
+    const bool valid = d < N;
+    const int dx = valid ? d % L : 0, dy = valid ? d / L : 0;
+    double w[DQMC_CUSTOM_MAX] = {0.0, 0.0, 0.0, 0.0};
+    if (valid) {
+        int bx = part % L, by = part / L;                   // site B = part + 8 i, kept as (bx, by)
+        const int stepx = TDP_PARTS % L, stepy = TDP_PARTS / L;
+        for (int B = part; B < N; B += TDP_PARTS) {
+            int ax = bx + dx, ay = by + dy;
+            if (ax >= L) ax -= L;
+            if (ay >= L) ay -= L;
+            const int A = ay * L + ax;
+            const cplx* pe = gs + (size_t)B * ng + (size_t)A;     // E_rc = gs(A r; B c) = pe[c N ng + r N]
+            const cplx* pt = gs + (size_t)A * ng + (size_t)B;     // T_rc = gs(B r; A c) = pt[c N ng + r N]
+            cplx e[R][R], t[R][R];
+#pragma unroll
+            for (int c2 = 0; c2 < R; ++c2)
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    e[r][c2] = pe[(size_t)c2 * N * ng + (size_t)r * N];
+                    t[r][c2] = pt[(size_t)c2 * N * ng + (size_t)r * N];
+                }
+#pragma unroll
+            for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
+                if (ch < count) {
+                    const cplx a = ob[(size_t)ch * N + A], b = ob[(size_t)ch * N + B];
+                    double v = (a.x * b.x - a.y * b.y) - cst_connected<OPDIM, R>(e, t, cm.m[ch], cm.mask[ch]);
+                    if (d == 0) v += ob[(size_t)(count + ch) * N + B].x;      // the delta term
+                    w[ch] += v;
+                }
+            bx += stepx; by += stepy;
+            if (bx >= L) { bx -= L; ++by; }
+        }
+    }
+#pragma unroll
+    for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) red[ch][part][lb] = w[ch];
+    __syncthreads();
+    if (part < count && valid) {                            // part ch writes channel ch of its bin
+        double s = red[part][0][lb];
+#pragma unroll
+        for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
+        acc[1 + (size_t)part * N + d] += s;
+    }
+    if (blockIdx.x == 0 && tid == 0) acc[0] += 1.0;
+}
+
+void launch_measure_eq_custom(const Launch& lc, const DevModel& hm, int count, const cplx* M, const unsigned* mask, const cplx* M2, const unsigned* mask2,
+                              const cplx* gs, cplx* ob, double* acc) {
+    const CustomMats cm = custom_mats(count, M, mask), cm2 = custom_mats(count, M2, mask2);
+    const dim3 g1((hm.N + 255) / 256, 1, lc.nb);
+    const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
+    const size_t obs = measure_eq_custom_onebody_cplx(count, hm.N), acs = 1 + measure_custom_row_doubles(count, hm.N);
+    if (hm.opdim == 1) {
+        hipLaunchKernelGGL((k_eq_custom_onebody<1>), g1, dim3(256), 0, lc.st, hm, cm, cm2, gs, ob, obs, lc.cs);
+        hipLaunchKernelGGL((k_measure_eq_custom<1>), grid, block, 0, lc.st, hm, cm, gs, ob, acc, obs, acs, lc.cs);
+    } else if (hm.opdim == 2) {
+        hipLaunchKernelGGL((k_eq_custom_onebody<2>), g1, dim3(256), 0, lc.st, hm, cm, cm2, gs, ob, obs, lc.cs);
+        hipLaunchKernelGGL((k_measure_eq_custom<2>), grid, block, 0, lc.st, hm, cm, gs, ob, acc, obs, acs, lc.cs);
+    } else {
+        hipLaunchKernelGGL((k_eq_custom_onebody<3>), g1, dim3(256), 0, lc.st, hm, cm, cm2, gs, ob, obs, lc.cs);
+        hipLaunchKernelGGL((k_measure_eq_custom<3>), grid, block, 0, lc.st, hm, cm, gs, ob, acc, obs, acs, lc.cs);
+    }
+}
+
 // End rows of the every-slice blocks (dqmc_measure_timedisplaced_ends): from the equal-time G = G(0), one elementwise pass writes
 //   tau = 0+:    G(0+,0) = G,          G(0,0+) = G - 1          -> a_t0, a_0t
 //   tau = beta-: G(beta-,0) = 1 - G,   G(0,beta-) = -G          -> b_t0, b_0t
@@ -1186,18 +1458,19 @@ static int tdm_ftile(const DevModel& hm, int channel, int nfreq) {
 }
 bool td_matsubara_fits(const DevModel& hm, int channel, int nfreq) { return tdm_ftile(hm, channel, nfreq) >= 1; }
 bool launch_td_matsubara(const Launch& lc, const DevModel& hm, const double* acc, int channel, int nfreq, int apbx, int apby,
-                         double* out, double* bad, size_t out_chain_stride) {
+                         double* out, double* bad, size_t out_chain_stride, int custom_count, size_t custom_chain_bytes) {
     const int L = hm.L, N = hm.N, m = hm.m, W = channel == 0 ? 2 * L - 1 : L;
-    const int rlen = channel == 0 ? 2 * W * W : N, ncomp = channel == 2 ? 3 : 2;
+    const int rlen = channel == 0 ? 2 * W * W : N, ncomp = channel == 5 ? custom_count : channel == 2 ? 3 : 2;
+    const int stride = channel == 5 ? (int)measure_custom_row_doubles(custom_count, N) : (int)measure_td_row_doubles(channel, N, L);
     const int ftile = tdm_ftile(hm, channel, nfreq);
     if (ftile < 1) return false;
     const size_t lds = measure_td_matsubara_lds_doubles(ftile, m, L, W, rlen) * sizeof(double);
     if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)k_td_matsubara, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         (void)hipGetLastError();                            // the launch below then reports the problem
-    TdmShape a{channel, ncomp, nfreq, ftile, m, L, N, W, W | 1, rlen, (int)measure_td_row_doubles(channel, N, L), apbx, apby,
+    TdmShape a{channel, ncomp, nfreq, ftile, m, L, N, W, W | 1, rlen, stride, apbx, apby,
                hm.dtau / (channel == 0 ? 2.0 * N : (double)N), out_chain_stride ? out_chain_stride : (size_t)ncomp * nfreq * N * 2};
     const dim3 grid((nfreq + ftile - 1) / ftile, ncomp, lc.nb);
-    hipLaunchKernelGGL(k_td_matsubara, grid, dim3(256), lds, lc.st, acc, out, bad, a, lc.cs);
+    hipLaunchKernelGGL(k_td_matsubara, grid, dim3(256), lds, lc.st, acc, out, bad, a, channel == 5 ? custom_chain_bytes : lc.cs);
     return true;
 }
 
@@ -1377,17 +1650,9 @@ void launch_series_derived(const Launch& lc, const DevModel& hm, const double* b
 // 0: bandDiff at Q = (L/2, L/2), 1: bandDiff at Q = (0, 0), 2: bandMix at Q = (L/2, L/2).  off = offset of the part inside a sample,
 // S_X(q) at off + (2 + X) N.  One thread per (chain, entry).
 struct SeriesBandDerivedShape { size_t S, off; int L, N, nb, B; };
-__global__ __launch_bounds__(64) void k_series_band_derived(const double* __restrict__ bins, SeriesBandDerivedShape a, double* __restrict__ value,
-                                                            double* __restrict__ err) {
-    const int t = blockIdx.x * 64 + threadIdx.x;
-    if (t >= a.nb * 3) return;
-    const int chain = t / 3, e = t - chain * 3, L = a.L, N = a.N;
-    const int Q = e == 1 ? 0 : L / 2, q1 = (Q + 1) % L;
-    const size_t base = a.off + (size_t)(2 + (e == 2 ? 1 : 0)) * N;
-    const size_t idx[3] = {base + (size_t)Q * L + Q, base + (size_t)Q * L + q1, base + (size_t)q1 * L + Q};
-    const size_t n = (size_t)a.nb * a.S;
-    const double* p = bins + (size_t)chain * a.S;
-    const int B = a.B;
+// value and jackknife error of R over the B closed bins of one chain (p: its row of bin 0, n: distance between bins) from the three
+// sample entries idx = S(Q), S(Q + dx), S(Q + dy)
+__device__ __forceinline__ void series_ratio_jackknife(const double* __restrict__ p, size_t n, int B, const size_t (&idx)[3], double& value, double& err) {
     double mu[3], tot[3], x[3];
     for (int j = 0; j < 3; ++j) {
         double sum = 0.0;
@@ -1406,8 +1671,35 @@ __global__ __launch_bounds__(64) void k_series_band_derived(const double* __rest
         const double d = series_derived_f(0, x) - tbar;
         acc += d * d;
     }
-    value[t] = series_derived_f(0, mu);
-    err[t] = sqrt((double)(B - 1) / (double)B * acc);
+    value = series_derived_f(0, mu);
+    err = sqrt((double)(B - 1) / (double)B * acc);
+}
+__global__ __launch_bounds__(64) void k_series_band_derived(const double* __restrict__ bins, SeriesBandDerivedShape a, double* __restrict__ value,
+                                                            double* __restrict__ err) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= a.nb * 3) return;
+    const int chain = t / 3, e = t - chain * 3, L = a.L, N = a.N;
+    const int Q = e == 1 ? 0 : L / 2, q1 = (Q + 1) % L;
+    const size_t base = a.off + (size_t)(2 + (e == 2 ? 1 : 0)) * N;
+    const size_t idx[3] = {base + (size_t)Q * L + Q, base + (size_t)Q * L + q1, base + (size_t)q1 * L + Q};
+    series_ratio_jackknife(bins + (size_t)chain * a.S, (size_t)a.nb * a.S, a.B, idx, value[t], err[t]);
+}
+// the same for the equal-time part of the user-defined bilinears, out[chain][count]: R of matrix e at the caller's Q = (qx, qy);
+// S_e(q) at off + (count + e) N
+struct SeriesCustomDerivedShape { size_t S, off; int L, N, nb, B, count, qx, qy; };
+__global__ __launch_bounds__(64) void k_series_custom_derived(const double* __restrict__ bins, SeriesCustomDerivedShape a, double* __restrict__ value,
+                                                              double* __restrict__ err) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= a.nb * a.count) return;
+    const int chain = t / a.count, e = t - chain * a.count, L = a.L;
+    const size_t base = a.off + (size_t)(a.count + e) * a.N;
+    const size_t idx[3] = {base + (size_t)a.qy * L + a.qx, base + (size_t)a.qy * L + (a.qx + 1) % L, base + (size_t)((a.qy + 1) % L) * L + a.qx};
+    series_ratio_jackknife(bins + (size_t)chain * a.S, (size_t)a.nb * a.S, a.B, idx, value[t], err[t]);
+}
+void launch_series_custom_derived(const Launch& lc, const DevModel& hm, const double* bins, size_t S, int B, size_t off, int count, int qx, int qy,
+                                  double* value, double* err) {
+    SeriesCustomDerivedShape a{S, off, hm.L, hm.N, lc.nb, B, count, qx, qy};
+    hipLaunchKernelGGL(k_series_custom_derived, dim3((unsigned)((lc.nb * count + 63) / 64)), dim3(64), 0, lc.st, bins, a, value, err);
 }
 void launch_series_band_derived(const Launch& lc, const DevModel& hm, const double* bins, size_t S, int B, size_t off, double* value, double* err) {
     SeriesBandDerivedShape a{S, off, hm.L, hm.N, lc.nb, B};

@@ -10,6 +10,7 @@ numpy arrays cross the boundary in the reference's layouts: complex128 column-ma
 matrices, phi as (N, OPDIM, m+1) column-major.
 """
 import ctypes as C
+import re
 from dataclasses import dataclass
 
 import numpy as np
@@ -127,6 +128,30 @@ SERIES_EQ, SERIES_MATS_G, SERIES_MATS_PAIR, SERIES_MATS_PH, SERIES_MATS_CURRENT 
 SERIES_PHI = 64
 # bit 7: the Matsubara transform of channel 4 (bandDiff, bandMix), bit 8: the equal-time band block, C_X(d) [2][N] then S_X(q) [2][N]
 SERIES_MATS_BAND, SERIES_EQ_BAND = 128, 256
+# bit 9: the Matsubara transform of channel 5 (one component per matrix of set_custom_bilinears), bit 10: their equal-time block,
+# C(d) [count][N] then S(q) [count][N]
+SERIES_MATS_CUSTOM, SERIES_EQ_CUSTOM = 512, 1024
+# observables of the custom bilinears (DetSDWBatch.set_custom_bilinears), matrix c = 0 .. 3: 'custom{c}Tau', 'custom{c}TauQ0' (with
+# 'Fine' twins), 'custom{c}Corr', 'custom{c}Sq' -> index base + c of detsdw_get_observable_vector
+CUSTOM_OBS_BASE = {"Tau": 42, "TauQ0": 46, "Corr": 50, "Sq": 54}
+
+
+def custom_observable(name):
+    """(kind, index) of a custom-bilinear observable name, kind in CUSTOM_OBS_BASE; None for any other name"""
+    m = re.fullmatch(r"custom([0-3])(Tau|TauQ0|Corr|Sq)", name)
+    return (m.group(2), CUSTOM_OBS_BASE[m.group(2)] + int(m.group(1))) if m else None
+
+
+def custom_ratio(name):
+    """matrix index c of the derived series quantity 'R_custom{c}'; None for any other name"""
+    m = re.fullmatch(r"R_custom([0-3])", name)
+    return int(m.group(1)) if m else None
+
+
+def _matsubara_index(name):
+    """index of detsdw_get_matsubara for a name of MATSUBARA or 'custom{c}Tau'; KeyError otherwise"""
+    cw = custom_observable(name)
+    return cw[1] if cw and cw[0] == "Tau" else MATSUBARA[name]
 # the order-parameter part of a series opened with phi=True: name -> index of detsdw_series_stats (real, (nfreq, N) and (5,))
 SERIES_PHI_OBS = {"phiChi": 32, "phiScalars": 33}
 
@@ -211,6 +236,11 @@ def _tuning(pipeline=0, qrVariant=0, greenVariant=0, maxJacobiSweeps=0, proposal
 def _fmat(a):
     """complex128, column-major, owned."""
     return np.array(a, dtype=np.complex128, order="F", copy=True)
+
+
+def _custom_matrices(mats):
+    """the argument of set_custom_bilinears as one C-contiguous complex array (count, 4, 4); the library validates the entries"""
+    return np.ascontiguousarray(np.asarray(list(mats), dtype=np.complex128).reshape(-1, 4, 4))
 
 
 class KernelContext:
@@ -352,6 +382,38 @@ class KernelContext:
         """count[n-1], then per boundary the N sums of Re W over the periodic site differences for bandDiff and bandMix"""
         return self._read_block(self.lib.dqmc_measure_td_band_accum_size, self.lib.dqmc_measure_td_band_read_host)
 
+    def set_custom_bilinears(self, mats):
+        """up to four Hermitian 4 x 4 matrices (band-spin order XUP, YDOWN, XDOWN, YUP) whose bilinears sum_ab c^+_a M_ab c_b are measured
+        time-displaced (measure_timedisplaced_custom, needs tdParticleHole=True) and at equal time (set_equal_time_custom); an empty list
+        removes them.  A second call replaces the matrices and clears their blocks"""
+        m = _custom_matrices(mats)
+        check(self.lib.dqmc_set_custom_bilinears(self.h, len(m), m.ctypes.data))
+
+    def get_custom_bilinears(self):
+        """the matrices that are set, complex (count, 4, 4)"""
+        n = C.c_int(0)
+        m = np.zeros((_lib.DQMC_CUSTOM_MAX, 4, 4), dtype=np.complex128)
+        check(self.lib.dqmc_get_custom_bilinears(self.h, C.byref(n), m.ctypes.data))
+        return m[:n.value].copy()
+
+    def measure_timedisplaced_custom(self, j):
+        """the correlators of every set matrix at boundary j, one launch, into their block (call it right after the advance that ended on
+        boundary j)"""
+        check(self.lib.dqmc_measure_timedisplaced_custom(self.h, j))
+
+    def measure_td_custom_read(self):
+        """count[n-1], then per boundary one row of N sums of Re W over the periodic site differences for every set matrix"""
+        return self._read_block(self.lib.dqmc_measure_td_custom_accum_size, self.lib.dqmc_measure_td_custom_read_host)
+
+    def set_equal_time_custom(self, on=True):
+        """while on, every measure_slice also bins the equal-time sums of every set matrix into a block of their own (independent of the
+        other two equal-time switches)"""
+        check(self.lib.dqmc_set_equal_time_custom(self.h, int(on)))
+
+    def measure_eq_custom_read(self):
+        """the selected chain's equal-time block of the set matrices: [count, one row of N raw sums per matrix], index dy L + dx"""
+        return self._read_block(self.lib.dqmc_measure_eq_custom_accum_size, self.lib.dqmc_measure_eq_custom_read_host)
+
     def measure_timedisplaced_segment(self, j):
         """every slice of boundary j's segment into the fine blocks, by propagation from the boundary's matrices (needs tdEverySlice=True at
         construction; call it right after the advance that ended on boundary j)"""
@@ -369,7 +431,7 @@ class KernelContext:
         """Matsubara transforms of the fine block of `channel`, every chain and component: complex (nchains, components, nfreq, N)"""
         out = np.zeros(self.lib.dqmc_measure_td_matsubara_size(self.h, channel, nfreq))
         check(self.lib.dqmc_measure_td_matsubara_host(self.h, channel, nfreq, out.ctypes.data_as(_lib._DP)))
-        return out.view(np.complex128).reshape(self.nchains_total(), 3 if channel == 2 else 2, nfreq, self.N)
+        return out.view(np.complex128).reshape(self.nchains_total(), -1, nfreq, self.N)     # 3 components for channel 2, one per matrix for 5
 
     def series_begin(self, bin_size, max_bins, nfreq=0, parts=SERIES_EQ):
         """open the measurement series of this context: bins of bin_size samples, at most max_bins of them; parts = SERIES_EQ |
@@ -410,7 +472,8 @@ class KernelContext:
 
     def series_layout(self, part):
         """(offset, length) of part 0 (equal-time: C_X(d) [5][N], S_X(q) [5][N]), 1 + channel (Matsubara, [component][nfreq][N] (re, im)), 6
-        (order parameter), 7 (Matsubara of the band channel) or 8 (equal-time band: C_X(d) [2][N], S_X(q) [2][N])"""
+        (order parameter), 7 (Matsubara of the band channel), 8 (equal-time band: C_X(d) [2][N], S_X(q) [2][N]), 9 (Matsubara of the custom
+        bilinears) or 10 (their equal-time block: C(d) [count][N], S(q) [count][N])"""
         off, ln = C.c_size_t(0), C.c_size_t(0)
         check(self.lib.dqmc_series_layout(self.h, int(part), C.byref(off), C.byref(ln)))
         return off.value, ln.value
@@ -442,6 +505,15 @@ class KernelContext:
         R_nematic (bandDiff at q = 0) and R_bandMix (bandMix at (pi, pi))"""
         v, e = np.zeros((self.nchains_total(), 3)), np.zeros((self.nchains_total(), 3))
         check(self.lib.dqmc_series_band_derived_host(self.h, v.ctypes.data_as(_lib._DP), e.ctypes.data_as(_lib._DP)))
+        return v, e
+
+    def series_custom_derived(self, Q=None):
+        """(value, err), (nchains, count) each, of a series with SERIES_EQ_CUSTOM: the jackknifed correlation ratio
+        R = 1 - [S(Q + dx) + S(Q + dy)] / (2 S(Q)) of every custom bilinear at Q = (qx, qy) in units of 2 pi / L, default (L/2, L/2)"""
+        qx, qy = (self.L // 2, self.L // 2) if Q is None else Q
+        count = len(self.get_custom_bilinears())
+        v, e = np.zeros((self.nchains_total(), count)), np.zeros((self.nchains_total(), count))
+        check(self.lib.dqmc_series_custom_derived_host(self.h, int(qx), int(qy), v.ctypes.data_as(_lib._DP), e.ctypes.data_as(_lib._DP)))
         return v, e
 
     def series_phi_derived(self):
@@ -830,7 +902,9 @@ class DetSDW:
         averaged over the m slices of the sweep and over translations) and their structure factors 'chargeSq', 'spinZSq', 'sdwSq',
         'pairPlusSq', 'pairMinusSq' (length N, column qy L + qx, q = 2 pi (qx, qy) / L; structure_factor of the former).  With
         bandCorrelators: 'bandDiffTau', 'bandMixTau', 'bandDiffTauQ0', 'bandMixTauQ0' (and their 'Fine' twins) next to 'chargeTau', and
-        'bandDiffCorr', 'bandMixCorr', 'bandDiffSq', 'bandMixSq' next to 'chargeCorr' / 'chargeSq'"""
+        'bandDiffCorr', 'bandMixCorr', 'bandDiffSq', 'bandMixSq' next to 'chargeCorr' / 'chargeSq'.  With matrices set by
+        DetSDWBatch.set_custom_bilinears: 'custom{c}Tau', 'custom{c}TauQ0' (and their 'Fine' twins), 'custom{c}Corr', 'custom{c}Sq' for
+        matrix c, shaped like the bandDiff names"""
         self._sel()
         info = self.info
         if name in EQ_CORRELATORS or name in BAND_EQ_CORRELATORS:
@@ -841,6 +915,15 @@ class DetSDW:
         fine = name.endswith("Fine")
         if fine:
             name = name[:-4]
+        cw = custom_observable(name)
+        if cw:
+            kind, which = cw
+            if fine and kind in ("Corr", "Sq"):
+                raise KeyError(name + "Fine")
+            rows = info.m + 1 if fine else info.n - 1
+            out = np.zeros(info.N if kind in ("Corr", "Sq") else (rows, info.N) if kind == "Tau" else rows)
+            check(self.lib.detsdw_get_observable_vector(self.h, which | (_lib.DETSDW_OBS_FINE if fine else 0), out.ctypes.data_as(_lib._DP)), host=True)
+            return out
         which = {"kOccX": 0, "kOccY": 1, "pairPlus": 2, "pairMinus": 3, "greenKTauX": 4, "greenKTauY": 5,
                  "pairPlusTau": 6, "pairMinusTau": 7, "pairPlusTauQ0": 8, "pairMinusTauQ0": 9,
                  "chargeTau": 10, "spinZTau": 11, "sdwTau": 12, "chargeTauQ0": 13, "spinZTauQ0": 14, "sdwTauQ0": 15,
@@ -860,7 +943,7 @@ class DetSDW:
         (needs timeDisplacedEverySlice; valid until the next sweep).  Frequencies: matsubara_frequencies()"""
         self._sel()
         out = np.zeros((int(nfreq), self.info.N), dtype=np.complex128)
-        check(self.lib.detsdw_get_matsubara(self.h, MATSUBARA[name], int(nfreq), out.ctypes.data_as(_lib._DP)), host=True)
+        check(self.lib.detsdw_get_matsubara(self.h, _matsubara_index(name), int(nfreq), out.ctypes.data_as(_lib._DP)), host=True)
         return out
 
     def _series_shape(self, name):
@@ -874,7 +957,10 @@ class DetSDW:
             return BAND_EQ_CORRELATORS[name], (info.N,), False
         if name in SERIES_PHI_OBS:
             return SERIES_PHI_OBS[name], ((self._batch._series_nfreq, info.N) if name == "phiChi" else (5,)), False
-        return MATSUBARA[name], (self._batch._series_nfreq, info.N), True
+        cw = custom_observable(name)
+        if cw and cw[0] in ("Corr", "Sq"):
+            return cw[1], (info.N,), False
+        return _matsubara_index(name), (self._batch._series_nfreq, info.N), True
 
     def series_stats(self, name):
         """(mean, err) of this chain over the closed bins of the open series (DetSDWBatch.series_begin): name = an equal-time
@@ -1053,10 +1139,17 @@ class DetSDWBatch:
     def load_state(self, path):
         check(self.lib.detsdw_load_state(self.h, str(path).encode()), host=True)
 
+    def set_custom_bilinears(self, mats):
+        """up to four Hermitian 4 x 4 matrices M (band-spin order XUP, YDOWN, XDOWN, YUP): from the next sweep(True) on the correlators of
+        sum_ab c^+_a M_ab c_b are measured like bandDiff -- 'custom{c}Tau' ... with timeDisplacedParticleHole, 'custom{c}Corr' / 'custom{c}Sq'
+        with equalTimeCorrelators (one of the two is needed).  Between sweeps; a second call replaces the matrices, [] removes them"""
+        m = _custom_matrices(mats)
+        check(self.lib.detsdw_set_custom_bilinears(self.h, len(m), m.ctypes.data), host=True)
+
     def matsubara_all(self, name, nfreq):
         """DetSDW.matsubara of every chain: complex (nchains, nfreq, N), one device call per sub-batch"""
         out = np.zeros((len(self.chains), int(nfreq), self.chains[0].info.N), dtype=np.complex128)
-        check(self.lib.detsdw_get_matsubara_all(self.h, MATSUBARA[name], int(nfreq), out.ctypes.data_as(_lib._DP)), host=True)
+        check(self.lib.detsdw_get_matsubara_all(self.h, _matsubara_index(name), int(nfreq), out.ctypes.data_as(_lib._DP)), host=True)
         return out
 
     def series_begin(self, binSize, maxBins, nfreq=0, host_copy=True, auto_rebin=False, track_variance=False, phi=False):
@@ -1138,10 +1231,20 @@ class DetSDWBatch:
         check(self.lib.detsdw_series_stats_all(self.h, which, mean.ctypes.data_as(_lib._DP), err.ctypes.data_as(_lib._DP)), host=True)
         return mean, err
 
-    def series_derived_all(self, name):
+    def series_derived_all(self, name, Q=None):
         """(value, err) per chain of a jackknifed derived quantity: the correlation ratios 'R_charge', 'R_spinZ', 'R_sdw',
-        'R_pairPlus', 'R_pairMinus' (equalTimeCorrelators) or 'rhoS' (timeDisplacedCurrent with timeDisplacedEverySlice)"""
+        'R_pairPlus', 'R_pairMinus' (equalTimeCorrelators) or 'rhoS' (timeDisplacedCurrent with timeDisplacedEverySlice);
+        'R_custom{c}': the correlation ratio of custom bilinear c at Q = (qx, qy) in units of 2 pi / L, default (L/2, L/2)"""
         v, e = np.zeros(len(self.chains)), np.zeros(len(self.chains))
+        c = custom_ratio(name)
+        if c is not None:
+            L = self.chains[0].info.L
+            qx, qy = (L // 2, L // 2) if Q is None else Q
+            check(self.lib.detsdw_series_custom_derived(self.h, c, int(qx), int(qy), v.ctypes.data_as(_lib._DP),
+                                                        e.ctypes.data_as(_lib._DP)), host=True)
+            return v, e
+        if Q is not None:
+            raise ValueError("Q belongs to 'R_custom{c}'")
         check(self.lib.detsdw_series_derived_all(self.h, SERIES_DERIVED[name], v.ctypes.data_as(_lib._DP), e.ctypes.data_as(_lib._DP)), host=True)
         return v, e
 

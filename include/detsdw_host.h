@@ -147,7 +147,11 @@ enum { DETSDW_OBS_KOCCX = 0, DETSDW_OBS_KOCCY = 1, DETSDW_OBS_PAIRPLUS = 2, DETS
        /* bandCorrelators: the time-displaced ones have DETSDW_OBS_FINE twins and Matsubara transforms like chargeTau, the equal-time
           ones are read and enter a series like chargeCorr / chargeSq */
        DETSDW_OBS_BANDDIFFTAU = 34, DETSDW_OBS_BANDMIXTAU = 35, DETSDW_OBS_BANDDIFFTAU_Q0 = 36, DETSDW_OBS_BANDMIXTAU_Q0 = 37,
-       DETSDW_OBS_BANDDIFFCORR = 38, DETSDW_OBS_BANDMIXCORR = 39, DETSDW_OBS_BANDDIFFSQ = 40, DETSDW_OBS_BANDMIXSQ = 41 };
+       DETSDW_OBS_BANDDIFFCORR = 38, DETSDW_OBS_BANDMIXCORR = 39, DETSDW_OBS_BANDDIFFSQ = 40, DETSDW_OBS_BANDMIXSQ = 41,
+       /* user-defined bilinears (detsdw_set_custom_bilinears), matrix c = 0 .. 3 at BASE + c: custom{c}Tau and custom{c}TauQ0 with the rows,
+          normalisation, DETSDW_OBS_FINE twins and Matsubara transforms of bandDiffTau; custom{c}Corr and custom{c}Sq with those of
+          bandDiffCorr / bandDiffSq.  ParameterWrong for a c that is not set, or without the family the observable rides on */
+       DETSDW_OBS_CUSTOMTAU = 42, DETSDW_OBS_CUSTOMTAU_Q0 = 46, DETSDW_OBS_CUSTOMCORR = 50, DETSDW_OBS_CUSTOMSQ = 54 };
 /* equalTimeCorrelators: flag bit of detsdw_params::fermionMeasurements */
 enum { DETSDW_FM_EQ_CORRELATORS = 0x100 };
 /* bandCorrelators: DETSDW_FM_EQ_BAND is a flag bit of detsdw_params::fermionMeasurements, DETSDW_TD_PH_BAND one of ::timeDisplacedParticleHole */
@@ -289,6 +293,20 @@ int detsdw_series_derived_all(detsdw_replica* r, int what, double* value, double
 /* what = 0 R_dCDW, 1 R_nematic, 2 R_bandMix (the same numbers as DETSDW_SERIES_R_DCDW .. _R_BANDMIX of detsdw_series_derived_all):
  * value[nchains], err[nchains]; ParameterWrong without DETSDW_FM_EQ_BAND */
 int detsdw_series_band_derived(detsdw_replica* r, int what, double* value, double* err);
+/* User-defined bilinears: count = 0 .. 4 Hermitian 4 x 4 matrices M[count][4][4] (row-major, band-spin order XUP, YDOWN, XDOWN, YUP) handed to
+ * dqmc_set_custom_bilinears of every sub-batch context; may be called between sweeps, a second call replaces the first.  ParameterWrong
+ * unless equalTimeCorrelators or timeDisplacedParticleHole >= 1 is on; the kernel level's refusals (a matrix that is not Hermitian, not
+ * finite or all zero; a series with a custom part open) come back as its error, and ParameterWrong while a series with
+ * DETSDW_SERIES_NO_HOST_COPY is open (it has no part for matrices set after it began, and nothing else would read their equal-time block).
+ * The Matsubara transforms of the other channels stay valid across the call.  Measurement sweeps then measure the matrices wherever
+ * they measure bandDiff / bandMix: at the coarse boundaries and on every slice (with timeDisplacedParticleHole) and at equal time (with
+ * equalTimeCorrelators); the observables are DETSDW_OBS_CUSTOMTAU .. above.  A series begun while matrices are set carries
+ * DQMC_SERIES_MATS_CUSTOM / DQMC_SERIES_EQ_CUSTOM, routed like every other part; detsdw_series_stats* / _read_bins / _binning* take
+ * custom{c}Tau, custom{c}Corr and custom{c}Sq; detsdw_series_save writes the count and the matrices behind everything else (files of
+ * series without a custom part keep their bytes) and detsdw_series_load raises ParameterWrong if they differ from the ones that are set.
+ * detsdw_series_custom_derived: value[nchains], err[nchains] of R = 1 - 1/2 [S(Q + dx) + S(Q + dy)] / S(Q) for matrix c at Q = (qx, qy). */
+int detsdw_set_custom_bilinears(detsdw_replica* r, int count, const dqmc_cplx* M);
+int detsdw_series_custom_derived(detsdw_replica* r, int c, int qx, int qy, double* value, double* err);
 int detsdw_series_read_bins(detsdw_replica* r, int which, int first, int count, double* out);
 int detsdw_series_end(detsdw_replica* r);
 /* The series over a long run (kernel calls and formulas: dqmc_hip.h).  All of it is new surface: without these calls nothing changes.

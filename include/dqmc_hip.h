@@ -413,6 +413,33 @@ int dqmc_measure_td_current_read_host(dqmc_ctx* ctx, double* out);
 int dqmc_measure_timedisplaced_band(dqmc_ctx* ctx, int j);
 size_t dqmc_measure_td_band_accum_size(dqmc_ctx* ctx);  /* 0 without the reservation */
 int dqmc_measure_td_band_read_host(dqmc_ctx* ctx, double* out);
+/* User-defined bilinears ("customBilinears"): the same W^M(A,B), and its equal-time form, for up to DQMC_CUSTOM_MAX Hermitian 4 x 4
+ * matrices M in band-spin space (order XUP, YDOWN, XDOWN, YUP) that are set at run time -- any on-site particle-hole bilinear
+ * O^M_i = sum_ab c^+_ia M_ab c_ib of the two-band model: one band's in-plane spin (XUP <-> XDOWN), n_x alone, ...  SDW model only.
+ * dqmc_set_custom_bilinears(ctx, count, M): M[count][4][4] row-major, count = 0 .. DQMC_CUSTOM_MAX.  DQMC_EINVAL with nothing changed: a
+ * count out of range, an entry that is not finite, M[a][b] != conj(M[b][a]) (compared exactly), a matrix that is all zero, a Hubbard
+ * context.  On success the blocks of an earlier call are released and new, cleared ones allocated outside the arena: the equal-time block
+ * 1 + count N; on a context created with td_particle_hole >= 1 the coarse block (n-1)(1 + count N); with DQMC_TD_EVERY_SLICE as well the fine
+ * block (m+1)(1 + count N), every-slice channel 5, filled by dqmc_measure_timedisplaced_segment / _ends and transformed by
+ * dqmc_measure_td_matsubara_host(5) into [count][nfreq][N] like the other channels.  count = 0 removes them (and switches
+ * dqmc_set_equal_time_custom off; a replacement leaves the switch as it is).  The matrices travel to the kernels as a launch argument; OPDIM < 3 keeps only the
+ * (XUP, YDOWN) sector of a Green's function, the (XDOWN, YUP) sector is its complex conjugate and the blocks between them vanish -- a
+ * matrix that couples the two sectors is legal.  dqmc_get_custom_bilinears reads count and the matrices back (M may be NULL).
+ * dqmc_measure_timedisplaced_custom(j) (all chains, every set matrix in one launch): preconditions, DQMC_EINVAL behaviour and independence
+ * of dqmc_measure_timedisplaced_band.  Layout (doubles, dqmc_measure_td_custom_accum_size of them): count[n-1], then for j = 1 .. n-1
+ * `count` rows of N raw sums sum_B Re W(B (+) d, B), bin dy L + dx, at offset (n-1) + (j-1) count N.
+ * dqmc_set_equal_time_custom(on): a third switch of dqmc_measure_slice, independent of the other two (DQMC_EINVAL while no matrix is set):
+ * one shifted matrix in every role, the delta term sum_bc (M^2)_cb g~(B b; B c) in the d = 0 bin (M^2 = 1 is not assumed).  Layout
+ * (dqmc_measure_eq_custom_accum_size doubles): count, then `count` rows of N raw sums.  dqmc_measure_reset clears both blocks. */
+#define DQMC_CUSTOM_MAX 4
+int dqmc_set_custom_bilinears(dqmc_ctx* ctx, int count, const dqmc_cplx* M);
+int dqmc_get_custom_bilinears(dqmc_ctx* ctx, int* count, dqmc_cplx* M);
+int dqmc_measure_timedisplaced_custom(dqmc_ctx* ctx, int j);
+size_t dqmc_measure_td_custom_accum_size(dqmc_ctx* ctx);  /* 0 without matrices or without td_particle_hole */
+int dqmc_measure_td_custom_read_host(dqmc_ctx* ctx, double* out);
+int dqmc_set_equal_time_custom(dqmc_ctx* ctx, int on);
+size_t dqmc_measure_eq_custom_accum_size(dqmc_ctx* ctx);  /* 0 while no matrix is set */
+int dqmc_measure_eq_custom_read_host(dqmc_ctx* ctx, double* out);
 /* G(0) of the last pair's field configuration, selected chain; *slice as for dqmc_get_green_timedisplaced_host.  DQMC_EINVAL without
  * td_particle_hole or if no pair was computed yet */
 int dqmc_get_green0_timedisplaced_host(dqmc_ctx* ctx, dqmc_cplx* g00, int* slice);
@@ -433,7 +460,8 @@ int dqmc_get_green0_timedisplaced_host(dqmc_ctx* ctx, dqmc_cplx* g00, int* slice
  * dqmc_measure_timedisplaced_ends() (all chains) measures rows 0 and m.  Precondition: the context stands at tau = 0 == beta
  * (current time slice 0 or m: the state after the closing advance of either sweep direction), so that G = G(0); DQMC_EINVAL
  * otherwise.  Both rows use G(tau) = G(0) = G.
- * Blocks: channel 0 = bins of dqmc_measure_timedisplaced, 1 = _pair, 2 = _ph, 3 = _current, 4 = _band (row stride 2N); a channel has a
+ * Blocks: channel 0 = bins of dqmc_measure_timedisplaced, 1 = _pair, 2 = _ph, 3 = _current, 4 = _band (row stride 2N), 5 = _custom (row
+ * stride count N, present while matrices are set); a channel has a
  * block if its coarse block is reserved.  Layout (doubles, dqmc_measure_td_fine_accum_size of them, 0 without the block): count[m+1], then row k = 0 .. m
  * at offset (m+1) + k stride, stride and contents of a row as in the coarse block: 4 (2L-1)^2, 2N, 3N, 2N + 2.
  * dqmc_measure_reset clears them as well. */
@@ -525,13 +553,20 @@ int dqmc_measure_td_matsubara_host(dqmc_ctx* ctx, int channel, int nfreq, double
  *                                                                    NaN where the argument of the root is negative
  * The band parts: DQMC_SERIES_MATS_BAND = 128 (bit 7: the Matsubara transform of every-slice channel 4, [2][nfreq][N] complex) and
  * DQMC_SERIES_EQ_BAND = 256 (bit 8: the block of dqmc_set_equal_time_band as C_X(d) [2][N] then S_X(q) [2][N], X = bandDiff, bandMix, formed
- * like bit 0 with the same cosine table and integer phase reduction).  The accepted mask is 0x1df.  Parts sit in mask order: the two lie
+ * like bit 0 with the same cosine table and integer phase reduction).  Parts sit in mask order: the two lie
  * behind the order-parameter part, and every mask without them keeps its S, its offsets and its bits.
  * dqmc_series_band_derived_host (all chains, value and err [nb][3]; DQMC_EINVAL for B < 2 or a series without bit 8), the jackknife of
  * dqmc_series_derived_host over R = 1 - 1/2 [S(Q + dx) + S(Q + dy)] / S(Q):
- *   0: bandDiff at Q = (L/2, L/2), the d-wave CDW     1: bandDiff at Q = (0, 0), the nematic     2: bandMix at Q = (L/2, L/2) */
+ *   0: bandDiff at Q = (L/2, L/2), the d-wave CDW     1: bandDiff at Q = (0, 0), the nematic     2: bandMix at Q = (L/2, L/2)
+ * The parts of the user-defined bilinears (`count` matrices set by dqmc_set_custom_bilinears), behind all of the above so that every
+ * older mask keeps its S, its offsets and its bits: DQMC_SERIES_MATS_CUSTOM = 512 (bit 9: the Matsubara transform of every-slice channel 5,
+ * [count][nfreq][N] complex) and DQMC_SERIES_EQ_CUSTOM = 1024 (bit 10: the block of dqmc_set_equal_time_custom as C(d) [count][N] then
+ * S(q) [count][N], formed like bit 8).  The accepted mask is 0x7df.  While a series with one of the two is open,
+ * dqmc_set_custom_bilinears returns DQMC_EINVAL.  dqmc_series_custom_derived_host(qx, qy) (all chains, value and err [nb][count];
+ * DQMC_EINVAL for B < 2, a series without bit 10, qx or qy outside 0 .. L-1): the same jackknife of R for every matrix at the caller's
+ * Q = (qx, qy), in units of 2 pi / L. */
 enum { DQMC_SERIES_EQ = 1, DQMC_SERIES_MATS_G = 2, DQMC_SERIES_MATS_PAIR = 4, DQMC_SERIES_MATS_PH = 8, DQMC_SERIES_MATS_CURRENT = 16,
-       DQMC_SERIES_PHI = 64, DQMC_SERIES_MATS_BAND = 128, DQMC_SERIES_EQ_BAND = 256 };
+       DQMC_SERIES_PHI = 64, DQMC_SERIES_MATS_BAND = 128, DQMC_SERIES_EQ_BAND = 256, DQMC_SERIES_MATS_CUSTOM = 512, DQMC_SERIES_EQ_CUSTOM = 1024 };
 int dqmc_series_begin(dqmc_ctx* ctx, int bin_size, int max_bins, int nfreq, int parts);
 int dqmc_series_layout(dqmc_ctx* ctx, int part, size_t* offset, size_t* length);
 int dqmc_series_add_sweep(dqmc_ctx* ctx);
@@ -544,6 +579,7 @@ int dqmc_series_stats_host(dqmc_ctx* ctx, double* mean, double* err);
 int dqmc_series_derived_host(dqmc_ctx* ctx, double* value, double* err);
 int dqmc_series_phi_derived_host(dqmc_ctx* ctx, double* value, double* err);
 int dqmc_series_band_derived_host(dqmc_ctx* ctx, double* value, double* err);
+int dqmc_series_custom_derived_host(dqmc_ctx* ctx, int qx, int qy, double* value, double* err);
 int dqmc_series_end(dqmc_ctx* ctx);
 /* ---- the series over a long run: re-binning, binning analysis with tau_int, export / import ------------
  * All of it is new surface: with none of these calls used, every call above keeps its bits, its error codes and its launches.
