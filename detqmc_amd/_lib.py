@@ -238,6 +238,8 @@ SYMBOLS = [
     ("dqmc_measure_td_band_read_host", C.c_int, [_P, _DP]),
     ("dqmc_set_custom_bilinears", C.c_int, [_P, C.c_int, _P]),
     ("dqmc_get_custom_bilinears", C.c_int, [_P, C.POINTER(C.c_int), _P]),
+    ("dqmc_set_custom_bond_bilinears", C.c_int, [_P, C.c_int, _P, _P, _P]),
+    ("dqmc_get_custom_bond_bilinears", C.c_int, [_P, C.POINTER(C.c_int), _P, _P, _P]),
     ("dqmc_measure_timedisplaced_custom", C.c_int, [_P, C.c_int]),
     ("dqmc_measure_td_custom_accum_size", C.c_size_t, [_P]),
     ("dqmc_measure_td_custom_read_host", C.c_int, [_P, _DP]),
@@ -299,6 +301,8 @@ SYMBOLS = [
     ("detsdw_series_derived_all", C.c_int, [_P, C.c_int, _DP, _DP]),
     ("detsdw_series_band_derived", C.c_int, [_P, C.c_int, _DP, _DP]),
     ("detsdw_set_custom_bilinears", C.c_int, [_P, C.c_int, _P]),
+    ("detsdw_set_custom_bond_bilinears", C.c_int, [_P, C.c_int, _P, _P, _P]),
+    ("detsdw_get_custom_bond_bilinears", C.c_int, [_P, C.POINTER(C.c_int), _P, _P, _P]),
     ("detsdw_series_custom_derived", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _DP, _DP]),
     ("detsdw_series_read_bins", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _DP]),
     ("detsdw_series_end", C.c_int, [_P]),

@@ -126,6 +126,11 @@ struct dqmc_ctx {
     unsigned cst_mask[DQMC_CUSTOM_MAX] = {}, cst_mask2[DQMC_CUSTOM_MAX] = {};
     bool eqc_on = false;
     cplx *cst_td_ob = nullptr, *cst_eq_ob = nullptr;
+    // dqmc_set_custom_bond_bilinears: the bond parts on the host (for the getter), and while at least one is non-zero (cst_bond_on) the
+    // device table and masks the stencil kernels read (CustomBond in dqmc_internal.h), allocated and freed with the blocks above
+    cplx cst_Mx[DQMC_CUSTOM_MAX * 16] = {}, cst_My[DQMC_CUSTOM_MAX * 16] = {};
+    bool cst_bond_on = false;
+    CustomBond cst_bond = {};
     // dqmc_series_*: the measurement series.  Device buffers outside the arena, allocated by dqmc_series_begin and freed by dqmc_series_end
     // or with the context: sample [nb][S], open bin [nb][S], closed bins [max_bins][nb][S], the per-part flags [9][nb], the cos / sin table
     // (2 pi j / L [2 L]; with the order-parameter part, index 6 of off / len, also 2 pi j / m [2 m] behind it) and the result buffer

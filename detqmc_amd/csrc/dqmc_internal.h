@@ -336,11 +336,19 @@ size_t measure_eq_band_onebody_cplx(int N);
 // [count][N].  Time-displaced: count[rows], then the rows; gs, hs as for launch_measure_td_ph.  Equal-time: count, then one row; M2, mask2 =
 // the squares of the matrices (the delta term).  acc and the scratch ob are plain device arrays outside the arena: chain b at acc + b * acs
 // (equal-time: 1 + measure_custom_row_doubles) and ob + b * measure_*_custom_onebody_cplx
-void launch_td_custom_onebody(const Launch& lc, const DevModel& hm, int count, const cplx* M, const unsigned* mask, const cplx* gs, cplx* ob, int t);
+// Bond parts (dqmc_set_custom_bond_bilinears): with bond != nullptr the three entries launch the stencil kernels instead, for every set
+// operator.  Device table tab (measure_custom_bond_table_cplx complex, shared by the chains): the five site blocks of every operator,
+// V[count][5][4][4] = M0, Mx, Mx^H, My, My^H, then the link factors u[2][N] of the stored sector (x bonds, y bonds); mk[count][5] the
+// non-zero masks of the blocks (device memory as well: the kernels index both by a loop variable); parts[c] bit k: block k of operator c
+// is non-zero -- the launch argument that lets on-site-only operators skip the bond block pairs.
+struct CustomBond { const cplx* tab; const unsigned* mk; unsigned parts[DQMC_CUSTOM_MAX]; };
+size_t measure_custom_bond_table_cplx(int count, int N);
+void launch_td_custom_onebody(const Launch& lc, const DevModel& hm, int count, const cplx* M, const unsigned* mask, const cplx* gs, cplx* ob, int t,
+                              const CustomBond* bond = nullptr);
 void launch_measure_td_custom(const Launch& lc, const DevModel& hm, int count, const cplx* M, const unsigned* mask, const cplx* gs, const cplx* hs,
-                              const cplx* ob, double* acc, size_t acs, int row, int rows);
+                              const cplx* ob, double* acc, size_t acs, int row, int rows, const CustomBond* bond = nullptr);
 void launch_measure_eq_custom(const Launch& lc, const DevModel& hm, int count, const cplx* M, const unsigned* mask, const cplx* M2, const unsigned* mask2,
-                              const cplx* gs, cplx* ob, double* acc);
+                              const cplx* gs, cplx* ob, double* acc, const CustomBond* bond = nullptr);
 size_t measure_custom_row_doubles(int count, int N);
 size_t measure_td_custom_onebody_cplx(int count, int N);
 size_t measure_eq_custom_onebody_cplx(int count, int N);

@@ -78,7 +78,8 @@ extern "C" int dqmc_measure_slice(dqmc_ctx* c) {
     if (c->eqb_on) { ProfScope ps(c, FAM_OTHER, 2); launch_measure_eq_band(c->lc, c->hm, c->T1, c->eqb_ob, c->acc[ACC_EQ_BAND].p); }
     if (c->eqc_on) {
         ProfScope ps(c, FAM_OTHER, 2);
-        launch_measure_eq_custom(c->lc, c->hm, c->cst_count, c->cst_M, c->cst_mask, c->cst_M2, c->cst_mask2, c->T1, c->cst_eq_ob, c->acc[ACC_EQ_CUSTOM].p);
+        launch_measure_eq_custom(c->lc, c->hm, c->cst_count, c->cst_M, c->cst_mask, c->cst_M2, c->cst_mask2, c->T1, c->cst_eq_ob, c->acc[ACC_EQ_CUSTOM].p,
+                                 c->cst_bond_on ? &c->cst_bond : nullptr);
     }
     return finish(c, "dqmc_measure_slice");
 }
@@ -124,32 +125,63 @@ extern "C" size_t dqmc_measure_eq_band_accum_size(dqmc_ctx* c) { return acc_size
 extern "C" int dqmc_measure_eq_band_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_EQ_BAND, out); }
 // user-defined bilinears (dqmc_hip.h): the matrices stay on the host, the blocks and the one-body scratch live outside the arena
 void custom_free(dqmc_ctx* c) {
-    for (void* q : {(void*)c->acc[ACC_TD_CUSTOM].p, (void*)c->acc[ACC_FINE0 + 5].p, (void*)c->acc[ACC_EQ_CUSTOM].p, (void*)c->cst_td_ob, (void*)c->cst_eq_ob})
+    for (void* q : {(void*)c->acc[ACC_TD_CUSTOM].p, (void*)c->acc[ACC_FINE0 + 5].p, (void*)c->acc[ACC_EQ_CUSTOM].p, (void*)c->cst_td_ob, (void*)c->cst_eq_ob,
+                    (void*)c->cst_bond.tab, (void*)c->cst_bond.mk})
         if (q) (void)hipFree(q);
     c->acc[ACC_TD_CUSTOM].p = c->acc[ACC_FINE0 + 5].p = c->acc[ACC_EQ_CUSTOM].p = nullptr;
     c->acc[ACC_TD_CUSTOM].n = c->acc[ACC_FINE0 + 5].n = c->acc[ACC_EQ_CUSTOM].n = 0;
     c->cst_td_ob = c->cst_eq_ob = nullptr;
+    c->cst_bond = CustomBond{};
+    c->cst_bond_on = false;
     c->cst_count = 0;
     c->eqc_on = false;
 }
-extern "C" int dqmc_set_custom_bilinears(dqmc_ctx* c, int count, const dqmc_cplx* M) {
+// Link factor of the bond site -> site (+) mu in the stored sector: the antiperiodic sign times the Peierls phase, what build_hopping_K
+// (dqmc_context.hip) puts on K[site (+) mu, site] with the amplitude left out
+static cplx custom_link(const dqmc_params& p, int mu, int site) {
+    const int L = p.L, N = L * L, sx = site % L, sy = site / L;
+    const bool apbc_x = (p.bc == DQMC_BC_APBC_X || p.bc == DQMC_BC_APBC_XY), apbc_y = (p.bc == DQMC_BC_APBC_Y || p.bc == DQMC_BC_APBC_XY);
+    const double zmag = p.weakZflux ? 1.0 / N : 0.0;
+    double sign = 1.0, arg = 0.0;
+    if (mu == 0) {
+        if (apbc_x && sx == L - 1) sign = -1.0;
+        arg = 2.0 * M_PI * zmag * sy;
+    } else {
+        if (apbc_y && sy == L - 1) sign = -1.0;
+        if (sy == L - 1) arg = -2.0 * M_PI * zmag * L * sx;
+    }
+    if (!p.weakZflux) return make_double2(sign, 0.0);
+    return make_double2(sign * std::cos(arg), sign * std::sin(arg));
+}
+// Both setters.  M0 [count][4][4] Hermitian, Mx / My arbitrary or nullptr (all zero); `who` names the entry in the messages.
+static int custom_set(dqmc_ctx* c, int count, const dqmc_cplx* M, const dqmc_cplx* Mx, const dqmc_cplx* My, const std::string& who) {
     if (!c) return fail(DQMC_EINVAL, "null ctx");
     if (c->hm.hubbard) return fail(DQMC_EINVAL, "the user-defined bilinears belong to the SDW model");
-    if (count < 0 || count > DQMC_CUSTOM_MAX) return fail(DQMC_EINVAL, "dqmc_set_custom_bilinears: count must be in 0 .. DQMC_CUSTOM_MAX");
+    if (count < 0 || count > DQMC_CUSTOM_MAX) return fail(DQMC_EINVAL, who + ": count must be in 0 .. DQMC_CUSTOM_MAX");
     if (count && !M) return fail(DQMC_EINVAL, "null argument");
     if (c->ser.open && (c->ser.parts & (DQMC_SERIES_MATS_CUSTOM | DQMC_SERIES_EQ_CUSTOM)))
-        return fail(DQMC_EINVAL, "dqmc_set_custom_bilinears: a measurement series with a part of the user-defined bilinears is open");
+        return fail(DQMC_EINVAL, who + ": a measurement series with a part of the user-defined bilinears is open");
+    bool bonds = false;
     for (int ch = 0; ch < count; ++ch) {
         const dqmc_cplx* m = M + 16 * ch;
         bool any = false;
         for (int a = 0; a < 4; ++a)
             for (int b = 0; b < 4; ++b) {
                 const dqmc_cplx v = m[4 * a + b], w = m[4 * b + a];
-                if (!std::isfinite(v.re) || !std::isfinite(v.im)) return fail(DQMC_EINVAL, "dqmc_set_custom_bilinears: an entry is not finite");
-                if (v.re != w.re || v.im != -w.im) return fail(DQMC_EINVAL, "dqmc_set_custom_bilinears: a matrix is not Hermitian");
+                if (!std::isfinite(v.re) || !std::isfinite(v.im)) return fail(DQMC_EINVAL, who + ": an entry is not finite");
+                if (v.re != w.re || v.im != -w.im) return fail(DQMC_EINVAL, who + ": a matrix is not Hermitian");
                 any = any || v.re != 0.0 || v.im != 0.0;
             }
-        if (!any) return fail(DQMC_EINVAL, "dqmc_set_custom_bilinears: a matrix is all zero");
+        for (const dqmc_cplx* bm : {Mx, My})
+            for (int k = 0; bm && k < 16; ++k) {
+                const dqmc_cplx v = bm[16 * ch + k];
+                if (!std::isfinite(v.re) || !std::isfinite(v.im)) return fail(DQMC_EINVAL, who + ": an entry is not finite");
+                if (v.re == 0.0 && v.im == 0.0) continue;
+                if (c->p.weakZflux && k / 4 != k % 4)
+                    return fail(DQMC_EINVAL, who + ": with weakZflux a bond part with a flavour-off-diagonal entry has no covariant definition");
+                any = bonds = true;
+            }
+        if (!any) return fail(DQMC_EINVAL, who + ": a matrix is all zero");
     }
     (void)hipSetDevice(c->p.device);
     // the new buffers first: a failed allocation leaves the context as it was
@@ -157,23 +189,59 @@ extern "C" int dqmc_set_custom_bilinears(dqmc_ctx* c, int count, const dqmc_cplx
     const size_t n_eq = count ? 1 + row : 0, n_td = count && c->G00 ? (size_t)(c->n - 1) * (1 + row) : 0;
     const size_t n_fine = n_td && c->td_fine ? (size_t)(c->m + 1) * (1 + row) : 0;
     const size_t ob_eq = count ? measure_eq_custom_onebody_cplx(count, c->N) : 0, ob_td = n_td ? measure_td_custom_onebody_cplx(count, c->N) : 0;
+    // the device table of the stencil kernels: blocks M0, Mx, Mx^H, My, My^H of every operator, then the link factors
+    std::vector<cplx> tab(bonds ? measure_custom_bond_table_cplx(count, c->N) : 0);
+    std::vector<unsigned> mk(bonds ? (size_t)count * 5 : 0);
+    CustomBond bond{};
+    if (bonds) {
+        for (int ch = 0; ch < count; ++ch) {
+            cplx* v = tab.data() + (size_t)ch * 80;
+            for (int a = 0; a < 4; ++a)
+                for (int b = 0; b < 4; ++b) {
+                    const dqmc_cplx zero{0.0, 0.0};
+                    const dqmc_cplx m0 = M[16 * ch + 4 * a + b];
+                    const dqmc_cplx x = Mx ? Mx[16 * ch + 4 * a + b] : zero, xt = Mx ? Mx[16 * ch + 4 * b + a] : zero;
+                    const dqmc_cplx y = My ? My[16 * ch + 4 * a + b] : zero, yt = My ? My[16 * ch + 4 * b + a] : zero;
+                    v[4 * a + b] = make_double2(m0.re, m0.im);
+                    v[16 + 4 * a + b] = make_double2(x.re, x.im);
+                    v[32 + 4 * a + b] = make_double2(xt.re, -xt.im);
+                    v[48 + 4 * a + b] = make_double2(y.re, y.im);
+                    v[64 + 4 * a + b] = make_double2(yt.re, -yt.im);
+                }
+            for (int k = 0; k < 5; ++k) {
+                unsigned bits = 0;
+                for (int e = 0; e < 16; ++e)
+                    if (v[16 * k + e].x != 0.0 || v[16 * k + e].y != 0.0) bits |= 1u << e;
+                mk[(size_t)ch * 5 + k] = bits;
+                if (bits) bond.parts[ch] |= 1u << k;
+            }
+        }
+        cplx* lk = tab.data() + (size_t)count * 80;
+        for (int mu = 0; mu < 2; ++mu)
+            for (int site = 0; site < c->N; ++site) lk[(size_t)mu * c->N + site] = custom_link(c->p, mu, site);
+    }
     double *eq = nullptr, *td = nullptr, *fine = nullptr;
-    cplx *oe = nullptr, *ot = nullptr;
+    cplx *oe = nullptr, *ot = nullptr, *dtab = nullptr;
+    unsigned* dmk = nullptr;
     hipError_t e = hipSuccess;
     if (n_eq) e = hipMalloc((void**)&eq, n_eq * nb * sizeof(double));
     if (e == hipSuccess && ob_eq) e = hipMalloc((void**)&oe, ob_eq * nb * sizeof(cplx));
     if (e == hipSuccess && n_td) e = hipMalloc((void**)&td, n_td * nb * sizeof(double));
     if (e == hipSuccess && ob_td) e = hipMalloc((void**)&ot, ob_td * nb * sizeof(cplx));
     if (e == hipSuccess && n_fine) e = hipMalloc((void**)&fine, n_fine * nb * sizeof(double));
+    if (e == hipSuccess && bonds) e = hipMalloc((void**)&dtab, tab.size() * sizeof(cplx));
+    if (e == hipSuccess && bonds) e = hipMalloc((void**)&dmk, mk.size() * sizeof(unsigned));
     if (e == hipSuccess && n_fine) e = hipMemsetAsync(fine, 0, n_fine * nb * sizeof(double), c->st);
     if (e == hipSuccess && n_eq) e = hipMemsetAsync(eq, 0, n_eq * nb * sizeof(double), c->st);
     if (e == hipSuccess && ob_eq) e = hipMemsetAsync(oe, 0, ob_eq * nb * sizeof(cplx), c->st);
     if (e == hipSuccess && n_td) e = hipMemsetAsync(td, 0, n_td * nb * sizeof(double), c->st);
     if (e == hipSuccess && ob_td) e = hipMemsetAsync(ot, 0, ob_td * nb * sizeof(cplx), c->st);
+    if (e == hipSuccess && bonds) e = hipMemcpyAsync(dtab, tab.data(), tab.size() * sizeof(cplx), hipMemcpyHostToDevice, c->st);
+    if (e == hipSuccess && bonds) e = hipMemcpyAsync(dmk, mk.data(), mk.size() * sizeof(unsigned), hipMemcpyHostToDevice, c->st);
     if (e == hipSuccess) e = hipStreamSynchronize(c->st);  // also: nothing enqueued still uses the blocks released below
     if (e != hipSuccess) {
-        for (void* q : {(void*)eq, (void*)oe, (void*)td, (void*)ot, (void*)fine}) if (q) (void)hipFree(q);
-        return fail(DQMC_EHIP, std::string("dqmc_set_custom_bilinears: ") + hipGetErrorString(e));
+        for (void* q : {(void*)eq, (void*)oe, (void*)td, (void*)ot, (void*)fine, (void*)dtab, (void*)dmk}) if (q) (void)hipFree(q);
+        return fail(DQMC_EHIP, who + ": " + hipGetErrorString(e));
     }
     const bool eq_switch = c->eqc_on && count > 0;          // the switch outlives a replacement, not the removal
     custom_free(c);
@@ -183,6 +251,14 @@ extern "C" int dqmc_set_custom_bilinears(dqmc_ctx* c, int count, const dqmc_cplx
     c->acc[ACC_FINE0 + 5].p = fine; c->acc[ACC_FINE0 + 5].n = n_fine; c->acc[ACC_FINE0 + 5].stride = n_fine * sizeof(double);
     c->cst_eq_ob = oe; c->cst_td_ob = ot;
     c->cst_count = count;
+    bond.tab = dtab; bond.mk = dmk;
+    c->cst_bond = bond;
+    c->cst_bond_on = bonds;
+    for (int k = 0; k < 16 * DQMC_CUSTOM_MAX; ++k) {
+        const bool in = k < 16 * count;
+        c->cst_Mx[k] = in && Mx ? make_double2(Mx[k].re, Mx[k].im) : make_double2(0.0, 0.0);
+        c->cst_My[k] = in && My ? make_double2(My[k].re, My[k].im) : make_double2(0.0, 0.0);
+    }
     for (int ch = 0; ch < count; ++ch) {
         cplx* m = c->cst_M + 16 * ch;
         cplx* m2 = c->cst_M2 + 16 * ch;
@@ -199,6 +275,23 @@ extern "C" int dqmc_set_custom_bilinears(dqmc_ctx* c, int count, const dqmc_cplx
                 if (m[4 * a + b].x != 0.0 || m[4 * a + b].y != 0.0) c->cst_mask[ch] |= 1u << (4 * a + b);
                 if (v.x != 0.0 || v.y != 0.0) c->cst_mask2[ch] |= 1u << (4 * a + b);
             }
+    }
+    return DQMC_OK;
+}
+extern "C" int dqmc_set_custom_bilinears(dqmc_ctx* c, int count, const dqmc_cplx* M) {
+    return custom_set(c, count, M, nullptr, nullptr, "dqmc_set_custom_bilinears");
+}
+extern "C" int dqmc_set_custom_bond_bilinears(dqmc_ctx* c, int count, const dqmc_cplx* M0, const dqmc_cplx* Mx, const dqmc_cplx* My) {
+    return custom_set(c, count, M0, Mx, My, "dqmc_set_custom_bond_bilinears");
+}
+extern "C" int dqmc_get_custom_bond_bilinears(dqmc_ctx* c, int* count, dqmc_cplx* M0, dqmc_cplx* Mx, dqmc_cplx* My) {
+    if (!c || !count) return fail(DQMC_EINVAL, "null argument");
+    if (c->hm.hubbard) return fail(DQMC_EINVAL, "the user-defined bilinears belong to the SDW model");
+    *count = c->cst_count;
+    for (int k = 0; k < 16 * c->cst_count; ++k) {
+        if (M0) { M0[k].re = c->cst_M[k].x; M0[k].im = c->cst_M[k].y; }
+        if (Mx) { Mx[k].re = c->cst_Mx[k].x; Mx[k].im = c->cst_Mx[k].y; }
+        if (My) { My[k].re = c->cst_My[k].x; My[k].im = c->cst_My[k].y; }
     }
     return DQMC_OK;
 }
@@ -250,7 +343,11 @@ static void td_onebody(dqmc_ctx* c, unsigned mask, const cplx* g, int t) {
     if (mask & CH_PH) { ProfScope ps(c, FAM_OTHER, 1); launch_td_ph_onebody(c->lc, c->hm, c->T1, c->ph_ob, t); }
     if (mask & CH_CUR) { ProfScope ps(c, FAM_OTHER, 1); launch_td_current_onebody(c->lc, c->hm, c->T1, c->cur_bt, c->cur_ob, t); }
     if (mask & CH_BAND) { ProfScope ps(c, FAM_OTHER, 1); launch_td_band_onebody(c->lc, c->hm, c->T1, c->band_ob, t); }
-    if (mask & CH_CUSTOM) { ProfScope ps(c, FAM_OTHER, 1); launch_td_custom_onebody(c->lc, c->hm, c->cst_count, c->cst_M, c->cst_mask, c->T1, c->cst_td_ob, t); }
+    if (mask & CH_CUSTOM) {
+        ProfScope ps(c, FAM_OTHER, 1);
+        launch_td_custom_onebody(c->lc, c->hm, c->cst_count, c->cst_M, c->cst_mask, c->T1, c->cst_td_ob, t,
+                                 c->cst_bond_on ? &c->cst_bond : nullptr);
+    }
 }
 // The one place that launches the channel kernels: row `row` of `rows` of the masked channels' blocks (channel ch: acc[first + ch]) from
 // (gt0, g0t, gtt, g00) = (G(tau,0), G(0,tau), G(tau), G(0)).  Every shifted matrix is prepared once and handed to all masked kernels:
@@ -275,7 +372,8 @@ static void td_row(dqmc_ctx* c, unsigned mask, int first, int row, int rows, con
     if (mask & CH_CUSTOM) {
         ProfScope ps(c, FAM_OTHER, 1);
         const AccBlock& a = c->acc[first + 5];
-        launch_measure_td_custom(c->lc, c->hm, c->cst_count, c->cst_M, c->cst_mask, c->T1, c->ph_H, c->cst_td_ob, a.p, a.stride / sizeof(double), row, rows);
+        launch_measure_td_custom(c->lc, c->hm, c->cst_count, c->cst_M, c->cst_mask, c->T1, c->ph_H, c->cst_td_ob, a.p, a.stride / sizeof(double), row, rows,
+                                 c->cst_bond_on ? &c->cst_bond : nullptr);
     }
 }
 // what every entry that works at boundary j asks for; need_current_G: the entry also reads G, which must still be G(tau_j)

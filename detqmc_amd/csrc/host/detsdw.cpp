@@ -1000,24 +1000,51 @@ void DetSDW::seriesCustomDerived(int c, int qx, int qy, double* value, double* e
 }
 bool DetSDW::customTd() const { return customCount() && ph_level(ch_[0].pars); }
 bool DetSDW::customEq() const { return customCount() && eq_correlators(ch_[0].pars); }
-void DetSDW::setCustomBilinears(int count, const dqmc_cplx* M) {
+void DetSDW::setCustomBilinears(int count, const dqmc_cplx* M) { setCustomOperators(count, M, nullptr, nullptr, false); }
+void DetSDW::setCustomBondBilinears(int count, const dqmc_cplx* M0, const dqmc_cplx* Mx, const dqmc_cplx* My) {
+    setCustomOperators(count, M0, Mx, My, true);
+}
+void DetSDW::getCustomBondBilinears(int* count, dqmc_cplx* M0, dqmc_cplx* Mx, dqmc_cplx* My) const {
+    if (!count) throw ParameterWrong("detsdw_get_custom_bond_bilinears: null argument");
+    *count = customCount();
+    const dqmc_cplx zero{0.0, 0.0};
+    for (size_t k = 0; k < customM_.size(); ++k) {
+        if (M0) M0[k] = customM_[k];
+        if (Mx) Mx[k] = customBond() ? customMx_[k] : zero;
+        if (My) My[k] = customBond() ? customMy_[k] : zero;
+    }
+}
+// Both setters: `bond` names the entry that was called (its kernel-level twin validates and words the refusals)
+void DetSDW::setCustomOperators(int count, const dqmc_cplx* M, const dqmc_cplx* Mx, const dqmc_cplx* My, bool bond) {
     const detsdw_params& p = ch_[0].pars;
+    const std::string host = bond ? "detsdw_set_custom_bond_bilinears" : "detsdw_set_custom_bilinears";
+    const std::string kern = bond ? "dqmc_set_custom_bond_bilinears: " : "dqmc_set_custom_bilinears: ";
     if (!eq_correlators(p) && !ph_level(p)) throw ParameterWrong("custom bilinears need equalTimeCorrelators or timeDisplacedParticleHole");
-    if (count < 0 || count > DQMC_CUSTOM_MAX || (count && !M)) throw ParameterWrong("detsdw_set_custom_bilinears: count must be in 0 .. 4, with the matrices");
+    if (count < 0 || count > DQMC_CUSTOM_MAX || (count && !M)) throw ParameterWrong(host + ": count must be in 0 .. 4, with the matrices");
     // such a series has no part for matrices set after it began and suppresses the host copy: their equal-time block would land nowhere
     if (seriesNoHostCopy()) throw ParameterWrong("custom bilinears cannot be set while a series with DETSDW_SERIES_NO_HOST_COPY is open");
     // The kernel contexts validate alike, so a refusal of the matrices comes from the first one and nothing has changed.  An allocation
     // can fail in a later one: the contexts that already took the new matrices get the old ones back (their blocks cleared), so that
     // every context and customM_ agree again before the error is passed on.
     for (size_t i = 0; i < groups_.size(); ++i) {
-        const int rc = dqmc_set_custom_bilinears(groups_[i].ctx, count, M);
+        const int rc = bond ? dqmc_set_custom_bond_bilinears(groups_[i].ctx, count, M, Mx, My) : dqmc_set_custom_bilinears(groups_[i].ctx, count, M);
         if (rc == DQMC_OK) continue;
         const std::string why = dqmc_last_error();
         for (size_t k = 0; k < i; ++k)
-            if (dqmc_set_custom_bilinears(groups_[k].ctx, customCount(), customM_.data()) != DQMC_OK)
-                throw GeneralError(rc, "dqmc_set_custom_bilinears: " + why + "; restoring the earlier matrices failed as well: the handle's kernel contexts disagree, destroy it");
-        throw GeneralError(rc, "dqmc_set_custom_bilinears: " + why);
+            if (dqmc_set_custom_bond_bilinears(groups_[k].ctx, customCount(), customM_.data(), customBond() ? customMx_.data() : nullptr,
+                                               customBond() ? customMy_.data() : nullptr) != DQMC_OK)
+                throw GeneralError(rc, kern + why + "; restoring the earlier matrices failed as well: the handle's kernel contexts disagree, destroy it");
+        throw GeneralError(rc, kern + why);
     }
+    // the bond parts are kept only while one of them is non-zero: without any the handle is in the state set_custom_bilinears leaves
+    const dqmc_cplx zero{0.0, 0.0};
+    std::vector<dqmc_cplx> bx((size_t)16 * count, zero), by((size_t)16 * count, zero);
+    if (Mx) bx.assign(Mx, Mx + (size_t)16 * count);
+    if (My) by.assign(My, My + (size_t)16 * count);
+    bool any = false;
+    for (size_t k = 0; k < bx.size(); ++k) any = any || bx[k].re != 0.0 || bx[k].im != 0.0 || by[k].re != 0.0 || by[k].im != 0.0;
+    if (!any) { bx.clear(); by.clear(); }
+    customMx_.swap(bx); customMy_.swap(by);
     customM_.assign(M, M + (size_t)16 * count);
     for (auto& g : groups_) g.matsNfreq[5] = 0;            // the other channels' transforms and blocks are untouched
     for (auto& c : ch_) {
@@ -1570,6 +1597,12 @@ void DetSDW::seriesSave(const std::string& path) {
         const int32_t nc = customCount();
         wr(fc.f, &nc, sizeof(nc));
         wr(fc.f, customM_.data(), customM_.size() * sizeof(dqmc_cplx));
+        if (customBond()) {                                  // one more block; without a bond part the file keeps its bytes
+            const int32_t flag = 1;
+            wr(fc.f, &flag, sizeof(flag));
+            wr(fc.f, customMx_.data(), customMx_.size() * sizeof(dqmc_cplx));
+            wr(fc.f, customMy_.data(), customMy_.size() * sizeof(dqmc_cplx));
+        }
     }
 }
 
@@ -1613,6 +1646,28 @@ void DetSDW::seriesLoad(const std::string& path) {
         rd(fc.f, M.data(), M.size() * sizeof(dqmc_cplx));
         if (std::memcmp(M.data(), customM_.data(), M.size() * sizeof(dqmc_cplx)) != 0)
             throw ParameterWrong("series file: written with other user-defined bilinears than the ones that are set");
+        // the bond block, present only if a bond part was set: told by the length of what is left, which is either nothing or the block
+        const size_t blockBytes = sizeof(int32_t) + (size_t)2 * 16 * nc * sizeof(dqmc_cplx);
+        const long here = std::ftell(fc.f);
+        if (here < 0 || std::fseek(fc.f, 0, SEEK_END) != 0) throw GeneralError(DQMC_EINVAL, "series file: cannot be positioned");
+        const long end = std::ftell(fc.f);
+        if (end < here || std::fseek(fc.f, here, SEEK_SET) != 0) throw GeneralError(DQMC_EINVAL, "series file: cannot be positioned");
+        const size_t rest = (size_t)(end - here);
+        if (rest != 0 && rest != blockBytes)
+            throw GeneralError(DQMC_EINVAL, rest > blockBytes ? "series file: longer than its header says" : "series file: truncated");
+        const bool has = rest == blockBytes;
+        int32_t flag = 0;
+        if (has) rd(fc.f, &flag, sizeof(flag));
+        if (has != customBond()) throw ParameterWrong("series file: the bond parts of the user-defined bilinears differ from the ones that are set");
+        if (has) {
+            if (flag != 1) throw GeneralError(DQMC_EINVAL, "series file: bad bond block of the user-defined bilinears");
+            std::vector<dqmc_cplx> bx((size_t)16 * nc), by((size_t)16 * nc);
+            rd(fc.f, bx.data(), bx.size() * sizeof(dqmc_cplx));
+            rd(fc.f, by.data(), by.size() * sizeof(dqmc_cplx));
+            if (std::memcmp(bx.data(), customMx_.data(), bx.size() * sizeof(dqmc_cplx)) != 0 ||
+                std::memcmp(by.data(), customMy_.data(), by.size() * sizeof(dqmc_cplx)) != 0)
+                throw ParameterWrong("series file: the bond parts of the user-defined bilinears differ from the ones that are set");
+        }
     }
     char more;
     if (std::fread(&more, 1, 1, fc.f) != 0) throw GeneralError(DQMC_EINVAL, "series file: longer than its header says");
@@ -1721,6 +1776,12 @@ extern "C" int detsdw_series_stats_all(detsdw_replica* r, int which, double* mea
 extern "C" int detsdw_series_derived_all(detsdw_replica* r, int what, double* value, double* err) {
     if (!value || !err) { g_host_err = "null argument"; return DQMC_EINVAL; }
     RGUARD(r->impl->seriesDerivedAll(what, value, err))
+}
+extern "C" int detsdw_set_custom_bond_bilinears(detsdw_replica* r, int count, const dqmc_cplx* M0, const dqmc_cplx* Mx, const dqmc_cplx* My) {
+    RGUARD(r->impl->setCustomBondBilinears(count, M0, Mx, My))
+}
+extern "C" int detsdw_get_custom_bond_bilinears(detsdw_replica* r, int* count, dqmc_cplx* M0, dqmc_cplx* Mx, dqmc_cplx* My) {
+    RGUARD(r->impl->getCustomBondBilinears(count, M0, Mx, My))
 }
 extern "C" int detsdw_set_custom_bilinears(detsdw_replica* r, int count, const dqmc_cplx* M) {
     RGUARD(r->impl->setCustomBilinears(count, M))

@@ -74,6 +74,8 @@ public:
     void seriesCustomDerived(int c, int qx, int qy, double* value, double* err);
     // user-defined bilinears (include/detsdw_host.h): count Hermitian 4 x 4 matrices for every kernel context, between sweeps
     void setCustomBilinears(int count, const dqmc_cplx* M);
+    void setCustomBondBilinears(int count, const dqmc_cplx* M0, const dqmc_cplx* Mx, const dqmc_cplx* My);
+    void getCustomBondBilinears(int* count, dqmc_cplx* M0, dqmc_cplx* Mx, dqmc_cplx* My) const;
     void seriesReadBins(int which, int first, int count, double* out, int b = 0);
     // long runs: options, re-binning, binning analysis (err, tau [levels] x the slice of seriesStats; tau may be null), series file
     void seriesConfigure(int flags);
@@ -147,6 +149,9 @@ private:
     int performedSweeps_ = 0;
     std::vector<dqmc_cplx> customM_;               // the matrices of setCustomBilinears, [count][4][4] (every kernel context holds the same)
     int customCount() const { return (int)customM_.size() / 16; }
+    std::vector<dqmc_cplx> customMx_, customMy_;   // the bond parts of setCustomBondBilinears, [count][4][4] each; empty while none is non-zero
+    bool customBond() const { return !customMx_.empty(); }
+    void setCustomOperators(int count, const dqmc_cplx* M, const dqmc_cplx* Mx, const dqmc_cplx* My, bool bond);
     bool customTd() const;                         // matrices are set and the handle measures the particle-hole family
     bool customEq() const;                         // ... the equal-time correlators
 

@@ -1164,6 +1164,12 @@ __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_td_custom(DevM
     if (blockIdx.x == 0 && tid == 0) acc[row] += 1.0;
 }
 
+// the stencil kernels of the bond parts, further down
+static void launch_td_custom_bond_onebody(const Launch& lc, const DevModel& hm, int count, const CustomBond& bond, const cplx* gs, cplx* ob, int t);
+static void launch_measure_td_custom_bond(const Launch& lc, const DevModel& hm, int count, const CustomBond& bond, const cplx* gs, const cplx* hs,
+                                          const cplx* ob, double* acc, size_t acs, int row, int rows);
+static void launch_measure_eq_custom_bond(const Launch& lc, const DevModel& hm, int count, const CustomBond& bond, const cplx* gs, cplx* ob, double* acc);
+
 static CustomMats custom_mats(int count, const cplx* M, const unsigned* mask) {
     CustomMats cm{};
     cm.count = count;
@@ -1174,7 +1180,9 @@ static CustomMats custom_mats(int count, const cplx* M, const unsigned* mask) {
     return cm;
 }
 
-void launch_td_custom_onebody(const Launch& lc, const DevModel& hm, int count, const cplx* M, const unsigned* mask, const cplx* gs, cplx* ob, int t) {
+void launch_td_custom_onebody(const Launch& lc, const DevModel& hm, int count, const cplx* M, const unsigned* mask, const cplx* gs, cplx* ob, int t,
+                              const CustomBond* bond) {
+    if (bond) return launch_td_custom_bond_onebody(lc, hm, count, *bond, gs, ob, t);
     const CustomMats cm = custom_mats(count, M, mask);
     const dim3 grid((hm.N + 255) / 256, 1, lc.nb);
     const size_t obs = measure_td_custom_onebody_cplx(count, hm.N);
@@ -1184,7 +1192,8 @@ void launch_td_custom_onebody(const Launch& lc, const DevModel& hm, int count, c
 }
 
 void launch_measure_td_custom(const Launch& lc, const DevModel& hm, int count, const cplx* M, const unsigned* mask, const cplx* gs, const cplx* hs,
-                              const cplx* ob, double* acc, size_t acs, int row, int rows) {
+                              const cplx* ob, double* acc, size_t acs, int row, int rows, const CustomBond* bond) {
+    if (bond) return launch_measure_td_custom_bond(lc, hm, count, *bond, gs, hs, ob, acc, acs, row, rows);
     const CustomMats cm = custom_mats(count, M, mask);
     const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
     const size_t obs = measure_td_custom_onebody_cplx(count, hm.N);
@@ -1272,7 +1281,8 @@ __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_eq_custom(DevM
 }
 
 void launch_measure_eq_custom(const Launch& lc, const DevModel& hm, int count, const cplx* M, const unsigned* mask, const cplx* M2, const unsigned* mask2,
-                              const cplx* gs, cplx* ob, double* acc) {
+                              const cplx* gs, cplx* ob, double* acc, const CustomBond* bond) {
+    if (bond) return launch_measure_eq_custom_bond(lc, hm, count, *bond, gs, ob, acc);
     const CustomMats cm = custom_mats(count, M, mask), cm2 = custom_mats(count, M2, mask2);
     const dim3 g1((hm.N + 255) / 256, 1, lc.nb);
     const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
@@ -1286,6 +1296,312 @@ void launch_measure_eq_custom(const Launch& lc, const DevModel& hm, int count, c
     } else {
         hipLaunchKernelGGL((k_eq_custom_onebody<3>), g1, dim3(256), 0, lc.st, hm, cm, cm2, gs, ob, obs, lc.cs);
         hipLaunchKernelGGL((k_measure_eq_custom<3>), grid, block, 0, lc.st, hm, cm, gs, ob, acc, obs, acs, lc.cs);
+    }
+}
+
+// Bond parts of the user-defined bilinears (dqmc_set_custom_bond_bilinears; definitions in dqmc_hip.h and DESIGN.md 6e).  As a one-body
+// matrix over (site, flavour) operator O_A has five 4 x 4 site blocks V_k(A) = f_k(A) W_k between the stencil sites A, Ax = A (+) x,
+// Ay = A (+) y:
+//   k    block (p, q)   W_k     f_k(A)              p: site of c^+, q: site of c
+//   0    (A,  A)        M0      1
+//   1    (Ax, A)        Mx      u_x(A)
+//   2    (A,  Ax)       Mx^H    conj u_x(A)
+//   3    (Ay, A)        My      u_y(A)
+//   4    (A,  Ay)       My^H    conj u_y(A)
+// u the link factor of the stored sector; the conjugate sector carries conj u, which is the stored-sector / conjugate-sector rule of cst_E
+// once the factor multiplies the stored part of a block of g (with flux u is complex and every W_k, k > 0, diagonal; without it u = +-1
+// and a W_k that couples the sectors is as legal as any other).  With E^(qr)_bc = gt0(A^q b; B^r c) and T^(sp)_da = g0t(B^s d; A^p a)
+//   o_t(A)     = tr M0 - sum_k f_k sum_ab (W_k)_ab g_t(A^q b; A^p a)
+//   conn(A, B) = sum_(k, k') Re f_k(A) f_k'(B) tr(W_k E^(qr) W_k' T^(sp)),        (p, q) of k at A, (r, s) of k' at B:
+// 25 block pairs, each the Re tr(M E M T) of the on-site kernel with two different matrices.  The pair loop is a real loop (not unrolled:
+// the body is the four channels' unrolled products already) and only its one E and one T block are live; the neighbour blocks are
+// re-read from L1 / L2 by the argument above k_measure_td_current.  The blocks W_k, their non-zero masks and u come from a small device
+// table indexed by the loop variables (uniform: scalar loads); parts[c] bit k = W_k of operator c is non-zero, so the pairs no operator
+// needs are skipped before their loads and an on-site-only operator takes part in pair (0, 0) alone.
+// Equal-time form: gt0 -> gs, g0t -> gs - 1, the 1 subtracted from the diagonal of T wherever B^s and A^p are the same site (d = 0,
+// +-x, +-y, +-(x - y)) -- the delta term in full, no M^2 shortcut.
+// Shape, walk order over B, LDS reduction, one writer per accumulator, fixed order, no atomics: those of k_measure_td_custom.
+#define CSTB_K 5
+size_t measure_custom_bond_table_cplx(int count, int N) { return (size_t)count * CSTB_K * 16 + 2 * (size_t)N; }
+struct CustomBondArg { const cplx* tab; const unsigned* mk; unsigned parts[DQMC_CUSTOM_MAX]; int count; };
+
+// Re tr(MA E MB T); e[r][c] = E_rc, t[r][c] = T_rc of the stored part, MA / MB row-major in device memory
+template<int OPDIM, int R>
+__device__ __forceinline__ double cstb_connected(const cplx (&e)[R][R], const cplx (&t)[R][R], const cplx* __restrict__ MA, unsigned ma,
+                                                 const cplx* __restrict__ MB, unsigned mb) {
+    double s = 0.0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        if (!((ma >> (4 * a)) & 0xfu)) continue;            // row a of MA is empty
+        cplx x[4], y[4];                                    // x[c] = (MA E)_ac, y[c] = (MB T)_ca
+#pragma unroll
+        for (int c2 = 0; c2 < 4; ++c2) x[c2] = y[c2] = make_double2(0.0, 0.0);
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+            if (ma & (1u << (4 * a + b))) {
+                const cplx m = MA[4 * a + b];
+#pragma unroll
+                for (int c2 = 0; c2 < 4; ++c2)
+                    if (cst_same<OPDIM>(b, c2)) cst_fma(x[c2], m, cst_E<OPDIM, R>(e, b, c2));
+            }
+#pragma unroll
+        for (int c2 = 0; c2 < 4; ++c2)
+#pragma unroll
+            for (int dl = 0; dl < 4; ++dl)
+                if (cst_same<OPDIM>(dl, a) && (mb & (1u << (4 * c2 + dl)))) cst_fma(y[c2], MB[4 * c2 + dl], cst_E<OPDIM, R>(t, dl, a));
+#pragma unroll
+        for (int c2 = 0; c2 < 4; ++c2) s += x[c2].x * y[c2].x - x[c2].y * y[c2].y;
+    }
+    return s;
+}
+
+// the sites (p, q) of block k at the stencil (S, Sx, Sy) and its link factor from (ux, uy)
+__device__ __forceinline__ void cstb_block(int k, int S, int Sx, int Sy, cplx ux, cplx uy, int& p, int& q, cplx& f) {
+    p = k == 1 ? Sx : k == 3 ? Sy : S;
+    q = k == 2 ? Sx : k == 4 ? Sy : S;
+    const cplx u = k < 3 ? ux : uy;
+    f = k == 0 ? make_double2(1.0, 0.0) : make_double2(u.x, (k & 1) ? u.y : -u.y);
+}
+__device__ __forceinline__ void cstb_stencil(int L, int sx, int sy, int& Sx, int& Sy) {
+    Sx = sy * L + (sx + 1 == L ? 0 : sx + 1);
+    Sy = (sy + 1 == L ? 0 : sy + 1) * L + sx;
+}
+
+// o(A) of operator ch from the shifted equal-time matrix gs
+template<int OPDIM>
+__device__ __forceinline__ cplx cstb_onebody(const cplx* __restrict__ gs, size_t ng, int N, int L, int A, const CustomBondArg& cb, int ch) {
+    constexpr int R = OPDIM == 3 ? 4 : 2;
+    const cplx* __restrict__ V = cb.tab + (size_t)ch * CSTB_K * 16;
+    const cplx* __restrict__ lk = cb.tab + (size_t)cb.count * CSTB_K * 16;
+    int Ax, Ay;
+    cstb_stencil(L, A % L, A / L, Ax, Ay);
+    const cplx ux = lk[A], uy = lk[N + A];
+    cplx s = make_double2(0.0, 0.0);
+#pragma unroll 1
+    for (int k = 0; k < CSTB_K; ++k) {
+        if (!((cb.parts[ch] >> k) & 1u)) continue;
+        int p, q;
+        cplx f;
+        cstb_block(k, A, Ax, Ay, ux, uy, p, q, f);
+        const cplx* base = gs + (size_t)p * ng + (size_t)q;      // x[b][a] = f g(A^q b; A^p a)
+        cplx x[R][R];
+#pragma unroll
+        for (int a = 0; a < R; ++a)
+#pragma unroll
+            for (int b = 0; b < R; ++b) x[b][a] = m_mul(f, base[(size_t)a * N * ng + (size_t)b * N]);
+        const cplx* __restrict__ M = V + 16 * k;
+        const unsigned mask = cb.mk[ch * CSTB_K + k];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                if (cst_same<OPDIM>(b, a) && (mask & (1u << (4 * a + b)))) cst_fma(s, M[4 * a + b], cst_E<OPDIM, R>(x, b, a));
+    }
+    const cplx tr = m_add(m_add(V[0], V[5]), m_add(V[10], V[15]));
+    return m_sub(tr, s);
+}
+
+// ob[chain][t][channel][site] as k_td_custom_onebody
+template<int OPDIM>
+__global__ __launch_bounds__(256) void k_td_custom_bond_onebody(DevModel dm, CustomBondArg cb, const cplx* __restrict__ gs, cplx* __restrict__ ob, int t,
+                                                                size_t obs, size_t cs) {
+    CHAIN(gs);
+    const int N = dm.N, A = blockIdx.x * 256 + threadIdx.x;
+    if (A >= N) return;
+    cplx* o = ob + (size_t)blockIdx.z * obs + (size_t)t * cb.count * N + A;
+#pragma unroll
+    for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
+        if (ch < cb.count) o[(size_t)ch * N] = cstb_onebody<OPDIM>(gs, (size_t)dm.ng, N, dm.L, A, cb, ch);
+}
+// ob[chain][channel][site]: the one set of values both factors of the equal-time form use
+template<int OPDIM>
+__global__ __launch_bounds__(256) void k_eq_custom_bond_onebody(DevModel dm, CustomBondArg cb, const cplx* __restrict__ gs, cplx* __restrict__ ob,
+                                                                size_t obs, size_t cs) {
+    CHAIN(gs);
+    const int N = dm.N, A = blockIdx.x * 256 + threadIdx.x;
+    if (A >= N) return;
+    cplx* o = ob + (size_t)blockIdx.z * obs + A;
+#pragma unroll
+    for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
+        if (ch < cb.count) o[(size_t)ch * N] = cstb_onebody<OPDIM>(gs, (size_t)dm.ng, N, dm.L, A, cb, ch);
+}
+
+// the sums over B of Re W(B (+) d, B) of one thread's (bin, part); EQ: hs is not read, ot == o0
+template<int OPDIM, bool EQ>
+__device__ __forceinline__ void cstb_walk(const DevModel& dm, const CustomBondArg& cb, const cplx* __restrict__ gs, const cplx* __restrict__ hs,
+                                          const cplx* __restrict__ ot, const cplx* __restrict__ o0, int part, int d, double (&w)[DQMC_CUSTOM_MAX]) {
+    constexpr int R = OPDIM == 3 ? 4 : 2;
+    const int N = dm.N, L = dm.L, count = cb.count;
+    const size_t ng = (size_t)dm.ng, cN = (size_t)N * ng;
+    const cplx* __restrict__ lk = cb.tab + (size_t)count * CSTB_K * 16;
+    const int dx = d % L, dy = d / L;
+    unsigned both[DQMC_CUSTOM_MAX];                         // bit 5 ka + kb: operator ch has the blocks ka and kb
+    unsigned need = 0;
+#pragma unroll
+    for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) {
+        both[ch] = 0;
+        if (ch < count)
+            for (int ka = 0; ka < CSTB_K; ++ka)
+                if ((cb.parts[ch] >> ka) & 1u) both[ch] |= (cb.parts[ch] & 0x1fu) << (CSTB_K * ka);
+        need |= both[ch];
+    }
+    int bx = part % L, by = part / L;                       // site B = part + 8 i, kept as (bx, by)
+    const int stepx = TDP_PARTS % L, stepy = TDP_PARTS / L;
+    for (int B = part; B < N; B += TDP_PARTS) {
+        int ax = bx + dx, ay = by + dy;
+        if (ax >= L) ax -= L;
+        if (ay >= L) ay -= L;
+        const int A = ay * L + ax;
+        int Ax, Ay, Bx, By;
+        cstb_stencil(L, ax, ay, Ax, Ay);
+        cstb_stencil(L, bx, by, Bx, By);
+        const cplx uax = lk[A], uay = lk[N + A], ubx = lk[B], uby = lk[N + B];
+#pragma unroll
+        for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
+            if (ch < count) {
+                const cplx a = ot[(size_t)ch * N + A], b = o0[(size_t)ch * N + B];
+                w[ch] += a.x * b.x - a.y * b.y;
+            }
+#pragma unroll 1
+        for (int pr = 0; pr < CSTB_K * CSTB_K; ++pr) {
+            if (!((need >> pr) & 1u)) continue;
+            const int ka = pr / CSTB_K, kb = pr % CSTB_K;
+            int p, q, r, s2;
+            cplx fa, fb;
+            cstb_block(ka, A, Ax, Ay, uax, uay, p, q, fa);
+            cstb_block(kb, B, Bx, By, ubx, uby, r, s2, fb);
+            const cplx f = m_mul(fa, fb);
+            const cplx* pe = gs + (size_t)r * ng + (size_t)q;         // E_bc = gt0(A^q b; B^r c) = pe[c N ng + b N]
+            cplx e[R][R], t[R][R];
+#pragma unroll
+            for (int c2 = 0; c2 < R; ++c2)
+#pragma unroll
+                for (int b = 0; b < R; ++b) e[b][c2] = m_mul(f, pe[(size_t)c2 * cN + (size_t)b * N]);
+            if (EQ) {
+                const cplx* pt = gs + (size_t)p * ng + (size_t)s2;    // T_da = gs(B^s d; A^p a) - delta = pt[a N ng + d N] - delta
+                const double one = s2 == p ? 1.0 : 0.0;
+#pragma unroll
+                for (int a = 0; a < R; ++a)
+#pragma unroll
+                    for (int dl = 0; dl < R; ++dl) {
+                        t[dl][a] = pt[(size_t)a * cN + (size_t)dl * N];
+                        if (dl == a) t[dl][a].x -= one;
+                    }
+            } else {
+                const cplx* ph = hs + (size_t)s2 * ng + (size_t)p;    // T_da = conj hs(A^p a; B^s d) = conj ph[d N ng + a N]
+#pragma unroll
+                for (int dl = 0; dl < R; ++dl)
+#pragma unroll
+                    for (int a = 0; a < R; ++a) {
+                        const cplx h = ph[(size_t)dl * cN + (size_t)a * N];
+                        t[dl][a] = make_double2(h.x, -h.y);
+                    }
+            }
+#pragma unroll
+            for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
+                if ((both[ch] >> pr) & 1u) {
+                    const cplx* __restrict__ V = cb.tab + (size_t)ch * CSTB_K * 16;
+                    w[ch] -= cstb_connected<OPDIM, R>(e, t, V + 16 * ka, cb.mk[ch * CSTB_K + ka], V + 16 * kb, cb.mk[ch * CSTB_K + kb]);
+                }
+        }
+        bx += stepx; by += stepy;
+        if (bx >= L) { bx -= L; ++by; }
+    }
+}
+
+template<int OPDIM>
+__global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_td_custom_bond(DevModel dm, CustomBondArg cb, const cplx* __restrict__ gs,
+                                                                                 const cplx* __restrict__ hs, const cplx* __restrict__ ob,
+                                                                                 double* __restrict__ acc, int row, int rows, size_t obs, size_t acs,
+                                                                                 size_t cs) {
+    CHAIN(gs); CHAIN(hs);
+    ob += (size_t)blockIdx.z * obs;
+    acc += (size_t)blockIdx.z * acs;
+    __shared__ double red[DQMC_CUSTOM_MAX][TDP_PARTS][TDP_BINS];
+    const int N = dm.N, tid = threadIdx.x, count = cb.count;
+    const int lb = tid % TDP_BINS, part = tid / TDP_BINS;
+    const int d = blockIdx.x * TDP_BINS + lb;
+    const bool valid = d < N;
+    double w[DQMC_CUSTOM_MAX] = {0.0, 0.0, 0.0, 0.0};
+    if (valid) cstb_walk<OPDIM, false>(dm, cb, gs, hs, ob, ob + (size_t)count * N, part, d, w);
+#pragma unroll
+    for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) red[ch][part][lb] = w[ch];
+    __syncthreads();
+    if (part < count && valid) {                            // part ch writes channel ch of its bin
+        double s = red[part][0][lb];
+#pragma unroll
+        for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
+        acc[rows + (size_t)row * count * N + (size_t)part * N + d] += s;
+    }
+    if (blockIdx.x == 0 && tid == 0) acc[row] += 1.0;
+}
+
+template<int OPDIM>
+__global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_eq_custom_bond(DevModel dm, CustomBondArg cb, const cplx* __restrict__ gs,
+                                                                                 const cplx* __restrict__ ob, double* __restrict__ acc, size_t obs,
+                                                                                 size_t acs, size_t cs) {
+    CHAIN(gs);
+    ob += (size_t)blockIdx.z * obs;
+    acc += (size_t)blockIdx.z * acs;
+    __shared__ double red[DQMC_CUSTOM_MAX][TDP_PARTS][TDP_BINS];
+    const int N = dm.N, tid = threadIdx.x, count = cb.count;
+    const int lb = tid % TDP_BINS, part = tid / TDP_BINS;
+    const int d = blockIdx.x * TDP_BINS + lb;
+    const bool valid = d < N;
+    double w[DQMC_CUSTOM_MAX] = {0.0, 0.0, 0.0, 0.0};
+    if (valid) cstb_walk<OPDIM, true>(dm, cb, gs, gs, ob, ob, part, d, w);
+#pragma unroll
+    for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) red[ch][part][lb] = w[ch];
+    __syncthreads();
+    if (part < count && valid) {                            // part ch writes channel ch of its bin
+        double s = red[part][0][lb];
+#pragma unroll
+        for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
+        acc[1 + (size_t)part * N + d] += s;
+    }
+    if (blockIdx.x == 0 && tid == 0) acc[0] += 1.0;
+}
+
+static CustomBondArg custom_bond_arg(int count, const CustomBond& bond) {
+    CustomBondArg cb{};
+    cb.tab = bond.tab; cb.mk = bond.mk; cb.count = count;
+    for (int ch = 0; ch < count; ++ch) cb.parts[ch] = bond.parts[ch];
+    return cb;
+}
+
+static void launch_td_custom_bond_onebody(const Launch& lc, const DevModel& hm, int count, const CustomBond& bond, const cplx* gs, cplx* ob, int t) {
+    const CustomBondArg cb = custom_bond_arg(count, bond);
+    const dim3 grid((hm.N + 255) / 256, 1, lc.nb);
+    const size_t obs = measure_td_custom_onebody_cplx(count, hm.N);
+    if (hm.opdim == 1) hipLaunchKernelGGL((k_td_custom_bond_onebody<1>), grid, dim3(256), 0, lc.st, hm, cb, gs, ob, t, obs, lc.cs);
+    else if (hm.opdim == 2) hipLaunchKernelGGL((k_td_custom_bond_onebody<2>), grid, dim3(256), 0, lc.st, hm, cb, gs, ob, t, obs, lc.cs);
+    else hipLaunchKernelGGL((k_td_custom_bond_onebody<3>), grid, dim3(256), 0, lc.st, hm, cb, gs, ob, t, obs, lc.cs);
+}
+
+static void launch_measure_td_custom_bond(const Launch& lc, const DevModel& hm, int count, const CustomBond& bond, const cplx* gs, const cplx* hs,
+                                          const cplx* ob, double* acc, size_t acs, int row, int rows) {
+    const CustomBondArg cb = custom_bond_arg(count, bond);
+    const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
+    const size_t obs = measure_td_custom_onebody_cplx(count, hm.N);
+    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_td_custom_bond<1>), grid, block, 0, lc.st, hm, cb, gs, hs, ob, acc, row, rows, obs, acs, lc.cs);
+    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_td_custom_bond<2>), grid, block, 0, lc.st, hm, cb, gs, hs, ob, acc, row, rows, obs, acs, lc.cs);
+    else hipLaunchKernelGGL((k_measure_td_custom_bond<3>), grid, block, 0, lc.st, hm, cb, gs, hs, ob, acc, row, rows, obs, acs, lc.cs);
+}
+
+static void launch_measure_eq_custom_bond(const Launch& lc, const DevModel& hm, int count, const CustomBond& bond, const cplx* gs, cplx* ob, double* acc) {
+    const CustomBondArg cb = custom_bond_arg(count, bond);
+    const dim3 g1((hm.N + 255) / 256, 1, lc.nb);
+    const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
+    const size_t obs = measure_eq_custom_onebody_cplx(count, hm.N), acs = 1 + measure_custom_row_doubles(count, hm.N);
+    if (hm.opdim == 1) {
+        hipLaunchKernelGGL((k_eq_custom_bond_onebody<1>), g1, dim3(256), 0, lc.st, hm, cb, gs, ob, obs, lc.cs);
+        hipLaunchKernelGGL((k_measure_eq_custom_bond<1>), grid, block, 0, lc.st, hm, cb, gs, ob, acc, obs, acs, lc.cs);
+    } else if (hm.opdim == 2) {
+        hipLaunchKernelGGL((k_eq_custom_bond_onebody<2>), g1, dim3(256), 0, lc.st, hm, cb, gs, ob, obs, lc.cs);
+        hipLaunchKernelGGL((k_measure_eq_custom_bond<2>), grid, block, 0, lc.st, hm, cb, gs, ob, acc, obs, acs, lc.cs);
+    } else {
+        hipLaunchKernelGGL((k_eq_custom_bond_onebody<3>), g1, dim3(256), 0, lc.st, hm, cb, gs, ob, obs, lc.cs);
+        hipLaunchKernelGGL((k_measure_eq_custom_bond<3>), grid, block, 0, lc.st, hm, cb, gs, ob, acc, obs, acs, lc.cs);
     }
 }
 

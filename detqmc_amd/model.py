@@ -243,6 +243,45 @@ def _custom_matrices(mats):
     return np.ascontiguousarray(np.asarray(list(mats), dtype=np.complex128).reshape(-1, 4, 4))
 
 
+def _custom_bond_operators(ops):
+    """the argument of set_custom_bond_bilinears, a list of (M0, Mx, My) with None for a zero matrix, as three C-contiguous complex
+    arrays (count, 4, 4); the library validates the entries"""
+    ops = [tuple(op) for op in ops]
+    if any(len(op) != 3 for op in ops):
+        raise ValueError("every operator is a tuple (M0, Mx, My); None stands for a zero matrix")
+    zero = np.zeros((4, 4), dtype=np.complex128)
+    return [_custom_matrices([zero if op[k] is None else op[k] for op in ops]) for k in range(3)]
+
+
+def _get_custom_bond(call, handle, host):
+    n = C.c_int(0)
+    m = [np.zeros((_lib.DQMC_CUSTOM_MAX, 4, 4), dtype=np.complex128) for _ in range(3)]
+    check(call(handle, C.byref(n), *[a.ctypes.data for a in m]), host=host)
+    return [tuple(a[c].copy() for a in m) for c in range(n.value)]
+
+
+def _bond_tuple(params, mu, factor):
+    """(None, Mx, My) with factor * diag(-t) of the flavours' bands on the bond of direction mu (0 / 'x' or 1 / 'y')"""
+    mu = {"x": 0, "y": 1}.get(mu, mu)
+    if mu not in (0, 1):
+        raise ValueError("mu must be 'x' or 'y' (0 or 1)")
+    hop = ((params.txhor, params.tyhor), (params.txver, params.tyver))[mu]        # band x, band y
+    M = factor * np.diag([-hop[0], -hop[1], -hop[0], -hop[1]]).astype(np.complex128)      # XUP, YDOWN, XDOWN, YUP
+    return (None, M, None) if mu == 0 else (None, None, M)
+
+
+def bond_current(params, mu):
+    """the (M0, Mx, My) tuple of the current operator j_mu of measure_timedisplaced_current for set_custom_bond_bilinears:
+    M_mu = diag(i T), T = -t of the flavour's band in direction mu; the link factor (boundary sign, Peierls phase) is supplied by the
+    library.  params: anything with txhor, txver, tyhor, tyver (SDWParams, dqmc_params)"""
+    return _bond_tuple(params, mu, 1j)
+
+
+def bond_kinetic(params, mu):
+    """the same for the bond kinetic energy k_mu: M_mu = diag(T)"""
+    return _bond_tuple(params, mu, 1.0)
+
+
 class KernelContext:
     """One dqmc_ctx.  Needs a GPU."""
 
@@ -388,6 +427,17 @@ class KernelContext:
         removes them.  A second call replaces the matrices and clears their blocks"""
         m = _custom_matrices(mats)
         check(self.lib.dqmc_set_custom_bilinears(self.h, len(m), m.ctypes.data))
+
+    def set_custom_bond_bilinears(self, ops):
+        """up to four operators (M0, Mx, My): M0 Hermitian on the site, Mx / My arbitrary complex 4 x 4 on the bonds A -> A + x, A -> A + y
+        (None: zero; the Hermitian conjugate and the bonds' link factors are added by the library), measured through the same entries and
+        blocks as set_custom_bilinears, which they replace.  See bond_current / bond_kinetic"""
+        m0, mx, my = _custom_bond_operators(ops)
+        check(self.lib.dqmc_set_custom_bond_bilinears(self.h, len(m0), m0.ctypes.data, mx.ctypes.data, my.ctypes.data))
+
+    def get_custom_bond_bilinears(self):
+        """the operators that are set: a list of (M0, Mx, My), complex 4 x 4 each"""
+        return _get_custom_bond(self.lib.dqmc_get_custom_bond_bilinears, self.h, False)
 
     def get_custom_bilinears(self):
         """the matrices that are set, complex (count, 4, 4)"""
@@ -1145,6 +1195,17 @@ class DetSDWBatch:
         with equalTimeCorrelators (one of the two is needed).  Between sweeps; a second call replaces the matrices, [] removes them"""
         m = _custom_matrices(mats)
         check(self.lib.detsdw_set_custom_bilinears(self.h, len(m), m.ctypes.data), host=True)
+
+    def set_custom_bond_bilinears(self, ops):
+        """set_custom_bilinears with nearest-neighbour bond parts: a list of up to four (M0, Mx, My), None for a zero matrix (see
+        KernelContext.set_custom_bond_bilinears, bond_current, bond_kinetic).  Every 'custom{c}...' observable, Matsubara transform and
+        series quantity serves the operators unchanged"""
+        m0, mx, my = _custom_bond_operators(ops)
+        check(self.lib.detsdw_set_custom_bond_bilinears(self.h, len(m0), m0.ctypes.data, mx.ctypes.data, my.ctypes.data), host=True)
+
+    def get_custom_bond_bilinears(self):
+        """the operators that are set: a list of (M0, Mx, My), complex 4 x 4 each"""
+        return _get_custom_bond(self.lib.detsdw_get_custom_bond_bilinears, self.h, True)
 
     def matsubara_all(self, name, nfreq):
         """DetSDW.matsubara of every chain: complex (nchains, nfreq, N), one device call per sub-batch"""

@@ -307,6 +307,14 @@ int detsdw_series_band_derived(detsdw_replica* r, int what, double* value, doubl
  * detsdw_series_custom_derived: value[nchains], err[nchains] of R = 1 - 1/2 [S(Q + dx) + S(Q + dy)] / S(Q) for matrix c at Q = (qx, qy). */
 int detsdw_set_custom_bilinears(detsdw_replica* r, int count, const dqmc_cplx* M);
 int detsdw_series_custom_derived(detsdw_replica* r, int c, int qx, int qy, double* value, double* err);
+/* The same with nearest-neighbour bond parts (dqmc_set_custom_bond_bilinears: M0 Hermitian, Mx / My arbitrary or NULL, [count][4][4] each):
+ * the contract of detsdw_set_custom_bilinears, the kernel level's further refusals (all three parts of an operator zero, an off-diagonal
+ * bond entry under weakZflux) included.  Every observable, Matsubara transform and series part above serves the operators unchanged.
+ * detsdw_series_save writes, only while a bond part is non-zero, one more block behind the matrices (int32 1, Mx[count], My[count]);
+ * detsdw_series_load raises ParameterWrong if the bond parts of the file and of the handle differ, a missing block on either side
+ * included.  detsdw_set_custom_bilinears clears the bond parts.  The getter returns count and the three parts (each may be NULL). */
+int detsdw_set_custom_bond_bilinears(detsdw_replica* r, int count, const dqmc_cplx* M0, const dqmc_cplx* Mx, const dqmc_cplx* My);
+int detsdw_get_custom_bond_bilinears(detsdw_replica* r, int* count, dqmc_cplx* M0, dqmc_cplx* Mx, dqmc_cplx* My);
 int detsdw_series_read_bins(detsdw_replica* r, int which, int first, int count, double* out);
 int detsdw_series_end(detsdw_replica* r);
 /* The series over a long run (kernel calls and formulas: dqmc_hip.h).  All of it is new surface: without these calls nothing changes.

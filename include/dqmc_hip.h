@@ -440,6 +440,25 @@ int dqmc_measure_td_custom_read_host(dqmc_ctx* ctx, double* out);
 int dqmc_set_equal_time_custom(dqmc_ctx* ctx, int on);
 size_t dqmc_measure_eq_custom_accum_size(dqmc_ctx* ctx);  /* 0 while no matrix is set */
 int dqmc_measure_eq_custom_read_host(dqmc_ctx* ctx, double* out);
+/* Bond (form-factor) parts of the user-defined bilinears.  Operator c is given by three 4 x 4 matrices: M0 (Hermitian, the on-site part as
+ * above) and Mx, My (arbitrary complex) on the bonds A -> A (+) x and A -> A (+) y, the Hermitian conjugate added by the library:
+ *   O_A = sum_ab c^+_{A a} M0_ab c_{A b} + sum_{mu = x, y} sum_ab [ u^ab_mu(A) Mmu_ab c^+_{A (+) mu, a} c_{A b} + h.c. ]
+ * u is the unit-modulus link factor the hopping bond carries (antiperiodic sign times Peierls phase, built from bc and the flux): without
+ * flux +-1 for every entry; with weakZflux entry (a, a) takes flavour a's link and a non-zero flavour-off-diagonal entry of Mx or My
+ * has no covariant definition.  As a one-body matrix over (site, flavour) O_A has the blocks (A, A) = M0, (A (+) mu, A) = u Mmu,
+ * (A, A (+) mu) = (u Mmu)^H, and the correlators are the definitions above with that matrix:
+ *   o_t(A) = tr M0 - sum_ij (O_A)_ij g_t(j; i),    W(A, B) = o_tau(A) o_0(B) - sum_ijkl (O_A)_ij (O_B)_kl g0t(l; i) gt0(j; k),
+ * equal-time with gt0 -> g~ and g0t -> g~ - 1, the delta wherever two stencil sites coincide.
+ * dqmc_set_custom_bond_bilinears(ctx, count, M0, Mx, My): each array [count][4][4] row-major; Mx and My may be NULL (all zero).  It
+ * replaces whatever an earlier call of either setter left, with the side effects of dqmc_set_custom_bilinears, and returns DQMC_EINVAL
+ * with nothing changed for a count out of range, an entry that is not finite, an M0 that is not Hermitian, an operator whose three
+ * parts are all zero (M0 = 0 with a bond part is legal), an off-diagonal bond entry under weakZflux, a series with a custom part open,
+ * a Hubbard context.  While at least one operator has a bond part, dqmc_measure_timedisplaced_custom, the every-slice channel 5 and
+ * dqmc_set_equal_time_custom run the stencil kernels for every set operator; blocks, sizes and layouts are the ones above.
+ * dqmc_set_custom_bilinears clears every bond part; dqmc_get_custom_bilinears keeps returning count and the M0.
+ * dqmc_get_custom_bond_bilinears reads all three back (each array may be NULL). */
+int dqmc_set_custom_bond_bilinears(dqmc_ctx* ctx, int count, const dqmc_cplx* M0, const dqmc_cplx* Mx, const dqmc_cplx* My);
+int dqmc_get_custom_bond_bilinears(dqmc_ctx* ctx, int* count, dqmc_cplx* M0, dqmc_cplx* Mx, dqmc_cplx* My);
 /* G(0) of the last pair's field configuration, selected chain; *slice as for dqmc_get_green_timedisplaced_host.  DQMC_EINVAL without
  * td_particle_hole or if no pair was computed yet */
 int dqmc_get_green0_timedisplaced_host(dqmc_ctx* ctx, dqmc_cplx* g00, int* slice);
