@@ -635,6 +635,7 @@ extern "C" void dqmc_destroy(dqmc_ctx* c) {
     for (void* q : c->allocs) (void)hipFree(q);
     if (c->mats_out) (void)hipFree(c->mats_out);
     custom_free(c);
+    custom_pair_free(c);
     series_free(c);
     if (c->jacobi_graph) (void)hipGraphExecDestroy(c->jacobi_graph);
     if (c->sw.hflag) (void)hipHostFree(c->sw.hflag);

@@ -37,12 +37,13 @@ enum { FAM_BMULT = DQMC_FAM_BMULT, FAM_GEMM = DQMC_FAM_GEMM, FAM_JACOBI = DQMC_F
 // The measurement accumulator blocks of a context, one table (dqmc_ctx::acc): the per-slice observables, the four coarse time-displaced
 // channels, the four every-slice ones (channel ch at ACC_FINE0 + ch, as ACC_TD + ch for the coarse ones) and the equal-time correlators;
 // channel 4 of both families and ACC_EQ_BAND are the band-resolved charge blocks (DQMC_TD_PH_BAND, dqmc_set_equal_time_band), channel 5
-// and ACC_EQ_CUSTOM the blocks of the user-defined bilinears (dqmc_set_custom_bilinears)
-enum { TD_CHANNELS = 6 };
-enum { ACC_SLICE, ACC_TD, ACC_TD_PAIR, ACC_TD_PH, ACC_TD_CUR, ACC_TD_BAND, ACC_TD_CUSTOM, ACC_FINE0, ACC_EQ = ACC_FINE0 + TD_CHANNELS, ACC_EQ_BAND,
-       ACC_EQ_CUSTOM, ACC_COUNT };
+// and ACC_EQ_CUSTOM the blocks of the user-defined bilinears (dqmc_set_custom_bilinears), channel 6 and ACC_EQ_CUSTOM_PAIR those of the
+// user-defined pair operators (dqmc_set_custom_pair_operators)
+enum { TD_CHANNELS = 7 };
+enum { ACC_SLICE, ACC_TD, ACC_TD_PAIR, ACC_TD_PH, ACC_TD_CUR, ACC_TD_BAND, ACC_TD_CUSTOM, ACC_TD_CUSTOM_PAIR, ACC_FINE0,
+       ACC_EQ = ACC_FINE0 + TD_CHANNELS, ACC_EQ_BAND, ACC_EQ_CUSTOM, ACC_EQ_CUSTOM_PAIR, ACC_COUNT };
 // n: doubles per chain, 0 while the context has no such block; chain b starts at (char*)p + b * stride (the arena's chain stride; the
-// equal-time blocks and every block of the user-defined bilinears live outside the arena as [chain][n]); missing: what a read of an absent
+// equal-time blocks and every block of the user-defined bilinears and pair operators live outside the arena as [chain][n]); missing: what a read of an absent
 // block reports
 struct AccBlock { double* p; size_t n, stride; const char* missing; };
 
@@ -87,12 +88,15 @@ struct dqmc_ctx {
         {nullptr, 0, 0, "context created without dqmc_params::td_particle_hole = 2"},
         {nullptr, 0, 0, "context created without DQMC_TD_PH_BAND"},
         {nullptr, 0, 0, "no user-defined bilinear is set (dqmc_set_custom_bilinears), or the context was created without dqmc_params::td_particle_hole"},
+        {nullptr, 0, 0, "no user-defined pair operator is set (dqmc_set_custom_pair_operators), or the context was created without dqmc_params::timedisplaced"},
+        {nullptr, 0, 0, "no every-slice block for this channel"},
         {nullptr, 0, 0, "no every-slice block for this channel"}, {nullptr, 0, 0, "no every-slice block for this channel"},
         {nullptr, 0, 0, "no every-slice block for this channel"}, {nullptr, 0, 0, "no every-slice block for this channel"},
         {nullptr, 0, 0, "no every-slice block for this channel"}, {nullptr, 0, 0, "no every-slice block for this channel"},
         {nullptr, 0, 0, "the equal-time correlators have never been enabled (dqmc_set_equal_time_correlators)"},
         {nullptr, 0, 0, "the equal-time band correlators have never been enabled (dqmc_set_equal_time_band)"},
-        {nullptr, 0, 0, "no user-defined bilinear is set (dqmc_set_custom_bilinears)"}};
+        {nullptr, 0, 0, "no user-defined bilinear is set (dqmc_set_custom_bilinears)"},
+        {nullptr, 0, 0, "no user-defined pair operator is set (dqmc_set_custom_pair_operators)"}};
     // time-displaced Green's functions (dqmc_params::timedisplaced reserves them; dqmc_set_timedisplaced switches them on)
     bool td_reserved = false, td_on = false;
     int td_slice = -1;                                        // tau slice of the last pair GT0 / G0T (all chains), -1: none yet
@@ -131,8 +135,18 @@ struct dqmc_ctx {
     cplx cst_Mx[DQMC_CUSTOM_MAX * 16] = {}, cst_My[DQMC_CUSTOM_MAX * 16] = {};
     bool cst_bond_on = false;
     CustomBond cst_bond = {};
+    // dqmc_set_custom_pair_operators: the operators (F0, Fx, Fy) [count][4][4] on the host (for the getter), Fa = F0 - F0^T with its
+    // non-zero masks (the on-site kernel's launch argument), and while an operator has a bond part (cpr_bond_on) the device table of the
+    // stencil kernel (CustomPair in dqmc_internal.h); the blocks ACC_TD_CUSTOM_PAIR [chain][(n-1)(1 + count N)], its every-slice twin
+    // and ACC_EQ_CUSTOM_PAIR [chain][1 + count N], outside the arena, allocated by the call and freed by the next one.  Independent of
+    // the user-defined bilinears above
+    int cpr_count = 0;
+    cplx cpr_F0[DQMC_CUSTOM_MAX * 16] = {}, cpr_Fx[DQMC_CUSTOM_MAX * 16] = {}, cpr_Fy[DQMC_CUSTOM_MAX * 16] = {}, cpr_Fa[DQMC_CUSTOM_MAX * 16] = {};
+    unsigned cpr_mask[DQMC_CUSTOM_MAX] = {};
+    bool eqp_on = false, cpr_bond_on = false;
+    CustomPair cpr_bond = {};
     // dqmc_series_*: the measurement series.  Device buffers outside the arena, allocated by dqmc_series_begin and freed by dqmc_series_end
-    // or with the context: sample [nb][S], open bin [nb][S], closed bins [max_bins][nb][S], the per-part flags [9][nb], the cos / sin table
+    // or with the context: sample [nb][S], open bin [nb][S], closed bins [max_bins][nb][S], the per-part flags [11][nb], the cos / sin table
     // (2 pi j / L [2 L]; with the order-parameter part, index 6 of off / len, also 2 pi j / m [2 m] behind it) and the result buffer
     // of the statistics calls (mean, err [nb][S] each, then value, err [nb][6] each).  The counters live on the host.
     // srctab [nb]: the source rows of dqmc_series_accumulate, filled from srchost before every launch; formed: the sample buffer holds
@@ -142,7 +156,7 @@ struct dqmc_ctx {
         int bin_size = 0, max_bins = 0, nfreq = 0, parts = 0, closed = 0, in_open = 0;
         int flags = 0;                                        // DQMC_SERIES_AUTO_REBIN | DQMC_SERIES_TRACK_VARIANCE (dqmc_series_configure)
         long long samples = 0, rebins = 0;                    // accumulates since begin / merges of neighbouring bins so far
-        size_t S = 0, off[11] = {}, len[11] = {};              // index = bit number; 5 is never used
+        size_t S = 0, off[13] = {}, len[13] = {};              // index = bit number; 5 is never used
         double *sample = nullptr, *openbin = nullptr, *bins = nullptr, *bad = nullptr, *trig = nullptr, *stat = nullptr;
         double *var = nullptr;                                // running mean w [nb][S], then m2 [nb][S]: allocated with TRACK_VARIANCE
         double *binning = nullptr;                            // result of dqmc_series_binning_host, err then tau [levels][nb][S] each,
@@ -275,4 +289,5 @@ DQMC_PRIVATE GemmArgs gemm_square(dqmc_ctx* c, const cplx* A, int opA, const cpl
 DQMC_PRIVATE void run_gemm(dqmc_ctx* c, const GemmArgs& g);
 DQMC_PRIVATE void bmult_dev(dqmc_ctx* c, int side, int inverse, int k2, int k1, cplx* A);
 DQMC_PRIVATE void series_free(dqmc_ctx* c);
+DQMC_PRIVATE void custom_pair_free(dqmc_ctx* c);            // dqmc_measure_api.hip: the blocks of dqmc_set_custom_pair_operators
 DQMC_PRIVATE void custom_free(dqmc_ctx* c);                 // dqmc_measure_api.hip: the blocks of dqmc_set_custom_bilinears

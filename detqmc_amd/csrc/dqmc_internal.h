@@ -264,7 +264,7 @@ size_t measure_td_doubles(int L, int n);
 // Matsubara transforms of the every-slice block `acc` of `channel` (count[m+1], then the rows): out[chain][component][nfreq][N] (re, im),
 // bad[chain] = 1 if a row of the chain was never measured; out and bad are plain device arrays (no chain stride).  false: the lattice
 // is too large for the kernel's LDS, nothing was launched.  out_chain_stride (doubles) != 0: chain b's results at out + b * stride.
-// Channel 5 (user-defined bilinears): custom_count components per row, and the block lives outside the arena, chain b at
+// Channels 5 and 6 (user-defined bilinears, pair operators): custom_count components per row, and the block lives outside the arena, chain b at
 // (char*)acc + b * custom_chain_bytes
 bool launch_td_matsubara(const Launch& lc, const DevModel& hm, const double* acc, int channel, int nfreq, int apbx, int apby,
                          double* out, double* bad, size_t out_chain_stride = 0, int custom_count = 0, size_t custom_chain_bytes = 0);
@@ -349,6 +349,16 @@ void launch_measure_td_custom(const Launch& lc, const DevModel& hm, int count, c
                               const cplx* ob, double* acc, size_t acs, int row, int rows, const CustomBond* bond = nullptr);
 void launch_measure_eq_custom(const Launch& lc, const DevModel& hm, int count, const cplx* M, const unsigned* mask, const cplx* M2, const unsigned* mask2,
                               const cplx* gs, cplx* ob, double* acc, const CustomBond* bond = nullptr);
+// user-defined pair operators (dqmc_set_custom_pair_operators): row `row` of `rows` of a block count[rows], then rows [count][N], from ONE
+// shifted matrix gs -- g~(tau,0) for the time-displaced blocks, g~ of the slice with (row, rows) = (0, 1) for the equal-time block.  Fa
+// [count][4][4] = F0 - F0^T with its non-zero masks (host memory, a kernel argument) serves the on-site kernel; with pair != nullptr the
+// stencil kernel runs instead, for every set operator.  Device table tab (measure_custom_pair_table_cplx complex, shared by the
+// chains): V[count][3 blocks 0, x, y][3 forms F, conj F, F^H][4][4], then the link signs u[2][N]; mk[count][3][2] the non-zero masks of
+// F and of F^H; parts[c] bit k: block k of operator c is non-zero.  acc lives outside the arena: chain b at acc + b * acs
+struct CustomPair { const cplx* tab; const unsigned* mk; unsigned parts[DQMC_CUSTOM_MAX]; };
+size_t measure_custom_pair_table_cplx(int count, int N);
+void launch_measure_custom_pair(const Launch& lc, const DevModel& hm, int count, const cplx* Fa, const unsigned* mask, const cplx* gs, double* acc,
+                                size_t acs, int row, int rows, const CustomPair* pair = nullptr);
 size_t measure_custom_row_doubles(int count, int N);
 size_t measure_td_custom_onebody_cplx(int count, int N);
 size_t measure_eq_custom_onebody_cplx(int count, int N);

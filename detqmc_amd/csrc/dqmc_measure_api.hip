@@ -81,6 +81,12 @@ extern "C" int dqmc_measure_slice(dqmc_ctx* c) {
         launch_measure_eq_custom(c->lc, c->hm, c->cst_count, c->cst_M, c->cst_mask, c->cst_M2, c->cst_mask2, c->T1, c->cst_eq_ob, c->acc[ACC_EQ_CUSTOM].p,
                                  c->cst_bond_on ? &c->cst_bond : nullptr);
     }
+    if (c->eqp_on) {                                        // the same contraction as the time-displaced rows, on the slice's own T1
+        ProfScope ps(c, FAM_OTHER, 1);
+        const AccBlock& a = c->acc[ACC_EQ_CUSTOM_PAIR];
+        launch_measure_custom_pair(c->lc, c->hm, c->cpr_count, c->cpr_Fa, c->cpr_mask, c->T1, a.p, a.stride / sizeof(double), 0, 1,
+                                   c->cpr_bond_on ? &c->cpr_bond : nullptr);
+    }
     return finish(c, "dqmc_measure_slice");
 }
 extern "C" size_t dqmc_measure_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_SLICE); }
@@ -311,6 +317,146 @@ extern "C" int dqmc_set_equal_time_custom(dqmc_ctx* c, int on) {
 }
 extern "C" size_t dqmc_measure_eq_custom_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_EQ_CUSTOM); }
 extern "C" int dqmc_measure_eq_custom_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_EQ_CUSTOM, out); }
+// user-defined pair operators (dqmc_hip.h): run-time state like the bilinears above and independent of them
+void custom_pair_free(dqmc_ctx* c) {
+    for (void* q : {(void*)c->acc[ACC_TD_CUSTOM_PAIR].p, (void*)c->acc[ACC_FINE0 + 6].p, (void*)c->acc[ACC_EQ_CUSTOM_PAIR].p, (void*)c->cpr_bond.tab,
+                    (void*)c->cpr_bond.mk})
+        if (q) (void)hipFree(q);
+    c->acc[ACC_TD_CUSTOM_PAIR].p = c->acc[ACC_FINE0 + 6].p = c->acc[ACC_EQ_CUSTOM_PAIR].p = nullptr;
+    c->acc[ACC_TD_CUSTOM_PAIR].n = c->acc[ACC_FINE0 + 6].n = c->acc[ACC_EQ_CUSTOM_PAIR].n = 0;
+    c->cpr_bond = CustomPair{};
+    c->cpr_bond_on = false;
+    c->cpr_count = 0;
+    c->eqp_on = false;
+}
+extern "C" int dqmc_set_custom_pair_operators(dqmc_ctx* c, int count, const dqmc_cplx* F0, const dqmc_cplx* Fx, const dqmc_cplx* Fy) {
+    const std::string who = "dqmc_set_custom_pair_operators";
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (c->hm.hubbard) return fail(DQMC_EINVAL, "the user-defined pair operators belong to the SDW model");
+    if (count < 0 || count > DQMC_CUSTOM_MAX) return fail(DQMC_EINVAL, who + ": count must be in 0 .. DQMC_CUSTOM_MAX");
+    if (count && !F0) return fail(DQMC_EINVAL, "null argument");
+    if (c->ser.open && (c->ser.parts & (DQMC_SERIES_MATS_CUSTOM_PAIR | DQMC_SERIES_EQ_CUSTOM_PAIR)))
+        return fail(DQMC_EINVAL, who + ": a measurement series with a part of the user-defined pair operators is open");
+    bool bonds = false;
+    for (int ch = 0; ch < count; ++ch) {
+        bool any = false;
+        for (int a = 0; a < 4; ++a)
+            for (int b = 0; b < 4; ++b) {
+                const dqmc_cplx v = F0[16 * ch + 4 * a + b], w = F0[16 * ch + 4 * b + a];
+                if (!std::isfinite(v.re) || !std::isfinite(v.im)) return fail(DQMC_EINVAL, who + ": an entry is not finite");
+                any = any || v.re != w.re || v.im != w.im;  // the antisymmetric part alone contributes
+            }
+        for (const dqmc_cplx* bm : {Fx, Fy})
+            for (int k = 0; bm && k < 16; ++k) {
+                const dqmc_cplx v = bm[16 * ch + k];
+                if (!std::isfinite(v.re) || !std::isfinite(v.im)) return fail(DQMC_EINVAL, who + ": an entry is not finite");
+                if (v.re == 0.0 && v.im == 0.0) continue;
+                if (c->p.weakZflux)
+                    return fail(DQMC_EINVAL, who + ": with weakZflux the two fermions of a bond pair carry flavour-dependent Peierls phases: a bond "
+                                "part has no gauge-covariant definition under the flux");
+                any = bonds = true;
+            }
+        if (!any) return fail(DQMC_EINVAL, who + ": an operator vanishes identically (F0 - F0^T = 0 and no bond part)");
+    }
+    (void)hipSetDevice(c->p.device);
+    // the new buffers first: a failed allocation leaves the context as it was
+    const size_t nb = (size_t)c->nb, row = measure_custom_row_doubles(count, c->N);
+    const size_t n_eq = count ? 1 + row : 0, n_td = count && c->td_reserved ? (size_t)(c->n - 1) * (1 + row) : 0;
+    const size_t n_fine = n_td && c->td_fine ? (size_t)(c->m + 1) * (1 + row) : 0;
+    // the device table of the stencil kernel: per operator and block 0, x, y the forms F, conj F, F^H, then the link signs
+    std::vector<cplx> tab(bonds ? measure_custom_pair_table_cplx(count, c->N) : 0);
+    std::vector<unsigned> mk(bonds ? (size_t)count * 6 : 0);
+    CustomPair pair{};
+    if (bonds) {
+        const dqmc_cplx zero{0.0, 0.0};
+        for (int ch = 0; ch < count; ++ch)
+            for (int k = 0; k < 3; ++k) {
+                const dqmc_cplx* src = k == 0 ? F0 : k == 1 ? Fx : Fy;
+                cplx* v = tab.data() + ((size_t)ch * 3 + k) * 48;
+                unsigned bits = 0, bits_h = 0;
+                for (int a = 0; a < 4; ++a)
+                    for (int b = 0; b < 4; ++b) {
+                        const dqmc_cplx f = src ? src[16 * ch + 4 * a + b] : zero, ft = src ? src[16 * ch + 4 * b + a] : zero;
+                        v[4 * a + b] = make_double2(f.re, f.im);
+                        v[16 + 4 * a + b] = make_double2(f.re, -f.im);
+                        v[32 + 4 * a + b] = make_double2(ft.re, -ft.im);
+                        if (f.re != 0.0 || f.im != 0.0) bits |= 1u << (4 * a + b);
+                        if (ft.re != 0.0 || ft.im != 0.0) bits_h |= 1u << (4 * a + b);
+                    }
+                mk[((size_t)ch * 3 + k) * 2] = bits; mk[((size_t)ch * 3 + k) * 2 + 1] = bits_h;
+                if (bits) pair.parts[ch] |= 1u << k;
+            }
+        cplx* lk = tab.data() + (size_t)count * 144;
+        for (int mu = 0; mu < 2; ++mu)
+            for (int site = 0; site < c->N; ++site) lk[(size_t)mu * c->N + site] = custom_link(c->p, mu, site);     // no flux here: +-1
+    }
+    double *eq = nullptr, *td = nullptr, *fine = nullptr;
+    cplx* dtab = nullptr;
+    unsigned* dmk = nullptr;
+    hipError_t e = hipSuccess;
+    if (n_eq) e = hipMalloc((void**)&eq, n_eq * nb * sizeof(double));
+    if (e == hipSuccess && n_td) e = hipMalloc((void**)&td, n_td * nb * sizeof(double));
+    if (e == hipSuccess && n_fine) e = hipMalloc((void**)&fine, n_fine * nb * sizeof(double));
+    if (e == hipSuccess && bonds) e = hipMalloc((void**)&dtab, tab.size() * sizeof(cplx));
+    if (e == hipSuccess && bonds) e = hipMalloc((void**)&dmk, mk.size() * sizeof(unsigned));
+    if (e == hipSuccess && n_eq) e = hipMemsetAsync(eq, 0, n_eq * nb * sizeof(double), c->st);
+    if (e == hipSuccess && n_td) e = hipMemsetAsync(td, 0, n_td * nb * sizeof(double), c->st);
+    if (e == hipSuccess && n_fine) e = hipMemsetAsync(fine, 0, n_fine * nb * sizeof(double), c->st);
+    if (e == hipSuccess && bonds) e = hipMemcpyAsync(dtab, tab.data(), tab.size() * sizeof(cplx), hipMemcpyHostToDevice, c->st);
+    if (e == hipSuccess && bonds) e = hipMemcpyAsync(dmk, mk.data(), mk.size() * sizeof(unsigned), hipMemcpyHostToDevice, c->st);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->st);  // also: nothing enqueued still uses the blocks released below
+    if (e != hipSuccess) {
+        for (void* q : {(void*)eq, (void*)td, (void*)fine, (void*)dtab, (void*)dmk}) if (q) (void)hipFree(q);
+        return fail(DQMC_EHIP, who + ": " + hipGetErrorString(e));
+    }
+    const bool eq_switch = c->eqp_on && count > 0;          // the switch outlives a replacement, not the removal
+    custom_pair_free(c);
+    c->eqp_on = eq_switch;
+    c->acc[ACC_EQ_CUSTOM_PAIR].p = eq; c->acc[ACC_EQ_CUSTOM_PAIR].n = n_eq; c->acc[ACC_EQ_CUSTOM_PAIR].stride = n_eq * sizeof(double);
+    c->acc[ACC_TD_CUSTOM_PAIR].p = td; c->acc[ACC_TD_CUSTOM_PAIR].n = n_td; c->acc[ACC_TD_CUSTOM_PAIR].stride = n_td * sizeof(double);
+    c->acc[ACC_FINE0 + 6].p = fine; c->acc[ACC_FINE0 + 6].n = n_fine; c->acc[ACC_FINE0 + 6].stride = n_fine * sizeof(double);
+    c->cpr_count = count;
+    pair.tab = dtab; pair.mk = dmk;
+    c->cpr_bond = pair;
+    c->cpr_bond_on = bonds;
+    for (int k = 0; k < 16 * DQMC_CUSTOM_MAX; ++k) {
+        const bool in = k < 16 * count;
+        c->cpr_F0[k] = in ? make_double2(F0[k].re, F0[k].im) : make_double2(0.0, 0.0);
+        c->cpr_Fx[k] = in && Fx ? make_double2(Fx[k].re, Fx[k].im) : make_double2(0.0, 0.0);
+        c->cpr_Fy[k] = in && Fy ? make_double2(Fy[k].re, Fy[k].im) : make_double2(0.0, 0.0);
+    }
+    for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) {
+        c->cpr_mask[ch] = 0;
+        for (int a = 0; a < 4; ++a)
+            for (int b = 0; b < 4; ++b) {
+                const cplx f = c->cpr_F0[16 * ch + 4 * a + b], ft = c->cpr_F0[16 * ch + 4 * b + a];
+                const cplx v = make_double2(f.x - ft.x, f.y - ft.y);
+                c->cpr_Fa[16 * ch + 4 * a + b] = v;
+                if (v.x != 0.0 || v.y != 0.0) c->cpr_mask[ch] |= 1u << (4 * a + b);
+            }
+    }
+    return DQMC_OK;
+}
+extern "C" int dqmc_get_custom_pair_operators(dqmc_ctx* c, int* count, dqmc_cplx* F0, dqmc_cplx* Fx, dqmc_cplx* Fy) {
+    if (!c || !count) return fail(DQMC_EINVAL, "null argument");
+    if (c->hm.hubbard) return fail(DQMC_EINVAL, "the user-defined pair operators belong to the SDW model");
+    *count = c->cpr_count;
+    for (int k = 0; k < 16 * c->cpr_count; ++k) {
+        if (F0) { F0[k].re = c->cpr_F0[k].x; F0[k].im = c->cpr_F0[k].y; }
+        if (Fx) { Fx[k].re = c->cpr_Fx[k].x; Fx[k].im = c->cpr_Fx[k].y; }
+        if (Fy) { Fy[k].re = c->cpr_Fy[k].x; Fy[k].im = c->cpr_Fy[k].y; }
+    }
+    return DQMC_OK;
+}
+extern "C" int dqmc_set_equal_time_custom_pair(dqmc_ctx* c, int on) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (c->hm.hubbard) return fail(DQMC_EINVAL, "the user-defined pair operators belong to the SDW model");
+    if (on && !c->cpr_count) return fail(DQMC_EINVAL, c->acc[ACC_EQ_CUSTOM_PAIR].missing);
+    c->eqp_on = on != 0;
+    return DQMC_OK;
+}
+extern "C" size_t dqmc_measure_eq_custom_pair_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_EQ_CUSTOM_PAIR); }
+extern "C" int dqmc_measure_eq_custom_pair_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_EQ_CUSTOM_PAIR, out); }
 
 // ---------------------------------------------------------------------------------------------
 // time-displaced Green's functions (dqmc_hip.h; computed inside green_from_udv while td_on)
@@ -334,7 +480,8 @@ extern "C" int dqmc_get_green_timedisplaced_host(dqmc_ctx* c, dqmc_cplx* g_t0, d
     return DQMC_OK;
 }
 // ---- the channel kernels: coarse boundaries and every time slice (DQMC_TD_EVERY_SLICE) ---------------------------------------------
-enum { CH_G = 1, CH_PAIR = 2, CH_PH = 4, CH_CUR = 8, CH_BAND = 16, CH_CUSTOM = 32, CH_TWO_BODY = CH_PH | CH_CUR | CH_BAND | CH_CUSTOM };     // bit ch of a channel mask
+enum { CH_G = 1, CH_PAIR = 2, CH_PH = 4, CH_CUR = 8, CH_BAND = 16, CH_CUSTOM = 32, CH_CUSTOM_PAIR = 64,
+       CH_TWO_BODY = CH_PH | CH_CUR | CH_BAND | CH_CUSTOM };     // bit ch of a channel mask; the pair channels need the shifted gt0 alone
 // One-body values of an equal-time matrix for the masked particle-hole / current / band kernels (t = 0: tau side, 1: 0 side): one shift of g,
 // then each masked table.  g == nullptr: T1 still holds the shifted matrix of the call before.
 static void td_onebody(dqmc_ctx* c, unsigned mask, const cplx* g, int t) {
@@ -375,6 +522,12 @@ static void td_row(dqmc_ctx* c, unsigned mask, int first, int row, int rows, con
         launch_measure_td_custom(c->lc, c->hm, c->cst_count, c->cst_M, c->cst_mask, c->T1, c->ph_H, c->cst_td_ob, a.p, a.stride / sizeof(double), row, rows,
                                  c->cst_bond_on ? &c->cst_bond : nullptr);
     }
+    if (mask & CH_CUSTOM_PAIR) {
+        ProfScope ps(c, FAM_OTHER, 1);
+        const AccBlock& a = c->acc[first + 6];
+        launch_measure_custom_pair(c->lc, c->hm, c->cpr_count, c->cpr_Fa, c->cpr_mask, c->T1, a.p, a.stride / sizeof(double), row, rows,
+                                   c->cpr_bond_on ? &c->cpr_bond : nullptr);
+    }
 }
 // what every entry that works at boundary j asks for; need_current_G: the entry also reads G, which must still be G(tau_j)
 static int td_boundary_ok(dqmc_ctx* c, int j, bool need_current_G) {
@@ -401,6 +554,7 @@ extern "C" int dqmc_measure_timedisplaced_ph(dqmc_ctx* c, int j) { return td_coa
 extern "C" int dqmc_measure_timedisplaced_current(dqmc_ctx* c, int j) { return td_coarse(c, 3, j, "dqmc_measure_timedisplaced_current"); }
 extern "C" int dqmc_measure_timedisplaced_band(dqmc_ctx* c, int j) { return td_coarse(c, 4, j, "dqmc_measure_timedisplaced_band"); }
 extern "C" int dqmc_measure_timedisplaced_custom(dqmc_ctx* c, int j) { return td_coarse(c, 5, j, "dqmc_measure_timedisplaced_custom"); }
+extern "C" int dqmc_measure_timedisplaced_custom_pair(dqmc_ctx* c, int j) { return td_coarse(c, 6, j, "dqmc_measure_timedisplaced_custom_pair"); }
 extern "C" size_t dqmc_measure_td_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_TD); }
 extern "C" int dqmc_measure_td_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_TD, out); }
 extern "C" size_t dqmc_measure_td_pair_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_TD_PAIR); }
@@ -413,6 +567,8 @@ extern "C" size_t dqmc_measure_td_band_accum_size(dqmc_ctx* c) { return acc_size
 extern "C" int dqmc_measure_td_band_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_TD_BAND, out); }
 extern "C" size_t dqmc_measure_td_custom_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_TD_CUSTOM); }
 extern "C" int dqmc_measure_td_custom_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_TD_CUSTOM, out); }
+extern "C" size_t dqmc_measure_td_custom_pair_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_TD_CUSTOM_PAIR); }
+extern "C" int dqmc_measure_td_custom_pair_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_TD_CUSTOM_PAIR, out); }
 extern "C" int dqmc_get_green0_timedisplaced_host(dqmc_ctx* c, dqmc_cplx* g00, int* slice) {
     if (!c || !g00 || !slice) return fail(DQMC_EINVAL, "null argument");
     if (!c->G00) return fail(DQMC_EINVAL, "context created without dqmc_params::td_particle_hole");
@@ -520,11 +676,11 @@ extern "C" int dqmc_measure_td_fine_read_host(dqmc_ctx* c, int channel, double* 
 }
 static bool ser_apbx(const dqmc_ctx* c) { return c->p.bc == DQMC_BC_APBC_X || c->p.bc == DQMC_BC_APBC_XY; }
 static bool ser_apby(const dqmc_ctx* c) { return c->p.bc == DQMC_BC_APBC_Y || c->p.bc == DQMC_BC_APBC_XY; }
-static int td_ncomp(const dqmc_ctx* c, int channel) { return channel == 5 ? c->cst_count : channel == 2 ? 3 : 2; }
-// the Matsubara launch of one every-slice block; channel 5 brings its component count and its own chain stride
+static int td_ncomp(const dqmc_ctx* c, int channel) { return channel == 6 ? c->cpr_count : channel == 5 ? c->cst_count : channel == 2 ? 3 : 2; }
+// the Matsubara launch of one every-slice block; channels 5 and 6 bring their component count and their own chain stride
 static bool mats_launch(dqmc_ctx* c, int ch, int nfreq, double* out, double* bad, size_t out_chain_stride) {
     const AccBlock& a = c->acc[ACC_FINE0 + ch];
-    return launch_td_matsubara(c->lc, c->hm, a.p, ch, nfreq, ser_apbx(c), ser_apby(c), out, bad, out_chain_stride, c->cst_count, a.stride);
+    return launch_td_matsubara(c->lc, c->hm, a.p, ch, nfreq, ser_apbx(c), ser_apby(c), out, bad, out_chain_stride, td_ncomp(c, ch), a.stride);
 }
 extern "C" size_t dqmc_measure_td_matsubara_size(dqmc_ctx* c, int channel, int nfreq) {
     if (!c || !td_fine_n(c, channel) || nfreq < 1 || nfreq > c->m) return 0;
@@ -564,13 +720,15 @@ extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nf
     if (!c) return fail(DQMC_EINVAL, "null ctx");
     if (c->hm.hubbard) return fail(DQMC_EINVAL, "the measurement series belongs to the SDW model");
     if (c->ser.open) return fail(DQMC_EINVAL, "a measurement series is already open (dqmc_series_end)");
-    if (parts <= 0 || (parts & ~0x7df)) return fail(DQMC_EINVAL, "dqmc_series_begin: parts must be a non-empty mask of bits 0 .. 4 and 6 .. 10");
+    if (parts <= 0 || (parts & ~0x1fdf)) return fail(DQMC_EINVAL, "dqmc_series_begin: parts must be a non-empty mask of bits 0 .. 4 and 6 .. 12");
     if (bin_size < 1) return fail(DQMC_EINVAL, "dqmc_series_begin: bin_size must be at least 1");
     if (max_bins < 2) return fail(DQMC_EINVAL, "dqmc_series_begin: max_bins must be at least 2");
     if ((parts & 1) && !c->acc[ACC_EQ].n) return fail(DQMC_EINVAL, "dqmc_series_begin: the equal-time block has never been enabled (dqmc_set_equal_time_correlators)");
     if ((parts & DQMC_SERIES_EQ_BAND) && !c->acc[ACC_EQ_BAND].n) return fail(DQMC_EINVAL, "dqmc_series_begin: the equal-time band block has never been enabled (dqmc_set_equal_time_band)");
     if ((parts & DQMC_SERIES_EQ_CUSTOM) && !c->acc[ACC_EQ_CUSTOM].n) return fail(DQMC_EINVAL, "dqmc_series_begin: no user-defined bilinear is set (dqmc_set_custom_bilinears)");
-    if ((parts & (1 | DQMC_SERIES_EQ_BAND | DQMC_SERIES_EQ_CUSTOM)) && series_eq_sample_lds_bytes(c->hm.L) > 152 * 1024)
+    if ((parts & (DQMC_SERIES_MATS_CUSTOM_PAIR | DQMC_SERIES_EQ_CUSTOM_PAIR)) && !c->cpr_count)
+        return fail(DQMC_EINVAL, "dqmc_series_begin: no user-defined pair operator is set (dqmc_set_custom_pair_operators): the part's block is missing");
+    if ((parts & (1 | DQMC_SERIES_EQ_BAND | DQMC_SERIES_EQ_CUSTOM | DQMC_SERIES_EQ_CUSTOM_PAIR)) && series_eq_sample_lds_bytes(c->hm.L) > 152 * 1024)
         return fail(DQMC_EINVAL, "dqmc_series_begin: the lattice is too large for the equal-time sample kernel's LDS");
     dqmc_ctx::Series s;
     const size_t N = (size_t)c->N;
@@ -602,8 +760,15 @@ extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nf
         s.off[9] = s.S; s.len[9] = (size_t)c->cst_count * nfreq * N * 2; s.S += s.len[9];
     }
     if (parts & DQMC_SERIES_EQ_CUSTOM) { s.off[10] = s.S; s.len[10] = (size_t)2 * c->cst_count * N; s.S += s.len[10]; }
+    if (parts & DQMC_SERIES_MATS_CUSTOM_PAIR) {             // the parts of the user-defined pair operators: behind everything else again
+        if (!c->td_fine || !td_fine_n(c, 6)) return fail(DQMC_EINVAL, "dqmc_series_begin: no every-slice block for a channel of the mask");
+        if (nfreq < 1 || nfreq > c->m) return fail(DQMC_EINVAL, "dqmc_series_begin: nfreq must be in 1..m");
+        if (!td_matsubara_fits(c->hm, 6, nfreq)) return fail(DQMC_EINVAL, "dqmc_series_begin: the lattice is too large for the Matsubara kernel's LDS");
+        s.off[11] = s.S; s.len[11] = (size_t)c->cpr_count * nfreq * N * 2; s.S += s.len[11];
+    }
+    if (parts & DQMC_SERIES_EQ_CUSTOM_PAIR) { s.off[12] = s.S; s.len[12] = (size_t)2 * c->cpr_count * N; s.S += s.len[12]; }
     s.bin_size = bin_size; s.max_bins = max_bins; s.parts = parts;
-    s.nfreq = (parts & (0x1e | DQMC_SERIES_PHI | DQMC_SERIES_MATS_BAND | DQMC_SERIES_MATS_CUSTOM)) ? nfreq : 0;
+    s.nfreq = (parts & (0x1e | DQMC_SERIES_PHI | DQMC_SERIES_MATS_BAND | DQMC_SERIES_MATS_CUSTOM | DQMC_SERIES_MATS_CUSTOM_PAIR)) ? nfreq : 0;
     (void)hipSetDevice(c->p.device);
     const size_t n = (size_t)c->nb * s.S, L = (size_t)c->hm.L;
     c->ser = s;                                             // from here on series_free releases what was allocated
@@ -612,7 +777,7 @@ extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nf
     if (e == hipSuccess) e = hipMalloc((void**)&r.sample, n * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&r.openbin, n * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&r.bins, (size_t)max_bins * n * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&r.bad, (size_t)9 * c->nb * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&r.bad, (size_t)11 * c->nb * sizeof(double));
     const size_t mt = (parts & DQMC_SERIES_PHI) ? (size_t)c->m : 0;     // the temporal table of the order-parameter part
     if (e == hipSuccess) e = hipMalloc((void**)&r.trig, 2 * (L + mt) * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&r.stat, (2 * n + (size_t)12 * c->nb) * sizeof(double));
@@ -620,7 +785,7 @@ extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nf
     if (e == hipSuccess) e = hipMemsetAsync(r.sample, 0, n * sizeof(double), c->st);
     if (e == hipSuccess) e = hipMemsetAsync(r.openbin, 0, n * sizeof(double), c->st);
     if (e == hipSuccess) e = hipMemsetAsync(r.bins, 0, (size_t)max_bins * n * sizeof(double), c->st);
-    if (e == hipSuccess) e = hipMemsetAsync(r.bad, 0, (size_t)9 * c->nb * sizeof(double), c->st);
+    if (e == hipSuccess) e = hipMemsetAsync(r.bad, 0, (size_t)11 * c->nb * sizeof(double), c->st);
     if (e == hipSuccess) {
         // cos / sin(2 pi j / L) as finishFermionic of the host layer forms them: the device's structure factors use the same values
         std::vector<double> trig(2 * (L + mt));
@@ -643,7 +808,7 @@ extern "C" int dqmc_series_end(dqmc_ctx* c) {
 extern "C" int dqmc_series_layout(dqmc_ctx* c, int part, size_t* offset, size_t* length) {
     if (!c || !offset || !length) return fail(DQMC_EINVAL, "null argument");
     if (!c->ser.open) return fail(DQMC_EINVAL, "no measurement series is open");
-    if (part < 0 || part > 10 || !(c->ser.parts & (1 << part))) return fail(DQMC_EINVAL, "dqmc_series_layout: the part is not in the series");
+    if (part < 0 || part > 12 || !(c->ser.parts & (1 << part))) return fail(DQMC_EINVAL, "dqmc_series_layout: the part is not in the series");
     *offset = c->ser.off[part]; *length = c->ser.len[part];
     return DQMC_OK;
 }
@@ -700,6 +865,17 @@ static int series_form_sample(dqmc_ctx* c, const char* entry) {
         if (s.parts & DQMC_SERIES_EQ_CUSTOM) {
             if (!launch_series_eq_sample(c->lc, c->hm, c->acc[ACC_EQ_CUSTOM].p, c->acc[ACC_EQ_CUSTOM].n, c->cst_count, s.trig, s.sample, s.S, s.off[10],
                                          s.bad + (size_t)nparts * c->nb))
+                return fail(DQMC_EINVAL, who + ": the lattice is too large for the equal-time sample kernel's LDS");
+            ++nparts;
+        }
+        if (s.parts & DQMC_SERIES_MATS_CUSTOM_PAIR) {
+            if (!mats_launch(c, 6, s.nfreq, s.sample + s.off[11], s.bad + (size_t)nparts * c->nb, s.S))
+                return fail(DQMC_EINVAL, who + ": the lattice is too large for the Matsubara kernel's LDS");
+            ++nparts;
+        }
+        if (s.parts & DQMC_SERIES_EQ_CUSTOM_PAIR) {
+            const AccBlock& a = c->acc[ACC_EQ_CUSTOM_PAIR];
+            if (!launch_series_eq_sample(c->lc, c->hm, a.p, a.n, c->cpr_count, s.trig, s.sample, s.S, s.off[12], s.bad + (size_t)nparts * c->nb))
                 return fail(DQMC_EINVAL, who + ": the lattice is too large for the equal-time sample kernel's LDS");
             ++nparts;
         }
@@ -858,21 +1034,30 @@ extern "C" int dqmc_series_band_derived_host(dqmc_ctx* c, double* value, double*
     HIPCHK(copy_sync(c, err, dv + nd, nd * sizeof(double), hipMemcpyDeviceToHost));
     return DQMC_OK;
 }
-extern "C" int dqmc_series_custom_derived_host(dqmc_ctx* c, int qx, int qy, double* value, double* err) {
+// R of every operator of an equal-time part [count][N] C(d), [count][N] S(q) at series part `bit`: the user-defined bilinears and pair operators
+static int series_ratio_derived(dqmc_ctx* c, int part, int bit, int count, int qx, int qy, double* value, double* err, const std::string& who,
+                                const char* what) {
     if (!c || !value || !err) return fail(DQMC_EINVAL, "null argument");
     const dqmc_ctx::Series& s = c->ser;
     if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
-    if (!(s.parts & DQMC_SERIES_EQ_CUSTOM)) return fail(DQMC_EINVAL, "dqmc_series_custom_derived_host: the series has no equal-time part of the user-defined bilinears");
-    if (qx < 0 || qx >= c->hm.L || qy < 0 || qy >= c->hm.L) return fail(DQMC_EINVAL, "dqmc_series_custom_derived_host: qx and qy must be in 0 .. L-1");
-    if (s.closed < 2) return fail(DQMC_EINVAL, "dqmc_series_custom_derived_host: the jackknife needs at least two closed bins");
+    if (!(s.parts & part)) return fail(DQMC_EINVAL, who + ": the series has no equal-time part of the user-defined " + what);
+    if (qx < 0 || qx >= c->hm.L || qy < 0 || qy >= c->hm.L) return fail(DQMC_EINVAL, who + ": qx and qy must be in 0 .. L-1");
+    if (s.closed < 2) return fail(DQMC_EINVAL, who + ": the jackknife needs at least two closed bins");
     (void)hipSetDevice(c->p.device);
-    const size_t n = (size_t)c->nb * s.S, nd = (size_t)c->cst_count * c->nb;
+    const size_t n = (size_t)c->nb * s.S, nd = (size_t)count * c->nb;
     double* dv = s.stat + 2 * n;                            // the result rows of dqmc_series_derived_host: the calls are synchronous
-    { ProfScope ps(c, FAM_OTHER, 1); launch_series_custom_derived(c->lc, c->hm, s.bins, s.S, s.closed, s.off[10], c->cst_count, qx, qy, dv, dv + nd); }
-    { const int rc = finish(c, "dqmc_series_custom_derived_host"); if (rc != DQMC_OK) return rc; }
+    { ProfScope ps(c, FAM_OTHER, 1); launch_series_custom_derived(c->lc, c->hm, s.bins, s.S, s.closed, s.off[bit], count, qx, qy, dv, dv + nd); }
+    { const int rc = finish(c, who.c_str()); if (rc != DQMC_OK) return rc; }
     HIPCHK(copy_sync(c, value, dv, nd * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHK(copy_sync(c, err, dv + nd, nd * sizeof(double), hipMemcpyDeviceToHost));
     return DQMC_OK;
+}
+extern "C" int dqmc_series_custom_derived_host(dqmc_ctx* c, int qx, int qy, double* value, double* err) {
+    return series_ratio_derived(c, DQMC_SERIES_EQ_CUSTOM, 10, c ? c->cst_count : 0, qx, qy, value, err, "dqmc_series_custom_derived_host", "bilinears");
+}
+extern "C" int dqmc_series_custom_pair_derived_host(dqmc_ctx* c, int qx, int qy, double* value, double* err) {
+    return series_ratio_derived(c, DQMC_SERIES_EQ_CUSTOM_PAIR, 12, c ? c->cpr_count : 0, qx, qy, value, err, "dqmc_series_custom_pair_derived_host",
+                                "pair operators");
 }
 extern "C" int dqmc_series_phi_derived_host(dqmc_ctx* c, double* value, double* err) {
     if (!c || !value || !err) return fail(DQMC_EINVAL, "null argument");

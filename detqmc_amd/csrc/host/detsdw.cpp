@@ -279,6 +279,7 @@ void DetSDW::measureTimeDisplaced(Group& g, int j) {
     if (ph_level(ch_[0].pars) == 2) check(dqmc_measure_timedisplaced_current(g.ctx, j), "measureTimeDisplacedCurrent");
     if (td_band(ch_[0].pars)) check(dqmc_measure_timedisplaced_band(g.ctx, j), "measureTimeDisplacedBand");
     if (customTd()) check(dqmc_measure_timedisplaced_custom(g.ctx, j), "measureTimeDisplacedCustom");
+    if (customPairTd()) check(dqmc_measure_timedisplaced_custom_pair(g.ctx, j), "measureTimeDisplacedCustomPair");
     // every slice of the boundary's segment, in the boundary's own field configuration
     if (td_every_slice(ch_[0].pars)) check(dqmc_measure_timedisplaced_segment(g.ctx, j), "measureTimeDisplacedSegment");
 }
@@ -366,10 +367,13 @@ void DetSDW::sweep(bool takeMeasurements) {
     const bool eqc = fermionic && customEq();
     if (eqb) for (auto& g : groups_) check(dqmc_set_equal_time_band(g.ctx, 1), "dqmc_set_equal_time_band");
     if (eqc) for (auto& g : groups_) check(dqmc_set_equal_time_custom(g.ctx, 1), "dqmc_set_equal_time_custom");
-    auto off = [this, eq, eqb, eqc]() {
+    const bool eqp = fermionic && customPairEq();
+    if (eqp) for (auto& g : groups_) check(dqmc_set_equal_time_custom_pair(g.ctx, 1), "dqmc_set_equal_time_custom_pair");
+    auto off = [this, eq, eqb, eqc, eqp]() {
         if (eq) for (auto& g : groups_) (void)dqmc_set_equal_time_correlators(g.ctx, 0);
         if (eqb) for (auto& g : groups_) (void)dqmc_set_equal_time_band(g.ctx, 0);
         if (eqc) for (auto& g : groups_) (void)dqmc_set_equal_time_custom(g.ctx, 0);
+        if (eqp) for (auto& g : groups_) (void)dqmc_set_equal_time_custom_pair(g.ctx, 0);
         measuring_ = false;
         if (measuringTD_) for (auto& g : groups_) (void)dqmc_set_timedisplaced(g.ctx, 0);
         measuringTD_ = false;
@@ -508,6 +512,12 @@ void DetSDW::finishFermionic(int b) {
             if ((int)eqc[0] != m) throw GeneralError(DQMC_EINVAL, "measurement sweep did not visit every time slice (equal-time custom bilinears)");
             for (int ch = 0; ch < customCount(); ++ch) form(&eqc[1 + (size_t)ch * N], eqc[0], c.customCorr[ch], c.customSq[ch]);
         }
+        if (customPairEq()) {                                    // the user-defined pair operators, from theirs
+            std::vector<double> eqp(dqmc_measure_eq_custom_pair_accum_size(ctx_));
+            check(dqmc_measure_eq_custom_pair_read_host(ctx_, eqp.data()), "dqmc_measure_eq_custom_pair_read_host");
+            if ((int)eqp[0] != m) throw GeneralError(DQMC_EINVAL, "measurement sweep did not visit every time slice (equal-time custom pair operators)");
+            for (int ch = 0; ch < pairCount(); ++ch) form(&eqp[1 + (size_t)ch * N], eqp[0], c.customPairCorr[ch], c.customPairSq[ch]);
+        }
     }
     // Time-displaced observables from one family of blocks: the coarse one (rows = interior boundaries j = 1 .. n-1) or, with
     // timeDisplacedEverySlice, also the fine one (rows = slices k = 0 .. m).  Same arithmetic for both.
@@ -517,12 +527,13 @@ void DetSDW::finishFermionic(int b) {
                                    : "measurement sweep did not visit every stabilisation boundary";
         // the coarse blocks' (size, read) entry points by channel; the fine blocks share one pair that takes the channel
         struct Coarse { size_t (*size)(dqmc_ctx*); int (*read)(dqmc_ctx*, double*); const char* name; };
-        static const Coarse coarse[6] = {{dqmc_measure_td_accum_size, dqmc_measure_td_read_host, "dqmc_measure_td_read_host"},
+        static const Coarse coarse[7] = {{dqmc_measure_td_accum_size, dqmc_measure_td_read_host, "dqmc_measure_td_read_host"},
                                          {dqmc_measure_td_pair_accum_size, dqmc_measure_td_pair_read_host, "dqmc_measure_td_pair_read_host"},
                                          {dqmc_measure_td_ph_accum_size, dqmc_measure_td_ph_read_host, "dqmc_measure_td_ph_read_host"},
                                          {dqmc_measure_td_current_accum_size, dqmc_measure_td_current_read_host, "dqmc_measure_td_current_read_host"},
                                          {dqmc_measure_td_band_accum_size, dqmc_measure_td_band_read_host, "dqmc_measure_td_band_read_host"},
-                                         {dqmc_measure_td_custom_accum_size, dqmc_measure_td_custom_read_host, "dqmc_measure_td_custom_read_host"}};
+                                         {dqmc_measure_td_custom_accum_size, dqmc_measure_td_custom_read_host, "dqmc_measure_td_custom_read_host"},
+                                         {dqmc_measure_td_custom_pair_accum_size, dqmc_measure_td_custom_pair_read_host, "dqmc_measure_td_custom_pair_read_host"}};
         auto read = [&](int channel, std::vector<double>& buf) {
             buf.resize(fine ? dqmc_measure_td_fine_accum_size(ctx_, channel) : coarse[channel].size(ctx_));
             if (fine) check(dqmc_measure_td_fine_read_host(ctx_, channel, buf.data()), "dqmc_measure_td_fine_read_host");
@@ -645,12 +656,11 @@ void DetSDW::finishFermionic(int b) {
                 }
             }
         }
-        // user-defined bilinears: the same normalisation, `count` rows of N per tau
-        if (customTd()) {
-            const int nc = customCount();
+        // user-defined bilinears (channel 5) and pair operators (channel 6): the same normalisation, `count` rows of N per tau
+        auto fillCustom = [&](int channel, int nc, std::vector<double>* tau, std::vector<double>* tauQ0) {
             std::vector<double> tb;
-            read(5, tb);
-            for (int ch = 0; ch < nc; ++ch) { t.customTau[ch].assign((size_t)rows * N, 0.0); t.customTauQ0[ch].assign(rows, 0.0); }
+            read(channel, tb);
+            for (int ch = 0; ch < nc; ++ch) { tau[ch].assign((size_t)rows * N, 0.0); tauQ0[ch].assign(rows, 0.0); }
             for (int r = 0; r < rows; ++r) {
                 const double cnt = tb[r];
                 if (cnt < 1.0) throw GeneralError(DQMC_EINVAL, missing);
@@ -659,13 +669,15 @@ void DetSDW::finishFermionic(int b) {
                     double q = 0.0;
                     for (int d = 0; d < N; ++d) {
                         const double v = T[d] / (double(N) * cnt);
-                        t.customTau[ch][(size_t)r * N + d] = v;
+                        tau[ch][(size_t)r * N + d] = v;
                         q += v;
                     }
-                    t.customTauQ0[ch][r] = q;
+                    tauQ0[ch][r] = q;
                 }
             }
-        }
+        };
+        if (customTd()) fillCustom(5, customCount(), t.customTau, t.customTauQ0);
+        if (customPairTd()) fillCustom(6, pairCount(), t.customPairTau, t.customPairTauQ0);
     };
     if (td_level(c.pars)) fill(false, c.td);
     // timeDisplacedFineOnDevice: the fine blocks stay on the device, their reader is getMatsubara
@@ -688,7 +700,8 @@ void DetSDW::getObservableVector(int which_in, double* out, int b) const {
     const int which = which_in & ~DETSDW_OBS_FINE;
     const bool bandTau = which >= DETSDW_OBS_BANDDIFFTAU && which <= DETSDW_OBS_BANDMIXTAU_Q0;
     const bool customTau = which >= DETSDW_OBS_CUSTOMTAU && which < DETSDW_OBS_CUSTOMCORR;
-    if (fine && (which < DETSDW_OBS_GREENKTAU_X || which > DETSDW_OBS_BONDKINETICY) && !bandTau && !customTau) throw ParameterWrong("unknown observable vector");
+    const bool pairTau = which >= DETSDW_OBS_CUSTOMPAIRTAU && which < DETSDW_OBS_CUSTOMPAIRCORR;
+    if (fine && (which < DETSDW_OBS_GREENKTAU_X || which > DETSDW_OBS_BONDKINETICY) && !bandTau && !customTau && !pairTau) throw ParameterWrong("unknown observable vector");
     if (fine && !td_every_slice(c.pars)) throw ParameterWrong("the ...Fine observables need timeDisplacedEverySlice");
     if (fine && td_fine_on_device(c.pars))
         throw ParameterWrong("the ...Fine observables are not formed with timeDisplacedFineOnDevice: read the Matsubara transforms");
@@ -720,6 +733,19 @@ void DetSDW::getObservableVector(int which_in, double* out, int b) const {
         const std::vector<double>& e = which < DETSDW_OBS_CUSTOMTAU_Q0 ? t.customTau[ch] : which < DETSDW_OBS_CUSTOMCORR ? t.customTauQ0[ch]
                                      : which < DETSDW_OBS_CUSTOMSQ ? c.customCorr[ch] : c.customSq[ch];
         if (e.empty()) throw GeneralError(DQMC_EINVAL, "no measurement sweep has run since the user-defined bilinears were set");
+        std::memcpy(out, e.data(), e.size() * sizeof(double));
+        return;
+    }
+    if (which >= DETSDW_OBS_CUSTOMPAIRTAU && which < DETSDW_OBS_CUSTOMPAIRSQ + DQMC_CUSTOM_MAX) {
+        const int ch = (which - DETSDW_OBS_CUSTOMPAIRTAU) % DQMC_CUSTOM_MAX;
+        if (ch >= pairCount()) throw ParameterWrong("no user-defined pair operator with this index is set (detsdw_set_custom_pair_operators)");
+        if (pairTau ? !customPairTd() : !customPairEq())
+            throw ParameterWrong(pairTau ? "customPair{c}Tau needs timeDisplacedMeasurements" : "customPair{c}Corr / customPair{c}Sq need equalTimeCorrelators");
+        if (!pairTau && seriesNoHostCopy())
+            throw ParameterWrong("the equal-time correlators are not copied to the host while a series with DETSDW_SERIES_NO_HOST_COPY is open: read the series");
+        const std::vector<double>& e = which < DETSDW_OBS_CUSTOMPAIRTAU_Q0 ? t.customPairTau[ch] : which < DETSDW_OBS_CUSTOMPAIRCORR ? t.customPairTauQ0[ch]
+                                     : which < DETSDW_OBS_CUSTOMPAIRSQ ? c.customPairCorr[ch] : c.customPairSq[ch];
+        if (e.empty()) throw GeneralError(DQMC_EINVAL, "no measurement sweep has run since the user-defined pair operators were set");
         std::memcpy(out, e.data(), e.size() * sizeof(double));
         return;
     }
@@ -755,7 +781,7 @@ void DetSDW::getObservableVector(int which_in, double* out, int b) const {
 // observables of all chains cost four calls per context.
 void DetSDW::invalidateMatsubara() {
     tdBlocksValid_ = false;
-    for (auto& g : groups_) for (int ch = 0; ch < 6; ++ch) g.matsNfreq[ch] = 0;
+    for (auto& g : groups_) for (int ch = 0; ch < 7; ++ch) g.matsNfreq[ch] = 0;
 }
 const double* DetSDW::matsubara(Group& g, int which, int nfreq, int& ncomp, int& comp) {
     const detsdw_params& p = ch_[0].pars;
@@ -766,8 +792,11 @@ const double* DetSDW::matsubara(Group& g, int which, int nfreq, int& ncomp, int&
     else if (which == DETSDW_OBS_CURRENTXTAU || which == DETSDW_OBS_CURRENTYTAU) { channel = 3; comp = which - DETSDW_OBS_CURRENTXTAU; }
     else if (which == DETSDW_OBS_BANDDIFFTAU || which == DETSDW_OBS_BANDMIXTAU) { channel = 4; comp = which - DETSDW_OBS_BANDDIFFTAU; }
     else if (which >= DETSDW_OBS_CUSTOMTAU && which < DETSDW_OBS_CUSTOMTAU_Q0) { channel = 5; comp = which - DETSDW_OBS_CUSTOMTAU; }
+    else if (which >= DETSDW_OBS_CUSTOMPAIRTAU && which < DETSDW_OBS_CUSTOMPAIRTAU_Q0) { channel = 6; comp = which - DETSDW_OBS_CUSTOMPAIRTAU; }
     else throw ParameterWrong("no Matsubara transform of this observable");
-    ncomp = channel == 5 ? customCount() : channel == 2 ? 3 : 2;
+    ncomp = channel == 6 ? pairCount() : channel == 5 ? customCount() : channel == 2 ? 3 : 2;
+    if (channel == 6 && (!customPairTd() || comp >= pairCount()))
+        throw ParameterWrong("customPair{c}Tau needs an operator set by detsdw_set_custom_pair_operators and timeDisplacedMeasurements");
     if (channel == 5 && (!customTd() || comp >= customCount()))
         throw ParameterWrong("custom{c}Tau needs a matrix set by detsdw_set_custom_bilinears and timeDisplacedParticleHole");
     if (!td_every_slice(p)) throw ParameterWrong("the Matsubara transforms need timeDisplacedEverySlice");
@@ -821,8 +850,10 @@ void DetSDW::seriesBegin(int binSize, int maxBins, int nfreq, int flags) {
         if (ph_level(p) == 2) parts |= DQMC_SERIES_MATS_CURRENT;
         if (td_band(p)) parts |= DQMC_SERIES_MATS_BAND;
         if (customTd()) parts |= DQMC_SERIES_MATS_CUSTOM;
+        if (customPairTd()) parts |= DQMC_SERIES_MATS_CUSTOM_PAIR;
     }
     if (blocks && customEq()) parts |= DQMC_SERIES_EQ_CUSTOM;
+    if (blocks && customPairEq()) parts |= DQMC_SERIES_EQ_CUSTOM_PAIR;
     if (!parts) throw ParameterWrong("a measurement series needs equalTimeCorrelators or timeDisplacedEverySlice");
     size_t opened = 0;
     try {
@@ -843,7 +874,7 @@ void DetSDW::seriesBegin(int binSize, int maxBins, int nfreq, int flags) {
         for (size_t i = 0; i < opened; ++i) (void)dqmc_series_end(groups_[i].ctx);
         throw;
     }
-    series_.open = true; series_.binSize = binSize; series_.maxBins = maxBins; series_.nfreq = (parts & ~(DQMC_SERIES_EQ | DQMC_SERIES_EQ_BAND | DQMC_SERIES_EQ_CUSTOM)) ? nfreq : 0;   // the phi part keeps nfreq too
+    series_.open = true; series_.binSize = binSize; series_.maxBins = maxBins; series_.nfreq = (parts & ~(DQMC_SERIES_EQ | DQMC_SERIES_EQ_BAND | DQMC_SERIES_EQ_CUSTOM | DQMC_SERIES_EQ_CUSTOM_PAIR)) ? nfreq : 0;   // the phi part keeps nfreq too
     series_.parts = parts; series_.flags = flags;
     seriesRoute_.resize(ch_.size());
     std::iota(seriesRoute_.begin(), seriesRoute_.end(), 0);
@@ -897,6 +928,16 @@ void DetSDW::seriesSlice(int which, int& part, size_t& offset, size_t& length) {
         if (!(series_.parts & DQMC_SERIES_MATS_CUSTOM) || ch >= customCount())
             throw ParameterWrong("the series holds no Matsubara part of this user-defined bilinear");
         part = 9; length = (size_t)series_.nfreq * N_ * 2; sub = (size_t)ch * length;
+    } else if (which >= DETSDW_OBS_CUSTOMPAIRCORR && which < DETSDW_OBS_CUSTOMPAIRSQ + DQMC_CUSTOM_MAX) {
+        const int ch = (which - DETSDW_OBS_CUSTOMPAIRCORR) % DQMC_CUSTOM_MAX;
+        if (!(series_.parts & DQMC_SERIES_EQ_CUSTOM_PAIR) || ch >= pairCount())
+            throw ParameterWrong("the series holds no equal-time part of this user-defined pair operator");
+        part = 12; length = (size_t)N_; sub = (size_t)((which >= DETSDW_OBS_CUSTOMPAIRSQ ? pairCount() : 0) + ch) * N_;
+    } else if (which >= DETSDW_OBS_CUSTOMPAIRTAU && which < DETSDW_OBS_CUSTOMPAIRTAU_Q0) {
+        const int ch = which - DETSDW_OBS_CUSTOMPAIRTAU;
+        if (!(series_.parts & DQMC_SERIES_MATS_CUSTOM_PAIR) || ch >= pairCount())
+            throw ParameterWrong("the series holds no Matsubara part of this user-defined pair operator");
+        part = 11; length = (size_t)series_.nfreq * N_ * 2; sub = (size_t)ch * length;
     } else if (which == DETSDW_OBS_PHICHI || which == DETSDW_OBS_PHISCALARS) {
         if (!(series_.parts & DQMC_SERIES_PHI)) throw ParameterWrong("the series has no order-parameter part: detsdw_series_begin with DETSDW_SERIES_PHI");
         part = 6;
@@ -997,6 +1038,63 @@ void DetSDW::seriesCustomDerived(int c, int qx, int qy, double* value, double* e
         check(dqmc_series_custom_derived_host(g.ctx, qx, qy, v.data(), e.data()), "dqmc_series_custom_derived_host");
         for (int b = 0; b < g.count; ++b) { value[g.first + b] = v[(size_t)b * nc + c]; err[g.first + b] = e[(size_t)b * nc + c]; }
     }
+}
+// R of user-defined pair operator c at Q = (qx, qy) for every chain in handle order
+void DetSDW::seriesCustomPairDerived(int c, int qx, int qy, double* value, double* err) {
+    if (!series_.open) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
+    if (!(series_.parts & DQMC_SERIES_EQ_CUSTOM_PAIR))
+        throw ParameterWrong("R_customPair needs operators set by detsdw_set_custom_pair_operators before the series began, and equalTimeCorrelators");
+    const int nc = pairCount();
+    if (c < 0 || c >= nc) throw ParameterWrong("no user-defined pair operator with this index is set");
+    std::vector<double> v, e;
+    for (auto& g : groups_) {
+        v.resize((size_t)g.count * nc); e.resize((size_t)g.count * nc);
+        check(dqmc_series_custom_pair_derived_host(g.ctx, qx, qy, v.data(), e.data()), "dqmc_series_custom_pair_derived_host");
+        for (int b = 0; b < g.count; ++b) { value[g.first + b] = v[(size_t)b * nc + c]; err[g.first + b] = e[(size_t)b * nc + c]; }
+    }
+}
+bool DetSDW::customPairTd() const { return pairCount() && td_level(ch_[0].pars); }
+bool DetSDW::customPairEq() const { return pairCount() && eq_correlators(ch_[0].pars); }
+void DetSDW::getCustomPairOperators(int* count, dqmc_cplx* F0, dqmc_cplx* Fx, dqmc_cplx* Fy) const {
+    if (!count) throw ParameterWrong("detsdw_get_custom_pair_operators: null argument");
+    *count = pairCount();
+    for (size_t k = 0; k < (size_t)16 * pairCount(); ++k) {
+        if (F0) F0[k] = pairF_[0][k];
+        if (Fx) Fx[k] = pairF_[1][k];
+        if (Fy) Fy[k] = pairF_[2][k];
+    }
+}
+// The contract of setCustomOperators for the pair operators; independent of the bilinears
+void DetSDW::setCustomPairOperators(int count, const dqmc_cplx* F0, const dqmc_cplx* Fx, const dqmc_cplx* Fy) {
+    const detsdw_params& p = ch_[0].pars;
+    if (!eq_correlators(p) && !td_level(p)) throw ParameterWrong("custom pair operators need equalTimeCorrelators or timeDisplacedMeasurements");
+    if (count < 0 || count > DQMC_CUSTOM_MAX || (count && !F0)) throw ParameterWrong("detsdw_set_custom_pair_operators: count must be in 0 .. 4, with the matrices");
+    if (seriesNoHostCopy()) throw ParameterWrong("custom pair operators cannot be set while a series with DETSDW_SERIES_NO_HOST_COPY is open");
+    // a refusal of the operators comes from the first context and nothing has changed; after a failed allocation in a later one the
+    // earlier contexts get their old operators back, so that every context and pairF_ agree again before the error is passed on
+    for (size_t i = 0; i < groups_.size(); ++i) {
+        const int rc = dqmc_set_custom_pair_operators(groups_[i].ctx, count, F0, Fx, Fy);
+        if (rc == DQMC_OK) continue;
+        const std::string why = dqmc_last_error();
+        for (size_t k = 0; k < i; ++k)
+            if (dqmc_set_custom_pair_operators(groups_[k].ctx, pairCount(), pairF_[0].data(), pairF_[1].data(), pairF_[2].data()) != DQMC_OK)
+                throw GeneralError(rc, "dqmc_set_custom_pair_operators: " + why + "; restoring the earlier operators failed as well: the handle's kernel contexts disagree, destroy it");
+        throw GeneralError(rc, "dqmc_set_custom_pair_operators: " + why);
+    }
+    const dqmc_cplx zero{0.0, 0.0};
+    const dqmc_cplx* src[3] = {F0, Fx, Fy};
+    for (int k = 0; k < 3; ++k) {
+        std::vector<dqmc_cplx> f((size_t)16 * DQMC_CUSTOM_MAX, zero);      // fixed length, zero padded: the block of the series file
+        if (src[k]) std::copy(src[k], src[k] + (size_t)16 * count, f.begin());
+        pairF_[k].swap(f);
+    }
+    pairCount_ = count;
+    for (auto& g : groups_) g.matsNfreq[6] = 0;            // the other channels' transforms and blocks are untouched
+    for (auto& c : ch_)
+        for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) {
+            c.customPairCorr[ch].clear(); c.customPairSq[ch].clear();
+            for (TdObs* t : {&c.td, &c.tdFine}) { t->customPairTau[ch].clear(); t->customPairTauQ0[ch].clear(); }
+        }
 }
 bool DetSDW::customTd() const { return customCount() && ph_level(ch_[0].pars); }
 bool DetSDW::customEq() const { return customCount() && eq_correlators(ch_[0].pars); }
@@ -1604,6 +1702,11 @@ void DetSDW::seriesSave(const std::string& path) {
             wr(fc.f, customMy_.data(), customMy_.size() * sizeof(dqmc_cplx));
         }
     }
+    if (st.parts & (DQMC_SERIES_MATS_CUSTOM_PAIR | DQMC_SERIES_EQ_CUSTOM_PAIR)) {     // the pair operators' block, behind everything else again
+        const int32_t nc = pairCount();
+        wr(fc.f, &nc, sizeof(nc));
+        for (int k = 0; k < 3; ++k) wr(fc.f, pairF_[k].data(), pairF_[k].size() * sizeof(dqmc_cplx));
+    }
 }
 
 void DetSDW::seriesLoad(const std::string& path) {
@@ -1638,6 +1741,8 @@ void DetSDW::seriesLoad(const std::string& path) {
     const size_t S = st.sample_len, B = (size_t)st.bins_closed, extra = seriesExtra(st.flags);
     std::vector<double> slots((size_t)nch * (B + extra) * S);
     rd(fc.f, slots.data(), slots.size() * sizeof(double));
+    const bool pairPart = (st.parts & (DQMC_SERIES_MATS_CUSTOM_PAIR | DQMC_SERIES_EQ_CUSTOM_PAIR)) != 0;
+    const size_t pairBytes = pairPart ? sizeof(int32_t) + (size_t)3 * 16 * DQMC_CUSTOM_MAX * sizeof(dqmc_cplx) : 0;
     if (st.parts & (DQMC_SERIES_MATS_CUSTOM | DQMC_SERIES_EQ_CUSTOM)) {
         int32_t nc = -1;
         rd(fc.f, &nc, sizeof(nc));
@@ -1652,7 +1757,8 @@ void DetSDW::seriesLoad(const std::string& path) {
         if (here < 0 || std::fseek(fc.f, 0, SEEK_END) != 0) throw GeneralError(DQMC_EINVAL, "series file: cannot be positioned");
         const long end = std::ftell(fc.f);
         if (end < here || std::fseek(fc.f, here, SEEK_SET) != 0) throw GeneralError(DQMC_EINVAL, "series file: cannot be positioned");
-        const size_t rest = (size_t)(end - here);
+        if ((size_t)(end - here) < pairBytes) throw GeneralError(DQMC_EINVAL, "series file: truncated");
+        const size_t rest = (size_t)(end - here) - pairBytes;         // the pair operators' block of fixed length follows the bond block
         if (rest != 0 && rest != blockBytes)
             throw GeneralError(DQMC_EINVAL, rest > blockBytes ? "series file: longer than its header says" : "series file: truncated");
         const bool has = rest == blockBytes;
@@ -1667,6 +1773,17 @@ void DetSDW::seriesLoad(const std::string& path) {
             if (std::memcmp(bx.data(), customMx_.data(), bx.size() * sizeof(dqmc_cplx)) != 0 ||
                 std::memcmp(by.data(), customMy_.data(), by.size() * sizeof(dqmc_cplx)) != 0)
                 throw ParameterWrong("series file: the bond parts of the user-defined bilinears differ from the ones that are set");
+        }
+    }
+    if (pairPart) {
+        int32_t nc = -1;
+        rd(fc.f, &nc, sizeof(nc));
+        if (nc != pairCount()) throw ParameterWrong("series file: written with a different number of user-defined pair operators");
+        std::vector<dqmc_cplx> F((size_t)16 * DQMC_CUSTOM_MAX);
+        for (int k = 0; k < 3; ++k) {
+            rd(fc.f, F.data(), F.size() * sizeof(dqmc_cplx));
+            if (std::memcmp(F.data(), pairF_[k].data(), F.size() * sizeof(dqmc_cplx)) != 0)
+                throw ParameterWrong("series file: written with other user-defined pair operators than the ones that are set");
         }
     }
     char more;
@@ -1782,6 +1899,16 @@ extern "C" int detsdw_set_custom_bond_bilinears(detsdw_replica* r, int count, co
 }
 extern "C" int detsdw_get_custom_bond_bilinears(detsdw_replica* r, int* count, dqmc_cplx* M0, dqmc_cplx* Mx, dqmc_cplx* My) {
     RGUARD(r->impl->getCustomBondBilinears(count, M0, Mx, My))
+}
+extern "C" int detsdw_set_custom_pair_operators(detsdw_replica* r, int count, const dqmc_cplx* F0, const dqmc_cplx* Fx, const dqmc_cplx* Fy) {
+    RGUARD(r->impl->setCustomPairOperators(count, F0, Fx, Fy))
+}
+extern "C" int detsdw_get_custom_pair_operators(detsdw_replica* r, int* count, dqmc_cplx* F0, dqmc_cplx* Fx, dqmc_cplx* Fy) {
+    RGUARD(r->impl->getCustomPairOperators(count, F0, Fx, Fy))
+}
+extern "C" int detsdw_series_custom_pair_derived(detsdw_replica* r, int c, int qx, int qy, double* value, double* err) {
+    if (!value || !err) { g_host_err = "null argument"; return DQMC_EINVAL; }
+    RGUARD(r->impl->seriesCustomPairDerived(c, qx, qy, value, err))
 }
 extern "C" int detsdw_set_custom_bilinears(detsdw_replica* r, int count, const dqmc_cplx* M) {
     RGUARD(r->impl->setCustomBilinears(count, M))

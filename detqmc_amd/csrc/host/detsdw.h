@@ -76,6 +76,10 @@ public:
     void setCustomBilinears(int count, const dqmc_cplx* M);
     void setCustomBondBilinears(int count, const dqmc_cplx* M0, const dqmc_cplx* Mx, const dqmc_cplx* My);
     void getCustomBondBilinears(int* count, dqmc_cplx* M0, dqmc_cplx* Mx, dqmc_cplx* My) const;
+    // user-defined pair operators (include/detsdw_host.h): count operators (F0, Fx, Fy) for every kernel context, between sweeps
+    void setCustomPairOperators(int count, const dqmc_cplx* F0, const dqmc_cplx* Fx, const dqmc_cplx* Fy);
+    void getCustomPairOperators(int* count, dqmc_cplx* F0, dqmc_cplx* Fx, dqmc_cplx* Fy) const;
+    void seriesCustomPairDerived(int c, int qx, int qy, double* value, double* err);
     void seriesReadBins(int which, int first, int count, double* out, int b = 0);
     // long runs: options, re-binning, binning analysis (err, tau [levels] x the slice of seriesStats; tau may be null), series file
     void seriesConfigure(int flags);
@@ -108,6 +112,7 @@ private:
         std::vector<double> phTau[3], phTauQ0[3];           // charge, spinZ, sdw: rows x N and the row sums (timeDisplacedParticleHole)
         std::vector<double> currentTau[2], currentTauQ0[2], bondKinetic[2];   // x, y: rows x N, row sums, rows (timeDisplacedParticleHole == 2)
         std::vector<double> bandTau[2], bandTauQ0[2];       // bandDiff, bandMix: rows x N and the row sums (DETSDW_TD_PH_BAND)
+        std::vector<double> customPairTau[DQMC_CUSTOM_MAX], customPairTauQ0[DQMC_CUSTOM_MAX];   // ... per user-defined pair operator (setCustomPairOperators)
         std::vector<double> customTau[DQMC_CUSTOM_MAX], customTauQ0[DQMC_CUSTOM_MAX];   // the same per user-defined bilinear (setCustomBilinears)
     };
     struct Chain {
@@ -124,6 +129,7 @@ private:
         detsdw_observables obs{};
         std::vector<double> kOccX, kOccY, pairPlus, pairMinus;
         std::vector<double> eqCorr[7], eqSq[7];    // charge, spinZ, sdw, pairPlus, pairMinus: C(d) and S(q), N each (DETSDW_FM_EQ_CORRELATORS); 5, 6: bandDiff, bandMix (DETSDW_FM_EQ_BAND)
+        std::vector<double> customPairCorr[DQMC_CUSTOM_MAX], customPairSq[DQMC_CUSTOM_MAX];   // ... of the user-defined pair operators
         std::vector<double> customCorr[DQMC_CUSTOM_MAX], customSq[DQMC_CUSTOM_MAX];   // C(d) and S(q) of the user-defined bilinears, N each
         TdObs td, tdFine;                      // rows = interior boundaries j = 1 .. n-1 / time slices k = 0 .. m (timeDisplacedEverySlice)
         Chain(const detsdw_params& p) : pars(p), rng(p.rngSeed, (uint32_t)p.simindex + 1u) {}   // detqmc.h:181
@@ -134,8 +140,8 @@ private:
         int first = 0, count = 0;
         std::vector<double> window;                // uniforms of the coming sweep, all chains of the group
         std::vector<double> fields;                // host staging of all chains' fields (global moves)
-        std::vector<double> mats[6];               // Matsubara transforms of the group's chains per channel, [chain][component][nfreq][N] (re, im)
-        int matsNfreq[6] = {0, 0, 0, 0, 0, 0};          // ... and the nfreq they hold (0: none); cleared by every sweep
+        std::vector<double> mats[7];               // Matsubara transforms of the group's chains per channel, [chain][component][nfreq][N] (re, im)
+        int matsNfreq[7] = {0, 0, 0, 0, 0, 0, 0};          // ... and the nfreq they hold (0: none); cleared by every sweep
         std::vector<double> seriesMean, seriesErr; // dqmc_series_stats_host of the group's chains, [chain][S] each ...
         int seriesStatsBins = 0;                   // ... and the number of closed bins they were formed from (0: none)
         std::vector<double> seriesBinErr, seriesBinTau;   // dqmc_series_binning_host of the group's chains, [level][chain][S] each ...
@@ -152,6 +158,11 @@ private:
     std::vector<dqmc_cplx> customMx_, customMy_;   // the bond parts of setCustomBondBilinears, [count][4][4] each; empty while none is non-zero
     bool customBond() const { return !customMx_.empty(); }
     void setCustomOperators(int count, const dqmc_cplx* M, const dqmc_cplx* Mx, const dqmc_cplx* My, bool bond);
+    std::vector<dqmc_cplx> pairF_[3];              // F0, Fx, Fy of setCustomPairOperators, [DQMC_CUSTOM_MAX][4][4] each, zero padded
+    int pairCount_ = 0;
+    int pairCount() const { return pairCount_; }
+    bool customPairTd() const;                     // pair operators are set and the handle measures time-displaced
+    bool customPairEq() const;                     // ... the equal-time correlators
     bool customTd() const;                         // matrices are set and the handle measures the particle-hole family
     bool customEq() const;                         // ... the equal-time correlators
 

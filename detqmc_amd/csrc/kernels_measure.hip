@@ -1605,6 +1605,245 @@ static void launch_measure_eq_custom_bond(const Launch& lc, const DevModel& hm, 
     }
 }
 
+// User-defined pair operators (dqmc_set_custom_pair_operators; definitions in dqmc_hip.h and DESIGN.md 6e):
+//   Delta_A = sum_ab F0_ab c_(A a) c_(A b) + sum_mu u_mu(A) sum_ab Fmu_ab c_(A (+) mu, a) c_(A b),   P(A, B) = <Delta_A(tau) Delta_B^+(0)>.
+// With E^(PQ)_rc = g~(P r; Q c) of ONE shifted matrix gs (g~(tau,0) time-displaced, g~ of the slice at equal time: <c c c^+ c^+> has no
+// delta term) and the site blocks k = 0, x, y of an operator at the sites (A^k, A), Wick's theorem gives for the block pair (k, k')
+//   direct   = sum_abcd F^k_ab E^(A^k B^k')_ac conj(F^k')_cd E^(A B)_bd
+//   exchange = sum_abcd F^k_ab E^(A^k B)_ad   (F^k'^H)_dc    E^(A B^k')_bc
+// and P = sum_(k, k') u_k(A) u_k'(B) (direct - exchange); both are the one form sum F_ab X_ac G_cd Y_bd (cpr_term).  No one-body scratch, no
+// second matrix.  OPDIM < 3: the sector rule of cst_E / cst_same; a pair operator usually couples the sectors (XUP with XDOWN), which the
+// rule resolves at compile time like any other entry.
+// On-site form (no operator has a bond part): all four blocks are the one E = g~(A .; B .), loaded once per site pair, and
+//   P = tr(F^T E (conj F - F^H) E^T) = 1/2 sum_ab Fa_ab [E conj(Fa) E^T]_ab,   Fa = F0 - F0^T
+// (E conj(Fa) E^T is antisymmetric, so only the antisymmetric part of F0 contributes), every channel contracted from registers; Fa and
+// its non-zero mask travel as a kernel argument, the mask branches are uniform over the launch.  Shape, walk order over B, LDS
+// reduction, one writer per accumulator, fixed summation order, no atomics: those of k_measure_td_custom.  The block is count[rows],
+// then the rows [count][N]; the equal-time block is the same with rows = 1.  Blocks live outside the arena: chain b at acc + b * acs.
+template<int OPDIM, int R>
+__device__ __forceinline__ double cpr_onsite(const cplx (&e)[R][R], const cplx (&F)[4][4], unsigned mask) {
+    double s = 0.0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        if (!((mask >> (4 * a)) & 0xfu)) continue;          // row a of Fa is empty
+        cplx x[4], y[4];                                    // x[d] = (E conj Fa)_ad, y[d] = (Fa E)_ad
+#pragma unroll
+        for (int dl = 0; dl < 4; ++dl) x[dl] = y[dl] = make_double2(0.0, 0.0);
+#pragma unroll
+        for (int c2 = 0; c2 < 4; ++c2)
+            if (cst_same<OPDIM>(a, c2)) {
+#pragma unroll
+                for (int dl = 0; dl < 4; ++dl)
+                    if (mask & (1u << (4 * c2 + dl))) cst_fma(x[dl], cst_E<OPDIM, R>(e, a, c2), make_double2(F[c2][dl].x, -F[c2][dl].y));
+            }
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+            if (mask & (1u << (4 * a + b))) {
+#pragma unroll
+                for (int dl = 0; dl < 4; ++dl)
+                    if (cst_same<OPDIM>(b, dl)) cst_fma(y[dl], F[a][b], cst_E<OPDIM, R>(e, b, dl));
+            }
+#pragma unroll
+        for (int dl = 0; dl < 4; ++dl) s += x[dl].x * y[dl].x - x[dl].y * y[dl].y;
+    }
+    return 0.5 * s;
+}
+
+template<int OPDIM>
+__global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_custom_pair(DevModel dm, CustomMats cm, const cplx* __restrict__ gs,
+                                                                              double* __restrict__ acc, int row, int rows, size_t acs, size_t cs) {
+    CHAIN(gs);
+    constexpr int R = OPDIM == 3 ? 4 : 2;
+    acc += (size_t)blockIdx.z * acs;
+    __shared__ double red[DQMC_CUSTOM_MAX][TDP_PARTS][TDP_BINS];
+    const int N = dm.N, L = dm.L, tid = threadIdx.x, count = cm.count;
+    const size_t ng = (size_t)dm.ng;
+    const int lb = tid % TDP_BINS, part = tid / TDP_BINS;
+    const int d = blockIdx.x * TDP_BINS + lb;
+    const bool valid = d < N;
+    const int dx = valid ? d % L : 0, dy = valid ? d / L : 0;
+    double w[DQMC_CUSTOM_MAX] = {0.0, 0.0, 0.0, 0.0};
+    if (valid) {
+        int bx = part % L, by = part / L;                   // site B = part + 8 i, kept as (bx, by)
+        const int stepx = TDP_PARTS % L, stepy = TDP_PARTS / L;
+        for (int B = part; B < N; B += TDP_PARTS) {
+            int ax = bx + dx, ay = by + dy;
+            if (ax >= L) ax -= L;
+            if (ay >= L) ay -= L;
+            const int A = ay * L + ax;
+            const cplx* pe = gs + (size_t)B * ng + (size_t)A;     // E_rc = gs(A r; B c) = pe[c N ng + r N]
+            cplx e[R][R];
+#pragma unroll
+            for (int c2 = 0; c2 < R; ++c2)
+#pragma unroll
+                for (int r = 0; r < R; ++r) e[r][c2] = pe[(size_t)c2 * N * ng + (size_t)r * N];
+#pragma unroll
+            for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
+                if (ch < count) w[ch] += cpr_onsite<OPDIM, R>(e, cm.m[ch], cm.mask[ch]);
+            bx += stepx; by += stepy;
+            if (bx >= L) { bx -= L; ++by; }
+        }
+    }
+#pragma unroll
+    for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) red[ch][part][lb] = w[ch];
+    __syncthreads();
+    if (part < count && valid) {                            // part ch writes channel ch of its bin
+        double s = red[part][0][lb];
+#pragma unroll
+        for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
+        acc[rows + (size_t)row * count * N + (size_t)part * N + d] += s;
+    }
+    if (blockIdx.x == 0 && tid == 0) acc[row] += 1.0;
+}
+
+// Stencil form (at least one operator has a bond part).  Device table tab (measure_custom_pair_table_cplx complex, shared by the chains):
+// per operator and site block k = 0, x, y the three forms F, conj F, F^H, V[count][3][3][4][4], then the link signs u[2][N] (real part;
+// bond parts are refused under flux, so u = +-1).  mk[count][3][2]: the non-zero masks of F (and conj F) and of F^H.  parts[c] bit k:
+// block k of operator c is non-zero.  The 9 block pairs run in a real loop, the two blocks of the direct term and then the two of the
+// exchange term are the only ones live; the at most nine distinct neighbour blocks are re-read from L1 / L2.  Pairs no operator needs
+// are skipped before their loads, an on-site-only operator takes part in pair (0, 0) alone.
+#define CPR_K 3
+size_t measure_custom_pair_table_cplx(int count, int N) { return (size_t)count * CPR_K * 3 * 16 + 2 * (size_t)N; }
+struct CustomPairArg { const cplx* tab; const unsigned* mk; unsigned parts[DQMC_CUSTOM_MAX]; int count; };
+
+// Re sum_abcd F_ab X_ac G_cd Y_bd; x[r][c], y[r][c] the stored parts, F / G row-major in device memory with masks mf / mg
+template<int OPDIM, int R>
+__device__ __forceinline__ double cpr_term(const cplx (&x)[R][R], const cplx (&y)[R][R], const cplx* __restrict__ F, unsigned mf,
+                                           const cplx* __restrict__ G, unsigned mg) {
+    double s = 0.0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        if (!((mf >> (4 * a)) & 0xfu)) continue;            // row a of F is empty
+        cplx p[4], q[4];                                    // p[d] = (X G)_ad, q[d] = (F Y)_ad
+#pragma unroll
+        for (int dl = 0; dl < 4; ++dl) p[dl] = q[dl] = make_double2(0.0, 0.0);
+#pragma unroll
+        for (int c2 = 0; c2 < 4; ++c2)
+            if (cst_same<OPDIM>(a, c2)) {
+#pragma unroll
+                for (int dl = 0; dl < 4; ++dl)
+                    if (mg & (1u << (4 * c2 + dl))) cst_fma(p[dl], cst_E<OPDIM, R>(x, a, c2), G[4 * c2 + dl]);
+            }
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+            if (mf & (1u << (4 * a + b))) {
+                const cplx f = F[4 * a + b];
+#pragma unroll
+                for (int dl = 0; dl < 4; ++dl)
+                    if (cst_same<OPDIM>(b, dl)) cst_fma(q[dl], f, cst_E<OPDIM, R>(y, b, dl));
+            }
+#pragma unroll
+        for (int dl = 0; dl < 4; ++dl) s += p[dl].x * q[dl].x - p[dl].y * q[dl].y;
+    }
+    return s;
+}
+// e[r][c] = gs(P r; Q c)
+template<int R>
+__device__ __forceinline__ void cpr_load(const cplx* __restrict__ gs, size_t ng, int N, int P, int Q, cplx (&e)[R][R]) {
+    const cplx* pe = gs + (size_t)Q * ng + (size_t)P;
+#pragma unroll
+    for (int c2 = 0; c2 < R; ++c2)
+#pragma unroll
+        for (int r = 0; r < R; ++r) e[r][c2] = pe[(size_t)c2 * N * ng + (size_t)r * N];
+}
+
+template<int OPDIM>
+__global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_custom_pair_bond(DevModel dm, CustomPairArg cp, const cplx* __restrict__ gs,
+                                                                                   double* __restrict__ acc, int row, int rows, size_t acs, size_t cs) {
+    CHAIN(gs);
+    constexpr int R = OPDIM == 3 ? 4 : 2;
+    acc += (size_t)blockIdx.z * acs;
+    __shared__ double red[DQMC_CUSTOM_MAX][TDP_PARTS][TDP_BINS];
+    const int N = dm.N, L = dm.L, tid = threadIdx.x, count = cp.count;
+    const size_t ng = (size_t)dm.ng;
+    const int lb = tid % TDP_BINS, part = tid / TDP_BINS;
+    const int d = blockIdx.x * TDP_BINS + lb;
+    const bool valid = d < N;
+    const int dx = valid ? d % L : 0, dy = valid ? d / L : 0;
+    const cplx* __restrict__ lk = cp.tab + (size_t)count * CPR_K * 3 * 16;
+    unsigned both[DQMC_CUSTOM_MAX];                         // bit 3 ka + kb: operator ch has the blocks ka and kb
+    unsigned need = 0;
+#pragma unroll
+    for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) {
+        both[ch] = 0;
+        if (ch < count)
+            for (int ka = 0; ka < CPR_K; ++ka)
+                if ((cp.parts[ch] >> ka) & 1u) both[ch] |= (cp.parts[ch] & 0x7u) << (CPR_K * ka);
+        need |= both[ch];
+    }
+    double w[DQMC_CUSTOM_MAX] = {0.0, 0.0, 0.0, 0.0};
+    if (valid) {
+        int bx = part % L, by = part / L;                   // site B = part + 8 i, kept as (bx, by)
+        const int stepx = TDP_PARTS % L, stepy = TDP_PARTS / L;
+        for (int B = part; B < N; B += TDP_PARTS) {
+            int ax = bx + dx, ay = by + dy;
+            if (ax >= L) ax -= L;
+            if (ay >= L) ay -= L;
+            const int A = ay * L + ax;
+            int Ax, Ay, Bx, By;
+            cstb_stencil(L, ax, ay, Ax, Ay);
+            cstb_stencil(L, bx, by, Bx, By);
+            const double uax = lk[A].x, uay = lk[N + A].x, ubx = lk[B].x, uby = lk[N + B].x;
+#pragma unroll 1
+            for (int pr = 0; pr < CPR_K * CPR_K; ++pr) {
+                if (!((need >> pr) & 1u)) continue;
+                const int ka = pr / CPR_K, kb = pr % CPR_K;
+                const int p = ka == 1 ? Ax : ka == 2 ? Ay : A, r = kb == 1 ? Bx : kb == 2 ? By : B;
+                const double f = (ka == 1 ? uax : ka == 2 ? uay : 1.0) * (kb == 1 ? ubx : kb == 2 ? uby : 1.0);
+                cplx x[R][R], y[R][R];
+                cpr_load<R>(gs, ng, N, p, r, x);            // direct: E(A^k; B^k'), E(A; B)
+                cpr_load<R>(gs, ng, N, A, B, y);
+#pragma unroll
+                for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
+                    if ((both[ch] >> pr) & 1u) {
+                        const cplx* __restrict__ V = cp.tab + (size_t)ch * CPR_K * 3 * 16;
+                        const unsigned* __restrict__ mk = cp.mk + ch * CPR_K * 2;
+                        w[ch] += f * cpr_term<OPDIM, R>(x, y, V + 48 * ka, mk[2 * ka], V + 48 * kb + 16, mk[2 * kb]);
+                    }
+                cpr_load<R>(gs, ng, N, p, B, x);            // exchange: E(A^k; B), E(A; B^k')
+                cpr_load<R>(gs, ng, N, A, r, y);
+#pragma unroll
+                for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
+                    if ((both[ch] >> pr) & 1u) {
+                        const cplx* __restrict__ V = cp.tab + (size_t)ch * CPR_K * 3 * 16;
+                        const unsigned* __restrict__ mk = cp.mk + ch * CPR_K * 2;
+                        w[ch] -= f * cpr_term<OPDIM, R>(x, y, V + 48 * ka, mk[2 * ka], V + 48 * kb + 32, mk[2 * kb + 1]);
+                    }
+            }
+            bx += stepx; by += stepy;
+            if (bx >= L) { bx -= L; ++by; }
+        }
+    }
+#pragma unroll
+    for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) red[ch][part][lb] = w[ch];
+    __syncthreads();
+    if (part < count && valid) {                            // part ch writes channel ch of its bin
+        double s = red[part][0][lb];
+#pragma unroll
+        for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
+        acc[rows + (size_t)row * count * N + (size_t)part * N + d] += s;
+    }
+    if (blockIdx.x == 0 && tid == 0) acc[row] += 1.0;
+}
+
+void launch_measure_custom_pair(const Launch& lc, const DevModel& hm, int count, const cplx* Fa, const unsigned* mask, const cplx* gs, double* acc,
+                                size_t acs, int row, int rows, const CustomPair* bond) {
+    const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
+    if (bond) {
+        CustomPairArg cp{};
+        cp.tab = bond->tab; cp.mk = bond->mk; cp.count = count;
+        for (int ch = 0; ch < count; ++ch) cp.parts[ch] = bond->parts[ch];
+        if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_custom_pair_bond<1>), grid, block, 0, lc.st, hm, cp, gs, acc, row, rows, acs, lc.cs);
+        else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_custom_pair_bond<2>), grid, block, 0, lc.st, hm, cp, gs, acc, row, rows, acs, lc.cs);
+        else hipLaunchKernelGGL((k_measure_custom_pair_bond<3>), grid, block, 0, lc.st, hm, cp, gs, acc, row, rows, acs, lc.cs);
+        return;
+    }
+    const CustomMats cm = custom_mats(count, Fa, mask);
+    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_custom_pair<1>), grid, block, 0, lc.st, hm, cm, gs, acc, row, rows, acs, lc.cs);
+    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_custom_pair<2>), grid, block, 0, lc.st, hm, cm, gs, acc, row, rows, acs, lc.cs);
+    else hipLaunchKernelGGL((k_measure_custom_pair<3>), grid, block, 0, lc.st, hm, cm, gs, acc, row, rows, acs, lc.cs);
+}
+
 // End rows of the every-slice blocks (dqmc_measure_timedisplaced_ends): from the equal-time G = G(0), one elementwise pass writes
 //   tau = 0+:    G(0+,0) = G,          G(0,0+) = G - 1          -> a_t0, a_0t
 //   tau = beta-: G(beta-,0) = 1 - G,   G(0,beta-) = -G          -> b_t0, b_0t
@@ -1776,8 +2015,8 @@ bool td_matsubara_fits(const DevModel& hm, int channel, int nfreq) { return tdm_
 bool launch_td_matsubara(const Launch& lc, const DevModel& hm, const double* acc, int channel, int nfreq, int apbx, int apby,
                          double* out, double* bad, size_t out_chain_stride, int custom_count, size_t custom_chain_bytes) {
     const int L = hm.L, N = hm.N, m = hm.m, W = channel == 0 ? 2 * L - 1 : L;
-    const int rlen = channel == 0 ? 2 * W * W : N, ncomp = channel == 5 ? custom_count : channel == 2 ? 3 : 2;
-    const int stride = channel == 5 ? (int)measure_custom_row_doubles(custom_count, N) : (int)measure_td_row_doubles(channel, N, L);
+    const int rlen = channel == 0 ? 2 * W * W : N, ncomp = channel >= 5 ? custom_count : channel == 2 ? 3 : 2;
+    const int stride = channel >= 5 ? (int)measure_custom_row_doubles(custom_count, N) : (int)measure_td_row_doubles(channel, N, L);
     const int ftile = tdm_ftile(hm, channel, nfreq);
     if (ftile < 1) return false;
     const size_t lds = measure_td_matsubara_lds_doubles(ftile, m, L, W, rlen) * sizeof(double);
@@ -1786,7 +2025,7 @@ bool launch_td_matsubara(const Launch& lc, const DevModel& hm, const double* acc
     TdmShape a{channel, ncomp, nfreq, ftile, m, L, N, W, W | 1, rlen, stride, apbx, apby,
                hm.dtau / (channel == 0 ? 2.0 * N : (double)N), out_chain_stride ? out_chain_stride : (size_t)ncomp * nfreq * N * 2};
     const dim3 grid((nfreq + ftile - 1) / ftile, ncomp, lc.nb);
-    hipLaunchKernelGGL(k_td_matsubara, grid, dim3(256), lds, lc.st, acc, out, bad, a, channel == 5 ? custom_chain_bytes : lc.cs);
+    hipLaunchKernelGGL(k_td_matsubara, grid, dim3(256), lds, lc.st, acc, out, bad, a, channel >= 5 ? custom_chain_bytes : lc.cs);
     return true;
 }
 

@@ -148,9 +148,29 @@ def custom_ratio(name):
     return int(m.group(1)) if m else None
 
 
+# bit 11: the Matsubara transform of channel 6 (one component per operator of set_custom_pair_operators), bit 12: their equal-time
+# block, C(d) [count][N] then S(q) [count][N]
+SERIES_MATS_CUSTOM_PAIR, SERIES_EQ_CUSTOM_PAIR = 2048, 4096
+# observables of the custom pair operators (DetSDWBatch.set_custom_pair_operators), operator c = 0 .. 3: 'customPair{c}Tau',
+# 'customPair{c}TauQ0' (with 'Fine' twins), 'customPair{c}Corr', 'customPair{c}Sq' -> index base + c of detsdw_get_observable_vector
+CUSTOM_PAIR_OBS_BASE = {"Tau": 58, "TauQ0": 62, "Corr": 66, "Sq": 70}
+
+
+def custom_pair_observable(name):
+    """(kind, index) of a custom-pair observable name, kind in CUSTOM_PAIR_OBS_BASE; None for any other name"""
+    m = re.fullmatch(r"customPair([0-3])(Tau|TauQ0|Corr|Sq)", name)
+    return (m.group(2), CUSTOM_PAIR_OBS_BASE[m.group(2)] + int(m.group(1))) if m else None
+
+
+def custom_pair_ratio(name):
+    """operator index c of the derived series quantity 'R_customPair{c}'; None for any other name"""
+    m = re.fullmatch(r"R_customPair([0-3])", name)
+    return int(m.group(1)) if m else None
+
+
 def _matsubara_index(name):
-    """index of detsdw_get_matsubara for a name of MATSUBARA or 'custom{c}Tau'; KeyError otherwise"""
-    cw = custom_observable(name)
+    """index of detsdw_get_matsubara for a name of MATSUBARA, 'custom{c}Tau' or 'customPair{c}Tau'; KeyError otherwise"""
+    cw = custom_observable(name) or custom_pair_observable(name)
     return cw[1] if cw and cw[0] == "Tau" else MATSUBARA[name]
 # the order-parameter part of a series opened with phi=True: name -> index of detsdw_series_stats (real, (nfreq, N) and (5,))
 SERIES_PHI_OBS = {"phiChi": 32, "phiScalars": 33}
@@ -280,6 +300,27 @@ def bond_current(params, mu):
 def bond_kinetic(params, mu):
     """the same for the bond kinetic energy k_mu: M_mu = diag(T)"""
     return _bond_tuple(params, mu, 1.0)
+
+
+def pair_operator(kind):
+    """the (F0, Fx, Fy) tuple of a common pairing channel for set_custom_pair_operators (band-spin order XUP, YDOWN, XDOWN, YUP).  With S
+    the singlet matrix, S[XUP, XDOWN] = S[YUP, YDOWN] = 1, S[XDOWN, XUP] = S[YDOWN, YUP] = -1:
+        's'       F0[XUP, XDOWN] = F0[YUP, YDOWN] = 1: the operator of pairPlus (4 C(d) = pairPlus)
+        'd_band'  F0[XUP, XDOWN] = 1, F0[YUP, YDOWN] = -1: the operator of pairMinus
+        's_ext'   Fx = Fy = S: extended s on the bonds
+        'd_bond'  Fx = S, Fy = -S: bond d-wave
+    The bond operators use the bonds A -> A + x and A -> A + y only, so they are bond-centred: their q = 0 sums equal those of the
+    four-bond operator up to a constant factor."""
+    XUP, YDOWN, XDOWN, YUP = 0, 1, 2, 3
+    F = np.zeros((4, 4), dtype=np.complex128)
+    if kind in ("s", "d_band"):
+        F[XUP, XDOWN], F[YUP, YDOWN] = 1.0, 1.0 if kind == "s" else -1.0
+        return (F, None, None)
+    if kind in ("s_ext", "d_bond"):
+        F[XUP, XDOWN] = F[YUP, YDOWN] = 1.0
+        F[XDOWN, XUP] = F[YDOWN, YUP] = -1.0
+        return (None, F, F.copy() if kind == "s_ext" else -F)
+    raise ValueError("kind must be 's', 'd_band', 's_ext' or 'd_bond'")
 
 
 class KernelContext:
@@ -464,6 +505,35 @@ class KernelContext:
         """the selected chain's equal-time block of the set matrices: [count, one row of N raw sums per matrix], index dy L + dx"""
         return self._read_block(self.lib.dqmc_measure_eq_custom_accum_size, self.lib.dqmc_measure_eq_custom_read_host)
 
+    def set_custom_pair_operators(self, ops):
+        """up to four pair operators (F0, Fx, Fy), complex 4 x 4 each, None for a zero matrix:
+        Delta_A = sum_ab F0_ab c_(A a) c_(A b) + sum_mu u_mu(A) sum_ab Fmu_ab c_(A + mu, a) c_(A b); <Delta_A(tau) Delta_B^+(0)> is measured
+        time-displaced (measure_timedisplaced_custom_pair, needs timeDisplaced >= 1) and at equal time (set_equal_time_custom_pair).  An
+        empty list removes them; independent of set_custom_bilinears.  See pair_operator"""
+        f0, fx, fy = _custom_bond_operators(ops)
+        check(self.lib.dqmc_set_custom_pair_operators(self.h, len(f0), f0.ctypes.data, fx.ctypes.data, fy.ctypes.data))
+
+    def get_custom_pair_operators(self):
+        """the pair operators that are set: a list of (F0, Fx, Fy), complex 4 x 4 each"""
+        return _get_custom_bond(self.lib.dqmc_get_custom_pair_operators, self.h, False)
+
+    def measure_timedisplaced_custom_pair(self, j):
+        """the pair correlators of every set operator at boundary j, one launch, into their block"""
+        check(self.lib.dqmc_measure_timedisplaced_custom_pair(self.h, j))
+
+    def measure_td_custom_pair_read(self):
+        """count[n-1], then per boundary one row of N sums of Re P over the periodic site differences for every set pair operator"""
+        return self._read_block(self.lib.dqmc_measure_td_custom_pair_accum_size, self.lib.dqmc_measure_td_custom_pair_read_host)
+
+    def set_equal_time_custom_pair(self, on=True):
+        """while on, every measure_slice also bins the equal-time sums of every set pair operator into a block of their own (independent
+        of the other three equal-time switches)"""
+        check(self.lib.dqmc_set_equal_time_custom_pair(self.h, int(on)))
+
+    def measure_eq_custom_pair_read(self):
+        """the selected chain's equal-time block of the set pair operators: [count, one row of N raw sums per operator], index dy L + dx"""
+        return self._read_block(self.lib.dqmc_measure_eq_custom_pair_accum_size, self.lib.dqmc_measure_eq_custom_pair_read_host)
+
     def measure_timedisplaced_segment(self, j):
         """every slice of boundary j's segment into the fine blocks, by propagation from the boundary's matrices (needs tdEverySlice=True at
         construction; call it right after the advance that ended on boundary j)"""
@@ -474,7 +544,8 @@ class KernelContext:
         check(self.lib.dqmc_measure_timedisplaced_ends(self.h))
 
     def measure_td_fine_read(self, channel):
-        """fine block of channel 0 (G(k, tau) bins), 1 (pairing), 2 (particle-hole), 3 (current), 4 (band): count[m+1], then rows k = 0 .. m"""
+        """fine block of channel 0 (G(k, tau) bins), 1 (pairing), 2 (particle-hole), 3 (current), 4 (band), 5 (custom bilinears), 6 (custom pair
+        operators): count[m+1], then rows k = 0 .. m"""
         return self._read_block(self.lib.dqmc_measure_td_fine_accum_size, self.lib.dqmc_measure_td_fine_read_host, channel)
 
     def measure_td_matsubara(self, channel, nfreq):
@@ -523,7 +594,7 @@ class KernelContext:
     def series_layout(self, part):
         """(offset, length) of part 0 (equal-time: C_X(d) [5][N], S_X(q) [5][N]), 1 + channel (Matsubara, [component][nfreq][N] (re, im)), 6
         (order parameter), 7 (Matsubara of the band channel), 8 (equal-time band: C_X(d) [2][N], S_X(q) [2][N]), 9 (Matsubara of the custom
-        bilinears) or 10 (their equal-time block: C(d) [count][N], S(q) [count][N])"""
+        bilinears), 10 (their equal-time block: C(d) [count][N], S(q) [count][N]), 11 and 12 (the same two of the custom pair operators)"""
         off, ln = C.c_size_t(0), C.c_size_t(0)
         check(self.lib.dqmc_series_layout(self.h, int(part), C.byref(off), C.byref(ln)))
         return off.value, ln.value
@@ -564,6 +635,14 @@ class KernelContext:
         count = len(self.get_custom_bilinears())
         v, e = np.zeros((self.nchains_total(), count)), np.zeros((self.nchains_total(), count))
         check(self.lib.dqmc_series_custom_derived_host(self.h, int(qx), int(qy), v.ctypes.data_as(_lib._DP), e.ctypes.data_as(_lib._DP)))
+        return v, e
+
+    def series_custom_pair_derived(self, Q=None):
+        """series_custom_derived for the custom pair operators of a series with SERIES_EQ_CUSTOM_PAIR: (value, err), (nchains, count)"""
+        qx, qy = (self.L // 2, self.L // 2) if Q is None else Q
+        count = len(self.get_custom_pair_operators())
+        v, e = np.zeros((self.nchains_total(), count)), np.zeros((self.nchains_total(), count))
+        check(self.lib.dqmc_series_custom_pair_derived_host(self.h, int(qx), int(qy), v.ctypes.data_as(_lib._DP), e.ctypes.data_as(_lib._DP)))
         return v, e
 
     def series_phi_derived(self):
@@ -954,7 +1033,8 @@ class DetSDW:
         bandCorrelators: 'bandDiffTau', 'bandMixTau', 'bandDiffTauQ0', 'bandMixTauQ0' (and their 'Fine' twins) next to 'chargeTau', and
         'bandDiffCorr', 'bandMixCorr', 'bandDiffSq', 'bandMixSq' next to 'chargeCorr' / 'chargeSq'.  With matrices set by
         DetSDWBatch.set_custom_bilinears: 'custom{c}Tau', 'custom{c}TauQ0' (and their 'Fine' twins), 'custom{c}Corr', 'custom{c}Sq' for
-        matrix c, shaped like the bandDiff names"""
+        matrix c, shaped like the bandDiff names; with operators set by DetSDWBatch.set_custom_pair_operators the same four as
+        'customPair{c}...' for pair operator c"""
         self._sel()
         info = self.info
         if name in EQ_CORRELATORS or name in BAND_EQ_CORRELATORS:
@@ -965,7 +1045,7 @@ class DetSDW:
         fine = name.endswith("Fine")
         if fine:
             name = name[:-4]
-        cw = custom_observable(name)
+        cw = custom_observable(name) or custom_pair_observable(name)
         if cw:
             kind, which = cw
             if fine and kind in ("Corr", "Sq"):
@@ -1007,7 +1087,7 @@ class DetSDW:
             return BAND_EQ_CORRELATORS[name], (info.N,), False
         if name in SERIES_PHI_OBS:
             return SERIES_PHI_OBS[name], ((self._batch._series_nfreq, info.N) if name == "phiChi" else (5,)), False
-        cw = custom_observable(name)
+        cw = custom_observable(name) or custom_pair_observable(name)
         if cw and cw[0] in ("Corr", "Sq"):
             return cw[1], (info.N,), False
         return _matsubara_index(name), (self._batch._series_nfreq, info.N), True
@@ -1207,6 +1287,18 @@ class DetSDWBatch:
         """the operators that are set: a list of (M0, Mx, My), complex 4 x 4 each"""
         return _get_custom_bond(self.lib.detsdw_get_custom_bond_bilinears, self.h, True)
 
+    def set_custom_pair_operators(self, ops):
+        """up to four pair operators (F0, Fx, Fy), None for a zero matrix (see KernelContext.set_custom_pair_operators, pair_operator): from
+        the next sweep(True) on <Delta_A(tau) Delta_B^+(0)> is measured -- 'customPair{c}Tau' / 'customPair{c}TauQ0' (and their 'Fine' twins)
+        with timeDisplacedMeasurements, 'customPair{c}Corr' / 'customPair{c}Sq' with equalTimeCorrelators (one of the two is needed).  Between
+        sweeps; a second call replaces the operators, [] removes them; independent of set_custom_bilinears"""
+        f0, fx, fy = _custom_bond_operators(ops)
+        check(self.lib.detsdw_set_custom_pair_operators(self.h, len(f0), f0.ctypes.data, fx.ctypes.data, fy.ctypes.data), host=True)
+
+    def get_custom_pair_operators(self):
+        """the pair operators that are set: a list of (F0, Fx, Fy), complex 4 x 4 each"""
+        return _get_custom_bond(self.lib.detsdw_get_custom_pair_operators, self.h, True)
+
     def matsubara_all(self, name, nfreq):
         """DetSDW.matsubara of every chain: complex (nchains, nfreq, N), one device call per sub-batch"""
         out = np.zeros((len(self.chains), int(nfreq), self.chains[0].info.N), dtype=np.complex128)
@@ -1295,7 +1387,8 @@ class DetSDWBatch:
     def series_derived_all(self, name, Q=None):
         """(value, err) per chain of a jackknifed derived quantity: the correlation ratios 'R_charge', 'R_spinZ', 'R_sdw',
         'R_pairPlus', 'R_pairMinus' (equalTimeCorrelators) or 'rhoS' (timeDisplacedCurrent with timeDisplacedEverySlice);
-        'R_custom{c}': the correlation ratio of custom bilinear c at Q = (qx, qy) in units of 2 pi / L, default (L/2, L/2)"""
+        'R_custom{c}' / 'R_customPair{c}': the correlation ratio of custom bilinear / pair operator c at Q = (qx, qy) in units of
+        2 pi / L, default (L/2, L/2)"""
         v, e = np.zeros(len(self.chains)), np.zeros(len(self.chains))
         c = custom_ratio(name)
         if c is not None:
@@ -1303,6 +1396,13 @@ class DetSDWBatch:
             qx, qy = (L // 2, L // 2) if Q is None else Q
             check(self.lib.detsdw_series_custom_derived(self.h, c, int(qx), int(qy), v.ctypes.data_as(_lib._DP),
                                                         e.ctypes.data_as(_lib._DP)), host=True)
+            return v, e
+        c = custom_pair_ratio(name)
+        if c is not None:                                   # 'R_customPair{c}': the same for pair operator c
+            L = self.chains[0].info.L
+            qx, qy = (L // 2, L // 2) if Q is None else Q
+            check(self.lib.detsdw_series_custom_pair_derived(self.h, c, int(qx), int(qy), v.ctypes.data_as(_lib._DP),
+                                                             e.ctypes.data_as(_lib._DP)), host=True)
             return v, e
         if Q is not None:
             raise ValueError("Q belongs to 'R_custom{c}'")

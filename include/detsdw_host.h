@@ -151,7 +151,10 @@ enum { DETSDW_OBS_KOCCX = 0, DETSDW_OBS_KOCCY = 1, DETSDW_OBS_PAIRPLUS = 2, DETS
        /* user-defined bilinears (detsdw_set_custom_bilinears), matrix c = 0 .. 3 at BASE + c: custom{c}Tau and custom{c}TauQ0 with the rows,
           normalisation, DETSDW_OBS_FINE twins and Matsubara transforms of bandDiffTau; custom{c}Corr and custom{c}Sq with those of
           bandDiffCorr / bandDiffSq.  ParameterWrong for a c that is not set, or without the family the observable rides on */
-       DETSDW_OBS_CUSTOMTAU = 42, DETSDW_OBS_CUSTOMTAU_Q0 = 46, DETSDW_OBS_CUSTOMCORR = 50, DETSDW_OBS_CUSTOMSQ = 54 };
+       DETSDW_OBS_CUSTOMTAU = 42, DETSDW_OBS_CUSTOMTAU_Q0 = 46, DETSDW_OBS_CUSTOMCORR = 50, DETSDW_OBS_CUSTOMSQ = 54,
+       /* user-defined pair operators (detsdw_set_custom_pair_operators), operator c = 0 .. 3 at BASE + c: customPair{c}Tau,
+          customPair{c}TauQ0 (DETSDW_OBS_FINE twins, Matsubara transforms), customPair{c}Corr, customPair{c}Sq, like the custom{c} ones */
+       DETSDW_OBS_CUSTOMPAIRTAU = 58, DETSDW_OBS_CUSTOMPAIRTAU_Q0 = 62, DETSDW_OBS_CUSTOMPAIRCORR = 66, DETSDW_OBS_CUSTOMPAIRSQ = 70 };
 /* equalTimeCorrelators: flag bit of detsdw_params::fermionMeasurements */
 enum { DETSDW_FM_EQ_CORRELATORS = 0x100 };
 /* bandCorrelators: DETSDW_FM_EQ_BAND is a flag bit of detsdw_params::fermionMeasurements, DETSDW_TD_PH_BAND one of ::timeDisplacedParticleHole */
@@ -315,6 +318,20 @@ int detsdw_series_custom_derived(detsdw_replica* r, int c, int qx, int qy, doubl
  * included.  detsdw_set_custom_bilinears clears the bond parts.  The getter returns count and the three parts (each may be NULL). */
 int detsdw_set_custom_bond_bilinears(detsdw_replica* r, int count, const dqmc_cplx* M0, const dqmc_cplx* Mx, const dqmc_cplx* My);
 int detsdw_get_custom_bond_bilinears(detsdw_replica* r, int* count, dqmc_cplx* M0, dqmc_cplx* Mx, dqmc_cplx* My);
+/* User-defined pair operators (dqmc_set_custom_pair_operators in dqmc_hip.h: the definition, the Wick form, the refusals): F0, Fx, Fy
+ * [count][4][4] each, Fx / Fy may be NULL, count = 0 removes them; independent of the custom bilinears.  Forwarded to every sub-batch
+ * context, between sweeps; if a later context fails the earlier ones get their old operators back.  ParameterWrong unless
+ * equalTimeCorrelators or timeDisplacedMeasurements is set, and while a series with DETSDW_SERIES_NO_HOST_COPY is open; the kernel
+ * level's refusals come back as its error.  Measurement sweeps then fill customPair{c}Tau / TauQ0 (timeDisplacedMeasurements >= 1; with
+ * timeDisplacedEverySlice also the DETSDW_OBS_FINE twins and detsdw_get_matsubara[_all]) and customPair{c}Corr / Sq
+ * (equalTimeCorrelators): C(d) = (1/N) sum_B Re <Delta_(B + d) Delta_B^+>, no factor 4 (pairPlusTau = 4 x the row of pair_operator 's').
+ * A series begun while operators are set carries DQMC_SERIES_MATS_CUSTOM_PAIR / DQMC_SERIES_EQ_CUSTOM_PAIR, routed like every other
+ * part; the series readers take customPair{c}Tau, Corr and Sq; detsdw_series_save appends one block (count, F0, Fx, Fy, zero padded to
+ * DQMC_CUSTOM_MAX) behind everything else only while such a part is open, and detsdw_series_load raises ParameterWrong on a mismatch
+ * before anything is imported.  detsdw_series_custom_pair_derived: value[nchains], err[nchains] of R at Q = (qx, qy) for operator c. */
+int detsdw_set_custom_pair_operators(detsdw_replica* r, int count, const dqmc_cplx* F0, const dqmc_cplx* Fx, const dqmc_cplx* Fy);
+int detsdw_get_custom_pair_operators(detsdw_replica* r, int* count, dqmc_cplx* F0, dqmc_cplx* Fx, dqmc_cplx* Fy);
+int detsdw_series_custom_pair_derived(detsdw_replica* r, int c, int qx, int qy, double* value, double* err);
 int detsdw_series_read_bins(detsdw_replica* r, int which, int first, int count, double* out);
 int detsdw_series_end(detsdw_replica* r);
 /* The series over a long run (kernel calls and formulas: dqmc_hip.h).  All of it is new surface: without these calls nothing changes.

@@ -459,6 +459,44 @@ int dqmc_measure_eq_custom_read_host(dqmc_ctx* ctx, double* out);
  * dqmc_get_custom_bond_bilinears reads all three back (each array may be NULL). */
 int dqmc_set_custom_bond_bilinears(dqmc_ctx* ctx, int count, const dqmc_cplx* M0, const dqmc_cplx* Mx, const dqmc_cplx* My);
 int dqmc_get_custom_bond_bilinears(dqmc_ctx* ctx, int* count, dqmc_cplx* M0, dqmc_cplx* Mx, dqmc_cplx* My);
+/* User-defined pair operators ("customPair"): the pairing channel of the user-defined bilinears.  Operator c = 0 .. DQMC_CUSTOM_MAX - 1
+ * is three complex 4 x 4 matrices (F0, Fx, Fy) in the band-spin order XUP, YDOWN, XDOWN, YUP:
+ *   Delta_A = sum_ab F0_ab c_{A a} c_{A b} + sum_{mu = x, y} u_mu(A) sum_ab Fmu_ab c_{A (+) mu, a} c_{A b}
+ * u_mu(A) = +-1 the antiperiodic sign of the bond A -> A (+) mu, so that Delta_A is translation-covariant under apbc-*.  Delta is not
+ * Hermitian and no Hermitian conjugate is added.  Only the antisymmetric part of F0 contributes; any F0 is accepted.  With bonds
+ * A -> A (+) x and A -> A (+) y only, a bond operator is bond-centred: its q = 0 sums equal those of the four-bond operator up to a
+ * constant factor.  Measured is
+ *   P_c(A, B; tau) = <Delta_A(tau) Delta_B^+(0)> = sum_ijkl D^A_ij conj(D^B_kl) [g(i; k) g(j; l) - g(i; l) g(j; k)],
+ * g the shifted G(tau,0) over (flavour, site), D_A the dense coefficient matrix of Delta_A with the site blocks (A, A) = F0,
+ * (A (+) mu, A) = u_mu Fmu.  A particle-conserving ensemble has no anomalous average: no disconnected term, and G(tau,0) alone is
+ * needed.  At equal time the same expression on the shifted G of the slice (<c c c^+ c^+> has no delta term).  Binned as every other
+ * correlator, C_c(d) = (1/N) sum_B Re P_c(B (+) d, B), bin dy L + dx, with NO factor 4: F0[XUP, XDOWN] = 1, F0[YUP, YDOWN] = +-1
+ * gives pairPlus / pairMinus of dqmc_measure_timedisplaced_pair divided by 4.
+ * dqmc_set_custom_pair_operators(ctx, count, F0, Fx, Fy): each array [count][4][4] row-major, Fx and Fy may be NULL (all zero), count = 0
+ * removes the operators.  Run-time state like dqmc_set_custom_bilinears and independent of it: neither call touches the other's
+ * operators or blocks.  The call allocates the blocks below outside the arena (a failed allocation leaves the context as it was); a
+ * second call replaces the operators and clears the blocks; the equal-time switch outlives a replacement, not the removal.  With no
+ * operator set no kernel of this section is launched and every other block, launch count and result keeps its bits.  DQMC_EINVAL
+ * with nothing changed: count out of range, an entry that is not finite, an operator that vanishes identically (F0 - F0^T = 0 with Fx =
+ * Fy = 0), a non-zero bond entry under weakZflux (the two fermions of a bond pair sit on different sites and carry flavour-dependent
+ * Peierls phases; no gauge choice is made here -- on-site operators are allowed under flux, the formula applied as it stands like the
+ * fixed channels), a Hubbard context, a series with a pair part open.  dqmc_get_custom_pair_operators reads count and the three
+ * arrays back (each may be NULL).
+ * dqmc_measure_timedisplaced_custom_pair(j) (all chains, every operator in one launch): preconditions of
+ * dqmc_measure_timedisplaced_pair; needs only timedisplaced >= 1.  Layout (doubles, dqmc_measure_td_custom_pair_accum_size of them):
+ * count[n-1], then for j = 1 .. n-1 `count` rows of N raw sums over B of Re P_c(B (+) d, B).  Every-slice channel 6 with
+ * DQMC_TD_EVERY_SLICE (row stride count N).
+ * dqmc_set_equal_time_custom_pair(on): a fourth switch of dqmc_measure_slice, independent of the other three (DQMC_EINVAL while no
+ * operator is set).  Block (dqmc_measure_eq_custom_pair_accum_size doubles): count, then `count` rows of N raw sums.
+ * dqmc_measure_reset clears all blocks. */
+int dqmc_set_custom_pair_operators(dqmc_ctx* ctx, int count, const dqmc_cplx* F0, const dqmc_cplx* Fx, const dqmc_cplx* Fy);
+int dqmc_get_custom_pair_operators(dqmc_ctx* ctx, int* count, dqmc_cplx* F0, dqmc_cplx* Fx, dqmc_cplx* Fy);
+int dqmc_measure_timedisplaced_custom_pair(dqmc_ctx* ctx, int j);
+size_t dqmc_measure_td_custom_pair_accum_size(dqmc_ctx* ctx);  /* 0 without operators or without timedisplaced */
+int dqmc_measure_td_custom_pair_read_host(dqmc_ctx* ctx, double* out);
+int dqmc_set_equal_time_custom_pair(dqmc_ctx* ctx, int on);
+size_t dqmc_measure_eq_custom_pair_accum_size(dqmc_ctx* ctx);  /* 0 while no operator is set */
+int dqmc_measure_eq_custom_pair_read_host(dqmc_ctx* ctx, double* out);
 /* G(0) of the last pair's field configuration, selected chain; *slice as for dqmc_get_green_timedisplaced_host.  DQMC_EINVAL without
  * td_particle_hole or if no pair was computed yet */
 int dqmc_get_green0_timedisplaced_host(dqmc_ctx* ctx, dqmc_cplx* g00, int* slice);
@@ -480,7 +518,7 @@ int dqmc_get_green0_timedisplaced_host(dqmc_ctx* ctx, dqmc_cplx* g00, int* slice
  * (current time slice 0 or m: the state after the closing advance of either sweep direction), so that G = G(0); DQMC_EINVAL
  * otherwise.  Both rows use G(tau) = G(0) = G.
  * Blocks: channel 0 = bins of dqmc_measure_timedisplaced, 1 = _pair, 2 = _ph, 3 = _current, 4 = _band (row stride 2N), 5 = _custom (row
- * stride count N, present while matrices are set); a channel has a
+ * stride count N, present while matrices are set), 6 = _custom_pair (row stride count N, present while pair operators are set); a channel has a
  * block if its coarse block is reserved.  Layout (doubles, dqmc_measure_td_fine_accum_size of them, 0 without the block): count[m+1], then row k = 0 .. m
  * at offset (m+1) + k stride, stride and contents of a row as in the coarse block: 4 (2L-1)^2, 2N, 3N, 2N + 2.
  * dqmc_measure_reset clears them as well. */
@@ -583,9 +621,17 @@ int dqmc_measure_td_matsubara_host(dqmc_ctx* ctx, int channel, int nfreq, double
  * S(q) [count][N], formed like bit 8).  The accepted mask is 0x7df.  While a series with one of the two is open,
  * dqmc_set_custom_bilinears returns DQMC_EINVAL.  dqmc_series_custom_derived_host(qx, qy) (all chains, value and err [nb][count];
  * DQMC_EINVAL for B < 2, a series without bit 10, qx or qy outside 0 .. L-1): the same jackknife of R for every matrix at the caller's
- * Q = (qx, qy), in units of 2 pi / L. */
+ * Q = (qx, qy), in units of 2 pi / L.
+ * The parts of the user-defined pair operators (dqmc_set_custom_pair_operators), behind all of the above again:
+ * DQMC_SERIES_MATS_CUSTOM_PAIR = 2048 (bit 11: the Matsubara transform of every-slice channel 6, [count][nfreq][N] complex) and
+ * DQMC_SERIES_EQ_CUSTOM_PAIR = 4096 (bit 12: the block of dqmc_set_equal_time_custom_pair as C(d) [count][N] then S(q) [count][N]).  Both
+ * are refused (DQMC_EINVAL) while no pair operator is set; the accepted mask is 0x1fdf.  While a series with one of the two is open,
+ * dqmc_set_custom_pair_operators returns DQMC_EINVAL.  dqmc_series_custom_pair_derived_host(qx, qy): R of every pair operator at the
+ * caller's Q by the routine of dqmc_series_custom_derived_host (value and err [nb][count]; DQMC_EINVAL for B < 2, a series without
+ * bit 12, qx or qy outside 0 .. L-1). */
 enum { DQMC_SERIES_EQ = 1, DQMC_SERIES_MATS_G = 2, DQMC_SERIES_MATS_PAIR = 4, DQMC_SERIES_MATS_PH = 8, DQMC_SERIES_MATS_CURRENT = 16,
-       DQMC_SERIES_PHI = 64, DQMC_SERIES_MATS_BAND = 128, DQMC_SERIES_EQ_BAND = 256, DQMC_SERIES_MATS_CUSTOM = 512, DQMC_SERIES_EQ_CUSTOM = 1024 };
+       DQMC_SERIES_PHI = 64, DQMC_SERIES_MATS_BAND = 128, DQMC_SERIES_EQ_BAND = 256, DQMC_SERIES_MATS_CUSTOM = 512, DQMC_SERIES_EQ_CUSTOM = 1024,
+       DQMC_SERIES_MATS_CUSTOM_PAIR = 2048, DQMC_SERIES_EQ_CUSTOM_PAIR = 4096 };
 int dqmc_series_begin(dqmc_ctx* ctx, int bin_size, int max_bins, int nfreq, int parts);
 int dqmc_series_layout(dqmc_ctx* ctx, int part, size_t* offset, size_t* length);
 int dqmc_series_add_sweep(dqmc_ctx* ctx);
@@ -599,6 +645,7 @@ int dqmc_series_derived_host(dqmc_ctx* ctx, double* value, double* err);
 int dqmc_series_phi_derived_host(dqmc_ctx* ctx, double* value, double* err);
 int dqmc_series_band_derived_host(dqmc_ctx* ctx, double* value, double* err);
 int dqmc_series_custom_derived_host(dqmc_ctx* ctx, int qx, int qy, double* value, double* err);
+int dqmc_series_custom_pair_derived_host(dqmc_ctx* ctx, int qx, int qy, double* value, double* err);
 int dqmc_series_end(dqmc_ctx* ctx);
 /* ---- the series over a long run: re-binning, binning analysis with tau_int, export / import ------------
  * All of it is new surface: with none of these calls used, every call above keeps its bits, its error codes and its launches.
