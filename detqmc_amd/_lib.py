@@ -180,6 +180,7 @@ SYMBOLS = [
     ("dqmc_set_fields_all_host", C.c_int, [_P, _DP]),
     ("dqmc_get_fields_all_host", C.c_int, [_P, _DP]),
     ("dqmc_bmult_host", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    ("dqmc_bmult_src_host", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     ("dqmc_udv_decompose_host", C.c_int, [_P, _P, _P, _DP, _P, C.POINTER(C.c_int)]),
     ("dqmc_gemm_host", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),
     ("dqmc_udv_setup", C.c_int, [_P]),
@@ -191,6 +192,7 @@ SYMBOLS = [
     ("dqmc_push_uniforms_all_host", C.c_int, [_P, _DP, C.c_size_t]),
     ("dqmc_update_slice", C.c_int, [_P, C.c_int, C.c_int]),
     ("dqmc_update_slice_ex", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("dqmc_update_slice_final", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("dqmc_get_schedule_info", C.c_int, [_P, C.POINTER(dqmc_schedule_info)]),
     ("dqmc_get_update_states_all_host", C.c_int, [_P, C.POINTER(dqmc_update_state)]),
     ("dqmc_get_update_state_host", C.c_int, [_P, C.POINTER(dqmc_update_state)]),

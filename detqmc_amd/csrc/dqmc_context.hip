@@ -754,14 +754,17 @@ void run_gemm(dqmc_ctx* c, const GemmArgs& g) {
 
 // chain order of checkerboard{Left,Right}MultiplyBmat[Inv] (detsdwopdim.cpp:2076-2090, 2172-2186,
 // 2307-2324, 2406-2420)
-void bmult_dev(dqmc_ctx* c, int side, int inverse, int k2, int k1, cplx* A) {
+// src != nullptr: out of place, A = (chain) src -- the first pass of the checkerboard kernel reads src instead of A, the copy in front
+// of an in-place multiply never happens.  (An empty chain and the dense propagator copy.)
+void bmult_dev(dqmc_ctx* c, int side, int inverse, int k2, int k1, cplx* A, const cplx* src) {
     const int count = k2 - k1;
+    if (src && (count <= 0 || c->hm.dense)) { launch_copy(c->lc, src, A, (size_t)c->n_g * c->n_g); src = nullptr; }
     if (count <= 0) return;
     bool ascending = (side == DQMC_LEFT) ? !inverse : (bool)inverse;
     int kfirst = ascending ? k1 + 1 : k2, kstep = ascending ? 1 : -1;
     if (!c->hm.dense) {
         ProfScope ps(c, FAM_BMULT, 1);
-        launch_bmult(c->lc, nullptr, c->hm, side, inverse, kfirst, kstep, count, A, c->n_g);
+        launch_bmult(c->lc, nullptr, c->hm, side, inverse, kfirst, kstep, count, A, c->n_g, 0, src);
         return;
     }
     // CB_NONE (sdw*MultiplyBmat[Inv] functors with CBM == CB_NONE, detsdwopdim.h:1305-1375): per slice
@@ -946,7 +949,13 @@ static int factorise_z(dqmc_ctx* c, double* svout, ZFactors* z, int* launches) {
 // dst = (X diag(scale)) U^-1 (LU)  or  (X diag(scale)) P R^-1 (QR routes)
 static int left_half(dqmc_ctx* c, const ZFactors& z, const cplx* X, const double* scale, cplx* dst) {
     ProfScope ps(c, FAM_JACOBI, 0);
-    launch_permute_scale_cols(c->lc, X, scale, z.route == Z_LU ? nullptr : c->qr_perm, c->n_g, dst);
+    if (z.route == Z_LU) {
+        // no column permutation: the solve reads X diag(scale) where it lies (first touch of dst), the scaled copy in front of it is gone
+        const ColSrc src = {X, c->n_g, nullptr, scale};
+        return run_trsm_right_upper(c->lc, c->n_g, z.tri, dst, c->qw, 0, 0, &src);
+    }
+    // QR routes: the scatter dst[:, perm[j]] = X[:, j] scale[j] stays a pass of its own (reading it in the solve needs the inverse permutation)
+    launch_permute_scale_cols(c->lc, X, scale, c->qr_perm, c->n_g, dst);
     return 1 + run_trsm_right_upper(c->lc, c->n_g, z.tri, dst, c->qw);
 }
 // dst = [L^-1 P (diag(scale) Yh^H)]^H (LU)  or  Q^H (diag(scale) Yh^H) (QR routes); stage: scratch of the explicit-Q route
@@ -956,8 +965,8 @@ static int right_half(dqmc_ctx* c, const ZFactors& z, const cplx* Yh, const doub
     {
         ProfScope ps(c, FAM_JACOBI, 0);
         if (z.route == Z_LU) {
-            launch_gather_scale_cols(c->lc, Yh, scale, c->qr_perm, n, dst);                  // dst = (Yh diag(scale)) P^T
-            launches += run_trsm_right_upper(c->lc, n, z.tri, dst, c->qw, 1, 1);             // dst <- dst L^-H
+            const ColSrc src = {Yh, n, c->qr_perm, scale};                                   // (Yh diag(scale)) P^T, read where it lies
+            launches = run_trsm_right_upper(c->lc, n, z.tri, dst, c->qw, 1, 1, &src);        // dst <- ((Yh diag(scale)) P^T) L^-H
         } else if (z.route == Z_QR_REFLECTORS) {
             launch_udt_init(c->lc, Yh, n, scale, nullptr, nullptr, 1, dst, n);               // dst = diag(scale) Yh^H
             launches += run_qr_apply_q(c->lc, n, dst, c->qw, 1);                             // dst <- Q^H dst
@@ -1098,8 +1107,7 @@ extern "C" int dqmc_udv_setup(dqmc_ctx* c) {
     if ((rc = decompose(c, c->T1, nullptr, nullptr, KIND_R, c->storage[1]))) return rc;
     for (int l = 1; l <= n - 1; ++l) {
         const int k_l = s * l, k_lp1 = (l < n - 1) ? s * (l + 1) : m;
-        launch_copy(c->lc, c->storage[l].U, c->T1, (size_t)ng * ng);
-        bmult_dev(c, DQMC_LEFT, 0, k_lp1, k_l, c->T1);
+        bmult_dev(c, DQMC_LEFT, 0, k_lp1, k_l, c->T1, c->storage[l].U);
         if ((rc = decompose_chained(c, c->T1, c->storage[l].d, nullptr, KIND_R, c->storage[l + 1], c->storage[l].Vt))) return rc;
     }
     if ((rc = green_from_eye(c, c->storage[n], KIND_R))) return rc;
@@ -1150,8 +1158,7 @@ extern "C" int dqmc_advance(dqmc_ctx* c, int dir, int l) {
         if (c->currentTimeslice != k_lp1) return fail(DQMC_EINVAL, "advanceUp: currentTimeslice != k_{l+1}");
         const UdVSlot& st = c->storage[l];
         UdVSlot T = c->spare;
-        launch_copy(c->lc, st.U, c->T1, (size_t)ng * ng);
-        bmult_dev(c, DQMC_LEFT, 0, k_lp1, k_l, c->T1);
+        bmult_dev(c, DQMC_LEFT, 0, k_lp1, k_l, c->T1, st.U);
         if ((rc = decompose_chained(c, c->T1, st.d, nullptr, KIND_R, T, st.Vt))) return rc;
         if (k_lp1 != m) {
             rc = green_from_udv(c, c->storage[l + 1], T);
@@ -1249,9 +1256,9 @@ extern "C" int dqmc_update_slice(dqmc_ctx* c, int k, int thermalization) {
     return dqmc_update_slice_ex(c, k, thermalization, DQMC_PROPOSE_BOX, DQMC_ADAPT_BOX, 0, 1);
 }
 
-extern "C" int dqmc_update_slice_ex(dqmc_ctx* c, int k, int thermalization, int proposal, int adapt, int adapt_scale_variance, int repeat) {
-    if (!c) return fail(DQMC_EINVAL, "null ctx");
-    (void)hipSetDevice(c->p.device);
+// skip_final: in the last pass over the slice a chain neither gathers nor flushes the block in which it finishes the slice
+// (dqmc_update_slice_final; sequential schedule only).  The decisions, and with them everything but G, X and GrT, are untouched.
+static int update_slice_run(dqmc_ctx* c, int k, int thermalization, int proposal, int adapt, int adapt_scale_variance, int repeat, bool skip_final) {
     if (k < 1 || k > c->m) return fail(DQMC_EINVAL, "updateInSlice: k out of range");
     if (c->currentTimeslice != k) return fail(DQMC_EINVAL, "updateInSlice: currentTimeslice != k");
     G_FRESH(c, "updateInSlice");
@@ -1275,7 +1282,9 @@ extern "C" int dqmc_update_slice_ex(dqmc_ctx* c, int k, int thermalization, int 
     // schedule: the flush is timed / checked on the stream it runs on.
     const bool pipe = c->pipelined;
     Launch lc2 = c->lc; lc2.st = c->st2;
-    auto pass = [&](int cdw_pass, int thermal, int reset_nd) -> int {
+    auto pass = [&](int cdw_pass, int thermal, int reset_nd, bool skip) -> int {
+        // skip: k_update_decide sets slice_done in the launch in which the chain's cursor reaches N and leaves block_j standing
+        const int* done = skip ? &c->us->slice_done : nullptr;
         for (int r = 0; r < rounds; ++r) {
             {
                 ProfScope ps(c, FAM_UPDATE, 1);
@@ -1285,7 +1294,7 @@ extern "C" int dqmc_update_slice_ex(dqmc_ctx* c, int k, int thermalization, int 
             if (pipe && r > 0) HIPCHK(hipStreamWaitEvent(c->st, c->ev_flush, 0));      // gather reads whole rows / columns of the flushed G
             {
                 ProfScope ps(c, FAM_GATHER, 1);
-                launch_update_gather(c->lc, c->hm, c->us, c->G, c->W, c->X, c->Gr);
+                launch_update_gather(c->lc, c->hm, c->us, c->G, c->W, c->X, c->Gr, skip);
             }
             if (pipe) {
                 { ProfScope ps(c, FAM_OTHER, 1); launch_update_window(c->lc, c->hm, c->us, c->G, c->X, c->Gr, c->Gwin, c->pipe_P); }
@@ -1299,7 +1308,7 @@ extern "C" int dqmc_update_slice_ex(dqmc_ctx* c, int k, int thermalization, int 
                 c->blocks_pipelined += 1;
             } else {
                 ProfScope ps(c, FAM_FLUSH, 1);
-                launch_flush(c->lc, c->X, c->Gr, c->n_g, c->G, c->n_g, c->n_g, WD, &c->us->block_j, c->MSF);
+                launch_flush(c->lc, c->X, c->Gr, c->n_g, c->G, c->n_g, c->n_g, WD, &c->us->block_j, c->MSF, 0, done);
                 c->blocks_sequential += 1;
             }
         }
@@ -1308,11 +1317,36 @@ extern "C" int dqmc_update_slice_ex(dqmc_ctx* c, int k, int thermalization, int 
     };
     // repeatUpdateInSlice passes over the slice (detsdwopdim.cpp:2438); the step-size adaptation sees the last one's acceptance ratio
     // (updateInSliceThermalization, :3294-3331); the Box-Muller stack of the scale proposals is reset once per updateInSlice (:2433)
-    for (int rep = 0; rep < repeat; ++rep) { int rc = pass(0, (thermalization && rep == repeat - 1) ? 1 : 0, rep == 0); if (rc) return rc; }
+    const bool skip = skip_final && !pipe;
+    for (int rep = 0; rep < repeat; ++rep) {
+        int rc = pass(0, (thermalization && rep == repeat - 1) ? 1 : 0, rep == 0, skip && rep == repeat - 1 && !c->hm.cdw_on);
+        if (rc) return rc;
+    }
     // cdwU != 0: the second pass over the slice updates the discrete field (detsdwopdim.cpp:2474-2485); its acceptance ratio is
     // discarded there and here (no step-width adaptation)
-    if (c->hm.cdw_on) { int rc = pass(1, 0, 0); if (rc) return rc; }
+    if (c->hm.cdw_on) { int rc = pass(1, 0, 0, skip); if (rc) return rc; }
     return finish(c, "dqmc_update_slice");
+}
+
+extern "C" int dqmc_update_slice_ex(dqmc_ctx* c, int k, int thermalization, int proposal, int adapt, int adapt_scale_variance, int repeat) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    (void)hipSetDevice(c->p.device);
+    return update_slice_run(c, k, thermalization, proposal, adapt, adapt_scale_variance, repeat, false);
+}
+
+extern "C" int dqmc_update_slice_final(dqmc_ctx* c, int k, int thermalization, int proposal, int adapt, int adapt_scale_variance, int repeat,
+                                       int then_wrap_dir) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    (void)hipSetDevice(c->p.device);
+    if (then_wrap_dir != 0 && then_wrap_dir != DQMC_DOWN) return fail(DQMC_EINVAL, "updateInSlice: then_wrap_dir must be 0 or DQMC_DOWN");
+    const bool skip = !c->pipelined && !c->hm.hubbard;
+    // k in 1 .. m and currentTimeslice == k (update_slice_run refuses anything else before it launches): wrapDown's own checks hold
+    int rc = update_slice_run(c, k, thermalization, proposal, adapt, adapt_scale_variance, repeat, skip);
+    if (rc) return rc;
+    if (!skip) return then_wrap_dir == DQMC_DOWN ? dqmc_wrap(c, DQMC_DOWN, k) : DQMC_OK;
+    if (then_wrap_dir == DQMC_DOWN) c->currentTimeslice = k - 1;
+    c->g_stale = true;
+    return DQMC_OK;
 }
 
 extern "C" int dqmc_get_schedule_info(dqmc_ctx* c, dqmc_schedule_info* out) {
@@ -1367,6 +1401,22 @@ extern "C" int dqmc_bmult_host(dqmc_ctx* c, int side, int inverse, int k2, int k
     HIPCHK(hipMemcpyAsync(A, selp(c, c->T1), n2 * sizeof(cplx), hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
     return finish(c, "dqmc_bmult_host");
+}
+// out of place: source in T3, destination T1 filled with NaN bit patterns first (nothing of its old content may enter the result)
+extern "C" int dqmc_bmult_src_host(dqmc_ctx* c, int side, int inverse, int k2, int k1, const dqmc_cplx* src, dqmc_cplx* out, dqmc_cplx* src_after) {
+    if (!c || !src || !out) return fail(DQMC_EINVAL, "null argument");
+    (void)hipSetDevice(c->p.device);
+    if (!(k2 > k1) || k2 > c->m || k1 < 0) return fail(DQMC_EINVAL, "need 0 <= k1 < k2 <= m");
+    const size_t n2 = (size_t)c->n_g * c->n_g;
+    for (int b = 0; b < c->nb; ++b) {
+        HIPCHK(hipMemcpyAsync(chainp(c, c->T3, b), src, n2 * sizeof(cplx), hipMemcpyHostToDevice, c->st));
+        HIPCHK(hipMemsetAsync(chainp(c, c->T1, b), 0xff, n2 * sizeof(cplx), c->st));
+    }
+    bmult_dev(c, side, inverse, k2, k1, c->T1, c->T3);
+    HIPCHK(hipMemcpyAsync(out, selp(c, c->T1), n2 * sizeof(cplx), hipMemcpyDeviceToHost, c->st));
+    if (src_after) HIPCHK(hipMemcpyAsync(src_after, selp(c, c->T3), n2 * sizeof(cplx), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    return finish(c, "dqmc_bmult_src_host");
 }
 
 extern "C" int dqmc_udv_decompose_host(dqmc_ctx* c, const dqmc_cplx* M, dqmc_cplx* U, double* d, dqmc_cplx* V_t,

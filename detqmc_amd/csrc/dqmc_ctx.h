@@ -287,7 +287,7 @@ struct ProfScope {
 // building blocks of dqmc_context.hip that the measurement entry points use
 DQMC_PRIVATE GemmArgs gemm_square(dqmc_ctx* c, const cplx* A, int opA, const cplx* B, int opB, cplx* C);
 DQMC_PRIVATE void run_gemm(dqmc_ctx* c, const GemmArgs& g);
-DQMC_PRIVATE void bmult_dev(dqmc_ctx* c, int side, int inverse, int k2, int k1, cplx* A);
+DQMC_PRIVATE void bmult_dev(dqmc_ctx* c, int side, int inverse, int k2, int k1, cplx* A, const cplx* src = nullptr);
 DQMC_PRIVATE void series_free(dqmc_ctx* c);
 DQMC_PRIVATE void custom_pair_free(dqmc_ctx* c);            // dqmc_measure_api.hip: the blocks of dqmc_set_custom_pair_operators
 DQMC_PRIVATE void custom_free(dqmc_ctx* c);                 // dqmc_measure_api.hip: the blocks of dqmc_set_custom_bilinears

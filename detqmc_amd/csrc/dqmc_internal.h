@@ -154,7 +154,29 @@ struct DevUpdateState {
 // ---- launchers (implemented in the kernels_*.hip files) ---------------------------------------
 // checkerboard chain: A <- prod B_k A etc. for k = kfirst, kfirst+kstep, ... (count slices)
 void launch_bmult(const Launch& lc, const DevModel* dm, const DevModel& hm, int side, int inverse,
-                  int kfirst, int kstep, int kcount, cplx* A, int lda, int shift = 0);   // shift: half-step hopping passes only
+                  int kfirst, int kstep, int kcount, cplx* A, int lda, int shift = 0,    // shift: half-step hopping passes only
+                  const cplx* Asrc = nullptr);   // Asrc: out of place -- the operands are read from Asrc (layout and lda of A), A is only written
+
+// A matrix that is read where it lies instead of being copied first: column j of it is X[:, col] * scale[col] with col = idx ? idx[j] : j
+// (idx == nullptr: the columns in place; scale == nullptr: 1).  k_gather_scale_cols and, with the identity, k_permute_scale_cols write
+// exactly these values; a kernel that takes a ColSrc forms them with col_src_value, the same single multiply per component.
+// X == nullptr: no source.  All three pointers are per-chain buffers.
+struct ColSrc { const cplx* X; int ld; const int* idx; const double* scale; };
+// the source of the columns from j0 on
+static inline ColSrc col_src_from(const ColSrc& s, int j0) {
+    ColSrc r = s;
+    if (!r.X) return r;
+    if (r.idx) r.idx += j0;
+    else { r.X += (size_t)j0 * r.ld; if (r.scale) r.scale += j0; }
+    return r;
+}
+#ifdef __HIPCC__
+// v * s, never contracted into a neighbouring add: the value equals the one a copy kernel would have stored
+__device__ __forceinline__ cplx col_src_value(cplx v, double s) {
+#pragma clang fp contract(off)
+    return make_double2(v.x * s, v.y * s);
+}
+#endif
 
 // C = alpha-less complex GEMM on MFMA f64: C[MxN] (+)= op(A)[MxK] . diag(kscale) . op(B)[KxN]
 struct GemmArgs {
@@ -179,6 +201,8 @@ struct GemmArgs {
     size_t part_count;          // capacity of part in complex numbers (0: eight slices of M x N, the round-3 contract)
     int tag;                    // 1: a product inside a factorisation (LU trailing update, triangular solve) -- same code, its own kernel
                                 // name (template argument), so that profiles keep it apart from the model's n_g^3 products
+    ColSrc csrc;                // with accumulate: the old value of C(i, j) is column j of this source instead of what C holds (C is only
+                                // written: the first touch of a destination that a scaled / gathered copy used to fill).  Not with split-K
 };
 void launch_gemm(const Launch& lc, const GemmArgs& a);
 // the same with the kernel path named: -1 what launch_gemm does, 0 the generic kernel, 1 the whole-tile kernel where the arguments
@@ -191,7 +215,8 @@ GemmPlan gemm_plan(const GemmArgs& a, int nb);
 // G += X GrT^T, K = min(Kmax, *Kdev * Kmul): the delayed-update flush as a register-only read-modify-write stream.  X and GrT are
 // n x K8 (K8 = K rounded up to a multiple of 8, columns K .. K8 - 1 zero), both with leading dimension ld
 void launch_flush(const Launch& lc, const cplx* X, const cplx* GrT, int ld, cplx* G, int ldc, int n, int Kmax,
-                  const int* Kdev, int Kmul, int tag = 0);    // G (n x n) += X GrT^T, K = min(Kmax, *Kdev * Kmul) (Kdev may be null); tag 1: own kernel name
+                  const int* Kdev, int Kmul, int tag = 0,     // G (n x n) += X GrT^T, K = min(Kmax, *Kdev * Kmul) (Kdev may be null); tag 1: own kernel name
+                  const int* skip = nullptr);                 // skip (per chain, may be null): nothing is done for a chain whose *skip != 0
 
 // one-sided Jacobi SVD, M = U diag(d) V^H, d descending.  work: A (n*n), V (n*n), norms(n), rank(n),
 // flag (int).  Host-driven sweep loop with one flag read-back per sweep.  Returns sweeps used or <0.
@@ -229,7 +254,7 @@ void launch_update_decide(const Launch& lc, const DevModel* dm, const DevModel& 
 void launch_update_window(const Launch& lc, const DevModel& hm, DevUpdateState* us, const cplx* G, const cplx* X, const cplx* GrT,
                           cplx* Gw, int P);
 void launch_update_gather(const Launch& lc, const DevModel& hm, const DevUpdateState* us, const cplx* G,
-                          const cplx* W, cplx* X, cplx* GrT);
+                          const cplx* W, cplx* X, cplx* GrT, int skip_done = 0);     // skip_done: nothing for a chain whose slice_done is set
 
 // Hubbard replica (kernels_hubbard.hip)
 void launch_hubbard_vscale(const Launch& lc, const DevModel& hm, int side, int inverse, int k, cplx* A, int lda);
@@ -371,7 +396,8 @@ int run_qr_apply_q(const Launch& lc, int n, cplx* C, const QrWork& w, int trans)
 // large n: QR by block Gram-Schmidt with reorthogonalisation + Cholesky-QR2 panels, all on the GEMM kernel (kernels_qr.hip); Q is always explicit
 int run_qr_bgs(const Launch& lc, int n, cplx* A, cplx* Q, const QrWork& w);
 void qr_reset_workspace(const Launch& lc, int n, const QrWork& w);      // zero w.V / w.T before Householder panels follow a block Gram-Schmidt run
-int run_trsm_right_upper(const Launch& lc, int n, const cplx* R, cplx* C, const QrWork& w, int trans = 0, int unit = 0);   // C <- C R^-1 (trans: R = (stored lower triangle)^H; unit: unit diagonal)
+int run_trsm_right_upper(const Launch& lc, int n, const cplx* R, cplx* C, const QrWork& w, int trans = 0, int unit = 0,     // C <- C R^-1 (trans: R = (stored lower triangle)^H; unit: unit diagonal)
+                         const ColSrc* src = nullptr);   // src: C <- S R^-1 with the right-hand side S read from the column source (ld n, not C itself); C is only written
 // (the diagonal reciprocals are scale-safe, cplx_recip: a diagonal entry outside ~ [1e-154, 1e154] is no special case)
 #define LU_SWAP_INTS 128
 // pivot search and multipliers are scale-safe: LU of 2^k A has the pivots and L of A and U scaled by 2^k, also where |a|^2 leaves

@@ -256,7 +256,9 @@ int DetSDW::uniformsPerSite() const {
 }
 
 // which proposal / adaptation this sweep uses (updateInSlice, updateInSliceThermalization: detsdwopdim.cpp:2438-2470, 3299-3321)
-void DetSDW::updateInSlice(Group& g, int k, bool thermalization) {
+// Last slice of a segment outside measurement sweeps (measure(k) reads G right after the update), sequential update schedule:
+// dqmc_update_slice_final leaves out the flush nobody reads and, in a down sweep, does the bookkeeping of the dead wrap as well.
+bool DetSDW::updateInSlice(Group& g, int k, bool thermalization, bool segmentEnd, bool down) {
     const detsdw_params& p = ch_[0].pars;
     int proposal = DQMC_PROPOSE_BOX, adapt = DQMC_ADAPT_BOX;
     if (p.spinProposalMethod == 1) {                       // rotate_then_scale: each sweep alternates between rotating and scaling
@@ -266,8 +268,18 @@ void DetSDW::updateInSlice(Group& g, int k, bool thermalization) {
         proposal = DQMC_PROPOSE_ROTATE_AND_SCALE;
         adapt = (performedSweeps_ % 200 < 100) ? DQMC_ADAPT_ROTATE : DQMC_ADAPT_SCALE;
     }
+    if (segmentEnd && !measuring_) {
+        dqmc_schedule_info si;
+        check(dqmc_get_schedule_info(g.ctx, &si), "dqmc_get_schedule_info");
+        if (!si.pipelined) {
+            check(dqmc_update_slice_final(g.ctx, k, thermalization ? 1 : 0, proposal, adapt, p.adaptScaleVariance, p.repeatUpdateInSlice,
+                                          down ? DQMC_DOWN : 0), "updateInSlice");
+            return down;
+        }
+    }
     check(dqmc_update_slice_ex(g.ctx, k, thermalization ? 1 : 0, proposal, adapt, p.adaptScaleVariance, p.repeatUpdateInSlice), "updateInSlice");
     if (measuring_) check(dqmc_measure_slice(g.ctx), "measure");     // updateInSliceAndMaybeMeasure (detmodel.h:1279-1285)
+    return false;
 }
 
 // the advance just made ended on the interior boundary tau_j = j s: it also computed G(tau_j, 0)
@@ -292,16 +304,19 @@ void DetSDW::measureTimeDisplacedEnds(Group& g) {
 void DetSDW::sweepDown(Group& g, bool thermalization) {
     dqmc_ctx* ctx_ = g.ctx;
     // the last wrap of every segment is dead: the advance that follows rebuilds G from the UdV factors (dqmc_wrap_skip)
+    // ... and so is the last flush of the segment's last slice (dqmc_update_slice_final, which then does the dead wrap's bookkeeping)
     for (int k = m_; k >= (n_ - 1) * s_ + 1; --k) {
-        updateInSlice(g, k, thermalization);
-        check(k > (n_ - 1) * s_ + 1 ? dqmc_wrap(ctx_, DQMC_DOWN, k) : dqmc_wrap_skip(ctx_, DQMC_DOWN, k), "wrapDownGreen");
+        const bool last = k == (n_ - 1) * s_ + 1;
+        if (updateInSlice(g, k, thermalization, last, true)) continue;
+        check(!last ? dqmc_wrap(ctx_, DQMC_DOWN, k) : dqmc_wrap_skip(ctx_, DQMC_DOWN, k), "wrapDownGreen");
     }
     for (int l = n_ - 1; l >= 1; --l) {
         check(dqmc_advance(ctx_, DQMC_DOWN, l + 1), "advanceDownGreen");
         measureTimeDisplaced(g, l);
         for (int k = l * s_; k >= (l - 1) * s_ + 1; --k) {
-            updateInSlice(g, k, thermalization);
-            check(k > (l - 1) * s_ + 1 ? dqmc_wrap(ctx_, DQMC_DOWN, k) : dqmc_wrap_skip(ctx_, DQMC_DOWN, k), "wrapDownGreen");
+            const bool last = k == (l - 1) * s_ + 1;
+            if (updateInSlice(g, k, thermalization, last, true)) continue;
+            check(!last ? dqmc_wrap(ctx_, DQMC_DOWN, k) : dqmc_wrap_skip(ctx_, DQMC_DOWN, k), "wrapDownGreen");
         }
     }
     check(dqmc_advance(ctx_, DQMC_DOWN, 1), "advanceDownGreen");
@@ -315,14 +330,14 @@ void DetSDW::sweepUp(Group& g, bool thermalization) {
     for (int l = 0; l <= n_ - 2; ++l) {
         for (int k = l * s_ + 1; k <= (l + 1) * s_; ++k) {
             check(dqmc_wrap(ctx_, DQMC_UP, k - 1), "wrapUpGreen");
-            updateInSlice(g, k, thermalization);
+            updateInSlice(g, k, thermalization, k == (l + 1) * s_);
         }
         check(dqmc_advance(ctx_, DQMC_UP, l), "advanceUpGreen");
         measureTimeDisplaced(g, l + 1);
     }
     for (int k = (n_ - 1) * s_ + 1; k <= m_; ++k) {
         check(dqmc_wrap(ctx_, DQMC_UP, k - 1), "wrapUpGreen");
-        updateInSlice(g, k, thermalization);
+        updateInSlice(g, k, thermalization, k == m_);
     }
     check(dqmc_advance(ctx_, DQMC_UP, n_ - 1), "advanceUpGreen");
     measureTimeDisplacedEnds(g);

@@ -192,7 +192,8 @@ private:
     void measureTimeDisplacedEnds(Group& g);
     void sweepDown(Group& g, bool thermalization);
     void sweepUp(Group& g, bool thermalization);
-    void updateInSlice(Group& g, int k, bool thermalization);
+    // segmentEnd: the advance that follows rebuilds G (last slice of a segment).  Returns true when it took the wrap of a down sweep along
+    bool updateInSlice(Group& g, int k, bool thermalization, bool segmentEnd = false, bool down = false);
     int uniformsPerSite() const;
 public:
     void exchangeActionsDevice(double* out_dev);        // out_dev[chain], device memory

@@ -61,9 +61,10 @@ __device__ __forceinline__ void build_V(cplx (&V)[MSF][MSF], double sign, double
 // CDW: cdwU != 0 (the discrete field's terms in e^{dtau V}); a template parameter so that the cdwU == 0 kernels are the round-2 code
 template<int MSF, bool RIGHT, bool INV, bool CDW>
 __global__ __launch_bounds__(512, MSF == 2 ? 4 : 2) void k_bmult_chain(DevModel dm, cplx* __restrict__ A, int lda, int nvec,
-                                                      int kfirst, int kstep, int kcount, int shift, size_t cs) {
+                                                      int kfirst, int kstep, int kcount, int shift, size_t cs, const cplx* Asrc) {
     extern __shared__ cplx sm[];
-    dm = chain_model(dm, cs); CHAIN(A);
+    dm = chain_model(dm, cs); CHAIN(A); CHAIN(Asrc);
+    const cplx* const Ain = Asrc ? Asrc : A;      // out of place: the operands come from Asrc (same layout and lda), the result goes to A
     const int N = dm.N, ng = dm.ng, P = dm.P;
     const int v0 = blockIdx.x * nvec;
     const int nv = min(nvec, ng - v0);
@@ -84,7 +85,7 @@ __global__ __launch_bounds__(512, MSF == 2 ? 4 : 2) void k_bmult_chain(DevModel 
     constexpr int SB = 8;
     if (!RIGHT) {
         const int total = nv * ng;
-        const cplx* src = A + (size_t)v0 * lda;
+        const cplx* src = Ain + (size_t)v0 * lda;
         for (int base = tid; base < total; base += SB * nth) {
             cplx r[SB];
 #pragma unroll
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(512, MSF == 2 ? 4 : 2) void k_bmult_chain(DevModel 
 #pragma unroll
             for (int u = 0; u < SB; ++u) {
                 la[u] = (base + u * nth < total && v < nv) ? e * rstride + v : -1;
-                r[u] = nt_load(A + (size_t)min(e, ng - 1) * lda + (v0 + min(v, nv - 1)));
+                r[u] = nt_load(Ain + (size_t)min(e, ng - 1) * lda + (v0 + min(v, nv - 1)));
                 v += rvd; e += red;
                 if (v >= nvec) { v -= nvec; e += 1; }
             }
@@ -461,9 +462,10 @@ __device__ __forceinline__ void direct_plaq_step(const DevModel& dm, int sub, in
 // register budget: that of k_bmult_chain with the real tables; the complex-table instantiations get that of two waves per SIMD
 template<int MSF, bool RIGHT, bool INV, bool CDW, bool REALT>
 __global__ __launch_bounds__(512, (MSF == 2 && REALT) ? 4 : 2) void k_bmult_direct(DevModel dm, cplx* __restrict__ A, int lda, int nvec,
-                                                       int kfirst, int kstep, int kcount, size_t cs) {
+                                                       int kfirst, int kstep, int kcount, size_t cs, const cplx* Asrc) {
     extern __shared__ cplx sm[];
-    dm = chain_model(dm, cs); CHAIN(A);
+    dm = chain_model(dm, cs); CHAIN(A); CHAIN(Asrc);
+    const char* const Ain = (const char*)(Asrc ? Asrc : A);      // out of place: the first pass reads Asrc (same layout and lda)
     const int N = dm.N, ng = dm.ng, P = dm.P;
     const int v0 = blockIdx.x * nvec;
     const int nv = min(nvec, ng - v0);
@@ -478,6 +480,10 @@ __global__ __launch_bounds__(512, (MSF == 2 && REALT) ? 4 : 2) void k_bmult_dire
         const unsigned el = RIGHT ? (unsigned)e * (unsigned)lda + (unsigned)(v0 + v) : (unsigned)(v0 + v) * (unsigned)lda + (unsigned)e;
         return (cplx*)((char*)A + (size_t)(el * 16u));
     };
+    auto gsrc = [&](int v, int e) -> const cplx* {
+        const unsigned el = RIGHT ? (unsigned)e * (unsigned)lda + (unsigned)(v0 + v) : (unsigned)(v0 + v) * (unsigned)lda + (unsigned)e;
+        return (const cplx*)(Ain + (size_t)(el * 16u));
+    };
     constexpr bool PASSES_FIRST = (RIGHT == INV);   // left B, right B^-1: hopping part acts first
     // items (p, v).  RIGHT: v fastest over the lanes -- the lanes of a tile row are one 128-byte piece of a column, the global
     // access shape of the staging loops of k_bmult_chain.  LEFT: p fastest -- with the x-fastest plaquette order the corners
@@ -490,7 +496,7 @@ __global__ __launch_bounds__(512, (MSF == 2 && REALT) ? 4 : 2) void k_bmult_dire
     };
 
     // ---- first pass: global -> sub-1 half step (after e^{-+dtau V} of the first slice where that acts first) -> LDS ----
-    // in place is safe: the tile belongs to this workgroup alone and every global load precedes the first barrier, every
+    // in place (Asrc == nullptr) is safe: the tile belongs to this workgroup alone and every global load precedes the first barrier, every
     // global store follows it
     for (int idx = tid; idx < items; idx += nth) {
         int p, v, site[4];
@@ -499,7 +505,7 @@ __global__ __launch_bounds__(512, (MSF == 2 && REALT) ? 4 : 2) void k_bmult_dire
 #pragma unroll
         for (int b = 0; b < MSF; ++b)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) x[b][q] = nt_load(gptr(v, b * N + site[q]));      // all requested before the first use
+            for (int q = 0; q < 4; ++q) x[b][q] = nt_load(gsrc(v, b * N + site[q]));      // all requested before the first use
         if (!PASSES_FIRST) direct_site_mix<MSF, RIGHT, INV, CDW>(dm, kfirst, site, x);
         direct_plaq_step<MSF, RIGHT, INV, REALT>(dm, 1, p, x);
 #pragma unroll
@@ -575,7 +581,7 @@ static bool bmult_use_direct(const DevModel& hm, int side, int kcount, int shift
 }
 
 void launch_bmult(const Launch& lc, const DevModel* /*dm*/, const DevModel& hm, int side, int inverse,
-                  int kfirst, int kstep, int kcount, cplx* A, int lda, int shift) {
+                  int kfirst, int kstep, int kcount, cplx* A, int lda, int shift, const cplx* Asrc) {
     const int ng = hm.ng;
     const bool direct = bmult_use_direct(hm, side, kcount, shift, lda);
     // LEFT: <= 64 KiB of LDS; RIGHT: up to 144 KiB (one workgroup per CU then, two below 80 KiB) so that a row tile can be
@@ -628,14 +634,14 @@ void launch_bmult(const Launch& lc, const DevModel* /*dm*/, const DevModel& hm, 
     const int nthreads = (side == DQMC_LEFT) ? 256 : (env_t ? env_t : (nvec >= 8 ? 512 : 256));
     // the direct path keeps the tile shapes, LDS footprint and thread counts of the rule above
 #define LAUNCH_DT(MSFV, R, I, C, T) hipLaunchKernelGGL((k_bmult_direct<MSFV, R, I, C, T>), dim3(grid, 1, lc.nb), dim3(nthreads), lds, lc.st, hm, A, lda, \
-                                                      nvec, kfirst, kstep, kcount, lc.cs)
+                                                      nvec, kfirst, kstep, kcount, lc.cs, Asrc)
 #define LAUNCH_D(MSFV, R, I, C) do { if (hm.pm_real || MSFV == 4) LAUNCH_DT(MSFV, R, I, C, true); else LAUNCH_DT(2, R, I, C, false); } while (0)
 #define LAUNCH(MSFV, R, I)                                                                              \
     do { if (direct) { if (hm.cdw_on) LAUNCH_D(MSFV, R, I, true); else LAUNCH_D(MSFV, R, I, false); }   \
          else if (hm.cdw_on) hipLaunchKernelGGL((k_bmult_chain<MSFV, R, I, true>), dim3(grid, 1, lc.nb), dim3(nthreads), lds, lc.st, hm, A, lda, nvec, \
-                                           kfirst, kstep, kcount, shift, lc.cs);                        \
+                                           kfirst, kstep, kcount, shift, lc.cs, Asrc);                        \
          else hipLaunchKernelGGL((k_bmult_chain<MSFV, R, I, false>), dim3(grid, 1, lc.nb), dim3(nthreads), lds, lc.st, hm, A, lda, nvec, \
-                                 kfirst, kstep, kcount, shift, lc.cs); } while (0)
+                                 kfirst, kstep, kcount, shift, lc.cs, Asrc); } while (0)
     if (hm.MSF == 2) {
         if (side == DQMC_LEFT) { if (!inverse) LAUNCH(2, false, false); else LAUNCH(2, false, true); }
         else                   { if (!inverse) LAUNCH(2, true, false);  else LAUNCH(2, true, true); }

@@ -50,6 +50,7 @@ __global__ __launch_bounds__(256, 2) void k_zgemm(GemmArgs g, size_t cs, int nb)
     if constexpr (!FULL) { g.Kdev = chain_ptr_i(g.Kdev, cs, chain); g.kscale = chain_ptr_i(g.kscale, cs, chain); }
     g.rowscale = chain_ptr_i(g.rowscale, cs, chain); g.colscale = chain_ptr_i(g.colscale, cs, chain);
     g.a_kgather = chain_ptr_i(g.a_kgather, cs, chain);
+    g.csrc.X = chain_ptr_i(g.csrc.X, cs, chain); g.csrc.idx = chain_ptr_i(g.csrc.idx, cs, chain); g.csrc.scale = chain_ptr_i(g.csrc.scale, cs, chain);
 
     int K = g.K;
     if (!FULL && g.Kdev) { int kd = (*g.Kdev) * g.Kmul; K = kd < K ? kd : K; }
@@ -316,7 +317,19 @@ __global__ __launch_bounds__(256, 2) void k_zgemm(GemmArgs g, size_t cs, int nb)
             const int gi = i0 + wm * 16 * TM + a * 16 + l15;
             const int gic = FULL ? gi : min(gi, Mm1);
             cplx cold[4];
-            if (g.accumulate) {                                    // the four loads together, bounds by select (see gload)
+            if (g.accumulate && g.csrc.X) {                        // first touch of C: its old value is read from the column source (uniform per launch)
+                int col[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int gj = j0 + wn * 16 * TN + b * 16 + l4 + 4 * r;
+                    const int gjc = FULL ? gj : min(gj, Nm1);
+                    col[r] = g.csrc.idx ? g.csrc.idx[gjc] : gjc;
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) cold[r] = g.csrc.X[(size_t)col[r] * g.csrc.ld + gic];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) cold[r] = col_src_value(cold[r], g.csrc.scale ? g.csrc.scale[col[r]] : 1.0);
+            } else if (g.accumulate) {                             // the four loads together, bounds by select (see gload)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int gj = j0 + wn * 16 * TN + b * 16 + l4 + 4 * r;
@@ -360,11 +373,13 @@ __global__ __launch_bounds__(256, 2) void k_zgemm(GemmArgs g, size_t cs, int nb)
 template<bool M3, bool FULL, int STAGE, int TAG>
 __global__ __launch_bounds__(256, (FULL && STAGE == 1) ? 3 : 2) void k_flush(const cplx* __restrict__ X, const cplx* __restrict__ GrT, int ld,
                                                   cplx* __restrict__ G, int ldc, int n, int Kmax, const int* __restrict__ Kdev,
-                                                  int Kmul, size_t cs, int nb) {
+                                                  int Kmul, size_t cs, int nb, const int* __restrict__ skip) {
     const int tn = (n + 63) / 64;
     int chain, tile;
     xcd_chain_tile(tn * tn, nb, chain, tile);
     X = chain_ptr_i(X, cs, chain); GrT = chain_ptr_i(GrT, cs, chain); G = chain_ptr_i(G, cs, chain); Kdev = chain_ptr_i(Kdev, cs, chain);
+    skip = chain_ptr_i(skip, cs, chain);
+    if (skip && *skip) return;                    // uniform over the workgroup: this chain's update has no reader (launch_flush)
     int K = Kmax;
     if (Kdev) { int kd = (*Kdev) * Kmul; K = kd < K ? kd : K; }
     if (K <= 0) return;
@@ -533,7 +548,7 @@ __global__ __launch_bounds__(256, (FULL && STAGE == 1) ? 3 : 2) void k_flush(con
 template<int TAG>
 __global__ __launch_bounds__(256, 2) void k_flush_lds(const cplx* __restrict__ X, const cplx* __restrict__ GrT, int ld,
                                                        cplx* __restrict__ G, int ldc, int n, int Kmax, const int* __restrict__ Kdev,
-                                                       int Kmul, size_t cs, int nb) {
+                                                       int Kmul, size_t cs, int nb, const int* __restrict__ skip) {
     extern __shared__ cplx flush_sm[];            // Xs[FLUSH_KH][64], Gs[FLUSH_KH][64]
     cplx* Xs = flush_sm;
     cplx* Gs = flush_sm + FLUSH_KH * 64;
@@ -541,6 +556,8 @@ __global__ __launch_bounds__(256, 2) void k_flush_lds(const cplx* __restrict__ X
     int chain, tile;
     xcd_chain_tile(tn * tn, nb, chain, tile);
     X = chain_ptr_i(X, cs, chain); GrT = chain_ptr_i(GrT, cs, chain); G = chain_ptr_i(G, cs, chain); Kdev = chain_ptr_i(Kdev, cs, chain);
+    skip = chain_ptr_i(skip, cs, chain);
+    if (skip && *skip) return;                    // uniform over the workgroup: this chain's update has no reader (launch_flush)
     int K = Kmax;
     if (Kdev) { int kd = (*Kdev) * Kmul; K = kd < K ? kd : K; }
     if (K <= 0) return;                                               // uniform over the workgroup
@@ -645,23 +662,23 @@ static bool use_4m() {
 }
 
 static void launch_flush_impl(const Launch& lc, const cplx* X, const cplx* GrT, int ld, cplx* G, int ldc, int n, int Kmax,
-                              const int* Kdev, int Kmul, int tag);
+                              const int* Kdev, int Kmul, int tag, const int* skip);
 void launch_flush(const Launch& lc, const cplx* X, const cplx* GrT, int ld, cplx* G, int ldc, int n, int Kmax,
-                  const int* Kdev, int Kmul, int tag) {
+                  const int* Kdev, int Kmul, int tag, const int* skip) {
     const bool sub = tag && lc.sub;
     if (sub) lc.sub->begin(lc.sub->user, SUBFAM_LU_UPDATE);
-    launch_flush_impl(lc, X, GrT, ld, G, ldc, n, Kmax, Kdev, Kmul, tag);
+    launch_flush_impl(lc, X, GrT, ld, G, ldc, n, Kmax, Kdev, Kmul, tag, skip);
     if (sub) lc.sub->end(lc.sub->user, SUBFAM_LU_UPDATE, 8.0 * n * n * Kmax * lc.nb, 16.0 * (2.0 * n * n + 2.0 * n * Kmax) * lc.nb);
 }
 static void launch_flush_impl(const Launch& lc, const cplx* X, const cplx* GrT, int ld, cplx* G, int ldc, int n, int Kmax,
-                              const int* Kdev, int Kmul, int tag) {
+                              const int* Kdev, int Kmul, int tag, const int* skip) {
     const int tn = (n + 63) / 64;
     const dim3 grid = (lc.nb % 8 == 0) ? dim3(tn * tn * lc.nb, 1, 1) : dim3(tn * tn, 1, lc.nb);
     static const bool force_ragged = dev_knob("DQMC_FLUSH_RAGGED") && atoi(dev_knob("DQMC_FLUSH_RAGGED")) != 0;   // developer knob (A/B)
     const bool full = n % 32 == 0 && !force_ragged;
     static const int stage = dev_knob("DQMC_FLUSH_STAGE") ? atoi(dev_knob("DQMC_FLUSH_STAGE")) : 1;                 // developer knob (A/B)
-#define FLUSH_LAUNCH(M3_, FULL_, ST_) do { if (tag) hipLaunchKernelGGL((k_flush<M3_, FULL_, ST_, 1>), grid, dim3(256), 0, lc.st, X, GrT, ld, G, ldc, n, Kmax, Kdev, Kmul, lc.cs, lc.nb); \
-                                           else hipLaunchKernelGGL((k_flush<M3_, FULL_, ST_, 0>), grid, dim3(256), 0, lc.st, X, GrT, ld, G, ldc, n, Kmax, Kdev, Kmul, lc.cs, lc.nb); } while (0)
+#define FLUSH_LAUNCH(M3_, FULL_, ST_) do { if (tag) hipLaunchKernelGGL((k_flush<M3_, FULL_, ST_, 1>), grid, dim3(256), 0, lc.st, X, GrT, ld, G, ldc, n, Kmax, Kdev, Kmul, lc.cs, lc.nb, skip); \
+                                           else hipLaunchKernelGGL((k_flush<M3_, FULL_, ST_, 0>), grid, dim3(256), 0, lc.st, X, GrT, ld, G, ldc, n, Kmax, Kdev, Kmul, lc.cs, lc.nb, skip); } while (0)
     static const bool flush_4m = dev_knob("DQMC_FLUSH_4M") && atoi(dev_knob("DQMC_FLUSH_4M")) != 0;               // developer knob (A/B): 4 MFMAs, 122 registers, 4 workgroups per CU
     static const bool flush_reg = dev_knob("DQMC_FLUSH_LDS") && atoi(dev_knob("DQMC_FLUSH_LDS")) == 0;            // developer knob (A/B): the register-fragment kernel of round 3
     // K <= 32 (delay depth <= 16 for O(1) / O(2), <= 8 for O(3); the LU's trailing updates): one LDS phase, 187 against 216 us per launch of
@@ -684,8 +701,8 @@ static void launch_flush_impl(const Launch& lc, const cplx* X, const cplx* GrT, 
                 else (void)hipGetLastError();      // the launch below then reports the problem
             }
         }
-        if (tag) hipLaunchKernelGGL((k_flush_lds<1>), grid, dim3(256), lds, lc.st, X, GrT, ld, G, ldc, n, Kmax, Kdev, Kmul, lc.cs, lc.nb);
-        else     hipLaunchKernelGGL((k_flush_lds<0>), grid, dim3(256), lds, lc.st, X, GrT, ld, G, ldc, n, Kmax, Kdev, Kmul, lc.cs, lc.nb);
+        if (tag) hipLaunchKernelGGL((k_flush_lds<1>), grid, dim3(256), lds, lc.st, X, GrT, ld, G, ldc, n, Kmax, Kdev, Kmul, lc.cs, lc.nb, skip);
+        else     hipLaunchKernelGGL((k_flush_lds<0>), grid, dim3(256), lds, lc.st, X, GrT, ld, G, ldc, n, Kmax, Kdev, Kmul, lc.cs, lc.nb, skip);
         return;
     }
     if (use_4m() || flush_4m) { if (full) FLUSH_LAUNCH(false, true, 1); else FLUSH_LAUNCH(false, false, 1); }

@@ -773,10 +773,12 @@ int run_qr_apply_q(const Launch& lc, int n, cplx* C, const QrWork& w, int trans)
 // ---------------------------------------------------------------------------------------------
 #define TRSM_NB 32
 // trans: the triangular matrix is the conjugate transpose of the stored LOWER triangle; unit: its diagonal is 1 (not read)
+// S.X != nullptr: the block is touched for the first time -- its right-hand side is read from the column source S (dqmc_internal.h)
+// instead of C, which is only written
 __global__ __launch_bounds__(256) void k_trsm_block(cplx* __restrict__ C, int ldc, const cplx* __restrict__ R, int ldr,
-                                                     int n, int j0, int nb, int trans, int unit, size_t cs) {
+                                                     int n, int j0, int nb, int trans, int unit, size_t cs, ColSrc S) {
     __shared__ cplx sR[TRSM_NB][TRSM_NB + 1];
-    CHAIN(C); CHAIN(R);
+    CHAIN(C); CHAIN(R); CHAIN(S.X); CHAIN(S.idx); CHAIN(S.scale);
     for (int i = threadIdx.x; i < TRSM_NB * TRSM_NB; i += 256) {
         int r = i % TRSM_NB, c = i / TRSM_NB;
         cplx v = make_double2(0.0, 0.0);
@@ -796,8 +798,18 @@ __global__ __launch_bounds__(256) void k_trsm_block(cplx* __restrict__ C, int ld
     cplx y[TRSM_NB];
     // all 32 loads go out together: clamped column instead of a select on the loaded value (which compiles to a branch around the
     // load and a wait behind it: 66 s_waitcnt vmcnt(0) for 34 loads before); columns >= nb are loaded but never used
+    if (S.X) {
+        int col[TRSM_NB];
 #pragma unroll
-    for (int c = 0; c < TRSM_NB; ++c) y[c] = C[(size_t)(j0 + min(c, nb - 1)) * ldc + row];
+        for (int c = 0; c < TRSM_NB; ++c) { const int jc = j0 + min(c, nb - 1); col[c] = S.idx ? S.idx[jc] : jc; }
+#pragma unroll
+        for (int c = 0; c < TRSM_NB; ++c) y[c] = S.X[(size_t)col[c] * S.ld + row];
+#pragma unroll
+        for (int c = 0; c < TRSM_NB; ++c) y[c] = col_src_value(y[c], S.scale ? S.scale[col[c]] : 1.0);
+    } else {
+#pragma unroll
+        for (int c = 0; c < TRSM_NB; ++c) y[c] = C[(size_t)(j0 + min(c, nb - 1)) * ldc + row];
+    }
 #pragma unroll
     for (int c = 0; c < TRSM_NB; ++c) {
         if (c < nb) {
@@ -830,26 +842,33 @@ __global__ void k_negate_copy_block(const cplx* __restrict__ R, int ldr, int row
 // recursive halving: the solve for columns [j0, j0 + len) once everything left of j0 has been subtracted.  The updates are then
 // ONE product per level and half (N = K = 256, 128, 64, 32 at n = 512) instead of fifteen with N = 32 and K up to 480: the same
 // multiply-adds on 64 x 64 tiles, which read half the operand bytes of the 32 x 32 ones.
-static int trsm_rec(const Launch& lc, int n, const cplx* R, cplx* C, int j0, int len, int trans, int unit) {
+// src (the right-hand side lies elsewhere, scaled / gathered by columns: ColSrc, indexed like C) is given on the left spine of the
+// recursion only, j0 == 0.  Every column block of C is touched for the first time there and nowhere else: columns [0, 32) by
+// k_trsm_block, every further block [h, len) as the accumulate input of this level's product.
+static int trsm_rec(const Launch& lc, int n, const cplx* R, cplx* C, int j0, int len, int trans, int unit, const ColSrc* src = nullptr) {
+    const ColSrc none = ColSrc();
     if (len <= TRSM_NB) {
-        hipLaunchKernelGGL(k_trsm_block, dim3((n + 255) / 256, 1, lc.nb), dim3(256), 0, lc.st, C, n, R, n, n, j0, len, trans, unit, lc.cs);
+        hipLaunchKernelGGL(k_trsm_block, dim3((n + 255) / 256, 1, lc.nb), dim3(256), 0, lc.st, C, n, R, n, n, j0, len, trans, unit, lc.cs,
+                           src ? col_src_from(*src, j0) : none);
         return 1;
     }
     const int h = ((len / 2 + TRSM_NB - 1) / TRSM_NB) * TRSM_NB;
-    int launches = trsm_rec(lc, n, R, C, j0, h, trans, unit);
+    int launches = trsm_rec(lc, n, R, C, j0, h, trans, unit, src);
     // C[:, j0 + h .. j0 + len) -= Y[:, j0 .. j0 + h) R[j0 .. j0 + h, j0 + h .. j0 + len)
     GemmArgs g = GemmArgs();
     g.A = C + (size_t)j0 * n; g.lda = n; g.opA = 0; g.C = C + (size_t)(j0 + h) * n; g.ldc = n;
     if (trans) { g.B = R + (size_t)j0 * n + (j0 + h); g.ldb = n; g.opB = 1; }          // (L^H)[J1, J2] = conj(L[J2, J1])^T
     else       { g.B = R + (size_t)(j0 + h) * n + j0; g.ldb = n; g.opB = 0; }
     g.M = n; g.N = len - h; g.K = h; g.Kmul = 1; g.accumulate = 1; g.negate = 1; g.tag = 1;
+    if (src) g.csrc = col_src_from(*src, j0 + h);
     launch_gemm(lc, g);
     launches += 1;
     return launches + trsm_rec(lc, n, R, C, j0 + h, len - h, trans, unit);
 }
-int run_trsm_right_upper(const Launch& lc, int n, const cplx* R, cplx* C, const QrWork& w, int trans, int unit) {
+int run_trsm_right_upper(const Launch& lc, int n, const cplx* R, cplx* C, const QrWork& w, int trans, int unit, const ColSrc* src) {
     (void)w;
-    return trsm_rec(lc, n, R, C, 0, n, trans, unit);
+    if (src && (!src->X || src->X == C)) src = nullptr;
+    return trsm_rec(lc, n, R, C, 0, n, trans, unit, src);
 }
 
 // ---------------------------------------------------------------------------------------------

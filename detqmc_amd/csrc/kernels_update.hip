@@ -1075,14 +1075,17 @@ typedef double u_v4d __attribute__((ext_vector_type(4)));
 #define GATHER_MAXSPAN 2048
 __global__ __launch_bounds__(256, 2) void k_update_gather(DevModel dm, const DevUpdateState* __restrict__ us,
                                                            const cplx* __restrict__ G, const cplx* __restrict__ Wg,
-                                                           cplx* __restrict__ X, cplx* __restrict__ GrT, size_t cs) {
+                                                           cplx* __restrict__ X, cplx* __restrict__ GrT, size_t cs, int skip_done) {
     CHAIN(us); CHAIN(G); CHAIN(Wg); CHAIN(X); CHAIN(GrT);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // skip_done: a chain that finished its slice in this round has no reader for the block's flush (dqmc_update_slice_final), so
+    // X and GrT are not formed either
+    const int sdone = us->slice_done;
     // ONE round trip for the block's bookkeeping: the count and all DQMC_MAX_WDIM site slots are requested together (slots >= j hold
     // sites of earlier blocks and are never used); round 3 before: count -> first / last site -> the list, three dependent trips
     const int j = us->block_j;
     const int mysite = us->block_sites[tid & (DQMC_MAX_WDIM - 1)];
-    if (j <= 0) return;
+    if (j <= 0 || (skip_done && sdone)) return;
     const int MSF = dm.MSF, N = dm.N, ng = dm.ng, WD = MSF * dm.D;
     const int nI = MSF * j, nI8 = (nI + 7) & ~7;
     __shared__ int ssite[DQMC_MAX_WDIM];
@@ -1229,6 +1232,6 @@ void launch_update_window(const Launch& lc, const DevModel& hm, DevUpdateState* 
 }
 
 void launch_update_gather(const Launch& lc, const DevModel& hm, const DevUpdateState* us, const cplx* G,
-                          const cplx* W, cplx* X, cplx* GrT) {
-    hipLaunchKernelGGL(k_update_gather, dim3((hm.ng + 31) / 32, 1, lc.nb), dim3(256), 0, lc.st, hm, us, G, W, X, GrT, lc.cs);
+                          const cplx* W, cplx* X, cplx* GrT, int skip_done) {
+    hipLaunchKernelGGL(k_update_gather, dim3((hm.ng + 31) / 32, 1, lc.nb), dim3(256), 0, lc.st, hm, us, G, W, X, GrT, lc.cs, skip_done);
 }

@@ -125,6 +125,27 @@ int dqmc_prim_trsm(void* arena, size_t bytes, int nb, size_t cs, int n, long lon
     });
 }
 
+// C <- S R^-1 with the right-hand side S = columns of X (n x n, ld n), scaled and gathered: idx n ints (< 0: none), scale n doubles (< 0:
+// none).  how 0: k_gather_scale_cols writes S into C (S[:, j] = X[:, idx[j]] scale[idx[j]]; idx required), then the solve in place;
+// how 1: k_permute_scale_cols (S[:, idx[j]] = X[:, j] scale[j]), then the solve in place; how 2: no copy -- the solve reads S through its
+// first-touch column source, gather form (ColSrc), and only writes C
+int dqmc_prim_trsm_src(void* arena, size_t bytes, int nb, size_t cs, int n, long long R, long long C, int trans, int unit,
+                       long long X, long long idx, long long scale, int how, char* msg, int msglen) {
+    return with_arena(arena, bytes, nb, cs, msg, msglen, [&](void* d, const Launch& lc) {
+        QrWork w = QrWork();
+        const cplx* x = at<const cplx>(d, X);
+        const int* ix = at<const int>(d, idx);
+        const double* sc = at<const double>(d, scale);
+        if (how == 2) {
+            const ColSrc src = {x, n, ix, sc};
+            return run_trsm_right_upper(lc, n, at<const cplx>(d, R), at<cplx>(d, C), w, trans, unit, &src);
+        }
+        if (how == 0) { if (!ix) return -2; launch_gather_scale_cols(lc, x, sc, ix, n, at<cplx>(d, C)); }
+        else launch_permute_scale_cols(lc, x, sc, ix, n, at<cplx>(d, C));
+        return run_trsm_right_upper(lc, n, at<const cplx>(d, R), at<cplx>(d, C), w, trans, unit);
+    });
+}
+
 // Householder QR: A -> R in place, Q explicit (Q < 0: reflectors only); V (n * n) and T (ceil(n / 16) * 512 complex) zero on entry.
 // C >= 0: afterwards C <- Q C (apply_trans 0) or Q^H C (1) from the reflectors (run_qr_apply_q).
 int dqmc_prim_qr(void* arena, size_t bytes, int nb, size_t cs, int n, long long A, long long Q, long long V, long long T,

@@ -746,6 +746,13 @@ class KernelContext:
         check(self.lib.dqmc_bmult_host(self.h, side, int(inverse), k2, k1, a.ctypes.data))
         return a
 
+    def bmult_src(self, side, inverse, k2, k1, A):
+        """dqmc_bmult_src_host: the same product out of place; returns (result, the source buffer as it is afterwards)"""
+        a = _fmat(A)
+        out, after = np.zeros_like(a), np.zeros_like(a)
+        check(self.lib.dqmc_bmult_src_host(self.h, side, int(inverse), k2, k1, a.ctypes.data, out.ctypes.data, after.ctypes.data))
+        return out, after
+
     def leftMultiplyBmat(self, A, k2, k1):
         return self.bmult(LEFT, 0, k2, k1, A)
 
@@ -803,6 +810,12 @@ class KernelContext:
     def updateInSlice(self, k, thermalization=False, proposal="box", adapt="box", adaptScaleVariance=False, repeat=1):
         """updateInSlice / updateInSliceThermalization; proposal: box | rotate | scale | rotate_and_scale (the latter three: O(3))"""
         check(self.lib.dqmc_update_slice_ex(self.h, k, int(thermalization), PROPOSE[proposal], ADAPT[adapt], int(adaptScaleVariance), int(repeat)))
+
+    def updateInSliceFinal(self, k, thermalization=False, proposal="box", adapt="box", adaptScaleVariance=False, repeat=1, thenWrap=0):
+        """dqmc_update_slice_final: updateInSlice of the last slice of a segment -- the block in which a chain finishes the slice is
+        not flushed, G is stale until the advance that follows; thenWrap: 0, or DOWN for the bookkeeping of wrapDownGreen(k) as well"""
+        check(self.lib.dqmc_update_slice_final(self.h, k, int(thermalization), PROPOSE[proposal], ADAPT[adapt], int(adaptScaleVariance),
+                                               int(repeat), int(thenWrap)))
 
     def update_state(self):
         st = _lib.dqmc_update_state()

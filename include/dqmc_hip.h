@@ -195,6 +195,10 @@ int dqmc_get_fields_all_host(dqmc_ctx* ctx, double* phi_all);
  * checkerboard{Left,Right}MultiplyBmat[Inv] (detsdwopdim.cpp:2076-2090, 2172-2186, 2307-2324,
  * 2406-2420), i.e. the four callables of sweep_skeleton (detmodel.h:256-260). */
 int dqmc_bmult_host(dqmc_ctx* ctx, int side, int inverse, int k2, int k1, dqmc_cplx* A);
+/* The same out of place, as the chain steps of dqmc_advance (DQMC_UP) and dqmc_udv_setup run it: out = B(k2,k1) src etc.; the device
+ * kernel reads its operands from a source buffer and writes another.  src_after (may be NULL) receives the source buffer as it is
+ * afterwards: unchanged. */
+int dqmc_bmult_src_host(dqmc_ctx* ctx, int side, int inverse, int k2, int k1, const dqmc_cplx* src, dqmc_cplx* out, dqmc_cplx* src_after);
 
 /* ---- UdV decomposition and dense products (a2, L1) ---------------------------------------- */
 /* udvDecompose (udv.h:68-102): M = U diag(d) V_t^H, d descending */
@@ -240,6 +244,15 @@ int dqmc_update_slice(dqmc_ctx* ctx, int k, int thermalization);
 enum { DQMC_PROPOSE_BOX = 0, DQMC_PROPOSE_ROTATE = 1, DQMC_PROPOSE_SCALE = 2, DQMC_PROPOSE_ROTATE_AND_SCALE = 3 };
 enum { DQMC_ADAPT_BOX = 0, DQMC_ADAPT_ROTATE = 1, DQMC_ADAPT_SCALE = 2 };
 int dqmc_update_slice_ex(dqmc_ctx* ctx, int k, int thermalization, int proposal, int adapt, int adapt_scale_variance, int repeat);
+/* The update of the LAST slice of a segment, whose G nobody reads: the dqmc_advance that follows rebuilds G from the UdV factors.  The
+ * same decisions as dqmc_update_slice_ex (fields, update state, counters bit for bit), but in the last pass over the slice a chain does
+ * not gather and flush the delayed-update block in which it finishes the slice.  G is marked stale as after dqmc_wrap_skip (every
+ * entry that reads G returns DQMC_EINVAL until dqmc_advance, dqmc_udv_setup or dqmc_set_green_host rebuild it).  then_wrap_dir: 0, or
+ * DQMC_DOWN to take the checks and the currentTimeslice bookkeeping of the down wrap of slice k along (dqmc_wrap_skip itself refuses a
+ * stale G).  A refused call changes nothing.  Where the block cannot be skipped (pipelined schedule, Hubbard replica) this is
+ * dqmc_update_slice_ex followed by dqmc_wrap for DQMC_DOWN, and G stays fresh. */
+int dqmc_update_slice_final(dqmc_ctx* ctx, int k, int thermalization, int proposal, int adapt, int adapt_scale_variance, int repeat,
+                            int then_wrap_dir);
 /* Which schedule dqmc_update_slice runs for this context (latched at dqmc_create from dqmc_tuning::pipeline and the shape of the
  * context) and how many delayed-update blocks have gone through each since dqmc_create. */
 typedef struct dqmc_schedule_info {
