@@ -32,6 +32,7 @@ DETSDW_FM_EQ_BAND = 0x200         # flag bit of detsdw_params.fermionMeasurement
 DQMC_SERIES_MATS_BAND, DQMC_SERIES_EQ_BAND = 128, 256   # parts of dqmc_series_begin: Matsubara transform of channel 4, equal-time band block
 DQMC_SERIES_MATS_CUSTOM, DQMC_SERIES_EQ_CUSTOM = 512, 1024   # ... Matsubara transform of channel 5, equal-time block of the custom bilinears
 DQMC_SERIES_MATS_CUSTOM_PAIR, DQMC_SERIES_EQ_CUSTOM_PAIR = 2048, 4096   # ... Matsubara transform of channel 6, equal-time block of the custom pair operators
+DQMC_SERIES_GREEN_MATRIX = 8192    # ... the normalised averaged Green's function of every slice (dqmc_set_green_matrix)
 DQMC_CUSTOM_MAX = 4               # matrices of dqmc_set_custom_bilinears at most
 
 
@@ -257,6 +258,10 @@ SYMBOLS = [
     ("dqmc_set_equal_time_custom_pair", C.c_int, [_P, C.c_int]),
     ("dqmc_measure_eq_custom_pair_accum_size", C.c_size_t, [_P]),
     ("dqmc_measure_eq_custom_pair_read_host", C.c_int, [_P, _DP]),
+    ("dqmc_set_green_matrix", C.c_int, [_P, C.c_int]),
+    ("dqmc_measure_timedisplaced_green_matrix", C.c_int, [_P, C.c_int]),
+    ("dqmc_measure_td_green_matrix_accum_size", C.c_size_t, [_P]),
+    ("dqmc_measure_td_green_matrix_read_host", C.c_int, [_P, _DP]),
     ("dqmc_measure_timedisplaced_segment", C.c_int, [_P, C.c_int]),
     ("dqmc_measure_timedisplaced_ends", C.c_int, [_P]),
     ("dqmc_measure_td_fine_accum_size", C.c_size_t, [_P, C.c_int]),
@@ -277,6 +282,8 @@ SYMBOLS = [
     ("dqmc_series_band_derived_host", C.c_int, [_P, _DP, _DP]),
     ("dqmc_series_custom_derived_host", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
     ("dqmc_series_custom_pair_derived_host", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
+    ("dqmc_series_pair_vertex_size", C.c_size_t, [_P]),
+    ("dqmc_series_pair_vertex_host", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
     ("dqmc_series_end", C.c_int, [_P]),
     ("dqmc_series_configure", C.c_int, [_P, C.c_int]),
     ("dqmc_series_get_state", C.c_int, [_P, C.POINTER(dqmc_series_state)]),
@@ -319,6 +326,8 @@ SYMBOLS = [
     ("detsdw_set_custom_pair_operators", C.c_int, [_P, C.c_int, _P, _P, _P]),
     ("detsdw_get_custom_pair_operators", C.c_int, [_P, C.POINTER(C.c_int), _P, _P, _P]),
     ("detsdw_series_custom_pair_derived", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _DP, _DP]),
+    ("detsdw_set_green_matrix", C.c_int, [_P, C.c_int]),
+    ("detsdw_series_pair_vertex", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _DP, _DP]),
     ("detsdw_series_read_bins", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _DP]),
     ("detsdw_series_end", C.c_int, [_P]),
     ("detsdw_series_configure", C.c_int, [_P, C.c_int]),

@@ -623,8 +623,9 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
 
 void series_free(dqmc_ctx* c) {
     dqmc_ctx::Series& s = c->ser;
-    for (double* q : {s.sample, s.openbin, s.bins, s.bad, s.trig, s.stat, s.var, s.binning}) if (q) (void)hipFree(q);
+    for (double* q : {s.sample, s.openbin, s.bins, s.bad, s.trig, s.stat, s.var, s.binning, s.vertex}) if (q) (void)hipFree(q);
     if (s.srctab) (void)hipFree((void*)s.srctab);
+    if (s.vertex_tab) (void)hipFree(s.vertex_tab);
     s = dqmc_ctx::Series{};
 }
 
@@ -636,6 +637,7 @@ extern "C" void dqmc_destroy(dqmc_ctx* c) {
     if (c->mats_out) (void)hipFree(c->mats_out);
     custom_free(c);
     custom_pair_free(c);
+    green_matrix_free(c);
     series_free(c);
     if (c->jacobi_graph) (void)hipGraphExecDestroy(c->jacobi_graph);
     if (c->sw.hflag) (void)hipHostFree(c->sw.hflag);

@@ -38,9 +38,9 @@ enum { FAM_BMULT = DQMC_FAM_BMULT, FAM_GEMM = DQMC_FAM_GEMM, FAM_JACOBI = DQMC_F
 // channels, the four every-slice ones (channel ch at ACC_FINE0 + ch, as ACC_TD + ch for the coarse ones) and the equal-time correlators;
 // channel 4 of both families and ACC_EQ_BAND are the band-resolved charge blocks (DQMC_TD_PH_BAND, dqmc_set_equal_time_band), channel 5
 // and ACC_EQ_CUSTOM the blocks of the user-defined bilinears (dqmc_set_custom_bilinears), channel 6 and ACC_EQ_CUSTOM_PAIR those of the
-// user-defined pair operators (dqmc_set_custom_pair_operators)
-enum { TD_CHANNELS = 7 };
-enum { ACC_SLICE, ACC_TD, ACC_TD_PAIR, ACC_TD_PH, ACC_TD_CUR, ACC_TD_BAND, ACC_TD_CUSTOM, ACC_TD_CUSTOM_PAIR, ACC_FINE0,
+// user-defined pair operators (dqmc_set_custom_pair_operators), channel 7 the averaged Green's function block (dqmc_set_green_matrix)
+enum { TD_CHANNELS = 8 };
+enum { ACC_SLICE, ACC_TD, ACC_TD_PAIR, ACC_TD_PH, ACC_TD_CUR, ACC_TD_BAND, ACC_TD_CUSTOM, ACC_TD_CUSTOM_PAIR, ACC_TD_GREEN_MATRIX, ACC_FINE0,
        ACC_EQ = ACC_FINE0 + TD_CHANNELS, ACC_EQ_BAND, ACC_EQ_CUSTOM, ACC_EQ_CUSTOM_PAIR, ACC_COUNT };
 // n: doubles per chain, 0 while the context has no such block; chain b starts at (char*)p + b * stride (the arena's chain stride; the
 // equal-time blocks and every block of the user-defined bilinears and pair operators live outside the arena as [chain][n]); missing: what a read of an absent
@@ -89,7 +89,8 @@ struct dqmc_ctx {
         {nullptr, 0, 0, "context created without DQMC_TD_PH_BAND"},
         {nullptr, 0, 0, "no user-defined bilinear is set (dqmc_set_custom_bilinears), or the context was created without dqmc_params::td_particle_hole"},
         {nullptr, 0, 0, "no user-defined pair operator is set (dqmc_set_custom_pair_operators), or the context was created without dqmc_params::timedisplaced"},
-        {nullptr, 0, 0, "no every-slice block for this channel"},
+        {nullptr, 0, 0, "the averaged Green's function block is switched off (dqmc_set_green_matrix)"},
+        {nullptr, 0, 0, "no every-slice block for this channel"}, {nullptr, 0, 0, "no every-slice block for this channel"},
         {nullptr, 0, 0, "no every-slice block for this channel"}, {nullptr, 0, 0, "no every-slice block for this channel"},
         {nullptr, 0, 0, "no every-slice block for this channel"}, {nullptr, 0, 0, "no every-slice block for this channel"},
         {nullptr, 0, 0, "no every-slice block for this channel"}, {nullptr, 0, 0, "no every-slice block for this channel"},
@@ -145,8 +146,11 @@ struct dqmc_ctx {
     unsigned cpr_mask[DQMC_CUSTOM_MAX] = {};
     bool eqp_on = false, cpr_bond_on = false;
     CustomPair cpr_bond = {};
+    // dqmc_set_green_matrix: while on, the blocks ACC_TD_GREEN_MATRIX [chain][(n-1)(1 + 2 R^2 N)] and its every-slice twin (channel 7),
+    // outside the arena, allocated by the switch-on and freed by the switch-off
+    bool gm_on = false;
     // dqmc_series_*: the measurement series.  Device buffers outside the arena, allocated by dqmc_series_begin and freed by dqmc_series_end
-    // or with the context: sample [nb][S], open bin [nb][S], closed bins [max_bins][nb][S], the per-part flags [11][nb], the cos / sin table
+    // or with the context: sample [nb][S], open bin [nb][S], closed bins [max_bins][nb][S], the per-part flags [12][nb], the cos / sin table
     // (2 pi j / L [2 L]; with the order-parameter part, index 6 of off / len, also 2 pi j / m [2 m] behind it) and the result buffer
     // of the statistics calls (mean, err [nb][S] each, then value, err [nb][6] each).  The counters live on the host.
     // srctab [nb]: the source rows of dqmc_series_accumulate, filled from srchost before every launch; formed: the sample buffer holds
@@ -156,11 +160,15 @@ struct dqmc_ctx {
         int bin_size = 0, max_bins = 0, nfreq = 0, parts = 0, closed = 0, in_open = 0;
         int flags = 0;                                        // DQMC_SERIES_AUTO_REBIN | DQMC_SERIES_TRACK_VARIANCE (dqmc_series_configure)
         long long samples = 0, rebins = 0;                    // accumulates since begin / merges of neighbouring bins so far
-        size_t S = 0, off[13] = {}, len[13] = {};              // index = bit number; 5 is never used
+        size_t S = 0, off[14] = {}, len[14] = {};              // index = bit number; 5 is never used
         double *sample = nullptr, *openbin = nullptr, *bins = nullptr, *bad = nullptr, *trig = nullptr, *stat = nullptr;
         double *var = nullptr;                                // running mean w [nb][S], then m2 [nb][S]: allocated with TRACK_VARIANCE
         double *binning = nullptr;                            // result of dqmc_series_binning_host, err then tau [levels][nb][S] each,
         size_t binning_cap = 0;                               // allocated on first use and grown on demand (doubles)
+        double *vertex = nullptr;                             // dqmc_series_pair_vertex_host: the per-row bubbles and the results;
+        size_t vertex_cap = 0;                                // allocated on first use and grown on demand (doubles)
+        void *vertex_tab = nullptr;                           // ... its operator table and masks while no operator has a bond part (else
+        CustomPair vertex_pair = {};                          // the measurement kernels' table serves): built by the first call
         const double** srctab = nullptr;
         std::vector<const double*> srchost;
     } ser;
@@ -289,5 +297,6 @@ DQMC_PRIVATE GemmArgs gemm_square(dqmc_ctx* c, const cplx* A, int opA, const cpl
 DQMC_PRIVATE void run_gemm(dqmc_ctx* c, const GemmArgs& g);
 DQMC_PRIVATE void bmult_dev(dqmc_ctx* c, int side, int inverse, int k2, int k1, cplx* A, const cplx* src = nullptr);
 DQMC_PRIVATE void series_free(dqmc_ctx* c);
+DQMC_PRIVATE void green_matrix_free(dqmc_ctx* c);           // dqmc_measure_api.hip: the blocks of dqmc_set_green_matrix
 DQMC_PRIVATE void custom_pair_free(dqmc_ctx* c);            // dqmc_measure_api.hip: the blocks of dqmc_set_custom_pair_operators
 DQMC_PRIVATE void custom_free(dqmc_ctx* c);                 // dqmc_measure_api.hip: the blocks of dqmc_set_custom_bilinears

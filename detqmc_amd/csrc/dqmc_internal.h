@@ -384,6 +384,17 @@ struct CustomPair { const cplx* tab; const unsigned* mk; unsigned parts[DQMC_CUS
 size_t measure_custom_pair_table_cplx(int count, int N);
 void launch_measure_custom_pair(const Launch& lc, const DevModel& hm, int count, const cplx* Fa, const unsigned* mask, const cplx* gs, double* acc,
                                 size_t acs, int row, int rows, const CustomPair* pair = nullptr);
+// the averaged Green's function block (dqmc_set_green_matrix): row `row` of `rows` of a block count[rows], then rows [N][R][R] (re, im), from
+// the shifted g~(tau,0); sample part 13 of the series from the every-slice block; bubble and vertex of the pair operators from the closed
+// bins (pair: the stencil table of every set operator; pb: nb (B + 1)(m + 1) count doubles of scratch; value, err [nb][count][5 + m])
+size_t measure_green_matrix_row_doubles(int opdim, int N);
+void launch_measure_green_matrix(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc, size_t acs, int row, int rows, int apbx, int apby);
+void launch_series_green_sample(const Launch& lc, const DevModel& hm, const double* fine, size_t chain_bytes, double* sample, size_t S, size_t off,
+                                double* bad);
+size_t series_pair_bubble_lds_bytes(int opdim, int N);
+bool launch_series_pair_vertex(const Launch& lc, const DevModel& hm, const double* bins, const double* mean, const double* trig, size_t S, int B,
+                               int nfreq, size_t off_chi, size_t off_g, int count, const CustomPair& pair, int qx, int qy, int apbx, int apby,
+                               double* pb, double* value, double* err);
 size_t measure_custom_row_doubles(int count, int N);
 size_t measure_td_custom_onebody_cplx(int count, int N);
 size_t measure_eq_custom_onebody_cplx(int count, int N);

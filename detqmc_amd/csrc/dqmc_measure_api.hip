@@ -329,6 +329,34 @@ void custom_pair_free(dqmc_ctx* c) {
     c->cpr_count = 0;
     c->eqp_on = false;
 }
+// the device table of the stencil kernel on the host (CustomPair in dqmc_internal.h): per operator and block 0, x, y the forms F, conj F,
+// F^H, then the link signs; mk the non-zero masks, pair.parts the blocks an operator has
+static void custom_pair_table(const dqmc_ctx* c, int count, const dqmc_cplx* F0, const dqmc_cplx* Fx, const dqmc_cplx* Fy, std::vector<cplx>& tab,
+                              std::vector<unsigned>& mk, CustomPair& pair) {
+    tab.assign(measure_custom_pair_table_cplx(count, c->N), make_double2(0.0, 0.0));
+    mk.assign((size_t)count * 6, 0u);
+    const dqmc_cplx zero{0.0, 0.0};
+    for (int ch = 0; ch < count; ++ch)
+        for (int k = 0; k < 3; ++k) {
+            const dqmc_cplx* src = k == 0 ? F0 : k == 1 ? Fx : Fy;
+            cplx* v = tab.data() + ((size_t)ch * 3 + k) * 48;
+            unsigned bits = 0, bits_h = 0;
+            for (int a = 0; a < 4; ++a)
+                for (int b = 0; b < 4; ++b) {
+                    const dqmc_cplx f = src ? src[16 * ch + 4 * a + b] : zero, ft = src ? src[16 * ch + 4 * b + a] : zero;
+                    v[4 * a + b] = make_double2(f.re, f.im);
+                    v[16 + 4 * a + b] = make_double2(f.re, -f.im);
+                    v[32 + 4 * a + b] = make_double2(ft.re, -ft.im);
+                    if (f.re != 0.0 || f.im != 0.0) bits |= 1u << (4 * a + b);
+                    if (ft.re != 0.0 || ft.im != 0.0) bits_h |= 1u << (4 * a + b);
+                }
+            mk[((size_t)ch * 3 + k) * 2] = bits; mk[((size_t)ch * 3 + k) * 2 + 1] = bits_h;
+            if (bits) pair.parts[ch] |= 1u << k;
+        }
+    cplx* lk = tab.data() + (size_t)count * 144;
+    for (int mu = 0; mu < 2; ++mu)
+        for (int site = 0; site < c->N; ++site) lk[(size_t)mu * c->N + site] = custom_link(c->p, mu, site);     // no flux here: +-1
+}
 extern "C" int dqmc_set_custom_pair_operators(dqmc_ctx* c, int count, const dqmc_cplx* F0, const dqmc_cplx* Fx, const dqmc_cplx* Fy) {
     const std::string who = "dqmc_set_custom_pair_operators";
     if (!c) return fail(DQMC_EINVAL, "null ctx");
@@ -363,33 +391,10 @@ extern "C" int dqmc_set_custom_pair_operators(dqmc_ctx* c, int count, const dqmc
     const size_t nb = (size_t)c->nb, row = measure_custom_row_doubles(count, c->N);
     const size_t n_eq = count ? 1 + row : 0, n_td = count && c->td_reserved ? (size_t)(c->n - 1) * (1 + row) : 0;
     const size_t n_fine = n_td && c->td_fine ? (size_t)(c->m + 1) * (1 + row) : 0;
-    // the device table of the stencil kernel: per operator and block 0, x, y the forms F, conj F, F^H, then the link signs
-    std::vector<cplx> tab(bonds ? measure_custom_pair_table_cplx(count, c->N) : 0);
-    std::vector<unsigned> mk(bonds ? (size_t)count * 6 : 0);
+    std::vector<cplx> tab;
+    std::vector<unsigned> mk;
     CustomPair pair{};
-    if (bonds) {
-        const dqmc_cplx zero{0.0, 0.0};
-        for (int ch = 0; ch < count; ++ch)
-            for (int k = 0; k < 3; ++k) {
-                const dqmc_cplx* src = k == 0 ? F0 : k == 1 ? Fx : Fy;
-                cplx* v = tab.data() + ((size_t)ch * 3 + k) * 48;
-                unsigned bits = 0, bits_h = 0;
-                for (int a = 0; a < 4; ++a)
-                    for (int b = 0; b < 4; ++b) {
-                        const dqmc_cplx f = src ? src[16 * ch + 4 * a + b] : zero, ft = src ? src[16 * ch + 4 * b + a] : zero;
-                        v[4 * a + b] = make_double2(f.re, f.im);
-                        v[16 + 4 * a + b] = make_double2(f.re, -f.im);
-                        v[32 + 4 * a + b] = make_double2(ft.re, -ft.im);
-                        if (f.re != 0.0 || f.im != 0.0) bits |= 1u << (4 * a + b);
-                        if (ft.re != 0.0 || ft.im != 0.0) bits_h |= 1u << (4 * a + b);
-                    }
-                mk[((size_t)ch * 3 + k) * 2] = bits; mk[((size_t)ch * 3 + k) * 2 + 1] = bits_h;
-                if (bits) pair.parts[ch] |= 1u << k;
-            }
-        cplx* lk = tab.data() + (size_t)count * 144;
-        for (int mu = 0; mu < 2; ++mu)
-            for (int site = 0; site < c->N; ++site) lk[(size_t)mu * c->N + site] = custom_link(c->p, mu, site);     // no flux here: +-1
-    }
+    if (bonds) custom_pair_table(c, count, F0, Fx, Fy, tab, mk, pair);
     double *eq = nullptr, *td = nullptr, *fine = nullptr;
     cplx* dtab = nullptr;
     unsigned* dmk = nullptr;
@@ -457,6 +462,52 @@ extern "C" int dqmc_set_equal_time_custom_pair(dqmc_ctx* c, int on) {
 }
 extern "C" size_t dqmc_measure_eq_custom_pair_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_EQ_CUSTOM_PAIR); }
 extern "C" int dqmc_measure_eq_custom_pair_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_EQ_CUSTOM_PAIR, out); }
+// the averaged Green's function block (dqmc_hip.h): run-time state like the operators above
+void green_matrix_free(dqmc_ctx* c) {
+    for (AccBlock* a : {&c->acc[ACC_TD_GREEN_MATRIX], &c->acc[ACC_FINE0 + 7]}) {
+        if (a->p) (void)hipFree(a->p);
+        a->p = nullptr; a->n = 0;
+    }
+    c->gm_on = false;
+}
+extern "C" int dqmc_set_green_matrix(dqmc_ctx* c, int on) {
+    const std::string who = "dqmc_set_green_matrix";
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (c->hm.hubbard) return fail(DQMC_EINVAL, "the averaged Green's function block belongs to the SDW model");
+    if (!on) {
+        if (c->ser.open && (c->ser.parts & DQMC_SERIES_GREEN_MATRIX))
+            return fail(DQMC_EINVAL, who + ": a measurement series with the part of the averaged Green's function is open");
+        if (!c->gm_on) return DQMC_OK;
+        (void)hipSetDevice(c->p.device);
+        HIPCHK(hipStreamSynchronize(c->st));               // nothing enqueued still uses the blocks
+        green_matrix_free(c);
+        return DQMC_OK;
+    }
+    if (c->p.weakZflux)
+        return fail(DQMC_EINVAL, who + ": with weakZflux <G> is invariant under magnetic translations only: the block has no gauge-independent "
+                    "definition under the flux");
+    if (!c->td_reserved) return fail(DQMC_EINVAL, who + ": needs a context created with dqmc_params::timedisplaced >= 1");
+    if (c->gm_on) return DQMC_OK;
+    (void)hipSetDevice(c->p.device);
+    // the new buffers first: a failed allocation leaves the context as it was
+    const size_t nb = (size_t)c->nb, row = measure_green_matrix_row_doubles(c->p.opdim, c->N);
+    const size_t n_td = (size_t)(c->n - 1) * (1 + row), n_fine = c->td_fine ? (size_t)(c->m + 1) * (1 + row) : 0;
+    double *td = nullptr, *fine = nullptr;
+    hipError_t e = hipMalloc((void**)&td, n_td * nb * sizeof(double));
+    if (e == hipSuccess && n_fine) e = hipMalloc((void**)&fine, n_fine * nb * sizeof(double));
+    if (e == hipSuccess) e = hipMemsetAsync(td, 0, n_td * nb * sizeof(double), c->st);
+    if (e == hipSuccess && n_fine) e = hipMemsetAsync(fine, 0, n_fine * nb * sizeof(double), c->st);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->st);
+    if (e != hipSuccess) {
+        for (void* q : {(void*)td, (void*)fine}) if (q) (void)hipFree(q);
+        return fail(DQMC_EHIP, who + ": " + hipGetErrorString(e));
+    }
+    AccBlock &a = c->acc[ACC_TD_GREEN_MATRIX], &f = c->acc[ACC_FINE0 + 7];
+    a.p = td; a.n = n_td; a.stride = n_td * sizeof(double);
+    f.p = fine; f.n = n_fine; f.stride = n_fine * sizeof(double);
+    c->gm_on = true;
+    return DQMC_OK;
+}
 
 // ---------------------------------------------------------------------------------------------
 // time-displaced Green's functions (dqmc_hip.h; computed inside green_from_udv while td_on)
@@ -480,8 +531,11 @@ extern "C" int dqmc_get_green_timedisplaced_host(dqmc_ctx* c, dqmc_cplx* g_t0, d
     return DQMC_OK;
 }
 // ---- the channel kernels: coarse boundaries and every time slice (DQMC_TD_EVERY_SLICE) ---------------------------------------------
-enum { CH_G = 1, CH_PAIR = 2, CH_PH = 4, CH_CUR = 8, CH_BAND = 16, CH_CUSTOM = 32, CH_CUSTOM_PAIR = 64,
-       CH_TWO_BODY = CH_PH | CH_CUR | CH_BAND | CH_CUSTOM };     // bit ch of a channel mask; the pair channels need the shifted gt0 alone
+enum { CH_G = 1, CH_PAIR = 2, CH_PH = 4, CH_CUR = 8, CH_BAND = 16, CH_CUSTOM = 32, CH_CUSTOM_PAIR = 64, CH_GREEN_MATRIX = 128,
+       CH_TWO_BODY = CH_PH | CH_CUR | CH_BAND | CH_CUSTOM };     // bit ch of a channel mask; the pair channels and the averaged Green's
+                                                                 // function need the shifted gt0 alone
+static bool ser_apbx(const dqmc_ctx* c) { return c->p.bc == DQMC_BC_APBC_X || c->p.bc == DQMC_BC_APBC_XY; }
+static bool ser_apby(const dqmc_ctx* c) { return c->p.bc == DQMC_BC_APBC_Y || c->p.bc == DQMC_BC_APBC_XY; }
 // One-body values of an equal-time matrix for the masked particle-hole / current / band kernels (t = 0: tau side, 1: 0 side): one shift of g,
 // then each masked table.  g == nullptr: T1 still holds the shifted matrix of the call before.
 static void td_onebody(dqmc_ctx* c, unsigned mask, const cplx* g, int t) {
@@ -528,6 +582,11 @@ static void td_row(dqmc_ctx* c, unsigned mask, int first, int row, int rows, con
         launch_measure_custom_pair(c->lc, c->hm, c->cpr_count, c->cpr_Fa, c->cpr_mask, c->T1, a.p, a.stride / sizeof(double), row, rows,
                                    c->cpr_bond_on ? &c->cpr_bond : nullptr);
     }
+    if (mask & CH_GREEN_MATRIX) {
+        ProfScope ps(c, FAM_OTHER, 1);
+        const AccBlock& a = c->acc[first + 7];
+        launch_measure_green_matrix(c->lc, c->hm, c->T1, a.p, a.stride / sizeof(double), row, rows, ser_apbx(c), ser_apby(c));
+    }
 }
 // what every entry that works at boundary j asks for; need_current_G: the entry also reads G, which must still be G(tau_j)
 static int td_boundary_ok(dqmc_ctx* c, int j, bool need_current_G) {
@@ -555,6 +614,7 @@ extern "C" int dqmc_measure_timedisplaced_current(dqmc_ctx* c, int j) { return t
 extern "C" int dqmc_measure_timedisplaced_band(dqmc_ctx* c, int j) { return td_coarse(c, 4, j, "dqmc_measure_timedisplaced_band"); }
 extern "C" int dqmc_measure_timedisplaced_custom(dqmc_ctx* c, int j) { return td_coarse(c, 5, j, "dqmc_measure_timedisplaced_custom"); }
 extern "C" int dqmc_measure_timedisplaced_custom_pair(dqmc_ctx* c, int j) { return td_coarse(c, 6, j, "dqmc_measure_timedisplaced_custom_pair"); }
+extern "C" int dqmc_measure_timedisplaced_green_matrix(dqmc_ctx* c, int j) { return td_coarse(c, 7, j, "dqmc_measure_timedisplaced_green_matrix"); }
 extern "C" size_t dqmc_measure_td_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_TD); }
 extern "C" int dqmc_measure_td_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_TD, out); }
 extern "C" size_t dqmc_measure_td_pair_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_TD_PAIR); }
@@ -569,6 +629,8 @@ extern "C" size_t dqmc_measure_td_custom_accum_size(dqmc_ctx* c) { return acc_si
 extern "C" int dqmc_measure_td_custom_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_TD_CUSTOM, out); }
 extern "C" size_t dqmc_measure_td_custom_pair_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_TD_CUSTOM_PAIR); }
 extern "C" int dqmc_measure_td_custom_pair_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_TD_CUSTOM_PAIR, out); }
+extern "C" size_t dqmc_measure_td_green_matrix_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_TD_GREEN_MATRIX); }
+extern "C" int dqmc_measure_td_green_matrix_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_TD_GREEN_MATRIX, out); }
 extern "C" int dqmc_get_green0_timedisplaced_host(dqmc_ctx* c, dqmc_cplx* g00, int* slice) {
     if (!c || !g00 || !slice) return fail(DQMC_EINVAL, "null argument");
     if (!c->G00) return fail(DQMC_EINVAL, "context created without dqmc_params::td_particle_hole");
@@ -674,8 +736,6 @@ extern "C" int dqmc_measure_td_fine_read_host(dqmc_ctx* c, int channel, double* 
     if (!td_fine_n(c, channel)) return fail(DQMC_EINVAL, c->acc[ACC_FINE0].missing);
     return acc_read(c, ACC_FINE0 + channel, out);
 }
-static bool ser_apbx(const dqmc_ctx* c) { return c->p.bc == DQMC_BC_APBC_X || c->p.bc == DQMC_BC_APBC_XY; }
-static bool ser_apby(const dqmc_ctx* c) { return c->p.bc == DQMC_BC_APBC_Y || c->p.bc == DQMC_BC_APBC_XY; }
 static int td_ncomp(const dqmc_ctx* c, int channel) { return channel == 6 ? c->cpr_count : channel == 5 ? c->cst_count : channel == 2 ? 3 : 2; }
 // the Matsubara launch of one every-slice block; channels 5 and 6 bring their component count and their own chain stride
 static bool mats_launch(dqmc_ctx* c, int ch, int nfreq, double* out, double* bad, size_t out_chain_stride) {
@@ -683,13 +743,14 @@ static bool mats_launch(dqmc_ctx* c, int ch, int nfreq, double* out, double* bad
     return launch_td_matsubara(c->lc, c->hm, a.p, ch, nfreq, ser_apbx(c), ser_apby(c), out, bad, out_chain_stride, td_ncomp(c, ch), a.stride);
 }
 extern "C" size_t dqmc_measure_td_matsubara_size(dqmc_ctx* c, int channel, int nfreq) {
-    if (!c || !td_fine_n(c, channel) || nfreq < 1 || nfreq > c->m) return 0;
+    if (!c || channel == 7 || !td_fine_n(c, channel) || nfreq < 1 || nfreq > c->m) return 0;      // channel 7: channel 0 serves G(k, i omega_n)
     return (size_t)c->nb * td_ncomp(c, channel) * nfreq * c->N * 2;
 }
 extern "C" int dqmc_measure_td_matsubara_host(dqmc_ctx* c, int channel, int nfreq, double* out) {
     if (!c || !out) return fail(DQMC_EINVAL, "null argument");
     if (!c->td_fine) return fail(DQMC_EINVAL, "context created without DQMC_TD_EVERY_SLICE");
     if (!td_fine_n(c, channel)) return fail(DQMC_EINVAL, c->acc[ACC_FINE0].missing);
+    if (channel == 7) return fail(DQMC_EINVAL, "dqmc_measure_td_matsubara_host: the averaged Green's function block has no transform (channel 0 serves G(k, i omega_n))");
     if (nfreq < 1 || nfreq > c->m) return fail(DQMC_EINVAL, "nfreq must be in 1..m");
     (void)hipSetDevice(c->p.device);
     const size_t n_out = dqmc_measure_td_matsubara_size(c, channel, nfreq), need = n_out + (size_t)c->nb;
@@ -720,7 +781,7 @@ extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nf
     if (!c) return fail(DQMC_EINVAL, "null ctx");
     if (c->hm.hubbard) return fail(DQMC_EINVAL, "the measurement series belongs to the SDW model");
     if (c->ser.open) return fail(DQMC_EINVAL, "a measurement series is already open (dqmc_series_end)");
-    if (parts <= 0 || (parts & ~0x1fdf)) return fail(DQMC_EINVAL, "dqmc_series_begin: parts must be a non-empty mask of bits 0 .. 4 and 6 .. 12");
+    if (parts <= 0 || (parts & ~0x3fdf)) return fail(DQMC_EINVAL, "dqmc_series_begin: parts must be a non-empty mask of bits 0 .. 4 and 6 .. 13");
     if (bin_size < 1) return fail(DQMC_EINVAL, "dqmc_series_begin: bin_size must be at least 1");
     if (max_bins < 2) return fail(DQMC_EINVAL, "dqmc_series_begin: max_bins must be at least 2");
     if ((parts & 1) && !c->acc[ACC_EQ].n) return fail(DQMC_EINVAL, "dqmc_series_begin: the equal-time block has never been enabled (dqmc_set_equal_time_correlators)");
@@ -728,6 +789,8 @@ extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nf
     if ((parts & DQMC_SERIES_EQ_CUSTOM) && !c->acc[ACC_EQ_CUSTOM].n) return fail(DQMC_EINVAL, "dqmc_series_begin: no user-defined bilinear is set (dqmc_set_custom_bilinears)");
     if ((parts & (DQMC_SERIES_MATS_CUSTOM_PAIR | DQMC_SERIES_EQ_CUSTOM_PAIR)) && !c->cpr_count)
         return fail(DQMC_EINVAL, "dqmc_series_begin: no user-defined pair operator is set (dqmc_set_custom_pair_operators): the part's block is missing");
+    if ((parts & DQMC_SERIES_GREEN_MATRIX) && (!c->gm_on || !td_fine_n(c, 7)))
+        return fail(DQMC_EINVAL, "dqmc_series_begin: the averaged Green's function has no every-slice block (dqmc_set_green_matrix, DQMC_TD_EVERY_SLICE)");
     if ((parts & (1 | DQMC_SERIES_EQ_BAND | DQMC_SERIES_EQ_CUSTOM | DQMC_SERIES_EQ_CUSTOM_PAIR)) && series_eq_sample_lds_bytes(c->hm.L) > 152 * 1024)
         return fail(DQMC_EINVAL, "dqmc_series_begin: the lattice is too large for the equal-time sample kernel's LDS");
     dqmc_ctx::Series s;
@@ -767,6 +830,9 @@ extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nf
         s.off[11] = s.S; s.len[11] = (size_t)c->cpr_count * nfreq * N * 2; s.S += s.len[11];
     }
     if (parts & DQMC_SERIES_EQ_CUSTOM_PAIR) { s.off[12] = s.S; s.len[12] = (size_t)2 * c->cpr_count * N; s.S += s.len[12]; }
+    if (parts & DQMC_SERIES_GREEN_MATRIX) {                 // the averaged Green's function: behind all older parts
+        s.off[13] = s.S; s.len[13] = (size_t)(c->m + 1) * measure_green_matrix_row_doubles(c->p.opdim, c->N); s.S += s.len[13];
+    }
     s.bin_size = bin_size; s.max_bins = max_bins; s.parts = parts;
     s.nfreq = (parts & (0x1e | DQMC_SERIES_PHI | DQMC_SERIES_MATS_BAND | DQMC_SERIES_MATS_CUSTOM | DQMC_SERIES_MATS_CUSTOM_PAIR)) ? nfreq : 0;
     (void)hipSetDevice(c->p.device);
@@ -777,7 +843,7 @@ extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nf
     if (e == hipSuccess) e = hipMalloc((void**)&r.sample, n * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&r.openbin, n * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&r.bins, (size_t)max_bins * n * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&r.bad, (size_t)11 * c->nb * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&r.bad, (size_t)12 * c->nb * sizeof(double));
     const size_t mt = (parts & DQMC_SERIES_PHI) ? (size_t)c->m : 0;     // the temporal table of the order-parameter part
     if (e == hipSuccess) e = hipMalloc((void**)&r.trig, 2 * (L + mt) * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&r.stat, (2 * n + (size_t)12 * c->nb) * sizeof(double));
@@ -785,7 +851,7 @@ extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nf
     if (e == hipSuccess) e = hipMemsetAsync(r.sample, 0, n * sizeof(double), c->st);
     if (e == hipSuccess) e = hipMemsetAsync(r.openbin, 0, n * sizeof(double), c->st);
     if (e == hipSuccess) e = hipMemsetAsync(r.bins, 0, (size_t)max_bins * n * sizeof(double), c->st);
-    if (e == hipSuccess) e = hipMemsetAsync(r.bad, 0, (size_t)11 * c->nb * sizeof(double), c->st);
+    if (e == hipSuccess) e = hipMemsetAsync(r.bad, 0, (size_t)12 * c->nb * sizeof(double), c->st);
     if (e == hipSuccess) {
         // cos / sin(2 pi j / L) as finishFermionic of the host layer forms them: the device's structure factors use the same values
         std::vector<double> trig(2 * (L + mt));
@@ -808,7 +874,7 @@ extern "C" int dqmc_series_end(dqmc_ctx* c) {
 extern "C" int dqmc_series_layout(dqmc_ctx* c, int part, size_t* offset, size_t* length) {
     if (!c || !offset || !length) return fail(DQMC_EINVAL, "null argument");
     if (!c->ser.open) return fail(DQMC_EINVAL, "no measurement series is open");
-    if (part < 0 || part > 12 || !(c->ser.parts & (1 << part))) return fail(DQMC_EINVAL, "dqmc_series_layout: the part is not in the series");
+    if (part < 0 || part > 13 || !(c->ser.parts & (1 << part))) return fail(DQMC_EINVAL, "dqmc_series_layout: the part is not in the series");
     *offset = c->ser.off[part]; *length = c->ser.len[part];
     return DQMC_OK;
 }
@@ -877,6 +943,11 @@ static int series_form_sample(dqmc_ctx* c, const char* entry) {
             const AccBlock& a = c->acc[ACC_EQ_CUSTOM_PAIR];
             if (!launch_series_eq_sample(c->lc, c->hm, a.p, a.n, c->cpr_count, s.trig, s.sample, s.S, s.off[12], s.bad + (size_t)nparts * c->nb))
                 return fail(DQMC_EINVAL, who + ": the lattice is too large for the equal-time sample kernel's LDS");
+            ++nparts;
+        }
+        if (s.parts & DQMC_SERIES_GREEN_MATRIX) {
+            const AccBlock& a = c->acc[ACC_FINE0 + 7];
+            launch_series_green_sample(c->lc, c->hm, a.p, a.stride, s.sample, s.S, s.off[13], s.bad + (size_t)nparts * c->nb);
             ++nparts;
         }
         c->fam_launches[FAM_OTHER] += (uint64_t)nparts;
@@ -1058,6 +1129,66 @@ extern "C" int dqmc_series_custom_derived_host(dqmc_ctx* c, int qx, int qy, doub
 extern "C" int dqmc_series_custom_pair_derived_host(dqmc_ctx* c, int qx, int qy, double* value, double* err) {
     return series_ratio_derived(c, DQMC_SERIES_EQ_CUSTOM_PAIR, 12, c ? c->cpr_count : 0, qx, qy, value, err, "dqmc_series_custom_pair_derived_host",
                                 "pair operators");
+}
+// Bubble and vertex of every pair operator at Q = (qx, qy) (dqmc_hip.h): the bin means, then the two kernels of launch_series_pair_vertex.
+// The scratch buffer s.vertex holds the bubbles pb [nb][B + 1][m + 1][count], then value and err [nb][count][5 + m] each
+extern "C" size_t dqmc_series_pair_vertex_size(dqmc_ctx* c) {
+    if (!c || !c->ser.open || (c->ser.parts & (DQMC_SERIES_MATS_CUSTOM_PAIR | DQMC_SERIES_GREEN_MATRIX)) != (DQMC_SERIES_MATS_CUSTOM_PAIR | DQMC_SERIES_GREEN_MATRIX))
+        return 0;
+    return (size_t)c->nb * c->cpr_count * (5 + c->m);
+}
+extern "C" int dqmc_series_pair_vertex_host(dqmc_ctx* c, int qx, int qy, double* value, double* err) {
+    const std::string who = "dqmc_series_pair_vertex_host";
+    if (!c || !value || !err) return fail(DQMC_EINVAL, "null argument");
+    dqmc_ctx::Series& s = c->ser;
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (!(s.parts & DQMC_SERIES_MATS_CUSTOM_PAIR) || !(s.parts & DQMC_SERIES_GREEN_MATRIX) || s.nfreq < 1)
+        return fail(DQMC_EINVAL, who + ": the series needs the Matsubara part of the pair operators (bit 11) and the averaged Green's function (bit 13)");
+    if (qx < 0 || qx >= c->hm.L || qy < 0 || qy >= c->hm.L) return fail(DQMC_EINVAL, who + ": qx and qy must be in 0 .. L-1");
+    if (s.closed < 2) return fail(DQMC_EINVAL, who + ": the jackknife needs at least two closed bins");
+    if (series_pair_bubble_lds_bytes(c->p.opdim, c->N) > 152 * 1024) return fail(DQMC_EINVAL, who + ": the lattice is too large for the bubble kernel's LDS");
+    (void)hipSetDevice(c->p.device);
+    const int count = c->cpr_count, B = s.closed;
+    // the operator table: the measurement kernels' own while an operator has a bond part; otherwise built once per series (the
+    // operators cannot change while a series holds bit 11) and kept in an allocation of its own, the table and then its masks
+    if (!c->cpr_bond_on && !s.vertex_tab) {
+        std::vector<dqmc_cplx> F[3];
+        const cplx* src[3] = {c->cpr_F0, c->cpr_Fx, c->cpr_Fy};
+        for (int k = 0; k < 3; ++k)
+            for (int e = 0; e < 16 * count; ++e) F[k].push_back(dqmc_cplx{src[k][e].x, src[k][e].y});
+        std::vector<cplx> tab;
+        std::vector<unsigned> mk;
+        CustomPair pair{};
+        custom_pair_table(c, count, F[0].data(), F[1].data(), F[2].data(), tab, mk, pair);
+        HIPCHK(hipMalloc((void**)&s.vertex_tab, tab.size() * sizeof(cplx) + mk.size() * sizeof(unsigned)));
+        pair.tab = (const cplx*)s.vertex_tab; pair.mk = (const unsigned*)((const cplx*)s.vertex_tab + tab.size());
+        hipError_t e = copy_sync(c, s.vertex_tab, tab.data(), tab.size() * sizeof(cplx), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = copy_sync(c, (void*)pair.mk, mk.data(), mk.size() * sizeof(unsigned), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(s.vertex_tab); s.vertex_tab = nullptr; HIPCHK(e); }
+        s.vertex_pair = pair;
+    }
+    const CustomPair& pair = c->cpr_bond_on ? c->cpr_bond : s.vertex_pair;
+    const size_t n = (size_t)c->nb * s.S, n_pb = (size_t)c->nb * (B + 1) * (c->m + 1) * count, n_out = dqmc_series_pair_vertex_size(c);
+    const size_t need = n_pb + 2 * n_out;
+    if (need > s.vertex_cap) {
+        HIPCHK(hipStreamSynchronize(c->st));
+        if (s.vertex) { (void)hipFree(s.vertex); s.vertex = nullptr; s.vertex_cap = 0; }
+        HIPCHK(hipMalloc((void**)&s.vertex, need * sizeof(double)));
+        s.vertex_cap = need;
+    }
+    double *pb = s.vertex, *dv = pb + n_pb, *de = dv + n_out;
+    bool launched;
+    {
+        ProfScope ps(c, FAM_OTHER, 3);
+        launch_series_stats(c->lc, s.bins, n, B, s.stat, s.stat + n);
+        launched = launch_series_pair_vertex(c->lc, c->hm, s.bins, s.stat, s.trig, s.S, B, s.nfreq, s.off[11], s.off[13], count, pair, qx, qy,
+                                             ser_apbx(c), ser_apby(c), pb, dv, de);
+    }
+    if (!launched) return fail(DQMC_EINVAL, who + ": the lattice is too large for the bubble kernel's LDS");
+    { const int rc = finish(c, who.c_str()); if (rc != DQMC_OK) return rc; }
+    HIPCHK(copy_sync(c, value, dv, n_out * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(c, err, de, n_out * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
 }
 extern "C" int dqmc_series_phi_derived_host(dqmc_ctx* c, double* value, double* err) {
     if (!c || !value || !err) return fail(DQMC_EINVAL, "null argument");

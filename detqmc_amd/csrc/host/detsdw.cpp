@@ -292,6 +292,7 @@ void DetSDW::measureTimeDisplaced(Group& g, int j) {
     if (td_band(ch_[0].pars)) check(dqmc_measure_timedisplaced_band(g.ctx, j), "measureTimeDisplacedBand");
     if (customTd()) check(dqmc_measure_timedisplaced_custom(g.ctx, j), "measureTimeDisplacedCustom");
     if (customPairTd()) check(dqmc_measure_timedisplaced_custom_pair(g.ctx, j), "measureTimeDisplacedCustomPair");
+    if (greenMatrix_) check(dqmc_measure_timedisplaced_green_matrix(g.ctx, j), "measureTimeDisplacedGreenMatrix");
     // every slice of the boundary's segment, in the boundary's own field configuration
     if (td_every_slice(ch_[0].pars)) check(dqmc_measure_timedisplaced_segment(g.ctx, j), "measureTimeDisplacedSegment");
 }
@@ -542,13 +543,14 @@ void DetSDW::finishFermionic(int b) {
                                    : "measurement sweep did not visit every stabilisation boundary";
         // the coarse blocks' (size, read) entry points by channel; the fine blocks share one pair that takes the channel
         struct Coarse { size_t (*size)(dqmc_ctx*); int (*read)(dqmc_ctx*, double*); const char* name; };
-        static const Coarse coarse[7] = {{dqmc_measure_td_accum_size, dqmc_measure_td_read_host, "dqmc_measure_td_read_host"},
+        static const Coarse coarse[8] = {{dqmc_measure_td_accum_size, dqmc_measure_td_read_host, "dqmc_measure_td_read_host"},
                                          {dqmc_measure_td_pair_accum_size, dqmc_measure_td_pair_read_host, "dqmc_measure_td_pair_read_host"},
                                          {dqmc_measure_td_ph_accum_size, dqmc_measure_td_ph_read_host, "dqmc_measure_td_ph_read_host"},
                                          {dqmc_measure_td_current_accum_size, dqmc_measure_td_current_read_host, "dqmc_measure_td_current_read_host"},
                                          {dqmc_measure_td_band_accum_size, dqmc_measure_td_band_read_host, "dqmc_measure_td_band_read_host"},
                                          {dqmc_measure_td_custom_accum_size, dqmc_measure_td_custom_read_host, "dqmc_measure_td_custom_read_host"},
-                                         {dqmc_measure_td_custom_pair_accum_size, dqmc_measure_td_custom_pair_read_host, "dqmc_measure_td_custom_pair_read_host"}};
+                                         {dqmc_measure_td_custom_pair_accum_size, dqmc_measure_td_custom_pair_read_host, "dqmc_measure_td_custom_pair_read_host"},
+                                         {dqmc_measure_td_green_matrix_accum_size, dqmc_measure_td_green_matrix_read_host, "dqmc_measure_td_green_matrix_read_host"}};
         auto read = [&](int channel, std::vector<double>& buf) {
             buf.resize(fine ? dqmc_measure_td_fine_accum_size(ctx_, channel) : coarse[channel].size(ctx_));
             if (fine) check(dqmc_measure_td_fine_read_host(ctx_, channel, buf.data()), "dqmc_measure_td_fine_read_host");
@@ -693,6 +695,28 @@ void DetSDW::finishFermionic(int b) {
         };
         if (customTd()) fillCustom(5, customCount(), t.customTau, t.customTauQ0);
         if (customPairTd()) fillCustom(6, pairCount(), t.customPairTau, t.customPairTauQ0);
+        // the averaged Green's function (channel 7): the stored R x R block of every d expanded to the full 4 x 4 one -- OPDIM < 3: the
+        // (XDOWN, YUP) sector is the complex conjugate of the stored one, the blocks between the sectors vanish
+        if (greenMatrix_) {
+            std::vector<double> gb;
+            read(7, gb);
+            const int R = c.pars.opdim == 3 ? 4 : 2;
+            t.greenMatrixTau.assign((size_t)rows * N * 32, 0.0);
+            for (int r = 0; r < rows; ++r) {
+                const double cnt = gb[r];
+                if (cnt < 1.0) throw GeneralError(DQMC_EINVAL, missing);
+                for (int d = 0; d < N; ++d) {
+                    const double* G = &gb[rows + ((size_t)r * N + d) * 2 * R * R];
+                    double* out = &t.greenMatrixTau[((size_t)r * N + d) * 32];
+                    for (int a = 0; a < R; ++a)
+                        for (int b2 = 0; b2 < R; ++b2) {
+                            const double re = G[2 * (a * R + b2)] / (double(N) * cnt), im = G[2 * (a * R + b2) + 1] / (double(N) * cnt);
+                            out[2 * (4 * a + b2)] = re; out[2 * (4 * a + b2) + 1] = im;
+                            if (R == 2) { out[2 * (4 * (a + 2) + b2 + 2)] = re; out[2 * (4 * (a + 2) + b2 + 2) + 1] = -im; }
+                        }
+                }
+            }
+        }
     };
     if (td_level(c.pars)) fill(false, c.td);
     // timeDisplacedFineOnDevice: the fine blocks stay on the device, their reader is getMatsubara
@@ -716,7 +740,8 @@ void DetSDW::getObservableVector(int which_in, double* out, int b) const {
     const bool bandTau = which >= DETSDW_OBS_BANDDIFFTAU && which <= DETSDW_OBS_BANDMIXTAU_Q0;
     const bool customTau = which >= DETSDW_OBS_CUSTOMTAU && which < DETSDW_OBS_CUSTOMCORR;
     const bool pairTau = which >= DETSDW_OBS_CUSTOMPAIRTAU && which < DETSDW_OBS_CUSTOMPAIRCORR;
-    if (fine && (which < DETSDW_OBS_GREENKTAU_X || which > DETSDW_OBS_BONDKINETICY) && !bandTau && !customTau && !pairTau) throw ParameterWrong("unknown observable vector");
+    const bool greenMat = which == DETSDW_OBS_GREENMATRIXTAU;
+    if (fine && (which < DETSDW_OBS_GREENKTAU_X || which > DETSDW_OBS_BONDKINETICY) && !bandTau && !customTau && !pairTau && !greenMat) throw ParameterWrong("unknown observable vector");
     if (fine && !td_every_slice(c.pars)) throw ParameterWrong("the ...Fine observables need timeDisplacedEverySlice");
     if (fine && td_fine_on_device(c.pars))
         throw ParameterWrong("the ...Fine observables are not formed with timeDisplacedFineOnDevice: read the Matsubara transforms");
@@ -762,6 +787,12 @@ void DetSDW::getObservableVector(int which_in, double* out, int b) const {
                                      : which < DETSDW_OBS_CUSTOMPAIRSQ ? c.customPairCorr[ch] : c.customPairSq[ch];
         if (e.empty()) throw GeneralError(DQMC_EINVAL, "no measurement sweep has run since the user-defined pair operators were set");
         std::memcpy(out, e.data(), e.size() * sizeof(double));
+        return;
+    }
+    if (greenMat) {
+        if (!greenMatrix_) throw ParameterWrong("greenMatrixTau needs detsdw_set_green_matrix");
+        if (t.greenMatrixTau.empty()) throw GeneralError(DQMC_EINVAL, "no measurement sweep has run since the averaged Green's function was switched on");
+        std::memcpy(out, t.greenMatrixTau.data(), t.greenMatrixTau.size() * sizeof(double));
         return;
     }
     const std::vector<double>* v = which == DETSDW_OBS_KOCCX ? &c.kOccX : which == DETSDW_OBS_KOCCY ? &c.kOccY
@@ -866,6 +897,7 @@ void DetSDW::seriesBegin(int binSize, int maxBins, int nfreq, int flags) {
         if (td_band(p)) parts |= DQMC_SERIES_MATS_BAND;
         if (customTd()) parts |= DQMC_SERIES_MATS_CUSTOM;
         if (customPairTd()) parts |= DQMC_SERIES_MATS_CUSTOM_PAIR;
+        if (greenMatrix_) parts |= DQMC_SERIES_GREEN_MATRIX;
     }
     if (blocks && customEq()) parts |= DQMC_SERIES_EQ_CUSTOM;
     if (blocks && customPairEq()) parts |= DQMC_SERIES_EQ_CUSTOM_PAIR;
@@ -953,6 +985,10 @@ void DetSDW::seriesSlice(int which, int& part, size_t& offset, size_t& length) {
         if (!(series_.parts & DQMC_SERIES_MATS_CUSTOM_PAIR) || ch >= pairCount())
             throw ParameterWrong("the series holds no Matsubara part of this user-defined pair operator");
         part = 11; length = (size_t)series_.nfreq * N_ * 2; sub = (size_t)ch * length;
+    } else if (which == DETSDW_OBS_GREENMATRIXTAU) {
+        if (!(series_.parts & DQMC_SERIES_GREEN_MATRIX))
+            throw ParameterWrong("the series holds no averaged Green's function: detsdw_set_green_matrix before the series began, and timeDisplacedEverySlice");
+        part = 13; length = (size_t)(m_ + 1) * N_ * (ch_[0].pars.opdim == 3 ? 32 : 8); sub = 0;
     } else if (which == DETSDW_OBS_PHICHI || which == DETSDW_OBS_PHISCALARS) {
         if (!(series_.parts & DQMC_SERIES_PHI)) throw ParameterWrong("the series has no order-parameter part: detsdw_series_begin with DETSDW_SERIES_PHI");
         part = 6;
@@ -1067,6 +1103,39 @@ void DetSDW::seriesCustomPairDerived(int c, int qx, int qy, double* value, doubl
         check(dqmc_series_custom_pair_derived_host(g.ctx, qx, qy, v.data(), e.data()), "dqmc_series_custom_pair_derived_host");
         for (int b = 0; b < g.count; ++b) { value[g.first + b] = v[(size_t)b * nc + c]; err[g.first + b] = e[(size_t)b * nc + c]; }
     }
+}
+// Bubble and vertex of user-defined pair operator c at Q = (qx, qy) for every slot in handle order: value, err [nchains][5 + m]
+void DetSDW::seriesPairVertex(int c, int qx, int qy, double* value, double* err) {
+    if (!series_.open) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
+    if (!(series_.parts & DQMC_SERIES_MATS_CUSTOM_PAIR) || !(series_.parts & DQMC_SERIES_GREEN_MATRIX))
+        throw ParameterWrong("the pair vertex needs operators set by detsdw_set_custom_pair_operators and detsdw_set_green_matrix before the series began, "
+                             "with timeDisplacedEverySlice");
+    const int nc = pairCount();
+    if (c < 0 || c >= nc) throw ParameterWrong("no user-defined pair operator with this index is set");
+    const size_t per = (size_t)5 + m_;
+    std::vector<double> v, e;
+    for (auto& g : groups_) {
+        v.resize((size_t)g.count * nc * per); e.resize(v.size());
+        check(dqmc_series_pair_vertex_host(g.ctx, qx, qy, v.data(), e.data()), "dqmc_series_pair_vertex_host");
+        for (int b = 0; b < g.count; ++b) {
+            std::memcpy(value + (size_t)(g.first + b) * per, &v[((size_t)b * nc + c) * per], per * sizeof(double));
+            std::memcpy(err + (size_t)(g.first + b) * per, &e[((size_t)b * nc + c) * per], per * sizeof(double));
+        }
+    }
+}
+// The averaged Green's function block of every kernel context; if a later context fails the earlier ones are switched back
+void DetSDW::setGreenMatrix(bool on) {
+    if (on && !td_level(ch_[0].pars)) throw ParameterWrong("detsdw_set_green_matrix needs timeDisplacedMeasurements");
+    if (on == greenMatrix_) return;
+    for (size_t i = 0; i < groups_.size(); ++i) {
+        const int rc = dqmc_set_green_matrix(groups_[i].ctx, on ? 1 : 0);
+        if (rc == DQMC_OK) continue;
+        const std::string why = dqmc_last_error();
+        for (size_t k = 0; k < i; ++k) (void)dqmc_set_green_matrix(groups_[k].ctx, on ? 0 : 1);
+        throw GeneralError(rc, "dqmc_set_green_matrix: " + why);
+    }
+    greenMatrix_ = on;
+    for (auto& c : ch_) { c.td.greenMatrixTau.clear(); c.tdFine.greenMatrixTau.clear(); }
 }
 bool DetSDW::customPairTd() const { return pairCount() && td_level(ch_[0].pars); }
 bool DetSDW::customPairEq() const { return pairCount() && eq_correlators(ch_[0].pars); }
@@ -1924,6 +1993,13 @@ extern "C" int detsdw_get_custom_pair_operators(detsdw_replica* r, int* count, d
 extern "C" int detsdw_series_custom_pair_derived(detsdw_replica* r, int c, int qx, int qy, double* value, double* err) {
     if (!value || !err) { g_host_err = "null argument"; return DQMC_EINVAL; }
     RGUARD(r->impl->seriesCustomPairDerived(c, qx, qy, value, err))
+}
+extern "C" int detsdw_set_green_matrix(detsdw_replica* r, int on) {
+    RGUARD(r->impl->setGreenMatrix(on != 0))
+}
+extern "C" int detsdw_series_pair_vertex(detsdw_replica* r, int c, int qx, int qy, double* value, double* err) {
+    if (!value || !err) { g_host_err = "null argument"; return DQMC_EINVAL; }
+    RGUARD(r->impl->seriesPairVertex(c, qx, qy, value, err))
 }
 extern "C" int detsdw_set_custom_bilinears(detsdw_replica* r, int count, const dqmc_cplx* M) {
     RGUARD(r->impl->setCustomBilinears(count, M))

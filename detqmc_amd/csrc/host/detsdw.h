@@ -80,6 +80,9 @@ public:
     void setCustomPairOperators(int count, const dqmc_cplx* F0, const dqmc_cplx* Fx, const dqmc_cplx* Fy);
     void getCustomPairOperators(int* count, dqmc_cplx* F0, dqmc_cplx* Fx, dqmc_cplx* Fy) const;
     void seriesCustomPairDerived(int c, int qx, int qy, double* value, double* err);
+    // the averaged Green's function block of every kernel context, and the bubble / vertex of pair operator c from the series
+    void setGreenMatrix(bool on);
+    void seriesPairVertex(int c, int qx, int qy, double* value, double* err);
     void seriesReadBins(int which, int first, int count, double* out, int b = 0);
     // long runs: options, re-binning, binning analysis (err, tau [levels] x the slice of seriesStats; tau may be null), series file
     void seriesConfigure(int flags);
@@ -112,6 +115,7 @@ private:
         std::vector<double> phTau[3], phTauQ0[3];           // charge, spinZ, sdw: rows x N and the row sums (timeDisplacedParticleHole)
         std::vector<double> currentTau[2], currentTauQ0[2], bondKinetic[2];   // x, y: rows x N, row sums, rows (timeDisplacedParticleHole == 2)
         std::vector<double> bandTau[2], bandTauQ0[2];       // bandDiff, bandMix: rows x N and the row sums (DETSDW_TD_PH_BAND)
+        std::vector<double> greenMatrixTau;                 // rows x N x 4 x 4 complex: the averaged Green's function (setGreenMatrix)
         std::vector<double> customPairTau[DQMC_CUSTOM_MAX], customPairTauQ0[DQMC_CUSTOM_MAX];   // ... per user-defined pair operator (setCustomPairOperators)
         std::vector<double> customTau[DQMC_CUSTOM_MAX], customTauQ0[DQMC_CUSTOM_MAX];   // the same per user-defined bilinear (setCustomBilinears)
     };
@@ -160,6 +164,7 @@ private:
     void setCustomOperators(int count, const dqmc_cplx* M, const dqmc_cplx* Mx, const dqmc_cplx* My, bool bond);
     std::vector<dqmc_cplx> pairF_[3];              // F0, Fx, Fy of setCustomPairOperators, [DQMC_CUSTOM_MAX][4][4] each, zero padded
     int pairCount_ = 0;
+    bool greenMatrix_ = false;                     // setGreenMatrix: every kernel context fills its averaged Green's function block
     int pairCount() const { return pairCount_; }
     bool customPairTd() const;                     // pair operators are set and the handle measures time-displaced
     bool customPairEq() const;                     // ... the equal-time correlators

@@ -1844,6 +1844,254 @@ void launch_measure_custom_pair(const Launch& lc, const DevModel& hm, int count,
     else hipLaunchKernelGGL((k_measure_custom_pair<3>), grid, block, 0, lc.st, hm, cm, gs, acc, row, rows, acs, lc.cs);
 }
 
+// The averaged Green's function block (dqmc_set_green_matrix; dqmc_hip.h and DESIGN.md 6e): from the shifted gs = g~(tau,0) the pair
+// kernels read,
+//   Gbar_rc(d) += sum_B sigma(B, d) gs((B (+) d) r; B c),   sigma = -1 for each antiperiodic direction in which B + d wraps,
+// r, c over the stored flavour block (R = 2: the (XUP, YDOWN) sector, R = 4 for O(3)).  Shape, walk order over B and the coalesced reads
+// along A of k_measure_custom_pair; a thread keeps the 2 R^2 sums of its bin in registers, and the LDS reduction over the parts runs in
+// passes of TDP_PARTS components: part q writes component pass TDP_PARTS + q of its bin -- one writer per accumulator, fixed summation
+// order, no atomics.  Block: count[rows], then the rows [N][R][R] (re, im); outside the arena: chain b at acc + b * acs.
+size_t measure_green_matrix_row_doubles(int opdim, int N) { return (size_t)(opdim == 3 ? 32 : 8) * N; }
+template<int OPDIM>
+__global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_green_matrix(DevModel dm, const cplx* __restrict__ gs, double* __restrict__ acc,
+                                                                               int row, int rows, size_t acs, size_t cs, int apbx, int apby) {
+    CHAIN(gs);
+    constexpr int R = OPDIM == 3 ? 4 : 2, NC = 2 * R * R;
+    static_assert(NC % TDP_PARTS == 0, "the reduction runs in passes of TDP_PARTS components");
+    acc += (size_t)blockIdx.z * acs;
+    __shared__ double red[TDP_PARTS][TDP_PARTS][TDP_BINS];  // [component of the pass][part][bin]
+    const int N = dm.N, L = dm.L, tid = threadIdx.x;
+    const size_t ng = (size_t)dm.ng;
+    const int lb = tid % TDP_BINS, part = tid / TDP_BINS;
+    const int d = blockIdx.x * TDP_BINS + lb;
+    const bool valid = d < N;
+    const int dx = valid ? d % L : 0, dy = valid ? d / L : 0;
+    double w[NC];
+#pragma unroll
+    for (int q = 0; q < NC; ++q) w[q] = 0.0;
+    if (valid) {
+        int bx = part % L, by = part / L;                   // site B = part + 8 i, kept as (bx, by)
+        const int stepx = TDP_PARTS % L, stepy = TDP_PARTS / L;
+        for (int B = part; B < N; B += TDP_PARTS) {
+            int ax = bx + dx, ay = by + dy;
+            const bool wx = ax >= L, wy = ay >= L;
+            if (wx) ax -= L;
+            if (wy) ay -= L;
+            const double sg = ((wx && apbx) != (wy && apby)) ? -1.0 : 1.0;
+            const cplx* pe = gs + (size_t)B * ng + (size_t)(ay * L + ax);     // gs(A r; B c) = pe[c N ng + r N]
+#pragma unroll
+            for (int c2 = 0; c2 < R; ++c2)
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const cplx v = pe[(size_t)c2 * N * ng + (size_t)r * N];
+                    w[2 * (r * R + c2)] += sg * v.x; w[2 * (r * R + c2) + 1] += sg * v.y;
+                }
+            bx += stepx; by += stepy;
+            if (bx >= L) { bx -= L; ++by; }
+        }
+    }
+#pragma unroll
+    for (int pass = 0; pass < NC / TDP_PARTS; ++pass) {
+        if (pass) __syncthreads();
+#pragma unroll
+        for (int q = 0; q < TDP_PARTS; ++q) red[q][part][lb] = w[pass * TDP_PARTS + q];
+        __syncthreads();
+        if (valid) {                                        // part q writes component pass TDP_PARTS + q of its bin
+            double s = red[part][0][lb];
+#pragma unroll
+            for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
+            acc[rows + ((size_t)row * N + d) * NC + pass * TDP_PARTS + part] += s;
+        }
+    }
+    if (blockIdx.x == 0 && tid == 0) acc[row] += 1.0;
+}
+void launch_measure_green_matrix(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc, size_t acs, int row, int rows, int apbx, int apby) {
+    const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
+    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_green_matrix<1>), grid, block, 0, lc.st, hm, gs, acc, row, rows, acs, lc.cs, apbx, apby);
+    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_green_matrix<2>), grid, block, 0, lc.st, hm, gs, acc, row, rows, acs, lc.cs, apbx, apby);
+    else hipLaunchKernelGGL((k_measure_green_matrix<3>), grid, block, 0, lc.st, hm, gs, acc, row, rows, acs, lc.cs, apbx, apby);
+}
+
+// Series part 13 (DQMC_SERIES_GREEN_MATRIX): the every-slice block of the kernel above normalised, out[k][N][R][R] (re, im) = row k /
+// (double(N) count[k]) (one division); bad[chain] = 1 if a row of the chain has no sample.  Grid (row pieces, rows, chains).
+__global__ __launch_bounds__(256) void k_series_green_sample(const double* __restrict__ fine, size_t chain_bytes, int rows, size_t rowlen, double Nd,
+                                                             double* __restrict__ sample, size_t S, size_t off, double* __restrict__ bad) {
+    const double* blk = (const double*)((const char*)fine + (size_t)blockIdx.z * chain_bytes);
+    const int k = blockIdx.y;
+    if (blockIdx.x == 0 && k == 0 && threadIdx.x == 0) {
+        double flag = 0.0;
+        for (int r = 0; r < rows; ++r) if (!(blk[r] >= 1.0)) flag = 1.0;
+        bad[blockIdx.z] = flag;
+    }
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rowlen) return;
+    const double den = Nd * blk[k];
+    sample[(size_t)blockIdx.z * S + off + (size_t)k * rowlen + i] = blk[rows + (size_t)k * rowlen + i] / den;
+}
+void launch_series_green_sample(const Launch& lc, const DevModel& hm, const double* fine, size_t chain_bytes, double* sample, size_t S, size_t off,
+                                double* bad) {
+    const size_t rowlen = measure_green_matrix_row_doubles(hm.opdim, hm.N);
+    hipLaunchKernelGGL(k_series_green_sample, dim3((unsigned)((rowlen + 255) / 256), (unsigned)(hm.m + 1), (unsigned)lc.nb), dim3(256), 0, lc.st, fine,
+                       chain_bytes, hm.m + 1, rowlen, (double)hm.N, sample, S, off, bad);
+}
+
+// Bubble and vertex of the pair operators from the series (dqmc_series_pair_vertex_host; dqmc_hip.h and DESIGN.md 6e), two kernels.
+// k_series_pair_bubble, grid (row k = 0 .. m, jackknife index b = 0 .. B, slot), 256 threads: the row of part 13 for index b -- the
+// leave-one-out mean x_(b) = (B mean - x_b) / (B - 1), b = B: the mean itself -- is staged in LDS as gbar[N][R][R]; then, with
+//   gbar(P r; Q c) = sigma(Q, P (-) Q) gbar_rc(P (-) Q)
+// in the place of the E blocks, thread d evaluates the contraction of k_measure_custom_pair_bond (cpr_term, the same table, masks and
+// link signs) for the site pair (A, B) = (d, 0) -- gbar is translation-covariant, the summand does not depend on B -- and adds
+// cos(Q d) Pbar_c(d) to its sum; a fixed tree over the 256 sums follows, and thread c writes pb[slot][b][k][c].
+// k_series_pair_vertex, one thread per (slot, operator, output): the tau quadrature of pb and the jackknife over b in index order.
+struct PairVertexShape { size_t S, off_g, off_chi; int L, N, m, nfreq, nb, B, count, qx, qy, apbx, apby; double dtau; };
+size_t series_pair_bubble_lds_bytes(int opdim, int N) { return (measure_green_matrix_row_doubles(opdim, N) + (size_t)DQMC_CUSTOM_MAX * 256) * sizeof(double); }
+// e[r][c] = the stored part of gbar(P .; Q .), P = (px, py) and Q = (qx, qy) reduced to 0 .. L-1
+template<int R>
+__device__ __forceinline__ void pvx_load(const cplx* __restrict__ g, int L, int apbx, int apby, int px, int py, int qx, int qy, cplx (&e)[R][R]) {
+    int dx = px - qx, dy = py - qy;
+    if (dx < 0) dx += L;
+    if (dy < 0) dy += L;
+    const double sg = ((apbx && qx + dx >= L) != (apby && qy + dy >= L)) ? -1.0 : 1.0;
+    const cplx* p = g + (size_t)(dy * L + dx) * R * R;
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int c2 = 0; c2 < R; ++c2) e[r][c2] = make_double2(sg * p[r * R + c2].x, sg * p[r * R + c2].y);
+}
+template<int OPDIM>
+__global__ __launch_bounds__(256) void k_series_pair_bubble(const double* __restrict__ bins, const double* __restrict__ mean,
+                                                            const double* __restrict__ trig, CustomPairArg cp, PairVertexShape a,
+                                                            double* __restrict__ pb) {
+    constexpr int R = OPDIM == 3 ? 4 : 2;
+    extern __shared__ __attribute__((aligned(16))) double pvx_sm[];
+    const int N = a.N, L = a.L, tid = threadIdx.x, count = cp.count, B = a.B;
+    const int k = blockIdx.x, b = blockIdx.y, slot = blockIdx.z;
+    const size_t rowlen = (size_t)2 * R * R * N, n = (size_t)a.nb * a.S, base = (size_t)slot * a.S + a.off_g + (size_t)k * rowlen;
+    double* red = pvx_sm + rowlen;                          // [DQMC_CUSTOM_MAX][256]
+    for (size_t e = tid; e < rowlen; e += 256) {
+        const double mu = mean[base + e];
+        pvx_sm[e] = b < B ? ((double)B * mu - bins[(size_t)b * n + base + e]) / (double)(B - 1) : mu;
+    }
+    __syncthreads();
+    const cplx* g = (const cplx*)pvx_sm;
+    const cplx* __restrict__ lk = cp.tab + (size_t)count * CPR_K * 3 * 16;
+    unsigned both[DQMC_CUSTOM_MAX];                         // bit 3 ka + kb: operator ch has the blocks ka and kb
+    unsigned need = 0;
+#pragma unroll
+    for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) {
+        both[ch] = 0;
+        if (ch < count)
+            for (int ka = 0; ka < CPR_K; ++ka)
+                if ((cp.parts[ch] >> ka) & 1u) both[ch] |= (cp.parts[ch] & 0x7u) << (CPR_K * ka);
+        need |= both[ch];
+    }
+    double w[DQMC_CUSTOM_MAX] = {0.0, 0.0, 0.0, 0.0};
+    const int B1 = 1 % L;                                   // the neighbours of site B = 0: (1, 0) and (0, 1)
+    const double ubx = lk[0].x, uby = lk[N].x;
+    for (int d = tid; d < N; d += 256) {
+        const int ax = d % L, ay = d / L;
+        const int axp = ax + 1 == L ? 0 : ax + 1, ayp = ay + 1 == L ? 0 : ay + 1;
+        const double uax = lk[d].x, uay = lk[N + d].x;
+        double v[DQMC_CUSTOM_MAX] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 1
+        for (int pr = 0; pr < CPR_K * CPR_K; ++pr) {
+            if (!((need >> pr) & 1u)) continue;
+            const int ka = pr / CPR_K, kb = pr % CPR_K;
+            const int px = ka == 1 ? axp : ax, py = ka == 2 ? ayp : ay, rx = kb == 1 ? B1 : 0, ry = kb == 2 ? B1 : 0;
+            const double f = (ka == 1 ? uax : ka == 2 ? uay : 1.0) * (kb == 1 ? ubx : kb == 2 ? uby : 1.0);
+            cplx x[R][R], y[R][R];
+            pvx_load<R>(g, L, a.apbx, a.apby, px, py, rx, ry, x);           // direct: gbar(A^k; B^k'), gbar(A; B)
+            pvx_load<R>(g, L, a.apbx, a.apby, ax, ay, 0, 0, y);
+#pragma unroll
+            for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
+                if ((both[ch] >> pr) & 1u) {
+                    const cplx* __restrict__ V = cp.tab + (size_t)ch * CPR_K * 3 * 16;
+                    const unsigned* __restrict__ mk = cp.mk + ch * CPR_K * 2;
+                    v[ch] += f * cpr_term<OPDIM, R>(x, y, V + 48 * ka, mk[2 * ka], V + 48 * kb + 16, mk[2 * kb]);
+                }
+            pvx_load<R>(g, L, a.apbx, a.apby, px, py, 0, 0, x);             // exchange: gbar(A^k; B), gbar(A; B^k')
+            pvx_load<R>(g, L, a.apbx, a.apby, ax, ay, rx, ry, y);
+#pragma unroll
+            for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
+                if ((both[ch] >> pr) & 1u) {
+                    const cplx* __restrict__ V = cp.tab + (size_t)ch * CPR_K * 3 * 16;
+                    const unsigned* __restrict__ mk = cp.mk + ch * CPR_K * 2;
+                    v[ch] -= f * cpr_term<OPDIM, R>(x, y, V + 48 * ka, mk[2 * ka], V + 48 * kb + 32, mk[2 * kb + 1]);
+                }
+        }
+        const double cq = trig[(a.qx * ax + a.qy * ay) % L];
+#pragma unroll
+        for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) w[ch] += cq * v[ch];
+    }
+#pragma unroll
+    for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) red[ch * 256 + tid] = w[ch];
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {                     // a fixed tree: the same order in every launch
+        if (tid < h)
+#pragma unroll
+            for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) red[ch * 256 + tid] += red[ch * 256 + tid + h];
+        __syncthreads();
+    }
+    if (tid < count) pb[(((size_t)slot * (B + 1) + b) * (a.m + 1) + k) * count + tid] = red[tid * 256];
+}
+// outputs per (slot, operator): 0 P = Re chi(Q, i omega_0) of part 11, 1 Pbar = dtau sum_k w_k pb, 2 Gamma = 1 / P - 1 / Pbar,
+// 3 Gamma Pbar = Pbar / P - 1, then pb at k = 0 .. m; NaN where a denominator vanishes
+__device__ __forceinline__ double pvx_f(int e, double P, double Pb) {
+    if (e == 0) return P;
+    if (e == 1) return Pb;
+    if (P == 0.0 || (e == 2 && Pb == 0.0)) return nan("");
+    return e == 2 ? 1.0 / P - 1.0 / Pb : Pb / P - 1.0;
+}
+__global__ __launch_bounds__(64) void k_series_pair_vertex(const double* __restrict__ bins, const double* __restrict__ pb, PairVertexShape a,
+                                                           double* __restrict__ value, double* __restrict__ err) {
+    const int per = 5 + a.m, t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= a.nb * a.count * per) return;
+    const int slot = t / (a.count * per), c = (t / per) % a.count, e = t % per, B = a.B, m = a.m;
+    const size_t n = (size_t)a.nb * a.S;
+    const double* p = bins + (size_t)slot * a.S + a.off_chi + ((size_t)c * a.nfreq * a.N + (size_t)a.qy * a.L + a.qx) * 2;     // Re, frequency 0
+    const double* r0 = pb + (size_t)slot * (B + 1) * (m + 1) * a.count + c;
+    double sum = 0.0;
+    for (int b = 0; b < B; ++b) sum += p[(size_t)b * n];
+    const double mu = sum / (double)B, tot = (double)B * mu;
+    auto theta = [&](int b) {
+        const double* r = r0 + (size_t)b * (m + 1) * a.count;
+        if (e >= 4) return r[(size_t)(e - 4) * a.count];
+        double s = 0.0;
+        for (int k = 0; k <= m; ++k) s += (k == 0 || k == m ? 0.5 : 1.0) * r[(size_t)k * a.count];
+        return pvx_f(e, b < B ? (tot - p[(size_t)b * n]) / (double)(B - 1) : mu, a.dtau * s);
+    };
+    double tsum = 0.0;
+    for (int b = 0; b < B; ++b) tsum += theta(b);
+    const double tbar = tsum / (double)B;
+    double acc = 0.0;
+    for (int b = 0; b < B; ++b) {
+        const double dl = theta(b) - tbar;
+        acc += dl * dl;
+    }
+    value[t] = theta(B);
+    err[t] = sqrt((double)(B - 1) / (double)B * acc);
+}
+// false: the lattice is too large for the bubble kernel's LDS, nothing was launched.  mean: the bin means [nb][S] (launch_series_stats)
+bool launch_series_pair_vertex(const Launch& lc, const DevModel& hm, const double* bins, const double* mean, const double* trig, size_t S, int B,
+                               int nfreq, size_t off_chi, size_t off_g, int count, const CustomPair& pair, int qx, int qy, int apbx, int apby,
+                               double* pb, double* value, double* err) {
+    const size_t lds = series_pair_bubble_lds_bytes(hm.opdim, hm.N);
+    if (lds > 152 * 1024) return false;
+    CustomPairArg cp{};
+    cp.tab = pair.tab; cp.mk = pair.mk; cp.count = count;
+    for (int ch = 0; ch < count; ++ch) cp.parts[ch] = pair.parts[ch];
+    const PairVertexShape a{S, off_g, off_chi, hm.L, hm.N, hm.m, nfreq, lc.nb, B, count, qx, qy, apbx, apby, hm.dtau};
+    const dim3 grid((unsigned)(hm.m + 1), (unsigned)(B + 1), (unsigned)lc.nb);
+    const void* fn = hm.opdim == 1 ? (const void*)k_series_pair_bubble<1> : hm.opdim == 2 ? (const void*)k_series_pair_bubble<2> : (const void*)k_series_pair_bubble<3>;
+    if (lds > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) (void)hipGetLastError();
+    if (hm.opdim == 1) hipLaunchKernelGGL((k_series_pair_bubble<1>), grid, dim3(256), lds, lc.st, bins, mean, trig, cp, a, pb);
+    else if (hm.opdim == 2) hipLaunchKernelGGL((k_series_pair_bubble<2>), grid, dim3(256), lds, lc.st, bins, mean, trig, cp, a, pb);
+    else hipLaunchKernelGGL((k_series_pair_bubble<3>), grid, dim3(256), lds, lc.st, bins, mean, trig, cp, a, pb);
+    const int total = lc.nb * count * (5 + hm.m);
+    hipLaunchKernelGGL(k_series_pair_vertex, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, lc.st, bins, pb, a, value, err);
+    return true;
+}
+
 // End rows of the every-slice blocks (dqmc_measure_timedisplaced_ends): from the equal-time G = G(0), one elementwise pass writes
 //   tau = 0+:    G(0+,0) = G,          G(0,0+) = G - 1          -> a_t0, a_0t
 //   tau = beta-: G(beta-,0) = 1 - G,   G(0,beta-) = -G          -> b_t0, b_0t

@@ -168,6 +168,21 @@ def custom_pair_ratio(name):
     return int(m.group(1)) if m else None
 
 
+# bit 13: the normalised averaged Green's function of every slice (set_green_matrix), [m+1][N][R][R] complex
+SERIES_GREEN_MATRIX = 8192
+# 'greenMatrixTau' (and its 'Fine' twin): index of detsdw_get_observable_vector / detsdw_series_stats
+GREEN_MATRIX_OBS = 74
+# derived series quantities of the pair vertex (DetSDWBatch.series_derived_all): name prefix -> entry of detsdw_series_pair_vertex
+PAIR_VERTEX_QUANTITIES = {"vertexCustomPair": 0, "bubbleCustomPair": 1, "gammaCustomPair": 2, "gammaBubbleCustomPair": 3}
+
+
+def pair_vertex_quantity(name):
+    """(entry, operator index c) of 'vertexCustomPair{c}' (P), 'bubbleCustomPair{c}' (Pbar), 'gammaCustomPair{c}' (Gamma = 1/P - 1/Pbar) or
+    'gammaBubbleCustomPair{c}' (Gamma Pbar = Pbar/P - 1); None for any other name"""
+    m = re.fullmatch(r"(vertexCustomPair|bubbleCustomPair|gammaCustomPair|gammaBubbleCustomPair)([0-3])", name)
+    return (PAIR_VERTEX_QUANTITIES[m.group(1)], int(m.group(2))) if m else None
+
+
 def _matsubara_index(name):
     """index of detsdw_get_matsubara for a name of MATSUBARA, 'custom{c}Tau' or 'customPair{c}Tau'; KeyError otherwise"""
     cw = custom_observable(name) or custom_pair_observable(name)
@@ -321,6 +336,57 @@ def pair_operator(kind):
         F[XDOWN, XUP] = F[YDOWN, YUP] = -1.0
         return (None, F, F.copy() if kind == "s_ext" else -F)
     raise ValueError("kind must be 's', 'd_band', 's_ext' or 'd_bond'")
+
+
+def pair_bubble(gbar, ops, L, bc="pbc"):
+    """The pairing bubble Pbar_c(d) of the pair operators `ops` (a list of (F0, Fx, Fy), see pair_operator) on an averaged Green's
+    function: the numpy counterpart of the device's bubble kernel, for users who want another function of the series bins.
+    gbar: complex (..., N, R, R), the normalised block of set_green_matrix, gbar[..., dy L + dx, r, c] = Gbar_rc(d) / (N count), R = 2 (the
+    (XUP, YDOWN) sector of O(1) / O(2)) or 4; leading axes (bins, time slices) are carried along.  The full matrix is
+    g(P r; Q c) = sigma(Q, P - Q) gbar_rc(P - Q), sigma = -1 for each antiperiodic direction of bc ('pbc', 'apbc-x', 'apbc-y', 'apbc-xy') in
+    which Q + (P - Q) wraps; the (XDOWN, YUP) sector of R = 2 is the complex conjugate.  Returns the real array (..., count, N),
+        Pbar_c(d) = Re sum_ijkl D^d_ij conj(D^0_kl) [g(i; k) g(j; l) - g(i; l) g(j; k)],
+    D^A the dense operator with the site blocks (A, A) = F0, (A + mu, A) = u_mu(A) Fmu; g is translation-covariant, so the site pair
+    (B + d, B) is taken at B = 0."""
+    g = np.asarray(gbar, dtype=np.complex128)
+    N, R = L * L, g.shape[-1]
+    if bc not in ("pbc", "apbc-x", "apbc-y", "apbc-xy") or g.shape[-3:] != (N, R, R) or R not in (2, 4):
+        raise ValueError("gbar must be (..., L L, R, R) with R = 2 or 4, bc one of 'pbc', 'apbc-x', 'apbc-y', 'apbc-xy'")
+    apb = (bc in ("apbc-x", "apbc-xy"), bc in ("apbc-y", "apbc-xy"))
+    if R == 2:
+        full = np.zeros(g.shape[:-2] + (4, 4), dtype=np.complex128)
+        full[..., :2, :2] = g
+        full[..., 2:, 2:] = np.conj(g)
+        g = full
+    ax, ay = np.arange(N) % L, np.arange(N) // L
+    zero = np.zeros((4, 4), dtype=np.complex128)
+
+    def block(px, py, qx, qy):
+        """g(P .; Q .) for the site arrays P and the one site Q: (..., N, 4, 4)"""
+        dx, dy = (px - qx) % L, (py - qy) % L
+        sg = np.where(apb[0] & (qx + dx >= L), -1.0, 1.0) * np.where(apb[1] & (qy + dy >= L), -1.0, 1.0)
+        return sg[:, None, None] * g[..., dy * L + dx, :, :]
+
+    # site blocks k = 0, x, y of the operator at A = d (all d at once) and at B = 0, with their link signs
+    PA = [(ax, ay, np.ones(N)), ((ax + 1) % L, ay, np.where(apb[0] & (ax == L - 1), -1.0, 1.0)), (ax, (ay + 1) % L, np.where(apb[1] & (ay == L - 1), -1.0, 1.0))]
+    QB = [(0, 0), (1 % L, 0), (0, 1 % L)]
+    out = []
+    for op in ops:
+        F = [zero if m is None else np.asarray(m, dtype=np.complex128) for m in op]
+        acc = np.zeros(g.shape[:-3] + (N,))
+        for ka in range(3):
+            if not F[ka].any():
+                continue
+            px, py, ua = PA[ka]
+            for kb in range(3):
+                if not F[kb].any():
+                    continue
+                qx, qy = QB[kb]
+                direct = np.einsum("ab,cd,...ac,...bd->...", F[ka], np.conj(F[kb]), block(px, py, qx, qy), block(ax, ay, 0, 0), optimize=True)
+                exchange = np.einsum("ab,cd,...ad,...bc->...", F[ka], np.conj(F[kb]), block(px, py, 0, 0), block(ax, ay, qx, qy), optimize=True)
+                acc = acc + ua * (direct - exchange).real
+        out.append(acc)
+    return np.stack(out, axis=-2) if out else np.zeros(g.shape[:-3] + (0, N))
 
 
 class KernelContext:
@@ -534,6 +600,20 @@ class KernelContext:
         """the selected chain's equal-time block of the set pair operators: [count, one row of N raw sums per operator], index dy L + dx"""
         return self._read_block(self.lib.dqmc_measure_eq_custom_pair_accum_size, self.lib.dqmc_measure_eq_custom_pair_read_host)
 
+    def set_green_matrix(self, on=True):
+        """while on, every time-displaced row also bins Gbar_rc(d) = sum_B sigma(B, d) g~((B + d) r; B c) of the shifted G(tau,0) into
+        a block of its own (coarse rows by measure_timedisplaced_green_matrix, every-slice channel 7): the input of the pairing bubble
+        (series_pair_vertex, pair_bubble).  Needs timeDisplaced >= 1; refused under weakZflux"""
+        check(self.lib.dqmc_set_green_matrix(self.h, int(on)))
+
+    def measure_timedisplaced_green_matrix(self, j):
+        """the averaged Green's function block at boundary j, one launch"""
+        check(self.lib.dqmc_measure_timedisplaced_green_matrix(self.h, j))
+
+    def measure_td_green_matrix_read(self):
+        """count[n-1], then per boundary one row [N][R][R] of raw sums as (re, im); bin dy L + dx"""
+        return self._read_block(self.lib.dqmc_measure_td_green_matrix_accum_size, self.lib.dqmc_measure_td_green_matrix_read_host)
+
     def measure_timedisplaced_segment(self, j):
         """every slice of boundary j's segment into the fine blocks, by propagation from the boundary's matrices (needs tdEverySlice=True at
         construction; call it right after the advance that ended on boundary j)"""
@@ -545,7 +625,7 @@ class KernelContext:
 
     def measure_td_fine_read(self, channel):
         """fine block of channel 0 (G(k, tau) bins), 1 (pairing), 2 (particle-hole), 3 (current), 4 (band), 5 (custom bilinears), 6 (custom pair
-        operators): count[m+1], then rows k = 0 .. m"""
+        operators), 7 (the averaged Green's function): count[m+1], then rows k = 0 .. m"""
         return self._read_block(self.lib.dqmc_measure_td_fine_accum_size, self.lib.dqmc_measure_td_fine_read_host, channel)
 
     def measure_td_matsubara(self, channel, nfreq):
@@ -644,6 +724,15 @@ class KernelContext:
         v, e = np.zeros((self.nchains_total(), count)), np.zeros((self.nchains_total(), count))
         check(self.lib.dqmc_series_custom_pair_derived_host(self.h, int(qx), int(qy), v.ctypes.data_as(_lib._DP), e.ctypes.data_as(_lib._DP)))
         return v, e
+
+    def series_pair_vertex(self, Q=(0, 0)):
+        """bubble and vertex of every custom pair operator at Q = (qx, qy), of a series with SERIES_MATS_CUSTOM_PAIR | SERIES_GREEN_MATRIX:
+        (value, err), (nchains, count, 5 + m) each -- P = Re chi(Q, i omega_0), Pbar, Gamma = 1/P - 1/Pbar, Gamma Pbar = Pbar/P - 1, then
+        Pbar(Q, tau_k) for k = 0 .. m; jackknife over the closed bins"""
+        n = self.lib.dqmc_series_pair_vertex_size(self.h)
+        v, e = np.zeros(max(n, 1)), np.zeros(max(n, 1))
+        check(self.lib.dqmc_series_pair_vertex_host(self.h, int(Q[0]), int(Q[1]), v.ctypes.data_as(_lib._DP), e.ctypes.data_as(_lib._DP)))
+        return v.reshape(self.nchains_total(), -1, 5 + self.m), e.reshape(self.nchains_total(), -1, 5 + self.m)
 
     def series_phi_derived(self):
         """(value, err), (nchains, 6) each, of a series with SERIES_PHI: the jackknifed Binder cumulant and ratio of |phibar|, beta N
@@ -1058,6 +1147,10 @@ class DetSDW:
         fine = name.endswith("Fine")
         if fine:
             name = name[:-4]
+        if name == "greenMatrixTau":                        # DetSDWBatch.set_green_matrix: <G(tau,0)> as full 4 x 4 blocks per d
+            out = np.zeros((info.m + 1 if fine else info.n - 1, info.N, 4, 4), dtype=np.complex128)
+            check(self.lib.detsdw_get_observable_vector(self.h, GREEN_MATRIX_OBS | (_lib.DETSDW_OBS_FINE if fine else 0), out.ctypes.data_as(_lib._DP)), host=True)
+            return out
         cw = custom_observable(name) or custom_pair_observable(name)
         if cw:
             kind, which = cw
@@ -1100,6 +1193,9 @@ class DetSDW:
             return BAND_EQ_CORRELATORS[name], (info.N,), False
         if name in SERIES_PHI_OBS:
             return SERIES_PHI_OBS[name], ((self._batch._series_nfreq, info.N) if name == "phiChi" else (5,)), False
+        if name == "greenMatrixTau":                        # the stored flavour block, as pair_bubble takes it
+            R = 4 if info.opdim == 3 else 2
+            return GREEN_MATRIX_OBS, (info.m + 1, info.N, R, R), True
         cw = custom_observable(name) or custom_pair_observable(name)
         if cw and cw[0] in ("Corr", "Sq"):
             return cw[1], (info.N,), False
@@ -1312,6 +1408,29 @@ class DetSDWBatch:
         """the pair operators that are set: a list of (F0, Fx, Fy), complex 4 x 4 each"""
         return _get_custom_bond(self.lib.detsdw_get_custom_pair_operators, self.h, True)
 
+    def set_green_matrix(self, on=True):
+        """from the next sweep(True) on every time-displaced row also bins the averaged Green's function
+        Gbar_rc(d; tau) = sum_B sigma(B, d) g~((B + d) r; B c) (see KernelContext.set_green_matrix): 'greenMatrixTau' (and 'greenMatrixTauFine'),
+        complex (rows, N, 4, 4), and, in a series opened afterwards with timeDisplacedEverySlice, the part behind
+        series_stats_all('greenMatrixTau') and the pair vertex (series_derived_all('gammaBubbleCustomPair{c}', Q=(0, 0)), series_pair_bubble_all).
+        The part costs (m+1) 2 R^2 N doubles per chain and bin: size maxBins accordingly.  Needs timeDisplacedMeasurements; between sweeps"""
+        check(self.lib.detsdw_set_green_matrix(self.h, int(on)), host=True)
+
+    def _series_pair_vertex(self, c, Q):
+        m = self.chains[0].info.m
+        if Q is None:
+            raise ValueError("the pair vertex needs Q = (qx, qy) in units of 2 pi / L: (0, 0) for uniform pairing")
+        qx, qy = Q
+        v, e = np.zeros((len(self.chains), 5 + m)), np.zeros((len(self.chains), 5 + m))
+        check(self.lib.detsdw_series_pair_vertex(self.h, int(c), int(qx), int(qy), v.ctypes.data_as(_lib._DP), e.ctypes.data_as(_lib._DP)), host=True)
+        return v, e
+
+    def series_pair_bubble_all(self, c, Q):
+        """(value, err), (nchains, m+1) each: the bubble Pbar_c(Q, tau_k) of pair operator c on the averaged Green's function of the series,
+        Q = (qx, qy) in units of 2 pi / L ((0, 0): uniform pairing), jackknife over the closed bins"""
+        v, e = self._series_pair_vertex(c, Q)
+        return v[:, 4:].copy(), e[:, 4:].copy()
+
     def matsubara_all(self, name, nfreq):
         """DetSDW.matsubara of every chain: complex (nchains, nfreq, N), one device call per sub-batch"""
         out = np.zeros((len(self.chains), int(nfreq), self.chains[0].info.N), dtype=np.complex128)
@@ -1401,7 +1520,14 @@ class DetSDWBatch:
         """(value, err) per chain of a jackknifed derived quantity: the correlation ratios 'R_charge', 'R_spinZ', 'R_sdw',
         'R_pairPlus', 'R_pairMinus' (equalTimeCorrelators) or 'rhoS' (timeDisplacedCurrent with timeDisplacedEverySlice);
         'R_custom{c}' / 'R_customPair{c}': the correlation ratio of custom bilinear / pair operator c at Q = (qx, qy) in units of
-        2 pi / L, default (L/2, L/2)"""
+        2 pi / L, default (L/2, L/2); with set_green_matrix and pair operators set before the series began, at a Q that must be given
+        ((0, 0) for uniform pairing; ValueError without it: the default of the R_ names would be the wrong one here):
+        'vertexCustomPair{c}' (P = Re chi(Q, i omega_0)), 'bubbleCustomPair{c}' (Pbar, the same contraction on the averaged Green's function),
+        'gammaCustomPair{c}' (Gamma = 1/P - 1/Pbar) and 'gammaBubbleCustomPair{c}' (Gamma Pbar = Pbar/P - 1; -> -1 at the instability)"""
+        pv = pair_vertex_quantity(name)
+        if pv is not None:
+            v, e = self._series_pair_vertex(pv[1], Q)
+            return v[:, pv[0]].copy(), e[:, pv[0]].copy()
         v, e = np.zeros(len(self.chains)), np.zeros(len(self.chains))
         c = custom_ratio(name)
         if c is not None:

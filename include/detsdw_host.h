@@ -154,7 +154,11 @@ enum { DETSDW_OBS_KOCCX = 0, DETSDW_OBS_KOCCY = 1, DETSDW_OBS_PAIRPLUS = 2, DETS
        DETSDW_OBS_CUSTOMTAU = 42, DETSDW_OBS_CUSTOMTAU_Q0 = 46, DETSDW_OBS_CUSTOMCORR = 50, DETSDW_OBS_CUSTOMSQ = 54,
        /* user-defined pair operators (detsdw_set_custom_pair_operators), operator c = 0 .. 3 at BASE + c: customPair{c}Tau,
           customPair{c}TauQ0 (DETSDW_OBS_FINE twins, Matsubara transforms), customPair{c}Corr, customPair{c}Sq, like the custom{c} ones */
-       DETSDW_OBS_CUSTOMPAIRTAU = 58, DETSDW_OBS_CUSTOMPAIRTAU_Q0 = 62, DETSDW_OBS_CUSTOMPAIRCORR = 66, DETSDW_OBS_CUSTOMPAIRSQ = 70 };
+       DETSDW_OBS_CUSTOMPAIRTAU = 58, DETSDW_OBS_CUSTOMPAIRTAU_Q0 = 62, DETSDW_OBS_CUSTOMPAIRCORR = 66, DETSDW_OBS_CUSTOMPAIRSQ = 70,
+       /* the averaged Green's function (detsdw_set_green_matrix): greenMatrixTau, rows x N x 4 x 4 complex as (re, im) -- per row and
+          periodic site difference d the full 4 x 4 block Gbar_ab(d) / (N count), expanded from the stored sector for OPDIM < 3; rows
+          j = 1 .. n-1, with DETSDW_OBS_FINE (greenMatrixTauFine) k = 0 .. m.  As a series observable: the stored block, [m+1][N][R][R] complex */
+       DETSDW_OBS_GREENMATRIXTAU = 74 };
 /* equalTimeCorrelators: flag bit of detsdw_params::fermionMeasurements */
 enum { DETSDW_FM_EQ_CORRELATORS = 0x100 };
 /* bandCorrelators: DETSDW_FM_EQ_BAND is a flag bit of detsdw_params::fermionMeasurements, DETSDW_TD_PH_BAND one of ::timeDisplacedParticleHole */
@@ -332,6 +336,18 @@ int detsdw_get_custom_bond_bilinears(detsdw_replica* r, int* count, dqmc_cplx* M
 int detsdw_set_custom_pair_operators(detsdw_replica* r, int count, const dqmc_cplx* F0, const dqmc_cplx* Fx, const dqmc_cplx* Fy);
 int detsdw_get_custom_pair_operators(detsdw_replica* r, int* count, dqmc_cplx* F0, dqmc_cplx* Fx, dqmc_cplx* Fy);
 int detsdw_series_custom_pair_derived(detsdw_replica* r, int c, int qx, int qy, double* value, double* err);
+/* The averaged Green's function and the pair vertex (dqmc_set_green_matrix, dqmc_series_pair_vertex_host in dqmc_hip.h: definitions, sign
+ * convention, refusals).  detsdw_set_green_matrix(on): forwarded to every sub-batch context, between sweeps; ParameterWrong without
+ * timeDisplacedMeasurements, the kernel level's refusals (weakZflux, an open series that holds the part) come back as its error.  While
+ * on, measurement sweeps fill greenMatrixTau (and, with timeDisplacedEverySlice, its DETSDW_OBS_FINE twin), and a series begun with
+ * timeDisplacedEverySlice carries DQMC_SERIES_GREEN_MATRIX -- no new flag of detsdw_series_begin -- routed, re-binned and saved like every
+ * other part: (m+1) 2 R^2 N doubles per chain and bin (0.8 MB at O(2), L = 16, m = 100), so maxBins is sized accordingly.  The series file
+ * records the part in the `parts` word of its header; detsdw_series_load raises ParameterWrong on a mismatch before anything is imported,
+ * and a series without the part writes the bytes it wrote before.  The series readers take DETSDW_OBS_GREENMATRIXTAU.
+ * detsdw_series_pair_vertex: value[nchains][5 + m], err[nchains][5 + m] for pair operator c at Q = (qx, qy): P, Pbar, Gamma, Gamma Pbar,
+ * then Pbar_c(Q, tau_k), k = 0 .. m; needs pair operators and the switch set before the series began. */
+int detsdw_set_green_matrix(detsdw_replica* r, int on);
+int detsdw_series_pair_vertex(detsdw_replica* r, int c, int qx, int qy, double* value, double* err);
 int detsdw_series_read_bins(detsdw_replica* r, int which, int first, int count, double* out);
 int detsdw_series_end(detsdw_replica* r);
 /* The series over a long run (kernel calls and formulas: dqmc_hip.h).  All of it is new surface: without these calls nothing changes.

@@ -510,6 +510,32 @@ int dqmc_measure_td_custom_pair_read_host(dqmc_ctx* ctx, double* out);
 int dqmc_set_equal_time_custom_pair(dqmc_ctx* ctx, int on);
 size_t dqmc_measure_eq_custom_pair_accum_size(dqmc_ctx* ctx);  /* 0 while no operator is set */
 int dqmc_measure_eq_custom_pair_read_host(dqmc_ctx* ctx, double* out);
+/* The averaged Green's function block ("greenMatrix"): what the pairing bubble Pbar, the Wick form on the ensemble-averaged <G(tau,0)>, is
+ * built from (dqmc_series_pair_vertex_host below).  SDW model only.  dqmc_set_green_matrix(ctx, on) is run-time state like the operators
+ * above; switching on allocates the blocks below, cleared, outside the arena (a failed allocation leaves the context as it was), switching
+ * off releases them; a repeated call changes nothing.  While on, every place that measures a time-displaced row -- the coarse call
+ * dqmc_measure_timedisplaced_green_matrix(j) (preconditions of dqmc_measure_timedisplaced_pair), dqmc_measure_timedisplaced_segment and
+ * dqmc_measure_timedisplaced_ends -- adds, from the shifted g~ = e^{-dtau K/2} G(tau,0) e^{+dtau K/2} the pair kernels read,
+ *   Gbar_rc(d; tau) += sum_B sigma(B, d) g~((B (+) d) r; B c),   d = (dx, dy) periodic, bin dy L + dx,
+ * r, c over the stored flavour block (R = 2 for O(1) and O(2): the (XUP, YDOWN) sector; R = 4 for O(3)), sigma(B, d) = -1 for each
+ * antiperiodic direction in which B + d wraps (bx + dx >= L, likewise in y), +1 otherwise.  With this sign the summand does not depend on
+ * B in a translation-invariant ensemble (G(P + L e_mu, Q) = -G(P, Q) along an antiperiodic direction), and the full matrix is recovered as
+ *   gbar(P r; Q c) = sigma(Q, P (-) Q) Gbar_rc(P (-) Q) / (N count);
+ * for OPDIM < 3 the (XDOWN, YUP) sector is the complex conjugate of the stored one and the blocks between the sectors vanish, element by
+ * element and therefore for averages too.  One launch per row over all chains, one writer per accumulator, fixed summation order, no
+ * atomics: bits do not depend on how chains are batched.
+ * Layout of the coarse block (doubles, dqmc_measure_td_green_matrix_accum_size of them, 0 while off): count[n-1], then for j = 1 .. n-1 a
+ * row [N][R][R] of raw sums as (re, im), 2 R^2 N doubles.  Every-slice channel 7 with DQMC_TD_EVERY_SLICE: count[m+1], then rows k = 0 .. m
+ * of the same form; dqmc_measure_td_fine_accum_size(ctx, 7) is 0 while the switch is off.  The channel has no Matsubara transform
+ * (dqmc_measure_td_matsubara_size(ctx, 7, .) is 0, the call returns DQMC_EINVAL): channel 0 serves G(k, i omega_n).  dqmc_measure_reset
+ * clears both blocks.  With the switch off no kernel of this section is launched and every other block, launch count and result keeps
+ * its bits.  DQMC_EINVAL with nothing changed: a Hubbard context; switching on under weakZflux (<G> is invariant under magnetic
+ * translations only; no gauge choice is made here) or on a context created without timedisplaced >= 1; switching off while a series
+ * holds DQMC_SERIES_GREEN_MATRIX. */
+int dqmc_set_green_matrix(dqmc_ctx* ctx, int on);
+int dqmc_measure_timedisplaced_green_matrix(dqmc_ctx* ctx, int j);
+size_t dqmc_measure_td_green_matrix_accum_size(dqmc_ctx* ctx);  /* 0 while the switch is off */
+int dqmc_measure_td_green_matrix_read_host(dqmc_ctx* ctx, double* out);
 /* G(0) of the last pair's field configuration, selected chain; *slice as for dqmc_get_green_timedisplaced_host.  DQMC_EINVAL without
  * td_particle_hole or if no pair was computed yet */
 int dqmc_get_green0_timedisplaced_host(dqmc_ctx* ctx, dqmc_cplx* g00, int* slice);
@@ -531,7 +557,8 @@ int dqmc_get_green0_timedisplaced_host(dqmc_ctx* ctx, dqmc_cplx* g00, int* slice
  * (current time slice 0 or m: the state after the closing advance of either sweep direction), so that G = G(0); DQMC_EINVAL
  * otherwise.  Both rows use G(tau) = G(0) = G.
  * Blocks: channel 0 = bins of dqmc_measure_timedisplaced, 1 = _pair, 2 = _ph, 3 = _current, 4 = _band (row stride 2N), 5 = _custom (row
- * stride count N, present while matrices are set), 6 = _custom_pair (row stride count N, present while pair operators are set); a channel has a
+ * stride count N, present while matrices are set), 6 = _custom_pair (row stride count N, present while pair operators are set), 7 = _green_matrix
+ * (row stride 2 R^2 N, present while dqmc_set_green_matrix is on); a channel has a
  * block if its coarse block is reserved.  Layout (doubles, dqmc_measure_td_fine_accum_size of them, 0 without the block): count[m+1], then row k = 0 .. m
  * at offset (m+1) + k stride, stride and contents of a row as in the coarse block: 4 (2L-1)^2, 2N, 3N, 2N + 2.
  * dqmc_measure_reset clears them as well. */
@@ -570,7 +597,7 @@ int dqmc_measure_td_matsubara_host(dqmc_ctx* ctx, int channel, int nfreq, double
  * dqmc_series_begin allocates, outside the arena, the sample [nb][S], the open bin [nb][S], the closed bins [max_bins][nb][S], the
  * per-part flags and the result buffer of the statistics calls.  DQMC_EINVAL: empty or unknown mask, a missing block, bin_size < 1,
  * max_bins < 2, a series already open, a Hubbard context, a lattice too large for the LDS of the Matsubara or sample kernel.
- * dqmc_series_layout: where part (= bit number 0 .. 4, 6: the order-parameter part, 7, 8: the band parts, all below) sits inside S.
+ * dqmc_series_layout: where part (= bit number 0 .. 4, 6: the order-parameter part, 7, 8: the band parts, 9 .. 13, all below) sits inside S.
  * dqmc_series_add_sweep (all chains): forms the sample and adds it to the open bin, open += sample, in call order; the bin_size-th call
  * writes closed[k] = open / bin_size and clears the open bin.  DQMC_EINVAL with no bin changed: the equal-time count of any chain or a
  * fine row count of any chain and channel of the mask is < 1; max_bins bins are already closed (nothing is dropped silently, and there
@@ -638,13 +665,31 @@ int dqmc_measure_td_matsubara_host(dqmc_ctx* ctx, int channel, int nfreq, double
  * The parts of the user-defined pair operators (dqmc_set_custom_pair_operators), behind all of the above again:
  * DQMC_SERIES_MATS_CUSTOM_PAIR = 2048 (bit 11: the Matsubara transform of every-slice channel 6, [count][nfreq][N] complex) and
  * DQMC_SERIES_EQ_CUSTOM_PAIR = 4096 (bit 12: the block of dqmc_set_equal_time_custom_pair as C(d) [count][N] then S(q) [count][N]).  Both
- * are refused (DQMC_EINVAL) while no pair operator is set; the accepted mask is 0x1fdf.  While a series with one of the two is open,
+ * are refused (DQMC_EINVAL) while no pair operator is set; with them the accepted mask was 0x1fdf (0x3fdf with the part below).  While a series with one of the two is open,
  * dqmc_set_custom_pair_operators returns DQMC_EINVAL.  dqmc_series_custom_pair_derived_host(qx, qy): R of every pair operator at the
  * caller's Q by the routine of dqmc_series_custom_derived_host (value and err [nb][count]; DQMC_EINVAL for B < 2, a series without
- * bit 12, qx or qy outside 0 .. L-1). */
+ * bit 12, qx or qy outside 0 .. L-1).
+ * The part of the averaged Green's function, DQMC_SERIES_GREEN_MATRIX = 8192 (bit 13, part index 13), behind all of the above: the
+ * normalised every-slice block of dqmc_set_green_matrix, Gbar_rc(d, tau_k) / (double(N) count) (one division), [m+1][N][R][R] complex as
+ * (re, im), formed by one launch.  It costs (m+1) 2 R^2 N doubles per chain and bin -- 0.8 MB at O(2), L = 16, m = 100 -- so max_bins is
+ * sized accordingly.  Refused (DQMC_EINVAL) unless the switch is on and the context has DQMC_TD_EVERY_SLICE; the accepted mask is 0x3fdf.
+ * Bins, re-binning, the running variance, routing, export and import treat it like every other part, through S alone.
+ * dqmc_series_pair_vertex_host(qx, qy) (all slots, every pair operator c; value and err [nb][count][5 + m],
+ * dqmc_series_pair_vertex_size doubles each, 0 where the call is refused): bubble and interaction vertex with jackknife errors.  For one
+ * set of bin means x -- the mean, or a leave-one-out mean x_(b) = (B mean - x_b) / (B - 1) -- with gbar(tau_k) rebuilt from part 13 of x:
+ *   Pbar_c(d, tau_k) = Re sum_ijkl D^d_ij conj(D^0_kl) [gbar(i; k) gbar(j; l) - gbar(i; l) gbar(j; k)]   (D of dqmc_set_custom_pair_operators
+ *                      with its link signs; gbar is translation-covariant, so the site pair (B (+) d, B) is evaluated at B = 0)
+ *   Pbar_c(Q, tau_k) = sum_d cos(Q d) Pbar_c(d, tau_k),   Pbar_c = dtau sum_k w_k Pbar_c(Q, tau_k),  w_0 = w_m = 1/2
+ *   P_c = Re chi_c(Q, i omega_0) of part 11,   Gamma_c = 1 / P_c - 1 / Pbar_c,   Gamma Pbar_c = Pbar_c / P_c - 1.
+ * Output per slot and operator: P, Pbar, Gamma, Gamma Pbar, then Pbar_c(Q, tau_k) for k = 0 .. m.  value = f(mean); err = the jackknife
+ * over theta_(b) = f(x_(b)) about the mean of the theta_(b), as dqmc_series_derived_host; an entry with a vanishing denominator is NaN.
+ * Gamma Pbar -> -1 marks the pairing instability; its sign says attractive or repulsive.  Two kernels: one workgroup per (slot, jackknife
+ * index, row) stages the row in LDS and reduces over d in a fixed tree; the second sums over k and the bins in index order.  No atomics:
+ * two calls give identical bits and a slot's result does not depend on batching.  DQMC_EINVAL: a series without bit 11 or bit 13, B < 2,
+ * qx or qy outside 0 .. L-1, a lattice whose row does not fit the LDS (2 R^2 N doubles + 8 KiB > 152 KiB). */
 enum { DQMC_SERIES_EQ = 1, DQMC_SERIES_MATS_G = 2, DQMC_SERIES_MATS_PAIR = 4, DQMC_SERIES_MATS_PH = 8, DQMC_SERIES_MATS_CURRENT = 16,
        DQMC_SERIES_PHI = 64, DQMC_SERIES_MATS_BAND = 128, DQMC_SERIES_EQ_BAND = 256, DQMC_SERIES_MATS_CUSTOM = 512, DQMC_SERIES_EQ_CUSTOM = 1024,
-       DQMC_SERIES_MATS_CUSTOM_PAIR = 2048, DQMC_SERIES_EQ_CUSTOM_PAIR = 4096 };
+       DQMC_SERIES_MATS_CUSTOM_PAIR = 2048, DQMC_SERIES_EQ_CUSTOM_PAIR = 4096, DQMC_SERIES_GREEN_MATRIX = 8192 };
 int dqmc_series_begin(dqmc_ctx* ctx, int bin_size, int max_bins, int nfreq, int parts);
 int dqmc_series_layout(dqmc_ctx* ctx, int part, size_t* offset, size_t* length);
 int dqmc_series_add_sweep(dqmc_ctx* ctx);
@@ -659,6 +704,8 @@ int dqmc_series_phi_derived_host(dqmc_ctx* ctx, double* value, double* err);
 int dqmc_series_band_derived_host(dqmc_ctx* ctx, double* value, double* err);
 int dqmc_series_custom_derived_host(dqmc_ctx* ctx, int qx, int qy, double* value, double* err);
 int dqmc_series_custom_pair_derived_host(dqmc_ctx* ctx, int qx, int qy, double* value, double* err);
+size_t dqmc_series_pair_vertex_size(dqmc_ctx* ctx);
+int dqmc_series_pair_vertex_host(dqmc_ctx* ctx, int qx, int qy, double* value, double* err);
 int dqmc_series_end(dqmc_ctx* ctx);
 /* ---- the series over a long run: re-binning, binning analysis with tau_int, export / import ------------
  * All of it is new surface: with none of these calls used, every call above keeps its bits, its error codes and its launches.
