@@ -284,6 +284,8 @@ SYMBOLS = [
     ("dqmc_series_custom_pair_derived_host", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
     ("dqmc_series_pair_vertex_size", C.c_size_t, [_P]),
     ("dqmc_series_pair_vertex_host", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
+    ("dqmc_series_ph_vertex_size", C.c_size_t, [_P]),
+    ("dqmc_series_ph_vertex_host", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
     ("dqmc_series_end", C.c_int, [_P]),
     ("dqmc_series_configure", C.c_int, [_P, C.c_int]),
     ("dqmc_series_get_state", C.c_int, [_P, C.POINTER(dqmc_series_state)]),
@@ -328,6 +330,7 @@ SYMBOLS = [
     ("detsdw_series_custom_pair_derived", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _DP, _DP]),
     ("detsdw_set_green_matrix", C.c_int, [_P, C.c_int]),
     ("detsdw_series_pair_vertex", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _DP, _DP]),
+    ("detsdw_series_ph_vertex", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _DP, _DP]),
     ("detsdw_series_read_bins", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _DP]),
     ("detsdw_series_end", C.c_int, [_P]),
     ("detsdw_series_configure", C.c_int, [_P, C.c_int]),

@@ -626,6 +626,7 @@ void series_free(dqmc_ctx* c) {
     for (double* q : {s.sample, s.openbin, s.bins, s.bad, s.trig, s.stat, s.var, s.binning, s.vertex}) if (q) (void)hipFree(q);
     if (s.srctab) (void)hipFree((void*)s.srctab);
     if (s.vertex_tab) (void)hipFree(s.vertex_tab);
+    if (s.ph_tab) (void)hipFree(s.ph_tab);
     s = dqmc_ctx::Series{};
 }
 

@@ -169,6 +169,8 @@ struct dqmc_ctx {
         size_t vertex_cap = 0;                                // allocated on first use and grown on demand (doubles)
         void *vertex_tab = nullptr;                           // ... its operator table and masks while no operator has a bond part (else
         CustomPair vertex_pair = {};                          // the measurement kernels' table serves): built by the first call
+        void *ph_tab = nullptr;                               // dqmc_series_ph_vertex_host (it shares the buffer `vertex`): the same for
+        CustomBond ph_bond = {};                              // the bilinears while none has a bond part
         const double** srctab = nullptr;
         std::vector<const double*> srchost;
     } ser;

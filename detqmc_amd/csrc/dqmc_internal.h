@@ -395,6 +395,12 @@ size_t series_pair_bubble_lds_bytes(int opdim, int N);
 bool launch_series_pair_vertex(const Launch& lc, const DevModel& hm, const double* bins, const double* mean, const double* trig, size_t S, int B,
                                int nfreq, size_t off_chi, size_t off_g, int count, const CustomPair& pair, int qx, int qy, int apbx, int apby,
                                double* pb, double* value, double* err);
+// particle-hole bubble and vertex of the user-defined bilinears from the closed bins (parts 9 and 13): bond: the stencil table of every set
+// operator; pb: nb (B + 1)(m + 1) count doubles of scratch; value, err [nb][count][6 + m]
+size_t series_ph_bubble_lds_bytes(int opdim, int N);
+bool launch_series_ph_vertex(const Launch& lc, const DevModel& hm, const double* bins, const double* mean, const double* trig, size_t S, int B,
+                             int nfreq, size_t off_chi, size_t off_g, int count, const CustomBond& bond, int qx, int qy, int apbx, int apby,
+                             double* pb, double* value, double* err);
 size_t measure_custom_row_doubles(int count, int N);
 size_t measure_td_custom_onebody_cplx(int count, int N);
 size_t measure_eq_custom_onebody_cplx(int count, int N);

@@ -159,6 +159,38 @@ static cplx custom_link(const dqmc_params& p, int mu, int site) {
     if (!p.weakZflux) return make_double2(sign, 0.0);
     return make_double2(sign * std::cos(arg), sign * std::sin(arg));
 }
+// the device table of the stencil kernels on the host (CustomBond in dqmc_internal.h): blocks M0, Mx, Mx^H, My, My^H of every operator,
+// then the link factors; mk the non-zero masks of the blocks, bond.parts the blocks an operator has
+static void custom_bond_table(const dqmc_ctx* c, int count, const dqmc_cplx* M, const dqmc_cplx* Mx, const dqmc_cplx* My, std::vector<cplx>& tab,
+                              std::vector<unsigned>& mk, CustomBond& bond) {
+    tab.assign(measure_custom_bond_table_cplx(count, c->N), make_double2(0.0, 0.0));
+    mk.assign((size_t)count * 5, 0u);
+    for (int ch = 0; ch < count; ++ch) {
+        cplx* v = tab.data() + (size_t)ch * 80;
+        for (int a = 0; a < 4; ++a)
+            for (int b = 0; b < 4; ++b) {
+                const dqmc_cplx zero{0.0, 0.0};
+                const dqmc_cplx m0 = M[16 * ch + 4 * a + b];
+                const dqmc_cplx x = Mx ? Mx[16 * ch + 4 * a + b] : zero, xt = Mx ? Mx[16 * ch + 4 * b + a] : zero;
+                const dqmc_cplx y = My ? My[16 * ch + 4 * a + b] : zero, yt = My ? My[16 * ch + 4 * b + a] : zero;
+                v[4 * a + b] = make_double2(m0.re, m0.im);
+                v[16 + 4 * a + b] = make_double2(x.re, x.im);
+                v[32 + 4 * a + b] = make_double2(xt.re, -xt.im);
+                v[48 + 4 * a + b] = make_double2(y.re, y.im);
+                v[64 + 4 * a + b] = make_double2(yt.re, -yt.im);
+            }
+        for (int k = 0; k < 5; ++k) {
+            unsigned bits = 0;
+            for (int e = 0; e < 16; ++e)
+                if (v[16 * k + e].x != 0.0 || v[16 * k + e].y != 0.0) bits |= 1u << e;
+            mk[(size_t)ch * 5 + k] = bits;
+            if (bits) bond.parts[ch] |= 1u << k;
+        }
+    }
+    cplx* lk = tab.data() + (size_t)count * 80;
+    for (int mu = 0; mu < 2; ++mu)
+        for (int site = 0; site < c->N; ++site) lk[(size_t)mu * c->N + site] = custom_link(c->p, mu, site);
+}
 // Both setters.  M0 [count][4][4] Hermitian, Mx / My arbitrary or nullptr (all zero); `who` names the entry in the messages.
 static int custom_set(dqmc_ctx* c, int count, const dqmc_cplx* M, const dqmc_cplx* Mx, const dqmc_cplx* My, const std::string& who) {
     if (!c) return fail(DQMC_EINVAL, "null ctx");
@@ -196,36 +228,10 @@ static int custom_set(dqmc_ctx* c, int count, const dqmc_cplx* M, const dqmc_cpl
     const size_t n_fine = n_td && c->td_fine ? (size_t)(c->m + 1) * (1 + row) : 0;
     const size_t ob_eq = count ? measure_eq_custom_onebody_cplx(count, c->N) : 0, ob_td = n_td ? measure_td_custom_onebody_cplx(count, c->N) : 0;
     // the device table of the stencil kernels: blocks M0, Mx, Mx^H, My, My^H of every operator, then the link factors
-    std::vector<cplx> tab(bonds ? measure_custom_bond_table_cplx(count, c->N) : 0);
-    std::vector<unsigned> mk(bonds ? (size_t)count * 5 : 0);
+    std::vector<cplx> tab;
+    std::vector<unsigned> mk;
     CustomBond bond{};
-    if (bonds) {
-        for (int ch = 0; ch < count; ++ch) {
-            cplx* v = tab.data() + (size_t)ch * 80;
-            for (int a = 0; a < 4; ++a)
-                for (int b = 0; b < 4; ++b) {
-                    const dqmc_cplx zero{0.0, 0.0};
-                    const dqmc_cplx m0 = M[16 * ch + 4 * a + b];
-                    const dqmc_cplx x = Mx ? Mx[16 * ch + 4 * a + b] : zero, xt = Mx ? Mx[16 * ch + 4 * b + a] : zero;
-                    const dqmc_cplx y = My ? My[16 * ch + 4 * a + b] : zero, yt = My ? My[16 * ch + 4 * b + a] : zero;
-                    v[4 * a + b] = make_double2(m0.re, m0.im);
-                    v[16 + 4 * a + b] = make_double2(x.re, x.im);
-                    v[32 + 4 * a + b] = make_double2(xt.re, -xt.im);
-                    v[48 + 4 * a + b] = make_double2(y.re, y.im);
-                    v[64 + 4 * a + b] = make_double2(yt.re, -yt.im);
-                }
-            for (int k = 0; k < 5; ++k) {
-                unsigned bits = 0;
-                for (int e = 0; e < 16; ++e)
-                    if (v[16 * k + e].x != 0.0 || v[16 * k + e].y != 0.0) bits |= 1u << e;
-                mk[(size_t)ch * 5 + k] = bits;
-                if (bits) bond.parts[ch] |= 1u << k;
-            }
-        }
-        cplx* lk = tab.data() + (size_t)count * 80;
-        for (int mu = 0; mu < 2; ++mu)
-            for (int site = 0; site < c->N; ++site) lk[(size_t)mu * c->N + site] = custom_link(c->p, mu, site);
-    }
+    if (bonds) custom_bond_table(c, count, M, Mx, My, tab, mk, bond);
     double *eq = nullptr, *td = nullptr, *fine = nullptr;
     cplx *oe = nullptr, *ot = nullptr, *dtab = nullptr;
     unsigned* dmk = nullptr;
@@ -1183,6 +1189,67 @@ extern "C" int dqmc_series_pair_vertex_host(dqmc_ctx* c, int qx, int qy, double*
         launch_series_stats(c->lc, s.bins, n, B, s.stat, s.stat + n);
         launched = launch_series_pair_vertex(c->lc, c->hm, s.bins, s.stat, s.trig, s.S, B, s.nfreq, s.off[11], s.off[13], count, pair, qx, qy,
                                              ser_apbx(c), ser_apby(c), pb, dv, de);
+    }
+    if (!launched) return fail(DQMC_EINVAL, who + ": the lattice is too large for the bubble kernel's LDS");
+    { const int rc = finish(c, who.c_str()); if (rc != DQMC_OK) return rc; }
+    HIPCHK(copy_sync(c, value, dv, n_out * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(c, err, de, n_out * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+// Particle-hole bubble and vertex of every user-defined bilinear at Q = (qx, qy) (dqmc_hip.h): the bin means, then the two kernels of
+// launch_series_ph_vertex.  s.vertex holds the bubbles pb [nb][B + 1][m + 1][count], then value and err [nb][count][6 + m] each
+static bool series_ph_vertex_ok(const dqmc_ctx* c) {
+    return c && c->ser.open && (c->ser.parts & DQMC_SERIES_MATS_CUSTOM) && (c->ser.parts & DQMC_SERIES_GREEN_MATRIX) && c->cst_count > 0;
+}
+extern "C" size_t dqmc_series_ph_vertex_size(dqmc_ctx* c) {
+    if (!series_ph_vertex_ok(c)) return 0;
+    return (size_t)c->nb * c->cst_count * (6 + c->m);
+}
+extern "C" int dqmc_series_ph_vertex_host(dqmc_ctx* c, int qx, int qy, double* value, double* err) {
+    const std::string who = "dqmc_series_ph_vertex_host";
+    if (!c || !value || !err) return fail(DQMC_EINVAL, "null argument");
+    dqmc_ctx::Series& s = c->ser;
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (!(s.parts & DQMC_SERIES_MATS_CUSTOM) || !(s.parts & DQMC_SERIES_GREEN_MATRIX) || s.nfreq < 1)
+        return fail(DQMC_EINVAL, who + ": the series needs the Matsubara part of the user-defined bilinears (bit 9) and the averaged Green's function (bit 13)");
+    if (!c->cst_count) return fail(DQMC_EINVAL, who + ": no user-defined bilinear is set (dqmc_set_custom_bilinears)");
+    if (qx < 0 || qx >= c->hm.L || qy < 0 || qy >= c->hm.L) return fail(DQMC_EINVAL, who + ": qx and qy must be in 0 .. L-1");
+    if (s.closed < 2) return fail(DQMC_EINVAL, who + ": the jackknife needs at least two closed bins");
+    if (series_ph_bubble_lds_bytes(c->p.opdim, c->N) > 152 * 1024) return fail(DQMC_EINVAL, who + ": the lattice is too large for the bubble kernel's LDS");
+    (void)hipSetDevice(c->p.device);
+    const int count = c->cst_count, B = s.closed;
+    // the operator table: the measurement kernels' own while an operator has a bond part; otherwise built once per series (the
+    // operators cannot change while a series holds bit 9) and kept in an allocation of its own, the table and then its masks
+    if (!c->cst_bond_on && !s.ph_tab) {
+        std::vector<dqmc_cplx> M0;
+        for (int e = 0; e < 16 * count; ++e) M0.push_back(dqmc_cplx{c->cst_M[e].x, c->cst_M[e].y});
+        std::vector<cplx> tab;
+        std::vector<unsigned> mk;
+        CustomBond bond{};
+        custom_bond_table(c, count, M0.data(), nullptr, nullptr, tab, mk, bond);
+        HIPCHK(hipMalloc((void**)&s.ph_tab, tab.size() * sizeof(cplx) + mk.size() * sizeof(unsigned)));
+        bond.tab = (const cplx*)s.ph_tab; bond.mk = (const unsigned*)((const cplx*)s.ph_tab + tab.size());
+        hipError_t e = copy_sync(c, s.ph_tab, tab.data(), tab.size() * sizeof(cplx), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = copy_sync(c, (void*)bond.mk, mk.data(), mk.size() * sizeof(unsigned), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(s.ph_tab); s.ph_tab = nullptr; HIPCHK(e); }
+        s.ph_bond = bond;
+    }
+    const CustomBond& bond = c->cst_bond_on ? c->cst_bond : s.ph_bond;
+    const size_t n = (size_t)c->nb * s.S, n_pb = (size_t)c->nb * (B + 1) * (c->m + 1) * count, n_out = dqmc_series_ph_vertex_size(c);
+    const size_t need = n_pb + 2 * n_out;
+    if (need > s.vertex_cap) {
+        HIPCHK(hipStreamSynchronize(c->st));
+        if (s.vertex) { (void)hipFree(s.vertex); s.vertex = nullptr; s.vertex_cap = 0; }
+        HIPCHK(hipMalloc((void**)&s.vertex, need * sizeof(double)));
+        s.vertex_cap = need;
+    }
+    double *pb = s.vertex, *dv = pb + n_pb, *de = dv + n_out;
+    bool launched;
+    {
+        ProfScope ps(c, FAM_OTHER, 3);
+        launch_series_stats(c->lc, s.bins, n, B, s.stat, s.stat + n);
+        launched = launch_series_ph_vertex(c->lc, c->hm, s.bins, s.stat, s.trig, s.S, B, s.nfreq, s.off[9], s.off[13], count, bond, qx, qy,
+                                           ser_apbx(c), ser_apby(c), pb, dv, de);
     }
     if (!launched) return fail(DQMC_EINVAL, who + ": the lattice is too large for the bubble kernel's LDS");
     { const int rc = finish(c, who.c_str()); if (rc != DQMC_OK) return rc; }

@@ -1123,6 +1123,25 @@ void DetSDW::seriesPairVertex(int c, int qx, int qy, double* value, double* err)
         }
     }
 }
+// Particle-hole bubble and vertex of user-defined bilinear c at Q = (qx, qy) for every slot in handle order: value, err [nchains][6 + m]
+void DetSDW::seriesPhVertex(int c, int qx, int qy, double* value, double* err) {
+    if (!series_.open) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
+    if (!(series_.parts & DQMC_SERIES_MATS_CUSTOM) || !(series_.parts & DQMC_SERIES_GREEN_MATRIX))
+        throw ParameterWrong("the particle-hole vertex needs matrices set by detsdw_set_custom_bilinears and detsdw_set_green_matrix before the series began, "
+                             "with timeDisplacedParticleHole and timeDisplacedEverySlice");
+    const int nc = customCount();
+    if (c < 0 || c >= nc) throw ParameterWrong("no user-defined bilinear with this index is set");
+    const size_t per = (size_t)6 + m_;
+    std::vector<double> v, e;
+    for (auto& g : groups_) {
+        v.resize((size_t)g.count * nc * per); e.resize(v.size());
+        check(dqmc_series_ph_vertex_host(g.ctx, qx, qy, v.data(), e.data()), "dqmc_series_ph_vertex_host");
+        for (int b = 0; b < g.count; ++b) {
+            std::memcpy(value + (size_t)(g.first + b) * per, &v[((size_t)b * nc + c) * per], per * sizeof(double));
+            std::memcpy(err + (size_t)(g.first + b) * per, &e[((size_t)b * nc + c) * per], per * sizeof(double));
+        }
+    }
+}
 // The averaged Green's function block of every kernel context; if a later context fails the earlier ones are switched back
 void DetSDW::setGreenMatrix(bool on) {
     if (on && !td_level(ch_[0].pars)) throw ParameterWrong("detsdw_set_green_matrix needs timeDisplacedMeasurements");
@@ -2000,6 +2019,10 @@ extern "C" int detsdw_set_green_matrix(detsdw_replica* r, int on) {
 extern "C" int detsdw_series_pair_vertex(detsdw_replica* r, int c, int qx, int qy, double* value, double* err) {
     if (!value || !err) { g_host_err = "null argument"; return DQMC_EINVAL; }
     RGUARD(r->impl->seriesPairVertex(c, qx, qy, value, err))
+}
+extern "C" int detsdw_series_ph_vertex(detsdw_replica* r, int c, int qx, int qy, double* value, double* err) {
+    if (!value || !err) { g_host_err = "null argument"; return DQMC_EINVAL; }
+    RGUARD(r->impl->seriesPhVertex(c, qx, qy, value, err))
 }
 extern "C" int detsdw_set_custom_bilinears(detsdw_replica* r, int count, const dqmc_cplx* M) {
     RGUARD(r->impl->setCustomBilinears(count, M))

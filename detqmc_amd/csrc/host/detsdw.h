@@ -83,6 +83,7 @@ public:
     // the averaged Green's function block of every kernel context, and the bubble / vertex of pair operator c from the series
     void setGreenMatrix(bool on);
     void seriesPairVertex(int c, int qx, int qy, double* value, double* err);
+    void seriesPhVertex(int c, int qx, int qy, double* value, double* err);      // ... of user-defined bilinear c
     void seriesReadBins(int which, int first, int count, double* out, int b = 0);
     // long runs: options, re-binning, binning analysis (err, tau [levels] x the slice of seriesStats; tau may be null), series file
     void seriesConfigure(int flags);

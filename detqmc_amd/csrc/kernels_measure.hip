@@ -2092,6 +2092,204 @@ bool launch_series_pair_vertex(const Launch& lc, const DevModel& hm, const doubl
     return true;
 }
 
+// Particle-hole bubble and vertex of the user-defined bilinears from the series (dqmc_series_ph_vertex_host; dqmc_hip.h and DESIGN.md
+// 6e), two kernels in the shape of the pair ones above.
+// k_series_ph_bubble, grid (row k = 0 .. m, jackknife index b = 0 .. B, slot), 256 threads: rows k and m - k of part 13 for index b are
+// staged in LDS (the leave-one-out mean as in k_series_pair_bubble); with
+//   gbar(tau_k,0)(P r; Q c) = sigma(Q, P (-) Q) gbar_rc(P (-) Q; tau_k),      gbar(0,tau_k) = -gbar(tau_{m-k},0)
+// (the cyclic invariance of the weight; the end rows carry the delta term) thread d evaluates the connected term of cstb_walk -- the
+// same table, masks, link factors and cstb_connected -- for the site pair (A, B) = (d, 0), with E from row k and T from row m - k, and adds
+// cos(Q d) chibar_c(d) to its sum; a fixed tree over the 256 sums follows, and thread c writes pb[slot][b][k][c].
+// k_series_ph_vertex, one thread per (slot, operator, output): the one-body value obar_c of row 0 at site 0, the tau quadrature of pb and
+// the jackknife over b in index order.
+struct PhVertexShape { size_t S, off_g, off_chi; int L, N, m, nfreq, nb, B, count, qx, qy, apbx, apby, R; double dtau; };
+size_t series_ph_bubble_lds_bytes(int opdim, int N) { return (2 * measure_green_matrix_row_doubles(opdim, N) + (size_t)DQMC_CUSTOM_MAX * 256) * sizeof(double); }
+// the sites (p, q) of block k at the stencil S = (sx, sy), Sx = (sxp, sy), Sy = (sx, syp) as coordinates, and its link factor (cstb_block)
+__device__ __forceinline__ void phv_block(int k, int sx, int sy, int sxp, int syp, cplx ux, cplx uy, int& px, int& py, int& qx, int& qy, cplx& f) {
+    px = k == 1 ? sxp : sx; py = k == 3 ? syp : sy;
+    qx = k == 2 ? sxp : sx; qy = k == 4 ? syp : sy;
+    const cplx u = k < 3 ? ux : uy;
+    f = k == 0 ? make_double2(1.0, 0.0) : make_double2(u.x, (k & 1) ? u.y : -u.y);
+}
+template<int OPDIM>
+__global__ __launch_bounds__(256) void k_series_ph_bubble(const double* __restrict__ bins, const double* __restrict__ mean,
+                                                          const double* __restrict__ trig, CustomBondArg cb, PhVertexShape a,
+                                                          double* __restrict__ pb) {
+    constexpr int R = OPDIM == 3 ? 4 : 2;
+    extern __shared__ __attribute__((aligned(16))) double phv_sm[];
+    const int N = a.N, L = a.L, tid = threadIdx.x, count = cb.count, B = a.B;
+    const int k = blockIdx.x, b = blockIdx.y, slot = blockIdx.z;
+    const size_t rowlen = (size_t)2 * R * R * N, n = (size_t)a.nb * a.S, part = (size_t)slot * a.S + a.off_g;
+    double* red = phv_sm + 2 * rowlen;                      // [DQMC_CUSTOM_MAX][256]
+    for (size_t e = tid; e < 2 * rowlen; e += 256) {        // row k, then row m - k
+        const size_t src = part + (size_t)(e < rowlen ? k : a.m - k) * rowlen + (e < rowlen ? e : e - rowlen);
+        const double mu = mean[src];
+        phv_sm[e] = b < B ? ((double)B * mu - bins[(size_t)b * n + src]) / (double)(B - 1) : mu;
+    }
+    __syncthreads();
+    const cplx* gk = (const cplx*)phv_sm;
+    const cplx* gr = gk + (size_t)R * R * N;
+    const cplx* __restrict__ lk = cb.tab + (size_t)count * CSTB_K * 16;
+    unsigned both[DQMC_CUSTOM_MAX];                         // bit 5 ka + kb: operator ch has the blocks ka and kb
+    unsigned need = 0;
+#pragma unroll
+    for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) {
+        both[ch] = 0;
+        if (ch < count)
+            for (int ka = 0; ka < CSTB_K; ++ka)
+                if ((cb.parts[ch] >> ka) & 1u) both[ch] |= (cb.parts[ch] & 0x1fu) << (CSTB_K * ka);
+        need |= both[ch];
+    }
+    double w[DQMC_CUSTOM_MAX] = {0.0, 0.0, 0.0, 0.0};
+    const int B1 = 1 % L;                                   // the neighbours of site B = 0: (1, 0) and (0, 1)
+    const cplx ubx = lk[0], uby = lk[N];
+    for (int d = tid; d < N; d += 256) {
+        const int ax = d % L, ay = d / L;
+        const int axp = ax + 1 == L ? 0 : ax + 1, ayp = ay + 1 == L ? 0 : ay + 1;
+        const cplx uax = lk[d], uay = lk[N + d];
+        double v[DQMC_CUSTOM_MAX] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 1
+        for (int pr = 0; pr < CSTB_K * CSTB_K; ++pr) {
+            if (!((need >> pr) & 1u)) continue;
+            const int ka = pr / CSTB_K, kb = pr % CSTB_K;
+            int px, py, qx, qy, rx, ry, sx, sy;
+            cplx fa, fb;
+            phv_block(ka, ax, ay, axp, ayp, uax, uay, px, py, qx, qy, fa);
+            phv_block(kb, 0, 0, B1, B1, ubx, uby, rx, ry, sx, sy, fb);
+            const cplx f = m_mul(fa, fb);
+            cplx e[R][R], t[R][R];
+            pvx_load<R>(gk, L, a.apbx, a.apby, qx, qy, rx, ry, e);          // E_bc = gbar(tau_k,0)(A^q b; B^r c)
+            pvx_load<R>(gr, L, a.apbx, a.apby, sx, sy, px, py, t);          // T_da = -gbar(tau_{m-k},0)(B^s d; A^p a)
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+#pragma unroll
+                for (int c2 = 0; c2 < R; ++c2) {
+                    e[r][c2] = m_mul(f, e[r][c2]);
+                    t[r][c2] = make_double2(-t[r][c2].x, -t[r][c2].y);
+                }
+#pragma unroll
+            for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
+                if ((both[ch] >> pr) & 1u) {
+                    const cplx* __restrict__ V = cb.tab + (size_t)ch * CSTB_K * 16;
+                    v[ch] -= cstb_connected<OPDIM, R>(e, t, V + 16 * ka, cb.mk[ch * CSTB_K + ka], V + 16 * kb, cb.mk[ch * CSTB_K + kb]);
+                }
+        }
+        const double cq = trig[(a.qx * ax + a.qy * ay) % L];
+#pragma unroll
+        for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) w[ch] += cq * v[ch];
+    }
+#pragma unroll
+    for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) red[ch * 256 + tid] = w[ch];
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {                     // a fixed tree: the same order in every launch
+        if (tid < h)
+#pragma unroll
+            for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) red[ch * 256 + tid] += red[ch * 256 + tid + h];
+        __syncthreads();
+    }
+    if (tid < count) pb[(((size_t)slot * (B + 1) + b) * (a.m + 1) + k) * count + tid] = red[tid * 256];
+}
+// outputs per (slot, operator): 0 chi = Re chi(Q, i omega_0) of part 9 - D, 1 chibar = dtau sum_k w_k pb, 2 Gamma = 1 / chi - 1 / chibar,
+// 3 Gamma chibar = chibar / chi - 1, 4 D = beta Re(obar^2) sum_d cos(Q d), then pb at k = 0 .. m; NaN where a denominator vanishes
+__device__ __forceinline__ double phv_f(int e, double chi, double chib, double D) {
+    if (e == 0) return chi;
+    if (e == 1) return chib;
+    if (e == 4) return D;
+    if (chi == 0.0 || (e == 2 && chib == 0.0)) return nan("");
+    return e == 2 ? 1.0 / chi - 1.0 / chib : chib / chi - 1.0;
+}
+__global__ __launch_bounds__(64) void k_series_ph_vertex(const double* __restrict__ bins, const double* __restrict__ mean, const double* __restrict__ pb,
+                                                         CustomBondArg cb, PhVertexShape a, double* __restrict__ value, double* __restrict__ err) {
+    const int per = 6 + a.m, t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= a.nb * a.count * per) return;
+    const int slot = t / (a.count * per), c = (t / per) % a.count, e = t % per, B = a.B, m = a.m, L = a.L, N = a.N, R = a.R;
+    const size_t n = (size_t)a.nb * a.S;
+    const double* p = bins + (size_t)slot * a.S + a.off_chi + ((size_t)c * a.nfreq * N + (size_t)a.qy * L + a.qx) * 2;     // Re, frequency 0
+    const double* r0 = pb + (size_t)slot * (B + 1) * (m + 1) * a.count + c;
+    const size_t g0 = (size_t)slot * a.S + a.off_g;         // row 0 of part 13
+    const cplx* __restrict__ V = cb.tab + (size_t)c * CSTB_K * 16;
+    const cplx* __restrict__ lk = cb.tab + (size_t)a.count * CSTB_K * 16;
+    const cplx ux = lk[0], uy = lk[N];
+    const int B1 = 1 % L;
+    const double dsum = (a.qx == 0 && a.qy == 0) ? (double)N : 0.0;      // sum_d cos(Q d)
+    unsigned parts = 0;                                     // cb.parts[c] without a run-time index into the kernel argument
+#pragma unroll
+    for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
+        if (ch == c) parts = cb.parts[ch];
+    double sum = 0.0;
+    for (int b = 0; b < B; ++b) sum += p[(size_t)b * n];
+    const double mu = sum / (double)B, tot = (double)B * mu;
+    // obar of jackknife index b: tr M0 - sum_k f_k sum_ab (W_k)_ab gbar(A^q b; A^p a) at A = 0 (cstb_onebody on the rebuilt matrix)
+    auto onebody = [&](int b) {
+        cplx s = make_double2(0.0, 0.0);
+        for (int k = 0; k < CSTB_K; ++k) {
+            if (!((parts >> k) & 1u)) continue;
+            int px, py, qx, qy;
+            cplx f;
+            phv_block(k, 0, 0, B1, B1, ux, uy, px, py, qx, qy, f);
+            int dx = qx - px, dy = qy - py;                 // gbar(P = A^q .; Q = A^p .) = sigma(Q, P (-) Q) gbar(P (-) Q)
+            if (dx < 0) dx += L;
+            if (dy < 0) dy += L;
+            const double sg = ((a.apbx && px + dx >= L) != (a.apby && py + dy >= L)) ? -1.0 : 1.0;
+            const size_t blk = g0 + (size_t)(dy * L + dx) * 2 * R * R;
+            const unsigned mask = cb.mk[c * CSTB_K + k];
+            for (int i = 0; i < 4; ++i)
+                for (int j = 0; j < 4; ++j) {
+                    if (!(mask & (1u << (4 * i + j)))) continue;
+                    if (R == 2 && (i < 2) != (j < 2)) continue;         // the blocks between the sectors vanish
+                    const bool cj = R == 2 && i >= 2;                   // the conjugate sector
+                    const size_t src = blk + (size_t)2 * ((j & (R - 1)) * R + (i & (R - 1)));    // element (j, i) of the stored block
+                    double re = mean[src], im = mean[src + 1];
+                    if (b < B) {
+                        re = ((double)B * re - bins[(size_t)b * n + src]) / (double)(B - 1);
+                        im = ((double)B * im - bins[(size_t)b * n + src + 1]) / (double)(B - 1);
+                    }
+                    cplx x = m_mul(f, make_double2(sg * re, sg * im));
+                    if (cj) x.y = -x.y;
+                    cst_fma(s, V[16 * k + 4 * i + j], x);
+                }
+        }
+        return m_sub(m_add(m_add(V[0], V[5]), m_add(V[10], V[15])), s);
+    };
+    auto theta = [&](int b) {
+        const double* r = r0 + (size_t)b * (m + 1) * a.count;
+        if (e >= 5) return r[(size_t)(e - 5) * a.count];
+        double s = 0.0;
+        for (int k = 0; k <= m; ++k) s += (k == 0 || k == m ? 0.5 : 1.0) * r[(size_t)k * a.count];
+        const cplx o = onebody(b);
+        const double D = a.dtau * (double)m * (o.x * o.x - o.y * o.y) * dsum;
+        return phv_f(e, (b < B ? (tot - p[(size_t)b * n]) / (double)(B - 1) : mu) - D, a.dtau * s, D);
+    };
+    double tsum = 0.0;
+    for (int b = 0; b < B; ++b) tsum += theta(b);
+    const double tbar = tsum / (double)B;
+    double acc = 0.0;
+    for (int b = 0; b < B; ++b) {
+        const double dl = theta(b) - tbar;
+        acc += dl * dl;
+    }
+    value[t] = theta(B);
+    err[t] = sqrt((double)(B - 1) / (double)B * acc);
+}
+// false: the lattice is too large for the bubble kernel's LDS, nothing was launched.  mean: the bin means [nb][S] (launch_series_stats)
+bool launch_series_ph_vertex(const Launch& lc, const DevModel& hm, const double* bins, const double* mean, const double* trig, size_t S, int B,
+                             int nfreq, size_t off_chi, size_t off_g, int count, const CustomBond& bond, int qx, int qy, int apbx, int apby,
+                             double* pb, double* value, double* err) {
+    const size_t lds = series_ph_bubble_lds_bytes(hm.opdim, hm.N);
+    if (lds > 152 * 1024) return false;
+    const CustomBondArg cb = custom_bond_arg(count, bond);
+    const PhVertexShape a{S, off_g, off_chi, hm.L, hm.N, hm.m, nfreq, lc.nb, B, count, qx, qy, apbx, apby, hm.opdim == 3 ? 4 : 2, hm.dtau};
+    const dim3 grid((unsigned)(hm.m + 1), (unsigned)(B + 1), (unsigned)lc.nb);
+    const void* fn = hm.opdim == 1 ? (const void*)k_series_ph_bubble<1> : hm.opdim == 2 ? (const void*)k_series_ph_bubble<2> : (const void*)k_series_ph_bubble<3>;
+    if (lds > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) (void)hipGetLastError();
+    if (hm.opdim == 1) hipLaunchKernelGGL((k_series_ph_bubble<1>), grid, dim3(256), lds, lc.st, bins, mean, trig, cb, a, pb);
+    else if (hm.opdim == 2) hipLaunchKernelGGL((k_series_ph_bubble<2>), grid, dim3(256), lds, lc.st, bins, mean, trig, cb, a, pb);
+    else hipLaunchKernelGGL((k_series_ph_bubble<3>), grid, dim3(256), lds, lc.st, bins, mean, trig, cb, a, pb);
+    const int total = lc.nb * count * (6 + hm.m);
+    hipLaunchKernelGGL(k_series_ph_vertex, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, lc.st, bins, mean, pb, cb, a, value, err);
+    return true;
+}
+
 // End rows of the every-slice blocks (dqmc_measure_timedisplaced_ends): from the equal-time G = G(0), one elementwise pass writes
 //   tau = 0+:    G(0+,0) = G,          G(0,0+) = G - 1          -> a_t0, a_0t
 //   tau = beta-: G(beta-,0) = 1 - G,   G(0,beta-) = -G          -> b_t0, b_0t

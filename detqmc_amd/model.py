@@ -183,6 +183,17 @@ def pair_vertex_quantity(name):
     return (PAIR_VERTEX_QUANTITIES[m.group(1)], int(m.group(2))) if m else None
 
 
+# ... of the particle-hole vertex of the custom bilinears: name prefix -> entry of detsdw_series_ph_vertex
+PH_VERTEX_QUANTITIES = {"vertexCustom": 0, "bubbleCustom": 1, "gammaCustom": 2, "gammaBubbleCustom": 3, "disconnectedCustom": 4}
+
+
+def ph_vertex_quantity(name):
+    """(entry, matrix index c) of 'vertexCustom{c}' (chi = Re chi(Q, i omega_0) - D), 'bubbleCustom{c}' (chibar), 'gammaCustom{c}'
+    (Gamma = 1/chi - 1/chibar), 'gammaBubbleCustom{c}' (Gamma chibar = chibar/chi - 1) or 'disconnectedCustom{c}' (D); None for any other name"""
+    m = re.fullmatch(r"(vertexCustom|bubbleCustom|gammaCustom|gammaBubbleCustom|disconnectedCustom)([0-3])", name)
+    return (PH_VERTEX_QUANTITIES[m.group(1)], int(m.group(2))) if m else None
+
+
 def _matsubara_index(name):
     """index of detsdw_get_matsubara for a name of MATSUBARA, 'custom{c}Tau' or 'customPair{c}Tau'; KeyError otherwise"""
     cw = custom_observable(name) or custom_pair_observable(name)
@@ -387,6 +398,79 @@ def pair_bubble(gbar, ops, L, bc="pbc"):
                 acc = acc + ua * (direct - exchange).real
         out.append(acc)
     return np.stack(out, axis=-2) if out else np.zeros(g.shape[:-3] + (0, N))
+
+
+def _ph_full(gbar, L, bc, lead):
+    """(full 4 x 4 blocks (..., N, 4, 4), antiperiodic flags) of a normalised block of set_green_matrix with at least `lead` leading axes"""
+    g = np.asarray(gbar, dtype=np.complex128)
+    N, R = L * L, g.shape[-1]
+    if bc not in ("pbc", "apbc-x", "apbc-y", "apbc-xy") or g.ndim < 3 + lead or g.shape[-3:] != (N, R, R) or R not in (2, 4):
+        raise ValueError("gbar must be (..., L L, R, R) with R = 2 or 4, bc one of 'pbc', 'apbc-x', 'apbc-y', 'apbc-xy'")
+    if R == 2:
+        full = np.zeros(g.shape[:-2] + (4, 4), dtype=np.complex128)
+        full[..., :2, :2] = g
+        full[..., 2:, 2:] = np.conj(g)
+        g = full
+    return g, (bc in ("apbc-x", "apbc-xy"), bc in ("apbc-y", "apbc-xy"))
+
+
+def _ph_block(g, L, apb, P, Q):
+    """g(P .; Q .) = sigma(Q, P - Q) g[..., P - Q, :, :] for site coordinate arrays P = (px, py), Q = (qx, qy) of one length: (..., n, 4, 4)"""
+    dx, dy = (P[0] - Q[0]) % L, (P[1] - Q[1]) % L
+    sg = np.where(apb[0] & (Q[0] + dx >= L), -1.0, 1.0) * np.where(apb[1] & (Q[1] + dy >= L), -1.0, 1.0)
+    return sg[:, None, None] * g[..., dy * L + dx, :, :]
+
+
+def _ph_stencil(op, L, apb, sx, sy):
+    """the five site blocks V_k(S) = f_k(S) W_k of the operator (M0, Mx, My) at the sites S = (sx, sy) (arrays): a list of
+    (W_k, p, q, f_k) with W = M0, Mx, Mx^H, My, My^H, p the site of c^+, q that of c, f_k = +-1 the link sign; zero blocks are left out"""
+    zero = np.zeros((4, 4), dtype=np.complex128)
+    M0, Mx, My = (zero if m is None else np.asarray(m, dtype=np.complex128) for m in op)
+    S, Sx, Sy = (sx, sy), ((sx + 1) % L, sy), (sx, (sy + 1) % L)
+    ux, uy = np.where(apb[0] & (sx == L - 1), -1.0, 1.0), np.where(apb[1] & (sy == L - 1), -1.0, 1.0)
+    blocks = [(M0, S, S, np.ones(len(sx))), (Mx, Sx, S, ux), (Mx.conj().T, S, Sx, ux), (My, Sy, S, uy), (My.conj().T, S, Sy, uy)]
+    return [b for b in blocks if b[0].any()]
+
+
+def ph_bubble(gbar, ops, L, bc="pbc"):
+    """The particle-hole bubble chibar_c(d, tau_k) of the bilinears `ops` (a list of (M0, Mx, My) as set_custom_bond_bilinears takes them; an
+    on-site matrix M is (M, None, None)) on an averaged Green's function: the numpy counterpart of the device's bubble kernel.
+    gbar: complex (..., m+1, N, R, R), all rows k = 0 .. m of the normalised block of set_green_matrix (see pair_bubble for the block, the
+    sign sigma and the sectors); leading axes (bins) are carried along.  With gbar(0, tau_k) = -gbar(tau_{m-k}, 0) -- the cyclic invariance
+    of the weight -- returns the real array (..., m+1, count, N),
+        chibar_c(d, tau_k) = -sum_{k, k'} Re f_k(A) f_k'(B) tr(W_k gbar(tau_k,0)(A^q; B^r) W_k' gbar(0,tau_k)(B^s; A^p)),   (A, B) = (d, 0),
+    the connected Wick term of <O_A(tau_k) O_B(0)> over the five site blocks V_k = f_k W_k of each operator (W = M0, Mx, Mx^H, My, My^H
+    between the sites (p, q) = (A, A), (A + x, A), (A, A + x), (A + y, A), (A, A + y), f_k the link sign)."""
+    g, apb = _ph_full(gbar, L, bc, 1)
+    N = L * L
+    gt = -np.flip(g, axis=-4)                               # gbar(0, tau_k)
+    ax, ay = np.arange(N) % L, np.arange(N) // L
+    zx = np.zeros(N, dtype=int)
+    out = []
+    for op in ops:
+        acc = np.zeros(g.shape[:-3] + (N,))
+        for WA, pA, qA, fA in _ph_stencil(op, L, apb, ax, ay):
+            for WB, rB, sB, fB in _ph_stencil(op, L, apb, zx, zx):
+                tr = np.einsum("ab,...bc,cd,...da->...", WA, _ph_block(g, L, apb, qA, rB), WB, _ph_block(gt, L, apb, sB, pA), optimize=True)
+                acc = acc - fA * fB * tr.real
+        out.append(acc)
+    return np.stack(out, axis=-2) if out else np.zeros(g.shape[:-3] + (0, N))
+
+
+def ph_one_body(gbar0, ops, L, bc="pbc"):
+    """The one-body value obar_c = tr M0 - sum_ij (O_0)_ij gbar(tau_0,0)(j; i) of the bilinears `ops` at site 0 (it does not depend on the
+    site for a translation-covariant matrix).  gbar0: complex (..., N, R, R), row 0 of the block ph_bubble takes.  Returns complex
+    (..., count); the disconnected part of chi_c(Q = 0, i omega_0) is beta N Re(obar_c^2)."""
+    g, apb = _ph_full(gbar0, L, bc, 0)
+    z = np.zeros(1, dtype=int)
+    out = []
+    for op in ops:
+        M0 = np.zeros((4, 4), dtype=np.complex128) if op[0] is None else np.asarray(op[0], dtype=np.complex128)
+        acc = np.trace(M0) + np.zeros(g.shape[:-3], dtype=np.complex128)
+        for W, p, q, f in _ph_stencil(op, L, apb, z, z):
+            acc = acc - f[0] * np.einsum("ab,...ba->...", W, _ph_block(g, L, apb, q, p)[..., 0, :, :])
+        out.append(acc)
+    return np.stack(out, axis=-1) if out else np.zeros(g.shape[:-3] + (0,), dtype=np.complex128)
 
 
 class KernelContext:
@@ -733,6 +817,16 @@ class KernelContext:
         v, e = np.zeros(max(n, 1)), np.zeros(max(n, 1))
         check(self.lib.dqmc_series_pair_vertex_host(self.h, int(Q[0]), int(Q[1]), v.ctypes.data_as(_lib._DP), e.ctypes.data_as(_lib._DP)))
         return v.reshape(self.nchains_total(), -1, 5 + self.m), e.reshape(self.nchains_total(), -1, 5 + self.m)
+
+    def series_ph_vertex(self, Q=(0, 0)):
+        """particle-hole bubble and vertex of every custom bilinear at Q = (qx, qy), of a series with SERIES_MATS_CUSTOM |
+        SERIES_GREEN_MATRIX: (value, err), (nchains, count, 6 + m) each -- chi = Re chi(Q, i omega_0) - D, chibar (the connected Wick term on
+        the averaged Green's function, ph_bubble), Gamma = 1/chi - 1/chibar, Gamma chibar = chibar/chi - 1, D = beta Re(obar^2) sum_d cos(Q d),
+        then chibar(Q, tau_k) for k = 0 .. m; jackknife over the closed bins"""
+        n = self.lib.dqmc_series_ph_vertex_size(self.h)
+        v, e = np.zeros(max(n, 1)), np.zeros(max(n, 1))
+        check(self.lib.dqmc_series_ph_vertex_host(self.h, int(Q[0]), int(Q[1]), v.ctypes.data_as(_lib._DP), e.ctypes.data_as(_lib._DP)))
+        return v.reshape(self.nchains_total(), -1, 6 + self.m), e.reshape(self.nchains_total(), -1, 6 + self.m)
 
     def series_phi_derived(self):
         """(value, err), (nchains, 6) each, of a series with SERIES_PHI: the jackknifed Binder cumulant and ratio of |phibar|, beta N
@@ -1431,6 +1525,22 @@ class DetSDWBatch:
         v, e = self._series_pair_vertex(c, Q)
         return v[:, 4:].copy(), e[:, 4:].copy()
 
+    def _series_ph_vertex(self, c, Q):
+        m = self.chains[0].info.m
+        if Q is None:
+            raise ValueError("the particle-hole vertex needs Q = (qx, qy) in units of 2 pi / L: (L/2, L/2) for the SDW channel, (0, 0) for nematic ones")
+        qx, qy = Q
+        v, e = np.zeros((len(self.chains), 6 + m)), np.zeros((len(self.chains), 6 + m))
+        check(self.lib.detsdw_series_ph_vertex(self.h, int(c), int(qx), int(qy), v.ctypes.data_as(_lib._DP), e.ctypes.data_as(_lib._DP)), host=True)
+        return v, e
+
+    def series_ph_bubble_all(self, c, Q):
+        """(value, err), (nchains, m+1) each: the particle-hole bubble chibar_c(Q, tau_k) of custom bilinear c on the averaged Green's function
+        of the series (set_green_matrix and the matrices set before it began), Q = (qx, qy) in units of 2 pi / L, jackknife over the closed
+        bins"""
+        v, e = self._series_ph_vertex(c, Q)
+        return v[:, 5:].copy(), e[:, 5:].copy()
+
     def matsubara_all(self, name, nfreq):
         """DetSDW.matsubara of every chain: complex (nchains, nfreq, N), one device call per sub-batch"""
         out = np.zeros((len(self.chains), int(nfreq), self.chains[0].info.N), dtype=np.complex128)
@@ -1523,10 +1633,16 @@ class DetSDWBatch:
         2 pi / L, default (L/2, L/2); with set_green_matrix and pair operators set before the series began, at a Q that must be given
         ((0, 0) for uniform pairing; ValueError without it: the default of the R_ names would be the wrong one here):
         'vertexCustomPair{c}' (P = Re chi(Q, i omega_0)), 'bubbleCustomPair{c}' (Pbar, the same contraction on the averaged Green's function),
-        'gammaCustomPair{c}' (Gamma = 1/P - 1/Pbar) and 'gammaBubbleCustomPair{c}' (Gamma Pbar = Pbar/P - 1; -> -1 at the instability)"""
+        'gammaCustomPair{c}' (Gamma = 1/P - 1/Pbar) and 'gammaBubbleCustomPair{c}' (Gamma Pbar = Pbar/P - 1; -> -1 at the instability);
+        the same for custom bilinear c (particle-hole channels, Q must be given as well): 'vertexCustom{c}' (chi = Re chi(Q, i omega_0) - D),
+        'bubbleCustom{c}' (chibar), 'gammaCustom{c}', 'gammaBubbleCustom{c}' and 'disconnectedCustom{c}' (D = beta Re(obar^2) sum_d cos(Q d))"""
         pv = pair_vertex_quantity(name)
         if pv is not None:
             v, e = self._series_pair_vertex(pv[1], Q)
+            return v[:, pv[0]].copy(), e[:, pv[0]].copy()
+        pv = ph_vertex_quantity(name)
+        if pv is not None:
+            v, e = self._series_ph_vertex(pv[1], Q)
             return v[:, pv[0]].copy(), e[:, pv[0]].copy()
         v, e = np.zeros(len(self.chains)), np.zeros(len(self.chains))
         c = custom_ratio(name)

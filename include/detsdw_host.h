@@ -348,6 +348,11 @@ int detsdw_series_custom_pair_derived(detsdw_replica* r, int c, int qx, int qy, 
  * then Pbar_c(Q, tau_k), k = 0 .. m; needs pair operators and the switch set before the series began. */
 int detsdw_set_green_matrix(detsdw_replica* r, int on);
 int detsdw_series_pair_vertex(detsdw_replica* r, int c, int qx, int qy, double* value, double* err);
+/* The particle-hole counterpart (dqmc_series_ph_vertex_host in dqmc_hip.h): value[nchains][6 + m], err[nchains][6 + m] for user-defined
+ * bilinear c (detsdw_set_custom_bilinears / detsdw_set_custom_bond_bilinears) at Q = (qx, qy): chi, chibar, Gamma, Gamma chibar, D, then
+ * chibar_c(Q, tau_k), k = 0 .. m, over all sub-batch contexts in handle order.  Needs the matrices and detsdw_set_green_matrix set before
+ * the series began, timeDisplacedParticleHole and timeDisplacedEverySlice; no new part and no new flag. */
+int detsdw_series_ph_vertex(detsdw_replica* r, int c, int qx, int qy, double* value, double* err);
 int detsdw_series_read_bins(detsdw_replica* r, int which, int first, int count, double* out);
 int detsdw_series_end(detsdw_replica* r);
 /* The series over a long run (kernel calls and formulas: dqmc_hip.h).  All of it is new surface: without these calls nothing changes.

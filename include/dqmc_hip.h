@@ -686,7 +686,24 @@ int dqmc_measure_td_matsubara_host(dqmc_ctx* ctx, int channel, int nfreq, double
  * Gamma Pbar -> -1 marks the pairing instability; its sign says attractive or repulsive.  Two kernels: one workgroup per (slot, jackknife
  * index, row) stages the row in LDS and reduces over d in a fixed tree; the second sums over k and the bins in index order.  No atomics:
  * two calls give identical bits and a slot's result does not depend on batching.  DQMC_EINVAL: a series without bit 11 or bit 13, B < 2,
- * qx or qy outside 0 .. L-1, a lattice whose row does not fit the LDS (2 R^2 N doubles + 8 KiB > 152 KiB). */
+ * qx or qy outside 0 .. L-1, a lattice whose row does not fit the LDS (2 R^2 N doubles + 8 KiB > 152 KiB).
+ * dqmc_series_ph_vertex_host(qx, qy) (all slots, every user-defined bilinear c = (M0, Mx, My) of dqmc_set_custom_bond_bilinears; value and
+ * err [nb][count][6 + m], dqmc_series_ph_vertex_size doubles each, 0 where the call is refused): the particle-hole counterpart, from parts
+ * 9 and 13.  No new part, flag or block: without the call nothing changes.  For one set of bin means x, with the five site blocks
+ * V_k(A) = f_k(A) W_k of the bond section and
+ *   gbar(0,tau_k)(P; Q) = -gbar(tau_{m-k},0)(P; Q),  k = 0 .. m     (cyclic invariance of the weight: exact in the ensemble average,
+ *                      element by element and so for the stored sector too; the end rows obey it as measured and carry the delta term)
+ *   chibar_c(d, tau_k) = -sum_(k, k') Re f_k(A) f_k'(B) tr(W_k gbar(tau_k,0)^(qr) W_k' gbar(0,tau_k)^(sp)),   (A, B) = (d, 0): the connected
+ *                      Wick term of W(A, B) with gbar in the place of g~, site superscripts as in the bond section
+ *   chibar_c(Q, tau_k) = sum_d cos(Q d) chibar_c(d, tau_k),   chibar_c = dtau sum_k w_k chibar_c(Q, tau_k),  w_0 = w_m = 1/2
+ *   obar_c = tr M0 - sum_ij (O_0)_ij gbar(tau_0,0)(j; i)   (site 0, row 0),   D_c = beta Re(obar_c^2) sum_d cos(Q d)   (beta N Re obar_c^2
+ *                      at Q = 0, else 0: the disconnected part that channel 5 carries)
+ *   chi_c = Re chi_c(Q, i omega_0) of part 9 - D_c,   Gamma_c = 1 / chi_c - 1 / chibar_c,   Gamma chibar_c = chibar_c / chi_c - 1.
+ * Output per slot and operator: chi, chibar, Gamma, Gamma chibar, D, then chibar_c(Q, tau_k) for k = 0 .. m.  Normalisation per site pair
+ * as the Matsubara transform; on a free matrix chi_c = chibar_c to rounding at every Q.  value, err, NaN rule, kernel pair, fixed
+ * summation order (no atomics, identical bits, independent of batching) as dqmc_series_pair_vertex_host; the bubble kernel stages rows
+ * k and m - k.  DQMC_EINVAL with nothing touched: a series without bit 9 or bit 13, B < 2, qx or qy outside 0 .. L-1, no bilinear set, a
+ * lattice whose two rows do not fit the LDS (4 R^2 N doubles + 8 KiB > 152 KiB). */
 enum { DQMC_SERIES_EQ = 1, DQMC_SERIES_MATS_G = 2, DQMC_SERIES_MATS_PAIR = 4, DQMC_SERIES_MATS_PH = 8, DQMC_SERIES_MATS_CURRENT = 16,
        DQMC_SERIES_PHI = 64, DQMC_SERIES_MATS_BAND = 128, DQMC_SERIES_EQ_BAND = 256, DQMC_SERIES_MATS_CUSTOM = 512, DQMC_SERIES_EQ_CUSTOM = 1024,
        DQMC_SERIES_MATS_CUSTOM_PAIR = 2048, DQMC_SERIES_EQ_CUSTOM_PAIR = 4096, DQMC_SERIES_GREEN_MATRIX = 8192 };
@@ -706,6 +723,8 @@ int dqmc_series_custom_derived_host(dqmc_ctx* ctx, int qx, int qy, double* value
 int dqmc_series_custom_pair_derived_host(dqmc_ctx* ctx, int qx, int qy, double* value, double* err);
 size_t dqmc_series_pair_vertex_size(dqmc_ctx* ctx);
 int dqmc_series_pair_vertex_host(dqmc_ctx* ctx, int qx, int qy, double* value, double* err);
+size_t dqmc_series_ph_vertex_size(dqmc_ctx* ctx);
+int dqmc_series_ph_vertex_host(dqmc_ctx* ctx, int qx, int qy, double* value, double* err);
 int dqmc_series_end(dqmc_ctx* ctx);
 /* ---- the series over a long run: re-binning, binning analysis with tau_int, export / import ------------
  * All of it is new surface: with none of these calls used, every call above keeps its bits, its error codes and its launches.
