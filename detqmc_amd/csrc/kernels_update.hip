@@ -294,7 +294,9 @@ __global__ __launch_bounds__(NT) void k_update_decide(DevModel dm, DevUpdateStat
     constexpr int NIT = (NITEMS + 63) / 64;
     static_assert(O_GCC % 2 == 0, "complex items must be 16-byte aligned in LDS");
     __shared__ __attribute__((aligned(16))) double scand[NIT * 64];
-    __shared__ __attribute__((aligned(16))) double sdec[4 * MSF * MSF + 4];   // wave 0 -> all: delta, G[c,c], exp(-dS), uniform, (CDW 2: null-proposal flag)
+    // wave 0 -> all: delta, G[c,c], exp(-dS), uniform, (CDW 2: null-proposal flag); PROP != 0: one more slot, "the proposal ran past the
+    // pushed uniforms"
+    __shared__ __attribute__((aligned(16))) double sdec[4 * MSF * MSF + (PROP != 0 ? 5 : 4)];
     __shared__ cplx salg[MSF == 4 ? NW * 80 : 1];                              // O(3): wave-private scratch of the 4 x 4 algebra (S, M', cofactors, M'^-1, F)
 
     auto neighbours = [&](int s, int (&nbr)[4]) {
@@ -506,13 +508,22 @@ __global__ __launch_bounds__(NT) void k_update_decide(DevModel dm, DevUpdateStat
             [[maybe_unused]] int consumed = 0;           // PROP != 0: uniforms this proposal drew
             [[maybe_unused]] bool valid = true;          //            changed != NONE
             [[maybe_unused]] double uacc_peek = 0.5;
+            // PROP != 0: a uniform was asked for at or past `avail` (the check at the top of the proposal covers two windows; a Box-Muller
+            // loop that rejects pair after pair runs past them), or the loop's guard ran out
+            [[maybe_unused]] bool rng_over = false;
+            [[maybe_unused]] const bool nd_has0 = nd_has;           // the Box-Muller stack as the proposal found it
+            [[maybe_unused]] const double nd_cached0 = nd_cached;
             if constexpr (PROP != 0) {
                 int wpos = (int)(cur - win_cur);
                 auto next_uniform = [&]() -> double {
                     const int wp = wpos + consumed;
                     double v;
                     if (wp < UNIW) v = scand[O_UNI + wp];
-                    else { const unsigned long long idx = cur + consumed; v = idx < avail ? uni[idx] : 0.25; }
+                    else {
+                        const unsigned long long idx = cur + consumed;
+                        if (idx < avail) v = uni[idx];
+                        else { v = 0.25; rng_over = true; }      // (0.25, 0.25) ends a Box-Muller loop; the launch ends with DQMC_ERNG
+                    }
                     consumed += 1;
                     return v;
                 };
@@ -530,6 +541,7 @@ __global__ __launch_bounds__(NT) void k_update_decide(DevModel dm, DevUpdateStat
                             v1 = 2.0 * u1 - 1.0; v2 = 2.0 * u2 - 1.0;
                             rsq = v1 * v1 + v2 * v2;
                         } while ((rsq >= 1.0 || rsq == 0.0) && ++guard < 64);
+                        if (rsq >= 1.0 || rsq == 0.0) { rng_over = true; rsq = 0.5; }      // the guard ran out: no log of a rejected pair
                         const double fac = sqrt(-2.0 * log(rsq) / rsq);
                         nd_cached = v1 * fac;            // pushed first, handed out second
                         var = v2 * fac;
@@ -580,8 +592,13 @@ __global__ __launch_bounds__(NT) void k_update_decide(DevModel dm, DevUpdateStat
                 {   // the uniform an acceptance test would draw next (not consumed here)
                     const int wp = wpos + consumed;
                     if (wp < UNIW) uacc_peek = scand[O_UNI + wp];
-                    else { const unsigned long long idx = cur + consumed; uacc_peek = idx < avail ? uni[idx] : 0.5; }
+                    else {
+                        const unsigned long long idx = cur + consumed;
+                        if (idx < avail) uacc_peek = uni[idx];
+                        else { uacc_peek = 0.5; if (valid) rng_over = true; }      // as at the top of the loop: it must be there, needed or not
+                    }
                 }
+                if (rng_over) { nd_has = nd_has0; nd_cached = nd_cached0; }      // nothing of a proposal that ran dry is kept
             }
 #pragma unroll
             for (int d = 0; d < OPDIM; ++d) {
@@ -693,7 +710,10 @@ __global__ __launch_bounds__(NT) void k_update_decide(DevModel dm, DevUpdateStat
             if (tid == 0) {
                 sdec[4 * MSF * MSF] = probSPhi;
                 if constexpr (PROP == 0) sdec[4 * MSF * MSF + 1] = scand[O_UNI + uoff + NPROP];
-                else { sdec[4 * MSF * MSF + 1] = uacc_peek; sdec[4 * MSF * MSF + 2] = valid ? 0.0 : 2.0; sdec[4 * MSF * MSF + 3] = (double)consumed; }
+                else {
+                    sdec[4 * MSF * MSF + 1] = uacc_peek; sdec[4 * MSF * MSF + 2] = valid ? 0.0 : 2.0; sdec[4 * MSF * MSF + 3] = (double)consumed;
+                    sdec[4 * MSF * MSF + 4] = rng_over ? 1.0 : 0.0;
+                }
                 if constexpr (CDW == 2) { sdec[4 * MSF * MSF + 2] = nullp ? 1.0 : 0.0; sdec[4 * MSF * MSF + 3] = lnew; }
             }
         }
@@ -702,6 +722,11 @@ __global__ __launch_bounds__(NT) void k_update_decide(DevModel dm, DevUpdateStat
         TICK(5);
         // ---- every thread picks up what wave 0 published ----
         const double probSPhi = sdec[4 * MSF * MSF], uacc = sdec[4 * MSF * MSF + 1];
+        if constexpr (PROP != 0) {
+            // the proposal drew past the pushed uniforms: nothing of it is kept, the launch ends as at the check at the top of the
+            // loop (every thread reads the same flag)
+            if (sdec[4 * MSF * MSF + 4] != 0.0) { err = DQMC_ERNG; break; }
+        }
         cplx delta[MSF == 2 ? 2 : 1][MSF == 2 ? 2 : 1], Minv[MSF == 2 ? 2 : 1][MSF == 2 ? 2 : 1];
         cplx det;
         if constexpr (MSF == 2) {
