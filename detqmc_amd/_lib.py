@@ -45,10 +45,13 @@ class dqmc_tuning(C.Structure):
                 ("max_jacobi_sweeps", C.c_int32), ("proposal_budget", C.c_int32), ("decide_threads", C.c_int32), ("bmult_path", C.c_int32)]
 
 
+DQMC_TUNING_NO_RNG_LOOKAHEAD = 0x100      # flag bit of dqmc_tuning.bmult_path
+
+
 class dqmc_schedule_info(C.Structure):
     _fields_ = [("pipelined", C.c_int32), ("proposal_budget", C.c_int32), ("blocks_pipelined", C.c_uint64),
                 ("blocks_sequential", C.c_uint64), ("qr_block_gram_schmidt", C.c_int32), ("green_lu", C.c_int32),
-                ("cholqr_fallbacks", C.c_uint64)]
+                ("cholqr_fallbacks", C.c_uint64), ("uniform_windows_advanced", C.c_uint64), ("uniform_windows_pushed", C.c_uint64)]
 
 
 class dqmc_params(C.Structure):
@@ -191,6 +194,10 @@ SYMBOLS = [
     ("dqmc_reset_storage0", C.c_int, [_P]),
     ("dqmc_push_uniforms_host", C.c_int, [_P, _DP, C.c_size_t]),
     ("dqmc_push_uniforms_all_host", C.c_int, [_P, _DP, C.c_size_t]),
+    ("dqmc_uniforms_staging_host", C.c_int, [_P, C.POINTER(_DP), C.POINTER(C.c_size_t)]),
+    ("dqmc_stage_uniforms_tail_host", C.c_int, [_P, _DP, C.c_size_t]),
+    ("dqmc_advance_uniforms", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("dqmc_get_uniform_window_host", C.c_int, [_P, _DP, C.c_size_t]),
     ("dqmc_update_slice", C.c_int, [_P, C.c_int, C.c_int]),
     ("dqmc_update_slice_ex", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("dqmc_update_slice_final", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -362,6 +369,8 @@ SYMBOLS = [
     ("detsdw_set_control_data", C.c_int, [_P, C.POINTER(detsdw_control_data)]),
     ("detsdw_replica_exchange_probability", C.c_double, [C.c_double] * 4),
     ("detsdw_rng_fill", C.c_int, [C.c_uint32, C.c_uint32, _DP, C.c_size_t]),
+    ("detsdw_rng_replay", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.c_size_t, _DP, C.c_size_t,
+                                    C.POINTER(C.c_size_t)]),
     ("dethubbard_create", C.c_int, [C.POINTER(dethubbard_params), C.c_int, C.POINTER(_P)]),
     ("dethubbard_destroy", None, [_P]),
     ("dethubbard_last_error", C.c_char_p, []),

@@ -367,7 +367,10 @@ extern "C" int dqmc_create_batch(const dqmc_params* p, int nchains, dqmc_ctx** o
     if (p->bc < 0 || p->bc > 3) return fail(DQMC_EINVAL, "bc");
     if (p->tuning.decide_threads != 0 && p->tuning.decide_threads != 256 && p->tuning.decide_threads != 512)
         return fail(DQMC_EINVAL, "tuning.decide_threads must be 0, 256 or 512");
-    if (p->tuning.bmult_path < 0 || p->tuning.bmult_path > 2) return fail(DQMC_EINVAL, "tuning.bmult_path must be 0, 1 or 2");
+    {   // the field also carries DQMC_TUNING_NO_RNG_LOOKAHEAD
+        const int path = p->tuning.bmult_path & ~DQMC_TUNING_NO_RNG_LOOKAHEAD;
+        if (p->tuning.bmult_path < 0 || path > 2) return fail(DQMC_EINVAL, "tuning.bmult_path must be 0, 1 or 2");
+    }
     if (p->stabilisation != DQMC_STAB_SVD && p->stabilisation != DQMC_STAB_QR) return fail(DQMC_EINVAL, "stabilisation");
     if (!(p->dtau > 0)) return fail(DQMC_EINVAL, "dtau");
     if (p->model != DQMC_MODEL_SDW && p->model != DQMC_MODEL_HUBBARD) return fail(DQMC_EINVAL, "model");
@@ -404,6 +407,8 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
     HIPCHK(hipStreamCreateWithFlags(&c->st2, hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&c->ev_win, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&c->ev_flush, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->ev_tail, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->ev_adv, hipEventDisableTiming));
 
     DevModel& hm = c->hm;
     memset(&hm, 0, sizeof(hm));
@@ -416,7 +421,7 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
     if (p->tuning.proposal_budget != 0) hm.pbudget = p->tuning.proposal_budget < 0 ? 0 : p->tuning.proposal_budget;
     if (hm.pbudget > 0 && hm.pbudget < p->delaySteps) hm.pbudget = p->delaySteps;
     hm.decide_nt = p->tuning.decide_threads;
-    hm.bmult_path = p->tuning.bmult_path;
+    hm.bmult_path = p->tuning.bmult_path & ~DQMC_TUNING_NO_RNG_LOOKAHEAD;
 #ifdef DQMC_DECIDE_TIMING
     hm.dbg = (getenv("DQMC_DECIDE_TIMING") && atoi(getenv("DQMC_DECIDE_TIMING"))) ? 8 : 0;   // phase timers of k_update_decide; never changes a result
 #endif
@@ -540,6 +545,9 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
     if (p->rng_window_per_site < 0 || p->rng_window_per_site > 4096) return fail(DQMC_EINVAL, "rng_window_per_site");
     c->uni_cap = (size_t)(p->rng_window_per_site > 0 ? p->rng_window_per_site : (p->opdim + 1 + (p->cdwU != 0.0 ? 2 : 0))) * N * p->m + 64;     // one sweep's worst case (+ the cdwl pass)
     A_(dalloc(c, &c->uniforms, c->uni_cap));
+    if (!(p->tuning.bmult_path & DQMC_TUNING_NO_RNG_LOOKAHEAD)) {       // the look-ahead's second window and tail (dqmc_advance_uniforms)
+        A_(dalloc(c, &c->uniforms_next, c->uni_cap)); A_(dalloc(c, &c->uni_tail, c->uni_cap));
+    }
     A_(dalloc(c, &c->us, 1));
     A_(dalloc(c, &c->scalar_out, 8));
     A_(salloc(c, &c->shift_buf, (size_t)c->nb * 3));
@@ -645,6 +653,11 @@ extern "C" void dqmc_destroy(dqmc_ctx* c) {
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     if (c->ev_win) (void)hipEventDestroy(c->ev_win);
     if (c->ev_flush) (void)hipEventDestroy(c->ev_flush);
+    if (c->st_up) (void)hipStreamSynchronize(c->st_up);
+    if (c->ev_tail) (void)hipEventDestroy(c->ev_tail);
+    if (c->ev_adv) (void)hipEventDestroy(c->ev_adv);
+    if (c->uni_pin) (void)hipHostFree(c->uni_pin);
+    if (c->st_up && c->st_up != c->st2) (void)hipStreamDestroy(c->st_up);
     if (c->st2) (void)hipStreamDestroy(c->st2);
     if (c->st) (void)hipStreamDestroy(c->st);
     delete c;
@@ -1227,6 +1240,9 @@ extern "C" int dqmc_push_uniforms_host(dqmc_ctx* c, const double* u, size_t nval
     uint64_t vals[2] = {0, (uint64_t)nvals};
     HIPCHK(copy_sync(c, (char*)selp(c, c->us) + offsetof(DevUpdateState, pub) + offsetof(dqmc_update_state, rng_consumed), vals,
                      sizeof(vals), hipMemcpyHostToDevice));
+    c->uni_n = c->nb == 1 ? nvals : 0;      // with more chains the windows may now differ in size: no look-ahead until all are pushed
+    c->tail_staged = false;
+    c->windows_pushed += 1;
     return DQMC_OK;
 }
 
@@ -1242,6 +1258,78 @@ extern "C" int dqmc_push_uniforms_all_host(dqmc_ctx* c, const double* u, size_t 
     HIPCHK(hipMemcpy2DAsync((char*)c->us + offsetof(DevUpdateState, pub) + offsetof(dqmc_update_state, rng_consumed), c->lc.cs, vals.data(),
                             2 * sizeof(uint64_t), 2 * sizeof(uint64_t), (size_t)c->nb, hipMemcpyHostToDevice, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
+    c->uni_n = nvals;
+    c->tail_staged = false;
+    c->windows_pushed += 1;
+    return DQMC_OK;
+}
+
+// ---- look-ahead on the uniforms (include/dqmc_hip.h; schedule and ordering: DESIGN.md section 19) ----
+// The staging buffer holds nb windows of uni_cap doubles and, behind them, the nb offsets the splice kernel reads straight from
+// host memory.  The upload's stream is st2 where the update schedule leaves it idle, else a stream of its own.
+static int lookahead_ready(dqmc_ctx* c) {
+    if (!c->uniforms_next) return fail(DQMC_EINVAL, "the context was created without the look-ahead on the uniforms (DQMC_TUNING_NO_RNG_LOOKAHEAD)");
+    if (c->uni_pin) return DQMC_OK;
+    if (!c->st_up) {
+        if (c->pipelined) HIPCHK(hipStreamCreateWithFlags(&c->st_up, hipStreamNonBlocking));
+        else c->st_up = c->st2;
+    }
+    void* q = nullptr;
+    HIPCHK(hipHostMalloc(&q, ((size_t)c->nb * c->uni_cap + (size_t)c->nb) * sizeof(double), hipHostMallocDefault));
+    c->uni_pin = (double*)q;
+    c->uni_off = (unsigned long long*)(c->uni_pin + (size_t)c->nb * c->uni_cap);
+    return DQMC_OK;
+}
+extern "C" int dqmc_uniforms_staging_host(dqmc_ctx* c, double** buf, size_t* capacity) {
+    if (!c || !buf) return fail(DQMC_EINVAL, "null argument");
+    (void)hipSetDevice(c->p.device);
+    if (int rc = lookahead_ready(c)) return rc;
+    if (c->tail_event_live) HIPCHK(hipEventSynchronize(c->ev_tail));       // an upload may still be reading the buffer
+    *buf = c->uni_pin;
+    if (capacity) *capacity = c->uni_cap;
+    return DQMC_OK;
+}
+extern "C" int dqmc_stage_uniforms_tail_host(dqmc_ctx* c, const double* u, size_t nvals) {
+    if (!c || !u) return fail(DQMC_EINVAL, "null argument");
+    (void)hipSetDevice(c->p.device);
+    if (int rc = lookahead_ready(c)) return rc;
+    if (nvals == 0 || nvals != c->uni_n) return fail(DQMC_EINVAL, "the tail must have the size of the current window of every chain");
+    if (u != c->uni_pin) {
+        if (c->tail_event_live) HIPCHK(hipEventSynchronize(c->ev_tail));
+        memcpy(c->uni_pin, u, (size_t)c->nb * nvals * sizeof(double));
+    }
+    // the last splice read the tail buffer: the upload overwrites it only behind that kernel
+    if (c->adv_event_live) HIPCHK(hipStreamWaitEvent(c->st_up, c->ev_adv, 0));
+    HIPCHK(hipMemcpy2DAsync(c->uni_tail, c->lc.cs, c->uni_pin, nvals * sizeof(double), nvals * sizeof(double), (size_t)c->nb,
+                            hipMemcpyHostToDevice, c->st_up));
+    HIPCHK(hipEventRecord(c->ev_tail, c->st_up));
+    c->tail_event_live = true;
+    c->tail_staged = true;
+    return DQMC_OK;
+}
+extern "C" int dqmc_advance_uniforms(dqmc_ctx* c, const uint64_t* offset) {
+    if (!c || !offset) return fail(DQMC_EINVAL, "null argument");
+    (void)hipSetDevice(c->p.device);
+    if (!c->uniforms_next) return fail(DQMC_EINVAL, "the context was created without the look-ahead on the uniforms (DQMC_TUNING_NO_RNG_LOOKAHEAD)");
+    if (!c->tail_staged || c->uni_n == 0) return fail(DQMC_EINVAL, "dqmc_advance_uniforms: no tail is staged");
+    for (int b = 0; b < c->nb; ++b)
+        if (offset[b] > c->uni_n) return fail(DQMC_EINVAL, "dqmc_advance_uniforms: offset past the end of the window");
+    if (c->adv_event_live) HIPCHK(hipEventSynchronize(c->ev_adv));         // the last splice may still be reading the offsets
+    for (int b = 0; b < c->nb; ++b) c->uni_off[b] = offset[b];
+    HIPCHK(hipStreamWaitEvent(c->st, c->ev_tail, 0));
+    launch_advance_uniforms(c->lc, c->us, c->uniforms, c->uni_tail, c->uniforms_next, c->uni_off, c->uni_n);
+    HIPCHK(hipEventRecord(c->ev_adv, c->st));
+    c->adv_event_live = true;
+    std::swap(c->uniforms, c->uniforms_next);
+    c->tail_staged = false;
+    c->windows_advanced += 1;
+    return finish(c, "dqmc_advance_uniforms");
+}
+extern "C" int dqmc_get_uniform_window_host(dqmc_ctx* c, double* out, size_t nvals) {
+    if (!c || (!out && nvals)) return fail(DQMC_EINVAL, "null argument");
+    (void)hipSetDevice(c->p.device);
+    if (nvals > c->uni_cap) return fail(DQMC_EINVAL, "more uniforms than the window holds");
+    HIPCHK(copy_sync(c, out, selp(c, c->uniforms), nvals * sizeof(double), hipMemcpyDeviceToHost));
     return DQMC_OK;
 }
 // out[nchains]: the update state of every chain, one strided copy
@@ -1362,6 +1450,8 @@ extern "C" int dqmc_get_schedule_info(dqmc_ctx* c, dqmc_schedule_info* out) {
     out->qr_block_gram_schmidt = (c->stab == DQMC_STAB_QR && c->qr_bgs) ? 1 : 0;
     out->green_lu = (c->stab == DQMC_STAB_QR && c->green_lu) ? 1 : 0;
     out->cholqr_fallbacks = c->cholqr_fallbacks;
+    out->uniform_windows_advanced = c->windows_advanced;
+    out->uniform_windows_pushed = c->windows_pushed;
     return DQMC_OK;
 }
 

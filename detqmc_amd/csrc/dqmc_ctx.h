@@ -198,6 +198,16 @@ struct dqmc_ctx {
     cplx *X = nullptr, *Gr = nullptr, *W = nullptr;
     double* uniforms = nullptr;
     size_t uni_cap = 0;
+    // look-ahead on the uniforms (dqmc_stage_uniforms_tail_host / dqmc_advance_uniforms): the window the next advance writes (it then
+    // changes places with `uniforms`), the draws behind the current window, the pinned staging buffer (room for [nb][uni_cap]) with the offsets
+    // [nb] of the advance behind it (allocated on first use), and the events that order upload and splice kernel
+    double *uniforms_next = nullptr, *uni_tail = nullptr, *uni_pin = nullptr;
+    unsigned long long* uni_off = nullptr;
+    size_t uni_n = 0;                   // size of the current window of every chain, 0: not known (a single chain was pushed)
+    bool tail_staged = false, tail_event_live = false, adv_event_live = false;
+    hipStream_t st_up = nullptr;        // the upload's stream: st2 unless the pipelined schedule uses that one
+    hipEvent_t ev_tail = nullptr, ev_adv = nullptr;
+    uint64_t windows_advanced = 0, windows_pushed = 0;
     DevUpdateState* us = nullptr;
     double* scalar_out = nullptr;
     double* shift_buf = nullptr;        // [nchains][opdim] displacements of a global shift move (shared buffer)

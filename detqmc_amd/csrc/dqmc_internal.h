@@ -255,6 +255,9 @@ void launch_update_window(const Launch& lc, const DevModel& hm, DevUpdateState* 
                           cplx* Gw, int P);
 void launch_update_gather(const Launch& lc, const DevModel& hm, const DevUpdateState* us, const cplx* G,
                           const cplx* W, cplx* X, cplx* GrT, int skip_done = 0);     // skip_done: nothing for a chain whose slice_done is set
+// nw = cur[off ..) followed by tail[0 .. off) per chain, `need` values; cursor of the window back to 0 (off: [nb], host-pinned)
+void launch_advance_uniforms(const Launch& lc, DevUpdateState* us, const double* cur, const double* tail, double* nw,
+                             const unsigned long long* off, size_t need);
 
 // Hubbard replica (kernels_hubbard.hip)
 void launch_hubbard_vscale(const Launch& lc, const DevModel& hm, int side, int inverse, int k, cplx* A, int lda);

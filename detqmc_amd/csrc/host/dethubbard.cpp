@@ -41,6 +41,7 @@ DetHubbard::DetHubbard(const dethubbard_params& in, int nchains) : p_(in) {
     kp.opdim = 1; kp.L = p_.L; kp.m = m_; kp.s = s_; kp.delaySteps = 1; kp.bc = DQMC_BC_PBC; kp.device = p_.device;
     kp.stabilisation = p_.stabilisation; kp.cb_none = p_.checkerboard ? 0 : 1;
     kp.dtau = p_.dtau; kp.txhor = p_.t; kp.u = p_.U; kp.mux = p_.mu; kp.muy = p_.mu; kp.accRatio = 0.5;
+    kp.tuning.bmult_path = DQMC_TUNING_NO_RNG_LOOKAHEAD;     // this replica pushes every window whole (beginLocalUpdates)
     check(dqmc_create_batch(&kp, nchains, &ctx_), "dqmc_create");
     try {
         std::vector<double> all((size_t)nchains * (m_ + 1) * N_, 0.0);

@@ -185,6 +185,7 @@ DetSDW::DetSDW(const detsdw_params* in, int nchains, int sub_batches) {
     // contexts overlap each other instead): automatic here means at most two sub-batches.
     kp.tuning = p.tuning;
     if (kp.tuning.pipeline == 0 && S > 2) kp.tuning.pipeline = -1;
+    lookahead_ = !(kp.tuning.bmult_path & DQMC_TUNING_NO_RNG_LOOKAHEAD);
     groups_.resize(S);
     try {
         for (int g = 0; g < S; ++g) {
@@ -227,11 +228,47 @@ void DetSDW::setupUdVStorage_and_calculateGreen(Group& g) {
 }
 
 // Ship the worst-case number of upcoming uniforms of this sweep; the device consumes a prefix.
+// With the look-ahead the draws behind the last sweep's window are on the device already: every chain's stream
+// has moved off_b draws since that window began (what the device consumed plus what global moves or the caller drew on the host), and
+// the device splices the new window from the rest of the old one and the tail -- nothing is drawn, copied or waited for here.  The
+// full push remains for the first sweep, after loadState / set_control_data, and when a chain drew more than a window in between.
 void DetSDW::beginLocalUpdates(Group& g) {
     const size_t need = (size_t)uniformsPerSite() * N_ * m_;
-    g.window.resize(need * g.count);               // all chains' windows back to back: one host -> device transfer
-    for (int b = 0; b < g.count; ++b) std::memcpy(&g.window[b * need], ch_[g.first + b].rng.peek(need), need * sizeof(double));
-    check(dqmc_push_uniforms_all_host(g.ctx, g.window.data(), need), "dqmc_push_uniforms_all_host");
+    g.windowStart.resize(g.count);
+    if (lookahead_ && g.tailStaged) {
+        std::vector<uint64_t> off(g.count);
+        bool inside = true;
+        for (int b = 0; b < g.count; ++b) {
+            off[b] = ch_[g.first + b].rng.drawn() - g.windowStart[b];
+            inside = inside && off[b] <= need;
+        }
+        g.tailStaged = false;
+        if (inside) {
+            check(dqmc_advance_uniforms(g.ctx, off.data()), "dqmc_advance_uniforms");
+            for (int b = 0; b < g.count; ++b) g.windowStart[b] += off[b];
+            return;
+        }
+    }
+    double* dst = nullptr;
+    if (lookahead_) check(dqmc_uniforms_staging_host(g.ctx, &dst, nullptr), "dqmc_uniforms_staging_host");   // pinned: a faster transfer
+    else { g.window.resize(need * g.count); dst = g.window.data(); }
+    // all chains' windows back to back: one host -> device transfer
+    for (int b = 0; b < g.count; ++b) {
+        std::memcpy(dst + b * need, ch_[g.first + b].rng.peek(need), need * sizeof(double));
+        g.windowStart[b] = ch_[g.first + b].rng.drawn();
+    }
+    check(dqmc_push_uniforms_all_host(g.ctx, dst, need), "dqmc_push_uniforms_all_host");
+}
+// The whole sweep is enqueued and nothing has waited for it yet: draw the window behind the one the device is working through and
+// send it after, on the context's upload stream.  The stream positions are those of beginLocalUpdates (no host draw in between).
+void DetSDW::stageLocalUpdates(Group& g) {
+    if (!lookahead_) return;
+    const size_t need = (size_t)uniformsPerSite() * N_ * m_;
+    double* pin = nullptr;
+    check(dqmc_uniforms_staging_host(g.ctx, &pin, nullptr), "dqmc_uniforms_staging_host");
+    for (int b = 0; b < g.count; ++b) std::memcpy(pin + b * need, ch_[g.first + b].rng.peek(2 * need) + need, need * sizeof(double));
+    check(dqmc_stage_uniforms_tail_host(g.ctx, pin, need), "dqmc_stage_uniforms_tail_host");
+    g.tailStaged = true;
 }
 void DetSDW::endLocalUpdates(Group& g) {
     std::vector<dqmc_update_state> st(g.count);
@@ -350,10 +387,12 @@ void DetSDW::sweep_skeleton(Group& g, bool thermalization) {
         globalMove(g);
         beginLocalUpdates(g);
         sweepDown(g, thermalization);
+        stageLocalUpdates(g);
         endLocalUpdates(g);
     } else {
         beginLocalUpdates(g);
         sweepUp(g, thermalization);
+        stageLocalUpdates(g);
         endLocalUpdates(g);
     }
 }
@@ -1619,6 +1658,7 @@ void DetSDW::set_control_data(const detsdw_control_data& in, int b) {
     ch_[b].addedWolffClusterSize = in.addedWolffClusterSize;
     dqmc_update_state st = in.adjust;
     st.rng_consumed = 0; st.rng_avail = 0; st.error = 0;      // the RNG window is per replica, never exchanged
+    grp(b).tailStaged = false;                                // ... and the next sweep pushes a whole one
     check(dqmc_set_update_state_host(ctx_, &st), "set_control_data");
     ch_[b].phiDelta = st.phiDelta;
     ch_[b].lastAccRatio = st.lastAccRatio;
@@ -2110,5 +2150,46 @@ extern "C" int detsdw_rng_fill(uint32_t seed, uint32_t processIndex, double* out
     if (!out) return DQMC_EINVAL;
     detqmc::RngStream rs(seed, processIndex);
     for (size_t i = 0; i < n; ++i) out[i] = rs.rand01();
+    return DQMC_OK;
+}
+extern "C" int detsdw_rng_replay(uint32_t seed, uint32_t processIndex, const int32_t* op, const uint64_t* arg, size_t nops, double* out,
+                                 size_t cap, size_t* nout) {
+    if ((nops && (!op || !arg)) || (cap && !out) || !nout) return DQMC_EINVAL;
+    detqmc::RngStream rs(seed, processIndex);
+    std::vector<char> seen(cap, 0);
+    size_t high = 0;
+    uint64_t shown = 0;                     // draws behind the current position that a peek has shown
+    auto record = [&](uint64_t pos, double v) {
+        if (pos >= cap) return false;
+        if (seen[pos] && std::memcmp(&out[pos], &v, sizeof(v)) != 0) return false;
+        out[pos] = v; seen[pos] = 1;
+        if (pos + 1 > high) high = (size_t)pos + 1;
+        return true;
+    };
+    for (size_t i = 0; i < nops; ++i) {
+        const uint64_t a = arg[i];
+        if (op[i] == DETSDW_RNG_RAND01) {
+            for (uint64_t j = 0; j < a; ++j) {
+                const uint64_t pos = rs.drawn();
+                if (!record(pos, rs.rand01())) return DQMC_EINVAL;
+                if (shown) --shown;
+            }
+        } else if (op[i] == DETSDW_RNG_PEEK) {
+            if (a > cap) return DQMC_EINVAL;
+            const double* u = rs.peek((size_t)a);
+            for (uint64_t j = 0; j < a; ++j) if (!record(rs.drawn() + j, u[j])) return DQMC_EINVAL;
+            if (a > shown) shown = a;
+        } else if (op[i] == DETSDW_RNG_CONSUME) {
+            if (a > shown) return DQMC_EINVAL;
+            rs.consume((size_t)a);
+            shown -= a;
+        } else if (op[i] == DETSDW_RNG_ROUNDTRIP) {
+            const std::vector<uint64_t> blob = rs.serialize();
+            detqmc::RngStream fresh(seed + 1u, processIndex + 1u);
+            fresh.deserialize(blob);
+            rs = fresh;
+        } else return DQMC_EINVAL;
+    }
+    *nout = high;
     return DQMC_OK;
 }

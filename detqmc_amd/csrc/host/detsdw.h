@@ -143,7 +143,9 @@ private:
     struct Group {                                 // one sub-batch = one kernel context, chains [first, first + count)
         dqmc_ctx* ctx = nullptr;
         int first = 0, count = 0;
-        std::vector<double> window;                // uniforms of the coming sweep, all chains of the group
+        std::vector<double> window;                // uniforms of the coming sweep, all chains of the group (full push without look-ahead)
+        std::vector<uint64_t> windowStart;         // per chain: rng.drawn() at which the window on the device begins
+        bool tailStaged = false;                   // the draws behind those windows are on the device or on their way (stageLocalUpdates)
         std::vector<double> fields;                // host staging of all chains' fields (global moves)
         std::vector<double> mats[7];               // Matsubara transforms of the group's chains per channel, [chain][component][nfreq][N] (re, im)
         int matsNfreq[7] = {0, 0, 0, 0, 0, 0, 0};          // ... and the nfreq they hold (0: none); cleared by every sweep
@@ -205,6 +207,8 @@ public:
     void exchangeActionsDevice(double* out_dev);        // out_dev[chain], device memory
 private:
     void beginLocalUpdates(Group& g);
+    void stageLocalUpdates(Group& g);              // look-ahead: draws and uploads the next window's tail while the device sweeps
+    bool lookahead_ = true;                        // detsdw_params::tuning without DQMC_TUNING_NO_RNG_LOOKAHEAD
     void endLocalUpdates(Group& g);
     void globalMove(Group& g);
     enum GlobalMoveKind { MoveShift, MoveWolff, MoveWolffShift };

@@ -1,4 +1,5 @@
 #include "dsfmt19937.h"
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -53,6 +54,21 @@ double DSFMT19937::genrand_open_open() {
     return d - 1.0;
 }
 
+void DSFMT19937::fill_open_open(double* out, size_t n) {
+    while (n > 0) {
+        if (idx_ >= 2 * N_) { gen_rand_all(); idx_ = 0; }
+        const size_t k = std::min(n, (size_t)(2 * N_ - idx_));
+        const uint64_t* w = st_ + idx_;
+        for (size_t j = 0; j < k; ++j) {
+            const uint64_t u = w[j] | 1ULL;
+            double d;
+            std::memcpy(&d, &u, sizeof(d));
+            out[j] = d - 1.0;
+        }
+        idx_ += (int)k; out += k; n -= k;
+    }
+}
+
 RngStream::RngStream(uint32_t seed, uint32_t processIndex) {
     // uint32 arithmetic exactly as rngwrapper.cpp:43
     mySeed_ = ((seed * 181u) * ((processIndex - 83u) * 359u)) % 104729u;
@@ -70,9 +86,20 @@ double RngStream::rand01() {
 }
 
 const double* RngStream::peek(size_t n) {
-    if (pos_ > 0) { buf_.erase(buf_.begin(), buf_.begin() + pos_); pos_ = 0; }
-    while (buf_.size() < n) buf_.push_back(gen_.genrand_open_open());
-    return buf_.data();
+    const size_t have = buf_.size() - pos_;
+    if (have < n) {
+        // the consumed front goes only once it is at least as long as the live part: disjoint ranges, and every buffered draw is
+        // moved at most once per draw consumed
+        if (pos_ > 0 && pos_ >= have) {
+            std::memcpy(buf_.data(), buf_.data() + pos_, have * sizeof(double));
+            buf_.resize(have);
+            pos_ = 0;
+        }
+        const size_t old = buf_.size();
+        buf_.resize(pos_ + n);
+        gen_.fill_open_open(buf_.data() + old, pos_ + n - old);
+    }
+    return buf_.data() + pos_;
 }
 
 void RngStream::consume(size_t n) {

@@ -17,6 +17,8 @@ public:
     void init(uint32_t seed);
     // uniform in (0,1): dsfmt_genrand_open_open
     double genrand_open_open();
+    // the next n values of genrand_open_open(), a generator block at a time (starts inside a partly used block)
+    void fill_open_open(double* out, size_t n);
     // raw generator state (checkpoints)
     static constexpr size_t state_words() { return (N_ + 1) * 2 + 1; }
     void get_state(uint64_t* out) const { for (int i = 0; i < (N_ + 1) * 2; ++i) out[i] = st_[i]; out[(N_ + 1) * 2] = (uint64_t)idx_; }
@@ -29,7 +31,8 @@ private:
 };
 
 // RngWrapper semantics + a look-ahead window so a batch of upcoming draws can be shipped to the
-// device and only the consumed prefix is retired afterwards.
+// device and only the consumed prefix is retired afterwards.  The window may reach past the sweep that is running (DESIGN.md
+// section 19): buf_[pos_ ..) are the buffered draws, the consumed front is dropped in large pieces, not at every call.
 class RngStream {
 public:
     RngStream(uint32_t seed = 0, uint32_t processIndex = 0);

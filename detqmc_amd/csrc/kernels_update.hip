@@ -1256,6 +1256,28 @@ void launch_update_window(const Launch& lc, const DevModel& hm, DevUpdateState* 
     hipLaunchKernelGGL(k_update_window, dim3((ldw * ldw + 255) / 256, 1, lc.nb), dim3(256), 0, lc.st, hm, us, G, X, GrT, Gw, P, lc.cs);
 }
 
+// The next sweep's window of uniforms, spliced on the device (dqmc_advance_uniforms): chain b's stream has moved off[b] <= need draws
+// since its current window began, so the new window is what is left of the current one followed by the first off[b] draws of the
+// tail the host uploaded meanwhile.  Pure copies: every value keeps its bits.  off lies in pinned host memory.  Also resets the cursor.
+__global__ __launch_bounds__(256) void k_advance_uniforms(DevUpdateState* us, const double* __restrict__ cur, const double* __restrict__ tail,
+                                                           double* __restrict__ nw, const unsigned long long* __restrict__ off,
+                                                           unsigned long long need, size_t cs) {
+    CHAIN(us); CHAIN(cur); CHAIN(tail); CHAIN(nw);
+    const unsigned long long o = off[blockIdx.z];
+    if (o > need) return;                                  // refused by the host already: never read or write out of bounds
+    const unsigned long long keep = need - o;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < need; i += (unsigned long long)gridDim.x * 256)
+        nw[i] = i < keep ? cur[o + i] : tail[i - keep];
+    if (blockIdx.x == 0 && threadIdx.x == 0) { us->pub.rng_consumed = 0; us->pub.rng_avail = need; us->pub.error = 0; }
+}
+void launch_advance_uniforms(const Launch& lc, DevUpdateState* us, const double* cur, const double* tail, double* nw,
+                             const unsigned long long* off, size_t need) {
+    const size_t want = (need + 2047) / 2048;                  // 8 values per thread, at most 64 workgroups per chain
+    const unsigned blocks = want < 1 ? 1u : want > 64 ? 64u : (unsigned)want;
+    hipLaunchKernelGGL(k_advance_uniforms, dim3(blocks, 1, lc.nb), dim3(256), 0, lc.st, us, cur, tail, nw, off,
+                       (unsigned long long)need, lc.cs);
+}
+
 void launch_update_gather(const Launch& lc, const DevModel& hm, const DevUpdateState* us, const cplx* G,
                           const cplx* W, cplx* X, cplx* GrT, int skip_done) {
     hipLaunchKernelGGL(k_update_gather, dim3((hm.ng + 31) / 32, 1, lc.nb), dim3(256), 0, lc.st, hm, us, G, W, X, GrT, lc.cs, skip_done);

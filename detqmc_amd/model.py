@@ -83,6 +83,7 @@ class SDWParams:
     proposalBudget: int = 0      # proposals per delayed-update block (-1: no limit)
     decideThreads: int = 0       # threads per workgroup of the decision kernel (0: automatic, 256, 512); launch shape only
     bmultPath: int = 0           # checkerboard B-multiply kernel (0: automatic, 1: staged, 2: direct wherever it applies); same bits
+    rngLookahead: int = 0        # the next sweep's uniforms are drawn and uploaded while the device sweeps (0: automatic = on, -1: off)
 
 
 # observables with a Matsubara transform (DetSDW.matsubara): name -> index of detsdw_get_observable_vector
@@ -273,10 +274,14 @@ PROPOSE = {"box": 0, "rotate": 1, "scale": 2, "rotate_and_scale": 3}
 ADAPT = {"box": 0, "rotate": 1, "scale": 2}
 
 
-def _tuning(pipeline=0, qrVariant=0, greenVariant=0, maxJacobiSweeps=0, proposalBudget=0, decideThreads=0, bmultPath=0):
+def _tuning(pipeline=0, qrVariant=0, greenVariant=0, maxJacobiSweeps=0, proposalBudget=0, decideThreads=0, bmultPath=0, rngLookahead=0):
+    if int(rngLookahead) not in (0, -1):
+        raise ValueError("rngLookahead must be 0 (automatic: on) or -1 (off)")
+    # dqmc_tuning has no free slot: the look-ahead switch travels as a flag bit of bmult_path (include/dqmc_hip.h)
+    path = int(bmultPath) | (_lib.DQMC_TUNING_NO_RNG_LOOKAHEAD if int(rngLookahead) == -1 and 0 <= int(bmultPath) <= 2 else 0)
     return _lib.dqmc_tuning(pipeline=int(pipeline), qr_variant=int(qrVariant), green_variant=int(greenVariant),
                             max_jacobi_sweeps=int(maxJacobiSweeps), proposal_budget=int(proposalBudget),
-                            decide_threads=int(decideThreads), bmult_path=int(bmultPath))
+                            decide_threads=int(decideThreads), bmult_path=path)
 
 
 def _fmat(a):
@@ -480,14 +485,14 @@ class KernelContext:
                  lambda_=1.0, txhor=-1.0, txver=-0.5, tyhor=0.5, tyver=1.0, mux=-0.5, muy=-0.5,
                  accRatio=0.5, phi2bosons=False, device=0, stabilisation="svd", checkerboard=True, nchains=1, cdwU=0.0,
                  pipeline=0, qrVariant=0, greenVariant=0, maxJacobiSweeps=0, proposalBudget=0, rngWindowPerSite=0, decideThreads=0, bmultPath=0,
-                 timeDisplaced=False, tdParticleHole=False, tdCurrent=False, tdEverySlice=False, tdBand=False):
+                 rngLookahead=0, timeDisplaced=False, tdParticleHole=False, tdCurrent=False, tdEverySlice=False, tdBand=False):
         self.lib = load()
         p = _lib.dqmc_params(opdim=opdim, L=L, m=m, s=s, delaySteps=delaySteps, bc=BC[bc],
                              weakZflux=int(weakZflux), phi2bosons=int(phi2bosons), device=device,
                              stabilisation=STABILISATION[stabilisation], cb_none=int(not checkerboard), dtau=dtau, r=r, c=c, u=u, lambda_=lambda_, txhor=txhor, txver=txver,
                              tyhor=tyhor, tyver=tyver, mux=mux, muy=muy, accRatio=accRatio, cdwU=cdwU, rng_window_per_site=int(rngWindowPerSite),
                              timedisplaced=int(timeDisplaced) | (_lib.DQMC_TD_EVERY_SLICE if tdEverySlice else 0), td_particle_hole=(2 if tdCurrent else int(tdParticleHole)) | (_lib.DQMC_TD_PH_BAND if tdBand else 0),
-                             tuning=_tuning(pipeline, qrVariant, greenVariant, maxJacobiSweeps, proposalBudget, decideThreads, bmultPath))
+                             tuning=_tuning(pipeline, qrVariant, greenVariant, maxJacobiSweeps, proposalBudget, decideThreads, bmultPath, rngLookahead))
         h = C.c_void_p()
         check(self.lib.dqmc_create_batch(C.byref(p), nchains, C.byref(h)))
         self.h = h
@@ -990,6 +995,34 @@ class KernelContext:
         u = np.ascontiguousarray(u, dtype=np.float64)
         check(self.lib.dqmc_push_uniforms_host(self.h, u.ctypes.data_as(_lib._DP), u.size))
 
+    def push_uniforms_all(self, u):
+        """u[nchains][n]: every chain's window in one transfer"""
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        check(self.lib.dqmc_push_uniforms_all_host(self.h, u.ctypes.data_as(_lib._DP), u.shape[1]))
+
+    def stage_uniforms_tail(self, u):
+        """u[nchains][n]: the n draws behind every chain's current window (dqmc_stage_uniforms_tail_host)"""
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        check(self.lib.dqmc_stage_uniforms_tail_host(self.h, u.ctypes.data_as(_lib._DP), u.shape[1]))
+
+    def advance_uniforms(self, offsets):
+        """dqmc_advance_uniforms: the new window of chain b starts offsets[b] draws behind the start of its current one"""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if off.size != self.nchains_total():
+            raise ValueError("one offset per chain")
+        check(self.lib.dqmc_advance_uniforms(self.h, off.ctypes.data_as(C.POINTER(C.c_uint64))))
+
+    def uniform_window(self, n):
+        """the first n uniforms of the selected chain's current window"""
+        out = np.zeros(int(n))
+        check(self.lib.dqmc_get_uniform_window_host(self.h, out.ctypes.data_as(_lib._DP), out.size))
+        return out
+
+    def update_states_all(self):
+        st = (_lib.dqmc_update_state * self.nchains_total())()
+        check(self.lib.dqmc_get_update_states_all_host(self.h, st))
+        return list(st)
+
     def updateInSlice(self, k, thermalization=False, proposal="box", adapt="box", adaptScaleVariance=False, repeat=1):
         """updateInSlice / updateInSliceThermalization; proposal: box | rotate | scale | rotate_and_scale (the latter three: O(3))"""
         check(self.lib.dqmc_update_slice_ex(self.h, k, int(thermalization), PROPOSE[proposal], ADAPT[adapt], int(adaptScaleVariance), int(repeat)))
@@ -1146,7 +1179,7 @@ def _host_params(pars: SDWParams):
         | (_lib.DETSDW_TD_EVERY_SLICE if pars.timeDisplacedEverySlice else 0)      # without timeDisplacedMeasurements: ParameterWrong from the library
         | (_lib.DETSDW_TD_FINE_ON_DEVICE if pars.timeDisplacedFineOnDevice else 0),  # without timeDisplacedEverySlice: the same
         timeDisplacedParticleHole=(2 if pars.timeDisplacedCurrent else int(bool(pars.timeDisplacedParticleHole))) | (_lib.DETSDW_TD_PH_BAND if band_td else 0),
-        tuning=_tuning(pars.pipeline, pars.qrVariant, pars.greenVariant, pars.maxJacobiSweeps, pars.proposalBudget, pars.decideThreads, pars.bmultPath))
+        tuning=_tuning(pars.pipeline, pars.qrVariant, pars.greenVariant, pars.maxJacobiSweeps, pars.proposalBudget, pars.decideThreads, pars.bmultPath, pars.rngLookahead))
 
 
 class DetSDW:

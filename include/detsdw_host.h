@@ -79,7 +79,10 @@ typedef struct detsdw_params {
                                          ...Fine observables raise ParameterWrong and detsdw_get_matsubara* are their readers */
     dqmc_tuning tuning;               /* result-neutral execution choices handed to every kernel context (dqmc_hip.h); all zero =
                                          automatic.  With pipeline = 0 the host layer switches the pipelined update on only for
-                                         handles of at most two kernel contexts (more contexts overlap each other instead) */
+                                         handles of at most two kernel contexts (more contexts overlap each other instead).
+                                         bmult_path | DQMC_TUNING_NO_RNG_LOOKAHEAD (rngLookahead = -1): every sweep pushes its whole
+                                         window of uniforms before it starts; otherwise the next window's draws are generated and
+                                         uploaded while the device sweeps and the window is spliced on the device (same chain) */
     int32_t timeDisplacedParticleHole; /* 1 (needs timeDisplacedMeasurements >= 1): a measurement sweep also takes the time-displaced
                                          charge, spin-z and SDW order-parameter correlators (DETSDW_OBS_CHARGETAU .. _SDWTAU_Q0).  The
                                          field took the second reserved slot of dqmc_tuning: the bytes of the struct are where they were.
@@ -426,6 +429,14 @@ double detsdw_replica_exchange_probability(double par1, double action1, double p
 
 /* RNG restatement, exposed for host-only tests: first n draws of RngWrapper(seed, processIndex) */
 int detsdw_rng_fill(uint32_t seed, uint32_t processIndex, double* out, size_t n);
+/* The same stream driven through the replica's own RngStream by a script of nops steps, host only: op[i] = DETSDW_RNG_RAND01 (arg[i]
+ * single draws), _PEEK (look at the next arg[i] draws without consuming them), _CONSUME (retire arg[i] draws a peek has shown) or
+ * _ROUNDTRIP (serialize, then deserialize into a fresh stream that takes over).  Every draw the script sees is written to
+ * out[its stream position]; *nout = one past the highest position written.  DQMC_EINVAL: a position beyond cap, a draw that differs
+ * from what the same position showed before, a consume past what was peeked, an unknown op. */
+enum { DETSDW_RNG_RAND01 = 0, DETSDW_RNG_PEEK = 1, DETSDW_RNG_CONSUME = 2, DETSDW_RNG_ROUNDTRIP = 3 };
+int detsdw_rng_replay(uint32_t seed, uint32_t processIndex, const int32_t* op, const uint64_t* arg, size_t nops, double* out, size_t cap,
+                      size_t* nout);
 
 #ifdef __cplusplus
 }

@@ -77,8 +77,12 @@ typedef struct dqmc_tuning {
     int32_t bmult_path;        /* checkerboard B-multiply kernel: 0 automatic (the direct kernel for the launch kinds where it measured
                                   faster), 1: the staged kernel k_bmult_chain everywhere, 2: the direct kernel wherever it
                                   applies (checkerboard launches outside shift mode).  Both give the same bits.  Other values:
-                                  DQMC_EINVAL.  (The field took the last reserved slot: the bytes of the struct are where they were.) */
+                                  DQMC_EINVAL.  (The field took the last reserved slot: the bytes of the struct are where they were.)
+                                  The struct has no free slot left, so one more choice travels as a flag bit of this field:
+                                  | DQMC_TUNING_NO_RNG_LOOKAHEAD: the context reserves no second window and no tail of pre-drawn
+                                  uniforms, dqmc_stage_uniforms_tail_host / dqmc_advance_uniforms return DQMC_EINVAL */
 } dqmc_tuning;
+enum { DQMC_TUNING_NO_RNG_LOOKAHEAD = 0x100 };
 
 /* ModelParamsDetSDW fields the kernels depend on (src/detsdwparams.h:24-120) */
 typedef struct dqmc_params {
@@ -230,6 +234,26 @@ int dqmc_reset_storage0(dqmc_ctx* ctx);
 int dqmc_push_uniforms_host(dqmc_ctx* ctx, const double* u, size_t n);
 /* the same for ALL chains of a batched context in one transfer: u = nchains windows of n uniforms each, back to back */
 int dqmc_push_uniforms_all_host(dqmc_ctx* ctx, const double* u, size_t n);
+/* Look-ahead on the stream of uniforms: while the device works through the window [p, p + n) of every chain, the host uploads the
+ * n draws behind it and the next sweep starts from a window spliced on the device -- no transfer and no wait at its head.
+ *   dqmc_uniforms_staging_host: the context's pinned staging buffer (nchains windows of `capacity` doubles are guaranteed to fit back
+ *     to back for every n the context accepts); allocated by the first call.  It waits for an upload that still reads the buffer, so
+ *     the caller may fill it when the call returns.
+ *   dqmc_stage_uniforms_tail_host: u = nchains runs of n uniforms, back to back, chain b's being the stream positions
+ *     [p_b + n, p_b + 2 n) behind its current window; n must be the size of the current window (the last dqmc_push_uniforms_all_host
+ *     or dqmc_advance_uniforms).  u may be the staging buffer itself; otherwise it is copied there first.  The upload runs on a stream
+ *     of its own, behind the last dqmc_advance_uniforms (event), and the call waits for nothing the main stream holds.
+ *   dqmc_advance_uniforms: ONE launch on the main stream, behind the staged upload (event).  offset[b] in 0 .. n = how far chain b's
+ *     stream has moved since its window began (what the device consumed plus what the host drew since); the new window of chain b is
+ *     new[i] = i < n - offset[b] ? cur[offset[b] + i] : tail[i - (n - offset[b])], it takes the place of the current one, and
+ *     rng_consumed = 0, rng_avail = n, error = 0.  The tail is used up: stage the next one before the next advance.
+ * DQMC_EINVAL (nothing launched, nothing changed): no tail staged, an offset > n, n unlike the current window's size, or a context
+ * created with DQMC_TUNING_NO_RNG_LOOKAHEAD.  dqmc_push_uniforms_*_host drop a staged tail.  dqmc_get_schedule_info counts both paths. */
+int dqmc_uniforms_staging_host(dqmc_ctx* ctx, double** buf, size_t* capacity);
+int dqmc_stage_uniforms_tail_host(dqmc_ctx* ctx, const double* u, size_t n);
+int dqmc_advance_uniforms(dqmc_ctx* ctx, const uint64_t* offset /* [nchains] */);
+/* the first n uniforms of the selected chain's current window (tests) */
+int dqmc_get_uniform_window_host(dqmc_ctx* ctx, double* out, size_t n);
 /* updateInSlice (detsdwopdim.cpp:2428-2489, delayed updates :3023-3175, box proposals :3922-3931,
  * deltaSPhi :4186-4239, get_delta_forsite :3179-3289); thermalization != 0 adds the step-size
  * adaptation of updateInSliceThermalization (:3294-3375) */
@@ -263,6 +287,8 @@ typedef struct dqmc_schedule_info {
     int32_t qr_block_gram_schmidt;  /* 1: chain factorisations by block Gram-Schmidt + CholQR2, 0: Householder panels */
     int32_t green_lu;               /* 1: inverse inside greenFromUdV by LU, 0: by QR */
     uint64_t cholqr_fallbacks;      /* factorisations in which a CholQR panel lost definiteness and was redone with Householder panels */
+    uint64_t uniform_windows_advanced;  /* windows of uniforms spliced on the device (dqmc_advance_uniforms) ... */
+    uint64_t uniform_windows_pushed;    /* ... and pushed whole from the host (dqmc_push_uniforms_host / _all_host) */
 } dqmc_schedule_info;
 int dqmc_get_schedule_info(dqmc_ctx* ctx, dqmc_schedule_info* out);
 int dqmc_get_update_state_host(dqmc_ctx* ctx, dqmc_update_state* out);
