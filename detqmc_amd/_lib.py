@@ -302,6 +302,10 @@ SYMBOLS = [
     ("dqmc_series_import_host", C.c_int, [_P, C.POINTER(dqmc_series_state), _DP, C.c_size_t]),
     ("dqmc_get_green_td_fine_host", C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_int)]),
     ("dqmc_td_fine_propagate", C.c_int, [_P, C.c_int, C.c_int]),     # tests only: exported, not declared in include/dqmc_hip.h
+    ("dqmc_set_green_check", C.c_int, [_P, C.c_int]),
+    ("dqmc_green_check_size", C.c_size_t, [_P]),
+    ("dqmc_green_check_read_host", C.c_int, [_P, _DP]),
+    ("dqmc_green_check_reset", C.c_int, [_P]),
     ("dqmc_profile_enable", C.c_int, [_P, C.c_int]),
     ("dqmc_profile_read", C.c_int, [_P, C.POINTER(dqmc_profile)]),
     ("detsdw_create", C.c_int, [C.POINTER(detsdw_params), C.POINTER(_P)]),
@@ -338,6 +342,9 @@ SYMBOLS = [
     ("detsdw_set_green_matrix", C.c_int, [_P, C.c_int]),
     ("detsdw_series_pair_vertex", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _DP, _DP]),
     ("detsdw_series_ph_vertex", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _DP, _DP]),
+    ("detsdw_set_green_check", C.c_int, [_P, C.c_int]),
+    ("detsdw_get_green_check", C.c_int, [_P, _DP]),
+    ("detsdw_reset_green_check", C.c_int, [_P]),
     ("detsdw_series_read_bins", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _DP]),
     ("detsdw_series_end", C.c_int, [_P]),
     ("detsdw_series_configure", C.c_int, [_P, C.c_int]),
@@ -384,6 +391,9 @@ SYMBOLS = [
     ("dethubbard_get_zcorr", C.c_int, [_P, _DP]),
     ("dethubbard_save_state", C.c_int, [_P, C.c_char_p]),
     ("dethubbard_load_state", C.c_int, [_P, C.c_char_p]),
+    ("dethubbard_set_green_check", C.c_int, [_P, C.c_int]),
+    ("dethubbard_get_green_check", C.c_int, [_P, _DP]),
+    ("dethubbard_reset_green_check", C.c_int, [_P]),
     ("dethubbard_rng_rand01", C.c_double, [_P]),
     ("dethubbard_ctx", _P, [_P]),
 ]

@@ -26,6 +26,7 @@ SOURCES = [
     "kernels_lu.hip",
     "kernels_measure.hip",
     "kernels_hubbard.hip",
+    "kernels_green_check.hip",
     "dqmc_context.hip",
     "dqmc_measure_api.hip",
     os.path.join("host", "dsfmt19937.cpp"),

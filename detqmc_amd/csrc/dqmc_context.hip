@@ -638,6 +638,7 @@ void series_free(dqmc_ctx* c) {
     s = dqmc_ctx::Series{};
 }
 
+static void green_check_free(dqmc_ctx* c);                 // the buffers of dqmc_set_green_check (below, next to dqmc_advance)
 extern "C" void dqmc_destroy(dqmc_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->p.device);
@@ -647,6 +648,7 @@ extern "C" void dqmc_destroy(dqmc_ctx* c) {
     custom_free(c);
     custom_pair_free(c);
     green_matrix_free(c);
+    green_check_free(c);
     series_free(c);
     if (c->jacobi_graph) (void)hipGraphExecDestroy(c->jacobi_graph);
     if (c->sw.hflag) (void)hipHostFree(c->sw.hflag);
@@ -1138,6 +1140,69 @@ extern "C" int dqmc_reset_storage0(dqmc_ctx* c) {
     return set_slot_identity(c, c->storage[0]);
 }
 
+// ---------------------------------------------------------------------------------------------
+// wrap-error diagnostics (dqmc_hip.h: dqmc_set_green_check; kernels_green_check.hip)
+// ---------------------------------------------------------------------------------------------
+static size_t green_check_doubles(const dqmc_ctx* c) { return (size_t)2 * (c->n + 1) * DQMC_GREEN_CHECK_FIELDS; }
+static void green_check_free(dqmc_ctx* c) {
+    for (void* q : {(void*)c->gc_keep, (void*)c->gc_part, (void*)c->gc_out, (void*)c->gc_table}) if (q) (void)hipFree(q);
+    c->gc_keep = nullptr; c->gc_part = c->gc_out = c->gc_table = nullptr;
+    c->gc_on = false;
+}
+extern "C" int dqmc_set_green_check(dqmc_ctx* c, int on) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if ((on != 0) == c->gc_on) return DQMC_OK;
+    (void)hipSetDevice(c->p.device);
+    HIPCHK(hipStreamSynchronize(c->st));                   // nothing enqueued still uses the buffers
+    if (!on) { green_check_free(c); return DQMC_OK; }
+    // the new buffers first: a failed allocation leaves the context as it was
+    const size_t nb = (size_t)c->nb, n2 = (size_t)c->n_g * c->n_g, tab = green_check_doubles(c) * nb * sizeof(double);
+    void *keep = nullptr, *part = nullptr, *out = nullptr, *table = nullptr;
+    hipError_t e = hipMalloc(&keep, n2 * nb * sizeof(cplx));
+    if (e == hipSuccess) e = hipMalloc(&part, green_diff_partial_doubles(c->n_g) * nb * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&out, 6 * nb * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&table, tab);
+    if (e == hipSuccess) e = hipMemsetAsync(table, 0, tab, c->st);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->st);
+    if (e != hipSuccess) {
+        for (void* q : {keep, part, out, table}) if (q) (void)hipFree(q);
+        return fail(DQMC_EHIP, std::string("dqmc_set_green_check: ") + hipGetErrorString(e));
+    }
+    c->gc_keep = (cplx*)keep; c->gc_part = (double*)part; c->gc_out = (double*)out; c->gc_table = (double*)table;
+    c->gc_on = true;
+    return DQMC_OK;
+}
+extern "C" size_t dqmc_green_check_size(dqmc_ctx* c) { return c && c->gc_on ? green_check_doubles(c) : 0; }
+extern "C" int dqmc_green_check_read_host(dqmc_ctx* c, double* out) {
+    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
+    if (!c->gc_on) return fail(DQMC_EINVAL, "the wrap-error diagnostics are switched off (dqmc_set_green_check)");
+    (void)hipSetDevice(c->p.device);
+    HIPCHK(copy_sync(c, out, c->gc_table, green_check_doubles(c) * c->nb * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+extern "C" int dqmc_green_check_reset(dqmc_ctx* c) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (!c->gc_on) return fail(DQMC_EINVAL, "the wrap-error diagnostics are switched off (dqmc_set_green_check)");
+    (void)hipSetDevice(c->p.device);
+    HIPCHK(hipMemsetAsync(c->gc_table, 0, green_check_doubles(c) * c->nb * sizeof(double), c->st));
+    return finish(c, "dqmc_green_check_reset");
+}
+// the advance is about to rebuild G: keep the wrapped one
+static void green_check_keep(dqmc_ctx* c) {
+    ProfScope ps(c, FAM_OTHER, 1);
+    const size_t n2 = (size_t)c->n_g * c->n_g;
+    launch_green_keep(c->lc, c->G, c->gc_keep, n2 * sizeof(cplx), n2);
+}
+// ... and it has: one sample into row [dir][j]; stored: the factorisation the advance is about to put into storage[j]
+static void green_check_sample(dqmc_ctx* c, int dir, int j, const UdVSlot& stored) {
+    ProfScope ps(c, FAM_OTHER, 2);
+    const size_t n2 = (size_t)c->n_g * c->n_g;
+    const GreenCheckFold fold = {c->gc_table, green_check_doubles(c) * sizeof(double), (dir == DQMC_UP ? c->n + 1 : 0) + j, stored.d,
+                                 c->stab == DQMC_STAB_SVD ? c->sv : nullptr};
+    launch_green_diff(c->lc, c->gc_keep, n2 * sizeof(cplx), c->G, c->n_g, c->n_g, c->N, c->gc_part,
+                      green_diff_partial_doubles(c->n_g) * sizeof(double), c->gc_out, 6 * sizeof(double), &fold);
+}
+
 // advanceDownGreen (detmodel.h:956-1017) / advanceUpGreen (detmodel.h:1109-1163)
 extern "C" int dqmc_advance(dqmc_ctx* c, int dir, int l) {
     if (!c) return fail(DQMC_EINVAL, "null ctx");
@@ -1148,6 +1213,8 @@ extern "C" int dqmc_advance(dqmc_ctx* c, int dir, int l) {
         if (l < 1 || l > n) return fail(DQMC_EINVAL, "advanceDown: l out of range");
         if (c->currentTimeslice != s * (l - 1)) return fail(DQMC_EINVAL, "advanceDown: currentTimeslice != s*(l-1)");
         const int k_l = (l < n) ? s * l : m, k_lm1 = s * (l - 1);
+        const bool check = c->gc_on && !c->g_stale;      // the wrapped G exists: compare it with the rebuilt one
+        if (check) green_check_keep(c);
         UdVSlot L = c->spare;
         if (l < n) {
             const UdVSlot& st = c->storage[l];
@@ -1164,6 +1231,7 @@ extern "C" int dqmc_advance(dqmc_ctx* c, int dir, int l) {
             if (!rc && c->td_on) c->td_slice = s * (l - 1);
         } else rc = green_from_eye(c, L, KIND_L);
         if (rc) return rc;
+        if (check) green_check_sample(c, dir, l - 1, L);
         std::swap(c->storage[l - 1], c->spare);          // storage[l-1] = UdV_L
         c->currentTimeslice = s * (l - 1);
         c->g_stale = false;
@@ -1172,6 +1240,8 @@ extern "C" int dqmc_advance(dqmc_ctx* c, int dir, int l) {
         if (l < 0 || l > n - 1) return fail(DQMC_EINVAL, "advanceUp: l out of range");
         const int k_l = s * l, k_lp1 = (l < n - 1) ? s * (l + 1) : m;
         if (c->currentTimeslice != k_lp1) return fail(DQMC_EINVAL, "advanceUp: currentTimeslice != k_{l+1}");
+        const bool check = c->gc_on && !c->g_stale;
+        if (check) green_check_keep(c);
         const UdVSlot& st = c->storage[l];
         UdVSlot T = c->spare;
         bmult_dev(c, DQMC_LEFT, 0, k_lp1, k_l, c->T1, st.U);
@@ -1181,6 +1251,7 @@ extern "C" int dqmc_advance(dqmc_ctx* c, int dir, int l) {
             if (!rc && c->td_on) c->td_slice = k_lp1;
         } else rc = green_from_eye(c, T, KIND_R);
         if (rc) return rc;
+        if (check) green_check_sample(c, dir, l + 1, T);
         std::swap(c->storage[l + 1], c->spare);
         c->currentTimeslice = k_lp1;
         c->g_stale = false;

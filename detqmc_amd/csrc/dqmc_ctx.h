@@ -213,6 +213,11 @@ struct dqmc_ctx {
     double* shift_buf = nullptr;        // [nchains][opdim] displacements of a global shift move (shared buffer)
     int currentTimeslice = 0;
     bool g_stale = false;          // dqmc_wrap_skip moved currentTimeslice without computing G: nothing may read G until it is rebuilt
+    // dqmc_set_green_check: while on, the wrapped G every advance keeps [chain][n_g^2], the compare kernel's partials and results and
+    // the table [chain][2][n+1][DQMC_GREEN_CHECK_FIELDS], outside the arena, allocated by the switch-on and freed by the switch-off
+    bool gc_on = false;
+    cplx* gc_keep = nullptr;
+    double *gc_part = nullptr, *gc_out = nullptr, *gc_table = nullptr;
     // profiling
     bool prof = false;
     int prof_depth = 0;                 // open ProfScopes (they nest)

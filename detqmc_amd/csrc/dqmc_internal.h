@@ -404,6 +404,17 @@ size_t series_ph_bubble_lds_bytes(int opdim, int N);
 bool launch_series_ph_vertex(const Launch& lc, const DevModel& hm, const double* bins, const double* mean, const double* trig, size_t S, int B,
                              int nfreq, size_t off_chi, size_t off_g, int count, const CustomBond& bond, int qx, int qy, int apbx, int apby,
                              double* pb, double* value, double* err);
+// wrap-error diagnostics (kernels_green_check.hip; dqmc_set_green_check): the six results of dqmc_hip.h for the wrapped Gw against the
+// fresh Gf, both n x n at leading dimension ld, in two launches.  Gf is a per-chain buffer at the chain stride; Gw, the partials
+// (green_diff_partial_doubles(n) doubles per chain) and out (6 doubles per chain: maxAbs, argmax, maxSiteDiag, sumAbs, maxFresh,
+// nonfinite) have strides of their own, in bytes (the context keeps them outside the arena).  fold != nullptr: the finalise step also
+// forms the log scale spreads of d and, unless null, sv (n values each, per-chain buffers at the chain stride) and folds the sample
+// into row `row` of every chain's table
+struct GreenCheckFold { double* table; size_t table_stride; int row; const double* d; const double* sv; };
+size_t green_diff_partial_doubles(int n);
+void launch_green_keep(const Launch& lc, const cplx* G, cplx* keep, size_t keep_stride, size_t count);   // keep[chain] = G of the chain
+void launch_green_diff(const Launch& lc, const cplx* Gw, size_t gw_stride, const cplx* Gf, int n, int ld, int N, double* part,
+                       size_t part_stride, double* out, size_t out_stride, const GreenCheckFold* fold = nullptr);
 size_t measure_custom_row_doubles(int count, int N);
 size_t measure_td_custom_onebody_cplx(int count, int N);
 size_t measure_eq_custom_onebody_cplx(int count, int N);

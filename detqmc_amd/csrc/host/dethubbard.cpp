@@ -261,5 +261,11 @@ extern "C" int dethubbard_load_state(dethubbard_replica* r, const char* path) {
     if (!path) { g_hub_err = "null path"; return DQMC_EINVAL; }
     HGUARD(r->impl->loadState(path))
 }
+extern "C" int dethubbard_set_green_check(dethubbard_replica* r, int on) { HGUARD(r->impl->setGreenCheck(on != 0)) }
+extern "C" int dethubbard_get_green_check(dethubbard_replica* r, double* out) {
+    if (!out) { g_hub_err = "null argument"; return DQMC_EINVAL; }
+    HGUARD(r->impl->getGreenCheck(out))
+}
+extern "C" int dethubbard_reset_green_check(dethubbard_replica* r) { HGUARD(r->impl->resetGreenCheck()) }
 extern "C" double dethubbard_rng_rand01(dethubbard_replica* r) { return r ? r->impl->rand01(r->sel) : -1.0; }
 extern "C" dqmc_ctx* dethubbard_ctx(dethubbard_replica* r) { return r ? r->impl->ctx() : nullptr; }

@@ -26,6 +26,10 @@ public:
     void saveState(const std::string& path);
     void loadState(const std::string& path);
     double rand01(int b) { return ch_[b].rng.rand01(); }
+    // wrap-error diagnostics of the kernel context (dqmc_set_green_check); out[nchains][2][n+1][DQMC_GREEN_CHECK_FIELDS]
+    void setGreenCheck(bool on) { check(dqmc_set_green_check(ctx_, on ? 1 : 0), "dqmc_set_green_check"); }
+    void getGreenCheck(double* out) { check(dqmc_green_check_read_host(ctx_, out), "dqmc_green_check_read_host"); }
+    void resetGreenCheck() { check(dqmc_green_check_reset(ctx_), "dqmc_green_check_reset"); }
     dqmc_ctx* ctx() { return ctx_; }
 
 private:

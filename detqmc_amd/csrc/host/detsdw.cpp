@@ -295,6 +295,7 @@ int DetSDW::uniformsPerSite() const {
 // which proposal / adaptation this sweep uses (updateInSlice, updateInSliceThermalization: detsdwopdim.cpp:2438-2470, 3299-3321)
 // Last slice of a segment outside measurement sweeps (measure(k) reads G right after the update), sequential update schedule:
 // dqmc_update_slice_final leaves out the flush nobody reads and, in a down sweep, does the bookkeeping of the dead wrap as well.
+// Not while the wrap-error diagnostics are on (setGreenCheck): the advance compares exactly the G these shortcuts leave out.
 bool DetSDW::updateInSlice(Group& g, int k, bool thermalization, bool segmentEnd, bool down) {
     const detsdw_params& p = ch_[0].pars;
     int proposal = DQMC_PROPOSE_BOX, adapt = DQMC_ADAPT_BOX;
@@ -305,7 +306,7 @@ bool DetSDW::updateInSlice(Group& g, int k, bool thermalization, bool segmentEnd
         proposal = DQMC_PROPOSE_ROTATE_AND_SCALE;
         adapt = (performedSweeps_ % 200 < 100) ? DQMC_ADAPT_ROTATE : DQMC_ADAPT_SCALE;
     }
-    if (segmentEnd && !measuring_) {
+    if (segmentEnd && !measuring_ && !greenCheck_) {
         dqmc_schedule_info si;
         check(dqmc_get_schedule_info(g.ctx, &si), "dqmc_get_schedule_info");
         if (!si.pipelined) {
@@ -346,7 +347,7 @@ void DetSDW::sweepDown(Group& g, bool thermalization) {
     for (int k = m_; k >= (n_ - 1) * s_ + 1; --k) {
         const bool last = k == (n_ - 1) * s_ + 1;
         if (updateInSlice(g, k, thermalization, last, true)) continue;
-        check(!last ? dqmc_wrap(ctx_, DQMC_DOWN, k) : dqmc_wrap_skip(ctx_, DQMC_DOWN, k), "wrapDownGreen");
+        check(!last || greenCheck_ ? dqmc_wrap(ctx_, DQMC_DOWN, k) : dqmc_wrap_skip(ctx_, DQMC_DOWN, k), "wrapDownGreen");
     }
     for (int l = n_ - 1; l >= 1; --l) {
         check(dqmc_advance(ctx_, DQMC_DOWN, l + 1), "advanceDownGreen");
@@ -354,7 +355,7 @@ void DetSDW::sweepDown(Group& g, bool thermalization) {
         for (int k = l * s_; k >= (l - 1) * s_ + 1; --k) {
             const bool last = k == (l - 1) * s_ + 1;
             if (updateInSlice(g, k, thermalization, last, true)) continue;
-            check(!last ? dqmc_wrap(ctx_, DQMC_DOWN, k) : dqmc_wrap_skip(ctx_, DQMC_DOWN, k), "wrapDownGreen");
+            check(!last || greenCheck_ ? dqmc_wrap(ctx_, DQMC_DOWN, k) : dqmc_wrap_skip(ctx_, DQMC_DOWN, k), "wrapDownGreen");
         }
     }
     check(dqmc_advance(ctx_, DQMC_DOWN, 1), "advanceDownGreen");
@@ -1194,6 +1195,27 @@ void DetSDW::setGreenMatrix(bool on) {
     }
     greenMatrix_ = on;
     for (auto& c : ch_) { c.td.greenMatrixTau.clear(); c.tdFine.greenMatrixTau.clear(); }
+}
+// The wrap-error diagnostics of every kernel context; if a later context fails the earlier ones are switched back
+void DetSDW::setGreenCheck(bool on) {
+    if (on == greenCheck_) return;
+    for (size_t i = 0; i < groups_.size(); ++i) {
+        const int rc = dqmc_set_green_check(groups_[i].ctx, on ? 1 : 0);
+        if (rc == DQMC_OK) continue;
+        const std::string why = dqmc_last_error();
+        for (size_t k = 0; k < i; ++k) (void)dqmc_set_green_check(groups_[k].ctx, on ? 0 : 1);
+        throw GeneralError(rc, "dqmc_set_green_check: " + why);
+    }
+    greenCheck_ = on;
+}
+void DetSDW::getGreenCheck(double* out) {
+    if (!greenCheck_) throw ParameterWrong("the wrap-error diagnostics are switched off (detsdw_set_green_check)");
+    const size_t per = (size_t)2 * (n_ + 1) * DQMC_GREEN_CHECK_FIELDS;
+    for (Group& g : groups_) check(dqmc_green_check_read_host(g.ctx, out + (size_t)g.first * per), "dqmc_green_check_read_host");
+}
+void DetSDW::resetGreenCheck() {
+    if (!greenCheck_) throw ParameterWrong("the wrap-error diagnostics are switched off (detsdw_set_green_check)");
+    for (Group& g : groups_) check(dqmc_green_check_reset(g.ctx), "dqmc_green_check_reset");
 }
 bool DetSDW::customPairTd() const { return pairCount() && td_level(ch_[0].pars); }
 bool DetSDW::customPairEq() const { return pairCount() && eq_correlators(ch_[0].pars); }
@@ -2055,6 +2077,16 @@ extern "C" int detsdw_series_custom_pair_derived(detsdw_replica* r, int c, int q
 }
 extern "C" int detsdw_set_green_matrix(detsdw_replica* r, int on) {
     RGUARD(r->impl->setGreenMatrix(on != 0))
+}
+extern "C" int detsdw_set_green_check(detsdw_replica* r, int on) {
+    RGUARD(r->impl->setGreenCheck(on != 0))
+}
+extern "C" int detsdw_get_green_check(detsdw_replica* r, double* out) {
+    if (!out) { g_host_err = "null argument"; return DQMC_EINVAL; }
+    RGUARD(r->impl->getGreenCheck(out))
+}
+extern "C" int detsdw_reset_green_check(detsdw_replica* r) {
+    RGUARD(r->impl->resetGreenCheck())
 }
 extern "C" int detsdw_series_pair_vertex(detsdw_replica* r, int c, int qx, int qy, double* value, double* err) {
     if (!value || !err) { g_host_err = "null argument"; return DQMC_EINVAL; }

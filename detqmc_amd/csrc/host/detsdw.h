@@ -82,6 +82,10 @@ public:
     void seriesCustomPairDerived(int c, int qx, int qy, double* value, double* err);
     // the averaged Green's function block of every kernel context, and the bubble / vertex of pair operator c from the series
     void setGreenMatrix(bool on);
+    // wrap-error diagnostics of every kernel context (include/detsdw_host.h); out[nchains][2][n+1][DQMC_GREEN_CHECK_FIELDS], handle order
+    void setGreenCheck(bool on);
+    void getGreenCheck(double* out);
+    void resetGreenCheck();
     void seriesPairVertex(int c, int qx, int qy, double* value, double* err);
     void seriesPhVertex(int c, int qx, int qy, double* value, double* err);      // ... of user-defined bilinear c
     void seriesReadBins(int which, int first, int count, double* out, int b = 0);
@@ -168,6 +172,7 @@ private:
     std::vector<dqmc_cplx> pairF_[3];              // F0, Fx, Fy of setCustomPairOperators, [DQMC_CUSTOM_MAX][4][4] each, zero padded
     int pairCount_ = 0;
     bool greenMatrix_ = false;                     // setGreenMatrix: every kernel context fills its averaged Green's function block
+    bool greenCheck_ = false;                      // setGreenCheck: the sweeps take the plain path at segment ends, so that every advance finds a wrapped G
     int pairCount() const { return pairCount_; }
     bool customPairTd() const;                     // pair operators are set and the handle measures time-displaced
     bool customPairEq() const;                     // ... the equal-time correlators

@@ -169,4 +169,16 @@ int dqmc_prim_qr_bgs(void* arena, size_t bytes, int nb, size_t cs, int n, long l
     });
 }
 
+// wrap-error compare (launch_green_diff): Gw against Gf, both n x n at leading dimension ld; N: sites (the site diagonal is row mod N ==
+// col mod N); part: green_diff_partial_doubles(n) = 6 ceil(n^2 / 2048) doubles of scratch, out: 6 doubles (maxAbs, argmax, maxSiteDiag,
+// sumAbs, maxFresh, nonfinite), all per chain at the chain stride
+int dqmc_prim_green_diff(void* arena, size_t bytes, int nb, size_t cs, long long Gw, long long Gf, long long part, long long out,
+                         int n, int ld, int N, char* msg, int msglen) {
+    return with_arena(arena, bytes, nb, cs, msg, msglen, [&](void* d, const Launch& lc) {
+        if (n < 1 || ld < n || N < 1 || Gw < 0 || Gf < 0 || part < 0 || out < 0) return -2;
+        launch_green_diff(lc, at<const cplx>(d, Gw), cs, at<const cplx>(d, Gf), n, ld, N, at<double>(d, part), cs, at<double>(d, out), cs);
+        return 0;
+    });
+}
+
 }  // extern "C"

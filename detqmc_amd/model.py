@@ -269,6 +269,74 @@ def binning_analysis(bins, bin_size, variance=None):
     return np.array(errs) if variance is None else (np.array(errs), np.array(taus))
 
 
+# wrap-error diagnostics (dqmc_set_green_check): the doubles of one table row, in order (include/dqmc_hip.h)
+GREEN_CHECK_FIELDS = ("count", "lastMaxAbs", "maxAbs", "sumMaxAbs", "maxSiteDiag", "sumMeanAbs", "maxRel", "argmax", "nonfinite",
+                      "logScaleSpread", "logSvSpread")
+
+
+def green_check_decode(raw, ng):
+    """The tables of dqmc_green_check_read_host / detsdw_get_green_check, raw (chains, 2, n+1, 11), as a dict of arrays of shape
+    (chains, 2, n+1): axis 1 is the sweep direction (0 down, 1 up), axis 2 the storage index j the advance landed on (boundary
+    tau = j s).  count; lastMaxAbs, maxAbs (running maximum), meanMaxAbs (mean over the samples) of max |G_wrapped - G_rebuilt|;
+    maxSiteDiag, the maximum over the entries local observables read (row mod N == col mod N); meanAbs, the mean over the samples of the
+    mean difference; maxRel = maxAbs / max |G_rebuilt|; argmax (..., 2) = (row, col) of the entry behind maxAbs; nonfinite, the entries
+    that were inf or NaN (maxAbs is inf then); logScaleSpread = log(max d / min d) of the stored factorisation; logSvSpread = log of the
+    condition number of G^-1 (SVD stabilisation; 0 with QR).  Means are 0 in rows without a sample"""
+    raw = np.asarray(raw, dtype=np.float64)
+    if raw.ndim != 4 or raw.shape[1] != 2 or raw.shape[3] != len(GREEN_CHECK_FIELDS):
+        raise ValueError("green_check_decode: expected shape (chains, 2, n+1, %d), got %r" % (len(GREEN_CHECK_FIELDS), raw.shape))
+    f = {name: raw[..., i] for i, name in enumerate(GREEN_CHECK_FIELDS)}
+    count = f["count"].astype(np.int64)
+    denom = np.maximum(count, 1)
+    idx = f["argmax"].astype(np.int64)
+    return {"count": count, "lastMaxAbs": f["lastMaxAbs"].copy(), "maxAbs": f["maxAbs"].copy(), "meanMaxAbs": f["sumMaxAbs"] / denom,
+            "maxSiteDiag": f["maxSiteDiag"].copy(), "meanAbs": f["sumMeanAbs"] / denom, "maxRel": f["maxRel"].copy(),
+            "argmax": np.stack([idx % ng, idx // ng], axis=-1), "nonfinite": f["nonfinite"].astype(np.int64),
+            "logScaleSpread": f["logScaleSpread"].copy(), "logSvSpread": f["logSvSpread"].copy()}
+
+
+def green_check_worst(decoded):
+    """per chain (maxAbs, dir, boundary, row, col) of the largest maxAbs of green_check_decode's result (the first row in (dir, boundary)
+    order on ties); dir 0: down sweep, 1: up sweep; a NaN-free inf (non-finite entries) wins"""
+    out = []
+    for mx, am in zip(decoded["maxAbs"], decoded["argmax"]):
+        d, j = np.unravel_index(int(np.argmax(mx)), mx.shape)
+        out.append((float(mx[d, j]), int(d), int(j), int(am[d, j, 0]), int(am[d, j, 1])))
+    return out
+
+
+class _GreenCheck:
+    """set_green_check / green_check / green_check_worst / green_check_reset of a host-layer handle; the class names its three C entry
+    points and the error channel in _gc_calls and answers _gc_shape() = (chains, n, n_g)"""
+
+    def _gc_handle(self):
+        return self.h
+
+    def set_green_check(self, on=True):
+        """wrap-error diagnostics: while on, every stabilisation boundary compares the Green's function carried by wraps and updates with
+        the one rebuilt from the UdV factors, on the device (green_check()).  The sweeps then take no shortcut at segment ends -- n more
+        wraps and flushes per sweep, a copy of G and the compare -- and the Markov chain keeps its bits.  Between sweeps"""
+        check(getattr(self.lib, self._gc_calls[0])(self._gc_handle(), int(on)), host=self._gc_calls[3])
+
+    def _green_check_raw(self):
+        chains, n, _ = self._gc_shape()
+        raw = np.zeros((chains, 2, n + 1, len(GREEN_CHECK_FIELDS)))
+        check(getattr(self.lib, self._gc_calls[1])(self._gc_handle(), raw.ctypes.data_as(_lib._DP)), host=self._gc_calls[3])
+        return raw
+
+    def green_check(self):
+        """dict of arrays (chains, 2, n+1) (see green_check_decode); raises while the switch is off"""
+        return green_check_decode(self._green_check_raw(), self._gc_shape()[2])
+
+    def green_check_worst(self):
+        """per chain (maxAbs, dir, boundary, row, col) of the worst boundary so far (green_check_worst)"""
+        return green_check_worst(self.green_check())
+
+    def green_check_reset(self):
+        """clears the tables; the switch stays on"""
+        check(getattr(self.lib, self._gc_calls[2])(self._gc_handle()), host=self._gc_calls[3])
+
+
 SPIN_PROPOSAL = {"box": 0, "rotate_then_scale": 1, "rotate_and_scale": 2}
 PROPOSE = {"box": 0, "rotate": 1, "scale": 2, "rotate_and_scale": 3}
 ADAPT = {"box": 0, "rotate": 1, "scale": 2}
@@ -694,6 +762,25 @@ class KernelContext:
         a block of its own (coarse rows by measure_timedisplaced_green_matrix, every-slice channel 7): the input of the pairing bubble
         (series_pair_vertex, pair_bubble).  Needs timeDisplaced >= 1; refused under weakZflux"""
         check(self.lib.dqmc_set_green_matrix(self.h, int(on)))
+
+    def set_green_check(self, on=True):
+        """wrap-error diagnostics: while on, every advance that finds G fresh keeps it and compares it with the rebuilt one on the device
+        (all chains, no host synchronisation), one sample into row [dir][j] of green_check()"""
+        check(self.lib.dqmc_set_green_check(self.h, int(on)))
+
+    def green_check_raw(self):
+        """the tables of all chains, (nchains, 2, n+1, 11) doubles (include/dqmc_hip.h); raises while the switch is off"""
+        raw = np.zeros((self.lib.dqmc_num_chains(self.h), 2, self.n + 1, len(GREEN_CHECK_FIELDS)))
+        if self.lib.dqmc_green_check_size(self.h) not in (0, raw[0].size):
+            raise RuntimeError("dqmc_green_check_size disagrees with the table layout")
+        check(self.lib.dqmc_green_check_read_host(self.h, raw.ctypes.data_as(_lib._DP)))
+        return raw
+
+    def green_check(self):
+        return green_check_decode(self.green_check_raw(), self.ng)
+
+    def green_check_reset(self):
+        check(self.lib.dqmc_green_check_reset(self.h))
 
     def measure_timedisplaced_green_matrix(self, j):
         """the averaged Green's function block at boundary j, one launch"""
@@ -1182,7 +1269,7 @@ def _host_params(pars: SDWParams):
         tuning=_tuning(pars.pipeline, pars.qrVariant, pars.greenVariant, pars.maxJacobiSweeps, pars.proposalBudget, pars.decideThreads, pars.bmultPath, pars.rngLookahead))
 
 
-class DetSDW:
+class DetSDW(_GreenCheck):
     """The replica (C++ host layer): same method names as the reference's DetSDW / DetModel.
 
     Also serves as the view of ONE chain of a DetSDWBatch (`batch.chain(b)`): then it does not own the
@@ -1220,6 +1307,17 @@ class DetSDW:
             self.close()
         except Exception:
             pass
+
+    _gc_calls = ("detsdw_set_green_check", "detsdw_get_green_check", "detsdw_reset_green_check", True)
+
+    def _gc_handle(self):
+        if self._batch is not None:
+            raise RuntimeError("the wrap-error diagnostics belong to the whole batch: call them on the DetSDWBatch")
+        return self.h
+
+    def _gc_shape(self):
+        i = self.info
+        return 1, i.n, i.n_g
 
     def sweep(self, takeMeasurements=False):
         if self._batch is not None:
@@ -1468,7 +1566,7 @@ class DetSDW:
         check(self.lib.detsdw_set_control_data(self.h, C.byref(cd)), host=True)
 
 
-class DetSDWBatch:
+class DetSDWBatch(_GreenCheck):
     """The replicas of one parallel-tempering ensemble on ONE GPU, swept in lockstep by one kernel context
     (detsdw_create_batch): every launch carries all chains, which is what fills the chip.  The parameter sets
     may differ only in r, rngSeed and simindex; chain b follows exactly the Markov chain of DetSDW(pars[b])."""
@@ -1489,6 +1587,13 @@ class DetSDWBatch:
 
     def __len__(self):
         return len(self.chains)
+
+    # the tables are per chain (per slot of the handle): not routed by control parameter, not part of save_state or of the series
+    _gc_calls = ("detsdw_set_green_check", "detsdw_get_green_check", "detsdw_reset_green_check", True)
+
+    def _gc_shape(self):
+        i = self.chains[0].info
+        return len(self.chains), i.n, i.n_g
 
     def chain(self, b):
         return self.chains[b]
@@ -1749,7 +1854,7 @@ class HubbardParams:
     stabilisation: str = "svd"
 
 
-class DetHubbard:
+class DetHubbard(_GreenCheck):
     """The Hubbard replica of BASELINE config 1 (C++ host layer detqmc_amd/csrc/host/dethubbard.cpp): the reference's
     DetHubbard (src/dethubbard.{h,cpp}) with both spin sectors in one block-diagonal Green's function on the GPU.
     nchains > 1: independent replicas (simindex, simindex + 1, ...) in lockstep; `select(b)` picks the one the getters
@@ -1779,6 +1884,12 @@ class DetHubbard:
 
     def select(self, b):
         check(self.lib.dethubbard_select_chain(self.h, b), host="hubbard")
+
+    _gc_calls = ("dethubbard_set_green_check", "dethubbard_get_green_check", "dethubbard_reset_green_check", "hubbard")
+
+    def _gc_shape(self):
+        i = self.info
+        return self.nchains, i.n, 2 * i.N
 
     def sweep(self, takeMeasurements=False):
         check(self.lib.dethubbard_sweep(self.h, int(takeMeasurements)), host="hubbard")

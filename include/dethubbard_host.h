@@ -68,6 +68,13 @@ int dethubbard_get_zcorr(dethubbard_replica* r, double* out /* [N] */);
 int dethubbard_save_state(dethubbard_replica* r, const char* path);
 int dethubbard_load_state(dethubbard_replica* r, const char* path);
 double dethubbard_rng_rand01(dethubbard_replica* r);
+/* Wrap-error diagnostics (dqmc_set_green_check in dqmc_hip.h: definitions and table layout).  dethubbard_set_green_check(r, on): the
+ * switch of the replica's kernel context, between sweeps; this replica's sweeps take no shortcut at segment ends, so every advance of a
+ * sweep samples and the chain does not depend on the switch.  dethubbard_get_green_check: out[nchains][2][n+1][DQMC_GREEN_CHECK_FIELDS];
+ * it and the reset return DQMC_EINVAL while the switch is off.  The table is per chain and is not part of dethubbard_save_state. */
+int dethubbard_set_green_check(dethubbard_replica* r, int on);
+int dethubbard_get_green_check(dethubbard_replica* r, double* out);
+int dethubbard_reset_green_check(dethubbard_replica* r);
 dqmc_ctx* dethubbard_ctx(dethubbard_replica* r);
 
 #ifdef __cplusplus

@@ -356,6 +356,18 @@ int detsdw_series_pair_vertex(detsdw_replica* r, int c, int qx, int qy, double* 
  * chibar_c(Q, tau_k), k = 0 .. m, over all sub-batch contexts in handle order.  Needs the matrices and detsdw_set_green_matrix set before
  * the series began, timeDisplacedParticleHole and timeDisplacedEverySlice; no new part and no new flag. */
 int detsdw_series_ph_vertex(detsdw_replica* r, int c, int qx, int qy, double* value, double* err);
+/* Wrap-error diagnostics (dqmc_set_green_check in dqmc_hip.h: definitions, table layout).  detsdw_set_green_check(on): forwarded to every
+ * sub-batch context, between sweeps.  While on, sweepDown and sweepUp take the plain path at segment ends in every sweep, measuring or
+ * not -- dqmc_update_slice_ex followed by dqmc_wrap, never dqmc_update_slice_final or dqmc_wrap_skip -- so that every one of the n
+ * advances of a sweep finds a wrapped G and takes a sample.  The shortcuts only leave out work nobody reads: fields, Green's functions,
+ * random streams and observables keep their bits whether the switch is on or off.  What it costs: n un-skipped wraps and flushes per
+ * sweep, a copy of G and the compare.  detsdw_get_green_check: out[nchains][2][n+1][DQMC_GREEN_CHECK_FIELDS], chain-major
+ * over all sub-batch contexts in handle order; it and detsdw_reset_green_check raise ParameterWrong while the switch is off.
+ * Not included: the table is per chain (per slot of the handle) -- it is not routed by control parameter under replica exchange -- and
+ * it is no part of detsdw_save_state or of the measurement series. */
+int detsdw_set_green_check(detsdw_replica* r, int on);
+int detsdw_get_green_check(detsdw_replica* r, double* out);
+int detsdw_reset_green_check(detsdw_replica* r);
 int detsdw_series_read_bins(detsdw_replica* r, int which, int first, int count, double* out);
 int detsdw_series_end(detsdw_replica* r);
 /* The series over a long run (kernel calls and formulas: dqmc_hip.h).  All of it is new surface: without these calls nothing changes.

@@ -228,6 +228,47 @@ int dqmc_wrap(dqmc_ctx* ctx, int dir, int k);
 int dqmc_wrap_skip(dqmc_ctx* ctx, int dir, int k);
 /* sweepUp resets storage[0] to the identity (detmodel.h:1293-1295) */
 int dqmc_reset_storage0(dqmc_ctx* ctx);
+/* Wrap-error diagnostics ("green check"): how far the Green's function carried by wraps and updates has drifted from the one rebuilt
+ * from the UdV factors, at every stabilisation boundary -- the number that tells whether the interval s is adequate (the reference's
+ * logGreenConsistency, detmodel.h:993-1010, 1129-1158, and logSV, detmodel.h:796-807).  Both models.  dqmc_set_green_check(ctx, on) is
+ * run-time state, to be changed between entry calls: switching on allocates, outside the arena and cleared, one G-sized buffer per chain,
+ * the partial results of the compare kernel and the table below (a failed allocation leaves the context as it was); switching off frees
+ * them; a repeated call changes nothing.  With the switch off no buffer exists, no launch is added and every entry point behaves bit
+ * for bit as without this section.
+ * While on, a dqmc_advance that finds G fresh on entry (no dqmc_wrap_skip / dqmc_update_slice_final since it was last computed or set)
+ * keeps a copy Gw of it, rebuilds G = Gf as always and then compares the two on the device, all chains in one stream-ordered pass
+ * (no host synchronisation, no atomics, fixed summation order: the same matrices give the same bits):
+ *   maxAbs      = max |Gw - Gf| over all entries, argmax = row + col n_g of the first entry (column-major order) that attains it,
+ *                 0 for an all-zero difference
+ *   maxSiteDiag = the same maximum over the entries with row mod N == col mod N (the reference's "block diagonals": what local
+ *                 observables read)
+ *   meanAbs     = sum |Gw - Gf| / n_g^2,   maxRel = maxAbs / max |Gf|
+ *   nonfinite   = entries where either matrix is inf or NaN; such an entry enters maxAbs (and argmax) as +inf and stays out of
+ *                 maxSiteDiag, meanAbs and max |Gf|, so a NaN is never hidden by a maximum
+ * and folds them into row [dir][j] of every chain's table, dir = 0 for DQMC_DOWN, 1 for DQMC_UP, j = the storage index the advance
+ * lands on (l - 1 for a down advance: 0 .. n-1; l + 1 for an up advance: 1 .. n).  An advance that finds G stale takes no sample and
+ * moves no count; dqmc_udv_setup, dqmc_restore and dqmc_set_green_host never take one themselves (the advance that follows a
+ * dqmc_set_green_host compares against the matrix that call set).
+ * Table: per chain [2][n+1] rows of DQMC_GREEN_CHECK_FIELDS doubles, all zero after the switch-on and dqmc_green_check_reset:
+ *   [0] count            samples folded into the row
+ *   [1] lastMaxAbs       maxAbs of the latest sample
+ *   [2] maxAbs           running maximum of maxAbs          [3] sumMaxAbs   sum of maxAbs (mean = / count)
+ *   [4] maxSiteDiag      running maximum                    [5] sumMeanAbs  sum of meanAbs (mean = / count)
+ *   [6] maxRel           running maximum                    [7] argmax      of the sample that set [2]
+ *   [8] nonfinite        sum over the samples
+ *   [9] logScaleSpread   running maximum of log(max d / min d) of the scales d of the factorisation the advance just stored in
+ *                        storage[j] (both stabilisation modes)
+ *   [10] logSvSpread     DQMC_STAB_SVD: running maximum of log(max sv) - log(min sv) of the singular values of G^-1 the rebuild found
+ *                        (dqmc_get_sv_host; the reference's logSV).  DQMC_STAB_QR: 0 (the vector holds the log-det factors there)
+ * The spreads are formed on the device in the finalise step of the compare.  dqmc_green_check_size: doubles per chain, 2 (n + 1)
+ * DQMC_GREEN_CHECK_FIELDS, 0 while off.  dqmc_green_check_read_host: out[nchains][2][n+1][DQMC_GREEN_CHECK_FIELDS], all chains;
+ * synchronises.  The readers and the reset return DQMC_EINVAL while the switch is off.  The table is per chain of this context: it is
+ * not part of any saved state or of the measurement series, and dqmc_measure_reset leaves it alone. */
+enum { DQMC_GREEN_CHECK_FIELDS = 11 };
+int dqmc_set_green_check(dqmc_ctx* ctx, int on);
+size_t dqmc_green_check_size(dqmc_ctx* ctx);
+int dqmc_green_check_read_host(dqmc_ctx* ctx, double* out);
+int dqmc_green_check_reset(dqmc_ctx* ctx);
 
 /* ---- local updates (a17-a20) ---------------------------------------------------------------- */
 /* replace the window of pre-drawn uniforms (0,1) the device consumes in stream order */
