@@ -186,6 +186,8 @@ SYMBOLS = [
     ("dqmc_bmult_host", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ("dqmc_bmult_src_host", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     ("dqmc_udv_decompose_host", C.c_int, [_P, _P, _P, _DP, _P, C.POINTER(C.c_int)]),
+    ("dqmc_decompose_host", C.c_int, [_P, _P, _DP, _DP, C.c_int, _P, _P, _DP, _P, C.POINTER(C.c_int)]),
+    ("dqmc_green_from_factors_host", C.c_int, [_P, _P, _DP, _P, _P, _DP, _P, _P, _DP, _P, _P, _P]),
     ("dqmc_gemm_host", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),
     ("dqmc_udv_setup", C.c_int, [_P]),
     ("dqmc_advance", C.c_int, [_P, C.c_int, C.c_int]),

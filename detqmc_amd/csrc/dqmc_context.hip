@@ -1600,6 +1600,86 @@ extern "C" int dqmc_udv_decompose_host(dqmc_ctx* c, const dqmc_cplx* M, dqmc_cpl
     return DQMC_OK;
 }
 
+// Test-facing: the stabilisation routines on caller-given operands, every chain its own (dqmc_hip.h).  They borrow buffers of the sweep
+// (spare, tmpudv, storage[0], T1, T3, sv, G and the time-displaced matrices), so the context's own state is void afterwards:
+static void stab_test_invalidate(dqmc_ctx* c) {
+    c->g_stale = true;
+    c->currentTimeslice = -1;                          // no dqmc_advance accepts this: only dqmc_udv_setup brings the context back
+    c->td_slice = -1;
+}
+// per-chain upload / download of [nb][count] host arrays
+template<class T>
+static int stab_upload(dqmc_ctx* c, T* dev, const void* host, size_t count) {
+    for (int b = 0; b < c->nb; ++b)
+        HIPCHK(hipMemcpyAsync(chainp(c, dev, b), (const T*)host + (size_t)b * count, count * sizeof(T), hipMemcpyHostToDevice, c->st));
+    return DQMC_OK;
+}
+template<class T>
+static int stab_download(dqmc_ctx* c, void* host, const T* dev, size_t count) {
+    if (!host) return DQMC_OK;
+    for (int b = 0; b < c->nb; ++b)
+        HIPCHK(hipMemcpyAsync((T*)host + (size_t)b * count, chainp(c, dev, b), count * sizeof(T), hipMemcpyDeviceToHost, c->st));
+    return DQMC_OK;
+}
+
+extern "C" int dqmc_decompose_host(dqmc_ctx* c, const dqmc_cplx* M, const double* colscale, const double* rowscale, int kind,
+                                   const dqmc_cplx* Aold, dqmc_cplx* U, double* d, dqmc_cplx* V_t, int* sweeps_used) {
+    if (!c || !M || !U || !d || !V_t) return fail(DQMC_EINVAL, "null argument");
+    if (kind != KIND_R && kind != KIND_L) return fail(DQMC_EINVAL, "kind must be 0 (R-type) or 1 (L-type)");
+    (void)hipSetDevice(c->p.device);
+    const size_t n2 = (size_t)c->n_g * c->n_g, ng = (size_t)c->n_g;
+    stab_test_invalidate(c);
+    int rc;
+    // operands where no factorisation writes: M in T1 (as in the sweep), the scales in tmpudv.d and sv, the old factor in T3
+    if ((rc = stab_upload(c, c->T1, M, n2))) return rc;
+    if (colscale && (rc = stab_upload(c, c->tmpudv.d, colscale, ng))) return rc;
+    if (rowscale && (rc = stab_upload(c, c->sv, rowscale, ng))) return rc;
+    if (Aold && (rc = stab_upload(c, c->T3, Aold, n2))) return rc;
+    const double* cs = colscale ? c->tmpudv.d : nullptr;
+    const double* rs = rowscale ? c->sv : nullptr;
+    c->last_svd_sweeps = 0;
+    rc = Aold ? decompose_chained(c, c->T1, cs, rs, kind, c->spare, c->T3) : decompose(c, c->T1, cs, rs, kind, c->spare);
+    if (rc) return rc;
+    if ((rc = stab_download(c, U, c->spare.U, n2))) return rc;
+    if ((rc = stab_download(c, d, c->spare.d, ng))) return rc;
+    if ((rc = stab_download(c, V_t, c->spare.Vt, n2))) return rc;
+    HIPCHK(hipStreamSynchronize(c->st));
+    if (sweeps_used) *sweeps_used = c->last_svd_sweeps;
+    return finish(c, "dqmc_decompose_host");
+}
+
+extern "C" int dqmc_green_from_factors_host(dqmc_ctx* c, const dqmc_cplx* U_l, const double* d_l, const dqmc_cplx* V_l,
+                                            const dqmc_cplx* U_r, const double* d_r, const dqmc_cplx* V_r,
+                                            dqmc_cplx* G, double* sv, dqmc_cplx* GT0, dqmc_cplx* G0T, dqmc_cplx* G00) {
+    if (!c || !G || !sv) return fail(DQMC_EINVAL, "null argument");
+    const bool hasL = U_l && d_l && V_l, hasR = U_r && d_r && V_r;
+    if ((!hasL && (U_l || d_l || V_l)) || (!hasR && (U_r || d_r || V_r))) return fail(DQMC_EINVAL, "a slot is given whole or not at all");
+    if (!hasL && !hasR) return fail(DQMC_EINVAL, "at least one slot is needed");
+    const bool td = hasL && hasR && c->td_on;
+    if ((GT0 || G0T) && !td) return fail(DQMC_EINVAL, "G(tau,0), G(0,tau): both slots and dqmc_set_timedisplaced(on) are needed");
+    if (G00 && !(td && c->G00)) return fail(DQMC_EINVAL, "G(0): both slots, dqmc_set_timedisplaced(on) and dqmc_params::td_particle_hole are needed");
+    (void)hipSetDevice(c->p.device);
+    const size_t n2 = (size_t)c->n_g * c->n_g, ng = (size_t)c->n_g;
+    stab_test_invalidate(c);
+    int rc;
+    // the slots where the sweep keeps them: no routine below writes spare or storage[0]
+    const UdVSlot &L = c->spare, &R = c->storage[0];
+    if (hasL) {
+        if ((rc = stab_upload(c, L.U, U_l, n2)) || (rc = stab_upload(c, L.d, d_l, ng)) || (rc = stab_upload(c, L.Vt, V_l, n2))) return rc;
+    }
+    if (hasR) {
+        if ((rc = stab_upload(c, R.U, U_r, n2)) || (rc = stab_upload(c, R.d, d_r, ng)) || (rc = stab_upload(c, R.Vt, V_r, n2))) return rc;
+    }
+    if (hasL && hasR) rc = green_from_udv(c, L, R);
+    else rc = hasR ? green_from_eye(c, R, KIND_R) : green_from_eye(c, L, KIND_L);
+    if (rc) return rc;
+    if ((rc = stab_download(c, G, c->G, n2)) || (rc = stab_download(c, sv, c->sv, ng))) return rc;
+    if (td && ((rc = stab_download(c, GT0, c->GT0, n2)) || (rc = stab_download(c, G0T, c->G0T, n2)))) return rc;
+    if (td && c->G00 && (rc = stab_download(c, G00, c->G00, n2))) return rc;
+    HIPCHK(hipStreamSynchronize(c->st));
+    return finish(c, "dqmc_green_from_factors_host");
+}
+
 extern "C" int dqmc_gemm_host(dqmc_ctx* c, int opA, int opB, const dqmc_cplx* A, const dqmc_cplx* B, dqmc_cplx* C) {
     if (!c || !A || !B || !C) return fail(DQMC_EINVAL, "null argument");
     (void)hipSetDevice(c->p.device);

@@ -1050,6 +1050,52 @@ class KernelContext:
                                                Vt.ctypes.data, C.byref(sw)))
         return U, d, Vt, sw.value
 
+    # per-chain operands of the two test-facing stabilisation calls: (nchains, n_g, n_g) <-> [chain] column-major, (nchains, n_g) scales
+    def _chain_mats(self, a):
+        if a is None:
+            return None
+        a = np.asarray(a, dtype=np.complex128).reshape(self.nchains_total(), self.ng, self.ng)
+        return np.ascontiguousarray(np.transpose(a, (0, 2, 1)))
+
+    def _chain_vecs(self, a):
+        if a is None:
+            return None
+        return np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(self.nchains_total(), self.ng))
+
+    def _chain_out(self):
+        return np.zeros((self.nchains_total(), self.ng, self.ng), dtype=np.complex128)
+
+    def decompose(self, M, colscale=None, rowscale=None, kind=0, Aold=None):
+        """dqmc_decompose_host: the chain factorisation of diag(rowscale) M diag(colscale) as the sweep calls it, every chain its own
+        operands, shapes (nchains, n_g, n_g) and (nchains, n_g); kind 0 R-type, 1 L-type; with Aold the chained step.  Returns
+        (U, d, V_t, sweeps), M' = U diag(d) V_t^H.  The context's own G is void afterwards (setupUdVStorage_and_calculateGreen rebuilds it)"""
+        m, a = self._chain_mats(M), self._chain_mats(Aold)
+        cs, rs = self._chain_vecs(colscale), self._chain_vecs(rowscale)
+        U, Vt, d = self._chain_out(), self._chain_out(), np.zeros((self.nchains_total(), self.ng))
+        sw = C.c_int(0)
+        dp = lambda v: None if v is None else v.ctypes.data_as(_lib._DP)
+        check(self.lib.dqmc_decompose_host(self.h, m.ctypes.data, dp(cs), dp(rs), int(kind), None if a is None else a.ctypes.data,
+                                           U.ctypes.data, dp(d), Vt.ctypes.data, C.byref(sw)))
+        return np.transpose(U, (0, 2, 1)).copy(), d, np.transpose(Vt, (0, 2, 1)).copy(), sw.value
+
+    def green_from_factors(self, L=None, R=None, td=False, g0=False):
+        """dqmc_green_from_factors_host: greenFromUdV of the L-type slot L = (U_l, d_l, V_l) and the R-type slot R = (U_r, d_r, V_r), per
+        chain; one of them None: greenFromEye_and_UdV of the other.  Returns a dict with 'G', 'sv' and, with td (set_timedisplaced on,
+        both slots), 'GT0', 'G0T', with g0 (tdParticleHole) also 'G00'.  The context's own G is void afterwards"""
+        slots = []
+        for sl in (L, R):
+            slots += [None, None, None] if sl is None else [self._chain_mats(sl[0]), self._chain_vecs(sl[1]), self._chain_mats(sl[2])]
+        out = {"G": self._chain_out(), "sv": np.zeros((self.nchains_total(), self.ng))}
+        if td:
+            out["GT0"], out["G0T"] = self._chain_out(), self._chain_out()
+        if g0:
+            out["G00"] = self._chain_out()
+        mp = lambda v: None if v is None else v.ctypes.data
+        dp = lambda v: None if v is None else v.ctypes.data_as(_lib._DP)
+        check(self.lib.dqmc_green_from_factors_host(self.h, mp(slots[0]), dp(slots[1]), mp(slots[2]), mp(slots[3]), dp(slots[4]), mp(slots[5]),
+                                                    mp(out["G"]), dp(out["sv"]), mp(out.get("GT0")), mp(out.get("G0T")), mp(out.get("G00"))))
+        return {k: (v if k == "sv" else np.transpose(v, (0, 2, 1)).copy()) for k, v in out.items()}
+
     def gemm(self, opA, opB, A, B):
         a, b = _fmat(A), _fmat(B)
         c = np.zeros_like(a)

@@ -208,6 +208,26 @@ int dqmc_bmult_src_host(dqmc_ctx* ctx, int side, int inverse, int k2, int k1, co
 /* udvDecompose (udv.h:68-102): M = U diag(d) V_t^H, d descending */
 int dqmc_udv_decompose_host(dqmc_ctx* ctx, const dqmc_cplx* M, dqmc_cplx* U, double* d, dqmc_cplx* V_t,
                             int* sweeps_used);
+/* Test-facing: the chain factorisation exactly as dqmc_udv_setup / dqmc_advance call it, on caller-given operands, every chain its own.
+ *   M [nchains][n_g^2], colscale / rowscale [nchains][n_g] (each may be NULL): the matrix factorised is M' = diag(rowscale) M diag(colscale)
+ *   kind 0: R-type, M' = U d V_t^H with U unitary (QR mode: V_t = (D^-1 R P^T)^H);  kind 1: L-type, V_t unitary, the adjoint's factorisation
+ *           (SVD mode: both factors are unitary for either kind, d descending)
+ *   Aold [nchains][n_g^2] or NULL: with it the chained step runs (QR mode: the lazy triangular product) and the non-unitary factor
+ *           returned (V_t for kind 0, U for kind 1) is Aold times the new one
+ *   U, V_t [nchains][n_g^2], d [nchains][n_g]; sweeps_used (may be NULL): Jacobi sweeps in SVD mode, 0 in QR mode
+ * dqmc_green_from_factors_host: greenFromUdV on an L-type slot (U_l, d_l, V_l) and an R-type slot (U_r, d_r, V_r), B_L = U_l d_l V_l^H,
+ * B_R = U_r d_r V_r^H, layouts as above; a slot is three pointers or three NULLs.  Both slots: G = (1 + B_R B_L)^-1 and, while
+ * dqmc_set_timedisplaced is on, G(tau,0) = G B_R, G(0,tau) = -B_L G and (dqmc_params::td_particle_hole) G(0) = 1 - B_L G B_R into GT0,
+ * G0T, G00 [nchains][n_g^2] (each may be NULL; non-NULL where the context does not compute it: DQMC_EINVAL).  One slot NULL:
+ * greenFromEye_and_UdV of the other with its kind, G alone.  Only U_r and V_l are taken as unitary.  sv [nchains][n_g]: what
+ * dqmc_get_sv_host reports (QR mode: sum of log sv = log |det(1 + B_R B_L)|).
+ * Both calls work in buffers of the sweep (UdV storage, G, the singular values): afterwards the context's G is stale and no advance is
+ * accepted until the next dqmc_udv_setup.  No sweep calls them. */
+int dqmc_decompose_host(dqmc_ctx* ctx, const dqmc_cplx* M, const double* colscale, const double* rowscale, int kind,
+                        const dqmc_cplx* Aold, dqmc_cplx* U, double* d, dqmc_cplx* V_t, int* sweeps_used);
+int dqmc_green_from_factors_host(dqmc_ctx* ctx, const dqmc_cplx* U_l, const double* d_l, const dqmc_cplx* V_l,
+                                 const dqmc_cplx* U_r, const double* d_r, const dqmc_cplx* V_r,
+                                 dqmc_cplx* G, double* sv, dqmc_cplx* GT0, dqmc_cplx* G0T, dqmc_cplx* G00);
 /* C = op(A) op(B), op = identity (0) or conjugate transpose (1): the zgemm calls behind
  * detmodel.h:784-815 */
 int dqmc_gemm_host(dqmc_ctx* ctx, int opA, int opB, const dqmc_cplx* A, const dqmc_cplx* B, dqmc_cplx* C);
