@@ -10,6 +10,7 @@
 // is done once per sweep on the host (detsdw.cpp).  Every accumulator has exactly one writer and a fixed summation
 // order: results are reproducible bit for bit.
 #include "dqmc_internal.h"
+#include <type_traits>
 
 size_t measure_accum_doubles(int N, int L) {
     const size_t nbins = (size_t)(2 * L - 1) * (2 * L - 1);
@@ -20,6 +21,33 @@ __device__ __forceinline__ cplx m_add(cplx a, cplx b) { return make_double2(a.x 
 __device__ __forceinline__ cplx m_sub(cplx a, cplx b) { return make_double2(a.x - b.x, a.y - b.y); }
 __device__ __forceinline__ cplx m_mul(cplx a, cplx b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 __device__ __forceinline__ cplx m_scale(double s, cplx a) { return make_double2(s * a.x, s * a.y); }
+__device__ __forceinline__ cplx m_conj(cplx a) { return make_double2(a.x, -a.y); }
+__device__ __forceinline__ double m_re_mul(cplx a, cplx b) { return a.x * b.x - a.y * b.y; }       // Re a b
+__device__ __forceinline__ double m_re_mulc(cplx a, cplx b) { return a.x * b.x + a.y * b.y; }      // Re a conj b
+__device__ __forceinline__ double m_abs2(cplx v) { return v.x * v.x + v.y * v.y; }
+// the R x R flavour block e[r][c] = g(P r; Q c) = pe[c N ng + r N] of a matrix g, pe = g + Q ng + P.  Which form to call: a kernel that
+// holds pe or the offset Q ng + P anyway (it reads the same pair from a second matrix, or its OPDIM < 3 branch loads from pe) hands that
+// pointer in, so that all its loads share their address registers (k_measure_td_band<3> needs 26 VGPRs more otherwise); a kernel with no
+// other use of the pointer names the pair
+template<int R>
+__device__ __forceinline__ void m_load_block(const cplx* __restrict__ pe, size_t ng, int N, cplx (&e)[R][R]) {
+#pragma unroll
+    for (int c2 = 0; c2 < R; ++c2)
+#pragma unroll
+        for (int r = 0; r < R; ++r) e[r][c2] = pe[(size_t)c2 * N * ng + (size_t)r * N];
+}
+template<int R>
+__device__ __forceinline__ void m_load_block(const cplx* __restrict__ g, size_t ng, int N, int P, int Q, cplx (&e)[R][R]) {
+    m_load_block(g + (size_t)Q * ng + (size_t)P, ng, N, e);
+}
+
+// f(std::integral_constant<int, OPDIM>) for the model's OPDIM: the one place a run-time opdim picks a kernel instantiation
+template<class F>
+static void dispatch_opdim(int opdim, F&& f) {
+    if (opdim == 1) f(std::integral_constant<int, 1>{});
+    else if (opdim == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 3>{});
+}
 
 // BandSpin: XUP = 0, YDOWN = 1, XDOWN = 2, YUP = 3 (detsdwopdim.h:223-232); gl1 of measure() (:594-612): for OPDIM < 3
 // only the (XUP, YDOWN) sector is stored, the (XDOWN, YUP) sector is its complex conjugate, the rest vanishes
@@ -169,9 +197,9 @@ __global__ __launch_bounds__(256) void k_measure_accum(DevModel dm, const cplx* 
 void launch_measure_accum(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc) {
     const int nbins = (2 * hm.L - 1) * (2 * hm.L - 1);
     const dim3 grid(3 + (2 * nbins * 8 + 255) / 256, 1, lc.nb);
-    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_accum<1>), grid, dim3(256), 0, lc.st, hm, gs, acc, lc.cs);
-    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_accum<2>), grid, dim3(256), 0, lc.st, hm, gs, acc, lc.cs);
-    else hipLaunchKernelGGL((k_measure_accum<3>), grid, dim3(256), 0, lc.st, hm, gs, acc, lc.cs);
+    dispatch_opdim(hm.opdim, [&](auto O) {
+        hipLaunchKernelGGL((k_measure_accum<decltype(O)::value>), grid, dim3(256), 0, lc.st, hm, gs, acc, lc.cs);
+    });
 }
 
 // Time-displaced block (dqmc_measure_timedisplaced): the S_X / S_Y bins of gs = e^{-dtau K/2} G(tau_j, 0) e^{+dtau K/2} into the block of
@@ -200,86 +228,116 @@ __global__ __launch_bounds__(256) void k_measure_td(DevModel dm, const cplx* __r
 void launch_measure_td(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc, int row, int rows) {
     const int nbins = (2 * hm.L - 1) * (2 * hm.L - 1);
     const dim3 grid((2 * nbins * 8 + 255) / 256, 1, lc.nb);
-    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_td<1>), grid, dim3(256), 0, lc.st, hm, gs, acc, row, rows, lc.cs);
-    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_td<2>), grid, dim3(256), 0, lc.st, hm, gs, acc, row, rows, lc.cs);
-    else hipLaunchKernelGGL((k_measure_td<3>), grid, dim3(256), 0, lc.st, hm, gs, acc, row, rows, lc.cs);
+    dispatch_opdim(hm.opdim, [&](auto O) {
+        hipLaunchKernelGGL((k_measure_td<decltype(O)::value>), grid, dim3(256), 0, lc.st, hm, gs, acc, row, rows, lc.cs);
+    });
 }
 
+// The binned kernels below (every k_measure_* with TDP_BINS * TDP_PARTS threads) share one shape.  A workgroup owns 32 consecutive bins
+// d = (dx, dy), the N periodic site differences, bin dy L + dx; thread (part, bin) walks the sites B = part, part + 8, ... in this order
+// and sums its kernel's summand over the pairs (A = B (+) d, B), so the 32 lanes of a half wave read consecutive rows A of one column
+// (runs of L elements between the periodic wraps).  BinWalk is that shape: the decode of threadIdx.x, the walk, and the reduction.
+// The walk is a loop header,   for (BinSite st = bw.first(N, L); st.B < N; bw.next(st, L)) { the kernel's summand at st },
+// so that the summand stays in the kernel's own loop body.
+#define TDP_BINS 32
+#define TDP_PARTS 8
+// one step of the walk: the pair A = (ax, ay) = B (+) d, B = (bx, by); wx / wy: B + d left the lattice in x / y (the antiperiodic sign of
+// k_measure_green_matrix)
+struct BinSite { int A, B, ax, ay, bx, by; bool wx, wy; };
+struct BinWalk {
+    int lb, part, d, dx, dy;
+    bool valid;                                             // d < N: the last workgroup's tile of bins may be ragged
+    __device__ __forceinline__ BinWalk(int N, int L) {
+        lb = threadIdx.x % TDP_BINS; part = threadIdx.x / TDP_BINS;
+        d = blockIdx.x * TDP_BINS + lb;
+        valid = d < N;
+        dx = valid ? d % L : 0; dy = valid ? d / L : 0;
+    }
+    __device__ __forceinline__ void place(BinSite& st, int L) const {       // A = B (+) d
+        st.ax = st.bx + dx; st.ay = st.by + dy;
+        st.wx = st.ax >= L; st.wy = st.ay >= L;
+        if (st.wx) st.ax -= L;
+        if (st.wy) st.ay -= L;
+        st.A = st.ay * L + st.ax;
+    }
+    __device__ __forceinline__ BinSite first(int N, int L) const {          // B = part; a thread without a bin starts at the end
+        BinSite st;
+        st.B = valid ? part : N;
+        st.bx = part % L; st.by = part / L;
+        place(st, L);
+        return st;
+    }
+    __device__ __forceinline__ void next(BinSite& st, int L) const {        // B += 8, kept as (bx, by)
+        st.B += TDP_PARTS;
+        st.bx += TDP_PARTS % L; st.by += TDP_PARTS / L;
+        if (st.bx >= L) { st.bx -= L; ++st.by; }
+        place(st, L);
+    }
+    // The eight partial sums w[c] of every channel c < NCH meet in LDS, and ONE thread per (bin, channel) -- part c for channel c < nch --
+    // adds them in the order part = 0 .. 7 and adds the result to dst[c pstride + d dstride]: one writer per accumulator, fixed order, no
+    // atomics, reproducible bit for bit.  count: the row's sample counter, which thread 0 of workgroup 0 bumps; nullptr where the caller
+    // counts elsewhere.  A caller with more than TDP_PARTS sums calls this once per TDP_PARTS of them, with a barrier in between.
+    template<int NCH>
+    __device__ __forceinline__ void reduce_add(const double* w, double (&red)[NCH][TDP_PARTS][TDP_BINS], int nch, double* dst, size_t pstride,
+                                               size_t dstride, double* count) const {
+#pragma unroll
+        for (int ch = 0; ch < NCH; ++ch) red[ch][part][lb] = w[ch];
+        __syncthreads();
+        if (part < nch && valid) {
+            double s = red[part][0][lb];
+#pragma unroll
+            for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
+            dst[(size_t)part * pstride + (size_t)d * dstride] += s;
+        }
+        if (count && blockIdx.x == 0 && threadIdx.x == 0) *count += 1.0;
+    }
+};
+
 // Time-displaced pairing block (dqmc_measure_timedisplaced_pair): with gs = e^{-dtau K/2} G(tau_j, 0) e^{+dtau K/2} and the P(b1, b2) of
-// role 2 above (:695-715) evaluated on gs for EVERY site pair (A, B),
+// role 2 of k_measure_accum above evaluated on gs for EVERY site pair (A, B),
 //   T+(A, B) = -4 [P(X,X) + P(X,Y) + P(Y,X) + P(Y,Y)],   T-(A, B) = -4 [P(X,X) - P(X,Y) - P(Y,X) + P(Y,Y)],
 // the block of boundary j receives  sum_B Re T+-(B (+) d, B)  for the N periodic site differences d = (dx, dy), bin dy L + dx (the 1 / N of
 // the translation average is left to the reader of the block).  A pair (A, B) needs the 4 x 4 band-spin elements gs(A bs1; B bs2), each
 // exactly once, so one launch streams gs once.  For OPDIM < 3 only the (XUP, YDOWN) sector e_rc = gs(A + N r; B + N c) is stored, the
 // (XDOWN, YUP) sector is its conjugate and the mixed sectors vanish (GreenAccess), which leaves
 //   P(X,X) = -|e_00|^2,  P(X,Y) = |e_01|^2,  P(Y,X) = |e_10|^2,  P(Y,Y) = -|e_11|^2:  four loads per pair instead of sixteen.
-// Shape: a workgroup owns 32 consecutive bins; thread (part, bin) walks the sites B = part, part + 8, ... in this order, so the 32 lanes
-// of a half wave read consecutive rows A of one column (runs of L elements between the periodic wraps).  The eight partial sums of a bin
-// meet in LDS and ONE thread adds them in the order part = 0 .. 7: one writer per accumulator, fixed order, reproducible bit for bit.
 size_t measure_td_pair_doubles(int N, int n) { return (size_t)(n - 1) * (1 + 2 * (size_t)N); }
 
-#define TDP_BINS 32
-#define TDP_PARTS 8
 template<int OPDIM>
 __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_td_pair(DevModel dm, const cplx* __restrict__ gs, double* __restrict__ acc, int row, int rows, size_t cs) {
     CHAIN(gs); CHAIN(acc);
     __shared__ double red[2][TDP_PARTS][TDP_BINS];
-    const int N = dm.N, L = dm.L, tid = threadIdx.x;
+    const int N = dm.N, L = dm.L;
     const size_t ng = (size_t)dm.ng;
-    const int lb = tid % TDP_BINS, part = tid / TDP_BINS;
-    const int d = blockIdx.x * TDP_BINS + lb;
-    const bool valid = d < N;
-    const int dx = valid ? d % L : 0, dy = valid ? d / L : 0;
+    const BinWalk bw(N, L);
     double tp = 0.0, tm = 0.0;
-    if (valid) {
-        int bx = part % L, by = part / L;                   // site B = part + 8 i, kept as (bx, by)
-        const int stepx = TDP_PARTS % L, stepy = TDP_PARTS / L;
-        for (int B = part; B < N; B += TDP_PARTS) {
-            int ax = bx + dx, ay = by + dy;
-            if (ax >= L) ax -= L;
-            if (ay >= L) ay -= L;
-            const cplx* p = gs + (size_t)B * ng + (size_t)(ay * L + ax);
-            auto abs2 = [](cplx v) { return v.x * v.x + v.y * v.y; };
-            if (OPDIM == 3) {
-                // e[bs1][bs2], BandSpin XUP = 0, YDOWN = 1, XDOWN = 2, YUP = 3
-                cplx e[4][4];
-#pragma unroll
-                for (int c2 = 0; c2 < 4; ++c2)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) e[r][c2] = p[(size_t)c2 * N * ng + (size_t)r * N];
-                auto re_mul = [](cplx a, cplx b) { return a.x * b.x - a.y * b.y; };
-                // Re P(b1, b2) with (dn1, up1) = band-spin rows of band b1, (up2, dn2) = band-spin columns of band b2
-                auto P = [&](int dn1, int up1, int up2, int dn2) { return re_mul(e[dn1][up2], e[up1][dn2]) - re_mul(e[dn1][dn2], e[up1][up2]); };
-                const double pxx = P(2, 0, 0, 2), pxy = P(2, 0, 3, 1), pyx = P(1, 3, 0, 2), pyy = P(1, 3, 3, 1);
-                tp += -4.0 * (((pxx + pxy) + pyx) + pyy);
-                tm += -4.0 * (((pxx - pxy) - pyx) + pyy);
-            } else {
-                const cplx e00 = p[0], e10 = p[N], e01 = p[(size_t)N * ng], e11 = p[(size_t)N * ng + N];
-                const double pxx = -abs2(e00), pxy = abs2(e01), pyx = abs2(e10), pyy = -abs2(e11);
-                tp += -4.0 * (((pxx + pxy) + pyx) + pyy);
-                tm += -4.0 * (((pxx - pxy) - pyx) + pyy);
-            }
-            bx += stepx; by += stepy;
-            if (bx >= L) { bx -= L; ++by; }
+    for (BinSite st = bw.first(N, L); st.B < N; bw.next(st, L)) {
+        const cplx* p = gs + (size_t)st.B * ng + (size_t)st.A;
+        if (OPDIM == 3) {
+            // e[bs1][bs2], BandSpin XUP = 0, YDOWN = 1, XDOWN = 2, YUP = 3
+            cplx e[4][4];
+            m_load_block(p, ng, N, e);
+            // Re P(b1, b2) with (dn1, up1) = band-spin rows of band b1, (up2, dn2) = band-spin columns of band b2
+            auto P = [&](int dn1, int up1, int up2, int dn2) { return m_re_mul(e[dn1][up2], e[up1][dn2]) - m_re_mul(e[dn1][dn2], e[up1][up2]); };
+            const double pxx = P(2, 0, 0, 2), pxy = P(2, 0, 3, 1), pyx = P(1, 3, 0, 2), pyy = P(1, 3, 3, 1);
+            tp += -4.0 * (((pxx + pxy) + pyx) + pyy);
+            tm += -4.0 * (((pxx - pxy) - pyx) + pyy);
+        } else {
+            const cplx e00 = p[0], e10 = p[N], e01 = p[(size_t)N * ng], e11 = p[(size_t)N * ng + N];
+            const double pxx = -m_abs2(e00), pxy = m_abs2(e01), pyx = m_abs2(e10), pyy = -m_abs2(e11);
+            tp += -4.0 * (((pxx + pxy) + pyx) + pyy);
+            tm += -4.0 * (((pxx - pxy) - pyx) + pyy);
         }
     }
-    red[0][part][lb] = tp;
-    red[1][part][lb] = tm;
-    __syncthreads();
-    if (part < 2 && valid) {                                // part 0 writes C+ of its bin, part 1 writes C-
-        double s = red[part][0][lb];
-#pragma unroll
-        for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
-        acc[rows + (size_t)row * 2 * N + (size_t)part * N + d] += s;
-    }
-    if (blockIdx.x == 0 && tid == 0) acc[row] += 1.0;
+    const double w[2] = {tp, tm};                           // C+, C-
+    bw.reduce_add(w, red, 2, acc + rows + (size_t)row * 2 * N, N, 1, acc + row);
 }
 
 void launch_measure_td_pair(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc, int row, int rows) {
     const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
-    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_td_pair<1>), grid, block, 0, lc.st, hm, gs, acc, row, rows, lc.cs);
-    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_td_pair<2>), grid, block, 0, lc.st, hm, gs, acc, row, rows, lc.cs);
-    else hipLaunchKernelGGL((k_measure_td_pair<3>), grid, block, 0, lc.st, hm, gs, acc, row, rows, lc.cs);
+    dispatch_opdim(hm.opdim, [&](auto O) {
+        hipLaunchKernelGGL((k_measure_td_pair<decltype(O)::value>), grid, block, 0, lc.st, hm, gs, acc, row, rows, lc.cs);
+    });
 }
 
 // Time-displaced particle-hole block (dqmc_measure_timedisplaced_ph; definitions in dqmc_hip.h and DESIGN.md 6e).  For a site bilinear
@@ -297,7 +355,6 @@ void launch_measure_td_pair(const Launch& lc, const DevModel& hm, const cplx* gs
 // h_rc = hs(A + N r; B + N c), d_rc = Re e_rc conj h_rc and q_ac = Re e_(1-a)c conj h_a(1-c),
 //   charge = 2 sum d_rc,   spinZ = (d_00 + d_11 - d_01 - d_10) / 2,   M_x = 2 (q_00 + q_01 + q_10 + q_11),   M_y = 2 (-q_00 + q_01 + q_10 - q_11):
 // eight loads per pair, nothing multiplied by a structural zero.
-// Shape, reduction and reproducibility: those of k_measure_td_pair above (32 bins x 8 parts, one writer per accumulator, fixed order).
 size_t measure_td_ph_doubles(int N, int n) { return (size_t)(n - 1) * (1 + 3 * (size_t)N); }
 
 #define TDPH_CH 5       // one-body values per site and time: charge, spinZ, M_x, M_y, M_z
@@ -326,6 +383,8 @@ template<int OPDIM>
 __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_td_ph(DevModel dm, const cplx* __restrict__ gs, const cplx* __restrict__ hs,
                                                                         const cplx* __restrict__ ob, double* __restrict__ acc, int row, int rows, size_t cs) {
     CHAIN(gs); CHAIN(hs); CHAIN(ob); CHAIN(acc);
+    // Not under BinWalk: the O(3) instantiation sits at 154 VGPRs, inside three waves per SIMD (168); under BinWalk as it stands it takes 169
+    // and runs two (profiles/measure_walk_resources_parent_vs_this.txt).  The shape of BinWalk written out.
     __shared__ double red[3][TDP_PARTS][TDP_BINS];
     const int N = dm.N, L = dm.L, tid = threadIdx.x;
     const size_t ng = (size_t)dm.ng;
@@ -418,16 +477,16 @@ size_t measure_td_ph_onebody_cplx(int N) { return (size_t)2 * TDPH_CH * N; }
 
 void launch_td_ph_onebody(const Launch& lc, const DevModel& hm, const cplx* gs, cplx* ob, int t) {
     const dim3 grid((hm.N + 255) / 256, 1, lc.nb);
-    if (hm.opdim == 1) hipLaunchKernelGGL((k_td_ph_onebody<1>), grid, dim3(256), 0, lc.st, hm, gs, ob, t, lc.cs);
-    else if (hm.opdim == 2) hipLaunchKernelGGL((k_td_ph_onebody<2>), grid, dim3(256), 0, lc.st, hm, gs, ob, t, lc.cs);
-    else hipLaunchKernelGGL((k_td_ph_onebody<3>), grid, dim3(256), 0, lc.st, hm, gs, ob, t, lc.cs);
+    dispatch_opdim(hm.opdim, [&](auto O) {
+        hipLaunchKernelGGL((k_td_ph_onebody<decltype(O)::value>), grid, dim3(256), 0, lc.st, hm, gs, ob, t, lc.cs);
+    });
 }
 
 void launch_measure_td_ph(const Launch& lc, const DevModel& hm, const cplx* gs, const cplx* hs, const cplx* ob, double* acc, int row, int rows) {
     const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
-    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_td_ph<1>), grid, block, 0, lc.st, hm, gs, hs, ob, acc, row, rows, lc.cs);
-    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_td_ph<2>), grid, block, 0, lc.st, hm, gs, hs, ob, acc, row, rows, lc.cs);
-    else hipLaunchKernelGGL((k_measure_td_ph<3>), grid, block, 0, lc.st, hm, gs, hs, ob, acc, row, rows, lc.cs);
+    dispatch_opdim(hm.opdim, [&](auto O) {
+        hipLaunchKernelGGL((k_measure_td_ph<decltype(O)::value>), grid, block, 0, lc.st, hm, gs, hs, ob, acc, row, rows, lc.cs);
+    });
 }
 
 // Equal-time two-particle block (dqmc_set_equal_time_correlators; definitions in dqmc_hip.h and DESIGN.md 6e).  The Wick forms of
@@ -445,7 +504,7 @@ void launch_measure_td_ph(const Launch& lc, const DevModel& hm, const cplx* gs, 
 // n_g^2 buffer.
 // One-body values: k_eq_onebody writes ob[5][N] (the t = 0 half of k_td_ph_onebody's layout) from the same matrix, 5 N complex numbers.
 // OPDIM < 3: the stored sector and its conjugate as in k_measure_td_ph and k_measure_td_pair -- eight loads per pair serve all five sums;
-// O(3): the sixteen e and sixteen t of the full 4 x 4 blocks.  Shape, walk order, reduction and reproducibility: those of k_measure_td_ph.
+// O(3): the sixteen e and sixteen t of the full 4 x 4 blocks.
 // Block of one chain (doubles): count, charge[N], spinZ[N], sdw[N], pairPlus[N], pairMinus[N]; it lives outside the chain arena, chain b
 // at acc + b (1 + 5 N).
 size_t measure_eq_doubles(int N) { return 1 + 5 * (size_t)N; }
@@ -477,6 +536,8 @@ __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_eq_corr(DevMod
     CHAIN(gs);
     ob += (size_t)blockIdx.z * TDPH_CH * dm.N;
     acc += (size_t)blockIdx.z * (1 + (size_t)EQ_CH * dm.N);
+    // Not under BinWalk: the O(1) instantiation sits at 80 VGPRs, the limit of six waves per SIMD; under BinWalk as it stands it takes 85
+    // and runs five (profiles/measure_walk_resources_parent_vs_this.txt).  The shape of BinWalk written out.
     __shared__ double red[EQ_CH][TDP_PARTS][TDP_BINS];
     const int N = dm.N, L = dm.L, tid = threadIdx.x;
     const size_t ng = (size_t)dm.ng;
@@ -579,16 +640,10 @@ __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_eq_corr(DevMod
 void launch_measure_eq_corr(const Launch& lc, const DevModel& hm, const cplx* gs, cplx* ob, double* acc) {
     const dim3 g1((hm.N + 255) / 256, 1, lc.nb);
     const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
-    if (hm.opdim == 1) {
-        hipLaunchKernelGGL((k_eq_onebody<1>), g1, dim3(256), 0, lc.st, hm, gs, ob, lc.cs);
-        hipLaunchKernelGGL((k_measure_eq_corr<1>), grid, block, 0, lc.st, hm, gs, ob, acc, lc.cs);
-    } else if (hm.opdim == 2) {
-        hipLaunchKernelGGL((k_eq_onebody<2>), g1, dim3(256), 0, lc.st, hm, gs, ob, lc.cs);
-        hipLaunchKernelGGL((k_measure_eq_corr<2>), grid, block, 0, lc.st, hm, gs, ob, acc, lc.cs);
-    } else {
-        hipLaunchKernelGGL((k_eq_onebody<3>), g1, dim3(256), 0, lc.st, hm, gs, ob, lc.cs);
-        hipLaunchKernelGGL((k_measure_eq_corr<3>), grid, block, 0, lc.st, hm, gs, ob, acc, lc.cs);
-    }
+    dispatch_opdim(hm.opdim, [&](auto O) {
+        hipLaunchKernelGGL((k_eq_onebody<decltype(O)::value>), g1, dim3(256), 0, lc.st, hm, gs, ob, lc.cs);
+        hipLaunchKernelGGL((k_measure_eq_corr<decltype(O)::value>), grid, block, 0, lc.st, hm, gs, ob, acc, lc.cs);
+    });
 }
 
 // Time-displaced current-current block (dqmc_measure_timedisplaced_current; definitions in dqmc_hip.h and DESIGN.md 6e).  A bond operator
@@ -604,8 +659,7 @@ void launch_measure_eq_corr(const Launch& lc, const DevModel& hm, const cplx* gs
 // matrices are diag(stored sector, its conjugate): the second sector contributes the complex conjugate of the first, so
 //   Re conn = 2 Re conn_stored,   o[j] = -2 i Re sum_stored (x - y),   o[k] = -2 Re sum_stored (x + y),   x = T g(A; A'), y = conj T g(A'; A),
 // and nothing is multiplied by a structural zero.  O(3) runs over the full 4 x 4 flavour pairs.
-// Shape, walk order over B, reduction and reproducibility: those of k_measure_td_ph (32 bins x 8 parts, partial sums meet in LDS, one writer
-// per accumulator, fixed order, no atomics).  Reuse instead of an LDS tile: the lanes of a half wave hold consecutive A of one column B, so
+// Reuse instead of an LDS tile: the lanes of a half wave hold consecutive A of one column B, so
 // Ax is the neighbouring 16 bytes of the same cache lines and Ay the row L further down the same column, which the lane of bin d + L reads
 // in the same step; column Bx is the column of part + 1 of the same step and By the column this workgroup walks one (L / 8 steps) later:
 // every re-read is served by the CU's L1 or the XCD's L2, and each matrix leaves HBM once per launch.
@@ -615,8 +669,6 @@ size_t measure_td_current_doubles(int N, int n) { return (size_t)(n - 1) * (1 + 
 #define TDC_OB 4        // one-body values per site and time: j_x, j_y, k_x, k_y
 size_t measure_td_current_onebody_cplx(int N) { return (size_t)2 * TDC_OB * N; }
 size_t measure_td_current_bond_cplx(int N, int opdim) { return (size_t)2 * (opdim == 3 ? 4 : 2) * N; }
-
-__device__ __forceinline__ cplx m_conj(cplx a) { return make_double2(a.x, -a.y); }
 
 // ob[t][j_x, j_y, k_x, k_y][site] for one of the two equal-time matrices (t = 0: G(tau_j), t = 1: G(0)); gs is its shifted form
 template<int OPDIM>
@@ -661,72 +713,52 @@ __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_td_current(Dev
     __shared__ double redk[TDP_BINS * TDP_PARTS];
     const int N = dm.N, L = dm.L, tid = threadIdx.x;
     const size_t ng = (size_t)dm.ng;
-    const int lb = tid % TDP_BINS, part = tid / TDP_BINS;
-    const int d = blockIdx.x * TDP_BINS + lb;
-    const bool valid = d < N;
-    const int dx = valid ? d % L : 0, dy = valid ? d / L : 0;
+    const BinWalk bw(N, L);
     const cplx* ot = ob;                                    // o_tau(A)
     const cplx* o0 = ob + (size_t)TDC_OB * N;               // o_0(B)
-    auto re_mul = [](cplx a, cplx b) { return a.x * b.x - a.y * b.y; };   // Re a b
     auto hce = [](cplx h, cplx e) { return make_double2(h.x * e.x + h.y * e.y, h.x * e.y - h.y * e.x); };      // conj(h) e
     double wx = 0.0, wy = 0.0;
-    if (valid) {
-        int bx = part % L, by = part / L;                   // site B = part + 8 i, kept as (bx, by)
-        const int stepx = TDP_PARTS % L, stepy = TDP_PARTS / L;
-        for (int B = part; B < N; B += TDP_PARTS) {
-            int ax = bx + dx, ay = by + dy;
-            if (ax >= L) ax -= L;
-            if (ay >= L) ay -= L;
-            const int A = ay * L + ax;
-            // element offsets of the x and y neighbours: rows of A, columns of B
-            const ptrdiff_t rx = ax + 1 == L ? 1 - L : 1, ry = ay + 1 == L ? (ptrdiff_t)L - N : L;
-            const ptrdiff_t cx = (ptrdiff_t)(bx + 1 == L ? 1 - L : 1) * (ptrdiff_t)ng, cy = (ptrdiff_t)(by + 1 == L ? L - N : L) * (ptrdiff_t)ng;
-            double sx = re_mul(ot[A], o0[B]), sy = re_mul(ot[N + A], o0[N + B]);      // disconnected parts
-            double kx = 0.0, ky = 0.0;                                                // connected parts
+    for (BinSite st = bw.first(N, L); st.B < N; bw.next(st, L)) {
+        const int A = st.A, B = st.B;
+        // element offsets of the x and y neighbours: rows of A, columns of B
+        const ptrdiff_t rx = st.ax + 1 == L ? 1 - L : 1, ry = st.ay + 1 == L ? (ptrdiff_t)L - N : L;
+        const ptrdiff_t cx = (ptrdiff_t)(st.bx + 1 == L ? 1 - L : 1) * (ptrdiff_t)ng, cy = (ptrdiff_t)(st.by + 1 == L ? L - N : L) * (ptrdiff_t)ng;
+        double sx = m_re_mul(ot[A], o0[B]), sy = m_re_mul(ot[N + A], o0[N + B]);      // disconnected parts
+        double kx = 0.0, ky = 0.0;                                                    // connected parts
 #pragma unroll
-            for (int a = 0; a < MSF; ++a) {
-                const cplx tax = bt[(size_t)a * N + A], tay = bt[(size_t)(MSF + a) * N + A];
+        for (int a = 0; a < MSF; ++a) {
+            const cplx tax = bt[(size_t)a * N + A], tay = bt[(size_t)(MSF + a) * N + A];
 #pragma unroll
-                for (int b = 0; b < MSF; ++b) {
-                    const cplx tbx = bt[(size_t)b * N + B], tby = bt[(size_t)(MSF + b) * N + B];
-                    const size_t off = (size_t)(B + N * b) * ng + (size_t)(A + N * a);
-                    const cplx* pe = gs + off;
-                    const cplx* ph = hs + off;
-                    const cplx e00 = pe[0], h00 = ph[0];
-                    {   // mu = x: rows {A, Ax}, columns {B, Bx}
-                        const cplx e10 = pe[rx], e01 = pe[cx], e11 = pe[rx + cx];
-                        const cplx h10 = ph[rx], h01 = ph[cx], h11 = ph[rx + cx];
-                        const cplx c = m_mul(tax, tbx), dd = m_mul(tax, m_conj(tbx));
-                        // P_uv = conj hs(A^u; B^(1-v)) gt0(A^(1-u); B^v)
-                        const cplx p11 = hce(h10, e01), p10 = hce(h11, e00), p01 = hce(h00, e11), p00 = hce(h01, e10);
-                        kx += (re_mul(dd, p10) + re_mul(m_conj(dd), p01)) - (re_mul(c, p11) + re_mul(m_conj(c), p00));
-                    }
-                    {   // mu = y: rows {A, Ay}, columns {B, By}
-                        const cplx e10 = pe[ry], e01 = pe[cy], e11 = pe[ry + cy];
-                        const cplx h10 = ph[ry], h01 = ph[cy], h11 = ph[ry + cy];
-                        const cplx c = m_mul(tay, tby), dd = m_mul(tay, m_conj(tby));
-                        const cplx p11 = hce(h10, e01), p10 = hce(h11, e00), p01 = hce(h00, e11), p00 = hce(h01, e10);
-                        ky += (re_mul(dd, p10) + re_mul(m_conj(dd), p01)) - (re_mul(c, p11) + re_mul(m_conj(c), p00));
-                    }
+            for (int b = 0; b < MSF; ++b) {
+                const cplx tbx = bt[(size_t)b * N + B], tby = bt[(size_t)(MSF + b) * N + B];
+                const size_t off = (size_t)(B + N * b) * ng + (size_t)(A + N * a);
+                const cplx* pe = gs + off;
+                const cplx* ph = hs + off;
+                const cplx e00 = pe[0], h00 = ph[0];
+                {   // mu = x: rows {A, Ax}, columns {B, Bx}
+                    const cplx e10 = pe[rx], e01 = pe[cx], e11 = pe[rx + cx];
+                    const cplx h10 = ph[rx], h01 = ph[cx], h11 = ph[rx + cx];
+                    const cplx c = m_mul(tax, tbx), dd = m_mul(tax, m_conj(tbx));
+                    // P_uv = conj hs(A^u; B^(1-v)) gt0(A^(1-u); B^v)
+                    const cplx p11 = hce(h10, e01), p10 = hce(h11, e00), p01 = hce(h00, e11), p00 = hce(h01, e10);
+                    kx += (m_re_mul(dd, p10) + m_re_mul(m_conj(dd), p01)) - (m_re_mul(c, p11) + m_re_mul(m_conj(c), p00));
+                }
+                {   // mu = y: rows {A, Ay}, columns {B, By}
+                    const cplx e10 = pe[ry], e01 = pe[cy], e11 = pe[ry + cy];
+                    const cplx h10 = ph[ry], h01 = ph[cy], h11 = ph[ry + cy];
+                    const cplx c = m_mul(tay, tby), dd = m_mul(tay, m_conj(tby));
+                    const cplx p11 = hce(h10, e01), p10 = hce(h11, e00), p01 = hce(h00, e11), p00 = hce(h01, e10);
+                    ky += (m_re_mul(dd, p10) + m_re_mul(m_conj(dd), p01)) - (m_re_mul(c, p11) + m_re_mul(m_conj(c), p00));
                 }
             }
-            if (OPDIM < 3) { kx *= 2.0; ky *= 2.0; }
-            wx += sx - kx;
-            wy += sy - ky;
-            bx += stepx; by += stepy;
-            if (bx >= L) { bx -= L; ++by; }
         }
+        if (OPDIM < 3) { kx *= 2.0; ky *= 2.0; }
+        wx += sx - kx;
+        wy += sy - ky;
     }
-    red[0][part][lb] = wx;
-    red[1][part][lb] = wy;
-    __syncthreads();
     double* blk = acc + rows + (size_t)row * (2 * (size_t)N + 2);
-    if (part < 2 && valid) {                                // part 0 writes Lambda_xx of its bin, part 1 Lambda_yy
-        double s = red[part][0][lb];
-#pragma unroll
-        for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
-        blk[(size_t)part * N + d] += s;
-    }
+    const double w[2] = {wx, wy};                           // Lambda_xx, Lambda_yy
+    bw.reduce_add(w, red, 2, blk, N, 1, nullptr);           // the count goes with the site sum below
     if (blockIdx.x == 0) {                                  // sum_A Re o_tau[k_mu(A)]
         double vx = 0.0, vy = 0.0;
         for (int A = tid; A < N; A += TDP_BINS * TDP_PARTS) { vx += ot[2 * N + A].x; vy += ot[3 * N + A].x; }
@@ -742,16 +774,16 @@ __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_td_current(Dev
 
 void launch_td_current_onebody(const Launch& lc, const DevModel& hm, const cplx* gs, const cplx* bt, cplx* ob, int t) {
     const dim3 grid((hm.N + 255) / 256, 1, lc.nb);
-    if (hm.opdim == 1) hipLaunchKernelGGL((k_td_current_onebody<1>), grid, dim3(256), 0, lc.st, hm, gs, bt, ob, t, lc.cs);
-    else if (hm.opdim == 2) hipLaunchKernelGGL((k_td_current_onebody<2>), grid, dim3(256), 0, lc.st, hm, gs, bt, ob, t, lc.cs);
-    else hipLaunchKernelGGL((k_td_current_onebody<3>), grid, dim3(256), 0, lc.st, hm, gs, bt, ob, t, lc.cs);
+    dispatch_opdim(hm.opdim, [&](auto O) {
+        hipLaunchKernelGGL((k_td_current_onebody<decltype(O)::value>), grid, dim3(256), 0, lc.st, hm, gs, bt, ob, t, lc.cs);
+    });
 }
 
 void launch_measure_td_current(const Launch& lc, const DevModel& hm, const cplx* gs, const cplx* hs, const cplx* bt, const cplx* ob, double* acc, int row, int rows) {
     const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
-    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_td_current<1>), grid, block, 0, lc.st, hm, gs, hs, bt, ob, acc, row, rows, lc.cs);
-    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_td_current<2>), grid, block, 0, lc.st, hm, gs, hs, bt, ob, acc, row, rows, lc.cs);
-    else hipLaunchKernelGGL((k_measure_td_current<3>), grid, block, 0, lc.st, hm, gs, hs, bt, ob, acc, row, rows, lc.cs);
+    dispatch_opdim(hm.opdim, [&](auto O) {
+        hipLaunchKernelGGL((k_measure_td_current<decltype(O)::value>), grid, block, 0, lc.st, hm, gs, hs, bt, ob, acc, row, rows, lc.cs);
+    });
 }
 
 // Band-resolved charge channels (dqmc_measure_timedisplaced_band, dqmc_set_equal_time_band; definitions in dqmc_hip.h and DESIGN.md 6e):
@@ -768,7 +800,7 @@ void launch_measure_td_current(const Launch& lc, const DevModel& hm, const cplx*
 //     a in the stored sector:     conj e_(1-a)(1-c) conj h_a c,     a in the conjugate sector:  e_(1-a)(1-c) h_a c      (same real part)
 //     connected = 2 Re (e_10 h_01 + e_11 h_00 + e_00 h_11 + e_01 h_10).
 //   The eight loads of k_measure_td_ph serve both sums; nothing is multiplied by a structural zero.
-// O(3): the sixteen e and sixteen h of the full blocks.  Shape, walk order, reduction and reproducibility: those of k_measure_td_ph.
+// O(3): the sixteen e and sixteen h of the full blocks.
 #define TDB_CH 2        // one-body values per site and time: bandDiff, bandMix
 size_t measure_td_band_doubles(int N, int n) { return (size_t)(n - 1) * (1 + 2 * (size_t)N); }
 size_t measure_td_band_onebody_cplx(int N) { return (size_t)2 * TDB_CH * N; }
@@ -807,91 +839,66 @@ __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_td_band(DevMod
                                                                           const cplx* __restrict__ ob, double* __restrict__ acc, int row, int rows, size_t cs) {
     CHAIN(gs); CHAIN(hs); CHAIN(ob); CHAIN(acc);
     __shared__ double red[TDB_CH][TDP_PARTS][TDP_BINS];
-    const int N = dm.N, L = dm.L, tid = threadIdx.x;
+    const int N = dm.N, L = dm.L;
     const size_t ng = (size_t)dm.ng;
-    const int lb = tid % TDP_BINS, part = tid / TDP_BINS;
-    const int d = blockIdx.x * TDP_BINS + lb;
-    const bool valid = d < N;
-    const int dx = valid ? d % L : 0, dy = valid ? d / L : 0;
+    const BinWalk bw(N, L);
     const cplx* ot = ob;                                    // o_tau(A)
     const cplx* o0 = ob + (size_t)TDB_CH * N;               // o_0(B)
-    auto rd = [](cplx a, cplx b) { return a.x * b.x + a.y * b.y; };       // Re a conj b
-    auto re_mul = [](cplx a, cplx b) { return a.x * b.x - a.y * b.y; };   // Re a b
     double wb = 0.0, wm = 0.0;
-    if (valid) {
-        int bx = part % L, by = part / L;                   // site B = part + 8 i, kept as (bx, by)
-        const int stepx = TDP_PARTS % L, stepy = TDP_PARTS / L;
-        for (int B = part; B < N; B += TDP_PARTS) {
-            int ax = bx + dx, ay = by + dy;
-            if (ax >= L) ax -= L;
-            if (ay >= L) ay -= L;
-            const int A = ay * L + ax;
-            const size_t off = (size_t)B * ng + (size_t)A;
-            const cplx* pe = gs + off;
-            const cplx* ph = hs + off;
-            double db, dmx, cb, cm;
-            if (OPDIM == 3) {
-                db = re_mul(ot[A], o0[B]);
-                dmx = re_mul(ot[N + A], o0[N + B]);
-                cplx e[4][4];
+    for (BinSite st = bw.first(N, L); st.B < N; bw.next(st, L)) {
+        const int A = st.A, B = st.B;
+        const size_t off = (size_t)B * ng + (size_t)A;
+        const cplx* pe = gs + off;
+        const cplx* ph = hs + off;
+        double db, dmx, cb, cm;
+        if (OPDIM == 3) {
+            db = m_re_mul(ot[A], o0[B]);
+            dmx = m_re_mul(ot[N + A], o0[N + B]);
+            cplx e[4][4];
+            m_load_block(pe, ng, N, e);
+            constexpr int pz[4] = {3, 2, 1, 0};
+            constexpr double sb[4] = {1.0, -1.0, 1.0, -1.0};
+            cb = 0.0; cm = 0.0;
 #pragma unroll
-                for (int c2 = 0; c2 < 4; ++c2)
+            for (int a = 0; a < 4; ++a) {
+                cplx h[4];                                        // h[dl] = hs(A a; B dl)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) e[r][c2] = pe[(size_t)c2 * N * ng + (size_t)r * N];
-                constexpr int pz[4] = {3, 2, 1, 0};
-                constexpr double sb[4] = {1.0, -1.0, 1.0, -1.0};
-                cb = 0.0; cm = 0.0;
+                for (int dl = 0; dl < 4; ++dl) h[dl] = ph[(size_t)dl * N * ng + (size_t)a * N];
 #pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    cplx h[4];                                        // h[dl] = hs(A a; B dl)
-#pragma unroll
-                    for (int dl = 0; dl < 4; ++dl) h[dl] = ph[(size_t)dl * N * ng + (size_t)a * N];
-#pragma unroll
-                    for (int c2 = 0; c2 < 4; ++c2) {
-                        cb += sb[a] * sb[c2] * rd(e[a][c2], h[c2]);
-                        cm += rd(e[pz[a]][c2], h[pz[c2]]);
-                    }
+                for (int c2 = 0; c2 < 4; ++c2) {
+                    cb += sb[a] * sb[c2] * m_re_mulc(e[a][c2], h[c2]);
+                    cm += m_re_mulc(e[pz[a]][c2], h[pz[c2]]);
                 }
-            } else {
-                db = ot[A].x * o0[B].x;                              // both real; the bandMix values are exact zeros
-                dmx = 0.0;
-                const size_t cN = (size_t)N * ng;
-                const cplx e00 = pe[0], e10 = pe[N], e01 = pe[cN], e11 = pe[cN + N];
-                const cplx h00 = ph[0], h10 = ph[N], h01 = ph[cN], h11 = ph[cN + N];
-                const double d00 = rd(e00, h00), d11 = rd(e11, h11), d01 = rd(e01, h01), d10 = rd(e10, h10);
-                cb = 2.0 * ((d00 + d11) - (d01 + d10));
-                cm = 2.0 * ((re_mul(e10, h01) + re_mul(e01, h10)) + (re_mul(e11, h00) + re_mul(e00, h11)));
             }
-            wb += db - cb;
-            wm += dmx - cm;
-            bx += stepx; by += stepy;
-            if (bx >= L) { bx -= L; ++by; }
+        } else {
+            db = ot[A].x * o0[B].x;                              // both real; the bandMix values are exact zeros
+            dmx = 0.0;
+            const size_t cN = (size_t)N * ng;
+            const cplx e00 = pe[0], e10 = pe[N], e01 = pe[cN], e11 = pe[cN + N];
+            const cplx h00 = ph[0], h10 = ph[N], h01 = ph[cN], h11 = ph[cN + N];
+            const double d00 = m_re_mulc(e00, h00), d11 = m_re_mulc(e11, h11), d01 = m_re_mulc(e01, h01), d10 = m_re_mulc(e10, h10);
+            cb = 2.0 * ((d00 + d11) - (d01 + d10));
+            cm = 2.0 * ((m_re_mul(e10, h01) + m_re_mul(e01, h10)) + (m_re_mul(e11, h00) + m_re_mul(e00, h11)));
         }
+        wb += db - cb;
+        wm += dmx - cm;
     }
-    red[0][part][lb] = wb;
-    red[1][part][lb] = wm;
-    __syncthreads();
-    if (part < TDB_CH && valid) {                           // part 0 writes bandDiff of its bin, part 1 bandMix
-        double s = red[part][0][lb];
-#pragma unroll
-        for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
-        acc[rows + (size_t)row * TDB_CH * N + (size_t)part * N + d] += s;
-    }
-    if (blockIdx.x == 0 && tid == 0) acc[row] += 1.0;
+    const double w[TDB_CH] = {wb, wm};                      // bandDiff, bandMix
+    bw.reduce_add(w, red, TDB_CH, acc + rows + (size_t)row * TDB_CH * N, N, 1, acc + row);
 }
 
 void launch_td_band_onebody(const Launch& lc, const DevModel& hm, const cplx* gs, cplx* ob, int t) {
     const dim3 grid((hm.N + 255) / 256, 1, lc.nb);
-    if (hm.opdim == 1) hipLaunchKernelGGL((k_td_band_onebody<1>), grid, dim3(256), 0, lc.st, hm, gs, ob, t, lc.cs);
-    else if (hm.opdim == 2) hipLaunchKernelGGL((k_td_band_onebody<2>), grid, dim3(256), 0, lc.st, hm, gs, ob, t, lc.cs);
-    else hipLaunchKernelGGL((k_td_band_onebody<3>), grid, dim3(256), 0, lc.st, hm, gs, ob, t, lc.cs);
+    dispatch_opdim(hm.opdim, [&](auto O) {
+        hipLaunchKernelGGL((k_td_band_onebody<decltype(O)::value>), grid, dim3(256), 0, lc.st, hm, gs, ob, t, lc.cs);
+    });
 }
 
 void launch_measure_td_band(const Launch& lc, const DevModel& hm, const cplx* gs, const cplx* hs, const cplx* ob, double* acc, int row, int rows) {
     const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
-    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_td_band<1>), grid, block, 0, lc.st, hm, gs, hs, ob, acc, row, rows, lc.cs);
-    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_td_band<2>), grid, block, 0, lc.st, hm, gs, hs, ob, acc, row, rows, lc.cs);
-    else hipLaunchKernelGGL((k_measure_td_band<3>), grid, block, 0, lc.st, hm, gs, hs, ob, acc, row, rows, lc.cs);
+    dispatch_opdim(hm.opdim, [&](auto O) {
+        hipLaunchKernelGGL((k_measure_td_band<decltype(O)::value>), grid, block, 0, lc.st, hm, gs, hs, ob, acc, row, rows, lc.cs);
+    });
 }
 
 // Equal-time form (dqmc_set_equal_time_band): one matrix gs in both roles as in k_measure_eq_corr, the transposed factor read in place,
@@ -928,93 +935,62 @@ __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_eq_band(DevMod
     ob += (size_t)blockIdx.z * EQB_OB * dm.N;
     acc += (size_t)blockIdx.z * (1 + (size_t)TDB_CH * dm.N);
     __shared__ double red[TDB_CH][TDP_PARTS][TDP_BINS];
-    const int N = dm.N, L = dm.L, tid = threadIdx.x;
+    const int N = dm.N, L = dm.L;
     const size_t ng = (size_t)dm.ng;
-    const int lb = tid % TDP_BINS, part = tid / TDP_BINS;
-    const int d = blockIdx.x * TDP_BINS + lb;
-    const bool valid = d < N;
-    const int dx = valid ? d % L : 0, dy = valid ? d / L : 0;
-    auto rd = [](cplx a, cplx b) { return a.x * b.x + a.y * b.y; };       // Re a conj b
-    auto re_mul = [](cplx a, cplx b) { return a.x * b.x - a.y * b.y; };   // Re a b
+    const BinWalk bw(N, L);
     double wb = 0.0, wm = 0.0;
-    if (valid) {
-        int bx = part % L, by = part / L;                   // site B = part + 8 i, kept as (bx, by)
-        const int stepx = TDP_PARTS % L, stepy = TDP_PARTS / L;
-        for (int B = part; B < N; B += TDP_PARTS) {
-            int ax = bx + dx, ay = by + dy;
-            if (ax >= L) ax -= L;
-            if (ay >= L) ay -= L;
-            const int A = ay * L + ax;
-            const cplx* pe = gs + (size_t)B * ng + (size_t)A;     // e_rc = gs(A + N r; B + N c) = pe[c N ng + r N]
-            const cplx* pt = gs + (size_t)A * ng + (size_t)B;     // t_rc = gs(B + N c; A + N r) = pt[r N ng + c N]
-            double db, dmx, cb, cm;
-            if (OPDIM == 3) {
-                db = re_mul(ob[A], ob[B]);
-                dmx = re_mul(ob[N + A], ob[N + B]);
-                cplx e[4][4];
+    for (BinSite st = bw.first(N, L); st.B < N; bw.next(st, L)) {
+        const int A = st.A, B = st.B;
+        const cplx* pe = gs + (size_t)B * ng + (size_t)A;     // e_rc = gs(A + N r; B + N c) = pe[c N ng + r N]
+        const cplx* pt = gs + (size_t)A * ng + (size_t)B;     // t_rc = gs(B + N c; A + N r) = pt[r N ng + c N]
+        double db, dmx, cb, cm;
+        if (OPDIM == 3) {
+            db = m_re_mul(ob[A], ob[B]);
+            dmx = m_re_mul(ob[N + A], ob[N + B]);
+            cplx e[4][4];
+            m_load_block(pe, ng, N, e);
+            constexpr int pz[4] = {3, 2, 1, 0};
+            constexpr double sb[4] = {1.0, -1.0, 1.0, -1.0};
+            cb = 0.0; cm = 0.0;
 #pragma unroll
-                for (int c2 = 0; c2 < 4; ++c2)
+            for (int a = 0; a < 4; ++a) {
+                cplx t[4];                                        // t[dl] = gs(B dl; A a)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) e[r][c2] = pe[(size_t)c2 * N * ng + (size_t)r * N];
-                constexpr int pz[4] = {3, 2, 1, 0};
-                constexpr double sb[4] = {1.0, -1.0, 1.0, -1.0};
-                cb = 0.0; cm = 0.0;
+                for (int dl = 0; dl < 4; ++dl) t[dl] = pt[(size_t)a * N * ng + (size_t)dl * N];
 #pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    cplx t[4];                                        // t[dl] = gs(B dl; A a)
-#pragma unroll
-                    for (int dl = 0; dl < 4; ++dl) t[dl] = pt[(size_t)a * N * ng + (size_t)dl * N];
-#pragma unroll
-                    for (int c2 = 0; c2 < 4; ++c2) {
-                        cb += sb[a] * sb[c2] * re_mul(e[a][c2], t[c2]);
-                        cm += re_mul(e[pz[a]][c2], t[pz[c2]]);
-                    }
+                for (int c2 = 0; c2 < 4; ++c2) {
+                    cb += sb[a] * sb[c2] * m_re_mul(e[a][c2], t[c2]);
+                    cm += m_re_mul(e[pz[a]][c2], t[pz[c2]]);
                 }
-            } else {
-                db = ob[A].x * ob[B].x;                              // both real; the bandMix values are exact zeros
-                dmx = 0.0;
-                const size_t cN = (size_t)N * ng;
-                const cplx e00 = pe[0], e10 = pe[N], e01 = pe[cN], e11 = pe[cN + N];
-                const cplx t00 = pt[0], t10 = pt[cN], t01 = pt[N], t11 = pt[cN + N];
-                const double d00 = re_mul(e00, t00), d11 = re_mul(e11, t11), d01 = re_mul(e01, t01), d10 = re_mul(e10, t10);
-                cb = 2.0 * ((d00 + d11) - (d01 + d10));
-                cm = 2.0 * ((rd(e10, t01) + rd(e01, t10)) + (rd(e11, t00) + rd(e00, t11)));
             }
-            if (d == 0) {                                   // the delta term: tr_4 gs(B; B) for M^2 = 1
-                const double tr = ob[2 * N + B].x;
-                db += tr; dmx += tr;
-            }
-            wb += db - cb;
-            wm += dmx - cm;
-            bx += stepx; by += stepy;
-            if (bx >= L) { bx -= L; ++by; }
+        } else {
+            db = ob[A].x * ob[B].x;                              // both real; the bandMix values are exact zeros
+            dmx = 0.0;
+            const size_t cN = (size_t)N * ng;
+            const cplx e00 = pe[0], e10 = pe[N], e01 = pe[cN], e11 = pe[cN + N];
+            const cplx t00 = pt[0], t10 = pt[cN], t01 = pt[N], t11 = pt[cN + N];
+            const double d00 = m_re_mul(e00, t00), d11 = m_re_mul(e11, t11), d01 = m_re_mul(e01, t01), d10 = m_re_mul(e10, t10);
+            cb = 2.0 * ((d00 + d11) - (d01 + d10));
+            cm = 2.0 * ((m_re_mulc(e10, t01) + m_re_mulc(e01, t10)) + (m_re_mulc(e11, t00) + m_re_mulc(e00, t11)));
         }
+        if (bw.d == 0) {                                // the delta term: tr_4 gs(B; B) for M^2 = 1
+            const double tr = ob[2 * N + B].x;
+            db += tr; dmx += tr;
+        }
+        wb += db - cb;
+        wm += dmx - cm;
     }
-    red[0][part][lb] = wb;
-    red[1][part][lb] = wm;
-    __syncthreads();
-    if (part < TDB_CH && valid) {                           // part 0 writes bandDiff of its bin, part 1 bandMix
-        double s = red[part][0][lb];
-#pragma unroll
-        for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
-        acc[1 + (size_t)part * N + d] += s;
-    }
-    if (blockIdx.x == 0 && tid == 0) acc[0] += 1.0;
+    const double w[TDB_CH] = {wb, wm};                      // bandDiff, bandMix
+    bw.reduce_add(w, red, TDB_CH, acc + 1, N, 1, acc);
 }
 
 void launch_measure_eq_band(const Launch& lc, const DevModel& hm, const cplx* gs, cplx* ob, double* acc) {
     const dim3 g1((hm.N + 255) / 256, 1, lc.nb);
     const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
-    if (hm.opdim == 1) {
-        hipLaunchKernelGGL((k_eq_band_onebody<1>), g1, dim3(256), 0, lc.st, hm, gs, ob, lc.cs);
-        hipLaunchKernelGGL((k_measure_eq_band<1>), grid, block, 0, lc.st, hm, gs, ob, acc, lc.cs);
-    } else if (hm.opdim == 2) {
-        hipLaunchKernelGGL((k_eq_band_onebody<2>), g1, dim3(256), 0, lc.st, hm, gs, ob, lc.cs);
-        hipLaunchKernelGGL((k_measure_eq_band<2>), grid, block, 0, lc.st, hm, gs, ob, acc, lc.cs);
-    } else {
-        hipLaunchKernelGGL((k_eq_band_onebody<3>), g1, dim3(256), 0, lc.st, hm, gs, ob, lc.cs);
-        hipLaunchKernelGGL((k_measure_eq_band<3>), grid, block, 0, lc.st, hm, gs, ob, acc, lc.cs);
-    }
+    dispatch_opdim(hm.opdim, [&](auto O) {
+        hipLaunchKernelGGL((k_eq_band_onebody<decltype(O)::value>), g1, dim3(256), 0, lc.st, hm, gs, ob, lc.cs);
+        hipLaunchKernelGGL((k_measure_eq_band<decltype(O)::value>), grid, block, 0, lc.st, hm, gs, ob, acc, lc.cs);
+    });
 }
 
 // User-defined bilinears (dqmc_set_custom_bilinears; definitions in dqmc_hip.h and DESIGN.md 6e): the W^M(A, B) of k_measure_td_ph for up to
@@ -1024,8 +1000,7 @@ void launch_measure_eq_band(const Launch& lc, const DevModel& hm, const cplx* gs
 // from row a of M E and column a of M T.  OPDIM < 3: only the (XUP, YDOWN) sector is stored, the (XDOWN, YUP) sector is its complex
 // conjugate and the blocks between the sectors vanish (GreenAccess), which cst_E / cst_same resolve at compile time after unrolling -- a
 // matrix that couples the sectors is as legal as any other.  A 16-bit mask per channel (bit 4 a + b: M_ab != 0) skips the structural
-// zeros; it is uniform over the launch, so no wave diverges.  Grid shape, walk order over B, LDS reduction, one writer per accumulator and
-// fixed summation order: those of k_measure_td_band.  The blocks and the one-body scratch live outside the arena: chain b at
+// zeros; it is uniform over the launch, so no wave diverges.  The blocks and the one-body scratch live outside the arena: chain b at
 // acc + b * acs and ob + b * obs.
 struct CustomMats { cplx m[DQMC_CUSTOM_MAX][4][4]; unsigned mask[DQMC_CUSTOM_MAX]; int count; };
 size_t measure_custom_row_doubles(int count, int N) { return (size_t)count * N; }
@@ -1074,12 +1049,8 @@ __device__ __forceinline__ double cst_connected(const cplx (&e)[R][R], const cpl
 template<int OPDIM>
 __device__ __forceinline__ cplx cst_onebody(const cplx* __restrict__ gs, int ng, int N, int A, const cplx (&M)[4][4], unsigned mask, bool with_trace) {
     constexpr int R = OPDIM == 3 ? 4 : 2;
-    const cplx* p = gs + (size_t)A * ng + A;                // g(r, c) = gs(A r; A c) = p[c N ng + r N]
-    cplx g[R][R];
-#pragma unroll
-    for (int c2 = 0; c2 < R; ++c2)
-#pragma unroll
-        for (int r = 0; r < R; ++r) g[r][c2] = p[(size_t)c2 * N * ng + (size_t)r * N];
+    cplx g[R][R];                                           // g(r, c) = gs(A r; A c)
+    m_load_block(gs, (size_t)ng, N, A, A, g);
     cplx v = make_double2(0.0, 0.0);
     if (with_trace) v = m_add(m_add(M[0][0], M[1][1]), m_add(M[2][2], M[3][3]));
     cplx s = make_double2(0.0, 0.0);
@@ -1113,55 +1084,33 @@ __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_td_custom(DevM
     ob += (size_t)blockIdx.z * obs;
     acc += (size_t)blockIdx.z * acs;
     __shared__ double red[DQMC_CUSTOM_MAX][TDP_PARTS][TDP_BINS];
-    const int N = dm.N, L = dm.L, tid = threadIdx.x, count = cm.count;
+    const int N = dm.N, L = dm.L, count = cm.count;
     const size_t ng = (size_t)dm.ng;
-    const int lb = tid % TDP_BINS, part = tid / TDP_BINS;
-    const int d = blockIdx.x * TDP_BINS + lb;
-    const bool valid = d < N;
-    const int dx = valid ? d % L : 0, dy = valid ? d / L : 0;
+    const BinWalk bw(N, L);
     const cplx* ot = ob;                                    // o_tau(A)
     const cplx* o0 = ob + (size_t)count * N;                // o_0(B)
     double w[DQMC_CUSTOM_MAX] = {0.0, 0.0, 0.0, 0.0};
-    if (valid) {
-        int bx = part % L, by = part / L;                   // site B = part + 8 i, kept as (bx, by)
-        const int stepx = TDP_PARTS % L, stepy = TDP_PARTS / L;
-        for (int B = part; B < N; B += TDP_PARTS) {
-            int ax = bx + dx, ay = by + dy;
-            if (ax >= L) ax -= L;
-            if (ay >= L) ay -= L;
-            const int A = ay * L + ax;
-            const size_t off = (size_t)B * ng + (size_t)A;
-            const cplx* pe = gs + off;
-            const cplx* ph = hs + off;
-            cplx e[R][R], t[R][R];
+    for (BinSite st = bw.first(N, L); st.B < N; bw.next(st, L)) {
+        const int A = st.A, B = st.B;
+        const size_t off = (size_t)B * ng + (size_t)A;
+        const cplx* ph = hs + off;
+        cplx e[R][R], t[R][R];
+        m_load_block(gs + off, ng, N, e);
 #pragma unroll
-            for (int c2 = 0; c2 < R; ++c2)
+        for (int c2 = 0; c2 < R; ++c2)
 #pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    e[r][c2] = pe[(size_t)c2 * N * ng + (size_t)r * N];
-                    const cplx h = ph[(size_t)c2 * N * ng + (size_t)r * N];      // hs(A r; B c2) = conj T_(c2 r)
-                    t[c2][r] = make_double2(h.x, -h.y);
-                }
+            for (int r = 0; r < R; ++r) {
+                const cplx h = ph[(size_t)c2 * N * ng + (size_t)r * N];      // hs(A r; B c2) = conj T_(c2 r)
+                t[c2][r] = make_double2(h.x, -h.y);
+            }
 #pragma unroll
-            for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
-                if (ch < count) {
-                    const cplx a = ot[(size_t)ch * N + A], b = o0[(size_t)ch * N + B];
-                    w[ch] += (a.x * b.x - a.y * b.y) - cst_connected<OPDIM, R>(e, t, cm.m[ch], cm.mask[ch]);
-                }
-            bx += stepx; by += stepy;
-            if (bx >= L) { bx -= L; ++by; }
-        }
+        for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
+            if (ch < count) {
+                const cplx a = ot[(size_t)ch * N + A], b = o0[(size_t)ch * N + B];
+                w[ch] += (a.x * b.x - a.y * b.y) - cst_connected<OPDIM, R>(e, t, cm.m[ch], cm.mask[ch]);
+            }
     }
-#pragma unroll
-    for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) red[ch][part][lb] = w[ch];
-    __syncthreads();
-    if (part < count && valid) {                            // part ch writes channel ch of its bin
-        double s = red[part][0][lb];
-#pragma unroll
-        for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
-        acc[rows + (size_t)row * count * N + (size_t)part * N + d] += s;
-    }
-    if (blockIdx.x == 0 && tid == 0) acc[row] += 1.0;
+    bw.reduce_add(w, red, count, acc + rows + (size_t)row * count * N, N, 1, acc + row);
 }
 
 // the stencil kernels of the bond parts, further down
@@ -1186,9 +1135,9 @@ void launch_td_custom_onebody(const Launch& lc, const DevModel& hm, int count, c
     const CustomMats cm = custom_mats(count, M, mask);
     const dim3 grid((hm.N + 255) / 256, 1, lc.nb);
     const size_t obs = measure_td_custom_onebody_cplx(count, hm.N);
-    if (hm.opdim == 1) hipLaunchKernelGGL((k_td_custom_onebody<1>), grid, dim3(256), 0, lc.st, hm, cm, gs, ob, t, obs, lc.cs);
-    else if (hm.opdim == 2) hipLaunchKernelGGL((k_td_custom_onebody<2>), grid, dim3(256), 0, lc.st, hm, cm, gs, ob, t, obs, lc.cs);
-    else hipLaunchKernelGGL((k_td_custom_onebody<3>), grid, dim3(256), 0, lc.st, hm, cm, gs, ob, t, obs, lc.cs);
+    dispatch_opdim(hm.opdim, [&](auto O) {
+        hipLaunchKernelGGL((k_td_custom_onebody<decltype(O)::value>), grid, dim3(256), 0, lc.st, hm, cm, gs, ob, t, obs, lc.cs);
+    });
 }
 
 void launch_measure_td_custom(const Launch& lc, const DevModel& hm, int count, const cplx* M, const unsigned* mask, const cplx* gs, const cplx* hs,
@@ -1197,9 +1146,9 @@ void launch_measure_td_custom(const Launch& lc, const DevModel& hm, int count, c
     const CustomMats cm = custom_mats(count, M, mask);
     const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
     const size_t obs = measure_td_custom_onebody_cplx(count, hm.N);
-    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_td_custom<1>), grid, block, 0, lc.st, hm, cm, gs, hs, ob, acc, row, rows, obs, acs, lc.cs);
-    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_td_custom<2>), grid, block, 0, lc.st, hm, cm, gs, hs, ob, acc, row, rows, obs, acs, lc.cs);
-    else hipLaunchKernelGGL((k_measure_td_custom<3>), grid, block, 0, lc.st, hm, cm, gs, hs, ob, acc, row, rows, obs, acs, lc.cs);
+    dispatch_opdim(hm.opdim, [&](auto O) {
+        hipLaunchKernelGGL((k_measure_td_custom<decltype(O)::value>), grid, block, 0, lc.st, hm, cm, gs, hs, ob, acc, row, rows, obs, acs, lc.cs);
+    });
 }
 
 // Equal-time form (dqmc_set_equal_time_custom): one matrix gs in both roles as in k_measure_eq_band, the transposed factor read in place,
@@ -1231,53 +1180,25 @@ __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_eq_custom(DevM
     ob += (size_t)blockIdx.z * obs;
     acc += (size_t)blockIdx.z * acs;
     __shared__ double red[DQMC_CUSTOM_MAX][TDP_PARTS][TDP_BINS];
-    const int N = dm.N, L = dm.L, tid = threadIdx.x, count = cm.count;
+    const int N = dm.N, L = dm.L, count = cm.count;
     const size_t ng = (size_t)dm.ng;
-    const int lb = tid % TDP_BINS, part = tid / TDP_BINS;
-    const int d = blockIdx.x * TDP_BINS + lb;
-    const bool valid = d < N;
-    const int dx = valid ? d % L : 0, dy = valid ? d / L : 0;
+    const BinWalk bw(N, L);
     double w[DQMC_CUSTOM_MAX] = {0.0, 0.0, 0.0, 0.0};
-    if (valid) {
-        int bx = part % L, by = part / L;                   // site B = part + 8 i, kept as (bx, by)
-        const int stepx = TDP_PARTS % L, stepy = TDP_PARTS / L;
-        for (int B = part; B < N; B += TDP_PARTS) {
-            int ax = bx + dx, ay = by + dy;
-            if (ax >= L) ax -= L;
-            if (ay >= L) ay -= L;
-            const int A = ay * L + ax;
-            const cplx* pe = gs + (size_t)B * ng + (size_t)A;     // E_rc = gs(A r; B c) = pe[c N ng + r N]
-            const cplx* pt = gs + (size_t)A * ng + (size_t)B;     // T_rc = gs(B r; A c) = pt[c N ng + r N]
-            cplx e[R][R], t[R][R];
+    for (BinSite st = bw.first(N, L); st.B < N; bw.next(st, L)) {
+        const int A = st.A, B = st.B;
+        cplx e[R][R], t[R][R];
+        m_load_block(gs, ng, N, A, B, e);                   // E_rc = gs(A r; B c)
+        m_load_block(gs, ng, N, B, A, t);                   // T_rc = gs(B r; A c)
 #pragma unroll
-            for (int c2 = 0; c2 < R; ++c2)
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    e[r][c2] = pe[(size_t)c2 * N * ng + (size_t)r * N];
-                    t[r][c2] = pt[(size_t)c2 * N * ng + (size_t)r * N];
-                }
-#pragma unroll
-            for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
-                if (ch < count) {
-                    const cplx a = ob[(size_t)ch * N + A], b = ob[(size_t)ch * N + B];
-                    double v = (a.x * b.x - a.y * b.y) - cst_connected<OPDIM, R>(e, t, cm.m[ch], cm.mask[ch]);
-                    if (d == 0) v += ob[(size_t)(count + ch) * N + B].x;      // the delta term
-                    w[ch] += v;
-                }
-            bx += stepx; by += stepy;
-            if (bx >= L) { bx -= L; ++by; }
-        }
+        for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
+            if (ch < count) {
+                const cplx a = ob[(size_t)ch * N + A], b = ob[(size_t)ch * N + B];
+                double v = (a.x * b.x - a.y * b.y) - cst_connected<OPDIM, R>(e, t, cm.m[ch], cm.mask[ch]);
+                if (bw.d == 0) v += ob[(size_t)(count + ch) * N + B].x;      // the delta term
+                w[ch] += v;
+            }
     }
-#pragma unroll
-    for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) red[ch][part][lb] = w[ch];
-    __syncthreads();
-    if (part < count && valid) {                            // part ch writes channel ch of its bin
-        double s = red[part][0][lb];
-#pragma unroll
-        for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
-        acc[1 + (size_t)part * N + d] += s;
-    }
-    if (blockIdx.x == 0 && tid == 0) acc[0] += 1.0;
+    bw.reduce_add(w, red, count, acc + 1, N, 1, acc);
 }
 
 void launch_measure_eq_custom(const Launch& lc, const DevModel& hm, int count, const cplx* M, const unsigned* mask, const cplx* M2, const unsigned* mask2,
@@ -1287,16 +1208,10 @@ void launch_measure_eq_custom(const Launch& lc, const DevModel& hm, int count, c
     const dim3 g1((hm.N + 255) / 256, 1, lc.nb);
     const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
     const size_t obs = measure_eq_custom_onebody_cplx(count, hm.N), acs = 1 + measure_custom_row_doubles(count, hm.N);
-    if (hm.opdim == 1) {
-        hipLaunchKernelGGL((k_eq_custom_onebody<1>), g1, dim3(256), 0, lc.st, hm, cm, cm2, gs, ob, obs, lc.cs);
-        hipLaunchKernelGGL((k_measure_eq_custom<1>), grid, block, 0, lc.st, hm, cm, gs, ob, acc, obs, acs, lc.cs);
-    } else if (hm.opdim == 2) {
-        hipLaunchKernelGGL((k_eq_custom_onebody<2>), g1, dim3(256), 0, lc.st, hm, cm, cm2, gs, ob, obs, lc.cs);
-        hipLaunchKernelGGL((k_measure_eq_custom<2>), grid, block, 0, lc.st, hm, cm, gs, ob, acc, obs, acs, lc.cs);
-    } else {
-        hipLaunchKernelGGL((k_eq_custom_onebody<3>), g1, dim3(256), 0, lc.st, hm, cm, cm2, gs, ob, obs, lc.cs);
-        hipLaunchKernelGGL((k_measure_eq_custom<3>), grid, block, 0, lc.st, hm, cm, gs, ob, acc, obs, acs, lc.cs);
-    }
+    dispatch_opdim(hm.opdim, [&](auto O) {
+        hipLaunchKernelGGL((k_eq_custom_onebody<decltype(O)::value>), g1, dim3(256), 0, lc.st, hm, cm, cm2, gs, ob, obs, lc.cs);
+        hipLaunchKernelGGL((k_measure_eq_custom<decltype(O)::value>), grid, block, 0, lc.st, hm, cm, gs, ob, acc, obs, acs, lc.cs);
+    });
 }
 
 // Bond parts of the user-defined bilinears (dqmc_set_custom_bond_bilinears; definitions in dqmc_hip.h and DESIGN.md 6e).  As a one-body
@@ -1320,7 +1235,6 @@ void launch_measure_eq_custom(const Launch& lc, const DevModel& hm, int count, c
 // needs are skipped before their loads and an on-site-only operator takes part in pair (0, 0) alone.
 // Equal-time form: gt0 -> gs, g0t -> gs - 1, the 1 subtracted from the diagonal of T wherever B^s and A^p are the same site (d = 0,
 // +-x, +-y, +-(x - y)) -- the delta term in full, no M^2 shortcut.
-// Shape, walk order over B, LDS reduction, one writer per accumulator, fixed order, no atomics: those of k_measure_td_custom.
 #define CSTB_K 5
 size_t measure_custom_bond_table_cplx(int count, int N) { return (size_t)count * CSTB_K * 16 + 2 * (size_t)N; }
 struct CustomBondArg { const cplx* tab; const unsigned* mk; unsigned parts[DQMC_CUSTOM_MAX]; int count; };
@@ -1429,12 +1343,11 @@ __global__ __launch_bounds__(256) void k_eq_custom_bond_onebody(DevModel dm, Cus
 // the sums over B of Re W(B (+) d, B) of one thread's (bin, part); EQ: hs is not read, ot == o0
 template<int OPDIM, bool EQ>
 __device__ __forceinline__ void cstb_walk(const DevModel& dm, const CustomBondArg& cb, const cplx* __restrict__ gs, const cplx* __restrict__ hs,
-                                          const cplx* __restrict__ ot, const cplx* __restrict__ o0, int part, int d, double (&w)[DQMC_CUSTOM_MAX]) {
+                                          const cplx* __restrict__ ot, const cplx* __restrict__ o0, const BinWalk& bw, double (&w)[DQMC_CUSTOM_MAX]) {
     constexpr int R = OPDIM == 3 ? 4 : 2;
     const int N = dm.N, L = dm.L, count = cb.count;
     const size_t ng = (size_t)dm.ng, cN = (size_t)N * ng;
     const cplx* __restrict__ lk = cb.tab + (size_t)count * CSTB_K * 16;
-    const int dx = d % L, dy = d / L;
     unsigned both[DQMC_CUSTOM_MAX];                         // bit 5 ka + kb: operator ch has the blocks ka and kb
     unsigned need = 0;
 #pragma unroll
@@ -1445,16 +1358,11 @@ __device__ __forceinline__ void cstb_walk(const DevModel& dm, const CustomBondAr
                 if ((cb.parts[ch] >> ka) & 1u) both[ch] |= (cb.parts[ch] & 0x1fu) << (CSTB_K * ka);
         need |= both[ch];
     }
-    int bx = part % L, by = part / L;                       // site B = part + 8 i, kept as (bx, by)
-    const int stepx = TDP_PARTS % L, stepy = TDP_PARTS / L;
-    for (int B = part; B < N; B += TDP_PARTS) {
-        int ax = bx + dx, ay = by + dy;
-        if (ax >= L) ax -= L;
-        if (ay >= L) ay -= L;
-        const int A = ay * L + ax;
+    for (BinSite st = bw.first(N, L); st.B < N; bw.next(st, L)) {
+        const int A = st.A, B = st.B;
         int Ax, Ay, Bx, By;
-        cstb_stencil(L, ax, ay, Ax, Ay);
-        cstb_stencil(L, bx, by, Bx, By);
+        cstb_stencil(L, st.ax, st.ay, Ax, Ay);
+        cstb_stencil(L, st.bx, st.by, Bx, By);
         const cplx uax = lk[A], uay = lk[N + A], ubx = lk[B], uby = lk[N + B];
 #pragma unroll
         for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
@@ -1504,8 +1412,6 @@ __device__ __forceinline__ void cstb_walk(const DevModel& dm, const CustomBondAr
                     w[ch] -= cstb_connected<OPDIM, R>(e, t, V + 16 * ka, cb.mk[ch * CSTB_K + ka], V + 16 * kb, cb.mk[ch * CSTB_K + kb]);
                 }
         }
-        bx += stepx; by += stepy;
-        if (bx >= L) { bx -= L; ++by; }
     }
 }
 
@@ -1518,22 +1424,11 @@ __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_td_custom_bond
     ob += (size_t)blockIdx.z * obs;
     acc += (size_t)blockIdx.z * acs;
     __shared__ double red[DQMC_CUSTOM_MAX][TDP_PARTS][TDP_BINS];
-    const int N = dm.N, tid = threadIdx.x, count = cb.count;
-    const int lb = tid % TDP_BINS, part = tid / TDP_BINS;
-    const int d = blockIdx.x * TDP_BINS + lb;
-    const bool valid = d < N;
+    const int N = dm.N, count = cb.count;
+    const BinWalk bw(N, dm.L);
     double w[DQMC_CUSTOM_MAX] = {0.0, 0.0, 0.0, 0.0};
-    if (valid) cstb_walk<OPDIM, false>(dm, cb, gs, hs, ob, ob + (size_t)count * N, part, d, w);
-#pragma unroll
-    for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) red[ch][part][lb] = w[ch];
-    __syncthreads();
-    if (part < count && valid) {                            // part ch writes channel ch of its bin
-        double s = red[part][0][lb];
-#pragma unroll
-        for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
-        acc[rows + (size_t)row * count * N + (size_t)part * N + d] += s;
-    }
-    if (blockIdx.x == 0 && tid == 0) acc[row] += 1.0;
+    cstb_walk<OPDIM, false>(dm, cb, gs, hs, ob, ob + (size_t)count * N, bw, w);
+    bw.reduce_add(w, red, count, acc + rows + (size_t)row * count * N, N, 1, acc + row);
 }
 
 template<int OPDIM>
@@ -1544,22 +1439,11 @@ __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_eq_custom_bond
     ob += (size_t)blockIdx.z * obs;
     acc += (size_t)blockIdx.z * acs;
     __shared__ double red[DQMC_CUSTOM_MAX][TDP_PARTS][TDP_BINS];
-    const int N = dm.N, tid = threadIdx.x, count = cb.count;
-    const int lb = tid % TDP_BINS, part = tid / TDP_BINS;
-    const int d = blockIdx.x * TDP_BINS + lb;
-    const bool valid = d < N;
+    const int N = dm.N, count = cb.count;
+    const BinWalk bw(N, dm.L);
     double w[DQMC_CUSTOM_MAX] = {0.0, 0.0, 0.0, 0.0};
-    if (valid) cstb_walk<OPDIM, true>(dm, cb, gs, gs, ob, ob, part, d, w);
-#pragma unroll
-    for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) red[ch][part][lb] = w[ch];
-    __syncthreads();
-    if (part < count && valid) {                            // part ch writes channel ch of its bin
-        double s = red[part][0][lb];
-#pragma unroll
-        for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
-        acc[1 + (size_t)part * N + d] += s;
-    }
-    if (blockIdx.x == 0 && tid == 0) acc[0] += 1.0;
+    cstb_walk<OPDIM, true>(dm, cb, gs, gs, ob, ob, bw, w);
+    bw.reduce_add(w, red, count, acc + 1, N, 1, acc);
 }
 
 static CustomBondArg custom_bond_arg(int count, const CustomBond& bond) {
@@ -1573,9 +1457,9 @@ static void launch_td_custom_bond_onebody(const Launch& lc, const DevModel& hm, 
     const CustomBondArg cb = custom_bond_arg(count, bond);
     const dim3 grid((hm.N + 255) / 256, 1, lc.nb);
     const size_t obs = measure_td_custom_onebody_cplx(count, hm.N);
-    if (hm.opdim == 1) hipLaunchKernelGGL((k_td_custom_bond_onebody<1>), grid, dim3(256), 0, lc.st, hm, cb, gs, ob, t, obs, lc.cs);
-    else if (hm.opdim == 2) hipLaunchKernelGGL((k_td_custom_bond_onebody<2>), grid, dim3(256), 0, lc.st, hm, cb, gs, ob, t, obs, lc.cs);
-    else hipLaunchKernelGGL((k_td_custom_bond_onebody<3>), grid, dim3(256), 0, lc.st, hm, cb, gs, ob, t, obs, lc.cs);
+    dispatch_opdim(hm.opdim, [&](auto O) {
+        hipLaunchKernelGGL((k_td_custom_bond_onebody<decltype(O)::value>), grid, dim3(256), 0, lc.st, hm, cb, gs, ob, t, obs, lc.cs);
+    });
 }
 
 static void launch_measure_td_custom_bond(const Launch& lc, const DevModel& hm, int count, const CustomBond& bond, const cplx* gs, const cplx* hs,
@@ -1583,9 +1467,9 @@ static void launch_measure_td_custom_bond(const Launch& lc, const DevModel& hm, 
     const CustomBondArg cb = custom_bond_arg(count, bond);
     const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
     const size_t obs = measure_td_custom_onebody_cplx(count, hm.N);
-    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_td_custom_bond<1>), grid, block, 0, lc.st, hm, cb, gs, hs, ob, acc, row, rows, obs, acs, lc.cs);
-    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_td_custom_bond<2>), grid, block, 0, lc.st, hm, cb, gs, hs, ob, acc, row, rows, obs, acs, lc.cs);
-    else hipLaunchKernelGGL((k_measure_td_custom_bond<3>), grid, block, 0, lc.st, hm, cb, gs, hs, ob, acc, row, rows, obs, acs, lc.cs);
+    dispatch_opdim(hm.opdim, [&](auto O) {
+        hipLaunchKernelGGL((k_measure_td_custom_bond<decltype(O)::value>), grid, block, 0, lc.st, hm, cb, gs, hs, ob, acc, row, rows, obs, acs, lc.cs);
+    });
 }
 
 static void launch_measure_eq_custom_bond(const Launch& lc, const DevModel& hm, int count, const CustomBond& bond, const cplx* gs, cplx* ob, double* acc) {
@@ -1593,16 +1477,10 @@ static void launch_measure_eq_custom_bond(const Launch& lc, const DevModel& hm, 
     const dim3 g1((hm.N + 255) / 256, 1, lc.nb);
     const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
     const size_t obs = measure_eq_custom_onebody_cplx(count, hm.N), acs = 1 + measure_custom_row_doubles(count, hm.N);
-    if (hm.opdim == 1) {
-        hipLaunchKernelGGL((k_eq_custom_bond_onebody<1>), g1, dim3(256), 0, lc.st, hm, cb, gs, ob, obs, lc.cs);
-        hipLaunchKernelGGL((k_measure_eq_custom_bond<1>), grid, block, 0, lc.st, hm, cb, gs, ob, acc, obs, acs, lc.cs);
-    } else if (hm.opdim == 2) {
-        hipLaunchKernelGGL((k_eq_custom_bond_onebody<2>), g1, dim3(256), 0, lc.st, hm, cb, gs, ob, obs, lc.cs);
-        hipLaunchKernelGGL((k_measure_eq_custom_bond<2>), grid, block, 0, lc.st, hm, cb, gs, ob, acc, obs, acs, lc.cs);
-    } else {
-        hipLaunchKernelGGL((k_eq_custom_bond_onebody<3>), g1, dim3(256), 0, lc.st, hm, cb, gs, ob, obs, lc.cs);
-        hipLaunchKernelGGL((k_measure_eq_custom_bond<3>), grid, block, 0, lc.st, hm, cb, gs, ob, acc, obs, acs, lc.cs);
-    }
+    dispatch_opdim(hm.opdim, [&](auto O) {
+        hipLaunchKernelGGL((k_eq_custom_bond_onebody<decltype(O)::value>), g1, dim3(256), 0, lc.st, hm, cb, gs, ob, obs, lc.cs);
+        hipLaunchKernelGGL((k_measure_eq_custom_bond<decltype(O)::value>), grid, block, 0, lc.st, hm, cb, gs, ob, acc, obs, acs, lc.cs);
+    });
 }
 
 // User-defined pair operators (dqmc_set_custom_pair_operators; definitions in dqmc_hip.h and DESIGN.md 6e):
@@ -1617,8 +1495,7 @@ static void launch_measure_eq_custom_bond(const Launch& lc, const DevModel& hm, 
 // On-site form (no operator has a bond part): all four blocks are the one E = g~(A .; B .), loaded once per site pair, and
 //   P = tr(F^T E (conj F - F^H) E^T) = 1/2 sum_ab Fa_ab [E conj(Fa) E^T]_ab,   Fa = F0 - F0^T
 // (E conj(Fa) E^T is antisymmetric, so only the antisymmetric part of F0 contributes), every channel contracted from registers; Fa and
-// its non-zero mask travel as a kernel argument, the mask branches are uniform over the launch.  Shape, walk order over B, LDS
-// reduction, one writer per accumulator, fixed summation order, no atomics: those of k_measure_td_custom.  The block is count[rows],
+// its non-zero mask travel as a kernel argument, the mask branches are uniform over the launch.  The block is count[rows],
 // then the rows [count][N]; the equal-time block is the same with rows = 1.  Blocks live outside the arena: chain b at acc + b * acs.
 template<int OPDIM, int R>
 __device__ __forceinline__ double cpr_onsite(const cplx (&e)[R][R], const cplx (&F)[4][4], unsigned mask) {
@@ -1656,44 +1533,18 @@ __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_custom_pair(De
     constexpr int R = OPDIM == 3 ? 4 : 2;
     acc += (size_t)blockIdx.z * acs;
     __shared__ double red[DQMC_CUSTOM_MAX][TDP_PARTS][TDP_BINS];
-    const int N = dm.N, L = dm.L, tid = threadIdx.x, count = cm.count;
+    const int N = dm.N, L = dm.L, count = cm.count;
     const size_t ng = (size_t)dm.ng;
-    const int lb = tid % TDP_BINS, part = tid / TDP_BINS;
-    const int d = blockIdx.x * TDP_BINS + lb;
-    const bool valid = d < N;
-    const int dx = valid ? d % L : 0, dy = valid ? d / L : 0;
+    const BinWalk bw(N, L);
     double w[DQMC_CUSTOM_MAX] = {0.0, 0.0, 0.0, 0.0};
-    if (valid) {
-        int bx = part % L, by = part / L;                   // site B = part + 8 i, kept as (bx, by)
-        const int stepx = TDP_PARTS % L, stepy = TDP_PARTS / L;
-        for (int B = part; B < N; B += TDP_PARTS) {
-            int ax = bx + dx, ay = by + dy;
-            if (ax >= L) ax -= L;
-            if (ay >= L) ay -= L;
-            const int A = ay * L + ax;
-            const cplx* pe = gs + (size_t)B * ng + (size_t)A;     // E_rc = gs(A r; B c) = pe[c N ng + r N]
-            cplx e[R][R];
+    for (BinSite st = bw.first(N, L); st.B < N; bw.next(st, L)) {
+        cplx e[R][R];
+        m_load_block(gs, ng, N, st.A, st.B, e);             // E_rc = gs(A r; B c)
 #pragma unroll
-            for (int c2 = 0; c2 < R; ++c2)
-#pragma unroll
-                for (int r = 0; r < R; ++r) e[r][c2] = pe[(size_t)c2 * N * ng + (size_t)r * N];
-#pragma unroll
-            for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
-                if (ch < count) w[ch] += cpr_onsite<OPDIM, R>(e, cm.m[ch], cm.mask[ch]);
-            bx += stepx; by += stepy;
-            if (bx >= L) { bx -= L; ++by; }
-        }
+        for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
+            if (ch < count) w[ch] += cpr_onsite<OPDIM, R>(e, cm.m[ch], cm.mask[ch]);
     }
-#pragma unroll
-    for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) red[ch][part][lb] = w[ch];
-    __syncthreads();
-    if (part < count && valid) {                            // part ch writes channel ch of its bin
-        double s = red[part][0][lb];
-#pragma unroll
-        for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
-        acc[rows + (size_t)row * count * N + (size_t)part * N + d] += s;
-    }
-    if (blockIdx.x == 0 && tid == 0) acc[row] += 1.0;
+    bw.reduce_add(w, red, count, acc + rows + (size_t)row * count * N, N, 1, acc + row);
 }
 
 // Stencil form (at least one operator has a bond part).  Device table tab (measure_custom_pair_table_cplx complex, shared by the chains):
@@ -1737,15 +1588,6 @@ __device__ __forceinline__ double cpr_term(const cplx (&x)[R][R], const cplx (&y
     }
     return s;
 }
-// e[r][c] = gs(P r; Q c)
-template<int R>
-__device__ __forceinline__ void cpr_load(const cplx* __restrict__ gs, size_t ng, int N, int P, int Q, cplx (&e)[R][R]) {
-    const cplx* pe = gs + (size_t)Q * ng + (size_t)P;
-#pragma unroll
-    for (int c2 = 0; c2 < R; ++c2)
-#pragma unroll
-        for (int r = 0; r < R; ++r) e[r][c2] = pe[(size_t)c2 * N * ng + (size_t)r * N];
-}
 
 template<int OPDIM>
 __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_custom_pair_bond(DevModel dm, CustomPairArg cp, const cplx* __restrict__ gs,
@@ -1754,12 +1596,9 @@ __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_custom_pair_bo
     constexpr int R = OPDIM == 3 ? 4 : 2;
     acc += (size_t)blockIdx.z * acs;
     __shared__ double red[DQMC_CUSTOM_MAX][TDP_PARTS][TDP_BINS];
-    const int N = dm.N, L = dm.L, tid = threadIdx.x, count = cp.count;
+    const int N = dm.N, L = dm.L, count = cp.count;
     const size_t ng = (size_t)dm.ng;
-    const int lb = tid % TDP_BINS, part = tid / TDP_BINS;
-    const int d = blockIdx.x * TDP_BINS + lb;
-    const bool valid = d < N;
-    const int dx = valid ? d % L : 0, dy = valid ? d / L : 0;
+    const BinWalk bw(N, L);
     const cplx* __restrict__ lk = cp.tab + (size_t)count * CPR_K * 3 * 16;
     unsigned both[DQMC_CUSTOM_MAX];                         // bit 3 ka + kb: operator ch has the blocks ka and kb
     unsigned need = 0;
@@ -1772,58 +1611,40 @@ __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_custom_pair_bo
         need |= both[ch];
     }
     double w[DQMC_CUSTOM_MAX] = {0.0, 0.0, 0.0, 0.0};
-    if (valid) {
-        int bx = part % L, by = part / L;                   // site B = part + 8 i, kept as (bx, by)
-        const int stepx = TDP_PARTS % L, stepy = TDP_PARTS / L;
-        for (int B = part; B < N; B += TDP_PARTS) {
-            int ax = bx + dx, ay = by + dy;
-            if (ax >= L) ax -= L;
-            if (ay >= L) ay -= L;
-            const int A = ay * L + ax;
-            int Ax, Ay, Bx, By;
-            cstb_stencil(L, ax, ay, Ax, Ay);
-            cstb_stencil(L, bx, by, Bx, By);
-            const double uax = lk[A].x, uay = lk[N + A].x, ubx = lk[B].x, uby = lk[N + B].x;
+    for (BinSite st = bw.first(N, L); st.B < N; bw.next(st, L)) {
+        const int A = st.A, B = st.B;
+        int Ax, Ay, Bx, By;
+        cstb_stencil(L, st.ax, st.ay, Ax, Ay);
+        cstb_stencil(L, st.bx, st.by, Bx, By);
+        const double uax = lk[A].x, uay = lk[N + A].x, ubx = lk[B].x, uby = lk[N + B].x;
 #pragma unroll 1
-            for (int pr = 0; pr < CPR_K * CPR_K; ++pr) {
-                if (!((need >> pr) & 1u)) continue;
-                const int ka = pr / CPR_K, kb = pr % CPR_K;
-                const int p = ka == 1 ? Ax : ka == 2 ? Ay : A, r = kb == 1 ? Bx : kb == 2 ? By : B;
-                const double f = (ka == 1 ? uax : ka == 2 ? uay : 1.0) * (kb == 1 ? ubx : kb == 2 ? uby : 1.0);
-                cplx x[R][R], y[R][R];
-                cpr_load<R>(gs, ng, N, p, r, x);            // direct: E(A^k; B^k'), E(A; B)
-                cpr_load<R>(gs, ng, N, A, B, y);
+        for (int pr = 0; pr < CPR_K * CPR_K; ++pr) {
+            if (!((need >> pr) & 1u)) continue;
+            const int ka = pr / CPR_K, kb = pr % CPR_K;
+            const int p = ka == 1 ? Ax : ka == 2 ? Ay : A, r = kb == 1 ? Bx : kb == 2 ? By : B;
+            const double f = (ka == 1 ? uax : ka == 2 ? uay : 1.0) * (kb == 1 ? ubx : kb == 2 ? uby : 1.0);
+            cplx x[R][R], y[R][R];
+            m_load_block(gs, ng, N, p, r, x);               // direct: E(A^k; B^k'), E(A; B)
+            m_load_block(gs, ng, N, A, B, y);
 #pragma unroll
-                for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
-                    if ((both[ch] >> pr) & 1u) {
-                        const cplx* __restrict__ V = cp.tab + (size_t)ch * CPR_K * 3 * 16;
-                        const unsigned* __restrict__ mk = cp.mk + ch * CPR_K * 2;
-                        w[ch] += f * cpr_term<OPDIM, R>(x, y, V + 48 * ka, mk[2 * ka], V + 48 * kb + 16, mk[2 * kb]);
-                    }
-                cpr_load<R>(gs, ng, N, p, B, x);            // exchange: E(A^k; B), E(A; B^k')
-                cpr_load<R>(gs, ng, N, A, r, y);
+            for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
+                if ((both[ch] >> pr) & 1u) {
+                    const cplx* __restrict__ V = cp.tab + (size_t)ch * CPR_K * 3 * 16;
+                    const unsigned* __restrict__ mk = cp.mk + ch * CPR_K * 2;
+                    w[ch] += f * cpr_term<OPDIM, R>(x, y, V + 48 * ka, mk[2 * ka], V + 48 * kb + 16, mk[2 * kb]);
+                }
+            m_load_block(gs, ng, N, p, B, x);               // exchange: E(A^k; B), E(A; B^k')
+            m_load_block(gs, ng, N, A, r, y);
 #pragma unroll
-                for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
-                    if ((both[ch] >> pr) & 1u) {
-                        const cplx* __restrict__ V = cp.tab + (size_t)ch * CPR_K * 3 * 16;
-                        const unsigned* __restrict__ mk = cp.mk + ch * CPR_K * 2;
-                        w[ch] -= f * cpr_term<OPDIM, R>(x, y, V + 48 * ka, mk[2 * ka], V + 48 * kb + 32, mk[2 * kb + 1]);
-                    }
-            }
-            bx += stepx; by += stepy;
-            if (bx >= L) { bx -= L; ++by; }
+            for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch)
+                if ((both[ch] >> pr) & 1u) {
+                    const cplx* __restrict__ V = cp.tab + (size_t)ch * CPR_K * 3 * 16;
+                    const unsigned* __restrict__ mk = cp.mk + ch * CPR_K * 2;
+                    w[ch] -= f * cpr_term<OPDIM, R>(x, y, V + 48 * ka, mk[2 * ka], V + 48 * kb + 32, mk[2 * kb + 1]);
+                }
         }
     }
-#pragma unroll
-    for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) red[ch][part][lb] = w[ch];
-    __syncthreads();
-    if (part < count && valid) {                            // part ch writes channel ch of its bin
-        double s = red[part][0][lb];
-#pragma unroll
-        for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
-        acc[rows + (size_t)row * count * N + (size_t)part * N + d] += s;
-    }
-    if (blockIdx.x == 0 && tid == 0) acc[row] += 1.0;
+    bw.reduce_add(w, red, count, acc + rows + (size_t)row * count * N, N, 1, acc + row);
 }
 
 void launch_measure_custom_pair(const Launch& lc, const DevModel& hm, int count, const cplx* Fa, const unsigned* mask, const cplx* gs, double* acc,
@@ -1833,24 +1654,23 @@ void launch_measure_custom_pair(const Launch& lc, const DevModel& hm, int count,
         CustomPairArg cp{};
         cp.tab = bond->tab; cp.mk = bond->mk; cp.count = count;
         for (int ch = 0; ch < count; ++ch) cp.parts[ch] = bond->parts[ch];
-        if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_custom_pair_bond<1>), grid, block, 0, lc.st, hm, cp, gs, acc, row, rows, acs, lc.cs);
-        else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_custom_pair_bond<2>), grid, block, 0, lc.st, hm, cp, gs, acc, row, rows, acs, lc.cs);
-        else hipLaunchKernelGGL((k_measure_custom_pair_bond<3>), grid, block, 0, lc.st, hm, cp, gs, acc, row, rows, acs, lc.cs);
+        dispatch_opdim(hm.opdim, [&](auto O) {
+            hipLaunchKernelGGL((k_measure_custom_pair_bond<decltype(O)::value>), grid, block, 0, lc.st, hm, cp, gs, acc, row, rows, acs, lc.cs);
+        });
         return;
     }
     const CustomMats cm = custom_mats(count, Fa, mask);
-    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_custom_pair<1>), grid, block, 0, lc.st, hm, cm, gs, acc, row, rows, acs, lc.cs);
-    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_custom_pair<2>), grid, block, 0, lc.st, hm, cm, gs, acc, row, rows, acs, lc.cs);
-    else hipLaunchKernelGGL((k_measure_custom_pair<3>), grid, block, 0, lc.st, hm, cm, gs, acc, row, rows, acs, lc.cs);
+    dispatch_opdim(hm.opdim, [&](auto O) {
+        hipLaunchKernelGGL((k_measure_custom_pair<decltype(O)::value>), grid, block, 0, lc.st, hm, cm, gs, acc, row, rows, acs, lc.cs);
+    });
 }
 
 // The averaged Green's function block (dqmc_set_green_matrix; dqmc_hip.h and DESIGN.md 6e): from the shifted gs = g~(tau,0) the pair
 // kernels read,
 //   Gbar_rc(d) += sum_B sigma(B, d) gs((B (+) d) r; B c),   sigma = -1 for each antiperiodic direction in which B + d wraps,
-// r, c over the stored flavour block (R = 2: the (XUP, YDOWN) sector, R = 4 for O(3)).  Shape, walk order over B and the coalesced reads
-// along A of k_measure_custom_pair; a thread keeps the 2 R^2 sums of its bin in registers, and the LDS reduction over the parts runs in
-// passes of TDP_PARTS components: part q writes component pass TDP_PARTS + q of its bin -- one writer per accumulator, fixed summation
-// order, no atomics.  Block: count[rows], then the rows [N][R][R] (re, im); outside the arena: chain b at acc + b * acs.
+// r, c over the stored flavour block (R = 2: the (XUP, YDOWN) sector, R = 4 for O(3)).  A thread keeps the 2 R^2 sums of its bin in
+// registers, and the reduction over the parts runs in passes of TDP_PARTS components: part q writes component pass TDP_PARTS + q of its
+// bin.  Block: count[rows], then the rows [N][R][R] (re, im); outside the arena: chain b at acc + b * acs.
 size_t measure_green_matrix_row_doubles(int opdim, int N) { return (size_t)(opdim == 3 ? 32 : 8) * N; }
 template<int OPDIM>
 __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_green_matrix(DevModel dm, const cplx* __restrict__ gs, double* __restrict__ acc,
@@ -1860,56 +1680,35 @@ __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_measure_green_matrix(D
     static_assert(NC % TDP_PARTS == 0, "the reduction runs in passes of TDP_PARTS components");
     acc += (size_t)blockIdx.z * acs;
     __shared__ double red[TDP_PARTS][TDP_PARTS][TDP_BINS];  // [component of the pass][part][bin]
-    const int N = dm.N, L = dm.L, tid = threadIdx.x;
+    const int N = dm.N, L = dm.L;
     const size_t ng = (size_t)dm.ng;
-    const int lb = tid % TDP_BINS, part = tid / TDP_BINS;
-    const int d = blockIdx.x * TDP_BINS + lb;
-    const bool valid = d < N;
-    const int dx = valid ? d % L : 0, dy = valid ? d / L : 0;
+    const BinWalk bw(N, L);
     double w[NC];
 #pragma unroll
     for (int q = 0; q < NC; ++q) w[q] = 0.0;
-    if (valid) {
-        int bx = part % L, by = part / L;                   // site B = part + 8 i, kept as (bx, by)
-        const int stepx = TDP_PARTS % L, stepy = TDP_PARTS / L;
-        for (int B = part; B < N; B += TDP_PARTS) {
-            int ax = bx + dx, ay = by + dy;
-            const bool wx = ax >= L, wy = ay >= L;
-            if (wx) ax -= L;
-            if (wy) ay -= L;
-            const double sg = ((wx && apbx) != (wy && apby)) ? -1.0 : 1.0;
-            const cplx* pe = gs + (size_t)B * ng + (size_t)(ay * L + ax);     // gs(A r; B c) = pe[c N ng + r N]
+    for (BinSite st = bw.first(N, L); st.B < N; bw.next(st, L)) {
+        const double sg = ((st.wx && apbx) != (st.wy && apby)) ? -1.0 : 1.0;
+        const cplx* pe = gs + (size_t)st.B * ng + (size_t)st.A;           // gs(A r; B c) = pe[c N ng + r N]
 #pragma unroll
-            for (int c2 = 0; c2 < R; ++c2)
+        for (int c2 = 0; c2 < R; ++c2)
 #pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const cplx v = pe[(size_t)c2 * N * ng + (size_t)r * N];
-                    w[2 * (r * R + c2)] += sg * v.x; w[2 * (r * R + c2) + 1] += sg * v.y;
-                }
-            bx += stepx; by += stepy;
-            if (bx >= L) { bx -= L; ++by; }
-        }
+            for (int r = 0; r < R; ++r) {
+                const cplx v = pe[(size_t)c2 * N * ng + (size_t)r * N];
+                w[2 * (r * R + c2)] += sg * v.x; w[2 * (r * R + c2) + 1] += sg * v.y;
+            }
     }
 #pragma unroll
     for (int pass = 0; pass < NC / TDP_PARTS; ++pass) {
-        if (pass) __syncthreads();
-#pragma unroll
-        for (int q = 0; q < TDP_PARTS; ++q) red[q][part][lb] = w[pass * TDP_PARTS + q];
-        __syncthreads();
-        if (valid) {                                        // part q writes component pass TDP_PARTS + q of its bin
-            double s = red[part][0][lb];
-#pragma unroll
-            for (int q = 1; q < TDP_PARTS; ++q) s += red[part][q][lb];
-            acc[rows + ((size_t)row * N + d) * NC + pass * TDP_PARTS + part] += s;
-        }
+        if (pass) __syncthreads();                          // red is free again
+        bw.reduce_add(w + pass * TDP_PARTS, red, TDP_PARTS, acc + rows + (size_t)row * N * NC + pass * TDP_PARTS, 1, NC,
+                      pass + 1 == NC / TDP_PARTS ? acc + row : nullptr);
     }
-    if (blockIdx.x == 0 && tid == 0) acc[row] += 1.0;
 }
 void launch_measure_green_matrix(const Launch& lc, const DevModel& hm, const cplx* gs, double* acc, size_t acs, int row, int rows, int apbx, int apby) {
     const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
-    if (hm.opdim == 1) hipLaunchKernelGGL((k_measure_green_matrix<1>), grid, block, 0, lc.st, hm, gs, acc, row, rows, acs, lc.cs, apbx, apby);
-    else if (hm.opdim == 2) hipLaunchKernelGGL((k_measure_green_matrix<2>), grid, block, 0, lc.st, hm, gs, acc, row, rows, acs, lc.cs, apbx, apby);
-    else hipLaunchKernelGGL((k_measure_green_matrix<3>), grid, block, 0, lc.st, hm, gs, acc, row, rows, acs, lc.cs, apbx, apby);
+    dispatch_opdim(hm.opdim, [&](auto O) {
+        hipLaunchKernelGGL((k_measure_green_matrix<decltype(O)::value>), grid, block, 0, lc.st, hm, gs, acc, row, rows, acs, lc.cs, apbx, apby);
+    });
 }
 
 // Series part 13 (DQMC_SERIES_GREEN_MATRIX): the every-slice block of the kernel above normalised, out[k][N][R][R] (re, im) = row k /
@@ -2082,11 +1881,11 @@ bool launch_series_pair_vertex(const Launch& lc, const DevModel& hm, const doubl
     for (int ch = 0; ch < count; ++ch) cp.parts[ch] = pair.parts[ch];
     const PairVertexShape a{S, off_g, off_chi, hm.L, hm.N, hm.m, nfreq, lc.nb, B, count, qx, qy, apbx, apby, hm.dtau};
     const dim3 grid((unsigned)(hm.m + 1), (unsigned)(B + 1), (unsigned)lc.nb);
-    const void* fn = hm.opdim == 1 ? (const void*)k_series_pair_bubble<1> : hm.opdim == 2 ? (const void*)k_series_pair_bubble<2> : (const void*)k_series_pair_bubble<3>;
-    if (lds > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) (void)hipGetLastError();
-    if (hm.opdim == 1) hipLaunchKernelGGL((k_series_pair_bubble<1>), grid, dim3(256), lds, lc.st, bins, mean, trig, cp, a, pb);
-    else if (hm.opdim == 2) hipLaunchKernelGGL((k_series_pair_bubble<2>), grid, dim3(256), lds, lc.st, bins, mean, trig, cp, a, pb);
-    else hipLaunchKernelGGL((k_series_pair_bubble<3>), grid, dim3(256), lds, lc.st, bins, mean, trig, cp, a, pb);
+    dispatch_opdim(hm.opdim, [&](auto O) {
+        const void* fn = (const void*)k_series_pair_bubble<decltype(O)::value>;
+        if (lds > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) (void)hipGetLastError();
+        hipLaunchKernelGGL((k_series_pair_bubble<decltype(O)::value>), grid, dim3(256), lds, lc.st, bins, mean, trig, cp, a, pb);
+    });
     const int total = lc.nb * count * (5 + hm.m);
     hipLaunchKernelGGL(k_series_pair_vertex, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, lc.st, bins, pb, a, value, err);
     return true;
@@ -2280,11 +2079,11 @@ bool launch_series_ph_vertex(const Launch& lc, const DevModel& hm, const double*
     const CustomBondArg cb = custom_bond_arg(count, bond);
     const PhVertexShape a{S, off_g, off_chi, hm.L, hm.N, hm.m, nfreq, lc.nb, B, count, qx, qy, apbx, apby, hm.opdim == 3 ? 4 : 2, hm.dtau};
     const dim3 grid((unsigned)(hm.m + 1), (unsigned)(B + 1), (unsigned)lc.nb);
-    const void* fn = hm.opdim == 1 ? (const void*)k_series_ph_bubble<1> : hm.opdim == 2 ? (const void*)k_series_ph_bubble<2> : (const void*)k_series_ph_bubble<3>;
-    if (lds > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) (void)hipGetLastError();
-    if (hm.opdim == 1) hipLaunchKernelGGL((k_series_ph_bubble<1>), grid, dim3(256), lds, lc.st, bins, mean, trig, cb, a, pb);
-    else if (hm.opdim == 2) hipLaunchKernelGGL((k_series_ph_bubble<2>), grid, dim3(256), lds, lc.st, bins, mean, trig, cb, a, pb);
-    else hipLaunchKernelGGL((k_series_ph_bubble<3>), grid, dim3(256), lds, lc.st, bins, mean, trig, cb, a, pb);
+    dispatch_opdim(hm.opdim, [&](auto O) {
+        const void* fn = (const void*)k_series_ph_bubble<decltype(O)::value>;
+        if (lds > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) (void)hipGetLastError();
+        hipLaunchKernelGGL((k_series_ph_bubble<decltype(O)::value>), grid, dim3(256), lds, lc.st, bins, mean, trig, cb, a, pb);
+    });
     const int total = lc.nb * count * (6 + hm.m);
     hipLaunchKernelGGL(k_series_ph_vertex, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, lc.st, bins, mean, pb, cb, a, value, err);
     return true;
