@@ -151,8 +151,11 @@ _DP = C.POINTER(C.c_double)
 class dethubbard_params(C.Structure):
     _fields_ = [("L", C.c_int32), ("d", C.c_int32), ("m", C.c_int32), ("s", C.c_int32), ("checkerboard", C.c_int32),
                 ("device", C.c_int32), ("simindex", C.c_int32), ("rngSeed", C.c_uint32), ("stabilisation", C.c_int32),
-                ("reserved", C.c_int32), ("beta", C.c_double), ("dtau", C.c_double), ("t", C.c_double), ("U", C.c_double),
+                ("measureFlags", C.c_int32), ("beta", C.c_double), ("dtau", C.c_double), ("t", C.c_double), ("U", C.c_double),
                 ("mu", C.c_double)]
+
+
+DETHUBBARD_MEASURE_EQ, DETHUBBARD_MEASURE_TD = 1, 2      # dethubbard_params.measureFlags (include/dethubbard_host.h)
 
 
 class dethubbard_observables(C.Structure):
@@ -231,6 +234,12 @@ SYMBOLS = [
     ("dqmc_set_equal_time_band", C.c_int, [_P, C.c_int]),
     ("dqmc_measure_eq_band_accum_size", C.c_size_t, [_P]),
     ("dqmc_measure_eq_band_read_host", C.c_int, [_P, _DP]),
+    ("dqmc_hubbard_set_equal_time_correlators", C.c_int, [_P, C.c_int]),
+    ("dqmc_hubbard_eq_accum_size", C.c_size_t, [_P]),
+    ("dqmc_hubbard_eq_read_host", C.c_int, [_P, _DP]),
+    ("dqmc_hubbard_measure_timedisplaced", C.c_int, [_P, C.c_int]),
+    ("dqmc_hubbard_td_accum_size", C.c_size_t, [_P]),
+    ("dqmc_hubbard_td_read_host", C.c_int, [_P, _DP]),
     ("dqmc_set_timedisplaced", C.c_int, [_P, C.c_int]),
     ("dqmc_get_green_timedisplaced_host", C.c_int, [_P, _P, _P, C.POINTER(C.c_int)]),
     ("dqmc_measure_timedisplaced", C.c_int, [_P, C.c_int]),
@@ -391,6 +400,8 @@ SYMBOLS = [
     ("dethubbard_get_green", C.c_int, [_P, _DP, _DP]),
     ("dethubbard_get_observables", C.c_int, [_P, C.POINTER(dethubbard_observables)]),
     ("dethubbard_get_zcorr", C.c_int, [_P, _DP]),
+    ("dethubbard_get_eq_correlators", C.c_int, [_P, _DP]),
+    ("dethubbard_get_td_correlators", C.c_int, [_P, _DP]),
     ("dethubbard_save_state", C.c_int, [_P, C.c_char_p]),
     ("dethubbard_load_state", C.c_int, [_P, C.c_char_p]),
     ("dethubbard_set_green_check", C.c_int, [_P, C.c_int]),

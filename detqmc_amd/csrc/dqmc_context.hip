@@ -556,7 +556,19 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
     const int td_level = p->timedisplaced & ~DQMC_TD_EVERY_SLICE;
     if (p->timedisplaced < 0 || td_level > 2) return fail(DQMC_EINVAL, "timedisplaced must be 0, 1 or 2 (| DQMC_TD_EVERY_SLICE)");
     if ((p->timedisplaced & DQMC_TD_EVERY_SLICE) && !td_level) return fail(DQMC_EINVAL, "DQMC_TD_EVERY_SLICE needs timedisplaced >= 1");
-    if (td_level) {                 // behind every other buffer: the layout of a context without them is unchanged
+    if (p->model == DQMC_MODEL_HUBBARD && (p->timedisplaced || p->td_particle_hole)) {
+        // the one reservation of this model, behind every other buffer: the matrices of the time-displaced Green's functions with G(0),
+        // the scratch of the correlators' prepare pass (ph_H: n_g^2 complex hold its 4 N^2 + 4 N doubles) and the block of
+        // dqmc_hubbard_measure_timedisplaced; none of the SDW blocks
+        if (p->timedisplaced != 1 || p->td_particle_hole != 1)
+            return fail(DQMC_EINVAL, "Hubbard replica: timedisplaced = 1 with td_particle_hole = 1 is the only time-displaced reservation (every "
+                                     "other value of the two fields: SDW model only)");
+        c->td_reserved = true;
+        A_(dalloc(c, &c->GT0, n2)); A_(dalloc(c, &c->G0T, n2)); A_(dalloc(c, &c->td_W, n2));
+        if (c->stab != DQMC_STAB_QR) { A_(alloc_qr_work(c)); A_(dalloc(c, &c->td_sv, (size_t)ng)); }
+        A_(dalloc(c, &c->G00, n2)); A_(dalloc(c, &c->ph_H, n2));
+        A_(acc_alloc(ACC_HUB_TD, hubbard_td_doubles(N, c->n)));
+    } else if (td_level) {          // behind every other buffer: the layout of a context without them is unchanged
         if (p->model != DQMC_MODEL_SDW) return fail(DQMC_EINVAL, "timedisplaced: SDW model only");
         c->td_reserved = true;
         A_(dalloc(c, &c->GT0, n2)); A_(dalloc(c, &c->G0T, n2)); A_(dalloc(c, &c->td_W, n2));
@@ -568,7 +580,7 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
     const bool ph_band = p->td_particle_hole >= 0 && (p->td_particle_hole & DQMC_TD_PH_BAND);
     if (p->td_particle_hole < 0 || ph_level > 2) return fail(DQMC_EINVAL, "td_particle_hole must be 0, 1 or 2 (| DQMC_TD_PH_BAND)");
     if (ph_band && !ph_level) return fail(DQMC_EINVAL, "DQMC_TD_PH_BAND needs td_particle_hole >= 1");
-    if (ph_level) {              // behind the blocks above: contexts without the flag are laid out as before
+    if (ph_level && p->model == DQMC_MODEL_SDW) {     // behind the blocks above: contexts without the flag are laid out as before
         if (!td_level) return fail(DQMC_EINVAL, "td_particle_hole needs timedisplaced >= 1");
         A_(dalloc(c, &c->G00, n2)); A_(dalloc(c, &c->ph_H, n2));
         A_(dalloc(c, &c->ph_ob, measure_td_ph_onebody_cplx(N)));
@@ -597,6 +609,7 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
     A_(arena_commit(c));                    // from here on the per-chain pointers are real (chain 0) addresses, zero filled
 #undef A_
     for (int id = 0; id < ACC_EQ; ++id) c->acc[id].stride = c->lc.cs;
+    c->acc[ACC_HUB_TD].stride = c->lc.cs;
     c->qw.err = &c->us->chol_fail;
     hm.phi = c->phi; hm.coshT = c->coshT; hm.sinhT = c->sinhT;
     if (p->cdwU != 0.0) {

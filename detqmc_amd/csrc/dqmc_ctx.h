@@ -38,10 +38,11 @@ enum { FAM_BMULT = DQMC_FAM_BMULT, FAM_GEMM = DQMC_FAM_GEMM, FAM_JACOBI = DQMC_F
 // channels, the four every-slice ones (channel ch at ACC_FINE0 + ch, as ACC_TD + ch for the coarse ones) and the equal-time correlators;
 // channel 4 of both families and ACC_EQ_BAND are the band-resolved charge blocks (DQMC_TD_PH_BAND, dqmc_set_equal_time_band), channel 5
 // and ACC_EQ_CUSTOM the blocks of the user-defined bilinears (dqmc_set_custom_bilinears), channel 6 and ACC_EQ_CUSTOM_PAIR those of the
-// user-defined pair operators (dqmc_set_custom_pair_operators), channel 7 the averaged Green's function block (dqmc_set_green_matrix)
+// user-defined pair operators (dqmc_set_custom_pair_operators), channel 7 the averaged Green's function block (dqmc_set_green_matrix);
+// ACC_HUB_EQ / ACC_HUB_TD the equal-time and time-displaced correlators of the Hubbard model (dqmc_hubbard_*), behind every SDW block
 enum { TD_CHANNELS = 8 };
 enum { ACC_SLICE, ACC_TD, ACC_TD_PAIR, ACC_TD_PH, ACC_TD_CUR, ACC_TD_BAND, ACC_TD_CUSTOM, ACC_TD_CUSTOM_PAIR, ACC_TD_GREEN_MATRIX, ACC_FINE0,
-       ACC_EQ = ACC_FINE0 + TD_CHANNELS, ACC_EQ_BAND, ACC_EQ_CUSTOM, ACC_EQ_CUSTOM_PAIR, ACC_COUNT };
+       ACC_EQ = ACC_FINE0 + TD_CHANNELS, ACC_EQ_BAND, ACC_EQ_CUSTOM, ACC_EQ_CUSTOM_PAIR, ACC_HUB_EQ, ACC_HUB_TD, ACC_COUNT };
 // n: doubles per chain, 0 while the context has no such block; chain b starts at (char*)p + b * stride (the arena's chain stride; the
 // equal-time blocks and every block of the user-defined bilinears and pair operators live outside the arena as [chain][n]); missing: what a read of an absent
 // block reports
@@ -97,7 +98,9 @@ struct dqmc_ctx {
         {nullptr, 0, 0, "the equal-time correlators have never been enabled (dqmc_set_equal_time_correlators)"},
         {nullptr, 0, 0, "the equal-time band correlators have never been enabled (dqmc_set_equal_time_band)"},
         {nullptr, 0, 0, "no user-defined bilinear is set (dqmc_set_custom_bilinears)"},
-        {nullptr, 0, 0, "no user-defined pair operator is set (dqmc_set_custom_pair_operators)"}};
+        {nullptr, 0, 0, "no user-defined pair operator is set (dqmc_set_custom_pair_operators)"},
+        {nullptr, 0, 0, "the Hubbard equal-time correlators have never been enabled (dqmc_hubbard_set_equal_time_correlators)"},
+        {nullptr, 0, 0, "Hubbard context created without dqmc_params::timedisplaced = 1 and td_particle_hole = 1"}};
     // time-displaced Green's functions (dqmc_params::timedisplaced reserves them; dqmc_set_timedisplaced switches them on)
     bool td_reserved = false, td_on = false;
     int td_slice = -1;                                        // tau slice of the last pair GT0 / G0T (all chains), -1: none yet
@@ -120,6 +123,10 @@ struct dqmc_ctx {
     // dqmc_set_equal_time_correlators: block [chain][1 + 5 N] and one-body scratch [chain][5 N], outside the arena, allocated by the first enable
     bool eq_on = false;
     cplx* eq_ob = nullptr;
+    // dqmc_hubbard_set_equal_time_correlators: block ACC_HUB_EQ [chain][1 + 8 N] and the scratch of the prepare pass [chain][4 N^2 + 4 N], outside
+    // the arena, allocated by the first enable.  The time-displaced block ACC_HUB_TD lives in the arena; its prepare pass writes into ph_H
+    bool hub_eq_on = false;
+    double* hub_eq_sc = nullptr;
     // dqmc_set_equal_time_band: block [chain][1 + 2 N] and one-body scratch [chain][3 N], outside the arena, allocated by the first enable
     bool eqb_on = false;
     cplx* eqb_ob = nullptr;

@@ -264,6 +264,22 @@ void launch_hubbard_vscale(const Launch& lc, const DevModel& hm, int side, int i
 void launch_hubbard_slice(const Launch& lc, const DevModel& hm, DevUpdateState* us, const double* uniforms, cplx* G, int k,
                           double e_m2a, double e_p2a);
 void launch_hubbard_measure(const Launch& lc, const DevModel& hm, const cplx* G, double* acc);
+// Correlators of the Hubbard replica (dqmc_hubbard_* in dqmc_hip.h).  Channels of the equal-time block count, [HUB_EQ_CH][N]: greenUp,
+// greenDn, charge, spinZZ, spinXX, pairS, pairSx, pairD; of the time-displaced block count[n-1], [n-1][HUB_TD_CH][N]: the first six.
+// launch_hubbard_corr_prep fills the scratch sc (hubbard_corr_scratch_doubles per chain) both walks read: the spin blocks of T transposed,
+// with S != nullptr the two stencilled forms of its down block, and the occupations of the tau side (from Gt) and the 0 side (from G0).
+// Equal time: (T, S, Gt, G0) = (G, G, G, G); time-displaced: (G(0,tau), nullptr, G(tau), G(0)), then the walk over G(tau,0).
+// sc and acc may live outside the arena: chain b at (char*)sc + b * scs, (char*)acc + b * acs
+#define HUB_EQ_CH 8
+#define HUB_TD_CH 6
+size_t hubbard_corr_scratch_doubles(int N);
+size_t hubbard_eq_doubles(int N);
+size_t hubbard_td_doubles(int N, int n);
+void launch_hubbard_corr_prep(const Launch& lc, const DevModel& hm, const cplx* T, const cplx* S, const cplx* Gt, const cplx* G0, double* sc,
+                              size_t scs);
+void launch_hubbard_eq_corr(const Launch& lc, const DevModel& hm, const cplx* G, const double* sc, size_t scs, double* acc, size_t acs);
+void launch_hubbard_td_corr(const Launch& lc, const DevModel& hm, const cplx* GT0, const double* sc, size_t scs, double* acc, size_t acs,
+                            int row, int rows);
 
 // misc elementwise
 void launch_cosh_sinh(const Launch& lc, const DevModel& hm);

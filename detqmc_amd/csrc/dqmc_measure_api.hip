@@ -68,8 +68,14 @@ extern "C" int dqmc_measure_slice(dqmc_ctx* c) {
     G_FRESH(c, "dqmc_measure_slice");
     (void)hipSetDevice(c->p.device);
     if (c->hm.hubbard) {            // DetHubbard::measure (dethubbard.cpp:521-545): accumulator layout in kernels_hubbard.hip
-        ProfScope ps(c, FAM_OTHER, 1);
-        launch_hubbard_measure(c->lc, c->hm, c->G, c->acc[ACC_SLICE].p);
+        { ProfScope ps(c, FAM_OTHER, 1); launch_hubbard_measure(c->lc, c->hm, c->G, c->acc[ACC_SLICE].p); }
+        if (c->hub_eq_on) {         // the same unshifted G: prepare pass (transposes, bond stencils, occupations), then the walk
+            ProfScope ps(c, FAM_OTHER, 2);
+            const AccBlock& a = c->acc[ACC_HUB_EQ];
+            const size_t scs = hubbard_corr_scratch_doubles(c->N) * sizeof(double);
+            launch_hubbard_corr_prep(c->lc, c->hm, c->G, c->G, c->G, c->G, c->hub_eq_sc, scs);
+            launch_hubbard_eq_corr(c->lc, c->hm, c->G, c->hub_eq_sc, scs, a.p, a.stride);
+        }
         return finish(c, "dqmc_measure_slice");
     }
     shift_green_dev(c);
@@ -110,6 +116,25 @@ extern "C" int dqmc_set_equal_time_correlators(dqmc_ctx* c, int on) {
 }
 extern "C" size_t dqmc_measure_eq_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_EQ); }
 extern "C" int dqmc_measure_eq_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_EQ, out); }
+// Hubbard replica (dqmc_hip.h): equal-time correlators, a switch of dqmc_measure_slice with a block of its own outside the arena ...
+extern "C" int dqmc_hubbard_set_equal_time_correlators(dqmc_ctx* c, int on) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (!c->hm.hubbard) return fail(DQMC_EINVAL, "dqmc_hubbard_set_equal_time_correlators belongs to the Hubbard model");
+    AccBlock& eq = c->acc[ACC_HUB_EQ];
+    if (on && !eq.n) {
+        (void)hipSetDevice(c->p.device);
+        const size_t n = hubbard_eq_doubles(c->N), nsc = hubbard_corr_scratch_doubles(c->N);
+        if (const int rc = salloc(c, &eq.p, n * (size_t)c->nb)) return rc;
+        if (const int rc = salloc(c, &c->hub_eq_sc, nsc * (size_t)c->nb)) return rc;
+        HIPCHK(hipMemsetAsync(eq.p, 0, n * (size_t)c->nb * sizeof(double), c->st));
+        HIPCHK(hipMemsetAsync(c->hub_eq_sc, 0, nsc * (size_t)c->nb * sizeof(double), c->st));
+        eq.n = n; eq.stride = n * sizeof(double);
+    }
+    c->hub_eq_on = on != 0;
+    return DQMC_OK;
+}
+extern "C" size_t dqmc_hubbard_eq_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_HUB_EQ); }
+extern "C" int dqmc_hubbard_eq_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_HUB_EQ, out); }
 // equal-time bandDiff / bandMix correlators (dqmc_hip.h): a second, independent switch of dqmc_measure_slice with a block of its own
 extern "C" int dqmc_set_equal_time_band(dqmc_ctx* c, int on) {
     if (!c) return fail(DQMC_EINVAL, "null ctx");
@@ -607,6 +632,7 @@ static int td_boundary_ok(dqmc_ctx* c, int j, bool need_current_G) {
 // of the boundary the context stands on).  Each call prepares its shifted matrices itself, so the five stand on their own in any order.
 static int td_coarse(dqmc_ctx* c, int ch, int j, const char* entry) {
     if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (c->hm.hubbard) return fail(DQMC_EINVAL, std::string(entry) + " belongs to the SDW model (Hubbard: dqmc_hubbard_measure_timedisplaced)");
     if (!c->acc[ACC_TD + ch].n) return fail(DQMC_EINVAL, c->acc[ACC_TD + ch].missing);
     if (const int rc = td_boundary_ok(c, j, ((1u << ch) & CH_TWO_BODY) != 0)) return rc;
     (void)hipSetDevice(c->p.device);
@@ -621,6 +647,22 @@ extern "C" int dqmc_measure_timedisplaced_band(dqmc_ctx* c, int j) { return td_c
 extern "C" int dqmc_measure_timedisplaced_custom(dqmc_ctx* c, int j) { return td_coarse(c, 5, j, "dqmc_measure_timedisplaced_custom"); }
 extern "C" int dqmc_measure_timedisplaced_custom_pair(dqmc_ctx* c, int j) { return td_coarse(c, 6, j, "dqmc_measure_timedisplaced_custom_pair"); }
 extern "C" int dqmc_measure_timedisplaced_green_matrix(dqmc_ctx* c, int j) { return td_coarse(c, 7, j, "dqmc_measure_timedisplaced_green_matrix"); }
+// ... and the time-displaced ones: row j - 1 of the block, from the four matrices of the boundary the context stands on, unshifted
+extern "C" int dqmc_hubbard_measure_timedisplaced(dqmc_ctx* c, int j) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (!c->hm.hubbard) return fail(DQMC_EINVAL, "dqmc_hubbard_measure_timedisplaced belongs to the Hubbard model");
+    const AccBlock& a = c->acc[ACC_HUB_TD];
+    if (!a.n) return fail(DQMC_EINVAL, a.missing);
+    if (const int rc = td_boundary_ok(c, j, true)) return rc;
+    (void)hipSetDevice(c->p.device);
+    ProfScope ps(c, FAM_OTHER, 2);
+    double* sc = (double*)c->ph_H;
+    launch_hubbard_corr_prep(c->lc, c->hm, c->G0T, nullptr, c->G, c->G00, sc, c->lc.cs);
+    launch_hubbard_td_corr(c->lc, c->hm, c->GT0, sc, c->lc.cs, a.p, a.stride, j - 1, c->n - 1);
+    return finish(c, "dqmc_hubbard_measure_timedisplaced");
+}
+extern "C" size_t dqmc_hubbard_td_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_HUB_TD); }
+extern "C" int dqmc_hubbard_td_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_HUB_TD, out); }
 extern "C" size_t dqmc_measure_td_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_TD); }
 extern "C" int dqmc_measure_td_read_host(dqmc_ctx* c, double* out) { return acc_read(c, ACC_TD, out); }
 extern "C" size_t dqmc_measure_td_pair_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_TD_PAIR); }

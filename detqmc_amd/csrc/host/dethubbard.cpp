@@ -32,6 +32,7 @@ DetHubbard::DetHubbard(const dethubbard_params& in, int nchains) : p_(in) {
     if (p_.d != 2) throw ParameterWrong("Hubbard replica: only d = 2 lattices are supported by this build");
     if (p_.checkerboard && p_.L % 2 != 0) throw ParameterWrong("Checker board decomposition only supported for even linear lattice sizes");
     if (p_.L % 2 != 0) throw ParameterWrong("this build needs an even linear lattice size");
+    if (p_.measureFlags & ~(DETHUBBARD_MEASURE_EQ | DETHUBBARD_MEASURE_TD)) throw ParameterWrong("Parameter measureFlags has an unknown bit set");
     N_ = p_.L * p_.L; m_ = p_.m; s_ = p_.s; n_ = (m_ + s_ - 1) / s_;
     alpha_ = std::acosh(std::exp(p_.dtau * p_.U * 0.5));
 
@@ -42,6 +43,7 @@ DetHubbard::DetHubbard(const dethubbard_params& in, int nchains) : p_(in) {
     kp.stabilisation = p_.stabilisation; kp.cb_none = p_.checkerboard ? 0 : 1;
     kp.dtau = p_.dtau; kp.txhor = p_.t; kp.u = p_.U; kp.mux = p_.mu; kp.muy = p_.mu; kp.accRatio = 0.5;
     kp.tuning.bmult_path = DQMC_TUNING_NO_RNG_LOOKAHEAD;     // this replica pushes every window whole (beginLocalUpdates)
+    if (p_.measureFlags & DETHUBBARD_MEASURE_TD) { kp.timedisplaced = 1; kp.td_particle_hole = 1; }   // G(tau,0), G(0,tau), G(0) and the block
     check(dqmc_create_batch(&kp, nchains, &ctx_), "dqmc_create");
     try {
         std::vector<double> all((size_t)nchains * (m_ + 1) * N_, 0.0);
@@ -70,23 +72,30 @@ void DetHubbard::updateInSlice(int k) {
     if (measuring_) check(dqmc_measure_slice(ctx_), "measure");     // updateInSliceAndMaybeMeasure (detmodel.h:1279-1285)
 }
 
+// an advance, and on the interior boundary it ends on the time-displaced correlators of that boundary (measurement sweeps with
+// DETHUBBARD_MEASURE_TD: the context has just formed G(tau_j,0), G(0,tau_j) and G(0) next to G(tau_j))
+void DetHubbard::advance(int dir, int l, int boundary, const char* what) {
+    check(dqmc_advance(ctx_, dir, l), what);
+    if (measuringTD_ && boundary) check(dqmc_hubbard_measure_timedisplaced(ctx_, boundary), "measureTimeDisplaced");
+}
+
 void DetHubbard::sweepDown() {                                      // detmodel.h:1333-1399
     for (int k = m_; k >= (n_ - 1) * s_ + 1; --k) { updateInSlice(k); check(dqmc_wrap(ctx_, DQMC_DOWN, k), "wrapDownGreen"); }
     for (int l = n_ - 1; l >= 1; --l) {
-        check(dqmc_advance(ctx_, DQMC_DOWN, l + 1), "advanceDownGreen");
+        advance(DQMC_DOWN, l + 1, l, "advanceDownGreen");
         for (int k = l * s_; k >= (l - 1) * s_ + 1; --k) { updateInSlice(k); check(dqmc_wrap(ctx_, DQMC_DOWN, k), "wrapDownGreen"); }
     }
-    check(dqmc_advance(ctx_, DQMC_DOWN, 1), "advanceDownGreen");
+    advance(DQMC_DOWN, 1, 0, "advanceDownGreen");
 }
 
 void DetHubbard::sweepUp() {                                        // detmodel.h:1266-1325
     check(dqmc_reset_storage0(ctx_), "reset storage[0]");
     for (int l = 0; l <= n_ - 2; ++l) {
         for (int k = l * s_ + 1; k <= (l + 1) * s_; ++k) { check(dqmc_wrap(ctx_, DQMC_UP, k - 1), "wrapUpGreen"); updateInSlice(k); }
-        check(dqmc_advance(ctx_, DQMC_UP, l), "advanceUpGreen");
+        advance(DQMC_UP, l, l + 1, "advanceUpGreen");
     }
     for (int k = (n_ - 1) * s_ + 1; k <= m_; ++k) { check(dqmc_wrap(ctx_, DQMC_UP, k - 1), "wrapUpGreen"); updateInSlice(k); }
-    check(dqmc_advance(ctx_, DQMC_UP, n_ - 1), "advanceUpGreen");
+    advance(DQMC_UP, n_ - 1, 0, "advanceUpGreen");
 }
 
 void DetHubbard::sweep_skeleton(bool takeMeasurements) {
@@ -97,10 +106,20 @@ void DetHubbard::sweep_skeleton(bool takeMeasurements) {
     check(dqmc_push_uniforms_all_host(ctx_, window_.data(), need), "dqmc_push_uniforms_all_host");
     if (takeMeasurements) check(dqmc_measure_reset(ctx_), "initMeasurements");
     measuring_ = takeMeasurements;
+    // the correlators ride on measurement sweeps only: thermalisation sweeps launch nothing new and never form the time-displaced pair
+    const bool eq = takeMeasurements && (p_.measureFlags & DETHUBBARD_MEASURE_EQ);
+    measuringTD_ = takeMeasurements && (p_.measureFlags & DETHUBBARD_MEASURE_TD);
+    if (eq) check(dqmc_hubbard_set_equal_time_correlators(ctx_, 1), "dqmc_hubbard_set_equal_time_correlators");
+    if (measuringTD_) check(dqmc_set_timedisplaced(ctx_, 1), "dqmc_set_timedisplaced");
+    auto off = [this, eq]() {
+        if (eq) (void)dqmc_hubbard_set_equal_time_correlators(ctx_, 0);
+        if (measuringTD_) (void)dqmc_set_timedisplaced(ctx_, 0);
+        measuring_ = measuringTD_ = false;
+    };
     try {
         if (lastSweepDir_ == Up) sweepDown(); else sweepUp();
-    } catch (...) { measuring_ = false; throw; }
-    measuring_ = false;
+    } catch (...) { off(); throw; }
+    off();
     lastSweepDir_ = (lastSweepDir_ == Up) ? Down : Up;
     ++performedSweeps_;
     std::vector<dqmc_update_state> st(nb);
@@ -122,6 +141,7 @@ void DetHubbard::finishMeasurements(int b) {
     if ((int)acc[5] != m_) throw GeneralError(DQMC_EINVAL, "measurement sweep did not visit every time slice");
     const double N = N_, m = m_;
     dethubbard_observables& o = ch_[b].obs;
+    o.valid = 0;
     o.occUp = 1.0 - (1.0 / (N * m)) * acc[0];
     o.occDn = 1.0 - (1.0 / (N * m)) * acc[1];
     o.occTotal = o.occUp + o.occDn;
@@ -130,9 +150,38 @@ void DetHubbard::finishMeasurements(int b) {
     o.ePotential = p_.U * o.occDouble;
     o.eKinetic = (p_.t / (N * m)) * (acc[2] + acc[3]) - p_.mu * o.occTotal;
     o.eTotal = o.eKinetic + o.ePotential;
-    o.valid = 1;
     ch_[b].zcorr.assign(N_, 0.0);
     for (int j = 0; j < N_; ++j) ch_[b].zcorr[j] = acc[6 + j] / m;
+    if (p_.measureFlags & DETHUBBARD_MEASURE_EQ) {                  // count, [8][N] raw sums -> C(d) = sum / (count N)
+        std::vector<double> blk(dqmc_hubbard_eq_accum_size(ctx_));
+        check(dqmc_hubbard_eq_read_host(ctx_, blk.data()), "dqmc_hubbard_eq_read_host");
+        if ((int)blk[0] != m_) throw GeneralError(DQMC_EINVAL, "measurement sweep did not bin the equal-time correlators on every time slice");
+        ch_[b].eqCorr.assign(blk.size() - 1, 0.0);
+        for (size_t i = 0; i + 1 < blk.size(); ++i) ch_[b].eqCorr[i] = blk[1 + i] / (m * N);
+    }
+    if (p_.measureFlags & DETHUBBARD_MEASURE_TD) {                  // count[n-1], [n-1][6][N]
+        std::vector<double> blk(dqmc_hubbard_td_accum_size(ctx_));
+        check(dqmc_hubbard_td_read_host(ctx_, blk.data()), "dqmc_hubbard_td_read_host");
+        const size_t rows = (size_t)(n_ - 1), row = (blk.size() - rows) / (rows ? rows : 1);
+        ch_[b].tdCorr.assign(rows * row, 0.0);
+        for (size_t j = 0; j < rows; ++j) {
+            if ((int)blk[j] != 1) throw GeneralError(DQMC_EINVAL, "measurement sweep did not take one time-displaced sample per interior boundary");
+            for (size_t i = 0; i < row; ++i) ch_[b].tdCorr[j * row + i] = blk[rows + j * row + i] / N;
+        }
+    }
+    o.valid = 1;                                                    // last: a sweep that threw above leaves no half-read observables behind
+}
+
+void DetHubbard::getEqCorrelators(double* out, int b) const {
+    if (!(p_.measureFlags & DETHUBBARD_MEASURE_EQ)) throw GeneralError(DQMC_EINVAL, "the equal-time correlators need DETHUBBARD_MEASURE_EQ in measureFlags");
+    if (!ch_[b].obs.valid) throw GeneralError(DQMC_EINVAL, "no measurement has been taken");
+    std::memcpy(out, ch_[b].eqCorr.data(), ch_[b].eqCorr.size() * sizeof(double));
+}
+
+void DetHubbard::getTdCorrelators(double* out, int b) const {
+    if (!(p_.measureFlags & DETHUBBARD_MEASURE_TD)) throw GeneralError(DQMC_EINVAL, "the time-displaced correlators need DETHUBBARD_MEASURE_TD in measureFlags");
+    if (!ch_[b].obs.valid) throw GeneralError(DQMC_EINVAL, "no measurement has been taken");
+    std::memcpy(out, ch_[b].tdCorr.data(), ch_[b].tdCorr.size() * sizeof(double));
 }
 
 void DetHubbard::getZcorr(double* out, int b) const {
@@ -253,6 +302,14 @@ extern "C" int dethubbard_get_auxfield(dethubbard_replica* r, double* out) { HGU
 extern "C" int dethubbard_get_green(dethubbard_replica* r, double* gUp, double* gDn) { HGUARD(r->impl->getGreen(gUp, gDn, r->sel)) }
 extern "C" int dethubbard_get_observables(dethubbard_replica* r, dethubbard_observables* out) { HGUARD(r->impl->getObservables(*out, r->sel)) }
 extern "C" int dethubbard_get_zcorr(dethubbard_replica* r, double* out) { HGUARD(r->impl->getZcorr(out, r->sel)) }
+extern "C" int dethubbard_get_eq_correlators(dethubbard_replica* r, double* out) {
+    if (!out) { g_hub_err = "null argument"; return DQMC_EINVAL; }
+    HGUARD(r->impl->getEqCorrelators(out, r->sel))
+}
+extern "C" int dethubbard_get_td_correlators(dethubbard_replica* r, double* out) {
+    if (!out) { g_hub_err = "null argument"; return DQMC_EINVAL; }
+    HGUARD(r->impl->getTdCorrelators(out, r->sel))
+}
 extern "C" int dethubbard_save_state(dethubbard_replica* r, const char* path) {
     if (!path) { g_hub_err = "null path"; return DQMC_EINVAL; }
     HGUARD(r->impl->saveState(path))

@@ -23,6 +23,8 @@ public:
     void getGreen(double* gUp, double* gDn, int b);
     void getObservables(dethubbard_observables& out, int b) const { out = ch_[b].obs; }
     void getZcorr(double* out, int b) const;
+    void getEqCorrelators(double* out, int b) const;       // [8][N], needs DETHUBBARD_MEASURE_EQ
+    void getTdCorrelators(double* out, int b) const;       // [n-1][6][N], needs DETHUBBARD_MEASURE_TD
     void saveState(const std::string& path);
     void loadState(const std::string& path);
     double rand01(int b) { return ch_[b].rng.rand01(); }
@@ -40,6 +42,7 @@ private:
         double lastAccRatio = 0.0;
         dethubbard_observables obs{};
         std::vector<double> zcorr;
+        std::vector<double> eqCorr, tdCorr;    // normalised C(d) of the last measurement sweep (measureFlags)
         Chain(uint32_t seed, uint32_t simindex) : rng(seed, simindex + 1u) {}      // detqmc.h:181
     };
     dethubbard_params p_;
@@ -51,12 +54,14 @@ private:
     SweepDirection lastSweepDir_ = Up;
     int performedSweeps_ = 0;
     bool measuring_ = false;
+    bool measuringTD_ = false;        // ... with G(tau_j, 0) and its correlators after every interior advance (DETHUBBARD_MEASURE_TD)
 
     static void check(int rc, const char* what);
     void sweep_skeleton(bool takeMeasurements);
     void sweepDown();
     void sweepUp();
     void updateInSlice(int k);
+    void advance(int dir, int l, int boundary, const char* what);     // boundary: the interior boundary j the advance ends on, 0: none
     void finishMeasurements(int b);
 };
 

@@ -11,7 +11,9 @@
 //                      weightRatioSingleFlip (:858-874), Metropolis, rank-1 Sherman-Morrison update of both spin blocks
 //                      (updateGreenFunctionWithFlip, :877-906) -- one workgroup per replica walks the whole slice
 //   k_hubbard_measure  measure(timeslice) (:521-545): sums over G_ii, nearest-neighbour G_ij and the spin-z correlation
+//   k_hubbard_corr_prep, k_hubbard_corr   equal-time and time-displaced correlators over all site differences (not in the reference)
 #include "dqmc_internal.h"
+#include "bin_walk.h"
 
 __global__ void k_hubbard_vscale(DevModel dm, cplx* __restrict__ A, int lda, int right, double sgn, int k, size_t cs) {
     dm = chain_model(dm, cs); CHAIN(A);
@@ -150,4 +152,119 @@ __global__ __launch_bounds__(256) void k_hubbard_measure(DevModel dm, const cplx
 }
 void launch_hubbard_measure(const Launch& lc, const DevModel& hm, const cplx* G, double* acc) {
     hipLaunchKernelGGL(k_hubbard_measure, dim3(1, 1, lc.nb), dim3(256), 0, lc.st, hm, G, acc, lc.cs);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Equal-time and time-displaced correlators (dqmc_hubbard_* in dqmc_hip.h; definitions and layouts in DESIGN.md).  G_s(A, B) =
+// <c_As c^+_Bs> is the .x half of spin block s of an n_g x n_g matrix (block 0 up, 1 down); the off-diagonal blocks are never read.
+// Two launches per sample, all chains each:
+//   k_hubbard_corr_prep   fills a per-chain scratch of doubles, everything the walk would otherwise read strided or sixteen-fold:
+//                           tU, tD [N][N]   tX[B N + A] = T_s(B, A), the spin blocks of T transposed through a 32 x 32 LDS tile
+//                           sS, sD [N][N]   sX[B N + A] = sum_{dl, dl'} f_dl f_dl' S_dn(A + dl, B + dl'), f = +1 (extended s) and
+//                                           f = +1 on +-x, -1 on +-y (d wave); only with a stencil source S
+//                           ob [4][N]       n_up, n_dn of the tau side (1 - Gt_s(A, A)), then of the 0 side (1 - G0_s(B, B))
+//   k_hubbard_corr<TD>    the displacement walk of bin_walk.h: a workgroup of TDP_BINS * TDP_PARTS threads owns 32 displacements d,
+//                         thread (part, d) sums the pairs (A = B (+) d, B), B = part, part + 8, ...; every load is one element per
+//                         pair at B ld + A, consecutive in A over the lanes.  One writer per accumulator, fixed order, no atomics.
+// The scratch and the blocks may live outside the arena: they carry chain strides of their own (bytes).
+size_t hubbard_corr_scratch_doubles(int N) { return 4 * (size_t)N * N + 4 * (size_t)N; }
+size_t hubbard_eq_doubles(int N) { return 1 + HUB_EQ_CH * (size_t)N; }
+size_t hubbard_td_doubles(int N, int n) { return (size_t)(n - 1) * (1 + HUB_TD_CH * (size_t)N); }
+
+__global__ __launch_bounds__(256) void k_hubbard_corr_prep(DevModel dm, const cplx* __restrict__ T, const cplx* __restrict__ S,
+                                                            const cplx* __restrict__ Gt, const cplx* __restrict__ G0,
+                                                            double* __restrict__ sc, size_t cs, size_t scs) {
+    __shared__ double tile[2][32][33];
+    CHAIN(T); CHAIN(S); CHAIN(Gt); CHAIN(G0);
+    sc = chain_ptr(sc, scs);
+    const int N = dm.N, tx = threadIdx.x % 32, ty = threadIdx.x / 32;
+    const size_t ng = (size_t)dm.ng, NN = (size_t)N * N;
+    const int tiles = (N + 31) / 32, A0 = (blockIdx.x % tiles) * 32, B0 = (blockIdx.x / tiles) * 32;
+    double *tU = sc, *tD = sc + NN, *sS = sc + 2 * NN, *sD = sc + 3 * NN, *ob = sc + 4 * NN;
+    // lanes along B, the row index of T: tile[a][b] = T_s(B0 + b, A0 + a)
+    for (int a = ty; a < 32; a += 8)
+        if (A0 + a < N && B0 + tx < N) {
+            tile[0][a][tx] = T[(size_t)(A0 + a) * ng + (B0 + tx)].x;
+            tile[1][a][tx] = T[(size_t)(N + A0 + a) * ng + (N + B0 + tx)].x;
+        }
+    __syncthreads();
+    // lanes along A
+    for (int b = ty; b < 32; b += 8) {
+        const int A = A0 + tx, B = B0 + b;
+        if (A >= N || B >= N) continue;
+        const size_t idx = (size_t)B * N + A;
+        tU[idx] = tile[0][tx][b];
+        tD[idx] = tile[1][tx][b];
+        if (S) {
+            double ss = 0.0, sd = 0.0;
+            for (int q = 0; q < 4; ++q) {                                       // dl' on B: XPLUS, XMINUS, YPLUS, YMINUS
+                const size_t col = (size_t)(N + dm.neigh[q * N + B]) * ng + N;
+                const double xs = S[col + dm.neigh[A]].x + S[col + dm.neigh[N + A]].x;           // dl = +-x
+                const double ys = S[col + dm.neigh[2 * N + A]].x + S[col + dm.neigh[3 * N + A]].x;   // dl = +-y
+                ss += xs + ys;
+                sd += q < 2 ? xs - ys : ys - xs;
+            }
+            sS[idx] = ss;
+            sD[idx] = sd;
+        }
+    }
+    if (blockIdx.x == 0)
+        for (int i = threadIdx.x; i < N; i += 256) {
+            ob[i] = 1.0 - Gt[(size_t)i * ng + i].x;
+            ob[N + i] = 1.0 - Gt[(size_t)(N + i) * ng + (N + i)].x;
+            ob[2 * N + i] = 1.0 - G0[(size_t)i * ng + i].x;
+            ob[3 * N + i] = 1.0 - G0[(size_t)(N + i) * ng + (N + i)].x;
+        }
+}
+void launch_hubbard_corr_prep(const Launch& lc, const DevModel& hm, const cplx* T, const cplx* S, const cplx* Gt, const cplx* G0, double* sc,
+                              size_t scs) {
+    const int tiles = (hm.N + 31) / 32;
+    hipLaunchKernelGGL(k_hubbard_corr_prep, dim3(tiles * tiles, 1, lc.nb), dim3(256), 0, lc.st, hm, T, S, Gt, G0, sc, lc.cs, scs);
+}
+
+// TD = 0: g = G of the slice, the scratch of (T, S) = (G, G): <c^+_A c_B> = delta_AB - G(B, A).  Block: count, [HUB_EQ_CH][N].
+// TD = 1: g = G(tau,0), the scratch of T = G(0,tau), no stencil: <c^+_A(tau) c_B(0)> = -G(0,tau)(B, A).  Row `row` of count[rows], [rows][HUB_TD_CH][N].
+template<int TD>
+__global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_hubbard_corr(DevModel dm, const cplx* __restrict__ g, const double* __restrict__ sc,
+                                                                       double* __restrict__ acc, int row, int rows, size_t cs, size_t scs, size_t acs) {
+    constexpr int NCH = TD ? HUB_TD_CH : HUB_EQ_CH;
+    __shared__ double red[NCH][TDP_PARTS][TDP_BINS];
+    CHAIN(g);
+    sc = chain_ptr(sc, scs); acc = chain_ptr(acc, acs);
+    const int N = dm.N, L = dm.L;
+    const size_t ng = (size_t)dm.ng, NN = (size_t)N * N;
+    const double *tU = sc, *tD = sc + NN, *sS = sc + 2 * NN, *sD = sc + 3 * NN, *ob = sc + 4 * NN;
+    const BinWalk bw(N, L);
+    const double dl = (!TD && bw.d == 0) ? 1.0 : 0.0;                           // delta_AB: the pairs of displacement 0
+    double w[NCH];
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) w[ch] = 0.0;
+    for (BinSite st = bw.first(N, L); st.B < N; bw.next(st, L)) {
+        const size_t idx = (size_t)st.B * N + st.A;
+        const double gu = g[(size_t)st.B * ng + st.A].x, gd = g[(size_t)(N + st.B) * ng + (N + st.A)].x;
+        const double hu = dl - tU[idx], hd = dl - tD[idx];                      // <c^+_A c_B> per spin
+        const double nuA = ob[st.A], ndA = ob[N + st.A], nuB = ob[2 * N + st.B], ndB = ob[3 * N + st.B];
+        const double conn = hu * gu + hd * gd;
+        w[0] += gu;
+        w[1] += gd;
+        w[2] += (nuA + ndA) * (nuB + ndB) + conn;
+        w[3] += 0.25 * ((nuA - ndA) * (nuB - ndB) + conn);
+        w[4] += 0.25 * (hu * gd + hd * gu);
+        w[5] += gu * gd;
+        if (!TD) {
+            w[NCH - 2] += 0.25 * gu * sS[idx];
+            w[NCH - 1] += 0.25 * gu * sD[idx];
+        }
+    }
+    double* dst = TD ? acc + rows + (size_t)row * NCH * N : acc + 1;
+    bw.reduce_add(w, red, NCH, dst, N, 1, TD ? acc + row : acc);
+}
+void launch_hubbard_eq_corr(const Launch& lc, const DevModel& hm, const cplx* G, const double* sc, size_t scs, double* acc, size_t acs) {
+    const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
+    hipLaunchKernelGGL(k_hubbard_corr<0>, grid, block, 0, lc.st, hm, G, sc, acc, 0, 1, lc.cs, scs, acs);
+}
+void launch_hubbard_td_corr(const Launch& lc, const DevModel& hm, const cplx* GT0, const double* sc, size_t scs, double* acc, size_t acs,
+                            int row, int rows) {
+    const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
+    hipLaunchKernelGGL(k_hubbard_corr<1>, grid, block, 0, lc.st, hm, GT0, sc, acc, row, rows, lc.cs, scs, acs);
 }

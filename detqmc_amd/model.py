@@ -101,7 +101,9 @@ BAND_EQ_CORRELATORS = {"bandDiffCorr": 38, "bandMixCorr": 39, "bandDiffSq": 40, 
 def structure_factor(c, L):
     """S(q) = sum_d cos(q . d) C(d) of an equal-time correlator C over the periodic site differences (last axis, index dy L + dx):
     last axis of the result = qy L + qx, q = 2 pi (qx, qy) / L.  The sum the '...Sq' observables are formed with, for averages of
-    '...Corr' a user keeps; leading axes are kept."""
+    '...Corr' a user keeps; leading axes are kept.  It serves any C(d) in this layout, the Hubbard replica's included:
+    structure_factor(hub.observable_vector("spinZZCorr"), L)[(L // 2) * L + L // 2] is the antiferromagnetic S(pi, pi),
+    1 - structure_factor(hub.observable_vector("greenUpCorr"), L) is n_up(k)."""
     c = np.asarray(c, dtype=np.float64)
     L = int(L)
     x = np.arange(L * L) % L
@@ -635,6 +637,25 @@ class KernelContext:
     def measure_eq_band_read(self):
         """the selected chain's equal-time band block: [count, bandDiff[N], bandMix[N]], raw sums, index dy L + dx"""
         return self._read_block(self.lib.dqmc_measure_eq_band_accum_size, self.lib.dqmc_measure_eq_band_read_host)
+
+    def hubbard_set_equal_time_correlators(self, on=True):
+        """Hubbard model: while on, every measure_slice also bins the eight equal-time correlators of the slice's own G into a block of
+        their own (the first enable allocates it)"""
+        check(self.lib.dqmc_hubbard_set_equal_time_correlators(self.h, int(on)))
+
+    def hubbard_eq_read(self):
+        """the selected chain's block: [count, greenUp[N], greenDn[N], charge[N], spinZZ[N], spinXX[N], pairS[N], pairSx[N], pairD[N]],
+        raw sums over B of X(B (+) d, B), index dy L + dx; C(d) = sum / (count N)"""
+        return self._read_block(self.lib.dqmc_hubbard_eq_accum_size, self.lib.dqmc_hubbard_eq_read_host)
+
+    def hubbard_measure_timedisplaced(self, j):
+        """Hubbard model: the six time-displaced correlators of boundary j from G(tau,0), G(0,tau), G(tau), G(0) into their block (call it
+        right after the advance that ended on boundary j, with set_timedisplaced on)"""
+        check(self.lib.dqmc_hubbard_measure_timedisplaced(self.h, j))
+
+    def hubbard_td_read(self):
+        """count[n-1], then per boundary [greenUp, greenDn, charge, spinZZ, spinXX, pairS][N], raw sums"""
+        return self._read_block(self.lib.dqmc_hubbard_td_accum_size, self.lib.dqmc_hubbard_td_read_host)
 
     def measure_timedisplaced(self, j):
         check(self.lib.dqmc_measure_timedisplaced(self.h, j))
@@ -1898,6 +1919,22 @@ class HubbardParams:
     simindex: int = 0
     device: int = 0
     stabilisation: str = "svd"
+    equalTimeCorrelators: bool = False        # measurement sweeps also bin the '...Corr' observables on every time slice
+    timeDisplacedCorrelators: bool = False    # ... and the '...Tau' observables at the interior boundaries tau_j = j s dtau
+
+
+# DetHubbard.observable_vector: row of the equal-time block (N,) / of every boundary's rows of the time-displaced block (n-1, N)
+HUBBARD_EQ_CORRELATORS = {"greenUpCorr": 0, "greenDnCorr": 1, "chargeCorr": 2, "spinZZCorr": 3, "spinXXCorr": 4, "pairSCorr": 5,
+                          "pairSxCorr": 6, "pairDCorr": 7}
+HUBBARD_TD_CORRELATORS = {"greenUpTau": 0, "greenDnTau": 1, "chargeTau": 2, "spinZZTau": 3, "spinXXTau": 4, "pairSTau": 5}
+
+
+def _hubbard_host_params(pars: HubbardParams):
+    """the dethubbard_params that DetHubbard hands to dethubbard_create"""
+    flags = (_lib.DETHUBBARD_MEASURE_EQ if pars.equalTimeCorrelators else 0) | (_lib.DETHUBBARD_MEASURE_TD if pars.timeDisplacedCorrelators else 0)
+    return _lib.dethubbard_params(L=pars.L, d=pars.d, m=pars.m, s=pars.s, checkerboard=int(pars.checkerboard), device=pars.device,
+                                  simindex=pars.simindex, rngSeed=pars.rngSeed, stabilisation=STABILISATION[pars.stabilisation],
+                                  measureFlags=flags, beta=pars.beta, dtau=pars.dtau, t=pars.t, U=pars.U, mu=pars.mu)
 
 
 class DetHubbard(_GreenCheck):
@@ -1909,9 +1946,7 @@ class DetHubbard(_GreenCheck):
     def __init__(self, pars: HubbardParams, nchains=1):
         self.lib = load()
         self.pars = pars
-        p = _lib.dethubbard_params(L=pars.L, d=pars.d, m=pars.m, s=pars.s, checkerboard=int(pars.checkerboard), device=pars.device,
-                                   simindex=pars.simindex, rngSeed=pars.rngSeed, stabilisation=STABILISATION[pars.stabilisation],
-                                   beta=pars.beta, dtau=pars.dtau, t=pars.t, U=pars.U, mu=pars.mu)
+        p = _hubbard_host_params(pars)
         h = C.c_void_p()
         check(self.lib.dethubbard_create(C.byref(p), nchains, C.byref(h)), host="hubbard")
         self.h = h
@@ -1976,6 +2011,28 @@ class DetHubbard(_GreenCheck):
         out = np.zeros(self.info.N)
         check(self.lib.dethubbard_get_zcorr(self.h, out.ctypes.data_as(_lib._DP)), host="hubbard")
         return out
+
+    def observable_vector(self, name):
+        """C(d) of the last measurement sweep, selected chain, index dy L + dx over the periodic site differences.
+        HubbardParams.equalTimeCorrelators: 'greenUpCorr', 'greenDnCorr', 'chargeCorr', 'spinZZCorr', 'spinXXCorr', 'pairSCorr', 'pairSxCorr',
+        'pairDCorr', shape (N,), averaged over the m time slices.  HubbardParams.timeDisplacedCorrelators: 'greenUpTau', 'greenDnTau',
+        'chargeTau', 'spinZZTau', 'spinXXTau', 'pairSTau', shape (n-1, N), rows = tau_grid().  structure_factor(c, L) turns either into
+        S(q) (e.g. the antiferromagnetic S(pi, pi) from 'spinZZCorr', n(k) from 'greenUpCorr')."""
+        i = self.info
+        if name in HUBBARD_EQ_CORRELATORS:
+            out = np.zeros((8, i.N))
+            check(self.lib.dethubbard_get_eq_correlators(self.h, out.ctypes.data_as(_lib._DP)), host="hubbard")
+            return out[HUBBARD_EQ_CORRELATORS[name]].copy()
+        if name in HUBBARD_TD_CORRELATORS:
+            out = np.zeros((i.n - 1, 6, i.N))
+            check(self.lib.dethubbard_get_td_correlators(self.h, out.ctypes.data_as(_lib._DP)), host="hubbard")
+            return out[:, HUBBARD_TD_CORRELATORS[name], :].copy()
+        raise KeyError(name)
+
+    def tau_grid(self):
+        """tau_j = j s dtau, j = 1 .. n-1: the rows of the '...Tau' observables"""
+        i = self.info
+        return np.arange(1, i.n) * (i.s * i.dtau)
 
     def rand01(self):
         return self.lib.dethubbard_rng_rand01(self.h)

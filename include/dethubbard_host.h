@@ -30,10 +30,17 @@ typedef struct dethubbard_params {
     int32_t simindex;
     uint32_t rngSeed;
     int32_t stabilisation;       /* DQMC_STAB_SVD (as the reference) or DQMC_STAB_QR */
-    int32_t reserved;
+    int32_t measureFlags;        /* DETHUBBARD_MEASURE_* bits; 0: the eight scalars and zcorr only.  Any other bit: ParameterWrong */
     double beta, dtau;
     double t, U, mu;
 } dethubbard_params;
+
+/* dethubbard_params::measureFlags (the word was `reserved`: same offset and size, 0 = what it always meant).
+ * _EQ: a measurement sweep also bins the equal-time correlators of dqmc_hubbard_set_equal_time_correlators on all m slices.
+ * _TD: the kernel context is created with the time-displaced reservation, and a measurement sweep computes G(tau_j,0), G(0,tau_j),
+ *      G(0) at every interior boundary j = 1 .. n-1 of its direction and bins dqmc_hubbard_measure_timedisplaced(j) there.
+ * Neither changes the Markov chain, the eight scalars or zcorr; thermalisation sweeps launch nothing new. */
+enum { DETHUBBARD_MEASURE_EQ = 1, DETHUBBARD_MEASURE_TD = 2 };
 
 /* obsScalar of DetHubbard (src/dethubbard.cpp:85-93), valid after dethubbard_sweep(r, 1) */
 typedef struct dethubbard_observables {
@@ -62,6 +69,11 @@ int dethubbard_get_auxfield(dethubbard_replica* r, double* out);
 int dethubbard_get_green(dethubbard_replica* r, double* gUp, double* gDn);
 int dethubbard_get_observables(dethubbard_replica* r, dethubbard_observables* out);
 int dethubbard_get_zcorr(dethubbard_replica* r, double* out /* [N] */);
+/* Normalised correlators C_X(d) = sum / (count N) of the last measurement sweep, selected chain, index dy L + dx (dqmc_hip.h: Hubbard
+ * model).  Equal time: greenUp, greenDn, charge, spinZZ, spinXX, pairS, pairSx, pairD; time-displaced: the first six at tau_j = j s dtau,
+ * j = 1 .. n-1.  DQMC_EINVAL without the flag or before a measurement sweep. */
+int dethubbard_get_eq_correlators(dethubbard_replica* r, double* out /* [8][N] */);
+int dethubbard_get_td_correlators(dethubbard_replica* r, double* out /* [n-1][6][N] */);
 /* Checkpoint / resume (what DetQMC::saveState keeps for the replica: auxfield, src/dethubbard.h:352-358, plus the position of
  * the random stream); dethubbard_load_state needs a replica created with the same parameters and rebuilds UdV storage and G(beta)
  * like the reference's loadContents does (src/dethubbard.h:345-350) */

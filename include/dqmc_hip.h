@@ -119,7 +119,9 @@ typedef struct dqmc_params {
                               1 | DQMC_TD_EVERY_SLICE, 2 | DQMC_TD_EVERY_SLICE: everything the low value reserves with the same layout,
                               launches and results, and behind every other buffer (those of td_particle_hole included) three work
                               matrices and one every-slice accumulator block per enabled channel (the struct has no free slot: the
-                              option travels as a flag bit).  Any other value, any other bit: DQMC_EINVAL */
+                              option travels as a flag bit).  Any other value, any other bit: DQMC_EINVAL.  DQMC_MODEL_HUBBARD accepts
+                              timedisplaced = 1 together with td_particle_hole = 1 and nothing else: the matrices of G(tau,0), G(0,tau),
+                              G(0), one scratch matrix and the block of dqmc_hubbard_measure_timedisplaced, behind every other buffer */
     dqmc_tuning tuning;   /* all zero = automatic */
     int32_t td_particle_hole; /* 1 (needs timedisplaced >= 1, SDW model; DQMC_EINVAL otherwise): also reserve, behind every other buffer,
                                  the equal-time G(0) of the boundary's own field configuration, one matrix for a shifted copy, the
@@ -417,6 +419,31 @@ int dqmc_measure_eq_read_host(dqmc_ctx* ctx, double* out);   /* selected chain; 
 int dqmc_set_equal_time_band(dqmc_ctx* ctx, int on);
 size_t dqmc_measure_eq_band_accum_size(dqmc_ctx* ctx);  /* 0 before the first enable, else 1 + 2 N */
 int dqmc_measure_eq_band_read_host(dqmc_ctx* ctx, double* out);   /* selected chain; DQMC_EINVAL before the first enable */
+/* ---- Hubbard model: equal-time and time-displaced correlators -----------------------
+ * G_s(A, B) = <c_As c^+_Bs> is spin block s of the context's G (0 up, 1 down), real parts; sites A = y L + x; A = B (+) d periodic, bin
+ * dy L + dx.  n_s = c^+_s c_s, n = n_up + n_dn, S^z = (n_up - n_dn) / 2; pair operators Delta_A = c_Aup c_Adn and
+ * Delta^f_A = 1/2 sum_dl f_dl c_Aup c_(A+dl)dn over the four neighbours, f = +1 (extended s) or +1 on +-x, -1 on +-y (d wave).
+ * Every block holds raw sums over B of X(B (+) d, B) per configuration and a sample counter: C_X(d) = sum / (count N).
+ * Equal time -- a switch of dqmc_measure_slice: while on, every dqmc_measure_slice also bins, from the slice's own unshifted G,
+ *   0 greenUp G_up(A,B)   1 greenDn G_dn(A,B)   2 charge <n_A n_B>   3 spinZZ <S^z_A S^z_B>   4 spinXX 1/4 <S^+_A S^-_B + S^-_A S^+_B>
+ *   5 pairS <Delta_A Delta^+_B>   6 pairSx, 7 pairD <Delta^f_A Delta^f+_B>
+ * with <c^+_As c_Bs> = delta_AB - G_s(B,A), <n_As n_Bs'> = <n_As><n_Bs'> + delta_ss' <c^+_As c_Bs> G_s(A,B),
+ * <S^+_A S^-_B> = <c^+_Aup c_Bup> G_dn(A,B), <Delta_A Delta^+_B> = G_up(A,B) G_dn(A,B) and
+ * <Delta^f_A Delta^f+_B> = 1/4 sum_{dl,dl'} f_dl f_dl' G_up(A,B) G_dn(A+dl, B+dl').  Block of one chain: count, then [8][N]
+ * (dqmc_hubbard_eq_accum_size = 1 + 8 N doubles), allocated for all chains outside the arena by the first enable, freed with the
+ * context, cleared by dqmc_measure_reset.  The block of dqmc_measure_read_host is the same either way.
+ * Time-displaced -- context created with timedisplaced = 1 and td_particle_hole = 1 (the only values a Hubbard context accepts besides
+ * 0, 0): dqmc_hubbard_measure_timedisplaced(ctx, j), right after the advance that ended on boundary j while dqmc_set_timedisplaced is
+ * on, bins channels 0 .. 5 as <O_A(tau_j) O^+_B(0)> from G(tau,0), G(0,tau), G(tau), G(0) (conventions below): the equal-time forms with
+ * G_s(A,B) -> G(tau,0)_s(A,B), <c^+_As c_Bs> -> -G(0,tau)_s(B,A), <n_As> from G(tau), <n_Bs> from G(0).  Block: count[n-1], then
+ * [n-1][6][N].  All chains in one launch each; one writer per accumulator, fixed summation order, bit-reproducible.
+ * DQMC_EINVAL: an SDW context; the time-displaced entries without the reservation or away from boundary j. */
+int dqmc_hubbard_set_equal_time_correlators(dqmc_ctx* ctx, int on);
+size_t dqmc_hubbard_eq_accum_size(dqmc_ctx* ctx);       /* 0 before the first enable */
+int dqmc_hubbard_eq_read_host(dqmc_ctx* ctx, double* out);   /* selected chain */
+int dqmc_hubbard_measure_timedisplaced(dqmc_ctx* ctx, int j);
+size_t dqmc_hubbard_td_accum_size(dqmc_ctx* ctx);       /* 0 without the reservation */
+int dqmc_hubbard_td_read_host(dqmc_ctx* ctx, double* out);   /* selected chain */
 /* ---- time-displaced Green's functions ----------------------------------------------------------
  * At an interior stabilisation boundary tau_j = j s (j = 1 .. n-1) the advance holds B(tau,0) = U_r D_r V_r^H and
  * B(beta,tau) = U_l D_l V_l^H at once.  With the scales split into their parts > 1 and <= 1 and
