@@ -34,6 +34,10 @@ DQMC_SERIES_MATS_CUSTOM, DQMC_SERIES_EQ_CUSTOM = 512, 1024   # ... Matsubara tra
 DQMC_SERIES_MATS_CUSTOM_PAIR, DQMC_SERIES_EQ_CUSTOM_PAIR = 2048, 4096   # ... Matsubara transform of channel 6, equal-time block of the custom pair operators
 DQMC_SERIES_GREEN_MATRIX = 8192    # ... the normalised averaged Green's function of every slice (dqmc_set_green_matrix)
 DQMC_CUSTOM_MAX = 4               # matrices of dqmc_set_custom_bilinears at most
+# detsdw_observable_desc: family and kind of an observable index (detsdw_describe_observable)
+DETSDW_OBS_FAMILY_SLICE, DETSDW_OBS_FAMILY_EQ, DETSDW_OBS_FAMILY_TD, DETSDW_OBS_FAMILY_PHI = 0, 1, 2, 3
+(DETSDW_OBS_KIND_SITE, DETSDW_OBS_KIND_TAU, DETSDW_OBS_KIND_TAU_Q0, DETSDW_OBS_KIND_ROW_SCALAR, DETSDW_OBS_KIND_CORR, DETSDW_OBS_KIND_SQ,
+ DETSDW_OBS_KIND_GREEN_MATRIX, DETSDW_OBS_KIND_PHI_CHI, DETSDW_OBS_KIND_PHI_SCALARS) = range(9)
 
 
 class dqmc_cplx(C.Structure):
@@ -128,6 +132,11 @@ class detsdw_info(C.Structure):
                 ("phiDelta", C.c_double), ("lastAccRatioLocal_phi", C.c_double), ("r", C.c_double),
                 ("angleDelta", C.c_double), ("scaleDelta", C.c_double),
                 ("rngDrawn", C.c_uint64)]
+
+
+class detsdw_observable_desc(C.Structure):
+    _fields_ = [(f, C.c_int32) for f in ("family", "block", "component", "kind", "fine", "has_fine_twin", "has_matsubara",
+                                          "series_part", "series_bit")]
 
 
 class detsdw_observables(C.Structure):
@@ -333,6 +342,7 @@ SYMBOLS = [
     ("detsdw_get_info", C.c_int, [_P, C.POINTER(detsdw_info)]),
     ("detsdw_get_observables", C.c_int, [_P, C.POINTER(detsdw_observables)]),
     ("detsdw_get_observable_vector", C.c_int, [_P, C.c_int, _DP]),
+    ("detsdw_describe_observable", C.c_int, [C.c_int, C.POINTER(detsdw_observable_desc)]),
     ("detsdw_get_matsubara", C.c_int, [_P, C.c_int, C.c_int, _DP]),
     ("detsdw_get_matsubara_all", C.c_int, [_P, C.c_int, C.c_int, _DP]),
     ("detsdw_series_begin", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -45,6 +45,7 @@ def build(force=False, verbose=True):
     objdir = os.path.join(LIBDIR, "obj")
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, "dqmc_internal.h"), os.path.join(CSRC, "dqmc_ctx.h"), os.path.join(CSRC, "bin_walk.h"), os.path.join(CSRC, "host", "detsdw.h"),
+               os.path.join(CSRC, "host", "obs_catalogue.h"),
                os.path.join(CSRC, "host", "dsfmt19937.h"),
                os.path.join(CSRC, "host", "dethubbard.h"),
                os.path.join(HERE, "..", "include", "dqmc_hip.h"), os.path.join(HERE, "..", "include", "detsdw_host.h"),

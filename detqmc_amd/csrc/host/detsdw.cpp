@@ -484,8 +484,10 @@ void DetSDW::finishFermionic(int b) {
     o.greenK0 = acc[0] / double(m);
     o.greenLocal = acc[1] / double(m);
     o.occDiffSq = acc[2] / double(m);
-    c.pairPlus.assign(N, 0.0); c.pairMinus.assign(N, 0.0); c.kOccX.assign(N, 0.0); c.kOccY.assign(N, 0.0);
-    for (int i = 0; i < N; ++i) { c.pairPlus[i] = acc[4 + i] / m; c.pairMinus[i] = acc[4 + N + i] / m; }
+    std::vector<double>& kOccX = c.slice[DETSDW_OBS_KOCCX]; std::vector<double>& kOccY = c.slice[DETSDW_OBS_KOCCY];
+    std::vector<double>& pairPlus = c.slice[DETSDW_OBS_PAIRPLUS]; std::vector<double>& pairMinus = c.slice[DETSDW_OBS_PAIRMINUS];
+    pairPlus.assign(N, 0.0); pairMinus.assign(N, 0.0); kOccX.assign(N, 0.0); kOccY.assign(N, 0.0);
+    for (int i = 0; i < N; ++i) { pairPlus[i] = acc[4 + i] / m; pairMinus[i] = acc[4 + N + i] / m; }
     // momentum-space occupation: Fourier sum over the (2L-1)^2 site-difference bins, k offset by half a step along
     // antiperiodic directions (:616-659)
     const int W = 2 * L - 1, nbins = W * W;
@@ -514,32 +516,23 @@ void DetSDW::finishFermionic(int b) {
             sx += cs * S[0][2 * bin] - sn * S[0][2 * bin + 1];
             sy += cs * S[1][2 * bin] - sn * S[1][2 * bin + 1];
         }
-        c.kOccX[ksite] = 2.0 - sx / double(m * N);      // 2.0: spin included (:938-941)
-        c.kOccY[ksite] = 2.0 - sy / double(m * N);
+        kOccX[ksite] = 2.0 - sx / double(m * N);      // 2.0: spin included (:938-941)
+        kOccY[ksite] = 2.0 - sy / double(m * N);
     }
     // pairing correlations at maximum distance: the 3 x 3 sites around (L/2, L/2) (:986-1002)
     double pp = 0.0, pm = 0.0;
     for (int oy = -1; oy <= 1; ++oy)
         for (int ox = -1; ox <= 1; ++ox) {
             const int i = (L / 2 + oy) * L + (L / 2 + ox);
-            pp += c.pairPlus[i]; pm += c.pairMinus[i];
+            pp += pairPlus[i]; pm += pairMinus[i];
         }
     o.pairPlusMax = pp / 9.0;
     o.pairMinusMax = pm / 9.0;
     // equal-time correlators: C(d) = sum / (count N), and S(q) = sum_d cos(q d) C(d), the real part of the Fourier sum
     if (eq_correlators(c.pars) && !seriesNoHostCopy()) {
-        std::vector<double> eq(dqmc_measure_eq_accum_size(ctx_));
-        check(dqmc_measure_eq_read_host(ctx_, eq.data()), "dqmc_measure_eq_read_host");
-        if ((int)eq[0] != m) throw GeneralError(DQMC_EINVAL, "measurement sweep did not visit every time slice (equal-time correlators)");
         // separable: cos(qx dx + qy dy) = cos cos - sin sin, phases 2 pi (q d mod L) / L from two tables -- O(N L) per channel
         std::vector<double> ct(L), st(L), Ac((size_t)N), As((size_t)N);
         for (int j = 0; j < L; ++j) { ct[j] = std::cos(2.0 * pi * double(j) / double(L)); st[j] = std::sin(2.0 * pi * double(j) / double(L)); }
-        std::vector<double> eqb;
-        if (eq_band(c.pars)) {
-            eqb.resize(dqmc_measure_eq_band_accum_size(ctx_));
-            check(dqmc_measure_eq_band_read_host(ctx_, eqb.data()), "dqmc_measure_eq_band_read_host");
-            if ((int)eqb[0] != m) throw GeneralError(DQMC_EINVAL, "measurement sweep did not visit every time slice (equal-time band correlators)");
-        }
         // one channel: the raw sums src [N] of a block with `cnt` samples -> C(d) and S(q)
         auto form = [&](const double* src, double cnt, std::vector<double>& corr, std::vector<double>& sqv) {
             corr.assign(N, 0.0); sqv.assign(N, 0.0);
@@ -560,19 +553,21 @@ void DetSDW::finishFermionic(int b) {
                     sqv[(size_t)qy * L + qx] = sq;
                 }
         };
-        for (int ch = 0; ch < (eqb.empty() ? 5 : 7); ++ch)       // 5, 6: bandDiff, bandMix from the block of their own
-            form(ch < 5 ? &eq[1 + (size_t)ch * N] : &eqb[1 + (size_t)(ch - 5) * N], ch < 5 ? eq[0] : eqb[0], c.eqCorr[ch], c.eqSq[ch]);
-        if (customEq()) {                                        // the user-defined bilinears, from theirs
-            std::vector<double> eqc(dqmc_measure_eq_custom_accum_size(ctx_));
-            check(dqmc_measure_eq_custom_read_host(ctx_, eqc.data()), "dqmc_measure_eq_custom_read_host");
-            if ((int)eqc[0] != m) throw GeneralError(DQMC_EINVAL, "measurement sweep did not visit every time slice (equal-time custom bilinears)");
-            for (int ch = 0; ch < customCount(); ++ch) form(&eqc[1 + (size_t)ch * N], eqc[0], c.customCorr[ch], c.customSq[ch]);
-        }
-        if (customPairEq()) {                                    // the user-defined pair operators, from theirs
-            std::vector<double> eqp(dqmc_measure_eq_custom_pair_accum_size(ctx_));
-            check(dqmc_measure_eq_custom_pair_read_host(ctx_, eqp.data()), "dqmc_measure_eq_custom_pair_read_host");
-            if ((int)eqp[0] != m) throw GeneralError(DQMC_EINVAL, "measurement sweep did not visit every time slice (equal-time custom pair operators)");
-            for (int ch = 0; ch < pairCount(); ++ch) form(&eqp[1 + (size_t)ch * N], eqp[0], c.customPairCorr[ch], c.customPairSq[ch]);
+        // the four blocks (fixed channels, band, user-defined bilinears, user-defined pair operators): count, then [components][N] raw sums
+        struct EqBlock { size_t (*size)(dqmc_ctx*); int (*read)(dqmc_ctx*, double*); const char* name; const char* missing; };
+        static const EqBlock blocks[kEqBlocks] = {
+            {dqmc_measure_eq_accum_size, dqmc_measure_eq_read_host, "dqmc_measure_eq_read_host", "measurement sweep did not visit every time slice (equal-time correlators)"},
+            {dqmc_measure_eq_band_accum_size, dqmc_measure_eq_band_read_host, "dqmc_measure_eq_band_read_host", "measurement sweep did not visit every time slice (equal-time band correlators)"},
+            {dqmc_measure_eq_custom_accum_size, dqmc_measure_eq_custom_read_host, "dqmc_measure_eq_custom_read_host", "measurement sweep did not visit every time slice (equal-time custom bilinears)"},
+            {dqmc_measure_eq_custom_pair_accum_size, dqmc_measure_eq_custom_pair_read_host, "dqmc_measure_eq_custom_pair_read_host", "measurement sweep did not visit every time slice (equal-time custom pair operators)"}};
+        std::vector<double> eq;
+        for (const ObsRow& r : kObsRows) {
+            if (r.family != DETSDW_OBS_FAMILY_EQ || r.kind != DETSDW_OBS_KIND_CORR || !has(r.needs)) continue;    // the SQ row shares the block
+            const EqBlock& blk = blocks[r.block];
+            eq.resize(blk.size(ctx_));
+            check(blk.read(ctx_, eq.data()), blk.name);
+            if ((int)eq[0] != m) throw GeneralError(DQMC_EINVAL, blk.missing);
+            for (int ch = 0; ch < live(r); ++ch) form(&eq[1 + (size_t)ch * N], eq[0], c.eq[r.block][ch].corr, c.eq[r.block][ch].sq);
         }
     }
     // Time-displaced observables from one family of blocks: the coarse one (rows = interior boundaries j = 1 .. n-1) or, with
@@ -583,7 +578,7 @@ void DetSDW::finishFermionic(int b) {
                                    : "measurement sweep did not visit every stabilisation boundary";
         // the coarse blocks' (size, read) entry points by channel; the fine blocks share one pair that takes the channel
         struct Coarse { size_t (*size)(dqmc_ctx*); int (*read)(dqmc_ctx*, double*); const char* name; };
-        static const Coarse coarse[8] = {{dqmc_measure_td_accum_size, dqmc_measure_td_read_host, "dqmc_measure_td_read_host"},
+        static const Coarse coarse[kTdChannels] = {{dqmc_measure_td_accum_size, dqmc_measure_td_read_host, "dqmc_measure_td_read_host"},
                                          {dqmc_measure_td_pair_accum_size, dqmc_measure_td_pair_read_host, "dqmc_measure_td_pair_read_host"},
                                          {dqmc_measure_td_ph_accum_size, dqmc_measure_td_ph_read_host, "dqmc_measure_td_ph_read_host"},
                                          {dqmc_measure_td_current_accum_size, dqmc_measure_td_current_read_host, "dqmc_measure_td_current_read_host"},
@@ -596,11 +591,9 @@ void DetSDW::finishFermionic(int b) {
             if (fine) check(dqmc_measure_td_fine_read_host(ctx_, channel, buf.data()), "dqmc_measure_td_fine_read_host");
             else check(coarse[channel].read(ctx_, buf.data()), coarse[channel].name);
         };
-        // G(k, tau) from the time-displaced bins: the same Fourier sum as kOcc, one row per tau
-        {
-            std::vector<double> td;
-            read(0, td);
-            t.greenKTauX.assign((size_t)rows * N, 0.0); t.greenKTauY.assign((size_t)rows * N, 0.0);
+        // channel 0 -- G(k, tau) from the time-displaced bins: the same Fourier sum as kOcc, one row per tau
+        auto formGreenK = [&](const std::vector<double>& td, std::vector<TdComp>& bands) {
+            for (TdComp& band : bands) band.val.assign((size_t)rows * N, 0.0);
             // separable: A(kx, dy) = sum_dx e^{i kx dx} S(dx, dy) first, then Re sum_dy e^{i ky dy} A(kx, dy)
             std::vector<double> A((size_t)L * W * 2);
             for (int r = 0; r < rows; ++r) {
@@ -620,7 +613,7 @@ void DetSDW::finishFermionic(int b) {
                             A[((size_t)kx * W + iy) * 2] = re; A[((size_t)kx * W + iy) * 2 + 1] = im;
                         }
                     }
-                    std::vector<double>& out = band == 0 ? t.greenKTauX : t.greenKTauY;
+                    std::vector<double>& out = bands[band].val;
                     for (int ksite = 0; ksite < N; ++ksite) {
                         const double* ty = &ey[(size_t)(ksite / L) * W * 2];
                         const double* a = &A[(size_t)(ksite % L) * W * 2];
@@ -630,124 +623,43 @@ void DetSDW::finishFermionic(int b) {
                     }
                 }
             }
-        }
-        // pairing correlators: translation average (1 / N) and sample count; the q = 0 sums are the plain row sums
-        if (td_level(c.pars) == 2) {
-            std::vector<double> tp;
-            read(1, tp);
-            t.pairPlusTau.assign((size_t)rows * N, 0.0); t.pairMinusTau.assign((size_t)rows * N, 0.0);
-            t.pairPlusTauQ0.assign(rows, 0.0); t.pairMinusTauQ0.assign(rows, 0.0);
-            for (int r = 0; r < rows; ++r) {
-                const double cnt = tp[r];
-                if (cnt < 1.0) throw GeneralError(DQMC_EINVAL, missing);
-                const double* T = &tp[rows + (size_t)r * 2 * N];
-                double qp = 0.0, qm = 0.0;
-                for (int d = 0; d < N; ++d) {
-                    const double vp = T[d] / (double(N) * cnt), vm = T[N + d] / (double(N) * cnt);
-                    t.pairPlusTau[(size_t)r * N + d] = vp; t.pairMinusTau[(size_t)r * N + d] = vm;
-                    qp += vp; qm += vm;
-                }
-                t.pairPlusTauQ0[r] = qp; t.pairMinusTauQ0[r] = qm;
+        };
+        // channels 1 .. 6 -- pairing, particle-hole, current, band, user-defined bilinears and pair operators: per tau `nc` rows of N raw
+        // sums and `nscal` trailing scalars (the bond kinetic energy of the current channel).  Translation average (1 / N) and sample
+        // count; the q = 0 sums are the plain row sums
+        auto normalise = [&](const std::vector<double>& tb, int nc, int nscal, std::vector<TdComp>& out) {
+            for (int ch = 0; ch < nc; ++ch) {
+                out[ch].val.assign((size_t)rows * N, 0.0); out[ch].q0.assign(rows, 0.0);
+                if (ch < nscal) out[ch].scalar.assign(rows, 0.0);
             }
-        }
-        // particle-hole correlators (charge, spinZ, sdw): the same normalisation
-        if (ph_level(c.pars)) {
-            std::vector<double> tp;
-            read(2, tp);
-            for (int ch = 0; ch < 3; ++ch) { t.phTau[ch].assign((size_t)rows * N, 0.0); t.phTauQ0[ch].assign(rows, 0.0); }
-            for (int r = 0; r < rows; ++r) {
-                const double cnt = tp[r];
-                if (cnt < 1.0) throw GeneralError(DQMC_EINVAL, missing);
-                for (int ch = 0; ch < 3; ++ch) {
-                    const double* T = &tp[rows + ((size_t)r * 3 + ch) * N];
-                    double q = 0.0;
-                    for (int d = 0; d < N; ++d) {
-                        const double v = T[d] / (double(N) * cnt);
-                        t.phTau[ch][(size_t)r * N + d] = v;
-                        q += v;
-                    }
-                    t.phTauQ0[ch][r] = q;
-                }
-            }
-        }
-        // current-current correlators and the bond kinetic energy: the same normalisation
-        if (ph_level(c.pars) == 2) {
-            std::vector<double> tc;
-            read(3, tc);
-            for (int mu = 0; mu < 2; ++mu) {
-                t.currentTau[mu].assign((size_t)rows * N, 0.0); t.currentTauQ0[mu].assign(rows, 0.0); t.bondKinetic[mu].assign(rows, 0.0);
-            }
-            for (int r = 0; r < rows; ++r) {
-                const double cnt = tc[r];
-                if (cnt < 1.0) throw GeneralError(DQMC_EINVAL, missing);
-                const double* blk = &tc[rows + (size_t)r * (2 * (size_t)N + 2)];
-                for (int mu = 0; mu < 2; ++mu) {
-                    double q = 0.0;
-                    for (int d = 0; d < N; ++d) {
-                        const double v = blk[(size_t)mu * N + d] / (double(N) * cnt);
-                        t.currentTau[mu][(size_t)r * N + d] = v;
-                        q += v;
-                    }
-                    t.currentTauQ0[mu][r] = q;
-                    t.bondKinetic[mu][r] = blk[2 * (size_t)N + mu] / (double(N) * cnt);
-                }
-            }
-        }
-        // band-resolved charge correlators (bandDiff, bandMix): the normalisation of the particle-hole channels
-        if (td_band(c.pars)) {
-            std::vector<double> tb;
-            read(4, tb);
-            for (int ch = 0; ch < 2; ++ch) { t.bandTau[ch].assign((size_t)rows * N, 0.0); t.bandTauQ0[ch].assign(rows, 0.0); }
             for (int r = 0; r < rows; ++r) {
                 const double cnt = tb[r];
                 if (cnt < 1.0) throw GeneralError(DQMC_EINVAL, missing);
-                for (int ch = 0; ch < 2; ++ch) {
-                    const double* T = &tb[rows + ((size_t)r * 2 + ch) * N];
-                    double q = 0.0;
-                    for (int d = 0; d < N; ++d) {
-                        const double v = T[d] / (double(N) * cnt);
-                        t.bandTau[ch][(size_t)r * N + d] = v;
-                        q += v;
-                    }
-                    t.bandTauQ0[ch][r] = q;
-                }
-            }
-        }
-        // user-defined bilinears (channel 5) and pair operators (channel 6): the same normalisation, `count` rows of N per tau
-        auto fillCustom = [&](int channel, int nc, std::vector<double>* tau, std::vector<double>* tauQ0) {
-            std::vector<double> tb;
-            read(channel, tb);
-            for (int ch = 0; ch < nc; ++ch) { tau[ch].assign((size_t)rows * N, 0.0); tauQ0[ch].assign(rows, 0.0); }
-            for (int r = 0; r < rows; ++r) {
-                const double cnt = tb[r];
-                if (cnt < 1.0) throw GeneralError(DQMC_EINVAL, missing);
+                const double* blk = &tb[rows + (size_t)r * ((size_t)nc * N + nscal)];
                 for (int ch = 0; ch < nc; ++ch) {
-                    const double* T = &tb[rows + ((size_t)r * nc + ch) * N];
+                    const double* T = blk + (size_t)ch * N;
                     double q = 0.0;
                     for (int d = 0; d < N; ++d) {
                         const double v = T[d] / (double(N) * cnt);
-                        tau[ch][(size_t)r * N + d] = v;
+                        out[ch].val[(size_t)r * N + d] = v;
                         q += v;
                     }
-                    tauQ0[ch][r] = q;
+                    out[ch].q0[r] = q;
                 }
+                for (int ch = 0; ch < nscal; ++ch) out[ch].scalar[r] = blk[(size_t)nc * N + ch] / (double(N) * cnt);
             }
         };
-        if (customTd()) fillCustom(5, customCount(), t.customTau, t.customTauQ0);
-        if (customPairTd()) fillCustom(6, pairCount(), t.customPairTau, t.customPairTauQ0);
-        // the averaged Green's function (channel 7): the stored R x R block of every d expanded to the full 4 x 4 one -- OPDIM < 3: the
+        // channel 7 -- the averaged Green's function: the stored R x R block of every d expanded to the full 4 x 4 one -- OPDIM < 3: the
         // (XDOWN, YUP) sector is the complex conjugate of the stored one, the blocks between the sectors vanish
-        if (greenMatrix_) {
-            std::vector<double> gb;
-            read(7, gb);
+        auto formGreenMatrix = [&](const std::vector<double>& gb, std::vector<double>& full) {
             const int R = c.pars.opdim == 3 ? 4 : 2;
-            t.greenMatrixTau.assign((size_t)rows * N * 32, 0.0);
+            full.assign((size_t)rows * N * 32, 0.0);
             for (int r = 0; r < rows; ++r) {
                 const double cnt = gb[r];
                 if (cnt < 1.0) throw GeneralError(DQMC_EINVAL, missing);
                 for (int d = 0; d < N; ++d) {
                     const double* G = &gb[rows + ((size_t)r * N + d) * 2 * R * R];
-                    double* out = &t.greenMatrixTau[((size_t)r * N + d) * 32];
+                    double* out = &full[((size_t)r * N + d) * 32];
                     for (int a = 0; a < R; ++a)
                         for (int b2 = 0; b2 < R; ++b2) {
                             const double re = G[2 * (a * R + b2)] / (double(N) * cnt), im = G[2 * (a * R + b2) + 1] / (double(N) * cnt);
@@ -756,6 +668,17 @@ void DetSDW::finishFermionic(int b) {
                         }
                 }
             }
+        };
+        // every enabled channel once, in the catalogue's order: its first row names the option it needs
+        std::vector<double> buf;
+        unsigned done = 0;
+        for (const ObsRow& r : kObsRows) {
+            if (r.family != DETSDW_OBS_FAMILY_TD || (done >> r.block & 1u) || !has(r.needs)) continue;
+            done |= 1u << r.block;
+            read(r.block, buf);
+            if (r.block == kTdGreenK) formGreenK(buf, t.ch[r.block]);
+            else if (r.kind == DETSDW_OBS_KIND_GREEN_MATRIX) formGreenMatrix(buf, t.ch[r.block][0].val);
+            else normalise(buf, live(r), obs_row_scalars(r.block), t.ch[r.block]);
         }
     };
     if (td_level(c.pars)) fill(false, c.td);
@@ -772,94 +695,54 @@ void DetSDW::getTauGridFine(double* out) const {
     for (int k = 0; k <= m_; ++k) out[k] = k * ch_[0].pars.dtau;
 }
 
-void DetSDW::getObservableVector(int which_in, double* out, int b) const {
+bool DetSDW::has(ObsNeeds needs) const {
+    const detsdw_params& p = ch_[0].pars;          // the chains of a handle share every option
+    switch (needs) {
+    case ObsNeeds::Nothing: return true;
+    case ObsNeeds::TdLevel: return td_level(p) != 0;
+    case ObsNeeds::TdLevel2: return td_level(p) == 2;
+    case ObsNeeds::PhLevel: return ph_level(p) != 0;
+    case ObsNeeds::PhLevel2: return ph_level(p) == 2;
+    case ObsNeeds::TdBand: return td_band(p);
+    case ObsNeeds::EqCorrelators: return eq_correlators(p);
+    case ObsNeeds::EqBand: return eq_band(p);
+    case ObsNeeds::CustomTd: return customTd();
+    case ObsNeeds::CustomEq: return customEq();
+    case ObsNeeds::CustomPairTd: return customPairTd();
+    case ObsNeeds::CustomPairEq: return customPairEq();
+    case ObsNeeds::GreenMatrix: return greenMatrix_;
+    }
+    return false;
+}
+const std::vector<double>& DetSDW::stored(const Chain& c, const ObsRow& r, int comp, bool fine) const {
+    if (r.family == DETSDW_OBS_FAMILY_SLICE) return c.slice[comp];
+    if (r.family == DETSDW_OBS_FAMILY_EQ) return r.kind == DETSDW_OBS_KIND_SQ ? c.eq[r.block][comp].sq : c.eq[r.block][comp].corr;
+    const TdComp& t = (fine ? c.tdFine : c.td).ch[r.block][comp];
+    return r.kind == DETSDW_OBS_KIND_TAU_Q0 ? t.q0 : r.kind == DETSDW_OBS_KIND_ROW_SCALAR ? t.scalar : t.val;
+}
+void DetSDW::dropStored(int tdChannel, int eqBlock) {
+    for (auto& c : ch_) {
+        for (TdObs* t : {&c.td, &c.tdFine}) for (TdComp& v : t->ch[tdChannel]) v = TdComp{};
+        if (eqBlock >= 0) for (EqComp& e : c.eq[eqBlock]) e = EqComp{};
+    }
+}
+
+void DetSDW::getObservableVector(int which, double* out, int b) const {
     const Chain& c = ch_[b];
     if (!c.obs.fermionic_valid) throw GeneralError(DQMC_EINVAL, "no fermionic measurement has been taken");
-    const bool fine = (which_in & DETSDW_OBS_FINE) != 0;
-    const int which = which_in & ~DETSDW_OBS_FINE;
-    const bool bandTau = which >= DETSDW_OBS_BANDDIFFTAU && which <= DETSDW_OBS_BANDMIXTAU_Q0;
-    const bool customTau = which >= DETSDW_OBS_CUSTOMTAU && which < DETSDW_OBS_CUSTOMCORR;
-    const bool pairTau = which >= DETSDW_OBS_CUSTOMPAIRTAU && which < DETSDW_OBS_CUSTOMPAIRCORR;
-    const bool greenMat = which == DETSDW_OBS_GREENMATRIXTAU;
-    if (fine && (which < DETSDW_OBS_GREENKTAU_X || which > DETSDW_OBS_BONDKINETICY) && !bandTau && !customTau && !pairTau && !greenMat) throw ParameterWrong("unknown observable vector");
-    if (fine && !td_every_slice(c.pars)) throw ParameterWrong("the ...Fine observables need timeDisplacedEverySlice");
-    if (fine && td_fine_on_device(c.pars))
+    const ObsRef o = obs_lookup(which);
+    if (!o.row || o.row->family == DETSDW_OBS_FAMILY_PHI) throw ParameterWrong("unknown observable vector");
+    const ObsRow& r = *o.row;
+    if (o.fine && !td_every_slice(c.pars)) throw ParameterWrong("the ...Fine observables need timeDisplacedEverySlice");
+    if (o.fine && td_fine_on_device(c.pars))
         throw ParameterWrong("the ...Fine observables are not formed with timeDisplacedFineOnDevice: read the Matsubara transforms");
-    const TdObs& t = fine ? c.tdFine : c.td;
-    if (!fine && which >= DETSDW_OBS_CHARGECORR && which <= DETSDW_OBS_PAIRMINUSSQ) {
-        if (!eq_correlators(c.pars))
-            throw ParameterWrong("the equal-time correlators and structure factors need equalTimeCorrelators (DETSDW_FM_EQ_CORRELATORS)");
-        if (seriesNoHostCopy())
-            throw ParameterWrong("the equal-time correlators are not copied to the host while a series with DETSDW_SERIES_NO_HOST_COPY is open: read the series");
-        const std::vector<double>& e = which < DETSDW_OBS_CHARGESQ ? c.eqCorr[which - DETSDW_OBS_CHARGECORR] : c.eqSq[which - DETSDW_OBS_CHARGESQ];
-        std::memcpy(out, e.data(), e.size() * sizeof(double));
-        return;
-    }
-    if (!fine && which >= DETSDW_OBS_BANDDIFFCORR && which <= DETSDW_OBS_BANDMIXSQ) {
-        if (!eq_band(c.pars)) throw ParameterWrong("bandDiffCorr / bandMixCorr / bandDiffSq / bandMixSq need bandCorrelators with equalTimeCorrelators (DETSDW_FM_EQ_BAND)");
-        if (seriesNoHostCopy())
-            throw ParameterWrong("the equal-time correlators are not copied to the host while a series with DETSDW_SERIES_NO_HOST_COPY is open: read the series");
-        const std::vector<double>& e = which < DETSDW_OBS_BANDDIFFSQ ? c.eqCorr[5 + which - DETSDW_OBS_BANDDIFFCORR] : c.eqSq[5 + which - DETSDW_OBS_BANDDIFFSQ];
-        std::memcpy(out, e.data(), e.size() * sizeof(double));
-        return;
-    }
-    if (which >= DETSDW_OBS_CUSTOMTAU && which < DETSDW_OBS_CUSTOMSQ + DQMC_CUSTOM_MAX) {
-        const int ch = (which - DETSDW_OBS_CUSTOMTAU) % DQMC_CUSTOM_MAX;
-        if (ch >= customCount()) throw ParameterWrong("no user-defined bilinear with this index is set (detsdw_set_custom_bilinears)");
-        if (customTau ? !customTd() : !customEq())
-            throw ParameterWrong(customTau ? "custom{c}Tau needs timeDisplacedParticleHole" : "custom{c}Corr / custom{c}Sq need equalTimeCorrelators");
-        if (!customTau && seriesNoHostCopy())
-            throw ParameterWrong("the equal-time correlators are not copied to the host while a series with DETSDW_SERIES_NO_HOST_COPY is open: read the series");
-        const std::vector<double>& e = which < DETSDW_OBS_CUSTOMTAU_Q0 ? t.customTau[ch] : which < DETSDW_OBS_CUSTOMCORR ? t.customTauQ0[ch]
-                                     : which < DETSDW_OBS_CUSTOMSQ ? c.customCorr[ch] : c.customSq[ch];
-        if (e.empty()) throw GeneralError(DQMC_EINVAL, "no measurement sweep has run since the user-defined bilinears were set");
-        std::memcpy(out, e.data(), e.size() * sizeof(double));
-        return;
-    }
-    if (which >= DETSDW_OBS_CUSTOMPAIRTAU && which < DETSDW_OBS_CUSTOMPAIRSQ + DQMC_CUSTOM_MAX) {
-        const int ch = (which - DETSDW_OBS_CUSTOMPAIRTAU) % DQMC_CUSTOM_MAX;
-        if (ch >= pairCount()) throw ParameterWrong("no user-defined pair operator with this index is set (detsdw_set_custom_pair_operators)");
-        if (pairTau ? !customPairTd() : !customPairEq())
-            throw ParameterWrong(pairTau ? "customPair{c}Tau needs timeDisplacedMeasurements" : "customPair{c}Corr / customPair{c}Sq need equalTimeCorrelators");
-        if (!pairTau && seriesNoHostCopy())
-            throw ParameterWrong("the equal-time correlators are not copied to the host while a series with DETSDW_SERIES_NO_HOST_COPY is open: read the series");
-        const std::vector<double>& e = which < DETSDW_OBS_CUSTOMPAIRTAU_Q0 ? t.customPairTau[ch] : which < DETSDW_OBS_CUSTOMPAIRCORR ? t.customPairTauQ0[ch]
-                                     : which < DETSDW_OBS_CUSTOMPAIRSQ ? c.customPairCorr[ch] : c.customPairSq[ch];
-        if (e.empty()) throw GeneralError(DQMC_EINVAL, "no measurement sweep has run since the user-defined pair operators were set");
-        std::memcpy(out, e.data(), e.size() * sizeof(double));
-        return;
-    }
-    if (greenMat) {
-        if (!greenMatrix_) throw ParameterWrong("greenMatrixTau needs detsdw_set_green_matrix");
-        if (t.greenMatrixTau.empty()) throw GeneralError(DQMC_EINVAL, "no measurement sweep has run since the averaged Green's function was switched on");
-        std::memcpy(out, t.greenMatrixTau.data(), t.greenMatrixTau.size() * sizeof(double));
-        return;
-    }
-    const std::vector<double>* v = which == DETSDW_OBS_KOCCX ? &c.kOccX : which == DETSDW_OBS_KOCCY ? &c.kOccY
-                                 : which == DETSDW_OBS_PAIRPLUS ? &c.pairPlus : which == DETSDW_OBS_PAIRMINUS ? &c.pairMinus
-                                 : which == DETSDW_OBS_GREENKTAU_X ? &t.greenKTauX : which == DETSDW_OBS_GREENKTAU_Y ? &t.greenKTauY
-                                 : which == DETSDW_OBS_PAIRPLUSTAU ? &t.pairPlusTau : which == DETSDW_OBS_PAIRMINUSTAU ? &t.pairMinusTau
-                                 : which == DETSDW_OBS_PAIRPLUSTAU_Q0 ? &t.pairPlusTauQ0 : which == DETSDW_OBS_PAIRMINUSTAU_Q0 ? &t.pairMinusTauQ0
-                                 : which >= DETSDW_OBS_CHARGETAU && which <= DETSDW_OBS_SDWTAU ? &t.phTau[which - DETSDW_OBS_CHARGETAU]
-                                 : which >= DETSDW_OBS_CHARGETAU_Q0 && which <= DETSDW_OBS_SDWTAU_Q0 ? &t.phTauQ0[which - DETSDW_OBS_CHARGETAU_Q0]
-                                 : which == DETSDW_OBS_CURRENTXTAU || which == DETSDW_OBS_CURRENTYTAU ? &t.currentTau[which - DETSDW_OBS_CURRENTXTAU]
-                                 : which == DETSDW_OBS_CURRENTXTAU_Q0 || which == DETSDW_OBS_CURRENTYTAU_Q0 ? &t.currentTauQ0[which - DETSDW_OBS_CURRENTXTAU_Q0]
-                                 : which == DETSDW_OBS_BONDKINETICX || which == DETSDW_OBS_BONDKINETICY ? &t.bondKinetic[which - DETSDW_OBS_BONDKINETICX]
-                                 : which == DETSDW_OBS_BANDDIFFTAU || which == DETSDW_OBS_BANDMIXTAU ? &t.bandTau[which - DETSDW_OBS_BANDDIFFTAU]
-                                 : which == DETSDW_OBS_BANDDIFFTAU_Q0 || which == DETSDW_OBS_BANDMIXTAU_Q0 ? &t.bandTauQ0[which - DETSDW_OBS_BANDDIFFTAU_Q0]
-                                 : nullptr;
-    if (!v) throw ParameterWrong("unknown observable vector");
-    if ((which == DETSDW_OBS_GREENKTAU_X || which == DETSDW_OBS_GREENKTAU_Y) && !td_level(c.pars))
-        throw ParameterWrong("greenKTauX / greenKTauY need timeDisplacedMeasurements");
-    if (which >= DETSDW_OBS_PAIRPLUSTAU && which <= DETSDW_OBS_PAIRMINUSTAU_Q0 && td_level(c.pars) != 2)
-        throw ParameterWrong("pairPlusTau / pairMinusTau need timeDisplacedMeasurements = 2");
-    if (which >= DETSDW_OBS_CHARGETAU && which <= DETSDW_OBS_SDWTAU_Q0 && !ph_level(c.pars))
-        throw ParameterWrong("chargeTau / spinZTau / sdwTau need timeDisplacedParticleHole");
-    if (which >= DETSDW_OBS_CURRENTXTAU && which <= DETSDW_OBS_BONDKINETICY && ph_level(c.pars) != 2)
-        throw ParameterWrong("currentXTau / currentYTau / bondKineticX / bondKineticY need timeDisplacedParticleHole = 2");
-    if (bandTau && !td_band(c.pars))
-        throw ParameterWrong("bandDiffTau / bandMixTau need bandCorrelators with timeDisplacedParticleHole (DETSDW_TD_PH_BAND)");
-    std::memcpy(out, v->data(), v->size() * sizeof(double));
+    if (o.comp >= live(r)) throw ParameterWrong(obs_not_set_text(r.count));
+    if (!has(r.needs)) throw ParameterWrong(r.needsMsg);
+    if (r.family == DETSDW_OBS_FAMILY_EQ && seriesNoHostCopy())
+        throw ParameterWrong("the equal-time correlators are not copied to the host while a series with DETSDW_SERIES_NO_HOST_COPY is open: read the series");
+    const std::vector<double>& v = stored(c, r, o.comp, o.fine);
+    if (r.staleMsg && v.empty()) throw GeneralError(DQMC_EINVAL, r.staleMsg);
+    std::memcpy(out, v.data(), v.size() * sizeof(double));
 }
 
 // Matsubara transforms of the every-slice blocks.  which -> (channel, component) of dqmc_measure_td_matsubara_host; one device call per
@@ -867,29 +750,21 @@ void DetSDW::getObservableVector(int which_in, double* out, int b) const {
 // observables of all chains cost four calls per context.
 void DetSDW::invalidateMatsubara() {
     tdBlocksValid_ = false;
-    for (auto& g : groups_) for (int ch = 0; ch < 7; ++ch) g.matsNfreq[ch] = 0;
+    for (auto& g : groups_) for (int& nfreq : g.matsNfreq) nfreq = 0;
 }
 const double* DetSDW::matsubara(Group& g, int which, int nfreq, int& ncomp, int& comp) {
     const detsdw_params& p = ch_[0].pars;
-    int channel;
-    if (which == DETSDW_OBS_GREENKTAU_X || which == DETSDW_OBS_GREENKTAU_Y) { channel = 0; comp = which - DETSDW_OBS_GREENKTAU_X; }
-    else if (which == DETSDW_OBS_PAIRPLUSTAU || which == DETSDW_OBS_PAIRMINUSTAU) { channel = 1; comp = which - DETSDW_OBS_PAIRPLUSTAU; }
-    else if (which >= DETSDW_OBS_CHARGETAU && which <= DETSDW_OBS_SDWTAU) { channel = 2; comp = which - DETSDW_OBS_CHARGETAU; }
-    else if (which == DETSDW_OBS_CURRENTXTAU || which == DETSDW_OBS_CURRENTYTAU) { channel = 3; comp = which - DETSDW_OBS_CURRENTXTAU; }
-    else if (which == DETSDW_OBS_BANDDIFFTAU || which == DETSDW_OBS_BANDMIXTAU) { channel = 4; comp = which - DETSDW_OBS_BANDDIFFTAU; }
-    else if (which >= DETSDW_OBS_CUSTOMTAU && which < DETSDW_OBS_CUSTOMTAU_Q0) { channel = 5; comp = which - DETSDW_OBS_CUSTOMTAU; }
-    else if (which >= DETSDW_OBS_CUSTOMPAIRTAU && which < DETSDW_OBS_CUSTOMPAIRTAU_Q0) { channel = 6; comp = which - DETSDW_OBS_CUSTOMPAIRTAU; }
-    else throw ParameterWrong("no Matsubara transform of this observable");
-    ncomp = channel == 6 ? pairCount() : channel == 5 ? customCount() : channel == 2 ? 3 : 2;
-    if (channel == 6 && (!customPairTd() || comp >= pairCount()))
-        throw ParameterWrong("customPair{c}Tau needs an operator set by detsdw_set_custom_pair_operators and timeDisplacedMeasurements");
-    if (channel == 5 && (!customTd() || comp >= customCount()))
-        throw ParameterWrong("custom{c}Tau needs a matrix set by detsdw_set_custom_bilinears and timeDisplacedParticleHole");
+    const ObsRef o = obs_lookup(which);
+    if (!o.row || o.fine || !o.row->matsubara) throw ParameterWrong("no Matsubara transform of this observable");
+    const ObsRow& r = *o.row;
+    const int channel = r.block;
+    comp = o.comp;
+    ncomp = live(r);
+    // the user-defined channels say what they lack before the every-slice check, the fixed ones after it
+    const bool counted = r.count != ObsCount::Fixed;
+    if (counted && (!has(r.needs) || comp >= ncomp)) throw ParameterWrong(r.matsMsg);
     if (!td_every_slice(p)) throw ParameterWrong("the Matsubara transforms need timeDisplacedEverySlice");
-    if (channel == 1 && td_level(p) != 2) throw ParameterWrong("pairPlusTau / pairMinusTau need timeDisplacedMeasurements = 2");
-    if (channel == 2 && !ph_level(p)) throw ParameterWrong("chargeTau / spinZTau / sdwTau need timeDisplacedParticleHole");
-    if (channel == 3 && ph_level(p) != 2) throw ParameterWrong("currentXTau / currentYTau need timeDisplacedParticleHole = 2");
-    if (channel == 4 && !td_band(p)) throw ParameterWrong("bandDiffTau / bandMixTau need bandCorrelators with timeDisplacedParticleHole (DETSDW_TD_PH_BAND)");
+    if (!counted && !has(r.needs)) throw ParameterWrong(r.matsMsg);
     if (nfreq < 1 || nfreq > m_) throw ParameterWrong("nfreq must be in 1 .. m");
     if (!tdBlocksValid_) throw GeneralError(DQMC_EINVAL, "the Matsubara transforms are valid after a measurement sweep and until the next sweep");
     if (g.matsNfreq[channel] != nfreq) {
@@ -927,20 +802,11 @@ void DetSDW::seriesBegin(int binSize, int maxBins, int nfreq, int flags) {
     // with DETSDW_SERIES_PHI a handle without fermionMeasurements opens the order-parameter part alone: its blocks are never filled
     const bool blocks = !phi || (p.fermionMeasurements & 1);
     int parts = phi ? DQMC_SERIES_PHI : 0;
-    if (blocks && eq_correlators(p)) parts |= DQMC_SERIES_EQ;
-    if (blocks && eq_band(p)) parts |= DQMC_SERIES_EQ_BAND;
-    if (blocks && td_every_slice(p)) {
-        parts |= DQMC_SERIES_MATS_G;
-        if (td_level(p) == 2) parts |= DQMC_SERIES_MATS_PAIR;
-        if (ph_level(p)) parts |= DQMC_SERIES_MATS_PH;
-        if (ph_level(p) == 2) parts |= DQMC_SERIES_MATS_CURRENT;
-        if (td_band(p)) parts |= DQMC_SERIES_MATS_BAND;
-        if (customTd()) parts |= DQMC_SERIES_MATS_CUSTOM;
-        if (customPairTd()) parts |= DQMC_SERIES_MATS_CUSTOM_PAIR;
-        if (greenMatrix_) parts |= DQMC_SERIES_GREEN_MATRIX;
-    }
-    if (blocks && customEq()) parts |= DQMC_SERIES_EQ_CUSTOM;
-    if (blocks && customPairEq()) parts |= DQMC_SERIES_EQ_CUSTOM_PAIR;
+    // every part whose observables are measured: the time-displaced ones enter through their every-slice blocks
+    if (blocks)
+        for (const ObsRow& r : kObsRows)
+            if (r.seriesBit && r.family != DETSDW_OBS_FAMILY_PHI && has(r.needs) && (r.family != DETSDW_OBS_FAMILY_TD || td_every_slice(p)))
+                parts |= r.seriesBit;
     if (!parts) throw ParameterWrong("a measurement series needs equalTimeCorrelators or timeDisplacedEverySlice");
     size_t opened = 0;
     try {
@@ -998,52 +864,20 @@ void DetSDW::seriesInfo(int* binsClosed, int* sweepsInOpenBin, size_t* sampleLen
 }
 void DetSDW::seriesSlice(int which, int& part, size_t& offset, size_t& length) {
     if (!series_.open) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
-    size_t sub;
-    if (which >= DETSDW_OBS_CHARGECORR && which <= DETSDW_OBS_PAIRMINUSSQ) {
-        if (!(series_.parts & DQMC_SERIES_EQ)) throw ParameterWrong("the equal-time part of the series needs equalTimeCorrelators");
-        part = 0; length = (size_t)N_; sub = (size_t)(which - DETSDW_OBS_CHARGECORR) * N_;
-    } else if (which >= DETSDW_OBS_BANDDIFFCORR && which <= DETSDW_OBS_BANDMIXSQ) {
-        if (!(series_.parts & DQMC_SERIES_EQ_BAND)) throw ParameterWrong("the equal-time band part of the series needs bandCorrelators with equalTimeCorrelators");
-        part = 8; length = (size_t)N_; sub = (size_t)(which - DETSDW_OBS_BANDDIFFCORR) * N_;
-    } else if (which >= DETSDW_OBS_CUSTOMCORR && which < DETSDW_OBS_CUSTOMSQ + DQMC_CUSTOM_MAX) {
-        const int ch = (which - DETSDW_OBS_CUSTOMCORR) % DQMC_CUSTOM_MAX;
-        if (!(series_.parts & DQMC_SERIES_EQ_CUSTOM) || ch >= customCount())
-            throw ParameterWrong("the series holds no equal-time part of this user-defined bilinear");
-        part = 10; length = (size_t)N_; sub = (size_t)((which >= DETSDW_OBS_CUSTOMSQ ? customCount() : 0) + ch) * N_;
-    } else if (which >= DETSDW_OBS_CUSTOMTAU && which < DETSDW_OBS_CUSTOMTAU_Q0) {
-        const int ch = which - DETSDW_OBS_CUSTOMTAU;
-        if (!(series_.parts & DQMC_SERIES_MATS_CUSTOM) || ch >= customCount())
-            throw ParameterWrong("the series holds no Matsubara part of this user-defined bilinear");
-        part = 9; length = (size_t)series_.nfreq * N_ * 2; sub = (size_t)ch * length;
-    } else if (which >= DETSDW_OBS_CUSTOMPAIRCORR && which < DETSDW_OBS_CUSTOMPAIRSQ + DQMC_CUSTOM_MAX) {
-        const int ch = (which - DETSDW_OBS_CUSTOMPAIRCORR) % DQMC_CUSTOM_MAX;
-        if (!(series_.parts & DQMC_SERIES_EQ_CUSTOM_PAIR) || ch >= pairCount())
-            throw ParameterWrong("the series holds no equal-time part of this user-defined pair operator");
-        part = 12; length = (size_t)N_; sub = (size_t)((which >= DETSDW_OBS_CUSTOMPAIRSQ ? pairCount() : 0) + ch) * N_;
-    } else if (which >= DETSDW_OBS_CUSTOMPAIRTAU && which < DETSDW_OBS_CUSTOMPAIRTAU_Q0) {
-        const int ch = which - DETSDW_OBS_CUSTOMPAIRTAU;
-        if (!(series_.parts & DQMC_SERIES_MATS_CUSTOM_PAIR) || ch >= pairCount())
-            throw ParameterWrong("the series holds no Matsubara part of this user-defined pair operator");
-        part = 11; length = (size_t)series_.nfreq * N_ * 2; sub = (size_t)ch * length;
-    } else if (which == DETSDW_OBS_GREENMATRIXTAU) {
-        if (!(series_.parts & DQMC_SERIES_GREEN_MATRIX))
-            throw ParameterWrong("the series holds no averaged Green's function: detsdw_set_green_matrix before the series began, and timeDisplacedEverySlice");
-        part = 13; length = (size_t)(m_ + 1) * N_ * (ch_[0].pars.opdim == 3 ? 32 : 8); sub = 0;
-    } else if (which == DETSDW_OBS_PHICHI || which == DETSDW_OBS_PHISCALARS) {
-        if (!(series_.parts & DQMC_SERIES_PHI)) throw ParameterWrong("the series has no order-parameter part: detsdw_series_begin with DETSDW_SERIES_PHI");
-        part = 6;
-        if (which == DETSDW_OBS_PHICHI) { length = (size_t)series_.nfreq * N_; sub = 0; }
-        else { length = 5; sub = (size_t)series_.nfreq * N_; }
-    } else {
-        int channel, comp;
-        if (which == DETSDW_OBS_GREENKTAU_X || which == DETSDW_OBS_GREENKTAU_Y) { channel = 0; comp = which - DETSDW_OBS_GREENKTAU_X; }
-        else if (which == DETSDW_OBS_PAIRPLUSTAU || which == DETSDW_OBS_PAIRMINUSTAU) { channel = 1; comp = which - DETSDW_OBS_PAIRPLUSTAU; }
-        else if (which >= DETSDW_OBS_CHARGETAU && which <= DETSDW_OBS_SDWTAU) { channel = 2; comp = which - DETSDW_OBS_CHARGETAU; }
-        else if (which == DETSDW_OBS_CURRENTXTAU || which == DETSDW_OBS_CURRENTYTAU) { channel = 3; comp = which - DETSDW_OBS_CURRENTXTAU; }
-        else if (which == DETSDW_OBS_BANDDIFFTAU || which == DETSDW_OBS_BANDMIXTAU) { channel = 4; comp = which - DETSDW_OBS_BANDDIFFTAU; }
-        else throw ParameterWrong("the measurement series does not hold this observable");
-        if (!(series_.parts & (channel == 4 ? DQMC_SERIES_MATS_BAND : (2 << channel)))) throw ParameterWrong("the series has no Matsubara part for this observable: the option it needs, or timeDisplacedEverySlice, is off");
-        part = channel == 4 ? 7 : 1 + channel; length = (size_t)series_.nfreq * N_ * 2; sub = (size_t)comp * length;
+    const ObsRef o = obs_lookup(which);
+    if (!o.row || o.fine || !o.row->seriesBit) throw ParameterWrong("the measurement series does not hold this observable");
+    const ObsRow& r = *o.row;
+    if (!(series_.parts & r.seriesBit) || o.comp >= live(r)) throw ParameterWrong(obs_series_missing_text(r.seriesBit));
+    part = obs_series_part(r.seriesBit);
+    size_t sub = 0;
+    switch (r.kind) {
+    case DETSDW_OBS_KIND_CORR: length = (size_t)N_; sub = (size_t)o.comp * N_; break;                    // C(d) of every component, then S(q)
+    case DETSDW_OBS_KIND_SQ: length = (size_t)N_; sub = (size_t)(live(r) + o.comp) * N_; break;
+    case DETSDW_OBS_KIND_TAU: length = (size_t)series_.nfreq * N_ * 2; sub = (size_t)o.comp * length; break;   // the Matsubara transform
+    case DETSDW_OBS_KIND_GREEN_MATRIX: length = (size_t)(m_ + 1) * N_ * (ch_[0].pars.opdim == 3 ? 32 : 8); break;   // the stored R x R block
+    case DETSDW_OBS_KIND_PHI_CHI: length = (size_t)series_.nfreq * N_; break;
+    case DETSDW_OBS_KIND_PHI_SCALARS: length = 5; sub = (size_t)series_.nfreq * N_; break;
+    default: throw ParameterWrong("the measurement series does not hold this observable");
     }
     size_t off = 0, len = 0;
     check(dqmc_series_layout(groups_[0].ctx, part, &off, &len), "dqmc_series_layout");
@@ -1194,7 +1028,7 @@ void DetSDW::setGreenMatrix(bool on) {
         throw GeneralError(rc, "dqmc_set_green_matrix: " + why);
     }
     greenMatrix_ = on;
-    for (auto& c : ch_) { c.td.greenMatrixTau.clear(); c.tdFine.greenMatrixTau.clear(); }
+    dropStored(kTdGreenMatrix, -1);
 }
 // The wrap-error diagnostics of every kernel context; if a later context fails the earlier ones are switched back
 void DetSDW::setGreenCheck(bool on) {
@@ -1253,12 +1087,8 @@ void DetSDW::setCustomPairOperators(int count, const dqmc_cplx* F0, const dqmc_c
         pairF_[k].swap(f);
     }
     pairCount_ = count;
-    for (auto& g : groups_) g.matsNfreq[6] = 0;            // the other channels' transforms and blocks are untouched
-    for (auto& c : ch_)
-        for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) {
-            c.customPairCorr[ch].clear(); c.customPairSq[ch].clear();
-            for (TdObs* t : {&c.td, &c.tdFine}) { t->customPairTau[ch].clear(); t->customPairTauQ0[ch].clear(); }
-        }
+    for (auto& g : groups_) g.matsNfreq[kTdCustomPair] = 0;      // the other channels' transforms and blocks are untouched
+    dropStored(kTdCustomPair, kEqCustomPair);
 }
 bool DetSDW::customTd() const { return customCount() && ph_level(ch_[0].pars); }
 bool DetSDW::customEq() const { return customCount() && eq_correlators(ch_[0].pars); }
@@ -1308,13 +1138,8 @@ void DetSDW::setCustomOperators(int count, const dqmc_cplx* M, const dqmc_cplx* 
     if (!any) { bx.clear(); by.clear(); }
     customMx_.swap(bx); customMy_.swap(by);
     customM_.assign(M, M + (size_t)16 * count);
-    for (auto& g : groups_) g.matsNfreq[5] = 0;            // the other channels' transforms and blocks are untouched
-    for (auto& c : ch_) {
-        for (int ch = 0; ch < DQMC_CUSTOM_MAX; ++ch) {
-            c.customCorr[ch].clear(); c.customSq[ch].clear();
-            for (TdObs* t : {&c.td, &c.tdFine}) { t->customTau[ch].clear(); t->customTauQ0[ch].clear(); }
-        }
-    }
+    for (auto& g : groups_) g.matsNfreq[kTdCustom] = 0;          // the other channels' transforms and blocks are untouched
+    dropStored(kTdCustom, kEqCustom);
 }
 void DetSDW::seriesReadBins(int which, int first, int count, double* out, int b) {
     int part; size_t off, len;
@@ -2027,6 +1852,16 @@ extern "C" int detsdw_get_observables(detsdw_replica* r, detsdw_observables* out
 }
 extern "C" int detsdw_get_observable_vector(detsdw_replica* r, int which, double* out) {
     RGUARD(r->impl->getObservableVector(which, out, r->sel))
+}
+extern "C" int detsdw_describe_observable(int which, detsdw_observable_desc* out) {
+    const detqmc::ObsRef o = detqmc::obs_lookup(which);
+    if (!out) { g_host_err = "null argument"; return DQMC_EINVAL; }
+    if (!o.row) { g_host_err = "unknown observable vector"; return DQMC_EINVAL; }
+    const detqmc::ObsRow& r = *o.row;
+    const bool series = r.seriesBit && !o.fine;
+    *out = detsdw_observable_desc{r.family, r.block, o.comp, r.kind, o.fine, r.fineTwin, r.matsubara && !o.fine,
+                                  series ? detqmc::obs_series_part(r.seriesBit) : -1, series ? r.seriesBit : -1};
+    return DQMC_OK;
 }
 extern "C" int detsdw_get_matsubara(detsdw_replica* r, int which, int nfreq, double* out) {
     if (!out) { g_host_err = "null argument"; return DQMC_EINVAL; }

@@ -9,6 +9,7 @@
 #include <vector>
 #include "../../../include/detsdw_host.h"
 #include "dsfmt19937.h"
+#include "obs_catalogue.h"
 
 namespace detqmc {
 
@@ -113,17 +114,11 @@ public:
 
 private:
     enum SweepDirection { Up = +1, Down = -1 };
-    struct TdObs {                                 // time-displaced observables, one row per tau of the family's grid
-        std::vector<double> greenKTauX, greenKTauY;         // rows x N (timeDisplacedMeasurements)
-        std::vector<double> pairPlusTau, pairMinusTau;      // rows x N, column = periodic site difference (timeDisplacedMeasurements == 2)
-        std::vector<double> pairPlusTauQ0, pairMinusTauQ0;  // rows: their row sums
-        std::vector<double> phTau[3], phTauQ0[3];           // charge, spinZ, sdw: rows x N and the row sums (timeDisplacedParticleHole)
-        std::vector<double> currentTau[2], currentTauQ0[2], bondKinetic[2];   // x, y: rows x N, row sums, rows (timeDisplacedParticleHole == 2)
-        std::vector<double> bandTau[2], bandTauQ0[2];       // bandDiff, bandMix: rows x N and the row sums (DETSDW_TD_PH_BAND)
-        std::vector<double> greenMatrixTau;                 // rows x N x 4 x 4 complex: the averaged Green's function (setGreenMatrix)
-        std::vector<double> customPairTau[DQMC_CUSTOM_MAX], customPairTauQ0[DQMC_CUSTOM_MAX];   // ... per user-defined pair operator (setCustomPairOperators)
-        std::vector<double> customTau[DQMC_CUSTOM_MAX], customTauQ0[DQMC_CUSTOM_MAX];   // the same per user-defined bilinear (setCustomBilinears)
-    };
+    // Storage of the observable vectors, addressed by what the catalogue returns for an index (obs_catalogue.h, DetSDW::stored)
+    struct TdComp { std::vector<double> val, q0, scalar; };     // one component of a time-displaced channel: rows x N (channel 7: rows x N x 4 x 4
+                                                                // complex), its row sums, and the channel's per-row scalar of that number
+    struct TdObs { std::vector<TdComp> ch[kTdChannels]; };      // one row per tau of the family's grid
+    struct EqComp { std::vector<double> corr, sq; };            // one component of an equal-time block: C(d) and S(q), N each
     struct Chain {
         detsdw_params pars;
         RngStream rng;
@@ -136,12 +131,15 @@ private:
         double phiDelta = 0.5, lastAccRatio = 0.0;
         double angleDelta = 0.0, scaleDelta = 0.1;          // AdjustmentData::InitialAngleDelta / InitialScaleDelta (detsdwopdim.h:490-491)
         detsdw_observables obs{};
-        std::vector<double> kOccX, kOccY, pairPlus, pairMinus;
-        std::vector<double> eqCorr[7], eqSq[7];    // charge, spinZ, sdw, pairPlus, pairMinus: C(d) and S(q), N each (DETSDW_FM_EQ_CORRELATORS); 5, 6: bandDiff, bandMix (DETSDW_FM_EQ_BAND)
-        std::vector<double> customPairCorr[DQMC_CUSTOM_MAX], customPairSq[DQMC_CUSTOM_MAX];   // ... of the user-defined pair operators
-        std::vector<double> customCorr[DQMC_CUSTOM_MAX], customSq[DQMC_CUSTOM_MAX];   // C(d) and S(q) of the user-defined bilinears, N each
+        std::vector<double> slice[4];          // kOccX, kOccY, pairPlus, pairMinus
+        std::vector<EqComp> eq[kEqBlocks];
         TdObs td, tdFine;                      // rows = interior boundaries j = 1 .. n-1 / time slices k = 0 .. m (timeDisplacedEverySlice)
-        Chain(const detsdw_params& p) : pars(p), rng(p.rngSeed, (uint32_t)p.simindex + 1u) {}   // detqmc.h:181
+        Chain(const detsdw_params& p) : pars(p), rng(p.rngSeed, (uint32_t)p.simindex + 1u) {   // detqmc.h:181
+            for (const ObsRow& r : kObsRows) {             // every component the catalogue can name exists, empty until it is measured
+                if (r.family == DETSDW_OBS_FAMILY_TD) { td.ch[r.block].resize(r.n); tdFine.ch[r.block].resize(r.n); }
+                if (r.family == DETSDW_OBS_FAMILY_EQ) eq[r.block].resize(r.n);
+            }
+        }
     };
     std::vector<Chain> ch_;
     struct Group {                                 // one sub-batch = one kernel context, chains [first, first + count)
@@ -151,8 +149,8 @@ private:
         std::vector<uint64_t> windowStart;         // per chain: rng.drawn() at which the window on the device begins
         bool tailStaged = false;                   // the draws behind those windows are on the device or on their way (stageLocalUpdates)
         std::vector<double> fields;                // host staging of all chains' fields (global moves)
-        std::vector<double> mats[7];               // Matsubara transforms of the group's chains per channel, [chain][component][nfreq][N] (re, im)
-        int matsNfreq[7] = {0, 0, 0, 0, 0, 0, 0};          // ... and the nfreq they hold (0: none); cleared by every sweep
+        std::vector<double> mats[kTdChannels];     // Matsubara transforms of the group's chains per channel, [chain][component][nfreq][N] (re, im)
+        int matsNfreq[kTdChannels] = {};           // ... and the nfreq they hold (0: none); cleared by every sweep
         std::vector<double> seriesMean, seriesErr; // dqmc_series_stats_host of the group's chains, [chain][S] each ...
         int seriesStatsBins = 0;                   // ... and the number of closed bins they were formed from (0: none)
         std::vector<double> seriesBinErr, seriesBinTau;   // dqmc_series_binning_host of the group's chains, [level][chain][S] each ...
@@ -178,6 +176,10 @@ private:
     bool customPairEq() const;                     // ... the equal-time correlators
     bool customTd() const;                         // matrices are set and the handle measures the particle-hole family
     bool customEq() const;                         // ... the equal-time correlators
+    bool has(ObsNeeds needs) const;                // the option predicate of a catalogue row
+    int live(const ObsRow& r) const { return r.count == ObsCount::Custom ? customCount() : r.count == ObsCount::Pair ? pairCount() : r.n; }
+    const std::vector<double>& stored(const Chain& c, const ObsRow& r, int comp, bool fine) const;
+    void dropStored(int tdChannel, int eqBlock);   // after the operators of a channel changed: its vectors are empty until the next measurement sweep
 
     Group& grp(int b) { return groups_[(size_t)b / (size_t)groups_[0].count]; }
     static void check(int rc, const char* what);

@@ -86,16 +86,25 @@ class SDWParams:
     rngLookahead: int = 0        # the next sweep's uniforms are drawn and uploaded while the device sweeps (0: automatic = on, -1: off)
 
 
-# observables with a Matsubara transform (DetSDW.matsubara): name -> index of detsdw_get_observable_vector
-MATSUBARA = {"greenKTauX": 4, "greenKTauY": 5, "pairPlusTau": 6, "pairMinusTau": 7, "chargeTau": 10, "spinZTau": 11, "sdwTau": 12,
-             "currentXTau": 16, "currentYTau": 17, "bandDiffTau": 34, "bandMixTau": 35}
-
-
-# equal-time correlators and structure factors (SDWParams.equalTimeCorrelators): name -> index of detsdw_get_observable_vector
-EQ_CORRELATORS = {"chargeCorr": 22, "spinZCorr": 23, "sdwCorr": 24, "pairPlusCorr": 25, "pairMinusCorr": 26,
-                  "chargeSq": 27, "spinZSq": 28, "sdwSq": 29, "pairPlusSq": 30, "pairMinusSq": 31}
-# ... of the band-resolved charge channels (SDWParams.bandCorrelators with equalTimeCorrelators), read and binned in a series like the above
-BAND_EQ_CORRELATORS = {"bandDiffCorr": 38, "bandMixCorr": 39, "bandDiffSq": 40, "bandMixSq": 41}
+# The observables of the SDW host replica: name -> DETSDW_OBS_* index (include/detsdw_host.h).  What an index is -- shape, 'Fine' twin,
+# Matsubara transform, series part -- is not restated here: the library's catalogue says it (describe_observable).  The matrices and pair
+# operators a user sets are named 'custom{c}...' / 'customPair{c}...' (custom_observable, custom_pair_observable below)
+OBSERVABLES = {"kOccX": 0, "kOccY": 1, "pairPlus": 2, "pairMinus": 3, "greenKTauX": 4, "greenKTauY": 5,
+               "pairPlusTau": 6, "pairMinusTau": 7, "pairPlusTauQ0": 8, "pairMinusTauQ0": 9,
+               "chargeTau": 10, "spinZTau": 11, "sdwTau": 12, "chargeTauQ0": 13, "spinZTauQ0": 14, "sdwTauQ0": 15,
+               "currentXTau": 16, "currentYTau": 17, "currentXTauQ0": 18, "currentYTauQ0": 19, "bondKineticX": 20, "bondKineticY": 21,
+               "chargeCorr": 22, "spinZCorr": 23, "sdwCorr": 24, "pairPlusCorr": 25, "pairMinusCorr": 26,
+               "chargeSq": 27, "spinZSq": 28, "sdwSq": 29, "pairPlusSq": 30, "pairMinusSq": 31, "phiChi": 32, "phiScalars": 33,
+               "bandDiffTau": 34, "bandMixTau": 35, "bandDiffTauQ0": 36, "bandMixTauQ0": 37,
+               "bandDiffCorr": 38, "bandMixCorr": 39, "bandDiffSq": 40, "bandMixSq": 41, "greenMatrixTau": 74}
+# views of the table: the fixed names with a Matsubara transform (DetSDW.matsubara); the equal-time correlators and structure factors
+# (SDWParams.equalTimeCorrelators) and those of the band-resolved charge channels (bandCorrelators); the order-parameter part of a series
+# opened with phi=True (real, (nfreq, N) and (5,)); 'greenMatrixTau' (and its 'Fine' twin)
+MATSUBARA = {n: OBSERVABLES[n] for n in "greenKTauX greenKTauY pairPlusTau pairMinusTau chargeTau spinZTau sdwTau currentXTau currentYTau bandDiffTau bandMixTau".split()}
+EQ_CORRELATORS = {n: OBSERVABLES[n] for n in "chargeCorr spinZCorr sdwCorr pairPlusCorr pairMinusCorr chargeSq spinZSq sdwSq pairPlusSq pairMinusSq".split()}
+BAND_EQ_CORRELATORS = {n: OBSERVABLES[n] for n in "bandDiffCorr bandMixCorr bandDiffSq bandMixSq".split()}
+SERIES_PHI_OBS = {n: OBSERVABLES[n] for n in "phiChi phiScalars".split()}
+GREEN_MATRIX_OBS = OBSERVABLES["greenMatrixTau"]
 
 
 def structure_factor(c, L):
@@ -173,8 +182,6 @@ def custom_pair_ratio(name):
 
 # bit 13: the normalised averaged Green's function of every slice (set_green_matrix), [m+1][N][R][R] complex
 SERIES_GREEN_MATRIX = 8192
-# 'greenMatrixTau' (and its 'Fine' twin): index of detsdw_get_observable_vector / detsdw_series_stats
-GREEN_MATRIX_OBS = 74
 # derived series quantities of the pair vertex (DetSDWBatch.series_derived_all): name prefix -> entry of detsdw_series_pair_vertex
 PAIR_VERTEX_QUANTITIES = {"vertexCustomPair": 0, "bubbleCustomPair": 1, "gammaCustomPair": 2, "gammaBubbleCustomPair": 3}
 
@@ -197,12 +204,37 @@ def ph_vertex_quantity(name):
     return (PH_VERTEX_QUANTITIES[m.group(1)], int(m.group(2))) if m else None
 
 
+def observable_index(name):
+    """(index, detsdw_observable_desc) of a name of OBSERVABLES, 'custom{c}...', 'customPair{c}...' or one of those + 'Fine' where the
+    observable has an every-slice twin; KeyError otherwise.  The descriptor is the library's catalogue entry of the index: no GPU"""
+    fine = name.endswith("Fine")
+    base = name[:-4] if fine else name
+    cw = custom_observable(base) or custom_pair_observable(base)
+    which = (cw[1] if cw else OBSERVABLES[base]) | (_lib.DETSDW_OBS_FINE if fine else 0)
+    d = _lib.detsdw_observable_desc()
+    if load().detsdw_describe_observable(which, C.byref(d)) != 0:
+        raise KeyError(name)
+    return which, d
+
+
+def observable_shape(d, info, nfreq=0, series=False):
+    """(shape, complex?) of one chain's values from the descriptor's kind: what observable_vector returns or, with series, what the series
+    readers return -- the Matsubara transform in place of the tau rows, the stored flavour block of the Green matrix.  info: N, m, n, opdim"""
+    K, N, R = _lib, info.N, 4 if info.opdim == 3 else 2
+    rows = info.m + 1 if d.fine else info.n - 1
+    shape = {K.DETSDW_OBS_KIND_SITE: (N,), K.DETSDW_OBS_KIND_CORR: (N,), K.DETSDW_OBS_KIND_SQ: (N,), K.DETSDW_OBS_KIND_TAU_Q0: (rows,),
+             K.DETSDW_OBS_KIND_ROW_SCALAR: (rows,), K.DETSDW_OBS_KIND_PHI_CHI: (int(nfreq), N), K.DETSDW_OBS_KIND_PHI_SCALARS: (5,),
+             K.DETSDW_OBS_KIND_TAU: (int(nfreq) if series else rows, N),
+             K.DETSDW_OBS_KIND_GREEN_MATRIX: (info.m + 1, N, R, R) if series else (rows, N, 4, 4)}[d.kind]
+    return shape, d.kind == K.DETSDW_OBS_KIND_GREEN_MATRIX or (series and d.kind == K.DETSDW_OBS_KIND_TAU)
+
+
 def _matsubara_index(name):
     """index of detsdw_get_matsubara for a name of MATSUBARA, 'custom{c}Tau' or 'customPair{c}Tau'; KeyError otherwise"""
-    cw = custom_observable(name) or custom_pair_observable(name)
-    return cw[1] if cw and cw[0] == "Tau" else MATSUBARA[name]
-# the order-parameter part of a series opened with phi=True: name -> index of detsdw_series_stats (real, (nfreq, N) and (5,))
-SERIES_PHI_OBS = {"phiChi": 32, "phiScalars": 33}
+    which, d = observable_index(name)
+    if not d.has_matsubara:
+        raise KeyError(name)
+    return which
 
 
 def phi_sample(phi, L, nfreq):
@@ -1430,38 +1462,12 @@ class DetSDW(_GreenCheck):
         matrix c, shaped like the bandDiff names; with operators set by DetSDWBatch.set_custom_pair_operators the same four as
         'customPair{c}...' for pair operator c"""
         self._sel()
-        info = self.info
-        if name in EQ_CORRELATORS or name in BAND_EQ_CORRELATORS:
-            out = np.zeros(info.N)
-            which = EQ_CORRELATORS.get(name, BAND_EQ_CORRELATORS.get(name))
-            check(self.lib.detsdw_get_observable_vector(self.h, which, out.ctypes.data_as(_lib._DP)), host=True)
-            return out
-        fine = name.endswith("Fine")
-        if fine:
-            name = name[:-4]
-        if name == "greenMatrixTau":                        # DetSDWBatch.set_green_matrix: <G(tau,0)> as full 4 x 4 blocks per d
-            out = np.zeros((info.m + 1 if fine else info.n - 1, info.N, 4, 4), dtype=np.complex128)
-            check(self.lib.detsdw_get_observable_vector(self.h, GREEN_MATRIX_OBS | (_lib.DETSDW_OBS_FINE if fine else 0), out.ctypes.data_as(_lib._DP)), host=True)
-            return out
-        cw = custom_observable(name) or custom_pair_observable(name)
-        if cw:
-            kind, which = cw
-            if fine and kind in ("Corr", "Sq"):
-                raise KeyError(name + "Fine")
-            rows = info.m + 1 if fine else info.n - 1
-            out = np.zeros(info.N if kind in ("Corr", "Sq") else (rows, info.N) if kind == "Tau" else rows)
-            check(self.lib.detsdw_get_observable_vector(self.h, which | (_lib.DETSDW_OBS_FINE if fine else 0), out.ctypes.data_as(_lib._DP)), host=True)
-            return out
-        which = {"kOccX": 0, "kOccY": 1, "pairPlus": 2, "pairMinus": 3, "greenKTauX": 4, "greenKTauY": 5,
-                 "pairPlusTau": 6, "pairMinusTau": 7, "pairPlusTauQ0": 8, "pairMinusTauQ0": 9,
-                 "chargeTau": 10, "spinZTau": 11, "sdwTau": 12, "chargeTauQ0": 13, "spinZTauQ0": 14, "sdwTauQ0": 15,
-                 "currentXTau": 16, "currentYTau": 17, "currentXTauQ0": 18, "currentYTauQ0": 19, "bondKineticX": 20, "bondKineticY": 21,
-                 "bandDiffTau": 34, "bandMixTau": 35, "bandDiffTauQ0": 36, "bandMixTauQ0": 37}[name]
-        if fine and which < 4:
-            raise KeyError(name + "Fine")
-        rows = info.m + 1 if fine else info.n - 1
-        out = np.zeros(info.N if which < 4 else (rows, info.N) if which < 8 or 10 <= which < 13 or 16 <= which < 18 or 34 <= which < 36 else rows)
-        check(self.lib.detsdw_get_observable_vector(self.h, which | (_lib.DETSDW_OBS_FINE if fine else 0), out.ctypes.data_as(_lib._DP)), host=True)
+        which, d = observable_index(name)
+        if d.family == _lib.DETSDW_OBS_FAMILY_PHI:            # the order-parameter part lives in a series only
+            raise KeyError(name)
+        shape, cplx = observable_shape(d, self.info)
+        out = np.zeros(shape, dtype=np.complex128 if cplx else np.float64)
+        check(self.lib.detsdw_get_observable_vector(self.h, which, out.ctypes.data_as(_lib._DP)), host=True)
         return out
 
     def matsubara(self, name, nfreq):
@@ -1478,20 +1484,10 @@ class DetSDW(_GreenCheck):
         """(index of detsdw_series_stats, shape of one chain's values, complex?) of a series observable"""
         if self._batch is None:
             raise RuntimeError("a measurement series is opened on a batch: DetSDWBatch([pars]).series_begin()")
-        info = self.info
-        if name in EQ_CORRELATORS:
-            return EQ_CORRELATORS[name], (info.N,), False
-        if name in BAND_EQ_CORRELATORS:
-            return BAND_EQ_CORRELATORS[name], (info.N,), False
-        if name in SERIES_PHI_OBS:
-            return SERIES_PHI_OBS[name], ((self._batch._series_nfreq, info.N) if name == "phiChi" else (5,)), False
-        if name == "greenMatrixTau":                        # the stored flavour block, as pair_bubble takes it
-            R = 4 if info.opdim == 3 else 2
-            return GREEN_MATRIX_OBS, (info.m + 1, info.N, R, R), True
-        cw = custom_observable(name) or custom_pair_observable(name)
-        if cw and cw[0] in ("Corr", "Sq"):
-            return cw[1], (info.N,), False
-        return _matsubara_index(name), (self._batch._series_nfreq, info.N), True
+        which, d = observable_index(name)
+        if d.series_part < 0:
+            raise KeyError(name)
+        return (which,) + observable_shape(d, self.info, self._batch._series_nfreq, series=True)
 
     def series_stats(self, name):
         """(mean, err) of this chain over the closed bins of the open series (DetSDWBatch.series_begin): name = an equal-time

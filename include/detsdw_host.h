@@ -173,6 +173,25 @@ enum { DETSDW_TD_FINE_ON_DEVICE = 0x200 };
 /* which | DETSDW_OBS_FINE for which = DETSDW_OBS_GREENKTAU_X .. _BONDKINETICY and DETSDW_OBS_BANDDIFFTAU .. _BANDMIXTAU_Q0: the every-slice twin ("...Fine") of the observable, rows
  * k = 0 .. m instead of j = 1 .. n-1, columns unchanged; needs timeDisplacedEverySlice next to the option its coarse twin needs */
 enum { DETSDW_OBS_FINE = 0x100 };    /* a bit of the observable index: unrelated to DETSDW_TD_EVERY_SLICE, a bit of a parameter */
+/* What an observable index is, from the host layer's catalogue (detqmc_amd/csrc/host/obs_catalogue.h); needs no handle and no GPU.
+ * family: where the values come from -- the per-slice accumulators (kOccX .. pairMinus), an equal-time block, a time-displaced block, or
+ *   the order-parameter part of a series.  block: the channel 0 .. 7 of dqmc_measure_td_fine_read_host (time-displaced) or the equal-time
+ *   block 0 .. 3 (fixed channels, band, custom bilinears, custom pair operators); component: the index inside the block.
+ * kind: the shape -- SITE [N]; TAU [rows][N]; TAU_Q0 and ROW_SCALAR [rows]; CORR and SQ [N]; GREEN_MATRIX [rows][N][4][4] complex (as a
+ *   series observable the stored [m+1][N][R][R] complex); PHI_CHI [nfreq][N]; PHI_SCALARS [5].  rows = n-1, or m+1 with DETSDW_OBS_FINE.
+ * fine: `which` carried DETSDW_OBS_FINE.  has_fine_twin, has_matsubara (detsdw_get_matsubara takes the index); series_part, series_bit:
+ *   the part index of dqmc_series_layout and the DQMC_SERIES_* bit of the part that holds it, both -1 where the series readers refuse
+ *   the index.  An index with DETSDW_OBS_FINE has no Matsubara transform and no series part of its own.
+ * DQMC_EINVAL: an unknown index, or DETSDW_OBS_FINE on an index without a twin. */
+enum { DETSDW_OBS_FAMILY_SLICE = 0, DETSDW_OBS_FAMILY_EQ = 1, DETSDW_OBS_FAMILY_TD = 2, DETSDW_OBS_FAMILY_PHI = 3 };
+enum { DETSDW_OBS_KIND_SITE = 0, DETSDW_OBS_KIND_TAU = 1, DETSDW_OBS_KIND_TAU_Q0 = 2, DETSDW_OBS_KIND_ROW_SCALAR = 3, DETSDW_OBS_KIND_CORR = 4,
+       DETSDW_OBS_KIND_SQ = 5, DETSDW_OBS_KIND_GREEN_MATRIX = 6, DETSDW_OBS_KIND_PHI_CHI = 7, DETSDW_OBS_KIND_PHI_SCALARS = 8 };
+typedef struct detsdw_observable_desc {
+    int32_t family, block, component, kind;
+    int32_t fine, has_fine_twin, has_matsubara;
+    int32_t series_part, series_bit;
+} detsdw_observable_desc;
+int detsdw_describe_observable(int which, detsdw_observable_desc* out);
 
 /* createReplica (src/detsdwopdim.cpp:49-84) + DetSDW ctor (:158-361): checks parameters, seeds the
  * RNG with (rngSeed, simindex + 1) (src/detqmc.h:181), draws the random field, builds UdV storage and
