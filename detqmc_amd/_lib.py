@@ -33,6 +33,7 @@ DQMC_SERIES_MATS_BAND, DQMC_SERIES_EQ_BAND = 128, 256   # parts of dqmc_series_b
 DQMC_SERIES_MATS_CUSTOM, DQMC_SERIES_EQ_CUSTOM = 512, 1024   # ... Matsubara transform of channel 5, equal-time block of the custom bilinears
 DQMC_SERIES_MATS_CUSTOM_PAIR, DQMC_SERIES_EQ_CUSTOM_PAIR = 2048, 4096   # ... Matsubara transform of channel 6, equal-time block of the custom pair operators
 DQMC_SERIES_GREEN_MATRIX = 8192    # ... the normalised averaged Green's function of every slice (dqmc_set_green_matrix)
+DQMC_SERIES_HUB_SCALARS, DQMC_SERIES_HUB_EQ, DQMC_SERIES_HUB_TD = 16384, 32768, 65536   # the parts of a Hubbard context (parts 14 .. 16)
 DQMC_CUSTOM_MAX = 4               # matrices of dqmc_set_custom_bilinears at most
 # detsdw_observable_desc: family and kind of an observable index (detsdw_describe_observable)
 DETSDW_OBS_FAMILY_SLICE, DETSDW_OBS_FAMILY_EQ, DETSDW_OBS_FAMILY_TD, DETSDW_OBS_FAMILY_PHI = 0, 1, 2, 3
@@ -165,6 +166,10 @@ class dethubbard_params(C.Structure):
 
 
 DETHUBBARD_MEASURE_EQ, DETHUBBARD_MEASURE_TD = 1, 2      # dethubbard_params.measureFlags (include/dethubbard_host.h)
+DETHUBBARD_SERIES_NO_HOST_COPY = 1                       # flag of dethubbard_series_begin
+# observable indices of the dethubbard_series_* readers: the eight '...Corr' / '...Sq' and the six '...Tau' / '...TauSq' follow in channel order
+(DETHUBBARD_OBS_SCALARS, DETHUBBARD_OBS_ZCORR, DETHUBBARD_OBS_GREENUPCORR, DETHUBBARD_OBS_GREENUPSQ, DETHUBBARD_OBS_GREENUPTAU,
+ DETHUBBARD_OBS_GREENUPTAUSQ) = 0, 1, 2, 10, 18, 24
 
 
 class dethubbard_observables(C.Structure):
@@ -313,6 +318,7 @@ SYMBOLS = [
     ("dqmc_series_pair_vertex_host", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
     ("dqmc_series_ph_vertex_size", C.c_size_t, [_P]),
     ("dqmc_series_ph_vertex_host", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
+    ("dqmc_series_hubbard_derived_host", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
     ("dqmc_series_end", C.c_int, [_P]),
     ("dqmc_series_configure", C.c_int, [_P, C.c_int]),
     ("dqmc_series_get_state", C.c_int, [_P, C.POINTER(dqmc_series_state)]),
@@ -419,6 +425,20 @@ SYMBOLS = [
     ("dethubbard_reset_green_check", C.c_int, [_P]),
     ("dethubbard_rng_rand01", C.c_double, [_P]),
     ("dethubbard_ctx", _P, [_P]),
+    ("dethubbard_series_begin", C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
+    ("dethubbard_series_info", C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    ("dethubbard_series_stats", C.c_int, [_P, C.c_int, _DP, _DP]),
+    ("dethubbard_series_stats_all", C.c_int, [_P, C.c_int, _DP, _DP]),
+    ("dethubbard_series_read_bins", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _DP]),
+    ("dethubbard_series_derived_all", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
+    ("dethubbard_series_configure", C.c_int, [_P, C.c_int]),
+    ("dethubbard_series_rebin", C.c_int, [_P]),
+    ("dethubbard_series_get_state", C.c_int, [_P, C.POINTER(dqmc_series_state)]),
+    ("dethubbard_series_binning", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
+    ("dethubbard_series_binning_all", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
+    ("dethubbard_series_save", C.c_int, [_P, C.c_char_p]),
+    ("dethubbard_series_load", C.c_int, [_P, C.c_char_p]),
+    ("dethubbard_series_end", C.c_int, [_P]),
 ]
 
 _lib = None

@@ -157,17 +157,19 @@ struct dqmc_ctx {
     // outside the arena, allocated by the switch-on and freed by the switch-off
     bool gm_on = false;
     // dqmc_series_*: the measurement series.  Device buffers outside the arena, allocated by dqmc_series_begin and freed by dqmc_series_end
-    // or with the context: sample [nb][S], open bin [nb][S], closed bins [max_bins][nb][S], the per-part flags [12][nb], the cos / sin table
-    // (2 pi j / L [2 L]; with the order-parameter part, index 6 of off / len, also 2 pi j / m [2 m] behind it) and the result buffer
-    // of the statistics calls (mean, err [nb][S] each, then value, err [nb][6] each).  The counters live on the host.
+    // or with the context: sample [nb][S], open bin [nb][S], closed bins [max_bins][nb][S], the per-part flags [SERIES_AUX_ROWS][nb], the cos /
+    // sin table (2 pi j / L [2 L]; with the order-parameter part, index 6 of off / len, also 2 pi j / m [2 m] behind it) and the result buffer
+    // of the statistics calls (mean, err [nb][S] each, then SERIES_AUX_ROWS rows [nb] for the derived calls: value, err [nb][6] each, or
+    // [nb][19] each for a Hubbard context).  The counters live on the host.
     // srctab [nb]: the source rows of dqmc_series_accumulate, filled from srchost before every launch; formed: the sample buffer holds
     // the sample of a successful dqmc_series_form_sample that no dqmc_series_accumulate has consumed yet.
+    enum { SERIES_AUX_ROWS = 38 };                            // 2 x 19: value and err of dqmc_series_hubbard_derived_host, the largest user
     struct Series {
         bool open = false, formed = false;
         int bin_size = 0, max_bins = 0, nfreq = 0, parts = 0, closed = 0, in_open = 0;
         int flags = 0;                                        // DQMC_SERIES_AUTO_REBIN | DQMC_SERIES_TRACK_VARIANCE (dqmc_series_configure)
         long long samples = 0, rebins = 0;                    // accumulates since begin / merges of neighbouring bins so far
-        size_t S = 0, off[14] = {}, len[14] = {};              // index = bit number; 5 is never used
+        size_t S = 0, off[17] = {}, len[17] = {};              // index = bit number; 5 is never used; 14 .. 16: a Hubbard context's parts
         double *sample = nullptr, *openbin = nullptr, *bins = nullptr, *bad = nullptr, *trig = nullptr, *stat = nullptr;
         double *var = nullptr;                                // running mean w [nb][S], then m2 [nb][S]: allocated with TRACK_VARIANCE
         double *binning = nullptr;                            // result of dqmc_series_binning_host, err then tau [levels][nb][S] each,

@@ -320,6 +320,45 @@ void launch_series_band_derived(const Launch& lc, const DevModel& hm, const doub
 void launch_series_custom_derived(const Launch& lc, const DevModel& hm, const double* bins, size_t S, int B, size_t off, int count, int qx, int qy,
                                   double* value, double* err);      // value, err [nb][count]: R of every user-defined bilinear at Q = (qx, qy)
 size_t series_eq_sample_lds_bytes(int L);
+#ifdef __HIPCC__
+// The separable cosine sum of the sample kernels (k_series_eq_sample, k_hubbard_series_td_sample): out[qy L + qx] = sum_d cos(q d) C(d) for
+// C [N] in LDS, in the order of the host's finishFermionic -- over dx into (Ac, As)[dy][qx], then over dy -- with the phase index reduced
+// mod L in integers and (ct, st) = cos / sin(2 pi j / L).  Called by all 256 threads of a workgroup after a barrier behind the writes
+// of C, ct and st; Ac and As are N doubles of LDS scratch each.
+__device__ __forceinline__ void series_cosine_sum(const double* C, double* Ac, double* As, const double* ct, const double* st, double* __restrict__ out,
+                                                  int L, int tid) {
+    const int N = L * L;
+    for (int i = tid; i < N; i += 256) {
+        const int dy = i / L, qx = i - dy * L;
+        double sc = 0.0, ss = 0.0;
+        for (int dx = 0; dx < L; ++dx) {
+            const double v = C[dy * L + dx];
+            const int j = (qx * dx) % L;
+            sc += ct[j] * v; ss += st[j] * v;
+        }
+        Ac[i] = sc; As[i] = ss;
+    }
+    __syncthreads();
+    for (int q = tid; q < N; q += 256) {
+        const int qy = q / L, qx = q - qy * L;
+        double sq = 0.0;
+        for (int dy = 0; dy < L; ++dy) {
+            const int j = (qy * dy) % L;
+            sq += ct[j] * Ac[dy * L + qx] - st[j] * As[dy * L + qx];
+        }
+        out[q] = sq;
+    }
+}
+#endif
+// the parts of a Hubbard context (DQMC_SERIES_HUB_*; kernels_hubbard.hip, the derived quantities in kernels_measure.hip).  slice / td: the
+// blocks ACC_SLICE and ACC_HUB_TD inside the arena (chain stride lc.cs); t, U, mu: the parameters the eight scalars are formed with.
+// launch_hubbard_series_td_sample returns false, with nothing launched, for a lattice beyond the sample kernels' LDS
+void launch_hubbard_series_scalars(const Launch& lc, const DevModel& hm, const double* slice, double t, double U, double mu, double* sample, size_t S,
+                                   size_t off, double* bad);
+bool launch_hubbard_series_td_sample(const Launch& lc, const DevModel& hm, const double* td, const double* trig, double* sample, size_t S, size_t off,
+                                     double* bad);
+void launch_series_hubbard_derived(const Launch& lc, const DevModel& hm, const double* bins, size_t S, int B, size_t off, int qx, int qy,
+                                   double* value, double* err);      // value, err [nb][19] (dqmc_series_hubbard_derived_host)
 void launch_series_accum(const Launch& lc, const double* sample, double* open, double* closed, size_t n, int close, int bin_size);
 void launch_series_accum_routed(const Launch& lc, const double* const* src, double* open, double* closed, size_t S, int close, int bin_size);
 void launch_series_stats(const Launch& lc, const double* bins, size_t n, int B, double* mean, double* err);

@@ -827,11 +827,19 @@ extern "C" int dqmc_measure_td_matsubara_host(dqmc_ctx* c, int channel, int nfre
 // ---------------------------------------------------------------------------------------------
 extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nfreq, int parts) {
     if (!c) return fail(DQMC_EINVAL, "null ctx");
-    if (c->hm.hubbard) return fail(DQMC_EINVAL, "the measurement series belongs to the SDW model");
     if (c->ser.open) return fail(DQMC_EINVAL, "a measurement series is already open (dqmc_series_end)");
-    if (parts <= 0 || (parts & ~0x3fdf)) return fail(DQMC_EINVAL, "dqmc_series_begin: parts must be a non-empty mask of bits 0 .. 4 and 6 .. 13");
+    const int hub_mask = DQMC_SERIES_HUB_SCALARS | DQMC_SERIES_HUB_EQ | DQMC_SERIES_HUB_TD;
+    if (c->hm.hubbard && (parts <= 0 || (parts & ~hub_mask)))
+        return fail(DQMC_EINVAL, "dqmc_series_begin: on a Hubbard context parts must be a non-empty mask of bits 14 .. 16 (the other parts belong to the SDW model)");
+    if (!c->hm.hubbard && (parts <= 0 || (parts & ~0x3fdf))) return fail(DQMC_EINVAL, "dqmc_series_begin: parts must be a non-empty mask of bits 0 .. 4 and 6 .. 13");
     if (bin_size < 1) return fail(DQMC_EINVAL, "dqmc_series_begin: bin_size must be at least 1");
     if (max_bins < 2) return fail(DQMC_EINVAL, "dqmc_series_begin: max_bins must be at least 2");
+    if ((parts & DQMC_SERIES_HUB_EQ) && !c->acc[ACC_HUB_EQ].n)
+        return fail(DQMC_EINVAL, "dqmc_series_begin: the Hubbard equal-time block has never been enabled (dqmc_hubbard_set_equal_time_correlators)");
+    if ((parts & DQMC_SERIES_HUB_TD) && (!c->acc[ACC_HUB_TD].n || c->n < 2))
+        return fail(DQMC_EINVAL, "dqmc_series_begin: no time-displaced block (a Hubbard context created with timedisplaced = 1, td_particle_hole = 1 and n >= 2)");
+    if ((parts & (DQMC_SERIES_HUB_EQ | DQMC_SERIES_HUB_TD)) && series_eq_sample_lds_bytes(c->hm.L) > 152 * 1024)
+        return fail(DQMC_EINVAL, "dqmc_series_begin: the lattice is too large for the sample kernels' LDS");
     if ((parts & 1) && !c->acc[ACC_EQ].n) return fail(DQMC_EINVAL, "dqmc_series_begin: the equal-time block has never been enabled (dqmc_set_equal_time_correlators)");
     if ((parts & DQMC_SERIES_EQ_BAND) && !c->acc[ACC_EQ_BAND].n) return fail(DQMC_EINVAL, "dqmc_series_begin: the equal-time band block has never been enabled (dqmc_set_equal_time_band)");
     if ((parts & DQMC_SERIES_EQ_CUSTOM) && !c->acc[ACC_EQ_CUSTOM].n) return fail(DQMC_EINVAL, "dqmc_series_begin: no user-defined bilinear is set (dqmc_set_custom_bilinears)");
@@ -881,6 +889,10 @@ extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nf
     if (parts & DQMC_SERIES_GREEN_MATRIX) {                 // the averaged Green's function: behind all older parts
         s.off[13] = s.S; s.len[13] = (size_t)(c->m + 1) * measure_green_matrix_row_doubles(c->p.opdim, c->N); s.S += s.len[13];
     }
+    // the parts of a Hubbard context, behind every SDW bit: scalars and zcorr, C_X(d) / S_X(q) [8][N] each, C_X(d, tau_j) / S_X(q, tau_j) [n-1][6][N] each
+    if (parts & DQMC_SERIES_HUB_SCALARS) { s.off[14] = s.S; s.len[14] = 8 + N; s.S += s.len[14]; }
+    if (parts & DQMC_SERIES_HUB_EQ) { s.off[15] = s.S; s.len[15] = (size_t)2 * HUB_EQ_CH * N; s.S += s.len[15]; }
+    if (parts & DQMC_SERIES_HUB_TD) { s.off[16] = s.S; s.len[16] = (size_t)2 * HUB_TD_CH * (c->n - 1) * N; s.S += s.len[16]; }
     s.bin_size = bin_size; s.max_bins = max_bins; s.parts = parts;
     s.nfreq = (parts & (0x1e | DQMC_SERIES_PHI | DQMC_SERIES_MATS_BAND | DQMC_SERIES_MATS_CUSTOM | DQMC_SERIES_MATS_CUSTOM_PAIR)) ? nfreq : 0;
     (void)hipSetDevice(c->p.device);
@@ -891,15 +903,15 @@ extern "C" int dqmc_series_begin(dqmc_ctx* c, int bin_size, int max_bins, int nf
     if (e == hipSuccess) e = hipMalloc((void**)&r.sample, n * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&r.openbin, n * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&r.bins, (size_t)max_bins * n * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&r.bad, (size_t)12 * c->nb * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&r.bad, (size_t)dqmc_ctx::SERIES_AUX_ROWS * c->nb * sizeof(double));
     const size_t mt = (parts & DQMC_SERIES_PHI) ? (size_t)c->m : 0;     // the temporal table of the order-parameter part
     if (e == hipSuccess) e = hipMalloc((void**)&r.trig, 2 * (L + mt) * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&r.stat, (2 * n + (size_t)12 * c->nb) * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&r.stat, (2 * n + (size_t)dqmc_ctx::SERIES_AUX_ROWS * c->nb) * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&r.srctab, (size_t)c->nb * sizeof(const double*));
     if (e == hipSuccess) e = hipMemsetAsync(r.sample, 0, n * sizeof(double), c->st);
     if (e == hipSuccess) e = hipMemsetAsync(r.openbin, 0, n * sizeof(double), c->st);
     if (e == hipSuccess) e = hipMemsetAsync(r.bins, 0, (size_t)max_bins * n * sizeof(double), c->st);
-    if (e == hipSuccess) e = hipMemsetAsync(r.bad, 0, (size_t)12 * c->nb * sizeof(double), c->st);
+    if (e == hipSuccess) e = hipMemsetAsync(r.bad, 0, (size_t)dqmc_ctx::SERIES_AUX_ROWS * c->nb * sizeof(double), c->st);
     if (e == hipSuccess) {
         // cos / sin(2 pi j / L) as finishFermionic of the host layer forms them: the device's structure factors use the same values
         std::vector<double> trig(2 * (L + mt));
@@ -922,7 +934,7 @@ extern "C" int dqmc_series_end(dqmc_ctx* c) {
 extern "C" int dqmc_series_layout(dqmc_ctx* c, int part, size_t* offset, size_t* length) {
     if (!c || !offset || !length) return fail(DQMC_EINVAL, "null argument");
     if (!c->ser.open) return fail(DQMC_EINVAL, "no measurement series is open");
-    if (part < 0 || part > 13 || !(c->ser.parts & (1 << part))) return fail(DQMC_EINVAL, "dqmc_series_layout: the part is not in the series");
+    if (part < 0 || part > 16 || !(c->ser.parts & (1 << part))) return fail(DQMC_EINVAL, "dqmc_series_layout: the part is not in the series");
     *offset = c->ser.off[part]; *length = c->ser.len[part];
     return DQMC_OK;
 }
@@ -996,6 +1008,22 @@ static int series_form_sample(dqmc_ctx* c, const char* entry) {
         if (s.parts & DQMC_SERIES_GREEN_MATRIX) {
             const AccBlock& a = c->acc[ACC_FINE0 + 7];
             launch_series_green_sample(c->lc, c->hm, a.p, a.stride, s.sample, s.S, s.off[13], s.bad + (size_t)nparts * c->nb);
+            ++nparts;
+        }
+        if (s.parts & DQMC_SERIES_HUB_SCALARS) {
+            launch_hubbard_series_scalars(c->lc, c->hm, c->acc[ACC_SLICE].p, c->p.txhor, c->p.u, c->p.mux, s.sample, s.S, s.off[14],
+                                          s.bad + (size_t)nparts * c->nb);
+            ++nparts;
+        }
+        if (s.parts & DQMC_SERIES_HUB_EQ) {                 // the block has the count, [nch][N] layout of the SDW equal-time blocks
+            const AccBlock& a = c->acc[ACC_HUB_EQ];
+            if (!launch_series_eq_sample(c->lc, c->hm, a.p, a.n, HUB_EQ_CH, s.trig, s.sample, s.S, s.off[15], s.bad + (size_t)nparts * c->nb))
+                return fail(DQMC_EINVAL, who + ": the lattice is too large for the equal-time sample kernel's LDS");
+            ++nparts;
+        }
+        if (s.parts & DQMC_SERIES_HUB_TD) {
+            if (!launch_hubbard_series_td_sample(c->lc, c->hm, c->acc[ACC_HUB_TD].p, s.trig, s.sample, s.S, s.off[16], s.bad + (size_t)nparts * c->nb))
+                return fail(DQMC_EINVAL, who + ": the lattice is too large for the time-displaced sample kernel's LDS");
             ++nparts;
         }
         c->fam_launches[FAM_OTHER] += (uint64_t)nparts;
@@ -1177,6 +1205,24 @@ extern "C" int dqmc_series_custom_derived_host(dqmc_ctx* c, int qx, int qy, doub
 extern "C" int dqmc_series_custom_pair_derived_host(dqmc_ctx* c, int qx, int qy, double* value, double* err) {
     return series_ratio_derived(c, DQMC_SERIES_EQ_CUSTOM_PAIR, 12, c ? c->cpr_count : 0, qx, qy, value, err, "dqmc_series_custom_pair_derived_host",
                                 "pair operators");
+}
+// R, xi of the eight equal-time channels of a Hubbard series and S, R, xi of the rotation-summed spin channel at Q = (qx, qy)
+extern "C" int dqmc_series_hubbard_derived_host(dqmc_ctx* c, int qx, int qy, double* value, double* err) {
+    const std::string who = "dqmc_series_hubbard_derived_host";
+    if (!c || !value || !err) return fail(DQMC_EINVAL, "null argument");
+    const dqmc_ctx::Series& s = c->ser;
+    if (!s.open) return fail(DQMC_EINVAL, "no measurement series is open");
+    if (!(s.parts & DQMC_SERIES_HUB_EQ)) return fail(DQMC_EINVAL, who + ": the series has no equal-time part of the Hubbard model (DQMC_SERIES_HUB_EQ)");
+    if (qx < 0 || qx >= c->hm.L || qy < 0 || qy >= c->hm.L) return fail(DQMC_EINVAL, who + ": qx and qy must be in 0 .. L-1");
+    if (s.closed < 2) return fail(DQMC_EINVAL, who + ": the jackknife needs at least two closed bins");
+    (void)hipSetDevice(c->p.device);
+    const size_t n = (size_t)c->nb * s.S, nd = (size_t)19 * c->nb;
+    double* dv = s.stat + 2 * n;                            // the result rows behind the statistics (SERIES_AUX_ROWS of them): the calls are synchronous
+    { ProfScope ps(c, FAM_OTHER, 1); launch_series_hubbard_derived(c->lc, c->hm, s.bins, s.S, s.closed, s.off[15], qx, qy, dv, dv + nd); }
+    { const int rc = finish(c, who.c_str()); if (rc != DQMC_OK) return rc; }
+    HIPCHK(copy_sync(c, value, dv, nd * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(c, err, dv + nd, nd * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
 }
 // Bubble and vertex of every pair operator at Q = (qx, qy) (dqmc_hip.h): the bin means, then the two kernels of launch_series_pair_vertex.
 // The scratch buffer s.vertex holds the bubbles pb [nb][B + 1][m + 1][count], then value and err [nb][count][5 + m] each

@@ -65,7 +65,10 @@ DetHubbard::DetHubbard(const dethubbard_params& in, int nchains) : p_(in) {
     }
 }
 
-DetHubbard::~DetHubbard() { dqmc_destroy(ctx_); }
+DetHubbard::~DetHubbard() {
+    if (seriesOpen_) (void)dqmc_series_end(ctx_);
+    dqmc_destroy(ctx_);
+}
 
 void DetHubbard::updateInSlice(int k) {
     check(dqmc_update_slice(ctx_, k, 0), "updateInSlice");
@@ -101,6 +104,12 @@ void DetHubbard::sweepUp() {                                        // detmodel.
 void DetHubbard::sweep_skeleton(bool takeMeasurements) {
     const size_t need = (size_t)2 * N_ * m_;                        // per proposal: one draw for the site, at most one for Metropolis
     const size_t nb = ch_.size();
+    const bool feedSeries = takeMeasurements && seriesOpen_;
+    if (feedSeries) {                  // nothing is dropped silently, and nothing has changed yet
+        dqmc_series_state st;
+        check(dqmc_series_get_state(ctx_, &st), "dqmc_series_get_state");
+        if (st.bins_closed >= st.max_bins) throw GeneralError(DQMC_EINVAL, "the measurement series is full (maxBins bins are closed): read it out and end it");
+    }
     window_.resize(need * nb);
     for (size_t b = 0; b < nb; ++b) std::memcpy(&window_[b * need], ch_[b].rng.peek(need), need * sizeof(double));
     check(dqmc_push_uniforms_all_host(ctx_, window_.data(), need), "dqmc_push_uniforms_all_host");
@@ -129,6 +138,8 @@ void DetHubbard::sweep_skeleton(bool takeMeasurements) {
         ch_[b].lastAccRatio = st[b].lastAccRatio;
         if (takeMeasurements) finishMeasurements((int)b); else ch_[b].obs.valid = 0;
     }
+    if (takeMeasurements) corrStale_ = seriesNoHostCopy();
+    if (feedSeries) check(dqmc_series_add_sweep(ctx_), "dqmc_series_add_sweep");     // one sample of every chain, from the blocks on the device
 }
 
 void DetHubbard::sweep(bool takeMeasurements) { sweep_skeleton(takeMeasurements); }
@@ -152,14 +163,15 @@ void DetHubbard::finishMeasurements(int b) {
     o.eTotal = o.eKinetic + o.ePotential;
     ch_[b].zcorr.assign(N_, 0.0);
     for (int j = 0; j < N_; ++j) ch_[b].zcorr[j] = acc[6 + j] / m;
-    if (p_.measureFlags & DETHUBBARD_MEASURE_EQ) {                  // count, [8][N] raw sums -> C(d) = sum / (count N)
+    const bool copy = !seriesNoHostCopy();                          // without it the series' own flags report a block without a sample
+    if (copy && (p_.measureFlags & DETHUBBARD_MEASURE_EQ)) {        // count, [8][N] raw sums -> C(d) = sum / (count N)
         std::vector<double> blk(dqmc_hubbard_eq_accum_size(ctx_));
         check(dqmc_hubbard_eq_read_host(ctx_, blk.data()), "dqmc_hubbard_eq_read_host");
         if ((int)blk[0] != m_) throw GeneralError(DQMC_EINVAL, "measurement sweep did not bin the equal-time correlators on every time slice");
         ch_[b].eqCorr.assign(blk.size() - 1, 0.0);
         for (size_t i = 0; i + 1 < blk.size(); ++i) ch_[b].eqCorr[i] = blk[1 + i] / (m * N);
     }
-    if (p_.measureFlags & DETHUBBARD_MEASURE_TD) {                  // count[n-1], [n-1][6][N]
+    if (copy && (p_.measureFlags & DETHUBBARD_MEASURE_TD)) {        // count[n-1], [n-1][6][N]
         std::vector<double> blk(dqmc_hubbard_td_accum_size(ctx_));
         check(dqmc_hubbard_td_read_host(ctx_, blk.data()), "dqmc_hubbard_td_read_host");
         const size_t rows = (size_t)(n_ - 1), row = (blk.size() - rows) / (rows ? rows : 1);
@@ -174,13 +186,17 @@ void DetHubbard::finishMeasurements(int b) {
 
 void DetHubbard::getEqCorrelators(double* out, int b) const {
     if (!(p_.measureFlags & DETHUBBARD_MEASURE_EQ)) throw GeneralError(DQMC_EINVAL, "the equal-time correlators need DETHUBBARD_MEASURE_EQ in measureFlags");
-    if (!ch_[b].obs.valid) throw GeneralError(DQMC_EINVAL, "no measurement has been taken");
+    if (seriesNoHostCopy())
+        throw GeneralError(DQMC_EINVAL, "the correlators are not copied to the host while a series with DETHUBBARD_SERIES_NO_HOST_COPY is open: read the series");
+    if (!ch_[b].obs.valid || corrStale_) throw GeneralError(DQMC_EINVAL, "no measurement has been taken");
     std::memcpy(out, ch_[b].eqCorr.data(), ch_[b].eqCorr.size() * sizeof(double));
 }
 
 void DetHubbard::getTdCorrelators(double* out, int b) const {
     if (!(p_.measureFlags & DETHUBBARD_MEASURE_TD)) throw GeneralError(DQMC_EINVAL, "the time-displaced correlators need DETHUBBARD_MEASURE_TD in measureFlags");
-    if (!ch_[b].obs.valid) throw GeneralError(DQMC_EINVAL, "no measurement has been taken");
+    if (seriesNoHostCopy())
+        throw GeneralError(DQMC_EINVAL, "the correlators are not copied to the host while a series with DETHUBBARD_SERIES_NO_HOST_COPY is open: read the series");
+    if (!ch_[b].obs.valid || corrStale_) throw GeneralError(DQMC_EINVAL, "no measurement has been taken");
     std::memcpy(out, ch_[b].tdCorr.data(), ch_[b].tdCorr.size() * sizeof(double));
 }
 
@@ -213,6 +229,131 @@ void DetHubbard::getGreen(double* gUp, double* gDn, int b) {
             if (gUp) gUp[(size_t)j * N_ + i] = g[(size_t)j * ng + i].re;
             if (gDn) gDn[(size_t)j * N_ + i] = g[(size_t)(N_ + j) * ng + (N_ + i)].re;
         }
+}
+
+// ---- measurement series (include/dethubbard_host.h): one dqmc_series on the kernel context ----
+void DetHubbard::seriesBegin(int binSize, int maxBins, int flags) {
+    if (seriesOpen_) throw GeneralError(DQMC_EINVAL, "a measurement series is already open");
+    if (flags & ~DETHUBBARD_SERIES_NO_HOST_COPY) throw ParameterWrong("unknown flag of dethubbard_series_begin");
+    int parts = DQMC_SERIES_HUB_SCALARS;
+    if (p_.measureFlags & DETHUBBARD_MEASURE_EQ) parts |= DQMC_SERIES_HUB_EQ;
+    if ((p_.measureFlags & DETHUBBARD_MEASURE_TD) && n_ >= 2) parts |= DQMC_SERIES_HUB_TD;
+    if ((parts & DQMC_SERIES_HUB_EQ) && !dqmc_hubbard_eq_accum_size(ctx_)) {     // the first enable allocates the block; measurement sweeps switch it on themselves
+        check(dqmc_hubbard_set_equal_time_correlators(ctx_, 1), "dqmc_hubbard_set_equal_time_correlators");
+        check(dqmc_hubbard_set_equal_time_correlators(ctx_, 0), "dqmc_hubbard_set_equal_time_correlators");
+    }
+    check(dqmc_series_begin(ctx_, binSize, maxBins, 0, parts), "dqmc_series_begin");
+    seriesOpen_ = true; seriesParts_ = parts; seriesFlags_ = flags;
+}
+void DetHubbard::seriesEnd() {
+    if (!seriesOpen_) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
+    seriesOpen_ = false;
+    check(dqmc_series_end(ctx_), "dqmc_series_end");
+}
+void DetHubbard::seriesInfo(int* binsClosed, int* sweepsInOpenBin, size_t* sampleLen) {
+    if (!seriesOpen_) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
+    check(dqmc_series_info(ctx_, binsClosed, sweepsInOpenBin, sampleLen), "dqmc_series_info");
+}
+DetHubbard::SeriesSlice DetHubbard::seriesSlice(int which) {
+    if (!seriesOpen_) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
+    if (which < 0 || which >= DETHUBBARD_OBS_COUNT) throw ParameterWrong("the measurement series does not hold this observable");
+    const size_t N = (size_t)N_, rows = (size_t)(n_ > 1 ? n_ - 1 : 0);
+    int part;
+    SeriesSlice s{0, 1, 0, N};
+    if (which == DETHUBBARD_OBS_SCALARS) { part = 14; s.len = 8; }
+    else if (which == DETHUBBARD_OBS_ZCORR) { part = 14; s.off = 8; }
+    else if (which < DETHUBBARD_OBS_GREENUPTAU) { part = 15; s.off = (size_t)(which - DETHUBBARD_OBS_GREENUPCORR) * N; }   // C_X [8][N], then S_X [8][N]
+    else {                                                  // C_X [n-1][6][N], then S_X [n-1][6][N]: channel X of every row
+        part = 16;
+        const bool sq = which >= DETHUBBARD_OBS_GREENUPTAUSQ;
+        const size_t X = (size_t)(which - (sq ? DETHUBBARD_OBS_GREENUPTAUSQ : DETHUBBARD_OBS_GREENUPTAU));
+        s.off = (sq ? rows * 6 * N : 0) + X * N; s.rows = rows; s.stride = 6 * N;
+    }
+    if (!(seriesParts_ & (1 << part)))
+        throw ParameterWrong(part == 15 ? "the series has no equal-time part: the handle needs DETHUBBARD_MEASURE_EQ"
+                                        : "the series has no time-displaced part: the handle needs DETHUBBARD_MEASURE_TD and n >= 2");
+    size_t off = 0, len = 0;
+    check(dqmc_series_layout(ctx_, part, &off, &len), "dqmc_series_layout");
+    s.off += off;
+    return s;
+}
+void DetHubbard::seriesStats(int which, double* mean, double* err, int b) {
+    const SeriesSlice s = seriesSlice(which);
+    size_t S = 0;
+    check(dqmc_series_info(ctx_, nullptr, nullptr, &S), "dqmc_series_info");
+    std::vector<double> mu(ch_.size() * S), er(ch_.size() * S);
+    check(dqmc_series_stats_host(ctx_, mu.data(), er.data()), "dqmc_series_stats_host");
+    for (size_t j = 0; j < s.rows; ++j) {
+        std::memcpy(mean + j * s.len, &mu[(size_t)b * S + s.off + j * s.stride], s.len * sizeof(double));
+        std::memcpy(err + j * s.len, &er[(size_t)b * S + s.off + j * s.stride], s.len * sizeof(double));
+    }
+}
+void DetHubbard::seriesStatsAll(int which, double* mean, double* err) {
+    const SeriesSlice s = seriesSlice(which);
+    size_t S = 0;
+    check(dqmc_series_info(ctx_, nullptr, nullptr, &S), "dqmc_series_info");
+    std::vector<double> mu(ch_.size() * S), er(ch_.size() * S);
+    check(dqmc_series_stats_host(ctx_, mu.data(), er.data()), "dqmc_series_stats_host");
+    const size_t per = s.rows * s.len;
+    for (size_t b = 0; b < ch_.size(); ++b)
+        for (size_t j = 0; j < s.rows; ++j) {
+            std::memcpy(mean + b * per + j * s.len, &mu[b * S + s.off + j * s.stride], s.len * sizeof(double));
+            std::memcpy(err + b * per + j * s.len, &er[b * S + s.off + j * s.stride], s.len * sizeof(double));
+        }
+}
+void DetHubbard::seriesReadBins(int which, int first, int count, double* out, int b) {
+    const SeriesSlice s = seriesSlice(which);
+    if (count < 1) throw ParameterWrong("dethubbard_series_read_bins: count must be at least 1");
+    size_t S = 0;
+    check(dqmc_series_info(ctx_, nullptr, nullptr, &S), "dqmc_series_info");
+    check(dqmc_select_chain(ctx_, b), "dqmc_select_chain");
+    std::vector<double> buf((size_t)count * S);
+    check(dqmc_series_read_bins_host(ctx_, first, count, buf.data()), "dqmc_series_read_bins_host");
+    const size_t per = s.rows * s.len;
+    for (size_t i = 0; i < (size_t)count; ++i)
+        for (size_t j = 0; j < s.rows; ++j) std::memcpy(out + i * per + j * s.len, &buf[i * S + s.off + j * s.stride], s.len * sizeof(double));
+}
+void DetHubbard::seriesDerivedAll(int qx, int qy, double* value, double* err) {
+    if (!seriesOpen_) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
+    if (!(seriesParts_ & DQMC_SERIES_HUB_EQ)) throw ParameterWrong("the derived quantities need the equal-time part: the handle needs DETHUBBARD_MEASURE_EQ");
+    check(dqmc_series_hubbard_derived_host(ctx_, qx, qy, value, err), "dqmc_series_hubbard_derived_host");
+}
+void DetHubbard::seriesConfigure(int flags) {
+    if (!seriesOpen_) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
+    check(dqmc_series_configure(ctx_, flags), "dqmc_series_configure");
+}
+void DetHubbard::seriesRebin() {
+    if (!seriesOpen_) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
+    check(dqmc_series_rebin(ctx_), "dqmc_series_rebin");
+}
+void DetHubbard::seriesGetState(dqmc_series_state& out) {
+    if (!seriesOpen_) throw GeneralError(DQMC_EINVAL, "no measurement series is open");
+    check(dqmc_series_get_state(ctx_, &out), "dqmc_series_get_state");
+}
+void DetHubbard::seriesBinningAll(int which, int levels, double* err, double* tau) {
+    const SeriesSlice s = seriesSlice(which);
+    if (levels < 1 || levels > 12) throw ParameterWrong("dethubbard_series_binning: levels must be in 1..12");
+    size_t S = 0;
+    check(dqmc_series_info(ctx_, nullptr, nullptr, &S), "dqmc_series_info");
+    const size_t nb = ch_.size(), per = s.rows * s.len;
+    std::vector<double> e((size_t)levels * nb * S), t(tau ? e.size() : 0);
+    check(dqmc_series_binning_host(ctx_, levels, e.data(), tau ? t.data() : nullptr), "dqmc_series_binning_host");
+    for (size_t b = 0; b < nb; ++b)
+        for (size_t l = 0; l < (size_t)levels; ++l)
+            for (size_t j = 0; j < s.rows; ++j) {
+                const size_t at = (l * nb + b) * S + s.off + j * s.stride, to = (b * levels + l) * per + j * s.len;
+                std::memcpy(err + to, &e[at], s.len * sizeof(double));
+                if (tau) std::memcpy(tau + to, &t[at], s.len * sizeof(double));
+            }
+}
+void DetHubbard::seriesBinning(int which, int levels, double* err, double* tau, int b) {
+    const SeriesSlice s = seriesSlice(which);
+    if (levels < 1 || levels > 12) throw ParameterWrong("dethubbard_series_binning: levels must be in 1..12");
+    const size_t len = (size_t)levels * s.rows * s.len, nb = ch_.size();
+    std::vector<double> e(nb * len), t(tau ? nb * len : 0);
+    seriesBinningAll(which, levels, e.data(), tau ? t.data() : nullptr);
+    std::memcpy(err, &e[(size_t)b * len], len * sizeof(double));
+    if (tau) std::memcpy(tau, &t[(size_t)b * len], len * sizeof(double));
 }
 
 // ---- checkpoint / resume ----
@@ -265,6 +406,67 @@ void DetHubbard::loadState(const std::string& path) {
     check(dqmc_udv_setup(ctx_), "setupUdVStorage_and_calculateGreen");       // dethubbard.h:345-350
     performedSweeps_ = hdr[4];
     lastSweepDir_ = Up;
+}
+
+// ---- the series file, in the format of detsdw_series_save: magic, version, dqmc_series_state, the route [nchains] int32 (the identity:
+// this replica has no routing), then per chain the closed bins [bins_closed][S], the open bin [S] and, if the variance is tracked, w [S]
+// and m2 [S]
+namespace {
+const char kSeriesMagic[8] = {'D', 'Q', 'M', 'C', 'S', 'E', 'R', '1'};
+const int32_t kSeriesVersion = 1;
+size_t seriesExtra(int flags) { return (flags & DQMC_SERIES_TRACK_VARIANCE) ? 3 : 1; }     // blocks [nb][S] of an export behind the closed bins
+}  // namespace
+
+void DetHubbard::seriesSave(const std::string& path) {
+    dqmc_series_state st;
+    seriesGetState(st);
+    HubFile hf{std::fopen(path.c_str(), "wb")};
+    if (!hf.f) throw GeneralError(DQMC_EINVAL, "Could not open file " + path + " for writing");
+    hwr(hf.f, kSeriesMagic, 8); hwr(hf.f, &kSeriesVersion, sizeof(kSeriesVersion)); hwr(hf.f, &st, sizeof(st));
+    std::vector<int32_t> route(ch_.size());
+    for (size_t b = 0; b < route.size(); ++b) route[b] = (int32_t)b;
+    hwr(hf.f, route.data(), route.size() * sizeof(int32_t));
+    const size_t S = st.sample_len, B = (size_t)st.bins_closed, extra = seriesExtra(st.flags), n = ch_.size() * S;
+    std::vector<double> buf((B + extra) * n), row((B + extra) * S);
+    check(dqmc_series_export_host(ctx_, buf.data(), buf.size()), "dqmc_series_export_host");
+    for (size_t b = 0; b < ch_.size(); ++b) {                // the export is [block][chain][S]: gather the chain's rows
+        for (size_t k = 0; k < B + extra; ++k) std::memcpy(&row[k * S], &buf[k * n + b * S], S * sizeof(double));
+        hwr(hf.f, row.data(), row.size() * sizeof(double));
+    }
+}
+
+void DetHubbard::seriesLoad(const std::string& path) {
+    if (!seriesOpen_) throw GeneralError(DQMC_EINVAL, "no measurement series is open: dethubbard_series_begin with the options of the run first");
+    HubFile hf{std::fopen(path.c_str(), "rb")};
+    if (!hf.f) throw GeneralError(DQMC_EINVAL, "Could not open file " + path + " for reading");
+    char magic[8]; int32_t version = 0; dqmc_series_state st;
+    hrd(hf.f, magic, 8); hrd(hf.f, &version, sizeof(version)); hrd(hf.f, &st, sizeof(st));
+    if (std::memcmp(magic, kSeriesMagic, 8) != 0 || version != kSeriesVersion) throw GeneralError(DQMC_EINVAL, "series file: not a detqmc_amd series file of this version");
+    const int nch = (int)ch_.size();
+    if (st.nb != nch) throw ParameterWrong("series file: written for a different number of chains");
+    // the whole file is read and checked before the kernel context imports
+    dqmc_series_state own;
+    check(dqmc_series_get_state(ctx_, &own), "dqmc_series_get_state");
+    if (st.sample_len != own.sample_len || st.parts != own.parts || st.nfreq != own.nfreq)
+        throw ParameterWrong("series file: parts or the sample length differ from the open series");
+    if (st.bins_closed < 0 || st.bins_closed >= own.max_bins) throw ParameterWrong("series file: more closed bins than maxBins of the open series holds");
+    if (st.bin_size < 1 || st.sweeps_in_open_bin < 0 || st.sweeps_in_open_bin >= st.bin_size || st.samples < 0 || st.rebins < 0)
+        throw ParameterWrong("series file: bad counters");
+    if ((st.flags & ~(DQMC_SERIES_AUTO_REBIN | DQMC_SERIES_TRACK_VARIANCE)) || ((st.flags & DQMC_SERIES_AUTO_REBIN) && (own.max_bins < 4 || own.max_bins % 2)))
+        throw ParameterWrong("series file: its options are not valid for maxBins of the open series");
+    std::vector<int32_t> route((size_t)nch);
+    hrd(hf.f, route.data(), route.size() * sizeof(int32_t));
+    for (int b = 0; b < nch; ++b)
+        if (route[(size_t)b] != b) throw ParameterWrong("series file: a routed series (written under replica exchange) does not load into a Hubbard replica");
+    const size_t S = st.sample_len, B = (size_t)st.bins_closed, extra = seriesExtra(st.flags), n = (size_t)nch * S;
+    std::vector<double> slots((size_t)nch * (B + extra) * S);
+    hrd(hf.f, slots.data(), slots.size() * sizeof(double));
+    char more;
+    if (std::fread(&more, 1, 1, hf.f) != 0) throw GeneralError(DQMC_EINVAL, "series file: longer than its header says");
+    std::vector<double> buf((B + extra) * n);
+    for (size_t b = 0; b < (size_t)nch; ++b)
+        for (size_t k = 0; k < B + extra; ++k) std::memcpy(&buf[k * n + b * S], &slots[(b * (B + extra) + k) * S], S * sizeof(double));
+    check(dqmc_series_import_host(ctx_, &st, buf.data(), buf.size()), "dqmc_series_import_host");
 }
 
 }  // namespace detqmc
@@ -324,5 +526,48 @@ extern "C" int dethubbard_get_green_check(dethubbard_replica* r, double* out) {
     HGUARD(r->impl->getGreenCheck(out))
 }
 extern "C" int dethubbard_reset_green_check(dethubbard_replica* r) { HGUARD(r->impl->resetGreenCheck()) }
+extern "C" int dethubbard_series_begin(dethubbard_replica* r, int binSize, int maxBins, int flags) { HGUARD(r->impl->seriesBegin(binSize, maxBins, flags)) }
+extern "C" int dethubbard_series_end(dethubbard_replica* r) { HGUARD(r->impl->seriesEnd()) }
+extern "C" int dethubbard_series_info(dethubbard_replica* r, int* binsClosed, int* sweepsInOpenBin, size_t* sampleLen) {
+    HGUARD(r->impl->seriesInfo(binsClosed, sweepsInOpenBin, sampleLen))
+}
+extern "C" int dethubbard_series_stats(dethubbard_replica* r, int which, double* mean, double* err) {
+    if (!mean || !err) { g_hub_err = "null argument"; return DQMC_EINVAL; }
+    HGUARD(r->impl->seriesStats(which, mean, err, r->sel))
+}
+extern "C" int dethubbard_series_stats_all(dethubbard_replica* r, int which, double* mean, double* err) {
+    if (!mean || !err) { g_hub_err = "null argument"; return DQMC_EINVAL; }
+    HGUARD(r->impl->seriesStatsAll(which, mean, err))
+}
+extern "C" int dethubbard_series_read_bins(dethubbard_replica* r, int which, int first, int count, double* out) {
+    if (!out) { g_hub_err = "null argument"; return DQMC_EINVAL; }
+    HGUARD(r->impl->seriesReadBins(which, first, count, out, r->sel))
+}
+extern "C" int dethubbard_series_derived_all(dethubbard_replica* r, int qx, int qy, double* value, double* err) {
+    if (!value || !err) { g_hub_err = "null argument"; return DQMC_EINVAL; }
+    HGUARD(r->impl->seriesDerivedAll(qx, qy, value, err))
+}
+extern "C" int dethubbard_series_configure(dethubbard_replica* r, int flags) { HGUARD(r->impl->seriesConfigure(flags)) }
+extern "C" int dethubbard_series_rebin(dethubbard_replica* r) { HGUARD(r->impl->seriesRebin()) }
+extern "C" int dethubbard_series_get_state(dethubbard_replica* r, dqmc_series_state* out) {
+    if (!out) { g_hub_err = "null argument"; return DQMC_EINVAL; }
+    HGUARD(r->impl->seriesGetState(*out))
+}
+extern "C" int dethubbard_series_binning(dethubbard_replica* r, int which, int levels, double* err, double* tau) {
+    if (!err) { g_hub_err = "null argument"; return DQMC_EINVAL; }
+    HGUARD(r->impl->seriesBinning(which, levels, err, tau, r->sel))
+}
+extern "C" int dethubbard_series_binning_all(dethubbard_replica* r, int which, int levels, double* err, double* tau) {
+    if (!err) { g_hub_err = "null argument"; return DQMC_EINVAL; }
+    HGUARD(r->impl->seriesBinningAll(which, levels, err, tau))
+}
+extern "C" int dethubbard_series_save(dethubbard_replica* r, const char* path) {
+    if (!path) { g_hub_err = "null path"; return DQMC_EINVAL; }
+    HGUARD(r->impl->seriesSave(path))
+}
+extern "C" int dethubbard_series_load(dethubbard_replica* r, const char* path) {
+    if (!path) { g_hub_err = "null path"; return DQMC_EINVAL; }
+    HGUARD(r->impl->seriesLoad(path))
+}
 extern "C" double dethubbard_rng_rand01(dethubbard_replica* r) { return r ? r->impl->rand01(r->sel) : -1.0; }
 extern "C" dqmc_ctx* dethubbard_ctx(dethubbard_replica* r) { return r ? r->impl->ctx() : nullptr; }

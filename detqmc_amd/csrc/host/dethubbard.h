@@ -33,6 +33,21 @@ public:
     void getGreenCheck(double* out) { check(dqmc_green_check_read_host(ctx_, out), "dqmc_green_check_read_host"); }
     void resetGreenCheck() { check(dqmc_green_check_reset(ctx_), "dqmc_green_check_reset"); }
     dqmc_ctx* ctx() { return ctx_; }
+    // measurement series (include/dethubbard_host.h): one dqmc_series on the kernel context with the parts the handle's measureFlags provide
+    void seriesBegin(int binSize, int maxBins, int flags);
+    void seriesEnd();
+    void seriesInfo(int* binsClosed, int* sweepsInOpenBin, size_t* sampleLen);
+    void seriesStats(int which, double* mean, double* err, int b);
+    void seriesStatsAll(int which, double* mean, double* err);
+    void seriesReadBins(int which, int first, int count, double* out, int b);
+    void seriesDerivedAll(int qx, int qy, double* value, double* err);
+    void seriesConfigure(int flags);
+    void seriesRebin();
+    void seriesGetState(dqmc_series_state& out);
+    void seriesBinning(int which, int levels, double* err, double* tau, int b);
+    void seriesBinningAll(int which, int levels, double* err, double* tau);
+    void seriesSave(const std::string& path);
+    void seriesLoad(const std::string& path);
 
 private:
     enum SweepDirection { Up = +1, Down = -1 };
@@ -55,6 +70,15 @@ private:
     int performedSweeps_ = 0;
     bool measuring_ = false;
     bool measuringTD_ = false;        // ... with G(tau_j, 0) and its correlators after every interior advance (DETHUBBARD_MEASURE_TD)
+
+    // the open series: its parts (DQMC_SERIES_HUB_*) and the flags of seriesBegin; corrStale_: the last measurement sweep did not copy
+    // the correlator blocks (DETHUBBARD_SERIES_NO_HOST_COPY), eqCorr / tdCorr of the chains are not its values
+    bool seriesOpen_ = false, corrStale_ = false;
+    int seriesParts_ = 0, seriesFlags_ = 0;
+    // where observable `which` sits inside a sample: `rows` rows of `len` doubles, row j at off + j * stride
+    struct SeriesSlice { size_t off, rows, stride, len; };
+    SeriesSlice seriesSlice(int which);
+    bool seriesNoHostCopy() const { return seriesOpen_ && (seriesFlags_ & DETHUBBARD_SERIES_NO_HOST_COPY); }
 
     static void check(int rc, const char* what);
     void sweep_skeleton(bool takeMeasurements);

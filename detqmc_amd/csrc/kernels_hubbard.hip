@@ -268,3 +268,74 @@ void launch_hubbard_td_corr(const Launch& lc, const DevModel& hm, const cplx* GT
     const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
     hipLaunchKernelGGL(k_hubbard_corr<1>, grid, block, 0, lc.st, hm, GT0, sc, acc, row, rows, lc.cs, scs, acs);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The parts of a Hubbard context in the measurement series (DQMC_SERIES_HUB_*, dqmc_hip.h).  They follow the contract of
+// the series kernels in kernels_measure.hip: the blocks are only read, one writer per output element, a fixed summation order, no
+// atomics, no element of a chain depends on another chain or on the number of chains.  The equal-time part needs no kernel of its
+// own: ACC_HUB_EQ has the count, [nch][N] layout of k_series_eq_sample.
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Part 14 from the block of k_hubbard_measure, a[0 .. 5 + N]: the eight scalars of DetHubbard::finishMeasurements with cnt = a[5] for the
+// number of slices (occUp, occDn, occTotal, occDouble, localMoment, eKinetic, ePotential, eTotal), then zcorr[j] = a[6 + j] / cnt.
+// One workgroup per chain: thread 0 writes the scalars and the flag bad[chain] = 1 if cnt < 1, the lanes write zcorr.
+__global__ __launch_bounds__(64) void k_hubbard_series_scalars(const double* __restrict__ acc, size_t cs, double* __restrict__ sample, size_t S,
+                                                               size_t off, double* __restrict__ bad, int N, double t, double U, double mu) {
+    CHAIN(acc);
+    double* out = sample + (size_t)blockIdx.z * S + off;
+    const double cnt = acc[5];
+    if (threadIdx.x == 0) {
+        bad[blockIdx.z] = cnt >= 1.0 ? 0.0 : 1.0;
+        const double inv = 1.0 / ((double)N * cnt);
+        const double occUp = 1.0 - inv * acc[0], occDn = 1.0 - inv * acc[1], occTotal = occUp + occDn;
+        const double occDouble = 1.0 + inv * (acc[4] - acc[0] - acc[1]);
+        const double ePotential = U * occDouble;
+        const double eKinetic = (t / ((double)N * cnt)) * (acc[2] + acc[3]) - mu * occTotal;
+        out[0] = occUp; out[1] = occDn; out[2] = occTotal; out[3] = occDouble; out[4] = occTotal - 2 * occDouble;
+        out[5] = eKinetic; out[6] = ePotential; out[7] = eKinetic + ePotential;
+    }
+    for (int j = threadIdx.x; j < N; j += 64) out[8 + j] = acc[6 + j] / cnt;
+}
+void launch_hubbard_series_scalars(const Launch& lc, const DevModel& hm, const double* slice, double t, double U, double mu, double* sample, size_t S,
+                                   size_t off, double* bad) {
+    hipLaunchKernelGGL(k_hubbard_series_scalars, dim3(1, 1, lc.nb), dim3(64), 0, lc.st, slice, lc.cs, sample, S, off, bad, hm.N, t, U, mu);
+}
+// Part 16 from the block count[rows], [rows][HUB_TD_CH][N], rows = n - 1: C_X(d, tau_j) = sum / (N count_j) into out[j][X][d], the layout of
+// the block, and S_X(q, tau_j) = sum_d cos(q d) C_X(d, tau_j) into out[rows + j][X][q].  One workgroup per (channel X, row j, chain) stages
+// its C in LDS like k_series_eq_sample -- (3 N + 2 L) doubles -- and runs the same cosine sum.  bad[chain] = 1 if any count_j < 1: one
+// writer, thread 0 of the workgroup of channel 0 and row 0, which walks all the counts.
+__global__ __launch_bounds__(256) void k_hubbard_series_td_sample(const double* __restrict__ acc, size_t cs, const double* __restrict__ trig,
+                                                                  double* __restrict__ sample, size_t S, size_t off, double* __restrict__ bad, int L) {
+    extern __shared__ double hts_sm[];
+    CHAIN(acc);
+    const int tid = threadIdx.x, ch = blockIdx.x, j = blockIdx.y, rows = gridDim.y, N = L * L;
+    double* out = sample + (size_t)blockIdx.z * S + off;
+    double* C = hts_sm;                                     // [N]
+    double* Ac = C + N;                                     // [dy][qx]
+    double* As = Ac + N;
+    double* ct = As + N;                                    // [L]
+    double* st = ct + L;
+    if (ch == 0 && j == 0 && tid == 0) {
+        double flag = 0.0;
+        for (int r = 0; r < rows; ++r) if (!(acc[r] >= 1.0)) flag = 1.0;
+        bad[blockIdx.z] = flag;
+    }
+    for (int i = tid; i < L; i += 256) { ct[i] = trig[i]; st[i] = trig[L + i]; }
+    const size_t row = ((size_t)j * HUB_TD_CH + ch) * N;
+    const double den = (double)N * acc[j];
+    for (int d = tid; d < N; d += 256) {
+        const double v = acc[rows + row + d] / den;
+        C[d] = v;
+        out[row + d] = v;
+    }
+    __syncthreads();
+    series_cosine_sum(C, Ac, As, ct, st, out + (size_t)rows * HUB_TD_CH * N + row, L, tid);
+}
+bool launch_hubbard_series_td_sample(const Launch& lc, const DevModel& hm, const double* td, const double* trig, double* sample, size_t S, size_t off,
+                                     double* bad) {
+    const size_t lds = series_eq_sample_lds_bytes(hm.L);
+    if (lds > 152 * 1024) return false;
+    if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)k_hubbard_series_td_sample, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        (void)hipGetLastError();
+    hipLaunchKernelGGL(k_hubbard_series_td_sample, dim3(HUB_TD_CH, hm.n - 1, lc.nb), dim3(256), lds, lc.st, td, lc.cs, trig, sample, S, off, bad, hm.L);
+    return true;
+}

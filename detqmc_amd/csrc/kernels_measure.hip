@@ -2249,26 +2249,7 @@ __global__ __launch_bounds__(256) void k_series_eq_sample(const double* __restri
         out[(size_t)ch * N + d] = v;
     }
     __syncthreads();
-    for (int i = tid; i < N; i += 256) {
-        const int dy = i / L, qx = i - dy * L;
-        double sc = 0.0, ss = 0.0;
-        for (int dx = 0; dx < L; ++dx) {
-            const double v = C[dy * L + dx];
-            const int j = (qx * dx) % L;
-            sc += ct[j] * v; ss += st[j] * v;
-        }
-        Ac[i] = sc; As[i] = ss;
-    }
-    __syncthreads();
-    for (int q = tid; q < N; q += 256) {
-        const int qy = q / L, qx = q - qy * L;
-        double sq = 0.0;
-        for (int dy = 0; dy < L; ++dy) {
-            const int j = (qy * dy) % L;
-            sq += ct[j] * Ac[dy * L + qx] - st[j] * As[dy * L + qx];
-        }
-        out[(size_t)(nch + ch) * N + q] = sq;
-    }
+    series_cosine_sum(C, Ac, As, ct, st, out + (size_t)(nch + ch) * N, L, tid);
 }
 // false: the lattice is too large for the kernel's LDS, nothing was launched
 bool launch_series_eq_sample(const Launch& lc, const DevModel& hm, const double* eqacc, size_t eq_n, int nch, const double* trig, double* sample,
@@ -2447,6 +2428,87 @@ void launch_series_custom_derived(const Launch& lc, const DevModel& hm, const do
 void launch_series_band_derived(const Launch& lc, const DevModel& hm, const double* bins, size_t S, int B, size_t off, double* value, double* err) {
     SeriesBandDerivedShape a{S, off, hm.L, hm.N, lc.nb, B};
     hipLaunchKernelGGL(k_series_band_derived, dim3((unsigned)((lc.nb * 3 + 63) / 64)), dim3(64), 0, lc.st, bins, a, value, err);
+}
+
+// The derived quantities of a Hubbard series (dqmc_series_hubbard_derived_host), out[chain][19], from the S_X(q) half of the equal-time part
+// (off: offset of the part, S_X(q) of channel X at off + (8 + X) N) at the caller's Q = (qx, qy):
+//   0 .. 7   R_X = 1 - Sbar_X / S_X(Q), Sbar = 1/2 [S(Q + dx) + S(Q + dy)], for the eight channels (series_ratio_jackknife)
+//   8 .. 15  xi_X = sqrt(S_X(Q) / Sbar_X - 1) / (2 sin(pi / L)), the definition of xi_phi above
+//   16 .. 18 S(Q), R and xi of the rotation-summed spin channel S_spin = S_spinZZ + 2 S_spinXX, formed bin by bin
+// value = f(bin mean), err = jackknife over theta_(b) = f(x_(b)) about their mean.  NaN rule: value is NaN where the root's argument of
+// f(mean) is negative or a denominator vanishes; err is NaN where that holds for the mean or for any leave-one-out set; no other entry
+// is affected.  One thread per (chain, entry), bins in index order.
+struct SeriesHubbardDerivedShape { size_t S, off; int L, N, nb, B, qx, qy; double twosin; };
+// kind 0: S(Q), 1: R, 2: xi
+__device__ __forceinline__ double series_hubbard_derived_f(int kind, const double* x, double twosin) {
+    if (kind == 0) return x[0];
+    const double sbar = 0.5 * (x[1] + x[2]);
+    if (kind == 1) return x[0] != 0.0 ? 1.0 - sbar / x[0] : nan("");
+    if (sbar == 0.0) return nan("");
+    const double arg = x[0] / sbar - 1.0;
+    return arg >= 0.0 ? sqrt(arg) / twosin : nan("");
+}
+__global__ __launch_bounds__(64) void k_series_hubbard_derived(const double* __restrict__ bins, SeriesHubbardDerivedShape a, double* __restrict__ value,
+                                                               double* __restrict__ err) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= a.nb * 19) return;
+    const int chain = t / 19, e = t - chain * 19, L = a.L, B = a.B;
+    const size_t q[3] = {(size_t)a.qy * L + a.qx, (size_t)a.qy * L + (a.qx + 1) % L, (size_t)((a.qy + 1) % L) * L + a.qx};
+    const size_t n = (size_t)a.nb * a.S;
+    const double* p = bins + (size_t)chain * a.S;
+    const int X = e < 16 ? (e & 7) : 3;                      // the spin entries: spinZZ (3) + 2 spinXX (4)
+    const size_t base = a.off + (size_t)(8 + X) * a.N;
+    const size_t idx[3] = {base + q[0], base + q[1], base + q[2]};
+    if (e < 8) {
+        series_ratio_jackknife(p, n, B, idx, value[t], err[t]);
+        // the NaN rule for a vanishing S_X(Q), in the mean or in a leave-one-out set
+        double sum = 0.0;
+        for (int b = 0; b < B; ++b) sum += p[(size_t)b * n + idx[0]];
+        const double mu = sum / (double)B, tot = (double)B * mu;
+        bool bad = false;
+        for (int b = 0; b < B; ++b) bad = bad || (tot - p[(size_t)b * n + idx[0]]) / (double)(B - 1) == 0.0;
+        if (mu == 0.0) value[t] = nan("");
+        if (mu == 0.0 || bad) err[t] = nan("");
+        return;
+    }
+    const int kind = e < 16 ? 2 : e - 16;
+    const double w = e < 16 ? 0.0 : 2.0;                     // weight of the spinXX column next to spinZZ's
+    const size_t N = (size_t)a.N;
+    double mu[3], tot[3], x[3];
+    for (int j = 0; j < 3; ++j) {
+        double sum = 0.0;
+        for (int b = 0; b < B; ++b) {
+            const double* r = p + (size_t)b * n + idx[j];
+            sum += w != 0.0 ? r[0] + w * r[N] : r[0];
+        }
+        mu[j] = sum / (double)B; tot[j] = (double)B * mu[j];
+    }
+    double tsum = 0.0;
+    for (int b = 0; b < B; ++b) {
+        for (int j = 0; j < 3; ++j) {
+            const double* r = p + (size_t)b * n + idx[j];
+            x[j] = (tot[j] - (w != 0.0 ? r[0] + w * r[N] : r[0])) / (double)(B - 1);
+        }
+        tsum += series_hubbard_derived_f(kind, x, a.twosin);
+    }
+    const double tbar = tsum / (double)B;
+    double acc = 0.0;
+    for (int b = 0; b < B; ++b) {
+        for (int j = 0; j < 3; ++j) {
+            const double* r = p + (size_t)b * n + idx[j];
+            x[j] = (tot[j] - (w != 0.0 ? r[0] + w * r[N] : r[0])) / (double)(B - 1);
+        }
+        const double d = series_hubbard_derived_f(kind, x, a.twosin) - tbar;
+        acc += d * d;
+    }
+    const double v = series_hubbard_derived_f(kind, mu, a.twosin);
+    value[t] = v;
+    err[t] = v != v ? nan("") : sqrt((double)(B - 1) / (double)B * acc);      // a NaN theta_(b) has made acc NaN already
+}
+void launch_series_hubbard_derived(const Launch& lc, const DevModel& hm, const double* bins, size_t S, int B, size_t off, int qx, int qy,
+                                   double* value, double* err) {
+    SeriesHubbardDerivedShape a{S, off, hm.L, hm.N, lc.nb, B, qx, qy, 2.0 * std::sin(M_PI / (double)hm.L)};
+    hipLaunchKernelGGL(k_series_hubbard_derived, dim3((unsigned)((lc.nb * 19 + 63) / 64)), dim3(64), 0, lc.st, bins, a, value, err);
 }
 
 // ---- the order-parameter part of the sample (DQMC_SERIES_PHI): chi_phi(q, i omega_n) and five scalars straight from the field ----

@@ -182,6 +182,8 @@ def custom_pair_ratio(name):
 
 # bit 13: the normalised averaged Green's function of every slice (set_green_matrix), [m+1][N][R][R] complex
 SERIES_GREEN_MATRIX = 8192
+# the parts of a Hubbard context (part indices 14 .. 16): scalars and zcorr, the equal-time and the time-displaced correlators
+SERIES_HUB_SCALARS, SERIES_HUB_EQ, SERIES_HUB_TD = 16384, 32768, 65536
 # derived series quantities of the pair vertex (DetSDWBatch.series_derived_all): name prefix -> entry of detsdw_series_pair_vertex
 PAIR_VERTEX_QUANTITIES = {"vertexCustomPair": 0, "bubbleCustomPair": 1, "gammaCustomPair": 2, "gammaBubbleCustomPair": 3}
 
@@ -902,7 +904,8 @@ class KernelContext:
 
     def series_layout(self, part):
         """(offset, length) of part 0 (equal-time: C_X(d) [5][N], S_X(q) [5][N]), 1 + channel (Matsubara, [component][nfreq][N] (re, im)), 6
-        (order parameter), 7 (Matsubara of the band channel), 8 (equal-time band: C_X(d) [2][N], S_X(q) [2][N]), 9 (Matsubara of the custom
+        (order parameter; 14 .. 16: a Hubbard context's scalars + zcorr, C_X(d) / S_X(q) [8][N] each, C_X(d, tau_j) / S_X(q, tau_j) [n-1][6][N]
+        each), 7 (Matsubara of the band channel), 8 (equal-time band: C_X(d) [2][N], S_X(q) [2][N]), 9 (Matsubara of the custom
         bilinears), 10 (their equal-time block: C(d) [count][N], S(q) [count][N]), 11 and 12 (the same two of the custom pair operators)"""
         off, ln = C.c_size_t(0), C.c_size_t(0)
         check(self.lib.dqmc_series_layout(self.h, int(part), C.byref(off), C.byref(ln)))
@@ -972,6 +975,14 @@ class KernelContext:
         v, e = np.zeros(max(n, 1)), np.zeros(max(n, 1))
         check(self.lib.dqmc_series_ph_vertex_host(self.h, int(Q[0]), int(Q[1]), v.ctypes.data_as(_lib._DP), e.ctypes.data_as(_lib._DP)))
         return v.reshape(self.nchains_total(), -1, 6 + self.m), e.reshape(self.nchains_total(), -1, 6 + self.m)
+
+    def series_hubbard_derived(self, Q):
+        """(value, err), (nchains, 19) each, of a Hubbard context's series with SERIES_HUB_EQ at Q = (qx, qy) in units of 2 pi / L: R_X
+        (entries 0 .. 7) and xi_X (8 .. 15) of greenUp, greenDn, charge, spinZZ, spinXX, pairS, pairSx, pairD, then S(Q), R and xi of
+        the rotation-summed spin channel spinZZ + 2 spinXX; NaN where the quantity is undefined"""
+        v, e = np.zeros((self.nchains_total(), 19)), np.zeros((self.nchains_total(), 19))
+        check(self.lib.dqmc_series_hubbard_derived_host(self.h, int(Q[0]), int(Q[1]), v.ctypes.data_as(_lib._DP), e.ctypes.data_as(_lib._DP)))
+        return v, e
 
     def series_phi_derived(self):
         """(value, err), (nchains, 6) each, of a series with SERIES_PHI: the jackknifed Binder cumulant and ratio of |phibar|, beta N
@@ -1923,6 +1934,21 @@ class HubbardParams:
 HUBBARD_EQ_CORRELATORS = {"greenUpCorr": 0, "greenDnCorr": 1, "chargeCorr": 2, "spinZZCorr": 3, "spinXXCorr": 4, "pairSCorr": 5,
                           "pairSxCorr": 6, "pairDCorr": 7}
 HUBBARD_TD_CORRELATORS = {"greenUpTau": 0, "greenDnTau": 1, "chargeTau": 2, "spinZZTau": 3, "spinXXTau": 4, "pairSTau": 5}
+HUBBARD_SCALARS = ("occUp", "occDn", "occTotal", "occDouble", "localMoment", "eKinetic", "ePotential", "eTotal")
+# DetHubbard.series_*: name -> observable index of dethubbard_series_* ('...Sq' = S_X(q) of '...Corr', '...TauSq' of '...Tau')
+HUBBARD_SERIES_OBS = {"scalars": _lib.DETHUBBARD_OBS_SCALARS, "zcorr": _lib.DETHUBBARD_OBS_ZCORR}
+for _n, _x in HUBBARD_EQ_CORRELATORS.items():
+    HUBBARD_SERIES_OBS[_n] = _lib.DETHUBBARD_OBS_GREENUPCORR + _x
+    HUBBARD_SERIES_OBS[_n[:-4] + "Sq"] = _lib.DETHUBBARD_OBS_GREENUPSQ + _x
+for _n, _x in HUBBARD_TD_CORRELATORS.items():
+    HUBBARD_SERIES_OBS[_n] = _lib.DETHUBBARD_OBS_GREENUPTAU + _x
+    HUBBARD_SERIES_OBS[_n + "Sq"] = _lib.DETHUBBARD_OBS_GREENUPTAUSQ + _x
+# DetHubbard.series_derived_all: name -> entry of dqmc_series_hubbard_derived_host; the channels whose default Q is (L/2, L/2)
+HUBBARD_SERIES_DERIVED = {"S_spin": 16, "R_spin": 17, "xi_spin": 18}
+for _n, _x in HUBBARD_EQ_CORRELATORS.items():
+    HUBBARD_SERIES_DERIVED["R_" + _n[:-4]] = _x
+    HUBBARD_SERIES_DERIVED["xi_" + _n[:-4]] = 8 + _x
+HUBBARD_Q_PI_PI = ("charge", "spinZZ", "spinXX", "spin")
 
 
 def _hubbard_host_params(pars: HubbardParams):
@@ -2035,6 +2061,116 @@ class DetHubbard(_GreenCheck):
 
     def save_state(self, path):
         check(self.lib.dethubbard_save_state(self.h, str(path).encode()), host="hubbard")
+
+    # ---- measurement series: bins over measurement sweeps and jackknife errors on the device ----
+    def series_begin(self, binSize, maxBins, host_copy=True, auto_rebin=False, track_variance=False):
+        """open a measurement series on the device: from now on every sweep(True) adds one sample per chain -- 'scalars' (the eight of
+        `observables`, in that order) and 'zcorr' always, the '...Corr' vectors and their structure factors '...Sq' with
+        equalTimeCorrelators, the '...Tau' rows and '...TauSq' ('greenUpTauSq' = Re G_up(k, tau_j)) with timeDisplacedCorrelators -- to bins
+        of binSize sweeps, at most maxBins of them.  host_copy=False: measurement sweeps no longer copy the correlator blocks to the host
+        (the '...Corr' / '...Tau' names of observable_vector raise while the series is open; observables and zcorr stay).
+        auto_rebin: whenever maxBins (even, >= 4) bins are closed, neighbouring bins are merged; track_variance: keep the variance of
+        the single samples, which series_binning_all needs for tau"""
+        flags = 0 if host_copy else _lib.DETHUBBARD_SERIES_NO_HOST_COPY
+        check(self.lib.dethubbard_series_begin(self.h, int(binSize), int(maxBins), flags), host="hubbard")
+        self._series_open = True
+        if auto_rebin or track_variance:
+            opts = (_lib.DQMC_SERIES_AUTO_REBIN if auto_rebin else 0) | (_lib.DQMC_SERIES_TRACK_VARIANCE if track_variance else 0)
+            try:
+                check(self.lib.dethubbard_series_configure(self.h, opts), host="hubbard")
+            except _lib.DqmcError:
+                self.lib.dethubbard_series_end(self.h)     # refused options: no half-configured series stays open
+                self._series_open = False
+                raise
+
+    def series_is_open(self):
+        return getattr(self, "_series_open", False)
+
+    def series_info(self):
+        """(bins closed, sweeps in the open bin, doubles per sample)"""
+        a, b, s = C.c_int(0), C.c_int(0), C.c_size_t(0)
+        check(self.lib.dethubbard_series_info(self.h, C.byref(a), C.byref(b), C.byref(s)), host="hubbard")
+        return a.value, b.value, s.value
+
+    def _series_shape(self, name):
+        """(observable index, per-chain shape) of a series name"""
+        if name not in HUBBARD_SERIES_OBS:
+            raise KeyError(name)
+        i = self.info
+        if name == "scalars":
+            return HUBBARD_SERIES_OBS[name], (8,)
+        if name.endswith("Tau") or name.endswith("TauSq"):
+            return HUBBARD_SERIES_OBS[name], (max(i.n - 1, 0), i.N)
+        return HUBBARD_SERIES_OBS[name], (i.N,)
+
+    def series_stats(self, name):
+        """(mean, err) of a series observable over the closed bins, jackknife, selected chain"""
+        which, shape = self._series_shape(name)
+        mean, err = np.zeros(shape), np.zeros(shape)
+        check(self.lib.dethubbard_series_stats(self.h, which, mean.ctypes.data_as(_lib._DP), err.ctypes.data_as(_lib._DP)), host="hubbard")
+        return mean, err
+
+    def series_stats_all(self, name):
+        """series_stats of every chain: (mean, err), (nchains,) + the per-chain shape each; one device call"""
+        which, shape = self._series_shape(name)
+        mean, err = np.zeros((self.nchains,) + shape), np.zeros((self.nchains,) + shape)
+        check(self.lib.dethubbard_series_stats_all(self.h, which, mean.ctypes.data_as(_lib._DP), err.ctypes.data_as(_lib._DP)), host="hubbard")
+        return mean, err
+
+    def series_bins(self, name, first=0, count=None):
+        """closed bins first .. first + count - 1 (default: all from first) of a series observable, selected chain: (count,) + shape"""
+        which, shape = self._series_shape(name)
+        count = self.series_info()[0] - first if count is None else int(count)
+        out = np.zeros((max(count, 0),) + shape)
+        check(self.lib.dethubbard_series_read_bins(self.h, which, int(first), count, out.ctypes.data_as(_lib._DP)), host="hubbard")
+        return out
+
+    def series_derived_all(self, name, Q=None):
+        """(value, err) per chain of a jackknifed derived quantity of the equal-time structure factors at Q = (qx, qy) in units of
+        2 pi / L: 'R_<channel>' = 1 - Sbar / S(Q) with Sbar = [S(Q + dx) + S(Q + dy)] / 2, 'xi_<channel>' = sqrt(S(Q) / Sbar - 1) /
+        (2 sin(pi / L)) for channel in greenUp, greenDn, charge, spinZZ, spinXX, pairS, pairSx, pairD, and 'S_spin', 'R_spin', 'xi_spin'
+        of the rotation-summed spin channel spinZZ + 2 spinXX.  Default Q: (L/2, L/2) for charge, spinZZ, spinXX and spin, (0, 0) for the
+        Green and pairing channels.  NaN where the root's argument is negative or a denominator vanishes"""
+        at = HUBBARD_SERIES_DERIVED[name]
+        if Q is None:
+            L = self.info.L
+            Q = (L // 2, L // 2) if name.split("_", 1)[1] in HUBBARD_Q_PI_PI else (0, 0)
+        v, e = np.zeros((self.nchains, 19)), np.zeros((self.nchains, 19))
+        check(self.lib.dethubbard_series_derived_all(self.h, int(Q[0]), int(Q[1]), v.ctypes.data_as(_lib._DP), e.ctypes.data_as(_lib._DP)), host="hubbard")
+        return v[:, at].copy(), e[:, at].copy()
+
+    def series_binning_all(self, name, levels):
+        """binning analysis of every chain: (err, tau), (nchains, levels) + the per-chain shape each -- the jackknife error over the bins
+        merged l times and the integrated autocorrelation time in sweeps it implies; tau is None without track_variance"""
+        which, shape = self._series_shape(name)
+        full = (self.nchains, max(int(levels), 0)) + shape
+        err = np.zeros(full)
+        tau = np.zeros(full) if self.series_state().flags & _lib.DQMC_SERIES_TRACK_VARIANCE else None
+        check(self.lib.dethubbard_series_binning_all(self.h, which, int(levels), err.ctypes.data_as(_lib._DP),
+                                                     tau.ctypes.data_as(_lib._DP) if tau is not None else None), host="hubbard")
+        return err, tau
+
+    def series_rebin(self):
+        """merge neighbouring closed bins of every chain: half as many bins of twice the size"""
+        check(self.lib.dethubbard_series_rebin(self.h), host="hubbard")
+
+    def series_state(self):
+        """the dqmc_series_state of the open series"""
+        st = _lib.dqmc_series_state()
+        check(self.lib.dethubbard_series_get_state(self.h, C.byref(st)), host="hubbard")
+        return st
+
+    def series_save(self, path):
+        """the whole series -- bins, open bin, counters, variance -- to a file of its own, next to save_state"""
+        check(self.lib.dethubbard_series_save(self.h, str(path).encode()), host="hubbard")
+
+    def series_load(self, path):
+        """restore a series_save file into the open series (series_begin with the options of the run first)"""
+        check(self.lib.dethubbard_series_load(self.h, str(path).encode()), host="hubbard")
+
+    def series_end(self):
+        check(self.lib.dethubbard_series_end(self.h), host="hubbard")
+        self._series_open = False
 
     def load_state(self, path):
         check(self.lib.dethubbard_load_state(self.h, str(path).encode()), host="hubbard")

@@ -71,7 +71,8 @@ int dethubbard_get_observables(dethubbard_replica* r, dethubbard_observables* ou
 int dethubbard_get_zcorr(dethubbard_replica* r, double* out /* [N] */);
 /* Normalised correlators C_X(d) = sum / (count N) of the last measurement sweep, selected chain, index dy L + dx (dqmc_hip.h: Hubbard
  * model).  Equal time: greenUp, greenDn, charge, spinZZ, spinXX, pairS, pairSx, pairD; time-displaced: the first six at tau_j = j s dtau,
- * j = 1 .. n-1.  DQMC_EINVAL without the flag or before a measurement sweep. */
+ * j = 1 .. n-1.  DQMC_EINVAL without the flag, before a measurement sweep, and while a series with DETHUBBARD_SERIES_NO_HOST_COPY is
+ * open (below).  Values of ONE sweep; averages and error bars over sweeps: the measurement series at the end of this header. */
 int dethubbard_get_eq_correlators(dethubbard_replica* r, double* out /* [8][N] */);
 int dethubbard_get_td_correlators(dethubbard_replica* r, double* out /* [n-1][6][N] */);
 /* Checkpoint / resume (what DetQMC::saveState keeps for the replica: auxfield, src/dethubbard.h:352-358, plus the position of
@@ -88,6 +89,49 @@ int dethubbard_set_green_check(dethubbard_replica* r, int on);
 int dethubbard_get_green_check(dethubbard_replica* r, double* out);
 int dethubbard_reset_green_check(dethubbard_replica* r);
 dqmc_ctx* dethubbard_ctx(dethubbard_replica* r);
+
+/* Measurement series: bins over measurement sweeps and jackknife errors, kept on the device (dqmc_series_* with the DQMC_SERIES_HUB_*
+ * parts, dqmc_hip.h).  The calls have the semantics of their detsdw_series_* namesakes (detsdw_host.h).
+ * dethubbard_series_begin: the parts follow from the handle -- scalars and zcorr always, the equal-time part with DETHUBBARD_MEASURE_EQ,
+ *   the time-displaced part with DETHUBBARD_MEASURE_TD and n >= 2.  flags: DETHUBBARD_SERIES_NO_HOST_COPY or 0; any other bit is
+ *   ParameterWrong.  While the series is open every dethubbard_sweep(r, 1) ends with one sample of every chain added to the series;
+ *   thermalisation sweeps and dethubbard_sweep(r, 0) add nothing.  A measurement sweep on a full series (maxBins bins closed, no
+ *   automatic re-binning) fails with DQMC_EINVAL before it pushes uniforms or touches the field.  The Markov chain does not depend on
+ *   the series or its flags.
+ *   DETHUBBARD_SERIES_NO_HOST_COPY: while the series is open a measurement sweep does not read the equal-time and time-displaced blocks
+ *   back; dethubbard_get_eq_correlators / _td_correlators fail with a message that names NO_HOST_COPY, and a block without a sample is
+ *   reported by the series' own flags.  The scalars and zcorr of dethubbard_get_observables / _get_zcorr are still filled.
+ * Readers take an observable index DETHUBBARD_OBS_*: SCALARS [8] (the order of dethubbard_observables), ZCORR [N], the eight C_X(d) [N]
+ *   (DETHUBBARD_OBS_GREENUPCORR + X) and S_X(q) [N] (DETHUBBARD_OBS_GREENUPSQ + X, column qy L + qx) of the equal-time channels, the six
+ *   C_X(d, tau_j) [n-1][N] (DETHUBBARD_OBS_GREENUPTAU + X) and S_X(q, tau_j) [n-1][N] (DETHUBBARD_OBS_GREENUPTAUSQ + X; for greenUp,
+ *   greenDn: Re G_s(k, tau_j)).  An index whose part the series lacks is ParameterWrong.
+ *   dethubbard_series_stats: mean and err of `which`, the selected chain; _stats_all: every chain, [nchains] x the same;
+ *   _read_bins: closed bins first .. first + count - 1 of `which`, selected chain; _binning / _binning_all: err (and tau unless NULL;
+ *   tau needs DQMC_SERIES_TRACK_VARIANCE) [levels] x the shape, _all: [nchains][levels] x the shape.
+ *   dethubbard_series_derived_all: value[nchains][19], err[nchains][19] of dqmc_series_hubbard_derived_host at Q = (qx, qy).
+ * dethubbard_series_configure / _rebin / _get_state: dqmc_series_configure / _rebin / _get_state of the kernel context.
+ * dethubbard_series_save / _load: the series file of detsdw_series_save -- magic "DQMCSER1", int32 version, dqmc_series_state, the route
+ *   [nchains] int32 (written as the identity: this replica has no routing), then per chain the closed bins [bins_closed][S], the open bin
+ *   [S] and, if the variance is tracked, w [S] and m2 [S].  _load needs an open series with the same number of chains, parts and sample
+ *   length; every refusal leaves the series as it was.  dethubbard_save_state / _load_state and their file do not change: a checkpoint
+ *   of a run with a series is the two files.  dethubbard_destroy ends an open series. */
+enum { DETHUBBARD_SERIES_NO_HOST_COPY = 1 };
+enum { DETHUBBARD_OBS_SCALARS = 0, DETHUBBARD_OBS_ZCORR = 1, DETHUBBARD_OBS_GREENUPCORR = 2, DETHUBBARD_OBS_GREENUPSQ = 10,
+       DETHUBBARD_OBS_GREENUPTAU = 18, DETHUBBARD_OBS_GREENUPTAUSQ = 24, DETHUBBARD_OBS_COUNT = 30 };
+int dethubbard_series_begin(dethubbard_replica* r, int binSize, int maxBins, int flags);
+int dethubbard_series_info(dethubbard_replica* r, int* binsClosed, int* sweepsInOpenBin, size_t* sampleLen);
+int dethubbard_series_stats(dethubbard_replica* r, int which, double* mean, double* err);
+int dethubbard_series_stats_all(dethubbard_replica* r, int which, double* mean, double* err);
+int dethubbard_series_read_bins(dethubbard_replica* r, int which, int first, int count, double* out);
+int dethubbard_series_derived_all(dethubbard_replica* r, int qx, int qy, double* value, double* err);
+int dethubbard_series_configure(dethubbard_replica* r, int flags);
+int dethubbard_series_rebin(dethubbard_replica* r);
+int dethubbard_series_get_state(dethubbard_replica* r, dqmc_series_state* out);
+int dethubbard_series_binning(dethubbard_replica* r, int which, int levels, double* err, double* tau);
+int dethubbard_series_binning_all(dethubbard_replica* r, int which, int levels, double* err, double* tau);
+int dethubbard_series_save(dethubbard_replica* r, const char* path);
+int dethubbard_series_load(dethubbard_replica* r, const char* path);
+int dethubbard_series_end(dethubbard_replica* r);
 
 #ifdef __cplusplus
 }

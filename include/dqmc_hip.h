@@ -697,7 +697,7 @@ int dqmc_measure_td_fine_read_host(dqmc_ctx* ctx, int channel, double* out);
  * identical bits.  The device result buffer lies outside the arena, is allocated on first use and freed with the context. */
 size_t dqmc_measure_td_matsubara_size(dqmc_ctx* ctx, int channel, int nfreq);
 int dqmc_measure_td_matsubara_host(dqmc_ctx* ctx, int channel, int nfreq, double* out);
-/* ---- measurement series: bins over sweeps and jackknife errors on the device (SDW model only) ----------
+/* ---- measurement series: bins over sweeps and jackknife errors on the device (the parts of a Hubbard context: below) ----------
  * One sample per measurement sweep, formed from the blocks above as they stand and accumulated into bins of bin_size sweeps; nothing is
  * copied per sweep.  All run-time calls: dqmc_params stays byte for byte.
  * parts (bit mask): bit 0 = the equal-time block (needs dqmc_measure_eq_accum_size != 0); bits 1 .. 4 = the Matsubara transform of
@@ -710,8 +710,8 @@ int dqmc_measure_td_matsubara_host(dqmc_ctx* ctx, int channel, int nfreq, double
  *           same kernel, launched with the sample buffer as its target
  * dqmc_series_begin allocates, outside the arena, the sample [nb][S], the open bin [nb][S], the closed bins [max_bins][nb][S], the
  * per-part flags and the result buffer of the statistics calls.  DQMC_EINVAL: empty or unknown mask, a missing block, bin_size < 1,
- * max_bins < 2, a series already open, a Hubbard context, a lattice too large for the LDS of the Matsubara or sample kernel.
- * dqmc_series_layout: where part (= bit number 0 .. 4, 6: the order-parameter part, 7, 8: the band parts, 9 .. 13, all below) sits inside S.
+ * max_bins < 2, a series already open, any of these parts on a Hubbard context, a lattice too large for the LDS of the Matsubara or sample kernel.
+ * dqmc_series_layout: where part (= bit number 0 .. 4, 6: the order-parameter part, 7, 8: the band parts, 9 .. 13, 14 .. 16: the Hubbard parts, all below) sits inside S.
  * dqmc_series_add_sweep (all chains): forms the sample and adds it to the open bin, open += sample, in call order; the bin_size-th call
  * writes closed[k] = open / bin_size and clears the open bin.  DQMC_EINVAL with no bin changed: the equal-time count of any chain or a
  * fine row count of any chain and channel of the mask is < 1; max_bins bins are already closed (nothing is dropped silently, and there
@@ -818,6 +818,29 @@ int dqmc_measure_td_matsubara_host(dqmc_ctx* ctx, int channel, int nfreq, double
  * summation order (no atomics, identical bits, independent of batching) as dqmc_series_pair_vertex_host; the bubble kernel stages rows
  * k and m - k.  DQMC_EINVAL with nothing touched: a series without bit 9 or bit 13, B < 2, qx or qy outside 0 .. L-1, no bilinear set, a
  * lattice whose two rows do not fit the LDS (4 R^2 N doubles + 8 KiB > 152 KiB). */
+/* The parts of a Hubbard context, behind all of the above (every older mask keeps its S, its offsets and its bits).  A Hubbard context
+ * accepts any non-empty subset of 0x1c000 and no other bit; an SDW context keeps its mask 0x3fdf and refuses the three; every refusal is
+ * DQMC_EINVAL with nothing allocated.  nfreq is ignored on a Hubbard context and stored as 0.  Formed from the blocks as they stand:
+ *   DQMC_SERIES_HUB_SCALARS = 16384 (bit 14, 8 + N doubles; needs nothing: the block of dqmc_measure_slice always exists): from
+ *     a[0 .. 5 + N] of dqmc_measure_read_host with cnt = a[5] and K = N cnt: occUp = 1 - a[0] / K, occDn = 1 - a[1] / K, occTotal,
+ *     occDouble = 1 + (a[4] - a[0] - a[1]) / K, localMoment = occTotal - 2 occDouble, eKinetic = txhor (a[2] + a[3]) / K - mux occTotal,
+ *     ePotential = u occDouble, eTotal, in this order, then zcorr[j] = a[6 + j] / cnt.  The chain is flagged if cnt < 1.
+ *   DQMC_SERIES_HUB_EQ = 32768 (bit 15, 16 N; needs dqmc_hubbard_eq_accum_size != 0): C_X(d) [8][N] then S_X(q) [8][N], X = greenUp,
+ *     greenDn, charge, spinZZ, spinXX, pairS, pairSx, pairD, formed like bit 0 by the same kernel.
+ *   DQMC_SERIES_HUB_TD = 65536 (bit 16, 12 (n-1) N; needs dqmc_hubbard_td_accum_size != 0 and n >= 2): C_X(d, tau_j) [n-1][6][N] =
+ *     sum / (double(N) count_j) in the layout of the block, then S_X(q, tau_j) [n-1][6][N] by the cosine sum of bit 0 (same table, same
+ *     integer phase reduction, same order); for greenUp, greenDn the second half is Re G_s(k = q, tau_j).  Flagged if any count_j < 1.
+ * dqmc_series_hubbard_derived_host(qx, qy) (all chains, value and err [nb][19]; DQMC_EINVAL with nothing touched for a series without bit
+ * 15, B < 2, qx or qy outside 0 .. L-1).  With Q = (qx, qy), Sbar_X = 1/2 [S_X(Q + dx) + S_X(Q + dy)], indices mod L:
+ *   0 .. 7:   R_X = 1 - Sbar_X / S_X(Q) for the eight channels
+ *   8 .. 15:  xi_X = sqrt(S_X(Q) / Sbar_X - 1) / (2 sin(pi / L))
+ *   16 .. 18: S(Q), R and xi of the rotation-summed spin channel S_spin = S_spinZZ + 2 S_spinXX (= <S.S>), summed bin by bin
+ * value = f(bin mean), err = the jackknife of dqmc_series_derived_host.  value is NaN where the root's argument of f(mean) is negative or
+ * a denominator vanishes; err is NaN where that holds for the mean or for any leave-one-out set; no other entry is affected.
+ * Everything else -- accumulate, routed accumulate, re-binning, running variance, statistics, binning analysis, export / import --
+ * treats a sample as S doubles and serves these parts unchanged. */
+enum { DQMC_SERIES_HUB_SCALARS = 16384, DQMC_SERIES_HUB_EQ = 32768, DQMC_SERIES_HUB_TD = 65536 };
+int dqmc_series_hubbard_derived_host(dqmc_ctx* ctx, int qx, int qy, double* value, double* err);
 enum { DQMC_SERIES_EQ = 1, DQMC_SERIES_MATS_G = 2, DQMC_SERIES_MATS_PAIR = 4, DQMC_SERIES_MATS_PH = 8, DQMC_SERIES_MATS_CURRENT = 16,
        DQMC_SERIES_PHI = 64, DQMC_SERIES_MATS_BAND = 128, DQMC_SERIES_EQ_BAND = 256, DQMC_SERIES_MATS_CUSTOM = 512, DQMC_SERIES_EQ_CUSTOM = 1024,
        DQMC_SERIES_MATS_CUSTOM_PAIR = 2048, DQMC_SERIES_EQ_CUSTOM_PAIR = 4096, DQMC_SERIES_GREEN_MATRIX = 8192 };
