@@ -19,6 +19,7 @@ class DqmcError(RuntimeError):
 
 
 DQMC_TD_EVERY_SLICE = 0x100     # flag bit of dqmc_params.timedisplaced
+DQMC_TD_HUB_EVERY_SLICE = 0x400  # flag bit of dqmc_params.timedisplaced, Hubbard model: the every-slice reservation
 DETSDW_TD_EVERY_SLICE = 0x100   # flag bit of detsdw_params.timeDisplacedMeasurements
 DETSDW_TD_FINE_ON_DEVICE = 0x200  # flag bit of detsdw_params.timeDisplacedMeasurements: the fine blocks stay on the device
 DETSDW_OBS_FINE = 0x100         # flag bit of the observable index: the every-slice twin
@@ -165,7 +166,7 @@ class dethubbard_params(C.Structure):
                 ("mu", C.c_double)]
 
 
-DETHUBBARD_MEASURE_EQ, DETHUBBARD_MEASURE_TD = 1, 2      # dethubbard_params.measureFlags (include/dethubbard_host.h)
+DETHUBBARD_MEASURE_EQ, DETHUBBARD_MEASURE_TD, DETHUBBARD_MEASURE_TD_FINE = 1, 2, 4      # dethubbard_params.measureFlags (include/dethubbard_host.h)
 DETHUBBARD_SERIES_NO_HOST_COPY = 1                       # flag of dethubbard_series_begin
 # observable indices of the dethubbard_series_* readers: the eight '...Corr' / '...Sq' and the six '...Tau' / '...TauSq' follow in channel order
 (DETHUBBARD_OBS_SCALARS, DETHUBBARD_OBS_ZCORR, DETHUBBARD_OBS_GREENUPCORR, DETHUBBARD_OBS_GREENUPSQ, DETHUBBARD_OBS_GREENUPTAU,
@@ -254,6 +255,13 @@ SYMBOLS = [
     ("dqmc_hubbard_measure_timedisplaced", C.c_int, [_P, C.c_int]),
     ("dqmc_hubbard_td_accum_size", C.c_size_t, [_P]),
     ("dqmc_hubbard_td_read_host", C.c_int, [_P, _DP]),
+    ("dqmc_hubbard_measure_timedisplaced_segment", C.c_int, [_P, C.c_int]),
+    ("dqmc_hubbard_measure_timedisplaced_ends", C.c_int, [_P]),
+    ("dqmc_hubbard_td_fine_accum_size", C.c_size_t, [_P]),
+    ("dqmc_hubbard_td_fine_read_host", C.c_int, [_P, _DP]),
+    ("dqmc_hubbard_td_fine_counts_host", C.c_int, [_P, _DP]),
+    ("dqmc_hubbard_td_matsubara_size", C.c_size_t, [_P, C.c_int]),
+    ("dqmc_hubbard_td_matsubara_host", C.c_int, [_P, C.c_int, _DP]),
     ("dqmc_set_timedisplaced", C.c_int, [_P, C.c_int]),
     ("dqmc_get_green_timedisplaced_host", C.c_int, [_P, _P, _P, C.POINTER(C.c_int)]),
     ("dqmc_measure_timedisplaced", C.c_int, [_P, C.c_int]),
@@ -418,6 +426,9 @@ SYMBOLS = [
     ("dethubbard_get_zcorr", C.c_int, [_P, _DP]),
     ("dethubbard_get_eq_correlators", C.c_int, [_P, _DP]),
     ("dethubbard_get_td_correlators", C.c_int, [_P, _DP]),
+    ("dethubbard_get_td_fine_correlators", C.c_int, [_P, _DP]),
+    ("dethubbard_get_matsubara", C.c_int, [_P, C.c_int, _DP]),
+    ("dethubbard_get_matsubara_all", C.c_int, [_P, C.c_int, _DP]),
     ("dethubbard_save_state", C.c_int, [_P, C.c_char_p]),
     ("dethubbard_load_state", C.c_int, [_P, C.c_char_p]),
     ("dethubbard_set_green_check", C.c_int, [_P, C.c_int]),

@@ -553,16 +553,19 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
     A_(salloc(c, &c->shift_buf, (size_t)c->nb * 3));
     auto acc_alloc = [c](int id, size_t count) { c->acc[id].n = count; return dalloc(c, &c->acc[id].p, count); };
     A_(acc_alloc(ACC_SLICE, measure_accum_doubles(N, p->L)));
-    const int td_level = p->timedisplaced & ~DQMC_TD_EVERY_SLICE;
-    if (p->timedisplaced < 0 || td_level > 2) return fail(DQMC_EINVAL, "timedisplaced must be 0, 1 or 2 (| DQMC_TD_EVERY_SLICE)");
+    const bool hub_fine = p->model == DQMC_MODEL_HUBBARD && p->timedisplaced > 0 && (p->timedisplaced & DQMC_TD_HUB_EVERY_SLICE);
+    const int td_level = p->timedisplaced & ~DQMC_TD_EVERY_SLICE & ~(hub_fine ? DQMC_TD_HUB_EVERY_SLICE : 0);
+    if (p->timedisplaced < 0 || td_level > 2)
+        return fail(DQMC_EINVAL, "timedisplaced must be 0, 1 or 2 (| DQMC_TD_EVERY_SLICE; DQMC_TD_HUB_EVERY_SLICE: Hubbard model only)");
     if ((p->timedisplaced & DQMC_TD_EVERY_SLICE) && !td_level) return fail(DQMC_EINVAL, "DQMC_TD_EVERY_SLICE needs timedisplaced >= 1");
     if (p->model == DQMC_MODEL_HUBBARD && (p->timedisplaced || p->td_particle_hole)) {
         // the one reservation of this model, behind every other buffer: the matrices of the time-displaced Green's functions with G(0),
         // the scratch of the correlators' prepare pass (ph_H: n_g^2 complex hold its 4 N^2 + 4 N doubles) and the block of
         // dqmc_hubbard_measure_timedisplaced; none of the SDW blocks
-        if (p->timedisplaced != 1 || p->td_particle_hole != 1)
-            return fail(DQMC_EINVAL, "Hubbard replica: timedisplaced = 1 with td_particle_hole = 1 is the only time-displaced reservation (every "
-                                     "other value of the two fields: SDW model only)");
+        if ((p->timedisplaced != 1 && p->timedisplaced != (1 | DQMC_TD_HUB_EVERY_SLICE)) || p->td_particle_hole != 1)
+            return fail(DQMC_EINVAL, "Hubbard replica: timedisplaced = 1 (| DQMC_TD_HUB_EVERY_SLICE) with td_particle_hole = 1 is the only "
+                                     "time-displaced reservation (every other value of the two fields: SDW model only)");
+        if (hub_fine && c->n < 2) return fail(DQMC_EINVAL, "Hubbard replica: DQMC_TD_HUB_EVERY_SLICE needs s < m (n >= 2)");
         c->td_reserved = true;
         A_(dalloc(c, &c->GT0, n2)); A_(dalloc(c, &c->G0T, n2)); A_(dalloc(c, &c->td_W, n2));
         if (c->stab != DQMC_STAB_QR) { A_(alloc_qr_work(c)); A_(dalloc(c, &c->td_sv, (size_t)ng)); }
@@ -606,10 +609,16 @@ static int create_fill(dqmc_ctx* c, const dqmc_params* p) {
         A_(acc_alloc(ACC_TD_BAND, measure_td_band_doubles(N, c->n)));
         if (c->td_fine) A_(acc_alloc(ACC_FINE0 + 4, (size_t)(p->m + 1) * (1 + measure_td_row_doubles(4, N, p->L))));
     }
+    if (hub_fine) {                         // behind every buffer above: a Hubbard context without the flag is laid out as before
+        c->td_fine = true;
+        A_(dalloc(c, &c->fGT0, n2)); A_(dalloc(c, &c->fG0T, n2)); A_(dalloc(c, &c->fGTT, n2));
+        A_(acc_alloc(ACC_HUB_TD_FINE, hubbard_td_fine_doubles(N, p->m)));
+    }
     A_(arena_commit(c));                    // from here on the per-chain pointers are real (chain 0) addresses, zero filled
 #undef A_
     for (int id = 0; id < ACC_EQ; ++id) c->acc[id].stride = c->lc.cs;
     c->acc[ACC_HUB_TD].stride = c->lc.cs;
+    c->acc[ACC_HUB_TD_FINE].stride = c->lc.cs;
     c->qw.err = &c->us->chol_fail;
     hm.phi = c->phi; hm.coshT = c->coshT; hm.sinhT = c->sinhT;
     if (p->cdwU != 0.0) {

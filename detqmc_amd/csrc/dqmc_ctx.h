@@ -39,10 +39,11 @@ enum { FAM_BMULT = DQMC_FAM_BMULT, FAM_GEMM = DQMC_FAM_GEMM, FAM_JACOBI = DQMC_F
 // channel 4 of both families and ACC_EQ_BAND are the band-resolved charge blocks (DQMC_TD_PH_BAND, dqmc_set_equal_time_band), channel 5
 // and ACC_EQ_CUSTOM the blocks of the user-defined bilinears (dqmc_set_custom_bilinears), channel 6 and ACC_EQ_CUSTOM_PAIR those of the
 // user-defined pair operators (dqmc_set_custom_pair_operators), channel 7 the averaged Green's function block (dqmc_set_green_matrix);
-// ACC_HUB_EQ / ACC_HUB_TD the equal-time and time-displaced correlators of the Hubbard model (dqmc_hubbard_*), behind every SDW block
+// ACC_HUB_EQ / ACC_HUB_TD the equal-time and time-displaced correlators of the Hubbard model (dqmc_hubbard_*), behind every SDW block,
+// ACC_HUB_TD_FINE its every-slice block (DQMC_TD_HUB_EVERY_SLICE)
 enum { TD_CHANNELS = 8 };
 enum { ACC_SLICE, ACC_TD, ACC_TD_PAIR, ACC_TD_PH, ACC_TD_CUR, ACC_TD_BAND, ACC_TD_CUSTOM, ACC_TD_CUSTOM_PAIR, ACC_TD_GREEN_MATRIX, ACC_FINE0,
-       ACC_EQ = ACC_FINE0 + TD_CHANNELS, ACC_EQ_BAND, ACC_EQ_CUSTOM, ACC_EQ_CUSTOM_PAIR, ACC_HUB_EQ, ACC_HUB_TD, ACC_COUNT };
+       ACC_EQ = ACC_FINE0 + TD_CHANNELS, ACC_EQ_BAND, ACC_EQ_CUSTOM, ACC_EQ_CUSTOM_PAIR, ACC_HUB_EQ, ACC_HUB_TD, ACC_HUB_TD_FINE, ACC_COUNT };
 // n: doubles per chain, 0 while the context has no such block; chain b starts at (char*)p + b * stride (the arena's chain stride; the
 // equal-time blocks and every block of the user-defined bilinears and pair operators live outside the arena as [chain][n]); missing: what a read of an absent
 // block reports
@@ -100,7 +101,8 @@ struct dqmc_ctx {
         {nullptr, 0, 0, "no user-defined bilinear is set (dqmc_set_custom_bilinears)"},
         {nullptr, 0, 0, "no user-defined pair operator is set (dqmc_set_custom_pair_operators)"},
         {nullptr, 0, 0, "the Hubbard equal-time correlators have never been enabled (dqmc_hubbard_set_equal_time_correlators)"},
-        {nullptr, 0, 0, "Hubbard context created without dqmc_params::timedisplaced = 1 and td_particle_hole = 1"}};
+        {nullptr, 0, 0, "Hubbard context created without dqmc_params::timedisplaced = 1 and td_particle_hole = 1"},
+        {nullptr, 0, 0, "Hubbard context created without DQMC_TD_HUB_EVERY_SLICE"}};
     // time-displaced Green's functions (dqmc_params::timedisplaced reserves them; dqmc_set_timedisplaced switches them on)
     bool td_reserved = false, td_on = false;
     int td_slice = -1;                                        // tau slice of the last pair GT0 / G0T (all chains), -1: none yet
@@ -114,7 +116,7 @@ struct dqmc_ctx {
     cplx *band_ob = nullptr;
     // DQMC_TD_EVERY_SLICE: work copies of G(tau_k,0), G(0,tau_k), G(tau_k) that the segment / ends entries propagate (the sweep's own G,
     // GT0, G0T, G00 are only read) and the slice they stand on; one fine accumulator block (m + 1 rows) per enabled channel: 0 G(k, tau)
-    // bins, 1 pairing, 2 particle-hole, 3 current
+    // bins, 1 pairing, 2 particle-hole, 3 current.  DQMC_TD_HUB_EVERY_SLICE: the same work copies and the one block ACC_HUB_TD_FINE
     bool td_fine = false;
     int fine_slice = -1;
     cplx *fGT0 = nullptr, *fG0T = nullptr, *fGTT = nullptr;

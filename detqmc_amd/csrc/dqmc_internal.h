@@ -280,6 +280,14 @@ void launch_hubbard_corr_prep(const Launch& lc, const DevModel& hm, const cplx* 
 void launch_hubbard_eq_corr(const Launch& lc, const DevModel& hm, const cplx* G, const double* sc, size_t scs, double* acc, size_t acs);
 void launch_hubbard_td_corr(const Launch& lc, const DevModel& hm, const cplx* GT0, const double* sc, size_t scs, double* acc, size_t acs,
                             int row, int rows);
+// Every-slice block of the Hubbard replica (DQMC_TD_HUB_EVERY_SLICE): count[m+1], [m+1][HUB_EQ_CH][N].  launch_hubbard_td_fine_corr is the
+// walk over G(tau,0) with all eight channels; its scratch comes from launch_hubbard_corr_prep(T = G(0,tau), S = G(tau,0), G(tau), G(0)).
+// launch_hubbard_td_matsubara: the transforms of that block (inside the arena), out[chain][HUB_EQ_CH][nfreq][N] (re, im), bad[chain] = 1 for
+// a chain with a row that was never measured; out and bad are plain device arrays.  false, nothing launched: the lattice is too large for the LDS
+size_t hubbard_td_fine_doubles(int N, int m);
+void launch_hubbard_td_fine_corr(const Launch& lc, const DevModel& hm, const cplx* GT0, const double* sc, size_t scs, double* acc, size_t acs,
+                                 int row, int rows);
+bool launch_hubbard_td_matsubara(const Launch& lc, const DevModel& hm, const double* acc, int nfreq, double* out, double* bad);
 
 // misc elementwise
 void launch_cosh_sinh(const Launch& lc, const DevModel& hm);
@@ -348,6 +356,44 @@ __device__ __forceinline__ void series_cosine_sum(const double* C, double* Ac, d
         }
         out[q] = sq;
     }
+}
+#endif
+// The Matsubara kernels (k_td_matsubara in kernels_measure.hip, k_hubbard_td_matsubara in kernels_hubbard.hip): a tile of at most TDM_FT
+// frequencies per workgroup, the shape both are launched with, the LDS a tile needs (doubles) and the separable spatial transform.
+#define TDM_FT 8
+struct TdmShape { int channel, ncomp, nfreq, ftile, m, L, N, W, WP, rlen, stride, apbx, apby; double scale; size_t ocs; };   // ocs: chain stride of out (doubles)
+size_t measure_td_matsubara_lds_doubles(int ftile, int m, int L, int W, int rlen);
+#ifdef __HIPCC__
+// T[ky][ix] = sum_iy ty[ky][iy] U[iy][ix], then emit(ky L + kx, sum_ix tx[kx][ix] T[ky][ix]); U = (ur, ui)[(iy W + ix) str]
+template<class Emit>
+__device__ __forceinline__ void tdm_dft2(const TdmShape& a, const double* tx, const double* ty, double* T, const double* ur, const double* ui,
+                                         int str, Emit emit) {
+    const int L = a.L, W = a.W, WP = a.WP;
+    for (int i = threadIdx.x; i < L * W; i += 256) {
+        const int ky = i / W, ix = i - ky * W;
+        const double* t = ty + (size_t)2 * ky * WP;
+        double re = 0.0, im = 0.0;
+        for (int iy = 0; iy < W; ++iy) {
+            const double c = t[2 * iy], s = t[2 * iy + 1], xr = ur[(size_t)(iy * W + ix) * str], xi = ui[(size_t)(iy * W + ix) * str];
+            re += c * xr - s * xi;
+            im += c * xi + s * xr;
+        }
+        T[2 * i] = re; T[2 * i + 1] = im;
+    }
+    __syncthreads();
+    for (int q = threadIdx.x; q < a.N; q += 256) {
+        const int ky = q / L, kx = q - ky * L;
+        const double* t = tx + (size_t)2 * kx * WP;
+        const double* v = T + (size_t)2 * ky * W;
+        double re = 0.0, im = 0.0;
+        for (int ix = 0; ix < W; ++ix) {
+            const double c = t[2 * ix], s = t[2 * ix + 1];
+            re += c * v[2 * ix] - s * v[2 * ix + 1];
+            im += c * v[2 * ix + 1] + s * v[2 * ix];
+        }
+        emit(q, re, im);
+    }
+    __syncthreads();                                        // T is free again
 }
 #endif
 // the parts of a Hubbard context (DQMC_SERIES_HUB_*; kernels_hubbard.hip, the derived quantities in kernels_measure.hip).  slice / td: the

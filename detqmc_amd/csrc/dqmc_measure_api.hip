@@ -725,6 +725,7 @@ static void td_fine_load_boundary(dqmc_ctx* c) {
 }
 extern "C" int dqmc_measure_timedisplaced_segment(dqmc_ctx* c, int j) {
     if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (c->hm.hubbard) return fail(DQMC_EINVAL, "dqmc_measure_timedisplaced_segment belongs to the SDW model (Hubbard: dqmc_hubbard_measure_timedisplaced_segment)");
     if (!c->td_fine) return fail(DQMC_EINVAL, "context created without DQMC_TD_EVERY_SLICE");
     if (const int rc = td_boundary_ok(c, j, true)) return rc;
     (void)hipSetDevice(c->p.device);
@@ -750,7 +751,7 @@ extern "C" int dqmc_measure_timedisplaced_segment(dqmc_ctx* c, int j) {
 // dqmc_measure_timedisplaced_segment takes (its preconditions; DQMC_EINVAL for a k outside the segment); nothing is measured
 extern "C" int dqmc_td_fine_propagate(dqmc_ctx* c, int j, int k) {
     if (!c) return fail(DQMC_EINVAL, "null ctx");
-    if (!c->td_fine) return fail(DQMC_EINVAL, "context created without DQMC_TD_EVERY_SLICE");
+    if (!c->td_fine) return fail(DQMC_EINVAL, "context created without DQMC_TD_EVERY_SLICE (Hubbard: DQMC_TD_HUB_EVERY_SLICE)");
     if (const int rc = td_boundary_ok(c, j, true)) return rc;
     const int s = c->s, k0 = s * j, k1 = (s * (j + 1) < c->m ? s * (j + 1) : c->m) - 1;
     if (k > k1 || k < (j == 1 ? 1 : k0)) return fail(DQMC_EINVAL, "slice k does not belong to the segment of boundary j");
@@ -762,6 +763,7 @@ extern "C" int dqmc_td_fine_propagate(dqmc_ctx* c, int j, int k) {
 }
 extern "C" int dqmc_measure_timedisplaced_ends(dqmc_ctx* c) {
     if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (c->hm.hubbard) return fail(DQMC_EINVAL, "dqmc_measure_timedisplaced_ends belongs to the SDW model (Hubbard: dqmc_hubbard_measure_timedisplaced_ends)");
     if (!c->td_fine) return fail(DQMC_EINVAL, "context created without DQMC_TD_EVERY_SLICE");
     if (c->currentTimeslice != 0 && c->currentTimeslice != c->m)
         return fail(DQMC_EINVAL, "the context does not stand at tau = 0 (beta): G is not G(0)");
@@ -778,11 +780,110 @@ extern "C" int dqmc_measure_timedisplaced_ends(dqmc_ctx* c) {
     td_row(c, mask, ACC_FINE0, c->m, c->m + 1, c->fGT0, c->fG0T, nullptr, nullptr);
     return finish(c, "dqmc_measure_timedisplaced_ends");
 }
-extern "C" size_t dqmc_measure_td_fine_accum_size(dqmc_ctx* c, int channel) { return c ? td_fine_n(c, channel) : 0; }
+// a Hubbard context has one every-slice block: it answers as channel 0
+extern "C" size_t dqmc_measure_td_fine_accum_size(dqmc_ctx* c, int channel) {
+    if (c && c->hm.hubbard) return channel == 0 ? acc_size(c, ACC_HUB_TD_FINE) : 0;
+    return c ? td_fine_n(c, channel) : 0;
+}
 extern "C" int dqmc_measure_td_fine_read_host(dqmc_ctx* c, int channel, double* out) {
     if (!c || !out) return fail(DQMC_EINVAL, "null argument");
+    if (c->hm.hubbard) {
+        if (channel != 0) return fail(DQMC_EINVAL, "a Hubbard context has one every-slice block, channel 0 (dqmc_hubbard_td_fine_read_host)");
+        return acc_read(c, ACC_HUB_TD_FINE, out);
+    }
     if (!td_fine_n(c, channel)) return fail(DQMC_EINVAL, c->acc[ACC_FINE0].missing);
     return acc_read(c, ACC_FINE0 + channel, out);
+}
+// ---- every time slice, Hubbard model (DQMC_TD_HUB_EVERY_SLICE): the work copies and steps above, the model's own contraction ----
+// row k of m + 1 from the displaced matrices (gt0, g0t), G(tau) = gtt and G(0) = g00: prepare pass with the stencil source, then the walk
+static void hubbard_fine_row(dqmc_ctx* c, int k, const cplx* gt0, const cplx* g0t, const cplx* gtt, const cplx* g00) {
+    ProfScope ps(c, FAM_OTHER, 2);
+    const AccBlock& a = c->acc[ACC_HUB_TD_FINE];
+    double* sc = (double*)c->ph_H;
+    launch_hubbard_corr_prep(c->lc, c->hm, g0t, gt0, gtt, g00, sc, c->lc.cs);
+    launch_hubbard_td_fine_corr(c->lc, c->hm, gt0, sc, c->lc.cs, a.p, a.stride, k, c->m + 1);
+}
+static int hubbard_fine_ok(dqmc_ctx* c, const char* entry) {
+    if (!c) return fail(DQMC_EINVAL, "null ctx");
+    if (!c->hm.hubbard) return fail(DQMC_EINVAL, std::string(entry) + " belongs to the Hubbard model");
+    if (!c->acc[ACC_HUB_TD_FINE].n) return fail(DQMC_EINVAL, c->acc[ACC_HUB_TD_FINE].missing);
+    return DQMC_OK;
+}
+extern "C" int dqmc_hubbard_measure_timedisplaced_segment(dqmc_ctx* c, int j) {
+    if (const int rc = hubbard_fine_ok(c, "dqmc_hubbard_measure_timedisplaced_segment")) return rc;
+    if (const int rc = td_boundary_ok(c, j, true)) return rc;
+    (void)hipSetDevice(c->p.device);
+    const int s = c->s, k0 = s * j, k1 = (s * (j + 1) < c->m ? s * (j + 1) : c->m) - 1;
+    td_fine_load_boundary(c);
+    for (int k = k0; k <= k1; ++k) {
+        hubbard_fine_row(c, k, c->fGT0, c->fG0T, c->fGTT, c->G00);
+        if (k < k1) td_fine_step(c, k, +1);
+    }
+    if (j == 1 && s > 1) {                    // the slices below the first boundary have no boundary of their own
+        td_fine_load_boundary(c);
+        for (int k = s; k >= 2; --k) {
+            td_fine_step(c, k, -1);
+            hubbard_fine_row(c, k - 1, c->fGT0, c->fG0T, c->fGTT, c->G00);
+        }
+    }
+    return finish(c, "dqmc_hubbard_measure_timedisplaced_segment");
+}
+extern "C" int dqmc_hubbard_measure_timedisplaced_ends(dqmc_ctx* c) {
+    if (const int rc = hubbard_fine_ok(c, "dqmc_hubbard_measure_timedisplaced_ends")) return rc;
+    if (c->currentTimeslice != 0 && c->currentTimeslice != c->m)
+        return fail(DQMC_EINVAL, "the context does not stand at tau = 0 (beta): G is not G(0)");
+    G_FRESH(c, "dqmc_hubbard_measure_timedisplaced_ends");
+    (void)hipSetDevice(c->p.device);
+    // staged as dqmc_measure_timedisplaced_ends does: row m in the work copies, row 0 in T2 / T3 (idle here)
+    { ProfScope ps(c, FAM_OTHER, 1); launch_td_ends(c->lc, c->G, c->T2, c->T3, c->fGT0, c->fG0T, c->fGTT, c->n_g); }
+    c->fine_slice = c->m;
+    hubbard_fine_row(c, 0, c->T2, c->T3, c->G, c->G);       // G(tau) = G(0) = G for both rows and both sides
+    hubbard_fine_row(c, c->m, c->fGT0, c->fG0T, c->G, c->G);
+    return finish(c, "dqmc_hubbard_measure_timedisplaced_ends");
+}
+extern "C" size_t dqmc_hubbard_td_fine_accum_size(dqmc_ctx* c) { return acc_size(c, ACC_HUB_TD_FINE); }
+extern "C" int dqmc_hubbard_td_fine_read_host(dqmc_ctx* c, double* out) {
+    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
+    if (!c->hm.hubbard) return fail(DQMC_EINVAL, "dqmc_hubbard_td_fine_read_host belongs to the Hubbard model");
+    return acc_read(c, ACC_HUB_TD_FINE, out);
+}
+extern "C" int dqmc_hubbard_td_fine_counts_host(dqmc_ctx* c, double* out) {
+    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
+    if (const int rc = hubbard_fine_ok(c, "dqmc_hubbard_td_fine_counts_host")) return rc;
+    const AccBlock& a = c->acc[ACC_HUB_TD_FINE];
+    (void)hipSetDevice(c->p.device);
+    HIPCHK(hipStreamSynchronize(c->st));
+    HIPCHK(copy_sync(c, out, (const char*)a.p + (size_t)c->sel * a.stride, (size_t)(c->m + 1) * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
+}
+extern "C" size_t dqmc_hubbard_td_matsubara_size(dqmc_ctx* c, int nfreq) {
+    if (!c || !c->hm.hubbard || !c->acc[ACC_HUB_TD_FINE].n || nfreq < 1 || nfreq > c->m) return 0;
+    return (size_t)c->nb * HUB_EQ_CH * nfreq * c->N * 2;
+}
+extern "C" int dqmc_hubbard_td_matsubara_host(dqmc_ctx* c, int nfreq, double* out) {
+    if (!c || !out) return fail(DQMC_EINVAL, "null argument");
+    if (const int rc = hubbard_fine_ok(c, "dqmc_hubbard_td_matsubara_host")) return rc;
+    if (nfreq < 1 || nfreq > c->m) return fail(DQMC_EINVAL, "nfreq must be in 1..m");
+    (void)hipSetDevice(c->p.device);
+    const size_t n_out = dqmc_hubbard_td_matsubara_size(c, nfreq), need = n_out + (size_t)c->nb;
+    if (need > c->mats_cap) {
+        HIPCHK(hipStreamSynchronize(c->st));
+        if (c->mats_out) { (void)hipFree(c->mats_out); c->mats_out = nullptr; c->mats_cap = 0; }
+        HIPCHK(hipMalloc((void**)&c->mats_out, need * sizeof(double)));
+        c->mats_cap = need;
+    }
+    bool launched;
+    {
+        ProfScope ps(c, FAM_OTHER, 1);
+        launched = launch_hubbard_td_matsubara(c->lc, c->hm, c->acc[ACC_HUB_TD_FINE].p, nfreq, c->mats_out, c->mats_out + n_out);
+    }
+    if (!launched) return fail(DQMC_EINVAL, "dqmc_hubbard_td_matsubara_host: the lattice is too large for the kernel's LDS");
+    { const int rc = finish(c, "dqmc_hubbard_td_matsubara_host"); if (rc != DQMC_OK) return rc; }
+    std::vector<double> bad((size_t)c->nb);
+    HIPCHK(copy_sync(c, bad.data(), c->mats_out + n_out, bad.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (double b : bad) if (b != 0.0) return fail(DQMC_EINVAL, "an every-slice row has no sample: the measurement sweep did not visit every time slice");
+    HIPCHK(copy_sync(c, out, c->mats_out, n_out * sizeof(double), hipMemcpyDeviceToHost));
+    return DQMC_OK;
 }
 static int td_ncomp(const dqmc_ctx* c, int channel) { return channel == 6 ? c->cpr_count : channel == 5 ? c->cst_count : channel == 2 ? 3 : 2; }
 // the Matsubara launch of one every-slice block; channels 5 and 6 bring their component count and their own chain stride
@@ -796,6 +897,7 @@ extern "C" size_t dqmc_measure_td_matsubara_size(dqmc_ctx* c, int channel, int n
 }
 extern "C" int dqmc_measure_td_matsubara_host(dqmc_ctx* c, int channel, int nfreq, double* out) {
     if (!c || !out) return fail(DQMC_EINVAL, "null argument");
+    if (c->hm.hubbard) return fail(DQMC_EINVAL, "dqmc_measure_td_matsubara_host belongs to the SDW model (Hubbard: dqmc_hubbard_td_matsubara_host)");
     if (!c->td_fine) return fail(DQMC_EINVAL, "context created without DQMC_TD_EVERY_SLICE");
     if (!td_fine_n(c, channel)) return fail(DQMC_EINVAL, c->acc[ACC_FINE0].missing);
     if (channel == 7) return fail(DQMC_EINVAL, "dqmc_measure_td_matsubara_host: the averaged Green's function block has no transform (channel 0 serves G(k, i omega_n))");

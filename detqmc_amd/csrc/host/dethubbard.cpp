@@ -25,6 +25,8 @@ DetHubbard::DetHubbard(const dethubbard_params& in, int nchains) : p_(in) {
     if (!(p_.beta > 0) && p_.m <= 0) throw ParameterWrong("Specify either parameter m or beta");
     if (p_.m <= 0) p_.m = (int32_t)std::round(p_.beta / p_.dtau);
     p_.beta = p_.m * p_.dtau;
+    if ((p_.measureFlags & DETHUBBARD_MEASURE_TD_FINE) && p_.s >= p_.m)
+        throw ParameterWrong("Parameter measureFlags: DETHUBBARD_MEASURE_TD_FINE needs s < m (at least one interior boundary)");
     while (p_.m <= p_.s) p_.s -= 1;
     if (p_.s < 1) throw ParameterWrong("Cannot choose parameter s obeying 0 < s < m");
     // ModelParams<DetHubbard>::check (dethubbardparams.cpp:21-55)
@@ -32,7 +34,10 @@ DetHubbard::DetHubbard(const dethubbard_params& in, int nchains) : p_(in) {
     if (p_.d != 2) throw ParameterWrong("Hubbard replica: only d = 2 lattices are supported by this build");
     if (p_.checkerboard && p_.L % 2 != 0) throw ParameterWrong("Checker board decomposition only supported for even linear lattice sizes");
     if (p_.L % 2 != 0) throw ParameterWrong("this build needs an even linear lattice size");
-    if (p_.measureFlags & ~(DETHUBBARD_MEASURE_EQ | DETHUBBARD_MEASURE_TD)) throw ParameterWrong("Parameter measureFlags has an unknown bit set");
+    if (p_.measureFlags & ~(DETHUBBARD_MEASURE_EQ | DETHUBBARD_MEASURE_TD | DETHUBBARD_MEASURE_TD_FINE))
+        throw ParameterWrong("Parameter measureFlags has an unknown bit set");
+    if ((p_.measureFlags & DETHUBBARD_MEASURE_TD_FINE) && !(p_.measureFlags & DETHUBBARD_MEASURE_TD))
+        throw ParameterWrong("Parameter measureFlags: DETHUBBARD_MEASURE_TD_FINE needs DETHUBBARD_MEASURE_TD");
     N_ = p_.L * p_.L; m_ = p_.m; s_ = p_.s; n_ = (m_ + s_ - 1) / s_;
     alpha_ = std::acosh(std::exp(p_.dtau * p_.U * 0.5));
 
@@ -44,6 +49,7 @@ DetHubbard::DetHubbard(const dethubbard_params& in, int nchains) : p_(in) {
     kp.dtau = p_.dtau; kp.txhor = p_.t; kp.u = p_.U; kp.mux = p_.mu; kp.muy = p_.mu; kp.accRatio = 0.5;
     kp.tuning.bmult_path = DQMC_TUNING_NO_RNG_LOOKAHEAD;     // this replica pushes every window whole (beginLocalUpdates)
     if (p_.measureFlags & DETHUBBARD_MEASURE_TD) { kp.timedisplaced = 1; kp.td_particle_hole = 1; }   // G(tau,0), G(0,tau), G(0) and the block
+    if (p_.measureFlags & DETHUBBARD_MEASURE_TD_FINE) kp.timedisplaced |= DQMC_TD_HUB_EVERY_SLICE;    // the work copies and the every-slice block
     check(dqmc_create_batch(&kp, nchains, &ctx_), "dqmc_create");
     try {
         std::vector<double> all((size_t)nchains * (m_ + 1) * N_, 0.0);
@@ -80,6 +86,8 @@ void DetHubbard::updateInSlice(int k) {
 void DetHubbard::advance(int dir, int l, int boundary, const char* what) {
     check(dqmc_advance(ctx_, dir, l), what);
     if (measuringTD_ && boundary) check(dqmc_hubbard_measure_timedisplaced(ctx_, boundary), "measureTimeDisplaced");
+    if (measuringFine_ && boundary) check(dqmc_hubbard_measure_timedisplaced_segment(ctx_, boundary), "measureTimeDisplacedSegment");
+    if (measuringFine_ && !boundary) check(dqmc_hubbard_measure_timedisplaced_ends(ctx_), "measureTimeDisplacedEnds");
 }
 
 void DetHubbard::sweepDown() {                                      // detmodel.h:1333-1399
@@ -118,12 +126,14 @@ void DetHubbard::sweep_skeleton(bool takeMeasurements) {
     // the correlators ride on measurement sweeps only: thermalisation sweeps launch nothing new and never form the time-displaced pair
     const bool eq = takeMeasurements && (p_.measureFlags & DETHUBBARD_MEASURE_EQ);
     measuringTD_ = takeMeasurements && (p_.measureFlags & DETHUBBARD_MEASURE_TD);
+    measuringFine_ = takeMeasurements && (p_.measureFlags & DETHUBBARD_MEASURE_TD_FINE);
+    fineLive_ = false;
     if (eq) check(dqmc_hubbard_set_equal_time_correlators(ctx_, 1), "dqmc_hubbard_set_equal_time_correlators");
     if (measuringTD_) check(dqmc_set_timedisplaced(ctx_, 1), "dqmc_set_timedisplaced");
     auto off = [this, eq]() {
         if (eq) (void)dqmc_hubbard_set_equal_time_correlators(ctx_, 0);
         if (measuringTD_) (void)dqmc_set_timedisplaced(ctx_, 0);
-        measuring_ = measuringTD_ = false;
+        measuring_ = measuringTD_ = measuringFine_ = false;
     };
     try {
         if (lastSweepDir_ == Up) sweepDown(); else sweepUp();
@@ -139,6 +149,7 @@ void DetHubbard::sweep_skeleton(bool takeMeasurements) {
         if (takeMeasurements) finishMeasurements((int)b); else ch_[b].obs.valid = 0;
     }
     if (takeMeasurements) corrStale_ = seriesNoHostCopy();
+    fineLive_ = takeMeasurements && (p_.measureFlags & DETHUBBARD_MEASURE_TD_FINE);
     if (feedSeries) check(dqmc_series_add_sweep(ctx_), "dqmc_series_add_sweep");     // one sample of every chain, from the blocks on the device
 }
 
@@ -181,6 +192,18 @@ void DetHubbard::finishMeasurements(int b) {
             for (size_t i = 0; i < row; ++i) ch_[b].tdCorr[j * row + i] = blk[rows + j * row + i] / N;
         }
     }
+    if (p_.measureFlags & DETHUBBARD_MEASURE_TD_FINE) {             // count[m+1], [m+1][8][N]; without the copy only the m + 1 counts are read
+        const size_t rows = (size_t)m_ + 1, row = (size_t)8 * N_;
+        std::vector<double> blk(copy ? dqmc_hubbard_td_fine_accum_size(ctx_) : rows);
+        if (copy) check(dqmc_hubbard_td_fine_read_host(ctx_, blk.data()), "dqmc_hubbard_td_fine_read_host");
+        else check(dqmc_hubbard_td_fine_counts_host(ctx_, blk.data()), "dqmc_hubbard_td_fine_counts_host");
+        for (size_t k = 0; k < rows; ++k)
+            if (blk[k] != 1.0) throw GeneralError(DQMC_EINVAL, "measurement sweep did not take one every-slice sample per time slice");
+        if (copy) {
+            ch_[b].tdFineCorr.assign(rows * row, 0.0);
+            for (size_t i = 0; i < rows * row; ++i) ch_[b].tdFineCorr[i] = blk[rows + i] / N;
+        }
+    }
     o.valid = 1;                                                    // last: a sweep that threw above leaves no half-read observables behind
 }
 
@@ -198,6 +221,26 @@ void DetHubbard::getTdCorrelators(double* out, int b) const {
         throw GeneralError(DQMC_EINVAL, "the correlators are not copied to the host while a series with DETHUBBARD_SERIES_NO_HOST_COPY is open: read the series");
     if (!ch_[b].obs.valid || corrStale_) throw GeneralError(DQMC_EINVAL, "no measurement has been taken");
     std::memcpy(out, ch_[b].tdCorr.data(), ch_[b].tdCorr.size() * sizeof(double));
+}
+
+void DetHubbard::getTdFineCorrelators(double* out, int b) const {
+    if (!(p_.measureFlags & DETHUBBARD_MEASURE_TD_FINE)) throw GeneralError(DQMC_EINVAL, "the every-slice correlators need DETHUBBARD_MEASURE_TD_FINE in measureFlags");
+    if (seriesNoHostCopy())
+        throw GeneralError(DQMC_EINVAL, "the correlators are not copied to the host while a series with DETHUBBARD_SERIES_NO_HOST_COPY is open: read the series");
+    if (!ch_[b].obs.valid || corrStale_) throw GeneralError(DQMC_EINVAL, "no measurement has been taken");
+    std::memcpy(out, ch_[b].tdFineCorr.data(), ch_[b].tdFineCorr.size() * sizeof(double));
+}
+
+void DetHubbard::getMatsubara(int nfreq, double* out, int b) {
+    if (!(p_.measureFlags & DETHUBBARD_MEASURE_TD_FINE)) throw GeneralError(DQMC_EINVAL, "the Matsubara transforms need DETHUBBARD_MEASURE_TD_FINE in measureFlags");
+    if (!fineLive_) throw GeneralError(DQMC_EINVAL, "the Matsubara transforms are valid after a measurement sweep, until the next sweep");
+    const size_t all = dqmc_hubbard_td_matsubara_size(ctx_, nfreq);
+    if (!all) throw GeneralError(DQMC_EINVAL, "nfreq must be in 1..m");
+    if (b < 0) { check(dqmc_hubbard_td_matsubara_host(ctx_, nfreq, out), "dqmc_hubbard_td_matsubara_host"); return; }
+    std::vector<double> buf(all);
+    check(dqmc_hubbard_td_matsubara_host(ctx_, nfreq, buf.data()), "dqmc_hubbard_td_matsubara_host");
+    const size_t per = all / ch_.size();
+    std::memcpy(out, &buf[(size_t)b * per], per * sizeof(double));
 }
 
 void DetHubbard::getZcorr(double* out, int b) const {
@@ -406,6 +449,7 @@ void DetHubbard::loadState(const std::string& path) {
     check(dqmc_udv_setup(ctx_), "setupUdVStorage_and_calculateGreen");       // dethubbard.h:345-350
     performedSweeps_ = hdr[4];
     lastSweepDir_ = Up;
+    fineLive_ = false;                                              // the every-slice block is no longer that of the last sweep
 }
 
 // ---- the series file, in the format of detsdw_series_save: magic, version, dqmc_series_state, the route [nchains] int32 (the identity:
@@ -511,6 +555,18 @@ extern "C" int dethubbard_get_eq_correlators(dethubbard_replica* r, double* out)
 extern "C" int dethubbard_get_td_correlators(dethubbard_replica* r, double* out) {
     if (!out) { g_hub_err = "null argument"; return DQMC_EINVAL; }
     HGUARD(r->impl->getTdCorrelators(out, r->sel))
+}
+extern "C" int dethubbard_get_td_fine_correlators(dethubbard_replica* r, double* out) {
+    if (!out) { g_hub_err = "null argument"; return DQMC_EINVAL; }
+    HGUARD(r->impl->getTdFineCorrelators(out, r->sel))
+}
+extern "C" int dethubbard_get_matsubara(dethubbard_replica* r, int nfreq, double* out) {
+    if (!out) { g_hub_err = "null argument"; return DQMC_EINVAL; }
+    HGUARD(r->impl->getMatsubara(nfreq, out, r->sel))
+}
+extern "C" int dethubbard_get_matsubara_all(dethubbard_replica* r, int nfreq, double* out) {
+    if (!out) { g_hub_err = "null argument"; return DQMC_EINVAL; }
+    HGUARD(r->impl->getMatsubara(nfreq, out, -1))
 }
 extern "C" int dethubbard_save_state(dethubbard_replica* r, const char* path) {
     if (!path) { g_hub_err = "null path"; return DQMC_EINVAL; }

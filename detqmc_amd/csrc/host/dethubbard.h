@@ -25,6 +25,8 @@ public:
     void getZcorr(double* out, int b) const;
     void getEqCorrelators(double* out, int b) const;       // [8][N], needs DETHUBBARD_MEASURE_EQ
     void getTdCorrelators(double* out, int b) const;       // [n-1][6][N], needs DETHUBBARD_MEASURE_TD
+    void getTdFineCorrelators(double* out, int b) const;   // [m+1][8][N], needs DETHUBBARD_MEASURE_TD_FINE
+    void getMatsubara(int nfreq, double* out, int b);      // [8][nfreq][N] complex, b < 0: every chain; from the block on the device
     void saveState(const std::string& path);
     void loadState(const std::string& path);
     double rand01(int b) { return ch_[b].rng.rand01(); }
@@ -57,7 +59,7 @@ private:
         double lastAccRatio = 0.0;
         dethubbard_observables obs{};
         std::vector<double> zcorr;
-        std::vector<double> eqCorr, tdCorr;    // normalised C(d) of the last measurement sweep (measureFlags)
+        std::vector<double> eqCorr, tdCorr, tdFineCorr;    // normalised C(d) of the last measurement sweep (measureFlags)
         Chain(uint32_t seed, uint32_t simindex) : rng(seed, simindex + 1u) {}      // detqmc.h:181
     };
     dethubbard_params p_;
@@ -70,6 +72,8 @@ private:
     int performedSweeps_ = 0;
     bool measuring_ = false;
     bool measuringTD_ = false;        // ... with G(tau_j, 0) and its correlators after every interior advance (DETHUBBARD_MEASURE_TD)
+    bool measuringFine_ = false;      // ... and the every-slice rows of the boundary's segment and of the ends (DETHUBBARD_MEASURE_TD_FINE)
+    bool fineLive_ = false;           // the every-slice block on the device is that of the last sweep, a measurement sweep
 
     // the open series: its parts (DQMC_SERIES_HUB_*) and the flags of seriesBegin; corrStale_: the last measurement sweep did not copy
     // the correlator blocks (DETHUBBARD_SERIES_NO_HOST_COPY), eqCorr / tdCorr of the chains are not its values
@@ -85,7 +89,7 @@ private:
     void sweepDown();
     void sweepUp();
     void updateInSlice(int k);
-    void advance(int dir, int l, int boundary, const char* what);     // boundary: the interior boundary j the advance ends on, 0: none
+    void advance(int dir, int l, int boundary, const char* what);     // boundary: the interior boundary j the advance ends on, 0: none (the closing advance)
     void finishMeasurements(int b);
 };
 

@@ -12,6 +12,7 @@
 //                      (updateGreenFunctionWithFlip, :877-906) -- one workgroup per replica walks the whole slice
 //   k_hubbard_measure  measure(timeslice) (:521-545): sums over G_ii, nearest-neighbour G_ij and the spin-z correlation
 //   k_hubbard_corr_prep, k_hubbard_corr   equal-time and time-displaced correlators over all site differences (not in the reference)
+//   k_hubbard_td_matsubara   chi_X(q, i omega_n) and G_s(k, i omega_n) of the every-slice block
 #include "dqmc_internal.h"
 #include "bin_walk.h"
 
@@ -170,6 +171,7 @@ void launch_hubbard_measure(const Launch& lc, const DevModel& hm, const cplx* G,
 size_t hubbard_corr_scratch_doubles(int N) { return 4 * (size_t)N * N + 4 * (size_t)N; }
 size_t hubbard_eq_doubles(int N) { return 1 + HUB_EQ_CH * (size_t)N; }
 size_t hubbard_td_doubles(int N, int n) { return (size_t)(n - 1) * (1 + HUB_TD_CH * (size_t)N); }
+size_t hubbard_td_fine_doubles(int N, int m) { return (size_t)(m + 1) * (1 + HUB_EQ_CH * (size_t)N); }
 
 __global__ __launch_bounds__(256) void k_hubbard_corr_prep(DevModel dm, const cplx* __restrict__ T, const cplx* __restrict__ S,
                                                             const cplx* __restrict__ Gt, const cplx* __restrict__ G0,
@@ -224,10 +226,11 @@ void launch_hubbard_corr_prep(const Launch& lc, const DevModel& hm, const cplx* 
 
 // TD = 0: g = G of the slice, the scratch of (T, S) = (G, G): <c^+_A c_B> = delta_AB - G(B, A).  Block: count, [HUB_EQ_CH][N].
 // TD = 1: g = G(tau,0), the scratch of T = G(0,tau), no stencil: <c^+_A(tau) c_B(0)> = -G(0,tau)(B, A).  Row `row` of count[rows], [rows][HUB_TD_CH][N].
+// TD = 2: the forms of TD = 1 and, from the scratch of (T, S) = (G(0,tau), G(tau,0)), the two bond channels.  Row `row` of count[rows], [rows][HUB_EQ_CH][N].
 template<int TD>
 __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_hubbard_corr(DevModel dm, const cplx* __restrict__ g, const double* __restrict__ sc,
                                                                        double* __restrict__ acc, int row, int rows, size_t cs, size_t scs, size_t acs) {
-    constexpr int NCH = TD ? HUB_TD_CH : HUB_EQ_CH;
+    constexpr int NCH = TD == 1 ? HUB_TD_CH : HUB_EQ_CH;
     __shared__ double red[NCH][TDP_PARTS][TDP_BINS];
     CHAIN(g);
     sc = chain_ptr(sc, scs); acc = chain_ptr(acc, acs);
@@ -251,7 +254,7 @@ __global__ __launch_bounds__(TDP_BINS * TDP_PARTS) void k_hubbard_corr(DevModel 
         w[3] += 0.25 * ((nuA - ndA) * (nuB - ndB) + conn);
         w[4] += 0.25 * (hu * gd + hd * gu);
         w[5] += gu * gd;
-        if (!TD) {
+        if (TD != 1) {
             w[NCH - 2] += 0.25 * gu * sS[idx];
             w[NCH - 1] += 0.25 * gu * sD[idx];
         }
@@ -267,6 +270,97 @@ void launch_hubbard_td_corr(const Launch& lc, const DevModel& hm, const cplx* GT
                             int row, int rows) {
     const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
     hipLaunchKernelGGL(k_hubbard_corr<1>, grid, block, 0, lc.st, hm, GT0, sc, acc, row, rows, lc.cs, scs, acs);
+}
+
+void launch_hubbard_td_fine_corr(const Launch& lc, const DevModel& hm, const cplx* GT0, const double* sc, size_t scs, double* acc, size_t acs,
+                                 int row, int rows) {
+    const dim3 grid((hm.N + TDP_BINS - 1) / TDP_BINS, 1, lc.nb), block(TDP_BINS * TDP_PARTS);
+    hipLaunchKernelGGL(k_hubbard_corr<2>, grid, block, 0, lc.st, hm, GT0, sc, acc, row, rows, lc.cs, scs, acs);
+}
+
+// Matsubara transforms of the every-slice block count[m+1], [m+1][HUB_EQ_CH][N] (dqmc_hubbard_td_matsubara_host; definitions in dqmc_hip.h
+// and DESIGN.md 24), with the contract and the structure of k_td_matsubara (kernels_measure.hip): one workgroup per (frequency tile,
+// channel, chain); the weighted twiddles tw[f][k] = w_k (cos, sin)(omega_n tau_k) / count_k of the tile in LDS, the phase index reduced in
+// integers -- 2 (n k mod m) for the bosonic channels 2 .. 7, (2n+1) k mod 2m for the fermionic channels 0, 1 -- and handed to sincospi;
+// thread e walks the rows k = 0 .. m of column e with the 2 nf sums in registers and leaves A = sum_k w_k cos C, B = sum_k w_k sin C in
+// LDS; there one complex separable L x L transform per frequency, F(A + i B) with e^{-i q d} (the lattice is periodic: the fermionic
+// channels use the same spatial phases).  One writer per output element, sums in ascending k, y, x, no atomics; threads past the end
+// store nothing.  bad[chain] = 1 if a row of the chain has a count < 1, written by workgroup (0, 0) of the chain alone.
+__global__ __launch_bounds__(256) void k_hubbard_td_matsubara(const double* __restrict__ acc, double* __restrict__ out, double* __restrict__ bad,
+                                                              TdmShape a, size_t cs) {
+    CHAIN(acc);
+    extern __shared__ double htm_sm[];
+    const int tid = threadIdx.x, comp = blockIdx.y, rows = a.m + 1, m = a.m, L = a.L, W = a.W, WP = a.WP, R = a.rlen;
+    const int f0 = blockIdx.x * a.ftile, nf = a.nfreq - f0 < a.ftile ? a.nfreq - f0 : a.ftile;
+    const bool fermionic = comp < 2;
+    double* tw = htm_sm;                                    // [ftile][rows] (w_k cos / count_k, w_k sin / count_k)
+    double* tx = tw + (size_t)a.ftile * rows * 2;           // [L][WP] (cos, sin)
+    double* ty = tx + (size_t)2 * L * WP;
+    double* T = ty + (size_t)2 * L * WP;                    // [L][W] complex, between the two passes
+    double* Z = T + (size_t)2 * L * W;                      // [ftile][A, B][R]
+    int anybad = 0;
+    for (int k = tid; k < rows; k += 256) anybad |= !(acc[k] >= 1.0);
+    for (int i = tid; i < nf * rows; i += 256) {
+        const int f = i / rows, k = i - f * rows, n = f0 + f;
+        const long long red = fermionic ? ((long long)(2 * n + 1) * k) % (2 * m) : (2 * (((long long)n * k) % m));
+        double s, c;
+        sincospi((double)red / (double)m, &s, &c);
+        const double w = ((k == 0 || k == m) ? 0.5 : 1.0) / acc[k];
+        tw[2 * i] = w * c; tw[2 * i + 1] = w * s;
+    }
+    for (int i = tid; i < L * W; i += 256) {
+        const int kk = i / W, d = i - kk * W;
+        int num = (-2 * kk * d) % (2 * L);                  // phase = pi num / L
+        if (num < 0) num += 2 * L;
+        double s, c;
+        sincospi((double)num / (double)L, &s, &c);
+        tx[2 * (kk * WP + d)] = c; tx[2 * (kk * WP + d) + 1] = s;
+        ty[2 * (kk * WP + d)] = c; ty[2 * (kk * WP + d) + 1] = s;
+    }
+    anybad = __syncthreads_or(anybad);
+    if (blockIdx.x == 0 && comp == 0 && tid == 0) bad[blockIdx.z] = anybad ? 1.0 : 0.0;
+    // time step: column e of the channel, rows in ascending order
+    const double* rowsp = acc + rows + (size_t)comp * R;
+    for (int e0 = 0; e0 < R; e0 += 256) {
+        const int e = e0 + tid;
+        const bool valid = e < R;
+        const double* p = rowsp + (valid ? e : 0);
+        double A[TDM_FT], B[TDM_FT];
+#pragma unroll
+        for (int f = 0; f < TDM_FT; ++f) { A[f] = 0.0; B[f] = 0.0; }
+#pragma unroll 4
+        for (int k = 0; k < rows; ++k) {
+            const double v = p[(size_t)k * a.stride];
+#pragma unroll
+            for (int f = 0; f < TDM_FT; ++f)
+                if (f < nf) { A[f] += tw[2 * (f * rows + k)] * v; B[f] += tw[2 * (f * rows + k) + 1] * v; }
+        }
+        if (valid) {
+#pragma unroll
+            for (int f = 0; f < TDM_FT; ++f)
+                if (f < nf) { Z[(size_t)(2 * f) * R + e] = A[f]; Z[(size_t)(2 * f + 1) * R + e] = B[f]; }
+        }
+    }
+    __syncthreads();
+    double* o = out + (size_t)blockIdx.z * a.ocs + ((size_t)comp * a.nfreq + f0) * (size_t)a.N * 2;
+    for (int f = 0; f < nf; ++f, o += (size_t)a.N * 2) {
+        const double* zA = Z + (size_t)(2 * f) * R;
+        const double sc = a.scale;
+        tdm_dft2(a, tx, ty, T, zA, zA + R, 1, [&](int q, double re, double im) { o[2 * q] = sc * re; o[2 * q + 1] = sc * im; });
+    }
+}
+bool launch_hubbard_td_matsubara(const Launch& lc, const DevModel& hm, const double* acc, int nfreq, double* out, double* bad) {
+    const int L = hm.L, N = hm.N, m = hm.m;
+    const size_t budget = 152 * 1024;
+    int ftile = nfreq < TDM_FT ? nfreq : TDM_FT;
+    while (ftile >= 1 && measure_td_matsubara_lds_doubles(ftile, m, L, L, N) * sizeof(double) > budget) --ftile;
+    if (ftile < 1) return false;
+    const size_t lds = measure_td_matsubara_lds_doubles(ftile, m, L, L, N) * sizeof(double);
+    if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)k_hubbard_td_matsubara, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        (void)hipGetLastError();                            // the launch below then reports the problem
+    TdmShape a{0, HUB_EQ_CH, nfreq, ftile, m, L, N, L, L | 1, N, HUB_EQ_CH * N, 0, 0, hm.dtau / (double)N, (size_t)HUB_EQ_CH * nfreq * N * 2};
+    hipLaunchKernelGGL(k_hubbard_td_matsubara, dim3((nfreq + ftile - 1) / ftile, HUB_EQ_CH, lc.nb), dim3(256), lds, lc.st, acc, out, bad, a, lc.cs);
+    return true;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------

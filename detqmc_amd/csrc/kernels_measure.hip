@@ -2074,44 +2074,10 @@ void launch_td_ends(const Launch& lc, const cplx* G, cplx* a_t0, cplx* a_0t, cpl
 // G = Re F(A) + i Re F(B) with the phases e^{+i k (d - (L-1))}, k = -pi + (kk + 1/2 on antiperiodic directions) 2 pi / L, of the host's
 // greenKTau sum: two transforms, each writes its half of the output element.  One writer per output element, fixed summation order
 // (k, then y, then x ascending), no atomics.  bad[chain] = 1 if a row of the chain has a count < 1 (written by workgroup (0, 0) alone).
-#define TDM_FT 8
-struct TdmShape { int channel, ncomp, nfreq, ftile, m, L, N, W, WP, rlen, stride, apbx, apby; double scale; size_t ocs; };   // ocs: chain stride of out (doubles)
-
+// TDM_FT, TdmShape and the separable transform tdm_dft2: dqmc_internal.h (k_hubbard_td_matsubara shares them)
 size_t measure_td_matsubara_lds_doubles(int ftile, int m, int L, int W, int rlen) {
     const int WP = W | 1;
     return (size_t)ftile * (m + 1) * 2 + 2 * (size_t)(2 * L * WP) + (size_t)2 * L * W + (size_t)ftile * 2 * rlen;
-}
-
-// T[ky][ix] = sum_iy ty[ky][iy] U[iy][ix], then emit(ky L + kx, sum_ix tx[kx][ix] T[ky][ix]); U = (ur, ui)[(iy W + ix) str]
-template<class Emit>
-__device__ __forceinline__ void tdm_dft2(const TdmShape& a, const double* tx, const double* ty, double* T, const double* ur, const double* ui,
-                                         int str, Emit emit) {
-    const int L = a.L, W = a.W, WP = a.WP;
-    for (int i = threadIdx.x; i < L * W; i += 256) {
-        const int ky = i / W, ix = i - ky * W;
-        const double* t = ty + (size_t)2 * ky * WP;
-        double re = 0.0, im = 0.0;
-        for (int iy = 0; iy < W; ++iy) {
-            const double c = t[2 * iy], s = t[2 * iy + 1], xr = ur[(size_t)(iy * W + ix) * str], xi = ui[(size_t)(iy * W + ix) * str];
-            re += c * xr - s * xi;
-            im += c * xi + s * xr;
-        }
-        T[2 * i] = re; T[2 * i + 1] = im;
-    }
-    __syncthreads();
-    for (int q = threadIdx.x; q < a.N; q += 256) {
-        const int ky = q / L, kx = q - ky * L;
-        const double* t = tx + (size_t)2 * kx * WP;
-        const double* v = T + (size_t)2 * ky * W;
-        double re = 0.0, im = 0.0;
-        for (int ix = 0; ix < W; ++ix) {
-            const double c = t[2 * ix], s = t[2 * ix + 1];
-            re += c * v[2 * ix] - s * v[2 * ix + 1];
-            im += c * v[2 * ix + 1] + s * v[2 * ix];
-        }
-        emit(q, re, im);
-    }
-    __syncthreads();                                        // T is free again
 }
 
 __global__ __launch_bounds__(256) void k_td_matsubara(const double* __restrict__ acc, double* __restrict__ out, double* __restrict__ bad,

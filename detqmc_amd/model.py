@@ -687,6 +687,26 @@ class KernelContext:
         right after the advance that ended on boundary j, with set_timedisplaced on)"""
         check(self.lib.dqmc_hubbard_measure_timedisplaced(self.h, j))
 
+    def hubbard_measure_timedisplaced_segment(self, j):
+        """Hubbard model, context with DQMC_TD_HUB_EVERY_SLICE: all eight channels on every slice of boundary j's segment into the every-slice
+        block, by propagation from the boundary's matrices (right after the advance that ended on boundary j)"""
+        check(self.lib.dqmc_hubbard_measure_timedisplaced_segment(self.h, j))
+
+    def hubbard_measure_timedisplaced_ends(self):
+        """Hubbard model: rows 0 and m of the every-slice block from G = G(0) (the context must stand at time slice 0 or m)"""
+        check(self.lib.dqmc_hubbard_measure_timedisplaced_ends(self.h))
+
+    def hubbard_td_fine_read(self):
+        """count[m+1], then [m+1][8][N] raw sums of the selected chain, the channel order of hubbard_eq_read"""
+        return self._read_block(self.lib.dqmc_hubbard_td_fine_accum_size, self.lib.dqmc_hubbard_td_fine_read_host)
+
+    def hubbard_td_matsubara(self, nfreq):
+        """Matsubara transforms of the every-slice block, every chain and channel: complex (nchains, 8, nfreq, N); channels 0, 1 at the
+        fermionic frequencies, 2 .. 7 at the bosonic ones"""
+        out = np.zeros(self.lib.dqmc_hubbard_td_matsubara_size(self.h, nfreq))
+        check(self.lib.dqmc_hubbard_td_matsubara_host(self.h, nfreq, out.ctypes.data_as(_lib._DP)))
+        return out.view(np.complex128).reshape(self.nchains_total(), 8, nfreq, self.N)
+
     def hubbard_td_read(self):
         """count[n-1], then per boundary [greenUp, greenDn, charge, spinZZ, spinXX, pairS][N], raw sums"""
         return self._read_block(self.lib.dqmc_hubbard_td_accum_size, self.lib.dqmc_hubbard_td_read_host)
@@ -1928,12 +1948,16 @@ class HubbardParams:
     stabilisation: str = "svd"
     equalTimeCorrelators: bool = False        # measurement sweeps also bin the '...Corr' observables on every time slice
     timeDisplacedCorrelators: bool = False    # ... and the '...Tau' observables at the interior boundaries tau_j = j s dtau
+    timeDisplacedEverySlice: bool = False     # ... and the '...TauFine' observables on every time slice tau_k = k dtau, k = 0 .. m (needs the line above)
 
 
 # DetHubbard.observable_vector: row of the equal-time block (N,) / of every boundary's rows of the time-displaced block (n-1, N)
 HUBBARD_EQ_CORRELATORS = {"greenUpCorr": 0, "greenDnCorr": 1, "chargeCorr": 2, "spinZZCorr": 3, "spinXXCorr": 4, "pairSCorr": 5,
                           "pairSxCorr": 6, "pairDCorr": 7}
 HUBBARD_TD_CORRELATORS = {"greenUpTau": 0, "greenDnTau": 1, "chargeTau": 2, "spinZZTau": 3, "spinXXTau": 4, "pairSTau": 5}
+# '...TauFine': all eight channels on every time slice (m+1, N); their Matsubara transforms go by the '...Tau' name
+HUBBARD_TD_FINE_CORRELATORS = {n[:-4] + "TauFine": x for n, x in HUBBARD_EQ_CORRELATORS.items()}
+HUBBARD_MATSUBARA = {n[:-4] + "Tau": x for n, x in HUBBARD_EQ_CORRELATORS.items()}
 HUBBARD_SCALARS = ("occUp", "occDn", "occTotal", "occDouble", "localMoment", "eKinetic", "ePotential", "eTotal")
 # DetHubbard.series_*: name -> observable index of dethubbard_series_* ('...Sq' = S_X(q) of '...Corr', '...TauSq' of '...Tau')
 HUBBARD_SERIES_OBS = {"scalars": _lib.DETHUBBARD_OBS_SCALARS, "zcorr": _lib.DETHUBBARD_OBS_ZCORR}
@@ -1953,7 +1977,8 @@ HUBBARD_Q_PI_PI = ("charge", "spinZZ", "spinXX", "spin")
 
 def _hubbard_host_params(pars: HubbardParams):
     """the dethubbard_params that DetHubbard hands to dethubbard_create"""
-    flags = (_lib.DETHUBBARD_MEASURE_EQ if pars.equalTimeCorrelators else 0) | (_lib.DETHUBBARD_MEASURE_TD if pars.timeDisplacedCorrelators else 0)
+    flags = ((_lib.DETHUBBARD_MEASURE_EQ if pars.equalTimeCorrelators else 0) | (_lib.DETHUBBARD_MEASURE_TD if pars.timeDisplacedCorrelators else 0)
+             | (_lib.DETHUBBARD_MEASURE_TD_FINE if pars.timeDisplacedEverySlice else 0))
     return _lib.dethubbard_params(L=pars.L, d=pars.d, m=pars.m, s=pars.s, checkerboard=int(pars.checkerboard), device=pars.device,
                                   simindex=pars.simindex, rngSeed=pars.rngSeed, stabilisation=STABILISATION[pars.stabilisation],
                                   measureFlags=flags, beta=pars.beta, dtau=pars.dtau, t=pars.t, U=pars.U, mu=pars.mu)
@@ -2039,7 +2064,9 @@ class DetHubbard(_GreenCheck):
         HubbardParams.equalTimeCorrelators: 'greenUpCorr', 'greenDnCorr', 'chargeCorr', 'spinZZCorr', 'spinXXCorr', 'pairSCorr', 'pairSxCorr',
         'pairDCorr', shape (N,), averaged over the m time slices.  HubbardParams.timeDisplacedCorrelators: 'greenUpTau', 'greenDnTau',
         'chargeTau', 'spinZZTau', 'spinXXTau', 'pairSTau', shape (n-1, N), rows = tau_grid().  structure_factor(c, L) turns either into
-        S(q) (e.g. the antiferromagnetic S(pi, pi) from 'spinZZCorr', n(k) from 'greenUpCorr')."""
+        S(q) (e.g. the antiferromagnetic S(pi, pi) from 'spinZZCorr', n(k) from 'greenUpCorr').  HubbardParams.timeDisplacedEverySlice:
+        'greenUpTauFine', 'greenDnTauFine', 'chargeTauFine', 'spinZZTauFine', 'spinXXTauFine', 'pairSTauFine', 'pairSxTauFine', 'pairDTauFine',
+        shape (m+1, N), rows = tau_grid(fine=True)."""
         i = self.info
         if name in HUBBARD_EQ_CORRELATORS:
             out = np.zeros((8, i.N))
@@ -2049,12 +2076,41 @@ class DetHubbard(_GreenCheck):
             out = np.zeros((i.n - 1, 6, i.N))
             check(self.lib.dethubbard_get_td_correlators(self.h, out.ctypes.data_as(_lib._DP)), host="hubbard")
             return out[:, HUBBARD_TD_CORRELATORS[name], :].copy()
+        if name in HUBBARD_TD_FINE_CORRELATORS:
+            out = np.zeros((i.m + 1, 8, i.N))
+            check(self.lib.dethubbard_get_td_fine_correlators(self.h, out.ctypes.data_as(_lib._DP)), host="hubbard")
+            return out[:, HUBBARD_TD_FINE_CORRELATORS[name], :].copy()
         raise KeyError(name)
 
-    def tau_grid(self):
-        """tau_j = j s dtau, j = 1 .. n-1: the rows of the '...Tau' observables"""
+    def tau_grid(self, fine=False):
+        """tau_j = j s dtau, j = 1 .. n-1: the rows of the '...Tau' observables; fine=True: tau_k = k dtau, k = 0 .. m, the rows of '...TauFine'"""
         i = self.info
+        if fine:
+            return np.arange(i.m + 1) * i.dtau
         return np.arange(1, i.n) * (i.s * i.dtau)
+
+    def matsubara(self, name, nfreq):
+        """Matsubara transform of the every-slice rows of the last measurement sweep, selected chain, complex (nfreq, N), column qy L + qx
+        (HubbardParams.timeDisplacedEverySlice; trapezoid rule over tau_grid(fine=True)).  'chargeTau', 'spinZZTau', 'spinXXTau', 'pairSTau',
+        'pairSxTau', 'pairDTau': chi_X(q, i omega_n) at the bosonic frequencies -- the spin susceptibility chi_s(pi, pi; 0) is
+        matsubara('spinZZTau', 1)[0, (L // 2) * L + L // 2], the pair susceptibilities P_s, P_d(q = 0; 0) are column 0 of 'pairSxTau' /
+        'pairDTau'; 'greenUpTau', 'greenDnTau': G_s(k, i omega_n) at the fermionic ones.  Valid until the next sweep of either kind"""
+        at = HUBBARD_MATSUBARA[name]
+        out = np.zeros((8, int(nfreq), self.info.N), dtype=np.complex128)
+        check(self.lib.dethubbard_get_matsubara(self.h, int(nfreq), out.ctypes.data_as(_lib._DP)), host="hubbard")
+        return out[at].copy()
+
+    def matsubara_all(self, name, nfreq):
+        """matsubara of every chain, complex (nchains, nfreq, N); one device call"""
+        at = HUBBARD_MATSUBARA[name]
+        out = np.zeros((self.nchains, 8, int(nfreq), self.info.N), dtype=np.complex128)
+        check(self.lib.dethubbard_get_matsubara_all(self.h, int(nfreq), out.ctypes.data_as(_lib._DP)), host="hubbard")
+        return out[:, at].copy()
+
+    def matsubara_frequencies(self, nfreq, fermionic=False):
+        """omega_n, n = 0 .. nfreq-1: 2 pi n / beta, or (2n+1) pi / beta with fermionic=True"""
+        n = np.arange(int(nfreq))
+        return (2 * n + 1) * np.pi / self.info.beta if fermionic else 2 * n * np.pi / self.info.beta
 
     def rand01(self):
         return self.lib.dethubbard_rng_rand01(self.h)

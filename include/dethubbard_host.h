@@ -30,7 +30,7 @@ typedef struct dethubbard_params {
     int32_t simindex;
     uint32_t rngSeed;
     int32_t stabilisation;       /* DQMC_STAB_SVD (as the reference) or DQMC_STAB_QR */
-    int32_t measureFlags;        /* DETHUBBARD_MEASURE_* bits; 0: the eight scalars and zcorr only.  Any other bit: ParameterWrong */
+    int32_t measureFlags;        /* DETHUBBARD_MEASURE_* bits; 0: the eight scalars and zcorr only.  Any other bit, _TD_FINE without _TD: ParameterWrong */
     double beta, dtau;
     double t, U, mu;
 } dethubbard_params;
@@ -39,8 +39,11 @@ typedef struct dethubbard_params {
  * _EQ: a measurement sweep also bins the equal-time correlators of dqmc_hubbard_set_equal_time_correlators on all m slices.
  * _TD: the kernel context is created with the time-displaced reservation, and a measurement sweep computes G(tau_j,0), G(0,tau_j),
  *      G(0) at every interior boundary j = 1 .. n-1 of its direction and bins dqmc_hubbard_measure_timedisplaced(j) there.
- * Neither changes the Markov chain, the eight scalars or zcorr; thermalisation sweeps launch nothing new. */
-enum { DETHUBBARD_MEASURE_EQ = 1, DETHUBBARD_MEASURE_TD = 2 };
+ * _TD_FINE (needs _TD, and s < m as given; ParameterWrong otherwise): the kernel context also gets the every-slice reservation
+ *      (DQMC_TD_HUB_EVERY_SLICE), and a measurement sweep bins all eight channels on the grid tau_k = k dtau, k = 0 .. m: after
+ *      dqmc_hubbard_measure_timedisplaced(j) the segment of boundary j, after the closing advance rows 0 and m.
+ * None changes the Markov chain, the eight scalars, zcorr or the blocks of the other flags; thermalisation sweeps launch nothing new. */
+enum { DETHUBBARD_MEASURE_EQ = 1, DETHUBBARD_MEASURE_TD = 2, DETHUBBARD_MEASURE_TD_FINE = 4 };
 
 /* obsScalar of DetHubbard (src/dethubbard.cpp:85-93), valid after dethubbard_sweep(r, 1) */
 typedef struct dethubbard_observables {
@@ -75,6 +78,14 @@ int dethubbard_get_zcorr(dethubbard_replica* r, double* out /* [N] */);
  * open (below).  Values of ONE sweep; averages and error bars over sweeps: the measurement series at the end of this header. */
 int dethubbard_get_eq_correlators(dethubbard_replica* r, double* out /* [8][N] */);
 int dethubbard_get_td_correlators(dethubbard_replica* r, double* out /* [n-1][6][N] */);
+/* DETHUBBARD_MEASURE_TD_FINE: all eight channels on every time slice, C_X(d, tau_k) = sum / (count N), k = 0 .. m, selected chain; refused
+ * like the two getters above.  dethubbard_get_matsubara / _all: chi_X(q, i omega_n) (channels 2 .. 7, omega_n = 2 pi n / beta) and
+ * G_s(k, i omega_n) (channels 0, 1, omega_n = (2n+1) pi / beta) of dqmc_hubbard_td_matsubara_host, n = 0 .. nfreq-1, 1 <= nfreq <= m, complex
+ * as (re, im), column qy L + qx; of the selected chain / of every chain.  They read the block on the device: valid after a measurement sweep
+ * until the next sweep of either kind (DQMC_EINVAL outside that window), also while a series with DETHUBBARD_SERIES_NO_HOST_COPY is open. */
+int dethubbard_get_td_fine_correlators(dethubbard_replica* r, double* out /* [m+1][8][N] */);
+int dethubbard_get_matsubara(dethubbard_replica* r, int nfreq, double* out /* [8][nfreq][N] complex */);
+int dethubbard_get_matsubara_all(dethubbard_replica* r, int nfreq, double* out /* [nchains][8][nfreq][N] complex */);
 /* Checkpoint / resume (what DetQMC::saveState keeps for the replica: auxfield, src/dethubbard.h:352-358, plus the position of
  * the random stream); dethubbard_load_state needs a replica created with the same parameters and rebuilds UdV storage and G(beta)
  * like the reference's loadContents does (src/dethubbard.h:345-350) */

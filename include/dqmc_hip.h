@@ -53,6 +53,9 @@ enum { DQMC_MODEL_SDW = 0, DQMC_MODEL_HUBBARD = 1 };
 /* flag bit of dqmc_params::timedisplaced (the low bits keep their values 0 / 1 / 2): also reserve what the every-slice entries
  * dqmc_measure_timedisplaced_segment / _ends need */
 enum { DQMC_TD_EVERY_SLICE = 0x100 };
+/* flag bit of dqmc_params::timedisplaced, DQMC_MODEL_HUBBARD only: also reserve what the every-slice entries of the Hubbard model
+ * dqmc_hubbard_measure_timedisplaced_segment / _ends need (three work matrices and one block of m + 1 rows, behind every other buffer) */
+enum { DQMC_TD_HUB_EVERY_SLICE = 0x400 };
 /* flag bit of dqmc_params::td_particle_hole (the low bits keep their values 0 / 1 / 2): also reserve what the band-resolved charge
  * channels bandDiff / bandMix need (dqmc_measure_timedisplaced_band below) */
 enum { DQMC_TD_PH_BAND = 0x100 };
@@ -121,7 +124,11 @@ typedef struct dqmc_params {
                               matrices and one every-slice accumulator block per enabled channel (the struct has no free slot: the
                               option travels as a flag bit).  Any other value, any other bit: DQMC_EINVAL.  DQMC_MODEL_HUBBARD accepts
                               timedisplaced = 1 together with td_particle_hole = 1 and nothing else: the matrices of G(tau,0), G(0,tau),
-                              G(0), one scratch matrix and the block of dqmc_hubbard_measure_timedisplaced, behind every other buffer */
+                              G(0), one scratch matrix and the block of dqmc_hubbard_measure_timedisplaced, behind every other buffer;
+                              1 | DQMC_TD_HUB_EVERY_SLICE with td_particle_hole = 1 (needs s < m, i.e. n >= 2): the same with the same
+                              layout, launches and results, and behind it three work matrices and the every-slice block of
+                              dqmc_hubbard_measure_timedisplaced_segment / _ends.  The SDW model refuses DQMC_TD_HUB_EVERY_SLICE, the
+                              Hubbard model DQMC_TD_EVERY_SLICE */
     dqmc_tuning tuning;   /* all zero = automatic */
     int32_t td_particle_hole; /* 1 (needs timedisplaced >= 1, SDW model; DQMC_EINVAL otherwise): also reserve, behind every other buffer,
                                  the equal-time G(0) of the boundary's own field configuration, one matrix for a shifted copy, the
@@ -444,6 +451,30 @@ int dqmc_hubbard_eq_read_host(dqmc_ctx* ctx, double* out);   /* selected chain *
 int dqmc_hubbard_measure_timedisplaced(dqmc_ctx* ctx, int j);
 size_t dqmc_hubbard_td_accum_size(dqmc_ctx* ctx);       /* 0 without the reservation */
 int dqmc_hubbard_td_read_host(dqmc_ctx* ctx, double* out);   /* selected chain */
+/* Every time slice, tau_k = k dtau, k = 0 .. m -- context created with timedisplaced = 1 | DQMC_TD_HUB_EVERY_SLICE and td_particle_hole = 1
+ * (DESIGN.md 24).  The propagation identities, preconditions and slice bookkeeping are those of dqmc_measure_timedisplaced_segment / _ends
+ * below (the same work copies, the same B-multiplies: G, the boundary pair and G(0) come out bit-identical):
+ * dqmc_hubbard_measure_timedisplaced_segment(ctx, j) bins rows k = j s .. min((j+1) s, m) - 1 and, for j = 1, k = s-1 .. 1;
+ * dqmc_hubbard_measure_timedisplaced_ends(ctx), at time slice 0 or m, rows 0 and m from G(0+,0) = G, G(0,0+) = G - 1, G(beta-,0) = 1 - G,
+ * G(0,beta-) = -G with G(tau) = G(0) = G.  Block of one chain (dqmc_hubbard_td_fine_accum_size = (m+1)(1 + 8 N) doubles, 0 without the
+ * reservation; inside the arena, cleared by dqmc_measure_reset): count[m+1], then [m+1][8][N] raw sums in the channel order of the
+ * equal-time block.  Channels 0 .. 5: the forms of dqmc_hubbard_measure_timedisplaced (row j s has the bits of coarse row j); channels 6, 7:
+ * <Delta^f_A(tau) Delta^f+_B(0)> = 1/4 G(tau,0)_up(A,B) sum_{dl,dl'} f_dl f_dl' G(tau,0)_dn(A+dl, B+dl').  Two launches per row, all chains;
+ * one writer per accumulator, fixed summation order.
+ * Matsubara transforms of the block, all chains and all eight channels in ONE launch (k_hubbard_td_matsubara): with C_X(d, tau_k) =
+ * row k / (count_k N), w_0 = w_m = 1/2 (1 otherwise), n = 0 .. nfreq-1, q = (2 pi / L)(qx, qy), column qy L + qx,
+ *   channels 2 .. 7 (bosonic, omega_n = 2 pi n / beta):        chi_X(q, i omega_n) = dtau sum_k w_k e^{i omega_n tau_k} sum_d e^{-i q d} C_X(d, tau_k)
+ *   channels 0, 1 (fermionic, omega_n = (2n+1) pi / beta):     G_s(k, i omega_n)   = dtau sum_k w_k e^{i omega_n tau_k} sum_d e^{-i k d} G_s(d, tau_k)
+ * out: [chain][8][nfreq][N] complex as (re, im), dqmc_hubbard_td_matsubara_size doubles (0 for arguments the call rejects).  DQMC_EINVAL,
+ * with nothing written to out: nfreq outside 1 .. m, a row of any chain with a sample count < 1, a lattice beyond the kernel's LDS.  Reads
+ * the block only; two calls give identical bits.  Every entry: DQMC_EINVAL on an SDW context or without the reservation. */
+int dqmc_hubbard_measure_timedisplaced_segment(dqmc_ctx* ctx, int j);
+int dqmc_hubbard_measure_timedisplaced_ends(dqmc_ctx* ctx);
+size_t dqmc_hubbard_td_fine_accum_size(dqmc_ctx* ctx);  /* 0 without the reservation */
+int dqmc_hubbard_td_fine_read_host(dqmc_ctx* ctx, double* out);   /* selected chain */
+int dqmc_hubbard_td_fine_counts_host(dqmc_ctx* ctx, double* out);   /* selected chain: the m + 1 sample counts alone, the block's prefix */
+size_t dqmc_hubbard_td_matsubara_size(dqmc_ctx* ctx, int nfreq);
+int dqmc_hubbard_td_matsubara_host(dqmc_ctx* ctx, int nfreq, double* out);
 /* ---- time-displaced Green's functions ----------------------------------------------------------
  * At an interior stabilisation boundary tau_j = j s (j = 1 .. n-1) the advance holds B(tau,0) = U_r D_r V_r^H and
  * B(beta,tau) = U_l D_l V_l^H at once.  With the scales split into their parts > 1 and <= 1 and
@@ -675,7 +706,9 @@ int dqmc_get_green0_timedisplaced_host(dqmc_ctx* ctx, dqmc_cplx* g00, int* slice
  * (row stride 2 R^2 N, present while dqmc_set_green_matrix is on); a channel has a
  * block if its coarse block is reserved.  Layout (doubles, dqmc_measure_td_fine_accum_size of them, 0 without the block): count[m+1], then row k = 0 .. m
  * at offset (m+1) + k stride, stride and contents of a row as in the coarse block: 4 (2L-1)^2, 2N, 3N, 2N + 2.
- * dqmc_measure_reset clears them as well. */
+ * dqmc_measure_reset clears them as well.  A Hubbard context returns DQMC_EINVAL from the segment, ends and Matsubara entries (its own:
+ * dqmc_hubbard_measure_timedisplaced_segment / _ends, dqmc_hubbard_td_matsubara_host); with DQMC_TD_HUB_EVERY_SLICE the size / read pair
+ * serves its one block as channel 0. */
 int dqmc_measure_timedisplaced_segment(dqmc_ctx* ctx, int j);
 int dqmc_measure_timedisplaced_ends(dqmc_ctx* ctx);
 size_t dqmc_measure_td_fine_accum_size(dqmc_ctx* ctx, int channel);
